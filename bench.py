@@ -12,6 +12,10 @@ when step k starts; the pinned host -> device copy of batch k + 1 (copy stream) 
 INSIDE the timed region (`audio_resident` is the same loop with the uploads left out).
 Rank 0 prints ONE JSON line. Random-init weights of the exact architecture, synthetic int16-range audio
 (no checkpoints / datasets exist offline).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the LAST timed step returned to its caller -- the token
+ids and their counts of every utterance of the (global) batch -- as DIR/token_ids.npy [batch, max_T] and
+DIR/num_ids.npy [batch], float64 (exact for ids). Seeded weights and audio: the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -32,6 +36,7 @@ PKG = "automatic-speech-recognition-asr-onnx_amd"
 
 MFMA_BF16_PEAK_TFLOPS = 2500.0      # dense bf16 MFMA, MI355X_MICROARCH.md:42
 HBM_PEAK_GBS = 8000.0               # HBM3E spec, MI355X_MICROARCH.md:35
+DUMP_LIMIT_BYTES = 64 << 20         # --dump-outputs: bound on everything one run writes
 
 
 def sensevoice_algorithmic_flops(cfg, lengths, blocks=None):
@@ -240,6 +245,17 @@ def cpu_leg_main(n_thr):
     print(json.dumps({"value": round(k * 8.0 / el, 2), "sample": f"{k} x 8 s utterances, {el:.1f} s wall, first pass included"}))
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64, at most DUMP_LIMIT_BYTES in all."""
+    conv = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte bound")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch_command(n_gpus, argv, port=None):
     """The command `python bench.py --gpus N ...` re-executes itself as when no launcher set WORLD_SIZE: one rank per GPU under
     torch.distributed.run on this node, rendezvous on 127.0.0.1 (the container hostname may not resolve)."""
@@ -260,7 +276,7 @@ def dry_run(args):
     import torch
     import torch.distributed as dist
     dp = importlib.import_module(PKG + ".dist")
-    rank, local_rank, world = dp.init_from_env()
+    rank, local_rank, world = dp.init_from_env("gloo")       # gloo even where a GPU is visible: a 1-GPU host still runs N CPU ranks
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
     cpu = torch.device("cpu")
     B = args.batch or (32 if args.workload == "whisper" else 64)
@@ -315,8 +331,14 @@ def main():
     ap.add_argument("--mxfp4", action="store_true", help="whisper / qwen: opt-in precision mode ASR_PRECISION_MXFP4W (decoder projections as OCP MXFP4; Whisper: cross-K/V as e4m3); a secondary figure, never the headline")
     ap.add_argument("--fp8", action="store_true", help="whisper / qwen: opt-in precision mode ASR_PRECISION_FP8W (decoder projections -- Whisper: and cross-K/V -- as e4m3 bytes); a secondary figure, never the headline")
     ap.add_argument("--decode-tokens", type=int, default=0, help="whisper: generated tokens per utterance (default 4 per audio second)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="sensevoice: write the last timed step's token ids / counts as DIR/<name>.npy (float64) after the timed steps")
     ap.add_argument("--cpu-leg", type=int, default=0, help=argparse.SUPPRESS)        # child process of the CPU baseline's every-core leg
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "sensevoice":
+        ap.error("--dump-outputs is implemented for the sensevoice workload only")
     if args.cpu_leg:
         return cpu_leg_main(args.cpu_leg)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # started by hand: become the launcher the contract describes
@@ -393,9 +415,10 @@ def main():
         tok, num = sess.run_packed(None, offsets, lang, audio_device_ptr=audio_dev[k & 1].data_ptr())
         if upload:
             copy_done.synchronize()
+        slabs = None
         if world > 1:                                      # hypotheses to rank 0 (latency-bound, < 120 KB per rank)
-            dp.gather_hypotheses(dp.pack_hypotheses(tok, num, max_t), device)
-        return tok, num
+            slabs = dp.gather_hypotheses(dp.pack_hypotheses(tok, num, max_t), device)
+        return tok, num, slabs
 
     def fence():
         if world > 1:
@@ -403,22 +426,27 @@ def main():
         torch.cuda.synchronize()
 
     def timed(n_steps, upload):
+        """(slowest rank's seconds for n_steps steps, the last step's result)"""
         fence()
         t0 = time.perf_counter()
         for k in range(n_steps):
-            step(k, upload)
+            last = step(k, upload)
         fence()
         el = time.perf_counter() - t0
-        return dp.max_over_ranks(el, device)
+        return dp.max_over_ranks(el, device), last
 
     for k in range(args.warmup):
         step(k)
-    elapsed = timed(args.steps, True)                      # the headline: EXACTLY --steps steps, uploads inside
-    tok, num = step(0, False)
-    elapsed_resident = timed(args.steps, False)            # same steps with the audio left in HBM (what round 1 reported as `value`)
+    elapsed, last = timed(args.steps, True)                # the headline: EXACTLY --steps steps, uploads inside
+    if args.dump_outputs and rank == 0:
+        tok, num, slabs = last
+        hyp = np.concatenate(slabs) if slabs else dp.pack_hypotheses(tok, num, max_t)      # [global batch, 1 + max_t]: count, ids
+        dump_outputs(args.dump_outputs, {"token_ids": hyp[:, 1:], "num_ids": hyp[:, 0]})
+    step(0, False)
+    elapsed_resident, _ = timed(args.steps, False)         # same steps with the audio left in HBM (what round 1 reported as `value`)
     steady = None
     if args.steps < 200 and not args.no_extras:            # a short --steps run is noisy (20 x 8 ms = 0.17 s): also time 200 steps
-        steady = timed(200, True)
+        steady, _ = timed(200, True)
 
     # ---- roofline leg: per-kernel-class HIP-event timing on the session stream (separate profiled steps)
     sess.profile(True)

@@ -25,6 +25,7 @@ SENSEVOICE_CASES = [
     # (fixture, config factory, ckpt seed, [(audio seed, n_samples, language_idx)])
     ("sensevoice_tiny", "sensevoice_tiny", 0, [(1234, 38880, 2), (1235, 128000, 0), (1236, 400, 6), (1237, 5999, 3)]),
     ("sensevoice_small", "sensevoice_small", 0, [(1234, 128000, 2), (1238, 38880, 1)]),
+    ("sensevoice_tiny_live", "sensevoice_tiny", 0, [(11, 16000, 4), (12, 801, 5)]),      # tests/test_oracle_sensevoice.py::test_oracle_matches_reference_live
 ]
 
 

@@ -3,6 +3,11 @@ counter passes, kernel-trace stats) -- and the committed bench lines keep the co
 import glob
 import json
 import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
 
 import bench
 
@@ -56,3 +61,22 @@ def test_block_kernel_numerator_is_a_known_answer():
     block0 = bench.sensevoice_algorithmic_flops(cfg, lengths, blocks=(0, cfg.n_enc0))
     for k in per_class:
         assert abs(walked[k] + block0[k] - whole[k]) < 1e-3 * whole[k]
+
+
+def test_dump_outputs_writes_float64_npy_files_within_the_bound(tmp_path):
+    tok = np.arange(64 * 137, dtype=np.int32).reshape(64, 137)
+    num = np.full(64, 137, np.int32)
+    bench.dump_outputs(str(tmp_path / "d"), {"token_ids": tok, "num_ids": num})
+    for name, want in (("token_ids", tok), ("num_ids", num)):
+        got = np.load(tmp_path / "d" / (name + ".npy"))
+        assert got.dtype == np.float64 and got.shape == want.shape and np.array_equal(got, want)
+    with pytest.raises(ValueError, match="exceed"):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1, np.float32)})
+    assert not os.path.exists(tmp_path / "big")
+
+
+@pytest.mark.parametrize("argv,msg", [(["--steps", "0"], "--steps must be at least 1"),
+                                      (["--workload", "whisper", "--dump-outputs", "d"], "--dump-outputs is implemented for the sensevoice workload only")])
+def test_bench_rejects_arguments_it_cannot_honour(argv, msg):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and msg in r.stderr

@@ -1,15 +1,12 @@
 """CPU: the onnxruntime-API shim's host logic and the ORT_IO restatement (no compute calls)."""
-import importlib.util
+import builtins
 import json
-import os
 
 import numpy as np
 import pytest
 
 from conftest import sub
-from helpers import sensevoice_setup
-
-REF_ORT_IO = "/root/reference/ORT_IO.py"
+from helpers import load_golden, sensevoice_setup
 
 
 class _Meta:
@@ -45,32 +42,25 @@ def test_ort_io_contract():
     assert io.load_special_token_ids(meta) == {"eos": [1, 2]}
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_ORT_IO), reason="reference only mounted in the build container")
 def test_ort_io_matches_reference_module():
-    spec = importlib.util.spec_from_file_location("ref_ort_io", REF_ORT_IO)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    """The reference ORT_IO's outputs (or exception types) over the case grid of oracle/gen_golden_host.py, stored as data."""
+    from oracle.gen_golden_host import ORT_IO_METAS, SCALAR_VALUE, ort_io_cases
+    g = load_golden("ort_io_reference")
     io = sub("ort_io")
-    rng = np.random.default_rng(0)
-    metas = [_Meta("a", [1, 1, "L"], "tensor(float)"), _Meta("b", ["batch", 20, 64, "hist"], "tensor(float16)"),
-             _Meta("c", [1], "tensor(int64)"), _Meta("d", [], "tensor(int32)")]
-    for m in metas:
-        for axes in (None, {0: 2}, {0: 1, 1: 1, 2: 4, 3: 0}):
-            for val in (rng.standard_normal(4), np.zeros((2, 20, 64, 3)), 5):
-                got = want = None
-                try:
-                    want = ref.array_for(m, val, axes=axes)
-                except Exception as e:
-                    want = type(e)
-                try:
-                    got = io.array_for(m, val, axes=axes)
-                except Exception as e:
-                    got = type(e)
-                if isinstance(want, type):
-                    assert got is want, (m.name, axes, np.shape(val), got, want)
-                else:
-                    assert got.dtype == want.dtype and got.shape == want.shape and np.array_equal(got, want)
-        assert np.array_equal(io.scalar_for(m, 3), ref.scalar_for(m, 3))
+    for i, (m, axes, val) in enumerate(ort_io_cases()):
+        want = getattr(builtins, str(g[f"array_{i}_raises"])) if f"array_{i}_raises" in g else g[f"array_{i}"]
+        try:
+            got = io.array_for(m, val, axes=axes)
+        except Exception as e:
+            got = type(e)
+        if isinstance(want, type):
+            assert got is want, (m.name, axes, np.shape(val), got, want)
+        else:
+            assert got.dtype == want.dtype and got.shape == want.shape and np.array_equal(got, want)
+    for j, m in enumerate(ORT_IO_METAS):
+        want = g[f"scalar_{j}"]
+        got = io.scalar_for(m, SCALAR_VALUE)
+        assert got.dtype == want.dtype and np.array_equal(got, want)
 
 
 def test_model_bundle_and_metadata_session(tmp_path):

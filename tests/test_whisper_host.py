@@ -1,15 +1,12 @@
 """Whisper host loop (probe -> language / no-speech -> prefill -> greedy decode): CPU pieces + GPU end-to-end vs the oracle."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import sub
+from helpers import load_golden
 from oracle.whisper_oracle import WhisperOracle
 from test_oracle_whisper import unit_audio, whisper_setup
-
-REF = "/root/reference/Whisper/Inference_Whisper_ONNX.py"
 
 
 def test_remove_repeated_parts_and_audio_prep_cpu():
@@ -24,18 +21,16 @@ def test_remove_repeated_parts_and_audio_prep_cpu():
     assert wh.prepare_audio_input(pcm, np.int16).dtype == np.int16
 
 
-@pytest.mark.skipif(not os.path.isfile(REF), reason="reference only mounted in the build container")
 def test_remove_repeated_parts_matches_reference_function():
-    import ast
-    src = open(REF).read()
-    fn = [n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == "remove_repeated_parts"][0]
-    ns = {}
-    exec(compile(ast.Module([fn], []), "ref", "exec"), ns)
+    """The reference function's outputs over the case grid of oracle/gen_golden_host.py, stored as data."""
+    from oracle.gen_golden_host import repeat_cases
+    g = load_golden("whisper_repeats_reference")
+    ends = np.cumsum(g["lengths"])
     wh = sub("whisper")
-    rng = np.random.default_rng(0)
-    for _ in range(200):
-        ids = rng.integers(0, 4, size=int(rng.integers(0, 14))).tolist()
-        assert list(wh.remove_repeated_parts(ids, 3, len(ids))) == list(ns["remove_repeated_parts"](ids, 3, len(ids)))
+    cases = list(repeat_cases())
+    assert len(cases) == g["lengths"].size
+    for (ids, thr, n), end, ln in zip(cases, ends, g["lengths"]):
+        assert list(wh.remove_repeated_parts(ids, thr, n)) == g["ids"][end - ln:end].tolist(), ids
 
 
 def test_no_speech_probability_matches_oracle_head_cpu():
