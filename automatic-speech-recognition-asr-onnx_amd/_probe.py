@@ -21,6 +21,15 @@ class GemmDesc(C.Structure):
                 ("kernel", C.c_char * 32)]
 
 
+class DecodeAttnDesc(C.Structure):
+    _fields_ = [("bf16", C.c_int32), ("cross", C.c_int32), ("B", C.c_int32), ("b0", C.c_int32), ("nb", C.c_int32), ("H", C.c_int32),
+                ("n", C.c_int32), ("causal", C.c_int32), ("q", _fp), ("ld_q", C.c_int32), ("q_col0", C.c_int32), ("max_keys", C.c_int32),
+                ("kv_new", _fp), ("k_hist", _fp), ("v_hist", _fp), ("hist", C.c_int32), ("hist_dev", C.c_int32), ("max_pos", C.c_int32),
+                ("paged", C.c_int32), ("n_pages", C.c_int32), ("pages_per_seq", C.c_int32), ("page_table", _ip), ("k_after", _fp), ("v_after", _fp),
+                ("k_slab", _fp), ("v_slab", _fp), ("rows", C.c_int32), ("row_off", _ip), ("n_lfr", _ip), ("fp8", C.c_int32),
+                ("kv8", C.c_void_p), ("scale8", _fp), ("out", _fp), ("stray", C.c_int32), ("kernel", C.c_char * 32)]
+
+
 SIGNATURES = {
     "asr_probe_gemm": (C.c_int, [C.POINTER(GemmDesc)]),
     "asr_probe_gemm_chain": (C.c_int, [C.c_int] * 6 + [_fp]),
@@ -29,6 +38,7 @@ SIGNATURES = {
     "asr_probe_quantize_mxfp4": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "asr_probe_decode_gemm_mxfp4": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _fp, C.c_int, _fp]),
     "asr_probe_decode_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _fp, _fp, C.c_int, _fp]),
+    "asr_probe_decode_attention": (C.c_int, [C.POINTER(DecodeAttnDesc)]),
     "asr_probe_gemm_counts": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "asr_probe_gemm_fp8": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _fp, C.c_float, _fp, _fp, C.c_int, C.c_void_p, _fp, C.c_int, _fp]),
     "asr_probe_gemm_bench": (C.c_int, [C.c_int] * 6 + [_fp]),
@@ -107,6 +117,64 @@ def gemm_chain(M, N, K, epilogue=0, cold_mb=768, replays=5):
     us = C.c_float(0.0)
     _lib.check(load().asr_probe_gemm_chain(M, N, K, epilogue, cold_mb, replays, C.byref(us)))
     return us.value, load().asr_probe_last_kernel().decode()
+
+
+def decode_attention(q, bf16=True, n=1, B=None, b0=0, nb=0, ld_q=None, q_col0=0, max_keys=0,
+                     kv_new=None, k_hist=None, v_hist=None, causal=True, hist_dev=False, max_pos=0, page_table=None, n_pages=0,
+                     k_slab=None, v_slab=None, row_off=None, n_lfr=None, fp8=False):
+    """One decoder attention call through launch_decode_attention (asr_mi355x_probe.h) on f32 host arrays (rounded to the element type on upload).
+
+    Self mode (kv_new given): q [B n][ld_q], kv_new [B n][2 H 64] (k, then v), k_hist / v_hist [B][H][hist][64], a contiguous cache of max_pos
+    positions or a paged one (page_table [B][pages_per_seq] over a pool of n_pages pages of 16 positions).
+    Cross mode (k_slab given): slabs [H][rows][64], sequence b at rows row_off[b] ... + n_lfr[b]; fp8 routes the slabs through the product quantiser.
+
+    Returns (out [B n][H 64], after, kernel): `after` is the self cache gathered to (k [B][H][hist + n][64], v [...], stray element count) or,
+    in FP8 cross mode, (bytes [2][H][rows][64] uint8, scales [2][H][B]); None otherwise."""
+    q = _f32(q)
+    d = DecodeAttnDesc()
+    cross = k_slab is not None
+    H = (k_slab.shape[0] if cross else kv_new.shape[1] // 128)
+    if B is None:
+        B = (len(n_lfr) if cross else k_hist.shape[0])
+    d.bf16, d.cross, d.B, d.b0, d.nb, d.H, d.n = int(bf16), int(cross), B, b0, nb, H, n
+    d.causal = int(causal and not cross)
+    d.ld_q, d.q_col0, d.max_keys = (ld_q or q.shape[1]), q_col0, max_keys
+    assert q.shape == (B * n, d.ld_q), q.shape
+    keep = [q]
+    d.q = q.ctypes.data_as(_fp)
+    out = np.zeros((B * n, H * 64), np.float32)
+    d.out = out.ctypes.data_as(_fp)
+    after = None
+    if not cross:
+        kv_new, k_hist, v_hist = _f32(kv_new), _f32(k_hist), _f32(v_hist)
+        hist = k_hist.shape[2]
+        assert kv_new.shape == (B * n, 2 * H * 64) and k_hist.shape == v_hist.shape == (B, H, hist, 64)
+        keep += [kv_new, k_hist, v_hist]
+        d.kv_new, d.k_hist, d.v_hist = kv_new.ctypes.data_as(_fp), k_hist.ctypes.data_as(_fp), v_hist.ctypes.data_as(_fp)
+        d.hist, d.hist_dev, d.max_pos = hist, int(hist_dev), max_pos
+        if page_table is not None:
+            pt = np.ascontiguousarray(page_table, np.int32)
+            keep.append(pt)
+            d.paged, d.n_pages, d.pages_per_seq, d.page_table = 1, n_pages, pt.shape[1], pt.ctypes.data_as(_ip)
+        ka = np.zeros((B, H, hist + n, 64), np.float32)
+        va = np.zeros_like(ka)
+        d.k_after, d.v_after = ka.ctypes.data_as(_fp), va.ctypes.data_as(_fp)
+    else:
+        k_slab, v_slab = _f32(k_slab), _f32(v_slab)
+        ro, nl = np.ascontiguousarray(row_off, np.int32), np.ascontiguousarray(n_lfr, np.int32)
+        assert k_slab.shape == v_slab.shape and k_slab.shape[2] == 64 and ro.shape == nl.shape == (B,)
+        keep += [k_slab, v_slab, ro, nl]
+        d.k_slab, d.v_slab, d.rows = k_slab.ctypes.data_as(_fp), v_slab.ctypes.data_as(_fp), k_slab.shape[1]
+        d.row_off, d.n_lfr, d.fp8 = ro.ctypes.data_as(_ip), nl.ctypes.data_as(_ip), int(fp8)
+        if fp8:
+            kv8 = np.zeros((2, H, k_slab.shape[1], 64), np.uint8)
+            sc8 = np.zeros((2, H, B), np.float32)
+            d.kv8, d.scale8 = kv8.ctypes.data, sc8.ctypes.data_as(_fp)
+            after = (kv8, sc8)
+    _lib.check(load().asr_probe_decode_attention(C.byref(d)))
+    if not cross:
+        after = (ka, va, d.stray)
+    return out, after, d.kernel.decode()
 
 
 def _bf16_bits(x):

@@ -98,6 +98,7 @@ void launch_quantize_crosskv_fp8(bf16_t* slabs, size_t slab_elems, int n_slabs, 
                                  int dq_in_place, hipStream_t s);
 template <typename T>
 void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s);
+const char* decode_attn_last_kernel();   // form of this thread's last launch_decode_attention ("self_wave", "cross_1pass[_fp8]", "general_n1[_fp8]", "general_n8[_fp8]"): test hook
 
 // ids[r] = first arg-max over n < n_valid of logits[r][n] + (extra ? extra[n] : 0)
 void launch_argmax_rows(const float* logits, int ld, int rows, int n_valid, const float* extra, int32_t* ids, hipStream_t s);

@@ -1738,6 +1738,9 @@ __global__ __launch_bounds__(256) void decode_self_attn_wave_kernel(const DecAtt
 
 }  // namespace
 
+static thread_local const char* g_decode_attn_kernel = "";
+const char* decode_attn_last_kernel() { return g_decode_attn_kernel; }
+
 template <typename T>
 void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s) {
   ASR_REQUIRE(a.n >= 1 && a.n <= DA_MAXN, "decode attention: %d new positions per call (max %d)", a.n, DA_MAXN);
@@ -1746,6 +1749,7 @@ void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s) {
     const bool wave_on = gemm_env_decode_attn_wave();
     if (wave_on && a.n == 1 && !a.plan && a.kv_new && !a.k_scale && !a.v_scale && (a.ld_q % 8) == 0 && (a.ld_new % 8) == 0 && (a.q_col0 % 8) == 0 &&
         (a.k_col0 % 8) == 0 && (a.v_col0 % 8) == 0 && (a.ld_out % 8) == 0) {                 // single-token self-attention: one wave per (sequence, head)
+      g_decode_attn_kernel = "self_wave";
       hipLaunchKernelGGL(decode_self_attn_wave_kernel, dim3(batch, (a.n_heads + 3) / 4), dim3(256), 0, s, a);
       HIP_CHECK(hipGetLastError());
       return;
@@ -1758,9 +1762,13 @@ void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s) {
     if (a.k_scale || a.v_scale) {
       if constexpr (std::is_same<T, bf16_t>::value) {
         ASR_REQUIRE(a.k_scale && a.v_scale, "decode attention: the FP8 cache path needs both scale arrays");
+        g_decode_attn_kernel = "cross_1pass_fp8";
         hipLaunchKernelGGL((decode_cross_attn_kernel<T, true>), dim3(batch, a.n_heads), dim3(256), 0, s, a);
       } else ASR_REQUIRE(false, "decode attention: FP8 K / V need a bf16 session");
-    } else hipLaunchKernelGGL((decode_cross_attn_kernel<T, false>), dim3(batch, a.n_heads), dim3(256), 0, s, a);
+    } else {
+      g_decode_attn_kernel = "cross_1pass";
+      hipLaunchKernelGGL((decode_cross_attn_kernel<T, false>), dim3(batch, a.n_heads), dim3(256), 0, s, a);
+    }
     HIP_CHECK(hipGetLastError());
     return;
   }
@@ -1770,12 +1778,16 @@ void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s) {
   if (a.k_scale || a.v_scale) {
     if constexpr (std::is_same<T, bf16_t>::value) {
       ASR_REQUIRE(a.k_scale && a.v_scale && !a.kv_new && a.plan, "decode attention: the FP8 cache path is the cross-attention of bf16 sessions");
+      g_decode_attn_kernel = a.n == 1 ? "general_n1_fp8" : "general_n8_fp8";
       if (a.n == 1) hipLaunchKernelGGL((decode_attn_kernel<T, 1, true>), dim3(batch, a.n_heads), dim3(256), lds, s, b);
       else hipLaunchKernelGGL((decode_attn_kernel<T, DA_MAXN, true>), dim3(batch, a.n_heads), dim3(256), lds, s, b);
     } else ASR_REQUIRE(false, "decode attention: FP8 K / V need a bf16 session");
   }
-  else if (a.n == 1) hipLaunchKernelGGL((decode_attn_kernel<T, 1>), dim3(batch, a.n_heads), dim3(256), lds, s, b);
-  else hipLaunchKernelGGL((decode_attn_kernel<T, DA_MAXN>), dim3(batch, a.n_heads), dim3(256), lds, s, b);
+  else {
+    g_decode_attn_kernel = a.n == 1 ? "general_n1" : "general_n8";
+    if (a.n == 1) hipLaunchKernelGGL((decode_attn_kernel<T, 1>), dim3(batch, a.n_heads), dim3(256), lds, s, b);
+    else hipLaunchKernelGGL((decode_attn_kernel<T, DA_MAXN>), dim3(batch, a.n_heads), dim3(256), lds, s, b);
+  }
   HIP_CHECK(hipGetLastError());
 }
 

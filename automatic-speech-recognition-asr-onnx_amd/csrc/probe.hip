@@ -454,6 +454,165 @@ extern "C" int asr_probe_gemm(asr_probe_gemm_desc* d) {
   });
 }
 
+// ---- decoder attention (launch_decode_attention) on host arrays: self-attention over a contiguous or paged cache, cross-attention over
+// packed slabs (optionally FP8 through the product's quantiser). Reports which form the dispatcher chose (asr_mi355x_probe.h).
+namespace {
+template <typename T> T elem_from_f32(float v);
+template <> float elem_from_f32<float>(float v) { return v; }
+template <> bf16_t elem_from_f32<bf16_t>(float v) { return f32_to_bf16(v); }
+inline float elem_to_f32(float v) { return v; }
+inline float elem_to_f32(bf16_t v) { return bf16_bits_to_f32(v); }
+template <typename T> T elem_nan();
+template <> float elem_nan<float>() { return std::nanf(""); }
+template <> bf16_t elem_nan<bf16_t>() { return (bf16_t)0x7fc0; }
+template <typename T> bool same_bits(T x, T y) { return std::memcmp(&x, &y, sizeof(T)) == 0; }
+
+template <typename T>
+void probe_decode_attention(asr_probe_decode_attn_desc* d) {
+  Tmp t;
+  const int B = d->B, H = d->H, n = d->n, D = H * 64, nb = d->nb > 0 ? d->nb : d->B - d->b0;
+  ASR_REQUIRE(B > 0 && H > 0 && n >= 1 && n <= 8 && d->b0 >= 0 && nb > 0 && d->b0 + nb <= B && d->q && d->out, "probe_decode_attention: bad geometry");
+  ASR_REQUIRE(d->ld_q >= d->q_col0 + D && d->q_col0 >= 0, "probe_decode_attention: q columns [%d, %d) past ld_q %d", d->q_col0, d->q_col0 + D, d->ld_q);
+  auto up = [&](const float* src, size_t count) -> T* {
+    std::vector<T> h(count);
+    for (size_t i = 0; i < count; ++i) h[i] = elem_from_f32<T>(src[i]);
+    T* p = (T*)t.alloc(count * sizeof(T));
+    HIP_CHECK(hipMemcpy(p, h.data(), count * sizeof(T), hipMemcpyHostToDevice));
+    return p;
+  };
+  DecAttnArgs a{};
+  a.q = up(d->q, (size_t)B * n * d->ld_q); a.ld_q = d->ld_q; a.q_col0 = d->q_col0;
+  a.n = n; a.n_heads = H; a.causal = d->causal; a.b0 = d->b0;
+  T* out = (T*)t.alloc((size_t)B * n * D * sizeof(T));
+  a.out = out; a.ld_out = D;
+  std::vector<T> cache;                 // self: host image of the cache (NaN wherever no cached row was placed)
+  T* dcache = nullptr;
+  std::vector<size_t> kpos, vpos;       // self: element offset of (b, h, s) row in the image, [B][H][hist + n]
+  const int S = d->hist + n;
+  if (!d->cross) {
+    ASR_REQUIRE(d->kv_new && (d->hist == 0 || (d->k_hist && d->v_hist)) && d->hist >= 0, "probe_decode_attention: self mode needs kv_new and the cached rows");
+    a.kv_new = up(d->kv_new, (size_t)B * n * 2 * D); a.ld_new = 2 * D; a.k_col0 = 0; a.v_col0 = D;
+    int cap;
+    if (d->paged) {
+      ASR_REQUIRE(d->page_table && d->n_pages > 0 && d->pages_per_seq > 0, "probe_decode_attention: paged cache without a page table");
+      for (int i = 0; i < B * d->pages_per_seq; ++i)
+        ASR_REQUIRE(d->page_table[i] >= 0 && d->page_table[i] < d->n_pages, "probe_decode_attention: page id %d outside the pool of %d", d->page_table[i], d->n_pages);
+      cap = d->pages_per_seq * 16;
+      cache.assign((size_t)d->n_pages * 2 * H * 1024, elem_nan<T>());     // pool [page][K | V][head][16][64], as whisper.hip lays it out
+    } else {
+      ASR_REQUIRE(d->max_pos > 0, "probe_decode_attention: contiguous cache without max_pos");
+      cap = d->max_pos;
+      cache.assign((size_t)2 * B * H * cap * 64, elem_nan<T>());          // K [B][H][max_pos][64], then V
+    }
+    a.max_keys = d->max_keys > 0 ? d->max_keys : cap;
+    ASR_REQUIRE(S <= cap && S <= a.max_keys && a.max_keys <= 1536, "probe_decode_attention: %d keys, cache of %d, max_keys %d", S, cap, a.max_keys);
+    kpos.resize((size_t)B * H * S); vpos.resize((size_t)B * H * S);
+    for (int b = 0; b < B; ++b)
+      for (int h = 0; h < H; ++h)
+        for (int s = 0; s < S; ++s) {
+          const size_t i = ((size_t)b * H + h) * S + s;
+          if (d->paged) {
+            kpos[i] = (size_t)d->page_table[(size_t)b * d->pages_per_seq + (s >> 4)] * 2 * H * 1024 + (size_t)h * 1024 + (size_t)(s & 15) * 64;
+            vpos[i] = kpos[i] + (size_t)H * 1024;
+          } else {
+            kpos[i] = (((size_t)b * H + h) * cap + s) * 64;
+            vpos[i] = kpos[i] + (size_t)B * H * cap * 64;
+          }
+          if (s < d->hist)
+            for (int e = 0; e < 64; ++e) {
+              const size_t src = (((size_t)b * H + h) * d->hist + s) * 64 + e;
+              cache[kpos[i] + e] = elem_from_f32<T>(d->k_hist[src]);
+              cache[vpos[i] + e] = elem_from_f32<T>(d->v_hist[src]);
+            }
+        }
+    dcache = (T*)t.alloc(cache.size() * sizeof(T));
+    HIP_CHECK(hipMemcpy(dcache, cache.data(), cache.size() * sizeof(T), hipMemcpyHostToDevice));
+    if (d->paged) {
+      int32_t* pt = (int32_t*)t.alloc((size_t)B * d->pages_per_seq * 4);
+      HIP_CHECK(hipMemcpy(pt, d->page_table, (size_t)B * d->pages_per_seq * 4, hipMemcpyHostToDevice));
+      a.k_base = dcache; a.v_base = dcache + (size_t)H * 1024;
+      a.page_table = pt; a.pages_per_seq = d->pages_per_seq; a.page_stride = (int64_t)2 * H * 1024;
+    } else {
+      a.k_base = dcache; a.v_base = dcache + (size_t)B * H * cap * 64;
+      a.stride_b = (int64_t)H * cap * 64; a.stride_h = (int64_t)cap * 64;
+    }
+    a.hist = d->hist;
+    if (d->hist_dev) {                  // graph-replay form: the by-value history is deliberately wrong
+      int32_t* hd = (int32_t*)t.alloc(4);
+      HIP_CHECK(hipMemcpy(hd, &d->hist, 4, hipMemcpyHostToDevice));
+      a.hist_dev = hd; a.hist = 0;
+    }
+  } else {
+    ASR_REQUIRE(d->k_slab && d->v_slab && d->row_off && d->n_lfr && d->rows > 0 && !d->causal, "probe_decode_attention: cross mode needs slabs and a plan");
+    std::vector<UttPlan> plan(B);
+    std::memset(plan.data(), 0, plan.size() * sizeof(UttPlan));
+    int longest = 0;
+    for (int b = 0; b < B; ++b) {
+      ASR_REQUIRE(d->n_lfr[b] >= 1 && d->row_off[b] >= 0 && d->row_off[b] + d->n_lfr[b] <= d->rows, "probe_decode_attention: sequence %d rows [%d, %d) outside the slab of %d",
+                  b, d->row_off[b], d->row_off[b] + d->n_lfr[b], d->rows);
+      plan[b].n_lfr = d->n_lfr[b]; plan[b].row_off = d->row_off[b]; plan[b].T = d->n_lfr[b];
+      longest = std::max(longest, d->n_lfr[b]);
+    }
+    a.max_keys = d->max_keys > 0 ? d->max_keys : longest;
+    ASR_REQUIRE(longest <= a.max_keys && a.max_keys <= 1536, "probe_decode_attention: %d keys, max_keys %d", longest, a.max_keys);
+    UttPlan* dp = (UttPlan*)t.alloc(plan.size() * sizeof(UttPlan));
+    HIP_CHECK(hipMemcpy(dp, plan.data(), plan.size() * sizeof(UttPlan), hipMemcpyHostToDevice));
+    const size_t slab = (size_t)d->rows * 64, half = (size_t)H * slab;
+    std::vector<float> kv(2 * half);
+    std::memcpy(kv.data(), d->k_slab, half * 4);
+    std::memcpy(kv.data() + half, d->v_slab, half * 4);
+    a.plan = dp; a.stride_b = 0; a.stride_h = (int64_t)slab;
+    if (d->fp8) {
+      ASR_REQUIRE(sizeof(T) == 2, "probe_decode_attention: FP8 slabs need a bf16 session");
+      std::vector<bf16_t> hb(kv.size());
+      for (size_t i = 0; i < kv.size(); ++i) hb[i] = f32_to_bf16(kv[i]);
+      bf16_t* src = (bf16_t*)t.alloc(hb.size() * 2);
+      HIP_CHECK(hipMemcpy(src, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
+      unsigned char* q8 = (unsigned char*)t.alloc(kv.size());
+      float* sc = (float*)t.alloc((size_t)2 * H * B * 4);
+      launch_quantize_crosskv_fp8(src, slab, 2 * H, dp, B, q8, sc, 0, nullptr);
+      a.k_base = q8; a.v_base = q8 + half;
+      a.k_scale = sc; a.v_scale = sc + (size_t)H * B; a.scale_ld = B;
+      HIP_CHECK(hipDeviceSynchronize());
+      if (d->kv8) HIP_CHECK(hipMemcpy(d->kv8, q8, kv.size(), hipMemcpyDeviceToHost));
+      if (d->scale8) HIP_CHECK(hipMemcpy(d->scale8, sc, (size_t)2 * H * B * 4, hipMemcpyDeviceToHost));
+    } else {
+      T* dkv = up(kv.data(), kv.size());
+      a.k_base = dkv; a.v_base = dkv + half;
+    }
+  }
+  launch_decode_attention<T>(a, nb, nullptr);
+  snprintf(d->kernel, sizeof(d->kernel), "%s", decode_attn_last_kernel());
+  HIP_CHECK(hipDeviceSynchronize());
+  std::vector<T> ho((size_t)B * n * D);
+  HIP_CHECK(hipMemcpy(ho.data(), out, ho.size() * sizeof(T), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < ho.size(); ++i) d->out[i] = elem_to_f32(ho[i]);
+  d->stray = 0;
+  if (dcache) {
+    std::vector<T> after(cache.size());
+    HIP_CHECK(hipMemcpy(after.data(), dcache, after.size() * sizeof(T), hipMemcpyDeviceToHost));
+    std::vector<unsigned char> seen(cache.size(), 0);
+    for (size_t i = 0; i < kpos.size(); ++i)
+      for (int e = 0; e < 64; ++e) {
+        if (d->k_after) d->k_after[i * 64 + e] = elem_to_f32(after[kpos[i] + e]);
+        if (d->v_after) d->v_after[i * 64 + e] = elem_to_f32(after[vpos[i] + e]);
+        seen[kpos[i] + e] = seen[vpos[i] + e] = 1;
+      }
+    for (size_t i = 0; i < cache.size(); ++i) d->stray += (!seen[i] && !same_bits(cache[i], after[i])) ? 1 : 0;
+  }
+}
+}  // namespace
+
+extern "C" int asr_probe_decode_attention(asr_probe_decode_attn_desc* d) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d, "probe_decode_attention: null descriptor");
+    asr_require_device(0);
+    gemm_reload_env();
+    if (d->bf16) probe_decode_attention<bf16_t>(d);
+    else probe_decode_attention<float>(d);
+  });
+}
+
 // ---- grid-barrier latency probe (tuning hook): a cooperative launch of one workgroup per CU crossing `iters` barriers.
 namespace {
 __device__ __forceinline__ bool grid_barrier_probe_step(unsigned int* counter, unsigned int target) {

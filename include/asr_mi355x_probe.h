@@ -55,6 +55,40 @@ int asr_probe_decode_gemm(int M, int N, int K, const uint16_t* a, const uint16_t
 int asr_probe_gemm_fp8(int M, int N, int K, const uint8_t* a8, const uint8_t* w8, const float* w_scale, float a_scale, const float* bias,
                        const float* add, int act, uint8_t* out8, float* out_f32, int iters, float* us);
 
+/* One Whisper decoder attention call through the product dispatcher (launch_decode_attention<bf16 | f32>, head_dim 64) on host arrays.
+ * Operands are rounded to the element type on upload. Sequences [b0, b0 + nb) of a batch of B are launched (nb = 0: B - b0).
+ *   self  (cross = 0): q [B n][ld_q] (head h at q_col0 + h 64), kv_new [B n][2 H 64] (k columns, then v), cached rows k_hist / v_hist
+ *         [B][H][hist][64]; the cache is a contiguous extent of max_pos positions per (sequence, head), or (paged = 1) pages of 16 positions
+ *         (n_pages of them, laid out as whisper.hip's pool: K page of every head, then V) addressed by page_table [B][pages_per_seq].
+ *         k_after / v_after [B][H][hist + n][64] receive the cache after the call. hist_dev = 1: the history length travels in device memory.
+ *   cross (cross = 1): slabs k_slab / v_slab [H][rows][64], sequence b at rows [row_off[b], row_off[b] + n_lfr[b]); fp8 = 1 (bf16 only):
+ *         the slabs go through the product's FP8 quantiser first, whose bytes ([2][H][rows][64], K then V) and scales ([2][H][B]) come back
+ *         in kv8 / scale8 when non-null.
+ * out [B n][H 64] (rows of sequences outside the launch stay 0); `kernel` receives the form that ran. */
+typedef struct asr_probe_decode_attn_desc {
+  int32_t bf16;            /* 1 bf16, 0 f32 */
+  int32_t cross, B, b0, nb, H, n, causal;
+  const float* q; int32_t ld_q, q_col0;
+  int32_t max_keys;        /* the launch's max_keys (0: max_pos / pages_per_seq 16 / the longest extent) */
+  /* self */
+  const float* kv_new;
+  const float* k_hist; const float* v_hist;
+  int32_t hist, hist_dev, max_pos;
+  int32_t paged, n_pages, pages_per_seq;
+  const int32_t* page_table;
+  float* k_after; float* v_after;
+  /* cross */
+  const float* k_slab; const float* v_slab;
+  int32_t rows;
+  const int32_t* row_off; const int32_t* n_lfr;
+  int32_t fp8;
+  uint8_t* kv8; float* scale8;
+  float* out;
+  int32_t stray;           /* out (self): cache elements outside positions [0, hist + n) of the batch's (sequence, head) extents that changed */
+  char kernel[32];         /* out: "self_wave", "cross_1pass", "cross_1pass_fp8", "general_n1", "general_n8", "general_n1_fp8", "general_n8_fp8" */
+} asr_probe_decode_attn_desc;
+int asr_probe_decode_attention(asr_probe_decode_attn_desc* d);
+
 /* launches per GEMM kernel family since the last reset, as "family=count;..." (host-side counters: hipGraph replays do not
  * count, so reset, run a session once on a new batch geometry, read). reset != 0 clears the counters after the read. */
 int asr_probe_gemm_counts(int reset, char* buf, int cap);
