@@ -75,6 +75,7 @@ SIGNATURES = {
     "asr_whisper_prefill": (_i, [_vp, _ip, _i, _ip, _fp]),
     "asr_whisper_decode": (_i, [_vp, _ip, _ip, _fp]),
     "asr_whisper_generate": (_i, [_vp, _i, _i, _ip, _ip]),
+    "asr_whisper_beam_search": (_i, [_vp, _i, _i, _i, _ip, _ip, _fp]),
     "asr_whisper_set_penalty": (_i, [_vp, C.c_float, _i]),
     "asr_whisper_track_history": (_i, [_vp, _i]),
     "asr_whisper_set_fp8_act_shift": (_i, [_vp, _i]),

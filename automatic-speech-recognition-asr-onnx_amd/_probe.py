@@ -30,6 +30,12 @@ class DecodeAttnDesc(C.Structure):
                 ("kv8", C.c_void_p), ("scale8", _fp), ("out", _fp), ("stray", C.c_int32), ("kernel", C.c_char * 32)]
 
 
+class BeamSelectDesc(C.Structure):
+    _fields_ = [("n_utt", C.c_int32), ("beam", C.c_int32), ("K", C.c_int32), ("ld", C.c_int32), ("first", C.c_int32), ("n_slots", C.c_int32),
+                ("n_stop", C.c_int32), ("topv", _fp), ("topi", _ip), ("cum", _fp), ("fin", _ip), ("len", _ip), ("next", _ip), ("done", _ip),
+                ("stop", _ip), ("src_in", _ip), ("tok_in", _ip), ("src_out", _ip), ("tok_out", _ip)]
+
+
 SIGNATURES = {
     "asr_probe_gemm": (C.c_int, [C.POINTER(GemmDesc)]),
     "asr_probe_gemm_chain": (C.c_int, [C.c_int] * 6 + [_fp]),
@@ -39,6 +45,8 @@ SIGNATURES = {
     "asr_probe_decode_gemm_mxfp4": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _fp, C.c_int, _fp]),
     "asr_probe_decode_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _fp, _fp, C.c_int, _fp]),
     "asr_probe_decode_attention": (C.c_int, [C.POINTER(DecodeAttnDesc)]),
+    "asr_probe_beam_select": (C.c_int, [C.POINTER(BeamSelectDesc)]),
+    "asr_probe_decode_attention_beam": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p]),
     "asr_probe_gemm_counts": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "asr_probe_gemm_fp8": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _fp, C.c_float, _fp, _fp, C.c_int, C.c_void_p, _fp, C.c_int, _fp]),
     "asr_probe_gemm_bench": (C.c_int, [C.c_int] * 6 + [_fp]),
@@ -175,6 +183,39 @@ def decode_attention(q, bf16=True, n=1, B=None, b0=0, nb=0, ld_q=None, q_col0=0,
     if not cross:
         after = (ka, va, d.stray)
     return out, after, d.kernel.decode()
+
+
+def decode_attention_beam(q, kv_new, ext, src, beam, p0, hist, bf16=True, hist_dev=False):
+    """One "self_beam" call (asr_mi355x_probe.h): q [rows][H 64], kv_new [rows][2 H 64], ext [rows][2][H][S][64] (the rows' extents before the call),
+    src [rows][ld_src] (row holding generated position p0 + j of row r). Returns (out [rows][H 64], ext after the call, stray element count, kernel)."""
+    q, kv_new = _f32(q), _f32(kv_new)
+    ext = np.array(ext, dtype=np.float32, order="C", copy=True)
+    src = np.ascontiguousarray(src, np.int32)
+    rows, _, H, S, _ = ext.shape
+    assert q.shape == (rows, H * 64) and kv_new.shape == (rows, 2 * H * 64) and src.ndim == 2 and src.shape[0] == rows
+    out = np.zeros((rows, H * 64), np.float32)
+    stray = np.zeros(1, np.int32)
+    kern = C.create_string_buffer(32)
+    _lib.check(load().asr_probe_decode_attention_beam(int(bf16), rows, int(beam), H, S, int(p0), int(hist), int(hist_dev), src.ctypes.data_as(_ip),
+                                                      src.shape[1], q.ctypes.data_as(_fp), kv_new.ctypes.data_as(_fp), ext.ctypes.data_as(_fp),
+                                                      out.ctypes.data_as(_fp), stray.ctypes.data_as(_ip), kern))
+    return out, ext, int(stray[0]), kern.value.decode()
+
+
+def beam_select(beam, K, n_slots, topv, topi, cum, fin, length, nxt, done, src_in, tok_in, src_out, tok_out, stop=(), first=False):
+    """One launch_beam_select pass (asr_mi355x_probe.h) on host arrays -> dict of the state and tables after it (inputs are not modified)."""
+    f32 = lambda x: np.array(x, np.float32, order="C", copy=True)
+    i32 = lambda x: np.array(x, np.int32, order="C", copy=True)
+    st = dict(topv=f32(topv), topi=i32(topi), cum=f32(cum), fin=i32(fin), len=i32(length), next=i32(nxt), done=i32(done),
+              stop=i32(list(stop) or [0]), src_in=i32(src_in), tok_in=i32(tok_in), src_out=i32(src_out), tok_out=i32(tok_out))
+    d = BeamSelectDesc()
+    d.n_utt, d.beam, d.K, d.ld, d.first, d.n_slots, d.n_stop = st["done"].size, beam, K, st["src_in"].shape[1], int(first), n_slots, len(stop)
+    for k in ("topv", "cum"):
+        setattr(d, k, st[k].ctypes.data_as(_fp))
+    for k in ("topi", "fin", "len", "next", "done", "stop", "src_in", "tok_in", "src_out", "tok_out"):
+        setattr(d, k, st[k].ctypes.data_as(_ip))
+    _lib.check(load().asr_probe_beam_select(C.byref(d)))
+    return st
 
 
 def _bf16_bits(x):

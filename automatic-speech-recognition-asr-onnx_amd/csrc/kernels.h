@@ -89,6 +89,10 @@ struct DecAttnArgs {
   // a launch over the sub-batch [b0, b0 + grid.x) of the session's batch (the decode chains of whisper.hip): every per-sequence index is b0 + blockIdx.x;
   // scale_ld = sequences per head row of k_scale / v_scale (0: the launch's own grid.x)
   int b0 = 0, scale_ld = 0;
+  // beam search ("self_beam": single-token self-attention of hypothesis rows, `batch` = rows = utterances x beam, utterance-major): row r's cache is an
+  // extent k_base + r * stride_b + h * stride_h (slot = position); positions below beam_p0 (the prompt, copied into every row) are read from the row's own
+  // extent, position p >= beam_p0 from the extent of row beam_src[r * ld_src + p - beam_p0] (its ancestry). The new row goes to the row's own slot `hist`.
+  const int32_t* beam_src = nullptr; int ld_src = 0, beam_p0 = 0, beam = 1;
 };
 // FP8 (OCP e4m3, power-of-two scales) quantisers of precision mode ASR_PRECISION_FP8W
 void launch_quantize_rows_fp8(const bf16_t* W, int ld, int N, int K, unsigned char* W8, float* scale, bf16_t* Wdq, hipStream_t s);
@@ -98,7 +102,25 @@ void launch_quantize_crosskv_fp8(bf16_t* slabs, size_t slab_elems, int n_slabs, 
                                  int dq_in_place, hipStream_t s);
 template <typename T>
 void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s);
-const char* decode_attn_last_kernel();   // form of this thread's last launch_decode_attention ("self_wave", "cross_1pass[_fp8]", "general_n1[_fp8]", "general_n8[_fp8]"): test hook
+const char* decode_attn_last_kernel();   // form of this thread's last launch_decode_attention ("self_wave", "self_beam", "cross_1pass[_fp8]", "general_n1[_fp8]", "general_n8[_fp8]"): test hook
+
+// ---- beam search ranking (Qwen3-ASR and Whisper; semantics of oracle/qwen_asr_oracle.py:beam_search_core). Hypotheses of utterance b are rows b * beam + r.
+constexpr int BEAM_MAX = 8;
+// per row: log-soft-max over the first n_valid columns of logits (+ bias[col] when bias is set: Whisper's BEGIN_SUPPRESS on the first ranking) and the
+// K best (log-prob, id) pairs, ties -> lower id: topv / topi [rows][K]
+void launch_beam_topk(const float* logits, int ld, int rows, int n_valid, const float* bias, int K, float* topv, int32_t* topi, hipStream_t s);
+struct BeamArgs {
+  int beam, K, ld, first, n_slots;       // ld: row stride of the ancestry / token tables; n_slots: generated cache slots after this pass
+  const float* topv; const int32_t* topi;
+  float* cum; int32_t* fin; int32_t* len; int32_t* next; int32_t* done;
+  const int32_t* stop; int n_stop;
+  const int32_t *src_in, *tok_in; int32_t *src_out, *tok_out;
+  const int32_t* slots_dev = nullptr;    // when set, n_slots = *slots_dev + slots_off (a device counter: the pass replays from a captured graph)
+  int slots_off = 0;
+};
+// one wave per utterance: rank the <= beam * K extensions (finished hypotheses stand as themselves), keep the best `beam` in order (score
+// descending, then hypothesis, then rank inside the hypothesis), rebuild the rows' ancestry / token tables from their parents'; done[b] = best has ended
+void launch_beam_select(const BeamArgs& a, int n_utt, hipStream_t s);
 
 // ids[r] = first arg-max over n < n_valid of logits[r][n] + (extra ? extra[n] : 0)
 void launch_argmax_rows(const float* logits, int ld, int rows, int n_valid, const float* extra, int32_t* ids, hipStream_t s);

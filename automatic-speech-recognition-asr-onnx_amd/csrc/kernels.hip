@@ -1736,6 +1736,117 @@ __global__ __launch_bounds__(256) void decode_self_attn_wave_kernel(const DecAtt
   }
 }
 
+// ---- beam search: single-token self-attention of hypothesis rows ("self_beam"), one wave per (row, head) with the online soft-max of the kernel above.
+// Row r's cache is an extent (slot = position); the prompt positions (< beam_p0) were copied into every row, a generated position p is read from the extent of
+// row beam_src[r][p - beam_p0] -- the hypothesis that wrote it -- so nothing is copied or re-ordered between steps. 1-D grid: the `beam` rows of one (utterance,
+// head group) take workgroup ids of one XCD (ids w and w + 8 share an XCD), so the ancestor rows they have in common come from HBM once into that XCD's L2.
+template <typename T>
+__global__ __launch_bounds__(256) void decode_self_attn_beam_kernel(const DecAttnArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, beam = a.beam;
+  const int w = blockIdx.x, units = gridDim.x / beam, HG = (a.n_heads + 3) >> 2;
+  int u, r;
+  if (units % 8 == 0) { const int x = w & 7, q = w >> 3; u = (q / beam) * 8 + x; r = q % beam; }
+  else { u = w / beam; r = w % beam; }
+  const int row = (u / HG) * beam + r, h = (u % HG) * 4 + wave;
+  if (h >= a.n_heads) return;
+  const int hist = a.hist_dev ? *a.hist_dev : a.hist;          // keys 0 .. hist - 1 are cached, key `hist` is the new row
+  const int sub = lane & 7, grp = lane >> 3, p0 = a.beam_p0;
+  const int32_t* src = a.beam_src + (size_t)row * a.ld_src;
+  T* Kb = reinterpret_cast<T*>(a.k_base) + (size_t)h * a.stride_h;
+  T* Vb = reinterpret_cast<T*>(a.v_base) + (size_t)h * a.stride_h;
+  const int utt0 = row - row % beam;
+  auto owner = [&](int s) -> int {                             // an entry outside the row's own utterance cannot be ancestry: read the row itself
+    const int o = s < p0 ? row : src[s - p0];
+    return (unsigned)(o - utt0) < (unsigned)beam ? o : row;
+  };
+  auto crow = [&](int s) -> size_t { return (size_t)owner(s) * a.stride_b + (size_t)s * 64 + sub * 8; };
+  const T* NEW = reinterpret_cast<const T*>(a.kv_new) + (size_t)row * a.ld_new + h * 64 + sub * 8;
+  Raw8<T> q8, nk, nv;
+  q8.load(reinterpret_cast<const T*>(a.q) + (size_t)row * a.ld_q + a.q_col0 + h * 64 + sub * 8);
+  nk.load(NEW + a.k_col0);
+  nv.load(NEW + a.v_col0);
+  auto dot8 = [&](const float (&x)[8], const float (&y)[8]) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc = fmaf(x[e], y[e], acc);
+    acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0xB1, 0xf, 0xf, true));
+    acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x4E, 0xf, 0xf, true));
+    acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x141, 0xf, 0xf, true));
+    return acc;
+  };
+  float m = -INFINITY, l = 0.0f, acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+  Raw8<T> kr[8], vr[8];
+#pragma unroll
+  for (int u8 = 0; u8 < 8; ++u8) {
+    kr[u8] = Raw8<T>{}; vr[u8] = Raw8<T>{};                    // slots past the history stay finite: 0 x garbage could be NaN
+    const int s0 = u8 * 8 + grp;
+    if (s0 < hist) { const size_t ro = crow(s0); kr[u8].load(Kb + ro); vr[u8].load(Vb + ro); }
+  }
+  if (grp == 0) {                                            // the new row goes to this row's own slot `hist` (read by its descendants in later steps)
+    const T* nkp = NEW + a.k_col0; const T* nvp = NEW + a.v_col0;
+    T* kd = Kb + (size_t)row * a.stride_b + (size_t)hist * 64 + sub * 8;
+    T* vd = Vb + (size_t)row * a.stride_b + (size_t)hist * 64 + sub * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { kd[e] = nkp[e]; vd[e] = nvp[e]; }
+  }
+  float qf[8];
+  q8.get(qf);
+  for (int blk = 0; blk < hist; blk += 64) {
+    float sc[8], vf[8][8];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int u8 = 0; u8 < 8; ++u8) {
+      float kf[8];
+      kr[u8].get(kf);
+      vr[u8].get(vf[u8]);
+      const float d = dot8(qf, kf);
+      sc[u8] = blk + u8 * 8 + grp < hist ? d : -INFINITY;
+      mx = fmaxf(mx, sc[u8]);
+    }
+    if (blk + 64 < hist) {
+#pragma unroll
+      for (int u8 = 0; u8 < 8; ++u8) {
+        const int s1 = blk + 64 + u8 * 8 + grp;
+        kr[u8] = Raw8<T>{}; vr[u8] = Raw8<T>{};
+        if (s1 < hist) { const size_t ro = crow(s1); kr[u8].load(Kb + ro); vr[u8].load(Vb + ro); }
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 8, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m, mx), alpha = __expf(m - m_new);
+    l *= alpha;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] *= alpha;
+#pragma unroll
+    for (int u8 = 0; u8 < 8; ++u8) {
+      const float p = __expf(sc[u8] - m_new);
+      l += p;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, vf[u8][e], acc[e]);
+    }
+    m = m_new;
+  }
+  l += __shfl_xor(l, 8, 64); l += __shfl_xor(l, 16, 64); l += __shfl_xor(l, 32, 64);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    acc[e] += __shfl_xor(acc[e], 8, 64); acc[e] += __shfl_xor(acc[e], 16, 64); acc[e] += __shfl_xor(acc[e], 32, 64);
+  }
+  float nkf[8], nvf[8];
+  nk.get(nkf);
+  nv.get(nvf);
+  const float s_new = dot8(qf, nkf);
+  const float m_fin = fmaxf(m, s_new), alpha = __expf(m - m_fin), p_new = __expf(s_new - m_fin);
+  const float inv = 1.0f / (l * alpha + p_new);
+  if (grp == 0) {
+    T* O = reinterpret_cast<T*>(a.out) + (size_t)row * a.ld_out + h * 64 + sub * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) Elem<T>::store(O + e, (acc[e] * alpha + p_new * nvf[e]) * inv);
+  }
+}
+
 }  // namespace
 
 static thread_local const char* g_decode_attn_kernel = "";
@@ -1745,6 +1856,16 @@ template <typename T>
 void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s) {
   ASR_REQUIRE(a.n >= 1 && a.n <= DA_MAXN, "decode attention: %d new positions per call (max %d)", a.n, DA_MAXN);
   ASR_REQUIRE(a.plan || a.hist_dev || a.hist + a.n <= DA_MAXKEYS, "decode attention: %d keys exceed %d", a.hist + a.n, DA_MAXKEYS);
+  if (a.beam_src) {                                          // beam search hypothesis rows: `batch` = rows, a multiple of the width
+    ASR_REQUIRE(a.n == 1 && a.kv_new && !a.plan && !a.page_table && !a.k_scale && !a.v_scale && a.b0 == 0 && a.beam >= 1 && batch % a.beam == 0 &&
+                a.ld_src > 0 && a.beam_p0 >= 0 && (a.ld_q % 8) == 0 && (a.ld_new % 8) == 0 && (a.q_col0 % 8) == 0 && (a.k_col0 % 8) == 0 &&
+                (a.v_col0 % 8) == 0 && (a.ld_out % 8) == 0 && (a.stride_b % 8) == 0 && (a.stride_h % 8) == 0,
+                "decode attention: the beam form is single-token self-attention over per-row extents");
+    g_decode_attn_kernel = "self_beam";
+    hipLaunchKernelGGL((decode_self_attn_beam_kernel<T>), dim3(batch * ((a.n_heads + 3) / 4)), dim3(256), 0, s, a);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   if constexpr (std::is_same<T, bf16_t>::value) {
     const bool wave_on = gemm_env_decode_attn_wave();
     if (wave_on && a.n == 1 && !a.plan && a.kv_new && !a.k_scale && !a.v_scale && (a.ld_q % 8) == 0 && (a.ld_new % 8) == 0 && (a.q_col0 % 8) == 0 &&
@@ -2432,5 +2553,150 @@ __global__ __launch_bounds__(256) void stream_state_copy_kernel(const StreamStat
 }
 void launch_stream_state_copy(const StreamStateSeg* segs, int n_segs, int n_items, const UttPlan* plan, int n_active, bool restore, hipStream_t s) {
   hipLaunchKernelGGL(stream_state_copy_kernel, dim3(n_active, n_items), dim3(256), 0, s, segs, n_segs, plan, restore ? 1 : 0);
+  HIP_CHECK(hipGetLastError());
+}
+
+namespace {
+// ------------------------------------------------------------------------------------ beam search ranking
+
+// per row: log-soft-max statistics and the K best (log-prob, id) pairs, ties -> lower id. One pass: every thread keeps a running
+// (max, sum) pair and its own sorted best-8 list; the lists merge in K rounds of a block-wide arg-max.
+// bias (nullable): added to every column first; a column the bias takes to -inf (BEGIN_SUPPRESS) is left out of the soft-max as well.
+__global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict__ logits, int ld, int n_valid, const float* __restrict__ bias, int K,
+                                                         float* __restrict__ topv, int32_t* __restrict__ topi) {
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* p = logits + (size_t)row * ld;
+  float tv[BEAM_MAX]; int ti[BEAM_MAX];
+#pragma unroll
+  for (int j = 0; j < BEAM_MAX; ++j) { tv[j] = -INFINITY; ti[j] = INT32_MAX; }
+  float m = -INFINITY, sum = 0.0f;
+  for (int v0 = tid * 4; v0 < n_valid; v0 += 4096) {
+    const float4 q = *reinterpret_cast<const float4*>(p + v0);
+    const float xs[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float x = xs[e];
+      if (v0 + e >= n_valid) continue;
+      if (bias) { x += bias[v0 + e]; if (x == -INFINITY) continue; }
+      if (x > m) { sum = sum * __expf(m - x) + 1.0f; m = x; } else { sum += __expf(x - m); }
+      if (x > tv[BEAM_MAX - 1]) {
+        tv[BEAM_MAX - 1] = x; ti[BEAM_MAX - 1] = v0 + e;
+#pragma unroll
+        for (int j = BEAM_MAX - 1; j > 0; --j)
+          if (tv[j] > tv[j - 1]) { const float a = tv[j]; tv[j] = tv[j - 1]; tv[j - 1] = a; const int c = ti[j]; ti[j] = ti[j - 1]; ti[j - 1] = c; }
+      }
+    }
+  }
+  __shared__ float sm[16], ss[16], sv[16];
+  __shared__ int si[16];
+  __shared__ float lse_sh;
+  __shared__ int win_sh;
+  auto merge = [](float& m1, float& s1, float m2, float s2) {
+    const float M = fmaxf(m1, m2);
+    const float a = m1 == -INFINITY ? 0.0f : s1 * __expf(m1 - M), b = m2 == -INFINITY ? 0.0f : s2 * __expf(m2 - M);
+    m1 = M; s1 = a + b;
+  };
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) merge(m, sum, __shfl_xor(m, o, 64), __shfl_xor(sum, o, 64));
+  if (lane == 0) { sm[wave] = m; ss[wave] = sum; }
+  __syncthreads();
+  if (tid == 0) {
+    float M = sm[0], S = ss[0];
+    for (int w = 1; w < 16; ++w) merge(M, S, sm[w], ss[w]);
+    lse_sh = M + logf(S);
+  }
+  for (int k = 0; k < K; ++k) {
+    float bv = tv[0]; int bi = ti[0];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { sv[wave] = bv; si[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+      float v = sv[0]; int i = si[0];
+      for (int w = 1; w < 16; ++w) if (sv[w] > v || (sv[w] == v && si[w] < i)) { v = sv[w]; i = si[w]; }
+      win_sh = i;
+      topv[(size_t)row * K + k] = v - lse_sh;
+      topi[(size_t)row * K + k] = i == INT32_MAX ? 0 : i;   // (no candidate left: NaN logits -- keep the id a valid embedding row)
+    }
+    __syncthreads();
+    if (ti[0] == win_sh) {                               // the owner pops its head
+#pragma unroll
+      for (int j = 0; j < BEAM_MAX - 1; ++j) { tv[j] = tv[j + 1]; ti[j] = ti[j + 1]; }
+      tv[BEAM_MAX - 1] = -INFINITY; ti[BEAM_MAX - 1] = INT32_MAX;
+    }
+  }
+}
+
+// one wave per utterance: rank the <= beam * K extensions (finished hypotheses stand as themselves), keep the best `beam` in order
+// (score descending, then hypothesis, then rank inside the hypothesis), and rebuild the rows' ancestry / token tables from their parents'.
+__global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x, beam = a.beam, K = a.K, base = b * beam;
+  const int n_slots = a.slots_dev ? *a.slots_dev + a.slots_off : a.n_slots;
+  __shared__ int par[BEAM_MAX], ntok[BEAM_MAX], nfin[BEAM_MAX], nlen[BEAM_MAX], nnext[BEAM_MAX];
+  __shared__ float ncum[BEAM_MAX];
+  const bool frozen_utt = !a.first && a.done[b] != 0;
+  const int r = lane / K, k = lane - r * K;
+  bool valid = r < beam && (!a.first || r == 0);
+  float score = -INFINITY; int tokv = -1, pf = 0, pl = 0, pn = 0;
+  if (valid) {
+    const int row = base + r;
+    if (a.first) { score = a.topv[(size_t)b * K + k]; tokv = a.topi[(size_t)b * K + k]; }
+    else {
+      pf = a.fin[row]; pl = a.len[row]; pn = a.next[row];
+      if (frozen_utt) { valid = k == 0; score = a.cum[row]; }
+      else if (pf) { valid = k == 0; score = a.cum[row]; }
+      else { score = a.cum[row] + a.topv[(size_t)row * K + k]; tokv = a.topi[(size_t)row * K + k]; }
+    }
+  }
+  const float sc = valid ? score : -INFINITY;
+  int rank = 0;
+  for (int j = 0; j < 64; ++j) {
+    const float sj = __shfl(sc, j, 64);
+    rank += (sj > sc || (sj == sc && j < lane)) ? 1 : 0;
+  }
+  if (frozen_utt) rank = r;                               // a finished utterance keeps its n-best list as it stands
+  if (valid && rank < beam) {
+    const bool frozen = frozen_utt || (!a.first && pf);
+    bool is_stop = false;
+    if (!frozen) for (int i = 0; i < a.n_stop; ++i) is_stop = is_stop || a.stop[i] == tokv;
+    par[rank] = r; ncum[rank] = score;
+    ntok[rank] = (frozen || is_stop) ? -1 : tokv;        // the id appended to the hypothesis (stop ids are not emitted)
+    nfin[rank] = (frozen ? pf : (is_stop ? 1 : 0));
+    nlen[rank] = pl + ((frozen || is_stop) ? 0 : 1);
+    nnext[rank] = frozen ? pn : tokv;
+  }
+  __syncthreads();
+  // tables: row r' = parent's generated-slot ancestry + the parent itself for the slot written by this pass; parent's tokens + the new id.
+  // Every pass writes that last slot, also for a finished utterance (whose rows are their own parents and still run through the decoder):
+  // the next pass's attention reads it, so it must name the row that wrote the slot, never a stale entry of the other table.
+  for (int q = 0; q < beam; ++q) {
+    const int prow = base + par[q], orow = base + q;
+    const int ncopy = n_slots - 1;
+    for (int j = lane; j < ncopy; j += 64) a.src_out[(size_t)orow * a.ld + j] = a.src_in[(size_t)prow * a.ld + j];
+    if (n_slots > 0 && lane == 0) a.src_out[(size_t)orow * a.ld + n_slots - 1] = prow;
+    const int keep = nlen[q] - (ntok[q] >= 0 ? 1 : 0);
+    for (int j = lane; j < keep; j += 64) a.tok_out[(size_t)orow * a.ld + j] = a.tok_in[(size_t)prow * a.ld + j];
+    if (ntok[q] >= 0 && lane == 0) a.tok_out[(size_t)orow * a.ld + keep] = ntok[q];
+  }
+  if (lane < beam) {
+    a.cum[base + lane] = ncum[lane]; a.fin[base + lane] = nfin[lane]; a.len[base + lane] = nlen[lane]; a.next[base + lane] = nnext[lane];
+  }
+  if (lane == 0) a.done[b] = nfin[0];
+}
+
+}  // namespace
+
+void launch_beam_topk(const float* logits, int ld, int rows, int n_valid, const float* bias, int K, float* topv, int32_t* topi, hipStream_t s) {
+  ASR_REQUIRE(K >= 1 && K <= BEAM_MAX && ld % 4 == 0, "beam_topk: K %d ld %d", K, ld);
+  hipLaunchKernelGGL(beam_topk_kernel, dim3(rows), dim3(1024), 0, s, logits, ld, n_valid, bias, K, topv, topi);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_beam_select(const BeamArgs& a, int n_utt, hipStream_t s) {
+  ASR_REQUIRE(a.beam >= 1 && a.beam <= BEAM_MAX && a.K >= 1 && a.beam * a.K <= 64, "beam_select: beam %d K %d", a.beam, a.K);
+  hipLaunchKernelGGL(beam_select_kernel, dim3(n_utt), dim3(64), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }

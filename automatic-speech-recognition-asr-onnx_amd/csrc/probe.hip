@@ -603,6 +603,109 @@ void probe_decode_attention(asr_probe_decode_attn_desc* d) {
 }
 }  // namespace
 
+namespace {
+template <typename T>
+void probe_decode_attention_beam(int rows, int beam, int H, int S, int p0, int hist, int hist_dev, const int32_t* src, int ld_src, const float* q,
+                                 const float* kv_new, float* ext, float* out, int32_t* stray, char* kernel) {
+  Tmp t;
+  const int D = H * 64;
+  ASR_REQUIRE(rows > 0 && beam >= 1 && beam <= 8 && rows % beam == 0 && H > 0 && S > 0 && p0 >= 0 && p0 <= hist && hist < S && ld_src >= hist - p0 && ld_src > 0 &&
+              src && q && kv_new && ext && out, "probe_decode_attention_beam: bad geometry");
+  for (int r = 0; r < rows; ++r)
+    for (int j = 0; j < hist - p0; ++j) {
+      const int a = src[(size_t)r * ld_src + j];
+      ASR_REQUIRE(a >= 0 && a < rows && a / beam == r / beam, "probe_decode_attention_beam: row %d slot %d names row %d outside its utterance", r, j, a);
+    }
+  auto up = [&](const float* h, size_t count) -> T* {
+    std::vector<T> v(count);
+    for (size_t i = 0; i < count; ++i) v[i] = elem_from_f32<T>(h[i]);
+    T* p = (T*)t.alloc(count * sizeof(T));
+    HIP_CHECK(hipMemcpy(p, v.data(), count * sizeof(T), hipMemcpyHostToDevice));
+    return p;
+  };
+  const size_t ext_n = (size_t)rows * 2 * H * S * 64;
+  std::vector<T> before(ext_n);
+  for (size_t i = 0; i < ext_n; ++i) before[i] = elem_from_f32<T>(ext[i]);
+  T* dext = up(ext, ext_n);
+  int32_t* dsrc = (int32_t*)t.alloc((size_t)rows * ld_src * 4);
+  HIP_CHECK(hipMemcpy(dsrc, src, (size_t)rows * ld_src * 4, hipMemcpyHostToDevice));
+  DecAttnArgs a{};
+  a.q = up(q, (size_t)rows * D); a.ld_q = D; a.q_col0 = 0;
+  a.kv_new = up(kv_new, (size_t)rows * 2 * D); a.ld_new = 2 * D; a.k_col0 = 0; a.v_col0 = D;
+  a.k_base = dext; a.v_base = dext + (size_t)H * S * 64; a.stride_b = (int64_t)2 * H * S * 64; a.stride_h = (int64_t)S * 64;
+  a.beam_src = dsrc; a.ld_src = ld_src; a.beam_p0 = p0; a.beam = beam;
+  a.n = 1; a.n_heads = H; a.causal = 1; a.max_keys = S; a.hist = hist;
+  if (hist_dev) {                       // graph-replay form: the by-value history is deliberately wrong
+    int32_t* hd = (int32_t*)t.alloc(4);
+    HIP_CHECK(hipMemcpy(hd, &hist, 4, hipMemcpyHostToDevice));
+    a.hist_dev = hd; a.hist = 0;
+  }
+  T* dout = (T*)t.alloc((size_t)rows * D * sizeof(T));
+  a.out = dout; a.ld_out = D;
+  launch_decode_attention<T>(a, rows, nullptr);
+  snprintf(kernel, 32, "%s", decode_attn_last_kernel());
+  HIP_CHECK(hipDeviceSynchronize());
+  std::vector<T> ho((size_t)rows * D), after(ext_n);
+  HIP_CHECK(hipMemcpy(ho.data(), dout, ho.size() * sizeof(T), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(after.data(), dext, ext_n * sizeof(T), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < ho.size(); ++i) out[i] = elem_to_f32(ho[i]);
+  int n_stray = 0;
+  for (size_t i = 0; i < ext_n; ++i) {
+    ext[i] = elem_to_f32(after[i]);
+    const bool own_slot = (int)((i / 64) % S) == hist;       // the one slot of every (row, K | V, head) the call writes
+    n_stray += (!own_slot && !same_bits(before[i], after[i])) ? 1 : 0;
+  }
+  if (stray) *stray = n_stray;
+}
+}  // namespace
+
+extern "C" int asr_probe_decode_attention_beam(int bf16, int rows, int beam, int H, int S, int p0, int hist, int hist_dev, const int32_t* src, int ld_src,
+                                               const float* q, const float* kv_new, float* ext, float* out, int32_t* stray, char* kernel) {
+  return asr_guard([&] {
+    ASR_REQUIRE(kernel, "probe_decode_attention_beam: null kernel buffer");
+    asr_require_device(0);
+    gemm_reload_env();
+    if (bf16) probe_decode_attention_beam<bf16_t>(rows, beam, H, S, p0, hist, hist_dev, src, ld_src, q, kv_new, ext, out, stray, kernel);
+    else probe_decode_attention_beam<float>(rows, beam, H, S, p0, hist, hist_dev, src, ld_src, q, kv_new, ext, out, stray, kernel);
+  });
+}
+
+extern "C" int asr_probe_beam_select(asr_probe_beam_select_desc* d) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d && d->n_utt > 0 && d->beam >= 1 && d->beam <= 8 && d->K >= 1 && d->beam * d->K <= 64 && d->ld > 0 && d->n_slots >= 0 && d->n_slots <= d->ld &&
+                d->n_stop >= 0 && d->topv && d->topi && d->cum && d->fin && d->len && d->next && d->done && d->src_in && d->tok_in && d->src_out && d->tok_out &&
+                (d->n_stop == 0 || d->stop), "probe_beam_select: bad descriptor");
+    asr_require_device(0);
+    Tmp t;
+    const int N = d->n_utt * d->beam;
+    for (int r = 0; r < N; ++r) ASR_REQUIRE(d->len[r] >= 0 && d->len[r] <= d->ld, "probe_beam_select: row %d length %d outside the table", r, d->len[r]);
+    auto up = [&](const void* h, size_t bytes) -> void* {
+      void* p = t.alloc(std::max(bytes, (size_t)4));
+      HIP_CHECK(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+      return p;
+    };
+    const size_t tab = (size_t)N * d->ld * 4, rows4 = (size_t)N * 4;
+    BeamArgs a{};
+    a.beam = d->beam; a.K = d->K; a.ld = d->ld; a.first = d->first; a.n_slots = d->n_slots;
+    a.topv = (const float*)up(d->topv, (size_t)(d->first ? d->n_utt : N) * d->K * 4);
+    a.topi = (const int32_t*)up(d->topi, (size_t)(d->first ? d->n_utt : N) * d->K * 4);
+    a.cum = (float*)up(d->cum, rows4); a.fin = (int32_t*)up(d->fin, rows4); a.len = (int32_t*)up(d->len, rows4); a.next = (int32_t*)up(d->next, rows4);
+    a.done = (int32_t*)up(d->done, (size_t)d->n_utt * 4);
+    a.stop = d->n_stop ? (const int32_t*)up(d->stop, (size_t)d->n_stop * 4) : nullptr; a.n_stop = d->n_stop;
+    a.src_in = (const int32_t*)up(d->src_in, tab); a.tok_in = (const int32_t*)up(d->tok_in, tab);
+    a.src_out = (int32_t*)up(d->src_out, tab); a.tok_out = (int32_t*)up(d->tok_out, tab);
+    launch_beam_select(a, d->n_utt, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(d->cum, a.cum, rows4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->fin, a.fin, rows4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->len, a.len, rows4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->next, a.next, rows4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->done, a.done, (size_t)d->n_utt * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->src_out, a.src_out, tab, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->tok_out, a.tok_out, tab, hipMemcpyDeviceToHost));
+  });
+}
+
 extern "C" int asr_probe_decode_attention(asr_probe_decode_attn_desc* d) {
   return asr_guard([&] {
     ASR_REQUIRE(d, "probe_decode_attention: null descriptor");

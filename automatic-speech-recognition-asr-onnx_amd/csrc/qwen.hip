@@ -511,140 +511,8 @@ __global__ void qw_hist_add_kernel(int32_t* __restrict__ hist, const UttPlan* __
 
 // ------------------------------------------------------------------------------------ beam search
 // Width-`beam` search over summed log-probabilities (README.md:38 names a beam mode for Qwen3-ASR; the reference ships no code for it, the
-// semantics are those of oracle/qwen_asr_oracle.py:beam_search_core). Hypotheses of utterance b are the decoder rows b * beam + r.
-constexpr int BEAM_MAX = 8;
-
-// per row: log-soft-max statistics and the K best (log-prob, id) pairs, ties -> lower id. One pass: every thread keeps a running
-// (max, sum) pair and its own sorted best-8 list; the lists merge in K rounds of a block-wide arg-max.
-__global__ __launch_bounds__(1024) void qw_beam_topk_kernel(const float* __restrict__ logits, int ld, int n_valid, int K, float* __restrict__ topv,
-                                                            int32_t* __restrict__ topi) {
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* p = logits + (size_t)row * ld;
-  float tv[BEAM_MAX]; int ti[BEAM_MAX];
-#pragma unroll
-  for (int j = 0; j < BEAM_MAX; ++j) { tv[j] = -INFINITY; ti[j] = INT32_MAX; }
-  float m = -INFINITY, sum = 0.0f;
-  for (int v0 = tid * 4; v0 < n_valid; v0 += 4096) {
-    const float4 q = *reinterpret_cast<const float4*>(p + v0);
-    const float xs[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float x = xs[e];
-      if (v0 + e >= n_valid) continue;
-      if (x > m) { sum = sum * __expf(m - x) + 1.0f; m = x; } else { sum += __expf(x - m); }
-      if (x > tv[BEAM_MAX - 1]) {
-        tv[BEAM_MAX - 1] = x; ti[BEAM_MAX - 1] = v0 + e;
-#pragma unroll
-        for (int j = BEAM_MAX - 1; j > 0; --j)
-          if (tv[j] > tv[j - 1]) { const float a = tv[j]; tv[j] = tv[j - 1]; tv[j - 1] = a; const int c = ti[j]; ti[j] = ti[j - 1]; ti[j - 1] = c; }
-      }
-    }
-  }
-  __shared__ float sm[16], ss[16], sv[16];
-  __shared__ int si[16];
-  __shared__ float lse_sh;
-  __shared__ int win_sh;
-  auto merge = [](float& m1, float& s1, float m2, float s2) {
-    const float M = fmaxf(m1, m2);
-    const float a = m1 == -INFINITY ? 0.0f : s1 * __expf(m1 - M), b = m2 == -INFINITY ? 0.0f : s2 * __expf(m2 - M);
-    m1 = M; s1 = a + b;
-  };
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) merge(m, sum, __shfl_xor(m, o, 64), __shfl_xor(sum, o, 64));
-  if (lane == 0) { sm[wave] = m; ss[wave] = sum; }
-  __syncthreads();
-  if (tid == 0) {
-    float M = sm[0], S = ss[0];
-    for (int w = 1; w < 16; ++w) merge(M, S, sm[w], ss[w]);
-    lse_sh = M + logf(S);
-  }
-  for (int k = 0; k < K; ++k) {
-    float bv = tv[0]; int bi = ti[0];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { sv[wave] = bv; si[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-      float v = sv[0]; int i = si[0];
-      for (int w = 1; w < 16; ++w) if (sv[w] > v || (sv[w] == v && si[w] < i)) { v = sv[w]; i = si[w]; }
-      win_sh = i;
-      topv[(size_t)row * K + k] = v - lse_sh;
-      topi[(size_t)row * K + k] = i;
-    }
-    __syncthreads();
-    if (ti[0] == win_sh) {                               // the owner pops its head
-#pragma unroll
-      for (int j = 0; j < BEAM_MAX - 1; ++j) { tv[j] = tv[j + 1]; ti[j] = ti[j + 1]; }
-      tv[BEAM_MAX - 1] = -INFINITY; ti[BEAM_MAX - 1] = INT32_MAX;
-    }
-  }
-}
-
-struct QwBeamArgs {
-  int beam, K, ld, first, n_slots;       // ld: row stride of the ancestry / token tables; n_slots: generated cache slots after this pass
-  const float* topv; const int32_t* topi;
-  float* cum; int32_t* fin; int32_t* len; int32_t* next; int32_t* done;
-  const int32_t* stop; int n_stop;
-  const int32_t *src_in, *tok_in; int32_t *src_out, *tok_out;
-};
-
-// one wave per utterance: rank the <= beam * K extensions (finished hypotheses stand as themselves), keep the best `beam` in order
-// (score descending, then hypothesis, then rank inside the hypothesis), and rebuild the rows' ancestry / token tables from their parents'.
-__global__ __launch_bounds__(64) void qw_beam_select_kernel(QwBeamArgs a) {
-  const int b = blockIdx.x, lane = threadIdx.x, beam = a.beam, K = a.K, base = b * beam;
-  __shared__ int par[BEAM_MAX], ntok[BEAM_MAX], nfin[BEAM_MAX], nlen[BEAM_MAX], nnext[BEAM_MAX];
-  __shared__ float ncum[BEAM_MAX];
-  const bool frozen_utt = !a.first && a.done[b] != 0;
-  const int r = lane / K, k = lane - r * K;
-  bool valid = r < beam && (!a.first || r == 0);
-  float score = -INFINITY; int tokv = -1, pf = 0, pl = 0, pn = 0;
-  if (valid) {
-    const int row = base + r;
-    if (a.first) { score = a.topv[(size_t)b * K + k]; tokv = a.topi[(size_t)b * K + k]; }
-    else {
-      pf = a.fin[row]; pl = a.len[row]; pn = a.next[row];
-      if (frozen_utt) { valid = k == 0; score = a.cum[row]; }
-      else if (pf) { valid = k == 0; score = a.cum[row]; }
-      else { score = a.cum[row] + a.topv[(size_t)row * K + k]; tokv = a.topi[(size_t)row * K + k]; }
-    }
-  }
-  const float sc = valid ? score : -INFINITY;
-  int rank = 0;
-  for (int j = 0; j < 64; ++j) {
-    const float sj = __shfl(sc, j, 64);
-    rank += (sj > sc || (sj == sc && j < lane)) ? 1 : 0;
-  }
-  if (frozen_utt) rank = r;                               // a finished utterance keeps its n-best list as it stands
-  if (valid && rank < beam) {
-    const bool frozen = frozen_utt || (!a.first && pf);
-    bool is_stop = false;
-    if (!frozen) for (int i = 0; i < a.n_stop; ++i) is_stop = is_stop || a.stop[i] == tokv;
-    par[rank] = r; ncum[rank] = score;
-    ntok[rank] = (frozen || is_stop) ? -1 : tokv;        // the id appended to the hypothesis (stop ids are not emitted)
-    nfin[rank] = (frozen ? pf : (is_stop ? 1 : 0));
-    nlen[rank] = pl + ((frozen || is_stop) ? 0 : 1);
-    nnext[rank] = frozen ? pn : tokv;
-  }
-  __syncthreads();
-  // tables: row r' = parent's generated-slot ancestry + the parent itself for the slot written by this pass; parent's tokens + the new id
-  for (int q = 0; q < beam; ++q) {
-    const int prow = base + par[q], orow = base + q;
-    const int ncopy = a.n_slots - (frozen_utt ? 0 : 1);
-    for (int j = lane; j < ncopy; j += 64) a.src_out[(size_t)orow * a.ld + j] = a.src_in[(size_t)prow * a.ld + j];
-    if (!frozen_utt && a.n_slots > 0 && lane == 0) a.src_out[(size_t)orow * a.ld + a.n_slots - 1] = prow;
-    const int keep = nlen[q] - (ntok[q] >= 0 ? 1 : 0);
-    for (int j = lane; j < keep; j += 64) a.tok_out[(size_t)orow * a.ld + j] = a.tok_in[(size_t)prow * a.ld + j];
-    if (ntok[q] >= 0 && lane == 0) a.tok_out[(size_t)orow * a.ld + keep] = ntok[q];
-  }
-  if (lane < beam) {
-    a.cum[base + lane] = ncum[lane]; a.fin[base + lane] = nfin[lane]; a.len[base + lane] = nlen[lane]; a.next[base + lane] = nnext[lane];
-  }
-  if (lane == 0) a.done[b] = nfin[0];
-}
-
+// semantics are those of oracle/qwen_asr_oracle.py:beam_search_core). Hypotheses of utterance b are the decoder rows b * beam + r. The
+// ranking kernels (launch_beam_topk / launch_beam_select) live in kernels.hip: the Whisper session ranks its hypotheses with them too.
 __global__ void qw_beam_init_kernel(const int32_t* __restrict__ hist_in, int B, int beam, int32_t* __restrict__ hist_out, int32_t* __restrict__ p0) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n < B * beam) { hist_out[n] = hist_in[n / beam]; p0[n] = hist_in[n / beam]; }
@@ -1510,10 +1378,10 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
   if (n_stop) HIP_CHECK(hipMemcpyAsync(d_bstop.ptr, stop_ids, (size_t)n_stop * 4, hipMemcpyHostToDevice, stream));
   HIP_CHECK(hipMemsetAsync(d_bdone.ptr, 0, (size_t)B * 4, stream));
   HIP_CHECK(hipMemsetAsync(d_blen.ptr, 0, (size_t)N * 4, stream));
-  hipLaunchKernelGGL(qw_beam_topk_kernel, dim3(B), dim3(1024), 0, stream, d_logits.as<float>(), vpad, c.vocab, beam, d_btopv.as<float>(), d_btopi.as<int32_t>());
+  launch_beam_topk(d_logits.as<float>(), vpad, B, c.vocab, nullptr, beam, d_btopv.as<float>(), d_btopi.as<int32_t>(), stream);
   DeviceBuffer& nxt = d_bnext;
   nxt.reserve((size_t)std::max(N, 64) * 4, stream);
-  QwBeamArgs ba{};
+  BeamArgs ba{};
   ba.beam = beam; ba.K = beam; ba.ld = ld; ba.topv = d_btopv.as<float>(); ba.topi = d_btopi.as<int32_t>();
   ba.cum = d_bcum.as<float>(); ba.fin = d_bfin.as<int32_t>(); ba.len = d_blen.as<int32_t>(); ba.done = d_bdone.as<int32_t>(); ba.next = nxt.as<int32_t>();
   ba.stop = d_bstop.as<int32_t>(); ba.n_stop = n_stop;
@@ -1522,7 +1390,7 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
     ba.first = first; ba.n_slots = n_slots;
     ba.src_in = d_bsrc[cur].as<int32_t>(); ba.tok_in = d_btok[cur].as<int32_t>();
     ba.src_out = d_bsrc[cur ^ 1].as<int32_t>(); ba.tok_out = d_btok[cur ^ 1].as<int32_t>();
-    hipLaunchKernelGGL(qw_beam_select_kernel, dim3(B), dim3(64), 0, stream, ba);
+    launch_beam_select(ba, B, stream);
     cur ^= 1;
   };
   select(1, 0);
@@ -1563,7 +1431,7 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
     P.beam_src = d_bsrc[cur].as<int32_t>();
     decoder_pass<T>(P);
     { ProfScope ps(prof, "beam_rank", stream);
-      hipLaunchKernelGGL(qw_beam_topk_kernel, dim3(N), dim3(1024), 0, stream, d_logits.as<float>(), vpad, c.vocab, beam, d_btopv.as<float>(), d_btopi.as<int32_t>());
+      launch_beam_topk(d_logits.as<float>(), vpad, N, c.vocab, nullptr, beam, d_btopv.as<float>(), d_btopi.as<int32_t>(), stream);
       select(0, t + 1); }
   }
   HIP_CHECK(hipGetLastError());

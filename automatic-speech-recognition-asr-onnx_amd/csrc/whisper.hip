@@ -20,6 +20,33 @@ namespace {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// Beam search: the prompt's self-K/V rows (positions < p0 of every layer, at most 8) from the session's cache -- the paged pool or the contiguous extents --
+// into every hypothesis row's extent, once per search. Grid (rows, layers x 2 x heads); extents [layer][row][K | V][head][S][64].
+template <typename T>
+__global__ __launch_bounds__(256) void wh_beam_prompt_kernel(const T* __restrict__ pool, const int32_t* __restrict__ ptable, int pages_per_seq,
+                                                             const T* __restrict__ kc, const T* __restrict__ vc, int max_pos, int B, int H, int p0, int beam,
+                                                             int S, T* __restrict__ ext) {
+  const int row = blockIdx.x, N = gridDim.x, lkh = blockIdx.y;   // lkh = (layer * 2 + K | V) * H + head
+  const int h = lkh % H, kv = (lkh / H) & 1, l = lkh / (2 * H), b = row / beam;
+  T* dst = ext + ((size_t)l * N + row) * 2 * H * S * 64 + ((size_t)kv * H + h) * S * 64;
+  for (int i = threadIdx.x; i < p0 * 64; i += blockDim.x) {
+    const int s = i >> 6, e = i & 63;
+    const T* src = pool ? pool + (size_t)ptable[(size_t)b * pages_per_seq + (s >> 4)] * gridDim.y * 1024 + (size_t)lkh * 1024 + (size_t)(s & 15) * 64
+                        : (kv ? vc : kc) + (((size_t)l * B + b) * H + h) * max_pos * 64 + (size_t)s * 64;
+    dst[(size_t)s * 64 + e] = src[e];
+  }
+}
+
+// one decoder pass of a beam search over its hypothesis rows (WhSession::beam_search)
+struct BeamStep {
+  int beam = 1, p0 = 0, S = 0;         // width, prompt positions, slots per row extent
+  const int32_t* src = nullptr; int ld_src = 0;
+  int32_t* hist = nullptr;             // the rows' position (all rows stand at the same one), advanced by the pass
+  float* logits = nullptr;             // [rows][vpad]
+  float* topv = nullptr; int32_t* topi = nullptr;
+  BeamArgs ba;
+};
+
 struct EncLayer { const void *wqkv, *wo, *w1, *w2; const float *bqkv, *bo, *b1, *b2; };
 struct DecLayer { const void *wqkv, *wo, *wcq, *wco, *w1, *w2; const float *bqkv, *bo, *bcq, *bco, *b1, *b2; };
 struct Dec8Layer { const unsigned char* w[6]; const float* s[6]; const unsigned char* s4[6]; };      // FP8W: bytes + per-column scales; MXFP4W: nibbles (w) + e8m0 block scales (s4)
@@ -84,21 +111,33 @@ struct WhSession : asr_session {
   std::vector<Dec8Layer> dec8;
   DeviceBuffer d_w8, d_wscale, d_wdq, d_cross8, d_cscale;
   hipGraphExec_t dec_graph = nullptr;      // the whole single-token step
+  hipGraphExec_t beam_graph[2] = {nullptr, nullptr};       // the beam-search step, one per ancestry-table parity
+  uint64_t beam_key[2] = {0, 0};
   void drop_graphs() {
     if (dec_graph) { (void)hipGraphExecDestroy(dec_graph); dec_graph = nullptr; }
+    for (auto& g : beam_graph) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
   }
+  // Beam search (asr_whisper_beam_search): hypothesis rows b * beam + r, each with its own self-K/V extent of S = prompt + max_new - 1 slots in d_bext
+  // [layer][row][K | V][head][S][64] (large-v3, 160 rows x 447 slots: 11.7 GB; kept for the next search), ancestry / token tables (double-buffered), ranking
+  // state and logits of its own: the session's pages, block table, history, ids and logits are left as the prefill left them.
+  DeviceBuffer d_bext, d_bhist, d_bsrc[2], d_btok[2], d_bcum, d_bfin, d_blen, d_bdone, d_btopv, d_btopi, d_bstop, d_bnext, d_blogits;
+  bool after_prefill = false;          // the last call on the session was a prefill (or a beam search, which leaves its state as it was)
   uint64_t dec_key = 0, dec_eager_key = 0, ws_epoch = 1;
   void* h_plan = nullptr; size_t h_plan_cap = 0;
   void* h_io = nullptr; size_t h_io_cap = 0;
+  int32_t* h_beam = nullptr; size_t h_beam_cap = 0;   // beam search's own pinned staging: [0] eos id, [1] prompt length, [16 ..) done flags
 
   ~WhSession() override {
     for (DeviceBuffer* b : {&d_plan, &d_audio, &d_mel, &d_blkmax, &d_x0, &d_h1, &d_xa, &d_xb, &d_xc, &d_h, &d_qk, &d_vt, &d_ctx,
-                            &d_ffn, &d_cross, &d_kc, &d_vc, &d_kvpool, &d_ptable, &d_ids, &d_next, &d_logits, &d_dx, &d_dqkv, &d_dtok, &d_hist, &d_save, &d_nsaved, &d_noise, &d_nsp, &d_skws, &d_skcnt, &d_colsum, &d_dlo, &d_w8, &d_wscale, &d_wdq, &d_cross8, &d_cscale, &d_ew8, &d_ewscale, &d_h8, &d_ffn8, &d_sat})
+                            &d_ffn, &d_cross, &d_kc, &d_vc, &d_kvpool, &d_ptable, &d_ids, &d_next, &d_logits, &d_dx, &d_dqkv, &d_dtok, &d_hist, &d_save, &d_nsaved, &d_noise, &d_nsp, &d_skws, &d_skcnt, &d_colsum, &d_dlo, &d_w8, &d_wscale, &d_wdq, &d_cross8, &d_cscale, &d_ew8, &d_ewscale, &d_h8, &d_ffn8, &d_sat,
+                            &d_bext, &d_bhist, &d_bsrc[0], &d_bsrc[1], &d_btok[0], &d_btok[1], &d_bcum, &d_bfin, &d_blen, &d_bdone, &d_btopv, &d_btopi, &d_bstop,
+                            &d_bnext, &d_blogits})
       b->release();
     drop_graphs();
     for (auto& kv : taps) kv.second.buf.release();
     if (h_plan) (void)hipHostFree(h_plan);
     if (h_io) (void)hipHostFree(h_io);
+    if (h_beam) (void)hipHostFree(h_beam);
     prof.release();
     arena.release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
@@ -123,8 +162,9 @@ struct WhSession : asr_session {
     return h_io;
   }
   template <typename T> void encode(const float* audio, int audio_mem, const int64_t* offs, int B, int32_t* n_pos_out);
-  template <typename T> void enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev);
+  template <typename T> void enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev, const BeamStep* bs = nullptr);
   template <typename T> void step(const int32_t* ids_host, int n, bool is_prefill, int32_t* next_out, float* logits_out);
+  template <typename T> void beam_search(int beam, int max_new, int eos_id, int32_t* tokens_out, int32_t* n_out, float* scores_out);
 };
 
 void WhSession::init() {
@@ -471,12 +511,15 @@ void WhSession::encode(const float* audio, int audio_mem, const int64_t* offs, i
 // ======================================================================================== decoder step
 // All launches of one step. `hist_dev` (device-resident history length) is what the kernels read, so the single-token
 // step is position independent and ONE captured hipGraph replays for every decode position.
+// Beam search (bs set, n = beam): the R = B * beam rows are hypotheses, one new position each (bs->hist); the self-attention follows every row's
+// ancestry through the row extents, the cross-attention reads each utterance's slab once for its n = beam rows (the prefill's form), and the head
+// ranks the rows' extensions instead of taking an arg-max.
 template <typename T>
-void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev) {
+void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev, const BeamStep* bs) {
   const auto& c = cfg;
   const int B = batch, d = c.d_model, dff = c.d_ffn, Ld = c.n_dec_layers, H = c.n_heads;
   const int R = B * n, Rp = round_up(R, 128);
-  const int32_t* hd = use_hist_dev ? d_hist.as<int32_t>() : nullptr;
+  const int32_t* hd = bs ? bs->hist : use_hist_dev ? d_hist.as<int32_t>() : nullptr;
   float* xa = d_dx.as<float>();
   float* xb = xa + (size_t)Rp * d;
   float* xc = xb + (size_t)Rp * d;
@@ -529,7 +572,7 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
   auto run_chain = [&](hipStream_t st, int ci, int b0, int nb) {
     const int r0 = b0 * n, Rc = nb * n;
     { ProfScope ps(prof, "dec_embed", st);
-      launch_embed_pos<T>(ids_dev + r0, Rc, n, hist, hd, (const T*)embed, dec_pos, d, xa + (size_t)r0 * d, st);
+      launch_embed_pos<T>(ids_dev + r0, Rc, bs ? 1 : n, hist, hd, (const T*)embed, dec_pos, d, xa + (size_t)r0 * d, st);
       if (dgm) launch_rows_to_bf16(xa + (size_t)r0 * d, xa_lo + (size_t)r0 * d, (size_t)(NC == 1 ? Rp : Rc) * d, st); }
     for (int l = 0; l < Ld; ++l) {
       const DecLayer& L = dec[l];
@@ -543,6 +586,15 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
         ProfScope ps(prof, "dec_self_attn", st);
         DecAttnArgs a;
         a.q = qkv; a.ld_q = 3 * d; a.q_col0 = 0; a.kv_new = qkv; a.ld_new = 3 * d; a.k_col0 = d; a.v_col0 = 2 * d;
+        if (bs) {
+          T* ext = d_bext.as<T>() + (size_t)l * R * 2 * H * bs->S * 64;
+          a.k_base = ext; a.v_base = ext + (size_t)H * bs->S * 64;
+          a.stride_b = (int64_t)2 * H * bs->S * 64; a.stride_h = (int64_t)bs->S * 64;
+          a.beam_src = bs->src; a.ld_src = bs->ld_src; a.beam_p0 = bs->p0; a.beam = bs->beam;
+          a.plan = nullptr; a.hist = 0; a.hist_dev = hd; a.n = 1; a.n_heads = H; a.causal = 1; a.out = ctx; a.ld_out = d;
+          a.max_keys = c.max_target_positions;
+          launch_decode_attention<T>(a, R, st);
+        } else {
         if (kv_paged) {
           a.k_base = d_kvpool.as<T>() + (size_t)(l * 2) * H * KV_PAGE * 64; a.v_base = d_kvpool.as<T>() + (size_t)(l * 2 + 1) * H * KV_PAGE * 64;
           a.page_table = d_ptable.as<int32_t>(); a.pages_per_seq = (c.max_target_positions + KV_PAGE - 1) / KV_PAGE;
@@ -555,6 +607,7 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
         a.max_keys = c.max_target_positions;
         a.b0 = b0;
         launch_decode_attention<T>(a, nb, st);
+        }
       }
       if (dgm) {
         dg(st, ci, r0, Rc, l, ctx, d, L.wo, 1, d, d, L.bo, nullptr, xa, ACT_NONE, xb, xb_lo, d);
@@ -620,17 +673,26 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
   // final LayerNorm of the LAST position of every sequence, tied proj_out, -128 suppress penalty (:663-666)
   {
     ProfScope ps(prof, "dec_logits", stream);
+    const int Ml = bs ? R : B, nl = bs ? 1 : n;           // beam search: every hypothesis row is a last position
+    float* lg = bs ? bs->logits : d_logits.as<float>();
     GemmArgs g;
-    g.W = embed; g.ldw = d; g.M = B; g.N = vpad; g.K = d; g.bias = suppress; g.out_f32 = d_logits.as<float>(); g.ld_out_f32 = vpad;
+    g.W = embed; g.ldw = d; g.M = Ml; g.N = vpad; g.K = d; g.bias = suppress; g.out_f32 = lg; g.ld_out_f32 = vpad;
     // up to 16 sequences: LayerNorm inside the weight-streaming GEMM; above, a separate LayerNorm feeds the 128 x 128 tiles (every 16-column
     // granule of the streaming kernel would re-read all B activation rows: 170 us for 32 x 51 866 x 1280 against ~45)
-    if (precision == ASR_PRECISION_BF16 && B <= 16 && d % 256 == 0) {
-      g.ln_x = xa + (size_t)(n - 1) * d; g.ld_ln_x = n * d; g.ln_gamma = dec_ln_g; g.ln_beta = dec_ln_b;
+    if (precision == ASR_PRECISION_BF16 && Ml <= 16 && d % 256 == 0) {
+      g.ln_x = xa + (size_t)(nl - 1) * d; g.ld_ln_x = nl * d; g.ln_gamma = dec_ln_g; g.ln_beta = dec_ln_b;
     } else {
-      launch_layernorm<T>(xa + (size_t)(n - 1) * d, n * d, B, d, dec_ln_g, dec_ln_b, 1e-5f, hl, d, d, stream);
+      launch_layernorm<T>(xa + (size_t)(nl - 1) * d, nl * d, Ml, d, dec_ln_g, dec_ln_b, 1e-5f, hl, d, d, stream);
       g.A = hl; g.lda = d;
     }
     gemm(g);
+    if (bs) {                              // rank the rows' extensions; the select pass writes the ids of the next step and the ancestry of this one
+      ProfScope pr(prof, "beam_rank", stream);
+      launch_beam_topk(lg, vpad, R, c.vocab, nullptr, bs->beam, bs->topv, bs->topi, stream);
+      launch_beam_select(bs->ba, B, stream);
+      launch_add_scalar(bs->hist, 1, stream);
+      return;
+    }
     const bool penalised = penalty_value != 1.0f && !sampling;
     if (penalised && !is_prefill)          // APPLY_PENALTY over the saved ids; the history is empty at the prefill (:312-325)
       launch_apply_penalty(d_logits.as<float>(), vpad, B, d_save.as<int32_t>(), c.max_target_positions, d_nsaved.as<int32_t>(),
@@ -776,6 +838,129 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
   }
 }
 
+// Beam search after a prefill (semantics of oracle/qwen_asr_oracle.py:beam_search_core, stop set {eos_id}): the first ranking reads the prefill's logits + BEGIN_SUPPRESS,
+// then every step is one decoder pass over the B * beam hypothesis rows at the same position. The prompt's K / V rows are copied once into every row's
+// extent; generated positions stay in the extent of the row that computed them and the self-attention follows each row's ancestry table, so nothing is
+// copied or re-ordered between steps. The cross-attention reads an utterance's slab once per step for all its rows. Ids, scores and tables stay on the
+// device; the host reads back the per-utterance "best hypothesis has ended" flags once per step. The step replays from a captured graph (one per table parity).
+// Output: per utterance its `beam` hypotheses best-first -- tokens_out [B][beam][max_new], n_out [B][beam], scores_out [B][beam] (nullable).
+template <typename T>
+void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_out, int32_t* n_out, float* scores_out) {
+  const auto& c = cfg;
+  ASR_REQUIRE(after_prefill && batch > 0 && hist > 0 && d_logits.ptr, "whisper_beam_search: prefill first");
+  ASR_REQUIRE(beam >= 1 && beam <= BEAM_MAX, "whisper_beam_search: beam width %d outside 1..%d", beam, BEAM_MAX);
+  ASR_REQUIRE(!sampling && penalty_value == 1.0f, "whisper_beam_search: the penalty / sampling heads do not combine with beam search");
+  ASR_REQUIRE(hist + max_new <= c.max_target_positions, "whisper_beam_search: %d prompt + %d new positions exceed max_target_positions %d", hist, max_new,
+              c.max_target_positions);
+  HIP_CHECK(hipSetDevice(device));
+  const int B = batch, N = B * beam, p0 = hist, d = c.d_model, dff = c.d_ffn, Ld = c.n_dec_layers, H = c.n_heads;
+  const int S = p0 + max_new - 1, ld = max_new;           // extent slots (positions ever written), stride of the ancestry / token tables
+  const int Rp = round_up(N, 128), Nn = std::max(N, 64);
+  const size_t eT = sizeof(T);
+  auto grow = [&](DeviceBuffer& buf, size_t bytes) { void* before = buf.ptr; buf.reserve(bytes, stream); if (buf.ptr != before) ++ws_epoch; };
+  grow(d_btopv, (size_t)Nn * BEAM_MAX * 4); grow(d_btopi, (size_t)Nn * BEAM_MAX * 4);
+  for (DeviceBuffer* q : {&d_bcum, &d_bfin, &d_blen, &d_bdone, &d_bnext}) grow(*q, (size_t)Nn * 4);
+  grow(d_bhist, 256); grow(d_bstop, 256);
+  for (int i = 0; i < 2; ++i) { grow(d_bsrc[i], (size_t)N * ld * 4); grow(d_btok[i], (size_t)N * ld * 4); }
+  grow(d_bext, (size_t)Ld * N * 2 * H * S * 64 * eT);
+  grow(d_blogits, (size_t)Rp * vpad * 4);
+  grow(d_dx, (size_t)3 * Rp * d * 4);
+  if (precision == ASR_PRECISION_BF16) grow(d_dlo, (size_t)3 * Rp * d * 2);
+  grow(d_dqkv, (size_t)Rp * (3 * d + d + d + dff + d) * eT + (size_t)Rp * d * eT);
+  const int n_stop = eos_id >= 0 ? 1 : 0;
+  // a prefill called with null outputs may still be copying from the shared staging buffer: the search starts behind it and stages through its own
+  HIP_CHECK(hipStreamSynchronize(stream));
+  const size_t stage_bytes = (size_t)(16 + std::max(B, 64)) * 4;
+  if (stage_bytes > h_beam_cap) {
+    if (h_beam) HIP_CHECK(hipHostFree(h_beam));
+    h_beam = nullptr; h_beam_cap = 0;
+    HIP_CHECK(hipHostMalloc((void**)&h_beam, stage_bytes, hipHostMallocDefault));
+    h_beam_cap = stage_bytes;
+  }
+  int32_t* hs = h_beam;
+  hs[0] = eos_id; hs[1] = p0;
+  HIP_CHECK(hipMemcpyAsync(d_bstop.ptr, hs, 4, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemcpyAsync(d_bhist.ptr, hs + 1, 4, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemsetAsync(d_bdone.ptr, 0, (size_t)B * 4, stream));
+  HIP_CHECK(hipMemsetAsync(d_blen.ptr, 0, (size_t)N * 4, stream));
+  // ---- first ranking: the prefill's logits (B rows, left in place) + BEGIN_SUPPRESS, as the arg-max head after a prefill
+  launch_beam_topk(d_logits.as<float>(), vpad, B, c.vocab, begin, beam, d_btopv.as<float>(), d_btopi.as<int32_t>(), stream);
+  BeamArgs ba{};
+  ba.beam = beam; ba.K = beam; ba.ld = ld; ba.topv = d_btopv.as<float>(); ba.topi = d_btopi.as<int32_t>();
+  ba.cum = d_bcum.as<float>(); ba.fin = d_bfin.as<int32_t>(); ba.len = d_blen.as<int32_t>(); ba.done = d_bdone.as<int32_t>(); ba.next = d_bnext.as<int32_t>();
+  ba.stop = d_bstop.as<int32_t>(); ba.n_stop = n_stop;
+  int cur = 0;
+  auto tables = [&](BeamArgs& a) {
+    a.src_in = d_bsrc[cur].as<int32_t>(); a.tok_in = d_btok[cur].as<int32_t>();
+    a.src_out = d_bsrc[cur ^ 1].as<int32_t>(); a.tok_out = d_btok[cur ^ 1].as<int32_t>();
+  };
+  ba.first = 1; ba.n_slots = 0;
+  tables(ba);
+  launch_beam_select(ba, B, stream);
+  cur ^= 1;
+  // ---- the prompt into every row's extent
+  if (max_new > 1) {
+    const int P = (c.max_target_positions + KV_PAGE - 1) / KV_PAGE;
+    const T* pool = kv_paged ? d_kvpool.as<T>() : nullptr;
+    hipLaunchKernelGGL(wh_beam_prompt_kernel<T>, dim3(N, Ld * 2 * H), dim3(256), 0, stream, pool, kv_paged ? d_ptable.as<int32_t>() : nullptr, P,
+                       kv_paged ? nullptr : d_kc.as<T>(), kv_paged ? nullptr : d_vc.as<T>(), c.max_target_positions, B, H, p0, beam, S, d_bext.as<T>());
+    HIP_CHECK(hipGetLastError());
+  }
+  BeamStep bs;
+  bs.beam = beam; bs.p0 = p0; bs.S = S; bs.ld_src = ld; bs.hist = d_bhist.as<int32_t>(); bs.logits = d_blogits.as<float>();
+  bs.topv = d_btopv.as<float>(); bs.topi = d_btopi.as<int32_t>();
+  bs.ba = ba; bs.ba.first = 0; bs.ba.slots_dev = d_bhist.as<int32_t>(); bs.ba.slots_off = 1 - p0;   // the pass at position p fills generated slot p - p0
+  const bool graphable = use_graph && !taps_enabled && !prof.enabled;
+  uint64_t key = 1469598103934665603ull;                    // everything the captured step bakes in
+  for (uint64_t v : {(uint64_t)B, (uint64_t)beam, (uint64_t)S, (uint64_t)p0, (uint64_t)ld, (uint64_t)n_stop, (uint64_t)Mpad, ws_epoch, (uint64_t)(uintptr_t)stream})
+    key = (key ^ v) * 1099511628211ull;
+  int32_t* h_done = h_beam + 16;
+  for (int t = 0; t + 1 < max_new; ++t) {
+    HIP_CHECK(hipMemcpyAsync(h_done, d_bdone.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    bool all = true;
+    for (int b = 0; b < B; ++b) all = all && h_done[b] != 0;
+    if (all) break;
+    bs.src = d_bsrc[cur].as<int32_t>();
+    tables(bs.ba);
+    if (graphable && t >= 2) {                              // (the first pass of each parity runs eagerly: lazily created workspaces exist before capture)
+      if (!beam_graph[cur] || beam_key[cur] != key) {
+        if (beam_graph[cur]) { (void)hipGraphExecDestroy(beam_graph[cur]); beam_graph[cur] = nullptr; }
+        hipGraph_t graph = nullptr;
+        HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+        try {
+          enqueue_step<T>(d_bnext.as<int32_t>(), beam, false, true, &bs);
+        } catch (...) {
+          (void)hipStreamEndCapture(stream, &graph);
+          if (graph) (void)hipGraphDestroy(graph);
+          throw;
+        }
+        HIP_CHECK(hipStreamEndCapture(stream, &graph));
+        HIP_CHECK(hipGraphInstantiate(&beam_graph[cur], graph, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(graph);
+        beam_key[cur] = key;
+      }
+      HIP_CHECK(hipGraphLaunch(beam_graph[cur], stream));
+    } else {
+      enqueue_step<T>(d_bnext.as<int32_t>(), beam, false, true, &bs);
+    }
+    cur ^= 1;
+  }
+  HIP_CHECK(hipGetLastError());
+  std::vector<int32_t> h_tok((size_t)N * ld), h_len(N);
+  std::vector<float> h_cum(N);
+  HIP_CHECK(hipMemcpyAsync(h_tok.data(), d_btok[cur].ptr, (size_t)N * ld * 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(h_len.data(), d_blen.ptr, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(h_cum.data(), d_bcum.ptr, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (prof.enabled) prof.collect();
+  for (int r = 0; r < N; ++r) {
+    n_out[r] = h_len[r];
+    if (scores_out) scores_out[r] = h_cum[r];
+    for (int j = 0; j < h_len[r] && j < max_new; ++j) tokens_out[(size_t)r * max_new + j] = h_tok[(size_t)r * ld + j];
+  }
+}
+
 }  // namespace
 
 extern "C" int asr_whisper_create(const asr_whisper_config* cfg, const void* arena, size_t arena_bytes, int arena_mem,
@@ -822,6 +1007,7 @@ extern "C" int asr_whisper_encode(asr_session* s, const float* audio, int audio_
     ASR_REQUIRE(s && s->kind == 2, "whisper_encode: not a Whisper session");
     TenantScope tenant(s);
     WhSession* w = static_cast<WhSession*>(s);
+    w->after_prefill = false;
     if (w->precision == ASR_PRECISION_BF16) w->encode<bf16_t>(audio, audio_mem, audio_offsets, batch, n_positions_out);
     else w->encode<float>(audio, audio_mem, audio_offsets, batch, n_positions_out);
   });
@@ -832,8 +1018,10 @@ extern "C" int asr_whisper_prefill(asr_session* s, const int32_t* ids, int n, in
     ASR_REQUIRE(s && s->kind == 2 && ids, "whisper_prefill: bad argument");
     TenantScope tenant(s);
     WhSession* w = static_cast<WhSession*>(s);
+    w->after_prefill = false;
     if (w->precision == ASR_PRECISION_BF16) w->step<bf16_t>(ids, n, true, next_ids_out, logits_out);
     else w->step<float>(ids, n, true, next_ids_out, logits_out);
+    w->after_prefill = true;
   });
 }
 
@@ -842,6 +1030,7 @@ extern "C" int asr_whisper_decode(asr_session* s, const int32_t* ids, int32_t* n
     ASR_REQUIRE(s && s->kind == 2, "whisper_decode: not a Whisper session");
     TenantScope tenant(s);
     WhSession* w = static_cast<WhSession*>(s);
+    w->after_prefill = false;
     if (w->precision == ASR_PRECISION_BF16) w->step<bf16_t>(ids, 1, false, next_ids_out, logits_out);
     else w->step<float>(ids, 1, false, next_ids_out, logits_out);
   });
@@ -944,6 +1133,7 @@ extern "C" int asr_whisper_generate(asr_session* s, int max_new, int eos_id, int
     TenantScope tenant(s);
     WhSession* w = static_cast<WhSession*>(s);
     ASR_REQUIRE(w->hist > 0, "whisper_generate: prefill first");
+    w->after_prefill = false;
     const int B = w->batch;
     std::vector<int32_t> cur(B);
     HIP_CHECK(hipSetDevice(w->device));
@@ -965,5 +1155,15 @@ extern "C" int asr_whisper_generate(asr_session* s, int max_new, int eos_id, int
       if (w->precision == ASR_PRECISION_BF16) w->step<bf16_t>(nullptr, 1, false, cur.data(), nullptr);
       else w->step<float>(nullptr, 1, false, cur.data(), nullptr);
     }
+  });
+}
+
+extern "C" int asr_whisper_beam_search(asr_session* s, int beam, int max_new, int eos_id, int32_t* tokens_out, int32_t* n_out, float* scores_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 2 && tokens_out && n_out && max_new >= 1, "whisper_beam_search: bad argument");
+    TenantScope tenant(s);
+    WhSession* w = static_cast<WhSession*>(s);
+    if (w->precision == ASR_PRECISION_BF16) w->beam_search<bf16_t>(beam, max_new, eos_id, tokens_out, n_out, scores_out);
+    else w->beam_search<float>(beam, max_new, eos_id, tokens_out, n_out, scores_out);
   });
 }

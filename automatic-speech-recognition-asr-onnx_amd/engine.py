@@ -320,6 +320,15 @@ class WhisperSession(_Session):
         _lib.check(_lib.load().asr_whisper_generate(self._h, max_new, eos_id, _ip(tok), _ip(n)))
         return [tok[b, :n[b]].copy() for b in range(self.batch)]
 
+    def beam_search(self, beam: int, max_new: int, eos_id: int):
+        """Width-`beam` search after a prefill -> per utterance a best-first list of (token ids, summed log-probability). Leaves the session's
+        greedy state as the prefill left it (generate() afterwards continues the same prefill)."""
+        tok = np.zeros((self.batch, beam, max_new), dtype=np.int32)
+        n = np.zeros((self.batch, beam), dtype=np.int32)
+        score = np.zeros((self.batch, beam), dtype=np.float32)
+        _lib.check(_lib.load().asr_whisper_beam_search(self._h, int(beam), int(max_new), int(eos_id), _ip(tok), _ip(n), _fp(score)))
+        return [[(tok[b, r, :n[b, r]].copy(), float(score[b, r])) for r in range(beam)] for b in range(self.batch)]
+
     def set_penalty(self, repeat_penalty: float = 1.0, penalty_range: int = 20):
         """Decode head: 1.0 = plain arg-max; else penalty-greedy (APPLY_PENALTY + GREEDY_SEARCH, the reference host's default)."""
         _lib.check(_lib.load().asr_whisper_set_penalty(self._h, C.c_float(repeat_penalty), int(penalty_range)))

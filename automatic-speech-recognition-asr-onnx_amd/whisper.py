@@ -8,7 +8,9 @@
                             ids)[<|nospeech|>] >= 0.6 => skip (:799-805, NO_SPEECH_DETECTION Export_Whisper.py:334-348)
   prefill                 = _prefill (:437-490) with [SOT, language, task, <|notimestamps|>] (:807)
   decode                  = _decode_tokens (:584-663): greedy (REPEAT_PENALTY = 1.0) or penalty-greedy (any other value; the
-                            multiplier applies once PENALTY_RANGE ids were generated, :630-632), limit MAX_SEQ_LEN - 4 (:821)
+                            multiplier applies once PENALTY_RANGE ids were generated, :630-632), limit MAX_SEQ_LEN - 4 (:821);
+                            beam_size > 1: the first hypothesis of the device beam search instead (this build's own mode: the
+                            reference has none; plain arg-max scores only, so no penalty or sampling beside it)
   windows of one file    = :745-806: stride SLIDING_WINDOW (or the window length), `ceil((len - window) / stride) + 1` windows, the
                             tail window zero-padded to the aligned length; the [SOT] probe (language, no-speech) runs on window 0
                             ONLY, a no-speech verdict aborts the whole file, later windows reuse window 0's language id; the
@@ -85,8 +87,11 @@ class WhisperTranscriber:
                  detect_language: bool = True, no_speech_detection: bool = True, no_speech_threshold: float = 0.6,
                  remove_repeats: bool = True, repeat_penalty: float = 1.0, penalty_range: int = 20,
                  use_sampling: bool = False, temperature: float = 0.8, top_k: int = 10, top_p: float = 0.95,
-                 sampling_repetition_penalty: float = 1.0, seed: int = 0):
+                 sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1):
+        if beam_size > 1 and (float(repeat_penalty) != 1.0 or use_sampling):
+            raise ValueError("beam_size > 1 does not combine with a repeat penalty or sampling")
         self.cfg, self.sess = cfg, session
+        self.beam_size = int(beam_size)
         self.suppress_tokens = list(suppress_tokens) if suppress_tokens is not None else None
         self.task_token = cfg.transcribe_id if task == "transcribe" else cfg.translate_id
         self.detect_language, self.no_speech_detection = detect_language, no_speech_detection
@@ -97,6 +102,12 @@ class WhisperTranscriber:
         self.repeat_penalty, self.penalty_range = float(repeat_penalty), int(penalty_range)
         # USE_SAMPLING / TEMPERATURE / TOP_K / TOP_P / SAMPLING_REPETITION_PENALTY (:71-75)
         self.sampling = (bool(use_sampling), float(temperature), int(top_k), float(top_p), float(sampling_repetition_penalty), int(seed))
+
+    def _continue(self, limit: int):
+        """Ids after the full-prompt prefill: greedy / penalty-greedy / sampling, or the first hypothesis of the beam search."""
+        if self.beam_size > 1:
+            return [hyps[0][0] for hyps in self.sess.beam_search(self.beam_size, limit, eos_id=self.cfg.eot_id)]
+        return self.sess.generate(limit, eos_id=self.cfg.eot_id)
 
     def transcribe(self, clips_int16: Sequence[np.ndarray], language_ids: Sequence[int] | None = None, max_new: int | None = None):
         """List of int16 mono 16 kHz clips (each <= 30 s) -> per clip dict(tokens, language_id, no_speech_prob, skipped)."""
@@ -123,7 +134,7 @@ class WhisperTranscriber:
         self.sess.set_penalty(self.repeat_penalty, self.penalty_range)
         self.sess.set_sampling(*self.sampling)
         self.sess.prefill(prompt, want_logits=False)
-        toks = self.sess.generate(limit, eos_id=cfg.eot_id) if limit > 0 else [np.zeros(0, np.int32)] * B
+        toks = self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * B
         wall = time.time() - t0
         out = []
         for b in range(B):
@@ -177,7 +188,7 @@ class WhisperTranscriber:
             self.sess.set_penalty(self.repeat_penalty, self.penalty_range)
             self.sess.set_sampling(*self.sampling)
             self.sess.prefill(prompt, want_logits=False)
-            toks = self.sess.generate(limit, eos_id=cfg.eot_id) if limit > 0 else [np.zeros(0, np.int32)] * n_win
+            toks = self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * n_win
             windows = [t.astype(int).tolist() for t in toks]
         wall = time.time() - t0
         ids = [t for w in windows for t in w]

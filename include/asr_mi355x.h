@@ -204,6 +204,17 @@ int asr_whisper_decode(asr_session* s, const int32_t* ids, int32_t* next_ids_out
  * (not emitted) -- the loop of _decode_tokens (Inference_Whisper_ONNX.py:584-663); the head is the one selected by
  * asr_whisper_set_penalty (plain arg-max by default). */
 int asr_whisper_generate(asr_session* s, int max_new, int eos_id, int32_t* tokens_out, int32_t* n_out);
+/* beam search after asr_whisper_prefill (the reference has no Whisper beam search; the rule is this build's own, the one written down in
+ * oracle/qwen_asr_oracle.py:beam_search_core, stop set {eos_id}; eos_id < 0: no stop id): width-`beam` (1..8) search over summed log-soft-max scores of
+ * the logits the greedy head sees (the -128 suppress penalty included; the first ranking adds BEGIN_SUPPRESS, as the arg-max after a prefill does), no
+ * length normalisation. A hypothesis ends at eos_id (not emitted) and then stands with its score; an utterance is finished when its best hypothesis has
+ * ended or after max_new ids. Every step is one decoder pass over the B * beam hypothesis rows: self-K/V in per-row extents of prompt + max_new - 1
+ * positions followed through each row's ancestry (device memory: layers x rows x 2 x d_model x slots x element size -- large-v3 bf16, 32 x 30 s at
+ * width 5 with 444 new ids: 11.7 GB, kept for the next search), cross-attention reading each utterance's slabs once for all of its rows. Host outputs,
+ * hypotheses best-first: tokens_out [B][beam][max_new], n_out [B][beam], scores_out [B][beam] (nullable). Errors: not right after a prefill ("prefill
+ * first"), width outside 1..8, a repeat penalty or sampling head set ("do not combine"), prompt + max_new > max_target_positions. The session's greedy
+ * state (pages, block table, history, ids, logits) is left as the prefill left it: asr_whisper_generate afterwards continues the same prefill. */
+int asr_whisper_beam_search(asr_session* s, int beam, int max_new, int eos_id, int32_t* tokens_out, int32_t* n_out, float* scores_out);
 /* decode head: repeat_penalty == 1 => ARGMAX (Export_Whisper.py:254-260); otherwise penalty-greedy = APPLY_PENALTY (:312-325)
  * + GREEDY_SEARCH (:243-251): the logits of the last penalty_range generated ids (1..64) are multiplied by repeat_penalty
  * once penalty_range ids exist (REPEAT_PENALTY / PENALTY_RANGE, Inference_Whisper_ONNX.py:78-79,630-632). The id history is kept

@@ -88,6 +88,28 @@ typedef struct asr_probe_decode_attn_desc {
   char kernel[32];         /* out: "self_wave", "cross_1pass", "cross_1pass_fp8", "general_n1", "general_n8", "general_n1_fp8", "general_n8_fp8" */
 } asr_probe_decode_attn_desc;
 int asr_probe_decode_attention(asr_probe_decode_attn_desc* d);
+/* One beam-search self-attention call ("self_beam": single-token, hypothesis rows with per-row extents and an ancestry table) through the same
+ * dispatcher. rows = utterances x beam (utterance-major), all at position hist (hist_dev = 1: read from device memory). ext [rows][2][H][S][64] holds
+ * every row's extent (K, then V; slot = position): uploaded (rounded to the element type) before the call and overwritten with the extents after it.
+ * Positions below p0 are read from the row's own extent, position p0 <= p < hist from the extent of row src[r][p - p0] (src [rows][ld_src]).
+ * q [rows][H 64], kv_new [rows][2 H 64] (k, then v), out [rows][H 64]; stray (nullable) = elements outside slot `hist` that changed;
+ * kernel (32 bytes) receives the form that ran. */
+int asr_probe_decode_attention_beam(int bf16, int rows, int beam, int H, int S, int p0, int hist, int hist_dev, const int32_t* src, int ld_src,
+                                    const float* q, const float* kv_new, float* ext, float* out, int32_t* stray, char* kernel);
+
+/* One pass of the beam-search ranking (launch_beam_select, shared by the Qwen3-ASR and Whisper searches) on host arrays. Hypotheses of utterance b
+ * are rows b * beam + r. topv / topi: the rows' K best (log-prob, id) pairs, [rows][K] ([n_utt][K] when first = 1); cum / fin / len / next [rows] and
+ * done [n_utt] are the search state, updated in place; stop [n_stop]; src_in / tok_in [rows][ld] the tables the pass reads, src_out / tok_out [rows][ld]
+ * the tables it writes (uploaded as given, so entries the pass leaves alone come back unchanged). n_slots: generated cache slots after the pass. */
+typedef struct asr_probe_beam_select_desc {
+  int32_t n_utt, beam, K, ld, first, n_slots, n_stop;
+  const float* topv; const int32_t* topi;
+  float* cum; int32_t* fin; int32_t* len; int32_t* next; int32_t* done;
+  const int32_t* stop;
+  const int32_t* src_in; const int32_t* tok_in;
+  int32_t* src_out; int32_t* tok_out;
+} asr_probe_beam_select_desc;
+int asr_probe_beam_select(asr_probe_beam_select_desc* d);
 
 /* launches per GEMM kernel family since the last reset, as "family=count;..." (host-side counters: hipGraph replays do not
  * count, so reset, run a session once on a new batch geometry, read). reset != 0 clears the counters after the read. */

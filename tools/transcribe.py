@@ -78,7 +78,7 @@ def run(a) -> dict:
             from transformers import AutoTokenizer
             tok = AutoTokenizer.from_pretrained(a.tokenizer)
         tr = _m("whisper").WhisperTranscriber(cfg, sess, suppress_tokens=ckm.whisper_suppress_tokens(cfg), detect_language=a.language == "auto",
-                                              repeat_penalty=a.repeat_penalty)
+                                              repeat_penalty=a.repeat_penalty, beam_size=a.beam)
         lang_id = None
         if a.language != "auto":
             if tok is None:
@@ -172,7 +172,7 @@ def main():
                    help="f32 = verification mode (the mode whose tokens equal the reference's); fp8w = Whisper / Qwen3-ASR, opt-in e4m3 decoder weights (Whisper: and cross-K/V); fp8mm = fp8w + encoder FFN on the FP8 matrix pipe; mxfp4w = fp8w with the Whisper decoder weights as OCP MXFP4")
     r.add_argument("--sliding-window", type=int, default=0)
     r.add_argument("--repeat-penalty", type=float, default=1.0, help="1.0 = plain greedy (the comparison default); the reference scripts default to 0.8")
-    r.add_argument("--beam", type=int, default=1)
+    r.add_argument("--beam", type=int, default=1, help="beam width (Whisper, Qwen3-ASR; 1 = greedy); > 1 takes the first hypothesis and needs --repeat-penalty 1")
     r.add_argument("--out", required=True)
     r.add_argument("--any-wav-width", dest="strict_wav", action="store_false",
                    help="accept 8 / 24 / 32-bit wav (rescaled to int16); by default only 16-bit wav is taken: the only width whose samples equal the reference's, "
