@@ -13,6 +13,12 @@ INSIDE the timed region (`audio_resident` is the same loop with the uploads left
 Rank 0 prints ONE JSON line. Random-init weights of the exact architecture, synthetic int16-range audio
 (no checkpoints / datasets exist offline).
 
+A plain run does only what the headline needs: set up, warm up, time the --steps steps, write --dump-outputs, print the line
+(metric, value, unit, ms_per_step, dtype, config, ...). --full adds every other leg after the timed steps: the same steps with the
+audio left in HBM, 200 steady steps, the per-kernel profile and roofline, two batches in flight, the CPU baselines, the parity
+spot check against the CPU oracle and the secondary figures (f32 mode, batch 1, Whisper, Paraformer streaming). The other
+workloads (--workload) always run their own legs.
+
 --dump-outputs DIR: after the timed steps, rank 0 writes what the LAST timed step returned to its caller -- the token
 ids and their counts of every utterance of the (global) batch -- as DIR/token_ids.npy [batch, max_T] and
 DIR/num_ids.npy [batch], float64 (exact for ids). Seeded weights and audio: the same arguments give the same inputs.
@@ -319,9 +325,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU per step (default 64; whisper: 32 = BASELINE.json configs[2])")
     ap.add_argument("--seconds", type=float, default=8.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="sensevoice: skip the PCIe-inclusive and batches-in-flight legs (rocprofv3 --stats runs: their overlapped launches would skew per-kernel averages)")
-    ap.add_argument("--profile-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="sensevoice: after the timed steps also run every leg beyond the headline (audio-resident and steady timings, per-kernel "
+                         "profile + roofline, batches in flight, CPU baselines, parity spot check, secondary figures); other workloads always run theirs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (sensevoice: and the parity spot check / secondary figures; those run with --full only)")
+    ap.add_argument("--no-extras", action="store_true", help="sensevoice --full: skip the PCIe-inclusive and batches-in-flight legs (rocprofv3 --stats runs: their overlapped launches would skew per-kernel averages)")
+    ap.add_argument("--profile-steps", type=int, default=3, help="steps of the per-kernel profile leg (sensevoice: with --full)")
     ap.add_argument("--workload", choices=("sensevoice", "whisper", "paraformer", "paraformer-streaming", "qwen", "mixed"), default="sensevoice",
                     help="sensevoice = BASELINE.json configs[1] (default, the headline line); whisper = large-v3 encoder + greedy decode")
     ap.add_argument("--inflight", type=int, default=1, help="whisper / qwen: also measure N batches in flight on N sessions / HIP streams")
@@ -442,6 +451,49 @@ def main():
         tok, num, slabs = last
         hyp = np.concatenate(slabs) if slabs else dp.pack_hypotheses(tok, num, max_t)      # [global batch, 1 + max_t]: count, ids
         dump_outputs(args.dump_outputs, {"token_ids": hyp[:, 1:], "num_ids": hyp[:, 0]})
+    if args.full:
+        full_legs = sensevoice_full_legs(args, cfg, eng, arena, sess, arena_dev, local_rank, offsets, lang, audio_dev, step, timed)
+
+    if rank == 0:
+        audio_s_per_step = world * B * n_samples / cfg.sample_rate
+        ms_per_step = elapsed / args.steps * 1e3
+        value = audio_s_per_step * args.steps / elapsed
+        flops = sensevoice_algorithmic_flops(cfg, lengths)
+        total_flops = sum(flops.values())                  # base classes only: the fused kernel's work is q|k|v + attention + FSMN, counted once
+        out = sensevoice_line(args, B, world, audio_s_per_step, elapsed, ms_per_step, value, total_flops, t_bcast)
+        if args.full:
+            out.update(sensevoice_full_report(args, cfg, B, n_samples, world, lengths, audio_s_per_step, ms_per_step, flops, total_flops, full_legs))
+            if world == 1 and not args.no_cpu_baseline:
+                out.update(sensevoice_checks(args, cfg, ck, sess, audio_np, audio_dev, offsets, lang, lengths, local_rank, device))
+        print(json.dumps(out))
+    if world > 1:
+        dp.barrier(device)
+        dist.destroy_process_group()
+
+
+def sensevoice_line(args, B, world, audio_s_per_step, elapsed, ms_per_step, value, total_flops, t_bcast):
+    """The keys of every sensevoice line, plain or --full: the headline and the figures derived from it without a run of their own."""
+    return {
+        "metric": "audio-sec/s, SenseVoiceSmall, 8 s @ 16 kHz chunks, batch 64 per GPU (RTF = 1/value per GPU-stream)",
+        "value": round(value, 1), "unit": "audio-s/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": f"SenseVoiceSmall bf16 (234 M params, 70 SANM blocks), batch={B} x {args.seconds:g} s per GPU, "
+                               "greedy CTC; step k's audio is resident in HBM when the step starts, batch k+1's host->device copy (pinned, copy stream) "
+                               "and every token-id download are inside the timed region",
+                   "global_batch": world * B, "audio_seconds_per_step": audio_s_per_step,
+                   "parallelism": f"dp{world} (utterance sharding, RCCL arena broadcast + hypothesis gather)"},
+        "rtf": round(elapsed / (audio_s_per_step * args.steps), 8),
+        "audio_s_per_s_per_gpu": round(value / world, 1),
+        "model_tflops_per_gpu": round(total_flops / (ms_per_step * 1e-3) / 1e12, 1),
+        "arena_broadcast_s": round(t_bcast, 4),
+    }
+
+
+def sensevoice_full_legs(args, cfg, eng, arena, sess, arena_dev, local_rank, offsets, lang, audio_dev, step, timed):
+    """--full, on every rank after the headline's timed steps: the audio-resident and steady timings, the profiled steps and two
+    batches in flight. Returns the raw figures sensevoice_full_report turns into keys of the line."""
+    import torch
     step(0, False)
     elapsed_resident, _ = timed(args.steps, False)         # same steps with the audio left in HBM (what round 1 reported as `value`)
     steady = None
@@ -479,105 +531,93 @@ def main():
         torch.cuda.synchronize()
         t_inflight = (time.perf_counter() - t1) / (2 * per)
         del sess2
+    return {"elapsed_resident": elapsed_resident, "steady": steady, "prof": prof, "t_inflight": t_inflight}
 
-    if rank == 0:
-        audio_s_per_step = world * B * n_samples / cfg.sample_rate
-        ms_per_step = elapsed / args.steps * 1e3
-        value = audio_s_per_step * args.steps / elapsed
-        flops = sensevoice_algorithmic_flops(cfg, lengths)
-        total_flops = sum(flops.values())                  # base classes only: the fused kernel's work is q|k|v + attention + FSMN, counted once
-        if "sanm_fused" in prof:      # q|k|v projection + attention + FSMN run as one kernel per (utterance, head)
-            flops["sanm_fused"] = flops["gemm_qkv"] + flops["attention"] + flops["fsmn"]
-        if "sanm_block" in prof:      # one persistent launch per SANM block: every GEMM, the attention and the FSMN of the block
-            # ... of the blocks the block kernel walks: n_enc0 .. n_blocks - 1 (the scope "sanm_block" times exactly those launches; block 0 is not in it)
-            flops["sanm_block"] = sum(sensevoice_algorithmic_flops(cfg, lengths, blocks=(cfg.n_enc0, cfg.n_blocks)).values())
-        kernels = {}
-        for name, p in sorted(prof.items(), key=lambda kv: -kv[1]["total_ms"]):
-            ms = p["total_ms"] / args.profile_steps
-            k = {"ms_per_step": round(ms, 4), "launches_per_step": p["launches"] // args.profile_steps}
-            # with the block kernel active the per-class GEMM scopes only see the first block's separate launches: no rate for those
-            covered = name in flops and not ("sanm_block" in prof and name in ("gemm_qkv", "gemm_out", "gemm_ffn1", "gemm_ffn2", "sanm_fused", "attention", "fsmn"))
-            if covered and ms > 0:
-                k["tflops"] = round(flops[name] / (ms * 1e-3) / 1e12, 1)
-            kernels[name] = k
-        if "sanm_block" in kernels:
-            dom, dom_match = ["sanm_block"], ("sanm_block8_kernel",)
-            dom_desc = ("sanm_block8_kernel (q|k|v + attention + FSMN + out-proj + FFN of a SANM block, clusters of four workgroups per window; one launch walks a "
-                        "whole run of blocks: 49 + 20 per step; csrc/sanm_block8.hip)")
-        else:
-            dom = [n for n in kernels if n.startswith("gemm_") and n != "gemm_ctc"]
-            dom_desc = ("gemm_bf16_t144 / gemm_bf16_t288w (SANM out-proj / ffn2: 144 x 128 tiles, ffn1: 288 x 256 tiles; the q|k|v projection "
-                        "runs inside sanm_qkv_attn_kernel and is listed under kernels.sanm_fused)")
-            dom_match = ("gemm_bf16_t144<", "gemm_bf16_t288w<1,")
-        gemm_ms = sum(kernels[n]["ms_per_step"] for n in dom)
-        gemm_flops = sum(flops[n] for n in dom)
-        gemm_launches = sum(kernels[n]["launches_per_step"] for n in dom)
-        achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        pmc_key = "sanm_block8_kernel" if "sanm_block" in kernels else "gemm_bf16_t144"
-        n_blocks_in_dom = cfg.n_blocks - cfg.n_enc0 if "sanm_block" in kernels else None        # blocks the block-kernel launches walk per step
-        traffic = hbm_traffic(pmc_key)
-        if traffic and n_blocks_in_dom:                       # a launch walks a run of blocks: the per-block figure is the comparable one
-            traffic["bytes_per_block"] = int(traffic["bytes_per_launch"] * gemm_launches / n_blocks_in_dom)
-        out = {
-            "metric": "audio-sec/s, SenseVoiceSmall, 8 s @ 16 kHz chunks, batch 64 per GPU (RTF = 1/value per GPU-stream)",
-            "value": round(value, 1), "unit": "audio-s/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": f"SenseVoiceSmall bf16 (234 M params, 70 SANM blocks), batch={B} x {args.seconds:g} s per GPU, "
-                                   "greedy CTC; step k's audio is resident in HBM when the step starts, batch k+1's host->device copy (pinned, copy stream) "
-                                   "and every token-id download are inside the timed region",
-                       "global_batch": world * B, "audio_seconds_per_step": audio_s_per_step,
-                       "parallelism": f"dp{world} (utterance sharding, RCCL arena broadcast + hypothesis gather)"},
-            "rtf": round(elapsed / (audio_s_per_step * args.steps), 8),
-            "audio_s_per_s_per_gpu": round(value / world, 1),
-            "audio_resident": {"audio_s_per_s_per_gpu": round(audio_s_per_step * args.steps / elapsed_resident / world, 1),
-                               "ms_per_step": round(elapsed_resident / args.steps * 1e3, 3), "what": "same steps, no uploads (audio left in HBM)"},
-            "steady": None if steady is None else {"steps": 200, "ms_per_step": round(steady / 200 * 1e3, 3),
-                                                   "audio_s_per_s_per_gpu": round(audio_s_per_step * 200 / steady / world, 1)},
-            "model_tflops_per_gpu": round(total_flops / (ms_per_step * 1e-3) / 1e12, 1),
-            "roofline": {"bound": "mfma", "kernel": dom_desc,
-                         "achieved": round(achieved, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": traffic, "pmc": mfma_util(pmc_key),
-                         "launches_per_step": gemm_launches, "avg_launch_us": round(gemm_ms * 1e3 / max(gemm_launches, 1), 2),
-                         "blocks_per_step": n_blocks_in_dom, "avg_block_us": None if not n_blocks_in_dom else round(gemm_ms * 1e3 / n_blocks_in_dom, 2),
-                         "rocprof": rocprof_avg_us(dom_match),
-                         "algorithmic_gflop_per_step": round(gemm_flops / 1e9, 1),
-                         "whole_step_frac": round(total_flops / (ms_per_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4)},
-            "kernels": kernels,
-            "inflight": None if t_inflight is None else {"batches_in_flight": 2, "audio_s_per_s_per_gpu": round(B * n_samples / cfg.sample_rate / t_inflight, 1),
-                                                         "ms_per_batch": round(t_inflight * 1e3, 3)},
-            "arena_broadcast_s": round(t_bcast, 4),
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg, ck, audio_np)
-            # spot check AT THE TIMED BATCH SIZE (the batch-64 dispatch: 288 x 256 FFN-1 / CTC tiles): CTC logits and frame arg-max of
-            # utterances 0 and B-1 tapped from the full batch, bf16 engine vs f32 oracle (CHECKER ONLY)
-            from oracle.sensevoice_oracle import SenseVoiceOracle
-            orc = SenseVoiceOracle(cfg, ck)
-            sess.taps(True)
-            sess.run_packed(None, offsets, lang, audio_device_ptr=audio_dev[0].data_ptr())
-            lg_all = sess.tap("logits")
-            rows = sess.utterance_rows(lengths)
-            sess.taps(False)
-            checks = []
-            for b in sorted({0, B - 1}):
-                st = orc.stages(audio_np[b, 0], 0)
-                r0, T = rows[b]
-                lg = lg_all[r0:r0 + T]
-                srt = np.sort(st["logits"], axis=1)
-                diff = float(np.abs(lg - st["logits"]).max())
-                safe = (srt[:, -1] - srt[:, -2]) > 2.0 * diff               # frames whose top-1 / top-2 margin exceeds twice the measured error
-                checks.append({"utterance": b, "max_abs_diff": round(diff, 4), "logit_abs_max": round(float(np.abs(st["logits"]).max()), 3),
-                               "frames": int(safe.size), "frames_with_safe_margin": int(safe.sum()),
-                               "argmax_equal_on_those": bool(np.array_equal(lg.argmax(1)[safe], st["frame_ids"][safe]))})
-            del lg_all
-            out["parity_spotcheck"] = {"what": f"CTC logits tapped from the timed batch of {B}, bf16 engine vs f32 oracle", "utterances": checks}
-            if not args.no_extras:
-                out["secondary"] = secondary_lines(cfg, ck, audio_np, local_rank, device, cpu_leg=True)
-        print(json.dumps(out))
-    if world > 1:
-        dp.barrier(device)
-        dist.destroy_process_group()
+
+def sensevoice_full_report(args, cfg, B, n_samples, world, lengths, audio_s_per_step, ms_per_step, flops, total_flops, legs):
+    """--full, rank 0: the keys of the line that come from sensevoice_full_legs (timings, kernels, roofline, batches in flight)."""
+    elapsed_resident, steady, prof, t_inflight = legs["elapsed_resident"], legs["steady"], legs["prof"], legs["t_inflight"]
+    if "sanm_fused" in prof:      # q|k|v projection + attention + FSMN run as one kernel per (utterance, head)
+        flops["sanm_fused"] = flops["gemm_qkv"] + flops["attention"] + flops["fsmn"]
+    if "sanm_block" in prof:      # one persistent launch per SANM block: every GEMM, the attention and the FSMN of the block
+        # ... of the blocks the block kernel walks: n_enc0 .. n_blocks - 1 (the scope "sanm_block" times exactly those launches; block 0 is not in it)
+        flops["sanm_block"] = sum(sensevoice_algorithmic_flops(cfg, lengths, blocks=(cfg.n_enc0, cfg.n_blocks)).values())
+    kernels = {}
+    for name, p in sorted(prof.items(), key=lambda kv: -kv[1]["total_ms"]):
+        ms = p["total_ms"] / args.profile_steps
+        k = {"ms_per_step": round(ms, 4), "launches_per_step": p["launches"] // args.profile_steps}
+        # with the block kernel active the per-class GEMM scopes only see the first block's separate launches: no rate for those
+        covered = name in flops and not ("sanm_block" in prof and name in ("gemm_qkv", "gemm_out", "gemm_ffn1", "gemm_ffn2", "sanm_fused", "attention", "fsmn"))
+        if covered and ms > 0:
+            k["tflops"] = round(flops[name] / (ms * 1e-3) / 1e12, 1)
+        kernels[name] = k
+    if "sanm_block" in kernels:
+        dom, dom_match = ["sanm_block"], ("sanm_block8_kernel",)
+        dom_desc = ("sanm_block8_kernel (q|k|v + attention + FSMN + out-proj + FFN of a SANM block, clusters of four workgroups per window; one launch walks a "
+                    "whole run of blocks: 49 + 20 per step; csrc/sanm_block8.hip)")
+    else:
+        dom = [n for n in kernels if n.startswith("gemm_") and n != "gemm_ctc"]
+        dom_desc = ("gemm_bf16_t144 / gemm_bf16_t288w (SANM out-proj / ffn2: 144 x 128 tiles, ffn1: 288 x 256 tiles; the q|k|v projection "
+                    "runs inside sanm_qkv_attn_kernel and is listed under kernels.sanm_fused)")
+        dom_match = ("gemm_bf16_t144<", "gemm_bf16_t288w<1,")
+    gemm_ms = sum(kernels[n]["ms_per_step"] for n in dom)
+    gemm_flops = sum(flops[n] for n in dom)
+    gemm_launches = sum(kernels[n]["launches_per_step"] for n in dom)
+    achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+    pmc_key = "sanm_block8_kernel" if "sanm_block" in kernels else "gemm_bf16_t144"
+    n_blocks_in_dom = cfg.n_blocks - cfg.n_enc0 if "sanm_block" in kernels else None        # blocks the block-kernel launches walk per step
+    traffic = hbm_traffic(pmc_key)
+    if traffic and n_blocks_in_dom:                       # a launch walks a run of blocks: the per-block figure is the comparable one
+        traffic["bytes_per_block"] = int(traffic["bytes_per_launch"] * gemm_launches / n_blocks_in_dom)
+    return {
+        "audio_resident": {"audio_s_per_s_per_gpu": round(audio_s_per_step * args.steps / elapsed_resident / world, 1),
+                           "ms_per_step": round(elapsed_resident / args.steps * 1e3, 3), "what": "same steps, no uploads (audio left in HBM)"},
+        "steady": None if steady is None else {"steps": 200, "ms_per_step": round(steady / 200 * 1e3, 3),
+                                               "audio_s_per_s_per_gpu": round(audio_s_per_step * 200 / steady / world, 1)},
+        "roofline": {"bound": "mfma", "kernel": dom_desc,
+                     "achieved": round(achieved, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": traffic, "pmc": mfma_util(pmc_key),
+                     "launches_per_step": gemm_launches, "avg_launch_us": round(gemm_ms * 1e3 / max(gemm_launches, 1), 2),
+                     "blocks_per_step": n_blocks_in_dom, "avg_block_us": None if not n_blocks_in_dom else round(gemm_ms * 1e3 / n_blocks_in_dom, 2),
+                     "rocprof": rocprof_avg_us(dom_match),
+                     "algorithmic_gflop_per_step": round(gemm_flops / 1e9, 1),
+                     "whole_step_frac": round(total_flops / (ms_per_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4)},
+        "kernels": kernels,
+        "inflight": None if t_inflight is None else {"batches_in_flight": 2, "audio_s_per_s_per_gpu": round(B * n_samples / cfg.sample_rate / t_inflight, 1),
+                                                     "ms_per_batch": round(t_inflight * 1e3, 3)},
+    }
+
+
+def sensevoice_checks(args, cfg, ck, sess, audio_np, audio_dev, offsets, lang, lengths, local_rank, device):
+    """--full, rank 0 of a one-GPU run: the CPU baselines, the parity spot check against the CPU oracle and the secondary figures."""
+    B = audio_np.shape[0]
+    out = {}
+    out["cpu_baseline"] = cpu_baseline(cfg, ck, audio_np)
+    # spot check AT THE TIMED BATCH SIZE (the batch-64 dispatch: 288 x 256 FFN-1 / CTC tiles): CTC logits and frame arg-max of
+    # utterances 0 and B-1 tapped from the full batch, bf16 engine vs f32 oracle (CHECKER ONLY)
+    from oracle.sensevoice_oracle import SenseVoiceOracle
+    orc = SenseVoiceOracle(cfg, ck)
+    sess.taps(True)
+    sess.run_packed(None, offsets, lang, audio_device_ptr=audio_dev[0].data_ptr())
+    lg_all = sess.tap("logits")
+    rows = sess.utterance_rows(lengths)
+    sess.taps(False)
+    checks = []
+    for b in sorted({0, B - 1}):
+        st = orc.stages(audio_np[b, 0], 0)
+        r0, T = rows[b]
+        lg = lg_all[r0:r0 + T]
+        srt = np.sort(st["logits"], axis=1)
+        diff = float(np.abs(lg - st["logits"]).max())
+        safe = (srt[:, -1] - srt[:, -2]) > 2.0 * diff               # frames whose top-1 / top-2 margin exceeds twice the measured error
+        checks.append({"utterance": b, "max_abs_diff": round(diff, 4), "logit_abs_max": round(float(np.abs(st["logits"]).max()), 3),
+                       "frames": int(safe.size), "frames_with_safe_margin": int(safe.sum()),
+                       "argmax_equal_on_those": bool(np.array_equal(lg.argmax(1)[safe], st["frame_ids"][safe]))})
+    del lg_all
+    out["parity_spotcheck"] = {"what": f"CTC logits tapped from the timed batch of {B}, bf16 engine vs f32 oracle", "utterances": checks}
+    if not args.no_extras:
+        out["secondary"] = secondary_lines(cfg, ck, audio_np, local_rank, device, cpu_leg=True)
+    return out
 
 
 def secondary_lines(cfg, ck, audio_np, local_rank, device, cpu_leg=False):

@@ -63,6 +63,30 @@ def test_block_kernel_numerator_is_a_known_answer():
         assert abs(walked[k] + block0[k] - whole[k]) < 1e-3 * whole[k]
 
 
+def test_full_report_prices_the_profiled_block_kernel():
+    """bench.py --full: the keys sensevoice_full_report adds to the line, from a profile of two block-kernel launches of 2.864 ms per step
+    (the r06 headline's sanm_block scope) over the 3 982.8 GFLOP those launches walk. The line of a plain run (sensevoice_line alone)
+    carries the headline and none of the keys --full adds."""
+    import argparse
+    import importlib
+    cfg = importlib.import_module("automatic-speech-recognition-asr-onnx_amd.config").SenseVoiceConfig()
+    lengths = [128000] * 64
+    flops = bench.sensevoice_algorithmic_flops(cfg, lengths)
+    prof = {"sanm_block": {"total_ms": 3 * 5.7295, "launches": 6}, "gemm_ctc": {"total_ms": 3 * 0.1989, "launches": 3}}
+    legs = {"elapsed_resident": 20 * 6.4e-3, "steady": None, "prof": prof, "t_inflight": 6.2e-3}
+    args = argparse.Namespace(steps=20, profile_steps=3)
+    rep = bench.sensevoice_full_report(args, cfg, 64, 128000, 1, lengths, 512.0, 6.481, flops, sum(flops.values()), legs)
+    assert set(rep) == {"audio_resident", "steady", "roofline", "kernels", "inflight"} and rep["steady"] is None
+    assert rep["kernels"]["sanm_block"] == {"ms_per_step": 5.7295, "launches_per_step": 2, "tflops": 695.1}
+    assert rep["roofline"]["achieved"] == 695.1 and rep["roofline"]["launches_per_step"] == 2 and rep["roofline"]["blocks_per_step"] == 69
+    assert rep["audio_resident"]["ms_per_step"] == 6.4 and rep["inflight"]["ms_per_batch"] == 6.2
+    args = argparse.Namespace(steps=20, warmup=5, seconds=8.0)
+    line = bench.sensevoice_line(args, 64, 1, 512.0, 20 * 6.481e-3, 6.481, 512.0 / 6.481e-3, sum(flops.values()), 0.05)
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"} <= set(line)
+    assert line["value"] == round(512.0 / 6.481e-3, 1) and line["ms_per_step"] == 6.481 and line["unit"] == "audio-s/s" and line["dtype"] == "bf16"
+    assert not set(line) & (set(rep) | {"cpu_baseline", "parity_spotcheck", "secondary"})
+
+
 def test_dump_outputs_writes_float64_npy_files_within_the_bound(tmp_path):
     tok = np.arange(64 * 137, dtype=np.int32).reshape(64, 137)
     num = np.full(64, 137, np.int32)

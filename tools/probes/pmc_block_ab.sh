@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/pmcab
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-B="python $R/bench.py --steps 3 --warmup 1 --profile-steps 1 --no-cpu-baseline --no-extras"
+B="python $R/bench.py --full --steps 3 --warmup 1 --profile-steps 1 --no-cpu-baseline --no-extras"
 for v in base:0:0 plain:4:0 scatter:0:1; do
   name=${v%%:*}; rest=${v#*:}; opt=${rest%%:*}; sc=${rest#*:}
   for c in FETCH_SIZE WRITE_SIZE; do

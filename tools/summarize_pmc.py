@@ -15,7 +15,7 @@ for kind, key in (("fetch", "fetch_kb_raw"), ("write", "write_kb")):
             agg[k][key] += float(r["Counter_Value"])
             if kind == "fetch":
                 agg[k]["launches"] += 1
-out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 3 --warmup 1 --profile-steps 1",
+out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --full --steps 3 --warmup 1 --profile-steps 1",
        "correction": "fetch bytes = 2 x FETCH_SIZE (gfx950 counts 128-B requests at 64 B); write bytes = WRITE_SIZE; both reported in KiB by rocprofv3",
        "kernels": {}}
 for k, v in sorted(agg.items(), key=lambda kv: -(2 * kv[1]["fetch_kb_raw"] + kv[1]["write_kb"])):

@@ -20,7 +20,7 @@ for r in csv.DictReader(open(f)):
     seen[cls].add(r["Dispatch_Id"])
 CUS, SIMDS, XCDS = 256, 4, 8
 out = {"source": "rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS "
-                 "SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE --kernel-trace -- python bench.py --steps 3 --warmup 1 --profile-steps 1 --no-cpu-baseline",
+                 "SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE --kernel-trace -- python bench.py --full --steps 3 --warmup 1 --profile-steps 1 --no-cpu-baseline",
        "formulas": {"mfma_util": "SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs * 256 CUs * 4 SIMDs); kernels run serialised and ~10 % slower under counter collection", "wave shares": "X / SQ_WAVE_CYCLES",
                     "lds_bank_conflict_per_cu_cycle": "SQ_LDS_BANK_CONFLICT / (GPU cycles * 256 CUs): extra LDS cycles lost to bank conflicts per CU-cycle"},
        "kernels": {}}
