@@ -47,7 +47,7 @@ class QwenConfigC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "sample_rate", "n_mels", "nfft", "hop_length", "enc_d", "enc_heads", "enc_ffn", "n_enc_layers", "conv_channels", "n_window",
         "n_window_infer", "max_source_positions", "d_model", "n_heads", "n_kv_heads", "d_head", "d_ffn", "n_layers", "vocab", "max_seq_len",
-        "max_audio_len")] + [("rms_eps", C.c_float), ("rope_theta", C.c_float), ("reserved", C.c_int32 * 9)]
+        "max_audio_len")] + [("rms_eps", C.c_float), ("rope_theta", C.c_float), ("classify_num", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
 # name -> (restype, argtypes); every symbol include/asr_mi355x.h declares
@@ -93,6 +93,7 @@ SIGNATURES = {
     "asr_qwen_track_history": (_i, [_vp, _i]),
     "asr_qwen_set_sampling": (_i, [_vp, _i, C.c_float, _i, C.c_float, C.c_float, C.c_uint64]),
     "asr_qwen_set_sampling_noise": (_i, [_vp, _fp, _i]),
+    "asr_qwen_align": (_i, [_vp, _vp, _i, _lp, _i, _ip, _ip, _ip, _ip, C.c_int32, _ip, _ip, C.c_int64, _fp, _ip]),
     "asr_mem_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "asr_mem_free": (_i, [_i, _vp]),
     "asr_mem_copy": (_i, [_i, _vp, _vp, _sz, _i]),

@@ -479,6 +479,21 @@ def build_paraformer_arena(cfg, ck: dict, precision: int = PRECISION_BF16, strea
 
 # =========================================================================== Qwen3-ASR
 def build_qwen_asr_arena(cfg, ck: dict, precision: int = PRECISION_BF16) -> np.ndarray:
+    return _build_qwen_arena(cfg, ck, precision, 0)
+
+
+def build_qwen_aligner_arena(cfg, ck: dict, classify_num: int, precision: int = PRECISION_BF16) -> np.ndarray:
+    """Qwen3-ForcedAligner arena: the Qwen3-ASR folds with `dec.lm_head` = the classify_num-row timestamp head (zero rows up to a
+    multiple of 128) and the rotary table rounded through f16, as FORCED_ALIGNER_ROTARY_MASK stores it (Export_Qwen_ForcedAligner.py:855-880).
+    bf16 or f32 weights only."""
+    if precision not in (PRECISION_BF16, PRECISION_F32):
+        raise ValueError(f"the forced aligner takes bf16 or f32 weights (precision {precision}: low-bit aligner weights are not supported)")
+    if not classify_num > 0 or np.asarray(ck["thinker.lm_head.weight"]).shape != (classify_num, cfg.d_model):
+        raise ValueError(f"thinker.lm_head.weight must be ({classify_num}, {cfg.d_model}), got {np.asarray(ck['thinker.lm_head.weight']).shape}")
+    return _build_qwen_arena(cfg, ck, precision, int(classify_num))
+
+
+def _build_qwen_arena(cfg, ck: dict, precision: int, classify_num: int) -> np.ndarray:
     """Fold an HF-layout Qwen3-ASR checkpoint (thinker.audio_tower.* / thinker.model.* / thinker.lm_head.weight) into the engine
     arena. Folds follow the exporter: encoder LayerNorm affines into q|k|v / fc1 / proj1 and d^-1/4 on q and k
     (Export_Qwen_ASR.py:381-398); decoder RMSNorm weights into q|k|v and gate|up, d^-1/4 into the q / k norm weights (:1141-1190).
@@ -542,13 +557,15 @@ def build_qwen_asr_arena(cfg, ck: dict, precision: int = PRECISION_BF16) -> np.n
     emb = np.zeros((vpad, d), dtype=np.float32)
     emb[:cfg.vocab] = ck[t + "embed_tokens.weight"]
     w.weight("dec.embed", emb, precision)
-    head = np.zeros((vpad, d), dtype=np.float32)
-    head[:cfg.vocab] = ck["thinker.lm_head.weight"]
+    rows = classify_num if classify_num else cfg.vocab
+    head = np.zeros(((rows + 127) // 128 * 128, d), dtype=np.float32)
+    head[:rows] = ck["thinker.lm_head.weight"]
     w.weight("dec.lm_head", head, precision)
-    # rotary table [position][cos | sin] in f32, like the exporter's precomputed cos / sin buffers (:933-960)
+    # rotary table [position][cos | sin] in f32, like the exporter's precomputed cos / sin buffers (:933-960); the aligner's are f16 values
     inv_freq = (1.0 / (cfg.rope_theta ** (np.arange(0, cfg.d_head, 2, dtype=np.float32) / cfg.d_head))).astype(np.float32)
     theta = np.arange(cfg.max_seq_len, dtype=np.float32)[:, None] * inv_freq[None, :]
-    w.add("dec.rope", np.concatenate([np.cos(theta), np.sin(theta)], 1).astype(np.float32), DT_F32)
+    rope = np.concatenate([np.cos(theta), np.sin(theta)], 1).astype(np.float32)
+    w.add("dec.rope", rope.astype(np.float16).astype(np.float32) if classify_num else rope, DT_F32)
     w.add("dec.final_norm", f32(ck[t + "norm.weight"]), DT_F32)
     sc = np.float32(float(cfg.d_head ** -0.25))
     for i in range(cfg.n_layers):

@@ -319,3 +319,12 @@ def synth_qwen_asr_checkpoint(cfg, seed: int = 0) -> dict:
     ck[t + "norm.weight"] = (1.0 + 0.1 * rng.standard_normal((h,), dtype=np.float32)).astype(np.float32)
     ck["thinker.lm_head.weight"] = _lin(rng, cfg.vocab, h, bias=False)[0]
     return ck
+
+
+def synth_qwen_aligner_checkpoint(cfg, seed: int = 0) -> dict:
+    """Qwen3-ForcedAligner-shaped checkpoint: the Qwen3-ASR synth with `thinker.lm_head.weight` replaced by a classify_num x d_model
+    timestamp head (Export_Qwen_ForcedAligner.py:546), drawn from its own stream so the rest matches synth_qwen_asr_checkpoint(seed)."""
+    ck = synth_qwen_asr_checkpoint(cfg, seed)
+    rng = np.random.default_rng(seed + 0x5A11)
+    ck["thinker.lm_head.weight"] = _lin(rng, cfg.classify_num, cfg.d_model, bias=False)[0]
+    return ck

@@ -245,3 +245,46 @@ def qwen_asr_mid() -> QwenAsrConfig:
     widths the weight-streaming GEMM's fused RMSNorm accepts (d_model % 256 == 0)."""
     return QwenAsrConfig(enc_d=256, enc_heads=4, enc_ffn=512, n_enc_layers=2, conv_channels=48, n_window_infer=800, d_model=256, n_heads=4,
                          n_kv_heads=2, d_head=128, d_ffn=512, n_layers=3, vocab=1000, max_seq_len=512)
+
+
+# =============================================================================== Qwen3-ForcedAligner
+@dataclass(frozen=True)
+class QwenAlignerConfig(QwenAsrConfig):
+    """Qwen3-ForcedAligner (Qwen_ForcedAligner/Export_Qwen_ForcedAligner.py): the Qwen3-ASR audio tower and Qwen3 decoder with a
+    `classify_num`-bucket timestamp classifier (:531-586) in place of the vocabulary LM head; one non-autoregressive pass over
+    [<|audio_start|> | audio | <|audio_end|> | words with <timestamp> slots] (MAX_SEQ_LEN 1024, 30 s of audio, :74-101)."""
+    classify_num: int = 5000
+    timestamp_segment_ms: int = 80           # one bucket = 80 ms (_MODEL_TIMESTAMP_SEGMENT_MS)
+    timestamp_tokens_per_word: int = 2       # start and end slot after every word (_MODEL_TIMESTAMP_TOKENS_PER_WORD)
+
+
+def qwen_aligner_from_hf(config: dict, max_seq_len: int = 1024, max_audio_len: int = 480000) -> QwenAlignerConfig:
+    """Geometry read from the checkpoint's Hugging Face config.json (thinker_config.audio_config / text_config / classify_num, the fields
+    Export_Qwen_ForcedAligner.py:1126-1146 reads)."""
+    th = config.get("thinker_config", config)
+    a, t = th["audio_config"], th["text_config"]
+    return QwenAlignerConfig(enc_d=int(a["d_model"]), enc_heads=int(a["encoder_attention_heads"]), enc_ffn=int(a["encoder_ffn_dim"]),
+                             n_enc_layers=int(a["encoder_layers"]), conv_channels=int(a["downsample_hidden_size"]), n_window=int(a["n_window"]),
+                             n_window_infer=int(a["n_window_infer"]), max_source_positions=int(a["max_source_positions"]),
+                             d_model=int(t["hidden_size"]), n_heads=int(t["num_attention_heads"]), n_kv_heads=int(t["num_key_value_heads"]),
+                             d_head=int(t.get("head_dim", int(t["hidden_size"]) // int(t["num_attention_heads"]))), d_ffn=int(t["intermediate_size"]),
+                             n_layers=int(t["num_hidden_layers"]), vocab=int(t["vocab_size"]), rms_eps=float(t["rms_norm_eps"]),
+                             rope_theta=float(t.get("rope_theta", (t.get("rope_parameters") or {}).get("rope_theta", 1000000.0))),
+                             classify_num=int(th.get("classify_num", config.get("classify_num", 5000))), max_seq_len=max_seq_len,
+                             max_audio_len=max_audio_len)
+
+
+def qwen_aligner_0p6b(hf_config: dict | None = None) -> QwenAlignerConfig:
+    """Qwen3-ForcedAligner-0.6B. With the checkpoint's config.json (parsed) the shape is read from it (qwen_aligner_from_hf); without
+    one, the Qwen3-ASR-0.6B thinker geometry it is built on and the exporter's default of 5000 buckets. tools/convert_checkpoint.py
+    infers every dimension from the tensors instead."""
+    if hf_config is not None:
+        return qwen_aligner_from_hf(hf_config)
+    return QwenAlignerConfig()
+
+
+def qwen_aligner_tiny() -> QwenAlignerConfig:
+    """Test geometry: qwen_asr_tiny's stacks with a 300-bucket head (not a multiple of 128: the padded rows are exercised) and the
+    reference's 1024-position prompt limit."""
+    return QwenAlignerConfig(enc_d=128, enc_heads=2, enc_ffn=256, n_enc_layers=2, conv_channels=32, n_window_infer=400, d_model=128, n_heads=2,
+                             n_kv_heads=1, d_head=128, d_ffn=256, n_layers=2, vocab=600, max_seq_len=1024, classify_num=300)

@@ -509,6 +509,53 @@ __global__ void qw_hist_add_kernel(int32_t* __restrict__ hist, const UttPlan* __
   if (b < B) hist[b] = min(hist[b] + plan[b].T, cap);
 }
 
+// ------------------------------------------------------------------------------------ forced-aligner head
+// Row selection of asr_qwen_align (Inference_Qwen_ForcedAligner_ONNX.py:565-567 gathers the positions whose prompt id is <timestamp>): one workgroup
+// per utterance over its prompt rows [row_off, row_off + T) of the packed decoder layout; `tid` < 0 selects every position (the graph's output_ids).
+__device__ __forceinline__ bool qw_slot_hit(const int32_t* src, int row, int tid) { return tid < 0 || src[row] == tid; }
+
+__global__ __launch_bounds__(256) void qw_slot_count_kernel(const int32_t* __restrict__ src, const UttPlan* __restrict__ plan, int tid, int32_t* __restrict__ cnt) {
+  __shared__ int total;
+  const UttPlan p = plan[blockIdx.x];
+  if (threadIdx.x == 0) total = 0;
+  __syncthreads();
+  int n = 0;
+  for (int t = threadIdx.x; t < p.T; t += 256) n += qw_slot_hit(src, p.row_off + t, tid) ? 1 : 0;
+  atomicAdd(&total, n);
+  __syncthreads();
+  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
+}
+
+// utterance b's slots go to rows[off[b] ...] in position order, off[b] = sum of the counts before it; writes stop at `cap` (the host's count)
+__global__ __launch_bounds__(256) void qw_slot_compact_kernel(const int32_t* __restrict__ src, const UttPlan* __restrict__ plan, int tid,
+                                                              const int32_t* __restrict__ cnt, int B, int cap, int32_t* __restrict__ off,
+                                                              int32_t* __restrict__ rows) {
+  __shared__ int base_sh, wave_n[4];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) base_sh = 0;
+  __syncthreads();
+  int s = 0;
+  for (int i = threadIdx.x; i < b; i += 256) s += cnt[i];
+  atomicAdd(&base_sh, s);
+  __syncthreads();
+  int base = base_sh;
+  if (threadIdx.x == 0) { off[b] = base; if (b == B - 1) off[B] = base + cnt[b]; }
+  const UttPlan p = plan[b];
+  for (int t0 = 0; t0 < p.T; t0 += 256) {
+    const int t = t0 + threadIdx.x;
+    const bool hit = t < p.T && qw_slot_hit(src, p.row_off + t, tid);
+    const unsigned long long m = __ballot(hit);
+    if (lane == 0) wave_n[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < wave; ++w) before += wave_n[w];
+    const int at = base + before + __popcll(m & ((1ull << lane) - 1ull));
+    if (hit && at < cap) rows[at] = p.row_off + t;
+    base += wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+    __syncthreads();                                     // (wave_n is rewritten by the next block of rows)
+  }
+}
+
 // ------------------------------------------------------------------------------------ beam search
 // Width-`beam` search over summed log-probabilities (README.md:38 names a beam mode for Qwen3-ASR; the reference ships no code for it, the
 // semantics are those of oracle/qwen_asr_oracle.py:beam_search_core). Hypotheses of utterance b are the decoder rows b * beam + r. The
@@ -530,11 +577,15 @@ struct DecPass {
   const int32_t *qb_utt = nullptr, *qb_q0 = nullptr; int n_qb = 0, qt = 0, nw = 0, max_T = 0, ld_vt = 0;
   // beam search: the rows are hypotheses with their own cache (slot stride S), history counters and generated-slot ancestry table
   void *kc = nullptr, *vc = nullptr; int S = 0; int32_t* hist = nullptr; const int32_t *beam_src = nullptr, *beam_p0 = nullptr; int ld_src = 0, beam = 1;
+  bool head = true;        // false: stop after the last layer (the forced aligner runs its own head on selected rows)
 };
+
+// asr_qwen_align's head request: row selection + host outputs
+struct AlignReq { int32_t tid = -1; int32_t* slot_off = nullptr; int32_t* buckets = nullptr; int64_t cap = 0; float* logits = nullptr; };
 
 struct QwSession : asr_session {
   asr_qwen_config cfg;
-  int vpad = 0, cpad = 0, n_bin_tiles = 0, n_kchunks = 0, chunk = 0, cpw = 0, rpw = 0, t_tok = 13;
+  int vpad = 0, hpad = 0, cpad = 0, n_bin_tiles = 0, n_kchunks = 0, chunk = 0, cpw = 0, rpw = 0, t_tok = 13;
   std::vector<QwEncLayer> enc;
   std::vector<QwDecLayer> dec;
   const float *dft = nullptr, *melp = nullptr, *conv1_b = nullptr, *conv2_b = nullptr, *conv3_b = nullptr, *enc_pos = nullptr,
@@ -582,6 +633,7 @@ struct QwSession : asr_session {
   bool sampling = false, noise_armed = false; float temperature = 0.8f, top_p = 0.95f, samp_rep_penalty = 1.0f; int top_k = 10; uint64_t samp_seed = 0;
   uint64_t head_epoch = 0;
   DeviceBuffer d_save, d_nsaved, d_noise;
+  DeviceBuffer d_sel, d_amax_v, d_amax_i, d_bucket;      // forced-aligner head: counts / offsets / rows, arg-max partials, buckets
   DeviceBuffer d_bkc, d_bvc, d_bhist, d_bp0, d_bplan, d_bsrc[2], d_btok[2], d_bcum, d_bfin, d_blen, d_bdone, d_btopv, d_btopi, d_bstop, d_bnext;   // beam search state
   hipGraphExec_t dec_graph = nullptr; uint64_t dec_key = 0, dec_eager_key = 0;
   void* h_plan = nullptr; size_t h_plan_cap = 0;
@@ -591,7 +643,7 @@ struct QwSession : asr_session {
   ~QwSession() override {
     for (DeviceBuffer* b : {&d_plan, &d_audio, &d_mel, &d_blkmax, &d_feat, &d_col, &d_c1, &d_c2, &d_c3, &d_xa, &d_xb, &d_h, &d_qk, &d_vt, &d_ctx,
                             &d_ffn, &d_aud_out, &d_dplan, &d_x, &d_x2, &d_dh, &d_qkv, &d_q, &d_dctx, &d_act, &d_last, &d_logits, &d_next,
-                            &d_kc, &d_vc, &d_kvtab, &d_hist, &d_stepplan, &d_skws, &d_skcnt, &d_vt2, &d_krows, &d_xlo, &d_x2lo, &d_save, &d_nsaved, &d_noise, &d_bkc, &d_bvc, &d_bhist, &d_bp0, &d_bplan, &d_bsrc[0], &d_bsrc[1], &d_btok[0], &d_btok[1], &d_bcum, &d_bfin, &d_blen, &d_bdone, &d_btopv, &d_btopi, &d_bstop, &d_bnext, &d_w8, &d_wscale, &d_wdq})
+                            &d_kc, &d_vc, &d_kvtab, &d_hist, &d_stepplan, &d_skws, &d_skcnt, &d_vt2, &d_krows, &d_xlo, &d_x2lo, &d_save, &d_nsaved, &d_noise, &d_sel, &d_amax_v, &d_amax_i, &d_bucket, &d_bkc, &d_bvc, &d_bhist, &d_bp0, &d_bplan, &d_bsrc[0], &d_bsrc[1], &d_btok[0], &d_btok[1], &d_bcum, &d_bfin, &d_blen, &d_bdone, &d_btopv, &d_btopi, &d_bstop, &d_bnext, &d_w8, &d_wscale, &d_wdq})
       b->release();
     for (auto& kv : taps) kv.second.buf.release();
     if (dec_graph) (void)hipGraphExecDestroy(dec_graph);
@@ -619,8 +671,11 @@ struct QwSession : asr_session {
     return p;
   }
   void init();
+  bool aligner() const { return cfg.classify_num > 0; }
   template <typename T> void prefill(const float* audio, int audio_mem, const int64_t* offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
-                                     const int32_t* post_ids, const int32_t* post_off, int32_t* next_out, float* logits_out, int32_t* ids_len_out);
+                                     const int32_t* post_ids, const int32_t* post_off, int32_t* next_out, float* logits_out, int32_t* ids_len_out,
+                                     const AlignReq* al = nullptr);
+  template <typename T> void align_head(int B, const UttPlan* ddp, const int32_t* d_src, int n_sel, const AlignReq& al);
   template <typename T> void decoder_pass(const DecPass& P);
   template <typename T> void logits_head(const DecPass& P);
   template <typename T> void step(const int32_t* ids_host, int32_t* next_out, float* logits_out);
@@ -640,6 +695,8 @@ void QwSession::init() {
   rpw = round_up(cpw * t_tok, 16);
   ASR_REQUIRE(cpw >= 1 && rpw <= 1024, "qwen: bad attention window");
   vpad = round_up(c.vocab, 128);
+  ASR_REQUIRE(c.classify_num >= 0, "qwen: classify_num %d", c.classify_num);
+  hpad = aligner() ? round_up(c.classify_num, 128) : vpad;   // rows of dec.lm_head: the vocabulary, or the aligner's timestamp buckets
   cpad = round_up(c.conv_channels, 128);
   n_bin_tiles = (c.nfft / 2 + 1 + 15) / 16;
   n_kchunks = c.nfft / 16;
@@ -663,7 +720,7 @@ void QwSession::init() {
   proj1_w = W("enc.proj1_w", {de, de});   proj1_b = F("enc.proj1_b", {de});
   proj2_w = W("enc.proj2_w", {d, de});    proj2_b = F("enc.proj2_b", {d});
   embed = W("dec.embed", {vpad, d});
-  lm_head = W("dec.lm_head", {vpad, d});
+  lm_head = W("dec.lm_head", {hpad, d});
   rope = F("dec.rope", {c.max_seq_len, c.d_head});             // [position][cos(64) | sin(64)] (ROTARY_MASK_PREFILL tables, :933-1002)
   final_norm = F("dec.final_norm", {d});
   dec.resize(c.n_layers);
@@ -942,7 +999,7 @@ void QwSession::decoder_pass(const DecPass& P) {
       bytes_of(g2, i, 3);
       gemm(g2); }
   }
-  logits_head<T>(P);
+  if (P.head) logits_head<T>(P);
 }
 
 // final RMSNorm (learned weight) of every sequence's last row, lm_head (:1331-1335), decode head
@@ -1001,7 +1058,8 @@ void QwSession::finish(int B, int32_t* next_out, float* logits_out, bool sync) {
 
 template <typename T>
 void QwSession::prefill(const float* audio, int audio_mem, const int64_t* offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
-                        const int32_t* post_ids, const int32_t* post_off, int32_t* next_out, float* logits_out, int32_t* ids_len_out) {
+                        const int32_t* post_ids, const int32_t* post_off, int32_t* next_out, float* logits_out, int32_t* ids_len_out,
+                        const AlignReq* al) {
   const auto& c = cfg;
   ASR_REQUIRE(audio && offs && B >= 1 && pre_off && post_off, "qwen_prefill: bad argument");
   HIP_CHECK(hipSetDevice(device));
@@ -1046,13 +1104,20 @@ void QwSession::prefill(const float* audio, int audio_mem, const int64_t* offs, 
   // decoder prompt rows
   std::vector<int> ids_len(B), drow0(B);
   int rows_d = 0;
+  int64_t n_sel = 0;                                     // aligner: rows the head will classify (the device's selection must agree)
   for (int b = 0; b < B; ++b) {
     ids_len[b] = (pre_off[b + 1] - pre_off[b]) + n_audio[b] + (post_off[b + 1] - post_off[b]);
     ASR_REQUIRE(ids_len[b] >= 1 && ids_len[b] <= c.max_seq_len, "qwen: prompt of %d positions exceeds max_seq_len %d", ids_len[b], c.max_seq_len);
     drow0[b] = rows_d;
     rows_d += round_up(ids_len[b], 16);
     if (ids_len_out) ids_len_out[b] = ids_len[b];
+    if (al && al->tid < 0) n_sel += ids_len[b];
+    else if (al) {
+      for (int i = pre_off[b]; i < pre_off[b + 1]; ++i) n_sel += pre_ids[i] == al->tid;
+      for (int i = post_off[b]; i < post_off[b + 1]; ++i) n_sel += post_ids[i] == al->tid;
+    }
   }
+  if (al) ASR_REQUIRE(n_sel <= al->cap, "qwen_align: %lld selected rows but buckets_cap is %lld", (long long)n_sel, (long long)al->cap);
   const int Md = (int)pad_rows(rows_d);
   int dqt = 0, dnw = 4, dq_rows = 0, n_dqb = 0, max_len = 0;
   for (int b = 0; b < B; ++b) max_len = std::max(max_len, ids_len[b]);
@@ -1260,7 +1325,9 @@ void QwSession::prefill(const float* audio, int audio_mem, const int64_t* offs, 
   DecPass P;
   P.plan = ddp; P.row_seq = d_row_seq; P.row_t = d_row_t; P.last_rows = d_last_rows; P.rows = rows_d; P.B = B; P.step = false;
   P.qb_utt = d_dqb_utt; P.qb_q0 = d_dqb_q0; P.n_qb = no_fuse ? 0 : n_dqb; P.qt = dqt; P.nw = dnw; P.max_T = max_len; P.ld_vt = Md;
+  P.head = al == nullptr;
   decoder_pass<T>(P);
+  if (al) { align_head<T>(B, ddp, d_src, (int)n_sel, *al); return; }
   // step plan for the decode calls that follow: one row per sequence
   {
     const int Mb = round_up(B, 128);
@@ -1277,6 +1344,65 @@ void QwSession::prefill(const float* audio, int audio_mem, const int64_t* offs, 
   }
   noise_armed = false;
   finish<T>(B, next_out, logits_out, true);
+}
+
+// Forced-aligner head (FORCED_ALIGNER_DECODER_MAIN :1104-1109 on the selected rows only): device-side row selection -> final RMSNorm of those
+// rows (learned weight) -> classify GEMM with the row arg-max. A few rows stream the weights (skinny GEMM to f32 logits + row arg-max); more
+// rows take the MFMA tiles with the fused arg-max epilogue (per 64-column partials, reduced afterwards), the CTC head's form.
+template <typename T>
+void QwSession::align_head(int B, const UttPlan* ddp, const int32_t* d_src, int n_sel, const AlignReq& al) {
+  const auto& c = cfg;
+  const int d = c.d_model, n_slabs = hpad / 64;
+  const bool want_logits = al.logits != nullptr;
+  d_sel.reserve((size_t)(2 * B + 1 + std::max(n_sel, 64)) * 4, stream);
+  int32_t* cnt = d_sel.as<int32_t>();
+  int32_t* off = cnt + B;
+  int32_t* rows = off + B + 1;
+  d_bucket.reserve((size_t)std::max(n_sel, 64) * 4, stream);
+  const bool stream_w = precision == ASR_PRECISION_BF16 && n_sel <= 64;
+  { ProfScope ps(prof, "align_head", stream);
+    hipLaunchKernelGGL(qw_slot_count_kernel, dim3(B), dim3(256), 0, stream, d_src, ddp, al.tid, cnt);
+    hipLaunchKernelGGL(qw_slot_compact_kernel, dim3(B), dim3(256), 0, stream, d_src, ddp, al.tid, (const int32_t*)cnt, B, n_sel, off, rows);
+    if (n_sel > 0) {
+      d_last.reserve(pad_rows(n_sel) * d * sizeof(T), stream);
+      T* last = d_last.as<T>();
+      hipLaunchKernelGGL(qw_rmsnorm_kernel<T>, dim3((n_sel + 3) / 4), dim3(256), 0, stream, d_x.as<float>(), d, n_sel, d, final_norm, c.rms_eps, last, d,
+                         (const int32_t*)rows);
+      GemmArgs g; g.A = last; g.lda = d; g.W = lm_head; g.ldw = d; g.M = n_sel; g.N = hpad; g.K = d;
+      if (stream_w || want_logits) {
+        d_logits.reserve(pad_rows(n_sel) * (size_t)hpad * 4, stream);
+        g.out_f32 = d_logits.as<float>(); g.ld_out_f32 = hpad;
+      }
+      if (stream_w) {
+        gemm(g);
+        launch_argmax_rows(d_logits.as<float>(), hpad, n_sel, c.classify_num, nullptr, d_bucket.as<int32_t>(), stream);
+      } else {
+        d_amax_v.reserve(pad_rows(n_sel) * n_slabs * 4, stream);
+        d_amax_i.reserve(pad_rows(n_sel) * n_slabs * 4, stream);
+        g.amax_val = d_amax_v.as<float>(); g.amax_idx = d_amax_i.as<int32_t>(); g.n_valid = c.classify_num;
+        gemm(g);
+        launch_argmax_reduce(d_amax_v.as<float>(), d_amax_i.as<int32_t>(), n_sel, n_slabs, d_bucket.as<int32_t>(), stream);
+      }
+    }
+    HIP_CHECK(hipGetLastError()); }
+  if (taps_enabled && n_sel > 0 && want_logits) save_tap("logits", d_logits.ptr, n_sel, c.classify_num, hpad, 4);
+  const size_t lbytes = want_logits ? (size_t)n_sel * c.classify_num * 4 : 0;
+  unsigned char* st = (unsigned char*)pinned(h_io, h_io_cap, (size_t)(B + 1 + n_sel) * 4 + 64 + lbytes);
+  int32_t* h_off = (int32_t*)st;
+  int32_t* h_bk = h_off + B + 1;
+  float* h_lg = (float*)(st + (size_t)(B + 1 + n_sel) * 4 + 64);
+  HIP_CHECK(hipMemcpyAsync(h_off, off, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost, stream));
+  if (n_sel > 0) {
+    HIP_CHECK(hipMemcpyAsync(h_bk, d_bucket.ptr, (size_t)n_sel * 4, hipMemcpyDeviceToHost, stream));
+    if (want_logits)
+      HIP_CHECK(hipMemcpy2DAsync(h_lg, (size_t)c.classify_num * 4, d_logits.ptr, (size_t)hpad * 4, (size_t)c.classify_num * 4, n_sel, hipMemcpyDeviceToHost, stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(stream));
+  ASR_REQUIRE(h_off[B] == n_sel, "qwen_align: the device selected %d rows, the host counted %d", h_off[B], n_sel);
+  memcpy(al.slot_off, h_off, (size_t)(B + 1) * 4);
+  if (n_sel > 0) memcpy(al.buckets, h_bk, (size_t)n_sel * 4);
+  if (want_logits && n_sel > 0) memcpy(al.logits, h_lg, lbytes);
+  if (prof.enabled) prof.collect();
 }
 
 template <typename T>
@@ -1466,6 +1592,7 @@ extern "C" int asr_qwen_create(const asr_qwen_config* cfg, const void* arena, si
       s->fp8 = precision == ASR_PRECISION_FP8W || s->fp4;
       s->precision = s->fp8 ? ASR_PRECISION_BF16 : precision;        // FP8 mode = bf16 mode with byte-wide decoder projections
       s->cfg = *cfg;
+      ASR_REQUIRE(cfg->classify_num == 0 || !s->fp8, "qwen_create: the forced aligner runs bf16 or f32 weights (FP8W / MXFP4W aligner sessions are not supported)");
       HIP_CHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
       s->own_stream = true;
       gemm_reload_env();
@@ -1492,6 +1619,7 @@ extern "C" int asr_qwen_prefill(asr_session* s, const float* audio, int audio_me
     ASR_REQUIRE(s && s->kind == 5, "qwen_prefill: not a Qwen3-ASR session");
     TenantScope tenant(s);
     QwSession* q = static_cast<QwSession*>(s);
+    ASR_REQUIRE(!q->aligner(), "qwen_prefill: a forced-aligner session (classify_num %d) has no LM head; call asr_qwen_align", q->cfg.classify_num);
     if (q->precision == ASR_PRECISION_BF16)
       q->prefill<bf16_t>(audio, audio_mem, audio_offsets, batch, pre_ids, pre_offsets, post_ids, post_offsets, next_ids_out, logits_out, ids_len_out);
     else
@@ -1504,6 +1632,7 @@ extern "C" int asr_qwen_decode(asr_session* s, const int32_t* ids, int32_t* next
     ASR_REQUIRE(s && s->kind == 5, "qwen_decode: not a Qwen3-ASR session");
     TenantScope tenant(s);
     QwSession* q = static_cast<QwSession*>(s);
+    ASR_REQUIRE(!q->aligner(), "qwen_decode: a forced-aligner session (classify_num %d) has no decode loop; call asr_qwen_align", q->cfg.classify_num);
     if (q->precision == ASR_PRECISION_BF16) q->step<bf16_t>(ids, next_ids_out, logits_out);
     else q->step<float>(ids, next_ids_out, logits_out);
   });
@@ -1567,6 +1696,7 @@ extern "C" int asr_qwen_beam_search(asr_session* s, int beam, int max_new, const
     ASR_REQUIRE(s && s->kind == 5 && tokens_out && n_out && max_new >= 1 && n_stop >= 0 && (n_stop == 0 || stop_ids), "qwen_beam_search: bad argument");
     TenantScope tenant(s);
     QwSession* q = static_cast<QwSession*>(s);
+    ASR_REQUIRE(!q->aligner(), "qwen_beam_search: a forced-aligner session (classify_num %d) has no decode loop; call asr_qwen_align", q->cfg.classify_num);
     if (q->precision == ASR_PRECISION_BF16) q->beam_search<bf16_t>(beam, max_new, stop_ids, n_stop, tokens_out, n_out, scores_out);
     else q->beam_search<float>(beam, max_new, stop_ids, n_stop, tokens_out, n_out, scores_out);
   });
@@ -1587,6 +1717,7 @@ extern "C" int asr_qwen_generate(asr_session* s, int max_new, const int32_t* sto
     ASR_REQUIRE(s && s->kind == 5 && tokens_out && n_out && max_new >= 1 && (n_stop == 0 || stop_ids), "qwen_generate: bad argument");
     TenantScope tenant(s);
     QwSession* q = static_cast<QwSession*>(s);
+    ASR_REQUIRE(!q->aligner(), "qwen_generate: a forced-aligner session (classify_num %d) has no decode loop; call asr_qwen_align", q->cfg.classify_num);
     ASR_REQUIRE(q->batch > 0, "qwen_generate: prefill first");
     const int B = q->batch;
     std::vector<int32_t> cur(B);
@@ -1617,5 +1748,24 @@ extern "C" int asr_qwen_generate(asr_session* s, int max_new, const int32_t* sto
       if (q->precision == ASR_PRECISION_BF16) q->step<bf16_t>(nullptr, cur.data(), nullptr);
       else q->step<float>(nullptr, cur.data(), nullptr);
     }
+  });
+}
+
+extern "C" int asr_qwen_align(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
+                              const int32_t* pre_offsets, const int32_t* post_ids, const int32_t* post_offsets, int32_t timestamp_id,
+                              int32_t* slot_offsets_out, int32_t* buckets_out, int64_t buckets_cap, float* logits_out, int32_t* ids_len_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 5, "qwen_align: not a Qwen3 session");
+    TenantScope tenant(s);
+    QwSession* q = static_cast<QwSession*>(s);
+    ASR_REQUIRE(q->aligner(), "qwen_align: not a forced-aligner session (classify_num = 0: this session has the vocabulary LM head)");
+    ASR_REQUIRE(slot_offsets_out && buckets_cap >= 0 && (buckets_out || buckets_cap == 0), "qwen_align: bad argument");
+    ASR_REQUIRE(timestamp_id < q->cfg.vocab, "qwen_align: timestamp id %d out of range", timestamp_id);
+    AlignReq al;
+    al.tid = timestamp_id < 0 ? -1 : timestamp_id; al.slot_off = slot_offsets_out; al.buckets = buckets_out; al.cap = buckets_cap; al.logits = logits_out;
+    if (q->precision == ASR_PRECISION_BF16)
+      q->prefill<bf16_t>(audio, audio_mem, audio_offsets, batch, pre_ids, pre_offsets, post_ids, post_offsets, nullptr, nullptr, ids_len_out, &al);
+    else
+      q->prefill<float>(audio, audio_mem, audio_offsets, batch, pre_ids, pre_offsets, post_ids, post_offsets, nullptr, nullptr, ids_len_out, &al);
   });
 }

@@ -505,6 +505,7 @@ class QwenAsrSession(_Session):
                   "n_window_infer", "max_source_positions", "d_model", "n_heads", "n_kv_heads", "d_head", "d_ffn", "n_layers", "vocab",
                   "max_seq_len", "max_audio_len", "rms_eps", "rope_theta"):
             setattr(c, f, getattr(cfg, f))
+        c.classify_num = int(getattr(cfg, "classify_num", 0))
         self._cfg_c = c
         if arena_device_ptr is not None:
             self._keep = arena
@@ -631,6 +632,53 @@ class QwenAsrSession(_Session):
         return [[(tok[b, r, :n[b, r]].copy(), float(score[b, r])) for r in range(beam)] for b in range(self.batch)]
 
 
+class QwenAlignerSession(QwenAsrSession):
+    """HIP replacement of the merged Qwen3-ForcedAligner graph (Qwen_ForcedAligner/Inference_Qwen_ForcedAligner_ONNX.py:540-575): the
+    Qwen3-ASR encoder and prompt assembly, one decoder pass over the whole prompt, the timestamp classifier's arg-max on the selected rows.
+    The session refuses prefill / decode / generate / beam_search (include/asr_mi355x.h asr_qwen_align)."""
+
+    @classmethod
+    def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0):
+        from .arena import build_qwen_aligner_arena
+        return cls(cfg, build_qwen_aligner_arena(cfg, ck, cfg.classify_num, precision), precision, device_id)
+
+    def align_packed(self, audio, offsets, pre_ids, post_ids, timestamp_id: int = -1, want_logits: bool = False,
+                     audio_device_ptr: int | None = None):
+        """pre_ids / post_ids: one id list per utterance (or one shared list); prompt = [pre | audio embeddings | post]. timestamp_id < 0
+        classifies every position. -> (buckets per utterance, logits per utterance (rows, classify_num) | None, ids_len (B,))"""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        B = offsets.size - 1
+        pre, pre_off = self._ragged(pre_ids, B)
+        post, post_off = self._ragged(post_ids, B)
+        ids_len = np.zeros(B, dtype=np.int32)
+        n_audio = [self.audio_tokens(int(offsets[b + 1] - offsets[b])) for b in range(B)]
+        if timestamp_id < 0:
+            cap = int(sum(n_audio) + pre_off[-1] + post_off[-1])
+        else:
+            cap = int(np.count_nonzero(pre[:pre_off[-1]] == timestamp_id) + np.count_nonzero(post[:post_off[-1]] == timestamp_id))
+        slot_off = np.zeros(B + 1, dtype=np.int32)
+        buckets = np.zeros(max(cap, 1), dtype=np.int32)
+        logits = np.empty((max(cap, 1), self.cfg.classify_num), dtype=np.float32) if want_logits else None
+        if audio_device_ptr is not None:
+            ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
+        else:
+            audio = _f32(audio).reshape(-1)
+            ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
+        _lib.check(_lib.load().asr_qwen_align(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(pre), _ip(pre_off),
+                                              _ip(post), _ip(post_off), int(timestamp_id), _ip(slot_off), _ip(buckets), cap, _fp(logits),
+                                              _ip(ids_len)))
+        self.batch = 0
+        bk = [buckets[slot_off[b]:slot_off[b + 1]].copy() for b in range(B)]
+        lg = [logits[slot_off[b]:slot_off[b + 1]].copy() for b in range(B)] if want_logits else None
+        return bk, lg, ids_len
+
+    def align(self, audios: Sequence[np.ndarray], pre_ids, post_ids, timestamp_id: int = -1, want_logits: bool = False):
+        flat = [_f32(a).reshape(-1) for a in audios]
+        offs = np.zeros(len(flat) + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([a.size for a in flat])
+        return self.align_packed(np.concatenate(flat), offs, pre_ids, post_ids, timestamp_id, want_logits)
+
+
 def load_session(path: str, device_id: int = 0):
     """Open an `.asrmodel` bundle (tools/convert_checkpoint.py, export_*) as the matching native session."""
     from . import config as cfgm
@@ -646,4 +694,6 @@ def load_session(path: str, device_id: int = 0):
         return WhisperSession(cfgm.WhisperConfig(**conf), blob, prec, device_id)
     if kind == "qwen_asr":
         return QwenAsrSession(cfgm.QwenAsrConfig(**conf), blob, prec, device_id)
+    if kind == "qwen_aligner":
+        return QwenAlignerSession(cfgm.QwenAlignerConfig(**conf), blob, prec, device_id)
     raise ValueError(f"{path!r}: no native session for bundle kind {kind!r}")

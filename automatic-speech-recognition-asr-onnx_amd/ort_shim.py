@@ -269,6 +269,12 @@ class InferenceSession:
             self._native = ParaformerSession(self._cfg, blob, info["precision"], device_id)
             self._inputs = [NodeArg("audio", [1, 1, "audio_len"], np.float32)]
             self._outputs = [NodeArg("token_ids", [1, "num_token"], np.int32), NodeArg("num_id", [1], np.int32)]
+        elif self._kind == "qwen_aligner":                      # the merged ForcedAligner graph: one stateless launch per clip
+            from .ort_shim_qwen import QwenAlignerGraph
+            self._graph = QwenAlignerGraph(info, blob, device_id)
+            self._native = self._graph.native
+            self._inputs = [NodeArg(n, sh, dt) for n, sh, dt in self._graph.inputs]
+            self._outputs = [NodeArg(n, sh, dt) for n, sh, dt in self._graph.outputs]
         elif self._kind in ("whisper_graph", "qwen_graph", "paraformer_stream_graph"):    # state lives in the folder's shared native session
             path = str(path_or_bytes)
             if not os.path.isfile(path) and path.endswith(".onnx"):
@@ -358,6 +364,8 @@ class InferenceSession:
             return {"metadata_marker_out": np.asarray(feeds["metadata_marker"].numpy())}
         if self._kind in ("whisper_graph", "qwen_graph", "paraformer_stream_graph"):
             return self._graph.execute(feeds, OrtValue)
+        if self._kind == "qwen_aligner":
+            return self._graph.execute(feeds)
         raise ValueError(self._kind)
 
     def run_with_iobinding(self, binding: IOBinding, run_options: RunOptions | None = None):

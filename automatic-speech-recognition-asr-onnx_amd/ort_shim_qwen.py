@@ -217,3 +217,57 @@ def export_qwen_asr_folder(folder: str, cfg: QwenAsrConfig, ck: dict, metadata: 
     save_model(os.path.join(folder, EMBED_FILE + ".asrmodel"), "qwen_graph", {"role": "embed", "weights": WEIGHTS_FILE + ".asrmodel"}, None, {}, precision)
     save_model(os.path.join(folder, METADATA_FILE + ".asrmodel"), "metadata", None, None, dict(metadata))
     return folder
+
+
+# ---------------------------------------------------------------------------------------------------- Qwen3-ForcedAligner
+ALIGNER_MERGED_FILE = "ForcedAligner_Merged"      # Qwen_ForcedAligner/Export_Qwen_ForcedAligner.py MODEL_FILE_NAMES["merged"]
+
+
+class QwenAlignerGraph:
+    """The merged ForcedAligner graph (Embed -> Encoder -> Rotary+Mask -> Decoder Main, Inference_Qwen_ForcedAligner_ONNX.py:554-560):
+    inputs `audio` (1, 1, audio_len) f32 in [-1, 1] and `input_ids` (1, text_len) = the word / <timestamp> ids; output `output_ids`
+    (1, L) int32, the arg-max bucket of EVERY position of [<|audio_start|> | audio | <|audio_end|> | input_ids] -- the native session's
+    all-positions mode (timestamp_id < 0)."""
+
+    def __init__(self, info: dict, blob, device_id: int):
+        from .config import QwenAlignerConfig
+        from .engine import QwenAlignerSession
+        self.cfg = QwenAlignerConfig(**info["config"])
+        meta = info.get("metadata", {})
+        special = meta["special_token_ids"]
+        self.special = json.loads(special) if isinstance(special, str) else dict(special)
+        self.native = QwenAlignerSession(self.cfg, blob, int(info.get("precision", 0)), device_id)
+        self.inputs = [("audio", [1, 1, "audio_len"], np.float32), ("input_ids", [1, "text_len"], np.int32)]
+        self.outputs = [("output_ids", [1, "ids_len"], np.int32)]
+
+    def execute(self, feeds: dict) -> dict:
+        for name, _, _ in self.inputs:
+            if name not in feeds:
+                raise ValueError(f"input {name!r} is not bound")
+        audio = feeds["audio"]
+        shape = tuple(audio._shape)
+        if len(shape) != 3 or shape[0] != 1 or shape[1] != 1 or np.dtype(audio._dtype) != np.float32:
+            raise ValueError(f"audio must be tensor(float) of shape (1, 1, audio_len) in [-1, 1], got {audio._dtype} {shape}")
+        ids = np.asarray(feeds["input_ids"].numpy(), dtype=np.int64)
+        if ids.ndim != 2 or ids.shape[0] != 1:
+            raise ValueError(f"input_ids must have shape (1, text_len), got {ids.shape}")
+        if ids.size and (ids.min() < 0 or ids.max() >= self.cfg.vocab):
+            raise ValueError(f"input_ids out of range [0, {self.cfg.vocab})")
+        pre = [[int(self.special["audio_start"])]]
+        post = [[int(self.special["audio_end"])] + [int(t) for t in ids.reshape(-1)]]
+        offsets = np.array([0, shape[2]], dtype=np.int64)
+        if audio._host is not None:
+            bk, _, _ = self.native.align_packed(audio._host.reshape(-1), offsets, pre, post, timestamp_id=-1)
+        else:
+            bk, _, _ = self.native.align_packed(None, offsets, pre, post, timestamp_id=-1, audio_device_ptr=audio._dptr.value)
+        return {"output_ids": bk[0].reshape(1, -1).astype(np.int32)}
+
+
+def export_qwen_aligner_folder(folder: str, cfg, ck: dict, metadata: dict, precision: int = 0) -> str:
+    """Model folder with the reference's runtime file names: `ForcedAligner_Merged.asrmodel` (arena + metadata map) and `ASR_Metadata.asrmodel`."""
+    from .ort_shim import save_model
+    from .qwen_aligner import export_qwen_aligner
+    os.makedirs(folder, exist_ok=True)
+    export_qwen_aligner(cfg, ck, os.path.join(folder, ALIGNER_MERGED_FILE + ".asrmodel"), metadata, precision)
+    save_model(os.path.join(folder, METADATA_FILE + ".asrmodel"), "metadata", None, None, dict(metadata))
+    return folder

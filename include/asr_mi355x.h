@@ -257,7 +257,11 @@ typedef struct asr_qwen_config {
   int32_t enc_d, enc_heads, enc_ffn, n_enc_layers, conv_channels, n_window, n_window_infer, max_source_positions;
   int32_t d_model, n_heads, n_kv_heads, d_head, d_ffn, n_layers, vocab, max_seq_len, max_audio_len;
   float rms_eps, rope_theta;
-  int32_t reserved[9];
+  /* 0: Qwen3-ASR (vocabulary LM head). > 0: Qwen3-ForcedAligner -- dec.lm_head holds classify_num timestamp-bucket rows (padded to a
+   * multiple of 128, like the vocabulary), Qwen_ForcedAligner/Export_Qwen_ForcedAligner.py:531-586; the session then serves
+   * asr_qwen_align only. */
+  int32_t classify_num;
+  int32_t reserved[8];
 } asr_qwen_config;
 
 int asr_qwen_create(const asr_qwen_config* cfg, const void* arena, size_t arena_bytes, int arena_mem, int device_id, int precision,
@@ -300,6 +304,19 @@ int asr_qwen_kv_stats(asr_session* s, int32_t* out4);
  * Plain arg-max head only (no penalty / sampling). The session's greedy state (asr_qwen_decode / _generate) is left untouched. */
 int asr_qwen_beam_search(asr_session* s, int beam, int max_new, const int32_t* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out,
                          float* scores_out);
+
+/* Forced alignment (aligner sessions only, classify_num > 0): the reference's one non-autoregressive pass of the merged
+ * ForcedAligner graph (Qwen_ForcedAligner/Inference_Qwen_ForcedAligner_ONNX.py:540-575) = FORCED_ALIGNER_ENCODER (Export_Qwen_ForcedAligner.py:678-836,
+ * the Qwen3-ASR audio path) + FORCED_ALIGNER_EMBED (:843) + FORCED_ALIGNER_ROTARY_MASK (:855-880, the f16-rounded cos / sin table lives
+ * in the arena) + FORCED_ALIGNER_DECODER_MAIN (:921-1110) whose final RMSNorm -> classify head -> arg-max (:1104-1109) runs on the
+ * selected rows only. Prompts as in asr_qwen_prefill: sequence b = [pre | audio embeddings | post] (the reference: pre = <|audio_start|>,
+ * post = <|audio_end|> + the word / <timestamp> ids). Rows selected on the device: positions whose prompt id == timestamp_id, or
+ * every position when timestamp_id < 0 (the graph's output_ids (1, L)). Host outputs, packed utterance-major in position order:
+ * slot_offsets_out [B + 1] (utterance b's rows are [off[b], off[b+1])), buckets_out [buckets_cap >= off[B]] = arg-max bucket per row,
+ * logits_out [off[B]][classify_num] (nullable), ids_len_out [B] (nullable). The KV cache is written as in a prefill, and nothing reads it. */
+int asr_qwen_align(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
+                   const int32_t* pre_offsets, const int32_t* post_ids, const int32_t* post_offsets, int32_t timestamp_id, int32_t* slot_offsets_out,
+                   int32_t* buckets_out, int64_t buckets_cap, float* logits_out, int32_t* ids_len_out);
 
 /* ------------------------------------------------------------------ device buffers
  * Backing store of the shim's OrtValue (OrtValue.ortvalue_from_numpy / update_inplace / numpy,

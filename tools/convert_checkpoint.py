@@ -4,6 +4,7 @@
     python tools/convert_checkpoint.py --family sensevoice --checkpoint model.pt --cmvn am.mvn --out SenseVoice_MI355X
     python tools/convert_checkpoint.py --family paraformer --checkpoint model.pt --cmvn am.mvn --tokens tokens.json --out Paraformer_MI355X
     python tools/convert_checkpoint.py --family whisper    --checkpoint model.safetensors --out Whisper_MI355X
+    python tools/convert_checkpoint.py --family qwen_aligner --checkpoint model.safetensors --tokens special.json --out Qwen_ForcedAligner_MI355X
 
 It performs what the tail of the reference's Export_*.py does for ONNX (Export_SenseVoice.py:355-405, Export_Paraformer.py:575-640,
 Export_Whisper.py:1040-1130) for the arena format: load the FunASR / Hugging Face state dict (torch `.pt` or `.safetensors`), read
@@ -119,17 +120,46 @@ def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=N
             raise ValueError("Qwen3-ASR needs the exporter's metadata map (--tokens metadata.json: special_token_ids, supported_languages, ...)")
         os.makedirs(out, exist_ok=True)
         importlib.import_module(PKG + ".qwen_asr").export_qwen_asr(cfg, sd, os.path.join(out, "Qwen_ASR.asrmodel"), tokens, precision)
+    elif family == "qwen_aligner":
+        cfg = qwen_aligner_config(sd)
+        if tokens is None:
+            raise ValueError("Qwen3-ForcedAligner needs the special token ids (--tokens special.json: {audio_start, audio_end, audio_pad, timestamp} "
+                             "or the exporter's metadata map with a special_token_ids entry)")
+        special = tokens.get("special_token_ids", tokens)
+        special = json.loads(special) if isinstance(special, str) else special
+        meta = importlib.import_module(PKG + ".qwen_aligner").aligner_metadata(cfg, special)
+        if "supported_languages" in tokens:
+            langs = tokens["supported_languages"]
+            meta["supported_languages"] = langs if isinstance(langs, str) else json.dumps(langs, ensure_ascii=False)
+        importlib.import_module(PKG + ".ort_shim_qwen").export_qwen_aligner_folder(out, cfg, sd, meta, precision)
     else:
         raise ValueError(family)
     return cfg
 
 
+def qwen_aligner_config(sd: dict):
+    """Qwen3-ForcedAligner geometry from the tensors (the Qwen3-ASR thinker's names; classify_num = the head's rows,
+    Export_Qwen_ForcedAligner.py:546)."""
+    cfgm = importlib.import_module(PKG + ".config")
+    a, t = "thinker.audio_tower.", "thinker.model."
+    de, d = sd[a + "ln_post.weight"].shape[0], sd[t + "norm.weight"].shape[0]
+    hd = sd[t + "layers.0.self_attn.q_norm.weight"].shape[0]
+    if "thinker.lm_head.weight" not in sd:
+        raise ValueError("thinker.lm_head.weight (the timestamp classifier) is missing: not a Qwen3-ForcedAligner checkpoint")
+    return cfgm.QwenAlignerConfig(enc_d=de, enc_heads=de // 64, enc_ffn=sd[a + "layers.0.fc1.weight"].shape[0],
+                                  n_enc_layers=_count(sd, r"thinker\.audio_tower\.layers\.(\d+)\."), conv_channels=sd[a + "conv2d1.weight"].shape[0],
+                                  d_model=d, d_head=hd, n_heads=sd[t + "layers.0.self_attn.q_proj.weight"].shape[0] // hd,
+                                  n_kv_heads=sd[t + "layers.0.self_attn.k_proj.weight"].shape[0] // hd,
+                                  d_ffn=sd[t + "layers.0.mlp.gate_proj.weight"].shape[0], n_layers=_count(sd, r"thinker\.model\.layers\.(\d+)\."),
+                                  vocab=sd[t + "embed_tokens.weight"].shape[0], classify_num=sd["thinker.lm_head.weight"].shape[0])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--family", required=True, choices=("sensevoice", "paraformer", "whisper", "qwen_asr"))
+    ap.add_argument("--family", required=True, choices=("sensevoice", "paraformer", "whisper", "qwen_asr", "qwen_aligner"))
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--cmvn", help="FunASR am.mvn (SenseVoice / Paraformer)")
-    ap.add_argument("--tokens", help="Paraformer token list: tokens.json (list) or one token per line; Qwen3-ASR: metadata.json (dict)")
+    ap.add_argument("--tokens", help="Paraformer token list: tokens.json (list) or one token per line; Qwen3-ASR: metadata.json (dict); Qwen3-ForcedAligner: special token ids (dict)")
     ap.add_argument("--language", default="zh")
     ap.add_argument("--decode-mode", default="zh", choices=("zh", "en"))
     ap.add_argument("--precision", default="bf16", choices=("bf16", "f32"))
