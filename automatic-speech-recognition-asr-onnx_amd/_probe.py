@@ -48,6 +48,7 @@ SIGNATURES = {
     "asr_probe_beam_select": (C.c_int, [C.POINTER(BeamSelectDesc)]),
     "asr_probe_decode_attention_beam": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p]),
     "asr_probe_gemm_counts": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
+    "asr_probe_live_device_bytes": (C.c_int, [C.POINTER(C.c_int64)]),
     "asr_probe_gemm_fp8": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _fp, C.c_float, _fp, _fp, C.c_int, C.c_void_p, _fp, C.c_int, _fp]),
     "asr_probe_gemm_bench": (C.c_int, [C.c_int] * 6 + [_fp]),
     "asr_probe_grid_barrier": (C.c_int, [C.c_int, C.c_int, _fp]),
@@ -118,6 +119,13 @@ def gemm_counts(reset: bool = False) -> dict:
     buf = C.create_string_buffer(1024)
     _lib.check(load().asr_probe_gemm_counts(int(reset), buf, 1024))
     return {k: int(v) for k, v in (kv.split("=") for kv in buf.value.decode().split(";") if kv)}
+
+
+def live_device_bytes() -> int:
+    """Device bytes held, process-wide, by session workspaces and the arenas they own (host-side counter)."""
+    n = C.c_int64(0)
+    _lib.check(load().asr_probe_live_device_bytes(C.byref(n)))
+    return n.value
 
 
 def gemm_chain(M, N, K, epilogue=0, cold_mb=768, replays=5):

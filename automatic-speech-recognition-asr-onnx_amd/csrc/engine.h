@@ -1,6 +1,7 @@
 // Session plumbing shared by the model families: weight arena, grow-only HBM workspace,
 // HIP-event profiler, debug taps.
 #pragma once
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -31,20 +32,80 @@ struct Arena {
   bool owned = false;
   std::map<std::string, TensorRef> tensors;
 
+  Arena() = default;
+  Arena(const Arena&) = delete;
+  Arena& operator=(const Arena&) = delete;
+  ~Arena();
   void load(const void* src, size_t nbytes, int mem, hipStream_t s);
-  void release();
   const TensorRef& get(const std::string& name) const;
   const TensorRef& get(const std::string& name, int dtype, std::initializer_list<int64_t> shape) const;
   bool has(const std::string& name) const { return tensors.count(name) != 0; }
 };
 
+// Device bytes held by DeviceBuffers and owned arenas, process-wide (the probe library reports it).
+int64_t asr_live_device_bytes();
+
+// HBM workspace. Owns its allocation: move-only, freed by the destructor (or early by release()).
+// No DeviceBuffer or PinnedBuffer may have static storage duration: it would be freed after the HIP runtime has shut down.
 struct DeviceBuffer {
   void* ptr = nullptr;
   size_t cap = 0;
-  // grow-only; new memory is zero-filled so padded rows/columns are finite
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  DeviceBuffer(DeviceBuffer&& o) noexcept : ptr(o.ptr), cap(o.cap) { o.ptr = nullptr; o.cap = 0; }
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept;
+  ~DeviceBuffer() { release(); }
+  // grow-only (the old buffer is freed after a synchronise of s); new memory is zero-filled so padded rows/columns are finite
   void reserve(size_t bytes, hipStream_t s);
   void release();
   template <typename T> T* as() const { return reinterpret_cast<T*>(ptr); }
+};
+
+// Pinned host staging: grow-only with 2x headroom, freed by the destructor.
+struct PinnedBuffer {
+  void* ptr = nullptr;
+  size_t cap = 0;
+  PinnedBuffer() = default;
+  PinnedBuffer(const PinnedBuffer&) = delete;
+  PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+  ~PinnedBuffer();
+  bool reserve(size_t bytes);      // true when the buffer was (re)allocated: a captured graph that copies into it is stale
+  template <typename T> T* as() const { return reinterpret_cast<T*>(ptr); }
+};
+
+// FNV-1a over the values a captured step bakes in
+struct GraphKey {
+  uint64_t h = 1469598103934665603ull;
+  GraphKey& mix(uint64_t v) { h = (h ^ v) * 1099511628211ull; return *this; }
+  GraphKey& mix(const void* p) { return mix((uint64_t)(uintptr_t)p); }
+};
+
+// One captured step and the capture policy every session uses: the first run of a key is eager (lazily created workspaces and kernel
+// attributes settle), the second is captured and launched, later runs with that key replay. A capture that throws is ended and discarded.
+// Runs that are not graphable are eager and leave the keys alone.
+struct StepGraph {
+  hipGraphExec_t exec = nullptr;
+  uint64_t key = 0, eager_key = 0;
+  StepGraph() = default;
+  StepGraph(const StepGraph&) = delete;
+  StepGraph& operator=(const StepGraph&) = delete;
+  ~StepGraph() { drop(); }
+  template <typename F> void run(hipStream_t s, bool graphable, uint64_t k, F&& enqueue) {
+    if (graphable && exec && k == key) {
+      HIP_CHECK(hipGraphLaunch(exec, s));
+    } else if (graphable && k == eager_key) {
+      capture(s, k, enqueue);
+      HIP_CHECK(hipGraphLaunch(exec, s));
+    } else {
+      enqueue();
+      if (graphable) eager_key = k;
+    }
+  }
+  void drop();
+
+ private:
+  void capture(hipStream_t s, uint64_t k, const std::function<void()>& enqueue);
 };
 
 struct Profiler {
@@ -56,12 +117,15 @@ struct Profiler {
   std::vector<Pending> pending;
   std::vector<hipEvent_t> pool;
 
+  Profiler() = default;
+  Profiler(const Profiler&) = delete;
+  Profiler& operator=(const Profiler&) = delete;
+  ~Profiler();
   int cls(const char* name);
   void begin(int c, hipStream_t s);
   void end(hipStream_t s);
   void collect();          // after the stream is synchronised
   void reset();
-  void release();
   hipEvent_t get_event();
 };
 
@@ -88,7 +152,7 @@ struct asr_session {
   Profiler prof;
   bool taps_enabled = false;
   std::map<std::string, Tap> taps;
-  virtual ~asr_session();
+  virtual ~asr_session();     // destroys an owned stream; a derived session's members are gone by then
   void save_tap(const char* name, const void* src, int64_t rows, int64_t cols, int64_t ld_src, int elt);
 };
 

@@ -1,6 +1,7 @@
 // Session plumbing: error channel, arena parsing, workspace, profiler, taps.
 #include "engine.h"
 
+#include <atomic>
 #include <cstring>
 
 static thread_local std::string g_last_error;
@@ -16,6 +17,9 @@ void asr_require_device(int device_id) {
     throw AsrError{ASR_ERR_INVALID, "device_id " + std::to_string(device_id) + " out of range (" + std::to_string(n) + " devices)"};
   HIP_CHECK(hipSetDevice(device_id));
 }
+
+static std::atomic<int64_t> g_live_bytes{0};
+int64_t asr_live_device_bytes() { return g_live_bytes.load(); }
 
 // ---------------------------------------------------------------------------------------- Arena
 namespace {
@@ -53,6 +57,7 @@ void Arena::load(const void* src, size_t nbytes, int mem, hipStream_t s) {
     memcpy(recs.data(), (const unsigned char*)src + sizeof(hdr), table);
     HIP_CHECK(hipMalloc((void**)&base, nbytes));
     owned = true;
+    g_live_bytes += (int64_t)nbytes;
     HIP_CHECK(hipMemcpyAsync(base, src, nbytes, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipStreamSynchronize(s));
   } else {
@@ -77,10 +82,8 @@ void Arena::load(const void* src, size_t nbytes, int mem, hipStream_t s) {
   }
 }
 
-void Arena::release() {
-  if (owned && base) (void)hipFree(base);
-  base = nullptr;
-  tensors.clear();
+Arena::~Arena() {
+  if (owned && base) { (void)hipFree(base); g_live_bytes -= (int64_t)bytes; }
 }
 
 const TensorRef& Arena::get(const std::string& name) const {
@@ -104,25 +107,71 @@ const TensorRef& Arena::get(const std::string& name, int dtype, std::initializer
   return t;
 }
 
-// ---------------------------------------------------------------------------------------- DeviceBuffer
+// ---------------------------------------------------------------------------------------- DeviceBuffer, PinnedBuffer, StepGraph
+DeviceBuffer& DeviceBuffer::operator=(DeviceBuffer&& o) noexcept {
+  if (this != &o) {
+    release();
+    ptr = o.ptr; cap = o.cap;
+    o.ptr = nullptr; o.cap = 0;
+  }
+  return *this;
+}
+
 void DeviceBuffer::reserve(size_t bytes, hipStream_t s) {
   if (bytes <= cap) return;
   if (ptr) {
     HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipFree(ptr));
-    ptr = nullptr;
-    cap = 0;
+    release();
   }
   const size_t want = (bytes + 255) & ~(size_t)255;
   HIP_CHECK(hipMalloc(&ptr, want));
-  HIP_CHECK(hipMemsetAsync(ptr, 0, want, s));
   cap = want;
+  g_live_bytes += (int64_t)want;
+  HIP_CHECK(hipMemsetAsync(ptr, 0, want, s));
 }
 
 void DeviceBuffer::release() {
-  if (ptr) (void)hipFree(ptr);
+  if (ptr) { (void)hipFree(ptr); g_live_bytes -= (int64_t)cap; }
   ptr = nullptr;
   cap = 0;
+}
+
+PinnedBuffer::~PinnedBuffer() {
+  if (ptr) (void)hipHostFree(ptr);
+}
+
+bool PinnedBuffer::reserve(size_t bytes) {
+  if (bytes <= cap) return false;
+  if (ptr) HIP_CHECK(hipHostFree(ptr));
+  ptr = nullptr;
+  cap = 0;
+  HIP_CHECK(hipHostMalloc(&ptr, bytes * 2, hipHostMallocDefault));
+  cap = bytes * 2;
+  return true;
+}
+
+void StepGraph::drop() {
+  if (exec) (void)hipGraphExecDestroy(exec);
+  exec = nullptr;
+}
+
+void StepGraph::capture(hipStream_t s, uint64_t k, const std::function<void()>& enqueue) {
+  drop();
+  hipGraph_t graph = nullptr;
+  HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  try {
+    enqueue();
+  } catch (...) {
+    (void)hipStreamEndCapture(s, &graph);
+    if (graph) (void)hipGraphDestroy(graph);
+    throw;
+  }
+  HIP_CHECK(hipStreamEndCapture(s, &graph));
+  const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  if (e != hipSuccess) exec = nullptr;
+  HIP_CHECK(e);
+  key = k;
 }
 
 // ---------------------------------------------------------------------------------------- Profiler
@@ -171,11 +220,9 @@ void Profiler::reset() {
   for (auto& v : launches) v = 0;
 }
 
-void Profiler::release() {
+Profiler::~Profiler() {
   for (auto& p : pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto e : pool) (void)hipEventDestroy(e);
-  pending.clear();
-  pool.clear();
 }
 
 // ---------------------------------------------------------------------------------------- taps
@@ -191,7 +238,6 @@ void asr_session::save_tap(const char* name, const void* src, int64_t rows, int6
 }
 
 // ---- tenancy table (engine.h)
-#include <atomic>
 #include <chrono>
 namespace {
 constexpr int TENANT_SLOTS = 512;
@@ -212,6 +258,7 @@ void asr_tenant_attach(asr_session* s) {
   }          // (table full: the session stays anonymous -- it is then never counted, which only ever errs towards the faster path)
 }
 asr_session::~asr_session() {
+  if (own_stream && stream) (void)hipStreamDestroy(stream);
   if (tenant_slot >= 0) { g_tenants[tenant_slot].device.store(-1); g_tenants[tenant_slot].used.store(0); tenant_slot = -1; }
 }
 TenantScope::TenantScope(asr_session* s_) : s(s_) {

@@ -247,7 +247,6 @@ extern "C" int asr_probe_quantize_fp8(const uint16_t* w_bf16, int N, int K, uint
     HIP_CHECK(hipMemcpy(out8, q.ptr, (size_t)N * K, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(scale, sc.ptr, (size_t)N * 4, hipMemcpyDeviceToHost));
     if (dq_bf16) HIP_CHECK(hipMemcpy(dq_bf16, dq.ptr, (size_t)N * K * 2, hipMemcpyDeviceToHost));
-    w.release(); q.release(); sc.release(); dq.release();
   });
 }
 
@@ -276,7 +275,6 @@ extern "C" int asr_probe_decode_gemm(int M, int N, int K, const uint16_t* a, con
     launch_decode_gemm(g, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, dout.ptr, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    for (DeviceBuffer* b : {&da, &dw, &dw8, &dsc, &db, &dcs, &dout, &ws, &cnt}) b->release();
   });
 }
 
@@ -293,7 +291,6 @@ extern "C" int asr_probe_quantize_mxfp4(const uint16_t* w_bf16, int N, int K, ui
     HIP_CHECK(hipMemcpy(out4, q.ptr, (size_t)N * K / 2, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(scale8, sc.ptr, (size_t)N * K / 32, hipMemcpyDeviceToHost));
     if (dq_bf16) HIP_CHECK(hipMemcpy(dq_bf16, dq.ptr, (size_t)N * K * 2, hipMemcpyDeviceToHost));
-    w.release(); q.release(); sc.release(); dq.release();
   });
 }
 
@@ -322,7 +319,6 @@ extern "C" int asr_probe_decode_gemm_mxfp4(int M, int N, int K, const uint16_t* 
     launch_decode_gemm(g, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, dout.ptr, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    for (DeviceBuffer* b : {&da, &dw, &dw4, &dsc, &db, &dcs, &dout, &ws, &cnt}) b->release();
   });
 }
 
@@ -363,11 +359,17 @@ extern "C" int asr_probe_gemm_fp8(int M, int N, int K, const uint8_t* a8, const 
       *us = ms * 1e3f / iters;
       (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
-    for (DeviceBuffer* b : {&da, &dw, &dsc, &db, &dadd, &dout}) b->release();
   });
 }
 
 extern "C" const char* asr_probe_last_kernel(void) { return g_chain_kernel; }
+
+extern "C" int asr_probe_live_device_bytes(int64_t* bytes) {
+  return asr_guard([&] {
+    ASR_REQUIRE(bytes, "probe_live_device_bytes: null argument");
+    *bytes = asr_live_device_bytes();
+  });
+}
 
 extern "C" int asr_probe_gemm_counts(int reset, char* buf, int cap) {
   return asr_guard([&] {

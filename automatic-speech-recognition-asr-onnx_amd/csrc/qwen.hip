@@ -616,7 +616,7 @@ struct QwSession : asr_session {
   std::vector<std::vector<int32_t>> kv_owned;             // pages of every sequence, in position order
   std::vector<char> kv_released;
   DeviceBuffer d_kvtab;
-  void* h_kvtab = nullptr; size_t h_kvtab_cap = 0;
+  PinnedBuffer h_kvtab;
   bool kv_table_dirty = false;
   size_t kv_page_elems() const { return (size_t)cfg.n_layers * cfg.n_kv_heads * 16 * cfg.d_head; }
   void kv_begin(int B, const std::vector<int>& lens, size_t eT);
@@ -635,40 +635,15 @@ struct QwSession : asr_session {
   DeviceBuffer d_save, d_nsaved, d_noise;
   DeviceBuffer d_sel, d_amax_v, d_amax_i, d_bucket;      // forced-aligner head: counts / offsets / rows, arg-max partials, buckets
   DeviceBuffer d_bkc, d_bvc, d_bhist, d_bp0, d_bplan, d_bsrc[2], d_btok[2], d_bcum, d_bfin, d_blen, d_bdone, d_btopv, d_btopi, d_bstop, d_bnext;   // beam search state
-  hipGraphExec_t dec_graph = nullptr; uint64_t dec_key = 0, dec_eager_key = 0;
-  void* h_plan = nullptr; size_t h_plan_cap = 0;
-  void* h_io = nullptr; size_t h_io_cap = 0;
-  void* h_ids = nullptr; size_t h_ids_cap = 0;
+  StepGraph dec_graph;
+  PinnedBuffer h_plan, h_io, h_ids;
 
-  ~QwSession() override {
-    for (DeviceBuffer* b : {&d_plan, &d_audio, &d_mel, &d_blkmax, &d_feat, &d_col, &d_c1, &d_c2, &d_c3, &d_xa, &d_xb, &d_h, &d_qk, &d_vt, &d_ctx,
-                            &d_ffn, &d_aud_out, &d_dplan, &d_x, &d_x2, &d_dh, &d_qkv, &d_q, &d_dctx, &d_act, &d_last, &d_logits, &d_next,
-                            &d_kc, &d_vc, &d_kvtab, &d_hist, &d_stepplan, &d_skws, &d_skcnt, &d_vt2, &d_krows, &d_xlo, &d_x2lo, &d_save, &d_nsaved, &d_noise, &d_sel, &d_amax_v, &d_amax_i, &d_bucket, &d_bkc, &d_bvc, &d_bhist, &d_bp0, &d_bplan, &d_bsrc[0], &d_bsrc[1], &d_btok[0], &d_btok[1], &d_bcum, &d_bfin, &d_blen, &d_bdone, &d_btopv, &d_btopi, &d_bstop, &d_bnext, &d_w8, &d_wscale, &d_wdq})
-      b->release();
-    for (auto& kv : taps) kv.second.buf.release();
-    if (dec_graph) (void)hipGraphExecDestroy(dec_graph);
-    if (h_plan) (void)hipHostFree(h_plan);
-    if (h_io) (void)hipHostFree(h_io);
-    if (h_ids) (void)hipHostFree(h_ids);
-    if (h_kvtab) (void)hipHostFree(h_kvtab);
-    prof.release();
-    arena.release();
-    if (own_stream && stream) (void)hipStreamDestroy(stream);
-  }
   void gemm(const GemmArgs& g0) {
     if (precision != ASR_PRECISION_BF16) { launch_gemm_f32(g0, stream); return; }
     if (!d_skws.ptr) { d_skws.reserve((size_t)16 << 20, stream); d_skcnt.reserve(4096 * 4, stream); }
     GemmArgs g = g0;
     g.sk_ws = d_skws.as<float>(); g.sk_ws_bytes = d_skws.cap; g.sk_cnt = d_skcnt.as<int32_t>();
     launch_gemm_bf16(g, stream);
-  }
-  void* pinned(void*& p, size_t& cap, size_t bytes) {
-    if (bytes > cap) {
-      if (p) HIP_CHECK(hipHostFree(p));
-      HIP_CHECK(hipHostMalloc(&p, bytes * 2, hipHostMallocDefault));
-      cap = bytes * 2;
-    }
-    return p;
   }
   void init();
   bool aligner() const { return cfg.classify_num > 0; }
@@ -762,7 +737,8 @@ void QwSession::init() {
 void QwSession::kv_upload() {
   if (!kv_table_dirty) return;
   const size_t bytes = kv_table.size() * 4;
-  int32_t* st = (int32_t*)pinned(h_kvtab, h_kvtab_cap, bytes);
+  h_kvtab.reserve(bytes);
+  int32_t* st = h_kvtab.as<int32_t>();
   memcpy(st, kv_table.data(), bytes);
   HIP_CHECK(hipMemcpyAsync(d_kvtab.ptr, st, bytes, hipMemcpyHostToDevice, stream));
   HIP_CHECK(hipStreamSynchronize(stream));               // (the staging buffer is reused by the next change)
@@ -775,17 +751,10 @@ int QwSession::kv_take(size_t eT) {
     DeviceBuffer nk, nv;
     nk.reserve((size_t)new_pages * kv_page_elems() * eT, stream);
     nv.reserve((size_t)new_pages * kv_page_elems() * eT, stream);
-    try {
-      HIP_CHECK(hipMemcpyAsync(nk.ptr, d_kc.ptr, (size_t)old_pages * kv_page_elems() * eT, hipMemcpyDeviceToDevice, stream));
-      HIP_CHECK(hipMemcpyAsync(nv.ptr, d_vc.ptr, (size_t)old_pages * kv_page_elems() * eT, hipMemcpyDeviceToDevice, stream));
-      HIP_CHECK(hipStreamSynchronize(stream));
-    } catch (...) {                                       // (DeviceBuffer has no destructor: a failed copy must not leak the new pools)
-      nk.release(); nv.release();
-      throw;
-    }
-    d_kc.release(); d_vc.release();
-    d_kc = nk; d_vc = nv;                                 // (the decode graph is keyed on these pointers: it is captured again)
-    nk.ptr = nullptr; nk.cap = 0; nv.ptr = nullptr; nv.cap = 0;
+    HIP_CHECK(hipMemcpyAsync(nk.ptr, d_kc.ptr, (size_t)old_pages * kv_page_elems() * eT, hipMemcpyDeviceToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(nv.ptr, d_vc.ptr, (size_t)old_pages * kv_page_elems() * eT, hipMemcpyDeviceToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    d_kc = std::move(nk); d_vc = std::move(nv);           // (the decode graph is keyed on these pointers: it is captured again)
     for (int p = new_pages - 1; p >= old_pages; --p) kv_free.push_back(p);
     kv_pool_pages = new_pages;
   }
@@ -1045,7 +1014,8 @@ void QwSession::finish(int B, int32_t* next_out, float* logits_out, bool sync) {
   if (taps_enabled) save_tap("logits", d_logits.ptr, B, c.vocab, vpad, 4);
   const bool wait = next_out || logits_out || sync || prof.enabled;
   if (wait) {
-    unsigned char* st = (unsigned char*)pinned(h_io, h_io_cap, (size_t)B * 4 + 64 + (logits_out ? (size_t)B * c.vocab * 4 : 0));
+    h_io.reserve((size_t)B * 4 + 64 + (logits_out ? (size_t)B * c.vocab * 4 : 0));
+    unsigned char* st = h_io.as<unsigned char>();
     if (next_out) HIP_CHECK(hipMemcpyAsync(st, d_next.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
     if (logits_out)
       HIP_CHECK(hipMemcpy2DAsync(st + (size_t)B * 4 + 64, (size_t)c.vocab * 4, d_logits.ptr, (size_t)vpad * 4, (size_t)c.vocab * 4, B, hipMemcpyDeviceToHost, stream));
@@ -1128,7 +1098,8 @@ void QwSession::prefill(const float* audio, int audio_mem, const int64_t* offs, 
   }
   // plan blob: [UttPlan B][win plans][dec plans B][blk_utt][blk_f0][qb_utt][qb_q0][slot_utt][slot_local][pos_rows Me][src Md][row_seq Md][row_t Md][last B]
   const size_t plan_bytes = (sizeof(UttPlan) * (2 * (size_t)B + wins) + 4 * (2 * (size_t)n_fb + 2 * (size_t)n_qb + 2 * (size_t)slots + Me + 3 * (size_t)Md + B + 2 * (size_t)n_dqb) + 15) / 16 * 16;
-  unsigned char* hp = (unsigned char*)pinned(h_plan, h_plan_cap, plan_bytes + sizeof(UttPlan) * B + 12 * (size_t)round_up(B, 128) + 64);
+  h_plan.reserve(plan_bytes + sizeof(UttPlan) * B + 12 * (size_t)round_up(B, 128) + 64);
+  unsigned char* hp = h_plan.as<unsigned char>();
   UttPlan* h_up = (UttPlan*)hp;
   UttPlan* h_wp = h_up + B;
   UttPlan* h_dp = h_wp + wins;
@@ -1387,7 +1358,8 @@ void QwSession::align_head(int B, const UttPlan* ddp, const int32_t* d_src, int 
     HIP_CHECK(hipGetLastError()); }
   if (taps_enabled && n_sel > 0 && want_logits) save_tap("logits", d_logits.ptr, n_sel, c.classify_num, hpad, 4);
   const size_t lbytes = want_logits ? (size_t)n_sel * c.classify_num * 4 : 0;
-  unsigned char* st = (unsigned char*)pinned(h_io, h_io_cap, (size_t)(B + 1 + n_sel) * 4 + 64 + lbytes);
+  h_io.reserve((size_t)(B + 1 + n_sel) * 4 + 64 + lbytes);
+  unsigned char* st = h_io.as<unsigned char>();
   int32_t* h_off = (int32_t*)st;
   int32_t* h_bk = h_off + B + 1;
   float* h_lg = (float*)(st + (size_t)(B + 1 + n_sel) * 4 + 64);
@@ -1419,7 +1391,8 @@ void QwSession::step(const int32_t* ids_host, int32_t* next_out, float* logits_o
                 "qwen_decode: sequence %d was finished by generate() and its cache pages were returned; prefill again", b);
   }
   if (ids_host) {
-    int32_t* st = (int32_t*)pinned(h_ids, h_ids_cap, (size_t)B * 4);
+    h_ids.reserve((size_t)B * 4);
+    int32_t* st = h_ids.as<int32_t>();
     for (int b = 0; b < B; ++b) {
       ASR_REQUIRE(ids_host[b] >= 0 && ids_host[b] < c.vocab, "qwen_decode: token id %d out of range", ids_host[b]);
       st[b] = ids_host[b];
@@ -1442,32 +1415,11 @@ void QwSession::step(const int32_t* ids_host, int32_t* next_out, float* logits_o
   };
   // every step reads its position from the device-side history counters => one captured graph replays for all of them
   const bool graphable = use_graph && !taps_enabled && !prof.enabled && !noise_armed;
-  uint64_t key = 1469598103934665603ull;
+  GraphKey key;
   for (const void* q : {d_x.ptr, d_x2.ptr, d_dh.ptr, d_qkv.ptr, d_q.ptr, d_dctx.ptr, d_xlo.ptr, d_x2lo.ptr, d_act.ptr, d_last.ptr, d_logits.ptr, d_next.ptr, d_kc.ptr,
                         d_vc.ptr, d_kvtab.ptr, d_hist.ptr, d_stepplan.ptr, d_skws.ptr, d_save.ptr, (void*)stream, (void*)(uintptr_t)B, (void*)(uintptr_t)head_epoch})
-    key = (key ^ (uint64_t)(uintptr_t)q) * 1099511628211ull;
-  if (graphable && dec_graph && key == dec_key) {
-    HIP_CHECK(hipGraphLaunch(dec_graph, stream));
-  } else if (graphable && key == dec_eager_key) {
-    if (dec_graph) { (void)hipGraphExecDestroy(dec_graph); dec_graph = nullptr; }
-    hipGraph_t graph = nullptr;
-    HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    try {
-      enqueue();
-    } catch (...) {
-      (void)hipStreamEndCapture(stream, &graph);
-      if (graph) (void)hipGraphDestroy(graph);
-      throw;
-    }
-    HIP_CHECK(hipStreamEndCapture(stream, &graph));
-    HIP_CHECK(hipGraphInstantiate(&dec_graph, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    dec_key = key;
-    HIP_CHECK(hipGraphLaunch(dec_graph, stream));
-  } else {
-    enqueue();                                           // first step of a geometry runs eagerly (lazy kernel attributes, workspaces)
-    if (graphable) dec_eager_key = key;
-  }
+    key.mix(q);
+  dec_graph.run(stream, graphable, key.h, enqueue);
   noise_armed = false;                                   // caller-supplied uniforms serve exactly one step
   for (int b = 0; b < B; ++b) seq_len[b] = std::min(seq_len[b] + 1, c.max_seq_len);
   finish<T>(B, next_out, logits_out, ids_host != nullptr);
@@ -1544,7 +1496,8 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
   DecPass P;
   P.plan = dsp; P.row_seq = (const int32_t*)(dsp + N); P.row_t = P.row_seq + Mb; P.last_rows = P.row_t + Mb; P.rows = N; P.B = N; P.step = true;
   P.kc = d_bkc.ptr; P.vc = d_bvc.ptr; P.S = Sb; P.hist = d_bhist.as<int32_t>(); P.beam_p0 = d_bp0.as<int32_t>(); P.ld_src = ld; P.beam = beam;
-  int32_t* h_done = (int32_t*)pinned(h_ids, h_ids_cap, (size_t)std::max(B, 64) * 4);
+  h_ids.reserve((size_t)std::max(B, 64) * 4);
+  int32_t* h_done = h_ids.as<int32_t>();
   for (int t = 0; t + 1 < max_new; ++t) {
     HIP_CHECK(hipMemcpyAsync(h_done, d_bdone.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));

@@ -56,28 +56,8 @@ struct SvSession : asr_session {
   DeviceBuffer d_x0lo, d_xalo, d_xblo;     // bf16 copies of the residual stream (operands of the LayerNorm-fused projections)
   DeviceBuffer d_plan, d_audio, d_mel, d_x0, d_xa, d_xb, d_h, d_qk, d_vt, d_ctx, d_mem, d_ffn, d_amax_v, d_amax_i, d_ids,
       d_tok, d_num, d_logits;
-  void* h_plan = nullptr;   // pinned staging
-  size_t h_plan_cap = 0;
-  void* h_out = nullptr;
-  size_t h_out_cap = 0;
+  PinnedBuffer h_plan, h_out;   // pinned staging
 
-  ~SvSession() override {
-    for (DeviceBuffer* b : {&d_dft_split, &d_times, &d_flags, &d_tpack, &d_tlayer_tab, &d_tkv, &d_ctplan, &d_mdev, &d_trow, &d_skws, &d_skcnt, &d_sta, &d_stb, &st_segs, &st_shadow, &st_wpack, &st_layer_tab, &st_flags, &st_times, &st_dpack, &st_dlayer_tab, &st_enk, &st_env, &st_dek, &st_dev, &st_defsmn, &st_prev, &st_cifh, &st_cifa, &st_enlen, &st_delen, &st_start, &d_sqkv, &d_skv,
-                            &d_x0lo, &d_xalo, &d_xblo, &d_plan, &d_audio, &d_mel, &d_x0, &d_xa, &d_xb, &d_h, &d_qk, &d_vt, &d_ctx, &d_mem, &d_ffn,
-                            &d_amax_v, &d_amax_i, &d_ids, &d_tok, &d_num, &d_logits, &d_enc_lo, &d_ck, &d_wk_all, &d_wv_all, &d_bk_all, &d_bv_all, &d_cifa, &d_alpha, &d_dec, &d_x2,
-                            &d_sa, &d_ffn32, &d_tplan})
-      b->release();
-    for (auto& kv : taps) kv.second.buf.release();
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    for (hipGraphExec_t g : st_graph) if (g) (void)hipGraphExecDestroy(g);
-    if (h_plan) (void)hipHostFree(h_plan);
-    if (h_out) (void)hipHostFree(h_out);
-    prof.release();
-    arena.release();
-    if (own_stream && stream) (void)hipStreamDestroy(stream);
-  }
-
-  // hipGraph replay of the forward pass (one graph per batch geometry)
   // ---- streaming Paraformer (kind 4): per-stream recurrent state in HBM, every step advances n streams by one chunk
   int st_chunk = 0, st_B = 0, st_C = 0, st_en_cap = 0, st_de_cap = 0, st_max = 0, st_frames = 0;
   DeviceBuffer st_enk, st_env, st_dek, st_dev, st_defsmn, st_prev, st_cifh, st_cifa, st_enlen, st_delen, st_start, d_sqkv, d_skv;
@@ -152,9 +132,9 @@ struct SvSession : asr_session {
   int block_min_utts = 12;      // ASR_SANM_BLOCK_MIN=<windows>: smallest batch that takes the block kernel (8-wave form: faster from ~10 windows on; tools/probes/block_min_sweep.sh)
   DeviceBuffer d_times; int block_dbg = -1;   // ASR_SANM_BLOCK_DBG=<block index>: phase clock of that block's launch on stderr
   DeviceBuffer d_flags;         // exchange counters of the block kernel: [n_blocks][batch][4] + the error word at the end
-  hipGraphExec_t graph_exec = nullptr;
-  uint64_t graph_key = 0, eager_key = 0, ws_epoch = 1;
-  hipGraphExec_t st_graph[3] = {nullptr, nullptr, nullptr}; uint64_t st_graph_key[3] = {0, 0, 0}, st_eager_key[3] = {0, 0, 0};     // streaming chunk step: per-launch / fused / fused + snapshot
+  StepGraph graph;              // hipGraph replay of the forward pass (one graph per batch geometry)
+  uint64_t ws_epoch = 1;
+  StepGraph st_graph[3];        // streaming chunk step: per-launch / fused / fused + snapshot
 
   void init();
   void copy_block_status(const struct SvRunCtx& r);   // the block kernel's error word rides home behind the token counts
@@ -318,7 +298,7 @@ void SvSession::ensure_block_pack() {
 
 void SvSession::copy_block_status(const SvRunCtx& r) {
   const size_t flag_words = (size_t)cfg.n_blocks * r.batch * 4;
-  HIP_CHECK(hipMemcpyAsync((unsigned char*)h_out + (size_t)r.batch * r.max_tokens * 4 + (size_t)r.batch * 4, d_flags.as<unsigned>() + flag_words, 4,
+  HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)r.batch * r.max_tokens * 4 + (size_t)r.batch * 4, d_flags.as<unsigned>() + flag_words, 4,
                            hipMemcpyDeviceToHost, stream));
 }
 
@@ -596,8 +576,8 @@ void SvSession::enqueue(const SvRunCtx& r) {
     save_tap("frame_ids", d_ids.ptr, rows, 1, 1, 4);
   }
   // ---- outputs (pinned host staging) ---------------------------------------------------------
-  HIP_CHECK(hipMemcpyAsync(h_out, d_tok.ptr, (size_t)r.batch * r.max_tokens * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync((unsigned char*)h_out + (size_t)r.batch * r.max_tokens * 4, d_num.ptr, (size_t)r.batch * 4,
+  HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, (size_t)r.batch * r.max_tokens * 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)r.batch * r.max_tokens * 4, d_num.ptr, (size_t)r.batch * 4,
                            hipMemcpyDeviceToHost, stream));
   copy_block_status(r);
 }
@@ -729,8 +709,8 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
     launch_gather_tokens(d_ids.as<int32_t>(), tplan, r.batch, d_tok.as<int32_t>(), r.max_tokens, stream);
   }
   if (taps_enabled) save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
-  HIP_CHECK(hipMemcpyAsync(h_out, d_tok.ptr, (size_t)r.batch * r.max_tokens * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync((unsigned char*)h_out + (size_t)r.batch * r.max_tokens * 4, d_num.ptr, (size_t)r.batch * 4,
+  HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, (size_t)r.batch * r.max_tokens * 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)r.batch * r.max_tokens * 4, d_num.ptr, (size_t)r.batch * 4,
                            hipMemcpyDeviceToHost, stream));
 }
 
@@ -752,8 +732,7 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
   SvRunCtx r{};
   int rows = 0, frames = 0, n_fb = 0, n_qb = 0, max_T = 0;
   const int64_t base0 = offs[0];
-  uint64_t key = 1469598103934665603ull;                 // FNV-1a over everything that shapes the launch sequence
-  auto mix = [&](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
+  GraphKey key;                                          // everything that shapes the launch sequence
   for (int b = 0; b < batch; ++b) {
     const int64_t n = offs[b + 1] - offs[b];
     ASR_REQUIRE(n >= c.win_length, "sensevoice: utterance %d has %lld samples (< one %d-sample frame)", b, (long long)n, c.win_length);
@@ -773,7 +752,7 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
     rows += round_up(p.T, 16);
     n_fb += (p.n_frames + 63) / 64;
     max_T = std::max(max_T, p.T);
-    mix((uint64_t)n);
+    key.mix((uint64_t)n);
   }
   ASR_REQUIRE(max_tokens >= 1, "sensevoice: max_tokens must be positive");
   int att_qt = 0, att_nw = 4, q_rows = 64;             // f32 kernel: fixed 64-row query blocks
@@ -785,13 +764,8 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
   // plan blob: [UttPlan x B][blk_utt n_fb][blk_f0 n_fb][qb_utt n_qb][qb_q0 n_qb][row_utt Mpad]
   const int n_tiles = rows / 16;
   const size_t plan_bytes = sizeof(UttPlan) * batch + sizeof(int32_t) * (2 * (size_t)n_fb + 2 * (size_t)n_qb + Mpad + 2 * (size_t)n_tiles);
-  if (plan_bytes > h_plan_cap) {
-    if (h_plan) HIP_CHECK(hipHostFree(h_plan));
-    HIP_CHECK(hipHostMalloc(&h_plan, plan_bytes * 2, hipHostMallocDefault));
-    h_plan_cap = plan_bytes * 2;
-    ++ws_epoch;
-  }
-  unsigned char* hp = (unsigned char*)h_plan;
+  if (h_plan.reserve(plan_bytes)) ++ws_epoch;
+  unsigned char* hp = h_plan.as<unsigned char>();
   memcpy(hp, plan.data(), sizeof(UttPlan) * batch);
   int32_t* blk_utt = (int32_t*)(hp + sizeof(UttPlan) * batch);
   int32_t* blk_f0 = blk_utt + n_fb;
@@ -817,7 +791,7 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
   const bool tiles = sizeof(T) == 2 && use_tiles && c.n_blocks > 1 && blocks[c.n_blocks - 1].cqkv && blocks[c.n_blocks - 1].c1 &&
                      !(use_block && batch >= block_min_utts) && n_tiles <= sanm_tiles_max_tiles() &&
                      sanm_tiles_supported(max_T, d, dff, c.n_heads, c.d_head, c.fsmn_kernel);
-  mix((uint64_t)tiles);
+  key.mix((uint64_t)tiles);
   // ---- workspace (grow-only; any re-allocation invalidates the captured graph) -----------------
   const size_t eT = sizeof(T);
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { void* before = buf.ptr; buf.reserve(bytes, stream); if (buf.ptr != before) ++ws_epoch; };
@@ -867,14 +841,9 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
     grow(d_trow, (size_t)Mpad * 4);
   }
   const size_t out_bytes = (size_t)batch * max_tokens * 4 + (size_t)batch * 4 + 16;
-  if (out_bytes > h_out_cap) {
-    if (h_out) HIP_CHECK(hipHostFree(h_out));
-    HIP_CHECK(hipHostMalloc(&h_out, out_bytes * 2, hipHostMallocDefault));
-    h_out_cap = out_bytes * 2;
-    ++ws_epoch;
-  }
+  if (h_out.reserve(out_bytes)) ++ws_epoch;
 
-  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan, plan_bytes, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan.ptr, plan_bytes, hipMemcpyHostToDevice, stream));
   if (audio_mem == ASR_MEM_HOST) {
     HIP_CHECK(hipMemcpyAsync(d_audio.ptr, audio + base0, (size_t)total_samples * 4, hipMemcpyHostToDevice, stream));
     r.d_aud = d_audio.as<float>();
@@ -892,8 +861,8 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
   r.d_row_utt = r.d_qb_q0 + n_qb;
   r.d_tile_win = r.d_row_utt + Mpad;
   r.d_tile_idx = r.d_tile_win + n_tiles;
-  mix((uint64_t)batch); mix((uint64_t)max_tokens); mix((uint64_t)(uintptr_t)r.d_aud); mix(ws_epoch); mix((uint64_t)(uintptr_t)stream);
-  mix((uint64_t)(block_cooldown > 0 || foreign_now));        // a session cooling down after a cluster give-up replays the four-launch capture, not the block one
+  key.mix((uint64_t)batch); key.mix((uint64_t)max_tokens); key.mix((uint64_t)(uintptr_t)r.d_aud); key.mix(ws_epoch); key.mix((uint64_t)(uintptr_t)stream);
+  key.mix((uint64_t)(block_cooldown > 0 || foreign_now));        // a session cooling down after a cluster give-up replays the four-launch capture, not the block one
 
   if (sizeof(T) == 2 && use_block && cfg.n_blocks > 1 && blocks[cfg.n_blocks - 1].cqkv && blocks[cfg.n_blocks - 1].c1 && batch >= block_min_utts &&
       sanm_block_supported(max_T, cfg.d_head, cfg.n_heads, cfg.d_model, cfg.d_ffn, cfg.fsmn_kernel))
@@ -901,29 +870,7 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
   if (tiles) ensure_tiles_pack();
   // ---- launch: eager the first time a geometry is seen (allocations settle), then capture once and replay ----
   // 570 launches per forward are host-launch-bound when issued eagerly (~13 us each); replay costs ~1 us per node.
-  const bool graphable = use_graph && !taps_enabled && !prof.enabled;
-  if (graphable && graph_exec && key == graph_key) {
-    HIP_CHECK(hipGraphLaunch(graph_exec, stream));
-  } else if (graphable && key == eager_key) {
-    if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
-    hipGraph_t graph = nullptr;
-    HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    try {
-      enqueue<T>(r);
-    } catch (...) {
-      (void)hipStreamEndCapture(stream, &graph);
-      if (graph) (void)hipGraphDestroy(graph);
-      throw;
-    }
-    HIP_CHECK(hipStreamEndCapture(stream, &graph));
-    HIP_CHECK(hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    graph_key = key;
-    HIP_CHECK(hipGraphLaunch(graph_exec, stream));
-  } else {
-    enqueue<T>(r);
-    eager_key = key;
-  }
+  graph.run(stream, use_graph && !taps_enabled && !prof.enabled, key.h, [&] { enqueue<T>(r); });
   HIP_CHECK(hipStreamSynchronize(stream));
   if (prof.enabled) prof.collect();
   if (tiles_dbg >= 0 && tiles && d_times.ptr) {          // tuning: mean phase intervals of one block of the tile kernel over its workgroups (100 MHz clock -> us)
@@ -978,20 +925,20 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
     // with another session's clusters until the bounded spin gives up. Such a forward pass is void: it is redone here on the four-launch
     // path (no cross-workgroup waits), still on the GPU; the error is raised only if that fails too.
     unsigned blk_err = 0;
-    memcpy(&blk_err, (unsigned char*)h_out + (size_t)batch * max_tokens * 4 + (size_t)batch * 4, 4);
+    memcpy(&blk_err, h_out.as<unsigned char>() + (size_t)batch * max_tokens * 4 + (size_t)batch * 4, 4);
     if (blk_err != 0 && (use_block || use_tiles)) {
       if (block_giveups++ == 0)
         fprintf(stderr, "[asr_mi355x] sanm_block: a workgroup gave up waiting for its cluster; the batch is redone on the four-launch path\n");
       block_cooldown = 16;                       // this batch and the next ones stay on the four-launch path
       enqueue<T>(r);
       HIP_CHECK(hipStreamSynchronize(stream));
-      memcpy(&blk_err, (unsigned char*)h_out + (size_t)batch * max_tokens * 4 + (size_t)batch * 4, 4);
+      memcpy(&blk_err, h_out.as<unsigned char>() + (size_t)batch * max_tokens * 4 + (size_t)batch * 4, 4);
     }
     else if (block_cooldown > 0) --block_cooldown;
     ASR_REQUIRE(blk_err == 0, "sensevoice: a SANM block workgroup gave up waiting for its cluster (results are invalid)");
   }
-  memcpy(num_out, (unsigned char*)h_out + (size_t)batch * max_tokens * 4, (size_t)batch * 4);
-  const int32_t* ht = (const int32_t*)h_out;
+  memcpy(num_out, h_out.as<unsigned char>() + (size_t)batch * max_tokens * 4, (size_t)batch * 4);
+  const int32_t* ht = h_out.as<const int32_t>();
   for (int b = 0; b < batch; ++b) {
     const int n = std::min(num_out[b], max_tokens);
     memcpy(tok_out + (size_t)b * max_tokens, ht + (size_t)b * max_tokens, (size_t)n * 4);
@@ -1150,13 +1097,9 @@ void SvSession::stream_step(const float* audio, int audio_mem, const int32_t* st
   std::vector<char> seen(st_max, 0);
   // ---- plan: one 16-row slot / one fbank workgroup per active stream
   const size_t plan_bytes = sizeof(UttPlan) * n + sizeof(int32_t) * (2 * (size_t)n + Mpad);
-  if (plan_bytes > h_plan_cap) {
-    if (h_plan) HIP_CHECK(hipHostFree(h_plan));
-    HIP_CHECK(hipHostMalloc(&h_plan, plan_bytes * 2, hipHostMallocDefault));
-    h_plan_cap = plan_bytes * 2;
-  }
-  UttPlan* hp = (UttPlan*)h_plan;
-  int32_t* blk_utt = (int32_t*)((unsigned char*)h_plan + sizeof(UttPlan) * n);
+  h_plan.reserve(plan_bytes);
+  UttPlan* hp = h_plan.as<UttPlan>();
+  int32_t* blk_utt = (int32_t*)(h_plan.as<unsigned char>() + sizeof(UttPlan) * n);
   int32_t* blk_f0 = blk_utt + n;
   int32_t* row_utt = blk_f0 + n;
   for (int i = 0; i < n; ++i) {
@@ -1203,12 +1146,8 @@ void SvSession::stream_step(const float* audio, int audio_mem, const int32_t* st
     grow(d_stb, (size_t)Mpad * (d / 32) * 8);
   }
   const size_t out_bytes = (size_t)n * max_tokens * 4 + (size_t)n * 4;
-  if (out_bytes + 16 > h_out_cap) {
-    if (h_out) HIP_CHECK(hipHostFree(h_out));
-    HIP_CHECK(hipHostMalloc(&h_out, out_bytes * 2 + 16, hipHostMallocDefault));
-    h_out_cap = out_bytes * 2 + 16;
-  }
-  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan, plan_bytes, hipMemcpyHostToDevice, stream));
+  h_out.reserve(out_bytes + 16);
+  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan.ptr, plan_bytes, hipMemcpyHostToDevice, stream));
   const float* d_aud = audio;
   if (audio_mem == ASR_MEM_HOST) {
     HIP_CHECK(hipMemcpyAsync(d_audio.ptr, audio, (size_t)n * st_chunk * 4, hipMemcpyHostToDevice, stream));
@@ -1473,47 +1412,22 @@ void SvSession::stream_step(const float* audio, int audio_mem, const int32_t* st
   launch_stream_advance(dp, tplan, n, st_B, st_en_cap, n_cur, st_de_cap, st_enlen.as<int32_t>(), st_delen.as<int32_t>(), stream);
   };
   {
-    const bool graphable = use_graph && !taps_enabled && !prof.enabled;
-    uint64_t key = 1469598103934665603ull;
+    GraphKey key;
     for (const void* q : {(const void*)d_aud, (const void*)d_plan.ptr, (const void*)d_mel.ptr, (const void*)d_x0.ptr, (const void*)d_xa.ptr, (const void*)d_xb.ptr,
                           (const void*)d_h.ptr, (const void*)d_sqkv.ptr, (const void*)d_skv.ptr, (const void*)d_qk.ptr, (const void*)d_ctx.ptr, (const void*)d_mem.ptr,
                           (const void*)d_ffn.ptr, (const void*)d_amax_v.ptr, (const void*)d_amax_i.ptr, (const void*)d_ids.ptr, (const void*)d_tok.ptr, (const void*)d_num.ptr,
                           (const void*)d_logits.ptr, (const void*)d_enc_lo.ptr, (const void*)d_cifa.ptr, (const void*)d_alpha.ptr, (const void*)d_dec.ptr, (const void*)d_x2.ptr,
                           (const void*)d_sa.ptr, (const void*)d_ffn32.ptr, (const void*)d_tplan.ptr, (const void*)stream, (const void*)(uintptr_t)n,
                           (const void*)(uintptr_t)max_tokens, (const void*)st_shadow.ptr, (const void*)d_xblo.ptr, (const void*)d_stb.ptr})
-      key = (key ^ (uint64_t)(uintptr_t)q) * 1099511628211ull;
+      key.mix(q);
     const int gi = step_fused ? (snapshot ? 2 : 1) : 0;            // one cached graph per path: a session that alternates (a co-tenant comes and goes) does not re-capture
-    hipGraphExec_t& st_graph = this->st_graph[gi];
-    uint64_t& st_graph_key = this->st_graph_key[gi];
-    uint64_t& st_eager_key = this->st_eager_key[gi];
-    if (graphable && !inject_fault && st_graph && key == st_graph_key) {
-      HIP_CHECK(hipGraphLaunch(st_graph, stream));
-    } else if (graphable && !inject_fault && key == st_eager_key) {
-      if (st_graph) { (void)hipGraphExecDestroy(st_graph); st_graph = nullptr; }
-      hipGraph_t graph = nullptr;
-      HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-      try {
-        enqueue();
-      } catch (...) {
-        (void)hipStreamEndCapture(stream, &graph);
-        if (graph) (void)hipGraphDestroy(graph);
-        throw;
-      }
-      HIP_CHECK(hipStreamEndCapture(stream, &graph));
-      HIP_CHECK(hipGraphInstantiate(&st_graph, graph, nullptr, nullptr, 0));
-      (void)hipGraphDestroy(graph);
-      st_graph_key = key;
-      HIP_CHECK(hipGraphLaunch(st_graph, stream));
-    } else {
-      enqueue();                                         // first step of a geometry runs eagerly (lazy kernel attributes, workspaces)
-      if (graphable && !inject_fault) st_eager_key = key;
-    }
+    st_graph[gi].run(stream, use_graph && !taps_enabled && !prof.enabled && !inject_fault, key.h, enqueue);
   }
   if (taps_enabled) save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
-  HIP_CHECK(hipMemcpyAsync(h_out, d_tok.ptr, (size_t)n * max_tokens * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync((unsigned char*)h_out + (size_t)n * max_tokens * 4, d_num.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, (size_t)n * max_tokens * 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)n * max_tokens * 4, d_num.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
   const bool fused_ran = step_fused;
-  unsigned* h_err = (unsigned*)((unsigned char*)h_out + out_bytes);
+  unsigned* h_err = (unsigned*)(h_out.as<unsigned char>() + out_bytes);
   *h_err = 0;
   if (fused_ran)
     HIP_CHECK(hipMemcpyAsync(h_err, st_flags.as<unsigned>() + (size_t)(c.n_blocks - 1) * n * 4, 4, hipMemcpyDeviceToHost, stream));
@@ -1546,16 +1460,16 @@ void SvSession::stream_step(const float* audio, int audio_mem, const int32_t* st
     launch_stream_state_copy(st_segs.as<StreamStateSeg>(), st_n_segs, st_n_items, dp, n, true, stream);
     step_fused = false; snapshot = false;
     enqueue();
-    HIP_CHECK(hipMemcpyAsync(h_out, d_tok.ptr, (size_t)n * max_tokens * 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipMemcpyAsync((unsigned char*)h_out + (size_t)n * max_tokens * 4, d_num.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, (size_t)n * max_tokens * 4, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)n * max_tokens * 4, d_num.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     if (prof.enabled) prof.collect();
     *h_err = 0;
   }
   ASR_REQUIRE(*h_err == 0, "streaming: a workgroup of the fused encoder launch gave up waiting for its cluster and no snapshot was taken (ASR_STREAM_SNAPSHOT=0, or no other "
               "session existed on this GPU when the step started); the step's results are invalid, reset its streams");
-  memcpy(num_out, (unsigned char*)h_out + (size_t)n * max_tokens * 4, (size_t)n * 4);
-  const int32_t* ht = (const int32_t*)h_out;
+  memcpy(num_out, h_out.as<unsigned char>() + (size_t)n * max_tokens * 4, (size_t)n * 4);
+  const int32_t* ht = h_out.as<const int32_t>();
   for (int i = 0; i < n; ++i) memcpy(tok_out + (size_t)i * max_tokens, ht + (size_t)i * max_tokens, (size_t)std::min(num_out[i], max_tokens) * 4);
 }
 

@@ -110,38 +110,17 @@ struct WhSession : asr_session {
   bool fp8 = false, fp8_fake = false, fp8_weights = true, fp8_kv = true;     // ASR_FP8_WEIGHTS=0 / ASR_FP8_KV=0: leave that half in bf16 (to price the halves separately)
   std::vector<Dec8Layer> dec8;
   DeviceBuffer d_w8, d_wscale, d_wdq, d_cross8, d_cscale;
-  hipGraphExec_t dec_graph = nullptr;      // the whole single-token step
-  hipGraphExec_t beam_graph[2] = {nullptr, nullptr};       // the beam-search step, one per ancestry-table parity
-  uint64_t beam_key[2] = {0, 0};
-  void drop_graphs() {
-    if (dec_graph) { (void)hipGraphExecDestroy(dec_graph); dec_graph = nullptr; }
-    for (auto& g : beam_graph) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-  }
+  StepGraph dec_graph;                 // the whole single-token step
+  StepGraph beam_graph[2];             // the beam-search step, one per ancestry-table parity
   // Beam search (asr_whisper_beam_search): hypothesis rows b * beam + r, each with its own self-K/V extent of S = prompt + max_new - 1 slots in d_bext
   // [layer][row][K | V][head][S][64] (large-v3, 160 rows x 447 slots: 11.7 GB; kept for the next search), ancestry / token tables (double-buffered), ranking
   // state and logits of its own: the session's pages, block table, history, ids and logits are left as the prefill left them.
   DeviceBuffer d_bext, d_bhist, d_bsrc[2], d_btok[2], d_bcum, d_bfin, d_blen, d_bdone, d_btopv, d_btopi, d_bstop, d_bnext, d_blogits;
   bool after_prefill = false;          // the last call on the session was a prefill (or a beam search, which leaves its state as it was)
-  uint64_t dec_key = 0, dec_eager_key = 0, ws_epoch = 1;
-  void* h_plan = nullptr; size_t h_plan_cap = 0;
-  void* h_io = nullptr; size_t h_io_cap = 0;
-  int32_t* h_beam = nullptr; size_t h_beam_cap = 0;   // beam search's own pinned staging: [0] eos id, [1] prompt length, [16 ..) done flags
+  uint64_t ws_epoch = 1;
+  PinnedBuffer h_plan, h_io;
+  PinnedBuffer h_beam;                 // beam search's own pinned staging: [0] eos id, [1] prompt length, [16 ..) done flags
 
-  ~WhSession() override {
-    for (DeviceBuffer* b : {&d_plan, &d_audio, &d_mel, &d_blkmax, &d_x0, &d_h1, &d_xa, &d_xb, &d_xc, &d_h, &d_qk, &d_vt, &d_ctx,
-                            &d_ffn, &d_cross, &d_kc, &d_vc, &d_kvpool, &d_ptable, &d_ids, &d_next, &d_logits, &d_dx, &d_dqkv, &d_dtok, &d_hist, &d_save, &d_nsaved, &d_noise, &d_nsp, &d_skws, &d_skcnt, &d_colsum, &d_dlo, &d_w8, &d_wscale, &d_wdq, &d_cross8, &d_cscale, &d_ew8, &d_ewscale, &d_h8, &d_ffn8, &d_sat,
-                            &d_bext, &d_bhist, &d_bsrc[0], &d_bsrc[1], &d_btok[0], &d_btok[1], &d_bcum, &d_bfin, &d_blen, &d_bdone, &d_btopv, &d_btopi, &d_bstop,
-                            &d_bnext, &d_blogits})
-      b->release();
-    drop_graphs();
-    for (auto& kv : taps) kv.second.buf.release();
-    if (h_plan) (void)hipHostFree(h_plan);
-    if (h_io) (void)hipHostFree(h_io);
-    if (h_beam) (void)hipHostFree(h_beam);
-    prof.release();
-    arena.release();
-    if (own_stream && stream) (void)hipStreamDestroy(stream);
-  }
   void init();
   DeviceBuffer d_skws, d_skcnt;        // split-K workspace + tickets of the skinny / decode GEMM (per session: sessions may run concurrently)
   static constexpr int SK_CNT = 4096;
@@ -152,14 +131,6 @@ struct WhSession : asr_session {
     GemmArgs g = g0;
     g.sk_ws = d_skws.as<float>(); g.sk_ws_bytes = SK_WS_BYTES; g.sk_cnt = d_skcnt.as<int32_t>();
     launch_gemm_bf16(g, stream);
-  }
-  void* pinned(size_t bytes) {
-    if (bytes > h_io_cap) {
-      if (h_io) HIP_CHECK(hipHostFree(h_io));
-      HIP_CHECK(hipHostMalloc(&h_io, bytes * 2, hipHostMallocDefault));
-      h_io_cap = bytes * 2;
-    }
-    return h_io;
   }
   template <typename T> void encode(const float* audio, int audio_mem, const int64_t* offs, int B, int32_t* n_pos_out);
   template <typename T> void enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev, const BeamStep* bs = nullptr);
@@ -308,12 +279,8 @@ void WhSession::encode(const float* audio, int audio_mem, const int64_t* offs, i
 
   // plan blob: [UttPlan B (encoder rows)][UttPlan B (stem rows)][blk_utt][blk_f0][qb_utt][qb_q0][row_utt Mpad][pos_rows Mg][grow_utt R]
   const size_t plan_bytes = 2 * sizeof(UttPlan) * B + 4 * (2 * (size_t)n_fb + 2 * (size_t)n_qb + (size_t)Mpad + (size_t)Mg + R);
-  if (plan_bytes > h_plan_cap) {
-    if (h_plan) HIP_CHECK(hipHostFree(h_plan));
-    HIP_CHECK(hipHostMalloc(&h_plan, plan_bytes * 2, hipHostMallocDefault));
-    h_plan_cap = plan_bytes * 2;
-  }
-  unsigned char* hp = (unsigned char*)h_plan;
+  h_plan.reserve(plan_bytes);
+  unsigned char* hp = h_plan.as<unsigned char>();
   memcpy(hp, plan.data(), sizeof(UttPlan) * B);
   memcpy(hp + sizeof(UttPlan) * B, splan.data(), sizeof(UttPlan) * B);
   int32_t* blk_utt = (int32_t*)(hp + 2 * sizeof(UttPlan) * B);
@@ -341,7 +308,7 @@ void WhSession::encode(const float* audio, int audio_mem, const int64_t* offs, i
     }
   }
   { void* before = d_plan.ptr; d_plan.reserve(plan_bytes, stream); if (d_plan.ptr != before) ++ws_epoch; }
-  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan, plan_bytes, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan.ptr, plan_bytes, hipMemcpyHostToDevice, stream));
   const UttPlan* dp = d_plan.as<UttPlan>();
   const UttPlan* dps = dp + B;                            // stem rows
   const int32_t* d_blk_utt = (const int32_t*)((unsigned char*)d_plan.ptr + 2 * sizeof(UttPlan) * B);
@@ -731,18 +698,13 @@ void WhSession::ensure_kv_pages(int B, int positions, size_t elem_bytes) {
   if (bytes > d_kvpool.cap) {
     DeviceBuffer fresh;
     fresh.reserve(bytes, stream);
-    try {
-      if (hist > 0 && old_bytes) HIP_CHECK(hipMemcpyAsync(fresh.ptr, d_kvpool.ptr, old_bytes, hipMemcpyDeviceToDevice, stream));
-      HIP_CHECK(hipStreamSynchronize(stream));
-    } catch (...) {
-      fresh.release();                   // (DeviceBuffer has no destructor: a failed copy must not leak the new pool)
-      throw;
-    }
-    d_kvpool.release();
-    d_kvpool = fresh;
+    if (hist > 0 && old_bytes) HIP_CHECK(hipMemcpyAsync(fresh.ptr, d_kvpool.ptr, old_bytes, hipMemcpyDeviceToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    d_kvpool = std::move(fresh);
   }
   d_ptable.reserve((size_t)B * P * 4, stream);
-  int32_t* tab = (int32_t*)pinned((size_t)B * P * 4 + 64);
+  h_io.reserve((size_t)B * P * 4 + 64);
+  int32_t* tab = h_io.as<int32_t>();
   for (int b = 0; b < B; ++b)
     for (int j = 0; j < P; ++j) tab[(size_t)b * P + j] = j < gens ? j * B + (kv_shuffle ? (B - 1 - b + j) % B : b) : -1;
   HIP_CHECK(hipMemcpyAsync(d_ptable.ptr, tab, (size_t)B * P * 4, hipMemcpyHostToDevice, stream));
@@ -777,7 +739,8 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
   grow(d_dqkv, (size_t)Rp * (3 * d + d + d + dff + d) * eT + (size_t)Bp * d * eT);
   const int32_t* ids_dev;
   if (ids_host) {
-    int32_t* stage = (int32_t*)pinned((size_t)R * 4 + 64);
+    h_io.reserve((size_t)R * 4 + 64);
+    int32_t* stage = h_io.as<int32_t>();
     for (int i = 0; i < R; ++i) {
       ASR_REQUIRE(ids_host[i] >= 0 && ids_host[i] < c.vocab, "whisper: token id %d out of range", ids_host[i]);
       stage[i] = ids_host[i];
@@ -794,39 +757,14 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
   }
   // single-token steps fed from the device are position independent => one graph for all of them
   const bool graphable = use_graph && !ids_host && n == 1 && !taps_enabled && !prof.enabled && !noise_armed;
-  const uint64_t key = ((uint64_t)B << 32) ^ (uint64_t)Mpad ^ (ws_epoch << 48) ^ (uint64_t)(uintptr_t)stream;
-  auto capture = [&](hipStream_t cs) {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    HIP_CHECK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-    try {
-      enqueue_step<T>(ids_dev, 1, false, true);
-    } catch (...) {
-      (void)hipStreamEndCapture(cs, &graph);
-      if (graph) (void)hipGraphDestroy(graph);
-      throw;
-    }
-    HIP_CHECK(hipStreamEndCapture(cs, &graph));
-    HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    return exec;
-  };
-  if (graphable && dec_graph && key == dec_key) {
-    HIP_CHECK(hipGraphLaunch(dec_graph, stream));
-  } else if (graphable && key == dec_eager_key) {
-    drop_graphs();
-    dec_graph = capture(stream);
-    dec_key = key;
-    HIP_CHECK(hipGraphLaunch(dec_graph, stream));
-  } else {
-    enqueue_step<T>(ids_dev, n, is_prefill, true);
-    if (graphable) dec_eager_key = key;
-  }
+  const uint64_t key = GraphKey().mix((uint64_t)B).mix((uint64_t)Mpad).mix(ws_epoch).mix(stream).h;
+  dec_graph.run(stream, graphable, key, [&] { enqueue_step<T>(ids_dev, n, is_prefill, true); });
   hist += n;
   noise_armed = false;                   // caller-supplied uniforms serve exactly one step
   if (taps_enabled) save_tap("logits", d_logits.ptr, B, c.vocab, vpad, 4);
   if (next_out || logits_out) {
-    unsigned char* st = (unsigned char*)pinned((size_t)B * 4 + (logits_out ? (size_t)B * c.vocab * 4 : 0));
+    h_io.reserve((size_t)B * 4 + (logits_out ? (size_t)B * c.vocab * 4 : 0));
+    unsigned char* st = h_io.as<unsigned char>();
     if (next_out) HIP_CHECK(hipMemcpyAsync(st, d_next.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
     if (logits_out)
       HIP_CHECK(hipMemcpy2DAsync(st + (size_t)B * 4, (size_t)c.vocab * 4, d_logits.ptr, (size_t)vpad * 4, (size_t)c.vocab * 4, B,
@@ -871,13 +809,8 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   // a prefill called with null outputs may still be copying from the shared staging buffer: the search starts behind it and stages through its own
   HIP_CHECK(hipStreamSynchronize(stream));
   const size_t stage_bytes = (size_t)(16 + std::max(B, 64)) * 4;
-  if (stage_bytes > h_beam_cap) {
-    if (h_beam) HIP_CHECK(hipHostFree(h_beam));
-    h_beam = nullptr; h_beam_cap = 0;
-    HIP_CHECK(hipHostMalloc((void**)&h_beam, stage_bytes, hipHostMallocDefault));
-    h_beam_cap = stage_bytes;
-  }
-  int32_t* hs = h_beam;
+  h_beam.reserve(stage_bytes);
+  int32_t* hs = h_beam.as<int32_t>();
   hs[0] = eos_id; hs[1] = p0;
   HIP_CHECK(hipMemcpyAsync(d_bstop.ptr, hs, 4, hipMemcpyHostToDevice, stream));
   HIP_CHECK(hipMemcpyAsync(d_bhist.ptr, hs + 1, 4, hipMemcpyHostToDevice, stream));
@@ -911,10 +844,10 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   bs.topv = d_btopv.as<float>(); bs.topi = d_btopi.as<int32_t>();
   bs.ba = ba; bs.ba.first = 0; bs.ba.slots_dev = d_bhist.as<int32_t>(); bs.ba.slots_off = 1 - p0;   // the pass at position p fills generated slot p - p0
   const bool graphable = use_graph && !taps_enabled && !prof.enabled;
-  uint64_t key = 1469598103934665603ull;                    // everything the captured step bakes in
+  GraphKey key;                                             // everything the captured step bakes in
   for (uint64_t v : {(uint64_t)B, (uint64_t)beam, (uint64_t)S, (uint64_t)p0, (uint64_t)ld, (uint64_t)n_stop, (uint64_t)Mpad, ws_epoch, (uint64_t)(uintptr_t)stream})
-    key = (key ^ v) * 1099511628211ull;
-  int32_t* h_done = h_beam + 16;
+    key.mix(v);
+  int32_t* h_done = hs + 16;
   for (int t = 0; t + 1 < max_new; ++t) {
     HIP_CHECK(hipMemcpyAsync(h_done, d_bdone.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -923,27 +856,7 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
     if (all) break;
     bs.src = d_bsrc[cur].as<int32_t>();
     tables(bs.ba);
-    if (graphable && t >= 2) {                              // (the first pass of each parity runs eagerly: lazily created workspaces exist before capture)
-      if (!beam_graph[cur] || beam_key[cur] != key) {
-        if (beam_graph[cur]) { (void)hipGraphExecDestroy(beam_graph[cur]); beam_graph[cur] = nullptr; }
-        hipGraph_t graph = nullptr;
-        HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        try {
-          enqueue_step<T>(d_bnext.as<int32_t>(), beam, false, true, &bs);
-        } catch (...) {
-          (void)hipStreamEndCapture(stream, &graph);
-          if (graph) (void)hipGraphDestroy(graph);
-          throw;
-        }
-        HIP_CHECK(hipStreamEndCapture(stream, &graph));
-        HIP_CHECK(hipGraphInstantiate(&beam_graph[cur], graph, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(graph);
-        beam_key[cur] = key;
-      }
-      HIP_CHECK(hipGraphLaunch(beam_graph[cur], stream));
-    } else {
-      enqueue_step<T>(d_bnext.as<int32_t>(), beam, false, true, &bs);
-    }
+    beam_graph[cur].run(stream, graphable, key.h, [&] { enqueue_step<T>(d_bnext.as<int32_t>(), beam, false, true, &bs); });
     cur ^= 1;
   }
   HIP_CHECK(hipGetLastError());

@@ -115,6 +115,10 @@ int asr_probe_beam_select(asr_probe_beam_select_desc* d);
  * count, so reset, run a session once on a new batch geometry, read). reset != 0 clears the counters after the read. */
 int asr_probe_gemm_counts(int reset, char* buf, int cap);
 
+/* device bytes held, process-wide, by the sessions' workspaces (DeviceBuffer) and the weight arenas they copied in: back at its
+ * earlier value once every session created since has been destroyed */
+int asr_probe_live_device_bytes(int64_t* bytes);
+
 /* Tuning hook: time `iters` launches of the bf16 GEMM on device-resident pseudo-random operands.
  * variant: -1 heuristic, 0..7 kernel variants (csrc/gemm.hip). epilogue: 0 bias->lo, 1 bias+relu->lo,
  * 2 bias+residual->f32, 3 two residual terms->f32, 4 transposed store, 5 LayerNorm-folded FFN-1, 6 producer epilogue. */
