@@ -30,6 +30,16 @@ class DecodeAttnDesc(C.Structure):
                 ("kv8", C.c_void_p), ("scale8", _fp), ("out", _fp), ("stray", C.c_int32), ("kernel", C.c_char * 32)]
 
 
+class QwenAttnDesc(C.Structure):
+    _fields_ = [("bf16", C.c_int32), ("step", C.c_int32), ("no_fuse", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("KV", C.c_int32),
+                ("rows", C.c_int32), ("qkv", _fp), ("qn", _fp), ("kn", _fp), ("rope", _fp), ("rope_rows", C.c_int32), ("eps", C.c_float),
+                ("hist", _ip), ("T", _ip), ("row_off", _ip), ("row_seq", _ip), ("row_t", _ip), ("S_max", C.c_int32), ("paged", C.c_int32),
+                ("n_pages", C.c_int32), ("pps", C.c_int32), ("table", _ip), ("hist_ld", C.c_int32), ("k_hist", _fp), ("v_hist", _fp),
+                ("after_ld", C.c_int32), ("k_after", _fp), ("v_after", _fp), ("beam", C.c_int32), ("ld_src", C.c_int32), ("S_hyp", C.c_int32),
+                ("src", _ip), ("p0", _ip), ("ext_k", _fp), ("ext_v", _fp), ("q_out", _fp), ("k_rows_out", _fp), ("ctx", _fp),
+                ("stray", C.c_int32), ("qt", C.c_int32), ("nw", C.c_int32), ("kernel", C.c_char * 32)]
+
+
 class BeamSelectDesc(C.Structure):
     _fields_ = [("n_utt", C.c_int32), ("beam", C.c_int32), ("K", C.c_int32), ("ld", C.c_int32), ("first", C.c_int32), ("n_slots", C.c_int32),
                 ("n_stop", C.c_int32), ("topv", _fp), ("topi", _ip), ("cum", _fp), ("fin", _ip), ("len", _ip), ("next", _ip), ("done", _ip),
@@ -45,6 +55,7 @@ SIGNATURES = {
     "asr_probe_decode_gemm_mxfp4": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _fp, C.c_int, _fp]),
     "asr_probe_decode_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _fp, _fp, C.c_int, _fp]),
     "asr_probe_decode_attention": (C.c_int, [C.POINTER(DecodeAttnDesc)]),
+    "asr_probe_qwen_attention": (C.c_int, [C.POINTER(QwenAttnDesc)]),
     "asr_probe_beam_select": (C.c_int, [C.POINTER(BeamSelectDesc)]),
     "asr_probe_decode_attention_beam": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p]),
     "asr_probe_gemm_counts": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
@@ -208,6 +219,63 @@ def decode_attention_beam(q, kv_new, ext, src, beam, p0, hist, bf16=True, hist_d
                                                       src.shape[1], q.ctypes.data_as(_fp), kv_new.ctypes.data_as(_fp), ext.ctypes.data_as(_fp),
                                                       out.ctypes.data_as(_fp), stray.ctypes.data_as(_ip), kern))
     return out, ext, int(stray[0]), kern.value.decode()
+
+
+def qwen_attention(qkv, H, KV, qn, kn, rope, eps, hist, T, S_max, bf16=True, step=False, no_fuse=False, row_off=None, k_hist=None, v_hist=None,
+                   table=None, n_pages=0, beam=0, src=None, p0=None, ext_k=None, ext_v=None):
+    """The attention stage of one Qwen3 decoder layer through launch_qwen_attention (asr_mi355x_probe.h) on f32 host arrays.
+
+    qkv [rows][(H + 2 KV) 128]; sequence b appends T[b] positions at hist[b], its rows starting at row_off[b] (default: consecutive, each sequence at
+    the next multiple of 16; a step: row b); rows no sequence owns are gap rows. k_hist / v_hist [seq][KV][>= max hist][128] are the cached rows;
+    table [seq][pps] selects the paged layout over a pool of n_pages. beam > 0: rows are hypotheses with extents ext_k / ext_v [B][KV][S_hyp][128],
+    ancestry src [B][ld_src] and prompt lengths p0 [B]; the cache is then the utterances' prompt cache.
+
+    Returns dict(ctx, q [rows][H 128] (NaN where unwritten), k_rows [rows][KV 128], k_after / v_after [B][KV][max(hist + T)][128] (NaN past a sequence's
+    positions), ext_k / ext_v (beam), stray, kernel, qt, nw, row_off)."""
+    qkv = _f32(qkv)
+    i32 = lambda x: np.ascontiguousarray(x, np.int32)
+    hist, T = i32(hist), i32(T)
+    B = hist.size
+    rows = qkv.shape[0]
+    if row_off is None:
+        row_off = np.arange(B) if step else np.concatenate([[0], np.cumsum((T + 15) // 16 * 16)[:-1]])
+    row_off = i32(row_off)
+    row_seq, row_t = np.full(rows, -1, np.int32), np.zeros(rows, np.int32)
+    for b in range(B):
+        row_seq[row_off[b]:row_off[b] + T[b]] = b
+        row_t[row_off[b]:row_off[b] + T[b]] = np.arange(T[b])
+    qn, kn, rope = _f32(qn), _f32(kn), _f32(rope)
+    assert qkv.shape == (rows, (H + 2 * KV) * 128) and qn.shape == kn.shape == (128,) and rope.ndim == 2 and rope.shape[1] == 128
+    d = QwenAttnDesc()
+    d.bf16, d.step, d.no_fuse, d.B, d.H, d.KV, d.rows, d.rope_rows, d.eps, d.S_max = int(bf16), int(step), int(no_fuse), B, H, KV, rows, rope.shape[0], eps, S_max
+    keep = [qkv, qn, kn, rope, hist, T, row_off, row_seq, row_t]
+    d.qkv, d.qn, d.kn, d.rope = (x.ctypes.data_as(_fp) for x in (qkv, qn, kn, rope))
+    d.hist, d.T, d.row_off, d.row_seq, d.row_t = (x.ctypes.data_as(_ip) for x in (hist, T, row_off, row_seq, row_t))
+    if k_hist is not None and k_hist.shape[2] > 0:
+        k_hist, v_hist = _f32(k_hist), _f32(v_hist)
+        assert k_hist.shape == v_hist.shape and k_hist.shape[1:] == (KV, k_hist.shape[2], 128)
+        keep += [k_hist, v_hist]
+        d.hist_ld, d.k_hist, d.v_hist = k_hist.shape[2], k_hist.ctypes.data_as(_fp), v_hist.ctypes.data_as(_fp)
+    if table is not None:
+        table = i32(table)
+        keep.append(table)
+        d.paged, d.n_pages, d.pps, d.table = 1, n_pages, table.shape[1], table.ctypes.data_as(_ip)
+    out = dict(ctx=np.zeros((rows, H * 128), np.float32), q=np.zeros((rows, H * 128), np.float32), k_rows=np.zeros((rows, KV * 128), np.float32), row_off=row_off)
+    d.ctx, d.q_out, d.k_rows_out = (out[k].ctypes.data_as(_fp) for k in ("ctx", "q", "k_rows"))
+    if beam:
+        src, p0 = i32(src), i32(p0)
+        out["ext_k"], out["ext_v"] = (np.array(x, dtype=np.float32, order="C", copy=True) for x in (ext_k, ext_v))
+        assert src.ndim == 2 and src.shape[0] == B and p0.shape == (B,) and out["ext_k"].shape == out["ext_v"].shape == (B, KV, ext_k.shape[2], 128)
+        keep += [src, p0]
+        d.beam, d.ld_src, d.S_hyp, d.src, d.p0 = beam, src.shape[1], ext_k.shape[2], src.ctypes.data_as(_ip), p0.ctypes.data_as(_ip)
+        d.ext_k, d.ext_v = out["ext_k"].ctypes.data_as(_fp), out["ext_v"].ctypes.data_as(_fp)
+    else:
+        n_after = int((hist + T).max())
+        out["k_after"], out["v_after"] = np.full((B, KV, n_after, 128), np.nan, np.float32), np.full((B, KV, n_after, 128), np.nan, np.float32)
+        d.after_ld, d.k_after, d.v_after = n_after, out["k_after"].ctypes.data_as(_fp), out["v_after"].ctypes.data_as(_fp)
+    _lib.check(load().asr_probe_qwen_attention(C.byref(d)))
+    out.update(stray=d.stray, kernel=d.kernel.decode(), qt=d.qt, nw=d.nw)
+    return out
 
 
 def beam_select(beam, K, n_slots, topv, topi, cum, fin, length, nxt, done, src_in, tok_in, src_out, tok_out, stop=(), first=False):

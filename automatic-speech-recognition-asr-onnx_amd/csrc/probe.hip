@@ -11,6 +11,7 @@
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "qwen_attn.h"
 
 namespace {
 
@@ -715,6 +716,200 @@ extern "C" int asr_probe_decode_attention(asr_probe_decode_attn_desc* d) {
     gemm_reload_env();
     if (d->bf16) probe_decode_attention<bf16_t>(d);
     else probe_decode_attention<float>(d);
+  });
+}
+
+// ---- the attention stage of a Qwen3 decoder layer (launch_qwen_attention, csrc/qwen_attn.h) on host arrays. The device state is what a session has at that
+// point and no more: zeros where the session guarantees zeros (the q|k|v rows of gap rows -- the packed layout starts every sequence at a multiple of 16 rows and
+// the gather writes zeros between them, so the V^T columns past a sequence are zero too), NaN everywhere else (cache slots at and past hist, pages and layers the
+// table does not name, operand / key / context rows nobody wrote).
+namespace {
+inline size_t qw_pad_rows(size_t r) { return (r + 127) / 128 * 128 + 144; }       // QwSession's row padding
+
+template <typename T>
+void probe_qwen_attention(asr_probe_qwen_attn_desc* d) {
+  Tmp t;
+  constexpr int HD = 128, LAYERS = 2, LAYER = 1;          // the paged pool is page-major over two layers and the call works on the second: page_stride matters
+  const int B = d->B, H = d->H, KV = d->KV, rows = d->rows, heads = H + 2 * KV;
+  const bool beam = d->beam > 0;
+  ASR_REQUIRE(B > 0 && H > 0 && KV > 0 && H % KV == 0 && rows > 0 && d->rope_rows > 0 && d->S_max > 0 && d->S_max <= 16000, "probe_qwen_attention: bad geometry");
+  ASR_REQUIRE(d->qkv && d->qn && d->kn && d->rope && d->hist && d->T && d->row_off && d->row_seq && d->row_t && d->ctx, "probe_qwen_attention: null operand");
+  const int G = H / KV;
+  const int n_seq = beam ? B / d->beam : B;               // sequences of the session's own cache
+  const int cap = d->paged ? d->pps * 16 : d->S_max;      // positions the session cache can address per sequence
+  if (d->paged) {
+    ASR_REQUIRE(d->table && d->n_pages > 0 && d->pps > 0, "probe_qwen_attention: paged cache without a table");
+    for (int i = 0; i < n_seq * d->pps; ++i)
+      ASR_REQUIRE(d->table[i] >= 0 && d->table[i] < d->n_pages, "probe_qwen_attention: page id %d outside the pool of %d", d->table[i], d->n_pages);
+  }
+  if (d->step) ASR_REQUIRE(rows == B, "probe_qwen_attention: a step has one row per sequence");
+  int max_len = 0;
+  for (int b = 0; b < B; ++b) {
+    const int hb = d->hist[b], Tb = d->T[b], r0 = d->row_off[b];
+    ASR_REQUIRE(Tb >= 1 && hb >= 0 && hb + Tb <= d->rope_rows && (beam || hb + Tb <= std::min(cap, d->S_max)), "probe_qwen_attention: sequence %d positions [%d, %d) outside the cache / rope table", b, hb, hb + Tb);
+    ASR_REQUIRE(r0 >= 0 && r0 + Tb <= rows && (d->step ? (Tb == 1 && r0 == b) : r0 % 16 == 0), "probe_qwen_attention: sequence %d rows [%d, %d) of %d", b, r0, r0 + Tb, rows);
+    max_len = std::max(max_len, Tb);
+  }
+  for (int r = 0; r < rows; ++r) {
+    const int b = d->row_seq[r];
+    ASR_REQUIRE(b >= -1 && b < B && (b < 0 || (d->row_t[r] >= 0 && d->row_t[r] < d->T[b] && r == d->row_off[b] + d->row_t[r])), "probe_qwen_attention: row %d does not match the plan", r);
+  }
+  if (beam) {
+    ASR_REQUIRE(d->beam <= 8 && B % d->beam == 0 && d->step && !d->no_fuse && (G == 1 || G == 2 || G == 4), "probe_qwen_attention: beam rows need the fused step (G in 1, 2, 4)");
+    ASR_REQUIRE(d->src && d->p0 && d->ext_k && d->ext_v && d->S_hyp > 0 && d->ld_src > 0, "probe_qwen_attention: beam mode without its tables");
+    for (int b = 0; b < B; ++b) {
+      const int p0 = d->p0[b], gen = d->hist[b] - p0;
+      ASR_REQUIRE(p0 == d->p0[b / d->beam * d->beam] && p0 >= 0 && p0 <= std::min(cap, d->S_max) && gen >= 0 && gen < d->S_hyp && gen <= d->ld_src, "probe_qwen_attention: row %d prompt %d, %d generated", b, p0, gen);
+      for (int j = 0; j < gen; ++j) {
+        const int a = d->src[(size_t)b * d->ld_src + j];
+        ASR_REQUIRE(a >= 0 && a < B && a / d->beam == b / d->beam, "probe_qwen_attention: row %d slot %d names row %d outside its utterance", b, j, a);
+      }
+    }
+  }
+  auto up_raw = [&](const void* h, size_t bytes) -> void* {
+    void* p = t.alloc(bytes);
+    HIP_CHECK(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+    return p;
+  };
+  auto up_t = [&](const std::vector<T>& h) -> T* { return (T*)up_raw(h.data(), h.size() * sizeof(T)); };
+  // ---- operands
+  const size_t Md = qw_pad_rows(rows);
+  std::vector<float> hqkv(Md * heads * HD, 0.0f);
+  std::memcpy(hqkv.data(), d->qkv, (size_t)rows * heads * HD * 4);
+  QwAttnArgs a;
+  a.bf16 = sizeof(T) == 2; a.step = d->step != 0; a.no_fuse = d->no_fuse != 0;
+  a.qkv = (const float*)up_raw(hqkv.data(), hqkv.size() * 4);
+  a.rows = rows; a.B = B; a.H = H; a.KV = KV; a.eps = d->eps;
+  a.qn = (const float*)up_raw(d->qn, HD * 4); a.kn = (const float*)up_raw(d->kn, HD * 4);
+  a.rope = (const float*)up_raw(d->rope, (size_t)d->rope_rows * HD * 4);
+  a.hist = (const int32_t*)up_raw(d->hist, (size_t)B * 4);
+  a.row_seq = (const int32_t*)up_raw(d->row_seq, (size_t)rows * 4);
+  a.row_t = (const int32_t*)up_raw(d->row_t, (size_t)rows * 4);
+  std::vector<UttPlan> plan(B);
+  std::memset(plan.data(), 0, plan.size() * sizeof(UttPlan));
+  for (int b = 0; b < B; ++b) { plan[b].T = d->T[b]; plan[b].n_lfr = d->T[b]; plan[b].row_off = d->row_off[b]; }
+  a.plan = (const UttPlan*)up_raw(plan.data(), plan.size() * sizeof(UttPlan));
+  const std::vector<T> nan_rows(Md * H * HD, elem_nan<T>());
+  T* dq = up_t(nan_rows);
+  T* dctx = up_t(nan_rows);
+  a.q = dq; a.ctx = dctx; a.S = d->S_max;
+  // ---- bf16 prefill: the MFMA form's inputs, as QwSession::prefill_impl makes them
+  T* dkrows = nullptr;
+  d->qt = d->nw = 0;
+  if (a.bf16 && !a.step) {
+    int qt = 0, nw = 4, n_qb = 0;
+    attention_geometry(max_len, HD, &qt, &nw);
+    const int dq_rows = 16 * qt * nw;
+    std::vector<int32_t> qb_utt, qb_q0;
+    for (int b = 0; b < B; ++b)
+      for (int q0 = 0; q0 < d->T[b]; q0 += dq_rows) { qb_utt.push_back(b); qb_q0.push_back(q0); ++n_qb; }
+    a.qb_utt = (const int32_t*)up_raw(qb_utt.data(), qb_utt.size() * 4);
+    a.qb_q0 = (const int32_t*)up_raw(qb_q0.data(), qb_q0.size() * 4);
+    a.n_qb = a.no_fuse ? 0 : n_qb; a.qt = qt; a.nw = nw; a.max_T = max_len; a.ld_vt = (int)Md;
+    d->qt = qt; d->nw = nw;
+    dkrows = up_t(std::vector<T>(Md * KV * HD, elem_nan<T>()));
+    a.k_rows = dkrows;
+    std::vector<T> vt((size_t)KV * HD * Md, elem_from_f32<T>(0.0f));          // V^T of the q|k|v rows; gap rows are zero rows of the GEMM's input
+    for (int r = 0; r < rows; ++r)
+      if (d->row_seq[r] >= 0)
+        for (int c = 0; c < KV * HD; ++c) vt[(size_t)c * Md + r] = elem_from_f32<T>(d->qkv[(size_t)r * heads * HD + (H + KV) * HD + c]);
+    a.vt = up_t(vt);
+  }
+  // ---- the session's own cache (beam: the utterances' prompt cache): host image, NaN wherever no cached row was placed
+  const size_t page_stride = (size_t)LAYERS * KV * 16 * HD;
+  const size_t own_n = d->paged ? (size_t)d->n_pages * page_stride : (size_t)n_seq * KV * d->S_max * HD;
+  auto own_off = [&](int b, int kvh, int s) -> size_t {
+    if (d->paged) return (size_t)d->table[(size_t)b * d->pps + (s >> 4)] * page_stride + (size_t)LAYER * KV * 16 * HD + ((size_t)kvh * 16 + (s & 15)) * HD;
+    return (((size_t)b * KV + kvh) * d->S_max + s) * HD;
+  };
+  std::vector<T> hk(own_n, elem_nan<T>()), hv(own_n, elem_nan<T>());
+  std::vector<unsigned char> may_k(own_n, 0);             // elements the call is entitled to write (same set for K and V)
+  for (int b = 0; b < n_seq; ++b) {
+    const int have = beam ? d->p0[b * d->beam] : d->hist[b];
+    ASR_REQUIRE(have == 0 || (d->k_hist && d->v_hist && have <= d->hist_ld), "probe_qwen_attention: sequence %d has %d cached positions, hist_ld %d", b, have, d->hist_ld);
+    for (int kvh = 0; kvh < KV; ++kvh) {
+      for (int s = 0; s < have; ++s)
+        for (int e = 0; e < HD; ++e) {
+          const size_t src = (((size_t)b * KV + kvh) * d->hist_ld + s) * HD + e;
+          hk[own_off(b, kvh, s) + e] = elem_from_f32<T>(d->k_hist[src]);
+          hv[own_off(b, kvh, s) + e] = elem_from_f32<T>(d->v_hist[src]);
+        }
+      if (!beam)
+        for (int s = have; s < have + d->T[b]; ++s)
+          for (int e = 0; e < HD; ++e) may_k[own_off(b, kvh, s) + e] = 1;
+    }
+  }
+  T* dk = up_t(hk);
+  T* dv = up_t(hv);
+  KvAddr own{nullptr, 0, 0, d->S_max};
+  if (d->paged) own = KvAddr{(const int32_t*)up_raw(d->table, (size_t)n_seq * d->pps * 4), d->pps, page_stride, d->S_max};
+  const size_t layer_off = d->paged ? (size_t)LAYER * KV * 16 * HD : 0;
+  // ---- beam search: hypothesis extents [B][KV][S_hyp][128], uploaded as given
+  const size_t ext_n = beam ? (size_t)B * KV * d->S_hyp * HD : 0;
+  std::vector<T> ek(ext_n), ev(ext_n);
+  T *dek = nullptr, *dev = nullptr;
+  if (beam) {
+    for (size_t i = 0; i < ext_n; ++i) { ek[i] = elem_from_f32<T>(d->ext_k[i]); ev[i] = elem_from_f32<T>(d->ext_v[i]); }
+    dek = up_t(ek); dev = up_t(ev);
+    a.kc = dek; a.vc = dev; a.ka = KvAddr{nullptr, 0, 0, d->S_hyp};
+    a.kc_p = dk + layer_off; a.vc_p = dv + layer_off; a.kap = own;
+    a.beam_src = (const int32_t*)up_raw(d->src, (size_t)B * d->ld_src * 4); a.ld_src = d->ld_src; a.beam = d->beam;
+    a.beam_p0 = (const int32_t*)up_raw(d->p0, (size_t)B * 4);
+  } else {
+    a.kc = dk + layer_off; a.vc = dv + layer_off; a.ka = own;
+  }
+  Profiler prof;                                          // (disabled: a ProfScope over it does nothing)
+  const char* form = launch_qwen_attention<T>(a, prof, nullptr);
+  HIP_CHECK(hipGetLastError());
+  snprintf(d->kernel, sizeof(d->kernel), "%s", form);
+  HIP_CHECK(hipDeviceSynchronize());
+  // ---- results
+  auto down = [&](const T* dev_p, size_t count, float* out) {
+    std::vector<T> h(count);
+    HIP_CHECK(hipMemcpy(h.data(), dev_p, count * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < count; ++i) out[i] = elem_to_f32(h[i]);
+  };
+  down(dctx, (size_t)rows * H * HD, d->ctx);
+  if (d->q_out) down(dq, (size_t)rows * H * HD, d->q_out);
+  if (d->k_rows_out) {
+    if (dkrows) down(dkrows, (size_t)rows * KV * HD, d->k_rows_out);
+    else for (size_t i = 0; i < (size_t)rows * KV * HD; ++i) d->k_rows_out[i] = std::nanf("");
+  }
+  int64_t stray = 0;
+  std::vector<T> ak(own_n), av(own_n);
+  HIP_CHECK(hipMemcpy(ak.data(), dk, own_n * sizeof(T), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(av.data(), dv, own_n * sizeof(T), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < own_n; ++i)
+    if (!may_k[i]) stray += (same_bits(hk[i], ak[i]) ? 0 : 1) + (same_bits(hv[i], av[i]) ? 0 : 1);
+  if (!beam && d->k_after && d->v_after)
+    for (int b = 0; b < B; ++b)
+      for (int kvh = 0; kvh < KV; ++kvh)
+        for (int s = 0; s < d->hist[b] + d->T[b] && s < d->after_ld; ++s)
+          for (int e = 0; e < HD; ++e) {
+            const size_t o = (((size_t)b * KV + kvh) * d->after_ld + s) * HD + e;
+            d->k_after[o] = elem_to_f32(ak[own_off(b, kvh, s) + e]);
+            d->v_after[o] = elem_to_f32(av[own_off(b, kvh, s) + e]);
+          }
+  if (beam) {
+    std::vector<T> bk(ext_n), bv(ext_n);
+    HIP_CHECK(hipMemcpy(bk.data(), dek, ext_n * sizeof(T), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(bv.data(), dev, ext_n * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ext_n; ++i) {
+      const int b = (int)(i / ((size_t)KV * d->S_hyp * HD)), slot = (int)((i / HD) % d->S_hyp);
+      if (slot != d->hist[b] - d->p0[b]) stray += (same_bits(ek[i], bk[i]) ? 0 : 1) + (same_bits(ev[i], bv[i]) ? 0 : 1);
+      d->ext_k[i] = elem_to_f32(bk[i]); d->ext_v[i] = elem_to_f32(bv[i]);
+    }
+  }
+  d->stray = (int32_t)std::min<int64_t>(stray, 0x7fffffff);
+}
+}  // namespace
+
+extern "C" int asr_probe_qwen_attention(asr_probe_qwen_attn_desc* d) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d, "probe_qwen_attention: null descriptor");
+    asr_require_device(0);
+    if (d->bf16) probe_qwen_attention<bf16_t>(d);
+    else probe_qwen_attention<float>(d);
   });
 }
 

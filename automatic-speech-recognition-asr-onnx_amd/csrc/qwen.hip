@@ -18,6 +18,7 @@
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "qwen_attn.h"
 
 namespace {
 
@@ -145,12 +146,7 @@ __global__ __launch_bounds__(256) void qw_rmsnorm_kernel(const float* __restrict
   }
 }
 
-// Where position s of (sequence b, kv head) lives. Two layouts of a layer's cache:
-//   extents (table == nullptr): [seq][kv head][S_max][128] -- beam-search hypothesis rows, the persistent decode kernel, ASR_QWEN_KV_PAGED=0;
-//   pages (the default): 16 positions per page behind a block table [seq][pps] of page ids, one pool for all layers laid out page-major
-//   [page][layer][kv head][16][128] (`base` carries the layer's offset, page_stride the elements between consecutive pages), so a sequence holds
-//   pages for the positions it has, not for max_seq_len, and a finished sequence's pages go back to the free list (host: QwSession::kv_*).
-struct KvAddr { const int32_t* table; int pps; size_t page_stride; int S_max; };
+// (KvAddr, the cache addressing of both layouts: qwen_attn.h)
 template <typename T>
 __device__ __forceinline__ T* kv_row(T* base, const KvAddr& a, int b, int kvh, int n_kv, int s) {
   if (a.table) return base + (size_t)a.table[(size_t)b * a.pps + (s >> 4)] * a.page_stride + ((size_t)kvh * 16 + (s & 15)) * 128;
@@ -179,7 +175,10 @@ __global__ __launch_bounds__(256) void qw_qk_rope_kernel(const float* __restrict
   const float* src = qkv + (size_t)(live ? row : 0) * heads * HD + hh * HD + 4 * l;
   const float4 lo = *reinterpret_cast<const float4*>(src), hi = *reinterpret_cast<const float4*>(src + 64);
   const float x0[4] = {lo.x, lo.y, lo.z, lo.w}, x1[4] = {hi.x, hi.y, hi.z, hi.w};              // the two rotary halves of this lane's four pairs
-  float ss = (x0[0] * x0[0] + x1[0] * x1[0]) + (x0[1] * x0[1] + x1[1] * x1[1]) + ((x0[2] * x0[2] + x1[2] * x1[2]) + (x0[3] * x0[3] + x1[3] * x1[3]));
+  // (explicit fmaf here and in the rotation below: which product of a * b + c * d gets fused is otherwise the compiler's choice per kernel, and the fused decode
+  //  kernel has to round exactly like this one -- a fused step and an unfused one cache the same bits, tests/test_qwen_attn_gpu.py::test_forms_agree)
+  auto sq2 = [](float a, float b) { return fmaf(a, a, b * b); };
+  float ss = (sq2(x0[0], x1[0]) + sq2(x0[1], x1[1])) + (sq2(x0[2], x1[2]) + sq2(x0[3], x1[3]));
 #pragma unroll
   for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);                                  // (every lane of the wave takes part: no early exit above)
   if (!live) return;
@@ -198,7 +197,7 @@ __global__ __launch_bounds__(256) void qw_qk_rope_kernel(const float* __restrict
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const float a0 = x0[e] * r * wa[e], a1 = x1[e] * r * wb[e];
-    y0[e] = a0 * cs[e] - a1 * sn[e]; y1[e] = a1 * cs[e] + a0 * sn[e];
+    y0[e] = fmaf(a0, cs[e], -(a1 * sn[e])); y1[e] = fmaf(a1, cs[e], a0 * sn[e]);
   }
   T* dst = (hh < n_heads ? q_out + (size_t)row * n_heads * HD + hh * HD : kv_row(kc, ka, b, hh - n_heads, n_kv, pos)) + 4 * l;
   qw_store4(dst, y0); qw_store4(dst + 64, y1);
@@ -382,11 +381,17 @@ __global__ __launch_bounds__(256) void qw_decode_attn_kernel(const float* __rest
       vnew[lane + 64] = Elem<T>::load(&t1);
       continue;
     }
-    const float r = rsqrtf(wave_sum(x0[t] * x0[t] + x1[t] * x1[t]) / (float)HD + eps);
+    // the sum of squares in qw_qk_rope_kernel's association (a lane there adds four consecutive pairs as (p0 + p1) + (p2 + p3), then its sixteen lanes combine
+    // by xor 8, 4, 2, 1 = element strides 32, 16, 8, 4) and with its explicit fmaf, so a fused step and an unfused one cache the same bits
+    float ss = fmaf(x0[t], x0[t], x1[t] * x1[t]);
+    ss += __shfl_xor(ss, 1, 64); ss += __shfl_xor(ss, 2, 64);
+#pragma unroll
+    for (int o = 32; o > 2; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    const float r = rsqrtf(ss / (float)HD + eps);
     const float* w = task == 0 ? kn : qn;
     const float a0 = x0[t] * r * w[lane], a1 = x1[t] * r * w[lane + 64];
-    Elem<T>::store(&t0, a0 * cs - a1 * sn);              // through the operand dtype, like the unfused path
-    Elem<T>::store(&t1, a1 * cs + a0 * sn);
+    Elem<T>::store(&t0, fmaf(a0, cs, -(a1 * sn)));       // through the operand dtype, like the unfused path
+    Elem<T>::store(&t1, fmaf(a1, cs, a0 * sn));
     float* dst = task == 0 ? knew : qsh[task - 2];
     dst[lane] = Elem<T>::load(&t0);
     dst[lane + 64] = Elem<T>::load(&t1);
@@ -488,6 +493,62 @@ __global__ __launch_bounds__(256) void qw_decode_attn_kernel(const float* __rest
     Elem<T>::store(ctx + (size_t)b * n_heads * HD + (kvh * G + g) * HD + e, num / den);
   }
 }
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------ the attention stage of a decoder layer (qwen_attn.h)
+QwAttnForm qwen_attention_form(const QwAttnArgs& a) {
+  const int G = a.H / a.KV;
+  const bool fused_attn = a.step && (G == 1 || G == 2 || G == 4) && !a.no_fuse;
+  if (fused_attn) return a.beam_src ? QW_ATTN_FUSED_BEAM : QW_ATTN_FUSED_DECODE;
+  const bool mfma_attn = a.bf16 && !a.step && a.n_qb > 0;
+  return mfma_attn ? QW_ATTN_ROPE_MFMA : QW_ATTN_ROPE_SCALAR;
+}
+
+template <typename T>
+const char* launch_qwen_attention(const QwAttnArgs& a, Profiler& prof, hipStream_t stream) {
+  const int H = a.H, KV = a.KV, B = a.B, rows = a.rows, hd = 128, G = H / KV;
+  const float* qkv = a.qkv;
+  const int32_t* hist = a.hist;
+  T *q = (T*)a.q, *kc = (T*)a.kc, *vc = (T*)a.vc, *ctx = (T*)a.ctx;
+  const KvAddr ka = a.ka;
+  const QwAttnForm form = qwen_attention_form(a);
+  if (form == QW_ATTN_FUSED_DECODE || form == QW_ATTN_FUSED_BEAM) {
+    ProfScope ps(prof, "dec_attn", stream);
+    const size_t lds = 0;
+    if (a.beam_src) {
+      const T *kc_p = (const T*)a.kc_p, *vc_p = (const T*)a.vc_p;
+      const KvAddr kap = a.kap;
+      if (G == 1) hipLaunchKernelGGL((qw_decode_attn_kernel<T, 1, true>), dim3(B * KV), dim3(256), lds, stream, qkv, H, KV, a.qn, a.kn, a.rope, a.eps, hist, kc, vc, ka, ctx, a.beam_src, a.ld_src, a.beam_p0, kc_p, vc_p, kap, a.beam);
+      else if (G == 2) hipLaunchKernelGGL((qw_decode_attn_kernel<T, 2, true>), dim3(B * KV), dim3(256), lds, stream, qkv, H, KV, a.qn, a.kn, a.rope, a.eps, hist, kc, vc, ka, ctx, a.beam_src, a.ld_src, a.beam_p0, kc_p, vc_p, kap, a.beam);
+      else hipLaunchKernelGGL((qw_decode_attn_kernel<T, 4, true>), dim3(B * KV), dim3(256), lds, stream, qkv, H, KV, a.qn, a.kn, a.rope, a.eps, hist, kc, vc, ka, ctx, a.beam_src, a.ld_src, a.beam_p0, kc_p, vc_p, kap, a.beam);
+      return G == 1 ? "beam_g1" : G == 2 ? "beam_g2" : "beam_g4";
+    }
+    if (G == 1) hipLaunchKernelGGL((qw_decode_attn_kernel<T, 1, false>), dim3(B, KV), dim3(256), lds, stream, qkv, H, KV, a.qn, a.kn, a.rope, a.eps, hist, kc, vc, ka, ctx, (const int32_t*)nullptr, 0, (const int32_t*)nullptr, (const T*)nullptr, (const T*)nullptr, KvAddr{nullptr, 0, 0, 0}, 1);
+    else if (G == 2) hipLaunchKernelGGL((qw_decode_attn_kernel<T, 2, false>), dim3(B, KV), dim3(256), lds, stream, qkv, H, KV, a.qn, a.kn, a.rope, a.eps, hist, kc, vc, ka, ctx, (const int32_t*)nullptr, 0, (const int32_t*)nullptr, (const T*)nullptr, (const T*)nullptr, KvAddr{nullptr, 0, 0, 0}, 1);
+    else hipLaunchKernelGGL((qw_decode_attn_kernel<T, 4, false>), dim3(B, KV), dim3(256), lds, stream, qkv, H, KV, a.qn, a.kn, a.rope, a.eps, hist, kc, vc, ka, ctx, (const int32_t*)nullptr, 0, (const int32_t*)nullptr, (const T*)nullptr, (const T*)nullptr, KvAddr{nullptr, 0, 0, 0}, 1);
+    return G == 1 ? "fused_g1" : G == 2 ? "fused_g2" : "fused_g4";
+  }
+  const bool mfma_attn = form == QW_ATTN_ROPE_MFMA;
+  { ProfScope ps(prof, "dec_rope", stream);
+    const int units = rows * (H + 2 * KV);           // sixteen lanes each
+    hipLaunchKernelGGL(qw_qk_rope_kernel<T>, dim3((units + 15) / 16), dim3(256), 0, stream, qkv, H, KV, a.qn, a.kn, a.rope, a.eps, a.row_seq, a.row_t,
+                       hist, rows, q, kc, vc, ka, mfma_attn ? (T*)a.k_rows : (T*)nullptr); }
+  ProfScope ps(prof, "dec_attn", stream);
+  if (mfma_attn) {
+    AttnArgs aa; aa.q = q; aa.ld_q = H * hd; aa.k = a.k_rows; aa.ld_qk = KV * hd; aa.vt = a.vt; aa.ld_vt = a.ld_vt; aa.ctx = ctx; aa.ld_ctx = H * hd;
+    aa.plan = a.plan; aa.qb_utt = a.qb_utt; aa.qb_q0 = a.qb_q0; aa.n_qblocks = a.n_qb; aa.n_heads = H; aa.qt = a.qt; aa.n_waves = a.nw; aa.max_T = a.max_T;
+    aa.causal = 1; aa.kv_group = G;
+    launch_attention_bf16_hd128(aa, stream);
+    return "rope_mfma";
+  }
+  hipLaunchKernelGGL(qw_attn_kernel<T>, dim3(B, H), dim3(128), (size_t)a.S * 4, stream, q, H, KV, kc, vc, ka, a.plan, hist, ctx);
+  return "rope_scalar";
+}
+template const char* launch_qwen_attention<float>(const QwAttnArgs&, Profiler&, hipStream_t);
+template const char* launch_qwen_attention<bf16_t>(const QwAttnArgs&, Profiler&, hipStream_t);
+
+namespace {
 
 // decoder input rows: src >= 0 -> embedding of token src; src < 0 -> audio embedding row -1 - src; pad rows are zero
 template <typename T>
@@ -850,11 +911,9 @@ void QwSession::decoder_pass(const DecPass& P) {
   const size_t layer_kv = own_paged ? (size_t)KV * 16 * hd : (size_t)B * KV * S * hd;
   const KvAddr ka = own_paged ? kv_addr() : KvAddr{nullptr, 0, 0, S};
   const int32_t* hist = P.hist ? P.hist : d_hist.as<int32_t>();
-  const int G = H / KV;
   // single-position steps of small batches (bf16): RMSNorm(x) W^T = rstd(x) (x W^T) -- the weight-streaming GEMM reads the raw residual
   // rows (bf16 copy written by the producing GEMM), sums x^2 from the fragments it streams anyway and scales its output rows
   const bool rms_in_gemm = P.step && bf && rows <= 64 && d % 256 == 0 && !no_fuse;
-  const bool fused_attn = P.step && (G == 1 || G == 2 || G == 4) && !no_fuse;
   const bool norm_in_reduce = bf && !rms_in_gemm && !no_fuse && d == 1024;
   const bool w8 = fp8 && !fp8_fake && rms_in_gemm;           // byte weights: the weight-streaming launches of a decode step
   auto bytes_of = [&](GemmArgs& g, int layer, int wi) {
@@ -910,43 +969,24 @@ void QwSession::decoder_pass(const DecPass& P) {
     T* kc = (P.kc ? (T*)P.kc : d_kc.as<T>()) + (size_t)i * layer_kv;
     T* vc = (P.vc ? (T*)P.vc : d_vc.as<T>()) + (size_t)i * layer_kv;
     { GemmArgs g; g.W = L.wqkv; g.ldw = d; g.M = rows; g.N = qkvn; g.K = d; g.out_f32 = qkv; g.ld_out_f32 = qkvn; bytes_of(g, i, 0); normed_gemm(x, xlo, g); }
-    if (fused_attn) {
-      ProfScope ps(prof, "dec_attn", stream);
-      const size_t lds = 0;
-      if (P.beam_src) {
-        ASR_REQUIRE(fused_attn, "qwen beam search needs the fused decode attention kernel");
-        const size_t prompt_kv = kv_paged ? (size_t)KV * 16 * hd : (size_t)(B / P.beam) * KV * c.max_seq_len * hd;    // the utterances' prefill cache, one layer
-        const T* kc_p = d_kc.as<T>() + (size_t)i * prompt_kv;
-        const T* vc_p = d_vc.as<T>() + (size_t)i * prompt_kv;
-        const KvAddr kap = kv_addr();
-        if (G == 1) hipLaunchKernelGGL((qw_decode_attn_kernel<T, 1, true>), dim3(B * KV), dim3(256), lds, stream, qkv, H, KV, L.qn, L.kn, rope, c.rms_eps, hist, kc, vc, ka, ctx, P.beam_src, P.ld_src, P.beam_p0, kc_p, vc_p, kap, P.beam);
-        else if (G == 2) hipLaunchKernelGGL((qw_decode_attn_kernel<T, 2, true>), dim3(B * KV), dim3(256), lds, stream, qkv, H, KV, L.qn, L.kn, rope, c.rms_eps, hist, kc, vc, ka, ctx, P.beam_src, P.ld_src, P.beam_p0, kc_p, vc_p, kap, P.beam);
-        else hipLaunchKernelGGL((qw_decode_attn_kernel<T, 4, true>), dim3(B * KV), dim3(256), lds, stream, qkv, H, KV, L.qn, L.kn, rope, c.rms_eps, hist, kc, vc, ka, ctx, P.beam_src, P.ld_src, P.beam_p0, kc_p, vc_p, kap, P.beam);
-      } else
-      if (G == 1) hipLaunchKernelGGL((qw_decode_attn_kernel<T, 1, false>), dim3(B, KV), dim3(256), lds, stream, qkv, H, KV, L.qn, L.kn, rope, c.rms_eps, hist, kc, vc, ka, ctx, (const int32_t*)nullptr, 0, (const int32_t*)nullptr, (const T*)nullptr, (const T*)nullptr, KvAddr{nullptr, 0, 0, 0}, 1);
-      else if (G == 2) hipLaunchKernelGGL((qw_decode_attn_kernel<T, 2, false>), dim3(B, KV), dim3(256), lds, stream, qkv, H, KV, L.qn, L.kn, rope, c.rms_eps, hist, kc, vc, ka, ctx, (const int32_t*)nullptr, 0, (const int32_t*)nullptr, (const T*)nullptr, (const T*)nullptr, KvAddr{nullptr, 0, 0, 0}, 1);
-      else hipLaunchKernelGGL((qw_decode_attn_kernel<T, 4, false>), dim3(B, KV), dim3(256), lds, stream, qkv, H, KV, L.qn, L.kn, rope, c.rms_eps, hist, kc, vc, ka, ctx, (const int32_t*)nullptr, 0, (const int32_t*)nullptr, (const T*)nullptr, (const T*)nullptr, KvAddr{nullptr, 0, 0, 0}, 1);
-    } else {
-      const bool mfma_attn = bf && !P.step && P.n_qb > 0;
-      if (mfma_attn) {                                   // V^T for the MFMA attention kernel (the cache gets V from the q|k|v GEMM)
-        ProfScope ps(prof, "dec_gemm", stream);
-        GemmArgs gv; gv.A = h; gv.lda = d; gv.W = (const T*)L.wqkv + (size_t)(H + KV) * hd * d; gv.ldw = d; gv.M = rows; gv.N = KV * hd; gv.K = d;
-        gv.out_t = d_vt2.ptr; gv.ld_out_t = P.ld_vt; gemm(gv);
-      }
-      { ProfScope ps(prof, "dec_rope", stream);
-        const int units = rows * (H + 2 * KV);           // sixteen lanes each
-        hipLaunchKernelGGL(qw_qk_rope_kernel<T>, dim3((units + 15) / 16), dim3(256), 0, stream, qkv, H, KV, L.qn, L.kn, rope, c.rms_eps, P.row_seq, P.row_t,
-                           hist, rows, q, kc, vc, ka, mfma_attn ? d_krows.as<T>() : (T*)nullptr); }
-      ProfScope ps(prof, "dec_attn", stream);
-      if (mfma_attn) {
-        AttnArgs aa; aa.q = q; aa.ld_q = H * hd; aa.k = d_krows.ptr; aa.ld_qk = KV * hd; aa.vt = d_vt2.ptr; aa.ld_vt = P.ld_vt; aa.ctx = ctx; aa.ld_ctx = H * hd;
-        aa.plan = P.plan; aa.qb_utt = P.qb_utt; aa.qb_q0 = P.qb_q0; aa.n_qblocks = P.n_qb; aa.n_heads = H; aa.qt = P.qt; aa.n_waves = P.nw; aa.max_T = P.max_T;
-        aa.causal = 1; aa.kv_group = G;
-        launch_attention_bf16_hd128(aa, stream);
-      } else {
-        hipLaunchKernelGGL(qw_attn_kernel<T>, dim3(B, H), dim3(128), (size_t)S * 4, stream, q, H, KV, kc, vc, ka, P.plan, hist, ctx);
-      }
+    QwAttnArgs at;
+    at.bf16 = bf; at.step = P.step; at.no_fuse = no_fuse;
+    at.qkv = qkv; at.rows = rows; at.B = B; at.H = H; at.KV = KV; at.qn = L.qn; at.kn = L.kn; at.rope = rope; at.eps = c.rms_eps;
+    at.hist = hist; at.row_seq = P.row_seq; at.row_t = P.row_t; at.plan = P.plan;
+    at.q = q; at.kc = kc; at.vc = vc; at.ctx = ctx; at.ka = ka; at.S = S;
+    at.k_rows = d_krows.ptr; at.vt = d_vt2.ptr; at.ld_vt = P.ld_vt;
+    at.qb_utt = P.qb_utt; at.qb_q0 = P.qb_q0; at.n_qb = P.n_qb; at.qt = P.qt; at.nw = P.nw; at.max_T = P.max_T;
+    if (P.beam_src) {
+      const size_t prompt_kv = kv_paged ? (size_t)KV * 16 * hd : (size_t)(B / P.beam) * KV * c.max_seq_len * hd;    // the utterances' prefill cache, one layer
+      at.beam_src = P.beam_src; at.beam_p0 = P.beam_p0; at.ld_src = P.ld_src; at.beam = P.beam;
+      at.kc_p = d_kc.as<T>() + (size_t)i * prompt_kv; at.vc_p = d_vc.as<T>() + (size_t)i * prompt_kv; at.kap = kv_addr();
     }
+    if (qwen_attention_form(at) == QW_ATTN_ROPE_MFMA) {    // V^T for the MFMA attention kernel (the cache gets V from the q|k|v GEMM)
+      ProfScope ps(prof, "dec_gemm", stream);
+      GemmArgs gv; gv.A = h; gv.lda = d; gv.W = (const T*)L.wqkv + (size_t)(H + KV) * hd * d; gv.ldw = d; gv.M = rows; gv.N = KV * hd; gv.K = d;
+      gv.out_t = d_vt2.ptr; gv.ld_out_t = P.ld_vt; gemm(gv);
+    }
+    launch_qwen_attention<T>(at, prof, stream);
     if constexpr (sizeof(T) == 2) { if (dgm) dg(ctx, H * hd, L.wo, i, 1, d, H * hd, x, x2, x2lo); }
     if (!(sizeof(T) == 2 && dgm))
     { ProfScope ps(prof, "dec_gemm", stream);

@@ -97,6 +97,41 @@ int asr_probe_decode_attention(asr_probe_decode_attn_desc* d);
 int asr_probe_decode_attention_beam(int bf16, int rows, int beam, int H, int S, int p0, int hist, int hist_dev, const int32_t* src, int ld_src,
                                     const float* q, const float* kv_new, float* ext, float* out, int32_t* stray, char* kernel);
 
+/* The attention stage of one Qwen3 decoder layer through the session's launcher (launch_qwen_attention, csrc/qwen_attn.h; head_dim 128) on host arrays:
+ * per-head RMSNorm of q and k, RoPE, cache write, causal GQA attention. Which kernels run follows from bf16 / step / no_fuse / H / KV exactly as in a session:
+ * "fused_g1|2|4" (a step), "beam_g1|2|4" (a step with beam > 0), "rope_mfma" (bf16 prefill), "rope_scalar" (f32, no_fuse). Cache operands are rounded to
+ * the element type on upload; qkv, qn, kn and rope are f32 as in a session.
+ *   rows / plan : qkv [rows][(H + 2 KV) 128] (q heads, k heads, v heads); sequence b has T[b] new positions at rows row_off[b] .. (a multiple of 16 unless
+ *                 step; step: T = 1, row_off = b, rows = B), appended at position hist[b]; row_seq / row_t [rows] name each row's sequence (-1: gap row) and t.
+ *   cache       : extents [seq][KV][S_max][128], or (paged = 1) pages of 16 positions [page][2 layers][KV][16][128] addressed by table [seq][pps] -- the call
+ *                 works on the second layer, so the page stride is not the layer size. k_hist / v_hist [seq][KV][hist_ld][128] supply positions below hist[b];
+ *                 every other slot is NaN before the call. k_after / v_after [B][KV][after_ld][128] receive positions below hist[b] + T[b] after it.
+ *   beam > 0    : the B rows are hypotheses, `beam` per utterance; the cache above is the utterances' prompt cache (seq = B / beam, positions below p0[b]);
+ *                 ext_k / ext_v [B][KV][S_hyp][128] are the rows' extents (slot j = position p0 + j), uploaded as given and overwritten with their state after
+ *                 the call; generated position p0[b] + j of row b is read from row src[b][j] (src [B][ld_src]).
+ * q_out [rows][H 128] (nullable) and k_rows_out [rows][KV 128] (nullable; the MFMA form's key copy) come back NaN where nothing was written; ctx [rows][H 128].
+ * stray: cache and extent elements outside positions [hist[b], hist[b] + T[b]) (beam: outside slot hist[b] - p0[b] of row b) whose bits changed.
+ * qt / nw: the MFMA form's query-block geometry (0 when it was not set up). */
+typedef struct asr_probe_qwen_attn_desc {
+  int32_t bf16, step, no_fuse;
+  int32_t B, H, KV, rows;
+  const float* qkv; const float* qn; const float* kn; const float* rope;
+  int32_t rope_rows; float eps;
+  const int32_t* hist; const int32_t* T; const int32_t* row_off; const int32_t* row_seq; const int32_t* row_t;
+  int32_t S_max;           /* the session's max_seq_len */
+  int32_t paged, n_pages, pps;
+  const int32_t* table;
+  int32_t hist_ld; const float* k_hist; const float* v_hist;
+  int32_t after_ld; float* k_after; float* v_after;
+  int32_t beam, ld_src, S_hyp;
+  const int32_t* src; const int32_t* p0;
+  float* ext_k; float* ext_v;
+  float* q_out; float* k_rows_out; float* ctx;
+  int32_t stray, qt, nw;
+  char kernel[32];
+} asr_probe_qwen_attn_desc;
+int asr_probe_qwen_attention(asr_probe_qwen_attn_desc* d);
+
 /* One pass of the beam-search ranking (launch_beam_select, shared by the Qwen3-ASR and Whisper searches) on host arrays. Hypotheses of utterance b
  * are rows b * beam + r. topv / topi: the rows' K best (log-prob, id) pairs, [rows][K] ([n_utt][K] when first = 1); cum / fin / len / next [rows] and
  * done [n_utt] are the search state, updated in place; stop [n_stop]; src_in / tok_in [rows][ld] the tables the pass reads, src_out / tok_out [rows][ld]
