@@ -100,6 +100,8 @@ SIGNATURES = {
     "asr_session_destroy": (_i, [_vp]),
     "asr_session_set_stream": (_i, [_vp, _vp]),
     "asr_session_device": (_i, [_vp, C.POINTER(C.c_int)]),
+    "asr_session_set_audio_dtype": (_i, [_vp, _i]),
+    "asr_session_audio_dtype": (_i, [_vp, C.POINTER(C.c_int)]),
     "asr_session_profile_enable": (_i, [_vp, _i]),
     "asr_session_profile_reset": (_i, [_vp]),
     "asr_session_profile_read": (_i, [_vp, _i, C.c_char_p, _dp, _lp, C.POINTER(C.c_int)]),

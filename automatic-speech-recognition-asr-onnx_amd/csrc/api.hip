@@ -72,6 +72,24 @@ extern "C" int asr_session_device(asr_session* s, int* device_id) {
   });
 }
 
+// The sample type is read at every audio entry (staging size, pointer step, fbank instantiation) and is part of the keys of the step graphs that hold the
+// front end, so it may change between any two compute calls.
+extern "C" int asr_session_set_audio_dtype(asr_session* s, int audio_dtype) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s, "set_audio_dtype: null session");
+    ASR_REQUIRE(audio_dtype == ASR_AUDIO_F32 || audio_dtype == ASR_AUDIO_I16 || audio_dtype == ASR_AUDIO_F16,
+                "set_audio_dtype: unknown audio dtype %d (0 = f32, 1 = int16, 2 = f16)", audio_dtype);
+    s->audio_dtype = audio_dtype;
+  });
+}
+
+extern "C" int asr_session_audio_dtype(asr_session* s, int* audio_dtype_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && audio_dtype_out, "audio_dtype: null argument");
+    *audio_dtype_out = s->audio_dtype;
+  });
+}
+
 extern "C" int asr_session_profile_enable(asr_session* s, int enable) {
   return asr_guard([&] {
     ASR_REQUIRE(s, "profile_enable: null session");

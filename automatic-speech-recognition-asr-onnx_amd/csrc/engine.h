@@ -146,6 +146,8 @@ struct asr_session {
   int device = 0;
   int tenant_slot = -1;       // this session's entry in the process-wide tenancy table (asr_tenant_attach; released by the destructor)
   int precision = 0;
+  int audio_dtype = 0;        // asr_audio_dtype: the sample type every audio entry of this session reads its `audio` pointer as (asr_session_set_audio_dtype)
+  size_t audio_elt() const { return audio_dtype == 0 ? 4 : 2; }
   hipStream_t stream = nullptr;
   bool own_stream = false;
   Arena arena;

@@ -4,7 +4,7 @@
 
 // Per-utterance geometry, built on the host for every run and uploaded with one copy.
 struct UttPlan {
-  int64_t audio_off;   // first sample in the packed audio buffer
+  int64_t audio_off;   // first sample in the packed audio buffer (a sample index whatever the sample type)
   int32_t n_samples;
   int32_t n_frames;    // fbank / STFT frames
   int32_t frame_off;   // first row in the packed mel buffer
@@ -17,8 +17,10 @@ struct UttPlan {
 
 // ---- Kaldi fbank: frames -> |DFT|^2 -> mel -> ln  (SenseVoice/Export_SenseVoice.py:139-160,275-278)
 // dft_packed / mel_packed are MFMA-fragment-ordered constant tables built by arena.py.
+enum { AUDIO_F32 = 0, AUDIO_I16 = 1, AUDIO_F16 = 2 };           // asr_audio_dtype of the C ABI
+inline size_t audio_elt_bytes(int audio_dtype) { return audio_dtype == AUDIO_F32 ? 4 : 2; }
 struct FbankArgs {
-  const float* audio;          // packed samples
+  const void* audio;           // packed samples of type audio_dtype
   const UttPlan* plan;
   const int32_t* blk_utt;      // per workgroup: utterance
   const int32_t* blk_f0;       // per workgroup: first frame (multiple of 64)
@@ -38,6 +40,9 @@ struct FbankArgs {
   float* blk_max;
   // bf16 sessions: the DFT on the bf16 matrix pipe with split operands (launch_fbank_split_table): null = exact-f32 MFMA
   const void* dft_split = nullptr;
+  // sample type of `audio`: the kernels are instantiated per type and launch_fbank dispatches (kept last: the kernels never read it, and the
+  // offsets of the fields they do read stay what they were)
+  int audio_dtype = AUDIO_F32;
 };
 void launch_fbank(const FbankArgs& a, int n_blocks, hipStream_t s);
 // three-term bf16 split (hi + mid + lo = the f32 value to 2^-24) of the packed DFT basis, as 16x16x32 fragments:

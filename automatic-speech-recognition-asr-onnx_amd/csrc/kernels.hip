@@ -21,6 +21,34 @@ constexpr int FB_PLD = 273;                  // power row stride (floats): 272 b
 // mel = power x melT on the same MFMA, then clamp + ln.  Frame m of the span starts at m*160, so the
 // A fragment (row = frame, k = sample) is a strided LDS read; the +1-per-hop skew makes the 16 rows
 // of a fragment hit 16 different banks.
+//
+// S is the session's audio sample type (asr_audio_dtype): float as is; int16_t raw PCM, widened at the load and -- for the Whisper / Qwen front end, whose
+// reference folds 1/32768 into the STFT window (Whisper/STFT_Process.py:143) -- scaled by 2^-15, which is exact and commutes with every later f32 rounding;
+// _Float16 widened as is. Loads are per lane and per sample (2-byte aligned only: utterances start at any sample offset). The load loop keeps the RAW samples
+// (one register each) and the store loop widens them; hold() between the two keeps the compiler from moving the conversion up to its load, where it would put a
+// wait behind every load (the round trip per sample that the load shape exists to avoid). The float instantiation has no hold and no conversion.
+// After the LDS store nothing differs.
+template <typename S> struct Pcm;
+template <> struct Pcm<float> {
+  typedef float raw_t;
+  static __device__ __forceinline__ raw_t load(const float* p, int i) { return p[i]; }
+  static __device__ __forceinline__ raw_t hold(raw_t r) { return r; }
+  static __device__ __forceinline__ float widen(raw_t r, float) { return r; }
+};
+template <> struct Pcm<int16_t> {
+  typedef int raw_t;                       // sign-extended by the load
+  static __device__ __forceinline__ raw_t load(const int16_t* p, int i) { return p[i]; }
+  static __device__ __forceinline__ raw_t hold(raw_t r) { asm volatile("" : "+v"(r)); return r; }
+  static __device__ __forceinline__ float widen(raw_t r, float scale) { return (float)r * scale; }
+};
+template <> struct Pcm<_Float16> {
+  typedef uint32_t raw_t;                  // the half's bits
+  static __device__ __forceinline__ raw_t load(const _Float16* p, int i) { return reinterpret_cast<const uint16_t*>(p)[i]; }
+  static __device__ __forceinline__ raw_t hold(raw_t r) { asm volatile("" : "+v"(r)); return r; }
+  static __device__ __forceinline__ float widen(raw_t r, float) { return (float)__builtin_bit_cast(_Float16, (uint16_t)r); }
+};
+
+template <typename S>
 __global__ __launch_bounds__(256) void fbank_kernel(const FbankArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* aud = reinterpret_cast<float*>(smem);
@@ -28,11 +56,12 @@ __global__ __launch_bounds__(256) void fbank_kernel(const FbankArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int u = a.blk_utt[blockIdx.x], f0 = a.blk_f0[blockIdx.x];
   const UttPlan up = a.plan[u];
-  const float* src = a.audio + up.audio_off;
+  const S* src = static_cast<const S*>(a.audio) + up.audio_off;
+  const float pcm_scale = a.whisper ? 0x1p-15f : 1.0f;   // int16 only
   const int s0 = f0 * HOP;
   // every thread requests all of its samples before it stores the first (a load / store loop runs as one memory round trip per iteration: see fbank_split_kernel)
   constexpr int NL = (FB_SPAN + 255) / 256;
-  float av[NL];
+  typename Pcm<S>::raw_t av[NL];
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
     // Kaldi reads x[s]; Whisper the padded signal [x[200..1] | x | x[L-2 .. L-41]]  (reflect, right pad shortened by one hop)
@@ -43,12 +72,14 @@ __global__ __launch_bounds__(256) void fbank_kernel(const FbankArgs a) {
       idx = p < half ? half - p : p < half + L ? p - half : 2 * L + half - 2 - p;
       ok = i < FB_SPAN && p < L + WIN - HOP;
     }
-    av[j] = ok ? src[idx] : 0.0f;
+    av[j] = ok ? Pcm<S>::load(src, idx) : (typename Pcm<S>::raw_t)0;
   }
+#pragma unroll
+  for (int j = 0; j < NL; ++j) av[j] = Pcm<S>::hold(av[j]);
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
     const int i = tid + j * 256;
-    if (i < FB_SPAN) aud[i + i / HOP] = av[j];
+    if (i < FB_SPAN) aud[i + i / HOP] = Pcm<S>::widen(av[j], pcm_scale);
   }
   __syncthreads();
 
@@ -140,6 +171,7 @@ constexpr int FB_A16 = ((FB_SPAN + 32 + HOP - 1) / HOP) * FB_HP; // bf16 element
 // fragment reads, its waits or its accumulator hand-offs (ablations, profiles/r05_fbank_ablations.txt: DFT 42 us and mel 26 us per workgroup against 19 + 5 us of MFMA
 // issue). Two waves per SIMD split the bin tiles (DFT) and the mel tiles (mel) of the same 64 frames; every accumulator still sums in the same order.
 constexpr int FB_WAVES = 8;
+template <typename S>
 __global__ __launch_bounds__(64 * FB_WAVES) void fbank_split_kernel(const FbankArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16_t* audh = reinterpret_cast<bf16_t*>(smem);
@@ -148,12 +180,13 @@ __global__ __launch_bounds__(64 * FB_WAVES) void fbank_split_kernel(const FbankA
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int u = a.blk_utt[blockIdx.x], f0 = a.blk_f0[blockIdx.x];
   const UttPlan up = a.plan[u];
-  const float* src = a.audio + up.audio_off;
+  const S* src = static_cast<const S*>(a.audio) + up.audio_off;
+  const float pcm_scale = a.whisper ? 0x1p-15f : 1.0f;   // int16 only
   const int s0 = f0 * HOP;
   // the workgroup's audio span: every thread requests ALL of its samples before it uses the first (written as one loop of load / split / store the compiler kept the
   // loads in program order behind a wait each -- 42 dependent memory round trips, ~60 of the workgroup's ~78 us, with nothing else on the CU to cover them)
   constexpr int FB_NL = (FB_SPAN + 32 + 64 * FB_WAVES - 1) / (64 * FB_WAVES);
-  float av[FB_NL];
+  typename Pcm<S>::raw_t av[FB_NL];
 #pragma unroll
   for (int j = 0; j < FB_NL; ++j) {
     const int i = tid + j * 64 * FB_WAVES;
@@ -165,13 +198,15 @@ __global__ __launch_bounds__(64 * FB_WAVES) void fbank_split_kernel(const FbankA
       idx = p < half ? half - p : p < half + L ? p - half : 2 * L + half - 2 - p;
       ok = i < FB_SPAN + 32 && p < L + WIN - HOP;
     }
-    av[j] = (ok && !(a.dbg & 4)) ? src[idx] : 0.0f;
+    av[j] = (ok && !(a.dbg & 4)) ? Pcm<S>::load(src, idx) : (typename Pcm<S>::raw_t)0;
   }
+#pragma unroll
+  for (int j = 0; j < FB_NL; ++j) av[j] = Pcm<S>::hold(av[j]);
 #pragma unroll
   for (int j = 0; j < FB_NL; ++j) {
     const int i = tid + j * 64 * FB_WAVES;
     if (i < FB_SPAN + 32) {
-      const float v = av[j];
+      const float v = Pcm<S>::widen(av[j], pcm_scale);
       const uint32_t hb = pack_bf16x2(v, 0.0f) & 0xffffu;
       const float hi = __uint_as_float(hb << 16);
       const int pos = i + (i / HOP) * 8;
@@ -1468,14 +1503,15 @@ __global__ void gather_tokens_kernel(const int32_t* __restrict__ ids, const UttP
 }  // namespace
 
 // ==================================================================================== launchers
-void launch_fbank(const FbankArgs& a, int n_blocks, hipStream_t s) {
+template <typename S>
+static void launch_fbank_typed(const FbankArgs& a, int n_blocks, hipStream_t s) {
   ASR_REQUIRE(a.win == WIN && a.hop == HOP, "fbank: only win=400 hop=160 is built (got %d/%d)", a.win, a.hop);
   ASR_REQUIRE(a.n_bin_tiles * 16 <= FB_PLD - 1, "fbank: too many frequency bins");
   ASR_REQUIRE(a.n_kchunks * 16 == WIN, "fbank: k-chunks must cover the window");
   const size_t lds = (size_t)(FB_AUDIO_LDS + FB_FRAMES * FB_PLD) * sizeof(float);
   static PerDeviceOnce attr_once;
   if (attr_once.first()) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fbank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fbank_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   if (a.dft_split) {
     FbankArgs b = a;
@@ -1483,14 +1519,22 @@ void launch_fbank(const FbankArgs& a, int n_blocks, hipStream_t s) {
     const size_t lds2 = (size_t)FB_A16 * 2 * 2 + (size_t)FB_FRAMES * FB_PLD * sizeof(float);
     static PerDeviceOnce attr2_once;
     if (attr2_once.first()) {
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fbank_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fbank_split_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
     }
-    hipLaunchKernelGGL(fbank_split_kernel, dim3(n_blocks), dim3(64 * FB_WAVES), lds2, s, b);
+    hipLaunchKernelGGL(fbank_split_kernel<S>, dim3(n_blocks), dim3(64 * FB_WAVES), lds2, s, b);
     HIP_CHECK(hipGetLastError());
     return;
   }
-  hipLaunchKernelGGL(fbank_kernel, dim3(n_blocks), dim3(256), lds, s, a);
+  hipLaunchKernelGGL(fbank_kernel<S>, dim3(n_blocks), dim3(256), lds, s, a);
   HIP_CHECK(hipGetLastError());
+}
+void launch_fbank(const FbankArgs& a, int n_blocks, hipStream_t s) {
+  switch (a.audio_dtype) {
+    case AUDIO_F32: return launch_fbank_typed<float>(a, n_blocks, s);
+    case AUDIO_I16: return launch_fbank_typed<int16_t>(a, n_blocks, s);
+    case AUDIO_F16: return launch_fbank_typed<_Float16>(a, n_blocks, s);
+    default: ASR_THROW(ASR_ERR_INVALID, "fbank: unknown audio sample type %d", a.audio_dtype);
+  }
 }
 
 size_t fbank_split_table_bytes(int n_bin_tiles, int win) {

@@ -708,7 +708,7 @@ struct QwSession : asr_session {
   }
   void init();
   bool aligner() const { return cfg.classify_num > 0; }
-  template <typename T> void prefill(const float* audio, int audio_mem, const int64_t* offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
+  template <typename T> void prefill(const void* audio, int audio_mem, const int64_t* offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
                                      const int32_t* post_ids, const int32_t* post_off, int32_t* next_out, float* logits_out, int32_t* ids_len_out,
                                      const AlignReq* al = nullptr);
   template <typename T> void align_head(int B, const UttPlan* ddp, const int32_t* d_src, int n_sel, const AlignReq& al);
@@ -1067,7 +1067,7 @@ void QwSession::finish(int B, int32_t* next_out, float* logits_out, bool sync) {
 }
 
 template <typename T>
-void QwSession::prefill(const float* audio, int audio_mem, const int64_t* offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
+void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
                         const int32_t* post_ids, const int32_t* post_off, int32_t* next_out, float* logits_out, int32_t* ids_len_out,
                         const AlignReq* al) {
   const auto& c = cfg;
@@ -1209,14 +1209,13 @@ void QwSession::prefill(const float* audio, int audio_mem, const int64_t* offs, 
   const int32_t* d_dqb_utt = d_last_rows + B;
   const int32_t* d_dqb_q0 = d_dqb_utt + n_dqb;
 
-  const float* d_aud;
+  const size_t eA = audio_elt();                          // the session's sample type: offsets are samples, bytes step in eA
+  const void* d_aud = static_cast<const unsigned char*>(audio) + (size_t)base0 * eA;
   const int64_t total_samples = offs[B] - base0;
   if (audio_mem == ASR_MEM_HOST) {
-    d_audio.reserve((size_t)total_samples * 4, stream);
-    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, audio + base0, (size_t)total_samples * 4, hipMemcpyHostToDevice, stream));
-    d_aud = d_audio.as<float>();
-  } else {
-    d_aud = audio + base0;
+    d_audio.reserve((size_t)total_samples * eA, stream);
+    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, d_aud, (size_t)total_samples * eA, hipMemcpyHostToDevice, stream));
+    d_aud = d_audio.ptr;
   }
   // ---- front-end + conv stem
   const size_t r1 = (size_t)slots * 50 * 64, r2 = (size_t)slots * 25 * 32, r3 = (size_t)wins * rpw * 16;
@@ -1238,10 +1237,11 @@ void QwSession::prefill(const float* audio, int audio_mem, const int64_t* offs, 
   {
     ProfScope ps(prof, "logmel", stream);
     FbankArgs fa;
-    fa.audio = d_aud; fa.plan = dup; fa.blk_utt = d_blk_utt; fa.blk_f0 = d_blk_f0; fa.dft_packed = dft; fa.mel_packed = melp;
+    fa.audio = d_aud; fa.audio_dtype = audio_dtype; fa.plan = dup; fa.blk_utt = d_blk_utt; fa.blk_f0 = d_blk_f0; fa.dft_packed = dft; fa.mel_packed = melp;
     fa.mel_out = d_mel.as<float>(); fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = c.n_mels / 16; fa.n_mels = c.n_mels;
     fa.win = c.nfft; fa.hop = c.hop_length; fa.log_floor = 1e-10f; fa.whisper = 1; fa.blk_max = d_blkmax.as<float>();
     launch_fbank(fa, n_fb, stream);
+    if (taps_enabled) save_tap("mel", d_mel.ptr, frames, c.n_mels, c.n_mels, 4);       // log10 mel before the per-utterance clamp: what the front end made of the samples
     hipLaunchKernelGGL(qw_mel_finish_kernel<T>, dim3(slots * chunk), dim3(128), 0, stream, d_mel.as<float>(), d_blkmax.as<float>(), dup, d_slot_utt,
                        d_slot_local, c.n_mels, chunk, d_feat.as<T>());
   }
@@ -1605,7 +1605,7 @@ extern "C" int asr_qwen_create(const asr_qwen_config* cfg, const void* arena, si
   });
 }
 
-extern "C" int asr_qwen_prefill(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
+extern "C" int asr_qwen_prefill(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
                                 const int32_t* pre_offsets, const int32_t* post_ids, const int32_t* post_offsets, int32_t* next_ids_out,
                                 float* logits_out, int32_t* ids_len_out) {
   return asr_guard([&] {
@@ -1744,7 +1744,7 @@ extern "C" int asr_qwen_generate(asr_session* s, int max_new, const int32_t* sto
   });
 }
 
-extern "C" int asr_qwen_align(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
+extern "C" int asr_qwen_align(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
                               const int32_t* pre_offsets, const int32_t* post_ids, const int32_t* post_offsets, int32_t timestamp_id,
                               int32_t* slot_offsets_out, int32_t* buckets_out, int64_t buckets_cap, float* logits_out, int32_t* ids_len_out) {
   return asr_guard([&] {

@@ -84,7 +84,7 @@ struct SvSession : asr_session {
   void ensure_stream_shadow();
   void stream_init(int chunk, int look_back_encoder, int look_back_decoder, int max_streams);
   void stream_reset(int sid);
-  template <typename T> void stream_step(const float* audio, int audio_mem, const int32_t* stream_ids, int n, int32_t* tok_out, int max_tokens,
+  template <typename T> void stream_step(const void* audio, int audio_mem, const int32_t* stream_ids, int n, int32_t* tok_out, int max_tokens,
                                          int32_t* num_out);
   bool use_graph = true;
   bool use_ln_alg = true;       // LayerNorm evaluated inside the projections from row statistics (ASR_LN_FUSED=0 disables)
@@ -139,7 +139,7 @@ struct SvSession : asr_session {
   void init();
   void copy_block_status(const struct SvRunCtx& r);   // the block kernel's error word rides home behind the token counts
   template <typename T> void enqueue(const struct SvRunCtx& r);
-  template <typename T> void run(const float* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang,
+  template <typename T> void run(const void* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang,
                                  int32_t* tok_out, int max_tokens, int32_t* num_out);
   DeviceBuffer d_skws, d_skcnt;        // split-K workspace + tickets of the skinny GEMM (per session: sessions may run concurrently)
   void gemm(const GemmArgs& g0) {
@@ -267,7 +267,7 @@ void SvSession::init() {
 // Everything a forward pass needs once the host plan is uploaded; captured into a hipGraph for replay.
 struct SvRunCtx {
   int batch, rows, Mpad, frames, n_fb, n_qb, max_T, max_tokens, att_qt, att_nw;
-  const float* d_aud;
+  const void* d_aud;          // packed samples of the session's audio_dtype
   const UttPlan* dp;
   const int32_t *d_blk_utt, *d_blk_f0, *d_qb_utt, *d_qb_q0, *d_row_utt;
   const int32_t *d_tile_win = nullptr, *d_tile_idx = nullptr;    // small batches (sanm_tiles.hip): per 16-row tile its window / its index inside the window
@@ -331,7 +331,7 @@ void SvSession::enqueue(const SvRunCtx& r) {
   {
     ProfScope ps(prof, "fbank", stream);
     FbankArgs fa;
-    fa.audio = r.d_aud; fa.plan = r.dp; fa.blk_utt = r.d_blk_utt; fa.blk_f0 = r.d_blk_f0;
+    fa.audio = r.d_aud; fa.audio_dtype = audio_dtype; fa.plan = r.dp; fa.blk_utt = r.d_blk_utt; fa.blk_f0 = r.d_blk_f0;
     fa.dft_packed = dft; fa.mel_packed = melp; fa.mel_out = d_mel.as<float>();
     fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = c.n_mels / 16; fa.n_mels = c.n_mels;
     fa.win = c.win_length; fa.hop = c.hop_length; fa.log_floor = 1.1920928955078125e-07f; fa.whisper = 0; fa.blk_max = nullptr;
@@ -715,7 +715,7 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
 }
 
 template <typename T>
-void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang, int32_t* tok_out,
+void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang, int32_t* tok_out,
                     int max_tokens, int32_t* num_out) {
   const auto& c = cfg;
   ASR_REQUIRE(batch > 0, "sensevoice: empty batch");
@@ -796,7 +796,8 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
   const size_t eT = sizeof(T);
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { void* before = buf.ptr; buf.reserve(bytes, stream); if (buf.ptr != before) ++ws_epoch; };
   grow(d_plan, plan_bytes);
-  if (audio_mem == ASR_MEM_HOST) grow(d_audio, (size_t)total_samples * 4);
+  const size_t eA = audio_elt();                       // the session's sample type: offsets are samples, bytes step in eA
+  if (audio_mem == ASR_MEM_HOST) grow(d_audio, (size_t)total_samples * eA);
   grow(d_mel, (size_t)frames * c.n_mels * 4);
   grow(d_x0, (size_t)Mpad * kpad0 * 4);
   grow(d_xa, (size_t)Mpad * d * 4);
@@ -844,11 +845,10 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
   if (h_out.reserve(out_bytes)) ++ws_epoch;
 
   HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan.ptr, plan_bytes, hipMemcpyHostToDevice, stream));
+  r.d_aud = static_cast<const unsigned char*>(audio) + (size_t)base0 * eA;
   if (audio_mem == ASR_MEM_HOST) {
-    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, audio + base0, (size_t)total_samples * 4, hipMemcpyHostToDevice, stream));
-    r.d_aud = d_audio.as<float>();
-  } else {
-    r.d_aud = audio + base0;
+    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, r.d_aud, (size_t)total_samples * eA, hipMemcpyHostToDevice, stream));
+    r.d_aud = d_audio.ptr;
   }
   r.batch = batch; r.rows = rows; r.Mpad = Mpad; r.frames = frames; r.n_fb = n_fb; r.n_qb = n_qb; r.max_T = max_T;
   r.max_tokens = max_tokens; r.att_qt = att_qt; r.att_nw = att_nw;
@@ -861,7 +861,7 @@ void SvSession::run(const float* audio, int audio_mem, const int64_t* offs, int 
   r.d_row_utt = r.d_qb_q0 + n_qb;
   r.d_tile_win = r.d_row_utt + Mpad;
   r.d_tile_idx = r.d_tile_win + n_tiles;
-  key.mix((uint64_t)batch); key.mix((uint64_t)max_tokens); key.mix((uint64_t)(uintptr_t)r.d_aud); key.mix(ws_epoch); key.mix((uint64_t)(uintptr_t)stream);
+  key.mix((uint64_t)batch); key.mix((uint64_t)max_tokens); key.mix((uint64_t)(uintptr_t)r.d_aud); key.mix((uint64_t)audio_dtype); key.mix(ws_epoch); key.mix((uint64_t)(uintptr_t)stream);
   key.mix((uint64_t)(block_cooldown > 0 || foreign_now));        // a session cooling down after a cluster give-up replays the four-launch capture, not the block one
 
   if (sizeof(T) == 2 && use_block && cfg.n_blocks > 1 && blocks[cfg.n_blocks - 1].cqkv && blocks[cfg.n_blocks - 1].c1 && batch >= block_min_utts &&
@@ -1083,7 +1083,7 @@ void SvSession::stream_reset(int sid) {
 }
 
 template <typename T>
-void SvSession::stream_step(const float* audio, int audio_mem, const int32_t* stream_ids, int n, int32_t* tok_out, int max_tokens,
+void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* stream_ids, int n, int32_t* tok_out, int max_tokens,
                             int32_t* num_out) {
   const auto& c = cfg;
   ASR_REQUIRE(st_max > 0, "streaming: session was not created with asr_paraformer_stream_create");
@@ -1115,7 +1115,8 @@ void SvSession::stream_step(const float* audio, int audio_mem, const int32_t* st
   const size_t eT = sizeof(T);
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { buf.reserve(bytes, stream); };
   grow(d_plan, plan_bytes);
-  if (audio_mem == ASR_MEM_HOST) grow(d_audio, (size_t)n * st_chunk * 4);
+  const size_t eA = audio_elt();
+  if (audio_mem == ASR_MEM_HOST) grow(d_audio, (size_t)n * st_chunk * eA);
   grow(d_mel, (size_t)frames * c.n_mels * 4);
   grow(d_x0, (size_t)Mpad * kpad0 * 4);
   grow(d_xa, (size_t)Mpad * d * 4);
@@ -1148,10 +1149,10 @@ void SvSession::stream_step(const float* audio, int audio_mem, const int32_t* st
   const size_t out_bytes = (size_t)n * max_tokens * 4 + (size_t)n * 4;
   h_out.reserve(out_bytes + 16);
   HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan.ptr, plan_bytes, hipMemcpyHostToDevice, stream));
-  const float* d_aud = audio;
+  const void* d_aud = audio;
   if (audio_mem == ASR_MEM_HOST) {
-    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, audio, (size_t)n * st_chunk * 4, hipMemcpyHostToDevice, stream));
-    d_aud = d_audio.as<float>();
+    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, audio, (size_t)n * st_chunk * eA, hipMemcpyHostToDevice, stream));
+    d_aud = d_audio.ptr;
   }
   // ---- which path this step takes (see the comment at st_fused_max)
   bool step_fused = st_fused && std::is_same<T, bf16_t>::value && n <= st_fused_max && st_cooldown == 0 && !foreign_now;
@@ -1176,13 +1177,14 @@ void SvSession::stream_step(const float* audio, int audio_mem, const int32_t* st
   {
     ProfScope ps(prof, "fbank", stream);
     FbankArgs fa;
-    fa.audio = d_aud; fa.plan = dp; fa.blk_utt = d_blk_utt; fa.blk_f0 = d_blk_f0;
+    fa.audio = d_aud; fa.audio_dtype = audio_dtype; fa.plan = dp; fa.blk_utt = d_blk_utt; fa.blk_f0 = d_blk_f0;
     fa.dft_packed = dft; fa.mel_packed = melp; fa.mel_out = d_mel.as<float>();
     fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = c.n_mels / 16; fa.n_mels = c.n_mels;
     fa.win = c.win_length; fa.hop = c.hop_length; fa.log_floor = 1.1920928955078125e-07f; fa.whisper = 0; fa.blk_max = nullptr;
     fa.dft_split = d_dft_split.ptr;
     launch_fbank(fa, n, stream);
   }
+  if (taps_enabled) save_tap("mel", d_mel.ptr, frames, c.n_mels, c.n_mels, 4);
   {
     ProfScope ps(prof, "lfr_cmvn", stream);
     StreamLfrArgs la;
@@ -1420,6 +1422,7 @@ void SvSession::stream_step(const float* audio, int audio_mem, const int32_t* st
                           (const void*)d_sa.ptr, (const void*)d_ffn32.ptr, (const void*)d_tplan.ptr, (const void*)stream, (const void*)(uintptr_t)n,
                           (const void*)(uintptr_t)max_tokens, (const void*)st_shadow.ptr, (const void*)d_xblo.ptr, (const void*)d_stb.ptr})
       key.mix(q);
+    key.mix((uint64_t)audio_dtype);                                 // the front end is inside the captured step
     const int gi = step_fused ? (snapshot ? 2 : 1) : 0;            // one cached graph per path: a session that alternates (a co-tenant comes and goes) does not re-capture
     st_graph[gi].run(stream, use_graph && !taps_enabled && !prof.enabled && !inject_fault, key.h, enqueue);
   }
@@ -1501,7 +1504,7 @@ extern "C" int asr_sensevoice_create(const asr_sensevoice_config* cfg, const voi
   });
 }
 
-extern "C" int asr_sensevoice_run(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+extern "C" int asr_sensevoice_run(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                                   const int32_t* language_idx, int32_t* token_ids_out, int max_tokens, int32_t* num_id_out) {
   return asr_guard([&] {
     ASR_REQUIRE(s && s->kind == 1, "sensevoice_run: not a SenseVoice session");
@@ -1579,7 +1582,7 @@ extern "C" int asr_paraformer_stream_reset(asr_session* s, int stream_id) {
   });
 }
 
-extern "C" int asr_paraformer_stream_step(asr_session* s, const float* audio, int audio_mem, const int32_t* stream_ids, int n_streams,
+extern "C" int asr_paraformer_stream_step(asr_session* s, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams,
                                           int32_t* token_ids_out, int max_tokens, int32_t* num_id_out) {
   return asr_guard([&] {
     ASR_REQUIRE(s && s->kind == 4, "paraformer_stream_step: not a streaming Paraformer session");
@@ -1608,7 +1611,7 @@ extern "C" int asr_sanm_stats(asr_session* s, int32_t* out8) {
   });
 }
 
-extern "C" int asr_paraformer_run(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+extern "C" int asr_paraformer_run(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                                   int32_t* token_ids_out, int max_tokens, int32_t* num_id_out) {
   return asr_guard([&] {
     ASR_REQUIRE(s && s->kind == 3, "paraformer_run: not a Paraformer session");

@@ -132,7 +132,7 @@ struct WhSession : asr_session {
     g.sk_ws = d_skws.as<float>(); g.sk_ws_bytes = SK_WS_BYTES; g.sk_cnt = d_skcnt.as<int32_t>();
     launch_gemm_bf16(g, stream);
   }
-  template <typename T> void encode(const float* audio, int audio_mem, const int64_t* offs, int B, int32_t* n_pos_out);
+  template <typename T> void encode(const void* audio, int audio_mem, const int64_t* offs, int B, int32_t* n_pos_out);
   template <typename T> void enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev, const BeamStep* bs = nullptr);
   template <typename T> void step(const int32_t* ids_host, int n, bool is_prefill, int32_t* next_out, float* logits_out);
   template <typename T> void beam_search(int beam, int max_new, int eos_id, int32_t* tokens_out, int32_t* n_out, float* scores_out);
@@ -236,7 +236,7 @@ void WhSession::init() {
 
 // ======================================================================================== encoder
 template <typename T>
-void WhSession::encode(const float* audio, int audio_mem, const int64_t* offs, int B, int32_t* n_pos_out) {
+void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, int B, int32_t* n_pos_out) {
   const auto& c = cfg;
   ASR_REQUIRE(B > 0 && audio && offs, "whisper_encode: bad argument");
   HIP_CHECK(hipSetDevice(device));
@@ -320,13 +320,12 @@ void WhSession::encode(const float* audio, int audio_mem, const int64_t* offs, i
   const int32_t* d_grow_utt = d_pos_rows + Mg;
 
   const size_t eT = sizeof(T);
-  const float* d_aud;
+  const size_t eA = audio_elt();                                    // the session's sample type: offsets are samples, bytes step in eA
+  const void* d_aud = static_cast<const unsigned char*>(audio) + (size_t)base0 * eA;
   if (audio_mem == ASR_MEM_HOST) {
-    d_audio.reserve((size_t)total_samples * 4, stream);
-    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, audio + base0, (size_t)total_samples * 4, hipMemcpyHostToDevice, stream));
-    d_aud = d_audio.as<float>();
-  } else {
-    d_aud = audio + base0;
+    d_audio.reserve((size_t)total_samples * eA, stream);
+    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, d_aud, (size_t)total_samples * eA, hipMemcpyHostToDevice, stream));
+    d_aud = d_audio.ptr;
   }
   const int Rpad = R + 256;                                        // tile-edge + halo rows of the strided conv views
   d_mel.reserve((size_t)frames * c.n_mels * 4, stream);
@@ -347,7 +346,7 @@ void WhSession::encode(const float* audio, int audio_mem, const int64_t* offs, i
   {
     ProfScope ps(prof, "logmel", stream);
     FbankArgs fa;
-    fa.audio = d_aud; fa.plan = dp; fa.blk_utt = d_blk_utt; fa.blk_f0 = d_blk_f0; fa.dft_packed = dft; fa.mel_packed = melp;
+    fa.audio = d_aud; fa.audio_dtype = audio_dtype; fa.plan = dp; fa.blk_utt = d_blk_utt; fa.blk_f0 = d_blk_f0; fa.dft_packed = dft; fa.mel_packed = melp;
     fa.mel_out = d_mel.as<float>(); fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = c.n_mels / 16;
     fa.n_mels = c.n_mels; fa.win = c.nfft; fa.hop = c.hop_length; fa.log_floor = 1e-10f; fa.whisper = 1;
     fa.blk_max = d_blkmax.as<float>();
@@ -914,7 +913,7 @@ extern "C" int asr_whisper_create(const asr_whisper_config* cfg, const void* are
   });
 }
 
-extern "C" int asr_whisper_encode(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+extern "C" int asr_whisper_encode(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                                   int32_t* n_positions_out) {
   return asr_guard([&] {
     ASR_REQUIRE(s && s->kind == 2, "whisper_encode: not a Whisper session");

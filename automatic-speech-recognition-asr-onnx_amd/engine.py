@@ -12,6 +12,27 @@ from .arena import PRECISION_BF16, PRECISION_F32, PRECISION_FP8MM, PRECISION_FP8
 from .config import SenseVoiceConfig
 
 MEM_HOST, MEM_DEVICE = 0, 1
+AUDIO_F32, AUDIO_I16, AUDIO_F16 = 0, 1, 2                         # asr_audio_dtype
+# the reference's INPUT_AUDIO_DTYPE names (Export_*.py) <-> sample types
+AUDIO_DTYPE_NAMES = {"F32": np.dtype(np.float32), "INT16": np.dtype(np.int16), "F16": np.dtype(np.float16)}
+_AUDIO_CODES = {np.dtype(np.float32): AUDIO_F32, np.dtype(np.int16): AUDIO_I16, np.dtype(np.float16): AUDIO_F16}
+
+
+def audio_np_dtype(audio_dtype) -> np.dtype:
+    """"INT16" | "F32" | "F16" (the reference's INPUT_AUDIO_DTYPE) or a numpy dtype -> one of the three sample types; ValueError otherwise."""
+    if isinstance(audio_dtype, str):
+        if audio_dtype not in AUDIO_DTYPE_NAMES:
+            raise ValueError(f"input audio dtype {audio_dtype!r}: expected one of {sorted(AUDIO_DTYPE_NAMES)}")
+        return AUDIO_DTYPE_NAMES[audio_dtype]
+    dt = np.dtype(audio_dtype)
+    if dt not in _AUDIO_CODES:
+        raise ValueError(f"audio dtype {dt.name}: expected float32, int16 or float16")
+    return dt
+
+
+def audio_dtype_name(audio_dtype) -> str:
+    dt = audio_np_dtype(audio_dtype)
+    return next(k for k, v in AUDIO_DTYPE_NAMES.items() if v == dt)
 
 
 def _f32(a):
@@ -43,6 +64,36 @@ class _Session:
     def __init__(self):
         self._h = C.c_void_p(None)
         self._keep = None
+        self._audio_np = np.dtype(np.float32)
+
+    @property
+    def audio_dtype(self) -> np.dtype:
+        """Sample type of the audio entries (asr_session_set_audio_dtype): float32 (default), int16 or float16. What a type means follows the
+        family's export (include/asr_mi355x.h, asr_audio_dtype). May be set between any two calls."""
+        return self._audio_np
+
+    @audio_dtype.setter
+    def audio_dtype(self, audio_dtype):
+        dt = audio_np_dtype(audio_dtype)
+        _lib.check(_lib.load().asr_session_set_audio_dtype(self._h, _AUDIO_CODES[dt]))
+        self._audio_np = dt
+
+    def _audio(self, a) -> np.ndarray:
+        """Clips in the session's sample type. A float32 session coerces whatever it is given; a 2-byte session takes exactly its own type: nothing is
+        rounded or rescaled silently."""
+        if self._audio_np == np.float32:
+            return _f32(a)
+        got = a.dtype if isinstance(a, np.ndarray) else np.asarray(a).dtype
+        if got != self._audio_np:
+            raise TypeError(f"{type(self).__name__}: the session's audio_dtype is {self._audio_np.name}, the audio given is {got.name} "
+                            f"(convert it explicitly, or set audio_dtype)")
+        return np.ascontiguousarray(a)
+
+    def _pack(self, audios):
+        flat = [self._audio(a).reshape(-1) for a in audios]
+        offs = np.zeros(len(flat) + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([a.size for a in flat])
+        return flat, np.concatenate(flat), offs
 
     def close(self):
         if self._h:
@@ -99,7 +150,7 @@ class SenseVoiceSession(_Session):
     """HIP replacement of `SenseVoiceSmall.onnx` (SENSE_VOICE.forward, Export_SenseVoice.py:271-296)."""
 
     def __init__(self, cfg: SenseVoiceConfig, arena, precision: int = PRECISION_BF16, device_id: int = 0,
-                 arena_device_ptr: int | None = None, arena_bytes: int | None = None):
+                 arena_device_ptr: int | None = None, arena_bytes: int | None = None, audio_dtype=np.float32):
         super().__init__()
         self.cfg, self.precision, self.device_id = cfg, precision, device_id
         self._cfg_c = sensevoice_config_c(cfg)
@@ -112,16 +163,17 @@ class SenseVoiceSession(_Session):
             blob = np.ascontiguousarray(arena, dtype=np.uint8)
             _lib.check(lib.asr_sensevoice_create(C.byref(self._cfg_c), blob.ctypes.data_as(C.c_void_p), blob.nbytes, MEM_HOST,
                                                  device_id, precision, C.byref(self._h)))
+        self.audio_dtype = audio_dtype
 
     @classmethod
-    def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0):
-        return cls(cfg, build_sensevoice_arena(cfg, ck, precision), precision, device_id)
+    def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0, audio_dtype=np.float32):
+        return cls(cfg, build_sensevoice_arena(cfg, ck, precision), precision, device_id, audio_dtype=audio_dtype)
 
     def seq_len(self, n_samples: int) -> int:
         return self.cfg.seq_len(n_samples)
 
     def run_packed(self, audio, offsets: np.ndarray, language_idx: np.ndarray, audio_device_ptr: int | None = None):
-        """audio: packed f32 samples (host ndarray) or None with `audio_device_ptr` (HBM-resident).
+        """audio: packed samples of the session's audio_dtype (host ndarray) or None with `audio_device_ptr` (HBM-resident, same type).
         Returns (token_ids [B, max_T] int32, num_id [B] int32)."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         lang = np.ascontiguousarray(language_idx, dtype=np.int32)
@@ -134,7 +186,7 @@ class SenseVoiceSession(_Session):
         if audio_device_ptr is not None:
             ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
         else:
-            audio = _f32(audio).reshape(-1)
+            audio = self._audio(audio).reshape(-1)
             ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
         _lib.check(lib.asr_sensevoice_run(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(lang),
                                           _ip(tok), max_t, _ip(num)))
@@ -142,10 +194,8 @@ class SenseVoiceSession(_Session):
 
     def run(self, audios: Sequence[np.ndarray], language_idx: Sequence[int]):
         """List of 1-D utterances -> list of int32 token-id arrays (one per utterance)."""
-        flat = [_f32(a).reshape(-1) for a in audios]
-        offs = np.zeros(len(flat) + 1, dtype=np.int64)
-        offs[1:] = np.cumsum([a.size for a in flat])
-        tok, num = self.run_packed(np.concatenate(flat), offs, np.asarray(language_idx, dtype=np.int32))
+        flat, packed, offs = self._pack(audios)
+        tok, num = self.run_packed(packed, offs, np.asarray(language_idx, dtype=np.int32))
         return [tok[b, :num[b]].copy() for b in range(len(flat))]
 
     def utterance_rows(self, lengths: Sequence[int]):
@@ -240,7 +290,7 @@ class WhisperSession(_Session):
     """HIP replacement of the merged Whisper graphs (encoder + KV-cache decoder + greedy heads)."""
 
     def __init__(self, cfg, arena, precision: int = PRECISION_BF16, device_id: int = 0, gelu_tanh: bool = False,
-                 arena_device_ptr: int | None = None, arena_bytes: int | None = None):
+                 arena_device_ptr: int | None = None, arena_bytes: int | None = None, audio_dtype=np.float32):
         super().__init__()
         self.cfg, self.precision, self.device_id = cfg, precision, device_id
         self._cfg_c = whisper_config_c(cfg, gelu_tanh)
@@ -254,13 +304,15 @@ class WhisperSession(_Session):
             _lib.check(lib.asr_whisper_create(C.byref(self._cfg_c), blob.ctypes.data_as(C.c_void_p), blob.nbytes, MEM_HOST,
                                               device_id, precision, C.byref(self._h)))
         self.batch = 0
+        self.audio_dtype = audio_dtype
 
     @classmethod
     def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0, suppress_tokens=None, begin_suppress_tokens=(),
-                        gelu_tanh=False):
+                        gelu_tanh=False, audio_dtype=np.float32):
         from .arena import build_whisper_arena
         arena_precision = PRECISION_BF16 if precision in (PRECISION_FP8W, PRECISION_FP8MM, PRECISION_MXFP4W) else precision
-        return cls(cfg, build_whisper_arena(cfg, ck, arena_precision, suppress_tokens, begin_suppress_tokens), precision, device_id, gelu_tanh)
+        return cls(cfg, build_whisper_arena(cfg, ck, arena_precision, suppress_tokens, begin_suppress_tokens), precision, device_id, gelu_tanh,
+                   audio_dtype=audio_dtype)
 
     def encode_packed(self, audio, offsets, audio_device_ptr: int | None = None) -> np.ndarray:
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -269,7 +321,7 @@ class WhisperSession(_Session):
         if audio_device_ptr is not None:
             ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
         else:
-            audio = _f32(audio).reshape(-1)
+            audio = self._audio(audio).reshape(-1)
             ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
         _lib.check(_lib.load().asr_whisper_encode(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(npos)))
         self.batch = B
@@ -292,10 +344,8 @@ class WhisperSession(_Session):
         _lib.check(_lib.load().asr_whisper_set_fp8_act_shift(self._h, int(shift)))
 
     def encode(self, audios: Sequence[np.ndarray]) -> np.ndarray:
-        flat = [_f32(a).reshape(-1) for a in audios]
-        offs = np.zeros(len(flat) + 1, dtype=np.int64)
-        offs[1:] = np.cumsum([a.size for a in flat])
-        return self.encode_packed(np.concatenate(flat), offs)
+        _, packed, offs = self._pack(audios)
+        return self.encode_packed(packed, offs)
 
     def prefill(self, ids, want_logits: bool = True):
         ids = np.ascontiguousarray(ids, dtype=np.int32)
@@ -373,7 +423,7 @@ class ParaformerSession(_Session):
     """HIP replacement of `Paraformer.onnx` (PARAFORMER.forward, Export_Paraformer.py:474-563)."""
 
     def __init__(self, cfg, arena, precision: int = PRECISION_BF16, device_id: int = 0, arena_device_ptr: int | None = None,
-                 arena_bytes: int | None = None):
+                 arena_bytes: int | None = None, audio_dtype=np.float32):
         super().__init__()
         self.cfg, self.precision, self.device_id = cfg, precision, device_id
         c = _lib.ParaformerConfigC()
@@ -392,11 +442,12 @@ class ParaformerSession(_Session):
             blob = np.ascontiguousarray(arena, dtype=np.uint8)
             _lib.check(lib.asr_paraformer_create(C.byref(c), blob.ctypes.data_as(C.c_void_p), blob.nbytes, MEM_HOST, device_id, precision,
                                                  C.byref(self._h)))
+        self.audio_dtype = audio_dtype
 
     @classmethod
-    def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0):
+    def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0, audio_dtype=np.float32):
         from .arena import build_paraformer_arena
-        return cls(cfg, build_paraformer_arena(cfg, ck, precision), precision, device_id)
+        return cls(cfg, build_paraformer_arena(cfg, ck, precision), precision, device_id, audio_dtype=audio_dtype)
 
     def run_packed(self, audio, offsets, audio_device_ptr: int | None = None):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -407,16 +458,14 @@ class ParaformerSession(_Session):
         if audio_device_ptr is not None:
             ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
         else:
-            audio = _f32(audio).reshape(-1)
+            audio = self._audio(audio).reshape(-1)
             ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
         _lib.check(_lib.load().asr_paraformer_run(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(tok), max_t, _ip(num)))
         return tok, num
 
     def run(self, audios: Sequence[np.ndarray]):
-        flat = [_f32(a).reshape(-1) for a in audios]
-        offs = np.zeros(len(flat) + 1, dtype=np.int64)
-        offs[1:] = np.cumsum([a.size for a in flat])
-        tok, num = self.run_packed(np.concatenate(flat), offs)
+        flat, packed, offs = self._pack(audios)
+        tok, num = self.run_packed(packed, offs)
         return [tok[b, :num[b]].copy() for b in range(len(flat))]
 
     def utterance_rows(self, lengths: Sequence[int]):
@@ -443,7 +492,7 @@ class ParaformerStreamSession(_Session):
     K/V histories) lives in the session; `step` advances a set of streams by one chunk (Export_Paraformer_Streaming.py:386-553)."""
 
     def __init__(self, cfg, ck_or_arena, precision: int = PRECISION_BF16, device_id: int = 0, chunk: int = 8000, look_back_encoder: int = 4,
-                 look_back_decoder: int = 1, max_streams: int = 8, max_continue: int = 502):
+                 look_back_decoder: int = 1, max_streams: int = 8, max_continue: int = 502, audio_dtype=np.float32):
         super().__init__()
         import dataclasses
         from .arena import build_paraformer_arena
@@ -463,18 +512,19 @@ class ParaformerStreamSession(_Session):
         c.tail_threshold = cfg.tail_threshold
         _lib.check(_lib.load().asr_paraformer_stream_create(C.byref(c), blob.ctypes.data_as(C.c_void_p), blob.nbytes, MEM_HOST, device_id, precision,
                                                             int(chunk), look_back_encoder, look_back_decoder, int(max_streams), C.byref(self._h)))
+        self.audio_dtype = audio_dtype
 
     def reset(self, stream_id: int = -1):
         _lib.check(_lib.load().asr_paraformer_stream_reset(self._h, int(stream_id)))
 
     def step(self, chunks, stream_ids, audio_device_ptr: int | None = None):
-        """chunks: (n, chunk) int16-range float32 (or None with `audio_device_ptr`: HBM-resident [n][chunk] floats); stream_ids: n
+        """chunks: (n, chunk) int16-range samples of the session's audio_dtype (or None with `audio_device_ptr`: HBM-resident [n][chunk]); stream_ids: n
         distinct ids -> list of n int32 arrays (tokens fired by this chunk)."""
         sid = np.ascontiguousarray(stream_ids, dtype=np.int32)
         if audio_device_ptr is not None:
             ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
         else:
-            a = _f32(chunks).reshape(sid.size, self.chunk)
+            a = self._audio(chunks).reshape(sid.size, self.chunk)
             ap, mem = a.ctypes.data_as(C.c_void_p), MEM_HOST
         cap = self.rows_per_chunk + 1
         tok = np.zeros((sid.size, cap), dtype=np.int32)
@@ -497,7 +547,7 @@ class QwenAsrSession(_Session):
     Qwen_ASR/Inference_Qwen_ASR_ONNX.py:424-760 drives them)."""
 
     def __init__(self, cfg, arena, precision: int = PRECISION_BF16, device_id: int = 0, arena_device_ptr: int | None = None,
-                 arena_bytes: int | None = None):
+                 arena_bytes: int | None = None, audio_dtype=np.float32):
         super().__init__()
         self.cfg, self.precision, self.device_id = cfg, precision, device_id
         c = _lib.QwenConfigC()
@@ -516,12 +566,13 @@ class QwenAsrSession(_Session):
             _lib.check(_lib.load().asr_qwen_create(C.byref(c), blob.ctypes.data_as(C.c_void_p), blob.nbytes, MEM_HOST, device_id, precision,
                                                    C.byref(self._h)))
         self.batch = 0
+        self.audio_dtype = audio_dtype
 
     @classmethod
-    def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0):
+    def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0, audio_dtype=np.float32):
         from .arena import build_qwen_asr_arena
         arena_precision = PRECISION_BF16 if precision in (PRECISION_FP8W, PRECISION_MXFP4W) else precision
-        return cls(cfg, build_qwen_asr_arena(cfg, ck, arena_precision), precision, device_id)
+        return cls(cfg, build_qwen_asr_arena(cfg, ck, arena_precision), precision, device_id, audio_dtype=audio_dtype)
 
     @staticmethod
     def _ragged(seqs, B):
@@ -548,7 +599,7 @@ class QwenAsrSession(_Session):
         if audio_device_ptr is not None:
             ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
         else:
-            audio = _f32(audio).reshape(-1)
+            audio = self._audio(audio).reshape(-1)
             ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
         _lib.check(_lib.load().asr_qwen_prefill(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(pre), _ip(pre_off),
                                                 _ip(post), _ip(post_off), _ip(nxt), _fp(logits), _ip(ids_len)))
@@ -556,10 +607,8 @@ class QwenAsrSession(_Session):
         return nxt, logits, ids_len
 
     def prefill(self, audios: Sequence[np.ndarray], pre_ids, post_ids, want_logits: bool = True):
-        flat = [_f32(a).reshape(-1) for a in audios]
-        offs = np.zeros(len(flat) + 1, dtype=np.int64)
-        offs[1:] = np.cumsum([a.size for a in flat])
-        return self.prefill_packed(np.concatenate(flat), offs, pre_ids, post_ids, want_logits)
+        _, packed, offs = self._pack(audios)
+        return self.prefill_packed(packed, offs, pre_ids, post_ids, want_logits)
 
     def decode(self, ids=None, want_logits: bool = False, sync: bool = True):
         nxt = np.zeros(self.batch, dtype=np.int32) if sync else None
@@ -638,9 +687,9 @@ class QwenAlignerSession(QwenAsrSession):
     The session refuses prefill / decode / generate / beam_search (include/asr_mi355x.h asr_qwen_align)."""
 
     @classmethod
-    def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0):
+    def from_checkpoint(cls, cfg, ck, precision=PRECISION_BF16, device_id=0, audio_dtype=np.float32):
         from .arena import build_qwen_aligner_arena
-        return cls(cfg, build_qwen_aligner_arena(cfg, ck, cfg.classify_num, precision), precision, device_id)
+        return cls(cfg, build_qwen_aligner_arena(cfg, ck, cfg.classify_num, precision), precision, device_id, audio_dtype=audio_dtype)
 
     def align_packed(self, audio, offsets, pre_ids, post_ids, timestamp_id: int = -1, want_logits: bool = False,
                      audio_device_ptr: int | None = None):
@@ -662,7 +711,7 @@ class QwenAlignerSession(QwenAsrSession):
         if audio_device_ptr is not None:
             ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
         else:
-            audio = _f32(audio).reshape(-1)
+            audio = self._audio(audio).reshape(-1)
             ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
         _lib.check(_lib.load().asr_qwen_align(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(pre), _ip(pre_off),
                                               _ip(post), _ip(post_off), int(timestamp_id), _ip(slot_off), _ip(buckets), cap, _fp(logits),
@@ -673,10 +722,8 @@ class QwenAlignerSession(QwenAsrSession):
         return bk, lg, ids_len
 
     def align(self, audios: Sequence[np.ndarray], pre_ids, post_ids, timestamp_id: int = -1, want_logits: bool = False):
-        flat = [_f32(a).reshape(-1) for a in audios]
-        offs = np.zeros(len(flat) + 1, dtype=np.int64)
-        offs[1:] = np.cumsum([a.size for a in flat])
-        return self.align_packed(np.concatenate(flat), offs, pre_ids, post_ids, timestamp_id, want_logits)
+        _, packed, offs = self._pack(audios)
+        return self.align_packed(packed, offs, pre_ids, post_ids, timestamp_id, want_logits)
 
 
 def load_session(path: str, device_id: int = 0):
@@ -685,15 +732,18 @@ def load_session(path: str, device_id: int = 0):
     from .ort_shim import load_model
     info, blob = load_model(path)
     kind, conf, prec = info["kind"], dict(info["config"] or {}), int(info.get("precision", 0))
+    adt = audio_np_dtype(info.get("input_audio_dtype", "F32"))        # the bundle's export type; old bundles carry none: F32
     if kind == "sensevoice":
         conf["language_prompt_token_ids"] = tuple(conf["language_prompt_token_ids"])
-        return SenseVoiceSession(cfgm.SenseVoiceConfig(**conf), blob, prec, device_id)
+        return SenseVoiceSession(cfgm.SenseVoiceConfig(**conf), blob, prec, device_id, audio_dtype=adt)
     if kind == "paraformer":
-        return ParaformerSession(cfgm.ParaformerConfig(**conf), blob, prec, device_id)
+        return ParaformerSession(cfgm.ParaformerConfig(**conf), blob, prec, device_id, audio_dtype=adt)
     if kind == "whisper":
-        return WhisperSession(cfgm.WhisperConfig(**conf), blob, prec, device_id)
+        return WhisperSession(cfgm.WhisperConfig(**conf), blob, prec, device_id, audio_dtype=adt)
     if kind == "qwen_asr":
-        return QwenAsrSession(cfgm.QwenAsrConfig(**conf), blob, prec, device_id)
+        return QwenAsrSession(cfgm.QwenAsrConfig(**conf), blob, prec, device_id, audio_dtype=adt)
+    if kind == "paraformer_streaming":
+        return ParaformerStreamSession(cfgm.ParaformerConfig(**conf), blob, prec, device_id, chunk=int(info["metadata"].get("chunk", 8000)), audio_dtype=adt)
     if kind == "qwen_aligner":
-        return QwenAlignerSession(cfgm.QwenAlignerConfig(**conf), blob, prec, device_id)
+        return QwenAlignerSession(cfgm.QwenAlignerConfig(**conf), blob, prec, device_id, audio_dtype=adt)
     raise ValueError(f"{path!r}: no native session for bundle kind {kind!r}")

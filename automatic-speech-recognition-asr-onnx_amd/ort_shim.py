@@ -37,10 +37,33 @@ _ORT_TYPES = {np.dtype(np.float32): "tensor(float)", np.dtype(np.float16): "tens
 
 
 # ------------------------------------------------------------------------------------- model bundles
+INPUT_AUDIO_DTYPES = {"F32": np.dtype(np.float32), "INT16": np.dtype(np.int16), "F16": np.dtype(np.float16)}    # the reference's INPUT_AUDIO_DTYPE
+
+
+def input_audio_dtype_name(name) -> str:
+    """Validate an exporter's `input_audio_dtype` argument ("INT16" | "F32" | "F16", as in the reference's Export_*.py)."""
+    if name not in INPUT_AUDIO_DTYPES:
+        raise ValueError(f"input_audio_dtype {name!r}: expected one of 'F32', 'INT16', 'F16'")
+    return name
+
+
+def bundle_audio_dtype(info: dict) -> np.dtype:
+    """Sample type of a bundle's `audio` input; a bundle written before the field existed is F32."""
+    return INPUT_AUDIO_DTYPES[input_audio_dtype_name(info.get("input_audio_dtype", "F32"))]
+
+
+def check_audio_type(audio: "OrtValue", expected: np.dtype, meaning: str) -> None:
+    """onnxruntime refuses a binding whose element type is not the graph's; so does this."""
+    if np.dtype(audio._dtype) != expected:
+        raise ValueError(f"audio must be {_ORT_TYPES[expected]} {meaning}, got {_ORT_TYPES.get(np.dtype(audio._dtype), str(audio._dtype))}")
+
+
 def save_model(path: str, kind: str, config: dict | None, arena: np.ndarray | None, metadata: dict[str, str],
-               precision: int = 0) -> None:
-    header = json.dumps({"kind": kind, "config": config, "metadata": {str(k): str(v) for k, v in metadata.items()},
-                         "precision": int(precision)}, ensure_ascii=False).encode("utf-8")
+               precision: int = 0, input_audio_dtype: str | None = None) -> None:
+    head = {"kind": kind, "config": config, "metadata": {str(k): str(v) for k, v in metadata.items()}, "precision": int(precision)}
+    if input_audio_dtype is not None:             # bundles with an `audio` input: the type the graph was exported with
+        head["input_audio_dtype"] = input_audio_dtype_name(input_audio_dtype)
+    header = json.dumps(head, ensure_ascii=False).encode("utf-8")
     pad = (-(16 + len(header))) % 256
     with open(path, "wb") as f:
         f.write(MAGIC + struct.pack("<Q", len(header)) + header + b"\0" * pad)
@@ -260,14 +283,16 @@ class InferenceSession:
             cfg = dict(info["config"])
             cfg["language_prompt_token_ids"] = tuple(cfg["language_prompt_token_ids"])
             self._cfg = SenseVoiceConfig(**cfg)
-            self._native = SenseVoiceSession(self._cfg, blob, info["precision"], device_id)
-            self._inputs = [NodeArg("audio", [1, 1, "audio_len"], np.float32), NodeArg("language_idx", [1], np.int32)]
+            self._audio_dtype = bundle_audio_dtype(info)
+            self._native = SenseVoiceSession(self._cfg, blob, info["precision"], device_id, audio_dtype=self._audio_dtype)
+            self._inputs = [NodeArg("audio", [1, 1, "audio_len"], self._audio_dtype), NodeArg("language_idx", [1], np.int32)]
             self._outputs = [NodeArg("token_ids", ["num_token"], np.int32), NodeArg("num_id", [1], np.int32)]
         elif self._kind == "paraformer":
             from .engine import ParaformerSession
             self._cfg = ParaformerConfig(**info["config"])
-            self._native = ParaformerSession(self._cfg, blob, info["precision"], device_id)
-            self._inputs = [NodeArg("audio", [1, 1, "audio_len"], np.float32)]
+            self._audio_dtype = bundle_audio_dtype(info)
+            self._native = ParaformerSession(self._cfg, blob, info["precision"], device_id, audio_dtype=self._audio_dtype)
+            self._inputs = [NodeArg("audio", [1, 1, "audio_len"], self._audio_dtype)]
             self._outputs = [NodeArg("token_ids", [1, "num_token"], np.int32), NodeArg("num_id", [1], np.int32)]
         elif self._kind == "qwen_aligner":                      # the merged ForcedAligner graph: one stateless launch per clip
             from .ort_shim_qwen import QwenAlignerGraph
@@ -321,8 +346,7 @@ class InferenceSession:
         shape = tuple(audio._shape)
         if len(shape) != 3 or shape[1] != 1:
             raise ValueError(f"audio must have shape (batch, 1, audio_len), got {shape}")
-        if np.dtype(audio._dtype) != np.float32:
-            raise ValueError(f"audio must be tensor(float) carrying int16-range values, got {audio._dtype}")
+        check_audio_type(audio, self._audio_dtype, "carrying int16-range values")
         B, L = shape[0], shape[2]
         lang_np = np.asarray(lang.numpy(), dtype=np.int32).reshape(-1)
         if lang_np.size != B:
@@ -343,8 +367,7 @@ class InferenceSession:
         shape = tuple(audio._shape)
         if len(shape) != 3 or shape[1] != 1:
             raise ValueError(f"audio must have shape (batch, 1, audio_len), got {shape}")
-        if np.dtype(audio._dtype) != np.float32:
-            raise ValueError(f"audio must be tensor(float) carrying int16-range values, got {audio._dtype}")
+        check_audio_type(audio, self._audio_dtype, "carrying int16-range values")
         B, L = shape[0], shape[2]
         offsets = np.arange(B + 1, dtype=np.int64) * L
         if audio._host is not None:
@@ -385,7 +408,9 @@ class InferenceSession:
         binding._outputs = outs
 
     def run(self, output_names: Sequence[str] | None, input_feed: dict[str, np.ndarray], run_options=None):
-        feeds = {k: OrtValue(np.asarray(v, dtype=self._dtype_of(k)), "cpu", 0) for k, v in input_feed.items()}
+        # values are coerced to the declared types, except audio for a 2-byte export: that takes exactly its own type (no silent float -> int16 rounding)
+        feeds = {k: OrtValue(np.asarray(v) if k == "audio" and self._dtype_of(k) != np.float32 else np.asarray(v, dtype=self._dtype_of(k)), "cpu", 0)
+                 for k, v in input_feed.items()}
         results = self._execute(feeds)
         names = list(output_names) if output_names else self._output_names
         return [results[n].numpy() if isinstance(results[n], OrtValue) else results[n] for n in names]

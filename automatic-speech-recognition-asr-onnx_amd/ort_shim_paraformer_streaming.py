@@ -31,14 +31,14 @@ class _Shared:
         self.tokens_taken = True
 
 
-def graph_io(cfg: ParaformerConfig, role: str, chunk: int, rows_per_chunk: int, carried: int, kv_dtype=np.float16):
+def graph_io(cfg: ParaformerConfig, role: str, chunk: int, rows_per_chunk: int, carried: int, kv_dtype=np.float16, audio_dtype=np.float32):
     H, hd, d, feat = cfg.n_heads, cfg.d_head, cfg.d_model, cfg.n_mels * cfg.lfr_m
     Le, Ld, pad = cfg.n_enc0 + cfg.n_enc, cfg.n_dec, cfg.fsmn_kernel - 1
     bridge = [("encoder_out", [1, rows_per_chunk + carried, d], np.float32), ("list_frame", [1, "num_frame", d], np.float32), ("list_frame_len", [], np.int64)]
     if role == "encoder":
         ins = [(f"in_en_key_{i}", [H, hd, "history_len"], kv_dtype) for i in range(Le)] + [(f"in_en_value_{i}", [H, "history_len", hd], kv_dtype) for i in range(Le)]
         ins += [("in_previous_mel_features", [1, carried, feat], np.float32), ("in_cif_hidden", [1, 1, d], np.float32), ("in_cif_alphas", [1], np.float32),
-                ("start_idx", [1], np.int64), ("audio", [1, 1, chunk], np.float32)]
+                ("start_idx", [1], np.int64), ("audio", [1, 1, chunk], audio_dtype)]
         outs = [(f"out_en_key_{i}", [H, hd, "history_len_out"], kv_dtype) for i in range(Le)] + [(f"out_en_value_{i}", [H, "history_len_out", hd], kv_dtype) for i in range(Le)]
         outs += [("out_previous_mel_features", [1, carried, feat], np.float32), ("out_cif_hidden", [1, 1, d], np.float32), ("out_cif_alphas", [1], np.float32),
                  ("end_idx", [1], np.int64)] + bridge
@@ -54,6 +54,7 @@ def graph_io(cfg: ParaformerConfig, role: str, chunk: int, rows_per_chunk: int, 
 class ParaformerStreamGraph:
     def __init__(self, stub_path: str, info: dict, device_id: int, load_model):
         from .engine import ParaformerStreamSession
+        from .ort_shim import bundle_audio_dtype
         conf = info["config"]
         self.role = conf["role"]
         wpath = os.path.join(os.path.dirname(os.path.abspath(stub_path)), conf["weights"])
@@ -62,13 +63,15 @@ class ParaformerStreamGraph:
             winfo, blob = load_model(wpath)
             cfg = ParaformerConfig(**winfo["config"])
             chunk = int(winfo["metadata"].get("chunk", 8000))
-            native = ParaformerStreamSession(cfg, blob, int(winfo.get("precision", 0)), device_id, chunk=chunk, max_streams=1)
+            native = ParaformerStreamSession(cfg, blob, int(winfo.get("precision", 0)), device_id, chunk=chunk, max_streams=1,
+                                             audio_dtype=bundle_audio_dtype(winfo))
             _SHARED[key] = _Shared(cfg, native, chunk)
         self.sh: _Shared = _SHARED[key]
         self.cfg = self.sh.cfg
         self.rows = self.sh.native.rows_per_chunk
         self.carried = self.rows // 2
-        self.inputs, self.outputs = graph_io(self.cfg, self.role, self.sh.chunk, self.rows, self.carried)
+        self.audio_dtype = self.sh.native.audio_dtype              # the weights bundle's INPUT_AUDIO_DTYPE
+        self.inputs, self.outputs = graph_io(self.cfg, self.role, self.sh.chunk, self.rows, self.carried, audio_dtype=self.audio_dtype)
 
     @staticmethod
     def _stamp(feeds, names):
@@ -100,8 +103,10 @@ class ParaformerStreamGraph:
             elif stamp != ("enc", id(sh), sh.enc_gen):
                 raise ValueError("stale encoder state: feed back the outputs of the latest window")
             audio = feeds["audio"]
-            if tuple(audio._shape) != (1, 1, sh.chunk) or np.dtype(audio._dtype) != np.float32:
-                raise ValueError(f"audio must be tensor(float) of shape (1, 1, {sh.chunk}) carrying int16-range values, got {audio._dtype} {tuple(audio._shape)}")
+            if tuple(audio._shape) != (1, 1, sh.chunk):
+                raise ValueError(f"audio must have shape (1, 1, {sh.chunk}), got {tuple(audio._shape)}")
+            from .ort_shim import check_audio_type
+            check_audio_type(audio, self.audio_dtype, "carrying int16-range values")
             if audio._host is not None:
                 fired = sh.native.step(audio._host.reshape(1, sh.chunk), [0])[0]
             else:
@@ -140,7 +145,7 @@ class ParaformerStreamGraph:
 
 
 def export_paraformer_streaming_folder(folder: str, cfg: ParaformerConfig, ck: dict, metadata: dict, precision: int = 0, chunk: int = 8000,
-                                       max_continue: int = 502) -> str:
+                                       max_continue: int = 502, input_audio_dtype: str = "F32") -> str:
     """`Paraformer_Streaming.asrmodel` (streaming arena) + stubs for the two graphs + `ASR_Metadata.asrmodel`."""
     import dataclasses
     from .arena import build_paraformer_arena
@@ -149,7 +154,7 @@ def export_paraformer_streaming_folder(folder: str, cfg: ParaformerConfig, ck: d
     n_pos = max_continue - 1
     scfg = dataclasses.replace(cfg, max_audio_len=cfg.win_length + cfg.hop_length * (n_pos * cfg.lfr_n - 1))       # as ParaformerStreamSession sizes it
     save_model(os.path.join(folder, WEIGHTS_FILE + ".asrmodel"), "paraformer_streaming", cfg.to_dict(), build_paraformer_arena(scfg, ck, precision, streaming=True),
-               {"chunk": str(int(chunk))}, precision)
+               {"chunk": str(int(chunk))}, precision, input_audio_dtype)
     for stem, role in ((ENCODER_FILE, "encoder"), (DECODER_FILE, "decoder")):
         save_model(os.path.join(folder, stem + ".asrmodel"), "paraformer_stream_graph", {"role": role, "weights": WEIGHTS_FILE + ".asrmodel"}, None, {}, precision)
     save_model(os.path.join(folder, "ASR_Metadata.asrmodel"), "metadata", None, None, dict(metadata))

@@ -66,14 +66,14 @@ def embedding_as_ids(arr, what: str) -> list:
     return [int(v) for v in a[0, :, 0]]
 
 
-def graph_io(cfg: QwenAsrConfig, role: str, strategy: str, kv_dtype=np.float16):
+def graph_io(cfg: QwenAsrConfig, role: str, strategy: str, kv_dtype=np.float16, audio_dtype=np.float32):
     if role == "embed":
         return [("input_ids", [1, "ids_len"], np.int32)], [("hidden_states", [1, "ids_len", cfg.d_model], np.float32)]
     L, KV, hd = cfg.n_layers, cfg.n_kv_heads, cfg.d_head
     ins = [(f"past_key_{i}", ["batch", KV, 1, hd, "history_len"], kv_dtype) for i in range(L)]
     ins += [(f"past_value_{i}", ["batch", KV, 1, "history_len", hd], kv_dtype) for i in range(L)]
     if role == "prefill":
-        ins += [("audio", [1, 1, "audio_len"], np.float32), ("query_embed", [1, "query_len", cfg.d_model], np.float32),
+        ins += [("audio", [1, 1, "audio_len"], audio_dtype), ("query_embed", [1, "query_len", cfg.d_model], np.float32),
                 ("language_tail_embed", [1, "language_tail_len", cfg.d_model], np.float32), ("prefill_history_len", [1], np.int64)]
     else:
         ins += [("hidden_states", [1, 1, cfg.d_model], np.float32), ("decode_kv_seq_len", [1], np.int64)]
@@ -97,6 +97,7 @@ def graph_io(cfg: QwenAsrConfig, role: str, strategy: str, kv_dtype=np.float16):
 class QwenGraph:
     def __init__(self, stub_path: str, info: dict, device_id: int, load_model):
         from .engine import QwenAsrSession
+        from .ort_shim import bundle_audio_dtype
         conf = info["config"]
         self.role, self.strategy = conf["role"], conf.get("strategy", "greedy")
         wpath = os.path.join(os.path.dirname(os.path.abspath(stub_path)), conf["weights"])
@@ -104,11 +105,13 @@ class QwenGraph:
         if key not in _SHARED:
             winfo, blob = load_model(wpath)
             cfg = QwenAsrConfig(**winfo["config"])
-            _SHARED[key] = _Shared(cfg, QwenAsrSession(cfg, blob, int(winfo.get("precision", 0)), device_id), winfo["metadata"])
+            _SHARED[key] = _Shared(cfg, QwenAsrSession(cfg, blob, int(winfo.get("precision", 0)), device_id, audio_dtype=bundle_audio_dtype(winfo)),
+                                   winfo["metadata"])
         self.sh: _Shared = _SHARED[key]
         self.cfg = self.sh.cfg
         self.kv_dtype = np.float16
-        self.inputs, self.outputs = graph_io(self.cfg, self.role, self.strategy, self.kv_dtype)
+        self.audio_dtype = self.sh.native.audio_dtype              # the weights bundle's INPUT_AUDIO_DTYPE
+        self.inputs, self.outputs = graph_io(self.cfg, self.role, self.strategy, self.kv_dtype, self.audio_dtype)
 
     def _configure_head(self, feeds, is_decode):
         sh, n = self.sh, self.sh.native
@@ -175,8 +178,10 @@ class QwenGraph:
                 raise ValueError("prefill_history_len must be 0 (the reference's one prefill per clip, :586-588)")
             audio = feeds["audio"]
             shape = tuple(audio._shape)
-            if len(shape) != 3 or shape[0] != 1 or shape[1] != 1 or np.dtype(audio._dtype) != np.float32:
-                raise ValueError(f"audio must be tensor(float) of shape (1, 1, audio_len) in [-1, 1], got {audio._dtype} {shape}")
+            if len(shape) != 3 or shape[0] != 1 or shape[1] != 1:
+                raise ValueError(f"audio must have shape (1, 1, audio_len), got {shape}")
+            from .ort_shim import check_audio_type
+            check_audio_type(audio, self.audio_dtype, "(raw PCM)" if self.audio_dtype == np.int16 else "in [-1, 1]")
             query = embedding_as_ids(feeds["query_embed"].numpy(), "query_embed")
             tail = embedding_as_ids(feeds["language_tail_embed"].numpy(), "language_tail_embed")
             self._configure_head(feeds, False)
@@ -204,13 +209,13 @@ class QwenGraph:
         return results
 
 
-def export_qwen_asr_folder(folder: str, cfg: QwenAsrConfig, ck: dict, metadata: dict, precision: int = 0) -> str:
+def export_qwen_asr_folder(folder: str, cfg: QwenAsrConfig, ck: dict, metadata: dict, precision: int = 0, input_audio_dtype: str = "F32") -> str:
     """Model folder with the reference's file names (Qwen_ASR/Shared_Merged.DEFAULT_MODEL_FILE_NAMES): `Qwen3_ASR.asrmodel` (arena + the
     exporter's metadata map), one stub per merged graph, the Embed stub and `ASR_Metadata.asrmodel`."""
     from .ort_shim import save_model
     from .qwen_asr import export_qwen_asr
     os.makedirs(folder, exist_ok=True)
-    export_qwen_asr(cfg, ck, os.path.join(folder, WEIGHTS_FILE + ".asrmodel"), metadata, precision)
+    export_qwen_asr(cfg, ck, os.path.join(folder, WEIGHTS_FILE + ".asrmodel"), metadata, precision, input_audio_dtype)
     for key, stem in GRAPH_FILES.items():
         role, strategy = key.split("_", 1)
         save_model(os.path.join(folder, stem + ".asrmodel"), "qwen_graph", {"role": role, "strategy": strategy, "weights": WEIGHTS_FILE + ".asrmodel"}, None, {}, precision)
@@ -232,12 +237,14 @@ class QwenAlignerGraph:
     def __init__(self, info: dict, blob, device_id: int):
         from .config import QwenAlignerConfig
         from .engine import QwenAlignerSession
+        from .ort_shim import bundle_audio_dtype
         self.cfg = QwenAlignerConfig(**info["config"])
         meta = info.get("metadata", {})
         special = meta["special_token_ids"]
         self.special = json.loads(special) if isinstance(special, str) else dict(special)
-        self.native = QwenAlignerSession(self.cfg, blob, int(info.get("precision", 0)), device_id)
-        self.inputs = [("audio", [1, 1, "audio_len"], np.float32), ("input_ids", [1, "text_len"], np.int32)]
+        self.audio_dtype = bundle_audio_dtype(info)
+        self.native = QwenAlignerSession(self.cfg, blob, int(info.get("precision", 0)), device_id, audio_dtype=self.audio_dtype)
+        self.inputs = [("audio", [1, 1, "audio_len"], self.audio_dtype), ("input_ids", [1, "text_len"], np.int32)]
         self.outputs = [("output_ids", [1, "ids_len"], np.int32)]
 
     def execute(self, feeds: dict) -> dict:
@@ -246,8 +253,10 @@ class QwenAlignerGraph:
                 raise ValueError(f"input {name!r} is not bound")
         audio = feeds["audio"]
         shape = tuple(audio._shape)
-        if len(shape) != 3 or shape[0] != 1 or shape[1] != 1 or np.dtype(audio._dtype) != np.float32:
-            raise ValueError(f"audio must be tensor(float) of shape (1, 1, audio_len) in [-1, 1], got {audio._dtype} {shape}")
+        if len(shape) != 3 or shape[0] != 1 or shape[1] != 1:
+            raise ValueError(f"audio must have shape (1, 1, audio_len), got {shape}")
+        from .ort_shim import check_audio_type
+        check_audio_type(audio, self.audio_dtype, "(raw PCM)" if self.audio_dtype == np.int16 else "in [-1, 1]")
         ids = np.asarray(feeds["input_ids"].numpy(), dtype=np.int64)
         if ids.ndim != 2 or ids.shape[0] != 1:
             raise ValueError(f"input_ids must have shape (1, text_len), got {ids.shape}")
@@ -263,11 +272,11 @@ class QwenAlignerGraph:
         return {"output_ids": bk[0].reshape(1, -1).astype(np.int32)}
 
 
-def export_qwen_aligner_folder(folder: str, cfg, ck: dict, metadata: dict, precision: int = 0) -> str:
+def export_qwen_aligner_folder(folder: str, cfg, ck: dict, metadata: dict, precision: int = 0, input_audio_dtype: str = "F32") -> str:
     """Model folder with the reference's runtime file names: `ForcedAligner_Merged.asrmodel` (arena + metadata map) and `ASR_Metadata.asrmodel`."""
     from .ort_shim import save_model
     from .qwen_aligner import export_qwen_aligner
     os.makedirs(folder, exist_ok=True)
-    export_qwen_aligner(cfg, ck, os.path.join(folder, ALIGNER_MERGED_FILE + ".asrmodel"), metadata, precision)
+    export_qwen_aligner(cfg, ck, os.path.join(folder, ALIGNER_MERGED_FILE + ".asrmodel"), metadata, precision, input_audio_dtype)
     save_model(os.path.join(folder, METADATA_FILE + ".asrmodel"), "metadata", None, None, dict(metadata))
     return folder

@@ -53,7 +53,7 @@ class _Shared:
         self.head = None            # (strategy, penalty value, penalty range, sampling scalars) configured on the native session
 
 
-def graph_io(cfg: WhisperConfig, role: str, strategy: str, kv_dtype=np.float16):
+def graph_io(cfg: WhisperConfig, role: str, strategy: str, kv_dtype=np.float16, audio_dtype=np.float32):
     """-> (inputs, outputs) as (name, shape, dtype) lists, in the order the merged graphs declare them: self-KV state first."""
     L, H = cfg.n_dec_layers, cfg.n_heads
     if role == "no_speech":
@@ -62,7 +62,7 @@ def graph_io(cfg: WhisperConfig, role: str, strategy: str, kv_dtype=np.float16):
     ins = [(f"in_de_key_layer_{i}", ["batch", H, cfg.d_head, hist], kv_dtype) for i in range(L)]
     ins += [(f"in_de_value_layer_{i}", ["batch", H, hist, cfg.d_head], kv_dtype) for i in range(L)]
     if role == "probe_prefill":
-        ins.append(("audio", [1, 1, "audio_len"], np.float32))
+        ins.append(("audio", [1, 1, "audio_len"], audio_dtype))
     else:
         ins += [(f"en_key_layer_{i}", [H, cfg.d_head, "signal_len"], kv_dtype) for i in range(L)]
         ins += [(f"en_value_layer_{i}", [H, "signal_len", cfg.d_head], kv_dtype) for i in range(L)]
@@ -99,6 +99,7 @@ class WhisperGraph:
 
     def __init__(self, stub_path: str, info: dict, device_id: int, load_model):
         from .engine import WhisperSession
+        from .ort_shim import bundle_audio_dtype
         conf = info["config"]
         self.role, self.strategy = conf["role"], conf.get("strategy", "greedy")
         wpath = os.path.join(os.path.dirname(os.path.abspath(stub_path)), conf["weights"])
@@ -106,12 +107,14 @@ class WhisperGraph:
         if key not in _SHARED:
             winfo, blob = load_model(wpath)
             cfg = WhisperConfig(**winfo["config"])
-            native = WhisperSession(cfg, blob, int(winfo.get("precision", 0)), device_id, gelu_tanh=bool(winfo["metadata"].get("gelu_tanh", "1") == "1"))
+            native = WhisperSession(cfg, blob, int(winfo.get("precision", 0)), device_id, gelu_tanh=bool(winfo["metadata"].get("gelu_tanh", "1") == "1"),
+                                    audio_dtype=bundle_audio_dtype(winfo))
             _SHARED[key] = _Shared(cfg, native, winfo["metadata"])
         self.sh: _Shared = _SHARED[key]
         self.cfg = self.sh.cfg
         self.kv_dtype = np.float16
-        self.inputs, self.outputs = graph_io(self.cfg, self.role, self.strategy, self.kv_dtype)
+        self.audio_dtype = self.sh.native.audio_dtype              # the weights bundle's INPUT_AUDIO_DTYPE
+        self.inputs, self.outputs = graph_io(self.cfg, self.role, self.strategy, self.kv_dtype, self.audio_dtype)
 
     # ------------------------------------------------------------------ helpers
     def _placeholder(self, OrtValue, shape, kind, gen):
@@ -210,8 +213,10 @@ class WhisperGraph:
         if self.role == "probe_prefill":
             audio = feeds["audio"]
             shape = tuple(audio._shape)
-            if len(shape) != 3 or shape[1] != 1 or np.dtype(audio._dtype) != np.float32:
-                raise ValueError(f"audio must be tensor(float) of shape (batch, 1, audio_len) in [-1, 1], got {audio._dtype} {shape}")
+            if len(shape) != 3 or shape[1] != 1:
+                raise ValueError(f"audio must have shape (batch, 1, audio_len), got {shape}")
+            from .ort_shim import check_audio_type
+            check_audio_type(audio, self.audio_dtype, "(raw PCM)" if self.audio_dtype == np.int16 else "in [-1, 1]")
             offsets = np.arange(shape[0] + 1, dtype=np.int64) * shape[2]
             if audio._host is not None:
                 sh.native.encode_packed(audio._host.reshape(-1), offsets)
@@ -241,15 +246,16 @@ class WhisperGraph:
 
 
 def export_whisper(folder: str, cfg: WhisperConfig, ck: dict, precision: int = 0, suppress_tokens=None, begin_suppress_tokens=(),
-                   supported_languages: dict | None = None, gelu_tanh: bool = True) -> str:
+                   supported_languages: dict | None = None, gelu_tanh: bool = True, input_audio_dtype: str = "F32") -> str:
     """Model folder with the reference's file names (Shared_Merged.DEFAULT_MODEL_FILE_NAMES): `Whisper.asrmodel` (arena), one stub per
     merged graph and for the no-speech graph, and `ASR_Metadata.asrmodel` with the exporter's metadata map (Export_Whisper.py:1064-1074)."""
     from .arena import build_whisper_arena
-    from .ort_shim import save_model
+    from .ort_shim import input_audio_dtype_name, save_model
+    input_audio_dtype_name(input_audio_dtype)
     os.makedirs(folder, exist_ok=True)
     meta_w = {"suppress_tokens": json.dumps([int(t) for t in (suppress_tokens or [])]), "gelu_tanh": "1" if gelu_tanh else "0"}
     save_model(os.path.join(folder, WEIGHTS_FILE + ".asrmodel"), "whisper", cfg.to_dict(),
-               build_whisper_arena(cfg, ck, precision, suppress_tokens, begin_suppress_tokens), meta_w, precision)
+               build_whisper_arena(cfg, ck, precision, suppress_tokens, begin_suppress_tokens), meta_w, precision, input_audio_dtype)
     for key, stem in GRAPH_FILES.items():
         role, strategy = key.rsplit("_", 1) if not key.endswith("penalty_greedy") else (key[:-len("_penalty_greedy")], "penalty_greedy")
         save_model(os.path.join(folder, stem + ".asrmodel"), "whisper_graph", {"role": role, "strategy": strategy, "weights": WEIGHTS_FILE + ".asrmodel"},

@@ -45,14 +45,16 @@ def build_tokenizer_metadata(token_list: Sequence[str], language: str, decode_mo
 
 
 def export_paraformer(folder: str, cfg: ParaformerConfig, ck: dict, token_list: Sequence[str], language: str = "zh",
-                      decode_mode: str = "zh", precision: int = 0) -> None:
+                      decode_mode: str = "zh", precision: int = 0, input_audio_dtype: str = "F32") -> None:
+    """`input_audio_dtype`: the reference's INPUT_AUDIO_DTYPE (Export_Paraformer.py:88): the type the `audio` input is declared and fed with."""
+    onnxruntime.input_audio_dtype_name(input_audio_dtype)
     os.makedirs(folder, exist_ok=True)
     special, langs = build_tokenizer_metadata(token_list, language, decode_mode)
     meta = {"sample_rate": str(cfg.sample_rate), "audio_pcm_scale": "1",
             "special_token_ids": json.dumps(special, separators=(",", ":")),
             "supported_languages": json.dumps(langs, ensure_ascii=False, sort_keys=True, separators=(",", ":"))}
     onnxruntime.save_model(os.path.join(folder, "Paraformer.asrmodel"), "paraformer", cfg.to_dict(),
-                           build_paraformer_arena(cfg, ck, precision), {}, precision)
+                           build_paraformer_arena(cfg, ck, precision), {}, precision, input_audio_dtype)
     onnxruntime.save_model(os.path.join(folder, "ASR_Metadata.asrmodel"), "metadata", None, None, meta)
     with open(os.path.join(folder, "Vocab_Paraformer.txt"), "w", encoding="utf-8") as f:
         for t in token_list:

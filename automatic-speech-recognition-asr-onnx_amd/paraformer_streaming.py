@@ -15,6 +15,7 @@ from typing import Sequence
 import numpy as np
 
 from .paraformer import decode_tokens
+from .engine import audio_dtype_name
 from .sensevoice import prepare_audio_input
 
 
@@ -43,10 +44,15 @@ class ParaformerStreamTranscriber:
         self.stop, self.decode_mode = list(stop_token_ids), decode_mode
         self.audio_pcm_scale, self.sample_rate = audio_pcm_scale, sample_rate
 
+    @property
+    def input_audio_dtype(self) -> str:
+        """"INT16" | "F32" | "F16": the type of the session's `audio` input (the reference reads it off the graph, Inference_Paraformer_Streaming_ONNX.py prepare_audio_input)."""
+        return audio_dtype_name(self.sess.audio_dtype)
+
     def transcribe_many(self, clips_int16: Sequence[np.ndarray], rng: np.random.Generator | None = None):
         """Concurrent streams, one per clip (<= session.max_streams). Returns per clip dict(text, pieces, token_ids), and stats."""
         chunk = self.sess.chunk
-        prepared = [pad_to_chunks(prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(1, 1, -1), "F32", audio_pcm_scale=self.audio_pcm_scale),
+        prepared = [pad_to_chunks(prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype, audio_pcm_scale=self.audio_pcm_scale),
                                   chunk, rng)[0, 0] for c in clips_int16]
         n_chunks = [a.size // chunk for a in prepared]
         ids = list(range(len(prepared)))

@@ -19,6 +19,9 @@ from typing import List, Sequence
 
 import numpy as np
 
+from .engine import audio_dtype_name
+from .whisper import prepare_audio_input
+
 # (first, last) code points of the CJK ideograph blocks the reference splits per character (:180-190)
 _CJK_RANGES = ((0x4E00, 0x9FFF), (0x3400, 0x4DBF), (0x20000, 0x2A6DF), (0x2A700, 0x2B73F), (0x2B740, 0x2B81F), (0x2B820, 0x2CEAF),
                (0xF900, 0xFAFF))
@@ -137,11 +140,11 @@ def aligner_metadata(cfg, special_token_ids: dict) -> dict:
             "classify_num": str(cfg.classify_num)}
 
 
-def export_qwen_aligner(cfg, ck: dict, path: str, metadata: dict, precision: int = 0) -> str:
+def export_qwen_aligner(cfg, ck: dict, path: str, metadata: dict, precision: int = 0, input_audio_dtype: str = "F32") -> str:
     """Checkpoint (HF state-dict names) -> `.asrmodel` bundle: folded aligner arena + config + metadata map."""
     from .arena import build_qwen_aligner_arena
     from .ort_shim import save_model
-    save_model(path, "qwen_aligner", cfg.to_dict(), build_qwen_aligner_arena(cfg, ck, cfg.classify_num, precision), dict(metadata), precision)
+    save_model(path, "qwen_aligner", cfg.to_dict(), build_qwen_aligner_arena(cfg, ck, cfg.classify_num, precision), dict(metadata), precision, input_audio_dtype)
     return path
 
 
@@ -166,11 +169,20 @@ class QwenForcedAligner:
         words = [str(w) for w, _ in transcript]
         return words, [[int(t) for t in ids] for _, ids in transcript]
 
+    @property
+    def input_audio_dtype(self) -> str:
+        """"INT16" | "F32" | "F16": the type of the session's `audio` input (the reference reads it off the graph, Inference_Qwen_ForcedAligner_ONNX.py prepare_audio_input)."""
+        return audio_dtype_name(self.sess.audio_dtype)
+
     def _audio(self, a):
-        a = np.asarray(a)
+        """A clip in the session's audio type: int16 PCM goes through the reference's prepare_audio_input (untouched for an INT16 session, / pcm_scale for
+        a float one); float samples in [-1, 1] serve a float session only -- nothing is rounded to int16 behind the caller's back."""
+        a, dt = np.asarray(a), self.sess.audio_dtype
         if a.dtype == np.int16:
-            return a.reshape(-1).astype(np.float32) * np.float32(1.0 / self.pcm_scale)
-        return np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+            return prepare_audio_input(a.reshape(-1), dt, audio_pcm_scale=self.pcm_scale)
+        if dt == np.int16:
+            raise TypeError(f"the aligner session takes int16 PCM (INPUT_AUDIO_DTYPE INT16), the clip given is {a.dtype.name}")
+        return np.ascontiguousarray(a, dtype=dt).reshape(-1)
 
     def align(self, audios: Sequence[np.ndarray], transcripts: Sequence, language="English") -> List[List[dict]]:
         """audios: 16 kHz mono clips (int16 PCM or float in [-1, 1]); transcripts: one per clip; language: one name for all clips or one per

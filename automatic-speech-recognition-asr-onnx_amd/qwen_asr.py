@@ -25,7 +25,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from .config import QwenAsrConfig
-from .engine import QwenAsrSession
+from .engine import QwenAsrSession, audio_dtype_name
 from .whisper import prepare_audio_input
 
 ASR_TEXT_TAG = "<asr_text>"
@@ -112,11 +112,11 @@ def parse_asr_output(raw: str, user_language: Optional[str] = None) -> Tuple[str
     return language, body.strip()
 
 
-def export_qwen_asr(cfg: QwenAsrConfig, ck: dict, path: str, metadata: dict, precision: int = 0) -> str:
+def export_qwen_asr(cfg: QwenAsrConfig, ck: dict, path: str, metadata: dict, precision: int = 0, input_audio_dtype: str = "F32") -> str:
     """Checkpoint (HF state-dict names) -> `.asrmodel` bundle: folded arena + config + the exporter's metadata map."""
     from .arena import build_qwen_asr_arena
     from .ort_shim import save_model
-    save_model(path, "qwen_asr", cfg.to_dict(), build_qwen_asr_arena(cfg, ck, precision), dict(metadata), precision)
+    save_model(path, "qwen_asr", cfg.to_dict(), build_qwen_asr_arena(cfg, ck, precision), dict(metadata), precision, input_audio_dtype)
     return path
 
 
@@ -144,6 +144,11 @@ class QwenAsrTranscriber:
         self.head_ids, self.suffix_ids, self.tail_ids = prompt_ids(self.special)
         self.normalise_audio = normalise_audio
 
+    @property
+    def input_audio_dtype(self) -> str:
+        """"INT16" | "F32" | "F16": the type of the session's `audio` input (the reference reads it off the graph, Inference_Qwen_ASR_ONNX.py prepare_audio_input)."""
+        return audio_dtype_name(self.sess.audio_dtype)
+
     def _query_ids(self, system_prompt) -> list:
         if not system_prompt:
             return []
@@ -162,7 +167,7 @@ class QwenAsrTranscriber:
         langs = list(language_prompts) * B if len(language_prompts) == 1 else list(language_prompts)
         if len(tasks) != B or len(langs) != B:
             raise ValueError("task_prompts / language_prompts must have one entry or one per clip")
-        audios = [prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(-1), np.float32, audio_pcm_scale=self.audio_pcm_scale,
+        audios = [prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(-1), self.sess.audio_dtype, audio_pcm_scale=self.audio_pcm_scale,
                                       normalise=self.normalise_audio)[:self.cfg.max_audio_len] for c in clips_int16]
         pre = [self.head_ids + self._query_ids(t) + self.suffix_ids for t in tasks]
         post = [self.tail_ids + (list(resolve_language(self.languages, l)[1]["prompt_token_ids"]) if l else []) for l in langs]

@@ -22,11 +22,13 @@ from .ort_io import array_for, filled_for, is_dynamic_dim, load_supported_langua
 C = onnxruntime  # `C.OrtDevice` in the reference scripts
 
 
-def export_sensevoice(folder: str, cfg: SenseVoiceConfig, ck: dict, precision: int = 0) -> None:
+def export_sensevoice(folder: str, cfg: SenseVoiceConfig, ck: dict, precision: int = 0, input_audio_dtype: str = "F32") -> None:
+    """`input_audio_dtype`: the reference's INPUT_AUDIO_DTYPE (Export_SenseVoice.py:21): the type the `audio` input is declared and fed with."""
+    onnxruntime.input_audio_dtype_name(input_audio_dtype)
     os.makedirs(folder, exist_ok=True)
     meta = onnxruntime.sensevoice_metadata(cfg)
     onnxruntime.save_model(os.path.join(folder, "SenseVoiceSmall.asrmodel"), "sensevoice", cfg.to_dict(),
-                           build_sensevoice_arena(cfg, ck, precision), {}, precision)
+                           build_sensevoice_arena(cfg, ck, precision), {}, precision, input_audio_dtype)
     onnxruntime.save_model(os.path.join(folder, "ASR_Metadata.asrmodel"), "metadata", None, None, meta)
 
 

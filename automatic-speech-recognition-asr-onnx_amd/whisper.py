@@ -26,7 +26,7 @@ from typing import Sequence
 import numpy as np
 
 from .config import WhisperConfig
-from .engine import WhisperSession
+from .engine import WhisperSession, audio_dtype_name
 
 
 def prepare_audio_input(audio_int16: np.ndarray, target_dtype=np.float32, *, audio_pcm_scale: int = 32768,
@@ -103,6 +103,11 @@ class WhisperTranscriber:
         # USE_SAMPLING / TEMPERATURE / TOP_K / TOP_P / SAMPLING_REPETITION_PENALTY (:71-75)
         self.sampling = (bool(use_sampling), float(temperature), int(top_k), float(top_p), float(sampling_repetition_penalty), int(seed))
 
+    @property
+    def input_audio_dtype(self) -> str:
+        """"INT16" | "F32" | "F16": the type of the session's `audio` input (the reference reads it off the graph, Inference_Whisper_ONNX.py:103-126)."""
+        return audio_dtype_name(self.sess.audio_dtype)
+
     def _continue(self, limit: int):
         """Ids after the full-prompt prefill: greedy / penalty-greedy / sampling, or the first hypothesis of the beam search."""
         if self.beam_size > 1:
@@ -112,7 +117,7 @@ class WhisperTranscriber:
     def transcribe(self, clips_int16: Sequence[np.ndarray], language_ids: Sequence[int] | None = None, max_new: int | None = None):
         """List of int16 mono 16 kHz clips (each <= 30 s) -> per clip dict(tokens, language_id, no_speech_prob, skipped)."""
         cfg = self.cfg
-        audios = [prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(-1)) for c in clips_int16]
+        audios = [prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(-1), self.sess.audio_dtype) for c in clips_int16]
         B = len(audios)
         lang = np.asarray(language_ids if language_ids is not None else [cfg.first_language_id] * B, dtype=np.int64)
         t0 = time.time()
@@ -161,7 +166,7 @@ class WhisperTranscriber:
             # the reference's default export keeps the audio axis dynamic (Export_Whisper.py:743): the window is the file, unpadded. A file longer than
             # the encoder's position table can only run through the static-axis export: windows of max_audio_len, the tail zero-padded.
             input_audio_length = None if audio_len <= cfg.max_audio_len else cfg.max_audio_len
-        audio = prepare_audio_input(raw)
+        audio = prepare_audio_input(raw, self.sess.audio_dtype)
         n_win, stride, window, aligned = plan_windows(audio_len, input_audio_length, sliding_window)
         if audio.size < aligned:                                         # zero-padded tail (:751-757)
             audio = np.concatenate([audio, np.zeros(aligned - audio.size, dtype=audio.dtype)])

@@ -70,6 +70,17 @@ enum asr_precision { ASR_PRECISION_BF16 = 0, ASR_PRECISION_F32 = 1, ASR_PRECISIO
 
 enum asr_mem { ASR_MEM_HOST = 0, ASR_MEM_DEVICE = 1 };
 
+/* Sample type of the `audio` argument of every entry that takes audio (asr_sensevoice_run, asr_paraformer_run, asr_paraformer_stream_step,
+ * asr_whisper_encode, asr_qwen_prefill, asr_qwen_align). The reference fixes it per exported graph (INPUT_AUDIO_DTYPE = "INT16" | "F32" | "F16"), so here
+ * it is a property of the session (asr_session_set_audio_dtype, default F32). What a value means follows the family's export:
+ *   SenseVoice / Paraformer / streaming Paraformer (SenseVoice/Export_SenseVoice.py:21,275,368; Paraformer/Non-Streaming/Export_Paraformer.py:88,359,594;
+ *     Paraformer/Streaming/Export_Paraformer_Streaming.py:21,316,596): I16 = raw PCM used as is (audio.float()); F32 / F16 = int16-RANGE values;
+ *   Whisper / Qwen3-ASR / ForcedAligner (Whisper/Export_Whisper.py:43,367,423,735,741; Qwen_ASR/Export_Qwen_ASR.py:80,710-731,854,1596): I16 = raw PCM, the
+ *     1/32768 that the export folds into the STFT window (STFT_Process.py:143) is applied at the load; F32 / F16 = values already in [-1, 1].
+ * Widening int16 / f16 to f32 is exact and 2^-15 commutes with every f32 rounding, so an I16 call equals the F32 call on the widened (and, for the second
+ * group, scaled) samples bit for bit. audio_offsets always count samples; a 2-byte utterance needs 2-byte alignment only. */
+enum asr_audio_dtype { ASR_AUDIO_F32 = 0, ASR_AUDIO_I16 = 1, ASR_AUDIO_F16 = 2 };
+
 typedef struct asr_session asr_session;
 
 int asr_abi_version(void);
@@ -115,10 +126,11 @@ typedef struct asr_sensevoice_config {
 int asr_sensevoice_create(const asr_sensevoice_config* cfg, const void* arena, size_t arena_bytes, int arena_mem,
                           int device_id, int precision, asr_session** out);
 
-/* audio: packed f32 samples; utterance b spans [audio_offsets[b], audio_offsets[b+1]).
+/* audio: packed samples of the session's asr_audio_dtype -- F32 / F16: int16-range values; I16: raw PCM used as is (Export_SenseVoice.py:275,368);
+ * utterance b spans samples [audio_offsets[b], audio_offsets[b+1]).
  * language_idx: B selector indices (host). token_ids_out: host [B][max_tokens] (row b holds num_id_out[b]
  * ids, rest untouched); num_id_out: host [B]. Fails if any utterance is shorter than one frame. */
-int asr_sensevoice_run(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+int asr_sensevoice_run(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                        const int32_t* language_idx, int32_t* token_ids_out, int max_tokens, int32_t* num_id_out);
 
 /* sequence length (prompt + LFR rows) the graph produces for an utterance of n_samples */
@@ -141,9 +153,9 @@ typedef struct asr_paraformer_config {
 
 int asr_paraformer_create(const asr_paraformer_config* cfg, const void* arena, size_t arena_bytes, int arena_mem, int device_id,
                           int precision, asr_session** out);
-/* same calling convention as asr_sensevoice_run (no language input): token_ids_out host [B][max_tokens], num_id_out host [B]
+/* same calling convention as asr_sensevoice_run, the audio types included (Export_Paraformer.py:88,359,594), no language input: token_ids_out host [B][max_tokens], num_id_out host [B]
  * (num_id is the CIF fire count; an utterance can legitimately yield zero tokens). */
-int asr_paraformer_run(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+int asr_paraformer_run(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                        int32_t* token_ids_out, int max_tokens, int32_t* num_id_out);
 
 /* Streaming Paraformer: replaces Paraformer_Streaming_Encoder.onnx + Paraformer_Streaming_Decoder.onnx (PARAFORMER_ENCODER /
@@ -151,7 +163,7 @@ int asr_paraformer_run(asr_session* s, const float* audio, int audio_mem, const 
  * Inference_Paraformer_Streaming_ONNX.py:309-449. The 100 in_en_key/value tensors, in_previous_mel_features, in_cif_hidden,
  * in_cif_alphas, start_idx, in_de_fsmn / in_de_key / in_de_value of a stream live in HBM inside the session, indexed by a
  * stream id in [0, max_streams); one step advances n_streams DIFFERENT streams by one chunk_samples-sample chunk each
- * (audio: [n_streams][chunk_samples], int16-range float) and runs the decoder for the streams whose CIF fired -- streams
+ * (audio: [n_streams][chunk_samples] of the session's asr_audio_dtype, int16-range values or raw PCM: Export_Paraformer_Streaming.py:21,316,596) and runs the decoder for the streams whose CIF fired -- streams
  * without a fired frame keep their decoder state, exactly like the host loop (:420-447). token_ids_out: host
  * [n_streams][max_tokens] (max_tokens >= LFR rows per chunk + 1), num_id_out: host [n_streams]. The arena is the
  * non-streaming Paraformer arena built for streaming (position table up to MAX_CONTINUE_STREAMING, causal decoder FSMN). */
@@ -159,7 +171,7 @@ int asr_paraformer_stream_create(const asr_paraformer_config* cfg, const void* a
                                  int precision, int chunk_samples, int look_back_encoder, int look_back_decoder, int max_streams,
                                  asr_session** out);
 int asr_paraformer_stream_reset(asr_session* s, int stream_id);      /* -1 = every stream: empty histories, zero CIF state */
-int asr_paraformer_stream_step(asr_session* s, const float* audio, int audio_mem, const int32_t* stream_ids, int n_streams,
+int asr_paraformer_stream_step(asr_session* s, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams,
                                int32_t* token_ids_out, int max_tokens, int32_t* num_id_out);
 /* Which path the chunk steps of a streaming session took (no reference counterpart: the reference runs one stream per InferenceSession and has no
  * co-tenancy to manage). A bf16 step runs the encoder / decoder layer loops as two cluster launches when (i) no more than fused_max streams are active,
@@ -189,9 +201,10 @@ typedef struct asr_whisper_config {
 
 int asr_whisper_create(const asr_whisper_config* cfg, const void* arena, size_t arena_bytes, int arena_mem, int device_id,
                        int precision, asr_session** out);
-/* audio: packed f32 samples in [-1, 1] (audio_pcm_scale 32768, Export_Whisper.py:1068); n_positions_out (host, B,
+/* audio: packed samples of the session's asr_audio_dtype -- F32 / F16 in [-1, 1] (audio_pcm_scale 32768, Export_Whisper.py:1068), I16 raw PCM scaled by
+ * 2^-15 at the load (Export_Whisper.py:43,367,423; STFT_Process.py:143); n_positions_out (host, B,
  * nullable) receives the encoder length (n_samples / 160 + 1) / 2 of each utterance. */
-int asr_whisper_encode(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+int asr_whisper_encode(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                        int32_t* n_positions_out);
 /* ids: host [B][n] prompt tokens (n <= 8), history is reset to 0 like the reference's prefill. next_ids_out (host B,
  * nullable): arg-max(logits + begin_suppress); logits_out (host [B][vocab], nullable): raw logits incl. the -128
@@ -270,8 +283,9 @@ int asr_qwen_create(const asr_qwen_config* cfg, const void* arena, size_t arena_
  * first-token selection. Sequence b's prompt is [pre_ids[pre_offsets[b] : pre_offsets[b+1]] | audio embeddings of utterance b |
  * post_ids[post_offsets[b] : post_offsets[b+1]]] -- pre = head + query + suffix ids, post = tail (+ language tail) ids
  * (:923-927, CONCAT_EMBED). next_ids_out (host B, nullable) = arg-max of the last position; logits_out (host [B][vocab],
- * nullable); ids_len_out (host B, nullable) = prompt length = the reference's kv_seq_len output (:672). Resets the KV cache. */
-int asr_qwen_prefill(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
+ * nullable); ids_len_out (host B, nullable) = prompt length = the reference's kv_seq_len output (:672). Resets the KV cache.
+ * audio: the session's asr_audio_dtype with Whisper's meaning (Export_Qwen_ASR.py:80,710-731,854,1596): F32 / F16 in [-1, 1], I16 raw PCM x 2^-15. */
+int asr_qwen_prefill(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
                      const int32_t* pre_offsets, const int32_t* post_ids, const int32_t* post_offsets, int32_t* next_ids_out, float* logits_out,
                      int32_t* ids_len_out);
 /* one position per sequence (Embed + decode_greedy, :690-716). ids: host [B], or NULL to feed the device-resident arg-max of the
@@ -313,8 +327,9 @@ int asr_qwen_beam_search(asr_session* s, int beam, int max_new, const int32_t* s
  * post = <|audio_end|> + the word / <timestamp> ids). Rows selected on the device: positions whose prompt id == timestamp_id, or
  * every position when timestamp_id < 0 (the graph's output_ids (1, L)). Host outputs, packed utterance-major in position order:
  * slot_offsets_out [B + 1] (utterance b's rows are [off[b], off[b+1])), buckets_out [buckets_cap >= off[B]] = arg-max bucket per row,
- * logits_out [off[B]][classify_num] (nullable), ids_len_out [B] (nullable). The KV cache is written as in a prefill, and nothing reads it. */
-int asr_qwen_align(asr_session* s, const float* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
+ * logits_out [off[B]][classify_num] (nullable), ids_len_out [B] (nullable). The KV cache is written as in a prefill, and nothing reads it.
+ * audio: as in asr_qwen_prefill (the aligner shares the Qwen3-ASR audio path and its INPUT_AUDIO_DTYPE, Export_Qwen_ASR.py:80,710-731). */
+int asr_qwen_align(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* pre_ids,
                    const int32_t* pre_offsets, const int32_t* post_ids, const int32_t* post_offsets, int32_t timestamp_id, int32_t* slot_offsets_out,
                    int32_t* buckets_out, int64_t buckets_cap, float* logits_out, int32_t* ids_len_out);
 
@@ -330,6 +345,10 @@ int asr_mem_copy(int device_id, void* dst, const void* src, size_t bytes, int ki
 int asr_session_destroy(asr_session* s);
 int asr_session_set_stream(asr_session* s, void* hip_stream);       /* borrow a caller stream (e.g. torch's) */
 int asr_session_device(asr_session* s, int* device_id);
+/* asr_audio_dtype of the session's audio entries (default ASR_AUDIO_F32). May be set between any two compute calls; the step graphs that hold the front
+ * end are keyed by it. INVALID for a null session or an unknown value. */
+int asr_session_set_audio_dtype(asr_session* s, int audio_dtype);
+int asr_session_audio_dtype(asr_session* s, int* audio_dtype_out);
 
 /* Per-kernel-class timing with HIP events on the session stream (bench.py roofline leg).
  * read: up to `cap` classes; names are NUL-terminated, 32 bytes apart in `names`. */

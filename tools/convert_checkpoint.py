@@ -67,7 +67,7 @@ def _count(sd, pattern):
     return max(ids) + 1 if ids else 0
 
 
-def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=None, language="zh", decode_mode="zh"):
+def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=None, language="zh", decode_mode="zh", input_audio_dtype="F32"):
     cfgm = importlib.import_module(PKG + ".config")
     if family in ("sensevoice", "paraformer"):
         if cmvn is not None:
@@ -79,7 +79,7 @@ def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=N
         cfg = cfgm.SenseVoiceConfig(d_model=d, d_ffn=sd["encoder.encoders.0.feed_forward.w_1.weight"].shape[0],
                                     n_enc=_count(sd, r"encoder\.encoders\.(\d+)\."), n_tp=_count(sd, r"encoder\.tp_encoders\.(\d+)\."),
                                     vocab=sd["ctc.ctc_lo.weight"].shape[0])
-        importlib.import_module(PKG + ".sensevoice").export_sensevoice(out, cfg, sd, precision)
+        importlib.import_module(PKG + ".sensevoice").export_sensevoice(out, cfg, sd, precision, input_audio_dtype)
     elif family == "paraformer":
         d = sd["encoder.after_norm.weight"].shape[0]
         cfg = cfgm.ParaformerConfig(d_model=d, d_ffn=sd["encoder.encoders.0.feed_forward.w_1.weight"].shape[0],
@@ -89,7 +89,7 @@ def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=N
                                     vocab=sd["decoder.output_layer.weight"].shape[0])
         if tokens is None:
             raise ValueError("Paraformer needs the token list (--tokens tokens.json or tokens.txt)")
-        importlib.import_module(PKG + ".paraformer").export_paraformer(out, cfg, sd, tokens, language, decode_mode, precision)
+        importlib.import_module(PKG + ".paraformer").export_paraformer(out, cfg, sd, tokens, language, decode_mode, precision, input_audio_dtype)
     elif family == "whisper":
         d = sd["model.encoder.layer_norm.weight"].shape[0]
         cfg = cfgm.WhisperConfig(d_model=d, n_heads=d // 64, d_ffn=sd["model.encoder.layers.0.fc1.weight"].shape[0],
@@ -103,7 +103,7 @@ def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=N
         shim = importlib.import_module(PKG + ".ort_shim")
         os.makedirs(out, exist_ok=True)
         blob = arena.build_whisper_arena(cfg, sd, precision, ckm.whisper_suppress_tokens(cfg), ckm.whisper_begin_suppress_tokens(cfg))
-        shim.save_model(os.path.join(out, "Whisper.asrmodel"), "whisper", cfg.to_dict(), blob, {}, precision)
+        shim.save_model(os.path.join(out, "Whisper.asrmodel"), "whisper", cfg.to_dict(), blob, {}, precision, input_audio_dtype)
     elif family == "qwen_asr":
         a, t = "thinker.audio_tower.", "thinker.model."
         de, d = sd[a + "ln_post.weight"].shape[0], sd[t + "norm.weight"].shape[0]
@@ -119,7 +119,7 @@ def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=N
         if tokens is None:
             raise ValueError("Qwen3-ASR needs the exporter's metadata map (--tokens metadata.json: special_token_ids, supported_languages, ...)")
         os.makedirs(out, exist_ok=True)
-        importlib.import_module(PKG + ".qwen_asr").export_qwen_asr(cfg, sd, os.path.join(out, "Qwen_ASR.asrmodel"), tokens, precision)
+        importlib.import_module(PKG + ".qwen_asr").export_qwen_asr(cfg, sd, os.path.join(out, "Qwen_ASR.asrmodel"), tokens, precision, input_audio_dtype)
     elif family == "qwen_aligner":
         cfg = qwen_aligner_config(sd)
         if tokens is None:
@@ -131,7 +131,7 @@ def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=N
         if "supported_languages" in tokens:
             langs = tokens["supported_languages"]
             meta["supported_languages"] = langs if isinstance(langs, str) else json.dumps(langs, ensure_ascii=False)
-        importlib.import_module(PKG + ".ort_shim_qwen").export_qwen_aligner_folder(out, cfg, sd, meta, precision)
+        importlib.import_module(PKG + ".ort_shim_qwen").export_qwen_aligner_folder(out, cfg, sd, meta, precision, input_audio_dtype)
     else:
         raise ValueError(family)
     return cfg
@@ -163,6 +163,9 @@ def main():
     ap.add_argument("--language", default="zh")
     ap.add_argument("--decode-mode", default="zh", choices=("zh", "en"))
     ap.add_argument("--precision", default="bf16", choices=("bf16", "f32"))
+    ap.add_argument("--input-audio-dtype", default="F32", choices=("F32", "INT16", "F16"),
+                    help="type of the bundle's audio input, the reference's INPUT_AUDIO_DTYPE: INT16 = raw PCM; F32 / F16 = int16-range values (SenseVoice, "
+                         "Paraformer) or samples in [-1, 1] (Whisper, Qwen3)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     tokens = None
@@ -170,7 +173,7 @@ def main():
         with open(a.tokens, "r", encoding="utf-8") as f:
             tokens = json.load(f) if a.tokens.endswith(".json") else [ln.rstrip("\n") for ln in f]
     cfg = convert(a.family, load_state_dict(a.checkpoint), a.out, 0 if a.precision == "bf16" else 1,
-                  load_kaldi_cmvn(a.cmvn) if a.cmvn else None, tokens, a.language, a.decode_mode)
+                  load_kaldi_cmvn(a.cmvn) if a.cmvn else None, tokens, a.language, a.decode_mode, a.input_audio_dtype)
     print(f"wrote {a.out}: {cfg}")
 
 

@@ -72,7 +72,7 @@ def run(a) -> dict:
             if bundle_prec != 0:
                 raise SystemExit("--precision %s needs a bf16 bundle (convert the checkpoint with --precision bf16)" % a.precision)
             bundle_prec = {"fp8w": 2, "fp8mm": 3, "mxfp4w": 4}[a.precision]
-        sess = eng.WhisperSession(cfg, blob, bundle_prec)
+        sess = eng.WhisperSession(cfg, blob, bundle_prec, audio_dtype=shim.bundle_audio_dtype(info))      # the bundle's INPUT_AUDIO_DTYPE
         tok = None
         if a.tokenizer:
             from transformers import AutoTokenizer
@@ -104,7 +104,7 @@ def run(a) -> dict:
             if bundle_prec != 0:
                 raise SystemExit("--precision %s needs a bf16 bundle (convert the checkpoint with --precision bf16)" % a.precision)
             bundle_prec = 2 if a.precision == "fp8w" else 4
-        sess = eng.QwenAsrSession(cfg, blob, bundle_prec)
+        sess = eng.QwenAsrSession(cfg, blob, bundle_prec, audio_dtype=shim.bundle_audio_dtype(info))
         tok = None
         if a.tokenizer:
             from transformers import AutoTokenizer
