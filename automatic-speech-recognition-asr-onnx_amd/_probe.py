@@ -46,6 +46,14 @@ class BeamSelectDesc(C.Structure):
                 ("stop", _ip), ("src_in", _ip), ("tok_in", _ip), ("src_out", _ip), ("tok_out", _ip)]
 
 
+class TokenHeadDesc(C.Structure):
+    _fields_ = [("op", C.c_int32), ("rows", C.c_int32), ("n_valid", C.c_int32), ("ld", C.c_int32), ("logits", _fp), ("vec", _fp),
+                ("K", C.c_int32), ("ld_save", C.c_int32), ("n_saved", C.c_int32), ("n_saved_after", C.c_int32), ("save_ids", _ip),
+                ("range", C.c_int32), ("partial", C.c_int32), ("value", C.c_float), ("next_in", _ip),
+                ("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float), ("noise", _fp), ("seed", C.c_uint64),
+                ("no_speech_id", C.c_int32), ("out_v", _fp), ("out_i", _ip)]
+
+
 SIGNATURES = {
     "asr_probe_gemm": (C.c_int, [C.POINTER(GemmDesc)]),
     "asr_probe_gemm_chain": (C.c_int, [C.c_int] * 6 + [_fp]),
@@ -57,6 +65,7 @@ SIGNATURES = {
     "asr_probe_decode_attention": (C.c_int, [C.POINTER(DecodeAttnDesc)]),
     "asr_probe_qwen_attention": (C.c_int, [C.POINTER(QwenAttnDesc)]),
     "asr_probe_beam_select": (C.c_int, [C.POINTER(BeamSelectDesc)]),
+    "asr_probe_token_head": (C.c_int, [C.POINTER(TokenHeadDesc)]),
     "asr_probe_decode_attention_beam": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p]),
     "asr_probe_gemm_counts": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "asr_probe_live_device_bytes": (C.c_int, [C.POINTER(C.c_int64)]),
@@ -292,6 +301,64 @@ def beam_select(beam, K, n_slots, topv, topi, cum, fin, length, nxt, done, src_i
         setattr(d, k, st[k].ctypes.data_as(_ip))
     _lib.check(load().asr_probe_beam_select(C.byref(d)))
     return st
+
+
+PAD_LOGIT = np.float32(1e30)              # what token_head puts in the pad columns [n_valid, ld) of every logits row
+_HEAD_OPS = {"argmax_rows": 0, "beam_topk": 1, "apply_penalty": 2, "append_ids": 3, "sample_topk_topp": 4, "no_speech_prob": 5}
+
+
+def token_head(op, logits=None, vec=None, K=0, save_ids=None, n_saved=0, range_=0, value=1.0, partial=0, next_ids=None,
+               temperature=1.0, top_p=1.0, repetition_penalty=1.0, noise=None, seed=0, no_speech_id=0):
+    """One token-selection head (asr_mi355x_probe.h: asr_probe_token_head) through its product launcher; `op` is the launcher's name less "launch_".
+
+    logits [rows][n_valid] are laid out with the sessions' leading dimension ld = roundup(n_valid, 128), the pad filled with PAD_LOGIT (+1e30: a kernel
+    that lets a pad column into a maximum, a top-k list or a soft-max sum fails visibly); vec (extra / bias / penalty, [n_valid]) gets zeros there.
+    Returns a dict: the head's outputs (ids | topv, topi | next | prob), logits [rows][ld] after the call, save_ids (the whole table) and n_saved after it."""
+    d = TokenHeadDesc()
+    d.op = _HEAD_OPS[op]
+    out, keep = {}, []
+    if logits is not None:
+        logits = _f32(logits)
+        rows, n_valid = logits.shape
+        ld = (n_valid + 127) // 128 * 128
+        padded = np.full((rows, ld), PAD_LOGIT, np.float32)
+        padded[:, :n_valid] = logits
+        out["logits"] = padded
+        d.logits, d.n_valid, d.ld = padded.ctypes.data_as(_fp), n_valid, ld
+        if vec is not None:
+            v = np.zeros(ld, np.float32)
+            v[:n_valid] = _f32(vec)
+            keep.append(v); d.vec = v.ctypes.data_as(_fp)
+    else:
+        rows, d.n_valid, d.ld = len(next_ids), 1, 128
+    d.rows, d.K = rows, K
+    if save_ids is not None:
+        out["save_ids"] = np.array(save_ids, np.int32, order="C", copy=True)
+        assert out["save_ids"].ndim == 2 and out["save_ids"].shape[0] == rows
+        d.save_ids, d.ld_save, d.n_saved = out["save_ids"].ctypes.data_as(_ip), out["save_ids"].shape[1], n_saved
+    d.range, d.partial, d.value = range_, partial, value
+    if next_ids is not None:
+        nx = np.ascontiguousarray(next_ids, np.int32)
+        keep.append(nx); d.next_in = nx.ctypes.data_as(_ip)
+    d.temperature, d.top_p, d.repetition_penalty, d.seed, d.no_speech_id = temperature, top_p, repetition_penalty, seed, no_speech_id
+    if noise is not None:
+        noise = _f32(noise)
+        assert noise.shape == (rows, K)
+        d.noise = noise.ctypes.data_as(_fp)
+    if op == "beam_topk":
+        out["topv"], out["topi"] = np.zeros((rows, K), np.float32), np.zeros((rows, K), np.int32)
+        d.out_v, d.out_i = out["topv"].ctypes.data_as(_fp), out["topi"].ctypes.data_as(_ip)
+    elif op == "no_speech_prob":
+        out["prob"] = np.zeros(rows, np.float32)
+        d.out_v = out["prob"].ctypes.data_as(_fp)
+    elif op in ("argmax_rows", "sample_topk_topp"):
+        key = "ids" if op == "argmax_rows" else "next"
+        out[key] = np.full(rows, -1, np.int32)
+        d.out_i = out[key].ctypes.data_as(_ip)
+    _lib.check(load().asr_probe_token_head(C.byref(d)))
+    if save_ids is not None:
+        out["n_saved"] = d.n_saved_after
+    return out
 
 
 def _bf16_bits(x):

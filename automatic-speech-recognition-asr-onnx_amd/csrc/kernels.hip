@@ -1243,7 +1243,7 @@ __global__ __launch_bounds__(1024) void argmax_rows_kernel(const float* __restri
   if (tid == 0) {
     for (int w = 1; w < 16; ++w)
       if (bv[w] > best || (bv[w] == best && bi[w] < bidx)) { best = bv[w]; bidx = bi[w]; }
-    ids[r] = bidx;
+    ids[r] = bidx == 0x7fffffff ? 0 : bidx;               // (no column above -inf: torch.argmax's 0, a valid embedding row)
   }
 }
 
@@ -2605,7 +2605,7 @@ namespace {
 
 // per row: log-soft-max statistics and the K best (log-prob, id) pairs, ties -> lower id. One pass: every thread keeps a running
 // (max, sum) pair and its own sorted best-8 list; the lists merge in K rounds of a block-wide arg-max.
-// bias (nullable): added to every column first; a column the bias takes to -inf (BEGIN_SUPPRESS) is left out of the soft-max as well.
+// bias (nullable): added to every column first; a -inf column (BEGIN_SUPPRESS through the bias, or a -inf logit) is left out of the soft-max as well.
 __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict__ logits, int ld, int n_valid, const float* __restrict__ bias, int K,
                                                          float* __restrict__ topv, int32_t* __restrict__ topi) {
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2621,7 +2621,8 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict
     for (int e = 0; e < 4; ++e) {
       float x = xs[e];
       if (v0 + e >= n_valid) continue;
-      if (bias) { x += bias[v0 + e]; if (x == -INFINITY) continue; }
+      if (bias) x += bias[v0 + e];
+      if (x == -INFINITY) continue;                        // zero weight, no candidate -- and exp(-inf - -inf) would poison the running sum
       if (x > m) { sum = sum * __expf(m - x) + 1.0f; m = x; } else { sum += __expf(x - m); }
       if (x > tv[BEAM_MAX - 1]) {
         tv[BEAM_MAX - 1] = x; ti[BEAM_MAX - 1] = v0 + e;

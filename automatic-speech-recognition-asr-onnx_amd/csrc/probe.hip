@@ -709,6 +709,86 @@ extern "C" int asr_probe_beam_select(asr_probe_beam_select_desc* d) {
   });
 }
 
+// ---- the token-selection heads (kernels.h) on host arrays: one product launcher per call, unchanged. Every index a kernel will follow is checked here first.
+extern "C" int asr_probe_token_head(asr_probe_token_head_desc* d) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d && d->op >= 0 && d->op <= 5 && d->rows > 0 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0, "probe_token_head: bad descriptor");
+    const int op = d->op, rows = d->rows, ld = d->ld;
+    const bool uses_logits = op != 3, uses_save = op == 2 || op == 3 || op == 4;
+    ASR_REQUIRE(!uses_logits || d->logits, "probe_token_head: logits missing");
+    ASR_REQUIRE((op == 2 || op == 3 || op == 5 || d->out_i) && ((op != 1 && op != 5) || d->out_v), "probe_token_head: output array missing");
+    ASR_REQUIRE(op != 2 || (d->range >= 1 && d->range <= 64 && d->range <= d->ld_save), "probe_token_head: apply_penalty range %d (1..64, within the table)", d->range);
+    ASR_REQUIRE(op != 5 || (d->no_speech_id >= 0 && d->no_speech_id < d->n_valid), "probe_token_head: no_speech_id %d outside the vocabulary of %d", d->no_speech_id, d->n_valid);
+    if (uses_save) {
+      ASR_REQUIRE(d->save_ids && d->ld_save >= 1 && d->n_saved >= 0, "probe_token_head: history table missing");
+      ASR_REQUIRE(op != 2 || d->n_saved <= d->ld_save, "probe_token_head: apply_penalty reads save_ids[n_saved - range, n_saved): n_saved %d past the table of %d", d->n_saved, d->ld_save);
+      const int used = op == 3 ? 0 : std::min(d->n_saved, d->ld_save);       // the columns whose ids index the logits row
+      for (int r = 0; r < rows; ++r)
+        for (int j = 0; j < used; ++j) {
+          const int32_t id = d->save_ids[(size_t)r * d->ld_save + j];
+          ASR_REQUIRE(id >= 0 && id < d->n_valid, "probe_token_head: saved id %d of row %d outside the vocabulary of %d", id, r, d->n_valid);
+        }
+    }
+    asr_require_device(0);
+    Tmp t;
+    auto up = [&](const void* h, size_t bytes) -> void* {
+      void* p = t.alloc(bytes);
+      HIP_CHECK(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+      return p;
+    };
+    const size_t lbytes = (size_t)rows * ld * 4, sbytes = uses_save ? (size_t)rows * d->ld_save * 4 : 0;
+    float* dlog = uses_logits ? (float*)up(d->logits, lbytes) : nullptr;
+    const float* dvec = d->vec ? (const float*)up(d->vec, (size_t)ld * 4) : nullptr;
+    int32_t* dsave = uses_save ? (int32_t*)up(d->save_ids, sbytes) : nullptr;
+    int32_t* dn = uses_save ? (int32_t*)up(&d->n_saved, 4) : nullptr;
+    float* dv = nullptr; int32_t* di = nullptr;
+    size_t nv = 0, ni = 0;
+    switch (op) {
+      case 0:
+        ni = rows; di = (int32_t*)t.alloc(ni * 4);
+        launch_argmax_rows(dlog, ld, rows, d->n_valid, dvec, di, nullptr);
+        break;
+      case 1:
+        ASR_REQUIRE(d->K >= 1 && d->K <= BEAM_MAX, "probe_token_head: beam_topk K %d", d->K);
+        nv = ni = (size_t)rows * d->K; dv = (float*)t.alloc(nv * 4); di = (int32_t*)t.alloc(ni * 4);
+        launch_beam_topk(dlog, ld, rows, d->n_valid, dvec, d->K, dv, di, nullptr);
+        break;
+      case 2:
+        launch_apply_penalty(dlog, ld, rows, dsave, d->ld_save, dn, d->range, d->value, nullptr, d->partial);
+        break;
+      case 3:
+        ASR_REQUIRE(d->next_in, "probe_token_head: append_ids without ids");
+        launch_append_ids((const int32_t*)up(d->next_in, (size_t)rows * 4), rows, dsave, d->ld_save, dn, nullptr);
+        break;
+      case 4: {
+        ASR_REQUIRE(d->K >= 1 && d->K <= 64 && d->K <= d->n_valid, "probe_token_head: sampler top_k %d", d->K);
+        ni = rows; di = (int32_t*)t.alloc(ni * 4);
+        SampleArgs a{};
+        a.logits = dlog; a.ld = ld; a.rows = rows; a.n_valid = d->n_valid; a.extra = dvec;
+        a.save_ids = dsave; a.ld_save = d->ld_save; a.n_saved = dn;
+        a.temperature = d->temperature; a.top_p = d->top_p; a.repetition_penalty = d->repetition_penalty; a.top_k = d->K;
+        a.noise = d->noise ? (const float*)up(d->noise, (size_t)rows * d->K * 4) : nullptr; a.seed = d->seed;
+        a.next = di;
+        launch_sample_topk_topp(a, nullptr);
+        break;
+      }
+      default:
+        ASR_REQUIRE(dvec, "probe_token_head: no_speech_prob without the penalty vector");
+        nv = rows; dv = (float*)t.alloc(nv * 4);
+        launch_no_speech_prob(dlog, ld, rows, d->n_valid, dvec, d->no_speech_id, dv, nullptr);
+        break;
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    if (nv) HIP_CHECK(hipMemcpy(d->out_v, dv, nv * 4, hipMemcpyDeviceToHost));
+    if (ni) HIP_CHECK(hipMemcpy(d->out_i, di, ni * 4, hipMemcpyDeviceToHost));
+    if (uses_logits) HIP_CHECK(hipMemcpy(d->logits, dlog, lbytes, hipMemcpyDeviceToHost));
+    if (uses_save) {
+      HIP_CHECK(hipMemcpy(d->save_ids, dsave, sbytes, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(&d->n_saved_after, dn, 4, hipMemcpyDeviceToHost));
+    }
+  });
+}
+
 extern "C" int asr_probe_decode_attention(asr_probe_decode_attn_desc* d) {
   return asr_guard([&] {
     ASR_REQUIRE(d, "probe_decode_attention: null descriptor");

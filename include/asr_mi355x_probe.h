@@ -146,6 +146,30 @@ typedef struct asr_probe_beam_select_desc {
 } asr_probe_beam_select_desc;
 int asr_probe_beam_select(asr_probe_beam_select_desc* d);
 
+/* One call of a token-selection head through its product launcher on host arrays. op: 0 launch_argmax_rows, 1 launch_beam_topk, 2 launch_apply_penalty,
+ * 3 launch_append_ids, 4 launch_sample_topk_topp, 5 launch_no_speech_prob. Rows keep their real leading dimension (ld, a multiple of 128, >= n_valid): the
+ * caller fills the pad columns, so a kernel that reads them shows. n_saved is put in device memory, as the sessions keep it; the logits, the whole save_ids
+ * table and the counter come back as they stand after the call (penalty and sampler work in place). Fields an op does not use are ignored. */
+typedef struct asr_probe_token_head_desc {
+  int32_t op, rows, n_valid, ld;
+  float* logits;             /* [rows][ld], in / out (ops 0 1 2 4 5) */
+  const float* vec;          /* [ld]: extra (0, 4), bias (1), nullable; penalty (5) */
+  int32_t K;                 /* beam_topk: pairs per row; sampler: top_k */
+  int32_t ld_save, n_saved;  /* history table geometry and the device counter's value (2 3 4) */
+  int32_t n_saved_after;     /* out: the device counter after the call */
+  int32_t* save_ids;         /* [rows][ld_save], in / out (2 3 4) */
+  int32_t range, partial;    /* apply_penalty */
+  float value;
+  const int32_t* next_in;    /* [rows] append_ids */
+  float temperature, top_p, repetition_penalty;   /* sampler */
+  const float* noise;        /* [rows][K] uniforms, or NULL: the counter-based generator keyed by seed */
+  uint64_t seed;
+  int32_t no_speech_id;
+  float* out_v;              /* topv [rows][K] (1), prob [rows] (5) */
+  int32_t* out_i;            /* ids [rows] (0), topi [rows][K] (1), next [rows] (4) */
+} asr_probe_token_head_desc;
+int asr_probe_token_head(asr_probe_token_head_desc* d);
+
 /* launches per GEMM kernel family since the last reset, as "family=count;..." (host-side counters: hipGraph replays do not
  * count, so reset, run a session once on a new batch geometry, read). reset != 0 clears the counters after the read. */
 int asr_probe_gemm_counts(int reset, char* buf, int cap);
