@@ -51,7 +51,9 @@ class TokenHeadDesc(C.Structure):
                 ("K", C.c_int32), ("ld_save", C.c_int32), ("n_saved", C.c_int32), ("n_saved_after", C.c_int32), ("save_ids", _ip),
                 ("range", C.c_int32), ("partial", C.c_int32), ("value", C.c_float), ("next_in", _ip),
                 ("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float), ("noise", _fp), ("seed", C.c_uint64),
-                ("no_speech_id", C.c_int32), ("out_v", _fp), ("out_i", _ip)]
+                ("no_speech_id", C.c_int32), ("out_v", _fp), ("out_i", _ip),
+                ("steps", C.c_int32), ("track_history", C.c_int32), ("sampling", C.c_int32), ("change_step", C.c_int32), ("range2", C.c_int32),
+                ("value2", C.c_float), ("picks", _ip)]
 
 
 SIGNATURES = {
@@ -358,6 +360,38 @@ def token_head(op, logits=None, vec=None, K=0, save_ids=None, n_saved=0, range_=
     _lib.check(load().asr_probe_token_head(C.byref(d)))
     if save_ids is not None:
         out["n_saved"] = d.n_saved_after
+    return out
+
+
+def head_steps(logits, steps, ld_save, range_, value, partial, bias=None, track_history=False, sampler=None, noise=None, change=None):
+    """A TokenHead (csrc/decode_head.h) driven through `steps` decoder steps on the same logits rows (asr_probe_token_head, op 6): step 0 is a prefill
+    (`bias` added, no penalty), the others are decode steps. sampler: (temperature, top_k, top_p, repetition_penalty, seed) or None; noise: uniforms
+    [rows][top_k] armed for step 0; change: (step, value, range) -- set_penalty before that step. Rows are padded as token_head pads them.
+    Returns {"picks": [steps][rows], "save_ids": the final history [rows][ld_save], "n_saved": the counter}."""
+    logits = _f32(logits)
+    rows, n_valid = logits.shape
+    ld = (n_valid + 127) // 128 * 128
+    padded = np.full((rows, ld), PAD_LOGIT, np.float32)
+    padded[:, :n_valid] = logits
+    d = TokenHeadDesc()
+    d.op, d.rows, d.n_valid, d.ld, d.logits = 6, rows, n_valid, ld, padded.ctypes.data_as(_fp)
+    if bias is not None:
+        v = np.zeros(ld, np.float32)
+        v[:n_valid] = _f32(bias)
+        d.vec = v.ctypes.data_as(_fp)
+    d.steps, d.ld_save, d.range, d.value, d.partial, d.track_history = steps, ld_save, range_, value, partial, int(track_history)
+    if sampler is not None:
+        d.sampling, (d.temperature, d.K, d.top_p, d.repetition_penalty, d.seed) = 1, sampler
+    if noise is not None:
+        noise = _f32(noise)
+        assert noise.shape == (rows, d.K)
+        d.noise = noise.ctypes.data_as(_fp)
+    if change is not None:
+        d.change_step, d.value2, d.range2 = change
+    out = {"picks": np.full((steps, rows), -1, np.int32), "save_ids": np.full((rows, ld_save), -1, np.int32)}
+    d.picks, d.save_ids = out["picks"].ctypes.data_as(_ip), out["save_ids"].ctypes.data_as(_ip)
+    _lib.check(load().asr_probe_token_head(C.byref(d)))
+    out["n_saved"] = d.n_saved_after
     return out
 
 

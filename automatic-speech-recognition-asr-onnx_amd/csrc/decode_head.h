@@ -1,0 +1,197 @@
+// What follows the logits GEMM of a decoder step, once for every decoder family: the token-selection head (arg-max, penalty-greedy,
+// top-k / top-p sampling + the id history they share), the beam-search ranking state, and the read-back of a step's picks and logits.
+// Header-only and hidden: the sessions and the probe library each compile their own copy, the product library exports nothing new.
+#pragma once
+#include <algorithm>
+#include <cstring>
+
+#include "engine.h"
+#include "kernels.h"
+
+#define ASR_LOCAL __attribute__((visibility("hidden")))
+
+// `buf` sized to `bytes`; true when its pointer moved (a captured step that holds it is stale)
+ASR_LOCAL inline bool reserve_moved(DeviceBuffer& buf, size_t bytes, hipStream_t s) {
+  void* before = buf.ptr;
+  buf.reserve(bytes, s);
+  return buf.ptr != before;
+}
+
+// ---- token-selection head (Export_Whisper.py:228-325, Inference_Qwen_ASR_ONNX.py:369-376): arg-max, penalty-greedy (APPLY_PENALTY + GREEDY_SEARCH) or
+// TOPK_TOPP_SAMPLING, and the history of picked ids [rows][ld_save] the last two read. What differs between the families is data, set by init().
+struct ASR_LOCAL TokenHead {
+  int ld_save = 0;                     // history capacity per sequence: max_target_positions (Whisper), max_seq_len (Qwen3)
+  int partial = 0;                     // launch_apply_penalty's window rule: 0 Whisper (nothing until `range` ids are saved), 1 Qwen3
+  int sampling_ld_limit = 0;           // set_sampling refuses a history wider than this
+  float penalty_value = 1.0f;          // 1.0 = plain greedy (REPEAT_PENALTY)
+  int penalty_range = 0;
+  bool track_history = false;          // GREEDY_SEARCH graphs append every pick to save_id even while the penalty value is 1.0
+  bool sampling = false;               // TOPK_TOPP_SAMPLING head (USE_SAMPLING)
+  float temperature = 0.8f, top_p = 0.95f, samp_rep_penalty = 1.0f;
+  int top_k = 10;
+  uint64_t samp_seed = 0;
+  DeviceBuffer d_save, d_nsaved;       // generated ids per sequence + their count (on the device: a captured step replays for every position)
+  DeviceBuffer d_noise;                // caller-supplied uniforms [rows][top_k] for the next step (parity tests); consumed once
+  bool noise_armed = false;            // a step with armed noise is not graphable
+  uint64_t epoch = 0;                  // moves with everything a captured step bakes in: a setter that changed a value, a history buffer that moved
+
+  void init(int ld_save_, int partial_, int default_range, int sampling_ld_limit_) {
+    ld_save = ld_save_; partial = partial_; penalty_range = default_range; sampling_ld_limit = sampling_ld_limit_;
+  }
+  bool plain() const { return !sampling && penalty_value == 1.0f; }
+
+  // `who`: the C entry's name, the prefix of its messages
+  void set_penalty(float value, int range, const char* who) {
+    ASR_REQUIRE(value > 0.0f && range >= 1 && range <= 64, "%s: value %g range %d", who, value, range);
+    if (penalty_value != value || penalty_range != range) { penalty_value = value; penalty_range = range; ++epoch; }
+  }
+  void set_track_history(bool enable) {
+    if (track_history != enable) { track_history = enable; ++epoch; }
+  }
+  void set_sampling(bool enable, float t, int k, float p, float rp, uint64_t seed, const char* who) {
+    if (enable) {
+      ASR_REQUIRE(t > 0.0f && k >= 1 && k <= 64 && p > 0.0f && rp > 0.0f && ld_save <= sampling_ld_limit, "%s: temperature %g top_k %d top_p %g penalty %g", who, t, k, p, rp);
+      temperature = t; top_k = k; top_p = p; samp_rep_penalty = rp; samp_seed = seed;
+    }
+    sampling = enable;
+    noise_armed = false;
+    ++epoch;
+  }
+  void arm_noise(const float* uniforms, int count, hipStream_t s) {
+    d_noise.reserve((size_t)count * 4, s);
+    HIP_CHECK(hipMemcpyAsync(d_noise.ptr, uniforms, (size_t)count * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    noise_armed = true;
+  }
+
+  void reserve(int rows, hipStream_t s) {
+    bool moved = reserve_moved(d_nsaved, 256, s);
+    moved |= reserve_moved(d_save, (size_t)rows * ld_save * 4, s);
+    if (moved) ++epoch;
+  }
+  void restart(hipStream_t s) { HIP_CHECK(hipMemsetAsync(d_nsaved.ptr, 0, 4, s)); }      // every prefill starts from an empty history
+
+  // The head's launches on logits [rows][ld]: picks go to next [rows]. bias: Whisper's BEGIN_SUPPRESS after a prefill, else null. penalise: false on a
+  // prefill (the prefill graphs select from the raw logits with an empty history; the decode graphs apply the penalty first).
+  void enqueue(float* logits, int ld, int rows, int n_valid, const float* bias, bool penalise, int32_t* next, hipStream_t s) {
+    const bool penalised = penalty_value != 1.0f && !sampling;
+    int32_t* save = d_save.as<int32_t>();
+    int32_t* n_saved = d_nsaved.as<int32_t>();
+    if (penalised && penalise) launch_apply_penalty(logits, ld, rows, save, ld_save, n_saved, penalty_range, penalty_value, s, partial);
+    if (sampling) {                        // the bias first, history = every sampled id
+      SampleArgs sa;
+      sa.logits = logits; sa.ld = ld; sa.rows = rows; sa.n_valid = n_valid; sa.extra = bias;
+      sa.save_ids = save; sa.ld_save = ld_save; sa.n_saved = n_saved;
+      sa.temperature = temperature; sa.top_p = top_p; sa.repetition_penalty = samp_rep_penalty; sa.top_k = top_k;
+      sa.noise = noise_armed ? d_noise.as<float>() : nullptr; sa.seed = samp_seed; sa.next = next;
+      launch_sample_topk_topp(sa, s);
+    } else {
+      launch_argmax_rows(logits, ld, rows, n_valid, bias, next, s);
+    }
+    if (penalised || sampling || track_history) {   // GREEDY_SEARCH / the sampling head append their pick to the history
+      launch_append_ids(next, rows, save, ld_save, n_saved, s);
+      launch_add_scalar(n_saved, 1, s);
+    }
+  }
+  void consumed() { noise_armed = false; }        // after the step: caller-supplied uniforms serve exactly one
+};
+
+// ---- beam-search ranking (semantics of oracle/qwen_asr_oracle.py:beam_search_core): hypothesis rows b * beam + r, their scores, lengths and ended flags, the
+// double-buffered ancestry / token tables [rows][ld] and the ids of the next pass, all on the device. The family keeps its hypothesis caches and its decoder pass.
+struct ASR_LOCAL BeamRanker {
+  DeviceBuffer topv, topi, cum, fin, len, done, next, stop, src[2], tok[2];
+  PinnedBuffer stage;                  // its own: a prefill called with null outputs may still be copying from the session's. [0, done_off) stop ids, then done flags
+  uint64_t epoch = 0;                  // moves when a buffer moved: a captured step that ranks is stale
+  int B = 0, beam = 0, ld = 0, n_stop = 0, done_off = 0, cur = 0;
+  const int32_t* slots_dev = nullptr;  // when set, the generated cache slots after a pass are *slots_dev + slots_off (a device counter: the pass replays from a captured graph)
+  int slots_off = 0;
+
+  int rows() const { return B * beam; }
+  const int32_t* ancestry() const { return src[cur].as<int32_t>(); }     // the table the next pass's self-attention follows
+  int32_t* next_ids() const { return next.as<int32_t>(); }
+
+  void begin(int B_, int beam_, int ld_, const int32_t* stop_ids, int n_stop_, hipStream_t s) {
+    B = B_; beam = beam_; ld = ld_; n_stop = n_stop_; cur = 0; slots_dev = nullptr; slots_off = 0;
+    const size_t N = (size_t)rows(), Nn = std::max<size_t>(N, 64);
+    bool moved = false;
+    for (DeviceBuffer* q : {&topv, &topi}) moved |= reserve_moved(*q, Nn * BEAM_MAX * 4, s);
+    for (DeviceBuffer* q : {&cum, &fin, &len, &done, &next}) moved |= reserve_moved(*q, Nn * 4, s);
+    moved |= reserve_moved(stop, (size_t)std::max(n_stop, 16) * 4, s);
+    for (DeviceBuffer* q : {&src[0], &src[1], &tok[0], &tok[1]}) moved |= reserve_moved(*q, N * ld * 4, s);
+    if (moved) ++epoch;
+    HIP_CHECK(hipStreamSynchronize(s));
+    done_off = std::max(n_stop, 16);
+    stage.reserve((size_t)(done_off + std::max(B, 64)) * 4);
+    if (n_stop) {
+      memcpy(stage.ptr, stop_ids, (size_t)n_stop * 4);
+      HIP_CHECK(hipMemcpyAsync(stop.ptr, stage.ptr, (size_t)n_stop * 4, hipMemcpyHostToDevice, s));
+    }
+    HIP_CHECK(hipMemsetAsync(done.ptr, 0, (size_t)B * 4, s));
+    HIP_CHECK(hipMemsetAsync(len.ptr, 0, N * 4, s));
+  }
+  // the first ranking: the prefill's logits, one row per utterance (+ bias: Whisper's BEGIN_SUPPRESS, as the arg-max head after a prefill)
+  void rank_first(const float* logits, int ld_logits, int n_valid, const float* bias, hipStream_t s) {
+    launch_beam_topk(logits, ld_logits, B, n_valid, bias, beam, topv.as<float>(), topi.as<int32_t>(), s);
+    select(1, 0, s);
+    flip();
+  }
+  // Rank the rows' extensions on the current tables: the select pass writes the ids of the next pass and the ancestry of this one. n_slots: generated cache
+  // slots after the pass (ignored once slots_dev is set). The caller flips afterwards -- outside a captured step, whose replay runs no host code.
+  void enqueue_rank(const float* logits, int ld_logits, int n_valid, int n_slots, hipStream_t s) {
+    launch_beam_topk(logits, ld_logits, rows(), n_valid, nullptr, beam, topv.as<float>(), topi.as<int32_t>(), s);
+    select(0, n_slots, s);
+  }
+  void flip() { cur ^= 1; }
+  // the per-utterance "best hypothesis has ended" flags, read back once per step
+  bool all_done(hipStream_t s) {
+    int32_t* h_done = stage.as<int32_t>() + done_off;
+    HIP_CHECK(hipMemcpyAsync(h_done, done.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    bool all = true;
+    for (int b = 0; b < B; ++b) all = all && h_done[b] != 0;
+    return all;
+  }
+  // per utterance its hypotheses best-first: tokens_out [rows][out_stride], n_out [rows], scores_out [rows] (nullable)
+  void download(int32_t* tokens_out, int out_stride, int32_t* n_out, float* scores_out, hipStream_t s) {
+    const size_t N = (size_t)rows();
+    std::vector<int32_t> h_tok(N * ld), h_len(N);
+    std::vector<float> h_cum(N);
+    HIP_CHECK(hipMemcpyAsync(h_tok.data(), tok[cur].ptr, N * ld * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(h_len.data(), len.ptr, N * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(h_cum.data(), cum.ptr, N * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t r = 0; r < N; ++r) {
+      n_out[r] = h_len[r];
+      if (scores_out) scores_out[r] = h_cum[r];
+      for (int j = 0; j < h_len[r] && j < out_stride; ++j) tokens_out[r * out_stride + j] = h_tok[r * ld + j];
+    }
+  }
+
+ private:
+  void select(int first, int n_slots, hipStream_t s) {
+    BeamArgs a{};
+    a.beam = beam; a.K = beam; a.ld = ld; a.first = first; a.n_slots = n_slots;
+    a.topv = topv.as<float>(); a.topi = topi.as<int32_t>();
+    a.cum = cum.as<float>(); a.fin = fin.as<int32_t>(); a.len = len.as<int32_t>(); a.done = done.as<int32_t>(); a.next = next.as<int32_t>();
+    a.stop = stop.as<int32_t>(); a.n_stop = n_stop;
+    a.src_in = src[cur].as<int32_t>(); a.tok_in = tok[cur].as<int32_t>();
+    a.src_out = src[cur ^ 1].as<int32_t>(); a.tok_out = tok[cur ^ 1].as<int32_t>();
+    if (!first) { a.slots_dev = slots_dev; a.slots_off = slots_off; }
+    launch_beam_select(a, B, s);
+  }
+};
+
+// A step's picks next [rows] and logits [rows][n_valid] (row stride ld on the device) to the caller through pinned staging; either output may be null.
+// Returns with the stream drained.
+ASR_LOCAL inline void download_step(PinnedBuffer& stage, const void* next, const void* logits, int ld, int rows, int n_valid, int32_t* next_out, float* logits_out,
+                                    hipStream_t s) {
+  const size_t nbytes = (size_t)rows * 4, lbytes = (size_t)rows * n_valid * 4;
+  stage.reserve(nbytes + 64 + (logits_out ? lbytes : 0));
+  unsigned char* st = stage.as<unsigned char>();
+  if (next_out) HIP_CHECK(hipMemcpyAsync(st, next, nbytes, hipMemcpyDeviceToHost, s));
+  if (logits_out)
+    HIP_CHECK(hipMemcpy2DAsync(st + nbytes + 64, (size_t)n_valid * 4, logits, (size_t)ld * 4, (size_t)n_valid * 4, rows, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (next_out) memcpy(next_out, st, nbytes);
+  if (logits_out) memcpy(logits_out, st + nbytes + 64, lbytes);
+}

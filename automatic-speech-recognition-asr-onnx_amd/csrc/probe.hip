@@ -8,6 +8,7 @@
 
 #include "../../include/asr_mi355x.h"
 #include "../../include/asr_mi355x_probe.h"
+#include "decode_head.h"
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
@@ -709,10 +710,47 @@ extern "C" int asr_probe_beam_select(asr_probe_beam_select_desc* d) {
   });
 }
 
+// ---- op 6 of asr_probe_token_head: a TokenHead driven as the sessions drive it -- restart, then enqueue + consumed per step on a fresh copy of the same rows
+static void probe_head_steps(asr_probe_token_head_desc* d) {
+  const char* who = "probe_token_head";
+  const int rows = d->rows, ld = d->ld, steps = d->steps;
+  ASR_REQUIRE(d->logits && d->picks && d->save_ids, "%s: head steps need logits, picks and save_ids", who);
+  ASR_REQUIRE(steps >= 1 && d->ld_save >= steps && d->ld_save <= 1024, "%s: %d steps do not fit the history table of %d", who, steps, d->ld_save);
+  ASR_REQUIRE(d->range <= d->ld_save && (d->change_step <= 0 || d->range2 <= d->ld_save), "%s: penalty range past the history table of %d", who, d->ld_save);
+  ASR_REQUIRE(!d->sampling || d->K <= d->n_valid, "%s: sampler top_k %d", who, d->K);
+  ASR_REQUIRE(!d->noise || d->sampling, "%s: noise without the sampler", who);
+  asr_require_device(0);
+  Tmp t;
+  const size_t lbytes = (size_t)rows * ld * 4;
+  float* dlog = (float*)t.alloc(lbytes);
+  int32_t* dpick = (int32_t*)t.alloc((size_t)steps * rows * 4);
+  float* dvec = nullptr;
+  if (d->vec) { dvec = (float*)t.alloc((size_t)ld * 4); HIP_CHECK(hipMemcpy(dvec, d->vec, (size_t)ld * 4, hipMemcpyHostToDevice)); }
+  TokenHead h;
+  h.init(d->ld_save, d->partial, d->range, 1024);
+  h.set_penalty(d->value, d->range, who);
+  h.set_track_history(d->track_history != 0);
+  if (d->sampling) h.set_sampling(true, d->temperature, d->K, d->top_p, d->repetition_penalty, d->seed, who);
+  h.reserve(rows, nullptr);
+  h.restart(nullptr);
+  if (d->noise) h.arm_noise(d->noise, rows * d->K, nullptr);
+  for (int i = 0; i < steps; ++i) {
+    if (i > 0 && i == d->change_step) h.set_penalty(d->value2, d->range2, who);
+    HIP_CHECK(hipMemcpy(dlog, d->logits, lbytes, hipMemcpyHostToDevice));
+    h.enqueue(dlog, ld, rows, d->n_valid, i == 0 ? dvec : nullptr, i > 0, dpick + (size_t)i * rows, nullptr);
+    h.consumed();
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpy(d->picks, dpick, (size_t)steps * rows * 4, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(d->save_ids, h.d_save.ptr, (size_t)rows * d->ld_save * 4, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(&d->n_saved_after, h.d_nsaved.ptr, 4, hipMemcpyDeviceToHost));
+}
+
 // ---- the token-selection heads (kernels.h) on host arrays: one product launcher per call, unchanged. Every index a kernel will follow is checked here first.
 extern "C" int asr_probe_token_head(asr_probe_token_head_desc* d) {
   return asr_guard([&] {
-    ASR_REQUIRE(d && d->op >= 0 && d->op <= 5 && d->rows > 0 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0, "probe_token_head: bad descriptor");
+    ASR_REQUIRE(d && d->op >= 0 && d->op <= 6 && d->rows > 0 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0, "probe_token_head: bad descriptor");
+    if (d->op == 6) { probe_head_steps(d); return; }
     const int op = d->op, rows = d->rows, ld = d->ld;
     const bool uses_logits = op != 3, uses_save = op == 2 || op == 3 || op == 4;
     ASR_REQUIRE(!uses_logits || d->logits, "probe_token_head: logits missing");

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/asr_mi355x.h"
+#include "decode_head.h"
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
@@ -688,14 +689,10 @@ struct QwSession : asr_session {
     if (kv_paged) return KvAddr{d_kvtab.as<int32_t>(), kv_pps, kv_page_elems(), cfg.max_seq_len};
     return KvAddr{nullptr, 0, 0, cfg.max_seq_len};
   }
-  // decode head (Inference_Qwen_ASR_ONNX.py:369-376): arg-max, penalty-greedy (APPLY_PENALTY + GREEDY_SEARCH) or top-k / top-p sampling
-  float penalty_value = 1.0f; int penalty_range = 10;
-  bool track_history = false;          // GREEDY_SEARCH graphs append every pick to save_id whatever the penalty value is
-  bool sampling = false, noise_armed = false; float temperature = 0.8f, top_p = 0.95f, samp_rep_penalty = 1.0f; int top_k = 10; uint64_t samp_seed = 0;
-  uint64_t head_epoch = 0;
-  DeviceBuffer d_save, d_nsaved, d_noise;
+  TokenHead head;                      // decode head (Inference_Qwen_ASR_ONNX.py:369-376) + the history of generated ids [B][max_seq_len]
   DeviceBuffer d_sel, d_amax_v, d_amax_i, d_bucket;      // forced-aligner head: counts / offsets / rows, arg-max partials, buckets
-  DeviceBuffer d_bkc, d_bvc, d_bhist, d_bp0, d_bplan, d_bsrc[2], d_btok[2], d_bcum, d_bfin, d_blen, d_bdone, d_btopv, d_btopi, d_bstop, d_bnext;   // beam search state
+  DeviceBuffer d_bkc, d_bvc, d_bhist, d_bp0, d_bplan;    // beam search: the hypothesis rows' caches, counters and row plan; scores and tables are the ranker's
+  BeamRanker ranker;
   StepGraph dec_graph;
   PinnedBuffer h_plan, h_io, h_ids;
 
@@ -715,7 +712,7 @@ struct QwSession : asr_session {
   template <typename T> void decoder_pass(const DecPass& P);
   template <typename T> void logits_head(const DecPass& P);
   template <typename T> void step(const int32_t* ids_host, int32_t* next_out, float* logits_out);
-  template <typename T> void finish(int B, int32_t* next_out, float* logits_out, bool sync);
+  void finish(int B, int32_t* next_out, float* logits_out, bool sync);
   template <typename T> void beam_search(int beam, int max_new, const int32_t* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out, float* scores_out);
 };
 
@@ -731,6 +728,7 @@ void QwSession::init() {
   rpw = round_up(cpw * t_tok, 16);
   ASR_REQUIRE(cpw >= 1 && rpw <= 1024, "qwen: bad attention window");
   vpad = round_up(c.vocab, 128);
+  head.init(c.max_seq_len, 1, 10, 1024);
   ASR_REQUIRE(c.classify_num >= 0, "qwen: classify_num %d", c.classify_num);
   hpad = aligner() ? round_up(c.classify_num, 128) : vpad;   // rows of dec.lm_head: the vocabulary, or the aligner's timestamp buckets
   cpad = round_up(c.conv_channels, 128);
@@ -1021,48 +1019,16 @@ void QwSession::logits_head(const DecPass& P) {
     T* last = d_last.as<T>();
     hipLaunchKernelGGL(qw_rmsnorm_kernel<T>, dim3((B + 3) / 4), dim3(256), 0, stream, x, d, B, d, final_norm, c.rms_eps, last, d, P.last_rows);
     GemmArgs g; g.A = last; g.lda = d; g.W = lm_head; g.ldw = d; g.M = B; g.N = vpad; g.K = d; g.out_f32 = d_logits.as<float>(); g.ld_out_f32 = vpad; gemm(g);
-    // heads: the prefill graphs select from the raw logits with an empty history; the decode graphs apply the penalty first
-    // (Shared_Merged.py merge_prefill_* / merge_decode_*)
-    const bool penalised = penalty_value != 1.0f && !sampling;
-    if (P.beam_src) {                                    // beam search ranks the rows' extensions itself
-    } else
-    if (penalised && P.step)
-      launch_apply_penalty(d_logits.as<float>(), vpad, B, d_save.as<int32_t>(), c.max_seq_len, d_nsaved.as<int32_t>(), penalty_range, penalty_value, stream, 1);
-    if (P.beam_src) {
-    } else if (sampling) {
-      SampleArgs sa;
-      sa.logits = d_logits.as<float>(); sa.ld = vpad; sa.rows = B; sa.n_valid = c.vocab; sa.extra = nullptr;
-      sa.save_ids = d_save.as<int32_t>(); sa.ld_save = c.max_seq_len; sa.n_saved = d_nsaved.as<int32_t>();
-      sa.temperature = temperature; sa.top_p = top_p; sa.repetition_penalty = samp_rep_penalty; sa.top_k = top_k;
-      sa.noise = noise_armed ? d_noise.as<float>() : nullptr; sa.seed = samp_seed; sa.next = d_next.as<int32_t>();
-      launch_sample_topk_topp(sa, stream);
-    } else {
-      launch_argmax_rows(d_logits.as<float>(), vpad, B, c.vocab, nullptr, d_next.as<int32_t>(), stream);
-    }
-    if (!P.beam_src && (penalised || sampling || track_history)) {        // GREEDY_SEARCH / the sampling head append their pick to save_id
-      launch_append_ids(d_next.as<int32_t>(), B, d_save.as<int32_t>(), c.max_seq_len, d_nsaved.as<int32_t>(), stream);
-      launch_add_scalar(d_nsaved.as<int32_t>(), 1, stream);
-    } }
+    // a beam pass ranks the rows' extensions itself
+    if (!P.beam_src) head.enqueue(d_logits.as<float>(), vpad, B, c.vocab, nullptr, P.step, d_next.as<int32_t>(), stream); }
   if (!P.hist_done) hipLaunchKernelGGL(qw_hist_add_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, P.hist ? P.hist : d_hist.as<int32_t>(), P.plan, B,
                                        P.step ? cfg.max_seq_len - 1 : INT32_MAX);
   HIP_CHECK(hipGetLastError());
 }
 
-template <typename T>
 void QwSession::finish(int B, int32_t* next_out, float* logits_out, bool sync) {
-  const auto& c = cfg;
-  if (taps_enabled) save_tap("logits", d_logits.ptr, B, c.vocab, vpad, 4);
-  const bool wait = next_out || logits_out || sync || prof.enabled;
-  if (wait) {
-    h_io.reserve((size_t)B * 4 + 64 + (logits_out ? (size_t)B * c.vocab * 4 : 0));
-    unsigned char* st = h_io.as<unsigned char>();
-    if (next_out) HIP_CHECK(hipMemcpyAsync(st, d_next.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-    if (logits_out)
-      HIP_CHECK(hipMemcpy2DAsync(st + (size_t)B * 4 + 64, (size_t)c.vocab * 4, d_logits.ptr, (size_t)vpad * 4, (size_t)c.vocab * 4, B, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    if (next_out) memcpy(next_out, st, (size_t)B * 4);
-    if (logits_out) memcpy(logits_out, st + (size_t)B * 4 + 64, (size_t)B * c.vocab * 4);
-  }
+  if (taps_enabled) save_tap("logits", d_logits.ptr, B, cfg.vocab, vpad, 4);
+  if (next_out || logits_out || sync || prof.enabled) download_step(h_io, d_next.ptr, d_logits.ptr, vpad, B, cfg.vocab, next_out, logits_out, stream);
   if (prof.enabled) prof.collect();
 }
 
@@ -1323,9 +1289,8 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
   d_last.reserve(pad_rows(B) * d * eT, stream);
   d_logits.reserve(pad_rows(B) * (size_t)vpad * 4, stream);
   d_next.reserve((size_t)std::max(B, 64) * 4, stream);
-  d_save.reserve((size_t)B * c.max_seq_len * 4, stream);
-  d_nsaved.reserve(64, stream);
-  HIP_CHECK(hipMemsetAsync(d_nsaved.ptr, 0, 4, stream));
+  head.reserve(B, stream);
+  head.restart(stream);
   { ProfScope ps(prof, "dec_embed", stream);
     hipLaunchKernelGGL(qw_gather_prompt_kernel<T>, dim3(Md), dim3(256), 0, stream, d_src, (const T*)embed, d_aud_out.as<float>(), d, PAD, d_x.as<float>(), (T*)nullptr); }
   if (taps_enabled) save_tap("prompt", d_x.ptr, rows_d, d, d, 4);
@@ -1353,8 +1318,8 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
     d_stepplan.reserve(sbytes, stream);
     HIP_CHECK(hipMemcpyAsync(d_stepplan.ptr, sh, sbytes, hipMemcpyHostToDevice, stream));
   }
-  noise_armed = false;
-  finish<T>(B, next_out, logits_out, true);
+  head.consumed();
+  finish(B, next_out, logits_out, true);
 }
 
 // Forced-aligner head (FORCED_ALIGNER_DECODER_MAIN :1104-1109 on the selected rows only): device-side row selection -> final RMSNorm of those
@@ -1454,15 +1419,16 @@ void QwSession::step(const int32_t* ids_host, int32_t* next_out, float* logits_o
     decoder_pass<T>(P);
   };
   // every step reads its position from the device-side history counters => one captured graph replays for all of them
-  const bool graphable = use_graph && !taps_enabled && !prof.enabled && !noise_armed;
+  const bool graphable = use_graph && !taps_enabled && !prof.enabled && !head.noise_armed;
   GraphKey key;
   for (const void* q : {d_x.ptr, d_x2.ptr, d_dh.ptr, d_qkv.ptr, d_q.ptr, d_dctx.ptr, d_xlo.ptr, d_x2lo.ptr, d_act.ptr, d_last.ptr, d_logits.ptr, d_next.ptr, d_kc.ptr,
-                        d_vc.ptr, d_kvtab.ptr, d_hist.ptr, d_stepplan.ptr, d_skws.ptr, d_save.ptr, (void*)stream, (void*)(uintptr_t)B, (void*)(uintptr_t)head_epoch})
+                        d_vc.ptr, d_kvtab.ptr, d_hist.ptr, d_stepplan.ptr, d_skws.ptr, (void*)stream, (void*)(uintptr_t)B})
     key.mix(q);
+  key.mix(head.epoch);
   dec_graph.run(stream, graphable, key.h, enqueue);
-  noise_armed = false;                                   // caller-supplied uniforms serve exactly one step
+  head.consumed();
   for (int b = 0; b < B; ++b) seq_len[b] = std::min(seq_len[b] + 1, c.max_seq_len);
-  finish<T>(B, next_out, logits_out, ids_host != nullptr);
+  finish(B, next_out, logits_out, ids_host != nullptr);
 }
 
 // Beam search after a prefill: every step runs the decoder over all B * beam hypothesis rows. The prompts stay where the prefill wrote
@@ -1477,7 +1443,7 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
   ASR_REQUIRE(beam >= 1 && beam <= BEAM_MAX, "qwen_beam_search: beam width %d outside 1..%d", beam, BEAM_MAX);
   ASR_REQUIRE(!no_fuse && (c.n_heads / c.n_kv_heads == 1 || c.n_heads / c.n_kv_heads == 2 || c.n_heads / c.n_kv_heads == 4),
               "qwen_beam_search: needs the fused decode attention kernel");
-  ASR_REQUIRE(!sampling && penalty_value == 1.0f, "qwen_beam_search: the penalty / sampling heads do not combine with beam search");
+  ASR_REQUIRE(head.plain(), "qwen_beam_search: the penalty / sampling heads do not combine with beam search");
   HIP_CHECK(hipSetDevice(device));
   const int B = batch, N = B * beam, KV = c.n_kv_heads, hd = c.d_head, d = c.d_model, H = c.n_heads, I = c.d_ffn, qkvn = (H + 2 * KV) * hd;
   const size_t eT = sizeof(T);
@@ -1488,31 +1454,10 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
   max_new = std::min(max_new, c.max_seq_len - max_len);  // positions (RoPE rows) end at max_seq_len
   const int Sb = round_up(max_new, 16), ld = Sb;         // generated slots per hypothesis row; the prompts stay in the prefill cache
   // ---- the first ranking reads the prefill logits; do it before any buffer grows
-  d_btopv.reserve((size_t)std::max(N, 64) * BEAM_MAX * 4, stream);
-  d_btopi.reserve((size_t)std::max(N, 64) * BEAM_MAX * 4, stream);
-  for (DeviceBuffer* q : {&d_bcum, &d_bfin, &d_blen, &d_bdone, &d_bhist, &d_bp0}) q->reserve((size_t)std::max(N, 64) * 4, stream);
-  for (int i = 0; i < 2; ++i) { d_bsrc[i].reserve((size_t)N * ld * 4, stream); d_btok[i].reserve((size_t)N * ld * 4, stream); }
-  d_bstop.reserve((size_t)std::max(n_stop, 16) * 4, stream);
-  if (n_stop) HIP_CHECK(hipMemcpyAsync(d_bstop.ptr, stop_ids, (size_t)n_stop * 4, hipMemcpyHostToDevice, stream));
-  HIP_CHECK(hipMemsetAsync(d_bdone.ptr, 0, (size_t)B * 4, stream));
-  HIP_CHECK(hipMemsetAsync(d_blen.ptr, 0, (size_t)N * 4, stream));
-  launch_beam_topk(d_logits.as<float>(), vpad, B, c.vocab, nullptr, beam, d_btopv.as<float>(), d_btopi.as<int32_t>(), stream);
-  DeviceBuffer& nxt = d_bnext;
-  nxt.reserve((size_t)std::max(N, 64) * 4, stream);
-  BeamArgs ba{};
-  ba.beam = beam; ba.K = beam; ba.ld = ld; ba.topv = d_btopv.as<float>(); ba.topi = d_btopi.as<int32_t>();
-  ba.cum = d_bcum.as<float>(); ba.fin = d_bfin.as<int32_t>(); ba.len = d_blen.as<int32_t>(); ba.done = d_bdone.as<int32_t>(); ba.next = nxt.as<int32_t>();
-  ba.stop = d_bstop.as<int32_t>(); ba.n_stop = n_stop;
-  int cur = 0;
-  auto select = [&](int first, int n_slots) {
-    ba.first = first; ba.n_slots = n_slots;
-    ba.src_in = d_bsrc[cur].as<int32_t>(); ba.tok_in = d_btok[cur].as<int32_t>();
-    ba.src_out = d_bsrc[cur ^ 1].as<int32_t>(); ba.tok_out = d_btok[cur ^ 1].as<int32_t>();
-    launch_beam_select(ba, B, stream);
-    cur ^= 1;
-  };
-  select(1, 0);
+  ranker.begin(B, beam, ld, stop_ids, n_stop, stream);
+  ranker.rank_first(d_logits.as<float>(), vpad, c.vocab, nullptr, stream);
   // ---- hypothesis rows: caches, counters, row buffers, the one-row-per-hypothesis plan
+  for (DeviceBuffer* q : {&d_bhist, &d_bp0}) q->reserve((size_t)std::max(N, 64) * 4, stream);
   d_bkc.reserve((size_t)c.n_layers * N * KV * Sb * hd * eT, stream);
   d_bvc.reserve((size_t)c.n_layers * N * KV * Sb * hd * eT, stream);
   hipLaunchKernelGGL(qw_beam_init_kernel, dim3((N + 63) / 64), dim3(64), 0, stream, d_hist.as<int32_t>(), B, beam, d_bhist.as<int32_t>(), d_bp0.as<int32_t>());
@@ -1536,36 +1481,19 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
   DecPass P;
   P.plan = dsp; P.row_seq = (const int32_t*)(dsp + N); P.row_t = P.row_seq + Mb; P.last_rows = P.row_t + Mb; P.rows = N; P.B = N; P.step = true;
   P.kc = d_bkc.ptr; P.vc = d_bvc.ptr; P.S = Sb; P.hist = d_bhist.as<int32_t>(); P.beam_p0 = d_bp0.as<int32_t>(); P.ld_src = ld; P.beam = beam;
-  h_ids.reserve((size_t)std::max(B, 64) * 4);
-  int32_t* h_done = h_ids.as<int32_t>();
-  for (int t = 0; t + 1 < max_new; ++t) {
-    HIP_CHECK(hipMemcpyAsync(h_done, d_bdone.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    bool all = true;
-    for (int b = 0; b < B; ++b) all = all && h_done[b] != 0;
-    if (all) break;
+  for (int t = 0; t + 1 < max_new && !ranker.all_done(stream); ++t) {
     { ProfScope ps(prof, "dec_embed", stream);
-      hipLaunchKernelGGL(qw_gather_prompt_kernel<T>, dim3(N), dim3(256), 0, stream, (const int32_t*)nxt.ptr, (const T*)embed, (const float*)nullptr, d,
+      hipLaunchKernelGGL(qw_gather_prompt_kernel<T>, dim3(N), dim3(256), 0, stream, (const int32_t*)ranker.next_ids(), (const T*)embed, (const float*)nullptr, d,
                          INT32_MIN, d_x.as<float>(), precision == ASR_PRECISION_BF16 ? d_xlo.as<T>() : (T*)nullptr); }
-    P.beam_src = d_bsrc[cur].as<int32_t>();
+    P.beam_src = ranker.ancestry();
     decoder_pass<T>(P);
     { ProfScope ps(prof, "beam_rank", stream);
-      launch_beam_topk(d_logits.as<float>(), vpad, N, c.vocab, nullptr, beam, d_btopv.as<float>(), d_btopi.as<int32_t>(), stream);
-      select(0, t + 1); }
+      ranker.enqueue_rank(d_logits.as<float>(), vpad, c.vocab, t + 1, stream); }
+    ranker.flip();
   }
   HIP_CHECK(hipGetLastError());
-  std::vector<int32_t> h_tok((size_t)N * ld), h_len(N);
-  std::vector<float> h_cum(N);
-  HIP_CHECK(hipMemcpyAsync(h_tok.data(), d_btok[cur].ptr, (size_t)N * ld * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync(h_len.data(), d_blen.ptr, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync(h_cum.data(), d_bcum.ptr, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipStreamSynchronize(stream));
+  ranker.download(tokens_out, out_stride, n_out, scores_out, stream);
   if (prof.enabled) prof.collect();
-  for (int n = 0; n < N; ++n) {
-    n_out[n] = h_len[n];
-    if (scores_out) scores_out[n] = h_cum[n];
-    for (int j = 0; j < h_len[n] && j < out_stride; ++j) tokens_out[(size_t)n * out_stride + j] = h_tok[(size_t)n * ld + j];
-  }
 }
 
 }  // namespace
@@ -1631,42 +1559,23 @@ extern "C" int asr_qwen_decode(asr_session* s, const int32_t* ids, int32_t* next
   });
 }
 
+// the decode-head entries: the checks and the state are TokenHead's (decode_head.h)
+static QwSession* qwen_session(asr_session* s, const char* who) {
+  ASR_REQUIRE(s && s->kind == 5, "%s: not a Qwen3-ASR session", who);
+  return static_cast<QwSession*>(s);
+}
+
 extern "C" int asr_qwen_set_penalty(asr_session* s, float repeat_penalty, int penalty_range) {
-  return asr_guard([&] {
-    ASR_REQUIRE(s && s->kind == 5, "qwen_set_penalty: not a Qwen3-ASR session");
-    ASR_REQUIRE(repeat_penalty > 0.0f && penalty_range >= 1 && penalty_range <= 64, "qwen_set_penalty: value %g range %d", repeat_penalty, penalty_range);
-    QwSession* q = static_cast<QwSession*>(s);
-    if (q->penalty_value != repeat_penalty || q->penalty_range != penalty_range) {
-      q->penalty_value = repeat_penalty;
-      q->penalty_range = penalty_range;
-      ++q->head_epoch;                     // the captured decode graph bakes the head in: re-capture
-    }
-  });
+  return asr_guard([&] { qwen_session(s, "qwen_set_penalty")->head.set_penalty(repeat_penalty, penalty_range, "qwen_set_penalty"); });
 }
 
 extern "C" int asr_qwen_track_history(asr_session* s, int enable) {
-  return asr_guard([&] {
-    ASR_REQUIRE(s && s->kind == 5, "qwen_track_history: not a Qwen3-ASR session");
-    QwSession* q = static_cast<QwSession*>(s);
-    if (q->track_history != (enable != 0)) {
-      q->track_history = enable != 0;
-      ++q->head_epoch;
-    }
-  });
+  return asr_guard([&] { qwen_session(s, "qwen_track_history")->head.set_track_history(enable != 0); });
 }
 
 extern "C" int asr_qwen_set_sampling(asr_session* s, int enable, float temperature, int top_k, float top_p, float repetition_penalty, uint64_t seed) {
   return asr_guard([&] {
-    ASR_REQUIRE(s && s->kind == 5, "qwen_set_sampling: not a Qwen3-ASR session");
-    QwSession* q = static_cast<QwSession*>(s);
-    if (enable) {
-      ASR_REQUIRE(temperature > 0.0f && top_k >= 1 && top_k <= 64 && top_p > 0.0f && repetition_penalty > 0.0f && q->cfg.max_seq_len <= 1024,
-                  "qwen_set_sampling: temperature %g top_k %d top_p %g penalty %g", temperature, top_k, top_p, repetition_penalty);
-      q->temperature = temperature; q->top_k = top_k; q->top_p = top_p; q->samp_rep_penalty = repetition_penalty; q->samp_seed = seed;
-    }
-    q->sampling = enable != 0;
-    q->noise_armed = false;
-    ++q->head_epoch;
+    qwen_session(s, "qwen_set_sampling")->head.set_sampling(enable != 0, temperature, top_k, top_p, repetition_penalty, seed, "qwen_set_sampling");
   });
 }
 
@@ -1674,12 +1583,9 @@ extern "C" int asr_qwen_set_sampling_noise(asr_session* s, const float* uniforms
   return asr_guard([&] {
     ASR_REQUIRE(s && s->kind == 5 && uniforms && count > 0, "qwen_set_sampling_noise: bad argument");
     QwSession* q = static_cast<QwSession*>(s);
-    ASR_REQUIRE(q->sampling && count % q->top_k == 0, "qwen_set_sampling_noise: expects batch x top_k uniforms for the next step");
+    ASR_REQUIRE(q->head.sampling && count % q->head.top_k == 0, "qwen_set_sampling_noise: expects batch x top_k uniforms for the next step");
     HIP_CHECK(hipSetDevice(q->device));
-    q->d_noise.reserve((size_t)count * 4, q->stream);
-    HIP_CHECK(hipMemcpyAsync(q->d_noise.ptr, uniforms, (size_t)count * 4, hipMemcpyHostToDevice, q->stream));
-    HIP_CHECK(hipStreamSynchronize(q->stream));
-    q->noise_armed = true;
+    q->head.arm_noise(uniforms, count, q->stream);
   });
 }
 

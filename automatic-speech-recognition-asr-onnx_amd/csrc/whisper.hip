@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "../../include/asr_mi355x.h"
+#include "decode_head.h"
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
@@ -43,8 +44,6 @@ struct BeamStep {
   const int32_t* src = nullptr; int ld_src = 0;
   int32_t* hist = nullptr;             // the rows' position (all rows stand at the same one), advanced by the pass
   float* logits = nullptr;             // [rows][vpad]
-  float* topv = nullptr; int32_t* topi = nullptr;
-  BeamArgs ba;
 };
 
 struct EncLayer { const void *wqkv, *wo, *w1, *w2; const float *bqkv, *bo, *b1, *b2; };
@@ -79,17 +78,8 @@ struct WhSession : asr_session {
   bool kv_paged = true;
   int kv_gens = 0, kv_batch = 0, kv_shuffle = 0;      // generations allocated, the batch they were cut for; kv_shuffle (tests): permute the page ids inside every generation
   void ensure_kv_pages(int B, int positions, size_t elem_bytes);
-  DeviceBuffer d_save, d_nsaved;       // penalty-greedy: generated ids per sequence [B][max_target_positions] + their count
-  bool sampling = false;               // TOPK_TOPP_SAMPLING head (USE_SAMPLING, Inference_Whisper_ONNX.py:71-75)
-  float temperature = 0.8f, top_p = 0.95f, samp_rep_penalty = 1.0f;
-  int top_k = 10;
-  uint64_t samp_seed = 0;
+  TokenHead head;                      // arg-max / penalty-greedy / sampling (Inference_Whisper_ONNX.py:71-78) + the history of generated ids [B][max_target_positions]
   DeviceBuffer d_nsp;                  // no-speech probabilities of the last prefill
-  DeviceBuffer d_noise;                // caller-supplied uniforms [B][top_k] for the next step (parity tests); consumed once
-  bool noise_armed = false;
-  float penalty_value = 1.0f;          // 1.0 = plain greedy (REPEAT_PENALTY, Inference_Whisper_ONNX.py:78)
-  bool track_history = false;          // GREEDY_SEARCH graphs append every pick to save_id even while the penalty value is 1.0
-  int penalty_range = 20;
   bool use_graph = true;
   bool use_decode_gemm = true;         // ASR_DECODE_GEMM=0: decode steps through the generic weight-streaming GEMM + LayerNorm prologues
   DeviceBuffer d_colsum, d_dlo;        // column sums of the LayerNorm-folded decoder projections; bf16 copies of the decoder's residual rows
@@ -113,13 +103,13 @@ struct WhSession : asr_session {
   StepGraph dec_graph;                 // the whole single-token step
   StepGraph beam_graph[2];             // the beam-search step, one per ancestry-table parity
   // Beam search (asr_whisper_beam_search): hypothesis rows b * beam + r, each with its own self-K/V extent of S = prompt + max_new - 1 slots in d_bext
-  // [layer][row][K | V][head][S][64] (large-v3, 160 rows x 447 slots: 11.7 GB; kept for the next search), ancestry / token tables (double-buffered), ranking
-  // state and logits of its own: the session's pages, block table, history, ids and logits are left as the prefill left them.
-  DeviceBuffer d_bext, d_bhist, d_bsrc[2], d_btok[2], d_bcum, d_bfin, d_blen, d_bdone, d_btopv, d_btopi, d_bstop, d_bnext, d_blogits;
+  // [layer][row][K | V][head][S][64] (large-v3, 160 rows x 447 slots: 11.7 GB; kept for the next search), a position counter and logits of its own, ranking
+  // state and ancestry / token tables in `ranker`: the session's pages, block table, history, ids and logits are left as the prefill left them.
+  DeviceBuffer d_bext, d_bhist, d_blogits;
+  BeamRanker ranker;
   bool after_prefill = false;          // the last call on the session was a prefill (or a beam search, which leaves its state as it was)
   uint64_t ws_epoch = 1;
   PinnedBuffer h_plan, h_io;
-  PinnedBuffer h_beam;                 // beam search's own pinned staging: [0] eos id, [1] prompt length, [16 ..) done flags
 
   void init();
   DeviceBuffer d_skws, d_skcnt;        // split-K workspace + tickets of the skinny / decode GEMM (per session: sessions may run concurrently)
@@ -146,6 +136,7 @@ void WhSession::init() {
   ASR_REQUIRE(c.n_mels % 16 == 0 && (3 * c.n_mels) % 64 == 0, "whisper: n_mels must make 3*n_mels a multiple of 64");
   ASR_REQUIRE(c.max_target_positions <= 1536, "whisper: decoder context too long for the attention kernel");
   vpad = round_up(c.vocab, 128);
+  head.init(c.max_target_positions, 0, 20, 512);
   n_bin_tiles = (c.nfft / 2 + 1 + 15) / 16;
   n_kchunks = c.nfft / 16;
   act = c.gelu_tanh ? ACT_GELU_TANH : ACT_GELU_ERF;
@@ -654,30 +645,12 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
     gemm(g);
     if (bs) {                              // rank the rows' extensions; the select pass writes the ids of the next step and the ancestry of this one
       ProfScope pr(prof, "beam_rank", stream);
-      launch_beam_topk(lg, vpad, R, c.vocab, nullptr, bs->beam, bs->topv, bs->topi, stream);
-      launch_beam_select(bs->ba, B, stream);
+      ranker.enqueue_rank(lg, vpad, c.vocab, 0, stream);
       launch_add_scalar(bs->hist, 1, stream);
       return;
     }
-    const bool penalised = penalty_value != 1.0f && !sampling;
-    if (penalised && !is_prefill)          // APPLY_PENALTY over the saved ids; the history is empty at the prefill (:312-325)
-      launch_apply_penalty(d_logits.as<float>(), vpad, B, d_save.as<int32_t>(), c.max_target_positions, d_nsaved.as<int32_t>(),
-                           penalty_range, penalty_value, stream);
-    if (sampling) {                        // TOPK_TOPP_SAMPLING (:263-308): BEGIN_SUPPRESS bias first, history = every sampled id
-      SampleArgs sa;
-      sa.logits = d_logits.as<float>(); sa.ld = vpad; sa.rows = B; sa.n_valid = c.vocab; sa.extra = is_prefill ? begin : nullptr;
-      sa.save_ids = d_save.as<int32_t>(); sa.ld_save = c.max_target_positions; sa.n_saved = d_nsaved.as<int32_t>();
-      sa.temperature = temperature; sa.top_p = top_p; sa.repetition_penalty = samp_rep_penalty; sa.top_k = top_k;
-      sa.noise = noise_armed ? d_noise.as<float>() : nullptr; sa.seed = samp_seed; sa.next = d_next.as<int32_t>();
-      launch_sample_topk_topp(sa, stream);
-    } else {
-      // BEGIN_SUPPRESS (-inf on begin_suppress_tokens) applies to the head after a prefill only (:228-240)
-      launch_argmax_rows(d_logits.as<float>(), vpad, B, c.vocab, is_prefill ? begin : nullptr, d_next.as<int32_t>(), stream);
-    }
-    if (penalised || sampling || track_history) {   // GREEDY_SEARCH / the sampling head append their pick to the history (:243-251,306)
-      launch_append_ids(d_next.as<int32_t>(), B, d_save.as<int32_t>(), c.max_target_positions, d_nsaved.as<int32_t>(), stream);
-      launch_add_scalar(d_nsaved.as<int32_t>(), 1, stream);
-    }
+    // BEGIN_SUPPRESS (-inf on begin_suppress_tokens) applies to the head after a prefill only (:228-240); the history is empty there (:312-325)
+    head.enqueue(d_logits.as<float>(), vpad, B, c.vocab, is_prefill ? begin : nullptr, !is_prefill, d_next.as<int32_t>(), stream);
     launch_add_scalar(d_hist.as<int32_t>(), n, stream);
   }
 }
@@ -730,8 +703,7 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
   grow(d_ids, (size_t)B * 8 * 4);
   grow(d_next, (size_t)B * 4);
   grow(d_hist, 256);
-  grow(d_nsaved, 256);
-  grow(d_save, (size_t)B * c.max_target_positions * 4);
+  head.reserve(B, stream);
   grow(d_logits, (size_t)Bp * vpad * 4);
   grow(d_dx, (size_t)3 * Rp * d * 4);                  // three f32 residual-stream buffers
   if (precision == ASR_PRECISION_BF16) grow(d_dlo, (size_t)3 * Rp * d * 2);     // ... and their bf16 copies (operands of the LayerNorm-folded projections)
@@ -752,25 +724,17 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
   }
   if (is_prefill) {
     HIP_CHECK(hipMemsetAsync(d_hist.ptr, 0, 4, stream));
-    HIP_CHECK(hipMemsetAsync(d_nsaved.ptr, 0, 4, stream));
+    head.restart(stream);
   }
   // single-token steps fed from the device are position independent => one graph for all of them
-  const bool graphable = use_graph && !ids_host && n == 1 && !taps_enabled && !prof.enabled && !noise_armed;
-  const uint64_t key = GraphKey().mix((uint64_t)B).mix((uint64_t)Mpad).mix(ws_epoch).mix(stream).h;
+  const bool graphable = use_graph && !ids_host && n == 1 && !taps_enabled && !prof.enabled && !head.noise_armed;
+  const uint64_t key = GraphKey().mix((uint64_t)B).mix((uint64_t)Mpad).mix(ws_epoch).mix(head.epoch).mix(stream).h;
   dec_graph.run(stream, graphable, key, [&] { enqueue_step<T>(ids_dev, n, is_prefill, true); });
   hist += n;
-  noise_armed = false;                   // caller-supplied uniforms serve exactly one step
+  head.consumed();
   if (taps_enabled) save_tap("logits", d_logits.ptr, B, c.vocab, vpad, 4);
   if (next_out || logits_out) {
-    h_io.reserve((size_t)B * 4 + (logits_out ? (size_t)B * c.vocab * 4 : 0));
-    unsigned char* st = h_io.as<unsigned char>();
-    if (next_out) HIP_CHECK(hipMemcpyAsync(st, d_next.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-    if (logits_out)
-      HIP_CHECK(hipMemcpy2DAsync(st + (size_t)B * 4, (size_t)c.vocab * 4, d_logits.ptr, (size_t)vpad * 4, (size_t)c.vocab * 4, B,
-                                 hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    if (next_out) memcpy(next_out, st, (size_t)B * 4);
-    if (logits_out) memcpy(logits_out, st + (size_t)B * 4, (size_t)B * c.vocab * 4);
+    download_step(h_io, d_next.ptr, d_logits.ptr, vpad, B, c.vocab, next_out, logits_out, stream);
     if (prof.enabled) prof.collect();
   }
 }
@@ -786,50 +750,27 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   const auto& c = cfg;
   ASR_REQUIRE(after_prefill && batch > 0 && hist > 0 && d_logits.ptr, "whisper_beam_search: prefill first");
   ASR_REQUIRE(beam >= 1 && beam <= BEAM_MAX, "whisper_beam_search: beam width %d outside 1..%d", beam, BEAM_MAX);
-  ASR_REQUIRE(!sampling && penalty_value == 1.0f, "whisper_beam_search: the penalty / sampling heads do not combine with beam search");
+  ASR_REQUIRE(head.plain(), "whisper_beam_search: the penalty / sampling heads do not combine with beam search");
   ASR_REQUIRE(hist + max_new <= c.max_target_positions, "whisper_beam_search: %d prompt + %d new positions exceed max_target_positions %d", hist, max_new,
               c.max_target_positions);
   HIP_CHECK(hipSetDevice(device));
   const int B = batch, N = B * beam, p0 = hist, d = c.d_model, dff = c.d_ffn, Ld = c.n_dec_layers, H = c.n_heads;
   const int S = p0 + max_new - 1, ld = max_new;           // extent slots (positions ever written), stride of the ancestry / token tables
-  const int Rp = round_up(N, 128), Nn = std::max(N, 64);
+  const int Rp = round_up(N, 128);
   const size_t eT = sizeof(T);
-  auto grow = [&](DeviceBuffer& buf, size_t bytes) { void* before = buf.ptr; buf.reserve(bytes, stream); if (buf.ptr != before) ++ws_epoch; };
-  grow(d_btopv, (size_t)Nn * BEAM_MAX * 4); grow(d_btopi, (size_t)Nn * BEAM_MAX * 4);
-  for (DeviceBuffer* q : {&d_bcum, &d_bfin, &d_blen, &d_bdone, &d_bnext}) grow(*q, (size_t)Nn * 4);
-  grow(d_bhist, 256); grow(d_bstop, 256);
-  for (int i = 0; i < 2; ++i) { grow(d_bsrc[i], (size_t)N * ld * 4); grow(d_btok[i], (size_t)N * ld * 4); }
+  auto grow = [&](DeviceBuffer& buf, size_t bytes) { if (reserve_moved(buf, bytes, stream)) ++ws_epoch; };
+  grow(d_bhist, 256);
   grow(d_bext, (size_t)Ld * N * 2 * H * S * 64 * eT);
   grow(d_blogits, (size_t)Rp * vpad * 4);
   grow(d_dx, (size_t)3 * Rp * d * 4);
   if (precision == ASR_PRECISION_BF16) grow(d_dlo, (size_t)3 * Rp * d * 2);
   grow(d_dqkv, (size_t)Rp * (3 * d + d + d + dff + d) * eT + (size_t)Rp * d * eT);
   const int n_stop = eos_id >= 0 ? 1 : 0;
-  // a prefill called with null outputs may still be copying from the shared staging buffer: the search starts behind it and stages through its own
-  HIP_CHECK(hipStreamSynchronize(stream));
-  const size_t stage_bytes = (size_t)(16 + std::max(B, 64)) * 4;
-  h_beam.reserve(stage_bytes);
-  int32_t* hs = h_beam.as<int32_t>();
-  hs[0] = eos_id; hs[1] = p0;
-  HIP_CHECK(hipMemcpyAsync(d_bstop.ptr, hs, 4, hipMemcpyHostToDevice, stream));
-  HIP_CHECK(hipMemcpyAsync(d_bhist.ptr, hs + 1, 4, hipMemcpyHostToDevice, stream));
-  HIP_CHECK(hipMemsetAsync(d_bdone.ptr, 0, (size_t)B * 4, stream));
-  HIP_CHECK(hipMemsetAsync(d_blen.ptr, 0, (size_t)N * 4, stream));
+  ranker.begin(B, beam, ld, &eos_id, n_stop, stream);
+  HIP_CHECK(hipMemcpyAsync(d_bhist.ptr, d_hist.ptr, 4, hipMemcpyDeviceToDevice, stream));      // the rows' position: the prompt length p0 the prefill left
   // ---- first ranking: the prefill's logits (B rows, left in place) + BEGIN_SUPPRESS, as the arg-max head after a prefill
-  launch_beam_topk(d_logits.as<float>(), vpad, B, c.vocab, begin, beam, d_btopv.as<float>(), d_btopi.as<int32_t>(), stream);
-  BeamArgs ba{};
-  ba.beam = beam; ba.K = beam; ba.ld = ld; ba.topv = d_btopv.as<float>(); ba.topi = d_btopi.as<int32_t>();
-  ba.cum = d_bcum.as<float>(); ba.fin = d_bfin.as<int32_t>(); ba.len = d_blen.as<int32_t>(); ba.done = d_bdone.as<int32_t>(); ba.next = d_bnext.as<int32_t>();
-  ba.stop = d_bstop.as<int32_t>(); ba.n_stop = n_stop;
-  int cur = 0;
-  auto tables = [&](BeamArgs& a) {
-    a.src_in = d_bsrc[cur].as<int32_t>(); a.tok_in = d_btok[cur].as<int32_t>();
-    a.src_out = d_bsrc[cur ^ 1].as<int32_t>(); a.tok_out = d_btok[cur ^ 1].as<int32_t>();
-  };
-  ba.first = 1; ba.n_slots = 0;
-  tables(ba);
-  launch_beam_select(ba, B, stream);
-  cur ^= 1;
+  ranker.rank_first(d_logits.as<float>(), vpad, c.vocab, begin, stream);
+  ranker.slots_dev = d_bhist.as<int32_t>(); ranker.slots_off = 1 - p0;   // the pass at position p fills generated slot p - p0
   // ---- the prompt into every row's extent
   if (max_new > 1) {
     const int P = (c.max_target_positions + KV_PAGE - 1) / KV_PAGE;
@@ -840,37 +781,19 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   }
   BeamStep bs;
   bs.beam = beam; bs.p0 = p0; bs.S = S; bs.ld_src = ld; bs.hist = d_bhist.as<int32_t>(); bs.logits = d_blogits.as<float>();
-  bs.topv = d_btopv.as<float>(); bs.topi = d_btopi.as<int32_t>();
-  bs.ba = ba; bs.ba.first = 0; bs.ba.slots_dev = d_bhist.as<int32_t>(); bs.ba.slots_off = 1 - p0;   // the pass at position p fills generated slot p - p0
   const bool graphable = use_graph && !taps_enabled && !prof.enabled;
   GraphKey key;                                             // everything the captured step bakes in
-  for (uint64_t v : {(uint64_t)B, (uint64_t)beam, (uint64_t)S, (uint64_t)p0, (uint64_t)ld, (uint64_t)n_stop, (uint64_t)Mpad, ws_epoch, (uint64_t)(uintptr_t)stream})
+  for (uint64_t v : {(uint64_t)B, (uint64_t)beam, (uint64_t)S, (uint64_t)p0, (uint64_t)ld, (uint64_t)n_stop, (uint64_t)Mpad, ws_epoch, ranker.epoch,
+                     (uint64_t)(uintptr_t)stream})
     key.mix(v);
-  int32_t* h_done = hs + 16;
-  for (int t = 0; t + 1 < max_new; ++t) {
-    HIP_CHECK(hipMemcpyAsync(h_done, d_bdone.ptr, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    bool all = true;
-    for (int b = 0; b < B; ++b) all = all && h_done[b] != 0;
-    if (all) break;
-    bs.src = d_bsrc[cur].as<int32_t>();
-    tables(bs.ba);
-    beam_graph[cur].run(stream, graphable, key.h, [&] { enqueue_step<T>(d_bnext.as<int32_t>(), beam, false, true, &bs); });
-    cur ^= 1;
+  for (int t = 0; t + 1 < max_new && !ranker.all_done(stream); ++t) {
+    bs.src = ranker.ancestry();
+    beam_graph[ranker.cur].run(stream, graphable, key.h, [&] { enqueue_step<T>(ranker.next_ids(), beam, false, true, &bs); });
+    ranker.flip();
   }
   HIP_CHECK(hipGetLastError());
-  std::vector<int32_t> h_tok((size_t)N * ld), h_len(N);
-  std::vector<float> h_cum(N);
-  HIP_CHECK(hipMemcpyAsync(h_tok.data(), d_btok[cur].ptr, (size_t)N * ld * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync(h_len.data(), d_blen.ptr, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync(h_cum.data(), d_bcum.ptr, (size_t)N * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipStreamSynchronize(stream));
+  ranker.download(tokens_out, max_new, n_out, scores_out, stream);
   if (prof.enabled) prof.collect();
-  for (int r = 0; r < N; ++r) {
-    n_out[r] = h_len[r];
-    if (scores_out) scores_out[r] = h_cum[r];
-    for (int j = 0; j < h_len[r] && j < max_new; ++j) tokens_out[(size_t)r * max_new + j] = h_tok[(size_t)r * ld + j];
-  }
 }
 
 }  // namespace
@@ -948,17 +871,14 @@ extern "C" int asr_whisper_decode(asr_session* s, const int32_t* ids, int32_t* n
   });
 }
 
+// the decode-head entries: the checks and the state are TokenHead's (decode_head.h)
+static WhSession* whisper_session(asr_session* s, const char* who) {
+  ASR_REQUIRE(s && s->kind == 2, "%s: not a Whisper session", who);
+  return static_cast<WhSession*>(s);
+}
+
 extern "C" int asr_whisper_set_penalty(asr_session* s, float repeat_penalty, int penalty_range) {
-  return asr_guard([&] {
-    ASR_REQUIRE(s && s->kind == 2, "whisper_set_penalty: not a Whisper session");
-    ASR_REQUIRE(repeat_penalty > 0.0f && penalty_range >= 1 && penalty_range <= 64, "whisper_set_penalty: value %g range %d", repeat_penalty, penalty_range);
-    WhSession* w = static_cast<WhSession*>(s);
-    if (w->penalty_value != repeat_penalty || w->penalty_range != penalty_range) {
-      w->penalty_value = repeat_penalty;
-      w->penalty_range = penalty_range;
-      ++w->ws_epoch;                       // the captured decode graph bakes the head in: re-capture
-    }
-  });
+  return asr_guard([&] { whisper_session(s, "whisper_set_penalty")->head.set_penalty(repeat_penalty, penalty_range, "whisper_set_penalty"); });
 }
 
 extern "C" int asr_whisper_no_speech_prob(asr_session* s, int no_speech_id, float* prob_out) {
@@ -999,29 +919,13 @@ extern "C" int asr_whisper_fp8_stats(asr_session* s, uint64_t stats[2]) {
 }
 
 extern "C" int asr_whisper_track_history(asr_session* s, int enable) {
-  return asr_guard([&] {
-    ASR_REQUIRE(s && s->kind == 2, "whisper_track_history: not a Whisper session");
-    WhSession* w = static_cast<WhSession*>(s);
-    if (w->track_history != (enable != 0)) {
-      w->track_history = enable != 0;
-      ++w->ws_epoch;                       // the captured decode graph bakes the head in: re-capture
-    }
-  });
+  return asr_guard([&] { whisper_session(s, "whisper_track_history")->head.set_track_history(enable != 0); });
 }
 
 extern "C" int asr_whisper_set_sampling(asr_session* s, int enable, float temperature, int top_k, float top_p,
                                         float repetition_penalty, uint64_t seed) {
   return asr_guard([&] {
-    ASR_REQUIRE(s && s->kind == 2, "whisper_set_sampling: not a Whisper session");
-    WhSession* w = static_cast<WhSession*>(s);
-    if (enable) {
-      ASR_REQUIRE(temperature > 0.0f && top_k >= 1 && top_k <= 64 && top_p > 0.0f && repetition_penalty > 0.0f && w->cfg.max_target_positions <= 512,
-                  "whisper_set_sampling: temperature %g top_k %d top_p %g penalty %g", temperature, top_k, top_p, repetition_penalty);
-      w->temperature = temperature; w->top_k = top_k; w->top_p = top_p; w->samp_rep_penalty = repetition_penalty; w->samp_seed = seed;
-    }
-    w->sampling = enable != 0;
-    w->noise_armed = false;
-    ++w->ws_epoch;                         // the captured decode graph bakes the head in: re-capture
+    whisper_session(s, "whisper_set_sampling")->head.set_sampling(enable != 0, temperature, top_k, top_p, repetition_penalty, seed, "whisper_set_sampling");
   });
 }
 
@@ -1029,13 +933,10 @@ extern "C" int asr_whisper_set_sampling_noise(asr_session* s, const float* unifo
   return asr_guard([&] {
     ASR_REQUIRE(s && s->kind == 2 && uniforms, "whisper_set_sampling_noise: bad argument");
     WhSession* w = static_cast<WhSession*>(s);
-    ASR_REQUIRE(w->sampling && w->batch > 0 && count == w->batch * w->top_k, "whisper_set_sampling_noise: expects batch x top_k = %d uniforms for the next step",
-                w->batch * w->top_k);
+    ASR_REQUIRE(w->head.sampling && w->batch > 0 && count == w->batch * w->head.top_k, "whisper_set_sampling_noise: expects batch x top_k = %d uniforms for the next step",
+                w->batch * w->head.top_k);
     HIP_CHECK(hipSetDevice(w->device));
-    w->d_noise.reserve((size_t)count * 4, w->stream);
-    HIP_CHECK(hipMemcpyAsync(w->d_noise.ptr, uniforms, (size_t)count * 4, hipMemcpyHostToDevice, w->stream));
-    HIP_CHECK(hipStreamSynchronize(w->stream));
-    w->noise_armed = true;
+    w->head.arm_noise(uniforms, count, w->stream);
   });
 }
 

@@ -286,7 +286,37 @@ def whisper_config_c(cfg, gelu_tanh: bool = False) -> _lib.WhisperConfigC:
     return c
 
 
-class WhisperSession(_Session):
+def _token_head(prefix: str, default_range: int, penalty_doc: str):
+    """The four decode-head methods of a decoder family, over its asr_<prefix>_* entries (csrc/decode_head.h holds the one head behind them)."""
+
+    def entry(name):
+        return getattr(_lib.load(), f"asr_{prefix}_{name}")
+
+    class TokenHeadMixin:
+        def set_penalty(self, repeat_penalty: float = 1.0, penalty_range: int = default_range):
+            _lib.check(entry("set_penalty")(self._h, C.c_float(repeat_penalty), int(penalty_range)))
+
+        def track_history(self, enable: bool):
+            """Append every pick to the device-side id history whatever the penalty value is (what the penalty-greedy graphs do, also at 1.0)."""
+            _lib.check(entry("track_history")(self._h, int(enable)))
+
+        def set_sampling(self, enable: bool, temperature: float = 0.8, top_k: int = 10, top_p: float = 0.95,
+                         repetition_penalty: float = 1.0, seed: int = 0):
+            """TOPK_TOPP_SAMPLING head (USE_SAMPLING in the reference host); enable=False restores arg-max / penalty-greedy."""
+            _lib.check(entry("set_sampling")(self._h, int(enable), C.c_float(temperature), int(top_k), C.c_float(top_p),
+                                             C.c_float(repetition_penalty), C.c_uint64(seed)))
+
+        def set_sampling_noise(self, uniforms):
+            """Parity hook: uniforms [batch, top_k] for the next prefill / decode step (otherwise the device generator is used)."""
+            u = _f32(uniforms).reshape(-1)
+            _lib.check(entry("set_sampling_noise")(self._h, _fp(u), u.size))
+
+    TokenHeadMixin.set_penalty.__doc__ = penalty_doc
+    return TokenHeadMixin
+
+
+class WhisperSession(_token_head("whisper", 20, "Decode head: 1.0 = plain arg-max; else penalty-greedy (APPLY_PENALTY + GREEDY_SEARCH, the reference host's default)."),
+                     _Session):
     """HIP replacement of the merged Whisper graphs (encoder + KV-cache decoder + greedy heads)."""
 
     def __init__(self, cfg, arena, precision: int = PRECISION_BF16, device_id: int = 0, gelu_tanh: bool = False,
@@ -379,30 +409,11 @@ class WhisperSession(_Session):
         _lib.check(_lib.load().asr_whisper_beam_search(self._h, int(beam), int(max_new), int(eos_id), _ip(tok), _ip(n), _fp(score)))
         return [[(tok[b, r, :n[b, r]].copy(), float(score[b, r])) for r in range(beam)] for b in range(self.batch)]
 
-    def set_penalty(self, repeat_penalty: float = 1.0, penalty_range: int = 20):
-        """Decode head: 1.0 = plain arg-max; else penalty-greedy (APPLY_PENALTY + GREEDY_SEARCH, the reference host's default)."""
-        _lib.check(_lib.load().asr_whisper_set_penalty(self._h, C.c_float(repeat_penalty), int(penalty_range)))
-
     def no_speech_prob(self, no_speech_id: int | None = None) -> np.ndarray:
         """NO_SPEECH_DETECTION on the device-resident logits of the last prefill (the probe): (B,) probabilities."""
         out = np.zeros(self.batch, dtype=np.float32)
         _lib.check(_lib.load().asr_whisper_no_speech_prob(self._h, int(self.cfg.no_speech_id if no_speech_id is None else no_speech_id), _fp(out)))
         return out
-
-    def track_history(self, enable: bool):
-        """Append every pick to the device-side id history even while the penalty value is 1.0 (what the *PenaltyGreedy graphs do)."""
-        _lib.check(_lib.load().asr_whisper_track_history(self._h, int(enable)))
-
-    def set_sampling(self, enable: bool, temperature: float = 0.8, top_k: int = 10, top_p: float = 0.95,
-                     repetition_penalty: float = 1.0, seed: int = 0):
-        """TOPK_TOPP_SAMPLING head (USE_SAMPLING in the reference host); enable=False restores arg-max / penalty-greedy."""
-        _lib.check(_lib.load().asr_whisper_set_sampling(self._h, int(enable), C.c_float(temperature), int(top_k), C.c_float(top_p),
-                                                        C.c_float(repetition_penalty), C.c_uint64(seed)))
-
-    def set_sampling_noise(self, uniforms):
-        """Parity hook: uniforms [batch, top_k] for the next prefill / decode step (otherwise the device generator is used)."""
-        u = _f32(uniforms).reshape(-1)
-        _lib.check(_lib.load().asr_whisper_set_sampling_noise(self._h, _fp(u), u.size))
 
     def cross_kv(self, lengths_pos: Sequence[int]):
         """Debug: (K, V) per utterance as (L, H, T, 64) arrays from the 'cross' tap (f32 mode)."""
@@ -542,7 +553,8 @@ class ParaformerStreamSession(_Session):
 
 
 # =============================================================================== Qwen3-ASR
-class QwenAsrSession(_Session):
+class QwenAsrSession(_token_head("qwen", 10, "Decode head: 1.0 = plain arg-max; else penalty-greedy (the reference host's default is 0.8 over the last 10 ids)."),
+                     _Session):
     """HIP replacement of the merged Qwen3-ASR graphs (audio encoder + prompt assembly + Qwen3 decoder prefill / decode + arg-max;
     Qwen_ASR/Inference_Qwen_ASR_ONNX.py:424-760 drives them)."""
 
@@ -616,23 +628,6 @@ class QwenAsrSession(_Session):
         idp = _ip(np.ascontiguousarray(ids, dtype=np.int32)) if ids is not None else None
         _lib.check(_lib.load().asr_qwen_decode(self._h, idp, _ip(nxt) if nxt is not None else None, _fp(logits)))
         return nxt, logits
-
-    def set_penalty(self, repeat_penalty: float = 1.0, penalty_range: int = 10):
-        """Decode head: 1.0 = plain arg-max; else penalty-greedy (the reference host's default is 0.8 over the last 10 ids)."""
-        _lib.check(_lib.load().asr_qwen_set_penalty(self._h, C.c_float(repeat_penalty), int(penalty_range)))
-
-    def track_history(self, enable: bool):
-        """Append every pick to the device-side id history whatever the penalty value is (what the *_Penalty_Greedy graphs do)."""
-        _lib.check(_lib.load().asr_qwen_track_history(self._h, int(enable)))
-
-    def set_sampling(self, enable: bool, temperature: float = 0.8, top_k: int = 10, top_p: float = 0.95, repetition_penalty: float = 1.0, seed: int = 0):
-        _lib.check(_lib.load().asr_qwen_set_sampling(self._h, int(enable), C.c_float(temperature), int(top_k), C.c_float(top_p),
-                                                     C.c_float(repetition_penalty), C.c_uint64(seed)))
-
-    def set_sampling_noise(self, uniforms):
-        """Parity hook: uniforms [batch, top_k] for the next prefill / decode step (otherwise the device generator is used)."""
-        u = _f32(uniforms).reshape(-1)
-        _lib.check(_lib.load().asr_qwen_set_sampling_noise(self._h, _fp(u), u.size))
 
     def audio_tokens(self, n_samples: int) -> int:
         """_get_feat_extract_output_lengths (Export_Qwen_ASR.py:519-527) of a clip's mel frames."""

@@ -58,6 +58,30 @@ def check_audio_type(audio: "OrtValue", expected: np.dtype, meaning: str) -> Non
         raise ValueError(f"audio must be {_ORT_TYPES[expected]} {meaning}, got {_ORT_TYPES.get(np.dtype(audio._dtype), str(audio._dtype))}")
 
 
+SAMPLING_INPUTS = ("sampling_temperature", "sampling_top_k", "sampling_top_p", "sampling_repetition_penalty")
+
+
+def configure_head(graph, feeds, is_decode: bool, default_range: int) -> None:
+    """Bring the native session's decode head in line with a Whisper / Qwen3-ASR graph's strategy and the control scalars bound to this run.
+    `graph` has .strategy and the shared state .sh (.native: the session, .head: what is configured now)."""
+    sh, n = graph.sh, graph.sh.native
+    value, rng, samp = 1.0, default_range, None
+    if graph.strategy == "penalty_greedy" and is_decode:
+        value = float(np.asarray(feeds["penalty_penalty_value"].numpy()).reshape(-1)[0])
+        rng = int(np.asarray(feeds["penalty_penalty_range"].numpy()).reshape(-1)[0])
+    if graph.strategy == "sampling":
+        samp = tuple(float(np.asarray(feeds[k].numpy()).reshape(-1)[0]) for k in SAMPLING_INPUTS)
+    head = (graph.strategy, value, rng, samp)
+    if head == sh.head:
+        return
+    n.set_sampling(False)
+    n.track_history(graph.strategy == "penalty_greedy")
+    n.set_penalty(value, min(max(rng, 1), 64))
+    if samp is not None:
+        n.set_sampling(True, samp[0], int(samp[1]), samp[2], samp[3], seed=0)
+    sh.head = head
+
+
 def save_model(path: str, kind: str, config: dict | None, arena: np.ndarray | None, metadata: dict[str, str],
                precision: int = 0, input_audio_dtype: str | None = None) -> None:
     head = {"kind": kind, "config": config, "metadata": {str(k): str(v) for k, v in metadata.items()}, "precision": int(precision)}

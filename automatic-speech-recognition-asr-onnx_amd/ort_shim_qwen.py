@@ -20,6 +20,7 @@ import os
 import numpy as np
 
 from .config import QwenAsrConfig
+from .ort_shim import SAMPLING_INPUTS, configure_head
 
 STRATEGIES = ("greedy", "penalty_greedy", "sampling")
 GRAPH_FILES = {"prefill_greedy": "Qwen3_ASR_Prefill_Greedy", "prefill_penalty_greedy": "Qwen3_ASR_Prefill_Penalty_Greedy", "prefill_sampling": "Qwen3_ASR_PrefillSampling",
@@ -27,7 +28,6 @@ GRAPH_FILES = {"prefill_greedy": "Qwen3_ASR_Prefill_Greedy", "prefill_penalty_gr
 EMBED_FILE, WEIGHTS_FILE, METADATA_FILE = "Qwen3_ASR_Decoder_Embed", "Qwen3_ASR", "ASR_Metadata"
 MAX_OUT = {"greedy": "greedy_max_logits_idx", "penalty_greedy": "penalty_greedy_max_logits_idx", "sampling": "sampling_sampled_id"}
 SAVE_OUT = {"greedy": None, "penalty_greedy": "penalty_greedy_save_id_out", "sampling": "sampling_save_id_out"}
-SAMPLING_INPUTS = ("sampling_temperature", "sampling_top_k", "sampling_top_p", "sampling_repetition_penalty")
 _TAG = np.float32(-7.25e18)         # element 1 of an id-carrying embedding row
 
 _SHARED: dict = {}
@@ -113,24 +113,6 @@ class QwenGraph:
         self.audio_dtype = self.sh.native.audio_dtype              # the weights bundle's INPUT_AUDIO_DTYPE
         self.inputs, self.outputs = graph_io(self.cfg, self.role, self.strategy, self.kv_dtype, self.audio_dtype)
 
-    def _configure_head(self, feeds, is_decode):
-        sh, n = self.sh, self.sh.native
-        value, rng, samp = 1.0, 10, None
-        if self.strategy == "penalty_greedy" and is_decode:
-            value = float(np.asarray(feeds["penalty_penalty_value"].numpy()).reshape(-1)[0])
-            rng = int(np.asarray(feeds["penalty_penalty_range"].numpy()).reshape(-1)[0])
-        if self.strategy == "sampling":
-            samp = tuple(float(np.asarray(feeds[k].numpy()).reshape(-1)[0]) for k in SAMPLING_INPUTS)
-        head = (self.strategy, value, rng, samp)
-        if head == sh.head:
-            return
-        n.set_sampling(False)
-        n.track_history(self.strategy == "penalty_greedy")
-        n.set_penalty(value, min(max(rng, 1), 64))
-        if samp is not None:
-            n.set_sampling(True, samp[0], int(samp[1]), samp[2], samp[3], seed=0)
-        sh.head = head
-
     def _check_state(self, feeds, required):
         for i in range(self.cfg.n_layers):
             for part in ("key", "value"):
@@ -184,7 +166,7 @@ class QwenGraph:
             check_audio_type(audio, self.audio_dtype, "(raw PCM)" if self.audio_dtype == np.int16 else "in [-1, 1]")
             query = embedding_as_ids(feeds["query_embed"].numpy(), "query_embed")
             tail = embedding_as_ids(feeds["language_tail_embed"].numpy(), "language_tail_embed")
-            self._configure_head(feeds, False)
+            configure_head(self, feeds, False, 10)
             pre, post = [sh.head_ids + query + sh.suffix_ids], [sh.tail_ids + tail]
             offsets = np.array([0, shape[2]], dtype=np.int64)
             if audio._host is not None:
@@ -202,7 +184,7 @@ class QwenGraph:
         ids = embedding_as_ids(feeds["hidden_states"].numpy(), "hidden_states")
         if len(ids) != 1:
             raise ValueError("hidden_states: one position per decode step")
-        self._configure_head(feeds, True)
+        configure_head(self, feeds, True, 10)
         nxt, _ = sh.native.decode(None if ids[0] == sh.last_next else np.asarray(ids, dtype=np.int32))
         sh.seq_len += 1
         self._outputs(OrtValue, results, nxt[0], "decode_kv_seq_len_next")

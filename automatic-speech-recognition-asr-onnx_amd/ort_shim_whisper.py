@@ -27,6 +27,7 @@ import os
 import numpy as np
 
 from .config import WhisperConfig
+from .ort_shim import SAMPLING_INPUTS, configure_head
 
 STRATEGIES = ("greedy", "penalty_greedy", "sampling")
 _SUFFIX = {"greedy": "Greedy", "penalty_greedy": "PenaltyGreedy", "sampling": "Sampling"}
@@ -35,7 +36,6 @@ GRAPH_FILES = {f"{role}_{st}": f"Whisper_{stem}{_SUFFIX[st]}" for role, stem in 
 NO_SPEECH_FILE, WEIGHTS_FILE, METADATA_FILE = "Whisper_No_Speech_Detection", "Whisper", "ASR_Metadata"
 MAX_OUT = {"greedy": "argmax_max_logits_idx", "penalty_greedy": "greedy_max_logits_idx", "sampling": "sampling_sampled_id"}
 SAVE_OUT = {"greedy": None, "penalty_greedy": "greedy_save_id_out", "sampling": "sampling_save_id_out"}
-SAMPLING_INPUTS = ("sampling_temperature", "sampling_top_k", "sampling_top_p", "sampling_repetition_penalty")
 
 _SHARED: dict = {}          # (weights bundle path, device) -> _Shared: the one native session of a model folder
 
@@ -137,24 +137,6 @@ class WhisperGraph:
                 elif h != (kind, id(self.sh), gen):
                     raise ValueError(f"{name!r} is a stale handle: it belongs to an earlier run than the state it is bound to")
 
-    def _configure_head(self, feeds, is_decode):
-        sh, n = self.sh, self.sh.native
-        value, rng, samp = 1.0, 20, None
-        if self.strategy == "penalty_greedy" and is_decode:
-            value = float(np.asarray(feeds["penalty_penalty_value"].numpy()).reshape(-1)[0])
-            rng = int(np.asarray(feeds["penalty_penalty_range"].numpy()).reshape(-1)[0])
-        if self.strategy == "sampling":
-            samp = tuple(float(np.asarray(feeds[k].numpy()).reshape(-1)[0]) for k in SAMPLING_INPUTS)
-        head = (self.strategy, value, rng, samp)
-        if head == sh.head:
-            return
-        n.set_sampling(False)
-        n.track_history(self.strategy == "penalty_greedy")
-        n.set_penalty(value, min(max(rng, 1), 64))
-        if samp is not None:
-            n.set_sampling(True, samp[0], int(samp[1]), samp[2], samp[3], seed=0)
-        sh.head = head
-
     def _state_outputs(self, OrtValue, results, B, new_len):
         H, hd = self.cfg.n_heads, self.cfg.d_head
         for i in range(self.cfg.n_dec_layers):
@@ -190,7 +172,7 @@ class WhisperGraph:
             seq = int(np.asarray(feeds["decode_kv_seq_len"].numpy()).reshape(-1)[0])
             if seq != sh.hist:
                 raise ValueError(f"decode_kv_seq_len = {seq} but the cache holds {sh.hist} positions")
-            self._configure_head(feeds, True)
+            configure_head(self, feeds, True, 20)
             if ids_v is sh.last_next:
                 nxt, _ = sh.native.decode(None)                        # the previous pick never left the device
             else:
@@ -233,7 +215,7 @@ class WhisperGraph:
             self._check_handles(feeds, "en_", "cross", sh.enc_gen, required=True)
         if ids.shape[0] != sh.batch:
             raise ValueError(f"embed_input_ids has batch {ids.shape[0]} but {sh.batch} clips are encoded")
-        self._configure_head(feeds, False)
+        configure_head(self, feeds, False, 20)
         nxt, logits = sh.native.prefill(ids, want_logits=True)
         sh.hist = ids.shape[1]
         sh.kv_gen += 1

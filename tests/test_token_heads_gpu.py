@@ -315,6 +315,30 @@ def test_sampler_generator_is_uniform_over_four_equal_logits():
     assert out["next"][:m][ok].tolist() == want[ok].tolist()
 
 
+# ------------------------------------------------------------------------------------------------ the head over several steps
+@pytest.mark.parametrize("name", list(R.head_steps_cases()))
+def test_head_steps(name):
+    """TokenHead (csrc/decode_head.h), the one head sequence of the Whisper and Qwen3-ASR sessions, over nine steps on the same three rows (257 valid columns
+    in rows of 384, pads at +1e30, a history table of 16): restart, then per step apply-penalty, sampler or arg-max, append, counter + 1, consumed.
+    tests/test_token_heads_ref_cpu.py shows on these inputs that a head which skips any of it gives other picks."""
+    c = R.HEAD_STEPS
+    x, _, _ = R.head_steps_inputs()
+    kw = R.head_steps_cases()[name]
+    want, save, n, decided = R.head_steps(x, c["steps"], c["ld_save"], **kw)
+    out = sub("_probe").head_steps(x, c["steps"], c["ld_save"], **kw)
+    print(f"head steps, {name}: picks\n{out['picks'].T}\ncounter {out['n_saved']}")
+    assert out["n_saved"] == n
+    if "sampler" not in kw:
+        assert np.array_equal(out["picks"], want) and np.array_equal(out["save_ids"], save)
+        return
+    ok = np.logical_and.accumulate(decided, axis=0)                 # a row's later steps read its earlier picks
+    skipped = 1.0 - ok.mean()
+    print(f"head steps, {name}: skipped {skipped:.3f} of {ok.size} picks")
+    assert skipped <= R.SKIP_CAP
+    assert out["picks"][ok].tolist() == want[ok].tolist()
+    assert np.array_equal(out["save_ids"][:, :n], out["picks"].T) and (out["save_ids"][:, n:] == 0).all()
+
+
 # ------------------------------------------------------------------------------------------------ no_speech_prob
 @pytest.mark.parametrize("n", R.LOOP_WIDTHS)
 def test_no_speech_prob(n):

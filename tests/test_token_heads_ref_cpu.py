@@ -225,3 +225,39 @@ def test_budgets_hold_for_a_plain_f32_evaluation():
         lse32 = (m[:, 0] + np.log(np.exp(x - m).sum(axis=1, dtype=np.float32))).astype(np.float32)
         v32 = np.take_along_axis(x, topi, 1) - lse32[:, None]
         assert (np.abs(v32 - topv) <= R.beam_topv_budget(n, m.astype(np.float64), lse[:, None], topv)).all()
+
+
+def test_head_steps_inputs_show_what_the_head_does():
+    """The inputs of test_head_steps (tests/test_token_heads_gpu.py): the same rows at every step, so every change of pick is the head's doing -- a head that
+    skips the bias, the penalty, the history or the hand-over of the noise gives other picks than these."""
+    c = R.HEAD_STEPS
+    x, bias, noise = R.head_steps_inputs()
+    cases = R.head_steps_cases()
+    run = lambda kw: R.head_steps(x, c["steps"], c["ld_save"], **kw)
+    raw, rng = R.argmax_rows(x)[0], c["range_"]
+    assert c["steps"] > rng + 1 and c["steps"] <= c["ld_save"] and len(cases) == 5
+    # partial 0 (Whisper): nothing is penalised until `range` ids are saved -- the pick is kept through the first `range` steps and changes at step range + 1
+    # (index `range`); the biased step 0 takes the second-best column instead of the raw arg-max
+    p, save, n, _ = run(dict(cases["partial 0, step-0 bias"], bias=None))
+    assert (p[:rng] == raw).all() and (p[rng] != raw).all()
+    p, save, n, _ = run(cases["partial 0, step-0 bias"])
+    assert (p[0] != raw).all() and (p[1:rng] == raw).all() and (p[rng] != raw).all()
+    assert n == c["steps"] and np.array_equal(save[:, :n], p.T) and (save[:, n:] == 0).all()
+    # partial 1 (Qwen3): whatever is saved is penalised -- the pick changes at the second step
+    p1, save, n, _ = run(cases["partial 1"])
+    assert (p1[0] == raw).all() and (p1[1] != p1[0]).all() and np.array_equal(save[:, :n], p1.T)
+    # value 1.0 with the history tracked: the picks never move, the history fills
+    p, save, n, _ = run(cases["value 1.0, history tracked"])
+    assert (p == raw).all() and n == c["steps"] and (save[:, :n] == raw[:, None]).all()
+    assert run(dict(cases["value 1.0, history tracked"], track_history=False))[2] == 0
+    # the sampler: every pick decided; noise kept armed for a second step, or never used, gives other picks
+    kw = cases["sampler, noise on step 0"]
+    p, save, n, decided = run(kw)
+    assert decided.all() and np.array_equal(save[:, :n], p.T) and len(np.unique(p)) > c["rows"]
+    every = [R.sample_topk_topp(x, save, t, *kw["sampler"][:4], noise=noise, seed=kw["sampler"][4])[0] for t in (1, 2)]
+    assert (every[0] != p[1]).any() or (every[1] != p[2]).any()
+    assert (run(dict(kw, noise=None))[0][0] != p[0]).any()
+    # the change of penalty shows in the steps after it and in none before
+    pc = run(cases["penalty changed after step 4"])[0]
+    at = cases["penalty changed after step 4"]["change"][0]
+    assert at == 5 and np.array_equal(pc[:at], p1[:at]) and (pc[at:] != p1[at:]).any()

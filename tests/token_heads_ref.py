@@ -184,6 +184,35 @@ def sampler_decided(margin, top_k, vmax=64.0):
     return (margin[:, 0] > g) & (margin[:, 1] > p)
 
 
+# ------------------------------------------------------------------------------------------------ the head over several steps
+def head_steps(logits, steps, ld_save, range_, value, partial, bias=None, track_history=False, sampler=None, noise=None, change=None):
+    """The sessions' head sequence (csrc/decode_head.h: TokenHead) on the same logits rows at every step, from an empty history: apply_penalty (decode
+    steps only, not under the sampler), then the sampler or the arg-max, then append_ids and counter + 1 when the head is penalised, samples or
+    tracks its history. Step 0 is the prefill: `bias` is added, nothing is penalised. sampler: (temperature, top_k, top_p, repetition_penalty, seed);
+    noise: caller uniforms for step 0 only; change: (step, value, range) takes effect before that step.
+    Returns (picks [steps][rows], save_ids [rows][ld_save], n_saved, decided [steps][rows]: the sampler's margins decide that pick -- all True for arg-max)."""
+    logits = np.asarray(logits, F32)
+    rows = len(logits)
+    save, n = np.zeros((rows, ld_save), np.int32), 0
+    picks, decided = np.zeros((steps, rows), np.int32), np.ones((steps, rows), bool)
+    for t in range(steps):
+        if change is not None and t == change[0]:
+            value, range_ = change[1], change[2]
+        penalised = value != 1.0 and sampler is None
+        x = apply_penalty(logits, save, n, range_, value, partial) if penalised and t > 0 else logits
+        if sampler is not None:
+            temperature, top_k, top_p, rp, seed = sampler
+            picks[t], margin, _ = sample_topk_topp(x, save, n, temperature, top_k, top_p, rp, extra=bias if t == 0 else None,
+                                                   noise=noise if t == 0 else None, seed=seed)
+            decided[t] = sampler_decided(margin, top_k)
+        else:
+            picks[t], _ = argmax_rows(x, bias if t == 0 else None)
+        if penalised or sampler is not None or track_history:
+            save = append_ids(save, picks[t], n)
+            n += 1
+    return picks, save, n, decided
+
+
 # ------------------------------------------------------------------------------------------------ no-speech
 def no_speech_prob(logits, penalty, no_speech_id):
     """NO_SPEECH_DETECTION: soft-max(logits - penalty)[no_speech_id]; the subtraction in f32, the soft-max in float64.
@@ -297,6 +326,34 @@ def sampler_extra_inputs(top_k):
 
 
 UNIFORM = dict(n_valid=129, rows=4096, ids=[3, 64, 65, 128], n_saved=2, seed=20240607, checked=64)
+
+
+HEAD_STEPS = dict(rows=3, n_valid=257, ld_save=16, steps=9, range_=4, value=0.5, sampler=(0.7, 10, 0.95, 1.3, 20240913))
+
+
+def head_steps_inputs():
+    """(logits, bias, noise): grid logits fed unchanged at every step, so an unpenalised head returns one id for ever; a step-0 bias that is -inf on each
+    row's raw arg-max (BEGIN_SUPPRESS); caller uniforms for the sampler's step 0."""
+    c = HEAD_STEPS
+    x = grid_logits([c["n_valid"], 21], c["rows"], c["n_valid"])
+    bias = np.zeros(c["n_valid"], F32)
+    bias[argmax_rows(x)[0]] = -np.inf
+    noise = np.random.default_rng(23).uniform(0.0, 1.0, (c["rows"], c["sampler"][1])).astype(F32)
+    return x, bias, noise
+
+
+def head_steps_cases():
+    """name -> keyword arguments of head_steps (and of the probe's head_steps) beyond the logits and the shape of HEAD_STEPS."""
+    c = HEAD_STEPS
+    _, bias, noise = head_steps_inputs()
+    base = dict(range_=c["range_"], value=c["value"])
+    return {
+        "partial 0, step-0 bias": dict(base, partial=0, bias=bias),
+        "partial 1": dict(base, partial=1),
+        "value 1.0, history tracked": dict(base, value=1.0, partial=0, track_history=True),
+        "sampler, noise on step 0": dict(base, partial=1, bias=bias, sampler=c["sampler"], noise=noise),
+        "penalty changed after step 4": dict(base, partial=1, change=(5, 0.25, 2)),
+    }
 
 
 def sampler_uniform_inputs():
