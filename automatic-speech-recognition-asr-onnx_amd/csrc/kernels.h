@@ -180,6 +180,10 @@ void launch_lfr_cmvn(const LfrArgs& a, hipStream_t s);
 template <typename OutT>
 void launch_layernorm(const float* x, int ld_x, int rows, int D, const float* gamma, const float* beta, float eps,
                       OutT* out, int ld_out, int fill_to, hipStream_t s, const int32_t* rows_dev = nullptr);   // rows_dev: device-side row count
+// f32 output (may be `x` itself) plus the bf16 rounding of the same values, from one pass over the rows (the stand-alone LayerNorm between two runs of
+// LayerNorm-fused blocks: normed stream + its operand copy). Columns [0, D) only.
+void launch_layernorm_with_bf16_copy(const float* x, int ld_x, int rows, int D, const float* gamma, const float* beta, float eps,
+                                     float* out, int ld_out, bf16_t* out_lo, int ld_lo, hipStream_t s);
 
 
 // ---- multi-head self-attention over packed ragged utterances (no mask inside an utterance).

@@ -414,11 +414,13 @@ __global__ void lfr_cmvn_kernel(const LfrArgs a) {
 // ------------------------------------------------------------------------------------ LayerNorm
 // One wave per row; the row (D <= 2048) is read ONCE as float4 per lane and held in registers; two-pass
 // mean / variance on the registers (same arithmetic order class as torch's), wave-shuffle reductions.
+// out_lo (optional, next to an f32 `out`): the bf16 rounding of the same values, the operand copy of a LayerNorm-fused projection.
 constexpr int LN_MAXV = 8;   // float4 per lane: 8 * 4 * 64 = 2048 columns
 template <typename OutT>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ld_x, int rows, int D,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        float eps, OutT* out, int ld_out, int fill_to, const int32_t* __restrict__ rows_dev) {
+                                                        float eps, OutT* out, int ld_out, int fill_to, const int32_t* __restrict__ rows_dev,
+                                                        bf16_t* out_lo, int ld_lo) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows || (rows_dev && row >= *rows_dev)) return;
@@ -456,6 +458,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       }
       if constexpr (sizeof(OutT) == 4) {
         *reinterpret_cast<float4*>(o + i) = make_float4(y0, y1, y2, y3);
+        if (out_lo) {
+          uint2 w;
+          w.x = pack_bf16x2(y0, y1);
+          w.y = pack_bf16x2(y2, y3);
+          *reinterpret_cast<uint2*>(out_lo + (size_t)row * ld_lo + i) = w;
+        }
       } else {
         uint2 w;
         w.x = pack_bf16x2(y0, y1);
@@ -1557,7 +1565,13 @@ void launch_layernorm(const float* x, int ld_x, int rows, int D, const float* ga
                       OutT* out, int ld_out, int fill_to, hipStream_t s, const int32_t* rows_dev) {
   ASR_REQUIRE(D % 4 == 0 && D <= LN_MAXV * 256 && ld_x % 4 == 0 && ld_out % 4 == 0, "layernorm: D=%d ld=%d unsupported", D, ld_x);
   hipLaunchKernelGGL(layernorm_kernel<OutT>, dim3((rows + 3) / 4), dim3(256), 0, s, x, ld_x, rows, D, gamma, beta, eps, out,
-                     ld_out, fill_to, rows_dev);
+                     ld_out, fill_to, rows_dev, (bf16_t*)nullptr, 0);
+  HIP_CHECK(hipGetLastError());
+}
+void launch_layernorm_with_bf16_copy(const float* x, int ld_x, int rows, int D, const float* gamma, const float* beta, float eps,
+                                     float* out, int ld_out, bf16_t* out_lo, int ld_lo, hipStream_t s) {
+  ASR_REQUIRE(D % 4 == 0 && D <= LN_MAXV * 256 && ld_x % 4 == 0 && ld_out % 4 == 0 && ld_lo % 4 == 0 && out_lo, "layernorm: D=%d ld=%d unsupported", D, ld_x);
+  hipLaunchKernelGGL(layernorm_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, s, x, ld_x, rows, D, gamma, beta, eps, out, ld_out, D, (const int32_t*)nullptr, out_lo, ld_lo);
   HIP_CHECK(hipGetLastError());
 }
 template void launch_layernorm<float>(const float*, int, int, int, const float*, const float*, float, float*, int, int, hipStream_t, const int32_t*);

@@ -17,8 +17,9 @@
 //   * No barrier inside a chunk, hand-counted `s_waitcnt vmcnt(N)` for both streams (see `Sched`): the compiler's own bookkeeping gives up
 //     (vmcnt(0) / lgkmcnt(0)) while an LDS-DMA is pending, so the W loads are inline asm and their waits are tied to the registers they fill.
 //
-//   A  q|k|v projection of head h (LayerNorm folded in) -> q / k / v^T images in LDS, attention (wave = one 16-query tile; the ninth tile is
-//      shared by all waves: scores redundantly, context split over the head dimension), FSMN        ctx[:, 128 h ..] (bf16)  -- exchange 0 -->
+//   A  q|k|v projection of head h (LayerNorm folded in) -> q / k / v^T images in LDS (the k image under its own slot swizzle `kswz`: the score pass reads
+//      it without bank conflicts), attention (wave = one 16-query tile; the ninth tile is shared by all waves: scored ONCE, wave s < 5 = its 32-key sub-tile s,
+//      maxima and probabilities handed over through LDS, context split over the head dimension), FSMN  ctx[:, 128 h ..] (bf16)  -- exchange 0 -->
 //   B  out-projection slab (wave = K-half x 32 columns; accumulators start from FSMN term + residual)
 //        -> x1 slab: f32 to memory (own rows, read back in D), bf16 copy + row statistics                                   -- exchange 1 -->
 //   C  FFN-1 slab: relu(LN(x1) W1[512 h ..]^T + b1) -> hid[:, 512 h ..] (bf16), the four own chunks of phase D, in LDS
@@ -43,13 +44,21 @@ constexpr int LDS_BYTES = 160 * 1024;
 // ---- LDS map (bytes)
 constexpr int CH = R * 256;                      // one chunk: 144 rows x 128 bf16 columns = 36864
 constexpr int NSLOT = 4;                         // chunk slots 0 .. 3 at q * CH
-constexpr int QS = 0, KS = CH, KEYS = 160, VS = KS + KEYS * 256, IMG_END = VS + HD * 512;       // phase A images: q (= slot 0, later the ctx chunk), k, v^T
+constexpr int QS = 0, KS = CH, KEYS = 160, VS = KS + KEYS * 256, IMG_END = VS + HD * 512;       // phase A images: q (= slot 0, later the ctx chunk), k (slots by `kswz`, rows 144..159 read and masked), v^T
 constexpr int TERM = CH;                         // FSMN term f32 [144][128] over slots 1, 2 (the k image and the head of v^T are dead by then)
 constexpr int RED = 2 * CH;                      // K-half exchange of phases B / D over slots 2, 3 (72 KB)
 constexpr int ST_F = NSLOT * CH;                 // (mean, rstd) [144] float2
 constexpr int ST_P = ST_F + R * 8;               // statistics partials [4 slots][144] float2
 constexpr int DUMMY = ST_P + NSLOT * R * 8;          // landing area of the L2 warm-up loads (256 B per wave, never read)
-static_assert(IMG_END <= ST_F && TERM + R * HD * 4 <= ST_F && DUMMY + NW * 256 <= LDS_BYTES, "LDS map");
+// shared ninth attention tile (phase A, T > 128): what the five scoring waves hand to all eight -- per-query maxima of the five 32-key sub-tiles f32 [5][16],
+// the probability fragments [5][64 lanes][16 B] and the per-lane terms of the row sums f32x2 [5][64 lanes]
+constexpr int T9_MX = DUMMY + NW * 256, T9_PF = T9_MX + 5 * 16 * 4, T9_LS = T9_PF + 5 * 64 * 16, T9_END = T9_LS + 5 * 64 * 8;
+static_assert(IMG_END <= ST_F && TERM + R * HD * 4 <= ST_F && DUMMY + NW * 256 <= LDS_BYTES && T9_END <= LDS_BYTES && T9_MX % 16 == 0 && T9_PF % 16 == 0 && T9_LS % 16 == 0, "LDS map");
+// 16-byte-slot XOR term of the K image, output bits {b0, b1, b0 ^ b2, b3} of the key. The images' `row & 15` is made for the chunk reads (lanes on rows 16 i + frow);
+// the score pass reads keys 8 (fq >> 2) + (fq & 3) (+ 4), and under `key & 15` the sixteen lanes of a ds_read_b128 group (keys 0-3, 24-27 and, one column slot on,
+// 8-11, 16-19) meet in eight slots: every K read was a 2-way bank conflict. Under this term they cover all sixteen, and the eight lanes (rows 16 i .. + 7) of a
+// ds_write_b128 group of the image store still cover all eight 16-byte bank groups. Only the attention reads the K image.
+__device__ __host__ constexpr int kswz(int key) { return (key & 3) | (((key ^ (key >> 2)) & 1) << 2) | (key & 8); }
 
 // ---- fragment-major weight copy of one block, bytes from the block's base (see launch_sanm_block8_pack for the element order)
 constexpr size_t PK_QKV = 0, PK_QKV_WAVE = 16 * 3 * 1024;                       // [h][wave][16 steps][3 frags][64 lanes][16 B]
@@ -546,7 +555,7 @@ __global__ __launch_bounds__(NT) void sanm_block8_kernel(const SanmBlockArgs a_b
           for (int r = 0; r < 4; ++r) { v[r] = acc[i][0][r]; v[4 + r] = acc[i][1][r]; }
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = (v[e] - mr.x * c8[e]) * mr.y + b8[e];
-          *reinterpret_cast<uint4*>(dst + row * 256 + ((((col >> 3)) ^ (row & 15)) << 4)) = pack8(v);
+          *reinterpret_cast<uint4*>(dst + row * 256 + ((((col >> 3)) ^ (grp == 0 ? (row & 15) : kswz(row))) << 4)) = pack8(v);
         }
         unsigned char* vdst = smem + VS + dcol * 512 + (fgrp & 1) * 8;
 #pragma unroll
@@ -574,8 +583,8 @@ __global__ __launch_bounds__(NT) void sanm_block8_kernel(const SanmBlockArgs a_b
     const float bc = L->bfsmn[h * HD + (tid & (HD - 1))];
 
     // ---- attention: wave w = the 16-query tile w with all <= 160 scores in registers (one soft-max pass); the ninth tile (queries 128..143) is shared:
-    //      every wave computes its scores and multiplies ONE 16-wide slice of the head dimension. A context tile goes back into the (dead) q rows of
-    //      the image, which is exactly the chunk format phase B reads.
+    //      waves 0..4 score one 32-key sub-tile each, every wave multiplies ONE 16-wide slice of the head dimension. A context tile goes back into the
+    //      (dead) q rows of the image, which is exactly the chunk format phase B reads.
     {
       const unsigned char* Qs = smem + QS;
       const unsigned char* Ks = smem + KS;
@@ -597,8 +606,8 @@ __global__ __launch_bounds__(NT) void sanm_block8_kernel(const SanmBlockArgs a_b
 #pragma unroll
             for (int ks = 0; ks < HD / 32; ++ks) {
               const int c = ks * 4 + g;
-              const bf16x8_t kf0 = *reinterpret_cast<const bf16x8_t*>(Ks + key0 * 256 + ((c ^ (key0 & 15)) << 4));
-              const bf16x8_t kf1 = *reinterpret_cast<const bf16x8_t*>(Ks + key1 * 256 + ((c ^ (key1 & 15)) << 4));
+              const bf16x8_t kf0 = *reinterpret_cast<const bf16x8_t*>(Ks + key0 * 256 + ((c ^ kswz(key0)) << 4));
+              const bf16x8_t kf1 = *reinterpret_cast<const bf16x8_t*>(Ks + key1 * 256 + ((c ^ kswz(key1)) << 4));
               st[s][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf0, qf[ks], st[s][0], 0, 0, 0);
               st[s][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf1, qf[ks], st[s][1], 0, 0, 0);
             }
@@ -677,15 +686,67 @@ __global__ __launch_bounds__(NT) void sanm_block8_kernel(const SanmBlockArgs a_b
       }
       STAMP_A(6);
       if (shared_tile) {
-        // (the waves' own tiles are rows 0..127: nobody has written rows 128..143 yet, and nobody will before the barrier below)
-        bf16x8_t qf8[HD / 32], pf[5];
-        const int qrow8 = 128 + fq;
+        // T > 128: all five 32-key sub-tiles exist. Wave s < 5 scores sub-tile s -- once per workgroup, not once per wave --; the waves meet twice in LDS
+        // (maxima, then probabilities), and every wave sums the five row-sum terms in the order s = 0 .. 4, the order of `scores`: same bits as a whole pass per wave.
+        // (the waves' own tiles are rows 0..127: nobody has written rows 128..143 yet, and nobody will before the first barrier below)
+        constexpr float LOG2E = 1.4426950408889634f;
+        float* t9_mx = reinterpret_cast<float*>(smem + T9_MX);
+        const bool scorer = wave < 5;                       // (wave-uniform)
+        f32x4_t s9[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
+        if (scorer) {
+          const int qrow8 = 128 + fq;
+          const int key0 = wave * 32 + ((fq >> 2) << 3) + (fq & 3), key1 = key0 + 4;
 #pragma unroll
-        for (int ks = 0; ks < HD / 32; ++ks) qf8[ks] = *reinterpret_cast<const bf16x8_t*>(Qs + qrow8 * 256 + (((ks * 4 + g) ^ (qrow8 & 15)) << 4));
-        float inv;
-        scores(qf8, pf, inv);
-        __syncthreads();                                    // every wave holds the shared tile's q fragments and scores: its rows may now take the context
-        context(pf, inv, 128 + fq, wave, std::integral_constant<int, 1>{});
+          for (int ks = 0; ks < HD / 32; ++ks) {
+            const int c = ks * 4 + g;
+            const bf16x8_t qf8 = *reinterpret_cast<const bf16x8_t*>(Qs + qrow8 * 256 + ((c ^ (qrow8 & 15)) << 4));
+            const bf16x8_t kf0 = *reinterpret_cast<const bf16x8_t*>(Ks + key0 * 256 + ((c ^ kswz(key0)) << 4));
+            const bf16x8_t kf1 = *reinterpret_cast<const bf16x8_t*>(Ks + key1 * 256 + ((c ^ kswz(key1)) << 4));
+            s9[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf0, qf8, s9[0], 0, 0, 0);
+            s9[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf1, qf8, s9[1], 0, 0, 0);
+          }
+          if (wave * 32 + 32 > T) {
+#pragma unroll
+            for (int hlf = 0; hlf < 2; ++hlf)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (wave * 32 + g * 8 + hlf * 4 + r >= T) s9[hlf][r] = -INFINITY;
+          }
+          float m = fmaxf(fmaxf(fmaxf(s9[0][0], s9[0][1]), fmaxf(s9[0][2], s9[0][3])), fmaxf(fmaxf(s9[1][0], s9[1][1]), fmaxf(s9[1][2], s9[1][3])));
+          m = fmaxf(m, __shfl_xor(m, 16, 64));
+          m = fmaxf(m, __shfl_xor(m, 32, 64));
+          if (g == 0) t9_mx[wave * 16 + fq] = m;
+        }
+        __syncthreads();                                    // the sub-tile maxima are out, and every read of the shared tile's q rows is done: they may take the context
+        float mx = t9_mx[fq];                               // (a maximum is exact in any order)
+#pragma unroll
+        for (int s = 1; s < 5; ++s) mx = fmaxf(mx, t9_mx[s * 16 + fq]);
+        if (scorer) {
+          const f32x2_t mneg = {-mx * LOG2E, -mx * LOG2E}, l2 = {LOG2E, LOG2E};
+          f32x2_t p[4];
+          uint4 w;
+          uint32_t* wd = reinterpret_cast<uint32_t*>(&w);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x2_t e = __builtin_elementwise_fma(f32x2_t{s9[q >> 1][2 * (q & 1)], s9[q >> 1][2 * (q & 1) + 1]}, l2, mneg);
+            p[q] = f32x2_t{__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])};
+            wd[q] = pack_bf16x2(p[q][0], p[q][1]);
+          }
+          *reinterpret_cast<uint4*>(smem + T9_PF + (wave * 64 + lane) * 16) = w;
+          *reinterpret_cast<f32x2_t*>(smem + T9_LS + (wave * 64 + lane) * 8) = (p[0] + p[1]) + (p[2] + p[3]);
+        }
+        __syncthreads();                                    // the five probability fragments and row-sum terms are out
+        bf16x8_t pf[5];
+        f32x2_t lsum = {0.0f, 0.0f};
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+          pf[s] = *reinterpret_cast<const bf16x8_t*>(smem + T9_PF + (s * 64 + lane) * 16);
+          lsum += *reinterpret_cast<const f32x2_t*>(smem + T9_LS + (s * 64 + lane) * 8);
+        }
+        float l = lsum[0] + lsum[1];
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+        context(pf, 1.0f / l, 128 + fq, wave, std::integral_constant<int, 1>{});
       }
       STAMP_A(7);
     }

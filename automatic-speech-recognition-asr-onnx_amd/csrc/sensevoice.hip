@@ -434,8 +434,7 @@ void SvSession::enqueue(const SvRunCtx& r) {
         st_in_block8 = true;
         if (i == c.n_main - 1 && !paraformer) {
           ProfScope ps2(prof, "layernorm", stream);
-          launch_layernorm<bf16_t>(xa, d, rows, d, after_g, after_b, 1e-5f, xalo, d, d, stream); st_in = nullptr;
-          launch_layernorm<float>(xa, d, rows, d, after_g, after_b, 1e-5f, xa, d, d, stream);
+          launch_layernorm_with_bf16_copy(xa, d, rows, d, after_g, after_b, 1e-5f, xa, d, xalo, d, stream); st_in = nullptr;
         }
         continue;
       }
@@ -543,8 +542,8 @@ void SvSession::enqueue(const SvRunCtx& r) {
     if (i == 0) save_tap("block0", xa, rows, d, d, 4);
     if (i == c.n_main - 1 && !paraformer) {
       ProfScope ps(prof, "layernorm", stream);
-      if (alg) { launch_layernorm<bf16_t>(xa, d, rows, d, after_g, after_b, 1e-5f, xalo, d, d, stream); st_in = nullptr; }   // operand copy of the normed stream
-      launch_layernorm<float>(xa, d, rows, d, after_g, after_b, 1e-5f, xa, d, d, stream);
+      if (alg) { launch_layernorm_with_bf16_copy(xa, d, rows, d, after_g, after_b, 1e-5f, xa, d, xalo, d, stream); st_in = nullptr; }   // normed stream + its operand copy
+      else launch_layernorm<float>(xa, d, rows, d, after_g, after_b, 1e-5f, xa, d, d, stream);
     }
   }
   if (paraformer) { copy_block_status(r); enqueue_paraformer_tail<T>(r); return; }
