@@ -58,6 +58,7 @@ class TokenHeadDesc(C.Structure):
 
 SIGNATURES = {
     "asr_probe_gemm": (C.c_int, [C.POINTER(GemmDesc)]),
+    "asr_probe_ctc_head": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, _ip, _fp, _ip, C.c_char_p]),
     "asr_probe_gemm_chain": (C.c_int, [C.c_int] * 6 + [_fp]),
     "asr_probe_last_kernel": (C.c_char_p, []),
     "asr_probe_quantize_fp8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, _fp, C.c_void_p]),
@@ -122,6 +123,19 @@ def gemm(a, w, bias=None, add=None, act=0, ln=False, ln_eps=1e-5, argmax=False, 
             out["stats"] = np.zeros((M, N // 32, 2), dtype=np.float32); d.out_stats = out["stats"].ctypes.data_as(_fp)
     _lib.check(load().asr_probe_gemm(C.byref(d)))
     return out, d.kernel.decode()
+
+
+def ctc_head(a, w, bias, n_valid=0, variant=-1):
+    """The CTC head with frame log-probabilities (arg-max GEMM with the sum-of-exponentials partial + row reduce) through the product dispatcher;
+    returns (ids[M], frame_logprob[M], words written past row M, kernel family name)."""
+    a, w, bias = _f32(a), _f32(w), _f32(bias)
+    M, K = a.shape
+    N = w.shape[0]
+    ids, lp = np.zeros((M,), dtype=np.int32), np.zeros((M,), dtype=np.float32)
+    stray, name = C.c_int32(-1), C.create_string_buffer(32)
+    _lib.check(load().asr_probe_ctc_head(M, N, K, a.ctypes.data_as(_fp), w.ctypes.data_as(_fp), bias.ctypes.data_as(_fp), n_valid, variant,
+                                         ids.ctypes.data_as(_ip), lp.ctypes.data_as(_fp), C.byref(stray), name))
+    return ids, lp, stray.value, name.value.decode()
 
 
 def gemm_bench(M, N, K, variant=-1, epilogue=0, iters=50) -> float:

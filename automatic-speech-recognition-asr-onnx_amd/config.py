@@ -57,6 +57,17 @@ class SenseVoiceConfig:
     def seq_len(self, audio_len: int) -> int:
         return self.n_lfr(audio_len) + self.n_prompt
 
+    def row_span_seconds(self, first: int, last: int) -> tuple:
+        """(start, end) in seconds of a token whose run covers sequence rows first..last (SenseVoiceSession.run_timed). Row j >= n_prompt is LFR row
+        j - n_prompt and covers [(j - n_prompt) lfr_n hop_length / sample_rate, (j - n_prompt + 1) lfr_n hop_length / sample_rate): the span runs from
+        the start of the first row to the end of the last. A run inside the prompt rows (language / emotion / event / ITN tags) has the span (0.0, 0.0);
+        one that starts there and ends in a speech row starts at 0.0."""
+        first, last = int(first), int(last)
+        if last < self.n_prompt:
+            return (0.0, 0.0)
+        row = self.lfr_n * self.hop_length / self.sample_rate
+        return (max(first - self.n_prompt, 0) * row, (last - self.n_prompt + 1) * row)
+
     def to_dict(self):
         return asdict(self)
 

@@ -397,6 +397,50 @@ extern "C" int asr_op_ctc_collapse(const int32_t* frame_ids, const int32_t* seq_
   });
 }
 
+extern "C" int asr_op_ctc_collapse_timed(const int32_t* frame_ids, const float* frame_logprob, const int32_t* seq_lens, int batch, int blank_id,
+                                         int32_t* token_ids, int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens,
+                                         int32_t* num_id) {
+  return asr_guard([&] {
+    ASR_REQUIRE(frame_ids && frame_logprob && seq_lens && token_ids && first_frame && last_frame && token_logprob && num_id && batch > 0 && max_tokens > 0,
+                "op_ctc_collapse_timed: bad argument");
+    asr_require_device(0);
+    Tmp t;
+    PackedPlan pp(seq_lens, batch);
+    std::vector<int32_t> ids(pp.Mpad, 0);
+    std::vector<float> lp(pp.Mpad, 0.0f);
+    size_t r = 0;
+    for (int b = 0; b < batch; ++b) {
+      memcpy(&ids[pp.plan[b].row_off], frame_ids + r, (size_t)seq_lens[b] * 4);
+      memcpy(&lp[pp.plan[b].row_off], frame_logprob + r, (size_t)seq_lens[b] * 4);
+      r += seq_lens[b];
+    }
+    const size_t out_bytes = (size_t)batch * max_tokens * 4;
+    int32_t* dids = (int32_t*)t.alloc((size_t)pp.Mpad * 4);
+    float* dlp = (float*)t.alloc((size_t)pp.Mpad * 4);
+    UttPlan* dplan = (UttPlan*)t.alloc(sizeof(UttPlan) * batch);
+    int32_t* dtok = (int32_t*)t.alloc(out_bytes);
+    int32_t* dfirst = (int32_t*)t.alloc(out_bytes);
+    int32_t* dlast = (int32_t*)t.alloc(out_bytes);
+    float* dtlp = (float*)t.alloc(out_bytes);
+    int32_t* dnum = (int32_t*)t.alloc((size_t)batch * 4);
+    HIP_CHECK(hipMemcpy(dids, ids.data(), (size_t)pp.Mpad * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dlp, lp.data(), (size_t)pp.Mpad * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dplan, pp.plan.data(), sizeof(UttPlan) * batch, hipMemcpyHostToDevice));
+    // the caller's arrays go up first, so that slots the kernel leaves alone come back as they were
+    HIP_CHECK(hipMemcpy(dtok, token_ids, out_bytes, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dfirst, first_frame, out_bytes, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dlast, last_frame, out_bytes, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dtlp, token_logprob, out_bytes, hipMemcpyHostToDevice));
+    launch_ctc_collapse_timed(dids, dlp, dplan, batch, blank_id, dtok, dfirst, dlast, dtlp, max_tokens, dnum, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(token_ids, dtok, out_bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(first_frame, dfirst, out_bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(last_frame, dlast, out_bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(token_logprob, dtlp, out_bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(num_id, dnum, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 extern "C" int asr_op_gemm_ln(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, int M, int N,
                               int K, float* out) {
   return asr_guard([&] {

@@ -69,6 +69,9 @@ struct GemmArgs {
   int group_m = 0;   // (set by the launcher) row tiles walked per column tile before moving on: keeps wide weight matrices L2-resident
   uint32_t* dbg_clk = nullptr;   // ping-pong kernel, timed instance (bench hook): per-phase segment clocks of two waves of workgroup 0
   int dbg = 0;   // tuning ablations (bench hook only): 1 = no refills, 2 = no MFMA, 4 = no epilogue
+  // third partial of the fused row arg-max (valid only with amax_val / amax_idx, same [M][N / 64] layout): S = sum over the slab's columns < n_valid of
+  // exp(v - slab max), 0 for a slab without a valid column. launch_argmax_lse_reduce merges the three partials into the row's log soft-max at its arg-max.
+  float* amax_sum = nullptr;
 };
 
 // operand dtype selects the kernel: bf16 MFMA (performance mode) or exact-f32 MFMA (verification mode)
@@ -137,3 +140,6 @@ void launch_gemm_fp8(const Fp8GemmArgs& g, hipStream_t s);
 
 // reduce the per-slab arg-max partials written by the GEMM epilogue: ids[m] = first index of the row max
 void launch_argmax_reduce(const float* val, const int32_t* idx, int M, int n_slabs, int32_t* ids, hipStream_t s);
+// the same with the sum-of-exponentials partials (GemmArgs::amax_sum): ids[m] as above, frame_logprob[m] = -log sum_s S_s exp(best_s - best_row),
+// the log soft-max of row m at its arg-max (<= 0)
+void launch_argmax_lse_reduce(const float* val, const int32_t* idx, const float* sum, int M, int n_slabs, int32_t* ids, float* frame_logprob, hipStream_t s);

@@ -1177,6 +1177,35 @@ __global__ void argmax_reduce_kernel(const float* __restrict__ val, const int32_
   if (lane == 0) ids[m] = bidx;
 }
 
+// the same merge with the sum-of-exponentials partials: the row's log soft-max at its arg-max. One wave per row, two passes over the row's slabs
+// (the first finds the row maximum every term is scaled by).
+__global__ void argmax_lse_reduce_kernel(const float* __restrict__ val, const int32_t* __restrict__ idx, const float* __restrict__ sum, int M, int n_slabs,
+                                         int32_t* __restrict__ ids, float* __restrict__ frame_logprob) {
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (m >= M) return;
+  float best = -INFINITY;
+  int bidx = 0x7fffffff;
+  for (int s = lane; s < n_slabs; s += 64) {
+    const float v = val[(size_t)m * n_slabs + s];
+    const int i = idx[(size_t)m * n_slabs + s];
+    if (v > best || (v == best && i < bidx)) { best = v; bidx = i; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bidx, o, 64);
+    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+  }
+  float tot = 0.0f;
+  for (int s = lane; s < n_slabs; s += 64) {
+    tot += sum[(size_t)m * n_slabs + s] * expf(val[(size_t)m * n_slabs + s] - best);      // a slab without a valid column: 0 * exp(-inf) = 0
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
+  if (lane == 0) { ids[m] = bidx; frame_logprob[m] = -logf(tot); }      // tot >= 1: the arg-max's own term is exp(0)
+}
+
 void check_args(const GemmArgs& g, int kstep, int elt) {
   ASR_REQUIRE(g.A && g.W, "gemm: null operand");
   ASR_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "gemm: empty problem M=%d N=%d K=%d", g.M, g.N, g.K);
@@ -1190,6 +1219,7 @@ void check_args(const GemmArgs& g, int kstep, int elt) {
   if (g.out_lo) ASR_REQUIRE(g.ld_out_lo % 8 == 0 && g.lo_group % 8 == 0, "gemm: ld_out_lo / lo_group must be multiples of 8");
   if (g.act == ACT_SWIGLU)
     ASR_REQUIRE(g.out_lo && !(g.add || g.add2 || g.out_f32 || g.amax_val || g.bias || g.lo_group || g.out_t), "gemm: SwiGLU stores to out_lo only");
+  if (g.amax_sum) ASR_REQUIRE(g.amax_val && g.amax_idx, "gemm: amax_sum is a third partial of the arg-max epilogue (amax_val / amax_idx missing)");
   if (g.out_t) {
     ASR_REQUIRE(!(g.add || g.add2 || g.out_f32 || g.out_lo || g.amax_val || g.act != ACT_NONE),
                 "gemm: the transposed store excludes row-major epilogue terms");
@@ -1325,7 +1355,7 @@ template <int BN_, int STAGES>
 void launch_pipe(const GemmArgs& g, hipStream_t s) {
   if (g.out_t) { launch_pipe_inst<BN_, STAGES, ACT_NONE, 0, false>(g, s); return; }
   const int epi = (g.add ? E_ADD : 0) | (g.add2 ? E_ADD2 : 0) | (g.out_f32 ? E_F32 : 0) | (g.out_lo ? E_LO : 0) |
-                  (g.amax_val ? E_AMAX : 0) | (g.bias ? E_BIAS : 0) | (g.st_out ? E_ST : 0);
+                  (g.amax_val ? E_AMAX : 0) | (g.bias ? E_BIAS : 0) | (g.st_out ? E_ST : 0) | (g.amax_sum ? E_LSE : 0);
 #define ASR_GEMM_CASE(ACT_, EPI_) \
   if (g.act == (ACT_) && epi == (EPI_)) { launch_pipe_inst<BN_, STAGES, ACT_, EPI_, true>(g, s); return; }
   ASR_GEMM_CASE(ACT_NONE, E_BIAS | E_LO)                    // q|k projection, cross-KV, plain projections
@@ -1342,6 +1372,7 @@ void launch_pipe(const GemmArgs& g, hipStream_t s) {
   ASR_GEMM_CASE(ACT_NONE, E_ADD | E_F32 | E_LO | E_ST)
   ASR_GEMM_CASE(ACT_NONE, E_BIAS | E_ADD | E_F32 | E_LO | E_ST)
   ASR_GEMM_CASE(ACT_NONE, E_BIAS | E_AMAX)                  // CTC / LM head arg-max
+  ASR_GEMM_CASE(ACT_NONE, E_BIAS | E_AMAX | E_LSE)          // ... with the per-slab sum of exponentials (timed CTC head)
   ASR_GEMM_CASE(ACT_NONE, E_BIAS | E_F32)                   // LM head logits
   ASR_GEMM_CASE(ACT_NONE, E_F32)
   ASR_GEMM_CASE(ACT_SWIGLU, E_LO)
@@ -1453,6 +1484,16 @@ bool launch_t288w_amax(const GemmArgs& g, hipStream_t s) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   }
   note_kernel("t288w_amax");
+  if (g.amax_sum) {                                          // timed CTC head: the per-slab sum of exponentials beside the (max, index) pair
+    static PerDeviceOnce lse_once;
+    if (lse_once.first()) {
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_t288w<ACT_NONE, E_BIAS | E_AMAX | E_LSE>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    }
+    hipLaunchKernelGGL((gemm_bf16_t288w<ACT_NONE, E_BIAS | E_AMAX | E_LSE>), dim3(tiles), dim3(512), lds, s, g);
+    HIP_CHECK(hipGetLastError());
+    return true;
+  }
   hipLaunchKernelGGL((gemm_bf16_t288w<ACT_NONE, E_BIAS | E_AMAX>), dim3(tiles), dim3(512), lds, s, g);
   HIP_CHECK(hipGetLastError());
   return true;
@@ -1620,6 +1661,11 @@ void launch_gemm_f32(const GemmArgs& g, hipStream_t s) {
   }
   if (g.out_t) hipLaunchKernelGGL(gemm_f32_128x128x16<false>, dim3(grid), dim3(256), 0, s, g);
   else hipLaunchKernelGGL(gemm_f32_128x128x16<true>, dim3(grid), dim3(256), 0, s, g);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_argmax_lse_reduce(const float* val, const int32_t* idx, const float* sum, int M, int n_slabs, int32_t* ids, float* frame_logprob, hipStream_t s) {
+  hipLaunchKernelGGL(argmax_lse_reduce_kernel, dim3((M + 3) / 4), dim3(256), 0, s, val, idx, sum, M, n_slabs, ids, frame_logprob);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -5,7 +5,7 @@
 
 namespace {
 
-enum { E_ADD = 1, E_ADD2 = 2, E_F32 = 4, E_LO = 8, E_AMAX = 32, E_BIAS = 64, E_LN = 128, E_ST = 256 };
+enum { E_ADD = 1, E_ADD2 = 2, E_F32 = 4, E_LO = 8, E_AMAX = 32, E_BIAS = 64, E_LN = 128, E_ST = 256, E_LSE = 512 };   // E_LSE: only together with E_AMAX
 
 template <int ACT>
 __device__ __forceinline__ float apply_act_ct(float v) {
@@ -128,6 +128,26 @@ __device__ __forceinline__ void epilogue_rows(const GemmArgs& g, f32x4_t (&acc)[
       if (fgrp == 0 && m < g.M) {
         g.amax_val[(size_t)m * n_slabs + slab] = best;
         g.amax_idx[(size_t)m * n_slabs + slab] = bidx;
+      }
+      // S = sum of exp(v - best) over the slab's valid columns, the same biased v in a second pass. Among the run-time-checked instances (EPI < 0) only
+      // those whose wave spans one 64-column slab (NJ = 4) are ever handed the head; the others keep the code they had.
+      if ((EPI >= 0 || NJ == 4) && epi_has<EPI, E_LSE>(g.amax_sum)) {
+        float sum = 0.0f;
+        if (best != -INFINITY) {                // a slab without a valid column has no term: never exp(-inf - -inf)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            const int n0 = n_wave + frag_col(j, fgrp * 4);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              float v = acc[i][j][r] + (has_bias ? (bias_at ? bias_at : g.bias)[n0 + r] : 0.0f);
+              if (n0 + r >= g.n_valid) v = -INFINITY;       // exp(-inf - best) = 0
+              sum += __expf(v - best);
+            }
+          }
+        }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        if (fgrp == 0 && m < g.M) g.amax_sum[(size_t)m * n_slabs + slab] = sum;
       }
     }
   }

@@ -284,6 +284,11 @@ void launch_fsmn(const InT* vt, int ld, const float* w, const float* b, int C, i
 // ---- CTC greedy collapse, circular next-neighbour rule (Export_SenseVoice.py:290-296)
 void launch_ctc_collapse(const int32_t* frame_ids, const UttPlan* plan, int n_utts, int blank_id, int32_t* token_ids,
                          int max_tokens, int32_t* num_id, hipStream_t s);
+// ... with each token's frame span and score: the token is emitted at last_frame = the last frame of its run, first_frame = the start of the maximal linear
+// run of equal ids ending there (frames are rows of the utterance's sequence), token_logprob = mean of frame_logprob over first..last (f32 sum in ascending
+// frame order / f32 count). Same ids, counts and max_tokens rule as launch_ctc_collapse.
+void launch_ctc_collapse_timed(const int32_t* frame_ids, const float* frame_logprob, const UttPlan* plan, int n_utts, int blank_id, int32_t* token_ids,
+                               int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, int32_t* num_id, hipStream_t s);
 
 // ---- Paraformer CIF predictor + decoder helpers (Paraformer/Non-Streaming/Export_Paraformer.py:499-563)
 // [x[t-1] | x[t] | x[t+1]] rows with zero padding at utterance edges: the k=3 conv as one GEMM (K = 3 d)

@@ -862,6 +862,62 @@ __global__ __launch_bounds__(256) void ctc_collapse_kernel(const int32_t* __rest
   if (tid == 0) num_id[u] = running;
 }
 
+// The same collapse, keeping what the walk above throws away: a token is emitted on the LAST frame t of its run, its span is [first, t] with first the
+// start of the maximal LINEAR run of equal ids ending at t (no wrap), its score the mean of frame_logprob over the span (f32 sum in ascending frame
+// order / f32 count). Run starts: every frame that differs from its predecessor (and frame 0) is a head; an inclusive max-scan of the head positions
+// gives each frame its run's start -- inside the wave by shuffles, across the four waves through LDS, across 256-frame chunks through `carry`
+// (the run start of the previous chunk's last frame), as `running` carries the count.
+__global__ __launch_bounds__(256) void ctc_collapse_timed_kernel(const int32_t* __restrict__ ids, const float* __restrict__ frame_logprob,
+                                                                 const UttPlan* __restrict__ plan, int blank_id, int32_t* __restrict__ token_ids,
+                                                                 int32_t* __restrict__ first_frame, int32_t* __restrict__ last_frame,
+                                                                 float* __restrict__ token_logprob, int max_tokens, int32_t* __restrict__ num_id) {
+  __shared__ int wave_cnt[4];
+  __shared__ int wave_head[4];
+  __shared__ int running;
+  __shared__ int carry;
+  const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = plan[u].T, base = plan[u].row_off;
+  if (tid == 0) { running = 0; carry = 0; }
+  __syncthreads();
+  for (int t0 = 0; t0 < T; t0 += 256) {
+    const int t = t0 + tid;
+    int id = 0;
+    bool keep = false;
+    int head = -1;                               // latest run start at or before t, as far as this lane / wave / chunk knows
+    if (t < T) {
+      id = ids[base + t];
+      const int nxt = ids[base + ((t + 1 == T) ? 0 : t + 1)];   // circular: last frame vs first
+      keep = (id != nxt) && (id != blank_id);
+      if (t == 0 || ids[base + t - 1] != id) head = t;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int other = __shfl_up(head, o, 64);
+      if (lane >= o) head = max(head, other);
+    }
+    const unsigned long long bal = __ballot(keep);
+    const int prefix = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_cnt[wave] = __popcll(bal);
+    if (lane == 63) wave_head[wave] = head;
+    __syncthreads();
+    int off = running + prefix;
+    for (int w2 = 0; w2 < wave; ++w2) { off += wave_cnt[w2]; head = max(head, wave_head[w2]); }
+    if (head < 0) head = carry;                  // the run began in an earlier chunk
+    if (keep && off < max_tokens) {
+      float sum = 0.0f;
+      for (int f = head; f <= t; ++f) sum += frame_logprob[base + f];
+      const size_t o = (size_t)u * max_tokens + off;
+      token_ids[o] = id; first_frame[o] = head; last_frame[o] = t;
+      token_logprob[o] = sum / (float)(t - head + 1);
+    }
+    __syncthreads();
+    if (tid == 0) running += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    if (tid == 255) carry = head;                // (a short last chunk leaves the loop: its carry is never read)
+    __syncthreads();
+  }
+  if (tid == 0) num_id[u] = running;
+}
+
 
 // ------------------------------------------------------------------------------------ Whisper log-mel finish / conv padding
 __device__ __forceinline__ int gapped_frame(const UttPlan& up, int j) {   // frame index of gapped row j, or -1
@@ -1648,6 +1704,13 @@ template void launch_fsmn<bf16_t>(const bf16_t*, int, const float*, const float*
 void launch_ctc_collapse(const int32_t* frame_ids, const UttPlan* plan, int n_utts, int blank_id, int32_t* token_ids,
                          int max_tokens, int32_t* num_id, hipStream_t s) {
   hipLaunchKernelGGL(ctc_collapse_kernel, dim3(n_utts), dim3(256), 0, s, frame_ids, plan, blank_id, token_ids, max_tokens, num_id);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_ctc_collapse_timed(const int32_t* frame_ids, const float* frame_logprob, const UttPlan* plan, int n_utts, int blank_id, int32_t* token_ids,
+                               int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, int32_t* num_id, hipStream_t s) {
+  hipLaunchKernelGGL(ctc_collapse_timed_kernel, dim3(n_utts), dim3(256), 0, s, frame_ids, frame_logprob, plan, blank_id, token_ids, first_frame, last_frame,
+                     token_logprob, max_tokens, num_id);
   HIP_CHECK(hipGetLastError());
 }
 

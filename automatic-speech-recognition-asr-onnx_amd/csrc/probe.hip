@@ -458,6 +458,57 @@ extern "C" int asr_probe_gemm(asr_probe_gemm_desc* d) {
   });
 }
 
+// The CTC head with frame log-probabilities: the arg-max GEMM with the third partial (GemmArgs::amax_sum) and launch_argmax_lse_reduce, operands set up
+// as asr_probe_gemm does with `argmax`. Every output buffer is padded to the 128-row tile edge and filled with a NaN pattern first; *stray counts the words
+// of rows >= M that no longer hold it.
+extern "C" int asr_probe_ctc_head(int M, int N, int K, const float* a, const float* w, const float* bias, int n_valid, int variant, int32_t* out_ids,
+                                  float* out_logprob, int32_t* stray, char* kernel32) {
+  return asr_guard([&] {
+    ASR_REQUIRE(a && w && bias && out_ids && out_logprob && M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 64 == 0 && n_valid >= 0 && n_valid <= N, "probe_ctc_head: bad argument");
+    asr_require_device(0);
+    gemm_reload_env();
+    Tmp t;
+    const int Mp = round_up(M, 128) + 128, n_slabs = N / 64;      // one whole spare tile of rows behind the padded operand
+    std::vector<bf16_t> ha((size_t)Mp * K, 0), hw((size_t)N * K);
+    for (size_t i = 0; i < (size_t)M * K; ++i) ha[i] = f32_to_bf16(a[i]);
+    for (size_t i = 0; i < (size_t)N * K; ++i) hw[i] = f32_to_bf16(w[i]);
+    bf16_t* da = (bf16_t*)t.alloc(ha.size() * 2);
+    bf16_t* dw = (bf16_t*)t.alloc(hw.size() * 2);
+    float* db = (float*)t.alloc((size_t)N * 4);
+    HIP_CHECK(hipMemcpy(da, ha.data(), ha.size() * 2, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(db, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+    const size_t part = (size_t)Mp * n_slabs;
+    uint32_t* dav = (uint32_t*)t.alloc(part * 4); uint32_t* dai = (uint32_t*)t.alloc(part * 4); uint32_t* das = (uint32_t*)t.alloc(part * 4);
+    uint32_t* dids = (uint32_t*)t.alloc((size_t)Mp * 4); uint32_t* dlp = (uint32_t*)t.alloc((size_t)Mp * 4);
+    for (uint32_t* p : {dav, dai, das}) HIP_CHECK(hipMemset(p, 0xff, part * 4));       // 0xffffffff: a NaN as f32, -1 as an index
+    for (uint32_t* p : {dids, dlp}) HIP_CHECK(hipMemset(p, 0xff, (size_t)Mp * 4));
+    GemmArgs g;
+    g.A = da; g.lda = K; g.W = dw; g.ldw = K; g.M = M; g.N = N; g.K = K; g.bias = db;
+    g.sk_ws = (float*)t.alloc((size_t)16 << 20); g.sk_ws_bytes = (size_t)16 << 20; g.sk_cnt = (int32_t*)t.alloc(4096 * 4);
+    g.amax_val = (float*)dav; g.amax_idx = (int32_t*)dai; g.amax_sum = (float*)das; g.n_valid = n_valid > 0 ? n_valid : N;
+    gemm_set_variant(variant);
+    try { launch_gemm_bf16(g, nullptr); } catch (...) { gemm_set_variant(-1); throw; }
+    gemm_set_variant(-1);
+    if (kernel32) snprintf(kernel32, 32, "%s", gemm_last_kernel());
+    launch_argmax_lse_reduce((const float*)dav, (const int32_t*)dai, (const float*)das, M, n_slabs, (int32_t*)dids, (float*)dlp, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out_ids, dids, (size_t)M * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(out_logprob, dlp, (size_t)M * 4, hipMemcpyDeviceToHost));
+    if (stray) {
+      int bad = 0;
+      std::vector<uint32_t> h;
+      auto tail = [&](const uint32_t* p, size_t per_row) {
+        h.resize((size_t)(Mp - M) * per_row);
+        HIP_CHECK(hipMemcpy(h.data(), p + (size_t)M * per_row, h.size() * 4, hipMemcpyDeviceToHost));
+        for (uint32_t v : h) bad += v != 0xffffffffu;
+      };
+      tail(dav, n_slabs); tail(dai, n_slabs); tail(das, n_slabs); tail(dids, 1); tail(dlp, 1);
+      *stray = bad;
+    }
+  });
+}
+
 // ---- decoder attention (launch_decode_attention) on host arrays: self-attention over a contiguous or paged cache, cross-attention over
 // packed slabs (optionally FP8 through the product's quantiser). Reports which form the dispatcher chose (asr_mi355x_probe.h).
 namespace {

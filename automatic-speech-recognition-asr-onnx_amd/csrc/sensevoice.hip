@@ -56,6 +56,7 @@ struct SvSession : asr_session {
   DeviceBuffer d_x0lo, d_xalo, d_xblo;     // bf16 copies of the residual stream (operands of the LayerNorm-fused projections)
   DeviceBuffer d_plan, d_audio, d_mel, d_x0, d_xa, d_xb, d_h, d_qk, d_vt, d_ctx, d_mem, d_ffn, d_amax_v, d_amax_i, d_ids,
       d_tok, d_num, d_logits;
+  DeviceBuffer d_amax_s, d_flp, d_first, d_last, d_tlp;   // timed runs only: sum-of-exponentials partials, frame log-probabilities, token spans and scores
   PinnedBuffer h_plan, h_out;   // pinned staging
 
   // ---- streaming Paraformer (kind 4): per-stream recurrent state in HBM, every step advances n streams by one chunk
@@ -139,8 +140,10 @@ struct SvSession : asr_session {
   void init();
   void copy_block_status(const struct SvRunCtx& r);   // the block kernel's error word rides home behind the token counts
   template <typename T> void enqueue(const struct SvRunCtx& r);
+  // first_out / last_out / logprob_out all set: the timed form (asr_sensevoice_run_timed) -- the CTC head also yields each token's frame span and score
   template <typename T> void run(const void* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang,
-                                 int32_t* tok_out, int max_tokens, int32_t* num_out);
+                                 int32_t* tok_out, int max_tokens, int32_t* num_out, int32_t* first_out = nullptr, int32_t* last_out = nullptr,
+                                 float* logprob_out = nullptr);
   DeviceBuffer d_skws, d_skcnt;        // split-K workspace + tickets of the skinny GEMM (per session: sessions may run concurrently)
   void gemm(const GemmArgs& g0) {
     if (!d_skws.ptr) { d_skws.reserve((size_t)16 << 20, stream); d_skcnt.reserve(4096 * 4, stream); }
@@ -273,6 +276,7 @@ struct SvRunCtx {
   const int32_t *d_tile_win = nullptr, *d_tile_idx = nullptr;    // small batches (sanm_tiles.hip): per 16-row tile its window / its index inside the window
   int n_tiles = 0;
   bool tiles = false;
+  bool timed = false;         // CTC head with frame log-probabilities, collapse with spans
 };
 
 // fragment-major weight copies for the 8-wave block kernel: one pass over the arena's bf16 matrices per session, outside any graph capture
@@ -562,23 +566,38 @@ void SvSession::enqueue(const SvRunCtx& r) {
     GemmArgs g;
     g.A = h; g.lda = d; g.W = ctc_w; g.ldw = d; g.M = rows; g.N = vpad; g.K = d; g.bias = ctc_b;
     g.amax_val = d_amax_v.as<float>(); g.amax_idx = d_amax_i.as<int32_t>(); g.n_valid = c.vocab;
+    if (r.timed) g.amax_sum = d_amax_s.as<float>();
     if (taps_enabled) { g.out_f32 = d_logits.as<float>(); g.ld_out_f32 = vpad; }
     gemm(g);
   }
   {
     ProfScope ps(prof, "ctc_tail", stream);
-    launch_argmax_reduce(d_amax_v.as<float>(), d_amax_i.as<int32_t>(), rows, n_slabs, d_ids.as<int32_t>(), stream);
-    launch_ctc_collapse(d_ids.as<int32_t>(), r.dp, r.batch, c.blank_id, d_tok.as<int32_t>(), r.max_tokens, d_num.as<int32_t>(), stream);
+    if (r.timed) {
+      launch_argmax_lse_reduce(d_amax_v.as<float>(), d_amax_i.as<int32_t>(), d_amax_s.as<float>(), rows, n_slabs, d_ids.as<int32_t>(), d_flp.as<float>(), stream);
+      launch_ctc_collapse_timed(d_ids.as<int32_t>(), d_flp.as<float>(), r.dp, r.batch, c.blank_id, d_tok.as<int32_t>(), d_first.as<int32_t>(), d_last.as<int32_t>(),
+                                d_tlp.as<float>(), r.max_tokens, d_num.as<int32_t>(), stream);
+    } else {
+      launch_argmax_reduce(d_amax_v.as<float>(), d_amax_i.as<int32_t>(), rows, n_slabs, d_ids.as<int32_t>(), stream);
+      launch_ctc_collapse(d_ids.as<int32_t>(), r.dp, r.batch, c.blank_id, d_tok.as<int32_t>(), r.max_tokens, d_num.as<int32_t>(), stream);
+    }
   }
   if (taps_enabled) {
     save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
     save_tap("frame_ids", d_ids.ptr, rows, 1, 1, 4);
+    if (r.timed) save_tap("frame_logprob", d_flp.ptr, rows, 1, 1, 4);
   }
   // ---- outputs (pinned host staging) ---------------------------------------------------------
-  HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, (size_t)r.batch * r.max_tokens * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)r.batch * r.max_tokens * 4, d_num.ptr, (size_t)r.batch * 4,
+  const size_t tok_bytes = (size_t)r.batch * r.max_tokens * 4;
+  HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + tok_bytes, d_num.ptr, (size_t)r.batch * 4,
                            hipMemcpyDeviceToHost, stream));
   copy_block_status(r);
+  if (r.timed) {                                          // spans and scores ride behind the existing outputs (tokens, counts, 16 status bytes)
+    unsigned char* ext = h_out.as<unsigned char>() + tok_bytes + (size_t)r.batch * 4 + 16;
+    HIP_CHECK(hipMemcpyAsync(ext, d_first.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(ext + tok_bytes, d_last.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(ext + 2 * tok_bytes, d_tlp.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+  }
 }
 
 
@@ -715,8 +734,10 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
 
 template <typename T>
 void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang, int32_t* tok_out,
-                    int max_tokens, int32_t* num_out) {
+                    int max_tokens, int32_t* num_out, int32_t* first_out, int32_t* last_out, float* logprob_out) {
   const auto& c = cfg;
+  const bool timed = first_out != nullptr;
+  ASR_REQUIRE(!timed || (last_out && logprob_out && !paraformer), "sensevoice: the timed form needs all three span outputs (CTC sessions only)");
   ASR_REQUIRE(batch > 0, "sensevoice: empty batch");
   ASR_REQUIRE(audio && offs && (lang || paraformer) && tok_out && num_out, "sensevoice: null argument");
   HIP_CHECK(hipSetDevice(device));
@@ -823,6 +844,13 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   grow(d_tok, (size_t)batch * max_tokens * 4);
   grow(d_num, (size_t)batch * 4);
   if (taps_enabled) grow(d_logits, (size_t)Mpad * vpad * 4);
+  if (timed) {
+    grow(d_amax_s, (size_t)Mpad * n_slabs * 4);
+    grow(d_flp, (size_t)Mpad * 4);
+    grow(d_first, (size_t)batch * max_tokens * 4);
+    grow(d_last, (size_t)batch * max_tokens * 4);
+    grow(d_tlp, (size_t)batch * max_tokens * 4);
+  }
   if (paraformer) {
     const int dd = pcfg.d_dec_ffn;
     grow(d_enc_lo, (size_t)Mpad * d * eT);
@@ -840,7 +868,7 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
     grow(d_mdev, 256);
     grow(d_trow, (size_t)Mpad * 4);
   }
-  const size_t out_bytes = (size_t)batch * max_tokens * 4 + (size_t)batch * 4 + 16;
+  const size_t out_bytes = (size_t)batch * max_tokens * 4 + (size_t)batch * 4 + 16 + (timed ? (size_t)batch * max_tokens * 12 : 0);
   if (h_out.reserve(out_bytes)) ++ws_epoch;
 
   HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan.ptr, plan_bytes, hipMemcpyHostToDevice, stream));
@@ -852,7 +880,7 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   r.batch = batch; r.rows = rows; r.Mpad = Mpad; r.frames = frames; r.n_fb = n_fb; r.n_qb = n_qb; r.max_T = max_T;
   r.max_tokens = max_tokens; r.att_qt = att_qt; r.att_nw = att_nw;
   r.dp = d_plan.as<UttPlan>();
-  r.n_tiles = n_tiles; r.tiles = tiles;
+  r.n_tiles = n_tiles; r.tiles = tiles; r.timed = timed;
   r.d_blk_utt = (const int32_t*)((unsigned char*)d_plan.ptr + sizeof(UttPlan) * batch);
   r.d_blk_f0 = r.d_blk_utt + n_fb;
   r.d_qb_utt = r.d_blk_f0 + n_fb;
@@ -862,6 +890,7 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   r.d_tile_idx = r.d_tile_win + n_tiles;
   key.mix((uint64_t)batch); key.mix((uint64_t)max_tokens); key.mix((uint64_t)(uintptr_t)r.d_aud); key.mix((uint64_t)audio_dtype); key.mix(ws_epoch); key.mix((uint64_t)(uintptr_t)stream);
   key.mix((uint64_t)(block_cooldown > 0 || foreign_now));        // a session cooling down after a cluster give-up replays the four-launch capture, not the block one
+  key.mix((uint64_t)timed);                                      // the timed CTC tail is another launch sequence
 
   if (sizeof(T) == 2 && use_block && cfg.n_blocks > 1 && blocks[cfg.n_blocks - 1].cqkv && blocks[cfg.n_blocks - 1].c1 && batch >= block_min_utts &&
       sanm_block_supported(max_T, cfg.d_head, cfg.n_heads, cfg.d_model, cfg.d_ffn, cfg.fsmn_kernel))
@@ -941,6 +970,16 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   for (int b = 0; b < batch; ++b) {
     const int n = std::min(num_out[b], max_tokens);
     memcpy(tok_out + (size_t)b * max_tokens, ht + (size_t)b * max_tokens, (size_t)n * 4);
+  }
+  if (timed) {
+    const size_t tok_bytes = (size_t)batch * max_tokens * 4;
+    const unsigned char* ext = h_out.as<const unsigned char>() + tok_bytes + (size_t)batch * 4 + 16;
+    for (int b = 0; b < batch; ++b) {
+      const size_t n = (size_t)std::min(num_out[b], max_tokens) * 4, o = (size_t)b * max_tokens * 4;
+      memcpy((unsigned char*)first_out + o, ext + o, n);
+      memcpy((unsigned char*)last_out + o, ext + tok_bytes + o, n);
+      memcpy((unsigned char*)logprob_out + o, ext + 2 * tok_bytes + o, n);
+    }
   }
 }
 
@@ -1513,6 +1552,21 @@ extern "C" int asr_sensevoice_run(asr_session* s, const void* audio, int audio_m
       sv->run<bf16_t>(audio, audio_mem, audio_offsets, batch, language_idx, token_ids_out, max_tokens, num_id_out);
     else
       sv->run<float>(audio, audio_mem, audio_offsets, batch, language_idx, token_ids_out, max_tokens, num_id_out);
+  });
+}
+
+extern "C" int asr_sensevoice_run_timed(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+                                        const int32_t* language_idx, int32_t* token_ids_out, int max_tokens, int32_t* num_id_out,
+                                        int32_t* first_frame_out, int32_t* last_frame_out, float* logprob_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 1, "sensevoice_run_timed: not a SenseVoice session");
+    ASR_REQUIRE(first_frame_out && last_frame_out && logprob_out, "sensevoice_run_timed: null span output");
+    TenantScope tenant(s);
+    SvSession* sv = static_cast<SvSession*>(s);
+    if (sv->precision == ASR_PRECISION_BF16)
+      sv->run<bf16_t>(audio, audio_mem, audio_offsets, batch, language_idx, token_ids_out, max_tokens, num_id_out, first_frame_out, last_frame_out, logprob_out);
+    else
+      sv->run<float>(audio, audio_mem, audio_offsets, batch, language_idx, token_ids_out, max_tokens, num_id_out, first_frame_out, last_frame_out, logprob_out);
   });
 }
 

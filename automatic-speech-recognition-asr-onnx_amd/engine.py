@@ -198,6 +198,37 @@ class SenseVoiceSession(_Session):
         tok, num = self.run_packed(packed, offs, np.asarray(language_idx, dtype=np.int32))
         return [tok[b, :num[b]].copy() for b in range(len(flat))]
 
+    def run_packed_timed(self, audio, offsets: np.ndarray, language_idx: np.ndarray, audio_device_ptr: int | None = None):
+        """run_packed with a frame span and a confidence per token (asr_sensevoice_run_timed). Returns (token_ids, num_id, first_frame, last_frame,
+        logprob): the three new arrays are [B, max_T] like token_ids (int32, int32, float32), row b valid up to num_id[b]. Frames are rows of the
+        utterance's sequence, prompt rows included (SenseVoiceConfig.row_span_seconds maps them to seconds); logprob is the mean over the token's
+        frames of log soft-max at the frame's arg-max."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        lang = np.ascontiguousarray(language_idx, dtype=np.int32)
+        B = lang.shape[0]
+        assert offsets.shape[0] == B + 1
+        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        tok = np.zeros((B, max_t), dtype=np.int32)
+        first, last = np.zeros((B, max_t), dtype=np.int32), np.zeros((B, max_t), dtype=np.int32)
+        logprob = np.zeros((B, max_t), dtype=np.float32)
+        num = np.zeros((B,), dtype=np.int32)
+        lib = _lib.load()
+        if audio_device_ptr is not None:
+            ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
+        else:
+            audio = self._audio(audio).reshape(-1)
+            ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
+        _lib.check(lib.asr_sensevoice_run_timed(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(lang),
+                                                _ip(tok), max_t, _ip(num), _ip(first), _ip(last), _fp(logprob)))
+        return tok, num, first, last, logprob
+
+    def run_timed(self, audios: Sequence[np.ndarray], language_idx: Sequence[int]):
+        """List of 1-D utterances -> one record per utterance: {"ids", "first_frame", "last_frame", "logprob"}, arrays of equal length."""
+        flat, packed, offs = self._pack(audios)
+        tok, num, first, last, logprob = self.run_packed_timed(packed, offs, np.asarray(language_idx, dtype=np.int32))
+        return [{"ids": tok[b, :num[b]].copy(), "first_frame": first[b, :num[b]].copy(), "last_frame": last[b, :num[b]].copy(),
+                 "logprob": logprob[b, :num[b]].copy()} for b in range(len(flat))]
+
     def utterance_rows(self, lengths: Sequence[int]):
         """(row_off, T) of each utterance inside the packed tap tensors (16-row aligned)."""
         out, r = [], 0
@@ -261,6 +292,24 @@ def op_ctc_collapse(frame_ids, seq_lens, blank_id=0):
     num = np.zeros((sl.size,), dtype=np.int32)
     _lib.check(_lib.load().asr_op_ctc_collapse(_ip(ids), _ip(sl), sl.size, blank_id, _ip(tok), max_t, _ip(num)))
     return [tok[b, :num[b]].copy() for b in range(sl.size)]
+
+
+def op_ctc_collapse_timed(frame_ids, frame_logprob, seq_lens, blank_id=0, max_tokens=None, fill=None):
+    """The collapse with spans on host arrays (asr_op_ctc_collapse_timed). Returns (token_ids, first_frame, last_frame, token_logprob, num_id): the four
+    arrays are [B, max_tokens] (default: the longest sequence) and start out holding `fill` = (int, float) (default zeros), which slots the kernel does
+    not write keep; num_id holds the full token count."""
+    ids = np.ascontiguousarray(frame_ids, dtype=np.int32)
+    lp = _f32(frame_logprob)
+    sl = np.ascontiguousarray(seq_lens, dtype=np.int32)
+    assert ids.size == lp.size == int(sl.sum())
+    max_t = int(sl.max()) if max_tokens is None else int(max_tokens)
+    fi, ff = (0, 0.0) if fill is None else fill
+    tok, first, last = (np.full((sl.size, max_t), fi, dtype=np.int32) for _ in range(3))
+    tlp = np.full((sl.size, max_t), ff, dtype=np.float32)
+    num = np.zeros((sl.size,), dtype=np.int32)
+    _lib.check(_lib.load().asr_op_ctc_collapse_timed(_ip(ids), _fp(lp), _ip(sl), sl.size, blank_id, _ip(tok), _ip(first), _ip(last), _fp(tlp), max_t,
+                                                     _ip(num)))
+    return tok, first, last, tlp, num
 
 
 def op_gemm_bench(M, N, K, variant=-1, epilogue=0, iters=50) -> float:

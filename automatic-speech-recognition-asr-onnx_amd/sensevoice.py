@@ -89,8 +89,23 @@ class SenseVoiceTranscriber:
             self.tokenizer = SentencePieceProcessor()
             self.tokenizer.Load(tokenizer_path)
 
-    def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False):
-        """int16 mono PCM at `sample_rate` -> dict(token_ids, text, rtf, windows)."""
+    def _run_window_timed(self, win: np.ndarray, language_idx: np.ndarray, offset_s: float, duration_s: float):
+        """One window through the native session under the shim session (the graph's two outputs carry no spans): (token ids, token records with the
+        window's offset added and both ends clipped to the audio's duration)."""
+        native = self.session._native
+        offsets = np.array([0, win.size], dtype=np.int64)
+        tok, num, first, last, logprob = native.run_packed_timed(win.reshape(-1), offsets, np.asarray(language_idx, dtype=np.int32).reshape(-1))
+        n = int(num[0])
+        tokens = []
+        for k in range(n):
+            t0, t1 = native.cfg.row_span_seconds(first[0, k], last[0, k])
+            tokens.append({"id": int(tok[0, k]), "start": min(offset_s + t0, duration_s), "end": min(offset_s + t1, duration_s),
+                           "logprob": float(logprob[0, k])})
+        return tok[0, :n].copy(), tokens
+
+    def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False, timestamps: bool = False):
+        """int16 mono PCM at `sample_rate` -> dict(token_ids, text, rtf, windows). timestamps=True adds "tokens": one {"id", "start", "end", "logprob"}
+        per token over all windows, in seconds of the whole audio (SenseVoiceConfig.row_span_seconds; logprob = mean frame log-probability)."""
         audio_len = int(np.asarray(audio_int16).size)
         audio = prepare_audio_input(np.asarray(audio_int16, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype,
                                     audio_pcm_scale=self.audio_pcm_scale, normalise=normalise)
@@ -110,23 +125,30 @@ class SenseVoiceTranscriber:
             language_buffer = onnxruntime.OrtValue.ortvalue_from_numpy(language_idx, "cpu", 0)
             binding.bind_ortvalue_input(self.audio_meta.name, audio_buffer)
             binding.bind_ortvalue_input(self.lang_meta.name, language_buffer)
-        ids_all, text = [], ""
+        ids_all, text, tokens_all = [], "", []
         start, end = 0, window
         t0 = time.time()
         while end <= aligned:
             win = array_for(self.audio_meta, audio[:, :, start:end], axes={0: 1, 1: 1, 2: window})
-            if audio_buffer is None:
-                binding.bind_cpu_input(self.audio_meta.name, win)
+            if timestamps:
+                token_ids, toks = self._run_window_timed(win, language_idx, start / self.sample_rate, audio_len / self.sample_rate)
+                tokens_all.extend(toks)
             else:
-                audio_buffer.update_inplace(win)
-            binding._iobinding.bind_output(self.out_name0, self.ort_device)     # token count is data dependent: re-bind per run
-            self.session.run_with_iobinding(binding, run_options=self.run_options)
-            token_ids = binding.get_outputs()[0].numpy()
+                if audio_buffer is None:
+                    binding.bind_cpu_input(self.audio_meta.name, win)
+                else:
+                    audio_buffer.update_inplace(win)
+                binding._iobinding.bind_output(self.out_name0, self.ort_device)     # token count is data dependent: re-bind per run
+                self.session.run_with_iobinding(binding, run_options=self.run_options)
+                token_ids = binding.get_outputs()[0].numpy()
             ids_all.append(token_ids.copy())
             if self.tokenizer is not None:
                 text += self.tokenizer.decode([token_ids.tolist()])[0]
             start += stride
             end = start + window
         wall = time.time() - t0
-        return {"token_ids": ids_all, "text": text if self.tokenizer is not None else None,
-                "rtf": wall / (audio_len / self.sample_rate), "windows": len(ids_all), "language": self.language}
+        out = {"token_ids": ids_all, "text": text if self.tokenizer is not None else None,
+               "rtf": wall / (audio_len / self.sample_rate), "windows": len(ids_all), "language": self.language}
+        if timestamps:
+            out["tokens"] = tokens_all
+        return out

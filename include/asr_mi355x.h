@@ -132,6 +132,15 @@ int asr_sensevoice_create(const asr_sensevoice_config* cfg, const void* arena, s
  * ids, rest untouched); num_id_out: host [B]. Fails if any utterance is shorter than one frame. */
 int asr_sensevoice_run(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                        const int32_t* language_idx, int32_t* token_ids_out, int max_tokens, int32_t* num_id_out);
+/* The same forward pass with a time span and a confidence per token (no reference counterpart: the reference graph returns ids only). The CTC head also
+ * yields log soft-max at the arg-max of every row (frame log-probability); the collapse keeps, for the token emitted on the last row of its run of equal
+ * ids, first_frame_out = the first row of that run (runs do not wrap), last_frame_out = that last row, logprob_out = the mean frame log-probability over
+ * first..last (<= 0). Rows are indices into the utterance's sequence, the n_prompt prompt rows included: row j >= n_prompt covers samples
+ * [(j - n_prompt) lfr_n hop_length, (j - n_prompt + 1) lfr_n hop_length). The three arrays are host [B][max_tokens] with the row contract of token_ids_out.
+ * Token ids and counts equal asr_sensevoice_run's. */
+int asr_sensevoice_run_timed(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+                             const int32_t* language_idx, int32_t* token_ids_out, int max_tokens, int32_t* num_id_out,
+                             int32_t* first_frame_out, int32_t* last_frame_out, float* logprob_out);
 
 /* sequence length (prompt + LFR rows) the graph produces for an utterance of n_samples */
 int asr_sensevoice_seq_len(const asr_sensevoice_config* cfg, int n_samples, int* seq_len);
@@ -379,6 +388,10 @@ int asr_op_gemm_ln(const float* x, const float* w, const float* bias, const floa
                    float* out);
 int asr_op_ctc_collapse(const int32_t* frame_ids, const int32_t* seq_lens, int batch, int blank_id, int32_t* token_ids,
                         int max_tokens, int32_t* num_id);
+/* the collapse of asr_sensevoice_run_timed on host arrays: frame_logprob [sum T] beside frame_ids; first_frame / last_frame / token_logprob host
+ * [batch][max_tokens] (slots at or past the token count, or past max_tokens, are not written) */
+int asr_op_ctc_collapse_timed(const int32_t* frame_ids, const float* frame_logprob, const int32_t* seq_lens, int batch, int blank_id,
+                              int32_t* token_ids, int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, int32_t* num_id);
 
 #ifdef __cplusplus
 }

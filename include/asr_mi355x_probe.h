@@ -32,6 +32,12 @@ typedef struct asr_probe_gemm_desc {
   char kernel[32];         /* out: "t288w", "t288w_amax", "t144w", "t144", "big", "pipe", "pipe_splitk", "skinny" */
 } asr_probe_gemm_desc;
 int asr_probe_gemm(asr_probe_gemm_desc* d);
+/* The CTC head with frame log-probabilities through the same dispatcher: operands as asr_probe_gemm with `argmax` (bias required), the arg-max epilogue also
+ * writes the per-slab sum of exponentials and the row reduce merges the three partials. out_ids[M]: first index of the row maximum over n < n_valid (0 = N);
+ * out_logprob[M]: log soft-max of the row at that index. `variant` as above. *stray (nullable): words of the padded rows >= M that the launches wrote.
+ * kernel32 (nullable, 32 bytes): the GEMM kernel family that ran. */
+int asr_probe_ctc_head(int M, int N, int K, const float* a, const float* w, const float* bias, int n_valid, int variant, int32_t* out_ids,
+                       float* out_logprob, int32_t* stray, char* kernel32);
 
 /* Decode-shaped GEMM (M <= 64 rows) as a captured chain of dependent launches over `cold_mb` megabytes of weight copies (larger than
  * the Infinity Cache => every launch streams its weights from HBM, like a decoder stack does once per token): microseconds per launch.

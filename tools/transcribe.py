@@ -51,6 +51,9 @@ def run(a) -> dict:
     prec = 1 if a.precision == "f32" else 0
     if (a.precision == "fp8mm" and a.family != "whisper") or (a.precision in ("fp8w", "mxfp4w") and a.family not in ("whisper", "qwen_asr")):
         raise SystemExit("--precision %s exists for --family whisper%s only" % (a.precision, " / qwen_asr" if a.precision == "fp8w" else ""))
+    timestamps = getattr(a, "timestamps", False)
+    if timestamps and a.family != "sensevoice":
+        raise SystemExit("--timestamps exists for --family sensevoice only")
     files = []
     if a.family in ("sensevoice", "paraformer"):
         mod = _m(a.family)
@@ -60,9 +63,14 @@ def run(a) -> dict:
             tr = mod.ParaformerTranscriber(a.model, vocab_path=a.tokenizer, device_type="cuda")
         for p in a.wav:
             pcm = audio_io.read_wav_int16(p, tr.sample_rate, exact_width=a.strict_wav)
-            r = tr.transcribe(pcm, sliding_window=a.sliding_window)
+            if timestamps:
+                r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=True)
+            else:
+                r = tr.transcribe(pcm, sliding_window=a.sliding_window)
             files.append({"path": p, "n_samples": int(pcm.size), "language": r.get("language", a.language),
                           "windows": [np.asarray(w).reshape(-1).astype(int).tolist() for w in r["token_ids"]], "text": r.get("text"), "rtf": r["rtf"]})
+            if timestamps:
+                files[-1]["tokens"] = r["tokens"]
     elif a.family == "whisper":
         info, blob = shim.load_model(os.path.join(a.model, "Whisper.asrmodel"))
         cfg = cfgm.WhisperConfig(**info["config"])
@@ -173,6 +181,7 @@ def main():
     r.add_argument("--sliding-window", type=int, default=0)
     r.add_argument("--repeat-penalty", type=float, default=1.0, help="1.0 = plain greedy (the comparison default); the reference scripts default to 0.8")
     r.add_argument("--beam", type=int, default=1, help="beam width (Whisper, Qwen3-ASR; 1 = greedy); > 1 takes the first hypothesis and needs --repeat-penalty 1")
+    r.add_argument("--timestamps", action="store_true", help="SenseVoice: add each token's start / end (seconds) and mean frame log-probability to the dump")
     r.add_argument("--out", required=True)
     r.add_argument("--any-wav-width", dest="strict_wav", action="store_false",
                    help="accept 8 / 24 / 32-bit wav (rescaled to int16); by default only 16-bit wav is taken: the only width whose samples equal the reference's, "
