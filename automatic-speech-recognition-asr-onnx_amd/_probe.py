@@ -53,7 +53,9 @@ class TokenHeadDesc(C.Structure):
                 ("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float), ("noise", _fp), ("seed", C.c_uint64),
                 ("no_speech_id", C.c_int32), ("out_v", _fp), ("out_i", _ip),
                 ("steps", C.c_int32), ("track_history", C.c_int32), ("sampling", C.c_int32), ("change_step", C.c_int32), ("range2", C.c_int32),
-                ("value2", C.c_float), ("picks", _ip)]
+                ("value2", C.c_float), ("picks", _ip),
+                ("timestamps", C.c_int32), ("ts_begin", C.c_int32), ("no_timestamps_id", C.c_int32), ("eot_id", C.c_int32), ("max_initial", C.c_int32),
+                ("n_saved_rows", _ip)]
 
 
 SIGNATURES = {
@@ -320,15 +322,16 @@ def beam_select(beam, K, n_slots, topv, topi, cum, fin, length, nxt, done, src_i
 
 
 PAD_LOGIT = np.float32(1e30)              # what token_head puts in the pad columns [n_valid, ld) of every logits row
-_HEAD_OPS = {"argmax_rows": 0, "beam_topk": 1, "apply_penalty": 2, "append_ids": 3, "sample_topk_topp": 4, "no_speech_prob": 5}
+_HEAD_OPS = {"argmax_rows": 0, "beam_topk": 1, "apply_penalty": 2, "append_ids": 3, "sample_topk_topp": 4, "no_speech_prob": 5, "timestamp_rules": 7}
 
 
 def token_head(op, logits=None, vec=None, K=0, save_ids=None, n_saved=0, range_=0, value=1.0, partial=0, next_ids=None,
-               temperature=1.0, top_p=1.0, repetition_penalty=1.0, noise=None, seed=0, no_speech_id=0):
+               temperature=1.0, top_p=1.0, repetition_penalty=1.0, noise=None, seed=0, no_speech_id=0, timestamps=None):
     """One token-selection head (asr_mi355x_probe.h: asr_probe_token_head) through its product launcher; `op` is the launcher's name less "launch_".
 
     logits [rows][n_valid] are laid out with the sessions' leading dimension ld = roundup(n_valid, 128), the pad filled with PAD_LOGIT (+1e30: a kernel
     that lets a pad column into a maximum, a top-k list or a soft-max sum fails visibly); vec (extra / bias / penalty, [n_valid]) gets zeros there.
+    timestamp_rules: timestamps = (ts_begin, no_timestamps_id, eot_id, max_initial); n_saved is one length for every row or an array of per-row lengths.
     Returns a dict: the head's outputs (ids | topv, topi | next | prob), logits [rows][ld] after the call, save_ids (the whole table) and n_saved after it."""
     d = TokenHeadDesc()
     d.op = _HEAD_OPS[op]
@@ -351,7 +354,15 @@ def token_head(op, logits=None, vec=None, K=0, save_ids=None, n_saved=0, range_=
     if save_ids is not None:
         out["save_ids"] = np.array(save_ids, np.int32, order="C", copy=True)
         assert out["save_ids"].ndim == 2 and out["save_ids"].shape[0] == rows
-        d.save_ids, d.ld_save, d.n_saved = out["save_ids"].ctypes.data_as(_ip), out["save_ids"].shape[1], n_saved
+        d.save_ids, d.ld_save = out["save_ids"].ctypes.data_as(_ip), out["save_ids"].shape[1]
+        if np.ndim(n_saved) == 0:
+            d.n_saved = int(n_saved)
+        else:
+            per_row = np.ascontiguousarray(n_saved, np.int32)
+            assert op == "timestamp_rules" and per_row.shape == (rows,)
+            keep.append(per_row); d.n_saved_rows = per_row.ctypes.data_as(_ip)
+    if timestamps is not None:
+        d.ts_begin, d.no_timestamps_id, d.eot_id, d.max_initial = (int(v) for v in timestamps)
     d.range, d.partial, d.value = range_, partial, value
     if next_ids is not None:
         nx = np.ascontiguousarray(next_ids, np.int32)
@@ -377,10 +388,11 @@ def token_head(op, logits=None, vec=None, K=0, save_ids=None, n_saved=0, range_=
     return out
 
 
-def head_steps(logits, steps, ld_save, range_, value, partial, bias=None, track_history=False, sampler=None, noise=None, change=None):
+def head_steps(logits, steps, ld_save, range_, value, partial, bias=None, track_history=False, sampler=None, noise=None, change=None, timestamps=None):
     """A TokenHead (csrc/decode_head.h) driven through `steps` decoder steps on the same logits rows (asr_probe_token_head, op 6): step 0 is a prefill
     (`bias` added, no penalty), the others are decode steps. sampler: (temperature, top_k, top_p, repetition_penalty, seed) or None; noise: uniforms
-    [rows][top_k] armed for step 0; change: (step, value, range) -- set_penalty before that step. Rows are padded as token_head pads them.
+    [rows][top_k] armed for step 0; change: (step, value, range) -- set_penalty before that step; timestamps: (ts_begin, no_timestamps_id, eot_id,
+    max_initial) -- Whisper's timestamp mode on. Rows are padded as token_head pads them.
     Returns {"picks": [steps][rows], "save_ids": the final history [rows][ld_save], "n_saved": the counter}."""
     logits = _f32(logits)
     rows, n_valid = logits.shape
@@ -402,6 +414,8 @@ def head_steps(logits, steps, ld_save, range_, value, partial, bias=None, track_
         d.noise = noise.ctypes.data_as(_fp)
     if change is not None:
         d.change_step, d.value2, d.range2 = change
+    if timestamps is not None:
+        d.timestamps, (d.ts_begin, d.no_timestamps_id, d.eot_id, d.max_initial) = 1, (int(v) for v in timestamps)
     out = {"picks": np.full((steps, rows), -1, np.int32), "save_ids": np.full((rows, ld_save), -1, np.int32)}
     d.picks, d.save_ids = out["picks"].ctypes.data_as(_ip), out["save_ids"].ctypes.data_as(_ip)
     _lib.check(load().asr_probe_token_head(C.byref(d)))

@@ -17,6 +17,22 @@ ASR_LOCAL inline bool reserve_moved(DeviceBuffer& buf, size_t bytes, hipStream_t
   return buf.ptr != before;
 }
 
+// ---- Whisper's timestamp rules (kernels.h: launch_timestamp_rules) as a head / ranker setting; off for every other family
+struct ASR_LOCAL TimestampRule {
+  bool on = false;
+  int ts_begin = 0, no_timestamps_id = 0, eot_id = 0, max_initial = -1;
+  bool operator==(const TimestampRule& o) const {
+    return on == o.on && ts_begin == o.ts_begin && no_timestamps_id == o.no_timestamps_id && eot_id == o.eot_id && max_initial == o.max_initial;
+  }
+  void enqueue(Profiler* prof, float* logits, int ld, int rows, int n_valid, const int32_t* ids, int ld_ids, const int32_t* n_ids, int n_ids_stride,
+               hipStream_t s) const {
+    const bool timed = prof && prof->enabled;
+    if (timed) prof->begin(prof->cls("timestamp_rules"), s);
+    launch_timestamp_rules(logits, ld, rows, n_valid, ids, ld_ids, n_ids, n_ids_stride, ts_begin, no_timestamps_id, eot_id, max_initial, s);
+    if (timed) prof->end(s);
+  }
+};
+
 // ---- token-selection head (Export_Whisper.py:228-325, Inference_Qwen_ASR_ONNX.py:369-376): arg-max, penalty-greedy (APPLY_PENALTY + GREEDY_SEARCH) or
 // TOPK_TOPP_SAMPLING, and the history of picked ids [rows][ld_save] the last two read. What differs between the families is data, set by init().
 struct ASR_LOCAL TokenHead {
@@ -30,6 +46,8 @@ struct ASR_LOCAL TokenHead {
   float temperature = 0.8f, top_p = 0.95f, samp_rep_penalty = 1.0f;
   int top_k = 10;
   uint64_t samp_seed = 0;
+  TimestampRule ts;                    // Whisper's timestamp mode: the rules run before every selection, every pick joins the history
+  Profiler* prof = nullptr;            // the owning session's, when it has one: the rule kernel is a profile class of its own
   DeviceBuffer d_save, d_nsaved;       // generated ids per sequence + their count (on the device: a captured step replays for every position)
   DeviceBuffer d_noise;                // caller-supplied uniforms [rows][top_k] for the next step (parity tests); consumed once
   bool noise_armed = false;            // a step with armed noise is not graphable
@@ -57,6 +75,16 @@ struct ASR_LOCAL TokenHead {
     noise_armed = false;
     ++epoch;
   }
+  void set_timestamps(bool enable, int ts_begin, int no_timestamps_id, int eot_id, int max_initial, int vocab, const char* who) {
+    TimestampRule t;
+    if (enable) {
+      ASR_REQUIRE(0 <= eot_id && eot_id < no_timestamps_id && no_timestamps_id < ts_begin && ts_begin < vocab && max_initial >= -1,
+                  "%s: eot %d < no_timestamps %d < timestamp_begin %d < vocab %d expected, max_initial_index %d >= -1", who, eot_id, no_timestamps_id, ts_begin, vocab,
+                  max_initial);
+      t.on = true; t.ts_begin = ts_begin; t.no_timestamps_id = no_timestamps_id; t.eot_id = eot_id; t.max_initial = max_initial;
+    }
+    if (!(t == ts)) { ts = t; ++epoch; }
+  }
   void arm_noise(const float* uniforms, int count, hipStream_t s) {
     d_noise.reserve((size_t)count * 4, s);
     HIP_CHECK(hipMemcpyAsync(d_noise.ptr, uniforms, (size_t)count * 4, hipMemcpyHostToDevice, s));
@@ -72,12 +100,14 @@ struct ASR_LOCAL TokenHead {
   void restart(hipStream_t s) { HIP_CHECK(hipMemsetAsync(d_nsaved.ptr, 0, 4, s)); }      // every prefill starts from an empty history
 
   // The head's launches on logits [rows][ld]: picks go to next [rows]. bias: Whisper's BEGIN_SUPPRESS after a prefill, else null. penalise: false on a
-  // prefill (the prefill graphs select from the raw logits with an empty history; the decode graphs apply the penalty first).
+  // prefill (the prefill graphs select from the raw logits with an empty history; the decode graphs apply the penalty first). Timestamp mode: the rules
+  // run on both, after the penalty and before the selection (an empty history is their initial rule).
   void enqueue(float* logits, int ld, int rows, int n_valid, const float* bias, bool penalise, int32_t* next, hipStream_t s) {
     const bool penalised = penalty_value != 1.0f && !sampling;
     int32_t* save = d_save.as<int32_t>();
     int32_t* n_saved = d_nsaved.as<int32_t>();
     if (penalised && penalise) launch_apply_penalty(logits, ld, rows, save, ld_save, n_saved, penalty_range, penalty_value, s, partial);
+    if (ts.on) ts.enqueue(prof, logits, ld, rows, n_valid, save, ld_save, n_saved, 0, s);
     if (sampling) {                        // the bias first, history = every sampled id
       SampleArgs sa;
       sa.logits = logits; sa.ld = ld; sa.rows = rows; sa.n_valid = n_valid; sa.extra = bias;
@@ -88,7 +118,7 @@ struct ASR_LOCAL TokenHead {
     } else {
       launch_argmax_rows(logits, ld, rows, n_valid, bias, next, s);
     }
-    if (penalised || sampling || track_history) {   // GREEDY_SEARCH / the sampling head append their pick to the history
+    if (penalised || sampling || track_history || ts.on) {   // GREEDY_SEARCH / the sampling head append their pick to the history
       launch_append_ids(next, rows, save, ld_save, n_saved, s);
       launch_add_scalar(n_saved, 1, s);
     }
@@ -103,6 +133,8 @@ struct ASR_LOCAL BeamRanker {
   PinnedBuffer stage;                  // its own: a prefill called with null outputs may still be copying from the session's. [0, done_off) stop ids, then done flags
   uint64_t epoch = 0;                  // moves when a buffer moved: a captured step that ranks is stale
   int B = 0, beam = 0, ld = 0, n_stop = 0, done_off = 0, cur = 0;
+  TimestampRule ts;                    // Whisper's timestamp mode (set by begin): the rules run on every row before it is ranked
+  Profiler* prof = nullptr;
   const int32_t* slots_dev = nullptr;  // when set, the generated cache slots after a pass are *slots_dev + slots_off (a device counter: the pass replays from a captured graph)
   int slots_off = 0;
 
@@ -110,8 +142,8 @@ struct ASR_LOCAL BeamRanker {
   const int32_t* ancestry() const { return src[cur].as<int32_t>(); }     // the table the next pass's self-attention follows
   int32_t* next_ids() const { return next.as<int32_t>(); }
 
-  void begin(int B_, int beam_, int ld_, const int32_t* stop_ids, int n_stop_, hipStream_t s) {
-    B = B_; beam = beam_; ld = ld_; n_stop = n_stop_; cur = 0; slots_dev = nullptr; slots_off = 0;
+  void begin(int B_, int beam_, int ld_, const int32_t* stop_ids, int n_stop_, const TimestampRule& ts_, hipStream_t s) {
+    B = B_; beam = beam_; ld = ld_; n_stop = n_stop_; cur = 0; slots_dev = nullptr; slots_off = 0; ts = ts_;
     const size_t N = (size_t)rows(), Nn = std::max<size_t>(N, 64);
     bool moved = false;
     for (DeviceBuffer* q : {&topv, &topi}) moved |= reserve_moved(*q, Nn * BEAM_MAX * 4, s);
@@ -129,15 +161,19 @@ struct ASR_LOCAL BeamRanker {
     HIP_CHECK(hipMemsetAsync(done.ptr, 0, (size_t)B * 4, s));
     HIP_CHECK(hipMemsetAsync(len.ptr, 0, N * 4, s));
   }
-  // the first ranking: the prefill's logits, one row per utterance (+ bias: Whisper's BEGIN_SUPPRESS, as the arg-max head after a prefill)
-  void rank_first(const float* logits, int ld_logits, int n_valid, const float* bias, hipStream_t s) {
+  // the first ranking: the prefill's logits, one row per utterance (+ bias: Whisper's BEGIN_SUPPRESS, as the arg-max head after a prefill). Timestamp mode:
+  // the rules with an empty history first (len is zero after begin; the token table is not read)
+  void rank_first(float* logits, int ld_logits, int n_valid, const float* bias, hipStream_t s) {
+    if (ts.on) ts.enqueue(prof, logits, ld_logits, B, n_valid, tok[cur].as<int32_t>(), ld, len.as<int32_t>(), 0, s);
     launch_beam_topk(logits, ld_logits, B, n_valid, bias, beam, topv.as<float>(), topi.as<int32_t>(), s);
     select(1, 0, s);
     flip();
   }
   // Rank the rows' extensions on the current tables: the select pass writes the ids of the next pass and the ancestry of this one. n_slots: generated cache
   // slots after the pass (ignored once slots_dev is set). The caller flips afterwards -- outside a captured step, whose replay runs no host code.
-  void enqueue_rank(const float* logits, int ld_logits, int n_valid, int n_slots, hipStream_t s) {
+  // Timestamp mode: the rules first, row r's history being its len[r] ids of the current token table.
+  void enqueue_rank(float* logits, int ld_logits, int n_valid, int n_slots, hipStream_t s) {
+    if (ts.on) ts.enqueue(prof, logits, ld_logits, rows(), n_valid, tok[cur].as<int32_t>(), ld, len.as<int32_t>(), 1, s);
     launch_beam_topk(logits, ld_logits, rows(), n_valid, nullptr, beam, topv.as<float>(), topi.as<int32_t>(), s);
     select(0, n_slots, s);
   }

@@ -115,6 +115,7 @@ struct Profiler {
   std::vector<int64_t> launches;
   struct Pending { int cls; hipEvent_t a, b; };
   std::vector<Pending> pending;
+  std::vector<int> open;   // indices into `pending` of the scopes begun and not yet ended
   std::vector<hipEvent_t> pool;
 
   Profiler() = default;

@@ -198,10 +198,14 @@ hipEvent_t Profiler::get_event() {
 void Profiler::begin(int c, hipStream_t s) {
   Pending p{c, get_event(), get_event()};
   HIP_CHECK(hipEventRecord(p.a, s));
+  open.push_back((int)pending.size());
   pending.push_back(p);
 }
 
-void Profiler::end(hipStream_t s) { HIP_CHECK(hipEventRecord(pending.back().b, s)); }
+void Profiler::end(hipStream_t s) {          // scopes nest: the innermost open one ends
+  HIP_CHECK(hipEventRecord(pending[open.back()].b, s));
+  open.pop_back();
+}
 
 void Profiler::collect() {
   for (auto& p : pending) {

@@ -142,6 +142,19 @@ void launch_apply_penalty(float* logits, int ld, int rows, const int32_t* save_i
 // save_ids[r][*n_saved] = next[r] (the counter itself is advanced by launch_add_scalar afterwards)
 void launch_append_ids(const int32_t* next, int rows, int32_t* save_ids, int ld_save, const int32_t* n_saved, hipStream_t s);
 
+// ---- Whisper timestamp rules (OpenAI Whisper's ApplyTimestampRules; the reference has no timestamp mode, this one is the build's own). In place on the f32
+// logits [rows][ld], before the selection. Columns: [0, eot) text, eot, (eot, ts_begin) specials, [ts_begin, n_valid) timestamps. Row r's history is
+// ids[r * ld_ids .. + h), h = n_ids[r * n_ids_stride] (stride 0: one shared counter), both on the device (graph replay). In order:
+//   1. no_timestamps_id is masked;
+//   2. last_ts = h >= 1 and id[h-1] >= ts_begin, penult_ts = h < 2 or id[h-2] >= ts_begin: after a pair the timestamps are masked, after a lone
+//      timestamp [0, eot) is;
+//   3. m = the largest id >= ts_begin of the history: [ts_begin, m + 1) is masked -- [ts_begin, m) after a lone timestamp (the next segment may open where the last one closed; every other timestamp is strictly later);
+//   4. h == 0: [0, ts_begin) is masked and, with max_initial >= 0, (ts_begin + max_initial, n_valid);
+//   5. over what is left, L = log-sum-exp of the timestamp columns, T = max of [0, ts_begin): L > T masks [0, ts_begin) (an empty side is -inf).
+// Masked = -inf. The pad columns [n_valid, ld) are not touched.
+void launch_timestamp_rules(float* logits, int ld, int rows, int n_valid, const int32_t* ids, int ld_ids, const int32_t* n_ids, int n_ids_stride, int ts_begin,
+                            int no_timestamps_id, int eot_id, int max_initial, hipStream_t s);
+
 // ---- TOPK_TOPP_SAMPLING head (Export_Whisper.py:263-308), one workgroup per sequence: repetition penalty on every saved id
 // (negative logits multiplied, others divided; gather before scatter), + `extra` bias (BEGIN_SUPPRESS), x 1/temperature, top-k
 // (k <= 64, ties to the lower index), soft-max + exclusive-cumsum top-p cut, Gumbel-max with clamped uniforms. The uniforms come

@@ -1353,6 +1353,103 @@ __global__ __launch_bounds__(64) void apply_penalty_kernel(float* __restrict__ l
   if (id >= 0) x[id] = v * value;
 }
 
+// ------------------------------------------------------------------------------------ Whisper timestamp rules
+// kernels.h: launch_timestamp_rules. One workgroup of 1024 threads per row, the arg-max kernel's geometry (16-byte loads, 4096-column stripes, two loads in
+// flight). A: the row's history -> last_ts, penult_ts, m, and from them the unmasked column ranges, text [text_lo, ts_begin) less no_ts and timestamps
+// [ts_lo, ts_hi). B: one pass over the row for the text maximum T and the timestamp maximum M (both exact), then the <= 1501 unmasked timestamp columns once
+// more for S = sum exp(x - M): with the exact maximum every term carries one __expf, no rescaling chain. L = M + logf(S). C: -inf on the masked ranges.
+// Nothing is subtracted from a -inf maximum; -inf columns add exp(-inf) = 0.
+// x[lo, hi) = -inf by a workgroup of 1024 threads; x is 16-byte aligned, lo and hi are not
+__device__ __forceinline__ void fill_neg_inf(float* __restrict__ x, int lo, int hi, int tid) {
+  if (lo >= hi) return;
+  const int a = min(hi, (lo + 3) & ~3), b = max(a, hi & ~3);
+  if (tid < a - lo) x[lo + tid] = -INFINITY;
+  const float4 ninf = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+  for (int q = a + tid * 4; q < b; q += 4096) *reinterpret_cast<float4*>(x + q) = ninf;
+  if (tid < hi - b) x[b + tid] = -INFINITY;
+}
+
+__global__ __launch_bounds__(1024) void timestamp_rules_kernel(float* __restrict__ logits, int ld, int n_valid, const int32_t* __restrict__ ids, int ld_ids,
+                                                               const int32_t* __restrict__ n_ids, int n_ids_stride, int ts_begin, int no_ts, int eot,
+                                                               int max_initial) {
+  __shared__ int red_i[16];
+  __shared__ float red_t[16], red_m[16], red_s[16];
+  __shared__ int mask_text_sh;
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* x = logits + (size_t)r * ld;
+  // ---- A: the history (whatever follows an eot is read like any other id: the ranges below stay inside the row for every content)
+  const int32_t* hv = ids + (size_t)r * ld_ids;
+  const int h = min(max(n_ids[(size_t)r * n_ids_stride], 0), ld_ids);
+  int m = -1;
+  for (int j = tid; j < h; j += 1024) {
+    const int id = hv[j];
+    if (id >= ts_begin) m = max(m, id);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
+  if (lane == 0) red_i[wave] = m;
+  __syncthreads();
+  m = red_i[0];
+#pragma unroll
+  for (int w = 1; w < 16; ++w) m = max(m, red_i[w]);
+  m = min(m, n_valid - 1);
+  const bool last_ts = h >= 1 && hv[h - 1] >= ts_begin;
+  const bool penult_ts = h < 2 || hv[h - 2] >= ts_begin;
+  const bool closing = last_ts && !penult_ts, first = h == 0;
+  int ts_lo = (last_ts && penult_ts) ? n_valid : ts_begin;                  // after a pair: text
+  if (m >= 0) ts_lo = max(ts_lo, closing ? m : m + 1);                      // never back in time; after a closing timestamp the next segment may open at the same one
+  const int ts_hi = (first && max_initial >= 0 && max_initial < n_valid - ts_begin) ? ts_begin + max_initial + 1 : n_valid;
+  const int text_lo = first ? ts_begin : (closing ? eot : 0);               // the first token is a timestamp; an open segment closes or the stream ends
+  // ---- B
+  float T = -INFINITY, M = -INFINITY;
+  auto scan1 = [&](float v, int col) {                  // selects, not branches: a column is unmasked text, an unmasked timestamp (ts_lo >= ts_begin) or neither
+    T = fmaxf(T, (col >= text_lo && col < ts_begin && col != no_ts) ? v : -INFINITY);
+    M = fmaxf(M, (col >= ts_lo && col < ts_hi) ? v : -INFINITY);
+  };
+  auto scan = [&](const float4 v, int c) { scan1(v.x, c); scan1(v.y, c + 1); scan1(v.z, c + 2); scan1(v.w, c + 3); };
+  int c = (text_lo & ~3) + tid * 4;
+  for (; c + 4096 < ts_hi; c += 8192) {
+    const float4 a = *reinterpret_cast<const float4*>(x + c), b = *reinterpret_cast<const float4*>(x + c + 4096);
+    scan(a, c);
+    scan(b, c + 4096);
+  }
+  if (c < ts_hi) scan(*reinterpret_cast<const float4*>(x + c), c);
+  T = wave_max(T);
+  M = wave_max(M);
+  if (lane == 0) { red_t[wave] = T; red_m[wave] = M; }
+  __syncthreads();
+  M = red_m[0];
+#pragma unroll
+  for (int w = 1; w < 16; ++w) M = fmaxf(M, red_m[w]);
+  float S = 0.0f;
+  if (M > -INFINITY) {
+    for (c = (ts_lo & ~3) + tid * 4; c < ts_hi; c += 4096) {
+      const float4 v = *reinterpret_cast<const float4*>(x + c);
+      if (c >= ts_lo && c < ts_hi) S += __expf(v.x - M);
+      if (c + 1 >= ts_lo && c + 1 < ts_hi) S += __expf(v.y - M);
+      if (c + 2 >= ts_lo && c + 2 < ts_hi) S += __expf(v.z - M);
+      if (c + 3 >= ts_lo && c + 3 < ts_hi) S += __expf(v.w - M);
+    }
+  }
+  S = wave_sum(S);
+  if (lane == 0) red_s[wave] = S;
+  __syncthreads();
+  if (tid == 0) {
+    float t = red_t[0], sum = red_s[0];
+    for (int w = 1; w < 16; ++w) { t = fmaxf(t, red_t[w]); sum += red_s[w]; }
+    mask_text_sh = (M > -INFINITY && M + logf(sum) > t) ? 1 : 0;            // an empty side is -inf: no timestamp left never wins, no text left always loses
+  }
+  __syncthreads();
+  // ---- C: contiguous ranges, ends not 16-byte aligned: scalar head and tail, 16-byte body
+  fill_neg_inf(x, ts_begin, ts_lo, tid);
+  fill_neg_inf(x, ts_hi, n_valid, tid);
+  if (first || mask_text_sh) fill_neg_inf(x, 0, ts_begin, tid);
+  else {
+    if (closing) fill_neg_inf(x, 0, eot, tid);
+    if (tid == 0) x[no_ts] = -INFINITY;
+  }
+}
+
 __device__ __forceinline__ float uniform_from_counter(uint64_t seed, uint32_t step, uint32_t row, uint32_t j) {
   uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)step * 0x100000001B3ull + ((uint64_t)row << 8) + j + 1);   // splitmix64
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -2193,6 +2290,16 @@ void launch_apply_penalty(float* logits, int ld, int rows, const int32_t* save_i
                           int range, float value, hipStream_t s, int partial) {
   ASR_REQUIRE(range >= 1 && range <= 64 && range <= ld_save, "apply_penalty: range %d (1..64)", range);
   hipLaunchKernelGGL(apply_penalty_kernel, dim3(rows), dim3(64), 0, s, logits, ld, save_ids, ld_save, n_saved, range, value, partial);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_timestamp_rules(float* logits, int ld, int rows, int n_valid, const int32_t* ids, int ld_ids, const int32_t* n_ids, int n_ids_stride, int ts_begin,
+                            int no_timestamps_id, int eot_id, int max_initial, hipStream_t s) {
+  ASR_REQUIRE(ld % 4 == 0 && n_valid <= ld && ids && n_ids && ld_ids >= 1 && n_ids_stride >= 0, "timestamp_rules: ld %d n_valid %d ld_ids %d", ld, n_valid, ld_ids);
+  ASR_REQUIRE(0 <= eot_id && eot_id < no_timestamps_id && no_timestamps_id < ts_begin && ts_begin < n_valid && max_initial >= -1,
+              "timestamp_rules: ids eot %d no_timestamps %d timestamp_begin %d of %d columns, max_initial %d", eot_id, no_timestamps_id, ts_begin, n_valid, max_initial);
+  hipLaunchKernelGGL(timestamp_rules_kernel, dim3(rows), dim3(1024), 0, s, logits, ld, n_valid, ids, ld_ids, n_ids, n_ids_stride, ts_begin, no_timestamps_id,
+                     eot_id, max_initial);
   HIP_CHECK(hipGetLastError());
 }
 

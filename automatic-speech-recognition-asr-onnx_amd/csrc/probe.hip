@@ -782,6 +782,7 @@ static void probe_head_steps(asr_probe_token_head_desc* d) {
   h.set_penalty(d->value, d->range, who);
   h.set_track_history(d->track_history != 0);
   if (d->sampling) h.set_sampling(true, d->temperature, d->K, d->top_p, d->repetition_penalty, d->seed, who);
+  if (d->timestamps) h.set_timestamps(true, d->ts_begin, d->no_timestamps_id, d->eot_id, d->max_initial, d->n_valid, who);
   h.reserve(rows, nullptr);
   h.restart(nullptr);
   if (d->noise) h.arm_noise(d->noise, rows * d->K, nullptr);
@@ -800,20 +801,22 @@ static void probe_head_steps(asr_probe_token_head_desc* d) {
 // ---- the token-selection heads (kernels.h) on host arrays: one product launcher per call, unchanged. Every index a kernel will follow is checked here first.
 extern "C" int asr_probe_token_head(asr_probe_token_head_desc* d) {
   return asr_guard([&] {
-    ASR_REQUIRE(d && d->op >= 0 && d->op <= 6 && d->rows > 0 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0, "probe_token_head: bad descriptor");
+    ASR_REQUIRE(d && d->op >= 0 && d->op <= 7 && d->rows > 0 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0, "probe_token_head: bad descriptor");
     if (d->op == 6) { probe_head_steps(d); return; }
     const int op = d->op, rows = d->rows, ld = d->ld;
-    const bool uses_logits = op != 3, uses_save = op == 2 || op == 3 || op == 4;
+    const bool uses_logits = op != 3, uses_save = op == 2 || op == 3 || op == 4 || op == 7;
     ASR_REQUIRE(!uses_logits || d->logits, "probe_token_head: logits missing");
-    ASR_REQUIRE((op == 2 || op == 3 || op == 5 || d->out_i) && ((op != 1 && op != 5) || d->out_v), "probe_token_head: output array missing");
+    ASR_REQUIRE((op == 2 || op == 3 || op == 5 || op == 7 || d->out_i) && ((op != 1 && op != 5) || d->out_v), "probe_token_head: output array missing");
     ASR_REQUIRE(op != 2 || (d->range >= 1 && d->range <= 64 && d->range <= d->ld_save), "probe_token_head: apply_penalty range %d (1..64, within the table)", d->range);
     ASR_REQUIRE(op != 5 || (d->no_speech_id >= 0 && d->no_speech_id < d->n_valid), "probe_token_head: no_speech_id %d outside the vocabulary of %d", d->no_speech_id, d->n_valid);
     if (uses_save) {
       ASR_REQUIRE(d->save_ids && d->ld_save >= 1 && d->n_saved >= 0, "probe_token_head: history table missing");
       ASR_REQUIRE(op != 2 || d->n_saved <= d->ld_save, "probe_token_head: apply_penalty reads save_ids[n_saved - range, n_saved): n_saved %d past the table of %d", d->n_saved, d->ld_save);
+      if (op == 7 && d->n_saved_rows)
+        for (int r = 0; r < rows; ++r) ASR_REQUIRE(d->n_saved_rows[r] >= 0, "probe_token_head: timestamp_rules counter %d of row %d", d->n_saved_rows[r], r);
       const int used = op == 3 ? 0 : std::min(d->n_saved, d->ld_save);       // the columns whose ids index the logits row
       for (int r = 0; r < rows; ++r)
-        for (int j = 0; j < used; ++j) {
+        for (int j = 0; j < (op == 7 ? d->ld_save : used); ++j) {      // (the rules only compare ids, but a whole table of valid ids is what a session holds)
           const int32_t id = d->save_ids[(size_t)r * d->ld_save + j];
           ASR_REQUIRE(id >= 0 && id < d->n_valid, "probe_token_head: saved id %d of row %d outside the vocabulary of %d", id, r, d->n_valid);
         }
@@ -859,6 +862,12 @@ extern "C" int asr_probe_token_head(asr_probe_token_head_desc* d) {
         a.noise = d->noise ? (const float*)up(d->noise, (size_t)rows * d->K * 4) : nullptr; a.seed = d->seed;
         a.next = di;
         launch_sample_topk_topp(a, nullptr);
+        break;
+      }
+      case 7: {             // the launcher checks the four parameters itself
+        const int32_t* dnr = d->n_saved_rows ? (const int32_t*)up(d->n_saved_rows, (size_t)rows * 4) : dn;
+        launch_timestamp_rules(dlog, ld, rows, d->n_valid, dsave, d->ld_save, dnr, d->n_saved_rows ? 1 : 0, d->ts_begin, d->no_timestamps_id, d->eot_id,
+                               d->max_initial, nullptr);
         break;
       }
       default:

@@ -1454,7 +1454,7 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
   max_new = std::min(max_new, c.max_seq_len - max_len);  // positions (RoPE rows) end at max_seq_len
   const int Sb = round_up(max_new, 16), ld = Sb;         // generated slots per hypothesis row; the prompts stay in the prefill cache
   // ---- the first ranking reads the prefill logits; do it before any buffer grows
-  ranker.begin(B, beam, ld, stop_ids, n_stop, stream);
+  ranker.begin(B, beam, ld, stop_ids, n_stop, TimestampRule{}, stream);
   ranker.rank_first(d_logits.as<float>(), vpad, c.vocab, nullptr, stream);
   // ---- hypothesis rows: caches, counters, row buffers, the one-row-per-hypothesis plan
   for (DeviceBuffer* q : {&d_bhist, &d_bp0}) q->reserve((size_t)std::max(N, 64) * 4, stream);

@@ -137,6 +137,7 @@ void WhSession::init() {
   ASR_REQUIRE(c.max_target_positions <= 1536, "whisper: decoder context too long for the attention kernel");
   vpad = round_up(c.vocab, 128);
   head.init(c.max_target_positions, 0, 20, 512);
+  head.prof = &prof; ranker.prof = &prof;
   n_bin_tiles = (c.nfft / 2 + 1 + 15) / 16;
   n_kchunks = c.nfft / 16;
   act = c.gelu_tanh ? ACT_GELU_TANH : ACT_GELU_ERF;
@@ -750,7 +751,7 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   const auto& c = cfg;
   ASR_REQUIRE(after_prefill && batch > 0 && hist > 0 && d_logits.ptr, "whisper_beam_search: prefill first");
   ASR_REQUIRE(beam >= 1 && beam <= BEAM_MAX, "whisper_beam_search: beam width %d outside 1..%d", beam, BEAM_MAX);
-  ASR_REQUIRE(head.plain(), "whisper_beam_search: the penalty / sampling heads do not combine with beam search");
+  ASR_REQUIRE(head.plain(), "whisper_beam_search: the penalty / sampling heads do not combine with beam search");     // (the timestamp rules do: they run before every ranking)
   ASR_REQUIRE(hist + max_new <= c.max_target_positions, "whisper_beam_search: %d prompt + %d new positions exceed max_target_positions %d", hist, max_new,
               c.max_target_positions);
   HIP_CHECK(hipSetDevice(device));
@@ -766,9 +767,10 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   if (precision == ASR_PRECISION_BF16) grow(d_dlo, (size_t)3 * Rp * d * 2);
   grow(d_dqkv, (size_t)Rp * (3 * d + d + d + dff + d) * eT + (size_t)Rp * d * eT);
   const int n_stop = eos_id >= 0 ? 1 : 0;
-  ranker.begin(B, beam, ld, &eos_id, n_stop, stream);
+  ranker.begin(B, beam, ld, &eos_id, n_stop, head.ts, stream);
   HIP_CHECK(hipMemcpyAsync(d_bhist.ptr, d_hist.ptr, 4, hipMemcpyDeviceToDevice, stream));      // the rows' position: the prompt length p0 the prefill left
-  // ---- first ranking: the prefill's logits (B rows, left in place) + BEGIN_SUPPRESS, as the arg-max head after a prefill
+  // ---- first ranking: the prefill's logits (B rows, left in place) + BEGIN_SUPPRESS, as the arg-max head after a prefill. In timestamp mode the head has
+  // already masked them by the initial rule; the ranker applies it again, which changes nothing.
   ranker.rank_first(d_logits.as<float>(), vpad, c.vocab, begin, stream);
   ranker.slots_dev = d_bhist.as<int32_t>(); ranker.slots_off = 1 - p0;   // the pass at position p fills generated slot p - p0
   // ---- the prompt into every row's extent
@@ -784,7 +786,7 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   const bool graphable = use_graph && !taps_enabled && !prof.enabled;
   GraphKey key;                                             // everything the captured step bakes in
   for (uint64_t v : {(uint64_t)B, (uint64_t)beam, (uint64_t)S, (uint64_t)p0, (uint64_t)ld, (uint64_t)n_stop, (uint64_t)Mpad, ws_epoch, ranker.epoch,
-                     (uint64_t)(uintptr_t)stream})
+                     (uint64_t)(uintptr_t)stream, head.epoch})
     key.mix(v);
   for (int t = 0; t + 1 < max_new && !ranker.all_done(stream); ++t) {
     bs.src = ranker.ancestry();
@@ -926,6 +928,13 @@ extern "C" int asr_whisper_set_sampling(asr_session* s, int enable, float temper
                                         float repetition_penalty, uint64_t seed) {
   return asr_guard([&] {
     whisper_session(s, "whisper_set_sampling")->head.set_sampling(enable != 0, temperature, top_k, top_p, repetition_penalty, seed, "whisper_set_sampling");
+  });
+}
+
+extern "C" int asr_whisper_set_timestamps(asr_session* s, int enable, int timestamp_begin_id, int no_timestamps_id, int eot_id, int max_initial_index) {
+  return asr_guard([&] {
+    WhSession* w = whisper_session(s, "whisper_set_timestamps");
+    w->head.set_timestamps(enable != 0, timestamp_begin_id, no_timestamps_id, eot_id, max_initial_index, w->cfg.vocab, "whisper_set_timestamps");
   });
 }
 

@@ -458,6 +458,14 @@ class WhisperSession(_token_head("whisper", 20, "Decode head: 1.0 = plain arg-ma
         _lib.check(_lib.load().asr_whisper_beam_search(self._h, int(beam), int(max_new), int(eos_id), _ip(tok), _ip(n), _fp(score)))
         return [[(tok[b, r, :n[b, r]].copy(), float(score[b, r])) for r in range(beam)] for b in range(self.batch)]
 
+    def set_timestamps(self, enable: bool, max_initial_index: int | None = 50):
+        """Timestamp mode (asr_whisper_set_timestamps; the build's own, the reference always decodes behind <|notimestamps|>): OpenAI Whisper's timestamp
+        rules run on the device before every selection, the prompt carries no <|notimestamps|>. The ids come from the config; timestamps start right after
+        <|notimestamps|>. max_initial_index: the latest first timestamp, in 0.02 s steps (None: no limit). Switch it off for the [SOT] probe."""
+        cfg = self.cfg
+        _lib.check(_lib.load().asr_whisper_set_timestamps(self._h, int(enable), cfg.no_timestamps_id + 1, cfg.no_timestamps_id, cfg.eot_id,
+                                                          -1 if max_initial_index is None else int(max_initial_index)))
+
     def no_speech_prob(self, no_speech_id: int | None = None) -> np.ndarray:
         """NO_SPEECH_DETECTION on the device-resident logits of the last prefill (the probe): (B,) probabilities."""
         out = np.zeros(self.batch, dtype=np.float32)

@@ -15,6 +15,11 @@
                             tail window zero-padded to the aligned length; the [SOT] probe (language, no-speech) runs on window 0
                             ONLY, a no-speech verdict aborts the whole file, later windows reuse window 0's language id; the
                             windows' ids are concatenated and the repeat guard sees the concatenation (:705-708)
+  timestamps=True         = this build's own mode (the reference defines NO_TIMESTAMPS_TOKEN and always uses it): the prompt is [SOT, language,
+                            task], OpenAI Whisper's timestamp rules run in the device decode head (asr_whisper_set_timestamps) from the full-prompt
+                            prefill on -- never on the [SOT] probe, which needs raw logits -- and split_segments() turns the <|t.tt|> ids into
+                            segments. The limit is max_target_positions - 3. The tail-repeat guard is NOT applied in this mode: it cuts the id
+                            stream at an arbitrary id, which would leave a segment without its closing timestamp.
 Batch extension: `transcribe` takes a list of independent clips as one batch (language detection / no-speech per clip);
 `transcribe_file` is the reference's per-file behaviour (the windows of one file form the batch).
 """
@@ -82,16 +87,49 @@ def no_speech_probability(logits: np.ndarray, suppress_tokens: Sequence[int], no
     return e[:, no_speech_id] / e.sum(axis=1)
 
 
+TIMESTAMP_PRECISION = 0.02               # seconds per timestamp id: two encoder positions
+
+
+def split_segments(ids: Sequence[int], ts_begin: int, window_offset_s: float, window_len_s: float, precision: float = TIMESTAMP_PRECISION):
+    """Ids of one window decoded in timestamp mode -> [{"start", "end", "tokens"}], times in seconds = (id - ts_begin) * precision + window_offset_s.
+    A timestamp opens a segment when none is open, text ids (everything below ts_begin) accumulate, the next timestamp closes it; the second timestamp
+    of a pair opens the next segment (a timestamp that follows a timestamp moves the opening). A segment still open with text when the ids end -- the
+    decoder met its limit, or stopped without closing -- ends with the window, at window_offset_s + window_len_s. Segments without text are dropped; text
+    before any timestamp (no stream of the timestamp rules has it) counts from the window's start."""
+    segs, start, toks = [], None, []
+    for i in ids:
+        i = int(i)
+        if i < ts_begin:
+            if start is None:
+                start = float(window_offset_s)
+            toks.append(i)
+            continue
+        t = (i - ts_begin) * precision + window_offset_s
+        if start is not None and toks:
+            segs.append({"start": start, "end": t, "tokens": toks})
+            start, toks = None, []
+        else:
+            start = t
+    if start is not None and toks:
+        segs.append({"start": start, "end": float(window_offset_s) + float(window_len_s), "tokens": toks})
+    return segs
+
+
 class WhisperTranscriber:
     def __init__(self, cfg: WhisperConfig, session: WhisperSession, suppress_tokens=None, task: str = "transcribe",
                  detect_language: bool = True, no_speech_detection: bool = True, no_speech_threshold: float = 0.6,
                  remove_repeats: bool = True, repeat_penalty: float = 1.0, penalty_range: int = 20,
                  use_sampling: bool = False, temperature: float = 0.8, top_k: int = 10, top_p: float = 0.95,
-                 sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1):
+                 sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1,
+                 timestamps: bool = False, max_initial_timestamp: float | None = 1.0):
         if beam_size > 1 and (float(repeat_penalty) != 1.0 or use_sampling):
             raise ValueError("beam_size > 1 does not combine with a repeat penalty or sampling")
         self.cfg, self.sess = cfg, session
         self.beam_size = int(beam_size)
+        # timestamp mode (the build's own; combines with every head): the latest first timestamp in seconds -> an index in TIMESTAMP_PRECISION steps
+        self.timestamps = bool(timestamps)
+        self.max_initial_index = None if max_initial_timestamp is None else int(round(max_initial_timestamp / TIMESTAMP_PRECISION))
+        self.ts_begin = cfg.no_timestamps_id + 1
         self.suppress_tokens = list(suppress_tokens) if suppress_tokens is not None else None
         self.task_token = cfg.transcribe_id if task == "transcribe" else cfg.translate_id
         self.detect_language, self.no_speech_detection = detect_language, no_speech_detection
@@ -108,6 +146,31 @@ class WhisperTranscriber:
         """"INT16" | "F32" | "F16": the type of the session's `audio` input (the reference reads it off the graph, Inference_Whisper_ONNX.py:103-126)."""
         return audio_dtype_name(self.sess.audio_dtype)
 
+    def _prompt(self, lang: int) -> list[int]:
+        head = [self.cfg.sot_id, int(lang), self.task_token]
+        return head if self.timestamps else head + [self.cfg.no_timestamps_id]
+
+    def _probe_prefill(self, B: int):
+        """The [SOT] probe: raw logits from the plain arg-max head (no penalty, no sampling, no timestamp rules)."""
+        self.sess.set_sampling(False)
+        self.sess.set_penalty(1.0, self.penalty_range)
+        if self.timestamps:
+            self.sess.set_timestamps(False)
+        return self.sess.prefill(np.full((B, 1), self.cfg.sot_id, dtype=np.int32))[1]
+
+    def _prefill_and_continue(self, prompt: np.ndarray, limit: int):
+        """The full-prompt prefill and the ids after it under the transcriber's head; timestamp mode is on from this prefill to the last id only."""
+        self.sess.set_penalty(self.repeat_penalty, self.penalty_range)
+        self.sess.set_sampling(*self.sampling)
+        if self.timestamps:
+            self.sess.set_timestamps(True, self.max_initial_index)
+        try:
+            self.sess.prefill(prompt, want_logits=False)
+            return self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * prompt.shape[0]
+        finally:
+            if self.timestamps:
+                self.sess.set_timestamps(False)
+
     def _continue(self, limit: int):
         """Ids after the full-prompt prefill: greedy / penalty-greedy / sampling, or the first hypothesis of the beam search."""
         if self.beam_size > 1:
@@ -115,7 +178,8 @@ class WhisperTranscriber:
         return self.sess.generate(limit, eos_id=self.cfg.eot_id)
 
     def transcribe(self, clips_int16: Sequence[np.ndarray], language_ids: Sequence[int] | None = None, max_new: int | None = None):
-        """List of int16 mono 16 kHz clips (each <= 30 s) -> per clip dict(tokens, language_id, no_speech_prob, skipped)."""
+        """List of int16 mono 16 kHz clips (each <= 30 s) -> per clip dict(tokens, language_id, no_speech_prob, skipped). Timestamp mode adds
+        segments = [{"start", "end", "tokens"}] (seconds from the clip's start) and keeps text ids only in tokens; the repeat guard is not applied."""
         cfg = self.cfg
         audios = [prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(-1), self.sess.audio_dtype) for c in clips_int16]
         B = len(audios)
@@ -124,30 +188,29 @@ class WhisperTranscriber:
         self.sess.encode(audios)                                         # STFT + encoder + cross-KV, once per window
         probs = np.zeros(B, dtype=np.float32)
         if self.detect_language or self.no_speech_detection:
-            self.sess.set_sampling(False)
-            self.sess.set_penalty(1.0, self.penalty_range)
-            _, logits = self.sess.prefill(np.full((B, 1), cfg.sot_id, dtype=np.int32))      # probe with [SOT]
+            logits = self._probe_prefill(B)                                 # probe with [SOT]
             if self.detect_language:
                 lang = self.language_token_ids[np.argmax(logits[:, self.language_token_ids], axis=1)]
             if self.no_speech_detection:
                 probs = self.sess.no_speech_prob(cfg.no_speech_id)          # device head over the probe's logits
         skipped = probs >= self.no_speech_threshold if self.no_speech_detection else np.zeros(B, dtype=bool)
-        prompt = np.stack([[cfg.sot_id, int(l), self.task_token, cfg.no_timestamps_id] for l in lang]).astype(np.int32)
+        prompt = np.stack([self._prompt(l) for l in lang]).astype(np.int32)
         limit = max(0, cfg.max_target_positions - prompt.shape[1])
         if max_new is not None:
             limit = min(limit, max_new)
-        self.sess.set_penalty(self.repeat_penalty, self.penalty_range)
-        self.sess.set_sampling(*self.sampling)
-        self.sess.prefill(prompt, want_logits=False)
-        toks = self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * B
+        toks = self._prefill_and_continue(prompt, limit)
         wall = time.time() - t0
         out = []
         for b in range(B):
             ids = [] if skipped[b] else toks[b].tolist()
-            if self.remove_repeats:
+            res = {"language_id": int(lang[b]), "no_speech_prob": float(probs[b]), "skipped": bool(skipped[b])}
+            if self.timestamps:
+                res["segments"] = split_segments(ids, self.ts_begin, 0.0, audios[b].size / cfg.sample_rate)
+                ids = [t for t in ids if t < self.ts_begin]
+            elif self.remove_repeats:
                 ids = list(remove_repeated_parts(ids, 3, len(ids)))
-            out.append({"tokens": np.asarray(ids, dtype=np.int32), "language_id": int(lang[b]), "no_speech_prob": float(probs[b]),
-                        "skipped": bool(skipped[b])})
+            res["tokens"] = np.asarray(ids, dtype=np.int32)
+            out.append(res)
         total_s = sum(a.size for a in audios) / cfg.sample_rate
         return out, {"rtf": wall / total_s, "wall_s": wall}
 
@@ -158,7 +221,10 @@ class WhisperTranscriber:
         -> dict(tokens = the windows' ids concatenated (repeat guard applied when enabled), windows = per-window ids,
                 language_id, no_speech_prob, no_speech), stats.
         The windows are independent once window 0's probe has fixed the language, so they run as ONE batch; the probe's [SOT]
-        prefill is evaluated for the batch but only window 0's row is read (the reference never probes a later window)."""
+        prefill is evaluated for the batch but only window 0's row is read (the reference never probes a later window).
+        Timestamp mode keeps these fixed, independently batched windows (no seek loop): window w's segments are offset by w * stride / sample_rate and
+        an open last segment ends with its window; the result gains segments, tokens holds text ids only (windows keeps every id, timestamps
+        included) and the repeat guard is not applied."""
         cfg = self.cfg
         raw = np.asarray(pcm_int16, dtype=np.int16).reshape(-1)
         audio_len = int(raw.size)
@@ -176,9 +242,7 @@ class WhisperTranscriber:
         self.sess.encode(clips)
         prob, no_speech = 0.0, False
         if self.detect_language or self.no_speech_detection:            # needs_probe: window 0 only (:768)
-            self.sess.set_sampling(False)
-            self.sess.set_penalty(1.0, self.penalty_range)
-            _, logits = self.sess.prefill(np.full((n_win, 1), cfg.sot_id, dtype=np.int32))
+            logits = self._probe_prefill(n_win)
             if self.detect_language:
                 lang = int(self.language_token_ids[np.argmax(logits[0, self.language_token_ids])])
             if self.no_speech_detection:
@@ -186,19 +250,21 @@ class WhisperTranscriber:
                 no_speech = prob >= self.no_speech_threshold             # aborts the file (:801-805)
         windows: list[list[int]] = []
         if not no_speech:
-            prompt = np.tile(np.asarray([[cfg.sot_id, lang, self.task_token, cfg.no_timestamps_id]], dtype=np.int32), (n_win, 1))
+            prompt = np.tile(np.asarray([self._prompt(lang)], dtype=np.int32), (n_win, 1))
             limit = max(0, cfg.max_target_positions - prompt.shape[1])
             if max_new is not None:
                 limit = min(limit, max_new)
-            self.sess.set_penalty(self.repeat_penalty, self.penalty_range)
-            self.sess.set_sampling(*self.sampling)
-            self.sess.prefill(prompt, want_logits=False)
-            toks = self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * n_win
+            toks = self._prefill_and_continue(prompt, limit)
             windows = [t.astype(int).tolist() for t in toks]
         wall = time.time() - t0
         ids = [t for w in windows for t in w]
-        if self.remove_repeats:
-            ids = list(remove_repeated_parts(ids, 3, len(ids)))
-        res = {"tokens": np.asarray(ids, dtype=np.int32), "windows": windows, "language_id": lang, "no_speech_prob": prob,
+        res = {"windows": windows, "language_id": lang, "no_speech_prob": prob,
                "no_speech": bool(no_speech), "n_windows": n_win, "stride": stride, "window": window}
+        if self.timestamps:
+            res["segments"] = [seg for w, win in enumerate(windows)
+                               for seg in split_segments(win, self.ts_begin, w * stride / cfg.sample_rate, window / cfg.sample_rate)]
+            ids = [t for t in ids if t < self.ts_begin]
+        elif self.remove_repeats:
+            ids = list(remove_repeated_parts(ids, 3, len(ids)))
+        res["tokens"] = np.asarray(ids, dtype=np.int32)
         return res, {"rtf": wall / max(audio_len / cfg.sample_rate, 1e-9), "wall_s": wall}

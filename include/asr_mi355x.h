@@ -234,7 +234,7 @@ int asr_whisper_generate(asr_session* s, int max_new, int eos_id, int32_t* token
  * positions followed through each row's ancestry (device memory: layers x rows x 2 x d_model x slots x element size -- large-v3 bf16, 32 x 30 s at
  * width 5 with 444 new ids: 11.7 GB, kept for the next search), cross-attention reading each utterance's slabs once for all of its rows. Host outputs,
  * hypotheses best-first: tokens_out [B][beam][max_new], n_out [B][beam], scores_out [B][beam] (nullable). Errors: not right after a prefill ("prefill
- * first"), width outside 1..8, a repeat penalty or sampling head set ("do not combine"), prompt + max_new > max_target_positions. The session's greedy
+ * first"), width outside 1..8, a repeat penalty or sampling head set ("do not combine"; asr_whisper_set_timestamps does combine), prompt + max_new > max_target_positions. The session's greedy
  * state (pages, block table, history, ids, logits) is left as the prefill left it: asr_whisper_generate afterwards continues the same prefill. */
 int asr_whisper_beam_search(asr_session* s, int beam, int max_new, int eos_id, int32_t* tokens_out, int32_t* n_out, float* scores_out);
 /* decode head: repeat_penalty == 1 => ARGMAX (Export_Whisper.py:254-260); otherwise penalty-greedy = APPLY_PENALTY (:312-325)
@@ -266,6 +266,24 @@ int asr_whisper_set_sampling(asr_session* s, int enable, float temperature, int 
                              uint64_t seed);
 /* parity hook: the uniforms of the NEXT prefill / decode step, host [batch][top_k] (count = batch * top_k); consumed once. */
 int asr_whisper_set_sampling_noise(asr_session* s, const float* uniforms, int count);
+/* Segment timestamps: OpenAI Whisper's ApplyTimestampRules inside the decode head. The reference has no timestamp mode (it defines NO_TIMESTAMPS_TOKEN and
+ * always puts it in the prompt), so -- like the beam search -- this mode is the build's own. With enable != 0 the prompt carries no <|notimestamps|> and,
+ * before every selection (arg-max, penalty-greedy after its penalty, sampling, every ranking of asr_whisper_beam_search), the f32 logits row of a sequence
+ * with h generated ids since the prefill is masked with -inf, in this order. Columns: [0, eot_id) text, eot_id, (eot_id, timestamp_begin_id) specials,
+ * [timestamp_begin_id, vocab) timestamps; timestamp_begin_id = no_timestamps_id + 1 in every released vocabulary.
+ *   1. no_timestamps_id.
+ *   2. last_ts = h >= 1 and id[h-1] >= timestamp_begin_id; penult_ts = h < 2 or id[h-2] >= timestamp_begin_id. After a pair (last_ts and penult_ts) all
+ *      timestamps: text follows. After a lone timestamp (last_ts and not penult_ts) [0, eot_id): the segment closes or the stream ends.
+ *   3. m = the largest generated id >= timestamp_begin_id, if any: [timestamp_begin_id, m + 1) -- after a lone timestamp [timestamp_begin_id, m): the next
+ *      segment may open where the last one closed, every other timestamp is strictly later (no segment of zero length).
+ *   4. h == 0: [0, timestamp_begin_id), and with max_initial_index >= 0 also (timestamp_begin_id + max_initial_index, vocab). -1: no limit.
+ *   5. Over the columns left, L = log-sum-exp of the timestamps and T = max of [0, timestamp_begin_id): if L > T, [0, timestamp_begin_id) (OpenAI's comparison of
+ *      log-probabilities; the soft-max normaliser is common to both sides. An empty side counts as -inf).
+ * Every pick is appended to the device-side history, which restarts at a prefill: a prefill in this mode selects by rule 4, so switch the mode off for the
+ * [SOT] probe that asr_whisper_no_speech_prob and the language detection read. logits_out of prefill / decode then holds the masked logits, as it holds
+ * the penalised ones under asr_whisper_set_penalty; beam scores are log-soft-max values of the masked rows, as OpenAI's are. Ids are checked:
+ * 0 <= eot_id < no_timestamps_id < timestamp_begin_id < vocab. enable = 0 ignores the other arguments; no kernel is added to any step then. */
+int asr_whisper_set_timestamps(asr_session* s, int enable, int timestamp_begin_id, int no_timestamps_id, int eot_id, int max_initial_index);
 
 /* ------------------------------------------------------------------ Qwen3-ASR (audio encoder + Qwen3 decoder with KV cache)
  * Replaces the merged graphs Qwen_ASR prefill_greedy / decode_greedy and the Embed graph (Qwen_ASR/Shared_Merged.py; I/O planner

@@ -153,13 +153,16 @@ typedef struct asr_probe_beam_select_desc {
 int asr_probe_beam_select(asr_probe_beam_select_desc* d);
 
 /* One call of a token-selection head through its product launcher on host arrays. op: 0 launch_argmax_rows, 1 launch_beam_topk, 2 launch_apply_penalty,
- * 3 launch_append_ids, 4 launch_sample_topk_topp, 5 launch_no_speech_prob; 6 "head steps", below. Rows keep their real leading dimension (ld, a multiple of 128, >= n_valid): the
+ * 3 launch_append_ids, 4 launch_sample_topk_topp, 5 launch_no_speech_prob, 7 launch_timestamp_rules; 6 "head steps", below. Rows keep their real leading dimension (ld, a multiple of 128, >= n_valid): the
  * caller fills the pad columns, so a kernel that reads them shows. n_saved is put in device memory, as the sessions keep it; the logits, the whole save_ids
  * table and the counter come back as they stand after the call (penalty and sampler work in place). Fields an op does not use are ignored.
  * op 6 drives a TokenHead (csrc/decode_head.h) as a session does: configured from value / range / partial / ld_save / track_history (+ the sampler fields when
  * sampling != 0), restarted, then `steps` times enqueue + consumed on a fresh copy of the same logits rows -- step 0 with `vec` as the bias and without the
  * penalty (a prefill), later steps without bias and with it (decode steps). `noise`, when set, is armed before step 0. Before step change_step (> 0) the penalty
- * is set to value2 / range2. Out: picks [steps][rows], save_ids (the final history table), n_saved_after (the counter); logits are not written back. */
+ * is set to value2 / range2. With timestamps != 0 the head runs in Whisper's timestamp mode (ts_begin / no_timestamps_id / eot_id / max_initial). Out: picks
+ * [steps][rows], save_ids (the final history table), n_saved_after (the counter); logits are not written back.
+ * op 7 masks the logits in place by the history save_ids [rows][ld_save] and its length: n_saved for every row (one shared device counter), or n_saved_rows
+ * [rows] when set (per-row counters, as the beam ranker keeps them). Every entry of the table must be a valid id. */
 typedef struct asr_probe_token_head_desc {
   int32_t op, rows, n_valid, ld;
   float* logits;             /* [rows][ld], in / out (ops 0 1 2 4 5) */
@@ -180,6 +183,9 @@ typedef struct asr_probe_token_head_desc {
   int32_t steps, track_history, sampling, change_step, range2;   /* head steps (6) */
   float value2;
   int32_t* picks;            /* out [steps][rows] (6) */
+  int32_t timestamps;        /* head steps (6): timestamp mode on */
+  int32_t ts_begin, no_timestamps_id, eot_id, max_initial;   /* timestamp rules (6 7) */
+  const int32_t* n_saved_rows;   /* [rows] per-row history lengths, or NULL: n_saved for all (7) */
 } asr_probe_token_head_desc;
 int asr_probe_token_head(asr_probe_token_head_desc* d);
 

@@ -52,8 +52,8 @@ def run(a) -> dict:
     if (a.precision == "fp8mm" and a.family != "whisper") or (a.precision in ("fp8w", "mxfp4w") and a.family not in ("whisper", "qwen_asr")):
         raise SystemExit("--precision %s exists for --family whisper%s only" % (a.precision, " / qwen_asr" if a.precision == "fp8w" else ""))
     timestamps = getattr(a, "timestamps", False)
-    if timestamps and a.family != "sensevoice":
-        raise SystemExit("--timestamps exists for --family sensevoice only")
+    if timestamps and a.family not in ("sensevoice", "whisper"):
+        raise SystemExit("--timestamps exists for --family sensevoice (per token) and --family whisper (per segment) only")
     files = []
     if a.family in ("sensevoice", "paraformer"):
         mod = _m(a.family)
@@ -86,7 +86,7 @@ def run(a) -> dict:
             from transformers import AutoTokenizer
             tok = AutoTokenizer.from_pretrained(a.tokenizer)
         tr = _m("whisper").WhisperTranscriber(cfg, sess, suppress_tokens=ckm.whisper_suppress_tokens(cfg), detect_language=a.language == "auto",
-                                              repeat_penalty=a.repeat_penalty, beam_size=a.beam)
+                                              repeat_penalty=a.repeat_penalty, beam_size=a.beam, timestamps=timestamps)
         lang_id = None
         if a.language != "auto":
             if tok is None:
@@ -98,12 +98,15 @@ def run(a) -> dict:
             # a no-speech verdict aborts the file, later windows reuse window 0's language
             r, stat = tr.transcribe_file(pcm, language_id=lang_id, sliding_window=a.sliding_window)
             ids = r["windows"]
-            flat = [t for w in ids for t in w]
+            flat = r["tokens"].tolist() if timestamps else [t for w in ids for t in w]      # timestamp mode: the text ids, repeat guard not applied
             text = None
             if tok is not None:
-                text = "[no speech detected]" if r["no_speech"] else (whisper_text(tok, flat) if flat else "")
+                text = "[no speech detected]" if r["no_speech"] else (whisper_text(tok, flat, remove_repeats=not timestamps) if flat else "")
             files.append({"path": p, "n_samples": int(pcm.size), "language": a.language, "windows": ids, "text": text, "rtf": stat["rtf"],
                           "language_ids": [r["language_id"]] * len(ids), "no_speech_prob": [r["no_speech_prob"]], "no_speech": r["no_speech"]})
+            if timestamps:                  # the build's own mode: windows keep every id, <|t.tt|> included; segments in seconds from the file's start
+                files[-1]["segments"] = [dict(seg, text=whisper_text(tok, seg["tokens"], remove_repeats=False)) if tok is not None else seg
+                                         for seg in r["segments"]]
     elif a.family == "qwen_asr":
         info, blob = shim.load_model(os.path.join(a.model, "Qwen_ASR.asrmodel"))
         cfg = cfgm.QwenAsrConfig(**info["config"])
@@ -181,7 +184,8 @@ def main():
     r.add_argument("--sliding-window", type=int, default=0)
     r.add_argument("--repeat-penalty", type=float, default=1.0, help="1.0 = plain greedy (the comparison default); the reference scripts default to 0.8")
     r.add_argument("--beam", type=int, default=1, help="beam width (Whisper, Qwen3-ASR; 1 = greedy); > 1 takes the first hypothesis and needs --repeat-penalty 1")
-    r.add_argument("--timestamps", action="store_true", help="SenseVoice: add each token's start / end (seconds) and mean frame log-probability to the dump")
+    r.add_argument("--timestamps", action="store_true", help="SenseVoice: add each token's start / end (seconds) and mean frame log-probability to the dump; Whisper: decode with timestamp tokens and add "
+                        "segments (start / end in seconds, token ids, text with --tokenizer)")
     r.add_argument("--out", required=True)
     r.add_argument("--any-wav-width", dest="strict_wav", action="store_false",
                    help="accept 8 / 24 / 32-bit wav (rescaled to int16); by default only 16-bit wav is taken: the only width whose samples equal the reference's, "
