@@ -85,6 +85,9 @@ SIGNATURES = {
     "asr_whisper_set_sampling": (_i, [_vp, _i, C.c_float, _i, C.c_float, C.c_float, C.c_uint64]),
     "asr_whisper_set_sampling_noise": (_i, [_vp, _fp, _i]),
     "asr_whisper_set_timestamps": (_i, [_vp, _i, _i, _i, _i, _i]),
+    "asr_whisper_set_word_timestamps": (_i, [_vp, _i, _ip, _i, _i]),
+    "asr_whisper_align": (_i, [_vp, _ip, _ip, _i, _ip, _i]),
+    "asr_whisper_align_read": (_i, [_vp, _i, _i, _vp, _sz, _ip]),
     "asr_qwen_create": (_i, [C.POINTER(QwenConfigC), _vp, _sz, _i, _i, _i, C.POINTER(_vp)]),
     "asr_qwen_prefill": (_i, [_vp, _vp, _i, _lp, _i, _ip, _ip, _ip, _ip, _ip, _fp, _ip]),
     "asr_qwen_decode": (_i, [_vp, _ip, _ip, _fp]),

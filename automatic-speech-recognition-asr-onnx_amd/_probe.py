@@ -58,6 +58,13 @@ class TokenHeadDesc(C.Structure):
                 ("n_saved_rows", _ip)]
 
 
+class WhisperAlignDesc(C.Structure):
+    _fields_ = [("op", C.c_int32), ("bf16", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("n", C.c_int32), ("n_pairs", C.c_int32),
+                ("max_rows", C.c_int32), ("ld", C.c_int32), ("q", _fp), ("k_slab", _fp), ("slab_rows", C.c_int32), ("row_off", _ip), ("n_lfr", _ip),
+                ("sel", _ip), ("n_sel", C.c_int32), ("position", C.c_int32), ("p0", C.c_int32), ("n_rows", _ip), ("n_frames", _ip), ("width", C.c_int32),
+                ("scores", _fp), ("stats", _fp), ("cost", _fp), ("frames", _ip), ("path", _ip), ("path_stride", C.c_int32), ("path_len", _ip)]
+
+
 SIGNATURES = {
     "asr_probe_gemm": (C.c_int, [C.POINTER(GemmDesc)]),
     "asr_probe_ctc_head": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, _ip, _fp, _ip, C.c_char_p]),
@@ -71,6 +78,7 @@ SIGNATURES = {
     "asr_probe_qwen_attention": (C.c_int, [C.POINTER(QwenAttnDesc)]),
     "asr_probe_beam_select": (C.c_int, [C.POINTER(BeamSelectDesc)]),
     "asr_probe_token_head": (C.c_int, [C.POINTER(TokenHeadDesc)]),
+    "asr_probe_whisper_align": (C.c_int, [C.POINTER(WhisperAlignDesc)]),
     "asr_probe_decode_attention_beam": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p]),
     "asr_probe_gemm_counts": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "asr_probe_live_device_bytes": (C.c_int, [C.POINTER(C.c_int64)]),
@@ -511,3 +519,63 @@ def gemm_fp8(a8, w8, w_scale, bias, a_scale=1.0, add=None, act=0, iters=0):
         _lib.check(load().asr_probe_gemm_fp8(M, N, K, a8.ctypes.data, w8.ctypes.data, sc.ctypes.data_as(_fp), a_scale, b.ctypes.data_as(_fp), r.ctypes.data_as(_fp), act,
                                              None, out.ctypes.data_as(_fp), iters, C.byref(us)))
     return out, us.value
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _ptr(a, typ):
+    return a.ctypes.data_as(typ)
+
+
+def whisper_align_scores(q, k_slab, row_off, n_lfr, sel, scores, position, p0, n=1, bf16=False):
+    """launch_align_scores on host arrays: q [B n][H 64], k_slab [H][rows][64], sel [(head, slot)], scores [B][n_pairs][max_rows][ld] (returned updated)."""
+    q, k = _f32(q), _f32(k_slab)
+    ro, nl, sl = _i32(row_off), _i32(n_lfr), _i32(sel).reshape(-1, 2)
+    out = _f32(scores).copy()
+    B, P, R, ld = out.shape
+    d = WhisperAlignDesc(op=0, bf16=int(bf16), B=B, H=k.shape[0], n=n, n_pairs=P, max_rows=R, ld=ld, q=_ptr(q, _fp), k_slab=_ptr(k, _fp), slab_rows=k.shape[1],
+                         row_off=_ptr(ro, _ip), n_lfr=_ptr(nl, _ip), sel=_ptr(sl, _ip), n_sel=sl.shape[0], position=int(position), p0=int(p0), scores=_ptr(out, _fp))
+    assert q.shape == (B * n, k.shape[0] * 64) and k.shape[2] == 64 and ro.size == nl.size == B
+    _lib.check(load().asr_probe_whisper_align(C.byref(d)))
+    return out
+
+
+def whisper_align_op(op, n_rows, n_frames, scores=None, stats=None, cost=None, width=7):
+    """One of the four alignment launches on host arrays. op "softmax" -> scores; "colstats" -> stats [B][n_pairs][2][ld]; "cost" (scores, stats, width) -> cost
+    [B][max_rows][ld] (`cost` given: what the kernel leaves alone comes back unchanged); "dtw" (cost) -> (frames [B][max_rows], paths: per utterance [(row, frame)]
+    in path order)."""
+    code = {"softmax": 1, "colstats": 2, "cost": 3, "dtw": 4}[op]
+    nr, nf = _i32(n_rows), _i32(n_frames)
+    d = WhisperAlignDesc(op=code, n_rows=_ptr(nr, _ip), n_frames=_ptr(nf, _ip), width=int(width))
+    if code <= 3:
+        sc = _f32(scores).copy()
+        B, P, R, ld = sc.shape
+        d.scores = _ptr(sc, _fp)
+    else:
+        co = _f32(cost).copy()
+        (B, R, ld), P = co.shape, 1
+    d.B, d.n_pairs, d.max_rows, d.ld = B, P, R, ld
+    assert nr.size == nf.size == B
+    if code == 1:
+        _lib.check(load().asr_probe_whisper_align(C.byref(d)))
+        return sc
+    if code == 2:
+        st = np.full((B, P, 2, ld), np.nan, np.float32)
+        d.stats = _ptr(st, _fp)
+        _lib.check(load().asr_probe_whisper_align(C.byref(d)))
+        return st
+    if code == 3:
+        st = _f32(stats)
+        co = np.full((B, R, ld), np.nan, np.float32) if cost is None else _f32(cost).copy()
+        d.stats, d.cost = _ptr(st, _fp), _ptr(co, _fp)
+        _lib.check(load().asr_probe_whisper_align(C.byref(d)))
+        return co
+    frames = np.full((B, R), -1, np.int32)
+    stride = R + ld
+    path = np.full((B, stride, 2), -1, np.int32)
+    plen = np.zeros(B, np.int32)
+    d.cost, d.frames, d.path, d.path_stride, d.path_len = _ptr(co, _fp), _ptr(frames, _ip), _ptr(path, _ip), stride, _ptr(plen, _ip)
+    _lib.check(load().asr_probe_whisper_align(C.byref(d)))
+    return frames, [path[b, :plen[b]][::-1].copy() for b in range(B)]

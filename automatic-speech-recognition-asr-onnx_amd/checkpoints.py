@@ -233,6 +233,23 @@ def whisper_begin_suppress_tokens(cfg: WhisperConfig) -> list:
     return sorted({220 % cfg.vocab, cfg.eot_id})
 
 
+def whisper_alignment_heads(model_dir: str):
+    """[(layer, head)] from the `alignment_heads` entry of a generation_config.json beside a Hugging Face Whisper checkpoint -- the cross-attention heads its
+    authors found to follow the audio, which the word timestamps align on --, or None when the folder has no such file or the file no such entry (the
+    transcriber then falls back to every head of the upper half of the decoder layers). `model_dir`: the checkpoint's folder, or a file inside it."""
+    import json
+    import os
+    folder = model_dir if os.path.isdir(model_dir) else os.path.dirname(os.path.abspath(model_dir))
+    path = os.path.join(folder, "generation_config.json")
+    if not os.path.isfile(path):
+        return None
+    with open(path, "r", encoding="utf-8") as f:
+        heads = json.load(f).get("alignment_heads")
+    if not heads:
+        return None
+    return [(int(l), int(h)) for l, h in heads]
+
+
 def synth_paraformer_checkpoint(cfg, seed: int = 0) -> dict:
     """Random Paraformer-shaped checkpoint with FunASR state-dict names (Export_Paraformer.py:389-457,474-563)."""
     rng = np.random.default_rng(seed)

@@ -155,6 +155,40 @@ void launch_append_ids(const int32_t* next, int rows, int32_t* save_ids, int ld_
 void launch_timestamp_rules(float* logits, int ld, int rows, int n_valid, const int32_t* ids, int ld_ids, const int32_t* n_ids, int n_ids_stride, int ts_begin,
                             int no_timestamps_id, int eot_id, int max_initial, hipStream_t s);
 
+// ---- Whisper token / word timestamps (csrc/whisper_align.hip): OpenAI Whisper's cross-attention DTW (openai-whisper timing.py; the reference has no
+// alignment, like the timestamp rules this is the build's own). Capture: the raw scores q . k (f32 accumulate, no extra scale: the folded projections carry
+// it) of the selected heads of ONE decoder layer for one query row per sequence -- row b * n + n - 1 of `q` -- against all n_lfr keys of the sequence's slab,
+// written to out[((b * n_pairs + slot) * max_rows + r) * ld + key], r = *pos_dev + row_bias (device-resident position: one captured graph serves every step).
+// Rows outside [0, max_rows) are not written. sel [n_sel][2] (device) = (head, slot) of this layer's selected heads. Grid (64-key tile, selected head, sequence).
+struct AlignScoresArgs {
+  const void* q; int ld_q; int n;                              // the step's cross-q rows [B n][ld_q], head h at column h * 64
+  const void* k_base; int64_t stride_h;                        // this layer's K slabs [H][rows][64]
+  const UttPlan* plan;                                         // row_off / n_lfr per sequence
+  const int32_t* sel; int n_sel;
+  const int32_t* pos_dev; int row_bias;
+  float* out; int n_pairs, max_rows, ld;
+  int max_keys;                                                // upper bound of n_lfr (sizes the grid)
+};
+template <typename T> void launch_align_scores(const AlignScoresArgs& a, int B, hipStream_t s);
+// The four launches of the alignment proper, on the captured scores [B][n_pairs][max_rows][ld]; n_rows / n_frames [B] live on the device, a sequence with
+// n_rows = 0 is skipped by every kernel. rows_max / frames_max bound them (grid sizes).
+//   1. soft-max, in place, over the first n_frames[b] scores of rows < n_rows[b];
+//   2. per (b, pair, frame) mean and 1 / sqrt(population variance) over the n_rows[b] rows (two passes; variance 0 -> 0: the column standardises to 0)
+//      -> stats [B][n_pairs][2][ld];
+//   3. cost[b][r][j] = -mean over pairs of median over the `width` (odd, <= 9) reflect-padded neighbours of j of the standardised weights
+//      (no filter when n_frames <= width / 2) -> cost [B][max_rows][ld];
+//   4. DTW, one workgroup per sequence, anti-diagonal wavefront, OpenAI's recurrence and tie rule (diagonal if c0 < c1 && c0 < c2, else vertical if
+//      c1 < c0 && c1 < c2, else horizontal), f32 costs; trace [B][trace_stride] bytes ((n_rows + 1) x (n_frames + 1) used); frames_out[b * out_stride + r] =
+//      the smallest frame of row r on the path. path_out (nullable, tests) [B][path_stride][2]: the path's (row, frame) cells from the end backwards,
+//      path_len [B] their count. rows_max bounds n_rows and sizes the three diagonals (dynamic LDS, 12 (rows_max + 1) bytes).
+void launch_align_softmax(float* scores, int B, int n_pairs, int max_rows, int ld, const int32_t* n_rows, const int32_t* n_frames, int rows_max, hipStream_t s);
+void launch_align_colstats(const float* scores, int B, int n_pairs, int max_rows, int ld, const int32_t* n_rows, const int32_t* n_frames, int frames_max,
+                           float* stats, hipStream_t s);
+void launch_align_cost(const float* scores, const float* stats, int B, int n_pairs, int max_rows, int ld, const int32_t* n_rows, const int32_t* n_frames,
+                       int rows_max, int frames_max, int width, float* cost, hipStream_t s);
+void launch_align_dtw(const float* cost, int B, int max_rows, int ld, const int32_t* n_rows, const int32_t* n_frames, int rows_max, unsigned char* trace, size_t trace_stride,
+                      int32_t* frames_out, int out_stride, int32_t* path_out, int path_stride, int32_t* path_len, hipStream_t s);
+
 // ---- TOPK_TOPP_SAMPLING head (Export_Whisper.py:263-308), one workgroup per sequence: repetition penalty on every saved id
 // (negative logits multiplied, others divided; gather before scatter), + `extra` bias (BEGIN_SUPPRESS), x 1/temperature, top-k
 // (k <= 64, ties to the lower index), soft-max + exclusive-cumsum top-p cut, Gumbel-max with clamped uniforms. The uniforms come

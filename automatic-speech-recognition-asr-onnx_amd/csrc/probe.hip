@@ -887,6 +887,101 @@ extern "C" int asr_probe_token_head(asr_probe_token_head_desc* d) {
   });
 }
 
+// ---- the kernels of the Whisper token-timestamp path (csrc/whisper_align.hip) on host arrays, one product launcher per call
+extern "C" int asr_probe_whisper_align(asr_probe_whisper_align_desc* d) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d && d->op >= 0 && d->op <= 4, "probe_whisper_align: bad descriptor");
+    const int op = d->op, B = d->B, P = d->n_pairs, R = d->max_rows, ld = d->ld;
+    ASR_REQUIRE(B >= 1 && B <= 64 && P >= 1 && P <= 64 && R >= 1 && R <= 1536 && ld >= 1 && ld <= 4096, "probe_whisper_align: extents B %d pairs %d rows %d ld %d", B, P, R, ld);
+    const size_t n_scores = (size_t)B * P * R * ld, n_cost = (size_t)B * R * ld, n_stats = (size_t)B * P * 2 * ld;
+    int rows_max = 0, frames_max = 0;
+    if (op >= 1) {
+      ASR_REQUIRE(d->n_rows && d->n_frames, "probe_whisper_align: n_rows / n_frames missing");
+      for (int b = 0; b < B; ++b) {
+        ASR_REQUIRE(d->n_rows[b] >= 0 && d->n_rows[b] <= R && d->n_frames[b] >= 1 && d->n_frames[b] <= ld, "probe_whisper_align: utterance %d: %d rows, %d frames", b,
+                    d->n_rows[b], d->n_frames[b]);
+        rows_max = std::max(rows_max, d->n_rows[b]); frames_max = std::max(frames_max, d->n_frames[b]);
+      }
+      ASR_REQUIRE(rows_max >= 1, "probe_whisper_align: no utterance has rows");
+    }
+    asr_require_device(0);
+    Tmp t;
+    auto up = [&](const void* h, size_t bytes) -> void* {
+      void* p = t.alloc(bytes);
+      HIP_CHECK(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+      return p;
+    };
+    const int32_t* dn = op >= 1 ? (const int32_t*)up(d->n_rows, (size_t)B * 4) : nullptr;
+    const int32_t* df = op >= 1 ? (const int32_t*)up(d->n_frames, (size_t)B * 4) : nullptr;
+    if (op == 0) {
+      const int H = d->H, n = d->n;
+      ASR_REQUIRE(d->q && d->k_slab && d->row_off && d->n_lfr && d->sel && d->scores, "probe_whisper_align: scores: array missing");
+      ASR_REQUIRE(H >= 1 && H <= 64 && n >= 1 && n <= 8 && d->n_sel >= 1 && d->n_sel <= P && d->slab_rows >= 1, "probe_whisper_align: scores: H %d n %d n_sel %d", H, n, d->n_sel);
+      int max_keys = 0;
+      std::vector<UttPlan> plan(B);
+      for (int b = 0; b < B; ++b) {
+        ASR_REQUIRE(d->n_lfr[b] >= 1 && d->n_lfr[b] <= ld && d->row_off[b] >= 0 && d->row_off[b] + d->n_lfr[b] <= d->slab_rows, "probe_whisper_align: utterance %d outside the slab", b);
+        plan[b] = UttPlan{}; plan[b].n_lfr = d->n_lfr[b]; plan[b].row_off = d->row_off[b];
+        max_keys = std::max(max_keys, d->n_lfr[b]);
+      }
+      for (int i = 0; i < d->n_sel; ++i)
+        ASR_REQUIRE(d->sel[2 * i] >= 0 && d->sel[2 * i] < H && d->sel[2 * i + 1] >= 0 && d->sel[2 * i + 1] < P, "probe_whisper_align: sel[%d] = (%d, %d)", i, d->sel[2 * i], d->sel[2 * i + 1]);
+      const size_t nq = (size_t)B * n * H * 64, nk = (size_t)H * d->slab_rows * 64;
+      AlignScoresArgs a;
+      if (d->bf16) {
+        std::vector<bf16_t> hq(nq), hk(nk);
+        for (size_t i = 0; i < nq; ++i) hq[i] = f32_to_bf16(d->q[i]);
+        for (size_t i = 0; i < nk; ++i) hk[i] = f32_to_bf16(d->k_slab[i]);
+        a.q = up(hq.data(), nq * 2); a.k_base = up(hk.data(), nk * 2);
+      } else {
+        a.q = up(d->q, nq * 4); a.k_base = up(d->k_slab, nk * 4);
+      }
+      a.ld_q = H * 64; a.n = n; a.stride_h = (int64_t)d->slab_rows * 64;
+      a.plan = (const UttPlan*)up(plan.data(), sizeof(UttPlan) * B);
+      a.sel = (const int32_t*)up(d->sel, (size_t)d->n_sel * 8); a.n_sel = d->n_sel;
+      a.pos_dev = (const int32_t*)up(&d->position, 4); a.row_bias = n - 1 - d->p0;
+      float* ds = (float*)up(d->scores, n_scores * 4);
+      a.out = ds; a.n_pairs = P; a.max_rows = R; a.ld = ld; a.max_keys = max_keys;
+      if (d->bf16) launch_align_scores<bf16_t>(a, B, nullptr);
+      else launch_align_scores<float>(a, B, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(d->scores, ds, n_scores * 4, hipMemcpyDeviceToHost));
+      return;
+    }
+    if (op == 1) {
+      ASR_REQUIRE(d->scores, "probe_whisper_align: scores missing");
+      float* ds = (float*)up(d->scores, n_scores * 4);
+      launch_align_softmax(ds, B, P, R, ld, dn, df, rows_max, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(d->scores, ds, n_scores * 4, hipMemcpyDeviceToHost));
+    } else if (op == 2) {
+      ASR_REQUIRE(d->scores && d->stats, "probe_whisper_align: scores / stats missing");
+      float* dst = (float*)up(d->stats, n_stats * 4);
+      launch_align_colstats((const float*)up(d->scores, n_scores * 4), B, P, R, ld, dn, df, frames_max, dst, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(d->stats, dst, n_stats * 4, hipMemcpyDeviceToHost));
+    } else if (op == 3) {
+      ASR_REQUIRE(d->scores && d->stats && d->cost, "probe_whisper_align: scores / stats / cost missing");
+      float* dc = (float*)up(d->cost, n_cost * 4);
+      launch_align_cost((const float*)up(d->scores, n_scores * 4), (const float*)up(d->stats, n_stats * 4), B, P, R, ld, dn, df, rows_max, frames_max, d->width, dc, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(d->cost, dc, n_cost * 4, hipMemcpyDeviceToHost));
+    } else {
+      ASR_REQUIRE(d->cost && d->frames && d->path && d->path_len && d->path_stride >= R + ld, "probe_whisper_align: dtw: array missing or path_stride below rows + frames");
+      const size_t trace_stride = (size_t)(R + 1) * (ld + 1);
+      int32_t* dfr = (int32_t*)up(d->frames, (size_t)B * R * 4);
+      int32_t* dp = (int32_t*)up(d->path, (size_t)B * d->path_stride * 8);
+      int32_t* dl = (int32_t*)t.alloc((size_t)B * 4);
+      launch_align_dtw((const float*)up(d->cost, n_cost * 4), B, R, ld, dn, df, rows_max, (unsigned char*)t.alloc((size_t)B * trace_stride), trace_stride, dfr, R, dp,
+                       d->path_stride, dl, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(d->frames, dfr, (size_t)B * R * 4, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(d->path, dp, (size_t)B * d->path_stride * 8, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(d->path_len, dl, (size_t)B * 4, hipMemcpyDeviceToHost));
+    }
+  });
+}
+
 extern "C" int asr_probe_decode_attention(asr_probe_decode_attn_desc* d) {
   return asr_guard([&] {
     ASR_REQUIRE(d, "probe_decode_attention: null descriptor");

@@ -108,6 +108,22 @@ struct WhSession : asr_session {
   DeviceBuffer d_bext, d_bhist, d_blogits;
   BeamRanker ranker;
   bool after_prefill = false;          // the last call on the session was a prefill (or a beam search, which leaves its state as it was)
+  // Word timestamps (asr_whisper_set_word_timestamps; csrc/whisper_align.hip): while on, the last position of a prefill and every single-token step write the
+  // raw cross-attention scores of the selected (layer, head) pairs into row position - wts_p0 of d_wscores, f32 [B][n_pairs][wts_max_rows][wts_ld]. The
+  // scores are taken against the bf16 (f32) slabs of d_cross in every precision mode: alignment should not inherit e4m3 K. asr_whisper_align turns the
+  // captured rows into frames: soft-max in place, column statistics (d_wstats), cost matrix (d_wcost [B][rows][ld]), DTW (d_wtrace, a byte per cell).
+  bool wts_on = false, wts_consumed = false;
+  int wts_max_rows = 0, wts_p0 = -1, wts_ld = 0, wts_rows = 0;      // wts_p0: prompt length - 1 of the last prefill under the mode; wts_rows: rows captured since
+  uint64_t wts_epoch = 0;                                           // moves with the pair list
+  std::vector<int32_t> wts_pairs;                                   // [n_pairs][2] as given
+  std::vector<int> wts_first, wts_count;                            // per decoder layer: its run in d_wsel
+  std::vector<int32_t> wts_n_rows, wts_n_frames;                    // of the last align
+  DeviceBuffer d_wsel, d_wscores, d_wstats, d_wcost, d_wtrace, d_wn, d_wframes;
+  PinnedBuffer h_walign;
+  int n_pairs() const { return (int)wts_pairs.size() / 2; }
+  void set_word_timestamps(int enable, const int32_t* pairs, int n, int max_rows);
+  void align(const int32_t* n_rows, const int32_t* n_frames, int width, int32_t* frames_out, int out_stride);
+  void align_read(int what, int b, void* host_out, size_t bytes, int32_t* shape_out);
   uint64_t ws_epoch = 1;
   PinnedBuffer h_plan, h_io;
 
@@ -581,6 +597,14 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
         g.W = L.wcq; g.ldw = d; g.M = R; g.N = d; g.K = d; g.bias = L.bcq; g.out_lo = cq; g.ld_out_lo = d;
         ln_gemm(xb, g);
       }
+      if (wts_on && !bs && wts_count[l]) {                 // word timestamps: this layer's selected heads, the step's last query row against the bf16 (f32) K slab
+        ProfScope ps(prof, "align_scores", st);
+        AlignScoresArgs a;
+        a.q = cq; a.ld_q = d; a.n = n; a.k_base = d_cross.as<T>() + (size_t)(0 * Ld + l) * H * Mpad * 64; a.stride_h = (int64_t)Mpad * 64; a.plan = dp;
+        a.sel = d_wsel.as<int32_t>() + 2 * wts_first[l]; a.n_sel = wts_count[l]; a.pos_dev = d_hist.as<int32_t>(); a.row_bias = n - 1 - wts_p0;
+        a.out = d_wscores.as<float>(); a.n_pairs = n_pairs(); a.max_rows = wts_max_rows; a.ld = wts_ld; a.max_keys = max_T_enc;
+        launch_align_scores<T>(a, B, st);
+      }
       {
         ProfScope ps(prof, "dec_cross_attn", st);
         DecAttnArgs a;
@@ -709,6 +733,12 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
   grow(d_dx, (size_t)3 * Rp * d * 4);                  // three f32 residual-stream buffers
   if (precision == ASR_PRECISION_BF16) grow(d_dlo, (size_t)3 * Rp * d * 2);     // ... and their bf16 copies (operands of the LayerNorm-folded projections)
   grow(d_dqkv, (size_t)Rp * (3 * d + d + d + dff + d) * eT + (size_t)Bp * d * eT);
+  if (wts_on) {
+    ASR_REQUIRE(is_prefill || n == 1, "whisper: word-timestamp capture takes one position per decode step (%d given)", n);
+    ASR_REQUIRE(is_prefill || wts_p0 >= 0, "whisper: word-timestamp capture starts at a prefill (none since the mode was switched on or the batch was encoded)");
+    if (is_prefill) { wts_p0 = n - 1; wts_rows = 0; wts_consumed = false; wts_ld = round_up(max_T_enc, 16); }
+    grow(d_wscores, (size_t)B * n_pairs() * wts_max_rows * wts_ld * 4);
+  }
   const int32_t* ids_dev;
   if (ids_host) {
     h_io.reserve((size_t)R * 4 + 64);
@@ -729,8 +759,12 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
   }
   // single-token steps fed from the device are position independent => one graph for all of them
   const bool graphable = use_graph && !ids_host && n == 1 && !taps_enabled && !prof.enabled && !head.noise_armed;
-  const uint64_t key = GraphKey().mix((uint64_t)B).mix((uint64_t)Mpad).mix(ws_epoch).mix(head.epoch).mix(stream).h;
+  GraphKey gk;
+  gk.mix((uint64_t)B).mix((uint64_t)Mpad).mix(ws_epoch).mix(head.epoch).mix(stream);
+  if (wts_on) gk.mix((uint64_t)1).mix(wts_epoch).mix((uint64_t)wts_p0).mix((uint64_t)wts_max_rows).mix((uint64_t)wts_ld).mix(d_wscores.ptr);      // what the capture bakes in
+  const uint64_t key = gk.h;
   dec_graph.run(stream, graphable, key, [&] { enqueue_step<T>(ids_dev, n, is_prefill, true); });
+  if (wts_on) wts_rows = std::min(wts_rows + 1, wts_max_rows);
   hist += n;
   head.consumed();
   if (taps_enabled) save_tap("logits", d_logits.ptr, B, c.vocab, vpad, 4);
@@ -752,6 +786,7 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   ASR_REQUIRE(after_prefill && batch > 0 && hist > 0 && d_logits.ptr, "whisper_beam_search: prefill first");
   ASR_REQUIRE(beam >= 1 && beam <= BEAM_MAX, "whisper_beam_search: beam width %d outside 1..%d", beam, BEAM_MAX);
   ASR_REQUIRE(head.plain(), "whisper_beam_search: the penalty / sampling heads do not combine with beam search");     // (the timestamp rules do: they run before every ranking)
+  ASR_REQUIRE(!wts_on, "whisper_beam_search: word-timestamp capture is on; align a beam's hypothesis with a forced pass over its ids after the search");
   ASR_REQUIRE(hist + max_new <= c.max_target_positions, "whisper_beam_search: %d prompt + %d new positions exceed max_target_positions %d", hist, max_new,
               c.max_target_positions);
   HIP_CHECK(hipSetDevice(device));
@@ -796,6 +831,104 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   HIP_CHECK(hipGetLastError());
   ranker.download(tokens_out, max_new, n_out, scores_out, stream);
   if (prof.enabled) prof.collect();
+}
+
+// ---- word timestamps: the mode, the alignment after generation and its read-back (include/asr_mi355x.h)
+void WhSession::set_word_timestamps(int enable, const int32_t* pairs, int n, int max_rows) {
+  const auto& c = cfg;
+  if (!enable) { wts_on = false; wts_p0 = -1; wts_rows = 0; wts_consumed = false; return; }
+  ASR_REQUIRE(pairs && n >= 1 && n <= c.n_dec_layers * c.n_heads, "whisper_set_word_timestamps: %d (layer, head) pairs outside 1..%d", n, c.n_dec_layers * c.n_heads);
+  ASR_REQUIRE(max_rows >= 1 && max_rows <= c.max_target_positions, "whisper_set_word_timestamps: max_rows %d outside 1..%d", max_rows, c.max_target_positions);
+  std::vector<char> seen((size_t)c.n_dec_layers * c.n_heads, 0);
+  for (int i = 0; i < n; ++i) {
+    const int l = pairs[2 * i], h = pairs[2 * i + 1];
+    ASR_REQUIRE(l >= 0 && l < c.n_dec_layers && h >= 0 && h < c.n_heads, "whisper_set_word_timestamps: pair %d = (layer %d, head %d) outside %d layers x %d heads", i, l, h,
+                c.n_dec_layers, c.n_heads);
+    ASR_REQUIRE(!seen[(size_t)l * c.n_heads + h], "whisper_set_word_timestamps: pair (layer %d, head %d) given twice", l, h);
+    seen[(size_t)l * c.n_heads + h] = 1;
+  }
+  HIP_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipStreamSynchronize(stream));                  // a step in flight may still read the old list
+  wts_p0 = -1; wts_rows = 0; wts_consumed = false;        // the arguments hold: the old capture ends here, the new one starts at the next prefill
+  wts_pairs.assign(pairs, pairs + 2 * n);
+  wts_max_rows = max_rows;
+  wts_first.assign(c.n_dec_layers, 0); wts_count.assign(c.n_dec_layers, 0);
+  std::vector<int32_t> sel;                                 // (head, slot) runs, layer by layer; slot = the pair's index as given
+  for (int l = 0; l < c.n_dec_layers; ++l) {
+    wts_first[l] = (int)sel.size() / 2;
+    for (int i = 0; i < n; ++i)
+      if (pairs[2 * i] == l) { sel.push_back(pairs[2 * i + 1]); sel.push_back(i); ++wts_count[l]; }
+  }
+  d_wsel.reserve(sel.size() * 4, stream);
+  HIP_CHECK(hipMemcpy(d_wsel.ptr, sel.data(), sel.size() * 4, hipMemcpyHostToDevice));
+  ++wts_epoch;
+  wts_on = true;
+}
+
+void WhSession::align(const int32_t* n_rows, const int32_t* n_frames, int width, int32_t* frames_out, int out_stride) {
+  ASR_REQUIRE(n_rows && n_frames && frames_out, "whisper_align: null argument");
+  ASR_REQUIRE(wts_on && wts_p0 >= 0 && wts_rows > 0 && batch > 0 && d_wscores.ptr, "whisper_align: nothing captured (switch word timestamps on, then prefill and decode)");
+  ASR_REQUIRE(!wts_consumed, "whisper_align: the captured rows were aligned already (the soft-max runs in place); prefill and decode again");
+  ASR_REQUIRE(width >= 1 && width <= 9 && (width & 1), "whisper_align: medfilt_width %d (odd, 1..9)", width);
+  const int B = batch, P = n_pairs();
+  int rows_max = 0, frames_max = 0;
+  for (int b = 0; b < B; ++b) {
+    ASR_REQUIRE(n_rows[b] == 0 || (n_rows[b] >= 2 && n_rows[b] <= wts_rows), "whisper_align: n_rows[%d] = %d (0, or 2..%d rows captured since the prefill)", b, n_rows[b], wts_rows);
+    ASR_REQUIRE(n_frames[b] >= 1 && n_frames[b] <= plan[b].n_lfr, "whisper_align: n_frames[%d] = %d outside 1..%d", b, n_frames[b], plan[b].n_lfr);
+    ASR_REQUIRE(n_rows[b] <= out_stride, "whisper_align: out_stride %d below n_rows[%d] = %d", out_stride, b, n_rows[b]);
+    rows_max = std::max(rows_max, n_rows[b]);
+    if (n_rows[b]) frames_max = std::max(frames_max, n_frames[b]);
+  }
+  wts_n_rows.assign(n_rows, n_rows + B); wts_n_frames.assign(n_frames, n_frames + B);
+  if (rows_max == 0) return;
+  HIP_CHECK(hipSetDevice(device));
+  const size_t trace_stride = (size_t)(wts_max_rows + 1) * (wts_ld + 1);
+  d_wn.reserve((size_t)2 * B * 4, stream);
+  d_wstats.reserve((size_t)B * P * 2 * wts_ld * 4, stream);
+  d_wcost.reserve((size_t)B * wts_max_rows * wts_ld * 4, stream);
+  d_wtrace.reserve((size_t)B * trace_stride, stream);
+  d_wframes.reserve((size_t)B * wts_max_rows * 4, stream);
+  h_walign.reserve((size_t)B * std::max(2, wts_max_rows) * 4);
+  int32_t* stage = h_walign.as<int32_t>();
+  memcpy(stage, n_rows, (size_t)B * 4); memcpy(stage + B, n_frames, (size_t)B * 4);
+  HIP_CHECK(hipMemcpyAsync(d_wn.ptr, stage, (size_t)2 * B * 4, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));                  // (the staging buffer receives the frames below)
+  const int32_t* dn = d_wn.as<int32_t>();
+  const int32_t* df = dn + B;
+  {
+    ProfScope ps(prof, "align", stream);
+    launch_align_softmax(d_wscores.as<float>(), B, P, wts_max_rows, wts_ld, dn, df, rows_max, stream);
+    launch_align_colstats(d_wscores.as<float>(), B, P, wts_max_rows, wts_ld, dn, df, frames_max, d_wstats.as<float>(), stream);
+    launch_align_cost(d_wscores.as<float>(), d_wstats.as<float>(), B, P, wts_max_rows, wts_ld, dn, df, rows_max, frames_max, width, d_wcost.as<float>(), stream);
+    launch_align_dtw(d_wcost.as<float>(), B, wts_max_rows, wts_ld, dn, df, rows_max, d_wtrace.as<unsigned char>(), trace_stride, d_wframes.as<int32_t>(),
+                     wts_max_rows, nullptr, 0, nullptr, stream);
+  }
+  wts_consumed = true;
+  HIP_CHECK(hipMemcpyAsync(stage, d_wframes.ptr, (size_t)B * wts_max_rows * 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  for (int b = 0; b < B; ++b)
+    for (int r = 0; r < n_rows[b]; ++r) frames_out[(size_t)b * out_stride + r] = stage[(size_t)b * wts_max_rows + r];
+  if (prof.enabled) prof.collect();
+}
+
+// what 0: the captured scores of utterance b, f32 [n_pairs][rows captured][n_lfr] (after an align the aligned part holds the soft-max: it runs in place);
+// what 1: its cost matrix of the last align, f32 [1][n_rows][n_frames]. shape_out [3] (nullable) receives the three extents; host_out null: only that.
+void WhSession::align_read(int what, int b, void* host_out, size_t bytes, int32_t* shape_out) {
+  ASR_REQUIRE(what == 0 || what == 1, "whisper_align_read: what = %d (0 captured scores, 1 cost matrix)", what);
+  ASR_REQUIRE(wts_on && wts_p0 >= 0 && wts_rows > 0 && d_wscores.ptr, "whisper_align_read: nothing captured");
+  ASR_REQUIRE(b >= 0 && b < batch, "whisper_align_read: utterance %d outside the batch of %d", b, batch);
+  ASR_REQUIRE(what == 0 || ((int)wts_n_rows.size() == batch && wts_consumed), "whisper_align_read: no cost matrix (align first)");
+  const int P = what == 0 ? n_pairs() : 1, rows = what == 0 ? wts_rows : wts_n_rows[b], cols = what == 0 ? plan[b].n_lfr : wts_n_frames[b];
+  if (shape_out) { shape_out[0] = P; shape_out[1] = rows; shape_out[2] = cols; }
+  if (!host_out) return;
+  ASR_REQUIRE(bytes == (size_t)P * rows * cols * 4, "whisper_align_read: %zu bytes given, %zu expected", bytes, (size_t)P * rows * cols * 4);
+  if (bytes == 0) return;
+  HIP_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  const float* src = what == 0 ? d_wscores.as<float>() + (size_t)b * n_pairs() * wts_max_rows * wts_ld : d_wcost.as<float>() + (size_t)b * wts_max_rows * wts_ld;
+  for (int p = 0; p < P; ++p)
+    HIP_CHECK(hipMemcpy2D((float*)host_out + (size_t)p * rows * cols, (size_t)cols * 4, src + (size_t)p * wts_max_rows * wts_ld, (size_t)wts_ld * 4, (size_t)cols * 4, rows,
+                          hipMemcpyDeviceToHost));
 }
 
 }  // namespace
@@ -845,6 +978,7 @@ extern "C" int asr_whisper_encode(asr_session* s, const void* audio, int audio_m
     TenantScope tenant(s);
     WhSession* w = static_cast<WhSession*>(s);
     w->after_prefill = false;
+    w->wts_p0 = -1; w->wts_rows = 0;                      // captured rows belong to the slabs they were scored against
     if (w->precision == ASR_PRECISION_BF16) w->encode<bf16_t>(audio, audio_mem, audio_offsets, batch, n_positions_out);
     else w->encode<float>(audio, audio_mem, audio_offsets, batch, n_positions_out);
   });
@@ -988,4 +1122,20 @@ extern "C" int asr_whisper_beam_search(asr_session* s, int beam, int max_new, in
     if (w->precision == ASR_PRECISION_BF16) w->beam_search<bf16_t>(beam, max_new, eos_id, tokens_out, n_out, scores_out);
     else w->beam_search<float>(beam, max_new, eos_id, tokens_out, n_out, scores_out);
   });
+}
+
+extern "C" int asr_whisper_set_word_timestamps(asr_session* s, int enable, const int32_t* layer_head_pairs, int n_pairs, int max_rows) {
+  return asr_guard([&] { whisper_session(s, "whisper_set_word_timestamps")->set_word_timestamps(enable, layer_head_pairs, n_pairs, max_rows); });
+}
+
+extern "C" int asr_whisper_align(asr_session* s, const int32_t* n_rows, const int32_t* n_frames, int medfilt_width, int32_t* token_frames_out, int out_stride) {
+  return asr_guard([&] {
+    WhSession* w = whisper_session(s, "whisper_align");
+    TenantScope tenant(s);
+    w->align(n_rows, n_frames, medfilt_width, token_frames_out, out_stride);
+  });
+}
+
+extern "C" int asr_whisper_align_read(asr_session* s, int what, int b, void* host_out, size_t bytes, int32_t* shape_out) {
+  return asr_guard([&] { whisper_session(s, "whisper_align_read")->align_read(what, b, host_out, bytes, shape_out); });
 }

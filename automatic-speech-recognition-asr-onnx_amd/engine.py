@@ -466,6 +466,52 @@ class WhisperSession(_token_head("whisper", 20, "Decode head: 1.0 = plain arg-ma
         _lib.check(_lib.load().asr_whisper_set_timestamps(self._h, int(enable), cfg.no_timestamps_id + 1, cfg.no_timestamps_id, cfg.eot_id,
                                                           -1 if max_initial_index is None else int(max_initial_index)))
 
+    def default_alignment_heads(self):
+        """OpenAI's documented fallback when a checkpoint names no alignment heads: every head of the upper half of the decoder layers."""
+        cfg = self.cfg
+        return [(l, h) for l in range(cfg.n_dec_layers // 2, cfg.n_dec_layers) for h in range(cfg.n_heads)]
+
+    def set_word_timestamps(self, enable: bool, alignment_heads=None, max_rows: int | None = None):
+        """Token / word timestamps (asr_whisper_set_word_timestamps; the build's own mode): while on, the last position of a prefill and every single-token
+        decode step capture the raw cross-attention scores of `alignment_heads` [(layer, head)] (None: default_alignment_heads()) for up to max_rows
+        positions (None: max_target_positions); align() turns them into frames. Device memory: batch x pairs x max_rows x ld x 4 bytes -- with the fallback
+        list of a large checkpoint that is 32 times the ten heads such a checkpoint ships, so pass its own list. Beam search is refused while it is on."""
+        if not enable:
+            _lib.check(_lib.load().asr_whisper_set_word_timestamps(self._h, 0, None, 0, 0))
+            return
+        heads = self.default_alignment_heads() if alignment_heads is None else alignment_heads
+        pairs = np.ascontiguousarray(np.asarray(heads, dtype=np.int32).reshape(-1, 2))
+        rows = self.cfg.max_target_positions if max_rows is None else int(max_rows)
+        _lib.check(_lib.load().asr_whisper_set_word_timestamps(self._h, 1, _ip(pairs), pairs.shape[0], rows))
+
+    def align(self, n_rows, n_frames=None, medfilt_width: int = 7):
+        """asr_whisper_align over the rows captured since the last prefill: per utterance an int32 array of n_rows[b] encoder frames (0.02 s each), the first
+        frame of every row on the DTW path. n_rows[b] = text tokens + 1 (0 skips the utterance); n_frames[b]: the encoder positions that hold audio
+        (None: the whole encoder length)."""
+        nr = np.ascontiguousarray(n_rows, dtype=np.int32).reshape(-1)
+        if n_frames is None:
+            n_frames = [self.align_read_shape(0, b)[2] for b in range(self.batch)]
+        nf = np.ascontiguousarray(n_frames, dtype=np.int32).reshape(-1)
+        if nr.size != self.batch or nf.size != self.batch:
+            raise ValueError(f"align: {nr.size} n_rows / {nf.size} n_frames for a batch of {self.batch}")
+        stride = max(1, int(nr.max()))
+        out = np.zeros((self.batch, stride), dtype=np.int32)
+        _lib.check(_lib.load().asr_whisper_align(self._h, _ip(nr), _ip(nf), int(medfilt_width), _ip(out), stride))
+        return [out[b, :nr[b]].copy() for b in range(self.batch)]
+
+    def align_read_shape(self, what: int, b: int):
+        shape = np.zeros(3, dtype=np.int32)
+        _lib.check(_lib.load().asr_whisper_align_read(self._h, int(what), int(b), None, 0, _ip(shape)))
+        return tuple(int(v) for v in shape)
+
+    def align_read(self, what: int, b: int) -> np.ndarray:
+        """Tests / debugging: what = 0 the captured scores of utterance b, f32 [pairs][rows captured][encoder length] (read them before align(): its soft-max
+        runs in place); what = 1 the cost matrix of the last align, f32 [n_rows][n_frames]."""
+        shape = self.align_read_shape(what, b)
+        out = np.zeros(shape, dtype=np.float32)
+        _lib.check(_lib.load().asr_whisper_align_read(self._h, int(what), int(b), out.ctypes.data_as(C.c_void_p), out.nbytes, None))
+        return out if what == 0 else out[0]
+
     def no_speech_prob(self, no_speech_id: int | None = None) -> np.ndarray:
         """NO_SPEECH_DETECTION on the device-resident logits of the last prefill (the probe): (B,) probabilities."""
         out = np.zeros(self.batch, dtype=np.float32)

@@ -20,11 +20,18 @@
                             prefill on -- never on the [SOT] probe, which needs raw logits -- and split_segments() turns the <|t.tt|> ids into
                             segments. The limit is max_target_positions - 3. The tail-repeat guard is NOT applied in this mode: it cuts the id
                             stream at an arbitrary id, which would leave a segment without its closing timestamp.
+  word_timestamps=True    = this build's own mode as well: OpenAI Whisper's cross-attention DTW (openai-whisper timing.py) on the device
+                            (asr_whisper_set_word_timestamps / asr_whisper_align). Behind <|notimestamps|> with a greedy / penalty / sampling head the rows
+                            captured while the ids are generated are the alignment sequence already, nothing is decoded twice; with timestamps=True or
+                            beam_size > 1 a forced pass over the final text ids behind a <|notimestamps|> prompt captures them, as OpenAI does. Results gain
+                            token_times [(start, end)] per text token (and words, with a piece decoder). The repeat guard is not applied; OpenAI's duration
+                            heuristics after the DTW and word probabilities are not part of it.
 Batch extension: `transcribe` takes a list of independent clips as one batch (language detection / no-speech per clip);
 `transcribe_file` is the reference's per-file behaviour (the windows of one file form the batch).
 """
 from __future__ import annotations
 
+import string
 import time
 from typing import Sequence
 
@@ -115,16 +122,107 @@ def split_segments(ids: Sequence[int], ts_begin: int, window_offset_s: float, wi
     return segs
 
 
+# ---- token / word timestamps (OpenAI Whisper timing.py: find_alignment's jump_times, tokenizer.split_tokens_on_spaces, merge_punctuations)
+PREPEND_PUNCTUATIONS = "\"'\u201c\u00bf([{-"
+APPEND_PUNCTUATIONS = "\"'.\u3002,\uff0c!\uff01?\uff1f:\uff1a\u201d)]}\u3001"
+
+
+def token_times(frames: Sequence[int], window_offset_s: float = 0.0, window_end_s: float | None = None, precision: float = TIMESTAMP_PRECISION):
+    """Frames of the aligned rows (WhisperSession.align: row r predicts text token r, the last row predicts eot) -> [(start, end)] in seconds per text
+    token: start = frames[r] * precision, end = frames[r + 1] * precision, both + window_offset_s; the eot row closes the last token. window_end_s given:
+    the ids were cut off before eot, every row is a text token and the last one ends with the window (window_end_s, absolute)."""
+    f = [float(window_offset_s) + int(v) * precision for v in frames]
+    if window_end_s is not None:
+        f.append(max(float(window_end_s), f[-1]) if f else float(window_end_s))
+    return [(f[r], f[r + 1]) for r in range(len(f) - 1)]
+
+
+def split_words(pieces: Sequence[str | None], prepended: str = PREPEND_PUNCTUATIONS, appended: str = APPEND_PUNCTUATIONS) -> list[int]:
+    """Token counts per word over the decoded pieces of the text tokens, in order (the counts sum to len(pieces)). OpenAI's split_tokens_on_spaces: a piece
+    opens a word when it starts with a space, is punctuation, or is the first; otherwise it continues the word. A token that ends inside a UTF-8 sequence
+    has no text of its own: its piece is None and it counts with the token that completes the character (split_tokens_on_unicode; decode_pieces below).
+    Then merge_punctuations: a word that is a space plus a prepended mark joins the word after it, a word that is an appended mark joins the word before
+    it when that one does not end with a space."""
+    words: list[list] = []                                   # [text, token count]
+    pending = 0
+    for piece in pieces:
+        if piece is None:
+            pending += 1
+            continue
+        punctuation = piece.strip() in string.punctuation    # (OpenAI's test as written: a substring of the ASCII punctuation run)
+        if piece.startswith(" ") or punctuation or not words:
+            words.append([piece, 1 + pending])
+        else:
+            words[-1][0] += piece
+            words[-1][1] += 1 + pending
+        pending = 0
+    if pending:                                              # ids that end inside a character: they stay with the last word
+        if words:
+            words[-1][1] += pending
+        else:
+            words.append(["", pending])
+    i, j = len(words) - 2, len(words) - 1
+    while i >= 0:
+        prev, nxt = words[i], words[j]
+        if prev[0].startswith(" ") and prev[0].strip() in prepended:
+            nxt[0], nxt[1] = prev[0] + nxt[0], prev[1] + nxt[1]
+            prev[0], prev[1] = "", 0
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(words):
+        prev, nxt = words[i], words[j]
+        if not prev[0].endswith(" ") and nxt[0] in appended:
+            prev[0], prev[1] = prev[0] + nxt[0], prev[1] + nxt[1]
+            nxt[0], nxt[1] = "", 0
+        else:
+            i = j
+        j += 1
+    return [n for _, n in words if n]
+
+
+def decode_pieces(ids: Sequence[int], decode) -> list:
+    """One piece per id for split_words: `decode`(list of ids) -> str; ids that end inside a UTF-8 sequence (the run so far decodes with U+FFFD) get None
+    and the id that completes the character carries its text (OpenAI's split_tokens_on_unicode)."""
+    pieces, run = [], []
+    for t in ids:
+        run.append(int(t))
+        text = decode(run)
+        if "\ufffd" in text:
+            pieces.append(None)
+        else:
+            pieces.append(text)
+            run = []
+    return pieces
+
+
+def word_times(pieces: Sequence[str], times: Sequence[tuple]):
+    """[{"word", "start", "end", "tokens"}]: the pieces grouped by split_words, each word from the start of its first token to the end of its last
+    (`times` = token_times(...), one pair per piece; "tokens" = the word's token count)."""
+    assert len(pieces) == len(times), (len(pieces), len(times))
+    out, at = [], 0
+    for n in split_words(pieces):
+        out.append({"word": "".join(p for p in pieces[at:at + n] if p), "start": times[at][0], "end": times[at + n - 1][1], "tokens": n})
+        at += n
+    return out
+
+
 class WhisperTranscriber:
     def __init__(self, cfg: WhisperConfig, session: WhisperSession, suppress_tokens=None, task: str = "transcribe",
                  detect_language: bool = True, no_speech_detection: bool = True, no_speech_threshold: float = 0.6,
                  remove_repeats: bool = True, repeat_penalty: float = 1.0, penalty_range: int = 20,
                  use_sampling: bool = False, temperature: float = 0.8, top_k: int = 10, top_p: float = 0.95,
                  sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1,
-                 timestamps: bool = False, max_initial_timestamp: float | None = 1.0):
+                 timestamps: bool = False, max_initial_timestamp: float | None = 1.0, word_timestamps: bool = False, alignment_heads=None,
+                 medfilt_width: int = 7, piece_decoder=None):
         if beam_size > 1 and (float(repeat_penalty) != 1.0 or use_sampling):
             raise ValueError("beam_size > 1 does not combine with a repeat penalty or sampling")
         self.cfg, self.sess = cfg, session
+        # word timestamps (the build's own): alignment_heads [(layer, head)] of the checkpoint (None: the upper half of the decoder layers, OpenAI's fallback);
+        # piece_decoder(list of ids) -> str (a tokenizer's decode), when given, adds words next to token_times
+        self.word_timestamps, self.alignment_heads, self.medfilt_width = bool(word_timestamps), alignment_heads, int(medfilt_width)
+        self.piece_decoder = piece_decoder
         self.beam_size = int(beam_size)
         # timestamp mode (the build's own; combines with every head): the latest first timestamp in seconds -> an index in TIMESTAMP_PRECISION steps
         self.timestamps = bool(timestamps)
@@ -158,18 +256,92 @@ class WhisperTranscriber:
             self.sess.set_timestamps(False)
         return self.sess.prefill(np.full((B, 1), self.cfg.sot_id, dtype=np.int32))[1]
 
-    def _prefill_and_continue(self, prompt: np.ndarray, limit: int):
-        """The full-prompt prefill and the ids after it under the transcriber's head; timestamp mode is on from this prefill to the last id only."""
+    def _prefill_and_continue(self, prompt: np.ndarray, limit: int, audio_samples=None, skip=None):
+        """The full-prompt prefill and the ids after it under the transcriber's head; timestamp mode is on from this prefill to the last id only.
+        -> (ids, frames). frames: per utterance (the aligned frames of its text tokens -- None: nothing aligned --, whether the ids ended with eot); with
+        word_timestamps they are captured live while the ids are generated, or by a forced pass when the ids carry timestamps or come from the beam search."""
+        B = prompt.shape[0]
+        live = self.word_timestamps and not self.timestamps and self.beam_size == 1 and limit > 0
+        frames = [(None, True)] * B
         self.sess.set_penalty(self.repeat_penalty, self.penalty_range)
         self.sess.set_sampling(*self.sampling)
         if self.timestamps:
             self.sess.set_timestamps(True, self.max_initial_index)
+        if live:
+            self.sess.set_word_timestamps(True, self.alignment_heads, limit + 1)
         try:
             self.sess.prefill(prompt, want_logits=False)
-            return self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * prompt.shape[0]
+            toks = self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * B
+            if live:
+                ended = [len(t) < limit for t in toks]                # fewer ids than the limit: the utterance met eot, whose row was captured too
+                frames = self._align([len(t) + int(e) for t, e in zip(toks, ended)], ended, audio_samples, skip)
         finally:
             if self.timestamps:
                 self.sess.set_timestamps(False)
+            if live:
+                self.sess.set_word_timestamps(False)
+        if self.word_timestamps and not live and limit > 0:
+            frames = self._forced_alignment(prompt, [self._text_ids(tk) for tk in toks], audio_samples, skip)
+        return toks, frames
+
+    def _text_ids(self, ids):
+        """The ids that carry text (and times): all of them behind <|notimestamps|>, the ones below the first timestamp id in timestamp mode."""
+        return [int(t) for t in ids if not self.timestamps or t < self.ts_begin]
+
+    def _align(self, n_rows, ended, audio_samples, skip):
+        """sess.align over the captured rows -> [(frames or None, ended)] per utterance. n_frames = the encoder positions that hold real samples (OpenAI's
+        num_frames // 2); fewer than two rows, or a skipped utterance: nothing to align."""
+        B = len(n_rows)
+        n_rows = [0 if n < 2 or (skip is not None and skip[b]) else n for b, n in enumerate(n_rows)]
+        n_enc = [self.sess.align_read_shape(0, b)[2] for b in range(B)]
+        hop2 = 2 * self.cfg.hop_length
+        n_frames = [n_enc[b] if audio_samples is None else max(1, min(n_enc[b], int(audio_samples[b]) // hop2)) for b in range(B)]
+        if not any(n_rows):
+            return [(None, e) for e in ended]
+        frames = self.sess.align(n_rows, n_frames, self.medfilt_width)
+        return [(frames[b] if n_rows[b] else None, ended[b]) for b in range(B)]
+
+    def _forced_alignment(self, prompt: np.ndarray, text_ids, audio_samples, skip):
+        """What OpenAI does after decoding: the capture over the final text ids only, behind a <|notimestamps|> prompt -- a prefill and host-fed decode steps
+        under the plain head, timestamp rules off; an utterance that has run out of ids is fed eot. The row of the last text id predicts eot."""
+        cfg, sess = self.cfg, self.sess
+        B, longest = prompt.shape[0], max((len(t) for t in text_ids), default=0)
+        if longest == 0:
+            return [(None, True)] * B
+        forced = np.concatenate([prompt[:, :3], np.full((B, 1), cfg.no_timestamps_id, np.int32)], axis=1).astype(np.int32)
+        sess.set_penalty(1.0, self.penalty_range)
+        sess.set_sampling(False)
+        sess.set_word_timestamps(True, self.alignment_heads, longest + 1)
+        try:
+            sess.prefill(forced, want_logits=False)
+            for t in range(longest):
+                sess.decode(np.asarray([ids[t] if t < len(ids) else cfg.eot_id for ids in text_ids], np.int32))
+            return self._align([len(ids) + 1 if ids else 0 for ids in text_ids], [True] * B, audio_samples, skip)
+        finally:
+            sess.set_word_timestamps(False)
+
+    def _token_times(self, aligned, text_ids, offset_s: float, window_s: float):
+        """token_times (and words) of one utterance's text ids from its entry of _prefill_and_continue's frames."""
+        frames, ended = aligned
+        n = len(text_ids)
+        if frames is None:                                   # nothing aligned (no ids, or a single id cut off at the limit): the ids span the window
+            times = [(float(offset_s), float(offset_s) + float(window_s))] * n
+        else:
+            times = token_times(frames[:n + 1] if ended else frames[:n], offset_s, None if ended else offset_s + window_s)
+        out = {"token_times": times}
+        if self.piece_decoder is not None:
+            out["words"] = word_times(decode_pieces(text_ids, self.piece_decoder), times)
+        return out
+
+    def _add_segment_times(self, segments, times, words_of=None):
+        """Segments of timestamp mode gain token_times (and words) by token count."""
+        at = 0
+        for seg in segments:
+            n = len(seg["tokens"])
+            seg["token_times"] = times[at:at + n]
+            if self.piece_decoder is not None:
+                seg["words"] = word_times(decode_pieces(seg["tokens"], self.piece_decoder), seg["token_times"])
+            at += n
 
     def _continue(self, limit: int):
         """Ids after the full-prompt prefill: greedy / penalty-greedy / sampling, or the first hypothesis of the beam search."""
@@ -198,7 +370,7 @@ class WhisperTranscriber:
         limit = max(0, cfg.max_target_positions - prompt.shape[1])
         if max_new is not None:
             limit = min(limit, max_new)
-        toks = self._prefill_and_continue(prompt, limit)
+        toks, aligned = self._prefill_and_continue(prompt, limit, [a.size for a in audios], skipped)
         wall = time.time() - t0
         out = []
         for b in range(B):
@@ -207,9 +379,13 @@ class WhisperTranscriber:
             if self.timestamps:
                 res["segments"] = split_segments(ids, self.ts_begin, 0.0, audios[b].size / cfg.sample_rate)
                 ids = [t for t in ids if t < self.ts_begin]
-            elif self.remove_repeats:
+            elif self.remove_repeats and not self.word_timestamps:
                 ids = list(remove_repeated_parts(ids, 3, len(ids)))
             res["tokens"] = np.asarray(ids, dtype=np.int32)
+            if self.word_timestamps:
+                res.update(self._token_times(aligned[b], ids, 0.0, audios[b].size / cfg.sample_rate))
+                if self.timestamps:
+                    self._add_segment_times(res["segments"], res["token_times"])
             out.append(res)
         total_s = sum(a.size for a in audios) / cfg.sample_rate
         return out, {"rtf": wall / total_s, "wall_s": wall}
@@ -254,7 +430,7 @@ class WhisperTranscriber:
             limit = max(0, cfg.max_target_positions - prompt.shape[1])
             if max_new is not None:
                 limit = min(limit, max_new)
-            toks = self._prefill_and_continue(prompt, limit)
+            toks, frames_w = self._prefill_and_continue(prompt, limit, [min(window, max(1, audio_len - w * stride)) for w in range(n_win)])
             windows = [t.astype(int).tolist() for t in toks]
         wall = time.time() - t0
         ids = [t for w in windows for t in w]
@@ -264,7 +440,15 @@ class WhisperTranscriber:
             res["segments"] = [seg for w, win in enumerate(windows)
                                for seg in split_segments(win, self.ts_begin, w * stride / cfg.sample_rate, window / cfg.sample_rate)]
             ids = [t for t in ids if t < self.ts_begin]
-        elif self.remove_repeats:
+        elif self.remove_repeats and not self.word_timestamps:
             ids = list(remove_repeated_parts(ids, 3, len(ids)))
         res["tokens"] = np.asarray(ids, dtype=np.int32)
+        if self.word_timestamps:                                        # per window, offset as the segments are; an open last token ends with its window
+            per = [self._token_times(frames_w[w], self._text_ids(win), w * stride / cfg.sample_rate, window / cfg.sample_rate)
+                   for w, win in enumerate(windows)]
+            res["token_times"] = [t for p in per for t in p["token_times"]]
+            if self.piece_decoder is not None:
+                res["words"] = [x for p in per for x in p["words"]]
+            if self.timestamps:
+                self._add_segment_times(res["segments"], res["token_times"])
         return res, {"rtf": wall / max(audio_len / cfg.sample_rate, 1e-9), "wall_s": wall}

@@ -284,6 +284,29 @@ int asr_whisper_set_sampling_noise(asr_session* s, const float* uniforms, int co
  * the penalised ones under asr_whisper_set_penalty; beam scores are log-soft-max values of the masked rows, as OpenAI's are. Ids are checked:
  * 0 <= eot_id < no_timestamps_id < timestamp_begin_id < vocab. enable = 0 ignores the other arguments; no kernel is added to any step then. */
 int asr_whisper_set_timestamps(asr_session* s, int enable, int timestamp_begin_id, int no_timestamps_id, int eot_id, int max_initial_index);
+/* Token / word timestamps: OpenAI Whisper's cross-attention DTW (openai-whisper timing.py). Like the beam search and the timestamp rules this is the build's own
+ * mode: the reference always decodes behind <|notimestamps|> and aligns nothing. With enable != 0 the last position of every prefill and the position of every
+ * single-token decode step (host-fed or fed from the device inside the captured graph) write one row of raw cross-attention scores q . k -- f32 accumulate, no
+ * extra scale: the folded projections carry it -- of every selected (layer, head) pair over all encoder positions of the sequence, into session memory
+ * f32 [B][n_pairs][max_rows][ld], ld >= the longest encoder length (B * n_pairs * max_rows * ld * 4 bytes: 32 x 10 x 225 x 1504 x 4 = 0.43 GB). Row index =
+ * position - (prompt length - 1); rows >= max_rows are not written. The scores are taken against the bf16 (f32 sessions: f32) cross-K slabs in every precision
+ * mode, FP8W / FP8MM / MXFP4W included. layer_head_pairs: host [n_pairs][2], in range, distinct, 1 <= n_pairs <= n_dec_layers * n_heads; 1 <= max_rows <=
+ * max_target_positions. While the mode is on asr_whisper_beam_search is refused (align a hypothesis with a forced pass over its ids: prefill + host-fed decode
+ * steps) and a decode step takes one position. enable = 0 ignores the other arguments; no kernel is added to any step then. */
+int asr_whisper_set_word_timestamps(asr_session* s, int enable, const int32_t* layer_head_pairs, int n_pairs, int max_rows);
+/* The alignment of the rows captured since the last prefill, four launches on the session's stream: soft-max over the first n_frames[b] scores of each row
+ * (crop, then soft-max, in place); mean and population variance over the n_rows[b] rows per (pair, frame) -- a column of variance 0 standardises to 0, where
+ * OpenAI divides by zero --; median filter of medfilt_width (odd, 1..9; OpenAI: 7) along frames with reflect padding (skipped when n_frames <= width / 2), mean
+ * over the pairs, negated; DTW with OpenAI's recurrence and tie rule in f32. n_rows[b] (host): 0 = skip, else 2 .. rows captured -- the text tokens plus one:
+ * the row of the <|notimestamps|> input predicts the first text token, the row of the last text token predicts eot. n_frames[b]: 1 .. encoder length of b, the
+ * part of the window that holds audio (OpenAI's num_frames / 2). token_frames_out host [B][out_stride]: for r < n_rows[b] the first encoder frame (0.02 s each)
+ * of row r on the path, OpenAI's jump_times before the division. One align per capture: the soft-max is in place. */
+int asr_whisper_align(asr_session* s, const int32_t* n_rows, const int32_t* n_frames, int medfilt_width, int32_t* token_frames_out, int out_stride);
+/* Tests / debugging: what = 0 the captured scores of utterance b, f32 [n_pairs][rows captured][encoder length of b] (after an align the aligned part holds the
+ * soft-max); what = 1 its cost matrix of the last align, f32 [1][n_rows[b]][n_frames[b]]. shape_out (host [3], nullable) receives the extents: the number of
+ * rows captured is the session's knowledge (asr_whisper_generate decides how many steps run), so a caller asks for it -- host_out NULL reports the extents
+ * only -- before it sizes host_out; else bytes must be their product times 4. */
+int asr_whisper_align_read(asr_session* s, int what, int b, void* host_out, size_t bytes, int32_t* shape_out);
 
 /* ------------------------------------------------------------------ Qwen3-ASR (audio encoder + Qwen3 decoder with KV cache)
  * Replaces the merged graphs Qwen_ASR prefill_greedy / decode_greedy and the Embed graph (Qwen_ASR/Shared_Merged.py; I/O planner

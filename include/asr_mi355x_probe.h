@@ -189,6 +189,30 @@ typedef struct asr_probe_token_head_desc {
 } asr_probe_token_head_desc;
 int asr_probe_token_head(asr_probe_token_head_desc* d);
 
+/* One kernel of the Whisper token-timestamp path (csrc/whisper_align.hip, launchers in csrc/kernels.h) on host arrays. Every extent a kernel follows is checked
+ * here first. op:
+ *   0 launch_align_scores: q [B n][H 64] and the K slabs k_slab [H][slab_rows][64] (rounded to bf16 on upload when bf16 != 0), sequence b at slab rows
+ *     [row_off[b], row_off[b] + n_lfr[b]); sel [n_sel][2] = (head, slot); the row written is position + n - 1 - p0 (position travels in device memory);
+ *   1 launch_align_softmax, 2 launch_align_colstats (-> stats [B][n_pairs][2][ld]: mean, 1 / std), 3 launch_align_cost (reads scores and stats, width =
+ *     medfilt width -> cost [B][max_rows][ld]), 4 launch_align_dtw (reads cost -> frames [B][max_rows], path [B][path_stride][2] from the end backwards, path_len [B]).
+ * scores [B][n_pairs][max_rows][ld] is uploaded as given and read back after ops 0 and 1; cost likewise after op 3 (what a kernel leaves alone comes back unchanged). */
+typedef struct asr_probe_whisper_align_desc {
+  int32_t op, bf16;
+  int32_t B, H, n, n_pairs, max_rows, ld;
+  /* op 0 */
+  const float* q; const float* k_slab;
+  int32_t slab_rows;
+  const int32_t* row_off; const int32_t* n_lfr;
+  const int32_t* sel; int32_t n_sel;
+  int32_t position, p0;
+  /* ops 1-4 */
+  const int32_t* n_rows; const int32_t* n_frames;
+  int32_t width;
+  float* scores; float* stats; float* cost;
+  int32_t* frames; int32_t* path; int32_t path_stride; int32_t* path_len;
+} asr_probe_whisper_align_desc;
+int asr_probe_whisper_align(asr_probe_whisper_align_desc* d);
+
 /* launches per GEMM kernel family since the last reset, as "family=count;..." (host-side counters: hipGraph replays do not
  * count, so reset, run a session once on a new batch geometry, read). reset != 0 clears the counters after the read. */
 int asr_probe_gemm_counts(int reset, char* buf, int cap);

@@ -67,7 +67,8 @@ def _count(sd, pattern):
     return max(ids) + 1 if ids else 0
 
 
-def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=None, language="zh", decode_mode="zh", input_audio_dtype="F32"):
+def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=None, language="zh", decode_mode="zh", input_audio_dtype="F32",
+            alignment_heads=None):
     cfgm = importlib.import_module(PKG + ".config")
     if family in ("sensevoice", "paraformer"):
         if cmvn is not None:
@@ -103,7 +104,9 @@ def convert(family: str, sd: dict, out: str, precision: int, cmvn=None, tokens=N
         shim = importlib.import_module(PKG + ".ort_shim")
         os.makedirs(out, exist_ok=True)
         blob = arena.build_whisper_arena(cfg, sd, precision, ckm.whisper_suppress_tokens(cfg), ckm.whisper_begin_suppress_tokens(cfg))
-        shim.save_model(os.path.join(out, "Whisper.asrmodel"), "whisper", cfg.to_dict(), blob, {}, precision, input_audio_dtype)
+        # the checkpoint's alignment heads (generation_config.json beside it, when there is one): what the word timestamps align on
+        meta = {"alignment_heads": json.dumps([[int(l), int(h)] for l, h in alignment_heads])} if alignment_heads else {}
+        shim.save_model(os.path.join(out, "Whisper.asrmodel"), "whisper", cfg.to_dict(), blob, meta, precision, input_audio_dtype)
     elif family == "qwen_asr":
         a, t = "thinker.audio_tower.", "thinker.model."
         de, d = sd[a + "ln_post.weight"].shape[0], sd[t + "norm.weight"].shape[0]
@@ -172,8 +175,9 @@ def main():
     if a.tokens:
         with open(a.tokens, "r", encoding="utf-8") as f:
             tokens = json.load(f) if a.tokens.endswith(".json") else [ln.rstrip("\n") for ln in f]
+    heads = importlib.import_module(PKG + ".checkpoints").whisper_alignment_heads(a.checkpoint) if a.family == "whisper" else None
     cfg = convert(a.family, load_state_dict(a.checkpoint), a.out, 0 if a.precision == "bf16" else 1,
-                  load_kaldi_cmvn(a.cmvn) if a.cmvn else None, tokens, a.language, a.decode_mode, a.input_audio_dtype)
+                  load_kaldi_cmvn(a.cmvn) if a.cmvn else None, tokens, a.language, a.decode_mode, a.input_audio_dtype, heads)
     print(f"wrote {a.out}: {cfg}")
 
 

@@ -52,6 +52,9 @@ def run(a) -> dict:
     if (a.precision == "fp8mm" and a.family != "whisper") or (a.precision in ("fp8w", "mxfp4w") and a.family not in ("whisper", "qwen_asr")):
         raise SystemExit("--precision %s exists for --family whisper%s only" % (a.precision, " / qwen_asr" if a.precision == "fp8w" else ""))
     timestamps = getattr(a, "timestamps", False)
+    word_ts = getattr(a, "word_timestamps", False)
+    if word_ts and a.family != "whisper":
+        raise SystemExit("--word-timestamps exists for --family whisper only")
     if timestamps and a.family not in ("sensevoice", "whisper"):
         raise SystemExit("--timestamps exists for --family sensevoice (per token) and --family whisper (per segment) only")
     files = []
@@ -85,8 +88,11 @@ def run(a) -> dict:
         if a.tokenizer:
             from transformers import AutoTokenizer
             tok = AutoTokenizer.from_pretrained(a.tokenizer)
+        # word timestamps align on the checkpoint's own heads (the converter copied generation_config.json's list into the bundle); without one, the fallback
+        heads = json.loads(info.get("metadata", {}).get("alignment_heads", "null")) if word_ts else None
         tr = _m("whisper").WhisperTranscriber(cfg, sess, suppress_tokens=ckm.whisper_suppress_tokens(cfg), detect_language=a.language == "auto",
-                                              repeat_penalty=a.repeat_penalty, beam_size=a.beam, timestamps=timestamps)
+                                              repeat_penalty=a.repeat_penalty, beam_size=a.beam, timestamps=timestamps, word_timestamps=word_ts,
+                                              alignment_heads=heads, piece_decoder=tok.decode if tok is not None and word_ts else None)
         lang_id = None
         if a.language != "auto":
             if tok is None:
@@ -101,9 +107,15 @@ def run(a) -> dict:
             flat = r["tokens"].tolist() if timestamps else [t for w in ids for t in w]      # timestamp mode: the text ids, repeat guard not applied
             text = None
             if tok is not None:
-                text = "[no speech detected]" if r["no_speech"] else (whisper_text(tok, flat, remove_repeats=not timestamps) if flat else "")
+                text = "[no speech detected]" if r["no_speech"] else (whisper_text(tok, flat, remove_repeats=not (timestamps or word_ts)) if flat else "")
             files.append({"path": p, "n_samples": int(pcm.size), "language": a.language, "windows": ids, "text": text, "rtf": stat["rtf"],
                           "language_ids": [r["language_id"]] * len(ids), "no_speech_prob": [r["no_speech_prob"]], "no_speech": r["no_speech"]})
+            if word_ts and not r["no_speech"]:          # the build's own mode: seconds from the file's start, one pair per text id; words with --tokenizer
+                files[-1]["token_times"] = [[float(s), float(e)] for s, e in r["token_times"]]
+                if "words" in r:
+                    files[-1]["words"] = r["words"]
+                    for w in r["words"]:
+                        print("%8.2f %8.2f %s" % (w["start"], w["end"], w["word"]))
             if timestamps:                  # the build's own mode: windows keep every id, <|t.tt|> included; segments in seconds from the file's start
                 files[-1]["segments"] = [dict(seg, text=whisper_text(tok, seg["tokens"], remove_repeats=False)) if tok is not None else seg
                                          for seg in r["segments"]]
@@ -186,6 +198,8 @@ def main():
     r.add_argument("--beam", type=int, default=1, help="beam width (Whisper, Qwen3-ASR; 1 = greedy); > 1 takes the first hypothesis and needs --repeat-penalty 1")
     r.add_argument("--timestamps", action="store_true", help="SenseVoice: add each token's start / end (seconds) and mean frame log-probability to the dump; Whisper: decode with timestamp tokens and add "
                         "segments (start / end in seconds, token ids, text with --tokenizer)")
+    r.add_argument("--word-timestamps", action="store_true", help="Whisper: add each text token's start / end in seconds (cross-attention DTW on the bundle's "
+                        "alignment heads) to the dump; with --tokenizer also words, printed as they are found")
     r.add_argument("--out", required=True)
     r.add_argument("--any-wav-width", dest="strict_wav", action="store_false",
                    help="accept 8 / 24 / 32-bit wav (rescaled to int16); by default only 16-bit wav is taken: the only width whose samples equal the reference's, "
