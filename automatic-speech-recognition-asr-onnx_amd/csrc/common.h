@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 #include <string>
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits
@@ -82,6 +83,12 @@ struct PerDeviceOnce {
     return true;
   }
 };
+
+// ---- environment knobs (debug / ablation switches). Three readings of the string exist and every knob keeps its own:
+//   env_flag: off only when the value starts with '0';  env_on: on only when it starts with '1';  env_int: atoi. Unset: `dflt`.
+inline bool env_flag(const char* name, bool dflt) { const char* e = getenv(name); return e ? e[0] != '0' : dflt; }
+inline bool env_on(const char* name, bool dflt) { const char* e = getenv(name); return e ? e[0] == '1' : dflt; }
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
 // ---- host-side error plumbing (thread-local message, integer status) -------------------
 enum {

@@ -7,6 +7,9 @@
 #include <vector>
 
 #include "common.h"
+#include "gemm.h"
+#include "kernels.h"
+#include "plan_layout.h"
 
 // ---- weight arena (layout written by arena.py) -----------------------------------------
 //   header  : "ASRARENA" | u32 version | u32 n_tensors | u64 data_offset | u64 total_bytes
@@ -72,6 +75,22 @@ struct PinnedBuffer {
   ~PinnedBuffer();
   bool reserve(size_t bytes);      // true when the buffer was (re)allocated: a captured graph that copies into it is stale
   template <typename T> T* as() const { return reinterpret_cast<T*>(ptr); }
+};
+
+// One call's index tables: sections declared once (PlanLayout), then the pinned and the device buffer reserved for the total, then host(x) and
+// dev(x) from the same stored offset, then one copy. The buffers stay the session's; a blob lives on the stack of the call that builds it.
+template <typename T> struct PlanSection { int i; };
+struct PlanBlob {
+  PlanLayout lay;
+  PinnedBuffer& h;
+  DeviceBuffer& d;
+  bool host_moved = false, dev_moved = false;       // set by commit(): a captured graph that bakes that buffer's address in is stale
+  PlanBlob(PinnedBuffer& h_, DeviceBuffer& d_) : h(h_), d(d_) {}
+  template <typename T> PlanSection<T> add(size_t count) { return PlanSection<T>{lay.add(sizeof(T), alignof(T), count)}; }
+  void commit(hipStream_t s, size_t round_to = 1);  // total rounded up to a multiple of round_to
+  template <typename T> T* host(PlanSection<T> x) const { return reinterpret_cast<T*>(h.as<unsigned char>() + lay.off[x.i]); }
+  template <typename T> const T* dev(PlanSection<T> x) const { return reinterpret_cast<const T*>(d.as<unsigned char>() + lay.off[x.i]); }
+  void upload(hipStream_t s) const;
 };
 
 // FNV-1a over the values a captured step bakes in
@@ -157,6 +176,53 @@ struct asr_session {
   std::map<std::string, Tap> taps;
   virtual ~asr_session();     // destroys an owned stream; a derived session's members are gone by then
   void save_tap(const char* name, const void* src, int64_t rows, int64_t cols, int64_t ld_src, int elt);
+};
+
+// ---- front end of a call, shared by the model families
+// The per-session constants of the fbank / STFT launch. whisper = 1: the Whisper STFT (frames = samples / hop, "n_fft" in messages); 0: Kaldi frames.
+struct FrontEnd {
+  const float *dft = nullptr, *melp = nullptr;
+  const void* dft_split = nullptr;
+  int n_bin_tiles = 0, n_kchunks = 0, n_mels = 0, win = 0, hop = 0, whisper = 0;
+  float log_floor = 0.0f;
+  void init(int nfft, int win_, int hop_, int n_mels_, int whisper_, float log_floor_);     // dft / melp / dft_split: set by the session from its arena
+  // utterance b of a packed batch: the length checks (messages carry the family's name), then its samples, frames and fbank workgroups into p;
+  // `frames` and `n_fb` are the batch's running totals
+  void plan_utt(const char* family, int b, const int64_t* offs, int max_audio_len, UttPlan& p, int& frames, int& n_fb) const;
+  FbankArgs args(const void* audio, int audio_dtype, const UttPlan* plan, const int32_t* blk_utt, const int32_t* blk_f0, float* mel_out, float* blk_max) const;
+};
+void fill_fbank_blocks(const UttPlan* plan, int B, int32_t* blk_utt, int32_t* blk_f0);                    // one entry per 64 frames
+void fill_query_blocks(const UttPlan* plan, int n, int q_rows, int32_t* qb_utt, int32_t* qb_q0);         // one entry per q_rows of every plan's T
+// samples [first_sample, first_sample + n_samples) of `audio` where the kernels can read them: host audio is copied into d_audio (grow-only; *moved
+// reports a re-allocation), device audio is used in place
+const void* stage_audio(asr_session& s, DeviceBuffer& d_audio, const void* audio, int audio_mem, int64_t first_sample, int64_t n_samples, bool* moved = nullptr);
+
+// The split-K workspace (16 MiB) and tickets of the skinny / decode GEMMs. Per session (sessions may run concurrently), allocated at the first use.
+struct SplitKGemm {
+  static constexpr size_t WS_BYTES = (size_t)16 << 20;
+  static constexpr int TICKETS = 4096;
+  DeviceBuffer ws, cnt;
+  void ensure(hipStream_t s) { if (!ws.ptr) { ws.reserve(WS_BYTES, s); cnt.reserve((size_t)TICKETS * 4, s); } }
+  GemmArgs attach(const GemmArgs& g0, hipStream_t s);                  // g0 with the workspace in place
+  void run(const GemmArgs& g0, int precision, hipStream_t s);          // bf16: with the workspace; f32: as given
+};
+
+// Decoder projections of an FP8W / MXFP4W session: e4m3 bytes + a power-of-two scale per output row (d_wscale as f32), or e2m1 nibbles + e8m0 block
+// scales per 32 k (d_wscale as bytes), for the weight-streaming GEMMs of a decode step; the exact bf16 dequantisation (d_wdq) serves every other path.
+struct LowBitWeights {
+  struct Slot { const void** w; int N, K; };            // one projection: where the session keeps its pointer, output rows, row length
+  struct Entry { const unsigned char* w; const float* s; const unsigned char* s4; };
+  DeviceBuffer d_w8, d_wscale, d_wdq;
+  std::vector<Entry> e;                                 // [n_layers][per_layer]
+  int per_layer = 0;
+  bool fp4 = false;
+  // layer_slots(i): the projections of layer i, the same (N, K) list in every layer. Quantises them and points every slot at its dequantised copy.
+  void build(int n_layers, bool fp4_, const std::function<std::vector<Slot>(int)>& layer_slots, hipStream_t s);
+  template <typename G> void select(G& g, int layer, int wi) const {      // G: GemmArgs or DecGemmArgs
+    const Entry& x = e[(size_t)layer * per_layer + wi];
+    if (fp4) { g.W4 = x.w; g.w_scale4 = x.s4; }
+    else { g.W8 = x.w; g.w_scale = x.s; }
+  }
 };
 
 template <typename F>

@@ -4,6 +4,8 @@
 #include <atomic>
 #include <cstring>
 
+#include "../../include/asr_mi355x.h"
+
 static thread_local std::string g_last_error;
 void asr_set_error(const std::string& msg) { g_last_error = msg; }
 const std::string& asr_get_error() { return g_last_error; }
@@ -150,6 +152,16 @@ bool PinnedBuffer::reserve(size_t bytes) {
   return true;
 }
 
+void PlanBlob::commit(hipStream_t s, size_t round_to) {
+  lay.round_total(round_to);
+  host_moved = h.reserve(lay.total);
+  void* before = d.ptr;
+  d.reserve(lay.total, s);
+  dev_moved = d.ptr != before;
+}
+
+void PlanBlob::upload(hipStream_t s) const { HIP_CHECK(hipMemcpyAsync(d.ptr, h.ptr, lay.total, hipMemcpyHostToDevice, s)); }
+
 void StepGraph::drop() {
   if (exec) (void)hipGraphExecDestroy(exec);
   exec = nullptr;
@@ -239,6 +251,93 @@ void asr_session::save_tap(const char* name, const void* src, int64_t rows, int6
   t.buf.reserve((size_t)rows * cols * elt, stream);
   HIP_CHECK(hipMemcpy2DAsync(t.buf.ptr, (size_t)cols * elt, src, (size_t)ld_src * elt, (size_t)cols * elt, (size_t)rows,
                              hipMemcpyDeviceToDevice, stream));
+}
+
+// ---------------------------------------------------------------------------------------- front end, session GEMM, low-bit weights
+void FrontEnd::init(int nfft, int win_, int hop_, int n_mels_, int whisper_, float log_floor_) {
+  n_bin_tiles = (nfft / 2 + 1 + 15) / 16;
+  n_kchunks = win_ / 16;
+  n_mels = n_mels_; win = win_; hop = hop_; whisper = whisper_; log_floor = log_floor_;
+}
+
+void FrontEnd::plan_utt(const char* family, int b, const int64_t* offs, int max_audio_len, UttPlan& p, int& frames, int& n_fb) const {
+  const int64_t n = offs[b + 1] - offs[b];
+  ASR_REQUIRE(n >= win, whisper ? "%s: utterance %d has %lld samples (< n_fft %d)" : "%s: utterance %d has %lld samples (< one %d-sample frame)", family, b, (long long)n, win);
+  ASR_REQUIRE(n <= max_audio_len, "%s: utterance %d has %lld samples (> max_audio_len %d)", family, b, (long long)n, max_audio_len);
+  p.audio_off = offs[b] - offs[0];
+  p.n_samples = (int)n;
+  p.n_frames = whisper ? (int)n / hop : ((int)n - win) / hop + 1;      // Whisper: centred STFT with the last frame dropped
+  p.frame_off = frames;
+  p.blk0 = n_fb;
+  frames += p.n_frames;
+  n_fb += (p.n_frames + 63) / 64;
+}
+
+FbankArgs FrontEnd::args(const void* audio, int audio_dtype, const UttPlan* plan, const int32_t* blk_utt, const int32_t* blk_f0, float* mel_out,
+                         float* blk_max) const {
+  FbankArgs fa;
+  fa.audio = audio; fa.audio_dtype = audio_dtype; fa.plan = plan; fa.blk_utt = blk_utt; fa.blk_f0 = blk_f0; fa.dft_packed = dft; fa.mel_packed = melp;
+  fa.mel_out = mel_out; fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = n_mels / 16; fa.n_mels = n_mels;
+  fa.win = win; fa.hop = hop; fa.log_floor = log_floor; fa.whisper = whisper; fa.blk_max = blk_max; fa.dft_split = dft_split;
+  return fa;
+}
+
+void fill_fbank_blocks(const UttPlan* plan, int B, int32_t* blk_utt, int32_t* blk_f0) {
+  for (int b = 0, i = 0; b < B; ++b)
+    for (int f0 = 0; f0 < plan[b].n_frames; f0 += 64) { blk_utt[i] = b; blk_f0[i++] = f0; }
+}
+void fill_query_blocks(const UttPlan* plan, int n, int q_rows, int32_t* qb_utt, int32_t* qb_q0) {
+  for (int u = 0, i = 0; u < n; ++u)
+    for (int q0 = 0; q0 < plan[u].T; q0 += q_rows) { qb_utt[i] = u; qb_q0[i++] = q0; }
+}
+
+const void* stage_audio(asr_session& s, DeviceBuffer& d_audio, const void* audio, int audio_mem, int64_t first_sample, int64_t n_samples, bool* moved) {
+  const size_t eA = s.audio_elt();                       // the session's sample type: offsets are samples, bytes step in eA
+  const void* src = static_cast<const unsigned char*>(audio) + (size_t)first_sample * eA;
+  void* before = d_audio.ptr;
+  if (audio_mem == ASR_MEM_HOST) {
+    d_audio.reserve((size_t)n_samples * eA, s.stream);
+    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, src, (size_t)n_samples * eA, hipMemcpyHostToDevice, s.stream));
+    src = d_audio.ptr;
+  }
+  if (moved) *moved = d_audio.ptr != before;
+  return src;
+}
+
+GemmArgs SplitKGemm::attach(const GemmArgs& g0, hipStream_t s) {
+  ensure(s);
+  GemmArgs g = g0;
+  g.sk_ws = ws.as<float>(); g.sk_ws_bytes = WS_BYTES; g.sk_cnt = cnt.as<int32_t>();
+  return g;
+}
+
+void SplitKGemm::run(const GemmArgs& g0, int precision, hipStream_t s) {
+  if (precision != ASR_PRECISION_BF16) { launch_gemm_f32(g0, s); return; }
+  launch_gemm_bf16(attach(g0, s), s);
+}
+
+void LowBitWeights::build(int n_layers, bool fp4_, const std::function<std::vector<Slot>(int)>& layer_slots, hipStream_t s) {
+  fp4 = fp4_;
+  size_t w_elems = 0, n_scales = 0;                      // per layer
+  for (const Slot& t : layer_slots(0)) { w_elems += (size_t)t.N * t.K; n_scales += t.N; ++per_layer; }
+  // MXFP4W: d_w8 holds the nibbles (half a byte per element), d_wscale the e8m0 block scales (one byte per 32 elements)
+  d_w8.reserve(fp4 ? n_layers * w_elems / 2 : n_layers * w_elems, s);
+  d_wscale.reserve(fp4 ? n_layers * w_elems / 32 : n_layers * n_scales * 4, s);
+  d_wdq.reserve(n_layers * w_elems * 2, s);
+  for (int i = 0; i < n_layers; ++i) {
+    unsigned char* w8 = d_w8.as<unsigned char>() + (fp4 ? i * w_elems / 2 : i * w_elems);
+    bf16_t* dq = d_wdq.as<bf16_t>() + i * w_elems;
+    float* sc = d_wscale.as<float>() + i * n_scales;
+    unsigned char* sc4 = d_wscale.as<unsigned char>() + i * w_elems / 32;
+    for (const Slot& t : layer_slots(i)) {
+      const size_t ne = (size_t)t.N * t.K;
+      if (fp4) launch_quantize_rows_mxfp4((const bf16_t*)*t.w, t.K, t.N, t.K, w8, sc4, dq, s);
+      else launch_quantize_rows_fp8((const bf16_t*)*t.w, t.K, t.N, t.K, w8, sc, dq, s);
+      e.push_back(Entry{w8, sc, sc4});
+      *t.w = dq;                                         // from here on "the weights" are the dequantised copies
+      w8 += fp4 ? ne / 2 : ne; dq += ne; sc += t.N; sc4 += ne / 32;
+    }
+  }
 }
 
 // ---- tenancy table (engine.h)

@@ -55,14 +55,12 @@ int gemm_kernel_counts(char* buf, int cap) {         // "name=count;name=count;.
   if (buf && cap > 0) snprintf(buf, cap, "%s", out.c_str());
   return (int)out.size();
 }
-static bool env_flag(const char* name, bool dflt) { const char* e = getenv(name); return e ? e[0] != '0' : dflt; }
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 void gemm_reload_env() {
   GemmEnv e;
   e.t144 = env_flag("ASR_GEMM_T144", true); e.t144w = env_flag("ASR_GEMM_T144W", true); e.t288w = env_flag("ASR_GEMM_T288W", true);
   e.amax_pp = env_flag("ASR_GEMM_AMAX_PP", true);
   e.big = env_flag("ASR_GEMM_BIG", true); e.pp = env_flag("ASR_GEMM_PP", true); e.splitk = env_flag("ASR_GEMM_SPLITK", true); e.deep = env_flag("ASR_GEMM_DEEP", true);
-  e.skinny144 = getenv("ASR_SKINNY_M144") && getenv("ASR_SKINNY_M144")[0] == '1';
+  e.skinny144 = env_on("ASR_SKINNY_M144", false);
   e.skinny_splitk = env_int("ASR_SKINNY_SPLITK", -1); e.tall_min = env_int("ASR_GEMM_TALL_MIN", 16);
   e.skinny_max_plain = env_int("ASR_SKINNY_MAX_M", 32); e.skinny_nt = env_int("ASR_SKINNY_NT", 2); e.decode_rb = env_int("ASR_DECODE_RB", 0);
   e.decode_nt = env_int("ASR_DECODE_NT", 0); e.decode_ks = env_int("ASR_DECODE_KS", 0); e.decode_attn_wave = env_flag("ASR_DECODE_ATTN_WAVE", true); e.decode_attn_online = env_flag("ASR_DECODE_ATTN_ONLINE", true);

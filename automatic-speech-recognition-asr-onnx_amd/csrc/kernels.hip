@@ -1676,7 +1676,7 @@ static void launch_fbank_typed(const FbankArgs& a, int n_blocks, hipStream_t s) 
   }
   if (a.dft_split) {
     FbankArgs b = a;
-    if (const char* e = getenv("ASR_FBANK_DBG")) b.dbg = atoi(e);
+    b.dbg = env_int("ASR_FBANK_DBG", b.dbg);
     const size_t lds2 = (size_t)FB_A16 * 2 * 2 + (size_t)FB_FRAMES * FB_PLD * sizeof(float);
     static PerDeviceOnce attr2_once;
     if (attr2_once.first()) {
@@ -1759,9 +1759,9 @@ void attention_geometry(int max_T, int head_dim, int* qt, int* nw) {
   const int n_tiles = (max_T + 15) / 16;
   int q = 1;
   while (q < qt_max && (n_tiles + q - 1) / q > 8) ++q;
-  if (const char* e = getenv("ASR_ATTN_QT")) q = std::max(1, std::min(qt_max, atoi(e)));
+  q = std::max(1, std::min(qt_max, env_int("ASR_ATTN_QT", q)));          // (unset: q and w lie inside their clamps already, max_T >= 1 at every caller)
   int w = std::min(8, (n_tiles + q - 1) / q);
-  if (const char* e = getenv("ASR_ATTN_NW")) w = std::max(1, std::min(8, atoi(e)));
+  w = std::max(1, std::min(8, env_int("ASR_ATTN_NW", w)));
   *qt = q;
   *nw = w;
 }

@@ -630,7 +630,6 @@ __global__ void qw_beam_init_kernel(const int32_t* __restrict__ hist_in, int B, 
 // ------------------------------------------------------------------------------------ session
 struct QwEncLayer { const void *wqkv, *wo, *w1, *w2; const float *bqkv, *bo, *b1, *b2; };
 struct QwDecLayer { const void *wqkv, *wo, *gate_up, *down; const float *qn, *kn; };
-struct QwDec8Layer { const unsigned char* w[4]; const float* s[4]; const unsigned char* s4[4]; };      // FP8W mode: e4m3 bytes + per-row power-of-two scales of wqkv, wo, gate_up, down
 
 // one decoder pass: the packed rows (T new positions per sequence) and, for the bf16 prefill, the MFMA attention geometry
 struct DecPass {
@@ -647,10 +646,11 @@ struct AlignReq { int32_t tid = -1; int32_t* slot_off = nullptr; int32_t* bucket
 
 struct QwSession : asr_session {
   asr_qwen_config cfg;
-  int vpad = 0, hpad = 0, cpad = 0, n_bin_tiles = 0, n_kchunks = 0, chunk = 0, cpw = 0, rpw = 0, t_tok = 13;
+  int vpad = 0, hpad = 0, cpad = 0, chunk = 0, cpw = 0, rpw = 0, t_tok = 13;
   std::vector<QwEncLayer> enc;
   std::vector<QwDecLayer> dec;
-  const float *dft = nullptr, *melp = nullptr, *conv1_b = nullptr, *conv2_b = nullptr, *conv3_b = nullptr, *enc_pos = nullptr,
+  FrontEnd fe;
+  const float *conv1_b = nullptr, *conv2_b = nullptr, *conv3_b = nullptr, *enc_pos = nullptr,
               *proj1_b = nullptr, *proj2_b = nullptr, *rope = nullptr, *final_norm = nullptr;
   const void *conv1_w = nullptr, *conv2_w = nullptr, *conv3_w = nullptr, *conv_out_w = nullptr, *proj1_w = nullptr, *proj2_w = nullptr,
              *embed = nullptr, *lm_head = nullptr;
@@ -658,7 +658,7 @@ struct QwSession : asr_session {
   std::vector<int> seq_len;                              // positions in the cache per sequence (host mirror)
   DeviceBuffer d_plan, d_audio, d_mel, d_blkmax, d_feat, d_col, d_c1, d_c2, d_c3, d_xa, d_xb, d_h, d_qk, d_vt, d_ctx, d_ffn, d_aud_out;
   std::vector<char> frozen;      // generate(): finished sequences, allowed to sit at max_seq_len while the others go on
-  DeviceBuffer d_dplan, d_x, d_x2, d_dh, d_qkv, d_q, d_dctx, d_act, d_last, d_logits, d_next, d_kc, d_vc, d_hist, d_stepplan, d_skws, d_skcnt, d_vt2, d_krows, d_xlo, d_x2lo;
+  DeviceBuffer d_dplan, d_x, d_x2, d_dh, d_qkv, d_q, d_dctx, d_act, d_last, d_logits, d_next, d_kc, d_vc, d_hist, d_stepplan, d_vt2, d_krows, d_xlo, d_x2lo;
   bool no_fuse = false, use_graph = true;
   // precision mode ASR_PRECISION_FP8W (opt-in; everything else as in bf16 mode; the MI355X counterpart of the reference's q4f32 / q8f32 decoders, README.md:70,
   // Optimize_ONNX_Common.py:27,55-60): the four projections of every decoder layer as e4m3 bytes with one power-of-two scale per output row, streamed by the
@@ -667,8 +667,7 @@ struct QwSession : asr_session {
   bool fp4 = false;                    // precision mode ASR_PRECISION_MXFP4W: the four projections as OCP MXFP4 (nibbles in d_w8, e8m0 block scales in d_wscale) instead of e4m3
   bool fp8 = false, fp8_fake = false;
   bool use_decode_gemm = true;         // ASR_QWEN_DECODE_GEMM=0: o_proj / down_proj of a decode step through the tiled split-K pass + reduce launch (rounds 1-4) instead of csrc/decode_gemm.hip
-  std::vector<QwDec8Layer> dec8;
-  DeviceBuffer d_w8, d_wscale, d_wdq;
+  LowBitWeights dec8;                  // wqkv, wo, gate_up, down of every decoder layer
   // ---- paged KV cache (the default; ASR_QWEN_KV_PAGED=0 and the persistent decode kernel keep extents). Pool [page][layer][kv head][16][128] for K and for V,
   // one block table [sequence][pps] for all layers, a free list on the host: a sequence holds pages for the positions it has, gets one more when it crosses a
   // page boundary, and gives all of them back the step after it finishes (its table row then points at page 0, a scratch page nobody reads meaningfully).
@@ -694,15 +693,12 @@ struct QwSession : asr_session {
   DeviceBuffer d_bkc, d_bvc, d_bhist, d_bp0, d_bplan;    // beam search: the hypothesis rows' caches, counters and row plan; scores and tables are the ranker's
   BeamRanker ranker;
   StepGraph dec_graph;
-  PinnedBuffer h_plan, h_io, h_ids;
-
-  void gemm(const GemmArgs& g0) {
-    if (precision != ASR_PRECISION_BF16) { launch_gemm_f32(g0, stream); return; }
-    if (!d_skws.ptr) { d_skws.reserve((size_t)16 << 20, stream); d_skcnt.reserve(4096 * 4, stream); }
-    GemmArgs g = g0;
-    g.sk_ws = d_skws.as<float>(); g.sk_ws_bytes = d_skws.cap; g.sk_cnt = d_skcnt.as<int32_t>();
-    launch_gemm_bf16(g, stream);
-  }
+  PinnedBuffer h_plan, h_stepplan, h_io, h_ids;
+  SplitKGemm sk;
+  void gemm(const GemmArgs& g) { sk.run(g, precision, stream); }
+  // the plan of a pass with one row per sequence (a decode step, a beam step over hypothesis rows): uploaded into `dev`, staged in h_stepplan
+  DecPass step_plan(DeviceBuffer& dev, int rows);
+  DecPass step_pass;                   // ... of the decode steps that follow a prefill
   void init();
   bool aligner() const { return cfg.classify_num > 0; }
   template <typename T> void prefill(const void* audio, int audio_mem, const int64_t* offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
@@ -732,14 +728,13 @@ void QwSession::init() {
   ASR_REQUIRE(c.classify_num >= 0, "qwen: classify_num %d", c.classify_num);
   hpad = aligner() ? round_up(c.classify_num, 128) : vpad;   // rows of dec.lm_head: the vocabulary, or the aligner's timestamp buckets
   cpad = round_up(c.conv_channels, 128);
-  n_bin_tiles = (c.nfft / 2 + 1 + 15) / 16;
-  n_kchunks = c.nfft / 16;
+  fe.init(c.nfft, c.nfft, c.hop_length, c.n_mels, 1, 1e-10f);
   const int wt = precision == ASR_PRECISION_BF16 ? ARENA_BF16 : ARENA_F32;
   const int de = c.enc_d, d = c.d_model, qkvn = (c.n_heads + 2 * c.n_kv_heads) * c.d_head;
   auto F = [&](const std::string& n, std::initializer_list<int64_t> sh) { return (const float*)arena.get(n, ARENA_F32, sh).ptr; };
   auto W = [&](const std::string& n, std::initializer_list<int64_t> sh) { return arena.get(n, wt, sh).ptr; };
-  dft = F("fe.dft", {(int64_t)n_bin_tiles * 2 * n_kchunks * 64 * 4});
-  melp = F("fe.mel", {(int64_t)(c.n_mels / 16) * n_bin_tiles * 64 * 4});
+  fe.dft = F("fe.dft", {(int64_t)fe.n_bin_tiles * 2 * fe.n_kchunks * 64 * 4});
+  fe.melp = F("fe.mel", {(int64_t)(c.n_mels / 16) * fe.n_bin_tiles * 64 * 4});
   conv1_w = W("enc.conv1_w", {cpad, 64});          conv1_b = F("enc.conv1_b", {cpad});
   conv2_w = W("enc.conv2_w", {cpad, 9 * cpad});    conv2_b = F("enc.conv2_b", {cpad});
   conv3_w = W("enc.conv3_w", {cpad, 9 * cpad});    conv3_b = F("enc.conv3_b", {cpad});
@@ -766,28 +761,10 @@ void QwSession::init() {
   if (fp8) {
     const int I = c.d_ffn, od = c.n_heads * c.d_head;
     ASR_REQUIRE(d % 256 == 0 && I % 256 == 0 && od % 256 == 0, "qwen: FP8 mode needs d_model, d_ffn and heads x head_dim to be multiples of 256");
-    const int Ns[4] = {qkvn, d, 2 * I, d}, Ks[4] = {d, od, d, I};
-    size_t w_elems = 0, n_scales = 0;
-    for (int j = 0; j < 4; ++j) { w_elems += (size_t)Ns[j] * Ks[j]; n_scales += Ns[j]; }
-    d_w8.reserve(fp4 ? c.n_layers * w_elems / 2 : c.n_layers * w_elems, stream); d_wscale.reserve(fp4 ? c.n_layers * w_elems / 32 : c.n_layers * n_scales * 4, stream);
-    d_wdq.reserve(c.n_layers * w_elems * 2, stream);
-    dec8.resize(c.n_layers);
-    for (int i = 0; i < c.n_layers; ++i) {
+    dec8.build(c.n_layers, fp4, [&](int i) {
       QwDecLayer& L = dec[i];
-      const void** slot[4] = {&L.wqkv, &L.wo, &L.gate_up, &L.down};
-      unsigned char* w8 = d_w8.as<unsigned char>() + (fp4 ? i * w_elems / 2 : i * w_elems);
-      bf16_t* dq = d_wdq.as<bf16_t>() + i * w_elems;
-      float* sc = d_wscale.as<float>() + i * n_scales;
-      unsigned char* sc4 = d_wscale.as<unsigned char>() + i * w_elems / 32;
-      for (int j = 0; j < 4; ++j) {
-        const size_t ne = (size_t)Ns[j] * Ks[j];
-        if (fp4) launch_quantize_rows_mxfp4((const bf16_t*)*slot[j], Ks[j], Ns[j], Ks[j], w8, sc4, dq, stream);
-        else launch_quantize_rows_fp8((const bf16_t*)*slot[j], Ks[j], Ns[j], Ks[j], w8, sc, dq, stream);
-        dec8[i].w[j] = w8; dec8[i].s[j] = sc; dec8[i].s4[j] = sc4;
-        *slot[j] = dq;                                     // from here on "the weights" are the dequantised copies
-        w8 += fp4 ? ne / 2 : ne; dq += ne; sc += Ns[j]; sc4 += ne / 32;
-      }
-    }
+      return std::vector<LowBitWeights::Slot>{{&L.wqkv, qkvn, d}, {&L.wo, d, od}, {&L.gate_up, 2 * I, d}, {&L.down, d, I}};
+    }, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
   }
 }
@@ -915,8 +892,9 @@ void QwSession::decoder_pass(const DecPass& P) {
   const bool norm_in_reduce = bf && !rms_in_gemm && !no_fuse && d == 1024;
   const bool w8 = fp8 && !fp8_fake && rms_in_gemm;           // byte weights: the weight-streaming launches of a decode step
   auto bytes_of = [&](GemmArgs& g, int layer, int wi) {
-    if (w8 && fp4) { g.W4 = dec8[layer].w[wi]; g.w_scale4 = dec8[layer].s4[wi]; }
-    else if (w8) { g.W8 = dec8[layer].w[wi]; g.ldw8 = g.K; g.w_scale = dec8[layer].s[wi]; }
+    if (!w8) return;
+    dec8.select(g, layer, wi);
+    if (!fp4) g.ldw8 = g.K;
   };
   // o_proj / down_proj of a decode step (<= 64 rows, + residual, f32 and bf16 copies of the stream): the decode GEMM of csrc/decode_gemm.hip -- K split across workgroups
   // with the hand-over inside the launch -- instead of the tiled split-K pass and its reduce launch (6.3 + 4.8 us per projection at 64 rows)
@@ -924,6 +902,7 @@ void QwSession::decoder_pass(const DecPass& P) {
   auto dgm_shape_ok = [&](int K, int lda) {
     DecGemmArgs a;
     a.A = (const bf16_t*)ctx; a.lda = lda; a.W = (const bf16_t*)ctx; a.ldw = K; a.M = rows; a.N = d; a.K = K;
+    // (a shape question without a layer: stand-in pointers, not dec8.select)
     if (w8 && fp4) { a.W = nullptr; a.W4 = (const unsigned char*)ctx; a.w_scale4 = (const unsigned char*)ctx; }
     else if (w8) { a.W = nullptr; a.W8 = (const unsigned char*)ctx; a.w_scale = (const float*)ctx; }
     return decode_gemm_supported(a);
@@ -931,21 +910,15 @@ void QwSession::decoder_pass(const DecPass& P) {
   const bool dgm = rms_in_gemm && use_decode_gemm && dgm_shape_ok(H * hd, H * hd) && dgm_shape_ok(I, I);
   auto dg = [&](const T* A, int lda, const void* Wt, int layer, int wi, int N, int K, const float* add, float* of32, T* olo) {
     ProfScope ps(prof, "dec_gemm", stream);
-    if (!d_skws.ptr) { d_skws.reserve((size_t)16 << 20, stream); d_skcnt.reserve(4096 * 4, stream); }
+    sk.ensure(stream);
     DecGemmArgs a;
     a.A = (const bf16_t*)A; a.lda = lda; a.W = (const bf16_t*)Wt; a.ldw = K; a.M = rows; a.N = N; a.K = K;
-    if (w8 && fp4) { a.W = nullptr; a.W4 = dec8[layer].w[wi]; a.w_scale4 = dec8[layer].s4[wi]; }
-    else if (w8) { a.W = nullptr; a.W8 = dec8[layer].w[wi]; a.w_scale = dec8[layer].s[wi]; }
+    if (w8) { a.W = nullptr; dec8.select(a, layer, wi); }
     a.add = add; a.ld_add = d; a.out_f32 = of32; a.ld_out_f32 = d; a.out_lo = (bf16_t*)olo; a.ld_out_lo = d;
-    a.ws = d_skws.as<float>(); a.ws_bytes = d_skws.cap; a.cnt = d_skcnt.as<int32_t>();
+    a.ws = sk.ws.as<float>(); a.ws_bytes = SplitKGemm::WS_BYTES; a.cnt = sk.cnt.as<int32_t>();
     launch_decode_gemm(a, stream);
   };
-  auto can_norm = [&](const GemmArgs& g0) {           // (the session's gemm() adds the split-K workspace: ask with it in place)
-    if (!d_skws.ptr) { d_skws.reserve((size_t)16 << 20, stream); d_skcnt.reserve(4096 * 4, stream); }
-    GemmArgs g = g0;
-    g.sk_ws = d_skws.as<float>(); g.sk_ws_bytes = d_skws.cap; g.sk_cnt = d_skcnt.as<int32_t>();
-    return gemm_reduce_can_norm(g);
-  };
+  auto can_norm = [&](const GemmArgs& g0) { return gemm_reduce_can_norm(sk.attach(g0, stream)); };     // (the session's gemm() adds the split-K workspace: ask with it in place)
   T* xlo = d_xlo.as<T>();
   T* x2lo = d_x2lo.as<T>();
   // 65+ rows (beam search, prefill of short prompts): o_proj / down_proj take the tiled split-K pass; its reduce launch then also writes
@@ -1032,6 +1005,21 @@ void QwSession::finish(int B, int32_t* next_out, float* logits_out, bool sync) {
   if (prof.enabled) prof.collect();
 }
 
+DecPass QwSession::step_plan(DeviceBuffer& dev, int rows) {
+  const int Mb = round_up(rows, 128);
+  PlanBlob pb(h_stepplan, dev);
+  const auto s_plan = pb.add<UttPlan>(rows);
+  const auto s_seq = pb.add<int32_t>(Mb), s_t = pb.add<int32_t>(Mb), s_last = pb.add<int32_t>(Mb);
+  pb.commit(stream);
+  int32_t *seq = pb.host(s_seq), *t = pb.host(s_t), *last = pb.host(s_last);
+  for (int r = 0; r < Mb; ++r) { seq[r] = r < rows ? r : -1; t[r] = 0; last[r] = r < rows ? r : 0; }
+  for (int r = 0; r < rows; ++r) { UttPlan p{}; p.T = 1; p.n_lfr = 1; p.row_off = r; pb.host(s_plan)[r] = p; }
+  pb.upload(stream);
+  DecPass P;
+  P.plan = pb.dev(s_plan); P.row_seq = pb.dev(s_seq); P.row_t = pb.dev(s_t); P.last_rows = pb.dev(s_last); P.rows = rows; P.B = rows; P.step = true;
+  return P;
+}
+
 template <typename T>
 void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
                         const int32_t* post_ids, const int32_t* post_off, int32_t* next_out, float* logits_out, int32_t* ids_len_out,
@@ -1047,17 +1035,14 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
   int frames = 0, n_fb = 0, slots = 0, wins = 0;
   const int64_t base0 = offs[0];
   for (int b = 0; b < B; ++b) {
-    const int64_t n = offs[b + 1] - offs[b];
-    ASR_REQUIRE(n >= c.nfft, "qwen: utterance %d has %lld samples (< n_fft %d)", b, (long long)n, c.nfft);
-    ASR_REQUIRE(n <= c.max_audio_len, "qwen: utterance %d has %lld samples (> max_audio_len %d)", b, (long long)n, c.max_audio_len);
     UttPlan& p = up[b];
-    p.audio_off = offs[b] - base0; p.n_samples = (int)n; p.n_frames = (int)n / c.hop_length; p.frame_off = frames; p.blk0 = n_fb; p.lang = 0;
+    fe.plan_utt("qwen", b, offs, c.max_audio_len, p, frames, n_fb);
     n_chunks[b] = (p.n_frames + chunk - 1) / chunk;
     n_win[b] = (n_chunks[b] + cpw - 1) / cpw;
     slot0[b] = slots; win0[b] = wins;
     n_audio[b] = feat_lengths(p.n_frames);
     p.n_lfr = n_audio[b]; p.T = n_audio[b]; p.row_off = wins * rpw;
-    frames += p.n_frames; n_fb += (p.n_frames + 63) / 64; slots += n_win[b] * cpw; wins += n_win[b];
+    slots += n_win[b] * cpw; wins += n_win[b];
   }
   const int rows_e = wins * rpw, Me = (int)pad_rows(rows_e);
   int att_qt = 0, att_nw = 4, q_rows = 64, max_T = cpw * t_tok, n_qb = 0;
@@ -1102,37 +1087,25 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
     dq_rows = 16 * dqt * dnw;
     for (int b = 0; b < B; ++b) n_dqb += (ids_len[b] + dq_rows - 1) / dq_rows;
   }
-  // plan blob: [UttPlan B][win plans][dec plans B][blk_utt][blk_f0][qb_utt][qb_q0][slot_utt][slot_local][pos_rows Me][src Md][row_seq Md][row_t Md][last B]
-  const size_t plan_bytes = (sizeof(UttPlan) * (2 * (size_t)B + wins) + 4 * (2 * (size_t)n_fb + 2 * (size_t)n_qb + 2 * (size_t)slots + Me + 3 * (size_t)Md + B + 2 * (size_t)n_dqb) + 15) / 16 * 16;
-  h_plan.reserve(plan_bytes + sizeof(UttPlan) * B + 12 * (size_t)round_up(B, 128) + 64);
-  unsigned char* hp = h_plan.as<unsigned char>();
-  UttPlan* h_up = (UttPlan*)hp;
-  UttPlan* h_wp = h_up + B;
-  UttPlan* h_dp = h_wp + wins;
-  int32_t* blk_utt = (int32_t*)(h_dp + B);
-  int32_t* blk_f0 = blk_utt + n_fb;
-  int32_t* qb_utt = blk_f0 + n_fb;
-  int32_t* qb_q0 = qb_utt + n_qb;
-  int32_t* slot_utt = qb_q0 + n_qb;
-  int32_t* slot_local = slot_utt + slots;
-  int32_t* pos_rows = slot_local + slots;
-  int32_t* src = pos_rows + Me;
-  int32_t* row_seq = src + Md;
-  int32_t* row_t = row_seq + Md;
-  int32_t* last = row_t + Md;
-  int32_t* dqb_utt = last + B;
-  int32_t* dqb_q0 = dqb_utt + n_dqb;
-  memcpy(h_up, up.data(), sizeof(UttPlan) * B);
-  memcpy(h_wp, wp.data(), sizeof(UttPlan) * wins);
+  // plan blob: [UttPlan B][win plans][dec plans B][blk_utt][blk_f0][qb_utt][qb_q0][slot_utt][slot_local][pos_rows Me][src Md][row_seq Md][row_t Md][last B][dqb_utt][dqb_q0]
+  PlanBlob pb(h_plan, d_plan);
+  const auto s_up = pb.add<UttPlan>(B), s_wp = pb.add<UttPlan>(wins), s_dp = pb.add<UttPlan>(B);
+  const auto s_blk_utt = pb.add<int32_t>(n_fb), s_blk_f0 = pb.add<int32_t>(n_fb), s_qb_utt = pb.add<int32_t>(n_qb), s_qb_q0 = pb.add<int32_t>(n_qb);
+  const auto s_slot_utt = pb.add<int32_t>(slots), s_slot_local = pb.add<int32_t>(slots), s_pos_rows = pb.add<int32_t>(Me);
+  const auto s_src = pb.add<int32_t>(Md), s_row_seq = pb.add<int32_t>(Md), s_row_t = pb.add<int32_t>(Md), s_last = pb.add<int32_t>(B);
+  const auto s_dqb_utt = pb.add<int32_t>(n_dqb), s_dqb_q0 = pb.add<int32_t>(n_dqb);
+  pb.commit(stream, 16);
+  UttPlan* h_dp = pb.host(s_dp);
+  int32_t *slot_utt = pb.host(s_slot_utt), *slot_local = pb.host(s_slot_local), *pos_rows = pb.host(s_pos_rows), *src = pb.host(s_src);
+  int32_t *row_seq = pb.host(s_row_seq), *row_t = pb.host(s_row_t), *last = pb.host(s_last), *dqb_utt = pb.host(s_dqb_utt), *dqb_q0 = pb.host(s_dqb_q0);
+  memcpy(pb.host(s_up), up.data(), sizeof(UttPlan) * B);
+  memcpy(pb.host(s_wp), wp.data(), sizeof(UttPlan) * wins);
+  fill_fbank_blocks(up.data(), B, pb.host(s_blk_utt), pb.host(s_blk_f0));
+  fill_query_blocks(wp.data(), wins, q_rows, pb.host(s_qb_utt), pb.host(s_qb_q0));     // attention units are windows
   constexpr int32_t PAD = INT32_MIN;
   {
-    int fi = 0, qi = 0;
-    for (int b = 0; b < B; ++b) {
-      for (int f0 = 0; f0 < up[b].n_frames; f0 += 64) { blk_utt[fi] = b; blk_f0[fi++] = f0; }
+    for (int b = 0; b < B; ++b)
       for (int k = 0; k < n_win[b] * cpw; ++k) { slot_utt[slot0[b] + k] = k < n_chunks[b] ? b : -1; slot_local[slot0[b] + k] = k; }
-    }
-    for (int w = 0; w < wins; ++w)
-      for (int q0 = 0; q0 < wp[w].T; q0 += q_rows) { qb_utt[qi] = w; qb_q0[qi++] = q0; }
     for (int r = 0; r < Me; ++r) pos_rows[r] = (r < rows_e && (r % rpw) < cpw * t_tok) ? (r % rpw) % t_tok : 0;
     for (int r = 0; r < Md; ++r) { src[r] = PAD; row_seq[r] = -1; row_t[r] = 0; }
     for (int b = 0; b < B; ++b) {
@@ -1156,33 +1129,13 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
       p.T = ids_len[b]; p.n_lfr = ids_len[b]; p.row_off = drow0[b];
     }
   }
-  d_plan.reserve(plan_bytes, stream);
-  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, hp, plan_bytes, hipMemcpyHostToDevice, stream));
-  const UttPlan* dup = d_plan.as<UttPlan>();
-  const UttPlan* dwp = dup + B;
-  const UttPlan* ddp = dwp + wins;
-  const int32_t* d_blk_utt = (const int32_t*)(ddp + B);
-  const int32_t* d_blk_f0 = d_blk_utt + n_fb;
-  const int32_t* d_qb_utt = d_blk_f0 + n_fb;
-  const int32_t* d_qb_q0 = d_qb_utt + n_qb;
-  const int32_t* d_slot_utt = d_qb_q0 + n_qb;
-  const int32_t* d_slot_local = d_slot_utt + slots;
-  const int32_t* d_pos_rows = d_slot_local + slots;
-  const int32_t* d_src = d_pos_rows + Me;
-  const int32_t* d_row_seq = d_src + Md;
-  const int32_t* d_row_t = d_row_seq + Md;
-  const int32_t* d_last_rows = d_row_t + Md;
-  const int32_t* d_dqb_utt = d_last_rows + B;
-  const int32_t* d_dqb_q0 = d_dqb_utt + n_dqb;
+  pb.upload(stream);
+  const UttPlan *dup = pb.dev(s_up), *dwp = pb.dev(s_wp), *ddp = pb.dev(s_dp);
+  const int32_t *d_blk_utt = pb.dev(s_blk_utt), *d_blk_f0 = pb.dev(s_blk_f0), *d_qb_utt = pb.dev(s_qb_utt), *d_qb_q0 = pb.dev(s_qb_q0);
+  const int32_t *d_slot_utt = pb.dev(s_slot_utt), *d_slot_local = pb.dev(s_slot_local), *d_pos_rows = pb.dev(s_pos_rows), *d_src = pb.dev(s_src);
+  const int32_t *d_row_seq = pb.dev(s_row_seq), *d_row_t = pb.dev(s_row_t), *d_last_rows = pb.dev(s_last), *d_dqb_utt = pb.dev(s_dqb_utt), *d_dqb_q0 = pb.dev(s_dqb_q0);
 
-  const size_t eA = audio_elt();                          // the session's sample type: offsets are samples, bytes step in eA
-  const void* d_aud = static_cast<const unsigned char*>(audio) + (size_t)base0 * eA;
-  const int64_t total_samples = offs[B] - base0;
-  if (audio_mem == ASR_MEM_HOST) {
-    d_audio.reserve((size_t)total_samples * eA, stream);
-    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, d_aud, (size_t)total_samples * eA, hipMemcpyHostToDevice, stream));
-    d_aud = d_audio.ptr;
-  }
+  const void* d_aud = stage_audio(*this, d_audio, audio, audio_mem, base0, offs[B] - base0);
   // ---- front-end + conv stem
   const size_t r1 = (size_t)slots * 50 * 64, r2 = (size_t)slots * 25 * 32, r3 = (size_t)wins * rpw * 16;
   d_mel.reserve((size_t)frames * c.n_mels * 4, stream);
@@ -1202,10 +1155,7 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
   d_aud_out.reserve((size_t)Me * d * 4, stream);
   {
     ProfScope ps(prof, "logmel", stream);
-    FbankArgs fa;
-    fa.audio = d_aud; fa.audio_dtype = audio_dtype; fa.plan = dup; fa.blk_utt = d_blk_utt; fa.blk_f0 = d_blk_f0; fa.dft_packed = dft; fa.mel_packed = melp;
-    fa.mel_out = d_mel.as<float>(); fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = c.n_mels / 16; fa.n_mels = c.n_mels;
-    fa.win = c.nfft; fa.hop = c.hop_length; fa.log_floor = 1e-10f; fa.whisper = 1; fa.blk_max = d_blkmax.as<float>();
+    const FbankArgs fa = fe.args(d_aud, audio_dtype, dup, d_blk_utt, d_blk_f0, d_mel.as<float>(), d_blkmax.as<float>());
     launch_fbank(fa, n_fb, stream);
     if (taps_enabled) save_tap("mel", d_mel.ptr, frames, c.n_mels, c.n_mels, 4);       // log10 mel before the per-utterance clamp: what the front end made of the samples
     hipLaunchKernelGGL(qw_mel_finish_kernel<T>, dim3(slots * chunk), dim3(128), 0, stream, d_mel.as<float>(), d_blkmax.as<float>(), dup, d_slot_utt,
@@ -1304,20 +1254,7 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
   P.head = al == nullptr;
   decoder_pass<T>(P);
   if (al) { align_head<T>(B, ddp, d_src, (int)n_sel, *al); return; }
-  // step plan for the decode calls that follow: one row per sequence
-  {
-    const int Mb = round_up(B, 128);
-    const size_t sbytes = sizeof(UttPlan) * B + 4 * 3 * (size_t)Mb;
-    unsigned char* sh = hp + plan_bytes;                 // tail of the pinned blob (reserved below)
-    UttPlan* sp = (UttPlan*)sh;
-    int32_t* s_seq = (int32_t*)(sp + B);
-    int32_t* s_t = s_seq + Mb;
-    int32_t* s_last = s_t + Mb;
-    for (int r = 0; r < Mb; ++r) { s_seq[r] = r < B ? r : -1; s_t[r] = 0; s_last[r] = r < B ? r : 0; }
-    for (int b = 0; b < B; ++b) { UttPlan p{}; p.T = 1; p.n_lfr = 1; p.row_off = b; sp[b] = p; }
-    d_stepplan.reserve(sbytes, stream);
-    HIP_CHECK(hipMemcpyAsync(d_stepplan.ptr, sh, sbytes, hipMemcpyHostToDevice, stream));
-  }
+  step_pass = step_plan(d_stepplan, B);                   // for the decode calls that follow
   head.consumed();
   finish(B, next_out, logits_out, true);
 }
@@ -1387,7 +1324,7 @@ void QwSession::step(const int32_t* ids_host, int32_t* next_out, float* logits_o
   const auto& c = cfg;
   ASR_REQUIRE(batch > 0, "qwen_decode: prefill first");
   HIP_CHECK(hipSetDevice(device));
-  const int B = batch, d = c.d_model, Mb = round_up(B, 128);
+  const int B = batch, d = c.d_model;
   for (int b = 0; b < B; ++b) {
     ASR_REQUIRE(seq_len[b] + 1 <= c.max_seq_len || (b < (int)frozen.size() && frozen[b]), "qwen_decode: sequence %d is at max_seq_len %d", b, c.max_seq_len);
     // a sequence that generate() finished has given its cache pages back (its table row points at the scratch page): it cannot be stepped again outside that
@@ -1405,13 +1342,7 @@ void QwSession::step(const int32_t* ids_host, int32_t* next_out, float* logits_o
     HIP_CHECK(hipMemcpyAsync(d_next.ptr, st, (size_t)B * 4, hipMemcpyHostToDevice, stream));
   }
   kv_prepare_step(sizeof(T));
-  // the step plan (one row per sequence) was uploaded by prefill
-  const UttPlan* dsp = d_stepplan.as<UttPlan>();
-  const int32_t* d_row_seq = (const int32_t*)(dsp + B);
-  const int32_t* d_row_t = d_row_seq + Mb;
-  const int32_t* d_lastrows = d_row_t + Mb;
-  DecPass P;
-  P.plan = dsp; P.row_seq = d_row_seq; P.row_t = d_row_t; P.last_rows = d_lastrows; P.rows = B; P.B = B; P.step = true;
+  const DecPass P = step_pass;                           // (one row per sequence: uploaded by prefill)
   auto enqueue = [&] {
     { ProfScope ps(prof, "dec_embed", stream);
       hipLaunchKernelGGL(qw_gather_prompt_kernel<T>, dim3(B), dim3(256), 0, stream, (const int32_t*)d_next.ptr, (const T*)embed, (const float*)nullptr, d,
@@ -1422,7 +1353,7 @@ void QwSession::step(const int32_t* ids_host, int32_t* next_out, float* logits_o
   const bool graphable = use_graph && !taps_enabled && !prof.enabled && !head.noise_armed;
   GraphKey key;
   for (const void* q : {d_x.ptr, d_x2.ptr, d_dh.ptr, d_qkv.ptr, d_q.ptr, d_dctx.ptr, d_xlo.ptr, d_x2lo.ptr, d_act.ptr, d_last.ptr, d_logits.ptr, d_next.ptr, d_kc.ptr,
-                        d_vc.ptr, d_kvtab.ptr, d_hist.ptr, d_stepplan.ptr, d_skws.ptr, (void*)stream, (void*)(uintptr_t)B})
+                        d_vc.ptr, d_kvtab.ptr, d_hist.ptr, d_stepplan.ptr, sk.ws.ptr, (void*)stream, (void*)(uintptr_t)B})
     key.mix(q);
   key.mix(head.epoch);
   dec_graph.run(stream, graphable, key.h, enqueue);
@@ -1465,21 +1396,7 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
   d_x.reserve(Mn * d * 4, stream); d_x2.reserve(Mn * d * 4, stream); d_dh.reserve(Mn * d * eT, stream); d_qkv.reserve(Mn * qkvn * 4, stream);
   d_dctx.reserve(Mn * H * hd * eT, stream); d_xlo.reserve(Mn * d * eT, stream); d_x2lo.reserve(Mn * d * eT, stream); d_act.reserve(Mn * I * eT, stream);
   d_last.reserve(Mn * d * eT, stream); d_logits.reserve(Mn * (size_t)vpad * 4, stream);
-  const int Mb = round_up(N, 128);
-  const size_t sbytes = sizeof(UttPlan) * N + 4 * 3 * (size_t)Mb;
-  {
-    std::vector<unsigned char> blob(sbytes);
-    UttPlan* sp = (UttPlan*)blob.data();
-    int32_t* s_seq = (int32_t*)(sp + N); int32_t* s_t = s_seq + Mb; int32_t* s_last = s_t + Mb;
-    for (int r = 0; r < Mb; ++r) { s_seq[r] = r < N ? r : -1; s_t[r] = 0; s_last[r] = r < N ? r : 0; }
-    for (int n = 0; n < N; ++n) { UttPlan p{}; p.T = 1; p.n_lfr = 1; p.row_off = n; sp[n] = p; }
-    d_bplan.reserve(sbytes, stream);
-    HIP_CHECK(hipMemcpyAsync(d_bplan.ptr, blob.data(), sbytes, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));             // `blob` is a stack object
-  }
-  const UttPlan* dsp = d_bplan.as<UttPlan>();
-  DecPass P;
-  P.plan = dsp; P.row_seq = (const int32_t*)(dsp + N); P.row_t = P.row_seq + Mb; P.last_rows = P.row_t + Mb; P.rows = N; P.B = N; P.step = true;
+  DecPass P = step_plan(d_bplan, N);
   P.kc = d_bkc.ptr; P.vc = d_bvc.ptr; P.S = Sb; P.hist = d_bhist.as<int32_t>(); P.beam_p0 = d_bp0.as<int32_t>(); P.ld_src = ld; P.beam = beam;
   for (int t = 0; t + 1 < max_new && !ranker.all_done(stream); ++t) {
     { ProfScope ps(prof, "dec_embed", stream);
@@ -1517,12 +1434,12 @@ extern "C" int asr_qwen_create(const asr_qwen_config* cfg, const void* arena, si
       HIP_CHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
       s->own_stream = true;
       gemm_reload_env();
-      if (const char* e = getenv("ASR_FP8_FAKE")) s->fp8_fake = e[0] == '1';
-      if (const char* e = getenv("ASR_QWEN_DECODE_GEMM")) s->use_decode_gemm = !(e[0] == '0');
-      if (const char* e = getenv("ASR_NO_GRAPH")) s->use_graph = !(e[0] == '1');
-      if (const char* e = getenv("ASR_QWEN_NO_FUSE")) s->no_fuse = e[0] == '1';
-      if (const char* e = getenv("ASR_QWEN_KV_PAGED")) s->kv_paged = !(e[0] == '0');
-      if (const char* e = getenv("ASR_KV_PAGE_SHUFFLE")) s->kv_shuffle = e[0] == '1';
+      s->fp8_fake = env_on("ASR_FP8_FAKE", s->fp8_fake);
+      s->use_decode_gemm = env_flag("ASR_QWEN_DECODE_GEMM", s->use_decode_gemm);
+      s->use_graph = !env_on("ASR_NO_GRAPH", !s->use_graph);
+      s->no_fuse = env_on("ASR_QWEN_NO_FUSE", s->no_fuse);
+      s->kv_paged = env_flag("ASR_QWEN_KV_PAGED", s->kv_paged);
+      s->kv_shuffle = env_on("ASR_KV_PAGE_SHUFFLE", s->kv_shuffle);
       s->arena.load(arena, arena_bytes, arena_mem, s->stream);
       s->init();
     } catch (...) {

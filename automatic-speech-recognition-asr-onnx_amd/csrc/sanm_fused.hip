@@ -359,7 +359,7 @@ void launch_sanm_qkv_attn(const SanmFusedArgs& a, hipStream_t s) {
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(sanm_qkv_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FLDS));
   }
   static int dbg = -1;
-  if (dbg < 0) { const char* e = getenv("ASR_FUSED_DBG"); dbg = e ? atoi(e) : 0; }     // kernel ablation switches (timing only)
+  if (dbg < 0) dbg = env_int("ASR_FUSED_DBG", 0);    // kernel ablation switches (timing only)
   SanmFusedArgs b = a;
   b.dbg = dbg;
   hipLaunchKernelGGL(sanm_qkv_attn_kernel, dim3(a.n_utts * a.n_heads), dim3(FNW * 64), FLDS, s, b);

@@ -43,9 +43,9 @@ struct SvSession : asr_session {
 
   asr_sensevoice_config cfg;
   int feat = 0, kpad0 = 0, vpad = 0, max_lfr = 0;
-  int n_bin_tiles = 0, n_kchunks = 0;
+  FrontEnd fe;
   std::vector<SvBlock> blocks;
-  const float *dft = nullptr, *melp = nullptr, *cmvn_means = nullptr, *cmvn_vars = nullptr, *speech_pos = nullptr;
+  const float *cmvn_means = nullptr, *cmvn_vars = nullptr, *speech_pos = nullptr;
   const float *language_embed = nullptr, *system_embed = nullptr;
   const float *after_g = nullptr, *after_b = nullptr, *tp_g = nullptr, *tp_b = nullptr, *ctc_b = nullptr;
   const void* ctc_w = nullptr;
@@ -112,22 +112,22 @@ struct SvSession : asr_session {
   int block_cooldown = 0;       // batches left on the four-launch path after a give-up (other sessions are holding CUs: do not walk into the same wait again)
   void load_env() {             // debug / ablation switches, re-read at every session creation
     gemm_reload_env();
-    if (const char* e = getenv("ASR_NO_GRAPH")) use_graph = !(e[0] == '1');
-    if (const char* e = getenv("ASR_SANM_FUSED")) use_fused = !(e[0] == '0');
-    if (const char* e = getenv("ASR_SANM_BLOCK")) use_block = !(e[0] == '0');
-    if (const char* e = getenv("ASR_FBANK_SPLIT")) use_fbank_split = !(e[0] == '0');
-    if (const char* e = getenv("ASR_SANM_BLOCK8_OPT")) block8_opt = atoi(e);
-    if (const char* e = getenv("ASR_SANM_BLOCK_FFNK")) block_ffnk = !(e[0] == '0');
+    use_graph = !env_on("ASR_NO_GRAPH", !use_graph);
+    use_fused = env_flag("ASR_SANM_FUSED", use_fused);
+    use_block = env_flag("ASR_SANM_BLOCK", use_block);
+    use_fbank_split = env_flag("ASR_FBANK_SPLIT", use_fbank_split);
+    block8_opt = env_int("ASR_SANM_BLOCK8_OPT", block8_opt);
+    block_ffnk = env_flag("ASR_SANM_BLOCK_FFNK", block_ffnk);
     if ((block8_opt >> 4) & 15) block_ffnk = false;          // the timing-only ablations exist for the round-4 loops
-    if (const char* e = getenv("ASR_SANM_TILES")) use_tiles = !(e[0] == '0');
-    if (const char* e = getenv("ASR_SANM_TILES_OPT")) tiles_opt = atoi(e);
-    if (const char* e = getenv("ASR_SANM_TILES_DBG")) tiles_dbg = atoi(e);
-    if (const char* e = getenv("ASR_SANM_BLOCK_PERSIST")) block_persist = !(e[0] == '0');
-    if (const char* e = getenv("ASR_SANM_BLOCK_SCATTER")) block_scatter = e[0] == '1';
-    if (const char* e = getenv("ASR_SANM_BLOCK_FAULT")) block_fault = e[0] == '1';
-    if (const char* e = getenv("ASR_SANM_BLOCK_DBG")) block_dbg = atoi(e);
-    if (const char* e = getenv("ASR_SANM_BLOCK_MIN")) block_min_utts = atoi(e);
-    if (const char* e = getenv("ASR_LN_FUSED")) use_ln_alg = !(e[0] == '0');
+    use_tiles = env_flag("ASR_SANM_TILES", use_tiles);
+    tiles_opt = env_int("ASR_SANM_TILES_OPT", tiles_opt);
+    tiles_dbg = env_int("ASR_SANM_TILES_DBG", tiles_dbg);
+    block_persist = env_flag("ASR_SANM_BLOCK_PERSIST", block_persist);
+    block_scatter = env_on("ASR_SANM_BLOCK_SCATTER", block_scatter);
+    block_fault = env_on("ASR_SANM_BLOCK_FAULT", block_fault);
+    block_dbg = env_int("ASR_SANM_BLOCK_DBG", block_dbg);
+    block_min_utts = env_int("ASR_SANM_BLOCK_MIN", block_min_utts);
+    use_ln_alg = env_flag("ASR_LN_FUSED", use_ln_alg);
   }
   int block_scatter = 0;        // ASR_SANM_BLOCK_SCATTER=1: test placement, every cluster spread over four XCDs
   int block_min_utts = 12;      // ASR_SANM_BLOCK_MIN=<windows>: smallest batch that takes the block kernel (8-wave form: faster from ~10 windows on; tools/probes/block_min_sweep.sh)
@@ -144,13 +144,11 @@ struct SvSession : asr_session {
   template <typename T> void run(const void* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang,
                                  int32_t* tok_out, int max_tokens, int32_t* num_out, int32_t* first_out = nullptr, int32_t* last_out = nullptr,
                                  float* logprob_out = nullptr);
-  DeviceBuffer d_skws, d_skcnt;        // split-K workspace + tickets of the skinny GEMM (per session: sessions may run concurrently)
+  SplitKGemm sk;
   void gemm(const GemmArgs& g0) {
-    if (!d_skws.ptr) { d_skws.reserve((size_t)16 << 20, stream); d_skcnt.reserve(4096 * 4, stream); }
-    GemmArgs g = g0;
-    g.sk_ws = d_skws.as<float>(); g.sk_ws_bytes = d_skws.cap; g.sk_cnt = d_skcnt.as<int32_t>();
-    if (precision != ASR_PRECISION_BF16) { launch_gemm_f32(g, stream); return; }      // (the workspace lets single windows split K)
-    launch_gemm_bf16(g, stream);
+    const GemmArgs g = sk.attach(g0, stream);          // in f32 sessions too: the workspace lets single windows split K
+    if (precision != ASR_PRECISION_BF16) launch_gemm_f32(g, stream);
+    else launch_gemm_bf16(g, stream);
   }
 };
 
@@ -168,20 +166,20 @@ void SvSession::init() {
   feat = c.n_mels * c.lfr_m;
   kpad0 = round_up(feat, 64);
   vpad = round_up(c.vocab, 128);
-  n_bin_tiles = (c.nfft / 2 + 1 + 15) / 16;
-  n_kchunks = c.win_length / 16;
+  fe.init(c.nfft, c.win_length, c.hop_length, c.n_mels, 0, 1.1920928955078125e-07f);
   const int n_frames_max = (c.max_audio_len - c.win_length) / c.hop_length + 1;
   max_lfr = (n_frames_max + c.lfr_n - 1) / c.lfr_n;
   const int wt = precision == ASR_PRECISION_BF16 ? ARENA_BF16 : ARENA_F32;
   const int d = c.d_model, dff = c.d_ffn;
 
-  dft = (const float*)arena.get("fe.dft", ARENA_F32, {(int64_t)n_bin_tiles * 2 * n_kchunks * 64 * 4}).ptr;
+  fe.dft = (const float*)arena.get("fe.dft", ARENA_F32, {(int64_t)fe.n_bin_tiles * 2 * fe.n_kchunks * 64 * 4}).ptr;
   if (precision == ASR_PRECISION_BF16 && use_fbank_split) {       // bf16 sessions: the DFT on the bf16 pipe with split operands (kernels.hip: fbank_split_kernel)
-    d_dft_split.reserve(fbank_split_table_bytes(n_bin_tiles, cfg.win_length), stream);
-    launch_fbank_split_table(dft, n_bin_tiles, n_kchunks, d_dft_split.ptr, stream);
+    d_dft_split.reserve(fbank_split_table_bytes(fe.n_bin_tiles, cfg.win_length), stream);
+    launch_fbank_split_table(fe.dft, fe.n_bin_tiles, fe.n_kchunks, d_dft_split.ptr, stream);
     HIP_CHECK(hipStreamSynchronize(stream));
+    fe.dft_split = d_dft_split.ptr;
   }
-  melp = (const float*)arena.get("fe.mel", ARENA_F32, {(int64_t)(c.n_mels / 16) * n_bin_tiles * 64 * 4}).ptr;
+  fe.melp = (const float*)arena.get("fe.mel", ARENA_F32, {(int64_t)(c.n_mels / 16) * fe.n_bin_tiles * 64 * 4}).ptr;
   cmvn_means = opt("fe.cmvn_means", {feat});
   cmvn_vars = (const float*)arena.get("fe.cmvn_vars", ARENA_F32, {feat}).ptr;
   speech_pos = (const float*)arena.get("fe.speech_pos", ARENA_F32, {max_lfr, feat}).ptr;
@@ -224,7 +222,7 @@ void SvSession::init() {
         L.bo = (const float*)arena.get(q + "bo", ARENA_F32, {d}).ptr;
       }
     }
-    if (const char* e = getenv("ASR_PF_KV_BATCH")) pf_kv_batch = !(e[0] == '0');
+    pf_kv_batch = env_flag("ASR_PF_KV_BATCH", pf_kv_batch);
     pf_n_full = 0;
     for (const PfDecLayer& L : pdec) pf_n_full += L.full ? 1 : 0;
     if (pf_kv_batch && pf_n_full > 0) {
@@ -334,12 +332,7 @@ void SvSession::enqueue(const SvRunCtx& r) {
   // ---- 1. Kaldi fbank (Export_SenseVoice.py:275-278) ---------------------------------------
   {
     ProfScope ps(prof, "fbank", stream);
-    FbankArgs fa;
-    fa.audio = r.d_aud; fa.audio_dtype = audio_dtype; fa.plan = r.dp; fa.blk_utt = r.d_blk_utt; fa.blk_f0 = r.d_blk_f0;
-    fa.dft_packed = dft; fa.mel_packed = melp; fa.mel_out = d_mel.as<float>();
-    fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = c.n_mels / 16; fa.n_mels = c.n_mels;
-    fa.win = c.win_length; fa.hop = c.hop_length; fa.log_floor = 1.1920928955078125e-07f; fa.whisper = 0; fa.blk_max = nullptr;
-    fa.dft_split = d_dft_split.ptr;
+    const FbankArgs fa = fe.args(r.d_aud, audio_dtype, r.dp, r.d_blk_utt, r.d_blk_f0, d_mel.as<float>(), nullptr);
     launch_fbank(fa, r.n_fb, stream);
   }
   save_tap("mel", d_mel.ptr, r.frames, c.n_mels, c.n_mels, 4);
@@ -754,58 +747,44 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   const int64_t base0 = offs[0];
   GraphKey key;                                          // everything that shapes the launch sequence
   for (int b = 0; b < batch; ++b) {
-    const int64_t n = offs[b + 1] - offs[b];
-    ASR_REQUIRE(n >= c.win_length, "sensevoice: utterance %d has %lld samples (< one %d-sample frame)", b, (long long)n, c.win_length);
-    ASR_REQUIRE(n <= c.max_audio_len, "sensevoice: utterance %d has %lld samples (> max_audio_len %d)", b, (long long)n, c.max_audio_len);
-    ASR_REQUIRE(paraformer || (lang[b] >= 0 && lang[b] < c.n_languages), "sensevoice: language_idx %d out of range", lang[b]);
     UttPlan& p = plan[b];
-    p.audio_off = offs[b] - base0;
-    p.n_samples = (int)n;
-    p.n_frames = ((int)n - c.win_length) / c.hop_length + 1;
-    p.frame_off = frames;
+    fe.plan_utt("sensevoice", b, offs, c.max_audio_len, p, frames, n_fb);
+    ASR_REQUIRE(paraformer || (lang[b] >= 0 && lang[b] < c.n_languages), "sensevoice: language_idx %d out of range", lang[b]);
     p.n_lfr = (p.n_frames + c.lfr_n - 1) / c.lfr_n;
     p.T = p.n_lfr + c.n_prompt;
     p.row_off = rows;
     p.lang = lang ? lang[b] : 0;
-    p.blk0 = n_fb;
-    frames += p.n_frames;
     rows += round_up(p.T, 16);
-    n_fb += (p.n_frames + 63) / 64;
     max_T = std::max(max_T, p.T);
-    key.mix((uint64_t)n);
+    key.mix((uint64_t)p.n_samples);
   }
   ASR_REQUIRE(max_tokens >= 1, "sensevoice: max_tokens must be positive");
   int att_qt = 0, att_nw = 4, q_rows = 64;             // f32 kernel: fixed 64-row query blocks
   if (precision == ASR_PRECISION_BF16) { attention_geometry(max_T, c.d_head, &att_qt, &att_nw); q_rows = 16 * att_qt * att_nw; }
   for (int b = 0; b < batch; ++b) n_qb += (plan[b].T + q_rows - 1) / q_rows;
   const int Mpad = round_up(rows, 128);
-  const int64_t total_samples = offs[batch] - base0;
 
-  // plan blob: [UttPlan x B][blk_utt n_fb][blk_f0 n_fb][qb_utt n_qb][qb_q0 n_qb][row_utt Mpad]
+  // plan blob: [UttPlan x B][blk_utt n_fb][blk_f0 n_fb][qb_utt n_qb][qb_q0 n_qb][row_utt Mpad][tile_win n_tiles][tile_idx n_tiles]
   const int n_tiles = rows / 16;
-  const size_t plan_bytes = sizeof(UttPlan) * batch + sizeof(int32_t) * (2 * (size_t)n_fb + 2 * (size_t)n_qb + Mpad + 2 * (size_t)n_tiles);
-  if (h_plan.reserve(plan_bytes)) ++ws_epoch;
-  unsigned char* hp = h_plan.as<unsigned char>();
-  memcpy(hp, plan.data(), sizeof(UttPlan) * batch);
-  int32_t* blk_utt = (int32_t*)(hp + sizeof(UttPlan) * batch);
-  int32_t* blk_f0 = blk_utt + n_fb;
-  int32_t* qb_utt = blk_f0 + n_fb;
-  int32_t* qb_q0 = qb_utt + n_qb;
-  int32_t* row_utt = qb_q0 + n_qb;
+  PlanBlob pb(h_plan, d_plan);
+  const auto s_plan = pb.add<UttPlan>(batch);
+  const auto s_blk_utt = pb.add<int32_t>(n_fb), s_blk_f0 = pb.add<int32_t>(n_fb), s_qb_utt = pb.add<int32_t>(n_qb), s_qb_q0 = pb.add<int32_t>(n_qb);
+  const auto s_row_utt = pb.add<int32_t>(Mpad), s_tile_win = pb.add<int32_t>(n_tiles), s_tile_idx = pb.add<int32_t>(n_tiles);
+  pb.commit(stream);
+  if (pb.host_moved) ++ws_epoch;                        // (any re-allocation invalidates the captured graph)
+  if (pb.dev_moved) ++ws_epoch;
+  memcpy(pb.host(s_plan), plan.data(), sizeof(UttPlan) * batch);
+  fill_fbank_blocks(plan.data(), batch, pb.host(s_blk_utt), pb.host(s_blk_f0));
+  fill_query_blocks(plan.data(), batch, q_rows, pb.host(s_qb_utt), pb.host(s_qb_q0));
   {
-    int fi = 0, qi = 0;
+    int32_t *row_utt = pb.host(s_row_utt), *tile_win = pb.host(s_tile_win), *tile_idx = pb.host(s_tile_idx);
+    int ti = 0;
     for (int b = 0; b < batch; ++b) {
-      for (int f0 = 0; f0 < plan[b].n_frames; f0 += 64) { blk_utt[fi] = b; blk_f0[fi++] = f0; }
-      for (int q0 = 0; q0 < plan[b].T; q0 += q_rows) { qb_utt[qi] = b; qb_q0[qi++] = q0; }
       const int r16 = round_up(plan[b].T, 16);
       for (int t = 0; t < r16; ++t) row_utt[plan[b].row_off + t] = b;
+      for (int t = 0; t < r16 / 16; ++t) { tile_win[ti] = b; tile_idx[ti++] = t; }
     }
     for (int t = rows; t < Mpad; ++t) row_utt[t] = -1;
-    int32_t* tile_win = row_utt + Mpad;
-    int32_t* tile_idx = tile_win + n_tiles;
-    int ti = 0;
-    for (int b = 0; b < batch; ++b)
-      for (int t = 0; t < round_up(plan[b].T, 16) / 16; ++t) { tile_win[ti] = b; tile_idx[ti++] = t; }
   }
   // small batches take the tile kernel (bf16, LayerNorm-folded arenas of the standard geometry, every workgroup resident at once)
   const bool tiles = sizeof(T) == 2 && use_tiles && c.n_blocks > 1 && blocks[c.n_blocks - 1].cqkv && blocks[c.n_blocks - 1].c1 &&
@@ -815,9 +794,9 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   // ---- workspace (grow-only; any re-allocation invalidates the captured graph) -----------------
   const size_t eT = sizeof(T);
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { void* before = buf.ptr; buf.reserve(bytes, stream); if (buf.ptr != before) ++ws_epoch; };
-  grow(d_plan, plan_bytes);
-  const size_t eA = audio_elt();                       // the session's sample type: offsets are samples, bytes step in eA
-  if (audio_mem == ASR_MEM_HOST) grow(d_audio, (size_t)total_samples * eA);
+  bool audio_moved = false;
+  r.d_aud = stage_audio(*this, d_audio, audio, audio_mem, base0, offs[batch] - base0, &audio_moved);
+  if (audio_moved) ++ws_epoch;
   grow(d_mel, (size_t)frames * c.n_mels * 4);
   grow(d_x0, (size_t)Mpad * kpad0 * 4);
   grow(d_xa, (size_t)Mpad * d * 4);
@@ -871,23 +850,13 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   const size_t out_bytes = (size_t)batch * max_tokens * 4 + (size_t)batch * 4 + 16 + (timed ? (size_t)batch * max_tokens * 12 : 0);
   if (h_out.reserve(out_bytes)) ++ws_epoch;
 
-  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan.ptr, plan_bytes, hipMemcpyHostToDevice, stream));
-  r.d_aud = static_cast<const unsigned char*>(audio) + (size_t)base0 * eA;
-  if (audio_mem == ASR_MEM_HOST) {
-    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, r.d_aud, (size_t)total_samples * eA, hipMemcpyHostToDevice, stream));
-    r.d_aud = d_audio.ptr;
-  }
+  pb.upload(stream);
   r.batch = batch; r.rows = rows; r.Mpad = Mpad; r.frames = frames; r.n_fb = n_fb; r.n_qb = n_qb; r.max_T = max_T;
   r.max_tokens = max_tokens; r.att_qt = att_qt; r.att_nw = att_nw;
-  r.dp = d_plan.as<UttPlan>();
+  r.dp = pb.dev(s_plan);
   r.n_tiles = n_tiles; r.tiles = tiles; r.timed = timed;
-  r.d_blk_utt = (const int32_t*)((unsigned char*)d_plan.ptr + sizeof(UttPlan) * batch);
-  r.d_blk_f0 = r.d_blk_utt + n_fb;
-  r.d_qb_utt = r.d_blk_f0 + n_fb;
-  r.d_qb_q0 = r.d_qb_utt + n_qb;
-  r.d_row_utt = r.d_qb_q0 + n_qb;
-  r.d_tile_win = r.d_row_utt + Mpad;
-  r.d_tile_idx = r.d_tile_win + n_tiles;
+  r.d_blk_utt = pb.dev(s_blk_utt); r.d_blk_f0 = pb.dev(s_blk_f0); r.d_qb_utt = pb.dev(s_qb_utt); r.d_qb_q0 = pb.dev(s_qb_q0);
+  r.d_row_utt = pb.dev(s_row_utt); r.d_tile_win = pb.dev(s_tile_win); r.d_tile_idx = pb.dev(s_tile_idx);
   key.mix((uint64_t)batch); key.mix((uint64_t)max_tokens); key.mix((uint64_t)(uintptr_t)r.d_aud); key.mix((uint64_t)audio_dtype); key.mix(ws_epoch); key.mix((uint64_t)(uintptr_t)stream);
   key.mix((uint64_t)(block_cooldown > 0 || foreign_now));        // a session cooling down after a cluster give-up replays the four-launch capture, not the block one
   key.mix((uint64_t)timed);                                      // the timed CTC tail is another launch sequence
@@ -1011,15 +980,15 @@ void SvSession::stream_init(int chunk, int look_back_encoder, int look_back_deco
   st_delen.reserve((size_t)max_streams * 4, stream);
   st_start.reserve((size_t)max_streams * 4, stream);
   // bf16 sessions of the standard geometry: layers 1 .. n - 1 of a chunk step run as one launch (layer 0 has the 560-wide input and no residual)
-  if (const char* e = getenv("ASR_STREAM_FUSED")) st_fused_env = atoi(e);
-  if (const char* e = getenv("ASR_STREAM_TIMES")) st_times_layer = atoi(e);
-  if (const char* e = getenv("ASR_STREAM_OPT")) st_opt = atoi(e);
+  st_fused_env = env_int("ASR_STREAM_FUSED", st_fused_env);
+  st_times_layer = env_int("ASR_STREAM_TIMES", st_times_layer);
+  st_opt = env_int("ASR_STREAM_OPT", st_opt);
   st_fused_max = gemm_env_cus() * 3 / 4;               // 192 streams on 256 CUs: tools/probes/stream_fused_sweep.sh (profiles/r05_stream_fused_sweep.txt) -- the cluster launches step by CU-loads of 64 streams
                                                        // (2.5 / 5.2 / 7.8 / 10.4 ms), the per-launch path grows smoothly (5.3 ms at 64, 8.1 at 192, 8.9 at 256) and is ahead from 193 on
-  if (const char* e = getenv("ASR_STREAM_FUSED_MAX")) st_fused_max = atoi(e);
-  if (const char* e = getenv("ASR_STREAM_SHARE")) st_share_rule = atoi(e);
-  if (const char* e = getenv("ASR_STREAM_SNAPSHOT")) st_snapshot_env = atoi(e);
-  if (const char* e = getenv("ASR_STREAM_FAULT")) st_fault = atoi(e);
+  st_fused_max = env_int("ASR_STREAM_FUSED_MAX", st_fused_max);
+  st_share_rule = env_int("ASR_STREAM_SHARE", st_share_rule);
+  st_snapshot_env = env_int("ASR_STREAM_SNAPSHOT", st_snapshot_env);
+  st_fault = env_int("ASR_STREAM_FAULT", st_fault);
   st_fused = st_fused_env != 0 && precision == ASR_PRECISION_BF16 && c.n_blocks > 1 &&
              stream_layers_supported(c.d_model, c.d_ffn, c.n_heads, st_en_cap, st_B + st_C, c.fsmn_kernel) && blocks[1].kpad == c.d_model;
   if (st_fused) {
@@ -1134,12 +1103,13 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
   const int rows = n * 16, Mpad = round_up(rows, 128), frames = n * st_frames, n_slabs = vpad / 64;
   std::vector<char> seen(st_max, 0);
   // ---- plan: one 16-row slot / one fbank workgroup per active stream
-  const size_t plan_bytes = sizeof(UttPlan) * n + sizeof(int32_t) * (2 * (size_t)n + Mpad);
-  h_plan.reserve(plan_bytes);
-  UttPlan* hp = h_plan.as<UttPlan>();
-  int32_t* blk_utt = (int32_t*)(h_plan.as<unsigned char>() + sizeof(UttPlan) * n);
-  int32_t* blk_f0 = blk_utt + n;
-  int32_t* row_utt = blk_f0 + n;
+  // plan blob: [UttPlan n][blk_utt n][blk_f0 n][row_utt Mpad]
+  PlanBlob pb(h_plan, d_plan);
+  const auto s_plan = pb.add<UttPlan>(n);
+  const auto s_blk_utt = pb.add<int32_t>(n), s_blk_f0 = pb.add<int32_t>(n), s_row_utt = pb.add<int32_t>(Mpad);
+  pb.commit(stream);                                     // (this step's graphs are keyed on the buffers themselves)
+  UttPlan* hp = pb.host(s_plan);
+  int32_t *blk_utt = pb.host(s_blk_utt), *blk_f0 = pb.host(s_blk_f0), *row_utt = pb.host(s_row_utt);
   for (int i = 0; i < n; ++i) {
     ASR_REQUIRE(stream_ids[i] >= 0 && stream_ids[i] < st_max && !seen[stream_ids[i]], "streaming: stream id %d invalid or repeated", stream_ids[i]);
     seen[stream_ids[i]] = 1;
@@ -1152,9 +1122,7 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
   for (int t = rows; t < Mpad; ++t) row_utt[t] = -1;
   const size_t eT = sizeof(T);
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { buf.reserve(bytes, stream); };
-  grow(d_plan, plan_bytes);
-  const size_t eA = audio_elt();
-  if (audio_mem == ASR_MEM_HOST) grow(d_audio, (size_t)n * st_chunk * eA);
+  const void* d_aud = stage_audio(*this, d_audio, audio, audio_mem, 0, (int64_t)n * st_chunk);
   grow(d_mel, (size_t)frames * c.n_mels * 4);
   grow(d_x0, (size_t)Mpad * kpad0 * 4);
   grow(d_xa, (size_t)Mpad * d * 4);
@@ -1186,12 +1154,7 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
   }
   const size_t out_bytes = (size_t)n * max_tokens * 4 + (size_t)n * 4;
   h_out.reserve(out_bytes + 16);
-  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan.ptr, plan_bytes, hipMemcpyHostToDevice, stream));
-  const void* d_aud = audio;
-  if (audio_mem == ASR_MEM_HOST) {
-    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, audio, (size_t)n * st_chunk * eA, hipMemcpyHostToDevice, stream));
-    d_aud = d_audio.ptr;
-  }
+  pb.upload(stream);
   // ---- which path this step takes (see the comment at st_fused_max)
   bool step_fused = st_fused && std::is_same<T, bf16_t>::value && n <= st_fused_max && st_cooldown == 0 && !foreign_now;
   bool snapshot = false;
@@ -1201,10 +1164,8 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
   if (snapshot) { ensure_stream_shadow(); ++st_snapshots; }
   const bool inject_fault = step_fused && st_fault == 1;
   if (inject_fault) st_fault = 2;                        // once per session
-  const UttPlan* dp = d_plan.as<UttPlan>();
-  const int32_t* d_blk_utt = (const int32_t*)((unsigned char*)d_plan.ptr + sizeof(UttPlan) * n);
-  const int32_t* d_blk_f0 = d_blk_utt + n;
-  const int32_t* d_row_utt = d_blk_f0 + n;
+  const UttPlan* dp = pb.dev(s_plan);
+  const int32_t *d_blk_utt = pb.dev(s_blk_utt), *d_blk_f0 = pb.dev(s_blk_f0), *d_row_utt = pb.dev(s_row_utt);
 
   // Everything below reads its geometry from the uploaded plan and the device-side state (history lengths, fired-token counts), so
   // the launch sequence depends on n only: one captured hipGraph replays every chunk step of a given set size.
@@ -1214,12 +1175,7 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
   // ---- front-end: fbank of the chunk, LFR rows, carried rows in front (:386-399)
   {
     ProfScope ps(prof, "fbank", stream);
-    FbankArgs fa;
-    fa.audio = d_aud; fa.audio_dtype = audio_dtype; fa.plan = dp; fa.blk_utt = d_blk_utt; fa.blk_f0 = d_blk_f0;
-    fa.dft_packed = dft; fa.mel_packed = melp; fa.mel_out = d_mel.as<float>();
-    fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = c.n_mels / 16; fa.n_mels = c.n_mels;
-    fa.win = c.win_length; fa.hop = c.hop_length; fa.log_floor = 1.1920928955078125e-07f; fa.whisper = 0; fa.blk_max = nullptr;
-    fa.dft_split = d_dft_split.ptr;
+    const FbankArgs fa = fe.args(d_aud, audio_dtype, dp, d_blk_utt, d_blk_f0, d_mel.as<float>(), nullptr);
     launch_fbank(fa, n, stream);
   }
   if (taps_enabled) save_tap("mel", d_mel.ptr, frames, c.n_mels, c.n_mels, 4);

@@ -48,15 +48,15 @@ struct BeamStep {
 
 struct EncLayer { const void *wqkv, *wo, *w1, *w2; const float *bqkv, *bo, *b1, *b2; };
 struct DecLayer { const void *wqkv, *wo, *wcq, *wco, *w1, *w2; const float *bqkv, *bo, *bcq, *bco, *b1, *b2; };
-struct Dec8Layer { const unsigned char* w[6]; const float* s[6]; const unsigned char* s4[6]; };      // FP8W: bytes + per-column scales; MXFP4W: nibbles (w) + e8m0 block scales (s4)
-struct Enc8Layer { const unsigned char *w1, *w2; const float *s1, *s2; };     // FP8MM mode: the encoder FFN pair as e4m3 bytes + per-row scales        // FP8 mode: e4m3 bytes + per-column scales of wqkv, wo, wcq, wco, w1, w2
+struct Enc8Layer { const unsigned char *w1, *w2; const float *s1, *s2; };     // FP8MM mode: the encoder FFN pair as e4m3 bytes + per-row scales
 
 struct WhSession : asr_session {
   asr_whisper_config cfg;
-  int vpad = 0, n_bin_tiles = 0, n_kchunks = 0, act = ACT_GELU_ERF;
+  int vpad = 0, act = ACT_GELU_ERF;
+  FrontEnd fe;
   std::vector<EncLayer> enc;
   std::vector<DecLayer> dec;
-  const float *dft = nullptr, *melp = nullptr, *conv1_b = nullptr, *conv2_b = nullptr, *enc_pos = nullptr, *enc_ln_g = nullptr,
+  const float *conv1_b = nullptr, *conv2_b = nullptr, *enc_pos = nullptr, *enc_ln_g = nullptr,
               *enc_ln_b = nullptr, *ckv_b = nullptr, *dec_pos = nullptr, *suppress = nullptr, *begin = nullptr, *dec_ln_g = nullptr,
               *dec_ln_b = nullptr;
   const void *conv1_w = nullptr, *conv2_w = nullptr, *ckv_w = nullptr, *embed = nullptr;
@@ -98,8 +98,8 @@ struct WhSession : asr_session {
   DeviceBuffer d_ew8, d_ewscale, d_h8, d_ffn8, d_sat;
   bool fp4 = false;                    // precision mode ASR_PRECISION_MXFP4W (opt-in): FP8W with the decoder projections as MXFP4 (e2m1 + e8m0 per 32 k) instead of e4m3
   bool fp8 = false, fp8_fake = false, fp8_weights = true, fp8_kv = true;     // ASR_FP8_WEIGHTS=0 / ASR_FP8_KV=0: leave that half in bf16 (to price the halves separately)
-  std::vector<Dec8Layer> dec8;
-  DeviceBuffer d_w8, d_wscale, d_wdq, d_cross8, d_cscale;
+  LowBitWeights dec8;                  // wqkv, wo, wcq, wco, w1, w2 of every decoder layer
+  DeviceBuffer d_cross8, d_cscale;
   StepGraph dec_graph;                 // the whole single-token step
   StepGraph beam_graph[2];             // the beam-search step, one per ancestry-table parity
   // Beam search (asr_whisper_beam_search): hypothesis rows b * beam + r, each with its own self-K/V extent of S = prompt + max_new - 1 slots in d_bext
@@ -128,16 +128,8 @@ struct WhSession : asr_session {
   PinnedBuffer h_plan, h_io;
 
   void init();
-  DeviceBuffer d_skws, d_skcnt;        // split-K workspace + tickets of the skinny / decode GEMM (per session: sessions may run concurrently)
-  static constexpr int SK_CNT = 4096;
-  static constexpr size_t SK_WS_BYTES = (size_t)16 << 20;
-  void gemm(const GemmArgs& g0) {
-    if (precision != ASR_PRECISION_BF16) { launch_gemm_f32(g0, stream); return; }
-    if (!d_skws.ptr) { d_skws.reserve(SK_WS_BYTES, stream); d_skcnt.reserve((size_t)SK_CNT * 4, stream); }
-    GemmArgs g = g0;
-    g.sk_ws = d_skws.as<float>(); g.sk_ws_bytes = SK_WS_BYTES; g.sk_cnt = d_skcnt.as<int32_t>();
-    launch_gemm_bf16(g, stream);
-  }
+  SplitKGemm sk;
+  void gemm(const GemmArgs& g) { sk.run(g, precision, stream); }
   template <typename T> void encode(const void* audio, int audio_mem, const int64_t* offs, int B, int32_t* n_pos_out);
   template <typename T> void enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev, const BeamStep* bs = nullptr);
   template <typename T> void step(const int32_t* ids_host, int n, bool is_prefill, int32_t* next_out, float* logits_out);
@@ -154,15 +146,14 @@ void WhSession::init() {
   vpad = round_up(c.vocab, 128);
   head.init(c.max_target_positions, 0, 20, 512);
   head.prof = &prof; ranker.prof = &prof;
-  n_bin_tiles = (c.nfft / 2 + 1 + 15) / 16;
-  n_kchunks = c.nfft / 16;
+  fe.init(c.nfft, c.nfft, c.hop_length, c.n_mels, 1, 1e-10f);
   act = c.gelu_tanh ? ACT_GELU_TANH : ACT_GELU_ERF;
   const int wt = precision == ASR_PRECISION_BF16 ? ARENA_BF16 : ARENA_F32;
   const int d = c.d_model, dff = c.d_ffn, Ld = c.n_dec_layers;
   auto F = [&](const std::string& n, std::initializer_list<int64_t> sh) { return (const float*)arena.get(n, ARENA_F32, sh).ptr; };
   auto W = [&](const std::string& n, std::initializer_list<int64_t> sh) { return arena.get(n, wt, sh).ptr; };
-  dft = F("fe.dft", {(int64_t)n_bin_tiles * 2 * n_kchunks * 64 * 4});
-  melp = F("fe.mel", {(int64_t)(c.n_mels / 16) * n_bin_tiles * 64 * 4});
+  fe.dft = F("fe.dft", {(int64_t)fe.n_bin_tiles * 2 * fe.n_kchunks * 64 * 4});
+  fe.melp = F("fe.mel", {(int64_t)(c.n_mels / 16) * fe.n_bin_tiles * 64 * 4});
   conv1_w = W("enc.conv1_w", {d, 3 * c.n_mels});
   conv1_b = F("enc.conv1_b", {d});
   conv2_w = W("enc.conv2_w", {d, 3 * d});
@@ -207,27 +198,10 @@ void WhSession::init() {
   }
   if (fp8 && fp8_weights) {
     ASR_REQUIRE(d % 256 == 0 && dff % 256 == 0, "whisper: FP8 / MXFP4 mode needs d_model and d_ffn to be multiples of 256");
-    const size_t w_elems = (size_t)6 * d * d + (size_t)2 * d * dff, n_scales = (size_t)7 * d + dff;      // per layer
-    // MXFP4W: d_w8 holds the nibbles (half a byte per element), d_wscale the e8m0 block scales (one byte per 32 elements)
-    d_w8.reserve(fp4 ? Ld * w_elems / 2 : Ld * w_elems, stream); d_wscale.reserve(fp4 ? Ld * w_elems / 32 : Ld * n_scales * 4, stream); d_wdq.reserve(Ld * w_elems * 2, stream);
-    dec8.resize(Ld);
-    for (int i = 0; i < Ld; ++i) {
+    dec8.build(Ld, fp4, [&](int i) {
       DecLayer& L = dec[i];
-      const void** slot[6] = {&L.wqkv, &L.wo, &L.wcq, &L.wco, &L.w1, &L.w2};
-      const int Ns[6] = {3 * d, d, d, d, dff, d}, Ks[6] = {d, d, d, d, d, dff};
-      unsigned char* w8 = d_w8.as<unsigned char>() + (fp4 ? i * w_elems / 2 : i * w_elems);
-      bf16_t* dq = d_wdq.as<bf16_t>() + i * w_elems;
-      float* sc = d_wscale.as<float>() + i * n_scales;
-      unsigned char* sc4 = d_wscale.as<unsigned char>() + i * w_elems / 32;
-      for (int j = 0; j < 6; ++j) {
-        const size_t ne = (size_t)Ns[j] * Ks[j];
-        if (fp4) launch_quantize_rows_mxfp4((const bf16_t*)*slot[j], Ks[j], Ns[j], Ks[j], w8, sc4, dq, stream);
-        else launch_quantize_rows_fp8((const bf16_t*)*slot[j], Ks[j], Ns[j], Ks[j], w8, sc, dq, stream);
-        dec8[i].w[j] = w8; dec8[i].s[j] = sc; dec8[i].s4[j] = sc4;
-        *slot[j] = dq;                                     // from here on "the weights" are the dequantised copies
-        w8 += fp4 ? ne / 2 : ne; dq += ne; sc += Ns[j]; sc4 += ne / 32;
-      }
-    }
+      return std::vector<LowBitWeights::Slot>{{&L.wqkv, 3 * d, d}, {&L.wo, d, d}, {&L.wcq, d, d}, {&L.wco, d, d}, {&L.w1, dff, d}, {&L.w2, d, dff}};
+    }, stream);
   }
   if (precision == ASR_PRECISION_BF16 && use_decode_gemm) {      // column sums of the three LayerNorm-folded projections of every decoder layer: [3d | d | dff]
     const size_t per = (size_t)3 * d + d + dff;
@@ -254,26 +228,16 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, in
   int r = 0, rg = 0, frames = 0, n_fb = 0, n_qb = 0, max_T = 0;
   const int64_t base0 = offs[0];
   for (int b = 0; b < B; ++b) {
-    const int64_t n = offs[b + 1] - offs[b];
-    ASR_REQUIRE(n >= c.nfft, "whisper: utterance %d has %lld samples (< n_fft %d)", b, (long long)n, c.nfft);
-    ASR_REQUIRE(n <= c.max_audio_len, "whisper: utterance %d has %lld samples (> max_audio_len %d)", b, (long long)n, c.max_audio_len);
     UttPlan& p = plan[b];
-    p.audio_off = offs[b] - base0;
-    p.n_samples = (int)n;
-    p.n_frames = (int)n / c.hop_length;                 // centred STFT with the last frame dropped (:96-103)
-    p.frame_off = frames;
+    fe.plan_utt("whisper", b, offs, c.max_audio_len, p, frames, n_fb);      // n_frames = samples / hop (:96-103)
     p.T = (p.n_frames + 1) / 2;                          // conv2 stride 2, pad 1
     p.n_lfr = p.T;
     ASR_REQUIRE(p.T <= c.max_source_positions, "whisper: %d encoder positions exceed max_source_positions", p.T);
     p.row_off = r;
-    p.lang = 0;
-    p.blk0 = n_fb;
-    frames += p.n_frames;
     splan[b] = p;
     splan[b].row_off = rg;
     r += round_up(p.T, 16);                              // encoder stream: compact, 16-row aligned (8 s: 400 rows per utterance)
     rg += round_up(p.T + 1, 16);                         // conv stem: +1 = room for the right zero-pad frame
-    n_fb += (p.n_frames + 63) / 64;
     max_T = std::max(max_T, p.T);
     if (n_pos_out) n_pos_out[b] = p.T;
   }
@@ -283,58 +247,38 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, in
   if (precision == ASR_PRECISION_BF16) { attention_geometry(max_T, c.d_head, &att_qt, &att_nw); q_rows = 16 * att_qt * att_nw; }
   for (int b = 0; b < B; ++b) n_qb += (plan[b].T + q_rows - 1) / q_rows;
   const int R = 2 * Mg;                                  // gapped (frame-rate) rows
-  const int64_t total_samples = offs[B] - base0;
 
   // plan blob: [UttPlan B (encoder rows)][UttPlan B (stem rows)][blk_utt][blk_f0][qb_utt][qb_q0][row_utt Mpad][pos_rows Mg][grow_utt R]
-  const size_t plan_bytes = 2 * sizeof(UttPlan) * B + 4 * (2 * (size_t)n_fb + 2 * (size_t)n_qb + (size_t)Mpad + (size_t)Mg + R);
-  h_plan.reserve(plan_bytes);
-  unsigned char* hp = h_plan.as<unsigned char>();
-  memcpy(hp, plan.data(), sizeof(UttPlan) * B);
-  memcpy(hp + sizeof(UttPlan) * B, splan.data(), sizeof(UttPlan) * B);
-  int32_t* blk_utt = (int32_t*)(hp + 2 * sizeof(UttPlan) * B);
-  int32_t* blk_f0 = blk_utt + n_fb;
-  int32_t* qb_utt = blk_f0 + n_fb;
-  int32_t* qb_q0 = qb_utt + n_qb;
-  int32_t* row_utt = qb_q0 + n_qb;
-  int32_t* pos_rows = row_utt + Mpad;
-  int32_t* grow_utt = pos_rows + Mg;
+  PlanBlob pb(h_plan, d_plan);
+  const auto s_plan = pb.add<UttPlan>(B), s_stem = pb.add<UttPlan>(B);
+  const auto s_blk_utt = pb.add<int32_t>(n_fb), s_blk_f0 = pb.add<int32_t>(n_fb), s_qb_utt = pb.add<int32_t>(n_qb), s_qb_q0 = pb.add<int32_t>(n_qb);
+  const auto s_row_utt = pb.add<int32_t>(Mpad), s_pos_rows = pb.add<int32_t>(Mg), s_grow_utt = pb.add<int32_t>(R);
+  pb.commit(stream);
+  if (pb.dev_moved) ++ws_epoch;
+  memcpy(pb.host(s_plan), plan.data(), sizeof(UttPlan) * B);
+  memcpy(pb.host(s_stem), splan.data(), sizeof(UttPlan) * B);
+  fill_fbank_blocks(plan.data(), B, pb.host(s_blk_utt), pb.host(s_blk_f0));
+  fill_query_blocks(plan.data(), B, q_rows, pb.host(s_qb_utt), pb.host(s_qb_q0));
+  int32_t *row_utt = pb.host(s_row_utt), *pos_rows = pb.host(s_pos_rows), *grow_utt = pb.host(s_grow_utt);
   for (int i = 0; i < Mpad; ++i) row_utt[i] = -1;
   for (int i = 0; i < Mg; ++i) pos_rows[i] = 0;
   for (int i = 0; i < R; ++i) grow_utt[i] = -1;
-  {
-    int fi = 0, qi = 0;
-    for (int b = 0; b < B; ++b) {
-      for (int f0 = 0; f0 < plan[b].n_frames; f0 += 64) { blk_utt[fi] = b; blk_f0[fi++] = f0; }
-      for (int q0 = 0; q0 < plan[b].T; q0 += q_rows) { qb_utt[qi] = b; qb_q0[qi++] = q0; }
-      const int rb = round_up(plan[b].T + 1, 16), rc = round_up(plan[b].T, 16);
-      for (int t = 0; t < rc; ++t) row_utt[plan[b].row_off + t] = b;
-      for (int t = 0; t < rb; ++t) {
-        pos_rows[splan[b].row_off + t] = t < plan[b].T ? t : 0;
-        grow_utt[2 * (splan[b].row_off + t)] = b;
-        grow_utt[2 * (splan[b].row_off + t) + 1] = b;
-      }
+  for (int b = 0; b < B; ++b) {
+    const int rb = round_up(plan[b].T + 1, 16), rc = round_up(plan[b].T, 16);
+    for (int t = 0; t < rc; ++t) row_utt[plan[b].row_off + t] = b;
+    for (int t = 0; t < rb; ++t) {
+      pos_rows[splan[b].row_off + t] = t < plan[b].T ? t : 0;
+      grow_utt[2 * (splan[b].row_off + t)] = b;
+      grow_utt[2 * (splan[b].row_off + t) + 1] = b;
     }
   }
-  { void* before = d_plan.ptr; d_plan.reserve(plan_bytes, stream); if (d_plan.ptr != before) ++ws_epoch; }
-  HIP_CHECK(hipMemcpyAsync(d_plan.ptr, h_plan.ptr, plan_bytes, hipMemcpyHostToDevice, stream));
-  const UttPlan* dp = d_plan.as<UttPlan>();
-  const UttPlan* dps = dp + B;                            // stem rows
-  const int32_t* d_blk_utt = (const int32_t*)((unsigned char*)d_plan.ptr + 2 * sizeof(UttPlan) * B);
-  const int32_t* d_blk_f0 = d_blk_utt + n_fb;
-  const int32_t* d_qb_utt = d_blk_f0 + n_fb;
-  const int32_t* d_qb_q0 = d_qb_utt + n_qb;
-  const int32_t* d_row_utt = d_qb_q0 + n_qb;
-  const int32_t* d_pos_rows = d_row_utt + Mpad;
-  const int32_t* d_grow_utt = d_pos_rows + Mg;
+  pb.upload(stream);
+  const UttPlan *dp = pb.dev(s_plan), *dps = pb.dev(s_stem);
+  const int32_t *d_blk_utt = pb.dev(s_blk_utt), *d_blk_f0 = pb.dev(s_blk_f0), *d_qb_utt = pb.dev(s_qb_utt), *d_qb_q0 = pb.dev(s_qb_q0);
+  const int32_t *d_row_utt = pb.dev(s_row_utt), *d_pos_rows = pb.dev(s_pos_rows), *d_grow_utt = pb.dev(s_grow_utt);
 
   const size_t eT = sizeof(T);
-  const size_t eA = audio_elt();                                    // the session's sample type: offsets are samples, bytes step in eA
-  const void* d_aud = static_cast<const unsigned char*>(audio) + (size_t)base0 * eA;
-  if (audio_mem == ASR_MEM_HOST) {
-    d_audio.reserve((size_t)total_samples * eA, stream);
-    HIP_CHECK(hipMemcpyAsync(d_audio.ptr, d_aud, (size_t)total_samples * eA, hipMemcpyHostToDevice, stream));
-    d_aud = d_audio.ptr;
-  }
+  const void* d_aud = stage_audio(*this, d_audio, audio, audio_mem, base0, offs[B] - base0);
   const int Rpad = R + 256;                                        // tile-edge + halo rows of the strided conv views
   d_mel.reserve((size_t)frames * c.n_mels * 4, stream);
   d_blkmax.reserve((size_t)n_fb * 4, stream);
@@ -353,11 +297,7 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, in
   // ---- STFT power -> mel -> log10 (STFT_Process.py:224-246, Export_Whisper.py:424-425)
   {
     ProfScope ps(prof, "logmel", stream);
-    FbankArgs fa;
-    fa.audio = d_aud; fa.audio_dtype = audio_dtype; fa.plan = dp; fa.blk_utt = d_blk_utt; fa.blk_f0 = d_blk_f0; fa.dft_packed = dft; fa.mel_packed = melp;
-    fa.mel_out = d_mel.as<float>(); fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = c.n_mels / 16;
-    fa.n_mels = c.n_mels; fa.win = c.nfft; fa.hop = c.hop_length; fa.log_floor = 1e-10f; fa.whisper = 1;
-    fa.blk_max = d_blkmax.as<float>();
+    const FbankArgs fa = fe.args(d_aud, audio_dtype, dp, d_blk_utt, d_blk_f0, d_mel.as<float>(), d_blkmax.as<float>());
     launch_fbank(fa, n_fb, stream);
     // per-utterance max clamp + (x+4)/4, written behind one leading zero row (the conv view of row j starts at j-1)
     T* x0 = d_x0.as<T>();
@@ -473,7 +413,7 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, in
       { void* before = d_cross8.ptr; void* before_s = d_cscale.ptr;      // either buffer moving invalidates the captured decode graph (the scales grow with B, the bytes with the rows)
         d_cross8.reserve((size_t)2 * Ld * H * Mpad * 64, stream); d_cscale.reserve((size_t)2 * Ld * H * B * 4, stream);
         if (d_cross8.ptr != before || d_cscale.ptr != before_s) ++ws_epoch; }
-      launch_quantize_crosskv_fp8(d_cross.as<bf16_t>(), (size_t)Mpad * 64, 2 * Ld * H, d_plan.as<UttPlan>(), B, d_cross8.as<unsigned char>(), d_cscale.as<float>(),
+      launch_quantize_crosskv_fp8(d_cross.as<bf16_t>(), (size_t)Mpad * 64, 2 * Ld * H, dp, B, d_cross8.as<unsigned char>(), d_cscale.as<float>(),
                                   fp8_fake ? 1 : 0, stream);
     }
   }
@@ -503,7 +443,7 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
   T* ffn = ctx + (size_t)Rp * d;
   T* cq = ffn + (size_t)Rp * dff;
   T* hl = cq + (size_t)Rp * d;
-  const UttPlan* dp = d_plan.as<UttPlan>();
+  const UttPlan* dp = d_plan.as<UttPlan>();              // (the first section of the blob encode() uploaded: the encoder-row plans)
   const size_t cache_l = (size_t)B * H * c.max_target_positions * 64;
   // bf16 mode, M <= 64 rows: the (affine-less) LayerNorm runs inside the skinny GEMM's prologue
   const bool fuse_ln = precision == ASR_PRECISION_BF16 && R <= 32 && d % 256 == 0;   // above 32 rows a separate LayerNorm launch is cheaper
@@ -527,19 +467,18 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
   const bool w8 = fp8 && fp8_weights && !fp8_fake;
   // (Round 5 also cut the batch into sub-batches whose layer loops ran on one stream each ("decode chains"): 3.29 vs 3.31 ms per token at 64 sequences,
   //  slower at 32 -- profiles/r05_whisper_decode_chains.txt; removed in round 6.)
-  if (!d_skws.ptr) { d_skws.reserve(SK_WS_BYTES, stream); d_skcnt.reserve((size_t)SK_CNT * 4, stream); }
+  sk.ensure(stream);
   const int plan_rows = 0, NC = 1;
   auto dg = [&](hipStream_t st, int ci, int r0, int Rc, int layer, const void* A, int lda, const void* Wt, int wi, int N, int K, const float* bias, const float* colsum,
                 const float* add, int act_, float* of32, void* olo, int ld_lo) {
     ProfScope ps(prof, "dec_gemm", st);
     DecGemmArgs g;
     g.A = (const bf16_t*)A + (size_t)r0 * lda; g.lda = lda; g.W = (const bf16_t*)Wt; g.ldw = K; g.M = Rc; g.plan_M = plan_rows; g.N = N; g.K = K; g.bias = bias; g.colsum = colsum;
-    if (w8 && fp4) { g.W = nullptr; g.W4 = dec8[layer].w[wi]; g.w_scale4 = dec8[layer].s4[wi]; }
-    else if (w8) { g.W = nullptr; g.W8 = dec8[layer].w[wi]; g.w_scale = dec8[layer].s[wi]; }
+    if (w8) { g.W = nullptr; dec8.select(g, layer, wi); }
     g.add = add ? add + (size_t)r0 * d : nullptr; g.ld_add = d; g.act = act_; g.out_f32 = of32 ? of32 + (size_t)r0 * d : nullptr; g.ld_out_f32 = d;
     g.out_lo = olo ? (bf16_t*)olo + (size_t)r0 * ld_lo : nullptr; g.ld_out_lo = ld_lo;
-    g.ws = reinterpret_cast<float*>(static_cast<unsigned char*>(d_skws.ptr) + (size_t)ci * SK_WS_BYTES); g.ws_bytes = SK_WS_BYTES;
-    g.cnt = d_skcnt.as<int32_t>() + (size_t)ci * SK_CNT;
+    g.ws = reinterpret_cast<float*>(static_cast<unsigned char*>(sk.ws.ptr) + (size_t)ci * SplitKGemm::WS_BYTES); g.ws_bytes = SplitKGemm::WS_BYTES;
+    g.cnt = sk.cnt.as<int32_t>() + (size_t)ci * SplitKGemm::TICKETS;
     launch_decode_gemm(g, st);
   };
   // embedding + layer loop of sequences [b0, b0 + nb) on stream `st` (chain ci)
@@ -951,14 +890,14 @@ extern "C" int asr_whisper_create(const asr_whisper_config* cfg, const void* are
       s->precision = s->fp8 ? ASR_PRECISION_BF16 : precision;        // FP8 mode = bf16 mode with byte-wide decoder weights and cross-K/V
       s->cfg = *cfg;
       gemm_reload_env();
-      if (const char* e = getenv("ASR_FP8_FAKE")) s->fp8_fake = e[0] == '1';
-      if (const char* e = getenv("ASR_FP8MM_ACT_SHIFT")) s->fp8_act_shift = std::min(std::max(atoi(e), 0), 16);
-      if (const char* e = getenv("ASR_FP8_WEIGHTS")) s->fp8_weights = !(e[0] == '0');
-      if (const char* e = getenv("ASR_FP8_KV")) s->fp8_kv = !(e[0] == '0');
-      if (const char* e = getenv("ASR_NO_GRAPH")) s->use_graph = !(e[0] == '1');
-      if (const char* e = getenv("ASR_KV_PAGED")) s->kv_paged = !(e[0] == '0');
-      if (const char* e = getenv("ASR_KV_PAGE_SHUFFLE")) s->kv_shuffle = e[0] == '1';
-      if (const char* e = getenv("ASR_DECODE_GEMM")) s->use_decode_gemm = !(e[0] == '0');
+      s->fp8_fake = env_on("ASR_FP8_FAKE", s->fp8_fake);
+      s->fp8_act_shift = std::min(std::max(env_int("ASR_FP8MM_ACT_SHIFT", s->fp8_act_shift), 0), 16);
+      s->fp8_weights = env_flag("ASR_FP8_WEIGHTS", s->fp8_weights);
+      s->fp8_kv = env_flag("ASR_FP8_KV", s->fp8_kv);
+      s->use_graph = !env_on("ASR_NO_GRAPH", !s->use_graph);
+      s->kv_paged = env_flag("ASR_KV_PAGED", s->kv_paged);
+      s->kv_shuffle = env_on("ASR_KV_PAGE_SHUFFLE", s->kv_shuffle);
+      s->use_decode_gemm = env_flag("ASR_DECODE_GEMM", s->use_decode_gemm);
       HIP_CHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
       s->own_stream = true;
       s->arena.load(arena, arena_bytes, arena_mem, s->stream);

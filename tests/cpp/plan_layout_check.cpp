@@ -1,0 +1,106 @@
+// Stand-alone check of csrc/plan_layout.h (built and run by tests/test_plan_blob_cpu.py under AddressSanitizer + UBSan).
+// For the section lists of the four call sites that build a plan blob -- WhSession::encode, QwSession::prefill (+ its step plan), SvSession::run and
+// SvSession::stream_step -- it checks every section's alignment, bounds and order, the total, and that the offsets are those of the hand-written layout
+// these sites used before PlanLayout: the expected numbers below are written out from those formulas, none comes from PlanLayout.
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+#include "plan_layout.h"
+
+struct Utt { int64_t audio_off; int32_t v[8]; };      // the shape of UttPlan (kernels.h): one int64 + eight int32
+static_assert(sizeof(Utt) == 40 && alignof(Utt) == 8, "UttPlan is 40 bytes, 8-aligned");
+constexpr size_t U = 40;
+
+struct Sec { size_t elt, align, count; };
+static const Sec utt(size_t n) { return Sec{U, 8, n}; }
+static const Sec i32(size_t n) { return Sec{4, 4, n}; }
+
+static int failures = 0;
+#define CHECK(cond, ...) do { if (!(cond)) { ++failures; printf("FAIL %s: ", name); printf(__VA_ARGS__); printf("\n"); } } while (0)
+
+static void check(const char* name, const std::vector<Sec>& secs, size_t round_to, const std::vector<size_t>& want_off, size_t want_total) {
+  PlanLayout lay;
+  std::vector<int> id;
+  for (const Sec& s : secs) id.push_back(lay.add(s.elt, s.align, s.count));
+  lay.round_total(round_to);
+  size_t end = 0, payload = 0, padding = 0;
+  for (size_t k = 0; k < secs.size(); ++k) {
+    const size_t off = lay.off[id[k]], bytes = lay.bytes[id[k]];
+    CHECK(id[k] == (int)k, "section %zu got index %d", k, id[k]);
+    CHECK(off % secs[k].align == 0, "section %zu at %zu is not %zu-aligned", k, off, secs[k].align);
+    CHECK(bytes == secs[k].elt * secs[k].count, "section %zu holds %zu bytes", k, bytes);
+    CHECK(off >= end, "section %zu at %zu overlaps its predecessor (ends at %zu)", k, off, end);
+    CHECK(off - end < secs[k].align, "section %zu: %zu bytes of padding for alignment %zu", k, off - end, secs[k].align);
+    CHECK(off + bytes <= lay.total, "section %zu ends at %zu, past the total %zu", k, off + bytes, lay.total);
+    CHECK(off == want_off[k], "section %zu at %zu, hand layout %zu", k, off, want_off[k]);
+    padding += off - end; payload += bytes; end = off + bytes;
+  }
+  padding += lay.total - end;
+  CHECK(lay.total - end < round_to, "total %zu is more than one rounding step past the last section (%zu)", lay.total, end);
+  CHECK(lay.total % round_to == 0, "total %zu is no multiple of %zu", lay.total, round_to);
+  CHECK(lay.total == payload + padding, "total %zu != %zu + %zu", lay.total, payload, padding);
+  CHECK(lay.total == want_total, "total %zu, hand layout %zu", lay.total, want_total);
+}
+
+static size_t up(size_t v, size_t m) { return (v + m - 1) / m * m; }
+
+// ---- the four sites: section lists in declaration order, expected offsets from the hand layouts
+static void whisper(const char* name, size_t B, size_t n_fb, size_t n_qb, size_t Mpad, size_t Mg) {
+  const size_t R = 2 * Mg, t0 = 2 * U * B;      // [UttPlan B][UttPlan B][blk_utt][blk_f0][qb_utt][qb_q0][row_utt Mpad][pos_rows Mg][grow_utt R]
+  check(name, {utt(B), utt(B), i32(n_fb), i32(n_fb), i32(n_qb), i32(n_qb), i32(Mpad), i32(Mg), i32(R)}, 1,
+        {0, U * B, t0, t0 + 4 * n_fb, t0 + 4 * (2 * n_fb), t0 + 4 * (2 * n_fb + n_qb), t0 + 4 * (2 * n_fb + 2 * n_qb), t0 + 4 * (2 * n_fb + 2 * n_qb + Mpad),
+         t0 + 4 * (2 * n_fb + 2 * n_qb + Mpad + Mg)},
+        2 * U * B + 4 * (2 * n_fb + 2 * n_qb + Mpad + Mg + R));
+}
+static void qwen(const char* name, size_t B, size_t wins, size_t n_fb, size_t n_qb, size_t slots, size_t Me, size_t Md, size_t n_dqb) {
+  // [UttPlan B][win plans][dec plans B][blk_utt][blk_f0][qb_utt][qb_q0][slot_utt][slot_local][pos_rows Me][src Md][row_seq Md][row_t Md][last B][dqb_utt][dqb_q0]
+  const size_t t0 = U * (2 * B + wins);
+  std::vector<size_t> off = {0, U * B, U * (B + wins)};
+  size_t words = 0;
+  for (size_t n : {n_fb, n_fb, n_qb, n_qb, slots, slots, Me, Md, Md, Md, B, n_dqb, n_dqb}) { off.push_back(t0 + 4 * words); words += n; }
+  check(name, {utt(B), utt(wins), utt(B), i32(n_fb), i32(n_fb), i32(n_qb), i32(n_qb), i32(slots), i32(slots), i32(Me), i32(Md), i32(Md), i32(Md), i32(B),
+               i32(n_dqb), i32(n_dqb)}, 16, off,
+        (U * (2 * B + wins) + 4 * (2 * n_fb + 2 * n_qb + 2 * slots + Me + 3 * Md + B + 2 * n_dqb) + 15) / 16 * 16);
+}
+static void qwen_step(const char* name, size_t rows) {      // [UttPlan rows][row_seq Mb][row_t Mb][last Mb], Mb = rows rounded up to 128
+  const size_t Mb = up(rows, 128);
+  check(name, {utt(rows), i32(Mb), i32(Mb), i32(Mb)}, 1, {0, U * rows, U * rows + 4 * Mb, U * rows + 8 * Mb}, U * rows + 4 * 3 * Mb);
+}
+static void sensevoice(const char* name, size_t B, size_t n_fb, size_t n_qb, size_t rows) {
+  const size_t Mpad = up(rows, 128), n_tiles = rows / 16, t0 = U * B;      // [UttPlan B][blk_utt][blk_f0][qb_utt][qb_q0][row_utt Mpad][tile_win][tile_idx]
+  check(name, {utt(B), i32(n_fb), i32(n_fb), i32(n_qb), i32(n_qb), i32(Mpad), i32(n_tiles), i32(n_tiles)}, 1,
+        {0, t0, t0 + 4 * n_fb, t0 + 8 * n_fb, t0 + 4 * (2 * n_fb + n_qb), t0 + 4 * (2 * n_fb + 2 * n_qb), t0 + 4 * (2 * n_fb + 2 * n_qb + Mpad),
+         t0 + 4 * (2 * n_fb + 2 * n_qb + Mpad + n_tiles)},
+        U * B + 4 * (2 * n_fb + 2 * n_qb + Mpad + 2 * n_tiles));
+}
+static void stream_step(const char* name, size_t n) {       // [UttPlan n][blk_utt n][blk_f0 n][row_utt Mpad], 16 rows per stream
+  const size_t Mpad = up(16 * n, 128);
+  check(name, {utt(n), i32(n), i32(n), i32(Mpad)}, 1, {0, U * n, U * n + 4 * n, U * n + 8 * n}, U * n + 4 * (2 * n + Mpad));
+}
+
+int main() {
+  // Whisper (hop 160; T = (frames + 1) / 2; encoder rows round16(T), stem rows round16(T + 1); f32 query blocks of 64 rows)
+  whisper("whisper B=1 (26240 samples)", 1, 3, 2, 128, 128);                      // 164 frames, T 82: 96 rows
+  whisper("whisper ragged B=3 (26240, 12640, 48000)", 3, 3 + 2 + 5, 2 + 1 + 3, 384, 384);   // T 82, 40, 150: rows 96 + 48 + 160, stem 96 + 48 + 160
+  whisper("whisper rows == Mpad (40000 samples)", 1, 4, 2, 128, 128);             // 250 frames, T 125: 128 rows, stem round16(126) = 128
+  whisper("whisper no query blocks", 2, 5, 0, 256, 256);
+  // Qwen3 (B, windows, fbank blocks, encoder query blocks, chunk slots, Me, Md, decoder query blocks)
+  qwen("qwen B=1", 1, 1, 3, 1, 8, 128, 128, 1);
+  qwen("qwen ragged B=3", 3, 4, 11, 5, 32, 512, 256, 4);
+  qwen("qwen f32: n_qb = 0, n_dqb = 0", 2, 2, 5, 0, 16, 256, 128, 0);
+  qwen("qwen total needs rounding", 1, 1, 1, 1, 8, 128, 128, 0);                 // 40 * 3 + 4 * (2 + 2 + 16 + 128 + 384 + 1) = 2252 -> 2256
+  qwen("qwen rows == Mpad", 2, 2, 6, 2, 16, 208, 128, 2);
+  for (size_t rows : {1, 3, 128, 129, 640}) qwen_step("qwen step plan", rows);
+  // SenseVoice (B, fbank blocks, query blocks, rows)
+  sensevoice("sensevoice B=1 (16000 samples)", 1, 2, 1, 32);
+  sensevoice("sensevoice ragged B=3", 3, 2 + 2 + 4, 3, 32 + 32 + 64);             // rows == Mpad == 128
+  sensevoice("sensevoice n_qb = 0", 2, 4, 0, 80);
+  sensevoice("sensevoice 12 utterances", 12, 30, 12, 12 * 48);
+  for (size_t n : {1, 3, 8, 9, 64}) stream_step("paraformer stream step", n);      // n = 8: rows == Mpad
+  // alignment: an odd run of 4-byte words in front of 8-aligned plans is padded (no site does this today; a new section order may)
+  check("padding before an 8-aligned section", {i32(3), utt(2), i32(1)}, 16, {0, 16, 96}, 112);
+  if (failures) { printf("%d checks failed\n", failures); return 1; }
+  printf("plan layout ok\n");
+  return 0;
+}
