@@ -55,7 +55,8 @@ class TokenHeadDesc(C.Structure):
                 ("steps", C.c_int32), ("track_history", C.c_int32), ("sampling", C.c_int32), ("change_step", C.c_int32), ("range2", C.c_int32),
                 ("value2", C.c_float), ("picks", _ip),
                 ("timestamps", C.c_int32), ("ts_begin", C.c_int32), ("no_timestamps_id", C.c_int32), ("eot_id", C.c_int32), ("max_initial", C.c_int32),
-                ("n_saved_rows", _ip)]
+                ("n_saved_rows", _ip), ("scores", C.c_int32), ("logprob", _fp), ("timed", C.c_int32),
+                ("head_ms", C.c_float)]
 
 
 class WhisperAlignDesc(C.Structure):
@@ -330,16 +331,19 @@ def beam_select(beam, K, n_slots, topv, topi, cum, fin, length, nxt, done, src_i
 
 
 PAD_LOGIT = np.float32(1e30)              # what token_head puts in the pad columns [n_valid, ld) of every logits row
-_HEAD_OPS = {"argmax_rows": 0, "beam_topk": 1, "apply_penalty": 2, "append_ids": 3, "sample_topk_topp": 4, "no_speech_prob": 5, "timestamp_rules": 7}
+_HEAD_OPS = {"argmax_rows": 0, "beam_topk": 1, "apply_penalty": 2, "append_ids": 3, "sample_topk_topp": 4, "no_speech_prob": 5, "timestamp_rules": 7,
+             "argmax_logprob_rows": 8, "logprob_at_rows": 9}
 
 
 def token_head(op, logits=None, vec=None, K=0, save_ids=None, n_saved=0, range_=0, value=1.0, partial=0, next_ids=None,
-               temperature=1.0, top_p=1.0, repetition_penalty=1.0, noise=None, seed=0, no_speech_id=0, timestamps=None):
+               temperature=1.0, top_p=1.0, repetition_penalty=1.0, noise=None, seed=0, no_speech_id=0, timestamps=None, logprob=None, ld_save=0):
     """One token-selection head (asr_mi355x_probe.h: asr_probe_token_head) through its product launcher; `op` is the launcher's name less "launch_".
 
     logits [rows][n_valid] are laid out with the sessions' leading dimension ld = roundup(n_valid, 128), the pad filled with PAD_LOGIT (+1e30: a kernel
     that lets a pad column into a maximum, a top-k list or a soft-max sum fails visibly); vec (extra / bias / penalty, [n_valid]) gets zeros there.
     timestamp_rules: timestamps = (ts_begin, no_timestamps_id, eot_id, max_initial); n_saved is one length for every row or an array of per-row lengths.
+    argmax_logprob_rows / logprob_at_rows: logprob = the score history [rows][ld_save] as it stands before the call (the caller's fill pattern), n_saved the
+    counter, next_ids the ids to score (logprob_at_rows); "ids" starts from a -1 fill, "logprob" comes back with whatever the kernel wrote.
     Returns a dict: the head's outputs (ids | topv, topi | next | prob), logits [rows][ld] after the call, save_ids (the whole table) and n_saved after it."""
     d = TokenHeadDesc()
     d.op = _HEAD_OPS[op]
@@ -386,6 +390,13 @@ def token_head(op, logits=None, vec=None, K=0, save_ids=None, n_saved=0, range_=
     elif op == "no_speech_prob":
         out["prob"] = np.zeros(rows, np.float32)
         d.out_v = out["prob"].ctypes.data_as(_fp)
+    elif op in ("argmax_logprob_rows", "logprob_at_rows"):
+        out["logprob"] = np.array(logprob, np.float32, order="C", copy=True)
+        assert out["logprob"].ndim == 2 and out["logprob"].shape[0] == rows
+        d.logprob, d.ld_save, d.n_saved = out["logprob"].ctypes.data_as(_fp), out["logprob"].shape[1], int(n_saved)
+        if op == "argmax_logprob_rows":
+            out["ids"] = np.full(rows, -1, np.int32)
+            d.out_i = out["ids"].ctypes.data_as(_ip)
     elif op in ("argmax_rows", "sample_topk_topp"):
         key = "ids" if op == "argmax_rows" else "next"
         out[key] = np.full(rows, -1, np.int32)
@@ -396,12 +407,15 @@ def token_head(op, logits=None, vec=None, K=0, save_ids=None, n_saved=0, range_=
     return out
 
 
-def head_steps(logits, steps, ld_save, range_, value, partial, bias=None, track_history=False, sampler=None, noise=None, change=None, timestamps=None):
+def head_steps(logits, steps, ld_save, range_, value, partial, bias=None, track_history=False, sampler=None, noise=None, change=None, timestamps=None,
+               scores=False, timed=False):
     """A TokenHead (csrc/decode_head.h) driven through `steps` decoder steps on the same logits rows (asr_probe_token_head, op 6): step 0 is a prefill
     (`bias` added, no penalty), the others are decode steps. sampler: (temperature, top_k, top_p, repetition_penalty, seed) or None; noise: uniforms
     [rows][top_k] armed for step 0; change: (step, value, range) -- set_penalty before that step; timestamps: (ts_begin, no_timestamps_id, eot_id,
-    max_initial) -- Whisper's timestamp mode on. Rows are padded as token_head pads them.
-    Returns {"picks": [steps][rows], "save_ids": the final history [rows][ld_save], "n_saved": the counter}."""
+    max_initial) -- Whisper's timestamp mode on; scores: token scores on. Rows are padded as token_head pads them.
+    Returns {"picks": [steps][rows], "save_ids": the final history [rows][ld_save], "n_saved": the counter} and, with scores, "logprob": the score history
+    [rows][ld_save] (NaN where no step wrote). timed (plain arg-max head only): the rows are uploaded once and "head_ms" is the device time of the steps'
+    launches, run back to back (tools/probes/token_scores_timing.py)."""
     logits = _f32(logits)
     rows, n_valid = logits.shape
     ld = (n_valid + 127) // 128 * 128
@@ -426,8 +440,14 @@ def head_steps(logits, steps, ld_save, range_, value, partial, bias=None, track_
         d.timestamps, (d.ts_begin, d.no_timestamps_id, d.eot_id, d.max_initial) = 1, (int(v) for v in timestamps)
     out = {"picks": np.full((steps, rows), -1, np.int32), "save_ids": np.full((rows, ld_save), -1, np.int32)}
     d.picks, d.save_ids = out["picks"].ctypes.data_as(_ip), out["save_ids"].ctypes.data_as(_ip)
+    if scores:
+        out["logprob"] = np.zeros((rows, ld_save), np.float32)
+        d.scores, d.logprob = 1, out["logprob"].ctypes.data_as(_fp)
+    d.timed = int(timed)
     _lib.check(load().asr_probe_token_head(C.byref(d)))
     out["n_saved"] = d.n_saved_after
+    if timed:
+        out["head_ms"] = float(d.head_ms)
     return out
 
 

@@ -47,8 +47,12 @@ struct ASR_LOCAL TokenHead {
   int top_k = 10;
   uint64_t samp_seed = 0;
   TimestampRule ts;                    // Whisper's timestamp mode: the rules run before every selection, every pick joins the history
+  bool scores = false;                 // token scores (kernels.h: launch_argmax_logprob_rows): every pick's log-probability joins d_scores, every pick the history
   Profiler* prof = nullptr;            // the owning session's, when it has one: the rule kernel is a profile class of its own
   DeviceBuffer d_save, d_nsaved;       // generated ids per sequence + their count (on the device: a captured step replays for every position)
+  int score_rows = 0;                  // rows d_scores was last reserved for
+  bool scored = false;                 // a prefill has restarted the histories since scores were switched on: d_scores[.., 0 .. *d_nsaved) are this run's
+  DeviceBuffer d_scores;               // scores mode: the picks' log-probabilities [rows][ld_save] f32, column for column beside d_save under the same counter
   DeviceBuffer d_noise;                // caller-supplied uniforms [rows][top_k] for the next step (parity tests); consumed once
   bool noise_armed = false;            // a step with armed noise is not graphable
   uint64_t epoch = 0;                  // moves with everything a captured step bakes in: a setter that changed a value, a history buffer that moved
@@ -85,6 +89,9 @@ struct ASR_LOCAL TokenHead {
     }
     if (!(t == ts)) { ts = t; ++epoch; }
   }
+  void set_scores(bool enable) {
+    if (scores != enable) { scores = enable; scored = false; ++epoch; }
+  }
   void arm_noise(const float* uniforms, int count, hipStream_t s) {
     d_noise.reserve((size_t)count * 4, s);
     HIP_CHECK(hipMemcpyAsync(d_noise.ptr, uniforms, (size_t)count * 4, hipMemcpyHostToDevice, s));
@@ -95,17 +102,22 @@ struct ASR_LOCAL TokenHead {
   void reserve(int rows, hipStream_t s) {
     bool moved = reserve_moved(d_nsaved, 256, s);
     moved |= reserve_moved(d_save, (size_t)rows * ld_save * 4, s);
+    if (scores) { moved |= reserve_moved(d_scores, (size_t)rows * ld_save * 4, s); score_rows = rows; }
     if (moved) ++epoch;
   }
-  void restart(hipStream_t s) { HIP_CHECK(hipMemsetAsync(d_nsaved.ptr, 0, 4, s)); }      // every prefill starts from an empty history
+  void restart(hipStream_t s) { HIP_CHECK(hipMemsetAsync(d_nsaved.ptr, 0, 4, s)); scored = scores; }      // every prefill starts from an empty history (ids and scores: one counter)
 
   // The head's launches on logits [rows][ld]: picks go to next [rows]. bias: Whisper's BEGIN_SUPPRESS after a prefill, else null. penalise: false on a
   // prefill (the prefill graphs select from the raw logits with an empty history; the decode graphs apply the penalty first). Timestamp mode: the rules
-  // run on both, after the penalty and before the selection (an empty history is their initial rule).
+  // run on both, after the penalty and before the selection (an empty history is their initial rule). Scores mode: the arg-max is the fused kernel, the
+  // sampler is followed by the at-id kernel (it sees the sampler's in-place repetition penalty), the pick joins the history; off, nothing new is launched.
   void enqueue(float* logits, int ld, int rows, int n_valid, const float* bias, bool penalise, int32_t* next, hipStream_t s) {
     const bool penalised = penalty_value != 1.0f && !sampling;
     int32_t* save = d_save.as<int32_t>();
     int32_t* n_saved = d_nsaved.as<int32_t>();
+    // the score kernels write row r of d_scores for every r < rows: reserve(rows) must have run with the mode on (the sessions call it before every step)
+    ASR_REQUIRE(!scores || (d_scores.ptr && rows <= score_rows), "token scores: the score history holds %d rows, this step has %d (switch token scores on before the prefill)",
+                d_scores.ptr ? score_rows : 0, rows);
     if (penalised && penalise) launch_apply_penalty(logits, ld, rows, save, ld_save, n_saved, penalty_range, penalty_value, s, partial);
     if (ts.on) ts.enqueue(prof, logits, ld, rows, n_valid, save, ld_save, n_saved, 0, s);
     if (sampling) {                        // the bias first, history = every sampled id
@@ -115,15 +127,47 @@ struct ASR_LOCAL TokenHead {
       sa.temperature = temperature; sa.top_p = top_p; sa.repetition_penalty = samp_rep_penalty; sa.top_k = top_k;
       sa.noise = noise_armed ? d_noise.as<float>() : nullptr; sa.seed = samp_seed; sa.next = next;
       launch_sample_topk_topp(sa, s);
+      if (scores) {
+        ScoreScope sc(prof, s);
+        launch_logprob_at_rows(logits, ld, rows, n_valid, bias, next, d_scores.as<float>(), ld_save, n_saved, s);
+      }
+    } else if (scores) {
+      ScoreScope sc(prof, s);
+      launch_argmax_logprob_rows(logits, ld, rows, n_valid, bias, next, d_scores.as<float>(), ld_save, n_saved, s);
     } else {
       launch_argmax_rows(logits, ld, rows, n_valid, bias, next, s);
     }
-    if (penalised || sampling || track_history || ts.on) {   // GREEDY_SEARCH / the sampling head append their pick to the history
+    if (penalised || sampling || track_history || ts.on || scores) {   // GREEDY_SEARCH / the sampling head append their pick to the history
       launch_append_ids(next, rows, save, ld_save, n_saved, s);
       launch_add_scalar(n_saved, 1, s);
     }
   }
   void consumed() { noise_armed = false; }        // after the step: caller-supplied uniforms serve exactly one
+
+  // The scores of the picks since the last restart, oldest first: logprob_out [rows][out_stride] gets min(count, out_stride) per row (slots past the count keep
+  // the caller's fill), *n_out the count. Returns with the stream drained. `who`: the C entry's name.
+  void download_scores(int rows, float* logprob_out, int out_stride, int32_t* n_out, hipStream_t s, const char* who) {
+    ASR_REQUIRE(logprob_out && n_out && out_stride >= 1, "%s: bad argument", who);
+    ASR_REQUIRE(scores, "%s: token scores are off (switch them on before the prefill)", who);
+    ASR_REQUIRE(rows > 0 && rows <= score_rows && scored && d_scores.ptr && d_nsaved.ptr, "%s: no prefill since token scores were switched on", who);
+    int32_t n = 0;
+    HIP_CHECK(hipMemcpyAsync(&n, d_nsaved.ptr, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    n = std::min(std::max(n, 0), ld_save);
+    *n_out = n;
+    const int take = std::min(n, out_stride);
+    if (take > 0) {
+      HIP_CHECK(hipMemcpy2DAsync(logprob_out, (size_t)out_stride * 4, d_scores.ptr, (size_t)ld_save * 4, (size_t)take * 4, rows, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+  }
+
+ private:
+  struct ScoreScope {                  // the score launches are a profile class of their own, as the timestamp rules are
+    Profiler* p; hipStream_t s;
+    ScoreScope(Profiler* p_, hipStream_t s_) : p(p_ && p_->enabled ? p_ : nullptr), s(s_) { if (p) p->begin(p->cls("token_scores"), s); }
+    ~ScoreScope() { if (p) p->end(s); }
+  };
 };
 
 // ---- beam-search ranking (semantics of oracle/qwen_asr_oracle.py:beam_search_core): hypothesis rows b * beam + r, their scores, lengths and ended flags, the

@@ -129,6 +129,19 @@ void launch_beam_select(const BeamArgs& a, int n_utt, hipStream_t s);
 
 // ids[r] = first arg-max over n < n_valid of logits[r][n] + (extra ? extra[n] : 0)
 void launch_argmax_rows(const float* logits, int ld, int rows, int n_valid, const float* extra, int32_t* ids, hipStream_t s);
+// ---- token scores (the build's own mode, after OpenAI Whisper's `logprobs`; the reference reports none). The score of a pick is the natural-log soft-max at
+// the picked id of v[n] = logits[r][n] + (extra ? extra[n] : 0) over n < n_valid -- the f32 row as the selection sees it, temperature / top-k / top-p not
+// part of it. Rows hold finite values and -inf (a mask); +inf or NaN in a row is outside the contract (exp(inf - inf)), as it is for every soft-max here.
+// A -inf column has zero weight; a row without a column above -inf, or a pick whose own column is -inf, scores -inf (never NaN); the pad columns
+// [n_valid, ld) are not read into the sum. One pass over the row in launch_argmax_rows' geometry, (max, sum of exp(v - max)) carried online. The score is
+// written to logprob[r * ld_save + *n_saved] (the counter lives on the device: a captured step replays for every position); columns at or past ld_save are
+// dropped, as launch_append_ids drops them.
+//   launch_argmax_logprob_rows: the greedy pick and its score in one kernel; ids equal launch_argmax_rows' bit for bit, score = -log S.
+//   launch_logprob_at_rows: the score of ids[r], picked elsewhere (the sampler); an id outside [0, n_valid) scores -inf.
+void launch_argmax_logprob_rows(const float* logits, int ld, int rows, int n_valid, const float* extra, int32_t* ids, float* logprob, int ld_save,
+                                const int32_t* n_saved, hipStream_t s);
+void launch_logprob_at_rows(const float* logits, int ld, int rows, int n_valid, const float* extra, const int32_t* ids, float* logprob, int ld_save,
+                            const int32_t* n_saved, hipStream_t s);
 // NO_SPEECH_DETECTION (Export_Whisper.py:334-348): prob[r] = softmax(logits[r] - penalty)[no_speech_id] over the first n_valid columns, where
 // `penalty` is the permanent suppress bias the logits carry (-128 on the suppressed ids: subtracting it re-adds the +128 the reference adds back)
 void launch_no_speech_prob(const float* logits, int ld, int rows, int n_valid, const float* penalty, int no_speech_id, float* prob, hipStream_t s);

@@ -1311,6 +1311,82 @@ __global__ __launch_bounds__(1024) void argmax_rows_kernel(const float* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------ token scores (kernels.h: launch_argmax_logprob_rows / launch_logprob_at_rows)
+// The arg-max kernel's geometry and tie rule with an online log-sum-exp beside the best pair: a thread's running maximum IS its best value, so the pair
+// (best, sum of exp(v - best)) costs one __expf per column and one rescale per 16-byte load whose maximum moves. Merges combine (max, sum) pairs; a side whose
+// maximum is -inf (an empty thread, a stripe of -inf columns) has weight 0 and nothing is ever subtracted from -inf. The holder of the row maximum adds
+// exp(0) = 1 and is only ever rescaled by exp(0), so S >= 1 and the fused score -logf(S) is <= 0.
+__device__ __forceinline__ float lse_scale(float m, float M) { return m == -INFINITY ? 0.0f : __expf(m - M); }
+
+// FUSED: ids[r] = the arg-max (bit for bit argmax_rows_kernel's), score = -logf(S). Otherwise ids[r] is read, score = x[id] + extra[id] - (M + logf(S)).
+// The score goes to column *n_saved of the row's history [ld_save]; a full table drops it (append_ids_kernel's rule).
+template <bool FUSED>
+__global__ __launch_bounds__(1024) void logprob_rows_kernel(const float* __restrict__ logits, int ld, int n_valid, const float* __restrict__ extra,
+                                                            int32_t* __restrict__ ids, float* __restrict__ logprob, int ld_save,
+                                                            const int32_t* __restrict__ n_saved) {
+  __shared__ float bv[16], bs[16];
+  __shared__ int bi[16];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* x = logits + (size_t)r * ld;
+  float best = -INFINITY, sum = 0.0f;
+  int bidx = 0x7fffffff;
+  auto take = [&](const float4 v, int c) {                    // ascending columns: strict > keeps the first maximum
+    const float a0 = c + 0 < n_valid ? v.x : -INFINITY, a1 = c + 1 < n_valid ? v.y : -INFINITY;
+    const float a2 = c + 2 < n_valid ? v.z : -INFINITY, a3 = c + 3 < n_valid ? v.w : -INFINITY;
+    const float m4 = fmaxf(fmaxf(a0, a1), fmaxf(a2, a3));
+    if (m4 > best) sum *= __expf(best - m4);                  // (best = -inf: sum is 0 and stays 0)
+    if (a0 > best) { best = a0; bidx = c; }
+    if (a1 > best) { best = a1; bidx = c + 1; }
+    if (a2 > best) { best = a2; bidx = c + 2; }
+    if (a3 > best) { best = a3; bidx = c + 3; }
+    const float mm = best == -INFINITY ? 0.0f : best;         // nothing above -inf yet: the four terms are exp(-inf) = 0
+    sum += __expf(a0 - mm);
+    sum += __expf(a1 - mm);
+    sum += __expf(a2 - mm);
+    sum += __expf(a3 - mm);
+  };
+  auto load = [&](int c) {
+    float4 v = *reinterpret_cast<const float4*>(x + c);       // rows are padded to a multiple of 128 columns
+    if (extra) { const float4 e = *reinterpret_cast<const float4*>(extra + c); v.x += e.x; v.y += e.y; v.z += e.z; v.w += e.w; }
+    return v;
+  };
+  int c = tid * 4;
+  for (; c + 4096 < n_valid; c += 8192) {
+    const float4 a = load(c), b = load(c + 4096);
+    take(a, c);
+    take(b, c + 4096);
+  }
+  if (c < n_valid) take(load(c), c);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64), os = __shfl_xor(sum, o, 64);
+    const int oi = __shfl_xor(bidx, o, 64);
+    const float M = fmaxf(best, ov);
+    sum = sum * lse_scale(best, M) + os * lse_scale(ov, M);
+    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+  }
+  if (lane == 0) { bv[wave] = best; bi[wave] = bidx; bs[wave] = sum; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 16; ++w)
+      if (bv[w] > best || (bv[w] == best && bi[w] < bidx)) { best = bv[w]; bidx = bi[w]; }
+    float S = 0.0f;
+    for (int w = 0; w < 16; ++w) S += bs[w] * lse_scale(bv[w], best);
+    float score;
+    if (FUSED) {
+      ids[r] = bidx == 0x7fffffff ? 0 : bidx;             // (no column above -inf: id 0, score -inf)
+      score = best == -INFINITY ? -INFINITY : -logf(S);
+    } else {
+      const int id = ids[r];
+      float v = -INFINITY;
+      if (id >= 0 && id < n_valid) v = x[id] + (extra ? extra[id] : 0.0f);
+      score = (best == -INFINITY || v == -INFINITY) ? -INFINITY : v - (best + logf(S));
+    }
+    const int n = *n_saved;
+    if (n >= 0 && n < ld_save) logprob[(size_t)r * ld_save + n] = score;
+  }
+}
+
 
 __global__ __launch_bounds__(1024) void no_speech_prob_kernel(const float* __restrict__ logits, int ld, int n_valid, const float* __restrict__ penalty,
                                                               int no_speech_id, float* __restrict__ prob) {
@@ -2283,6 +2359,20 @@ void launch_argmax_rows(const float* logits, int ld, int rows, int n_valid, cons
 void launch_no_speech_prob(const float* logits, int ld, int rows, int n_valid, const float* penalty, int no_speech_id, float* prob, hipStream_t s) {
   ASR_REQUIRE(no_speech_id >= 0 && no_speech_id < n_valid, "no_speech_prob: id %d outside the vocabulary", no_speech_id);
   hipLaunchKernelGGL(no_speech_prob_kernel, dim3(rows), dim3(1024), 0, s, logits, ld, n_valid, penalty, no_speech_id, prob);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_argmax_logprob_rows(const float* logits, int ld, int rows, int n_valid, const float* extra, int32_t* ids, float* logprob, int ld_save,
+                                const int32_t* n_saved, hipStream_t s) {
+  ASR_REQUIRE(ld % 4 == 0 && n_valid <= ld && ids && logprob && n_saved && ld_save >= 1, "argmax_logprob_rows: ld %d n_valid %d ld_save %d", ld, n_valid, ld_save);
+  hipLaunchKernelGGL(logprob_rows_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, ld, n_valid, extra, ids, logprob, ld_save, n_saved);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_logprob_at_rows(const float* logits, int ld, int rows, int n_valid, const float* extra, const int32_t* ids, float* logprob, int ld_save,
+                            const int32_t* n_saved, hipStream_t s) {
+  ASR_REQUIRE(ld % 4 == 0 && n_valid <= ld && ids && logprob && n_saved && ld_save >= 1, "logprob_at_rows: ld %d n_valid %d ld_save %d", ld, n_valid, ld_save);
+  hipLaunchKernelGGL(logprob_rows_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, ld, n_valid, extra, const_cast<int32_t*>(ids), logprob, ld_save, n_saved);
   HIP_CHECK(hipGetLastError());
 }
 

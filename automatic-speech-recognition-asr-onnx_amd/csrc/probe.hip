@@ -766,7 +766,13 @@ static void probe_head_steps(asr_probe_token_head_desc* d) {
   const char* who = "probe_token_head";
   const int rows = d->rows, ld = d->ld, steps = d->steps;
   ASR_REQUIRE(d->logits && d->picks && d->save_ids, "%s: head steps need logits, picks and save_ids", who);
-  ASR_REQUIRE(steps >= 1 && d->ld_save >= steps && d->ld_save <= 1024, "%s: %d steps do not fit the history table of %d", who, steps, d->ld_save);
+  // (more steps than the table holds: only where nothing indexes the table by the raw counter -- the penalty window does)
+  const bool may_overflow = d->scores && d->value == 1.0f && d->change_step <= 0 && d->logprob;
+  ASR_REQUIRE(steps >= 1 && (d->ld_save >= steps || may_overflow) && d->ld_save >= 1 && d->ld_save <= 1024, "%s: %d steps do not fit the history table of %d", who, steps,
+              d->ld_save);
+  ASR_REQUIRE(!d->scores || d->logprob, "%s: scores without the logprob table", who);
+  // timed: the rows are uploaded once (only a head that edits nothing in place may skip the fresh copy) and the steps' launches run back to back between two device events
+  ASR_REQUIRE(!d->timed || (d->value == 1.0f && d->change_step <= 0 && !d->sampling && !d->timestamps), "%s: timed steps need the plain arg-max head", who);
   ASR_REQUIRE(d->range <= d->ld_save && (d->change_step <= 0 || d->range2 <= d->ld_save), "%s: penalty range past the history table of %d", who, d->ld_save);
   ASR_REQUIRE(!d->sampling || d->K <= d->n_valid, "%s: sampler top_k %d", who, d->K);
   ASR_REQUIRE(!d->noise || d->sampling, "%s: noise without the sampler", who);
@@ -783,30 +789,44 @@ static void probe_head_steps(asr_probe_token_head_desc* d) {
   h.set_track_history(d->track_history != 0);
   if (d->sampling) h.set_sampling(true, d->temperature, d->K, d->top_p, d->repetition_penalty, d->seed, who);
   if (d->timestamps) h.set_timestamps(true, d->ts_begin, d->no_timestamps_id, d->eot_id, d->max_initial, d->n_valid, who);
+  h.set_scores(d->scores != 0);
   h.reserve(rows, nullptr);
   h.restart(nullptr);
+  if (d->scores) HIP_CHECK(hipMemset(h.d_scores.ptr, 0xFF, (size_t)rows * d->ld_save * 4));      // NaN: a column no step wrote shows
   if (d->noise) h.arm_noise(d->noise, rows * d->K, nullptr);
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (d->timed) { HIP_CHECK(hipEventCreate(&ev[0])); HIP_CHECK(hipEventCreate(&ev[1])); }
+  d->head_ms = 0.0f;
   for (int i = 0; i < steps; ++i) {
     if (i > 0 && i == d->change_step) h.set_penalty(d->value2, d->range2, who);
-    HIP_CHECK(hipMemcpy(dlog, d->logits, lbytes, hipMemcpyHostToDevice));
+    if (i == 0 || !d->timed) HIP_CHECK(hipMemcpy(dlog, d->logits, lbytes, hipMemcpyHostToDevice));
+    if (d->timed && i == 0) HIP_CHECK(hipEventRecord(ev[0], nullptr));
     h.enqueue(dlog, ld, rows, d->n_valid, i == 0 ? dvec : nullptr, i > 0, dpick + (size_t)i * rows, nullptr);
     h.consumed();
   }
+  if (d->timed) HIP_CHECK(hipEventRecord(ev[1], nullptr));
   HIP_CHECK(hipDeviceSynchronize());
+  if (d->timed) {
+    HIP_CHECK(hipEventElapsedTime(&d->head_ms, ev[0], ev[1]));
+    HIP_CHECK(hipEventDestroy(ev[0])); HIP_CHECK(hipEventDestroy(ev[1]));
+  }
   HIP_CHECK(hipMemcpy(d->picks, dpick, (size_t)steps * rows * 4, hipMemcpyDeviceToHost));
   HIP_CHECK(hipMemcpy(d->save_ids, h.d_save.ptr, (size_t)rows * d->ld_save * 4, hipMemcpyDeviceToHost));
   HIP_CHECK(hipMemcpy(&d->n_saved_after, h.d_nsaved.ptr, 4, hipMemcpyDeviceToHost));
+  if (d->scores) HIP_CHECK(hipMemcpy(d->logprob, h.d_scores.ptr, (size_t)rows * d->ld_save * 4, hipMemcpyDeviceToHost));
 }
 
 // ---- the token-selection heads (kernels.h) on host arrays: one product launcher per call, unchanged. Every index a kernel will follow is checked here first.
 extern "C" int asr_probe_token_head(asr_probe_token_head_desc* d) {
   return asr_guard([&] {
-    ASR_REQUIRE(d && d->op >= 0 && d->op <= 7 && d->rows > 0 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0, "probe_token_head: bad descriptor");
+    ASR_REQUIRE(d && d->op >= 0 && d->op <= 9 && d->rows > 0 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0, "probe_token_head: bad descriptor");
     if (d->op == 6) { probe_head_steps(d); return; }
     const int op = d->op, rows = d->rows, ld = d->ld;
     const bool uses_logits = op != 3, uses_save = op == 2 || op == 3 || op == 4 || op == 7;
     ASR_REQUIRE(!uses_logits || d->logits, "probe_token_head: logits missing");
-    ASR_REQUIRE((op == 2 || op == 3 || op == 5 || op == 7 || d->out_i) && ((op != 1 && op != 5) || d->out_v), "probe_token_head: output array missing");
+    const bool scoring = op == 8 || op == 9;
+    ASR_REQUIRE(!scoring || (d->logprob && d->ld_save >= 1 && d->n_saved >= 0 && (op == 8 || d->next_in)), "probe_token_head: score ops need the logprob table and a counter >= 0 (op 9: ids)");
+    ASR_REQUIRE((op == 2 || op == 3 || op == 5 || op == 7 || op == 9 || d->out_i) && ((op != 1 && op != 5) || d->out_v), "probe_token_head: output array missing");
     ASR_REQUIRE(op != 2 || (d->range >= 1 && d->range <= 64 && d->range <= d->ld_save), "probe_token_head: apply_penalty range %d (1..64, within the table)", d->range);
     ASR_REQUIRE(op != 5 || (d->no_speech_id >= 0 && d->no_speech_id < d->n_valid), "probe_token_head: no_speech_id %d outside the vocabulary of %d", d->no_speech_id, d->n_valid);
     if (uses_save) {
@@ -862,6 +882,21 @@ extern "C" int asr_probe_token_head(asr_probe_token_head_desc* d) {
         a.noise = d->noise ? (const float*)up(d->noise, (size_t)rows * d->K * 4) : nullptr; a.seed = d->seed;
         a.next = di;
         launch_sample_topk_topp(a, nullptr);
+        break;
+      }
+      case 8:
+      case 9: {             // ids outside the vocabulary are the kernel's to refuse (score -inf): it checks before it reads
+        const size_t tbytes = (size_t)rows * d->ld_save * 4;
+        float* dlp = (float*)up(d->logprob, tbytes);
+        const int32_t* dcnt = (const int32_t*)up(&d->n_saved, 4);
+        if (op == 8) {
+          ni = rows; di = (int32_t*)up(d->out_i, ni * 4);
+          launch_argmax_logprob_rows(dlog, ld, rows, d->n_valid, dvec, di, dlp, d->ld_save, dcnt, nullptr);
+        } else {
+          launch_logprob_at_rows(dlog, ld, rows, d->n_valid, dvec, (const int32_t*)up(d->next_in, (size_t)rows * 4), dlp, d->ld_save, dcnt, nullptr);
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(d->logprob, dlp, tbytes, hipMemcpyDeviceToHost));
         break;
       }
       case 7: {             // the launcher checks the four parameters itself

@@ -725,6 +725,7 @@ void QwSession::init() {
   ASR_REQUIRE(cpw >= 1 && rpw <= 1024, "qwen: bad attention window");
   vpad = round_up(c.vocab, 128);
   head.init(c.max_seq_len, 1, 10, 1024);
+  head.prof = &prof;
   ASR_REQUIRE(c.classify_num >= 0, "qwen: classify_num %d", c.classify_num);
   hpad = aligner() ? round_up(c.classify_num, 128) : vpad;   // rows of dec.lm_head: the vocabulary, or the aligner's timestamp buckets
   cpad = round_up(c.conv_channels, 128);
@@ -1325,6 +1326,7 @@ void QwSession::step(const int32_t* ids_host, int32_t* next_out, float* logits_o
   ASR_REQUIRE(batch > 0, "qwen_decode: prefill first");
   HIP_CHECK(hipSetDevice(device));
   const int B = batch, d = c.d_model;
+  head.reserve(B, stream);                               // (token scores switched on since the prefill: their history covers this batch before anything is enqueued)
   for (int b = 0; b < B; ++b) {
     ASR_REQUIRE(seq_len[b] + 1 <= c.max_seq_len || (b < (int)frozen.size() && frozen[b]), "qwen_decode: sequence %d is at max_seq_len %d", b, c.max_seq_len);
     // a sequence that generate() finished has given its cache pages back (its table row points at the scratch page): it cannot be stepped again outside that
@@ -1493,6 +1495,18 @@ extern "C" int asr_qwen_track_history(asr_session* s, int enable) {
 extern "C" int asr_qwen_set_sampling(asr_session* s, int enable, float temperature, int top_k, float top_p, float repetition_penalty, uint64_t seed) {
   return asr_guard([&] {
     qwen_session(s, "qwen_set_sampling")->head.set_sampling(enable != 0, temperature, top_k, top_p, repetition_penalty, seed, "qwen_set_sampling");
+  });
+}
+
+extern "C" int asr_qwen_set_token_scores(asr_session* s, int enable) {
+  return asr_guard([&] { qwen_session(s, "qwen_set_token_scores")->head.set_scores(enable != 0); });
+}
+
+extern "C" int asr_qwen_token_scores(asr_session* s, float* logprob_out, int out_stride, int32_t* n_out) {
+  return asr_guard([&] {
+    QwSession* q = qwen_session(s, "qwen_token_scores");
+    HIP_CHECK(hipSetDevice(q->device));
+    q->head.download_scores(q->batch, logprob_out, out_stride, n_out, q->stream, "qwen_token_scores");
   });
 }
 

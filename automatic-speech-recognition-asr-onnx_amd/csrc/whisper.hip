@@ -1011,6 +1011,18 @@ extern "C" int asr_whisper_set_timestamps(asr_session* s, int enable, int timest
   });
 }
 
+extern "C" int asr_whisper_set_token_scores(asr_session* s, int enable) {
+  return asr_guard([&] { whisper_session(s, "whisper_set_token_scores")->head.set_scores(enable != 0); });
+}
+
+extern "C" int asr_whisper_token_scores(asr_session* s, float* logprob_out, int out_stride, int32_t* n_out) {
+  return asr_guard([&] {
+    WhSession* w = whisper_session(s, "whisper_token_scores");
+    HIP_CHECK(hipSetDevice(w->device));
+    w->head.download_scores(w->batch, logprob_out, out_stride, n_out, w->stream, "whisper_token_scores");
+  });
+}
+
 extern "C" int asr_whisper_set_sampling_noise(asr_session* s, const float* uniforms, int count) {
   return asr_guard([&] {
     ASR_REQUIRE(s && s->kind == 2 && uniforms, "whisper_set_sampling_noise: bad argument");

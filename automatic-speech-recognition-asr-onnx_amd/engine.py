@@ -360,6 +360,20 @@ def _token_head(prefix: str, default_range: int, penalty_doc: str):
             u = _f32(uniforms).reshape(-1)
             _lib.check(entry("set_sampling_noise")(self._h, _fp(u), u.size))
 
+        def set_token_scores(self, enable: bool):
+            """Token scores (asr_<family>_set_token_scores): every pick of the arg-max, penalty-greedy and sampling heads is scored by the natural-log
+            soft-max of the logits row the selection sees (temperature, top-k and top-p apart). Switch it before the prefill; off, no step changes."""
+            _lib.check(entry("set_token_scores")(self._h, int(enable)))
+
+        def token_scores(self) -> np.ndarray:
+            """float32 [batch][count]: the log-probabilities of the picks since the last prefill, oldest first (column 0 is the prefill's pick; after
+            generate() the stop pick and what finished sequences picked while others went on are included). Drains the stream."""
+            cap = self._score_capacity()
+            out = np.full((max(self.batch, 1), cap), np.nan, dtype=np.float32)
+            n = np.zeros(1, dtype=np.int32)
+            _lib.check(entry("token_scores")(self._h, _fp(out), cap, _ip(n)))
+            return out[:self.batch, :int(n[0])].copy()
+
     TokenHeadMixin.set_penalty.__doc__ = penalty_doc
     return TokenHeadMixin
 
@@ -442,6 +456,9 @@ class WhisperSession(_token_head("whisper", 20, "Decode head: 1.0 = plain arg-ma
         idp = _ip(np.ascontiguousarray(ids, dtype=np.int32)) if ids is not None else None
         _lib.check(_lib.load().asr_whisper_decode(self._h, idp, _ip(nxt) if nxt is not None else None, _fp(logits)))
         return nxt, logits
+
+    def _score_capacity(self) -> int:
+        return int(self.cfg.max_target_positions)
 
     def generate(self, max_new: int, eos_id: int):
         tok = np.zeros((self.batch, max_new), dtype=np.int32)
@@ -754,6 +771,9 @@ class QwenAsrSession(_token_head("qwen", 10, "Decode head: 1.0 = plain arg-max; 
             out.append(rows[:self.audio_tokens(n)].copy())
             win += n_win
         return out
+
+    def _score_capacity(self) -> int:
+        return int(self.cfg.max_seq_len)
 
     def generate(self, max_new: int, stop_ids=()):
         tok = np.zeros((self.batch, max_new), dtype=np.int32)

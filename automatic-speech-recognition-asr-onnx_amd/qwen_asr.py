@@ -26,7 +26,7 @@ import numpy as np
 
 from .config import QwenAsrConfig
 from .engine import QwenAsrSession, audio_dtype_name
-from .whisper import prepare_audio_input
+from .whisper import avg_logprob, prepare_audio_input
 
 ASR_TEXT_TAG = "<asr_text>"
 LANG_PREFIX = "language "
@@ -123,7 +123,7 @@ def export_qwen_asr(cfg: QwenAsrConfig, ck: dict, path: str, metadata: dict, pre
 class QwenAsrTranscriber:
     def __init__(self, cfg: QwenAsrConfig, session: QwenAsrSession, metadata: dict, tokenizer=None, normalise_audio: bool = False,
                  repeat_penalty: float = 1.0, penalty_range: int = 10, use_sampling: bool = False, temperature: float = 0.8, top_k: int = 10,
-                 top_p: float = 0.95, sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1):
+                 top_p: float = 0.95, sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1, token_scores: bool = False):
         self.cfg, self.sess, self.tokenizer = cfg, session, tokenizer
         # _resolve_strategy (:369-376): sampling wins; REPEAT_PENALTY == 1.0 selects greedy, any other value penalty-greedy (the
         # reference's defaults are 0.8 over PENALTY_RANGE = 10 ids)
@@ -134,6 +134,10 @@ class QwenAsrTranscriber:
         self.beam_size = int(beam_size)
         if self.beam_size > 1 and (use_sampling or self.repeat_penalty != 1.0):
             raise ValueError("beam_size > 1 needs REPEAT_PENALTY = 1.0 and no sampling")
+        # token scores (the build's own: asr_qwen_set_token_scores): results gain token_logprobs (one per entry of tokens) and avg_logprob (the stop pick included)
+        self.token_scores = bool(token_scores)
+        if self.token_scores and self.beam_size > 1:
+            raise ValueError("token_scores needs beam_size == 1: the beam search reports a score per hypothesis, not per token")
         self.audio_pcm_scale = int(metadata["audio_pcm_scale"])
         self.max_seq_len = int(metadata["max_seq_len"])
         special = metadata["special_token_ids"]
@@ -174,16 +178,13 @@ class QwenAsrTranscriber:
         t0 = time.time()
         self.sess.set_penalty(self.repeat_penalty, self.penalty_range)
         self.sess.set_sampling(*self.sampling)
-        first, _, ids_len = self.sess.prefill(audios, pre, post, want_logits=False)
-        limits = np.maximum(self.max_seq_len - 10 - ids_len, 0)
-        if max_new is not None:
-            limits = np.minimum(limits, max_new)
-        if limits.max() <= 0:
-            toks = [np.zeros(0, np.int32)] * B
-        elif self.beam_size > 1:
-            toks = [h[0][0] for h in self.sess.beam_search(self.beam_size, int(limits.max()), stop_ids=self.stop)]
-        else:
-            toks = self.sess.generate(int(limits.max()), stop_ids=self.stop)
+        if self.token_scores:
+            self.sess.set_token_scores(True)
+        try:
+            toks, limits, ids_len, scores = self._prefill_and_generate(audios, pre, post, max_new)
+        finally:
+            if self.token_scores:
+                self.sess.set_token_scores(False)
         wall = time.time() - t0
         out = []
         for b in range(B):
@@ -196,6 +197,26 @@ class QwenAsrTranscriber:
                 language, text = parse_asr_output(raw)
                 if langs[b]:
                     language = resolve_language(self.languages, langs[b])[1]["name"]
-            out.append({"tokens": np.asarray(ids, dtype=np.int32), "language": language, "text": text, "prompt_tokens": int(ids_len[b])})
+            res = {"tokens": np.asarray(ids, dtype=np.int32), "language": language, "text": text, "prompt_tokens": int(ids_len[b])}
+            if scores is not None:                               # ended: the utterance met a stop id before its own limit and before the batch's
+                ended = len(toks[b]) <= limits[b] and len(toks[b]) < int(limits.max())
+                res["token_logprobs"] = np.asarray(scores[b][:len(ids)], dtype=np.float32)
+                res["avg_logprob"] = avg_logprob(scores[b], len(ids), ended)
+            out.append(res)
         total_s = sum(a.size for a in audios) / self.cfg.sample_rate
         return out, {"rtf": wall / total_s, "wall_s": wall}
+
+    def _prefill_and_generate(self, audios, pre, post, max_new):
+        """-> (ids per clip, per-clip limits, prompt lengths, sess.token_scores() or None)"""
+        B = len(audios)
+        first, _, ids_len = self.sess.prefill(audios, pre, post, want_logits=False)
+        limits = np.maximum(self.max_seq_len - 10 - ids_len, 0)
+        if max_new is not None:
+            limits = np.minimum(limits, max_new)
+        if limits.max() <= 0:
+            toks = [np.zeros(0, np.int32)] * B
+        elif self.beam_size > 1:
+            toks = [h[0][0] for h in self.sess.beam_search(self.beam_size, int(limits.max()), stop_ids=self.stop)]
+        else:
+            toks = self.sess.generate(int(limits.max()), stop_ids=self.stop)
+        return toks, limits, ids_len, self.sess.token_scores() if self.token_scores else None

@@ -25,7 +25,14 @@
                             captured while the ids are generated are the alignment sequence already, nothing is decoded twice; with timestamps=True or
                             beam_size > 1 a forced pass over the final text ids behind a <|notimestamps|> prompt captures them, as OpenAI does. Results gain
                             token_times [(start, end)] per text token (and words, with a piece decoder). The repeat guard is not applied; OpenAI's duration
-                            heuristics after the DTW and word probabilities are not part of it.
+                            heuristics after the DTW are not part of it.
+  token_scores=True       = this build's own mode (the reference reports no score): the device decode head scores every pick with the log-soft-max of the
+                            logits row it selects from (asr_whisper_set_token_scores). Results gain token_logprobs (one per entry of tokens), avg_logprob
+                            (OpenAI's sum_logprobs / (len + 1): every pick, timestamp ids and the stop pick included), compression_ratio (with a piece
+                            decoder) and temperature; words gain probability. The repeat guard is not applied (it would break the pairing).
+  temperature_fallback    = OpenAI's decode fallback: an utterance whose avg_logprob is below logprob_threshold, or whose compression_ratio is above its
+                            threshold, is decoded again by the sampler at the next temperature of the list (seed + attempt); the encoder output and the
+                            cross-K/V stay, the full-prompt prefill restarts the rest. The last attempt stands.
 Batch extension: `transcribe` takes a list of independent clips as one batch (language detection / no-speech per clip);
 `transcribe_file` is the reference's per-file behaviour (the windows of one file form the batch).
 """
@@ -33,6 +40,7 @@ from __future__ import annotations
 
 import string
 import time
+import zlib
 from typing import Sequence
 
 import numpy as np
@@ -197,15 +205,38 @@ def decode_pieces(ids: Sequence[int], decode) -> list:
     return pieces
 
 
-def word_times(pieces: Sequence[str], times: Sequence[tuple]):
+def word_times(pieces: Sequence[str], times: Sequence[tuple], logprobs=None):
     """[{"word", "start", "end", "tokens"}]: the pieces grouped by split_words, each word from the start of its first token to the end of its last
-    (`times` = token_times(...), one pair per piece; "tokens" = the word's token count)."""
+    (`times` = token_times(...), one pair per piece; "tokens" = the word's token count). logprobs (one per piece) adds "probability": the mean of
+    exp(logprob) over the word's tokens, OpenAI's word probability."""
     assert len(pieces) == len(times), (len(pieces), len(times))
+    assert logprobs is None or len(logprobs) == len(pieces), (len(logprobs), len(pieces))
     out, at = [], 0
     for n in split_words(pieces):
-        out.append({"word": "".join(p for p in pieces[at:at + n] if p), "start": times[at][0], "end": times[at + n - 1][1], "tokens": n})
+        word = {"word": "".join(p for p in pieces[at:at + n] if p), "start": times[at][0], "end": times[at + n - 1][1], "tokens": n}
+        if logprobs is not None:
+            word["probability"] = float(np.mean(np.exp(np.asarray(logprobs[at:at + n], dtype=np.float64))))
+        out.append(word)
         at += n
     return out
+
+
+# ---- token scores (OpenAI Whisper decoding.py: sum_logprobs / (len + 1); transcribe.py: compression_ratio, the temperature fallback)
+def avg_logprob(scores_row, n_tokens: int, ended: bool) -> float:
+    """The mean log-probability of an utterance's picks: the n_tokens emitted ones plus, when the utterance ended, the stop pick that follows them in
+    scores_row (WhisperSession.token_scores()[b]) -- OpenAI's sum_logprobs / (len + 1). Nothing summed (no id and no stop pick): 0.0."""
+    n = int(n_tokens) + int(bool(ended))
+    if n == 0:
+        return 0.0
+    row = np.asarray(scores_row, dtype=np.float64)
+    assert row.size >= n, (row.size, n)
+    return float(row[:n].sum() / n)
+
+
+def compression_ratio(text: str) -> float:
+    """len(utf8) / len(zlib.compress(utf8)): a transcript stuck in a repetition loop compresses far better than speech does."""
+    raw = text.encode("utf-8")
+    return len(raw) / len(zlib.compress(raw))
 
 
 class WhisperTranscriber:
@@ -215,9 +246,18 @@ class WhisperTranscriber:
                  use_sampling: bool = False, temperature: float = 0.8, top_k: int = 10, top_p: float = 0.95,
                  sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1,
                  timestamps: bool = False, max_initial_timestamp: float | None = 1.0, word_timestamps: bool = False, alignment_heads=None,
-                 medfilt_width: int = 7, piece_decoder=None):
+                 medfilt_width: int = 7, piece_decoder=None, token_scores: bool = False, temperature_fallback=None,
+                 compression_ratio_threshold: float | None = 2.4, logprob_threshold: float | None = -1.0):
         if beam_size > 1 and (float(repeat_penalty) != 1.0 or use_sampling):
             raise ValueError("beam_size > 1 does not combine with a repeat penalty or sampling")
+        # token scores / the temperature fallback (the build's own; thresholds are OpenAI's defaults, arguments and not measurements)
+        self.temperature_fallback = tuple(float(t) for t in temperature_fallback) if temperature_fallback else ()
+        self.token_scores = bool(token_scores) or bool(self.temperature_fallback)
+        if self.token_scores and beam_size > 1:
+            raise ValueError("token_scores / temperature_fallback need beam_size == 1: the beam search reports a score per hypothesis, not per token")
+        if any(t <= 0.0 for t in self.temperature_fallback):
+            raise ValueError("temperature_fallback: the temperatures after attempt 0 must be > 0")
+        self.compression_ratio_threshold, self.logprob_threshold = compression_ratio_threshold, logprob_threshold
         self.cfg, self.sess = cfg, session
         # word timestamps (the build's own): alignment_heads [(layer, head)] of the checkpoint (None: the upper half of the decoder layers, OpenAI's fallback);
         # piece_decoder(list of ids) -> str (a tokenizer's decode), when given, adds words next to token_times
@@ -256,33 +296,90 @@ class WhisperTranscriber:
             self.sess.set_timestamps(False)
         return self.sess.prefill(np.full((B, 1), self.cfg.sot_id, dtype=np.int32))[1]
 
-    def _prefill_and_continue(self, prompt: np.ndarray, limit: int, audio_samples=None, skip=None):
-        """The full-prompt prefill and the ids after it under the transcriber's head; timestamp mode is on from this prefill to the last id only.
-        -> (ids, frames). frames: per utterance (the aligned frames of its text tokens -- None: nothing aligned --, whether the ids ended with eot); with
-        word_timestamps they are captured live while the ids are generated, or by a forced pass when the ids carry timestamps or come from the beam search."""
+    def _prefill_and_continue(self, prompt: np.ndarray, limit: int, audio_samples=None, skip=None, sampling=None, align: bool = True):
+        """The full-prompt prefill and the ids after it under the transcriber's head (sampling: another sampler setting for this call, a fallback attempt);
+        timestamp mode and token scores are on from this prefill to the last id only.
+        -> (ids, frames, scores). frames: per utterance (the aligned frames of its text tokens -- None: nothing aligned --, whether the ids ended with eot); with
+        word_timestamps they are captured live while the ids are generated, or by a forced pass when the ids carry timestamps or come from the beam search
+        (align=False: neither, the caller aligns the ids it keeps). scores: sess.token_scores() of this decode, None with token_scores off."""
         B = prompt.shape[0]
-        live = self.word_timestamps and not self.timestamps and self.beam_size == 1 and limit > 0
+        live = self.word_timestamps and not self.timestamps and self.beam_size == 1 and limit > 0 and align
         frames = [(None, True)] * B
+        scores = None
         self.sess.set_penalty(self.repeat_penalty, self.penalty_range)
-        self.sess.set_sampling(*self.sampling)
+        self.sess.set_sampling(*(self.sampling if sampling is None else sampling))
         if self.timestamps:
             self.sess.set_timestamps(True, self.max_initial_index)
+        if self.token_scores:
+            self.sess.set_token_scores(True)
         if live:
             self.sess.set_word_timestamps(True, self.alignment_heads, limit + 1)
         try:
             self.sess.prefill(prompt, want_logits=False)
             toks = self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * B
+            if self.token_scores:
+                scores = self.sess.token_scores()
             if live:
                 ended = [len(t) < limit for t in toks]                # fewer ids than the limit: the utterance met eot, whose row was captured too
                 frames = self._align([len(t) + int(e) for t, e in zip(toks, ended)], ended, audio_samples, skip)
         finally:
             if self.timestamps:
                 self.sess.set_timestamps(False)
+            if self.token_scores:
+                self.sess.set_token_scores(False)
             if live:
                 self.sess.set_word_timestamps(False)
-        if self.word_timestamps and not live and limit > 0:
+        if self.word_timestamps and not live and limit > 0 and align:
             frames = self._forced_alignment(prompt, [self._text_ids(tk) for tk in toks], audio_samples, skip)
-        return toks, frames
+        return toks, frames, scores
+
+    def _quality(self, ids, scores_row, limit: int, temperature: float) -> dict:
+        """What token scores say about one utterance's decode: its picks' log-probabilities (one per id), avg_logprob (the stop pick included when the ids
+        ended before the limit, the rule _prefill_and_continue uses), the compression ratio of its text (None without a piece decoder), the temperature."""
+        n = len(ids)
+        ratio = compression_ratio(self.piece_decoder(self._text_ids(ids))) if self.piece_decoder is not None else None
+        return {"logprobs": np.asarray(scores_row[:n], dtype=np.float32), "avg_logprob": avg_logprob(scores_row, n, n < limit),
+                "compression_ratio": ratio, "temperature": float(temperature)}
+
+    def _needs_fallback(self, q: dict) -> bool:
+        """OpenAI's test: too repetitive (compression ratio, when it is known) or too unlikely (average log-probability)."""
+        if self.compression_ratio_threshold is not None and q["compression_ratio"] is not None and q["compression_ratio"] > self.compression_ratio_threshold:
+            return True
+        return self.logprob_threshold is not None and q["avg_logprob"] < self.logprob_threshold
+
+    def _decode(self, prompt: np.ndarray, limit: int, audio_samples=None, skip=None):
+        """What transcribe and transcribe_file share after the prompt is known -> (ids, frames, quality). quality: None with token_scores off, else one
+        _quality dict per utterance. With a temperature_fallback list, attempt 0 is the configured head; attempt k repeats the full-prompt prefill for the
+        whole batch (the encoder output and the cross-K/V stay, the prefill restarts the self-KV and both histories) and decodes with the sampler at the
+        list's k-th temperature and seed + k; only the utterances that still needed it take its result. A skipped utterance never needs one. The loop ends
+        when none needs one or the list is exhausted: the last attempt stands. Word timestamps then come from a forced pass over the ids that were kept."""
+        if not self.token_scores:
+            toks, frames, _ = self._prefill_and_continue(prompt, limit, audio_samples, skip)
+            return toks, frames, None
+        B = prompt.shape[0]
+        fallback = bool(self.temperature_fallback)
+        use, temperature, top_k, top_p, rep_penalty, seed = self.sampling
+        toks, quality, frames = [None] * B, [None] * B, [(None, True)] * B
+        need = [True] * B
+        try:
+            for k, t_k in enumerate((temperature if use else 0.0,) + self.temperature_fallback):
+                sampling = None if k == 0 else (True, t_k, top_k, top_p, rep_penalty, seed + k)
+                got, frames_k, scores = self._prefill_and_continue(prompt, limit, audio_samples, skip, sampling=sampling, align=not fallback)
+                if k == 0:
+                    frames = frames_k
+                for b in range(B):
+                    if need[b]:
+                        toks[b], quality[b] = got[b], self._quality(got[b], scores[b], limit, t_k)
+                        need[b] = fallback and not (skip is not None and skip[b]) and self._needs_fallback(quality[b])
+                if not any(need):
+                    break
+            if fallback and self.word_timestamps and limit > 0:
+                frames = self._forced_alignment(prompt, [self._text_ids(tk) for tk in toks], audio_samples, skip)
+        finally:
+            if fallback:                                         # the head is left as attempt 0 configured it
+                self.sess.set_penalty(self.repeat_penalty, self.penalty_range)
+                self.sess.set_sampling(*self.sampling)
+        return toks, frames, quality
 
     def _text_ids(self, ids):
         """The ids that carry text (and times): all of them behind <|notimestamps|>, the ones below the first timestamp id in timestamp mode."""
@@ -320,8 +417,8 @@ class WhisperTranscriber:
         finally:
             sess.set_word_timestamps(False)
 
-    def _token_times(self, aligned, text_ids, offset_s: float, window_s: float):
-        """token_times (and words) of one utterance's text ids from its entry of _prefill_and_continue's frames."""
+    def _token_times(self, aligned, text_ids, offset_s: float, window_s: float, logprobs=None):
+        """token_times (and words; with logprobs, one per text id, their probability) of one utterance's text ids from its entry of _prefill_and_continue's frames."""
         frames, ended = aligned
         n = len(text_ids)
         if frames is None:                                   # nothing aligned (no ids, or a single id cut off at the limit): the ids span the window
@@ -330,18 +427,23 @@ class WhisperTranscriber:
             times = token_times(frames[:n + 1] if ended else frames[:n], offset_s, None if ended else offset_s + window_s)
         out = {"token_times": times}
         if self.piece_decoder is not None:
-            out["words"] = word_times(decode_pieces(text_ids, self.piece_decoder), times)
+            out["words"] = word_times(decode_pieces(text_ids, self.piece_decoder), times, logprobs)
         return out
 
-    def _add_segment_times(self, segments, times, words_of=None):
+    def _add_segment_times(self, segments, times, words_of=None, logprobs=None):
         """Segments of timestamp mode gain token_times (and words) by token count."""
         at = 0
         for seg in segments:
             n = len(seg["tokens"])
             seg["token_times"] = times[at:at + n]
             if self.piece_decoder is not None:
-                seg["words"] = word_times(decode_pieces(seg["tokens"], self.piece_decoder), seg["token_times"])
+                seg["words"] = word_times(decode_pieces(seg["tokens"], self.piece_decoder), seg["token_times"],
+                                          None if logprobs is None else logprobs[at:at + n])
             at += n
+
+    def _text_logprobs(self, ids, logprobs):
+        """The scores of the ids that stay in `tokens`: all of them behind <|notimestamps|>, the text ids in timestamp mode."""
+        return np.asarray([lp for t, lp in zip(ids, logprobs) if not self.timestamps or t < self.ts_begin], dtype=np.float32)
 
     def _continue(self, limit: int):
         """Ids after the full-prompt prefill: greedy / penalty-greedy / sampling, or the first hypothesis of the beam search."""
@@ -370,22 +472,28 @@ class WhisperTranscriber:
         limit = max(0, cfg.max_target_positions - prompt.shape[1])
         if max_new is not None:
             limit = min(limit, max_new)
-        toks, aligned = self._prefill_and_continue(prompt, limit, [a.size for a in audios], skipped)
+        toks, aligned, quality = self._decode(prompt, limit, [a.size for a in audios], skipped)
         wall = time.time() - t0
         out = []
         for b in range(B):
             ids = [] if skipped[b] else toks[b].tolist()
             res = {"language_id": int(lang[b]), "no_speech_prob": float(probs[b]), "skipped": bool(skipped[b])}
+            lps = None
+            if quality is not None:
+                q = quality[b]
+                lps = self._text_logprobs(ids, q["logprobs"])
+                res.update(token_logprobs=lps, avg_logprob=0.0 if skipped[b] else q["avg_logprob"],
+                           compression_ratio=None if skipped[b] else q["compression_ratio"], temperature=q["temperature"])
             if self.timestamps:
                 res["segments"] = split_segments(ids, self.ts_begin, 0.0, audios[b].size / cfg.sample_rate)
                 ids = [t for t in ids if t < self.ts_begin]
-            elif self.remove_repeats and not self.word_timestamps:
+            elif self.remove_repeats and not self.word_timestamps and not self.token_scores:
                 ids = list(remove_repeated_parts(ids, 3, len(ids)))
             res["tokens"] = np.asarray(ids, dtype=np.int32)
             if self.word_timestamps:
-                res.update(self._token_times(aligned[b], ids, 0.0, audios[b].size / cfg.sample_rate))
+                res.update(self._token_times(aligned[b], ids, 0.0, audios[b].size / cfg.sample_rate, lps))
                 if self.timestamps:
-                    self._add_segment_times(res["segments"], res["token_times"])
+                    self._add_segment_times(res["segments"], res["token_times"], logprobs=lps)
             out.append(res)
         total_s = sum(a.size for a in audios) / cfg.sample_rate
         return out, {"rtf": wall / total_s, "wall_s": wall}
@@ -400,7 +508,10 @@ class WhisperTranscriber:
         prefill is evaluated for the batch but only window 0's row is read (the reference never probes a later window).
         Timestamp mode keeps these fixed, independently batched windows (no seek loop): window w's segments are offset by w * stride / sample_rate and
         an open last segment ends with its window; the result gains segments, tokens holds text ids only (windows keeps every id, timestamps
-        included) and the repeat guard is not applied."""
+        included) and the repeat guard is not applied.
+        With token_scores the result gains token_logprobs (the windows' scores concatenated as their ids are), avg_logprob (pooled over every pick of every
+        window), compression_ratio (of the whole text), temperature (the highest any window needed) and window_scores = per window
+        {"avg_logprob", "compression_ratio", "temperature"}: the fallback decides window by window, so these are the figures it acted on."""
         cfg = self.cfg
         raw = np.asarray(pcm_int16, dtype=np.int16).reshape(-1)
         audio_len = int(raw.size)
@@ -425,12 +536,13 @@ class WhisperTranscriber:
                 prob = float(self.sess.no_speech_prob(cfg.no_speech_id)[0])
                 no_speech = prob >= self.no_speech_threshold             # aborts the file (:801-805)
         windows: list[list[int]] = []
+        quality = None
         if not no_speech:
             prompt = np.tile(np.asarray([self._prompt(lang)], dtype=np.int32), (n_win, 1))
             limit = max(0, cfg.max_target_positions - prompt.shape[1])
             if max_new is not None:
                 limit = min(limit, max_new)
-            toks, frames_w = self._prefill_and_continue(prompt, limit, [min(window, max(1, audio_len - w * stride)) for w in range(n_win)])
+            toks, frames_w, quality = self._decode(prompt, limit, [min(window, max(1, audio_len - w * stride)) for w in range(n_win)])
             windows = [t.astype(int).tolist() for t in toks]
         wall = time.time() - t0
         ids = [t for w in windows for t in w]
@@ -440,15 +552,27 @@ class WhisperTranscriber:
             res["segments"] = [seg for w, win in enumerate(windows)
                                for seg in split_segments(win, self.ts_begin, w * stride / cfg.sample_rate, window / cfg.sample_rate)]
             ids = [t for t in ids if t < self.ts_begin]
-        elif self.remove_repeats and not self.word_timestamps:
+        elif self.remove_repeats and not self.word_timestamps and not self.token_scores:
             ids = list(remove_repeated_parts(ids, 3, len(ids)))
         res["tokens"] = np.asarray(ids, dtype=np.int32)
+        win_lps = None
+        if self.token_scores:
+            # the windows' scores concatenated as their ids are; avg_logprob pools every pick of every window, window_scores keeps each window's own figures
+            quality = quality or []
+            win_lps = [self._text_logprobs(win, q["logprobs"]) for win, q in zip(windows, quality)]
+            res["token_logprobs"] = np.concatenate(win_lps).astype(np.float32) if win_lps else np.zeros(0, np.float32)
+            picks = [len(win) + int(len(win) < limit) for win in windows]
+            res["avg_logprob"] = float(sum(q["avg_logprob"] * n for q, n in zip(quality, picks) if n) / max(1, sum(picks)))
+            res["compression_ratio"] = compression_ratio(self.piece_decoder(ids)) if self.piece_decoder is not None and windows else None
+            res["temperature"] = max((q["temperature"] for q in quality), default=0.0)
+            res["window_scores"] = [{k: q[k] for k in ("avg_logprob", "compression_ratio", "temperature")} for q in quality]
         if self.word_timestamps:                                        # per window, offset as the segments are; an open last token ends with its window
-            per = [self._token_times(frames_w[w], self._text_ids(win), w * stride / cfg.sample_rate, window / cfg.sample_rate)
+            per = [self._token_times(frames_w[w], self._text_ids(win), w * stride / cfg.sample_rate, window / cfg.sample_rate,
+                                     None if win_lps is None else win_lps[w])
                    for w, win in enumerate(windows)]
             res["token_times"] = [t for p in per for t in p["token_times"]]
             if self.piece_decoder is not None:
                 res["words"] = [x for p in per for x in p["words"]]
             if self.timestamps:
-                self._add_segment_times(res["segments"], res["token_times"])
+                self._add_segment_times(res["segments"], res["token_times"], logprobs=None if win_lps is None else res["token_logprobs"])
         return res, {"rtf": wall / max(audio_len / cfg.sample_rate, 1e-9), "wall_s": wall}

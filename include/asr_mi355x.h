@@ -266,6 +266,19 @@ int asr_whisper_set_sampling(asr_session* s, int enable, float temperature, int 
                              uint64_t seed);
 /* parity hook: the uniforms of the NEXT prefill / decode step, host [batch][top_k] (count = batch * top_k); consumed once. */
 int asr_whisper_set_sampling_noise(asr_session* s, const float* uniforms, int count);
+/* Token scores: the log-probability of every pick of the arg-max, penalty-greedy and sampling heads (the beam search keeps its hypothesis score). The
+ * reference reports none; the definition is the build's own, after OpenAI Whisper's `logprobs`: the natural-log soft-max, at the picked id, of the f32 logits
+ * row as the selection sees it over the vocabulary -- after the repeat penalty, the timestamp rules and the sampler's repetition penalty, plus BEGIN_SUPPRESS
+ * on the prefill step; temperature, top-k and top-p are not part of it. It is the log-soft-max of what logits_out of that step holds (+ BEGIN_SUPPRESS after a
+ * prefill). Logits are finite or -inf (masks); a row that holds +inf or NaN is outside the contract. A -inf column has zero weight; a pick whose own column is -inf, or a row without a column above -inf, scores -inf; never NaN. With enable != 0
+ * every pick also joins the device-side id history (as in timestamp mode), and the greedy pick and its score come out of one kernel; with enable = 0 no step
+ * launches anything new. Switch it before the prefill whose picks are wanted.
+ * asr_whisper_token_scores drains the stream and copies the scores of the picks since the last prefill, oldest first (column 0: the prefill's pick), to
+ * logprob_out host [batch][out_stride] -- min(count, out_stride) per sequence, slots past the count keep the caller's fill; *n_out = count. It works after
+ * asr_whisper_generate (count = 1 + decode steps run: the stop pick and whatever a finished sequence picked while others went on are included) and after
+ * hand-driven prefill / decode loops. Errors: the mode is off, or no prefill has run since it was switched on. */
+int asr_whisper_set_token_scores(asr_session* s, int enable);
+int asr_whisper_token_scores(asr_session* s, float* logprob_out, int out_stride, int32_t* n_out);
 /* Segment timestamps: OpenAI Whisper's ApplyTimestampRules inside the decode head. The reference has no timestamp mode (it defines NO_TIMESTAMPS_TOKEN and
  * always puts it in the prompt), so -- like the beam search -- this mode is the build's own. With enable != 0 the prompt carries no <|notimestamps|> and,
  * before every selection (arg-max, penalty-greedy after its penalty, sampling, every ranking of asr_whisper_beam_search), the f32 logits row of a sequence
@@ -351,6 +364,9 @@ int asr_qwen_set_penalty(asr_session* s, float repeat_penalty, int penalty_range
 int asr_qwen_track_history(asr_session* s, int enable);   /* like asr_whisper_track_history: the *_Penalty_Greedy graphs append every pick */
 int asr_qwen_set_sampling(asr_session* s, int enable, float temperature, int top_k, float top_p, float repetition_penalty, uint64_t seed);
 int asr_qwen_set_sampling_noise(asr_session* s, const float* uniforms, int count);
+/* token scores, as asr_whisper_set_token_scores / asr_whisper_token_scores (no bias on the prefill step here) */
+int asr_qwen_set_token_scores(asr_session* s, int enable);
+int asr_qwen_token_scores(asr_session* s, float* logprob_out, int out_stride, int32_t* n_out);
 /* continuation after a prefill with the selected head (:687-745): tokens_out host [B][max_new], n_out host [B]; a sequence ends at
  * the first id in stop_ids (not emitted) or when the cache is full. */
 int asr_qwen_generate(asr_session* s, int max_new, const int32_t* stop_ids, int n_stop, int32_t* tokens_out, int32_t* n_out);

@@ -153,7 +153,7 @@ typedef struct asr_probe_beam_select_desc {
 int asr_probe_beam_select(asr_probe_beam_select_desc* d);
 
 /* One call of a token-selection head through its product launcher on host arrays. op: 0 launch_argmax_rows, 1 launch_beam_topk, 2 launch_apply_penalty,
- * 3 launch_append_ids, 4 launch_sample_topk_topp, 5 launch_no_speech_prob, 7 launch_timestamp_rules; 6 "head steps", below. Rows keep their real leading dimension (ld, a multiple of 128, >= n_valid): the
+ * 3 launch_append_ids, 4 launch_sample_topk_topp, 5 launch_no_speech_prob, 7 launch_timestamp_rules, 8 / 9 the token-score kernels; 6 "head steps", below. Rows keep their real leading dimension (ld, a multiple of 128, >= n_valid): the
  * caller fills the pad columns, so a kernel that reads them shows. n_saved is put in device memory, as the sessions keep it; the logits, the whole save_ids
  * table and the counter come back as they stand after the call (penalty and sampler work in place). Fields an op does not use are ignored.
  * op 6 drives a TokenHead (csrc/decode_head.h) as a session does: configured from value / range / partial / ld_save / track_history (+ the sampler fields when
@@ -161,6 +161,10 @@ int asr_probe_beam_select(asr_probe_beam_select_desc* d);
  * penalty (a prefill), later steps without bias and with it (decode steps). `noise`, when set, is armed before step 0. Before step change_step (> 0) the penalty
  * is set to value2 / range2. With timestamps != 0 the head runs in Whisper's timestamp mode (ts_begin / no_timestamps_id / eot_id / max_initial). Out: picks
  * [steps][rows], save_ids (the final history table), n_saved_after (the counter); logits are not written back.
+ * ops 8 / 9 are the token-score kernels: 8 launch_argmax_logprob_rows (-> out_i [rows], uploaded as given), 9 launch_logprob_at_rows (ids = next_in [rows], any
+ * value); both write column n_saved of `logprob` [rows][ld_save] (the counter in device memory; n_saved >= ld_save writes nothing). op 6 with scores != 0 runs
+ * the head in scores mode and returns its score history in `logprob` (columns no step wrote are NaN); steps may then exceed ld_save when value == 1 and no
+ * change is scheduled (the overflow is dropped).
  * op 7 masks the logits in place by the history save_ids [rows][ld_save] and its length: n_saved for every row (one shared device counter), or n_saved_rows
  * [rows] when set (per-row counters, as the beam ranker keeps them). Every entry of the table must be a valid id. */
 typedef struct asr_probe_token_head_desc {
@@ -186,6 +190,10 @@ typedef struct asr_probe_token_head_desc {
   int32_t timestamps;        /* head steps (6): timestamp mode on */
   int32_t ts_begin, no_timestamps_id, eot_id, max_initial;   /* timestamp rules (6 7) */
   const int32_t* n_saved_rows;   /* [rows] per-row history lengths, or NULL: n_saved for all (7) */
+  int32_t scores;            /* head steps (6): token scores on */
+  float* logprob;            /* the score history [rows][ld_save]: in / out (8 9: uploaded as given, so what the kernel leaves alone comes back unchanged), out (6) */
+  int32_t timed;             /* head steps (6), plain arg-max head only: upload the rows once, run the steps' launches back to back between two device events */
+  float head_ms;             /* out (6, timed): the device time between the two events */
 } asr_probe_token_head_desc;
 int asr_probe_token_head(asr_probe_token_head_desc* d);
 

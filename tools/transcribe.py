@@ -57,6 +57,14 @@ def run(a) -> dict:
         raise SystemExit("--word-timestamps exists for --family whisper only")
     if timestamps and a.family not in ("sensevoice", "whisper"):
         raise SystemExit("--timestamps exists for --family sensevoice (per token) and --family whisper (per segment) only")
+    fallback = getattr(a, "temperature_fallback", None)
+    scores = bool(getattr(a, "token_scores", False)) or bool(fallback)
+    if fallback and a.family != "whisper":
+        raise SystemExit("--temperature-fallback exists for --family whisper only")
+    if scores and a.family not in ("whisper", "qwen_asr"):
+        raise SystemExit("--token-scores exists for --family whisper and --family qwen_asr only")
+    if scores and a.beam > 1:
+        raise SystemExit("--token-scores / --temperature-fallback need --beam 1 (the beam search reports a score per hypothesis)")
     files = []
     if a.family in ("sensevoice", "paraformer"):
         mod = _m(a.family)
@@ -92,7 +100,8 @@ def run(a) -> dict:
         heads = json.loads(info.get("metadata", {}).get("alignment_heads", "null")) if word_ts else None
         tr = _m("whisper").WhisperTranscriber(cfg, sess, suppress_tokens=ckm.whisper_suppress_tokens(cfg), detect_language=a.language == "auto",
                                               repeat_penalty=a.repeat_penalty, beam_size=a.beam, timestamps=timestamps, word_timestamps=word_ts,
-                                              alignment_heads=heads, piece_decoder=tok.decode if tok is not None and word_ts else None)
+                                              alignment_heads=heads, piece_decoder=tok.decode if tok is not None and (word_ts or scores) else None,
+                                              token_scores=scores, temperature_fallback=fallback)
         lang_id = None
         if a.language != "auto":
             if tok is None:
@@ -107,9 +116,12 @@ def run(a) -> dict:
             flat = r["tokens"].tolist() if timestamps else [t for w in ids for t in w]      # timestamp mode: the text ids, repeat guard not applied
             text = None
             if tok is not None:
-                text = "[no speech detected]" if r["no_speech"] else (whisper_text(tok, flat, remove_repeats=not (timestamps or word_ts)) if flat else "")
+                text = "[no speech detected]" if r["no_speech"] else (whisper_text(tok, flat, remove_repeats=not (timestamps or word_ts or scores)) if flat else "")
             files.append({"path": p, "n_samples": int(pcm.size), "language": a.language, "windows": ids, "text": text, "rtf": stat["rtf"],
                           "language_ids": [r["language_id"]] * len(ids), "no_speech_prob": [r["no_speech_prob"]], "no_speech": r["no_speech"]})
+            if scores:                      # the build's own mode: one log-probability per entry of r["tokens"], OpenAI's avg_logprob / compression ratio per file and per window
+                files[-1].update(tokens=r["tokens"].astype(int).tolist(), token_logprobs=[float(v) for v in r["token_logprobs"]], avg_logprob=r["avg_logprob"],
+                                 compression_ratio=r["compression_ratio"], temperature=r["temperature"], window_scores=r["window_scores"])
             if word_ts and not r["no_speech"]:          # the build's own mode: seconds from the file's start, one pair per text id; words with --tokenizer
                 files[-1]["token_times"] = [[float(s), float(e)] for s, e in r["token_times"]]
                 if "words" in r:
@@ -132,13 +144,16 @@ def run(a) -> dict:
         if a.tokenizer:
             from transformers import AutoTokenizer
             tok = AutoTokenizer.from_pretrained(a.tokenizer)
-        tr = _m("qwen_asr").QwenAsrTranscriber(cfg, sess, info["metadata"], tokenizer=tok, repeat_penalty=a.repeat_penalty, beam_size=a.beam)
+        tr = _m("qwen_asr").QwenAsrTranscriber(cfg, sess, info["metadata"], tokenizer=tok, repeat_penalty=a.repeat_penalty, beam_size=a.beam,
+                                               token_scores=scores)
         for p in a.wav:
             pcm = audio_io.read_wav_int16(p, cfg.sample_rate, exact_width=a.strict_wav)
             out, stat = tr.transcribe([pcm], language_prompts=("" if a.language == "auto" else a.language,))
             r = out[0]
             files.append({"path": p, "n_samples": int(pcm.size), "language": r.get("language") or a.language,
                           "windows": [np.asarray(r["tokens"]).astype(int).tolist()], "text": r.get("text"), "rtf": stat["rtf"]})
+            if scores:
+                files[-1].update(token_logprobs=[float(v) for v in r["token_logprobs"]], avg_logprob=r["avg_logprob"])
     else:
         raise SystemExit(a.family)
     return {"family": a.family, "precision": a.precision, "engine": "automatic-speech-recognition-asr-onnx_amd (MI355X)", "files": files}
@@ -200,6 +215,10 @@ def main():
                         "segments (start / end in seconds, token ids, text with --tokenizer)")
     r.add_argument("--word-timestamps", action="store_true", help="Whisper: add each text token's start / end in seconds (cross-attention DTW on the bundle's "
                         "alignment heads) to the dump; with --tokenizer also words, printed as they are found")
+    r.add_argument("--token-scores", action="store_true", help="Whisper, Qwen3-ASR: add each token's log-probability and the average (the stop pick included) to the "
+                        "dump; Whisper with --tokenizer also the compression ratio, and with --word-timestamps a probability per word")
+    r.add_argument("--temperature-fallback", type=float, nargs="+", metavar="T", help="Whisper: decode an utterance again by sampling at these temperatures, in "
+                        "order, while its average log-probability is below -1.0 or its compression ratio above 2.4 (e.g. 0.2 0.4 0.6 0.8 1.0); implies --token-scores")
     r.add_argument("--out", required=True)
     r.add_argument("--any-wav-width", dest="strict_wav", action="store_false",
                    help="accept 8 / 24 / 32-bit wav (rescaled to int16); by default only 16-bit wav is taken: the only width whose samples equal the reference's, "
