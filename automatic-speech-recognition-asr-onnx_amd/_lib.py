@@ -67,9 +67,11 @@ SIGNATURES = {
     "asr_sensevoice_seq_len": (_i, [C.POINTER(SenseVoiceConfigC), _i, C.POINTER(C.c_int)]),
     "asr_paraformer_create": (_i, [C.POINTER(ParaformerConfigC), _vp, _sz, _i, _i, _i, C.POINTER(_vp)]),
     "asr_paraformer_run": (_i, [_vp, _vp, _i, _lp, _i, _ip, _i, _ip]),
+    "asr_paraformer_run_timed": (_i, [_vp, _vp, _i, _lp, _i, _ip, _i, _ip, _ip, _fp]),
     "asr_paraformer_stream_create": (_i, [C.POINTER(ParaformerConfigC), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "asr_paraformer_stream_reset": (_i, [_vp, _i]),
     "asr_paraformer_stream_step": (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _ip]),
+    "asr_paraformer_stream_step_timed": (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _ip, _ip, _fp]),
     "asr_paraformer_stream_stats": (_i, [_vp, _ip]),
     "asr_whisper_create": (_i, [C.POINTER(WhisperConfigC), _vp, _sz, _i, _i, _i, C.POINTER(_vp)]),
     "asr_whisper_encode": (_i, [_vp, _vp, _i, _lp, _i, _ip]),
@@ -124,6 +126,7 @@ SIGNATURES = {
     "asr_op_gemm_ln": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
     "asr_op_ctc_collapse": (_i, [_ip, _ip, _i, _i, _ip, _i, _ip]),
     "asr_op_ctc_collapse_timed": (_i, [_ip, _fp, _ip, _i, _i, _ip, _ip, _ip, _fp, _i, _ip]),
+    "asr_op_cif_scan_timed": (_i, [_fp, _fp, _i, _ip, _i, C.c_float, _fp, _ip, _i, _ip]),
 }
 
 

@@ -441,6 +441,38 @@ extern "C" int asr_op_ctc_collapse_timed(const int32_t* frame_ids, const float* 
   });
 }
 
+extern "C" int asr_op_cif_scan_timed(const float* alpha, const float* enc, int d, const int32_t* seq_lens, int batch, float tail_threshold,
+                                     float* acoustic_out, int32_t* fire_frame_out, int max_tokens, int32_t* num_id_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(alpha && enc && seq_lens && acoustic_out && fire_frame_out && num_id_out && batch > 0 && d > 0 && max_tokens > 0, "op_cif_scan_timed: bad argument");
+    asr_require_device(0);
+    Tmp t;
+    PackedPlan pp(seq_lens, batch);
+    std::vector<float> aa, ea;
+    to_aligned(pp, seq_lens, batch, 1, alpha, aa);
+    to_aligned(pp, seq_lens, batch, d, enc, ea);
+    const size_t fire_bytes = (size_t)batch * max_tokens * 4;
+    float* dalpha = (float*)t.alloc((size_t)pp.Mpad * 4);
+    float* denc = (float*)t.alloc((size_t)pp.Mpad * d * 4);
+    float* dac = (float*)t.alloc((size_t)pp.Mpad * d * 4);
+    UttPlan* dplan = (UttPlan*)t.alloc(sizeof(UttPlan) * batch);
+    UttPlan* dtplan = (UttPlan*)t.alloc(sizeof(UttPlan) * batch);
+    int32_t* dfire = (int32_t*)t.alloc(fire_bytes);
+    int32_t* dnum = (int32_t*)t.alloc((size_t)batch * 4);
+    HIP_CHECK(hipMemcpy(dalpha, aa.data(), (size_t)pp.Mpad * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(denc, ea.data(), (size_t)pp.Mpad * d * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dplan, pp.plan.data(), sizeof(UttPlan) * batch, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dfire, fire_frame_out, fire_bytes, hipMemcpyHostToDevice));      // slots the kernel leaves alone come back as they were
+    launch_cif_scan_timed(dalpha, denc, d, dplan, batch, tail_threshold, dac, dtplan, dnum, dfire, max_tokens, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<float> oa((size_t)pp.Mpad * d);
+    HIP_CHECK(hipMemcpy(oa.data(), dac, oa.size() * 4, hipMemcpyDeviceToHost));
+    from_aligned(pp, seq_lens, batch, d, oa, acoustic_out);
+    HIP_CHECK(hipMemcpy(fire_frame_out, dfire, fire_bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(num_id_out, dnum, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 extern "C" int asr_op_gemm_ln(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, int M, int N,
                               int K, float* out) {
   return asr_guard([&] {

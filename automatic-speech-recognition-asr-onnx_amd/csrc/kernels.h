@@ -362,6 +362,11 @@ void launch_alpha(const T* h, int d, const float* w, const float* b, int rows, f
 // DEVICE-side token plan (row_off, T = max(N,1), n_lfr = N) so the decoder needs no host round trip.
 void launch_cif_scan(const float* alpha, const float* enc_out, int d, const UttPlan* plan, int n_utts, float tail_threshold,
                      float* acoustic, UttPlan* token_plan, int32_t* num_id, hipStream_t s);
+// ... the same scan (every output above bit-identical) that also records where each token fired: fire_frame[u * max_tokens + k] = the row t in [0, T] at
+// which floor((float)prefix sum) rose for token k (t == T: the tail threshold fired it behind the last row). Tokens at or past max_tokens are dropped;
+// num_id keeps the full count.
+void launch_cif_scan_timed(const float* alpha, const float* enc_out, int d, const UttPlan* plan, int n_utts, float tail_threshold,
+                           float* acoustic, UttPlan* token_plan, int32_t* num_id, int32_t* fire_frame, int max_tokens, hipStream_t s);
 // out[t] = res[t] + depth-wise conv (k taps, zero padded inside the token sequence) of x, all row-major f32
 void launch_fsmn_rows(const float* x, const float* res, const float* w, int d, int ktaps, const UttPlan* token_plan,
                       const int32_t* row_utt, int n_rows, float* out, hipStream_t s, const int32_t* rows_dev = nullptr);
@@ -373,6 +378,8 @@ void launch_token_compact(const UttPlan* own_plan, int n_utts, int n_rows_max, U
 void launch_compact_rows(const float* src, const UttPlan* own_plan, const UttPlan* compact_plan, int n_utts, int d, float* dst, hipStream_t s);
 // token_ids[b][i] = ids[row_off_b + i], i < N_b
 void launch_gather_tokens(const int32_t* ids, const UttPlan* token_plan, int n_utts, int32_t* token_ids, int max_tokens, hipStream_t s);
+// token_logprob[b][i] = row_logprob[row_off_b + i], i < N_b (the dummy row of a zero-token utterance is never read)
+void launch_gather_token_logprob(const float* row_logprob, const UttPlan* token_plan, int n_utts, float* token_logprob, int max_tokens, hipStream_t s);
 
 
 // ---- streaming Paraformer (Paraformer/Streaming/Export_Paraformer_Streaming.py:386-553). Every active stream owns a 16-row slot
@@ -413,6 +420,11 @@ void launch_stream_fsmn(const T* v, int ld_v, int v_col0, const float* w, const 
 // unrolled integrate-and-fire over rows [0, n_int) of every slot with the carried (hidden, alphas) (:438-462)
 void launch_stream_cif(const float* alpha, const float* enc, int d, const UttPlan* plan, int n_active, int n_int, float* cif_hidden,
                        float* cif_alphas, float* frames_out, UttPlan* token_plan, int32_t* num, hipStream_t s);
+// ... that also records the integration step of every fire: fire_step[i * max_tokens + k] = t in [0, n_int), or -1 for the entry fire in front of the loop
+// (the carried weight had already reached 1). Every other output is bit-identical.
+void launch_stream_cif_timed(const float* alpha, const float* enc, int d, const UttPlan* plan, int n_active, int n_int, float* cif_hidden,
+                             float* cif_alphas, float* frames_out, UttPlan* token_plan, int32_t* num, int32_t* fire_step, int max_tokens,
+                             hipStream_t s);
 // decoder FSMN over [hist | tokens] (valid conv, identity folded into the LAST tap) + residual; history advances when tokens exist
 void launch_stream_dec_fsmn(const float* x, const float* res, const float* w, int d, int ktaps, const UttPlan* token_plan, int n_active,
                             float* hist, float* out, hipStream_t s);

@@ -1640,8 +1640,11 @@ __global__ __launch_bounds__(256) void alpha_kernel(const T* __restrict__ h, int
   if (lane == 0) alpha[m] = 1.0f / (1.0f + expf(-(acc + b[0])));
 }
 
+// TIMED: the thread that writes the token plan also records the row t at which each token fired (t == T: the tail threshold fired it after the last row)
+template <bool TIMED>
 __global__ void cif_scan_kernel(const float* __restrict__ alpha, const float* __restrict__ enc, int d, const UttPlan* __restrict__ plan,
-                                float tail, float* __restrict__ acoustic, UttPlan* __restrict__ tplan, int32_t* __restrict__ num_id) {
+                                float tail, float* __restrict__ acoustic, UttPlan* __restrict__ tplan, int32_t* __restrict__ num_id,
+                                int32_t* __restrict__ fire_frame, int max_tokens) {
   const int u = blockIdx.x;
   const UttPlan up = plan[u];
   const int T = up.T, row0 = up.row_off;
@@ -1660,6 +1663,9 @@ __global__ void cif_scan_kernel(const float* __restrict__ alpha, const float* __
         const float completed = __fsub_rn(hsum, __fmul_rn(p32 - fl, hv));
         if (k < rows16) acoustic[(size_t)(row0 + k) * d + c] = completed - prev_completed;
         prev_completed = completed;
+        if constexpr (TIMED) {
+          if (c == 0 && k < max_tokens) fire_frame[(size_t)u * max_tokens + k] = t;
+        }
         ++k;
       }
       prev_floor = fl;
@@ -1735,6 +1741,14 @@ __global__ void gather_tokens_kernel(const int32_t* __restrict__ ids, const UttP
   const int u = blockIdx.x;
   const int n = min(tplan[u].n_lfr, max_tokens);
   for (int i = threadIdx.x; i < n; i += blockDim.x) token_ids[(size_t)u * max_tokens + i] = ids[tplan[u].row_off + i];
+}
+
+// the same gather for a per-row score (n_lfr = 0: the zero-token utterance's dummy row yields nothing)
+__global__ void gather_token_logprob_kernel(const float* __restrict__ row_logprob, const UttPlan* __restrict__ tplan,
+                                            float* __restrict__ token_logprob, int max_tokens) {
+  const int u = blockIdx.x;
+  const int n = min(tplan[u].n_lfr, max_tokens);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) token_logprob[(size_t)u * max_tokens + i] = row_logprob[tplan[u].row_off + i];
 }
 
 }  // namespace
@@ -2423,8 +2437,16 @@ template void launch_alpha<bf16_t>(const bf16_t*, int, const float*, const float
 
 void launch_cif_scan(const float* alpha, const float* enc_out, int d, const UttPlan* plan, int n_utts, float tail_threshold,
                      float* acoustic, UttPlan* token_plan, int32_t* num_id, hipStream_t s) {
-  hipLaunchKernelGGL(cif_scan_kernel, dim3(n_utts), dim3(std::min(1024, (d + 63) / 64 * 64)), 0, s, alpha, enc_out, d, plan, tail_threshold,
-                     acoustic, token_plan, num_id);
+  hipLaunchKernelGGL(cif_scan_kernel<false>, dim3(n_utts), dim3(std::min(1024, (d + 63) / 64 * 64)), 0, s, alpha, enc_out, d, plan, tail_threshold,
+                     acoustic, token_plan, num_id, nullptr, 0);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_cif_scan_timed(const float* alpha, const float* enc_out, int d, const UttPlan* plan, int n_utts, float tail_threshold,
+                           float* acoustic, UttPlan* token_plan, int32_t* num_id, int32_t* fire_frame, int max_tokens, hipStream_t s) {
+  ASR_REQUIRE(fire_frame && max_tokens >= 1, "cif_scan_timed: fire_frame / max_tokens %d", max_tokens);
+  hipLaunchKernelGGL(cif_scan_kernel<true>, dim3(n_utts), dim3(std::min(1024, (d + 63) / 64 * 64)), 0, s, alpha, enc_out, d, plan, tail_threshold,
+                     acoustic, token_plan, num_id, fire_frame, max_tokens);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2447,6 +2469,11 @@ void launch_compact_rows(const float* src, const UttPlan* own_plan, const UttPla
 
 void launch_gather_tokens(const int32_t* ids, const UttPlan* token_plan, int n_utts, int32_t* token_ids, int max_tokens, hipStream_t s) {
   hipLaunchKernelGGL(gather_tokens_kernel, dim3(n_utts), dim3(256), 0, s, ids, token_plan, token_ids, max_tokens);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_gather_token_logprob(const float* row_logprob, const UttPlan* token_plan, int n_utts, float* token_logprob, int max_tokens, hipStream_t s) {
+  hipLaunchKernelGGL(gather_token_logprob_kernel, dim3(n_utts), dim3(256), 0, s, row_logprob, token_plan, token_logprob, max_tokens);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2703,10 +2730,13 @@ __global__ __launch_bounds__(256) void stream_fsmn_kernel(const T* __restrict__ 
   }
 }
 
+// TIMED: thread 0 also records the integration step of every fire (-1: the entry fire in front of the loop)
+template <bool TIMED>
 __global__ __launch_bounds__(256) void stream_cif_kernel(const float* __restrict__ alpha, const float* __restrict__ enc, int d,
                                                          const UttPlan* __restrict__ plan, int n_int, float* __restrict__ cif_hidden,
                                                          float* __restrict__ cif_alphas, float* __restrict__ frames_out,
-                                                         UttPlan* __restrict__ token_plan, int32_t* __restrict__ num) {
+                                                         UttPlan* __restrict__ token_plan, int32_t* __restrict__ num,
+                                                         int32_t* __restrict__ fire_step, int max_tokens) {
   const int i = blockIdx.x, sid = plan[i].lang, row0 = plan[i].row_off;
   const float ca0 = cif_alphas[sid];
   int n_fired = 0;
@@ -2718,7 +2748,12 @@ __global__ __launch_bounds__(256) void stream_cif_kernel(const float* __restrict
     float cond_a = ca < 1.0f ? 1.0f : 0.0f, cond_b = 1.0f - cond_a;
     float frames = ca * ch * cond_a + ch * cond_b;
     float listed = frames;                                 // last entry of the reference's list_frame (fired or not)
-    if (cond_b != 0.0f) frames_out[(size_t)(row0 + k++) * d + c] = frames;
+    if (cond_b != 0.0f) {
+      if constexpr (TIMED) {
+        if (c == 0 && k < max_tokens) fire_step[(size_t)i * max_tokens + k] = -1;
+      }
+      frames_out[(size_t)(row0 + k++) * d + c] = frames;
+    }
     ca -= cond_b;
     frames = frames * cond_a + ca * ch * cond_b;
     for (int t = 0; t < n_int; ++t) {
@@ -2728,7 +2763,12 @@ __global__ __launch_bounds__(256) void stream_cif_kernel(const float* __restrict
       cond_b = 1.0f - cond_a;
       frames = (frames + al * hid) * cond_a + (frames + thr * hid) * cond_b;
       listed = frames;
-      if (cond_b != 0.0f) frames_out[(size_t)(row0 + k++) * d + c] = frames;
+      if (cond_b != 0.0f) {
+        if constexpr (TIMED) {
+          if (c == 0 && k < max_tokens) fire_step[(size_t)i * max_tokens + k] = t;
+        }
+        frames_out[(size_t)(row0 + k++) * d + c] = frames;
+      }
       ca = ca + al;
       ca -= cond_b;
       frames = frames * cond_a + ca * hid * cond_b;
@@ -2833,8 +2873,17 @@ template void launch_stream_fsmn<bf16_t>(const bf16_t*, int, int, const float*, 
 void launch_stream_cif(const float* alpha, const float* enc, int d, const UttPlan* plan, int n_active, int n_int, float* cif_hidden,
                        float* cif_alphas, float* frames_out, UttPlan* token_plan, int32_t* num, hipStream_t s) {
   ASR_REQUIRE(n_int + 1 <= 16, "stream_cif: %d frames per chunk exceed the 16-row slot", n_int + 1);
-  hipLaunchKernelGGL(stream_cif_kernel, dim3(n_active), dim3(256), 0, s, alpha, enc, d, plan, n_int, cif_hidden, cif_alphas, frames_out,
-                     token_plan, num);
+  hipLaunchKernelGGL(stream_cif_kernel<false>, dim3(n_active), dim3(256), 0, s, alpha, enc, d, plan, n_int, cif_hidden, cif_alphas, frames_out,
+                     token_plan, num, nullptr, 0);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_stream_cif_timed(const float* alpha, const float* enc, int d, const UttPlan* plan, int n_active, int n_int, float* cif_hidden,
+                             float* cif_alphas, float* frames_out, UttPlan* token_plan, int32_t* num, int32_t* fire_step, int max_tokens,
+                             hipStream_t s) {
+  ASR_REQUIRE(n_int + 1 <= 16 && fire_step && max_tokens >= 1, "stream_cif_timed: %d frames per chunk, max_tokens %d", n_int + 1, max_tokens);
+  hipLaunchKernelGGL(stream_cif_kernel<true>, dim3(n_active), dim3(256), 0, s, alpha, enc, d, plan, n_int, cif_hidden, cif_alphas, frames_out,
+                     token_plan, num, fire_step, max_tokens);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -57,6 +57,7 @@ struct SvSession : asr_session {
   DeviceBuffer d_plan, d_audio, d_mel, d_x0, d_xa, d_xb, d_h, d_qk, d_vt, d_ctx, d_mem, d_ffn, d_amax_v, d_amax_i, d_ids,
       d_tok, d_num, d_logits;
   DeviceBuffer d_amax_s, d_flp, d_first, d_last, d_tlp;   // timed runs only: sum-of-exponentials partials, frame log-probabilities, token spans and scores
+                                                          // (Paraformer: row log-probabilities in d_flp, fire rows / steps in d_first, token log-probabilities in d_tlp)
   PinnedBuffer h_plan, h_out;   // pinned staging
 
   // ---- streaming Paraformer (kind 4): per-stream recurrent state in HBM, every step advances n streams by one chunk
@@ -85,8 +86,10 @@ struct SvSession : asr_session {
   void ensure_stream_shadow();
   void stream_init(int chunk, int look_back_encoder, int look_back_decoder, int max_streams);
   void stream_reset(int sid);
+  // fire_out / logprob_out set: the timed form (asr_paraformer_stream_step_timed)
   template <typename T> void stream_step(const void* audio, int audio_mem, const int32_t* stream_ids, int n, int32_t* tok_out, int max_tokens,
-                                         int32_t* num_out);
+                                         int32_t* num_out, int32_t* fire_out = nullptr, float* logprob_out = nullptr);
+  DeviceBuffer st_zero;                 // a device counter that stays 0: the timed step's head saves each row's score at column 0 (launch_argmax_logprob_rows)
   bool use_graph = true;
   bool use_ln_alg = true;       // LayerNorm evaluated inside the projections from row statistics (ASR_LN_FUSED=0 disables)
   bool use_fused = true;        // fused q|k|v + attention + FSMN kernel for windows of <= 144 rows (ASR_SANM_FUSED=0 disables)
@@ -134,13 +137,16 @@ struct SvSession : asr_session {
   DeviceBuffer d_times; int block_dbg = -1;   // ASR_SANM_BLOCK_DBG=<block index>: phase clock of that block's launch on stderr
   DeviceBuffer d_flags;         // exchange counters of the block kernel: [n_blocks][batch][4] + the error word at the end
   StepGraph graph;              // hipGraph replay of the forward pass (one graph per batch geometry)
+  StepGraph graph_timed;        // ... of the timed forms, so that a caller who alternates the two forms replays both
   uint64_t ws_epoch = 1;
   StepGraph st_graph[3];        // streaming chunk step: per-launch / fused / fused + snapshot
+  StepGraph st_graph_timed[3];  // ... of the timed step
 
   void init();
   void copy_block_status(const struct SvRunCtx& r);   // the block kernel's error word rides home behind the token counts
   template <typename T> void enqueue(const struct SvRunCtx& r);
-  // first_out / last_out / logprob_out all set: the timed form (asr_sensevoice_run_timed) -- the CTC head also yields each token's frame span and score
+  // first_out / last_out / logprob_out all set: the timed form (asr_sensevoice_run_timed) -- the CTC head also yields each token's frame span and score.
+  // Paraformer sessions (asr_paraformer_run_timed): first_out = the CIF fire rows, logprob_out = the token log-probabilities, no last_out.
   template <typename T> void run(const void* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang,
                                  int32_t* tok_out, int max_tokens, int32_t* num_out, int32_t* first_out = nullptr, int32_t* last_out = nullptr,
                                  float* logprob_out = nullptr);
@@ -634,7 +640,11 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
     launch_alpha<T>(ctx, d, cif_out_w, cif_out_b, rows, d_alpha.as<float>(), stream);
     // fired frames land in the utterance's own rows first; then they are packed (16-row aligned per utterance) so that the decoder
     // touches ~ the token count of the batch instead of every encoder row -- the count stays on the device (GemmArgs::m_dev)
-    launch_cif_scan(d_alpha.as<float>(), enc32, d, r.dp, r.batch, pcfg.tail_threshold, x2_own, own_plan, d_num.as<int32_t>(), stream);
+    if (r.timed)
+      launch_cif_scan_timed(d_alpha.as<float>(), enc32, d, r.dp, r.batch, pcfg.tail_threshold, x2_own, own_plan, d_num.as<int32_t>(), d_first.as<int32_t>(),
+                            r.max_tokens, stream);
+    else
+      launch_cif_scan(d_alpha.as<float>(), enc32, d, r.dp, r.batch, pcfg.tail_threshold, x2_own, own_plan, d_num.as<int32_t>(), stream);
     launch_token_compact(own_plan, r.batch, Mpad, tplan, d_trow.as<int32_t>(), d_mdev.as<int32_t>(), stream);
     launch_compact_rows(x2_own, own_plan, tplan, r.batch, d, dec, stream);
   }
@@ -714,15 +724,35 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
     GemmArgs g;
     g.A = h; g.lda = d; g.W = pf_out_w; g.ldw = d; g.M = rows; g.N = vpad; g.K = d; g.bias = pf_out_b;
     g.amax_val = d_amax_v.as<float>(); g.amax_idx = d_amax_i.as<int32_t>(); g.n_valid = c.vocab; g.m_dev = m_dev;
+    if (r.timed) g.amax_sum = d_amax_s.as<float>();         // (rows at or past *m_dev are neither computed nor stored: the epilogue's row guard uses the device-side count)
     if (taps_enabled) { g.out_f32 = d_logits.as<float>(); g.ld_out_f32 = vpad; }
     gemm(g);
-    launch_argmax_reduce(d_amax_v.as<float>(), d_amax_i.as<int32_t>(), rows, n_slabs, d_ids.as<int32_t>(), stream);
-    launch_gather_tokens(d_ids.as<int32_t>(), tplan, r.batch, d_tok.as<int32_t>(), r.max_tokens, stream);
+    if (r.timed) {
+      // reduce rows at or past the device-side token-row count merge partials nobody wrote: they hold nothing defined and the gathers below, which walk
+      // the token plan, never read them
+      launch_argmax_lse_reduce(d_amax_v.as<float>(), d_amax_i.as<int32_t>(), d_amax_s.as<float>(), rows, n_slabs, d_ids.as<int32_t>(), d_flp.as<float>(), stream);
+      launch_gather_tokens(d_ids.as<int32_t>(), tplan, r.batch, d_tok.as<int32_t>(), r.max_tokens, stream);
+      launch_gather_token_logprob(d_flp.as<float>(), tplan, r.batch, d_tlp.as<float>(), r.max_tokens, stream);
+    } else {
+      launch_argmax_reduce(d_amax_v.as<float>(), d_amax_i.as<int32_t>(), rows, n_slabs, d_ids.as<int32_t>(), stream);
+      launch_gather_tokens(d_ids.as<int32_t>(), tplan, r.batch, d_tok.as<int32_t>(), r.max_tokens, stream);
+    }
   }
-  if (taps_enabled) save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
-  HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, (size_t)r.batch * r.max_tokens * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)r.batch * r.max_tokens * 4, d_num.ptr, (size_t)r.batch * 4,
-                           hipMemcpyDeviceToHost, stream));
+  if (taps_enabled) {
+    save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
+    if (r.timed) {
+      save_tap("fire_frames", d_first.ptr, r.batch, r.max_tokens, r.max_tokens, 4);
+      save_tap("token_logprob", d_tlp.ptr, r.batch, r.max_tokens, r.max_tokens, 4);
+    }
+  }
+  const size_t tok_bytes = (size_t)r.batch * r.max_tokens * 4;
+  HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + tok_bytes, d_num.ptr, (size_t)r.batch * 4, hipMemcpyDeviceToHost, stream));
+  if (r.timed) {                                          // fire rows and scores ride behind the existing outputs, in the slots of the timed CTC tail's first_frame / token_logprob
+    unsigned char* ext = h_out.as<unsigned char>() + tok_bytes + (size_t)r.batch * 4 + 16;
+    HIP_CHECK(hipMemcpyAsync(ext, d_first.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(ext + 2 * tok_bytes, d_tlp.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+  }
 }
 
 template <typename T>
@@ -730,7 +760,7 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
                     int max_tokens, int32_t* num_out, int32_t* first_out, int32_t* last_out, float* logprob_out) {
   const auto& c = cfg;
   const bool timed = first_out != nullptr;
-  ASR_REQUIRE(!timed || (last_out && logprob_out && !paraformer), "sensevoice: the timed form needs all three span outputs (CTC sessions only)");
+  ASR_REQUIRE(!timed || (logprob_out && (paraformer ? !last_out : last_out != nullptr)), "sensevoice: the timed form needs all of its outputs");
   ASR_REQUIRE(batch > 0, "sensevoice: empty batch");
   ASR_REQUIRE(audio && offs && (lang || paraformer) && tok_out && num_out, "sensevoice: null argument");
   HIP_CHECK(hipSetDevice(device));
@@ -867,7 +897,7 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   if (tiles) ensure_tiles_pack();
   // ---- launch: eager the first time a geometry is seen (allocations settle), then capture once and replay ----
   // 570 launches per forward are host-launch-bound when issued eagerly (~13 us each); replay costs ~1 us per node.
-  graph.run(stream, use_graph && !taps_enabled && !prof.enabled, key.h, [&] { enqueue<T>(r); });
+  (timed ? graph_timed : graph).run(stream, use_graph && !taps_enabled && !prof.enabled, key.h, [&] { enqueue<T>(r); });
   HIP_CHECK(hipStreamSynchronize(stream));
   if (prof.enabled) prof.collect();
   if (tiles_dbg >= 0 && tiles && d_times.ptr) {          // tuning: mean phase intervals of one block of the tile kernel over its workgroups (100 MHz clock -> us)
@@ -946,7 +976,7 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
     for (int b = 0; b < batch; ++b) {
       const size_t n = (size_t)std::min(num_out[b], max_tokens) * 4, o = (size_t)b * max_tokens * 4;
       memcpy((unsigned char*)first_out + o, ext + o, n);
-      memcpy((unsigned char*)last_out + o, ext + tok_bytes + o, n);
+      if (last_out) memcpy((unsigned char*)last_out + o, ext + tok_bytes + o, n);
       memcpy((unsigned char*)logprob_out + o, ext + 2 * tok_bytes + o, n);
     }
   }
@@ -1091,7 +1121,7 @@ void SvSession::stream_reset(int sid) {
 
 template <typename T>
 void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* stream_ids, int n, int32_t* tok_out, int max_tokens,
-                            int32_t* num_out) {
+                            int32_t* num_out, int32_t* fire_out, float* logprob_out) {
   const auto& c = cfg;
   ASR_REQUIRE(st_max > 0, "streaming: session was not created with asr_paraformer_stream_create");
   ASR_REQUIRE(audio && stream_ids && tok_out && num_out && n >= 1 && n <= st_max && max_tokens >= st_B + 1, "streaming: bad argument (n = %d)", n);
@@ -1099,6 +1129,8 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
   ClusterScope cluster(device);                          // (as in run(): fused = cluster kernels; a foreign section open on this GPU sends the step down the per-launch path)
   foreign_now = !cluster.ok;
   if (foreign_now) ++foreign_diverted;
+  const bool timed = fire_out != nullptr;
+  ASR_REQUIRE(!timed || logprob_out, "streaming: the timed step needs both of its outputs");
   const int d = c.d_model, dff = c.d_ffn, dd = pcfg.d_dec_ffn, H = c.n_heads, n_cur = st_B + st_C;
   const int rows = n * 16, Mpad = round_up(rows, 128), frames = n * st_frames, n_slabs = vpad / 64;
   std::vector<char> seen(st_max, 0);
@@ -1148,12 +1180,21 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
   grow(d_sa, (size_t)Mpad * d * 4);
   grow(d_ffn32, (size_t)Mpad * dd * 4);
   grow(d_tplan, sizeof(UttPlan) * n);
+  if (timed) {
+    if (!st_zero.ptr) {                                 // made by the first timed step: a session that never asks for times allocates what it always did
+      st_zero.reserve(256, stream);
+      HIP_CHECK(hipMemsetAsync(st_zero.ptr, 0, 256, stream));
+    }
+    grow(d_flp, (size_t)Mpad * 4);
+    grow(d_first, (size_t)n * max_tokens * 4);
+    grow(d_tlp, (size_t)n * max_tokens * 4);
+  }
   if (precision == ASR_PRECISION_BF16) {                // LayerNorm inside the per-launch layers' projections (see the layer loop): bf16 copies of the residual stream + their row statistics
     grow(d_xblo, (size_t)Mpad * d * 2);
     grow(d_stb, (size_t)Mpad * (d / 32) * 8);
   }
-  const size_t out_bytes = (size_t)n * max_tokens * 4 + (size_t)n * 4;
-  h_out.reserve(out_bytes + 16);
+  const size_t tok_bytes = (size_t)n * max_tokens * 4, out_bytes = tok_bytes + (size_t)n * 4;
+  h_out.reserve(out_bytes + 16 + (timed ? 2 * tok_bytes : 0));        // (timed: fire steps and scores behind the error word)
   pb.upload(stream);
   // ---- which path this step takes (see the comment at st_fused_max)
   bool step_fused = st_fused && std::is_same<T, bf16_t>::value && n <= st_fused_max && st_cooldown == 0 && !foreign_now;
@@ -1320,7 +1361,11 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
     g.out_lo = ctx; g.ld_out_lo = d;
     gemm(g);
     launch_alpha<T>(ctx, d, cif_out_w, cif_out_b, rows, d_alpha.as<float>(), stream);
-    launch_stream_cif(d_alpha.as<float>(), enc32, d, dp, n, st_B, st_cifh.as<float>(), st_cifa.as<float>(), dec, tplan, d_num.as<int32_t>(), stream);
+    if (timed)
+      launch_stream_cif_timed(d_alpha.as<float>(), enc32, d, dp, n, st_B, st_cifh.as<float>(), st_cifa.as<float>(), dec, tplan, d_num.as<int32_t>(),
+                              d_first.as<int32_t>(), max_tokens, stream);
+    else
+      launch_stream_cif(d_alpha.as<float>(), enc32, d, dp, n, st_B, st_cifh.as<float>(), st_cifa.as<float>(), dec, tplan, d_num.as<int32_t>(), stream);
   }
   save_tap("alphas", d_alpha.ptr, rows, 1, 1, 4);
   save_tap("list_frame", dec, rows, d, d, 4);
@@ -1402,8 +1447,14 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
     GemmArgs g;
     g.A = h; g.lda = d; g.W = pf_out_w; g.ldw = d; g.M = rows; g.N = vpad; g.K = d; g.bias = pf_out_b; g.out_f32 = d_logits.as<float>(); g.ld_out_f32 = vpad;
     gemm(g);
-    launch_argmax_rows(d_logits.as<float>(), vpad, rows, c.vocab, nullptr, d_ids.as<int32_t>(), stream);
-    launch_gather_tokens(d_ids.as<int32_t>(), tplan, n, d_tok.as<int32_t>(), max_tokens, stream);
+    if (timed) {                                        // the pick and its score in one kernel (ids equal launch_argmax_rows' bit for bit); one score per row: column 0 of a 1-wide history
+      launch_argmax_logprob_rows(d_logits.as<float>(), vpad, rows, c.vocab, nullptr, d_ids.as<int32_t>(), d_flp.as<float>(), 1, st_zero.as<int32_t>(), stream);
+      launch_gather_tokens(d_ids.as<int32_t>(), tplan, n, d_tok.as<int32_t>(), max_tokens, stream);
+      launch_gather_token_logprob(d_flp.as<float>(), tplan, n, d_tlp.as<float>(), max_tokens, stream);
+    } else {
+      launch_argmax_rows(d_logits.as<float>(), vpad, rows, c.vocab, nullptr, d_ids.as<int32_t>(), stream);
+      launch_gather_tokens(d_ids.as<int32_t>(), tplan, n, d_tok.as<int32_t>(), max_tokens, stream);
+    }
   }
   launch_stream_advance(dp, tplan, n, st_B, st_en_cap, n_cur, st_de_cap, st_enlen.as<int32_t>(), st_delen.as<int32_t>(), stream);
   };
@@ -1417,12 +1468,27 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
                           (const void*)(uintptr_t)max_tokens, (const void*)st_shadow.ptr, (const void*)d_xblo.ptr, (const void*)d_stb.ptr})
       key.mix(q);
     key.mix((uint64_t)audio_dtype);                                 // the front end is inside the captured step
+    key.mix((uint64_t)timed);                                       // the timed step is another launch sequence ...
+    if (timed) for (const void* q : {(const void*)d_flp.ptr, (const void*)d_first.ptr, (const void*)d_tlp.ptr}) key.mix(q);     // ... over three more buffers
     const int gi = step_fused ? (snapshot ? 2 : 1) : 0;            // one cached graph per path: a session that alternates (a co-tenant comes and goes) does not re-capture
-    st_graph[gi].run(stream, use_graph && !taps_enabled && !prof.enabled && !inject_fault, key.h, enqueue);
+    (timed ? st_graph_timed : st_graph)[gi].run(stream, use_graph && !taps_enabled && !prof.enabled && !inject_fault, key.h, enqueue);
   }
-  if (taps_enabled) save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
-  HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, (size_t)n * max_tokens * 4, hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)n * max_tokens * 4, d_num.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+  if (taps_enabled) {
+    save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
+    if (timed) {
+      save_tap("fire_frames", d_first.ptr, n, max_tokens, max_tokens, 4);
+      save_tap("token_logprob", d_tlp.ptr, n, max_tokens, max_tokens, 4);
+    }
+  }
+  auto copy_out = [&]() {
+    HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + tok_bytes, d_num.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    if (timed) {
+      HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + out_bytes + 16, d_first.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + out_bytes + 16 + tok_bytes, d_tlp.ptr, tok_bytes, hipMemcpyDeviceToHost, stream));
+    }
+  };
+  copy_out();
   const bool fused_ran = step_fused;
   unsigned* h_err = (unsigned*)(h_out.as<unsigned char>() + out_bytes);
   *h_err = 0;
@@ -1457,8 +1523,7 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
     launch_stream_state_copy(st_segs.as<StreamStateSeg>(), st_n_segs, st_n_items, dp, n, true, stream);
     step_fused = false; snapshot = false;
     enqueue();
-    HIP_CHECK(hipMemcpyAsync(h_out.ptr, d_tok.ptr, (size_t)n * max_tokens * 4, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)n * max_tokens * 4, d_num.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+    copy_out();                                          // (the redone step's outputs, the timed ones included)
     HIP_CHECK(hipStreamSynchronize(stream));
     if (prof.enabled) prof.collect();
     *h_err = 0;
@@ -1468,6 +1533,14 @@ void SvSession::stream_step(const void* audio, int audio_mem, const int32_t* str
   memcpy(num_out, h_out.as<unsigned char>() + (size_t)n * max_tokens * 4, (size_t)n * 4);
   const int32_t* ht = h_out.as<const int32_t>();
   for (int i = 0; i < n; ++i) memcpy(tok_out + (size_t)i * max_tokens, ht + (size_t)i * max_tokens, (size_t)std::min(num_out[i], max_tokens) * 4);
+  if (timed) {
+    const unsigned char* ext = h_out.as<const unsigned char>() + out_bytes + 16;
+    for (int i = 0; i < n; ++i) {
+      const size_t nb = (size_t)std::min(num_out[i], max_tokens) * 4, o = (size_t)i * max_tokens * 4;
+      memcpy((unsigned char*)fire_out + o, ext + o, nb);
+      memcpy((unsigned char*)logprob_out + o, ext + tok_bytes + o, nb);
+    }
+  }
 }
 
 }  // namespace
@@ -1602,6 +1675,20 @@ extern "C" int asr_paraformer_stream_step(asr_session* s, const void* audio, int
   });
 }
 
+extern "C" int asr_paraformer_stream_step_timed(asr_session* s, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams,
+                                                int32_t* token_ids_out, int max_tokens, int32_t* num_id_out, int32_t* fire_step_out, float* logprob_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 4, "paraformer_stream_step_timed: not a streaming Paraformer session");
+    ASR_REQUIRE(fire_step_out && logprob_out, "paraformer_stream_step_timed: null timed output");
+    TenantScope tenant(s);
+    SvSession* sv = static_cast<SvSession*>(s);
+    if (sv->precision == ASR_PRECISION_BF16)
+      sv->stream_step<bf16_t>(audio, audio_mem, stream_ids, n_streams, token_ids_out, max_tokens, num_id_out, fire_step_out, logprob_out);
+    else
+      sv->stream_step<float>(audio, audio_mem, stream_ids, n_streams, token_ids_out, max_tokens, num_id_out, fire_step_out, logprob_out);
+  });
+}
+
 extern "C" int asr_paraformer_stream_stats(asr_session* s, int32_t* out8) {
   return asr_guard([&] {
     ASR_REQUIRE(s && s->kind == 4 && out8, "paraformer_stream_stats: not a streaming Paraformer session");
@@ -1630,5 +1717,19 @@ extern "C" int asr_paraformer_run(asr_session* s, const void* audio, int audio_m
       sv->run<bf16_t>(audio, audio_mem, audio_offsets, batch, nullptr, token_ids_out, max_tokens, num_id_out);
     else
       sv->run<float>(audio, audio_mem, audio_offsets, batch, nullptr, token_ids_out, max_tokens, num_id_out);
+  });
+}
+
+extern "C" int asr_paraformer_run_timed(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+                                        int32_t* token_ids_out, int max_tokens, int32_t* num_id_out, int32_t* fire_frame_out, float* logprob_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 3, "paraformer_run_timed: not a Paraformer session");
+    ASR_REQUIRE(fire_frame_out && logprob_out, "paraformer_run_timed: null timed output");
+    TenantScope tenant(s);
+    SvSession* sv = static_cast<SvSession*>(s);
+    if (sv->precision == ASR_PRECISION_BF16)
+      sv->run<bf16_t>(audio, audio_mem, audio_offsets, batch, nullptr, token_ids_out, max_tokens, num_id_out, fire_frame_out, nullptr, logprob_out);
+    else
+      sv->run<float>(audio, audio_mem, audio_offsets, batch, nullptr, token_ids_out, max_tokens, num_id_out, fire_frame_out, nullptr, logprob_out);
   });
 }

@@ -312,6 +312,21 @@ def op_ctc_collapse_timed(frame_ids, frame_logprob, seq_lens, blank_id=0, max_to
     return tok, first, last, tlp, num
 
 
+def op_cif_scan_timed(alpha, enc, seq_lens, tail_threshold, max_tokens=None, fill=0):
+    """The CIF scan with fire rows on host arrays (asr_op_cif_scan_timed). alpha [sum T], enc [sum T, d]. Returns (acoustic [sum T, d], fire_frame
+    [B, max_tokens] int32, num_id [B]): fire_frame starts out holding `fill`, which slots the kernel does not write keep; num_id holds the full count."""
+    al, en = _f32(alpha).reshape(-1), _f32(enc)
+    sl = np.ascontiguousarray(seq_lens, dtype=np.int32)
+    assert al.size == en.shape[0] == int(sl.sum())
+    max_t = int(sl.max()) + 1 if max_tokens is None else int(max_tokens)
+    ac = np.zeros_like(en)
+    fire = np.full((sl.size, max_t), fill, dtype=np.int32)
+    num = np.zeros((sl.size,), dtype=np.int32)
+    _lib.check(_lib.load().asr_op_cif_scan_timed(_fp(al), _fp(en), en.shape[1], _ip(sl), sl.size, float(tail_threshold), _fp(ac), _ip(fire), max_t,
+                                                 _ip(num)))
+    return ac, fire, num
+
+
 def op_gemm_bench(M, N, K, variant=-1, epilogue=0, iters=50) -> float:
     """Tuning hook (probe library, not the product ABI): average milliseconds per launch of the bf16 GEMM."""
     from . import _probe
@@ -599,6 +614,33 @@ class ParaformerSession(_Session):
         tok, num = self.run_packed(packed, offs)
         return [tok[b, :num[b]].copy() for b in range(len(flat))]
 
+    def run_packed_timed(self, audio, offsets, audio_device_ptr: int | None = None):
+        """run_packed with the CIF fire row and the log-probability of every token (asr_paraformer_run_timed). Returns (token_ids, num_id, fire_frame,
+        logprob): the two new arrays are [B, max_T] like token_ids (int32, float32), row b valid up to num_id[b]. fire_frame is the utterance's LFR row
+        at which the token fired, in [0, T]; T means the tail threshold fired it behind the last row (paraformer.token_times maps rows to seconds)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        B = offsets.size - 1
+        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        tok = np.zeros((B, max_t), dtype=np.int32)
+        fire = np.zeros((B, max_t), dtype=np.int32)
+        logprob = np.zeros((B, max_t), dtype=np.float32)
+        num = np.zeros((B,), dtype=np.int32)
+        if audio_device_ptr is not None:
+            ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
+        else:
+            audio = self._audio(audio).reshape(-1)
+            ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
+        _lib.check(_lib.load().asr_paraformer_run_timed(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(tok), max_t, _ip(num),
+                                                        _ip(fire), _fp(logprob)))
+        return tok, num, fire, logprob
+
+    def run_timed(self, audios: Sequence[np.ndarray]):
+        """List of 1-D utterances -> one record per utterance: {"ids", "fire_frame", "logprob"}, arrays of equal length."""
+        flat, packed, offs = self._pack(audios)
+        tok, num, fire, logprob = self.run_packed_timed(packed, offs)
+        return [{"ids": tok[b, :num[b]].copy(), "fire_frame": fire[b, :num[b]].copy(), "logprob": logprob[b, :num[b]].copy()}
+                for b in range(len(flat))]
+
     def utterance_rows(self, lengths: Sequence[int]):
         out, r = [], 0
         for n in lengths:
@@ -618,6 +660,14 @@ class ParaformerSession(_Session):
         return out
 
 
+def stream_absolute_rows(fire_step, chunk_index: int, rows_new: int, rows_carried: int) -> np.ndarray:
+    """Integration step t of a stream's chunk_index-th chunk since its reset -> the stream's absolute LFR row chunk_index * B + t - C (B new and C
+    carried rows per step: a step integrates the C carried rows, then the first B - C new ones; t = -1 is the previous chunk's last integrated row).
+    Rows in front of the stream's first one (the zero rows carried into chunk 0) clip to 0."""
+    rows = int(chunk_index) * int(rows_new) + np.asarray(fire_step, dtype=np.int64) - int(rows_carried)
+    return np.maximum(rows, 0)
+
+
 class ParaformerStreamSession(_Session):
     """Streaming Paraformer: per-stream recurrent state (encoder K/V histories, carried LFR rows, CIF state, decoder FSMN / cross
     K/V histories) lives in the session; `step` advances a set of streams by one chunk (Export_Paraformer_Streaming.py:386-553)."""
@@ -633,6 +683,8 @@ class ParaformerStreamSession(_Session):
         self.cfg, self.precision, self.chunk, self.max_streams = cfg, precision, int(chunk), int(max_streams)
         n_frames = (chunk - cfg.win_length) // cfg.hop_length + 1
         self.rows_per_chunk = ((cfg.lfr_m - 1) // 2 + n_frames) // cfg.lfr_n + 1
+        self.rows_carried = self.rows_per_chunk // 2                      # rows carried into the next step (the session's st_C)
+        self.chunks_done = np.zeros(int(max_streams), dtype=np.int64)     # timed steps: chunks of each stream since its reset
         blob = build_paraformer_arena(cfg, ck_or_arena, precision, streaming=True) if isinstance(ck_or_arena, dict) else ck_or_arena
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         c = _lib.ParaformerConfigC()
@@ -647,6 +699,10 @@ class ParaformerStreamSession(_Session):
 
     def reset(self, stream_id: int = -1):
         _lib.check(_lib.load().asr_paraformer_stream_reset(self._h, int(stream_id)))
+        if stream_id < 0:
+            self.chunks_done[:] = 0
+        else:
+            self.chunks_done[int(stream_id)] = 0
 
     def step(self, chunks, stream_ids, audio_device_ptr: int | None = None):
         """chunks: (n, chunk) int16-range samples of the session's audio_dtype (or None with `audio_device_ptr`: HBM-resident [n][chunk]); stream_ids: n
@@ -661,7 +717,32 @@ class ParaformerStreamSession(_Session):
         tok = np.zeros((sid.size, cap), dtype=np.int32)
         num = np.zeros(sid.size, dtype=np.int32)
         _lib.check(_lib.load().asr_paraformer_stream_step(self._h, ap, mem, _ip(sid), sid.size, _ip(tok), cap, _ip(num)))
+        self.chunks_done[sid] += 1
         return [tok[i, :num[i]].copy() for i in range(sid.size)]
+
+    def absolute_rows(self, fire_step, chunk_index: int) -> np.ndarray:
+        return stream_absolute_rows(fire_step, chunk_index, self.rows_per_chunk, self.rows_carried)
+
+    def step_timed(self, chunks, stream_ids, audio_device_ptr: int | None = None):
+        """`step` with the fire step and the log-probability of every token (asr_paraformer_stream_step_timed) -> one record per stream:
+        {"ids", "fire_step", "row", "logprob"}; "row" is the stream's absolute LFR row of the fire (absolute_rows: the session counts each stream's chunks
+        since its reset, over `step` and `step_timed` alike)."""
+        sid = np.ascontiguousarray(stream_ids, dtype=np.int32)
+        if audio_device_ptr is not None:
+            ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
+        else:
+            a = self._audio(chunks).reshape(sid.size, self.chunk)
+            ap, mem = a.ctypes.data_as(C.c_void_p), MEM_HOST
+        cap = self.rows_per_chunk + 1
+        tok = np.zeros((sid.size, cap), dtype=np.int32)
+        fire = np.zeros((sid.size, cap), dtype=np.int32)
+        logprob = np.zeros((sid.size, cap), dtype=np.float32)
+        num = np.zeros(sid.size, dtype=np.int32)
+        _lib.check(_lib.load().asr_paraformer_stream_step_timed(self._h, ap, mem, _ip(sid), sid.size, _ip(tok), cap, _ip(num), _ip(fire), _fp(logprob)))
+        rows = np.maximum(self.chunks_done[sid][:, None] * self.rows_per_chunk + fire - self.rows_carried, 0)      # stream_absolute_rows, every stream at once
+        self.chunks_done[sid] += 1
+        return [{"ids": tok[i, :n].copy(), "fire_step": fire[i, :n].copy(), "row": rows[i, :n].copy(), "logprob": logprob[i, :n].copy()}
+                for i, n in enumerate(num)]
 
     def stream_stats(self) -> dict:
         """Which path the chunk steps took (asr_paraformer_stream_stats): give-ups recovered, steps moved to the per-launch path because the GPU was shared,

@@ -5,6 +5,7 @@
   build_tokenizer_metadata() = :136-159 (blank/eos/stop ids by token role, one artefact language with its decode mode)
   decode_tokens()       = Inference_Paraformer_ONNX.py:86-89 ("en": BPE "@@ " joins; otherwise plain concatenation)
   transcribe()          = :236-297 (window/pad, one pre-bound audio buffer updated in place, per-window run, stop ids stripped)
+  token_times()         the build's own rule (no reference counterpart): CIF fire rows -> a (start, end) per token
 prepare_audio_input / plan_windows are the SenseVoice ones (identical code in the reference, :62-84, :243-259).
 """
 from __future__ import annotations
@@ -67,6 +68,23 @@ def decode_tokens(tokens: Sequence[str], mode: str) -> str:
     return "".join(tokens).strip()
 
 
+def token_times(fire_frame, n_rows: int, row_seconds: float, max_token_rows: int = 4) -> np.ndarray:
+    """CIF fire rows of one utterance -> [n, 2] float64 (start, end) in seconds from the utterance's first sample. The build's own rule -- the reference
+    returns ids only. Token k ends behind the row that fired it, min(fire_k + 1, n_rows) rows in (a tail fire, fire_k == n_rows, ends with the last row);
+    it starts at the later of the previous token's end (0 for the first token) and end - max_token_rows. A token is thus the interval over which CIF
+    integrated it, capped so that silence in front of it is not charged to it. The cap's default, 4 rows (0.24 s at 60 ms rows), is an assumption: it
+    follows the 12 frames of 20 ms of FunASR's CIF timestamp rule as remembered, not as read from a file."""
+    fire = np.asarray(fire_frame, dtype=np.int64).reshape(-1)
+    out = np.zeros((fire.size, 2), dtype=np.float64)
+    prev_end = 0
+    for k, f in enumerate(fire):
+        end = max(min(int(f) + 1, int(n_rows)), prev_end)
+        start = max(prev_end, end - int(max_token_rows))
+        out[k] = (start * row_seconds, end * row_seconds)
+        prev_end = end
+    return out
+
+
 class ParaformerTranscriber:
     def __init__(self, model_folder: str, vocab_path: str | None = None, device_id: int = 0, device_type: str = "cpu"):
         opts = onnxruntime.SessionOptions()
@@ -93,8 +111,22 @@ class ParaformerTranscriber:
         with open(vocab_path or os.path.join(model_folder, "Vocab_Paraformer.txt"), "r", encoding="UTF-8") as f:
             self.tokenizer = np.array([line.rstrip("\n") for line in f], dtype=np.str_)
 
-    def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False):
-        """int16 mono PCM at `sample_rate` -> dict(token_ids per window, text, rtf, windows)."""
+    def _run_window_timed(self, win: np.ndarray, offset_s: float, duration_s: float, max_token_rows: int):
+        """One window through the native session under the shim session (the graph's two outputs carry no times): (token ids as the graph returns them,
+        one record per token with the window's offset added and both ends clipped to the audio's duration)."""
+        native = self.session._native
+        cfg = native.cfg
+        tok, num, fire, logprob = native.run_packed_timed(win.reshape(-1), np.array([0, win.size], dtype=np.int64))
+        n = int(num[0])
+        spans = token_times(fire[0, :n], cfg.seq_len(win.size), cfg.lfr_n * cfg.hop_length / cfg.sample_rate, max_token_rows)
+        tokens = [{"id": int(tok[0, k]), "text": str(self.tokenizer[tok[0, k]]), "start": min(offset_s + float(spans[k, 0]), duration_s),
+                   "end": min(offset_s + float(spans[k, 1]), duration_s), "logprob": float(logprob[0, k])} for k in range(n)]
+        return tok[0, :n].copy(), tokens
+
+    def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False, timestamps: bool = False, max_token_rows: int = 4):
+        """int16 mono PCM at `sample_rate` -> dict(token_ids per window, text, rtf, windows). timestamps=True adds "tokens": one {"id", "text", "start",
+        "end", "logprob"} per kept token over all windows, in seconds of the whole audio (token_times over the CIF fire rows; logprob = log soft-max of the
+        decoder head at the pick); records of stop ids are dropped with their ids."""
         audio_len = int(np.asarray(audio_int16).size)
         audio = prepare_audio_input(np.asarray(audio_int16, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype,
                                     audio_pcm_scale=self.audio_pcm_scale, normalise=normalise)
@@ -107,20 +139,28 @@ class ParaformerTranscriber:
         audio_buffer = onnxruntime.OrtValue.ortvalue_from_numpy(
             filled_for(self.audio_meta, axes={0: 1, 1: 1, 2: window}), self.device_type, self.device_id)
         binding.bind_ortvalue_input(self.audio_meta.name, audio_buffer)
-        ids_all, pieces = [], []
+        ids_all, pieces, tokens_all = [], [], []
         start, end = 0, window
         t0 = time.time()
         while end <= aligned:
-            audio_buffer.update_inplace(array_for(self.audio_meta, audio[:, :, start:end], axes={0: 1, 1: 1, 2: window}))
-            for name in self.out_names:                                         # data-dependent token count: re-arm per window
-                binding._iobinding.bind_output(name, self.ort_device)
-            self.session.run_with_iobinding(binding, run_options=self.run_options)
-            token_ids = binding.get_outputs()[0].numpy().reshape(-1)
+            win = array_for(self.audio_meta, audio[:, :, start:end], axes={0: 1, 1: 1, 2: window})
+            if timestamps:
+                token_ids, toks = self._run_window_timed(win, start / self.sample_rate, audio_len / self.sample_rate, max_token_rows)
+                tokens_all.extend(t for t in toks if t["id"] not in self.stop_token_ids)
+            else:
+                audio_buffer.update_inplace(win)
+                for name in self.out_names:                                     # data-dependent token count: re-arm per window
+                    binding._iobinding.bind_output(name, self.ort_device)
+                self.session.run_with_iobinding(binding, run_options=self.run_options)
+                token_ids = binding.get_outputs()[0].numpy().reshape(-1)
             token_ids = token_ids[~np.isin(token_ids, self.stop_token_ids)]
             ids_all.append(token_ids.copy())
             pieces.extend(self.tokenizer[token_ids].tolist())
             start += stride
             end = start + window
         wall = time.time() - t0
-        return {"token_ids": ids_all, "text": decode_tokens(pieces, self.decode_mode), "rtf": wall / (audio_len / self.sample_rate),
-                "windows": len(ids_all), "language": self.language}
+        out = {"token_ids": ids_all, "text": decode_tokens(pieces, self.decode_mode), "rtf": wall / (audio_len / self.sample_rate),
+               "windows": len(ids_all), "language": self.language}
+        if timestamps:
+            out["tokens"] = tokens_all
+        return out

@@ -14,7 +14,7 @@ from typing import Sequence
 
 import numpy as np
 
-from .paraformer import decode_tokens
+from .paraformer import decode_tokens, token_times
 from .engine import audio_dtype_name
 from .sensevoice import prepare_audio_input
 
@@ -49,8 +49,11 @@ class ParaformerStreamTranscriber:
         """"INT16" | "F32" | "F16": the type of the session's `audio` input (the reference reads it off the graph, Inference_Paraformer_Streaming_ONNX.py prepare_audio_input)."""
         return audio_dtype_name(self.sess.audio_dtype)
 
-    def transcribe_many(self, clips_int16: Sequence[np.ndarray], rng: np.random.Generator | None = None):
-        """Concurrent streams, one per clip (<= session.max_streams). Returns per clip dict(text, pieces, token_ids), and stats."""
+    def transcribe_many(self, clips_int16: Sequence[np.ndarray], rng: np.random.Generator | None = None, timestamps: bool = False,
+                        max_token_rows: int = 4):
+        """Concurrent streams, one per clip (<= session.max_streams). Returns per clip dict(text, pieces, token_ids), and stats. timestamps=True takes the
+        timed step and adds "tokens" per clip: one {"id", "text", "start", "end", "logprob"} per kept token, in seconds of the clip (paraformer.token_times
+        over the stream's absolute fire rows, ends clipped to the clip's duration); records of stop ids are dropped with their ids."""
         chunk = self.sess.chunk
         prepared = [pad_to_chunks(prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype, audio_pcm_scale=self.audio_pcm_scale),
                                   chunk, rng)[0, 0] for c in clips_int16]
@@ -59,11 +62,19 @@ class ParaformerStreamTranscriber:
         for i in ids:
             self.sess.reset(i)
         out = [dict(pieces=[], token_ids=[]) for _ in prepared]
+        timed = [dict(ids=[], rows=[], logprob=[]) for _ in prepared]
         rtfs = []
         for k in range(max(n_chunks)):
             live = [i for i in ids if k < n_chunks[i]]
             t0 = time.time()
-            fired = self.sess.step(np.stack([prepared[i][k * chunk:(k + 1) * chunk] for i in live]), live)
+            block = np.stack([prepared[i][k * chunk:(k + 1) * chunk] for i in live])
+            if timestamps:
+                recs = self.sess.step_timed(block, live)
+                fired = [r["ids"] for r in recs]
+                for i, r in zip(live, recs):
+                    timed[i]["ids"].append(r["ids"]); timed[i]["rows"].append(r["row"]); timed[i]["logprob"].append(r["logprob"])
+            else:
+                fired = self.sess.step(block, live)
             rtfs.append((time.time() - t0) / (chunk / self.sample_rate))
             for i, tok in zip(live, fired):
                 if tok.size:                                    # the decoder ran for this stream
@@ -73,6 +84,16 @@ class ParaformerStreamTranscriber:
         for o in out:
             o["text"] = "".join(o["pieces"])
             o["token_ids"] = np.concatenate(o["token_ids"]) if o["token_ids"] else np.zeros(0, np.int32)
+        if timestamps:
+            cfg = self.sess.cfg
+            row_s = cfg.lfr_n * cfg.hop_length / cfg.sample_rate
+            for o, t, clip, n in zip(out, timed, clips_int16, n_chunks):
+                ids, rows, lps = (np.concatenate(t[k]) if t[k] else np.zeros(0) for k in ("ids", "rows", "logprob"))
+                dur = np.asarray(clip).size / self.sample_rate
+                n_rows = n * self.sess.rows_per_chunk - self.sess.rows_carried          # rows integrated by the clip's last step
+                spans = token_times(rows, n_rows, row_s, max_token_rows)
+                o["tokens"] = [{"id": int(i), "text": str(self.tokens[int(i)]), "start": min(float(s), dur), "end": min(float(e), dur), "logprob": float(lp)}
+                               for i, (s, e), lp in zip(ids, spans, lps) if int(i) not in self.stop]
         return out, {"rtf_per_chunk": rtfs, "chunks": max(n_chunks)}
 
     def transcribe(self, audio_int16: np.ndarray, rng: np.random.Generator | None = None):

@@ -166,6 +166,15 @@ int asr_paraformer_create(const asr_paraformer_config* cfg, const void* arena, s
  * (num_id is the CIF fire count; an utterance can legitimately yield zero tokens). */
 int asr_paraformer_run(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                        int32_t* token_ids_out, int max_tokens, int32_t* num_id_out);
+/* The same forward pass with the row at which the CIF predictor fired each token and the token's log-probability (no reference counterpart: the reference
+ * graph returns ids only, Export_Paraformer.py:600-606). Fire rule (:505-507): the alphas of the utterance's T rows, then the tail threshold as row T, are
+ * summed in float64; after each row the running sum is rounded ONCE to f32 and floored, and a token fires at the row t where that floor rises.
+ * fire_frame_out[b][k] = t of token k, in [0, T] and strictly increasing; t == T means the tail threshold fired the token behind the last row (the value is
+ * kept: the caller clips). Rows are the utterance's LFR rows, there are no prompt rows: row j covers samples [j lfr_n hop_length, (j + 1) lfr_n hop_length).
+ * logprob_out[b][k] = natural-log soft-max of the decoder head's logits row of token k at its arg-max (<= 0). Both arrays are host [B][max_tokens] with the
+ * row contract of token_ids_out (row b holds min(num_id_out[b], max_tokens) entries, the rest untouched). Token ids and counts equal asr_paraformer_run's. */
+int asr_paraformer_run_timed(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+                             int32_t* token_ids_out, int max_tokens, int32_t* num_id_out, int32_t* fire_frame_out, float* logprob_out);
 
 /* Streaming Paraformer: replaces Paraformer_Streaming_Encoder.onnx + Paraformer_Streaming_Decoder.onnx (PARAFORMER_ENCODER /
  * PARAFORMER_DECODER, Paraformer/Streaming/Export_Paraformer_Streaming.py:330-553) and the state shuttling of
@@ -182,6 +191,17 @@ int asr_paraformer_stream_create(const asr_paraformer_config* cfg, const void* a
 int asr_paraformer_stream_reset(asr_session* s, int stream_id);      /* -1 = every stream: empty histories, zero CIF state */
 int asr_paraformer_stream_step(asr_session* s, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams,
                                int32_t* token_ids_out, int max_tokens, int32_t* num_id_out);
+/* The same step with the integration step at which each token fired and the token's log-probability (the build's own mode, as asr_paraformer_run_timed).
+ * A step integrates B rows -- the C rows carried from the previous chunk, then the first B - C of its B new rows (B, C = LFR rows per chunk and its half:
+ * 9 and 4 at the reference's chunk; Export_Paraformer_Streaming.py:398-399, 447-458) -- in f32, firing where the carried weight plus the row's alpha reaches 1.
+ * fire_step_out[i][k] = that step t in [0, B), or -1 for a token fired in front of the loop because the weight carried in had already reached 1 (:440-446):
+ * it belongs to the previous chunk's last integrated row. For the stream's c-th chunk since its reset (c = 0, 1, ..) step t is the absolute LFR row
+ * c B + t - C of the stream (negative for the zero rows in front of the first chunk); absolute row j covers samples [j lfr_n hop_length, (j + 1) lfr_n hop_length)
+ * up to the front end's window centring. logprob_out[i][k] = natural-log soft-max of the token's logits row at its arg-max. Both arrays are host
+ * [n_streams][max_tokens], row i holds num_id_out[i] entries, the rest untouched. Ids and counts equal asr_paraformer_stream_step's; the two forms may be mixed
+ * freely on one session. */
+int asr_paraformer_stream_step_timed(asr_session* s, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams,
+                                     int32_t* token_ids_out, int max_tokens, int32_t* num_id_out, int32_t* fire_step_out, float* logprob_out);
 /* Which path the chunk steps of a streaming session took (no reference counterpart: the reference runs one stream per InferenceSession and has no
  * co-tenancy to manage). A bf16 step runs the encoder / decoder layer loops as two cluster launches when (i) no more than fused_max streams are active,
  * (ii) no other session of this process is computing on the same GPU (otherwise the per-launch path, which leaves CUs to the other tenant and waits on nobody);
@@ -424,7 +444,7 @@ int asr_session_profile_read(asr_session* s, int cap, char* names, double* total
 
 /* Debug taps (the reference's decode graphs expose no logits; the 1e-3 logit check needs one).
  * enable before a run; read copies the named f32 tensor of the LAST run to host.
- * names: "mel" "enc_in" "block0" "enc_out" "logits" "frame_ids"(i32) */
+ * names: "mel" "enc_in" "block0" "enc_out" "logits" "frame_ids"(i32); timed Paraformer runs add "fire_frames"(i32) "token_logprob" ([utterances][max_tokens]) */
 int asr_session_taps_enable(asr_session* s, int enable);
 int asr_session_tap_shape(asr_session* s, const char* name, int64_t* rows, int64_t* cols);
 int asr_session_tap_read(asr_session* s, const char* name, void* host_out, size_t bytes);
@@ -449,6 +469,11 @@ int asr_op_ctc_collapse(const int32_t* frame_ids, const int32_t* seq_lens, int b
  * [batch][max_tokens] (slots at or past the token count, or past max_tokens, are not written) */
 int asr_op_ctc_collapse_timed(const int32_t* frame_ids, const float* frame_logprob, const int32_t* seq_lens, int batch, int blank_id,
                               int32_t* token_ids, int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, int32_t* num_id);
+/* the CIF scan of asr_paraformer_run_timed on host arrays: alpha [sum T], enc [sum T][d], seq_lens [batch] (each >= 1); acoustic_out [sum T][d] receives, per
+ * utterance, its token embeddings in its first rows and zeros behind them (tokens past row T - 1 of a 16-row-padded range are not returned);
+ * fire_frame_out host [batch][max_tokens] (slots at or past the token count, or past max_tokens, are not written); num_id_out [batch] holds the full count */
+int asr_op_cif_scan_timed(const float* alpha, const float* enc, int d, const int32_t* seq_lens, int batch, float tail_threshold, float* acoustic_out,
+                          int32_t* fire_frame_out, int max_tokens, int32_t* num_id_out);
 
 #ifdef __cplusplus
 }

@@ -55,8 +55,11 @@ def run(a) -> dict:
     word_ts = getattr(a, "word_timestamps", False)
     if word_ts and a.family != "whisper":
         raise SystemExit("--word-timestamps exists for --family whisper only")
-    if timestamps and a.family not in ("sensevoice", "whisper"):
-        raise SystemExit("--timestamps exists for --family sensevoice (per token) and --family whisper (per segment) only")
+    if timestamps and a.family not in ("sensevoice", "paraformer", "whisper"):
+        raise SystemExit("--timestamps exists for --family sensevoice / paraformer (per token) and --family whisper (per segment), not for --family qwen_asr")
+    bundle = {"sensevoice": "SenseVoiceSmall", "paraformer": "Paraformer", "whisper": "Whisper", "qwen_asr": "Qwen_ASR"}[a.family]
+    if not any(os.path.isfile(os.path.join(a.model, bundle + ext)) for ext in (".asrmodel", ".onnx")):
+        raise SystemExit("--model %s holds no %s.asrmodel: it is not a --family %s folder" % (a.model, bundle, a.family))
     fallback = getattr(a, "temperature_fallback", None)
     scores = bool(getattr(a, "token_scores", False)) or bool(fallback)
     if fallback and a.family != "whisper":
@@ -211,7 +214,7 @@ def main():
     r.add_argument("--sliding-window", type=int, default=0)
     r.add_argument("--repeat-penalty", type=float, default=1.0, help="1.0 = plain greedy (the comparison default); the reference scripts default to 0.8")
     r.add_argument("--beam", type=int, default=1, help="beam width (Whisper, Qwen3-ASR; 1 = greedy); > 1 takes the first hypothesis and needs --repeat-penalty 1")
-    r.add_argument("--timestamps", action="store_true", help="SenseVoice: add each token's start / end (seconds) and mean frame log-probability to the dump; Whisper: decode with timestamp tokens and add "
+    r.add_argument("--timestamps", action="store_true", help="SenseVoice: add each token's start / end (seconds) and mean frame log-probability to the dump; Paraformer: each token's start / end from its CIF fire row and its log-probability; Whisper: decode with timestamp tokens and add "
                         "segments (start / end in seconds, token ids, text with --tokenizer)")
     r.add_argument("--word-timestamps", action="store_true", help="Whisper: add each text token's start / end in seconds (cross-attention DTW on the bundle's "
                         "alignment heads) to the dump; with --tokenizer also words, printed as they are found")
