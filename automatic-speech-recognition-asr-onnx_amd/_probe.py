@@ -69,6 +69,7 @@ class WhisperAlignDesc(C.Structure):
 SIGNATURES = {
     "asr_probe_gemm": (C.c_int, [C.POINTER(GemmDesc)]),
     "asr_probe_ctc_head": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, _ip, _fp, _ip, C.c_char_p]),
+    "asr_probe_ctc_topk": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _fp, C.c_char_p]),
     "asr_probe_gemm_chain": (C.c_int, [C.c_int] * 6 + [_fp]),
     "asr_probe_last_kernel": (C.c_char_p, []),
     "asr_probe_quantize_fp8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, _fp, C.c_void_p]),
@@ -147,6 +148,19 @@ def ctc_head(a, w, bias, n_valid=0, variant=-1):
     _lib.check(load().asr_probe_ctc_head(M, N, K, a.ctypes.data_as(_fp), w.ctypes.data_as(_fp), bias.ctypes.data_as(_fp), n_valid, variant,
                                          ids.ctypes.data_as(_ip), lp.ctypes.data_as(_fp), C.byref(stray), name))
     return ids, lp, stray.value, name.value.decode()
+
+
+def ctc_topk(a, w, bias, topk, n_valid=0, variant=-1, precision=0):
+    """The candidate kernel of the CTC prefix beam search behind the head of ctc_head (asr_probe_ctc_topk); precision 0 = bf16 operands, 1 = f32.
+    Returns (ids[M, topk], logprob[M, topk], kernel family name of the head GEMM)."""
+    a, w, bias = _f32(a), _f32(w), _f32(bias)
+    M, K = a.shape
+    N = w.shape[0]
+    ids, lp = np.zeros((M, topk), dtype=np.int32), np.zeros((M, topk), dtype=np.float32)
+    name = C.create_string_buffer(32)
+    _lib.check(load().asr_probe_ctc_topk(M, N, K, a.ctypes.data_as(_fp), w.ctypes.data_as(_fp), bias.ctypes.data_as(_fp), n_valid, variant, precision, topk,
+                                         ids.ctypes.data_as(_ip), lp.ctypes.data_as(_fp), name))
+    return ids, lp, name.value.decode()
 
 
 def gemm_bench(M, N, K, variant=-1, epilogue=0, iters=50) -> float:

@@ -441,6 +441,76 @@ extern "C" int asr_op_ctc_collapse_timed(const int32_t* frame_ids, const float* 
   });
 }
 
+extern "C" int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id,
+                                      const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
+                                      const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
+                                      int32_t* num_id, float* score, float* ctc_score) {
+  return asr_guard([&] {
+    ASR_REQUIRE(cand_id && cand_logprob && seq_lens && token_ids && num_id && score && ctc_score && batch > 0 && max_tokens > 0, "op_ctc_prefix_beam: bad argument");
+    ASR_REQUIRE(topk >= 1 && topk <= 16 && beam >= 1 && beam <= 16 && nbest >= 1 && nbest <= beam, "op_ctc_prefix_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)",
+                beam, topk, nbest);
+    ASR_REQUIRE(n_nodes >= 0 && (n_nodes <= 1 || (trie_depth && trie_is_end && trie_child_off && trie_child_tok && trie_child_node)), "op_ctc_prefix_beam: trie arrays missing");
+    if (n_nodes > 1) {                                   // a tree in the documented layout: every node but the root is the child of exactly one node, one level below it
+      ASR_REQUIRE(trie_child_off[0] == 0 && trie_child_off[n_nodes] == n_nodes - 1 && trie_depth[0] == 0, "op_ctc_prefix_beam: malformed trie");
+      for (int n = 0; n < n_nodes; ++n) {
+        ASR_REQUIRE(trie_child_off[n] <= trie_child_off[n + 1], "op_ctc_prefix_beam: malformed trie (child_off)");
+        for (int e = trie_child_off[n]; e < trie_child_off[n + 1]; ++e) {
+          const int ch = trie_child_node[e];
+          ASR_REQUIRE(ch > 0 && ch < n_nodes && trie_depth[ch] == trie_depth[n] + 1 && trie_child_tok[e] != blank_id && (e == trie_child_off[n] || trie_child_tok[e - 1] < trie_child_tok[e]),
+                      "op_ctc_prefix_beam: malformed trie (node %d, child entry %d)", n, e);
+        }
+      }
+    }
+    asr_require_device(0);
+    Tmp t;
+    PackedPlan pp(seq_lens, batch);
+    int max_T = 1;
+    std::vector<int32_t> ids((size_t)pp.Mpad * topk, 0);
+    std::vector<float> lp((size_t)pp.Mpad * topk, 0.0f);
+    size_t r = 0;
+    for (int b = 0; b < batch; ++b) {
+      const size_t n = (size_t)seq_lens[b] * topk;
+      for (int q = 0; q < seq_lens[b]; ++q)
+        for (int i = 0; i < topk; ++i)
+          for (int j = 0; j < i; ++j)
+            ASR_REQUIRE(cand_id[(r + q) * topk + i] != cand_id[(r + q) * topk + j], "op_ctc_prefix_beam: utterance %d row %d lists token %d twice", b, q, cand_id[(r + q) * topk + i]);
+      memcpy(&ids[(size_t)pp.plan[b].row_off * topk], cand_id + r * topk, n * 4);
+      memcpy(&lp[(size_t)pp.plan[b].row_off * topk], cand_logprob + r * topk, n * 4);
+      r += seq_lens[b];
+      max_T = std::max(max_T, seq_lens[b]);
+    }
+    int32_t* dids = (int32_t*)t.alloc(ids.size() * 4);
+    float* dlp = (float*)t.alloc(lp.size() * 4);
+    UttPlan* dplan = (UttPlan*)t.alloc(sizeof(UttPlan) * batch);
+    HIP_CHECK(hipMemcpy(dids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dlp, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dplan, pp.plan.data(), sizeof(UttPlan) * batch, hipMemcpyHostToDevice));
+    HotTrie trie;
+    if (n_nodes > 1) {
+      std::vector<int32_t> img;
+      img.insert(img.end(), trie_depth, trie_depth + n_nodes); img.insert(img.end(), trie_is_end, trie_is_end + n_nodes);
+      img.insert(img.end(), trie_child_off, trie_child_off + n_nodes + 1); img.insert(img.end(), trie_child_tok, trie_child_tok + n_nodes - 1);
+      img.insert(img.end(), trie_child_node, trie_child_node + n_nodes - 1);
+      int32_t* dtrie = (int32_t*)t.alloc(img.size() * 4);
+      HIP_CHECK(hipMemcpy(dtrie, img.data(), img.size() * 4, hipMemcpyHostToDevice));
+      trie = hot_trie_view(dtrie, n_nodes, boost);
+    }
+    const int pool_stride = max_T * beam;
+    int2* dpool = (int2*)t.alloc((size_t)batch * pool_stride * sizeof(int2));
+    const size_t hyps = (size_t)batch * nbest;
+    int32_t* dtok = (int32_t*)t.alloc(hyps * max_tokens * 4);
+    int32_t* dnum = (int32_t*)t.alloc(hyps * 4);
+    float* dsc = (float*)t.alloc(hyps * 4);
+    float* dctc = (float*)t.alloc(hyps * 4);
+    launch_ctc_prefix_beam(dids, dlp, topk, dplan, batch, blank_id, beam, nbest, trie, dpool, pool_stride, dtok, max_tokens, dnum, dsc, dctc, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(token_ids, dtok, hyps * max_tokens * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(num_id, dnum, hyps * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(score, dsc, hyps * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(ctc_score, dctc, hyps * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 extern "C" int asr_op_cif_scan_timed(const float* alpha, const float* enc, int d, const int32_t* seq_lens, int batch, float tail_threshold,
                                      float* acoustic_out, int32_t* fire_frame_out, int max_tokens, int32_t* num_id_out) {
   return asr_guard([&] {

@@ -1,5 +1,7 @@
 // Non-GEMM kernels of the ASR hot path (gfx950).
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 // Per-utterance geometry, built on the host for every run and uploaded with one copy.
@@ -349,6 +351,31 @@ void launch_ctc_collapse(const int32_t* frame_ids, const UttPlan* plan, int n_ut
 // frame order / f32 count). Same ids, counts and max_tokens rule as launch_ctc_collapse.
 void launch_ctc_collapse_timed(const int32_t* frame_ids, const float* frame_logprob, const UttPlan* plan, int n_utts, int blank_id, int32_t* token_ids,
                                int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, int32_t* num_id, hipStream_t s);
+
+// ---- CTC prefix beam search (ctc_beam.hip)
+// The hotword context graph as the device sees it: node 0 is the root; children of node n are child_tok / child_node [child_off[n], child_off[n + 1]), sorted
+// by token. n_nodes <= 1: no hotwords (no pointer is read).
+struct HotTrie {
+  const int32_t *depth = nullptr, *is_end = nullptr, *child_off = nullptr, *child_tok = nullptr, *child_node = nullptr;
+  int n_nodes = 0;
+  float boost = 0.0f;
+};
+// phrases (flattened ids, offsets [n_phrases + 1]) -> one int32 image [depth n][is_end n][child_off n + 1][child_tok n - 1][child_node n - 1]; hot_trie_view
+// points a HotTrie into a device copy of it
+std::vector<int32_t> build_hot_trie(const int32_t* ids, const int32_t* offsets, int n_phrases, int* n_nodes_out);
+HotTrie hot_trie_view(const int32_t* dev_words, int n_nodes, float boost);
+// Per row the `topk` (1..16) best columns n < n_valid of h W^T + bias and their log soft-max, from the per-slab partials of the timed CTC head (amax_val /
+// amax_sum [M][n_slabs], 64-column slabs): only the topk slabs with the largest maxima are recomputed (f32 accumulation from the operand type T).
+// cand_id / cand_lp [M][topk], higher value first, lower id on ties.
+template <typename T>
+void launch_ctc_topk(const T* h, int ldh, const T* W, int ldw, const float* bias, int K, const float* amax_val, const float* amax_sum, int n_slabs, int M,
+                     int n_valid, int topk, int32_t* cand_id, float* cand_lp, hipStream_t s);
+// The search, one workgroup per utterance over rows plan[u].row_off .. + T of the candidate arrays. pool: [n_utts][pool_stride] (parent, token) nodes,
+// pool_stride >= max T * beam. Outputs [n_utts][nbest] (token_ids [n_utts][nbest][max_tokens], best first; num_id keeps the full length); hypotheses beyond the
+// number found have num_id 0 and score -inf.
+void launch_ctc_prefix_beam(const int32_t* cand_id, const float* cand_lp, int topk, const UttPlan* plan, int n_utts, int blank_id, int beam, int nbest,
+                            const HotTrie& trie, int2* pool, int pool_stride, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score,
+                            hipStream_t s);
 
 // ---- Paraformer CIF predictor + decoder helpers (Paraformer/Non-Streaming/Export_Paraformer.py:499-563)
 // [x[t-1] | x[t] | x[t+1]] rows with zero padding at utterance edges: the k=3 conv as one GEMM (K = 3 d)

@@ -509,6 +509,57 @@ extern "C" int asr_probe_ctc_head(int M, int N, int K, const float* a, const flo
   });
 }
 
+// The candidate kernel behind the same head (launch_ctc_topk): operands and `variant` as asr_probe_ctc_head; precision ASR_PRECISION_BF16 rounds a / w to
+// bf16 as that entry does, ASR_PRECISION_F32 keeps them and runs the f32 GEMM (variant is then ignored). out_ids / out_logprob [M][topk].
+extern "C" int asr_probe_ctc_topk(int M, int N, int K, const float* a, const float* w, const float* bias, int n_valid, int variant, int precision, int topk,
+                                  int32_t* out_ids, float* out_logprob, char* kernel32) {
+  return asr_guard([&] {
+    ASR_REQUIRE(a && w && bias && out_ids && out_logprob && M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 64 == 0 && n_valid >= 0 && n_valid <= N, "probe_ctc_topk: bad argument");
+    ASR_REQUIRE(precision == ASR_PRECISION_BF16 || precision == ASR_PRECISION_F32, "probe_ctc_topk: precision %d (bf16 or f32)", precision);
+    asr_require_device(0);
+    gemm_reload_env();
+    Tmp t;
+    const bool lo = precision == ASR_PRECISION_BF16;
+    const int Mp = round_up(M, 128) + 128, n_slabs = N / 64, nv = n_valid > 0 ? n_valid : N;
+    void *da = nullptr, *dw = nullptr;
+    if (lo) {
+      std::vector<bf16_t> ha((size_t)Mp * K, 0), hw((size_t)N * K);
+      for (size_t i = 0; i < (size_t)M * K; ++i) ha[i] = f32_to_bf16(a[i]);
+      for (size_t i = 0; i < (size_t)N * K; ++i) hw[i] = f32_to_bf16(w[i]);
+      da = t.alloc(ha.size() * 2); dw = t.alloc(hw.size() * 2);
+      HIP_CHECK(hipMemcpy(da, ha.data(), ha.size() * 2, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+    } else {
+      da = t.alloc((size_t)Mp * K * 4); dw = t.alloc((size_t)N * K * 4);
+      HIP_CHECK(hipMemcpy(da, a, (size_t)M * K * 4, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dw, w, (size_t)N * K * 4, hipMemcpyHostToDevice));
+    }
+    float* db = (float*)t.alloc((size_t)N * 4);
+    HIP_CHECK(hipMemcpy(db, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+    const size_t part = (size_t)Mp * n_slabs;
+    float* dav = (float*)t.alloc(part * 4); int32_t* dai = (int32_t*)t.alloc(part * 4); float* das = (float*)t.alloc(part * 4);
+    int32_t* dci = (int32_t*)t.alloc((size_t)Mp * topk * 4); float* dcl = (float*)t.alloc((size_t)Mp * topk * 4);
+    GemmArgs g;
+    g.A = da; g.lda = K; g.W = dw; g.ldw = K; g.M = M; g.N = N; g.K = K; g.bias = db;
+    g.amax_val = dav; g.amax_idx = dai; g.amax_sum = das; g.n_valid = nv;
+    if (lo) {
+      g.sk_ws = (float*)t.alloc((size_t)16 << 20); g.sk_ws_bytes = (size_t)16 << 20; g.sk_cnt = (int32_t*)t.alloc(4096 * 4);
+      gemm_set_variant(variant);
+      try { launch_gemm_bf16(g, nullptr); } catch (...) { gemm_set_variant(-1); throw; }
+      gemm_set_variant(-1);
+      if (kernel32) snprintf(kernel32, 32, "%s", gemm_last_kernel());
+      launch_ctc_topk<bf16_t>((const bf16_t*)da, K, (const bf16_t*)dw, K, db, K, dav, das, n_slabs, M, nv, topk, dci, dcl, nullptr);
+    } else {
+      launch_gemm_f32(g, nullptr);
+      if (kernel32) snprintf(kernel32, 32, "f32");
+      launch_ctc_topk<float>((const float*)da, K, (const float*)dw, K, db, K, dav, das, n_slabs, M, nv, topk, dci, dcl, nullptr);
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out_ids, dci, (size_t)M * topk * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(out_logprob, dcl, (size_t)M * topk * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 // ---- decoder attention (launch_decode_attention) on host arrays: self-attention over a contiguous or paged cache, cross-attention over
 // packed slabs (optionally FP8 through the product's quantiser). Reports which form the dispatcher chose (asr_mi355x_probe.h).
 namespace {

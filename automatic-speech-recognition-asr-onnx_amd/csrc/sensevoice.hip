@@ -1,5 +1,6 @@
 // SenseVoiceSmall hot path on one MI355X: packed ragged batch -> fbank -> LFR/CMVN -> SANM blocks ->
 // CTC arg-max + collapse. Follows SENSE_VOICE.forward (SenseVoice/Export_SenseVoice.py:271-296).
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -59,6 +60,15 @@ struct SvSession : asr_session {
   DeviceBuffer d_amax_s, d_flp, d_first, d_last, d_tlp;   // timed runs only: sum-of-exponentials partials, frame log-probabilities, token spans and scores
                                                           // (Paraformer: row log-probabilities in d_flp, fire rows / steps in d_first, token log-probabilities in d_tlp)
   PinnedBuffer h_plan, h_out;   // pinned staging
+  // beam runs only (asr_sensevoice_run_beam, ctc_beam.hip): candidates [rows][topk], the (parent, token) node pool, the outputs as one block
+  // [tokens B nbest max_tokens][counts B nbest][scores B nbest][ctc scores B nbest], the hotword trie image
+  DeviceBuffer d_cand_i, d_cand_l, d_pool, d_bout, d_hot;
+  int hot_nodes = 0; float hot_boost = 0.0f;
+  uint64_t beam_epoch = 1;      // bumped when a beam-only buffer moves or the hotword list changes: part of the beam graph's key, not of the others'
+  struct BeamReq { int beam, topk, nbest; int32_t* tok_out; int32_t* num_out; float* score_out; float* ctc_out; };
+  const BeamReq* beam_req = nullptr;    // set around run() by run_beam()
+  void set_hotwords(const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+  template <typename T> void run_beam(const void* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang, const BeamReq& req, int max_tokens);
 
   // ---- streaming Paraformer (kind 4): per-stream recurrent state in HBM, every step advances n streams by one chunk
   int st_chunk = 0, st_B = 0, st_C = 0, st_en_cap = 0, st_de_cap = 0, st_max = 0, st_frames = 0;
@@ -138,6 +148,7 @@ struct SvSession : asr_session {
   DeviceBuffer d_flags;         // exchange counters of the block kernel: [n_blocks][batch][4] + the error word at the end
   StepGraph graph;              // hipGraph replay of the forward pass (one graph per batch geometry)
   StepGraph graph_timed;        // ... of the timed forms, so that a caller who alternates the two forms replays both
+  StepGraph graph_beam;         // ... of the beam form
   uint64_t ws_epoch = 1;
   StepGraph st_graph[3];        // streaming chunk step: per-launch / fused / fused + snapshot
   StepGraph st_graph_timed[3];  // ... of the timed step
@@ -281,6 +292,7 @@ struct SvRunCtx {
   int n_tiles = 0;
   bool tiles = false;
   bool timed = false;         // CTC head with frame log-probabilities, collapse with spans
+  int beam = 0, topk = 0, nbest = 0, pool_stride = 0;     // beam > 0: CTC head with the sum-of-exponentials partial, candidates, prefix beam search
 };
 
 // fragment-major weight copies for the 8-wave block kernel: one pass over the arena's bf16 matrices per session, outside any graph capture
@@ -565,9 +577,32 @@ void SvSession::enqueue(const SvRunCtx& r) {
     GemmArgs g;
     g.A = h; g.lda = d; g.W = ctc_w; g.ldw = d; g.M = rows; g.N = vpad; g.K = d; g.bias = ctc_b;
     g.amax_val = d_amax_v.as<float>(); g.amax_idx = d_amax_i.as<int32_t>(); g.n_valid = c.vocab;
-    if (r.timed) g.amax_sum = d_amax_s.as<float>();
+    if (r.timed || r.beam) g.amax_sum = d_amax_s.as<float>();
     if (taps_enabled) { g.out_f32 = d_logits.as<float>(); g.ld_out_f32 = vpad; }
     gemm(g);
+  }
+  if (r.beam) {                                           // ---- 5b. prefix beam search over the top-k tokens of every row
+    const size_t hyps = (size_t)r.batch * r.nbest, tokb = hyps * r.max_tokens * 4;
+    unsigned char* bo = d_bout.as<unsigned char>();
+    {
+      ProfScope ps(prof, "ctc_topk", stream);
+      launch_ctc_topk<T>(h, d, (const T*)ctc_w, d, ctc_b, d, d_amax_v.as<float>(), d_amax_s.as<float>(), n_slabs, rows, c.vocab, r.topk, d_cand_i.as<int32_t>(),
+                         d_cand_l.as<float>(), stream);
+    }
+    {
+      ProfScope ps(prof, "ctc_beam", stream);
+      launch_ctc_prefix_beam(d_cand_i.as<int32_t>(), d_cand_l.as<float>(), r.topk, r.dp, r.batch, c.blank_id, r.beam, r.nbest,
+                             hot_trie_view(d_hot.as<int32_t>(), hot_nodes, hot_boost), (int2*)d_pool.ptr, r.pool_stride, (int32_t*)bo, r.max_tokens,
+                             (int32_t*)(bo + tokb), (float*)(bo + tokb + hyps * 4), (float*)(bo + tokb + hyps * 8), stream);
+    }
+    if (taps_enabled) {
+      save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
+      save_tap("cand_ids", d_cand_i.ptr, rows, r.topk, r.topk, 4);
+      save_tap("cand_logprob", d_cand_l.ptr, rows, r.topk, r.topk, 4);
+    }
+    copy_block_status(r);                                 // the plain outputs' slots stay unused; the beam block rides behind the 16 status bytes
+    HIP_CHECK(hipMemcpyAsync(h_out.as<unsigned char>() + (size_t)r.batch * r.max_tokens * 4 + (size_t)r.batch * 4 + 16, bo, tokb + hyps * 12, hipMemcpyDeviceToHost, stream));
+    return;
   }
   {
     ProfScope ps(prof, "ctc_tail", stream);
@@ -760,9 +795,11 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
                     int max_tokens, int32_t* num_out, int32_t* first_out, int32_t* last_out, float* logprob_out) {
   const auto& c = cfg;
   const bool timed = first_out != nullptr;
+  const BeamReq* const bq = beam_req;
+  ASR_REQUIRE(!bq || (!paraformer && !timed), "sensevoice: the beam form is SenseVoice's, without spans");
   ASR_REQUIRE(!timed || (logprob_out && (paraformer ? !last_out : last_out != nullptr)), "sensevoice: the timed form needs all of its outputs");
   ASR_REQUIRE(batch > 0, "sensevoice: empty batch");
-  ASR_REQUIRE(audio && offs && (lang || paraformer) && tok_out && num_out, "sensevoice: null argument");
+  ASR_REQUIRE(audio && offs && (lang || paraformer) && (bq || (tok_out && num_out)), "sensevoice: null argument");
   HIP_CHECK(hipSetDevice(device));
   // no cluster kernel beside a foreign (RCCL) section: this whole call -- it returns with the stream drained -- is one cluster pass, or takes the four-launch path
   ClusterScope cluster(device);
@@ -860,6 +897,14 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
     grow(d_last, (size_t)batch * max_tokens * 4);
     grow(d_tlp, (size_t)batch * max_tokens * 4);
   }
+  if (bq) {
+    auto grow_beam = [&](DeviceBuffer& buf, size_t bytes) { void* before = buf.ptr; buf.reserve(bytes, stream); if (buf.ptr != before) ++beam_epoch; };
+    grow(d_amax_s, (size_t)Mpad * n_slabs * 4);
+    grow_beam(d_cand_i, (size_t)Mpad * bq->topk * 4);
+    grow_beam(d_cand_l, (size_t)Mpad * bq->topk * 4);
+    grow_beam(d_pool, (size_t)batch * max_T * bq->beam * sizeof(int2));
+    grow_beam(d_bout, (size_t)batch * bq->nbest * ((size_t)max_tokens * 4 + 12));
+  }
   if (paraformer) {
     const int dd = pcfg.d_dec_ffn;
     grow(d_enc_lo, (size_t)Mpad * d * eT);
@@ -877,7 +922,8 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
     grow(d_mdev, 256);
     grow(d_trow, (size_t)Mpad * 4);
   }
-  const size_t out_bytes = (size_t)batch * max_tokens * 4 + (size_t)batch * 4 + 16 + (timed ? (size_t)batch * max_tokens * 12 : 0);
+  const size_t out_bytes = (size_t)batch * max_tokens * 4 + (size_t)batch * 4 + 16 + (timed ? (size_t)batch * max_tokens * 12 : 0) +
+                           (bq ? (size_t)batch * bq->nbest * ((size_t)max_tokens * 4 + 12) : 0);
   if (h_out.reserve(out_bytes)) ++ws_epoch;
 
   pb.upload(stream);
@@ -885,11 +931,16 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   r.max_tokens = max_tokens; r.att_qt = att_qt; r.att_nw = att_nw;
   r.dp = pb.dev(s_plan);
   r.n_tiles = n_tiles; r.tiles = tiles; r.timed = timed;
+  if (bq) { r.beam = bq->beam; r.topk = bq->topk; r.nbest = bq->nbest; r.pool_stride = max_T * bq->beam; }
   r.d_blk_utt = pb.dev(s_blk_utt); r.d_blk_f0 = pb.dev(s_blk_f0); r.d_qb_utt = pb.dev(s_qb_utt); r.d_qb_q0 = pb.dev(s_qb_q0);
   r.d_row_utt = pb.dev(s_row_utt); r.d_tile_win = pb.dev(s_tile_win); r.d_tile_idx = pb.dev(s_tile_idx);
   key.mix((uint64_t)batch); key.mix((uint64_t)max_tokens); key.mix((uint64_t)(uintptr_t)r.d_aud); key.mix((uint64_t)audio_dtype); key.mix(ws_epoch); key.mix((uint64_t)(uintptr_t)stream);
   key.mix((uint64_t)(block_cooldown > 0 || foreign_now));        // a session cooling down after a cluster give-up replays the four-launch capture, not the block one
   key.mix((uint64_t)timed);                                      // the timed CTC tail is another launch sequence
+  if (bq) {                                                      // ... and so is the beam tail, per (beam, topk, nbest), hotword list and boost
+    uint32_t boost_bits; memcpy(&boost_bits, &hot_boost, 4);
+    key.mix((uint64_t)bq->beam); key.mix((uint64_t)bq->topk); key.mix((uint64_t)bq->nbest); key.mix(beam_epoch); key.mix((uint64_t)hot_nodes); key.mix((uint64_t)boost_bits);
+  }
 
   if (sizeof(T) == 2 && use_block && cfg.n_blocks > 1 && blocks[cfg.n_blocks - 1].cqkv && blocks[cfg.n_blocks - 1].c1 && batch >= block_min_utts &&
       sanm_block_supported(max_T, cfg.d_head, cfg.n_heads, cfg.d_model, cfg.d_ffn, cfg.fsmn_kernel))
@@ -897,7 +948,7 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
   if (tiles) ensure_tiles_pack();
   // ---- launch: eager the first time a geometry is seen (allocations settle), then capture once and replay ----
   // 570 launches per forward are host-launch-bound when issued eagerly (~13 us each); replay costs ~1 us per node.
-  (timed ? graph_timed : graph).run(stream, use_graph && !taps_enabled && !prof.enabled, key.h, [&] { enqueue<T>(r); });
+  (bq ? graph_beam : timed ? graph_timed : graph).run(stream, use_graph && !taps_enabled && !prof.enabled, key.h, [&] { enqueue<T>(r); });
   HIP_CHECK(hipStreamSynchronize(stream));
   if (prof.enabled) prof.collect();
   if (tiles_dbg >= 0 && tiles && d_times.ptr) {          // tuning: mean phase intervals of one block of the tile kernel over its workgroups (100 MHz clock -> us)
@@ -964,6 +1015,16 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
     else if (block_cooldown > 0) --block_cooldown;
     ASR_REQUIRE(blk_err == 0, "sensevoice: a SANM block workgroup gave up waiting for its cluster (results are invalid)");
   }
+  if (bq) {
+    const size_t hyps = (size_t)batch * bq->nbest, tokb = hyps * max_tokens * 4;
+    const unsigned char* bo = h_out.as<const unsigned char>() + (size_t)batch * max_tokens * 4 + (size_t)batch * 4 + 16;
+    memcpy(bq->num_out, bo + tokb, hyps * 4);
+    memcpy(bq->score_out, bo + tokb + hyps * 4, hyps * 4);
+    memcpy(bq->ctc_out, bo + tokb + hyps * 8, hyps * 4);
+    for (size_t q = 0; q < hyps; ++q)
+      memcpy(bq->tok_out + q * max_tokens, bo + q * max_tokens * 4, (size_t)std::min(bq->num_out[q], max_tokens) * 4);
+    return;
+  }
   memcpy(num_out, h_out.as<unsigned char>() + (size_t)batch * max_tokens * 4, (size_t)batch * 4);
   const int32_t* ht = h_out.as<const int32_t>();
   for (int b = 0; b < batch; ++b) {
@@ -980,6 +1041,41 @@ void SvSession::run(const void* audio, int audio_mem, const int64_t* offs, int b
       memcpy((unsigned char*)logprob_out + o, ext + 2 * tok_bytes + o, n);
     }
   }
+}
+
+template <typename T>
+void SvSession::run_beam(const void* audio, int audio_mem, const int64_t* offs, int batch, const int32_t* lang, const BeamReq& req, int max_tokens) {
+  ASR_REQUIRE(!paraformer, "sensevoice_run_beam: not a SenseVoice session");
+  ASR_REQUIRE(req.beam >= 1 && req.beam <= 16 && req.topk >= 1 && req.topk <= 16 && req.nbest >= 1 && req.nbest <= req.beam && req.topk <= cfg.vocab,
+              "sensevoice_run_beam: beam %d, topk %d, nbest %d (beam and topk 1..16, nbest 1..beam)", req.beam, req.topk, req.nbest);
+  ASR_REQUIRE(req.tok_out && req.num_out && req.score_out && req.ctc_out, "sensevoice_run_beam: null output");
+  ASR_REQUIRE(cfg.d_model <= 2048, "sensevoice_run_beam: d_model %d (the candidate kernel holds a row of 2048 at most)", cfg.d_model);
+  struct Scope { SvSession* s; ~Scope() { s->beam_req = nullptr; } } scope{this};
+  beam_req = &req;
+  run<T>(audio, audio_mem, offs, batch, lang, nullptr, max_tokens, nullptr);
+}
+
+void SvSession::set_hotwords(const int32_t* ids, const int32_t* offsets, int n_phrases, float boost) {
+  ASR_REQUIRE(!paraformer, "sensevoice_set_hotwords: not a SenseVoice session");
+  ASR_REQUIRE(n_phrases >= 0 && (n_phrases == 0 || (ids && offsets)) && std::isfinite(boost), "sensevoice_set_hotwords: bad argument");
+  HIP_CHECK(hipSetDevice(device));
+  if (n_phrases == 0) { hot_nodes = 0; hot_boost = 0.0f; ++beam_epoch; return; }
+  ASR_REQUIRE(offsets[0] >= 0, "sensevoice_set_hotwords: offsets[0] = %d", offsets[0]);
+  for (int p = 0; p < n_phrases; ++p) {
+    ASR_REQUIRE(offsets[p + 1] > offsets[p], "sensevoice_set_hotwords: phrase %d is empty", p);
+    for (int32_t i = offsets[p]; i < offsets[p + 1]; ++i) {
+      ASR_REQUIRE(ids[i] >= 0 && ids[i] < cfg.vocab, "sensevoice_set_hotwords: phrase %d holds token %d (vocabulary %d)", p, ids[i], cfg.vocab);
+      ASR_REQUIRE(ids[i] != cfg.blank_id, "sensevoice_set_hotwords: phrase %d holds the blank id", p);
+    }
+  }
+  int n_nodes = 0;
+  const std::vector<int32_t> img = build_hot_trie(ids, offsets, n_phrases, &n_nodes);
+  HIP_CHECK(hipStreamSynchronize(stream));
+  d_hot.reserve(img.size() * 4, stream);
+  HIP_CHECK(hipMemcpyAsync(d_hot.ptr, img.data(), img.size() * 4, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  hot_nodes = n_nodes; hot_boost = boost;
+  ++beam_epoch;                                          // the trie's words are graph-kernel operands: a captured beam step is stale
 }
 
 // ---- streaming Paraformer (Paraformer/Streaming/Export_Paraformer_Streaming.py:386-553; host loop Inference_..._Streaming_ONNX.py:401-449)
@@ -1672,6 +1768,26 @@ extern "C" int asr_paraformer_stream_step(asr_session* s, const void* audio, int
     SvSession* sv = static_cast<SvSession*>(s);
     if (sv->precision == ASR_PRECISION_BF16) sv->stream_step<bf16_t>(audio, audio_mem, stream_ids, n_streams, token_ids_out, max_tokens, num_id_out);
     else sv->stream_step<float>(audio, audio_mem, stream_ids, n_streams, token_ids_out, max_tokens, num_id_out);
+  });
+}
+
+extern "C" int asr_sensevoice_run_beam(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+                                       const int32_t* language_idx, int beam, int topk, int nbest, int32_t* token_ids_out, int max_tokens,
+                                       int32_t* num_id_out, float* score_out, float* ctc_score_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 1, "sensevoice_run_beam: not a SenseVoice session");
+    TenantScope tenant(s);
+    auto* sv = static_cast<SvSession*>(s);
+    const SvSession::BeamReq req{beam, topk, nbest, token_ids_out, num_id_out, score_out, ctc_score_out};
+    if (s->precision == ASR_PRECISION_F32) sv->run_beam<float>(audio, audio_mem, audio_offsets, batch, language_idx, req, max_tokens);
+    else sv->run_beam<bf16_t>(audio, audio_mem, audio_offsets, batch, language_idx, req, max_tokens);
+  });
+}
+
+extern "C" int asr_sensevoice_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 1, "sensevoice_set_hotwords: not a SenseVoice session");
+    static_cast<SvSession*>(s)->set_hotwords(ids, offsets, n_phrases, boost);
   });
 }
 

@@ -229,6 +229,46 @@ class SenseVoiceSession(_Session):
         return [{"ids": tok[b, :num[b]].copy(), "first_frame": first[b, :num[b]].copy(), "last_frame": last[b, :num[b]].copy(),
                  "logprob": logprob[b, :num[b]].copy()} for b in range(len(flat))]
 
+    def set_hotwords(self, phrases: Sequence[Sequence[int]], boost: float = 2.0):
+        """Hotwords of run_beam (asr_sensevoice_set_hotwords): token-id lists; a hypothesis gains `boost` per token while it spells one of them, and a
+        partial match gives its part back. An empty list clears them. Empty phrases, the blank id and ids outside the vocabulary raise AsrError."""
+        phrases = [np.asarray(p, dtype=np.int32).reshape(-1) for p in phrases]
+        offs = np.zeros(len(phrases) + 1, dtype=np.int32)
+        offs[1:] = np.cumsum([p.size for p in phrases])
+        ids = np.ascontiguousarray(np.concatenate(phrases) if phrases else np.zeros(0, np.int32), dtype=np.int32)
+        ids = ids if ids.size else np.zeros(1, np.int32)
+        _lib.check(_lib.load().asr_sensevoice_set_hotwords(self._h, _ip(ids), _ip(offs), len(phrases), float(boost)))
+
+    def run_packed_beam(self, audio, offsets: np.ndarray, language_idx: np.ndarray, beam: int, topk: int | None = None, nbest: int = 1,
+                        audio_device_ptr: int | None = None):
+        """run_packed with a CTC prefix beam search instead of the arg-max collapse (asr_sensevoice_run_beam): the `topk` (default: beam) best tokens
+        of every row, `beam` live prefixes, the `nbest` best hypotheses. Returns (token_ids [B, nbest, max_T] int32, num_id [B, nbest] int32, score
+        [B, nbest], ctc_score [B, nbest] float32), best first; hypotheses beyond the number found have num 0 and score -inf."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        lang = np.ascontiguousarray(language_idx, dtype=np.int32)
+        B = lang.shape[0]
+        assert offsets.shape[0] == B + 1
+        topk = int(beam if topk is None else topk)
+        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        tok = np.zeros((B, nbest, max_t), dtype=np.int32)
+        num = np.zeros((B, nbest), dtype=np.int32)
+        score, ctc = np.zeros((B, nbest), dtype=np.float32), np.zeros((B, nbest), dtype=np.float32)
+        if audio_device_ptr is not None:
+            ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
+        else:
+            audio = self._audio(audio).reshape(-1)
+            ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
+        _lib.check(_lib.load().asr_sensevoice_run_beam(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(lang), int(beam), topk,
+                                                       int(nbest), _ip(tok), max_t, _ip(num), _fp(score), _fp(ctc)))
+        return tok, num, score, ctc
+
+    def run_beam(self, audios: Sequence[np.ndarray], language_idx: Sequence[int], beam: int, topk: int | None = None, nbest: int = 1):
+        """List of 1-D utterances -> per utterance the list of hypotheses found (at most nbest), best first: {"tokens", "score", "ctc_score"}."""
+        flat, packed, offs = self._pack(audios)
+        tok, num, score, ctc = self.run_packed_beam(packed, offs, np.asarray(language_idx, dtype=np.int32), beam, topk, nbest)
+        return [[{"tokens": tok[b, n, :num[b, n]].copy(), "score": float(score[b, n]), "ctc_score": float(ctc[b, n])}
+                 for n in range(nbest) if np.isfinite(score[b, n])] for b in range(len(flat))]
+
     def utterance_rows(self, lengths: Sequence[int]):
         """(row_off, T) of each utterance inside the packed tap tensors (16-row aligned)."""
         out, r = [], 0
@@ -310,6 +350,60 @@ def op_ctc_collapse_timed(frame_ids, frame_logprob, seq_lens, blank_id=0, max_to
     _lib.check(_lib.load().asr_op_ctc_collapse_timed(_ip(ids), _fp(lp), _ip(sl), sl.size, blank_id, _ip(tok), _ip(first), _ip(last), _fp(tlp), max_t,
                                                      _ip(num)))
     return tok, first, last, tlp, num
+
+
+def hotword_trie(phrases):
+    """Token-id lists -> the trie arrays of op_ctc_prefix_beam (depth, is_end, child_off, child_tok, child_node; node 0 the root, nodes numbered breadth
+    first, children sorted by token)."""
+    kids, depth, is_end = [{}], [0], [0]
+    for ph in phrases:
+        ph = [int(t) for t in ph]
+        if not ph:
+            raise ValueError("empty hotword phrase")
+        n = 0
+        for t in ph:
+            if t not in kids[n]:
+                kids[n][t] = len(kids)
+                kids.append({})
+                depth.append(depth[n] + 1)
+                is_end.append(0)
+            n = kids[n][t]
+        is_end[n] = 1
+    order, remap = [0], {0: 0}
+    for n in order:
+        for t in sorted(kids[n]):
+            remap[kids[n][t]] = len(order)
+            order.append(kids[n][t])
+    off, tok, node = [0], [], []
+    for n in order:
+        for t in sorted(kids[n]):
+            tok.append(t)
+            node.append(remap[kids[n][t]])
+        off.append(len(tok))
+    i32 = lambda a: np.asarray(a, dtype=np.int32)
+    return {"depth": i32([depth[n] for n in order]), "is_end": i32([is_end[n] for n in order]), "child_off": i32(off), "child_tok": i32(tok),
+            "child_node": i32(node)}
+
+
+def op_ctc_prefix_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, blank_id=0, trie=None, boost=0.0, max_tokens=None):
+    """The CTC prefix beam search on host arrays (asr_op_ctc_prefix_beam): cand_id / cand_logprob [sum T, topk], `trie` as hotword_trie returns it (None:
+    no hotwords). Returns (token_ids [B, nbest, max_tokens], num_id [B, nbest], score [B, nbest], ctc_score [B, nbest]), best first."""
+    ids = np.ascontiguousarray(cand_id, dtype=np.int32)
+    lp = _f32(cand_logprob)
+    sl = np.ascontiguousarray(seq_lens, dtype=np.int32)
+    assert ids.ndim == 2 and ids.shape == lp.shape and ids.shape[0] == int(sl.sum())
+    max_t = int(sl.max()) if max_tokens is None else int(max_tokens)
+    tok = np.zeros((sl.size, nbest, max_t), dtype=np.int32)
+    num = np.zeros((sl.size, nbest), dtype=np.int32)
+    score, ctc = np.zeros((sl.size, nbest), dtype=np.float32), np.zeros((sl.size, nbest), dtype=np.float32)
+    if trie is not None and trie["depth"].size > 1:
+        t = {k: np.ascontiguousarray(trie[k], dtype=np.int32) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")}
+        targs, n_nodes = [_ip(t[k]) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")], int(t["depth"].size)
+    else:
+        targs, n_nodes = [None] * 5, 0
+    _lib.check(_lib.load().asr_op_ctc_prefix_beam(_ip(ids), _fp(lp), ids.shape[1], _ip(sl), sl.size, blank_id, *targs, n_nodes, float(boost), int(beam),
+                                                  int(nbest), _ip(tok), max_t, _ip(num), _fp(score), _fp(ctc)))
+    return tok, num, score, ctc
 
 
 def op_cif_scan_timed(alpha, enc, seq_lens, tail_threshold, max_tokens=None, fill=0):

@@ -103,9 +103,45 @@ class SenseVoiceTranscriber:
                            "logprob": float(logprob[0, k])})
         return tok[0, :n].copy(), tokens
 
-    def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False, timestamps: bool = False):
+    def _hotword_ids(self, hotwords):
+        """Hotwords as token-id lists: id lists pass through, text needs the tokenizer (tokenizer.encode)."""
+        out = []
+        for h in hotwords or []:
+            if isinstance(h, str):
+                if self.tokenizer is None:
+                    raise ValueError("hotwords given as text need a tokenizer (tokenizer_path); pass token-id lists instead")
+                h = self.tokenizer.encode(h)
+            out.append([int(t) for t in h])
+        return out
+
+    def _run_window_beam(self, win: np.ndarray, language_idx: np.ndarray, beam_size: int, nbest: int):
+        """One window through the native session's CTC prefix beam search: (token ids of the best hypothesis, the hypotheses found, best first)."""
+        native = self.session._native
+        offsets = np.array([0, win.size], dtype=np.int64)
+        tok, num, score, ctc = native.run_packed_beam(win.reshape(-1), offsets, np.asarray(language_idx, dtype=np.int32).reshape(-1), beam_size, None, nbest)
+        hyps = []
+        for n in range(nbest):
+            if not np.isfinite(score[0, n]):
+                break
+            ids = tok[0, n, :num[0, n]].copy()
+            hyps.append({"token_ids": ids, "score": float(score[0, n]), "ctc_score": float(ctc[0, n]),
+                         "text": self.tokenizer.decode([ids.tolist()])[0] if self.tokenizer is not None else None})
+        return hyps[0]["token_ids"], hyps
+
+    def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False, timestamps: bool = False, beam_size: int = 1,
+                   nbest: int = 1, hotwords=None, hotword_boost: float = 2.0):
         """int16 mono PCM at `sample_rate` -> dict(token_ids, text, rtf, windows). timestamps=True adds "tokens": one {"id", "start", "end", "logprob"}
-        per token over all windows, in seconds of the whole audio (SenseVoiceConfig.row_span_seconds; logprob = mean frame log-probability)."""
+        per token over all windows, in seconds of the whole audio (SenseVoiceConfig.row_span_seconds; logprob = mean frame log-probability).
+        beam_size > 1, nbest > 1 or hotwords: every window is decoded by the CTC prefix beam search (SenseVoiceSession.run_packed_beam) instead of the
+        arg-max collapse; token_ids / text hold the best hypothesis and "nbest" holds, per window, the hypotheses found, best first:
+        {"token_ids", "score", "ctc_score", "text"}. hotwords: token-id lists, or text when a tokenizer is loaded; hotword_boost per matched token."""
+        use_beam = beam_size > 1 or nbest > 1 or bool(hotwords)
+        if use_beam:
+            if timestamps:
+                raise ValueError("timestamps are not available for beam hypotheses")
+            if not 1 <= nbest <= beam_size <= 16:
+                raise ValueError(f"beam_size {beam_size}, nbest {nbest}: expected 1 <= nbest <= beam_size <= 16")
+            self.session._native.set_hotwords(self._hotword_ids(hotwords), hotword_boost)        # exactly this call's list (an empty one clears)
         audio_len = int(np.asarray(audio_int16).size)
         audio = prepare_audio_input(np.asarray(audio_int16, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype,
                                     audio_pcm_scale=self.audio_pcm_scale, normalise=normalise)
@@ -125,7 +161,7 @@ class SenseVoiceTranscriber:
             language_buffer = onnxruntime.OrtValue.ortvalue_from_numpy(language_idx, "cpu", 0)
             binding.bind_ortvalue_input(self.audio_meta.name, audio_buffer)
             binding.bind_ortvalue_input(self.lang_meta.name, language_buffer)
-        ids_all, text, tokens_all = [], "", []
+        ids_all, text, tokens_all, nbest_all = [], "", [], []
         start, end = 0, window
         t0 = time.time()
         while end <= aligned:
@@ -133,6 +169,9 @@ class SenseVoiceTranscriber:
             if timestamps:
                 token_ids, toks = self._run_window_timed(win, language_idx, start / self.sample_rate, audio_len / self.sample_rate)
                 tokens_all.extend(toks)
+            elif use_beam:
+                token_ids, hyps = self._run_window_beam(win, language_idx, beam_size, nbest)
+                nbest_all.append(hyps)
             else:
                 if audio_buffer is None:
                     binding.bind_cpu_input(self.audio_meta.name, win)
@@ -151,4 +190,6 @@ class SenseVoiceTranscriber:
                "rtf": wall / (audio_len / self.sample_rate), "windows": len(ids_all), "language": self.language}
         if timestamps:
             out["tokens"] = tokens_all
+        if use_beam:
+            out["nbest"] = nbest_all
         return out

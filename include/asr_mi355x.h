@@ -142,6 +142,20 @@ int asr_sensevoice_run_timed(asr_session* s, const void* audio, int audio_mem, c
                              const int32_t* language_idx, int32_t* token_ids_out, int max_tokens, int32_t* num_id_out,
                              int32_t* first_frame_out, int32_t* last_frame_out, float* logprob_out);
 
+/* CTC prefix beam search instead of the frame-wise arg-max (no reference counterpart). The forward pass is asr_sensevoice_run's up to the head;
+ * per row the `topk` (1..16) best tokens and their log soft-max are taken without storing the logits, and a standard (not circular) prefix beam search of width
+ * `beam` (1..16) runs over every utterance's rows, prompt rows included. The `nbest` (1..beam) best hypotheses come back best first: token_ids_out host
+ * [B][nbest][max_tokens] (each row holds min(num, max_tokens) ids, rest untouched), num_id_out [B][nbest] (the full length), score_out [B][nbest] = the
+ * hypothesis' CTC log-probability over the candidates plus its hotword bonus, ctc_score_out [B][nbest] = without the bonus. Hypotheses beyond the number
+ * found have num 0 and score -inf. Scores tie-break to the earlier entry of the documented enumeration; two calls on the same input return the same bytes. */
+int asr_sensevoice_run_beam(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
+                            const int32_t* language_idx, int beam, int topk, int nbest, int32_t* token_ids_out, int max_tokens,
+                            int32_t* num_id_out, float* score_out, float* ctc_score_out);
+/* Hotwords of asr_sensevoice_run_beam: n_phrases token-id lists, phrase p = ids[offsets[p] .. offsets[p + 1]) (host). A hypothesis gains `boost` per token
+ * while it spells a phrase; a partial match that breaks off, or is still open at the end of the utterance, gives its part back. n_phrases == 0 clears the
+ * list. Ids outside the vocabulary, empty phrases and phrases containing the blank id are rejected (the list in force stays). */
+int asr_sensevoice_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+
 /* sequence length (prompt + LFR rows) the graph produces for an utterance of n_samples */
 int asr_sensevoice_seq_len(const asr_sensevoice_config* cfg, int n_samples, int* seq_len);
 /* Counters of a SenseVoice / Paraformer session's cluster kernels: out8 = {forward passes redone cluster-free because a cluster gave up, batches left on the
@@ -469,6 +483,14 @@ int asr_op_ctc_collapse(const int32_t* frame_ids, const int32_t* seq_lens, int b
  * [batch][max_tokens] (slots at or past the token count, or past max_tokens, are not written) */
 int asr_op_ctc_collapse_timed(const int32_t* frame_ids, const float* frame_logprob, const int32_t* seq_lens, int batch, int blank_id,
                               int32_t* token_ids, int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, int32_t* num_id);
+/* the search of asr_sensevoice_run_beam on host arrays: cand_id / cand_logprob [sum T][topk] (ids distinct inside a row, -inf log-probabilities ignored),
+ * seq_lens [batch] (each >= 1). The hotword trie: node 0 the root, per node depth / is_end [n_nodes], children of node n = child_tok / child_node
+ * [child_off[n], child_off[n + 1]) sorted by token (child_off [n_nodes + 1]); n_nodes <= 1: no hotwords, the arrays may be null. Outputs as above
+ * ([batch][nbest]...; token slots the search does not write come back 0). */
+int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id,
+                           const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
+                           const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
+                           int32_t* num_id, float* score, float* ctc_score);
 /* the CIF scan of asr_paraformer_run_timed on host arrays: alpha [sum T], enc [sum T][d], seq_lens [batch] (each >= 1); acoustic_out [sum T][d] receives, per
  * utterance, its token embeddings in its first rows and zeros behind them (tokens past row T - 1 of a 16-row-padded range are not returned);
  * fire_frame_out host [batch][max_tokens] (slots at or past the token count, or past max_tokens, are not written); num_id_out [batch] holds the full count */

@@ -39,6 +39,12 @@ int asr_probe_gemm(asr_probe_gemm_desc* d);
 int asr_probe_ctc_head(int M, int N, int K, const float* a, const float* w, const float* bias, int n_valid, int variant, int32_t* out_ids,
                        float* out_logprob, int32_t* stray, char* kernel32);
 
+/* The candidate kernel of the CTC prefix beam search behind the same head: per row the topk (1..16) best columns n < n_valid and their log soft-max,
+ * recomputed from the topk slabs with the largest maxima. precision: ASR_PRECISION_BF16 (operands rounded to bf16, `variant` as above) or ASR_PRECISION_F32
+ * (the f32 GEMM, variant ignored). out_ids / out_logprob [M][topk], higher value first, lower id on ties. */
+int asr_probe_ctc_topk(int M, int N, int K, const float* a, const float* w, const float* bias, int n_valid, int variant, int precision, int topk,
+                       int32_t* out_ids, float* out_logprob, char* kernel32);
+
 /* Decode-shaped GEMM (M <= 64 rows) as a captured chain of dependent launches over `cold_mb` megabytes of weight copies (larger than
  * the Infinity Cache => every launch streams its weights from HBM, like a decoder stack does once per token): microseconds per launch.
  * epilogue: 0 bias -> bf16, 1 bias + GELU -> bf16, 2 bias + residual -> f32, 3 LayerNorm prologue (f32 rows in) -> bf16. */

@@ -46,6 +46,23 @@ def whisper_text(tokenizer, ids, remove_repeats=True):
     return text
 
 
+def parse_hotword_file(path):
+    """One phrase per line: token ids separated by blanks or commas ("4125 77, 9") or text (encoded by the transcriber's tokenizer). Empty lines and lines
+    starting with # are skipped. Returns a list of id lists / strings."""
+    phrases = []
+    with open(path, encoding="utf-8") as f:
+        for line in f:
+            line = line.strip()
+            if not line or line.startswith("#"):
+                continue
+            parts = line.replace(",", " ").split()
+            if all(q.lstrip("-").isdigit() for q in parts):
+                phrases.append([int(q) for q in parts])
+            else:
+                phrases.append(line)
+    return phrases
+
+
 def run(a) -> dict:
     shim, eng, audio_io, cfgm = _m("ort_shim"), _m("engine"), _m("audio_io"), _m("config")
     prec = 1 if a.precision == "f32" else 0
@@ -57,6 +74,14 @@ def run(a) -> dict:
         raise SystemExit("--word-timestamps exists for --family whisper only")
     if timestamps and a.family not in ("sensevoice", "paraformer", "whisper"):
         raise SystemExit("--timestamps exists for --family sensevoice / paraformer (per token) and --family whisper (per segment), not for --family qwen_asr")
+    nbest, hot_file = getattr(a, "nbest", 1), getattr(a, "hotwords", None)
+    if (nbest > 1 or hot_file) and a.family != "sensevoice":
+        raise SystemExit("--nbest / --hotwords exist for --family sensevoice only")
+    sv_beam = a.family == "sensevoice" and (a.beam > 1 or nbest > 1 or bool(hot_file))
+    if sv_beam and timestamps:
+        raise SystemExit("--timestamps is not available with --beam / --nbest / --hotwords (beam hypotheses carry no time spans)")
+    if sv_beam and not 1 <= nbest <= a.beam <= 16:
+        raise SystemExit("--family sensevoice: --beam 1..16 and --nbest 1..beam (got --beam %d --nbest %d)" % (a.beam, nbest))
     bundle = {"sensevoice": "SenseVoiceSmall", "paraformer": "Paraformer", "whisper": "Whisper", "qwen_asr": "Qwen_ASR"}[a.family]
     if not any(os.path.isfile(os.path.join(a.model, bundle + ext)) for ext in (".asrmodel", ".onnx")):
         raise SystemExit("--model %s holds no %s.asrmodel: it is not a --family %s folder" % (a.model, bundle, a.family))
@@ -79,12 +104,18 @@ def run(a) -> dict:
             pcm = audio_io.read_wav_int16(p, tr.sample_rate, exact_width=a.strict_wav)
             if timestamps:
                 r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=True)
+            elif sv_beam:
+                r = tr.transcribe(pcm, sliding_window=a.sliding_window, beam_size=a.beam, nbest=nbest, hotwords=parse_hotword_file(hot_file) if hot_file else None,
+                                  hotword_boost=getattr(a, "hotword_boost", 2.0))
             else:
                 r = tr.transcribe(pcm, sliding_window=a.sliding_window)
             files.append({"path": p, "n_samples": int(pcm.size), "language": r.get("language", a.language),
                           "windows": [np.asarray(w).reshape(-1).astype(int).tolist() for w in r["token_ids"]], "text": r.get("text"), "rtf": r["rtf"]})
             if timestamps:
                 files[-1]["tokens"] = r["tokens"]
+            if sv_beam:                     # per window the hypotheses found, best first (windows[k] is nbest[k][0])
+                files[-1]["nbest"] = [[{"ids": np.asarray(h["token_ids"]).astype(int).tolist(), "score": h["score"], "ctc_score": h["ctc_score"], "text": h["text"]}
+                                       for h in win] for win in r["nbest"]]
     elif a.family == "whisper":
         info, blob = shim.load_model(os.path.join(a.model, "Whisper.asrmodel"))
         cfg = cfgm.WhisperConfig(**info["config"])
@@ -213,7 +244,11 @@ def main():
                    help="f32 = verification mode (the mode whose tokens equal the reference's); fp8w = Whisper / Qwen3-ASR, opt-in e4m3 decoder weights (Whisper: and cross-K/V); fp8mm = fp8w + encoder FFN on the FP8 matrix pipe; mxfp4w = fp8w with the Whisper decoder weights as OCP MXFP4")
     r.add_argument("--sliding-window", type=int, default=0)
     r.add_argument("--repeat-penalty", type=float, default=1.0, help="1.0 = plain greedy (the comparison default); the reference scripts default to 0.8")
-    r.add_argument("--beam", type=int, default=1, help="beam width (Whisper, Qwen3-ASR; 1 = greedy); > 1 takes the first hypothesis and needs --repeat-penalty 1")
+    r.add_argument("--beam", type=int, default=1, help="beam width (Whisper, Qwen3-ASR; 1 = greedy); > 1 takes the first hypothesis and needs --repeat-penalty 1. "
+                        "SenseVoice: CTC prefix beam search over the beam best tokens of every frame (1..16)")
+    r.add_argument("--nbest", type=int, default=1, help="SenseVoice: keep the N best hypotheses of every window in the dump (1..beam), with their scores")
+    r.add_argument("--hotwords", metavar="FILE", help="SenseVoice: phrases the beam search favours, one per line: token ids, or text with --tokenizer")
+    r.add_argument("--hotword-boost", type=float, default=2.0, help="SenseVoice: log-probability bonus per matched hotword token")
     r.add_argument("--timestamps", action="store_true", help="SenseVoice: add each token's start / end (seconds) and mean frame log-probability to the dump; Paraformer: each token's start / end from its CIF fire row and its log-probability; Whisper: decode with timestamp tokens and add "
                         "segments (start / end in seconds, token ids, text with --tokenizer)")
     r.add_argument("--word-timestamps", action="store_true", help="Whisper: add each text token's start / end in seconds (cross-attention DTW on the bundle's "
