@@ -66,6 +66,32 @@ class WhisperAlignDesc(C.Structure):
                 ("scores", _fp), ("stats", _fp), ("cost", _fp), ("frames", _ip), ("path", _ip), ("path_stride", C.c_int32), ("path_len", _ip)]
 
 
+class HotwordDesc(C.Structure):
+    _fields_ = [("op", C.c_int32), ("rows", C.c_int32), ("n_valid", C.c_int32), ("ld", C.c_int32), ("logits", _fp), ("vec", _fp),
+                ("ids", _ip), ("offsets", _ip), ("n_phrases", C.c_int32), ("boost", C.c_float), ("node", _ip), ("n_saved", C.c_int32),
+                ("next_in", _ip), ("root_save", _fp), ("n_root", C.c_int32), ("K", C.c_int32), ("topv", _fp), ("topi", _ip), ("lse", _fp)]
+
+
+class HotwordHeadDesc(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("n_valid", C.c_int32), ("ld", C.c_int32), ("steps", C.c_int32), ("logits", _fp), ("vec", _fp),
+                ("ld_save", C.c_int32), ("range", C.c_int32), ("partial", C.c_int32), ("value", C.c_float),
+                ("sampling", C.c_int32), ("K", C.c_int32), ("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
+                ("seed", C.c_uint64), ("noise", _fp),
+                ("timestamps", C.c_int32), ("ts_begin", C.c_int32), ("no_timestamps_id", C.c_int32), ("eot_id", C.c_int32), ("max_initial", C.c_int32),
+                ("scores", C.c_int32), ("ids", _ip), ("offsets", _ip), ("n_phrases", C.c_int32), ("boost", C.c_float),
+                ("picks", _ip), ("save_ids", _ip), ("n_saved_after", C.c_int32), ("nodes", _ip), ("logprob", _fp), ("logits_out", _fp),
+                ("timed", C.c_int32), ("head_ms", C.c_float)]
+
+
+class HotwordRankDesc(C.Structure):
+    _fields_ = [("n_utt", C.c_int32), ("beam", C.c_int32), ("tab_ld", C.c_int32), ("first", C.c_int32), ("n_slots", C.c_int32), ("n_stop", C.c_int32),
+                ("n_valid", C.c_int32), ("ld", C.c_int32), ("logits", _fp), ("vec", _fp),
+                ("ids", _ip), ("offsets", _ip), ("n_phrases", C.c_int32), ("boost", C.c_float),
+                ("cum", _fp), ("fin", _ip), ("len", _ip), ("next", _ip), ("done", _ip), ("stop", _ip),
+                ("src_in", _ip), ("tok_in", _ip), ("src_out", _ip), ("tok_out", _ip), ("node_in", _ip), ("node_out", _ip), ("topv", _fp), ("topi", _ip),
+                ("iters", C.c_int32), ("ms_topk", C.c_float), ("ms_rerank", C.c_float)]
+
+
 SIGNATURES = {
     "asr_probe_gemm": (C.c_int, [C.POINTER(GemmDesc)]),
     "asr_probe_ctc_head": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, _ip, _fp, _ip, C.c_char_p]),
@@ -81,6 +107,9 @@ SIGNATURES = {
     "asr_probe_beam_select": (C.c_int, [C.POINTER(BeamSelectDesc)]),
     "asr_probe_token_head": (C.c_int, [C.POINTER(TokenHeadDesc)]),
     "asr_probe_whisper_align": (C.c_int, [C.POINTER(WhisperAlignDesc)]),
+    "asr_probe_hotword": (C.c_int, [C.POINTER(HotwordDesc)]),
+    "asr_probe_hotword_head_steps": (C.c_int, [C.POINTER(HotwordHeadDesc)]),
+    "asr_probe_hotword_rank": (C.c_int, [C.POINTER(HotwordRankDesc)]),
     "asr_probe_decode_attention_beam": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p]),
     "asr_probe_gemm_counts": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "asr_probe_live_device_bytes": (C.c_int, [C.POINTER(C.c_int64)]),
@@ -463,6 +492,131 @@ def head_steps(logits, steps, ld_save, range_, value, partial, bias=None, track_
     if timed:
         out["head_ms"] = float(d.head_ms)
     return out
+
+
+def _pad_rows(logits):
+    """[..., n_valid] -> ([..., ld] with PAD_LOGIT in the pad columns, n_valid, ld): the sessions' leading dimension, as token_head pads."""
+    logits = _f32(logits)
+    n_valid = logits.shape[-1]
+    ld = (n_valid + 127) // 128 * 128
+    padded = np.full(logits.shape[:-1] + (ld,), PAD_LOGIT, np.float32)
+    padded[..., :n_valid] = logits
+    return padded, n_valid, ld
+
+
+def _phrases(d, phrases, boost, keep):
+    """Flatten token-id lists into the ids / offsets / n_phrases / boost fields of a hotword descriptor."""
+    phrases = [np.asarray(p, np.int32).reshape(-1) for p in phrases]
+    offs = np.zeros(len(phrases) + 1, np.int32)
+    offs[1:] = np.cumsum([p.size for p in phrases])
+    ids = np.ascontiguousarray(np.concatenate(phrases) if phrases else np.zeros(1, np.int32), np.int32)
+    keep += [ids, offs]
+    d.ids, d.offsets, d.n_phrases, d.boost = ids.ctypes.data_as(_ip), offs.ctypes.data_as(_ip), len(phrases), float(boost)
+
+
+def hotword_op(op, phrases, boost, node, logits=None, n_saved=1, next_ids=None, bias=None, K=0, n_root=0):
+    """One hotword kernel on host arrays (asr_probe_hotword). op "bias": logits [rows][n_valid] -> {"logits" [rows][ld] after the update, "root_save"
+    [rows][n_root] when n_root > 0 (NaN where nothing was saved)}; "advance": next_ids -> {"node"}; "rerank": launch_beam_topk + launch_hotword_rerank ->
+    {"topv", "topi" [rows][K], "lse" [rows]}. node [rows]: the rows' trie nodes; n_saved: the device counter (0: every row counts as at the root)."""
+    d, keep, out = HotwordDesc(), [], {}
+    d.op = {"bias": 0, "advance": 1, "rerank": 2}[op]
+    node = np.array(node, np.int32, order="C", copy=True)
+    d.rows, d.node, d.n_saved = node.size, node.ctypes.data_as(_ip), int(n_saved)
+    _phrases(d, phrases, boost, keep)
+    if logits is not None:
+        out["logits"], d.n_valid, d.ld = _pad_rows(logits)
+        d.logits = out["logits"].ctypes.data_as(_fp)
+        if bias is not None:
+            v = np.zeros(d.ld, np.float32)
+            v[:d.n_valid] = _f32(bias)
+            keep.append(v); d.vec = v.ctypes.data_as(_fp)
+    if next_ids is not None:
+        nx = np.ascontiguousarray(next_ids, np.int32)
+        keep.append(nx); d.next_in = nx.ctypes.data_as(_ip)
+    if op == "bias" and n_root:
+        out["root_save"] = np.full((node.size, n_root), np.nan, np.float32)
+        d.root_save, d.n_root = out["root_save"].ctypes.data_as(_fp), n_root
+    if op == "rerank":
+        out["topv"], out["topi"], out["lse"] = np.zeros((node.size, K), np.float32), np.zeros((node.size, K), np.int32), np.zeros(node.size, np.float32)
+        d.K, d.topv, d.topi, d.lse = K, out["topv"].ctypes.data_as(_fp), out["topi"].ctypes.data_as(_ip), out["lse"].ctypes.data_as(_fp)
+    _lib.check(load().asr_probe_hotword(C.byref(d)))
+    out["node"] = node
+    return out
+
+
+def hotword_head_steps(logits, phrases, boost, ld_save, range_=4, value=1.0, partial=0, bias=None, sampler=None, noise=None, timestamps=None, scores=False,
+                       want_logits=False, timed=0):
+    """A TokenHead with hotwords driven through logits [steps][rows][n_valid], a different row per step (asr_probe_hotword_head_steps): step 0 is a prefill
+    (`bias` added, no penalty). sampler: (temperature, top_k, top_p, repetition_penalty, seed); noise [steps][rows][top_k]: caller uniforms for every step;
+    timestamps: (ts_begin, no_timestamps_id, eot_id, max_initial). An empty phrase list leaves the mode off.
+    Returns {"picks" [steps][rows], "save_ids" [rows][ld_save], "n_saved", "nodes" [steps][rows] (-1 with the mode off)} and "logprob" [rows][ld_save] with
+    scores, "logits" [steps][rows][ld] with want_logits. timed = N > 0 (arg-max head): logits holds one step's rows [1][rows][n_valid], reused by N steps
+    whose launches run back to back between two device events -> "head_ms" (tools/probes/hotword_timing.py); picks and histories are not results then."""
+    d, keep = HotwordHeadDesc(), []
+    padded, n_valid, ld = _pad_rows(logits)
+    steps, rows = padded.shape[:2]
+    if timed:
+        assert steps == 1
+        steps = int(timed)
+    d.rows, d.n_valid, d.ld, d.steps, d.logits = rows, n_valid, ld, steps, padded.ctypes.data_as(_fp)
+    if bias is not None:
+        v = np.zeros(ld, np.float32)
+        v[:n_valid] = _f32(bias)
+        keep.append(v); d.vec = v.ctypes.data_as(_fp)
+    d.ld_save, d.range, d.partial, d.value = ld_save, range_, partial, value
+    if sampler is not None:
+        d.sampling, (d.temperature, d.K, d.top_p, d.repetition_penalty, d.seed) = 1, sampler
+    if noise is not None:
+        noise = _f32(noise)
+        assert noise.shape == (steps, rows, d.K)
+        d.noise = noise.ctypes.data_as(_fp)
+    if timestamps is not None:
+        d.timestamps, (d.ts_begin, d.no_timestamps_id, d.eot_id, d.max_initial) = 1, (int(v) for v in timestamps)
+    _phrases(d, phrases, boost, keep)
+    out = {"picks": np.full((steps, rows), -1, np.int32), "save_ids": np.full((rows, ld_save), -1, np.int32), "nodes": np.full((steps, rows), -1, np.int32)}
+    d.picks, d.save_ids, d.nodes = (out[k].ctypes.data_as(_ip) for k in ("picks", "save_ids", "nodes"))
+    if scores:
+        out["logprob"] = np.zeros((rows, ld_save), np.float32)
+        d.scores, d.logprob = 1, out["logprob"].ctypes.data_as(_fp)
+    if want_logits:
+        out["logits"] = np.zeros_like(padded)
+        d.logits_out = out["logits"].ctypes.data_as(_fp)
+    d.timed = int(bool(timed))
+    _lib.check(load().asr_probe_hotword_head_steps(C.byref(d)))
+    out["n_saved"] = d.n_saved_after
+    if timed:
+        out["head_ms"] = float(d.head_ms)
+    return out
+
+
+def hotword_rank(logits, phrases, boost, beam, n_slots, cum, fin, length, nxt, done, src_in, tok_in, node_in, stop=(), first=False, bias=None, iters=0):
+    """One ranking pass of the beam search with hotwords (asr_probe_hotword_rank): beam_topk + re-rank + select with the node hand-over, on logits
+    [rows][n_valid] ([n_utt][n_valid] when first). Returns the state, the tables written (from a -1 fill), "node_out" and the re-ranked "topv" / "topi"."""
+    d, keep = HotwordRankDesc(), []
+    f32 = lambda x: np.array(x, np.float32, order="C", copy=True)
+    i32 = lambda x: np.array(x, np.int32, order="C", copy=True)
+    padded, n_valid, ld = _pad_rows(logits)
+    st = dict(cum=f32(cum), fin=i32(fin), len=i32(length), next=i32(nxt), done=i32(done), stop=i32(list(stop) or [0]), src_in=i32(src_in), tok_in=i32(tok_in),
+              node_in=i32(node_in))
+    st["src_out"], st["tok_out"] = np.full_like(st["src_in"], -1), np.full_like(st["tok_in"], -1)
+    st["node_out"] = np.full_like(st["node_in"], -1)
+    st["topv"], st["topi"] = np.zeros((len(padded), beam), np.float32), np.zeros((len(padded), beam), np.int32)
+    d.n_utt, d.beam, d.tab_ld, d.first, d.n_slots, d.n_stop = st["done"].size, beam, st["src_in"].shape[1], int(first), n_slots, len(stop)
+    d.n_valid, d.ld, d.logits = n_valid, ld, padded.ctypes.data_as(_fp)
+    if bias is not None:
+        v = np.zeros(ld, np.float32)
+        v[:n_valid] = _f32(bias)
+        keep.append(v); d.vec = v.ctypes.data_as(_fp)
+    _phrases(d, phrases, boost, keep)
+    for k in ("cum", "topv"):
+        setattr(d, k, st[k].ctypes.data_as(_fp))
+    for k in ("fin", "len", "next", "done", "stop", "src_in", "tok_in", "src_out", "tok_out", "node_in", "node_out", "topi"):
+        setattr(d, k, st[k].ctypes.data_as(_ip))
+    d.iters = int(iters)
+    _lib.check(load().asr_probe_hotword_rank(C.byref(d)))
+    if iters:
+        st["ms_topk"], st["ms_rerank"] = float(d.ms_topk), float(d.ms_rerank)
+    return st
 
 
 def _bf16_bits(x):

@@ -4,6 +4,7 @@
 #include <map>
 
 #include "engine.h"
+#include "hot_trie.h"
 #include "kernels.h"
 
 namespace {
@@ -132,31 +133,6 @@ __device__ __forceinline__ uint64_t hash_step(uint64_t h, int c) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ int trie_child(const HotTrie& tr, int node, int c) {
-  int lo = tr.child_off[node], hi = tr.child_off[node + 1];
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    const int t = tr.child_tok[mid];
-    if (t == c) return tr.child_node[mid];
-    if (t < c) lo = mid + 1; else hi = mid;
-  }
-  return -1;
-}
-
-// (node, bonus) after appending the non-blank token c: a child c -> there, + boost, back to the root when it ends a phrase (the bonus stays); no child and
-// not at the root -> the partial match is taken back, then the root's child c by the same rule. No fail links.
-__device__ __forceinline__ void trie_step(const HotTrie& tr, int& node, float& bonus, int c) {
-  if (tr.n_nodes <= 1) return;
-  int ch = trie_child(tr, node, c);
-  if (ch < 0 && node != 0) {
-    bonus -= (float)tr.depth[node] * tr.boost;
-    node = 0;
-    ch = trie_child(tr, 0, c);
-  }
-  if (ch >= 0) { bonus += tr.boost; node = tr.is_end[ch] ? 0 : ch; }
-  else node = 0;
 }
 
 struct BeamLive {                     // the live prefixes of one frame, in rank order

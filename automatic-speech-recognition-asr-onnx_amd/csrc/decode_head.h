@@ -3,6 +3,7 @@
 // Header-only and hidden: the sessions and the probe library each compile their own copy, the product library exports nothing new.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "engine.h"
@@ -33,6 +34,19 @@ struct ASR_LOCAL TimestampRule {
   }
 };
 
+// ---- hotwords (kernels.h: launch_hotword_*) as the beam ranker takes them from the head: the trie view, and the root children's values the head
+// saved when it biased the prefill's row in place (null: that row is the model's own)
+struct ASR_LOCAL HotView {
+  HotTrie trie;
+  const float* root_save = nullptr;
+  bool on() const { return trie.n_nodes > 1; }
+};
+struct ASR_LOCAL HotScope {            // the hotword launches of the head and the ranker are a profile class of their own, as the timestamp rules are
+  Profiler* p; hipStream_t s;
+  HotScope(Profiler* p_, hipStream_t s_) : p(p_ && p_->enabled ? p_ : nullptr), s(s_) { if (p) p->begin(p->cls("hotwords"), s); }
+  ~HotScope() { if (p) p->end(s); }
+};
+
 // ---- token-selection head (Export_Whisper.py:228-325, Inference_Qwen_ASR_ONNX.py:369-376): arg-max, penalty-greedy (APPLY_PENALTY + GREEDY_SEARCH) or
 // TOPK_TOPP_SAMPLING, and the history of picked ids [rows][ld_save] the last two read. What differs between the families is data, set by init().
 struct ASR_LOCAL TokenHead {
@@ -56,6 +70,13 @@ struct ASR_LOCAL TokenHead {
   DeviceBuffer d_noise;                // caller-supplied uniforms [rows][top_k] for the next step (parity tests); consumed once
   bool noise_armed = false;            // a step with armed noise is not graphable
   uint64_t epoch = 0;                  // moves with everything a captured step bakes in: a setter that changed a value, a history buffer that moved
+  // hotwords: the trie image on the device (its words are kernel operands: a new list moves the epoch), every row's node, and the root children's values of
+  // the row a prefill biased (the beam ranker's first pass restores them). Off (hot_nodes <= 1) nothing is allocated and no step launches anything new.
+  DeviceBuffer d_trie, d_node, d_rootsave;
+  int hot_nodes = 0, hot_root = 0, node_rows = 0;
+  float hot_boost = 0.0f;
+  uint64_t hot_gen = 0, biased_gen = 0;   // the list's generation, and the one the last prefill row was biased with
+  bool row_biased = false;             // the logits row of the last prefill carries the bias (restart clears)
 
   void init(int ld_save_, int partial_, int default_range, int sampling_ld_limit_) {
     ld_save = ld_save_; partial = partial_; penalty_range = default_range; sampling_ld_limit = sampling_ld_limit_;
@@ -92,6 +113,43 @@ struct ASR_LOCAL TokenHead {
   void set_scores(bool enable) {
     if (scores != enable) { scores = enable; scored = false; ++epoch; }
   }
+  bool hot() const { return hot_nodes > 1; }
+  HotTrie hot_trie() const { return hot() ? hot_trie_view(d_trie.as<int32_t>(), hot_nodes, hot_boost) : HotTrie{}; }
+  // what the beam ranker needs; `who` fails when the prefill's row was biased with another list than the current one (it cannot be restored)
+  HotView hot_view(const char* who) const {
+    ASR_REQUIRE(!row_biased || biased_gen == hot_gen, "%s: the hotword list changed since the prefill; prefill again", who);
+    HotView v;
+    v.trie = hot_trie();
+    if (row_biased && hot()) v.root_save = d_rootsave.as<float>();
+    return v;
+  }
+  // phrases as flattened ids + offsets [n_phrases + 1] (asr_sensevoice_set_hotwords' shape); an empty list switches the mode off. Checked before anything
+  // changes: ids in [0, vocab), no empty phrase, a finite boost. Every row's node goes back to the root.
+  void set_hotwords(const int32_t* ids, const int32_t* offsets, int n_phrases, float boost, int vocab, hipStream_t s, const char* who) {
+    ASR_REQUIRE(n_phrases >= 0 && (n_phrases == 0 || (ids && offsets)) && std::isfinite(boost), "%s: bad argument", who);
+    if (n_phrases > 0) {
+      ASR_REQUIRE(offsets[0] >= 0, "%s: offsets[0] = %d", who, offsets[0]);
+      for (int p = 0; p < n_phrases; ++p) {
+        ASR_REQUIRE(offsets[p + 1] > offsets[p], "%s: phrase %d is empty", who, p);
+        for (int32_t i = offsets[p]; i < offsets[p + 1]; ++i)
+          ASR_REQUIRE(ids[i] >= 0 && ids[i] < vocab, "%s: phrase %d holds token %d (vocabulary %d)", who, p, ids[i], vocab);
+      }
+    }
+    HIP_CHECK(hipStreamSynchronize(s));                  // (nothing in flight reads the image that is about to change)
+    if (n_phrases == 0) { hot_nodes = 0; hot_root = 0; hot_boost = 0.0f; }
+    else {
+      int n = 0;
+      const std::vector<int32_t> words = build_hot_trie(ids, offsets, n_phrases, &n);
+      d_trie.reserve(words.size() * 4, s);
+      HIP_CHECK(hipMemcpyAsync(d_trie.ptr, words.data(), words.size() * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      hot_nodes = n; hot_boost = boost;
+      hot_root = words[(size_t)2 * n + 1];               // child_off[1]: the root's children
+    }
+    if (d_node.ptr && node_rows > 0) HIP_CHECK(hipMemsetAsync(d_node.ptr, 0, (size_t)node_rows * 4, s));
+    ++hot_gen;
+    ++epoch;
+  }
   void arm_noise(const float* uniforms, int count, hipStream_t s) {
     d_noise.reserve((size_t)count * 4, s);
     HIP_CHECK(hipMemcpyAsync(d_noise.ptr, uniforms, (size_t)count * 4, hipMemcpyHostToDevice, s));
@@ -103,14 +161,25 @@ struct ASR_LOCAL TokenHead {
     bool moved = reserve_moved(d_nsaved, 256, s);
     moved |= reserve_moved(d_save, (size_t)rows * ld_save * 4, s);
     if (scores) { moved |= reserve_moved(d_scores, (size_t)rows * ld_save * 4, s); score_rows = rows; }
+    if (hot()) {
+      if (reserve_moved(d_node, (size_t)std::max(rows, 64) * 4, s) || rows > node_rows) {       // fresh rows start at the root
+        moved = true;
+        HIP_CHECK(hipMemsetAsync(d_node.ptr, 0, (size_t)std::max(rows, 64) * 4, s));
+      }
+      node_rows = std::max(node_rows, rows);
+      moved |= reserve_moved(d_rootsave, (size_t)rows * std::max(hot_root, 1) * 4, s);
+    }
     if (moved) ++epoch;
   }
-  void restart(hipStream_t s) { HIP_CHECK(hipMemsetAsync(d_nsaved.ptr, 0, 4, s)); scored = scores; }      // every prefill starts from an empty history (ids and scores: one counter)
+  void restart(hipStream_t s) { HIP_CHECK(hipMemsetAsync(d_nsaved.ptr, 0, 4, s)); scored = scores; row_biased = false; }      // every prefill starts from an empty history (ids and scores: one counter)
 
   // The head's launches on logits [rows][ld]: picks go to next [rows]. bias: Whisper's BEGIN_SUPPRESS after a prefill, else null. penalise: false on a
   // prefill (the prefill graphs select from the raw logits with an empty history; the decode graphs apply the penalty first). Timestamp mode: the rules
   // run on both, after the penalty and before the selection (an empty history is their initial rule). Scores mode: the arg-max is the fused kernel, the
   // sampler is followed by the at-id kernel (it sees the sampler's in-place repetition penalty), the pick joins the history; off, nothing new is launched.
+  // Hotwords: the sparse bias (launch_hotword_bias) after the penalty and before the timestamp rules, so the selection, rule 5 and the token score all read
+  // the biased row ("the row the selection sees"), and logits_out of the step shows it; the node follows the pick in the launch that appends it. Every pick
+  // joins the history. Off, nothing new is launched.
   void enqueue(float* logits, int ld, int rows, int n_valid, const float* bias, bool penalise, int32_t* next, hipStream_t s) {
     const bool penalised = penalty_value != 1.0f && !sampling;
     int32_t* save = d_save.as<int32_t>();
@@ -119,6 +188,13 @@ struct ASR_LOCAL TokenHead {
     ASR_REQUIRE(!scores || (d_scores.ptr && rows <= score_rows), "token scores: the score history holds %d rows, this step has %d (switch token scores on before the prefill)",
                 d_scores.ptr ? score_rows : 0, rows);
     if (penalised && penalise) launch_apply_penalty(logits, ld, rows, save, ld_save, n_saved, penalty_range, penalty_value, s, partial);
+    const HotTrie trie = hot_trie();
+    if (hot()) {
+      ASR_REQUIRE(d_node.ptr && rows <= node_rows, "hotwords: the node table holds %d rows, this step has %d", d_node.ptr ? node_rows : 0, rows);
+      HotScope hs(prof, s);
+      launch_hotword_bias(logits, ld, rows, n_valid, trie, d_node.as<int32_t>(), n_saved, penalise ? nullptr : d_rootsave.as<float>(), s);
+      if (!penalise) { row_biased = true; biased_gen = hot_gen; }
+    }
     if (ts.on) ts.enqueue(prof, logits, ld, rows, n_valid, save, ld_save, n_saved, 0, s);
     if (sampling) {                        // the bias first, history = every sampled id
       SampleArgs sa;
@@ -137,8 +213,13 @@ struct ASR_LOCAL TokenHead {
     } else {
       launch_argmax_rows(logits, ld, rows, n_valid, bias, next, s);
     }
-    if (penalised || sampling || track_history || ts.on || scores) {   // GREEDY_SEARCH / the sampling head append their pick to the history
-      launch_append_ids(next, rows, save, ld_save, n_saved, s);
+    if (penalised || sampling || track_history || ts.on || scores || hot()) {   // GREEDY_SEARCH / the sampling head append their pick to the history
+      if (hot()) {                         // the append and the node's step are one launch: the mode adds the bias kernel to a head that keeps a history
+        HotScope hs(prof, s);
+        launch_hotword_advance(next, rows, trie, d_node.as<int32_t>(), n_saved, s, save, ld_save);
+      } else {
+        launch_append_ids(next, rows, save, ld_save, n_saved, s);
+      }
       launch_add_scalar(n_saved, 1, s);
     }
   }
@@ -174,6 +255,8 @@ struct ASR_LOCAL TokenHead {
 // double-buffered ancestry / token tables [rows][ld] and the ids of the next pass, all on the device. The family keeps its hypothesis caches and its decoder pass.
 struct ASR_LOCAL BeamRanker {
   DeviceBuffer topv, topi, cum, fin, len, done, next, stop, src[2], tok[2];
+  DeviceBuffer node[2], lse;           // hotwords: the rows' trie nodes, double-buffered with `cur` like src / tok, and beam_topk's log-sum-exp per row
+  HotView hot;                         // set by begin (the head's); off, no pass launches anything new
   PinnedBuffer stage;                  // its own: a prefill called with null outputs may still be copying from the session's. [0, done_off) stop ids, then done flags
   uint64_t epoch = 0;                  // moves when a buffer moved: a captured step that ranks is stale
   int B = 0, beam = 0, ld = 0, n_stop = 0, done_off = 0, cur = 0;
@@ -186,14 +269,15 @@ struct ASR_LOCAL BeamRanker {
   const int32_t* ancestry() const { return src[cur].as<int32_t>(); }     // the table the next pass's self-attention follows
   int32_t* next_ids() const { return next.as<int32_t>(); }
 
-  void begin(int B_, int beam_, int ld_, const int32_t* stop_ids, int n_stop_, const TimestampRule& ts_, hipStream_t s) {
-    B = B_; beam = beam_; ld = ld_; n_stop = n_stop_; cur = 0; slots_dev = nullptr; slots_off = 0; ts = ts_;
+  void begin(int B_, int beam_, int ld_, const int32_t* stop_ids, int n_stop_, const TimestampRule& ts_, const HotView& hot_, hipStream_t s) {
+    B = B_; beam = beam_; ld = ld_; n_stop = n_stop_; cur = 0; slots_dev = nullptr; slots_off = 0; ts = ts_; hot = hot_;
     const size_t N = (size_t)rows(), Nn = std::max<size_t>(N, 64);
     bool moved = false;
     for (DeviceBuffer* q : {&topv, &topi}) moved |= reserve_moved(*q, Nn * BEAM_MAX * 4, s);
     for (DeviceBuffer* q : {&cum, &fin, &len, &done, &next}) moved |= reserve_moved(*q, Nn * 4, s);
     moved |= reserve_moved(stop, (size_t)std::max(n_stop, 16) * 4, s);
     for (DeviceBuffer* q : {&src[0], &src[1], &tok[0], &tok[1]}) moved |= reserve_moved(*q, N * ld * 4, s);
+    if (hot.on()) for (DeviceBuffer* q : {&node[0], &node[1], &lse}) moved |= reserve_moved(*q, Nn * 4, s);
     if (moved) ++epoch;
     HIP_CHECK(hipStreamSynchronize(s));
     done_off = std::max(n_stop, 16);
@@ -204,12 +288,16 @@ struct ASR_LOCAL BeamRanker {
     }
     HIP_CHECK(hipMemsetAsync(done.ptr, 0, (size_t)B * 4, s));
     HIP_CHECK(hipMemsetAsync(len.ptr, 0, N * 4, s));
+    if (hot.on()) HIP_CHECK(hipMemsetAsync(node[0].ptr, 0, Nn * 4, s));        // every hypothesis starts at the root
   }
   // the first ranking: the prefill's logits, one row per utterance (+ bias: Whisper's BEGIN_SUPPRESS, as the arg-max head after a prefill). Timestamp mode:
-  // the rules with an empty history first (len is zero after begin; the token table is not read)
+  // the rules with an empty history first (len is zero after begin; the token table is not read). Hotwords: a row the head biased in place gets the model's
+  // own values back first -- a hypothesis score is log-soft-max(model) + delta, and a soft-max over the biased row would renormalise
   void rank_first(float* logits, int ld_logits, int n_valid, const float* bias, hipStream_t s) {
+    if (hot.on() && hot.root_save) { HotScope hs(prof, s); launch_hotword_restore(logits, ld_logits, B, n_valid, hot.trie, hot.root_save, s); }
     if (ts.on) ts.enqueue(prof, logits, ld_logits, B, n_valid, tok[cur].as<int32_t>(), ld, len.as<int32_t>(), 0, s);
-    launch_beam_topk(logits, ld_logits, B, n_valid, bias, beam, topv.as<float>(), topi.as<int32_t>(), s);
+    launch_beam_topk(logits, ld_logits, B, n_valid, bias, beam, topv.as<float>(), topi.as<int32_t>(), s, hot.on() ? lse.as<float>() : nullptr);
+    if (hot.on()) rerank(logits, ld_logits, B, n_valid, bias, beam, s);        // utterance b's one row is at the root, as node[cur][b * beam] says
     select(1, 0, s);
     flip();
   }
@@ -218,7 +306,8 @@ struct ASR_LOCAL BeamRanker {
   // Timestamp mode: the rules first, row r's history being its len[r] ids of the current token table.
   void enqueue_rank(float* logits, int ld_logits, int n_valid, int n_slots, hipStream_t s) {
     if (ts.on) ts.enqueue(prof, logits, ld_logits, rows(), n_valid, tok[cur].as<int32_t>(), ld, len.as<int32_t>(), 1, s);
-    launch_beam_topk(logits, ld_logits, rows(), n_valid, nullptr, beam, topv.as<float>(), topi.as<int32_t>(), s);
+    launch_beam_topk(logits, ld_logits, rows(), n_valid, nullptr, beam, topv.as<float>(), topi.as<int32_t>(), s, hot.on() ? lse.as<float>() : nullptr);
+    if (hot.on()) rerank(logits, ld_logits, rows(), n_valid, nullptr, 1, s);
     select(0, n_slots, s);
   }
   void flip() { cur ^= 1; }
@@ -248,6 +337,12 @@ struct ASR_LOCAL BeamRanker {
   }
 
  private:
+  // hotwords: the K best of topK u S by log-prob + delta, back into topv / topi (launch_hotword_rerank)
+  void rerank(const float* logits, int ld_logits, int n_rows, int n_valid, const float* bias, int node_stride, hipStream_t s) {
+    HotScope hs(prof, s);
+    launch_hotword_rerank(logits, ld_logits, n_rows, n_valid, bias, lse.as<float>(), hot.trie, node[cur].as<int32_t>(), node_stride, beam, topv.as<float>(),
+                          topi.as<int32_t>(), s);
+  }
   void select(int first, int n_slots, hipStream_t s) {
     BeamArgs a{};
     a.beam = beam; a.K = beam; a.ld = ld; a.first = first; a.n_slots = n_slots;
@@ -257,6 +352,7 @@ struct ASR_LOCAL BeamRanker {
     a.src_in = src[cur].as<int32_t>(); a.tok_in = tok[cur].as<int32_t>();
     a.src_out = src[cur ^ 1].as<int32_t>(); a.tok_out = tok[cur ^ 1].as<int32_t>();
     if (!first) { a.slots_dev = slots_dev; a.slots_off = slots_off; }
+    if (hot.on()) { a.node_in = node[cur].as<int32_t>(); a.node_out = node[cur ^ 1].as<int32_t>(); a.trie = hot.trie; }
     launch_beam_select(a, B, s);
   }
 };

@@ -111,11 +111,21 @@ template <typename T>
 void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s);
 const char* decode_attn_last_kernel();   // form of this thread's last launch_decode_attention ("self_wave", "self_beam", "cross_1pass[_fp8]", "general_n1[_fp8]", "general_n8[_fp8]"): test hook
 
+// The hotword context graph as the device sees it: node 0 is the root; children of node n are child_tok / child_node [child_off[n], child_off[n + 1]), sorted
+// by token. n_nodes <= 1: no hotwords (no pointer is read).
+struct HotTrie {
+  const int32_t *depth = nullptr, *is_end = nullptr, *child_off = nullptr, *child_tok = nullptr, *child_node = nullptr;
+  int n_nodes = 0;
+  float boost = 0.0f;
+};
+
 // ---- beam search ranking (Qwen3-ASR and Whisper; semantics of oracle/qwen_asr_oracle.py:beam_search_core). Hypotheses of utterance b are rows b * beam + r.
 constexpr int BEAM_MAX = 8;
 // per row: log-soft-max over the first n_valid columns of logits (+ bias[col] when bias is set: Whisper's BEGIN_SUPPRESS on the first ranking) and the
 // K best (log-prob, id) pairs, ties -> lower id: topv / topi [rows][K]
-void launch_beam_topk(const float* logits, int ld, int rows, int n_valid, const float* bias, int K, float* topv, int32_t* topi, hipStream_t s);
+// lse_out (nullable) [rows]: the log-sum-exp each row's topv was formed with (the hotword re-rank scores further columns against the very same value)
+void launch_beam_topk(const float* logits, int ld, int rows, int n_valid, const float* bias, int K, float* topv, int32_t* topi, hipStream_t s,
+                      float* lse_out = nullptr);
 struct BeamArgs {
   int beam, K, ld, first, n_slots;       // ld: row stride of the ancestry / token tables; n_slots: generated cache slots after this pass
   const float* topv; const int32_t* topi;
@@ -124,6 +134,10 @@ struct BeamArgs {
   const int32_t *src_in, *tok_in; int32_t *src_out, *tok_out;
   const int32_t* slots_dev = nullptr;    // when set, n_slots = *slots_dev + slots_off (a device counter: the pass replays from a captured graph)
   int slots_off = 0;
+  // hotwords (null: none): node_in / node_out [rows] the rows' trie nodes before / after the pass -- a kept row inherits its parent's node advanced by its
+  // token (trie_step); a finished hypothesis and the rows of a finished utterance keep theirs. first: every parent is at the root, node_in is not read.
+  const int32_t* node_in = nullptr; int32_t* node_out = nullptr;
+  HotTrie trie;
 };
 // one wave per utterance: rank the <= beam * K extensions (finished hypotheses stand as themselves), keep the best `beam` in order (score
 // descending, then hypothesis, then rank inside the hypothesis), rebuild the rows' ancestry / token tables from their parents'; done[b] = best has ended
@@ -156,6 +170,31 @@ void launch_apply_penalty(float* logits, int ld, int rows, const int32_t* save_i
                           int range, float value, hipStream_t s, int partial = 0);
 // save_ids[r][*n_saved] = next[r] (the counter itself is advanced by launch_add_scalar afterwards)
 void launch_append_ids(const int32_t* next, int rows, int32_t* save_ids, int ld_save, const int32_t* n_saved, hipStream_t s);
+
+// ---- hotword boosting of the autoregressive decoders (hotword.hip; the build's own mode, the float64 statement is tests/hotword_heads_ref.py).
+// Every row carries a node of the HotTrie; delta(c) is what trie_step would add to the bonus for token c from that node: + boost for a child of the node,
+// boost - depth * boost for a root child that is no child of the node, - depth * boost for everything else.
+//   launch_hotword_bias: delta + the row constant depth * boost, in place on the f32 logits [rows][ld], before the selection: children of the node get
+//     (float)(depth + 1) * boost, root children that are not children of the node get boost, nothing else is touched (a column in both lists is written once;
+//     -inf stays -inf). Arg-max, soft-max and log-soft-max do not see a row constant, so the sparse form selects and scores as the dense one would. The node
+//     is node[r], or the root while *n_saved == 0 (the step after a restart). root_save (nullable) [rows][child_off[1]]: while *n_saved == 0 the root
+//     children's values before the update, in child order (launch_hotword_restore puts them back: the beam ranker's first pass needs the model's own row).
+//   launch_hotword_advance: node[r] = trie_step(node[r] or the root while *n_saved == 0, next[r]); the pick need not be a valid column. Run it before the
+//     counter moves. O(1) per row: one thread per row. save_ids (nullable) [rows][ld_save]: the pick is also appended to the id history, by
+//     launch_append_ids' rule (the head's two per-row writes of a step in one launch; a full table drops the id and the node still moves).
+//   launch_hotword_rerank: the beam ranker's merge. topv / topi [rows][K] hold launch_beam_topk's pairs of the UNBIASED row and lse [rows] its lse_out;
+//     the K best of topK u S by (log-prob + delta, then id ascending) are written back, S = children of the row's node + children of the root scored as
+//     (logits + bias) - lse. A column at -inf is no candidate, a top-K entry that is also in S counts once, ranks past the last candidate are (-inf, 0).
+//     Among columns outside S delta is one constant, so nothing outside topK u S can enter. Row r's node is node[r * node_stride].
+// All take one wave per row and walk child lists longer than 64 in lane strides. Tokens of the trie must lie in [0, n_valid) (set_hotwords checks; the
+// kernels skip the others).
+void launch_hotword_bias(float* logits, int ld, int rows, int n_valid, const HotTrie& trie, const int32_t* node, const int32_t* n_saved, float* root_save,
+                         hipStream_t s);
+void launch_hotword_restore(float* logits, int ld, int rows, int n_valid, const HotTrie& trie, const float* root_save, hipStream_t s);
+void launch_hotword_advance(const int32_t* next, int rows, const HotTrie& trie, int32_t* node, const int32_t* n_saved, hipStream_t s,
+                            int32_t* save_ids = nullptr, int ld_save = 0);
+void launch_hotword_rerank(const float* logits, int ld, int rows, int n_valid, const float* bias, const float* lse, const HotTrie& trie, const int32_t* node,
+                           int node_stride, int K, float* topv, int32_t* topi, hipStream_t s);
 
 // ---- Whisper timestamp rules (OpenAI Whisper's ApplyTimestampRules; the reference has no timestamp mode, this one is the build's own). In place on the f32
 // logits [rows][ld], before the selection. Columns: [0, eot) text, eot, (eot, ts_begin) specials, [ts_begin, n_valid) timestamps. Row r's history is
@@ -353,13 +392,6 @@ void launch_ctc_collapse_timed(const int32_t* frame_ids, const float* frame_logp
                                int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, int32_t* num_id, hipStream_t s);
 
 // ---- CTC prefix beam search (ctc_beam.hip)
-// The hotword context graph as the device sees it: node 0 is the root; children of node n are child_tok / child_node [child_off[n], child_off[n + 1]), sorted
-// by token. n_nodes <= 1: no hotwords (no pointer is read).
-struct HotTrie {
-  const int32_t *depth = nullptr, *is_end = nullptr, *child_off = nullptr, *child_tok = nullptr, *child_node = nullptr;
-  int n_nodes = 0;
-  float boost = 0.0f;
-};
 // phrases (flattened ids, offsets [n_phrases + 1]) -> one int32 image [depth n][is_end n][child_off n + 1][child_tok n - 1][child_node n - 1]; hot_trie_view
 // points a HotTrie into a device copy of it
 std::vector<int32_t> build_hot_trie(const int32_t* ids, const int32_t* offsets, int n_phrases, int* n_nodes_out);

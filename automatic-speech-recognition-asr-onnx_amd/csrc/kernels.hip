@@ -1,6 +1,7 @@
 // Non-GEMM kernels of the ASR hot path for gfx950 (wave64, MFMA, LDS-staged tiles).
 #include "kernels.h"
 #include "gemm.h"
+#include "hot_trie.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -2930,7 +2931,7 @@ namespace {
 // (max, sum) pair and its own sorted best-8 list; the lists merge in K rounds of a block-wide arg-max.
 // bias (nullable): added to every column first; a -inf column (BEGIN_SUPPRESS through the bias, or a -inf logit) is left out of the soft-max as well.
 __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict__ logits, int ld, int n_valid, const float* __restrict__ bias, int K,
-                                                         float* __restrict__ topv, int32_t* __restrict__ topi) {
+                                                         float* __restrict__ topv, int32_t* __restrict__ topi, float* __restrict__ lse_out) {
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* p = logits + (size_t)row * ld;
   float tv[BEAM_MAX]; int ti[BEAM_MAX];
@@ -2972,6 +2973,7 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict
     float M = sm[0], S = ss[0];
     for (int w = 1; w < 16; ++w) merge(M, S, sm[w], ss[w]);
     lse_sh = M + logf(S);
+    if (lse_out) lse_out[row] = lse_sh;
   }
   for (int k = 0; k < K; ++k) {
     float bv = tv[0]; int bi = ti[0];
@@ -3003,7 +3005,7 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict
 __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
   const int b = blockIdx.x, lane = threadIdx.x, beam = a.beam, K = a.K, base = b * beam;
   const int n_slots = a.slots_dev ? *a.slots_dev + a.slots_off : a.n_slots;
-  __shared__ int par[BEAM_MAX], ntok[BEAM_MAX], nfin[BEAM_MAX], nlen[BEAM_MAX], nnext[BEAM_MAX];
+  __shared__ int par[BEAM_MAX], ntok[BEAM_MAX], nfin[BEAM_MAX], nlen[BEAM_MAX], nnext[BEAM_MAX], nnode[BEAM_MAX];
   __shared__ float ncum[BEAM_MAX];
   const bool frozen_utt = !a.first && a.done[b] != 0;
   const int r = lane / K, k = lane - r * K;
@@ -3035,6 +3037,12 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
     nfin[rank] = (frozen ? pf : (is_stop ? 1 : 0));
     nlen[rank] = pl + ((frozen || is_stop) ? 0 : 1);
     nnext[rank] = frozen ? pn : tokv;
+    if (a.node_in) {                                       // hotwords: the parent's trie node, advanced by the row's token unless the row stands as it is
+      int nd = a.first ? 0 : a.node_in[base + r];
+      float unused = 0.0f;
+      if (!frozen) trie_step(a.trie, nd, unused, tokv);
+      nnode[rank] = nd;
+    }
   }
   __syncthreads();
   // tables: row r' = parent's generated-slot ancestry + the parent itself for the slot written by this pass; parent's tokens + the new id.
@@ -3053,18 +3061,20 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
     a.cum[base + lane] = ncum[lane]; a.fin[base + lane] = nfin[lane]; a.len[base + lane] = nlen[lane]; a.next[base + lane] = nnext[lane];
   }
   if (lane == 0) a.done[b] = nfin[0];
+  if (a.node_in && lane < beam) a.node_out[base + lane] = nnode[lane];
 }
 
 }  // namespace
 
-void launch_beam_topk(const float* logits, int ld, int rows, int n_valid, const float* bias, int K, float* topv, int32_t* topi, hipStream_t s) {
+void launch_beam_topk(const float* logits, int ld, int rows, int n_valid, const float* bias, int K, float* topv, int32_t* topi, hipStream_t s, float* lse_out) {
   ASR_REQUIRE(K >= 1 && K <= BEAM_MAX && ld % 4 == 0, "beam_topk: K %d ld %d", K, ld);
-  hipLaunchKernelGGL(beam_topk_kernel, dim3(rows), dim3(1024), 0, s, logits, ld, n_valid, bias, K, topv, topi);
+  hipLaunchKernelGGL(beam_topk_kernel, dim3(rows), dim3(1024), 0, s, logits, ld, n_valid, bias, K, topv, topi, lse_out);
   HIP_CHECK(hipGetLastError());
 }
 
 void launch_beam_select(const BeamArgs& a, int n_utt, hipStream_t s) {
   ASR_REQUIRE(a.beam >= 1 && a.beam <= BEAM_MAX && a.K >= 1 && a.beam * a.K <= 64, "beam_select: beam %d K %d", a.beam, a.K);
+  ASR_REQUIRE(!a.node_in || (a.node_out && a.node_out != a.node_in), "beam_select: the hotword node tables are double-buffered");
   hipLaunchKernelGGL(beam_select_kernel, dim3(n_utt), dim3(64), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }

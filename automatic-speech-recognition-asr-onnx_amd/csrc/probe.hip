@@ -1421,3 +1421,198 @@ extern "C" int asr_probe_grid_barrier(int n_workgroups, int iters, float* us_per
     *us_per_barrier = ms * 1e3f / iters;
   });
 }
+
+// ---- hotword boosting of the autoregressive decoders (kernels.h: launch_hotword_*; asr_mi355x_probe.h)
+namespace {
+struct ProbeTrie {
+  HotTrie view;
+  int n_nodes = 0, n_root = 0;
+  // phrases -> the product's trie image on the device (build_hot_trie + hot_trie_view, as TokenHead::set_hotwords does); ids are checked against n_valid first
+  ProbeTrie(Tmp& t, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost, int n_valid, const char* who) {
+    ASR_REQUIRE(n_phrases >= 1 && ids && offsets && offsets[0] >= 0 && std::isfinite(boost), "%s: hotword phrases missing", who);
+    for (int p = 0; p < n_phrases; ++p) {
+      ASR_REQUIRE(offsets[p + 1] > offsets[p], "%s: phrase %d is empty", who, p);
+      for (int32_t i = offsets[p]; i < offsets[p + 1]; ++i) ASR_REQUIRE(ids[i] >= 0 && ids[i] < n_valid, "%s: phrase %d holds token %d (vocabulary %d)", who, p, ids[i], n_valid);
+    }
+    const std::vector<int32_t> words = build_hot_trie(ids, offsets, n_phrases, &n_nodes);
+    int32_t* dw = (int32_t*)t.alloc(words.size() * 4);
+    HIP_CHECK(hipMemcpy(dw, words.data(), words.size() * 4, hipMemcpyHostToDevice));
+    view = hot_trie_view(dw, n_nodes, boost);
+    n_root = words[(size_t)2 * n_nodes + 1];
+  }
+};
+}  // namespace
+
+extern "C" int asr_probe_hotword(asr_probe_hotword_desc* d) {
+  return asr_guard([&] {
+    const char* who = "probe_hotword";
+    ASR_REQUIRE(d && d->op >= 0 && d->op <= 2 && d->rows > 0 && d->node, "%s: bad descriptor", who);
+    ASR_REQUIRE(d->op == 1 || (d->logits && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0), "%s: logits missing", who);
+    asr_require_device(0);
+    Tmp t;
+    const int rows = d->rows;
+    ProbeTrie tr(t, d->ids, d->offsets, d->n_phrases, d->boost, d->op == 1 ? INT32_MAX : d->n_valid, who);
+    for (int r = 0; r < rows; ++r) ASR_REQUIRE(d->node[r] >= 0 && d->node[r] < tr.n_nodes, "%s: node %d of row %d outside the trie of %d", who, d->node[r], r, tr.n_nodes);
+    auto up = [&](const void* h, size_t bytes) -> void* {
+      void* p = t.alloc(std::max(bytes, (size_t)4));
+      HIP_CHECK(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+      return p;
+    };
+    int32_t* dnode = (int32_t*)up(d->node, (size_t)rows * 4);
+    const int32_t* dn = (const int32_t*)up(&d->n_saved, 4);
+    const size_t lbytes = d->op == 1 ? 0 : (size_t)rows * d->ld * 4;
+    float* dlog = lbytes ? (float*)up(d->logits, lbytes) : nullptr;
+    if (d->op == 0) {
+      float* dsave = nullptr;
+      if (d->root_save) { ASR_REQUIRE(d->n_root == tr.n_root, "%s: root_save is %d wide, the root has %d children", who, d->n_root, tr.n_root); dsave = (float*)up(d->root_save, (size_t)rows * d->n_root * 4); }
+      launch_hotword_bias(dlog, d->ld, rows, d->n_valid, tr.view, dnode, dn, dsave, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(d->logits, dlog, lbytes, hipMemcpyDeviceToHost));
+      if (dsave) HIP_CHECK(hipMemcpy(d->root_save, dsave, (size_t)rows * d->n_root * 4, hipMemcpyDeviceToHost));
+    } else if (d->op == 1) {
+      ASR_REQUIRE(d->next_in, "%s: advance without picks", who);
+      launch_hotword_advance((const int32_t*)up(d->next_in, (size_t)rows * 4), rows, tr.view, dnode, dn, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(d->node, dnode, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    } else {
+      ASR_REQUIRE(d->K >= 1 && d->K <= BEAM_MAX && d->topv && d->topi, "%s: rerank K %d", who, d->K);
+      const float* dvec = d->vec ? (const float*)up(d->vec, (size_t)d->ld * 4) : nullptr;
+      const size_t kb = (size_t)rows * d->K * 4;
+      float* dv = (float*)t.alloc(kb); int32_t* di = (int32_t*)t.alloc(kb); float* dl = (float*)t.alloc((size_t)rows * 4);
+      launch_beam_topk(dlog, d->ld, rows, d->n_valid, dvec, d->K, dv, di, nullptr, dl);
+      launch_hotword_rerank(dlog, d->ld, rows, d->n_valid, dvec, dl, tr.view, dnode, 1, d->K, dv, di, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipMemcpy(d->topv, dv, kb, hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(d->topi, di, kb, hipMemcpyDeviceToHost));
+      if (d->lse) HIP_CHECK(hipMemcpy(d->lse, dl, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    }
+  });
+}
+
+extern "C" int asr_probe_hotword_head_steps(asr_probe_hotword_head_desc* d) {
+  return asr_guard([&] {
+    const char* who = "probe_hotword_head_steps";
+    ASR_REQUIRE(d && d->rows > 0 && d->steps >= 1 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0 && d->logits && d->picks && d->save_ids && d->nodes,
+                "%s: bad descriptor", who);
+    ASR_REQUIRE(d->ld_save >= d->steps && d->ld_save <= 1024 && d->range >= 1 && d->range <= d->ld_save, "%s: %d steps / range %d and a history table of %d", who, d->steps,
+                d->range, d->ld_save);
+    ASR_REQUIRE(!d->scores || d->logprob, "%s: scores without the logprob table", who);
+    ASR_REQUIRE(!d->sampling || (d->K >= 1 && d->K <= d->n_valid), "%s: sampler top_k %d", who, d->K);
+    ASR_REQUIRE(!d->noise || d->sampling, "%s: noise without the sampler", who);
+    ASR_REQUIRE(!d->timed || (d->value == 1.0f && !d->sampling && !d->timestamps), "%s: timed steps need the arg-max head", who);
+    asr_require_device(0);
+    Tmp t;
+    const int rows = d->rows, ld = d->ld, steps = d->steps;
+    const size_t lbytes = (size_t)rows * ld * 4;
+    // timed: logits holds ONE step's rows, uploaded once and reused by every step (the bias accumulates in them: a timing, not a result), and the launches
+    // run back to back between two events; else one row buffer, uploaded before every step
+    float* dlog = (float*)t.alloc(lbytes);
+    if (d->timed) HIP_CHECK(hipMemcpy(dlog, d->logits, lbytes, hipMemcpyHostToDevice));
+    int32_t* dpick = (int32_t*)t.alloc((size_t)steps * rows * 4);
+    int32_t* dnodes = (int32_t*)t.alloc((size_t)steps * rows * 4);
+    float* dvec = nullptr;
+    if (d->vec) { dvec = (float*)t.alloc((size_t)ld * 4); HIP_CHECK(hipMemcpy(dvec, d->vec, (size_t)ld * 4, hipMemcpyHostToDevice)); }
+    TokenHead h;
+    h.init(d->ld_save, d->partial, d->range, 1024);
+    h.set_penalty(d->value, d->range, who);
+    if (d->sampling) h.set_sampling(true, d->temperature, d->K, d->top_p, d->repetition_penalty, d->seed, who);
+    if (d->timestamps) h.set_timestamps(true, d->ts_begin, d->no_timestamps_id, d->eot_id, d->max_initial, d->n_valid, who);
+    h.set_scores(d->scores != 0);
+    h.set_hotwords(d->ids, d->offsets, d->n_phrases, d->boost, d->n_valid, nullptr, who);
+    h.reserve(rows, nullptr);
+    h.restart(nullptr);
+    if (d->scores) HIP_CHECK(hipMemset(h.d_scores.ptr, 0xFF, (size_t)rows * d->ld_save * 4));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (d->timed) { HIP_CHECK(hipEventCreate(&ev[0])); HIP_CHECK(hipEventCreate(&ev[1])); HIP_CHECK(hipEventRecord(ev[0], nullptr)); }
+    d->head_ms = 0.0f;
+    for (int i = 0; i < steps; ++i) {
+      float* row = dlog;
+      if (!d->timed) HIP_CHECK(hipMemcpy(row, d->logits + (size_t)i * rows * ld, lbytes, hipMemcpyHostToDevice));
+      if (d->noise) h.arm_noise(d->noise + (size_t)i * rows * d->K, rows * d->K, nullptr);
+      h.enqueue(row, ld, rows, d->n_valid, i == 0 ? dvec : nullptr, i > 0, dpick + (size_t)i * rows, nullptr);
+      h.consumed();
+      if (h.hot() && !d->timed) HIP_CHECK(hipMemcpyAsync(dnodes + (size_t)i * rows, h.d_node.ptr, (size_t)rows * 4, hipMemcpyDeviceToDevice, nullptr));
+      if (d->logits_out && !d->timed) {
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(d->logits_out + (size_t)i * rows * ld, row, lbytes, hipMemcpyDeviceToHost));
+      }
+    }
+    if (d->timed) HIP_CHECK(hipEventRecord(ev[1], nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
+    if (d->timed) {
+      HIP_CHECK(hipEventElapsedTime(&d->head_ms, ev[0], ev[1]));
+      HIP_CHECK(hipEventDestroy(ev[0])); HIP_CHECK(hipEventDestroy(ev[1]));
+    }
+    HIP_CHECK(hipMemcpy(d->picks, dpick, (size_t)steps * rows * 4, hipMemcpyDeviceToHost));
+    if (h.hot() && !d->timed) HIP_CHECK(hipMemcpy(d->nodes, dnodes, (size_t)steps * rows * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->save_ids, h.d_save.ptr, (size_t)rows * d->ld_save * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&d->n_saved_after, h.d_nsaved.ptr, 4, hipMemcpyDeviceToHost));
+    if (d->scores) HIP_CHECK(hipMemcpy(d->logprob, h.d_scores.ptr, (size_t)rows * d->ld_save * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+extern "C" int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d) {
+  return asr_guard([&] {
+    const char* who = "probe_hotword_rank";
+    ASR_REQUIRE(d && d->n_utt > 0 && d->beam >= 1 && d->beam <= BEAM_MAX && d->beam * d->beam <= 64 && d->tab_ld > 0 && d->n_slots >= 0 && d->n_slots <= d->tab_ld &&
+                d->n_stop >= 0 && (d->n_stop == 0 || d->stop) && d->logits && d->n_valid >= d->beam && d->ld >= d->n_valid && d->ld % 128 == 0 && d->cum && d->fin && d->len &&
+                d->next && d->done && d->src_in && d->tok_in && d->src_out && d->tok_out && d->node_in && d->node_out && d->topv && d->topi, "%s: bad descriptor", who);
+    asr_require_device(0);
+    Tmp t;
+    const int N = d->n_utt * d->beam, R = d->first ? d->n_utt : N, K = d->beam;
+    ProbeTrie tr(t, d->ids, d->offsets, d->n_phrases, d->boost, d->n_valid, who);
+    for (int r = 0; r < N; ++r) {
+      ASR_REQUIRE(d->len[r] >= 0 && d->len[r] <= d->tab_ld, "%s: row %d length %d outside the table", who, r, d->len[r]);
+      ASR_REQUIRE(d->node_in[r] >= 0 && d->node_in[r] < tr.n_nodes, "%s: node %d of row %d outside the trie", who, d->node_in[r], r);
+    }
+    auto up = [&](const void* h, size_t bytes) -> void* {
+      void* p = t.alloc(std::max(bytes, (size_t)4));
+      HIP_CHECK(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+      return p;
+    };
+    const size_t tab = (size_t)N * d->tab_ld * 4, rows4 = (size_t)N * 4, kb = (size_t)R * K * 4;
+    float* dlog = (float*)up(d->logits, (size_t)R * d->ld * 4);
+    const float* dvec = d->vec ? (const float*)up(d->vec, (size_t)d->ld * 4) : nullptr;
+    float* dv = (float*)t.alloc(kb); int32_t* di = (int32_t*)t.alloc(kb); float* dl = (float*)t.alloc((size_t)R * 4);
+    BeamArgs a{};
+    a.beam = d->beam; a.K = K; a.ld = d->tab_ld; a.first = d->first; a.n_slots = d->n_slots;
+    a.topv = dv; a.topi = di;
+    a.cum = (float*)up(d->cum, rows4); a.fin = (int32_t*)up(d->fin, rows4); a.len = (int32_t*)up(d->len, rows4); a.next = (int32_t*)up(d->next, rows4);
+    a.done = (int32_t*)up(d->done, (size_t)d->n_utt * 4);
+    a.stop = d->n_stop ? (const int32_t*)up(d->stop, (size_t)d->n_stop * 4) : nullptr; a.n_stop = d->n_stop;
+    a.src_in = (const int32_t*)up(d->src_in, tab); a.tok_in = (const int32_t*)up(d->tok_in, tab);
+    a.src_out = (int32_t*)up(d->src_out, tab); a.tok_out = (int32_t*)up(d->tok_out, tab);
+    a.node_in = (const int32_t*)up(d->node_in, rows4); a.node_out = (int32_t*)up(d->node_out, rows4); a.trie = tr.view;
+    // the ranker's sequence (decode_head.h: BeamRanker::rank_first / enqueue_rank with hotwords on)
+    launch_beam_topk(dlog, d->ld, R, d->n_valid, dvec, K, dv, di, nullptr, dl);
+    launch_hotword_rerank(dlog, d->ld, R, d->n_valid, dvec, dl, tr.view, a.node_in, d->first ? d->beam : 1, K, dv, di, nullptr);
+    launch_beam_select(a, d->n_utt, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(d->topv, dv, kb, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->topi, di, kb, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->cum, a.cum, rows4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->fin, a.fin, rows4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->len, a.len, rows4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->next, a.next, rows4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->done, a.done, (size_t)d->n_utt * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->src_out, a.src_out, tab, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->tok_out, a.tok_out, tab, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->node_out, a.node_out, rows4, hipMemcpyDeviceToHost));
+    d->ms_topk = d->ms_rerank = 0.0f;
+    if (d->iters > 0) {                  // timing: beam_topk alone against beam_topk (lse_out) + re-rank, `iters` launches back to back (the pairs go to scratch)
+      hipEvent_t ev[2];
+      HIP_CHECK(hipEventCreate(&ev[0])); HIP_CHECK(hipEventCreate(&ev[1]));
+      for (int mode = 0; mode < 2; ++mode) {
+        HIP_CHECK(hipEventRecord(ev[0], nullptr));
+        for (int i = 0; i < d->iters; ++i) {
+          launch_beam_topk(dlog, d->ld, R, d->n_valid, dvec, K, dv, di, nullptr, mode ? dl : nullptr);
+          if (mode) launch_hotword_rerank(dlog, d->ld, R, d->n_valid, dvec, dl, tr.view, a.node_in, d->first ? d->beam : 1, K, dv, di, nullptr);
+        }
+        HIP_CHECK(hipEventRecord(ev[1], nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipEventElapsedTime(mode ? &d->ms_rerank : &d->ms_topk, ev[0], ev[1]));
+      }
+      HIP_CHECK(hipEventDestroy(ev[0])); HIP_CHECK(hipEventDestroy(ev[1]));
+    }
+  });
+}

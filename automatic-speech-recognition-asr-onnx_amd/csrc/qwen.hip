@@ -725,7 +725,7 @@ void QwSession::init() {
   ASR_REQUIRE(cpw >= 1 && rpw <= 1024, "qwen: bad attention window");
   vpad = round_up(c.vocab, 128);
   head.init(c.max_seq_len, 1, 10, 1024);
-  head.prof = &prof;
+  head.prof = &prof; ranker.prof = &prof;
   ASR_REQUIRE(c.classify_num >= 0, "qwen: classify_num %d", c.classify_num);
   hpad = aligner() ? round_up(c.classify_num, 128) : vpad;   // rows of dec.lm_head: the vocabulary, or the aligner's timestamp buckets
   cpad = round_up(c.conv_channels, 128);
@@ -1387,7 +1387,7 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
   max_new = std::min(max_new, c.max_seq_len - max_len);  // positions (RoPE rows) end at max_seq_len
   const int Sb = round_up(max_new, 16), ld = Sb;         // generated slots per hypothesis row; the prompts stay in the prefill cache
   // ---- the first ranking reads the prefill logits; do it before any buffer grows
-  ranker.begin(B, beam, ld, stop_ids, n_stop, TimestampRule{}, stream);
+  ranker.begin(B, beam, ld, stop_ids, n_stop, TimestampRule{}, head.hot_view("qwen_beam_search"), stream);
   ranker.rank_first(d_logits.as<float>(), vpad, c.vocab, nullptr, stream);
   // ---- hypothesis rows: caches, counters, row buffers, the one-row-per-hypothesis plan
   for (DeviceBuffer* q : {&d_bhist, &d_bp0}) q->reserve((size_t)std::max(N, 64) * 4, stream);
@@ -1495,6 +1495,14 @@ extern "C" int asr_qwen_track_history(asr_session* s, int enable) {
 extern "C" int asr_qwen_set_sampling(asr_session* s, int enable, float temperature, int top_k, float top_p, float repetition_penalty, uint64_t seed) {
   return asr_guard([&] {
     qwen_session(s, "qwen_set_sampling")->head.set_sampling(enable != 0, temperature, top_k, top_p, repetition_penalty, seed, "qwen_set_sampling");
+  });
+}
+
+extern "C" int asr_qwen_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost) {
+  return asr_guard([&] {
+    QwSession* q = qwen_session(s, "qwen_set_hotwords");
+    HIP_CHECK(hipSetDevice(q->device));
+    q->head.set_hotwords(ids, offsets, n_phrases, boost, q->cfg.vocab, q->stream, "qwen_set_hotwords");
   });
 }
 

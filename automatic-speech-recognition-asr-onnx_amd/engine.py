@@ -483,8 +483,47 @@ def _token_head(prefix: str, default_range: int, penalty_doc: str):
             _lib.check(entry("token_scores")(self._h, _fp(out), cap, _ip(n)))
             return out[:self.batch, :int(n[0])].copy()
 
+        def set_hotwords(self, phrases: Sequence[Sequence[int]], boost: float = 2.0):
+            """Hotword boosting of the decoder (asr_<family>_set_hotwords): token-id lists. Every sequence -- every hypothesis of beam_search -- carries a
+            node of the phrases' context graph that follows its own picks from the root after a prefill: a token that continues a phrase gains `boost`, a
+            token that breaks a partial match of depth d gives d * boost back. The selection heads see it as a sparse logit bias (a token score is the
+            log-soft-max of the biased row), beam_search as log-probability + bonus change. An empty list switches the mode off. Set it before the prefill.
+            Empty phrases, ids outside the vocabulary and a boost that is not finite raise AsrError and leave the list in force alone."""
+            ids, offs = _flatten_phrases(phrases)
+            _lib.check(entry("set_hotwords")(self._h, _ip(ids), _ip(offs), len(offs) - 1, C.c_float(boost)))
+
     TokenHeadMixin.set_penalty.__doc__ = penalty_doc
     return TokenHeadMixin
+
+
+def _flatten_phrases(phrases):
+    """Token-id lists -> (ids int32 [sum, at least 1], offsets int32 [n + 1]): the shape of the asr_*_set_hotwords entries."""
+    phrases = [np.asarray(p, dtype=np.int32).reshape(-1) for p in phrases]
+    offs = np.zeros(len(phrases) + 1, dtype=np.int32)
+    offs[1:] = np.cumsum([p.size for p in phrases])
+    ids = np.ascontiguousarray(np.concatenate(phrases) if phrases else np.zeros(0, np.int32), dtype=np.int32)
+    return (ids if ids.size else np.zeros(1, np.int32)), offs
+
+
+def hotword_id_variants(phrases, encode):
+    """Hotwords as the decoders' set_hotwords takes them: a text phrase becomes the distinct tokenisations of `phrase` and " " + phrase (byte-level BPE spells
+    a word differently at the start of the text and inside it; `encode`: text -> id list, without special tokens); id lists pass through unchanged. Order is
+    kept; duplicate and empty tokenisations of a text are dropped."""
+    out, seen = [], set()
+    for ph in phrases or []:
+        if isinstance(ph, str):
+            if encode is None:
+                raise ValueError("hotwords given as text need a tokenizer (tokenizer_path); pass token-id lists instead")
+            text = ph.strip()
+            variants = [list(map(int, encode(text))), list(map(int, encode(" " + text)))] if text else []
+        else:
+            out.append([int(t) for t in ph])
+            continue
+        for v in variants:
+            if v and tuple(v) not in seen:
+                seen.add(tuple(v))
+                out.append(v)
+    return out
 
 
 class WhisperSession(_token_head("whisper", 20, "Decode head: 1.0 = plain arg-max; else penalty-greedy (APPLY_PENALTY + GREEDY_SEARCH, the reference host's default)."),

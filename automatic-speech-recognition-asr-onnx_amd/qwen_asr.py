@@ -123,8 +123,14 @@ def export_qwen_asr(cfg: QwenAsrConfig, ck: dict, path: str, metadata: dict, pre
 class QwenAsrTranscriber:
     def __init__(self, cfg: QwenAsrConfig, session: QwenAsrSession, metadata: dict, tokenizer=None, normalise_audio: bool = False,
                  repeat_penalty: float = 1.0, penalty_range: int = 10, use_sampling: bool = False, temperature: float = 0.8, top_k: int = 10,
-                 top_p: float = 0.95, sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1, token_scores: bool = False):
+                 top_p: float = 0.95, sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1, token_scores: bool = False,
+                 hotwords=None, hotword_boost: float = 2.0):
         self.cfg, self.sess, self.tokenizer = cfg, session, tokenizer
+        # hotword boosting (the build's own: asr_qwen_set_hotwords): token-id lists, or text when a tokenizer is loaded (both spellings of a phrase, at the
+        # start of the text and inside it); in force for the prefill and every id after it, the beam search included
+        from .engine import hotword_id_variants
+        encode = (lambda t: tokenizer.encode(t, add_special_tokens=False)) if tokenizer is not None else None
+        self.hotwords, self.hotword_boost = hotword_id_variants(hotwords, encode), float(hotword_boost)
         # _resolve_strategy (:369-376): sampling wins; REPEAT_PENALTY == 1.0 selects greedy, any other value penalty-greedy (the
         # reference's defaults are 0.8 over PENALTY_RANGE = 10 ids)
         self.repeat_penalty, self.penalty_range = float(repeat_penalty), int(penalty_range)
@@ -180,11 +186,15 @@ class QwenAsrTranscriber:
         self.sess.set_sampling(*self.sampling)
         if self.token_scores:
             self.sess.set_token_scores(True)
+        if self.hotwords:
+            self.sess.set_hotwords(self.hotwords, self.hotword_boost)
         try:
             toks, limits, ids_len, scores = self._prefill_and_generate(audios, pre, post, max_new)
         finally:
             if self.token_scores:
                 self.sess.set_token_scores(False)
+            if self.hotwords:
+                self.sess.set_hotwords([])
         wall = time.time() - t0
         out = []
         for b in range(B):

@@ -33,6 +33,10 @@
   temperature_fallback    = OpenAI's decode fallback: an utterance whose avg_logprob is below logprob_threshold, or whose compression_ratio is above its
                             threshold, is decoded again by the sampler at the next temperature of the list (seed + attempt); the encoder output and the
                             cross-K/V stay, the full-prompt prefill restarts the rest. The last attempt stands.
+  hotwords=[...]          = this build's own mode (the reference has no bias of any kind): phrases -- token-id lists, or text with hotword_encoder -- the
+                            decoder favours (asr_whisper_set_hotwords): a pick that continues a phrase gains hotword_boost, a broken partial match gives its
+                            part back. In force from the full-prompt prefill to the last id of every decode (fallback attempts and beam_size > 1 included);
+                            the [SOT] probe and the forced alignment pass run without it.
 Batch extension: `transcribe` takes a list of independent clips as one batch (language detection / no-speech per clip);
 `transcribe_file` is the reference's per-file behaviour (the windows of one file form the batch).
 """
@@ -247,7 +251,14 @@ class WhisperTranscriber:
                  sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1,
                  timestamps: bool = False, max_initial_timestamp: float | None = 1.0, word_timestamps: bool = False, alignment_heads=None,
                  medfilt_width: int = 7, piece_decoder=None, token_scores: bool = False, temperature_fallback=None,
-                 compression_ratio_threshold: float | None = 2.4, logprob_threshold: float | None = -1.0):
+                 compression_ratio_threshold: float | None = 2.4, logprob_threshold: float | None = -1.0,
+                 hotwords=None, hotword_boost: float = 2.0, hotword_encoder=None):
+        # hotword boosting (the build's own: asr_whisper_set_hotwords): token-id lists, or text when hotword_encoder(text) -> ids is given (a tokenizer's
+        # encode without special tokens; a text phrase is boosted in both of its spellings, at the start of the text and inside it). The list is in force from
+        # the full-prompt prefill to the last id of every decode, fallback attempts and the beam search included; the [SOT] probe and the forced alignment
+        # pass run without it.
+        from .engine import hotword_id_variants
+        self.hotwords, self.hotword_boost = hotword_id_variants(hotwords, hotword_encoder), float(hotword_boost)
         if beam_size > 1 and (float(repeat_penalty) != 1.0 or use_sampling):
             raise ValueError("beam_size > 1 does not combine with a repeat penalty or sampling")
         # token scores / the temperature fallback (the build's own; thresholds are OpenAI's defaults, arguments and not measurements)
@@ -294,6 +305,8 @@ class WhisperTranscriber:
         self.sess.set_penalty(1.0, self.penalty_range)
         if self.timestamps:
             self.sess.set_timestamps(False)
+        if self.hotwords:
+            self.sess.set_hotwords([])                                      # language detection and the no-speech probability read raw logits
         return self.sess.prefill(np.full((B, 1), self.cfg.sot_id, dtype=np.int32))[1]
 
     def _prefill_and_continue(self, prompt: np.ndarray, limit: int, audio_samples=None, skip=None, sampling=None, align: bool = True):
@@ -314,6 +327,8 @@ class WhisperTranscriber:
             self.sess.set_token_scores(True)
         if live:
             self.sess.set_word_timestamps(True, self.alignment_heads, limit + 1)
+        if self.hotwords:
+            self.sess.set_hotwords(self.hotwords, self.hotword_boost)
         try:
             self.sess.prefill(prompt, want_logits=False)
             toks = self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * B
@@ -329,6 +344,8 @@ class WhisperTranscriber:
                 self.sess.set_token_scores(False)
             if live:
                 self.sess.set_word_timestamps(False)
+            if self.hotwords:
+                self.sess.set_hotwords([])
         if self.word_timestamps and not live and limit > 0 and align:
             frames = self._forced_alignment(prompt, [self._text_ids(tk) for tk in toks], audio_samples, skip)
         return toks, frames, scores

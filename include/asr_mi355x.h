@@ -312,6 +312,21 @@ int asr_whisper_set_sampling_noise(asr_session* s, const float* uniforms, int co
  * asr_whisper_generate (count = 1 + decode steps run: the stop pick and whatever a finished sequence picked while others went on are included) and after
  * hand-driven prefill / decode loops. Errors: the mode is off, or no prefill has run since it was switched on. */
 int asr_whisper_set_token_scores(asr_session* s, int enable);
+/* Hotword boosting of the decoder (the build's own mode, the reference has none): n_phrases token-id lists, phrase p = ids[offsets[p] ..
+ * offsets[p + 1]) (host), in the shape of asr_sensevoice_set_hotwords and with its context graph. Every sequence (in asr_whisper_beam_search every hypothesis)
+ * carries a node of the graph that follows its own picks -- the root after a prefill; prompt tokens and ids the host feeds to asr_whisper_decode do not move it.
+ * A token that continues the match gains `boost`; the node returns to the root when a phrase ends (the bonus stays); a token that breaks a partial match of
+ * depth d gives d * boost back, and the root's child is tried by the same rule. No fail links: a phrase that continues another complete phrase is unreachable.
+ * Selection head (arg-max, penalty-greedy, sampler): before every selection the logits row is biased in place -- children of the node + (d + 1) * boost, the
+ * root's other children + boost -- after the repeat penalty and before the timestamp rules; that is the bonus change plus the row constant d * boost, which
+ * no selection and no log-soft-max sees. logits_out of a step shows the biased row, and a token score (asr_whisper_set_token_scores) is the log-soft-max of
+ * the biased row. Every pick joins the device-side id history, as in timestamp mode. Beam search: a hypothesis score is log-soft-max(model)(c) + the bonus
+ * change of c, the refund included; scores_out reports these sums. A stop id picked inside a partial match pays the refund; a hypothesis cut off at max_new
+ * keeps the bonus of a match still open. The mode combines with the penalty, the sampler, the timestamp rules, token scores and beam search; word-timestamp
+ * capture and asr_whisper_align are unaffected. n_phrases == 0 clears the list: no step launches anything new and results are what they were without the mode.
+ * Every call returns all nodes to the root. Ids outside the vocabulary, empty phrases and a boost that is not finite are rejected (the list in force stays).
+ * Set the list before the prefill; asr_whisper_beam_search refuses a list that changed between the prefill and the search. */
+int asr_whisper_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
 int asr_whisper_token_scores(asr_session* s, float* logprob_out, int out_stride, int32_t* n_out);
 /* Segment timestamps: OpenAI Whisper's ApplyTimestampRules inside the decode head. The reference has no timestamp mode (it defines NO_TIMESTAMPS_TOKEN and
  * always puts it in the prompt), so -- like the beam search -- this mode is the build's own. With enable != 0 the prompt carries no <|notimestamps|> and,
@@ -400,6 +415,8 @@ int asr_qwen_set_sampling(asr_session* s, int enable, float temperature, int top
 int asr_qwen_set_sampling_noise(asr_session* s, const float* uniforms, int count);
 /* token scores, as asr_whisper_set_token_scores / asr_whisper_token_scores (no bias on the prefill step here) */
 int asr_qwen_set_token_scores(asr_session* s, int enable);
+/* hotword boosting, as asr_whisper_set_hotwords (no timestamp rules here; in asr_qwen_beam_search every hypothesis carries its node) */
+int asr_qwen_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
 int asr_qwen_token_scores(asr_session* s, float* logprob_out, int out_stride, int32_t* n_out);
 /* continuation after a prefill with the selected head (:687-745): tokens_out host [B][max_new], n_out host [B]; a sequence ends at
  * the first id in stop_ids (not emitted) or when the cache is full. */

@@ -203,6 +203,63 @@ typedef struct asr_probe_token_head_desc {
 } asr_probe_token_head_desc;
 int asr_probe_token_head(asr_probe_token_head_desc* d);
 
+/* Hotword boosting of the autoregressive decoders (csrc/hotword.hip, launchers in csrc/kernels.h). The phrases -- ids / offsets [n_phrases + 1], as
+ * asr_whisper_set_hotwords takes them -- are turned into the product's trie image (nodes breadth first, children by token: tests/ctc_beam_ref.py numbers
+ * them the same way); every id must lie in [0, n_valid).
+ * asr_probe_hotword, one kernel on host arrays. node [rows] in (each inside the trie), n_saved the device counter's value (0: every row counts as at the root).
+ *   op 0 launch_hotword_bias: logits [rows][ld] in / out; root_save (nullable) [rows][n_root], n_root = the root's child count, uploaded as given and read back.
+ *   op 1 launch_hotword_advance: next_in [rows] (any value) -> node out.
+ *   op 2 launch_beam_topk (with lse_out) + launch_hotword_rerank: logits, vec (bias, nullable), K -> topv / topi [rows][K], lse [rows] (nullable). */
+typedef struct asr_probe_hotword_desc {
+  int32_t op, rows, n_valid, ld;
+  float* logits; const float* vec;
+  const int32_t* ids; const int32_t* offsets; int32_t n_phrases; float boost;
+  int32_t* node; int32_t n_saved;
+  const int32_t* next_in;
+  float* root_save; int32_t n_root;
+  int32_t K; float* topv; int32_t* topi; float* lse;
+} asr_probe_hotword_desc;
+int asr_probe_hotword(asr_probe_hotword_desc* d);
+
+/* "Hotword head steps": a TokenHead (csrc/decode_head.h) driven as a session drives it -- configured (penalty value / range / partial, the sampler fields when
+ * sampling != 0, Whisper's timestamp mode when timestamps != 0, token scores when scores != 0, then set_hotwords; n_phrases == 0: the mode stays off),
+ * reserved, restarted, then `steps` times enqueue + consumed, step i on rows logits[i] ([steps][rows][ld], a different row per step) -- step 0 with `vec` as
+ * the bias and without the penalty (a prefill), later steps without bias and with it. noise (nullable) [steps][rows][K]: armed before every step. Out: picks
+ * [steps][rows], save_ids [rows][ld_save] (the final history), n_saved_after, nodes [steps][rows] (the node table after every step; untouched with the
+ * mode off), logprob [rows][ld_save] with scores (NaN where no step wrote), logits_out (nullable) [steps][rows][ld]: every step's rows after the head ran.
+ * timed (arg-max head only): logits holds ONE step's rows [rows][ld], uploaded once and reused by all `steps` steps (the bias accumulates: a timing, not a
+ * result); the steps' launches run back to back between two device events (head_ms); nodes / logits_out are not written. */
+typedef struct asr_probe_hotword_head_desc {
+  int32_t rows, n_valid, ld, steps;
+  const float* logits; const float* vec;
+  int32_t ld_save, range, partial; float value;
+  int32_t sampling, K; float temperature, top_p, repetition_penalty; uint64_t seed; const float* noise;
+  int32_t timestamps, ts_begin, no_timestamps_id, eot_id, max_initial;
+  int32_t scores;
+  const int32_t* ids; const int32_t* offsets; int32_t n_phrases; float boost;
+  int32_t* picks; int32_t* save_ids; int32_t n_saved_after; int32_t* nodes; float* logprob; float* logits_out;
+  int32_t timed; float head_ms;
+} asr_probe_hotword_head_desc;
+int asr_probe_hotword_head_steps(asr_probe_hotword_head_desc* d);
+
+/* One ranking pass of the beam search with hotwords on, as BeamRanker runs it: launch_beam_topk (K = beam, lse_out) on logits ([rows][ld]; [n_utt][ld] and
+ * `vec` as the bias when first != 0), launch_hotword_rerank, launch_beam_select with the node hand-over. The search state and the tables are those of
+ * asr_probe_beam_select (tab_ld their row stride); node_in [rows] the rows' nodes before the pass, node_out [rows] uploaded as given and read back. topv / topi
+ * come back as the re-rank left them. iters > 0: afterwards launch_beam_topk alone (ms_topk) and launch_beam_topk with lse_out + the re-rank (ms_rerank)
+ * are timed, `iters` launches each back to back between two device events. */
+typedef struct asr_probe_hotword_rank_desc {
+  int32_t n_utt, beam, tab_ld, first, n_slots, n_stop, n_valid, ld;
+  const float* logits; const float* vec;
+  const int32_t* ids; const int32_t* offsets; int32_t n_phrases; float boost;
+  float* cum; int32_t* fin; int32_t* len; int32_t* next; int32_t* done;
+  const int32_t* stop;
+  const int32_t* src_in; const int32_t* tok_in; int32_t* src_out; int32_t* tok_out;
+  const int32_t* node_in; int32_t* node_out;
+  float* topv; int32_t* topi;
+  int32_t iters; float ms_topk, ms_rerank;
+} asr_probe_hotword_rank_desc;
+int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d);
+
 /* One kernel of the Whisper token-timestamp path (csrc/whisper_align.hip, launchers in csrc/kernels.h) on host arrays. Every extent a kernel follows is checked
  * here first. op:
  *   0 launch_align_scores: q [B n][H 64] and the K slabs k_slab [H][slab_rows][64] (rounded to bf16 on upload when bf16 != 0), sequence b at slab rows

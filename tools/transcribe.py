@@ -82,6 +82,12 @@ def run(a) -> dict:
         raise SystemExit("--timestamps is not available with --beam / --nbest / --hotwords (beam hypotheses carry no time spans)")
     if sv_beam and not 1 <= nbest <= a.beam <= 16:
         raise SystemExit("--family sensevoice: --beam 1..16 and --nbest 1..beam (got --beam %d --nbest %d)" % (a.beam, nbest))
+    dec_hot_file, dec_hot_boost = getattr(a, "decoder_hotwords", None), getattr(a, "decoder_hotword_boost", 2.0)
+    if dec_hot_file and a.family not in ("whisper", "qwen_asr"):
+        raise SystemExit("--decoder-hotwords exists for --family whisper and --family qwen_asr only (SenseVoice: --hotwords)")
+    dec_hot = parse_hotword_file(dec_hot_file) if dec_hot_file else None
+    if dec_hot and any(isinstance(p, str) for p in dec_hot) and not a.tokenizer:
+        raise SystemExit("--decoder-hotwords: text phrases need --tokenizer (or give token ids)")
     bundle = {"sensevoice": "SenseVoiceSmall", "paraformer": "Paraformer", "whisper": "Whisper", "qwen_asr": "Qwen_ASR"}[a.family]
     if not any(os.path.isfile(os.path.join(a.model, bundle + ext)) for ext in (".asrmodel", ".onnx")):
         raise SystemExit("--model %s holds no %s.asrmodel: it is not a --family %s folder" % (a.model, bundle, a.family))
@@ -135,7 +141,8 @@ def run(a) -> dict:
         tr = _m("whisper").WhisperTranscriber(cfg, sess, suppress_tokens=ckm.whisper_suppress_tokens(cfg), detect_language=a.language == "auto",
                                               repeat_penalty=a.repeat_penalty, beam_size=a.beam, timestamps=timestamps, word_timestamps=word_ts,
                                               alignment_heads=heads, piece_decoder=tok.decode if tok is not None and (word_ts or scores) else None,
-                                              token_scores=scores, temperature_fallback=fallback)
+                                              token_scores=scores, temperature_fallback=fallback, hotwords=dec_hot, hotword_boost=dec_hot_boost,
+                                              hotword_encoder=(lambda t: tok.encode(t, add_special_tokens=False)) if tok is not None else None)
         lang_id = None
         if a.language != "auto":
             if tok is None:
@@ -179,7 +186,7 @@ def run(a) -> dict:
             from transformers import AutoTokenizer
             tok = AutoTokenizer.from_pretrained(a.tokenizer)
         tr = _m("qwen_asr").QwenAsrTranscriber(cfg, sess, info["metadata"], tokenizer=tok, repeat_penalty=a.repeat_penalty, beam_size=a.beam,
-                                               token_scores=scores)
+                                               token_scores=scores, hotwords=dec_hot, hotword_boost=dec_hot_boost)
         for p in a.wav:
             pcm = audio_io.read_wav_int16(p, cfg.sample_rate, exact_width=a.strict_wav)
             out, stat = tr.transcribe([pcm], language_prompts=("" if a.language == "auto" else a.language,))
@@ -249,6 +256,9 @@ def main():
     r.add_argument("--nbest", type=int, default=1, help="SenseVoice: keep the N best hypotheses of every window in the dump (1..beam), with their scores")
     r.add_argument("--hotwords", metavar="FILE", help="SenseVoice: phrases the beam search favours, one per line: token ids, or text with --tokenizer")
     r.add_argument("--hotword-boost", type=float, default=2.0, help="SenseVoice: log-probability bonus per matched hotword token")
+    r.add_argument("--decoder-hotwords", metavar="FILE", help="Whisper, Qwen3-ASR: phrases the decoder favours (greedy, sampling and --beam alike), one per line: "
+                        "token ids, or text with --tokenizer (boosted in both spellings, at the start of the text and inside it)")
+    r.add_argument("--decoder-hotword-boost", type=float, default=2.0, help="Whisper, Qwen3-ASR: logit / log-probability bonus per matched hotword token")
     r.add_argument("--timestamps", action="store_true", help="SenseVoice: add each token's start / end (seconds) and mean frame log-probability to the dump; Paraformer: each token's start / end from its CIF fire row and its log-probability; Whisper: decode with timestamp tokens and add "
                         "segments (start / end in seconds, token ids, text with --tokenizer)")
     r.add_argument("--word-timestamps", action="store_true", help="Whisper: add each text token's start / end in seconds (cross-attention DTW on the bundle's "
