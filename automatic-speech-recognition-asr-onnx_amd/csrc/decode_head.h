@@ -9,15 +9,6 @@
 #include "engine.h"
 #include "kernels.h"
 
-#define ASR_LOCAL __attribute__((visibility("hidden")))
-
-// `buf` sized to `bytes`; true when its pointer moved (a captured step that holds it is stale)
-ASR_LOCAL inline bool reserve_moved(DeviceBuffer& buf, size_t bytes, hipStream_t s) {
-  void* before = buf.ptr;
-  buf.reserve(bytes, s);
-  return buf.ptr != before;
-}
-
 // ---- Whisper's timestamp rules (kernels.h: launch_timestamp_rules) as a head / ranker setting; off for every other family
 struct ASR_LOCAL TimestampRule {
   bool on = false;

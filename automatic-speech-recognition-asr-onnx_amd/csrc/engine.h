@@ -1,6 +1,8 @@
 // Session plumbing shared by the model families: weight arena, grow-only HBM workspace,
 // HIP-event profiler, debug taps.
 #pragma once
+#include <algorithm>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <string>
@@ -10,6 +12,9 @@
 #include "gemm.h"
 #include "kernels.h"
 #include "plan_layout.h"
+#include "result_layout.h"
+
+#define ASR_LOCAL __attribute__((visibility("hidden")))
 
 // ---- weight arena (layout written by arena.py) -----------------------------------------
 //   header  : "ASRARENA" | u32 version | u32 n_tensors | u64 data_offset | u64 total_bytes
@@ -65,6 +70,13 @@ struct DeviceBuffer {
   template <typename T> T* as() const { return reinterpret_cast<T*>(ptr); }
 };
 
+// `buf` sized to `bytes`; true when its pointer moved (a captured step that holds it is stale)
+ASR_LOCAL inline bool reserve_moved(DeviceBuffer& buf, size_t bytes, hipStream_t s) {
+  void* before = buf.ptr;
+  buf.reserve(bytes, s);
+  return buf.ptr != before;
+}
+
 // Pinned host staging: grow-only with 2x headroom, freed by the destructor.
 struct PinnedBuffer {
   void* ptr = nullptr;
@@ -91,6 +103,26 @@ struct PlanBlob {
   template <typename T> T* host(PlanSection<T> x) const { return reinterpret_cast<T*>(h.as<unsigned char>() + lay.off[x.i]); }
   template <typename T> const T* dev(PlanSection<T> x) const { return reinterpret_cast<const T*>(d.as<unsigned char>() + lay.off[x.i]); }
   void upload(hipStream_t s) const;
+};
+
+// One call's results, the PlanBlob counterpart for the way home: the sections of a ResultLayout in the session's pinned result buffer. The D2H copies a step
+// enqueues (inside or outside a capture) and the host reads after the sync take their addresses from the same handles.
+struct ResultBlob {
+  ResultLayout lay;
+  PinnedBuffer& h;
+  ResultBlob(PinnedBuffer& h_, const ResultLayout& lay_) : lay(lay_), h(h_) {}
+  bool commit() { return h.reserve(lay.total()); }          // true when the host buffer moved: a captured graph that copies into it is stale
+  template <typename T> T* host(ResultSection<T> x) const { return reinterpret_cast<T*>(h.as<unsigned char>() + lay.off(x)); }
+  template <typename T> T* dev(ResultSection<T> x, const DeviceBuffer& beam_block) const { return reinterpret_cast<T*>(beam_block.as<unsigned char>() + lay.dev_off(x)); }
+  template <typename T> void enqueue_copy(ResultSection<T> x, const void* src, hipStream_t s) const {
+    HIP_CHECK(hipMemcpyAsync(host(x), src, lay.bytes(x), hipMemcpyDeviceToHost, s));
+  }
+  // row r of a [rows][max_tokens] section into row r of dst, min(counts[r], max_tokens) elements of it
+  template <typename T> void scatter_rows(ResultSection<T> x, T* dst, const int32_t* counts, int max_tokens) const {
+    const T* src = host(x);
+    for (size_t r = 0, n = lay.rows(x); r < n; ++r)
+      memcpy(dst + r * max_tokens, src + r * max_tokens, (size_t)std::min(counts[r], max_tokens) * sizeof(T));
+  }
 };
 
 // FNV-1a over the values a captured step bakes in
@@ -261,3 +293,8 @@ struct ClusterScope {
   explicit ClusterScope(int device);
   ~ClusterScope();
 };
+
+// Tuning: the phase clocks a debugged cluster launch left in `times` ([workgroup][16] stamps of the 100 MHz clock; interval k = stamp k - stamp k - 1), over the
+// workgroups that ran, to stderr. names == nullptr: one line "<title> (us, mean of N workgroups): ..." of the means of intervals first .. last. Otherwise a table
+// "[<title>] ..." of mean and maximum per named interval, with the stamps taken inside phase A as rows of their own when inside_a is set.
+void dump_phase_clocks(const DeviceBuffer& times, int n_workgroups, int first, int last, const char* const* names, const char* title, bool inside_a = false);

@@ -1,7 +1,9 @@
 // Session plumbing: error channel, arena parsing, workspace, profiler, taps.
 #include "engine.h"
 
+#include <algorithm>
 #include <atomic>
+#include <cstdio>
 #include <cstring>
 
 #include "../../include/asr_mi355x.h"
@@ -434,4 +436,39 @@ extern "C" int asr_device_foreign_stats(int device_id, int64_t* out4) {
     std::lock_guard<std::mutex> lk(g_gate_mu);
     for (int i = 0; i < 4; ++i) out4[i] = g_gate_stats[device_id][i];
   });
+}
+
+// ---- phase clocks of a debugged cluster launch (engine.h)
+void dump_phase_clocks(const DeviceBuffer& times, int n_workgroups, int first, int last, const char* const* names, const char* title, bool inside_a) {
+  std::vector<unsigned long long> t((size_t)n_workgroups * 16);
+  HIP_CHECK(hipMemcpy(t.data(), times.ptr, t.size() * 8, hipMemcpyDeviceToHost));
+  auto us = [&](int w, int from, int to) { return (double)(t[(size_t)w * 16 + to] - t[(size_t)w * 16 + from]) * 0.01; };     // 100 MHz clock -> us
+  unsigned long long t_first = ~0ull, t_last = 0;
+  int n = 0, n_plain = 0;
+  double sum[16] = {}, mx[16] = {};
+  for (int w = 0; w < n_workgroups; ++w) {
+    if (!t[(size_t)w * 16]) continue;
+    ++n;
+    t_first = std::min(t_first, t[(size_t)w * 16 + first - 1]); t_last = std::max(t_last, t[(size_t)w * 16 + last]); n_plain += (int)t[(size_t)w * 16 + 15];
+    for (int k = first; k <= last; ++k) { sum[k] += us(w, k - 1, k); mx[k] = std::max(mx[k], us(w, k - 1, k)); }
+  }
+  if (!names) {
+    fprintf(stderr, "%s (us, mean of %d workgroups):", title, n);
+    for (int k = first; k <= last; ++k) fprintf(stderr, " %.2f", sum[k] / std::max(n, 1));
+    fprintf(stderr, "\n");
+    return;
+  }
+  if (!n) return;
+  fprintf(stderr, "[%s] %d workgroups, first start -> last end %.1f us\n", title, n, (double)(t_last - t_first) * 0.01);
+  for (int k = first; k <= last; ++k) fprintf(stderr, "  %-22s avg %6.2f us  max %6.2f us\n", names[k - first], sum[k] / n, mx[k]);
+  if (inside_a) {                         // stamps 4..7 were taken inside phase A (the rows "B prologue .. B epilogue" above are then meaningless)
+    static const char* const inside[5] = {"A: statistics", "A: q/k/v images", "A: own attention tile", "A: shared 9th tile", "A: closing barrier"};
+    const int from[5] = {1, 4, 5, 6, 7}, to[5] = {4, 5, 6, 7, 2};
+    for (int q = 0; q < 5; ++q) {
+      double sm = 0.0, m2 = 0.0;
+      for (int w = 0; w < n_workgroups; ++w) if (t[(size_t)w * 16]) { sm += us(w, from[q], to[q]); m2 = std::max(m2, us(w, from[q], to[q])); }
+      fprintf(stderr, "  %-22s avg %6.2f us  max %6.2f us\n", inside[q], sm / n, m2);
+    }
+  }
+  fprintf(stderr, "  (debug word 15: %d of %d workgroups)\n", n_plain, n);
 }

@@ -1,0 +1,47 @@
+// The result sections of one SenseVoice / Paraformer call, offline or streaming: what the call's D2H copies write into the pinned result buffer and what
+// the host reads after the sync, declared once as a function of (n_rows, max_tokens, form, nbest). Every result offset is computed here and nowhere else.
+// Plain C++ without HIP types (ResultBlob in engine.h adds the buffer): tests/test_plan_blob_cpu.py compiles it on the CPU.
+//   plain              [tokens n x max_tokens][counts n][status: error word + 3 reserved words]
+//   SenseVoice timed   ... [first][last][logprob]      (n x max_tokens each)
+//   Paraformer timed   ... [first][logprob]            (offline: fire rows, streaming: fire steps; one layout for both)
+//   SenseVoice beam    ... [beam block: hyp_tokens n nbest x max_tokens][hyp_counts n nbest][hyp_scores n nbest][hyp_ctc n nbest]
+// The beam block is a layout of its own: the device-side block the beam kernel writes has the same four sections from offset 0 and comes home in one copy.
+#pragma once
+#include <cstdint>
+
+#include "plan_layout.h"
+
+enum class ResultForm { PLAIN, SV_TIMED, PF_TIMED, SV_BEAM };
+
+template <typename T> struct ResultSection { int i = -1; bool in_beam = false; };      // i < 0: the form has no such section
+
+struct ResultLayout {
+  PlanLayout lay, beam_lay;
+  size_t n_rows, max_tokens;
+  ResultSection<int32_t> tokens, counts, first, last, hyp_tokens, hyp_counts;
+  ResultSection<uint32_t> status;
+  ResultSection<float> logprob, hyp_scores, hyp_ctc;
+  ResultSection<unsigned char> beam;                     // the four hyp_* sections as one
+  ResultLayout(size_t n, size_t max_tok, ResultForm form, size_t nbest = 1) : n_rows(n), max_tokens(max_tok) {
+    const size_t toks = n * max_tok, hyps = n * nbest;
+    tokens.i = lay.add(4, 4, toks);
+    counts.i = lay.add(4, 4, n);
+    status.i = lay.add(4, 4, 1);
+    lay.add(4, 4, 3);
+    if (form == ResultForm::SV_TIMED || form == ResultForm::PF_TIMED) first.i = lay.add(4, 4, toks);
+    if (form == ResultForm::SV_TIMED) last.i = lay.add(4, 4, toks);
+    if (form == ResultForm::SV_TIMED || form == ResultForm::PF_TIMED) logprob.i = lay.add(4, 4, toks);
+    if (form != ResultForm::SV_BEAM) return;
+    hyp_tokens = {beam_lay.add(4, 4, hyps * max_tok), true};
+    hyp_counts = {beam_lay.add(4, 4, hyps), true};
+    hyp_scores = {beam_lay.add(4, 4, hyps), true};
+    hyp_ctc = {beam_lay.add(4, 4, hyps), true};
+    beam.i = lay.add(1, 4, beam_lay.total);
+  }
+  size_t total() const { return lay.total; }             // what the pinned buffer is reserved for
+  template <typename T> bool has(ResultSection<T> s) const { return s.i >= 0; }
+  template <typename T> size_t bytes(ResultSection<T> s) const { assert(has(s)); return (s.in_beam ? beam_lay : lay).bytes[s.i]; }
+  template <typename T> size_t off(ResultSection<T> s) const { assert(has(s)); return s.in_beam ? lay.off[beam.i] + beam_lay.off[s.i] : lay.off[s.i]; }
+  template <typename T> size_t dev_off(ResultSection<T> s) const { assert(has(s) && s.in_beam); return beam_lay.off[s.i]; }      // inside the device-side beam block
+  template <typename T> size_t rows(ResultSection<T> s) const { return bytes(s) / (sizeof(T) * max_tokens); }                     // of a [rows][max_tokens] section
+};

@@ -2,11 +2,13 @@
 // For the section lists of the four call sites that build a plan blob -- WhSession::encode, QwSession::prefill (+ its step plan), SvSession::run and
 // SvSession::stream_step -- it checks every section's alignment, bounds and order, the total, and that the offsets are those of the hand-written layout
 // these sites used before PlanLayout: the expected numbers below are written out from those formulas, none comes from PlanLayout.
+// The same for csrc/result_layout.h, the result blob of the SenseVoice / Paraformer session, in every form (result_blob below).
 #include <cstdint>
 #include <cstdio>
 #include <vector>
 
 #include "plan_layout.h"
+#include "result_layout.h"
 
 struct Utt { int64_t audio_off; int32_t v[8]; };      // the shape of UttPlan (kernels.h): one int64 + eight int32
 static_assert(sizeof(Utt) == 40 && alignof(Utt) == 8, "UttPlan is 40 bytes, 8-aligned");
@@ -79,7 +81,71 @@ static void stream_step(const char* name, size_t n) {       // [UttPlan n][blk_u
   check(name, {utt(n), i32(n), i32(n), i32(Mpad)}, 1, {0, U * n, U * n + 4 * n, U * n + 8 * n}, U * n + 4 * (2 * n + Mpad));
 }
 
+// ---- the result blob of the SenseVoice / Paraformer session (csrc/result_layout.h): every form against the byte arithmetic SvSession::enqueue, ::run and
+// ::stream_step spelled out by hand before ResultLayout. Offline Paraformer timed had a gap the size of `last` in front of `logprob`; it now has the streaming
+// step's compact layout, which is what is asserted for it.
+struct Span { const char* what; size_t off, bytes; };
+static void result_sections(const char* name, const ResultLayout& L, const std::vector<Span>& got, const std::vector<size_t>& want_off, size_t want_total) {
+  CHECK(got.size() == want_off.size(), "%zu sections, %zu expected", got.size(), want_off.size());
+  for (size_t k = 0; k < got.size() && k < want_off.size(); ++k) {
+    CHECK(got[k].off == want_off[k], "%s at %zu, hand layout %zu", got[k].what, got[k].off, want_off[k]);
+    CHECK(got[k].off % 4 == 0 && got[k].bytes % 4 == 0, "%s at %zu (%zu bytes) is not 4-byte aligned", got[k].what, got[k].off, got[k].bytes);
+    CHECK(got[k].off + got[k].bytes <= L.total(), "%s ends at %zu, past the total %zu", got[k].what, got[k].off + got[k].bytes, L.total());
+    for (size_t j = 0; j < k; ++j)
+      CHECK(got[j].off + got[j].bytes <= got[k].off || got[k].off + got[k].bytes <= got[j].off, "%s overlaps %s", got[k].what, got[j].what);
+  }
+  CHECK(L.total() == want_total, "total %zu, the hand-written reserve() argument %zu", L.total(), want_total);
+}
+#define SPAN(L, s) Span{#s, (L).off((L).s), (L).bytes((L).s)}
+static void result_blob(size_t n, size_t mt, size_t nbest) {
+  char name[96];
+  const size_t tok_bytes = n * mt * 4;
+  {
+    snprintf(name, sizeof name, "result plain n=%zu max_tokens=%zu", n, mt);
+    const ResultLayout L(n, mt, ResultForm::PLAIN);
+    result_sections(name, L, {SPAN(L, tokens), SPAN(L, counts), Span{"status (16 bytes)", L.off(L.status), 16}}, {0, n * mt * 4, n * mt * 4 + n * 4}, n * mt * 4 + n * 4 + 16);
+    CHECK(L.bytes(L.tokens) == tok_bytes && L.bytes(L.counts) == n * 4 && L.bytes(L.status) == 4, "section sizes");
+    CHECK(!L.has(L.first) && !L.has(L.last) && !L.has(L.logprob) && !L.has(L.beam), "the plain form has three sections");
+    CHECK(L.rows(L.tokens) == n, "%zu token rows", L.rows(L.tokens));
+  }
+  {
+    snprintf(name, sizeof name, "result sensevoice timed n=%zu max_tokens=%zu", n, mt);
+    const ResultLayout L(n, mt, ResultForm::SV_TIMED);
+    const size_t ext = tok_bytes + n * 4 + 16;          // SvSession::enqueue: unsigned char* ext = h_out + tok_bytes + batch * 4 + 16
+    result_sections(name, L, {SPAN(L, tokens), SPAN(L, counts), Span{"status (16 bytes)", L.off(L.status), 16}, SPAN(L, first), SPAN(L, last), SPAN(L, logprob)},
+                    {0, tok_bytes, tok_bytes + n * 4, ext, ext + tok_bytes, ext + 2 * tok_bytes}, n * mt * 4 + n * 4 + 16 + n * mt * 12);
+    CHECK(L.bytes(L.first) == tok_bytes && L.bytes(L.last) == tok_bytes && L.bytes(L.logprob) == tok_bytes, "span sections hold n x max_tokens words");
+  }
+  for (int offline = 0; offline < 2; ++offline) {       // streaming timed as it was; offline Paraformer timed: the same, compact
+    snprintf(name, sizeof name, "result paraformer timed (%s) n=%zu max_tokens=%zu", offline ? "offline" : "streaming", n, mt);
+    const ResultLayout L(n, mt, ResultForm::PF_TIMED);
+    const size_t out_bytes = tok_bytes + n * 4;         // SvSession::stream_step: h_out.reserve(out_bytes + 16 + 2 * tok_bytes), fire steps at out_bytes + 16
+    result_sections(name, L, {SPAN(L, tokens), SPAN(L, counts), Span{"status (16 bytes)", L.off(L.status), 16}, SPAN(L, first), SPAN(L, logprob)},
+                    {0, tok_bytes, out_bytes, out_bytes + 16, out_bytes + 16 + tok_bytes}, out_bytes + 16 + 2 * tok_bytes);
+    CHECK(!L.has(L.last), "Paraformer has no last-frame section");
+  }
+  {
+    snprintf(name, sizeof name, "result sensevoice beam n=%zu max_tokens=%zu nbest=%zu", n, mt, nbest);
+    const ResultLayout L(n, mt, ResultForm::SV_BEAM, nbest);
+    const size_t hyps = n * nbest, tokb = hyps * mt * 4, bo = n * mt * 4 + n * 4 + 16;
+    result_sections(name, L, {SPAN(L, tokens), SPAN(L, counts), Span{"status (16 bytes)", L.off(L.status), 16}, SPAN(L, hyp_tokens), SPAN(L, hyp_counts), SPAN(L, hyp_scores),
+                              SPAN(L, hyp_ctc)},
+                    {0, n * mt * 4, n * mt * 4 + n * 4, bo, bo + tokb, bo + tokb + hyps * 4, bo + tokb + hyps * 8}, n * mt * 4 + n * 4 + 16 + n * nbest * (mt * 4 + 12));
+    // the device-side block: launch_ctc_prefix_beam's four outputs at bo, bo + tokb, bo + tokb + hyps * 4, bo + tokb + hyps * 8 of d_bout, copied home as tokb + hyps * 12 bytes
+    CHECK(L.dev_off(L.hyp_tokens) == 0 && L.dev_off(L.hyp_counts) == tokb && L.dev_off(L.hyp_scores) == tokb + hyps * 4 && L.dev_off(L.hyp_ctc) == tokb + hyps * 8, "device beam block");
+    CHECK(L.off(L.beam) == bo && L.bytes(L.beam) == tokb + hyps * 12 && L.bytes(L.beam) == n * nbest * (mt * 4 + 12), "beam block at %zu, %zu bytes", L.off(L.beam), L.bytes(L.beam));
+    CHECK(L.bytes(L.hyp_tokens) == tokb && L.bytes(L.hyp_counts) == hyps * 4 && L.bytes(L.hyp_scores) == hyps * 4 && L.bytes(L.hyp_ctc) == hyps * 4, "beam section sizes");
+    CHECK(L.rows(L.hyp_tokens) == hyps, "%zu hypothesis rows", L.rows(L.hyp_tokens));
+  }
+}
+
 int main() {
+  result_blob(1, 1, 1);
+  result_blob(1, 5, 1);
+  result_blob(3, 7, 2);
+  result_blob(64, 213, 16);
+  for (size_t n : {1, 3, 64}) result_blob(n, 11 + 1, 1);       // the streaming step's minimum, max_tokens = st_B + 1 (600 ms chunks: st_B = 11)
+  result_blob(1, 1 + 1, 1);                                     // ... of the smallest chunk (st_B = 1)
   // Whisper (hop 160; T = (frames + 1) / 2; encoder rows round16(T), stem rows round16(T + 1); f32 query blocks of 64 rows)
   whisper("whisper B=1 (26240 samples)", 1, 3, 2, 128, 128);                      // 164 frames, T 82: 96 rows
   whisper("whisper ragged B=3 (26240, 12640, 48000)", 3, 3 + 2 + 5, 2 + 1 + 3, 384, 384);   // T 82, 40, 150: rows 96 + 48 + 160, stem 96 + 48 + 160

@@ -1,6 +1,8 @@
 """The layout arithmetic behind every plan blob (csrc/plan_layout.h), checked by a stand-alone C++ program under AddressSanitizer + UBSan: for the section
 lists of the four call sites, every section is aligned, in bounds and behind its predecessor, the total is sections + padding, and the offsets are those of
-the hand-written layouts the sites had before (tests/cpp/plan_layout_check.cpp spells them out). Nothing is loaded into Python."""
+the hand-written layouts the sites had before (tests/cpp/plan_layout_check.cpp spells them out). The same program takes csrc/result_layout.h, the result
+blob of the SenseVoice / Paraformer session, through every form: sections 4-byte aligned, pairwise disjoint, in bounds, at the offsets the session computed
+by hand before, the total equal to what the pinned buffer is reserved for. Nothing is loaded into Python."""
 import os
 import shutil
 import subprocess
