@@ -78,6 +78,7 @@ SIGNATURES = {
     "asr_whisper_create": (_i, [C.POINTER(WhisperConfigC), _vp, _sz, _i, _i, _i, C.POINTER(_vp)]),
     "asr_whisper_encode": (_i, [_vp, _vp, _i, _lp, _i, _ip]),
     "asr_whisper_prefill": (_i, [_vp, _ip, _i, _ip, _fp]),
+    "asr_whisper_prefill_prompts": (_i, [_vp, _ip, _ip, _ip, _fp]),
     "asr_whisper_decode": (_i, [_vp, _ip, _ip, _fp]),
     "asr_whisper_generate": (_i, [_vp, _i, _i, _ip, _ip]),
     "asr_whisper_beam_search": (_i, [_vp, _i, _i, _i, _ip, _ip, _fp]),

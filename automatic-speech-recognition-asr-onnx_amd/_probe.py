@@ -111,6 +111,9 @@ SIGNATURES = {
     "asr_probe_hotword_head_steps": (C.c_int, [C.POINTER(HotwordHeadDesc)]),
     "asr_probe_hotword_rank": (C.c_int, [C.POINTER(HotwordRankDesc)]),
     "asr_probe_decode_attention_beam": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p]),
+    "asr_probe_decode_attention_ks": (C.c_int, [C.POINTER(DecodeAttnDesc), _ip]),
+    "asr_probe_decode_attention_beam_ks": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p, _ip]),
+    "asr_probe_prompt_attention": (C.c_int, [C.POINTER(DecodeAttnDesc), _ip]),
     "asr_probe_gemm_counts": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "asr_probe_live_device_bytes": (C.c_int, [C.POINTER(C.c_int64)]),
     "asr_probe_gemm_fp8": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _fp, C.c_float, _fp, _fp, C.c_int, C.c_void_p, _fp, C.c_int, _fp]),
@@ -227,12 +230,15 @@ def gemm_chain(M, N, K, epilogue=0, cold_mb=768, replays=5):
 
 def decode_attention(q, bf16=True, n=1, B=None, b0=0, nb=0, ld_q=None, q_col0=0, max_keys=0,
                      kv_new=None, k_hist=None, v_hist=None, causal=True, hist_dev=False, max_pos=0, page_table=None, n_pages=0,
-                     k_slab=None, v_slab=None, row_off=None, n_lfr=None, fp8=False):
+                     k_slab=None, v_slab=None, row_off=None, n_lfr=None, fp8=False, key_start=None, prompt=False, ks_entry=False):
     """One decoder attention call through launch_decode_attention (asr_mi355x_probe.h) on f32 host arrays (rounded to the element type on upload).
 
     Self mode (kv_new given): q [B n][ld_q], kv_new [B n][2 H 64] (k, then v), k_hist / v_hist [B][H][hist][64], a contiguous cache of max_pos
     positions or a paged one (page_table [B][pages_per_seq] over a pool of n_pages pages of 16 positions).
     Cross mode (k_slab given): slabs [H][rows][64], sequence b at rows row_off[b] ... + n_lfr[b]; fp8 routes the slabs through the product quantiser.
+
+    key_start [B] (left-padded prompts): the single-token self forms with DecAttnArgs::key_start (asr_probe_decode_attention_ks), or -- prompt=True --
+    the prompt-attention kernel (asr_probe_prompt_attention: any n, empty cache, key_start = the left pads, may be None).
 
     Returns (out [B n][H 64], after, kernel): `after` is the self cache gathered to (k [B][H][hist + n][64], v [...], stray element count) or,
     in FP8 cross mode, (bytes [2][H][rows][64] uint8, scales [2][H][B]); None otherwise."""
@@ -277,13 +283,19 @@ def decode_attention(q, bf16=True, n=1, B=None, b0=0, nb=0, ld_q=None, q_col0=0,
             sc8 = np.zeros((2, H, B), np.float32)
             d.kv8, d.scale8 = kv8.ctypes.data, sc8.ctypes.data_as(_fp)
             after = (kv8, sc8)
-    _lib.check(load().asr_probe_decode_attention(C.byref(d)))
+    if prompt or ks_entry or key_start is not None:          # (ks_entry: asr_probe_decode_attention_ks even with a null key_start)
+        ks = None if key_start is None else np.ascontiguousarray(key_start, np.int32)
+        assert ks is None or ks.shape == (B,)
+        entry = load().asr_probe_prompt_attention if prompt else load().asr_probe_decode_attention_ks
+        _lib.check(entry(C.byref(d), None if ks is None else ks.ctypes.data_as(_ip)))
+    else:
+        _lib.check(load().asr_probe_decode_attention(C.byref(d)))
     if not cross:
         after = (ka, va, d.stray)
     return out, after, d.kernel.decode()
 
 
-def decode_attention_beam(q, kv_new, ext, src, beam, p0, hist, bf16=True, hist_dev=False):
+def decode_attention_beam(q, kv_new, ext, src, beam, p0, hist, bf16=True, hist_dev=False, key_start=None):
     """One "self_beam" call (asr_mi355x_probe.h): q [rows][H 64], kv_new [rows][2 H 64], ext [rows][2][H][S][64] (the rows' extents before the call),
     src [rows][ld_src] (row holding generated position p0 + j of row r). Returns (out [rows][H 64], ext after the call, stray element count, kernel)."""
     q, kv_new = _f32(q), _f32(kv_new)
@@ -294,9 +306,14 @@ def decode_attention_beam(q, kv_new, ext, src, beam, p0, hist, bf16=True, hist_d
     out = np.zeros((rows, H * 64), np.float32)
     stray = np.zeros(1, np.int32)
     kern = C.create_string_buffer(32)
-    _lib.check(load().asr_probe_decode_attention_beam(int(bf16), rows, int(beam), H, S, int(p0), int(hist), int(hist_dev), src.ctypes.data_as(_ip),
-                                                      src.shape[1], q.ctypes.data_as(_fp), kv_new.ctypes.data_as(_fp), ext.ctypes.data_as(_fp),
-                                                      out.ctypes.data_as(_fp), stray.ctypes.data_as(_ip), kern))
+    args = (int(bf16), rows, int(beam), H, S, int(p0), int(hist), int(hist_dev), src.ctypes.data_as(_ip), src.shape[1], q.ctypes.data_as(_fp),
+            kv_new.ctypes.data_as(_fp), ext.ctypes.data_as(_fp), out.ctypes.data_as(_fp), stray.ctypes.data_as(_ip), kern)
+    if key_start is not None:           # [rows / beam]: the utterances' left pads (asr_probe_decode_attention_beam_ks)
+        ks = np.ascontiguousarray(key_start, np.int32)
+        assert ks.shape == (rows // beam,)
+        _lib.check(load().asr_probe_decode_attention_beam_ks(*args, ks.ctypes.data_as(_ip)))
+    else:
+        _lib.check(load().asr_probe_decode_attention_beam(*args))
     return out, ext, int(stray[0]), kern.value.decode()
 
 

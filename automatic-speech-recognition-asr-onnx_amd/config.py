@@ -107,6 +107,7 @@ class WhisperConfig:
     no_speech_id: int = 50363
     first_language_id: int = 50259
     n_languages: int = 100
+    sot_prev_id: int = 50362     # <|startofprev|>: opens the previous-text part of a prompt (whisper.build_prompt)
 
     def n_frames(self, audio_len: int) -> int:
         return audio_len // self.hop_length
@@ -129,7 +130,7 @@ def whisper_tiny_test() -> WhisperConfig:
                          max_source_positions=1500, max_target_positions=64,
                          sot_id=500, eot_id=499, transcribe_id=560, translate_id=559,
                          no_timestamps_id=564, no_speech_id=563, first_language_id=501,
-                         n_languages=58)
+                         n_languages=58, sot_prev_id=562)
 
 
 def whisper_mid_test() -> WhisperConfig:
@@ -137,7 +138,7 @@ def whisper_mid_test() -> WhisperConfig:
     return WhisperConfig(n_mels=128, d_model=384, n_heads=6, d_head=64, d_ffn=1536, n_enc_layers=4, n_dec_layers=4, vocab=5000,
                          max_source_positions=1500, max_target_positions=448,
                          sot_id=4900, eot_id=4899, transcribe_id=4990, translate_id=4989, no_timestamps_id=4994,
-                         no_speech_id=4993, first_language_id=4901, n_languages=80)
+                         no_speech_id=4993, first_language_id=4901, n_languages=80, sot_prev_id=4992)
 
 
 def whisper_d256_test() -> WhisperConfig:
@@ -145,7 +146,7 @@ def whisper_d256_test() -> WhisperConfig:
     return WhisperConfig(n_mels=128, d_model=256, n_heads=4, d_head=64, d_ffn=1024, n_enc_layers=2, n_dec_layers=3, vocab=3000,
                          max_source_positions=1500, max_target_positions=448,
                          sot_id=2900, eot_id=2899, transcribe_id=2990, translate_id=2989, no_timestamps_id=2994,
-                         no_speech_id=2993, first_language_id=2901, n_languages=80)
+                         no_speech_id=2993, first_language_id=2901, n_languages=80, sot_prev_id=2992)
 
 
 @dataclass(frozen=True)

@@ -69,9 +69,11 @@ void launch_zero_gap_rows(T* buf, int ld, int n_cols, const UttPlan* plan, const
 void launch_layernorm_fp8(const float* x, int ld_x, int rows, int D, float eps, float inv_scale, unsigned char* out, int ld_out, hipStream_t s);
 
 // ---- decoder token + position embedding: x[b*n + i] = embed[ids[b*n + i]] + pos[hist + i]   (Export_Whisper.py:450-497)
+// kstart (nullable, device [sequences]): left-padded prompts -- slot hist + i of sequence b = row / kstart_rows (0: n) is position hist + i - kstart[b]; a
+// pad slot (below kstart[b]) takes position 0 and the id staged for it, so it reads inside both tables (its row is never attended by a real one).
 template <typename T>
 void launch_embed_pos(const int32_t* ids, int rows, int n, int hist, const int32_t* hist_dev, const T* embed, const float* pos, int d,
-                      float* x, hipStream_t s);
+                      float* x, hipStream_t s, const int32_t* kstart = nullptr, int kstart_rows = 0);
 void launch_add_scalar(int32_t* p, int v, hipStream_t s);      // *p += v (device-side history counter)
 
 // ---- decoder attention, head_dim 64, n <= 8 new queries per sequence. Keys/values are rows of 64:
@@ -100,7 +102,34 @@ struct DecAttnArgs {
   // extent k_base + r * stride_b + h * stride_h (slot = position); positions below beam_p0 (the prompt, copied into every row) are read from the row's own
   // extent, position p >= beam_p0 from the extent of row beam_src[r * ld_src + p - beam_p0] (its ancestry). The new row goes to the row's own slot `hist`.
   const int32_t* beam_src = nullptr; int ld_src = 0, beam_p0 = 0, beam = 1;
+  // left-padded prompts (asr_whisper_prefill_prompts): single-token self-attention ("self_wave", "general_n1", "self_beam") of sequence b sees cached keys
+  // key_start[b] .. hist - 1 only (the beam form reads key_start[row / beam]); the slots below are never loaded. Null: every key, and the kernels are
+  // the instances they were before the field existed.
+  const int32_t* key_start = nullptr;
 };
+
+// ---- prompt attention, head_dim 64, any number n of query rows per sequence (prefills of more than 8 ids or of ragged lengths; csrc/prompt_attn.hip).
+// One workgroup per (sequence, head, tile of query rows: 16 for f32, 64 for bf16); keys go through LDS in blocks of 64 under an online soft-max (exp2 on
+// pre-scaled scores).
+//   self : q / k / v are rows b * n + slot of the fused q|k|v GEMM output; query slot i of sequence b sees key slots key_start[b] .. i. Later keys are
+//          SKIPPED (the reference adds -128 to them, Export_Whisper.py:468-480: exp(-128) of an f32 soft-max at |score| << 100 is below half an ulp of
+//          the sum, so the two are indistinguishable). All n K / V rows are written to the cache (contiguous or paged, as decode_attn_kernel does);
+//          a query row without a visible key (a pad slot) writes zeros.
+//   cross: keys / values are the per-(layer, head) slabs [row][64] through the plan (row_off, n_lfr), unmasked; pad slots write zeros too.
+// bf16: QK^T and PV on v_mfma_f32_16x16x32_bf16, probabilities rounded to bf16 for PV; f32: f32 FMAs (the arithmetic class of decode_attn_kernel<float>).
+struct PromptAttnArgs {
+  const void* q = nullptr; int ld_q = 0, q_col0 = 0;
+  const void* kv_new = nullptr; int ld_new = 0, k_col0 = 0, v_col0 = 0;      // self: the n new rows per sequence; null for cross
+  void* k_base = nullptr; void* v_base = nullptr;                            // self: the cache to fill; cross: the slabs
+  int64_t stride_b = 0, stride_h = 0;
+  const int32_t* page_table = nullptr; int pages_per_seq = 0; int64_t page_stride = 0;
+  const UttPlan* plan = nullptr;                                             // cross
+  const int32_t* key_start = nullptr;                                        // [batch] pad slots per sequence (null: 0)
+  int n = 0, n_heads = 0;
+  void* out = nullptr; int ld_out = 0;
+};
+template <typename T>
+void launch_prompt_attention(const PromptAttnArgs& a, int batch, hipStream_t s);
 // FP8 (OCP e4m3, power-of-two scales) quantisers of precision mode ASR_PRECISION_FP8W
 void launch_quantize_rows_fp8(const bf16_t* W, int ld, int N, int K, unsigned char* W8, float* scale, bf16_t* Wdq, hipStream_t s);
 // MXFP4 (e2m1 + one e8m0 scale per 32 k): W4 [N][K / 2] bytes, S [N][K / 32] bytes, Wdq (nullable) the exact bf16 dequantisation
@@ -109,7 +138,7 @@ void launch_quantize_crosskv_fp8(bf16_t* slabs, size_t slab_elems, int n_slabs, 
                                  int dq_in_place, hipStream_t s);
 template <typename T>
 void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s);
-const char* decode_attn_last_kernel();   // form of this thread's last launch_decode_attention ("self_wave", "self_beam", "cross_1pass[_fp8]", "general_n1[_fp8]", "general_n8[_fp8]"): test hook
+const char* decode_attn_last_kernel();   // form of this thread's last launch_decode_attention ("self_wave", "self_beam", "cross_1pass[_fp8]", "general_n1[_fp8]", "general_n8[_fp8]", each self form + "_ks" with key_start): test hook
 
 // The hotword context graph as the device sees it: node 0 is the root; children of node n are child_tok / child_node [child_off[n], child_off[n + 1]), sorted
 // by token. n_nodes <= 1: no hotwords (no pointer is read).

@@ -977,11 +977,13 @@ __global__ void compact_rows_kernel(const float* __restrict__ src, const UttPlan
 // ------------------------------------------------------------------------------------ decoder embedding
 template <typename T>
 __global__ void embed_pos_kernel(const int32_t* __restrict__ ids, int n, int hist, const int32_t* __restrict__ hist_dev,
-                                 const T* __restrict__ embed, const float* __restrict__ pos, int d, float* __restrict__ x) {
+                                 const T* __restrict__ embed, const float* __restrict__ pos, int d, float* __restrict__ x, const int32_t* __restrict__ kstart, int kstart_rows) {
   const int r = blockIdx.x;
   if (hist_dev) hist = *hist_dev;
   const T* e = embed + (size_t)ids[r] * d;
-  const float* p = pos + (size_t)(hist + r % n) * d;
+  int at = hist + r % n;
+  if (kstart) at = max(at - kstart[r / kstart_rows], 0);               // left-padded prompts: the slot's position; a pad slot takes position 0
+  const float* p = pos + (size_t)at * d;
   for (int c = threadIdx.x; c < d; c += blockDim.x) x[(size_t)r * d + c] = Elem<T>::load(e + c) + p[c];
 }
 
@@ -1025,7 +1027,8 @@ template <typename T> __device__ __forceinline__ void load8dims(const T* p, floa
 // NQ = compile-time bound on the queries per sequence: 1 for single-token decode steps (lean registers: more loads in flight),
 // DA_MAXN for prefills.
 // KV8: the cached K / V rows are e4m3 bytes with one power-of-two scale per (sequence, head) slab (cross-attention only: no new rows)
-template <typename T, int NQ, bool KV8 = false>
+// KS: key_start is set -- the keys below key_start[b] are left out of every loop (k0 is the constant 0 in the other instances)
+template <typename T, int NQ, bool KV8 = false, bool KS = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(const DecAttnArgs a) {
   using KT = typename std::conditional<KV8, fp8_t, T>::type;
   extern __shared__ __attribute__((aligned(16))) unsigned char da_smem[];
@@ -1042,6 +1045,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const DecAttnArgs a) {
   if (a.plan) { n_cached = a.plan[b].n_lfr; row0 = a.plan[b].row_off; }
   else n_cached = hist;
   const int S = a.plan ? n_cached : hist + n;
+  int k0 = 0;                                    // first key of the sequence
+  if constexpr (KS) k0 = min(max(a.key_start[b], 0), hist);      // (self-attention: the new rows stay visible)
   // cache row s of this (sequence, head): contiguous extent, or through the block table of the paged self-KV cache (pages of 16 positions)
   const int32_t* pt = a.page_table ? a.page_table + (size_t)b * a.pages_per_seq : nullptr;
   const KT* Kc = reinterpret_cast<const KT*>(a.k_base) + (pt ? (size_t)h * 1024 : (size_t)b * a.stride_b + (size_t)h * a.stride_h + (size_t)row0 * 64);
@@ -1076,8 +1081,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const DecAttnArgs a) {
   {
     Raw8<KT> nxt[DU];
 #pragma unroll
-    for (int u = 0; u < DU; ++u) { const int s0 = (tid >> 3) + u * 32; if (s0 < S) nxt[u].load(k_ptr(s0)); }
-    for (int sb = (tid >> 3); sb < S; sb += 32 * DU) {
+    for (int u = 0; u < DU; ++u) { const int s0 = k0 + (tid >> 3) + u * 32; if (s0 < S) nxt[u].load(k_ptr(s0)); }
+    for (int sb = k0 + (tid >> 3); sb < S; sb += 32 * DU) {
       Raw8<KT> cur[DU];
 #pragma unroll
       for (int u = 0; u < DU; ++u) cur[u] = nxt[u];
@@ -1109,14 +1114,14 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const DecAttnArgs a) {
   // the V stream does not depend on the scores: its first trip is requested before the soft-max statistics are computed
   Raw8<KT> vnxt[DU];
 #pragma unroll
-  for (int u = 0; u < DU; ++u) { const int s0 = (tid >> 3) + u * 32; if (s0 < S) vnxt[u].load(v_ptr(s0)); }
+  for (int u = 0; u < DU; ++u) { const int s0 = k0 + (tid >> 3) + u * 32; if (s0 < S) vnxt[u].load(v_ptr(s0)); }
   // ---- soft-max statistics per query (wave w handles queries w, w+4)
   for (int i = wave; i < n; i += 4) {
     float mx = -INFINITY;
-    for (int s = lane; s < S; s += 64) mx = fmaxf(mx, sc[i * sc_ld + s]);
+    for (int s = k0 + lane; s < S; s += 64) mx = fmaxf(mx, sc[i * sc_ld + s]);
     mx = wave_max(mx);
     float sum = 0.0f;
-    for (int s = lane; s < S; s += 64) {
+    for (int s = k0 + lane; s < S; s += 64) {
       const float e = expf(sc[i * sc_ld + s] - mx);
       sc[i * sc_ld + s] = e;
       sum += e;
@@ -1132,7 +1137,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const DecAttnArgs a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[i][e] = 0.0f;
   {
-    for (int sb = (tid >> 3); sb < S; sb += 32 * DU) {
+    for (int sb = k0 + (tid >> 3); sb < S; sb += 32 * DU) {
       Raw8<KT> cur[DU];
 #pragma unroll
       for (int u = 0; u < DU; ++u) cur[u] = vnxt[u];
@@ -1927,12 +1932,12 @@ void launch_compact_rows(const float* src, const UttPlan* from, const UttPlan* t
 
 template <typename T>
 void launch_embed_pos(const int32_t* ids, int rows, int n, int hist, const int32_t* hist_dev, const T* embed, const float* pos, int d,
-                      float* x, hipStream_t s) {
-  hipLaunchKernelGGL(embed_pos_kernel<T>, dim3(rows), dim3(256), 0, s, ids, n, hist, hist_dev, embed, pos, d, x);
+                      float* x, hipStream_t s, const int32_t* kstart, int kstart_rows) {
+  hipLaunchKernelGGL(embed_pos_kernel<T>, dim3(rows), dim3(256), 0, s, ids, n, hist, hist_dev, embed, pos, d, x, kstart, kstart_rows > 0 ? kstart_rows : n);
   HIP_CHECK(hipGetLastError());
 }
-template void launch_embed_pos<float>(const int32_t*, int, int, int, const int32_t*, const float*, const float*, int, float*, hipStream_t);
-template void launch_embed_pos<bf16_t>(const int32_t*, int, int, int, const int32_t*, const bf16_t*, const float*, int, float*, hipStream_t);
+template void launch_embed_pos<float>(const int32_t*, int, int, int, const int32_t*, const float*, const float*, int, float*, hipStream_t, const int32_t*, int);
+template void launch_embed_pos<bf16_t>(const int32_t*, int, int, int, const int32_t*, const bf16_t*, const float*, int, float*, hipStream_t, const int32_t*, int);
 
 namespace { __global__ void add_scalar_kernel(int32_t* p, int v) { *p += v; } }
 void launch_add_scalar(int32_t* p, int v, hipStream_t s) {
@@ -1945,12 +1950,17 @@ namespace {
 // global-load rounds on <= 40 cached positions (15 us per launch at 64 sequences: 22 % of a Whisper decode step). Here every load a wave needs
 // (its query, the new K / V row, up to 64 cached K and V rows) is requested at once, 8 lanes per 128-byte row (16 B each, coalesced), the dot
 // products are reduced inside the 8-lane groups by DPP, the soft-max runs online over blocks of 64 keys with wave shuffles, and nothing goes through LDS.
+// KS: key_start is set -- the cached keys below ks = key_start[b] are never loaded; the walk starts at the block of 64 that holds ks.
+template <bool KS>
 __global__ __launch_bounds__(256) void decode_self_attn_wave_kernel(const DecAttnArgs a) {
   const int b = blockIdx.x + a.b0, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int h = blockIdx.y * 4 + wave;
   if (h >= a.n_heads) return;
   const int hist = a.hist_dev ? *a.hist_dev : a.hist;          // keys 0 .. hist - 1 are cached, key `hist` is the new row
   const int sub = lane & 7, grp = lane >> 3;
+  // (blk0 stays a visible multiple of 64 -- the page lookups of a block are then wave-uniform, as they are from 0; a start at or past the history empties the walk)
+  int ks = 0, blk0 = 0, hist_w = hist;
+  if constexpr (KS) { ks = max(a.key_start[b], 0); blk0 = ks & ~63; hist_w = ks < hist ? hist : 0; }
   // cache row s: contiguous extent, or through the block table (a wave instruction covers 8 consecutive rows = one 16-position page: the lookup is wave-uniform)
   const int32_t* pt = a.page_table ? a.page_table + (size_t)b * a.pages_per_seq : nullptr;
   bf16_t* Kc = reinterpret_cast<bf16_t*>(a.k_base) + (pt ? (size_t)h * 1024 : (size_t)b * a.stride_b + (size_t)h * a.stride_h);
@@ -1977,8 +1987,8 @@ __global__ __launch_bounds__(256) void decode_self_attn_wave_kernel(const DecAtt
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
     kr[u].v = make_uint4(0, 0, 0, 0); vr[u].v = make_uint4(0, 0, 0, 0);      // slots past the history stay finite: 0 x garbage could be NaN
-    const int s0 = u * 8 + grp;
-    if (s0 < hist) { const size_t ro = crow(s0); kr[u].load(Kc + ro + sub * 8); vr[u].load(Vc + ro + sub * 8); }
+    const int s0 = blk0 + u * 8 + grp;
+    if (s0 >= ks && s0 < hist_w) { const size_t ro = crow(s0); kr[u].load(Kc + ro + sub * 8); vr[u].load(Vc + ro + sub * 8); }
   }
   if (grp == 0) {                                            // append the new row (read back only by later steps)
     const size_t ro = crow(hist);
@@ -1987,7 +1997,7 @@ __global__ __launch_bounds__(256) void decode_self_attn_wave_kernel(const DecAtt
   }
   float qf[8];
   q8.get(qf);
-  for (int blk = 0; blk < hist; blk += 64) {
+  for (int blk = blk0; blk < hist_w; blk += 64) {
     float sc[8], vf[8][8];
     float mx = -INFINITY;
 #pragma unroll
@@ -1996,7 +2006,7 @@ __global__ __launch_bounds__(256) void decode_self_attn_wave_kernel(const DecAtt
       kr[u].get(kf);
       vr[u].get(vf[u]);
       const float d = dot8(qf, kf);
-      sc[u] = blk + u * 8 + grp < hist ? d : -INFINITY;
+      sc[u] = (blk + u * 8 + grp < hist && blk + u * 8 + grp >= ks) ? d : -INFINITY;
       mx = fmaxf(mx, sc[u]);
     }
     if (blk + 64 < hist) {                                   // the next block's rows (more than 64 positions of history)
@@ -2049,7 +2059,7 @@ __global__ __launch_bounds__(256) void decode_self_attn_wave_kernel(const DecAtt
 // Row r's cache is an extent (slot = position); the prompt positions (< beam_p0) were copied into every row, a generated position p is read from the extent of
 // row beam_src[r][p - beam_p0] -- the hypothesis that wrote it -- so nothing is copied or re-ordered between steps. 1-D grid: the `beam` rows of one (utterance,
 // head group) take workgroup ids of one XCD (ids w and w + 8 share an XCD), so the ancestor rows they have in common come from HBM once into that XCD's L2.
-template <typename T>
+template <typename T, bool KS>
 __global__ __launch_bounds__(256) void decode_self_attn_beam_kernel(const DecAttnArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, beam = a.beam;
   const int w = blockIdx.x, units = gridDim.x / beam, HG = (a.n_heads + 3) >> 2;
@@ -2060,6 +2070,9 @@ __global__ __launch_bounds__(256) void decode_self_attn_beam_kernel(const DecAtt
   if (h >= a.n_heads) return;
   const int hist = a.hist_dev ? *a.hist_dev : a.hist;          // keys 0 .. hist - 1 are cached, key `hist` is the new row
   const int sub = lane & 7, grp = lane >> 3, p0 = a.beam_p0;
+  int ks = 0, blk0 = 0;                                        // KS: the keys below key_start[utterance] are never loaded (the wave kernel's rule)
+  int hist_w = hist;
+  if constexpr (KS) { ks = max(a.key_start[row / beam], 0); blk0 = ks & ~63; hist_w = ks < hist ? hist : 0; }
   const int32_t* src = a.beam_src + (size_t)row * a.ld_src;
   T* Kb = reinterpret_cast<T*>(a.k_base) + (size_t)h * a.stride_h;
   T* Vb = reinterpret_cast<T*>(a.v_base) + (size_t)h * a.stride_h;
@@ -2090,8 +2103,8 @@ __global__ __launch_bounds__(256) void decode_self_attn_beam_kernel(const DecAtt
 #pragma unroll
   for (int u8 = 0; u8 < 8; ++u8) {
     kr[u8] = Raw8<T>{}; vr[u8] = Raw8<T>{};                    // slots past the history stay finite: 0 x garbage could be NaN
-    const int s0 = u8 * 8 + grp;
-    if (s0 < hist) { const size_t ro = crow(s0); kr[u8].load(Kb + ro); vr[u8].load(Vb + ro); }
+    const int s0 = blk0 + u8 * 8 + grp;
+    if (s0 >= ks && s0 < hist_w) { const size_t ro = crow(s0); kr[u8].load(Kb + ro); vr[u8].load(Vb + ro); }
   }
   if (grp == 0) {                                            // the new row goes to this row's own slot `hist` (read by its descendants in later steps)
     const T* nkp = NEW + a.k_col0; const T* nvp = NEW + a.v_col0;
@@ -2102,7 +2115,7 @@ __global__ __launch_bounds__(256) void decode_self_attn_beam_kernel(const DecAtt
   }
   float qf[8];
   q8.get(qf);
-  for (int blk = 0; blk < hist; blk += 64) {
+  for (int blk = blk0; blk < hist_w; blk += 64) {
     float sc[8], vf[8][8];
     float mx = -INFINITY;
 #pragma unroll
@@ -2111,7 +2124,7 @@ __global__ __launch_bounds__(256) void decode_self_attn_beam_kernel(const DecAtt
       kr[u8].get(kf);
       vr[u8].get(vf[u8]);
       const float d = dot8(qf, kf);
-      sc[u8] = blk + u8 * 8 + grp < hist ? d : -INFINITY;
+      sc[u8] = (blk + u8 * 8 + grp < hist && blk + u8 * 8 + grp >= ks) ? d : -INFINITY;
       mx = fmaxf(mx, sc[u8]);
     }
     if (blk + 64 < hist) {
@@ -2165,13 +2178,15 @@ template <typename T>
 void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s) {
   ASR_REQUIRE(a.n >= 1 && a.n <= DA_MAXN, "decode attention: %d new positions per call (max %d)", a.n, DA_MAXN);
   ASR_REQUIRE(a.plan || a.hist_dev || a.hist + a.n <= DA_MAXKEYS, "decode attention: %d keys exceed %d", a.hist + a.n, DA_MAXKEYS);
+  ASR_REQUIRE(!a.key_start || (a.n == 1 && a.kv_new && !a.plan && !a.k_scale && !a.v_scale), "decode attention: key_start belongs to single-token self-attention");
   if (a.beam_src) {                                          // beam search hypothesis rows: `batch` = rows, a multiple of the width
     ASR_REQUIRE(a.n == 1 && a.kv_new && !a.plan && !a.page_table && !a.k_scale && !a.v_scale && a.b0 == 0 && a.beam >= 1 && batch % a.beam == 0 &&
                 a.ld_src > 0 && a.beam_p0 >= 0 && (a.ld_q % 8) == 0 && (a.ld_new % 8) == 0 && (a.q_col0 % 8) == 0 && (a.k_col0 % 8) == 0 &&
                 (a.v_col0 % 8) == 0 && (a.ld_out % 8) == 0 && (a.stride_b % 8) == 0 && (a.stride_h % 8) == 0,
                 "decode attention: the beam form is single-token self-attention over per-row extents");
-    g_decode_attn_kernel = "self_beam";
-    hipLaunchKernelGGL((decode_self_attn_beam_kernel<T>), dim3(batch * ((a.n_heads + 3) / 4)), dim3(256), 0, s, a);
+    g_decode_attn_kernel = a.key_start ? "self_beam_ks" : "self_beam";
+    if (a.key_start) hipLaunchKernelGGL((decode_self_attn_beam_kernel<T, true>), dim3(batch * ((a.n_heads + 3) / 4)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((decode_self_attn_beam_kernel<T, false>), dim3(batch * ((a.n_heads + 3) / 4)), dim3(256), 0, s, a);
     HIP_CHECK(hipGetLastError());
     return;
   }
@@ -2179,8 +2194,9 @@ void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s) {
     const bool wave_on = gemm_env_decode_attn_wave();
     if (wave_on && a.n == 1 && !a.plan && a.kv_new && !a.k_scale && !a.v_scale && (a.ld_q % 8) == 0 && (a.ld_new % 8) == 0 && (a.q_col0 % 8) == 0 &&
         (a.k_col0 % 8) == 0 && (a.v_col0 % 8) == 0 && (a.ld_out % 8) == 0) {                 // single-token self-attention: one wave per (sequence, head)
-      g_decode_attn_kernel = "self_wave";
-      hipLaunchKernelGGL(decode_self_attn_wave_kernel, dim3(batch, (a.n_heads + 3) / 4), dim3(256), 0, s, a);
+      g_decode_attn_kernel = a.key_start ? "self_wave_ks" : "self_wave";
+      if (a.key_start) hipLaunchKernelGGL(decode_self_attn_wave_kernel<true>, dim3(batch, (a.n_heads + 3) / 4), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL(decode_self_attn_wave_kernel<false>, dim3(batch, (a.n_heads + 3) / 4), dim3(256), 0, s, a);
       HIP_CHECK(hipGetLastError());
       return;
     }
@@ -2212,6 +2228,10 @@ void launch_decode_attention(const DecAttnArgs& a, int batch, hipStream_t s) {
       if (a.n == 1) hipLaunchKernelGGL((decode_attn_kernel<T, 1, true>), dim3(batch, a.n_heads), dim3(256), lds, s, b);
       else hipLaunchKernelGGL((decode_attn_kernel<T, DA_MAXN, true>), dim3(batch, a.n_heads), dim3(256), lds, s, b);
     } else ASR_REQUIRE(false, "decode attention: FP8 K / V need a bf16 session");
+  }
+  else if (a.key_start) {
+    g_decode_attn_kernel = "general_n1_ks";
+    hipLaunchKernelGGL((decode_attn_kernel<T, 1, false, true>), dim3(batch, a.n_heads), dim3(256), lds, s, b);
   }
   else {
     g_decode_attn_kernel = a.n == 1 ? "general_n1" : "general_n8";

@@ -573,11 +573,23 @@ template <> float elem_nan<float>() { return std::nanf(""); }
 template <> bf16_t elem_nan<bf16_t>() { return (bf16_t)0x7fc0; }
 template <typename T> bool same_bits(T x, T y) { return std::memcmp(&x, &y, sizeof(T)) == 0; }
 
+// key_start (host [B], nullable): the single-token self forms with DecAttnArgs::key_start; prompt: the call goes to launch_prompt_attention instead
+// (any n, whole batch, empty cache), with key_start as the per-sequence left pad.
 template <typename T>
-void probe_decode_attention(asr_probe_decode_attn_desc* d) {
+void probe_decode_attention(asr_probe_decode_attn_desc* d, const int32_t* key_start = nullptr, bool prompt = false) {
   Tmp t;
   const int B = d->B, H = d->H, n = d->n, D = H * 64, nb = d->nb > 0 ? d->nb : d->B - d->b0;
-  ASR_REQUIRE(B > 0 && H > 0 && n >= 1 && n <= 8 && d->b0 >= 0 && nb > 0 && d->b0 + nb <= B && d->q && d->out, "probe_decode_attention: bad geometry");
+  ASR_REQUIRE(B > 0 && H > 0 && n >= 1 && n <= (prompt ? 1536 : 8) && d->b0 >= 0 && nb > 0 && d->b0 + nb <= B && d->q && d->out, "probe_decode_attention: bad geometry");
+  ASR_REQUIRE(!prompt || (d->b0 == 0 && nb == B && !d->fp8 && !d->hist_dev && (d->cross || d->hist == 0)), "probe_prompt_attention: whole batch, empty cache, bf16 / f32 slabs");
+  ASR_REQUIRE(!key_start || prompt || (!d->cross && n == 1), "probe_decode_attention_ks: key_start belongs to single-token self-attention");
+  if (key_start)
+    for (int b = 0; b < B; ++b)
+      ASR_REQUIRE(key_start[b] >= 0 && key_start[b] <= (prompt ? n : d->hist), "probe: key_start[%d] = %d outside 0..%d", b, key_start[b], prompt ? n : d->hist);
+  int32_t* dks = nullptr;
+  if (key_start) {
+    dks = (int32_t*)t.alloc((size_t)B * 4);
+    HIP_CHECK(hipMemcpy(dks, key_start, (size_t)B * 4, hipMemcpyHostToDevice));
+  }
   ASR_REQUIRE(d->ld_q >= d->q_col0 + D && d->q_col0 >= 0, "probe_decode_attention: q columns [%d, %d) past ld_q %d", d->q_col0, d->q_col0 + D, d->ld_q);
   auto up = [&](const float* src, size_t count) -> T* {
     std::vector<T> h(count);
@@ -687,8 +699,19 @@ void probe_decode_attention(asr_probe_decode_attn_desc* d) {
       a.k_base = dkv; a.v_base = dkv + half;
     }
   }
-  launch_decode_attention<T>(a, nb, nullptr);
-  snprintf(d->kernel, sizeof(d->kernel), "%s", decode_attn_last_kernel());
+  if (prompt) {
+    PromptAttnArgs pa;
+    pa.q = a.q; pa.ld_q = a.ld_q; pa.q_col0 = a.q_col0; pa.kv_new = a.kv_new; pa.ld_new = a.ld_new; pa.k_col0 = a.k_col0; pa.v_col0 = a.v_col0;
+    pa.k_base = a.k_base; pa.v_base = a.v_base; pa.stride_b = a.stride_b; pa.stride_h = a.stride_h;
+    pa.page_table = a.page_table; pa.pages_per_seq = a.pages_per_seq; pa.page_stride = a.page_stride; pa.plan = a.plan;
+    pa.key_start = dks; pa.n = n; pa.n_heads = H; pa.out = a.out; pa.ld_out = a.ld_out;
+    launch_prompt_attention<T>(pa, B, nullptr);
+    snprintf(d->kernel, sizeof(d->kernel), "%s", d->cross ? "prompt_cross" : "prompt_self");
+  } else {
+    a.key_start = dks;
+    launch_decode_attention<T>(a, nb, nullptr);
+    snprintf(d->kernel, sizeof(d->kernel), "%s", decode_attn_last_kernel());
+  }
   HIP_CHECK(hipDeviceSynchronize());
   std::vector<T> ho((size_t)B * n * D);
   HIP_CHECK(hipMemcpy(ho.data(), out, ho.size() * sizeof(T), hipMemcpyDeviceToHost));
@@ -712,7 +735,7 @@ void probe_decode_attention(asr_probe_decode_attn_desc* d) {
 namespace {
 template <typename T>
 void probe_decode_attention_beam(int rows, int beam, int H, int S, int p0, int hist, int hist_dev, const int32_t* src, int ld_src, const float* q,
-                                 const float* kv_new, float* ext, float* out, int32_t* stray, char* kernel) {
+                                 const float* kv_new, float* ext, float* out, int32_t* stray, char* kernel, const int32_t* key_start = nullptr) {
   Tmp t;
   const int D = H * 64;
   ASR_REQUIRE(rows > 0 && beam >= 1 && beam <= 8 && rows % beam == 0 && H > 0 && S > 0 && p0 >= 0 && p0 <= hist && hist < S && ld_src >= hist - p0 && ld_src > 0 &&
@@ -741,6 +764,12 @@ void probe_decode_attention_beam(int rows, int beam, int H, int S, int p0, int h
   a.k_base = dext; a.v_base = dext + (size_t)H * S * 64; a.stride_b = (int64_t)2 * H * S * 64; a.stride_h = (int64_t)S * 64;
   a.beam_src = dsrc; a.ld_src = ld_src; a.beam_p0 = p0; a.beam = beam;
   a.n = 1; a.n_heads = H; a.causal = 1; a.max_keys = S; a.hist = hist;
+  if (key_start) {                      // [rows / beam]: the utterances' left pads
+    for (int u = 0; u < rows / beam; ++u) ASR_REQUIRE(key_start[u] >= 0 && key_start[u] <= hist, "probe_decode_attention_beam: key_start[%d] = %d outside 0..%d", u, key_start[u], hist);
+    int32_t* dks = (int32_t*)t.alloc((size_t)(rows / beam) * 4);
+    HIP_CHECK(hipMemcpy(dks, key_start, (size_t)(rows / beam) * 4, hipMemcpyHostToDevice));
+    a.key_start = dks;
+  }
   if (hist_dev) {                       // graph-replay form: the by-value history is deliberately wrong
     int32_t* hd = (int32_t*)t.alloc(4);
     HIP_CHECK(hipMemcpy(hd, &hist, 4, hipMemcpyHostToDevice));
@@ -773,6 +802,17 @@ extern "C" int asr_probe_decode_attention_beam(int bf16, int rows, int beam, int
     gemm_reload_env();
     if (bf16) probe_decode_attention_beam<bf16_t>(rows, beam, H, S, p0, hist, hist_dev, src, ld_src, q, kv_new, ext, out, stray, kernel);
     else probe_decode_attention_beam<float>(rows, beam, H, S, p0, hist, hist_dev, src, ld_src, q, kv_new, ext, out, stray, kernel);
+  });
+}
+
+extern "C" int asr_probe_decode_attention_beam_ks(int bf16, int rows, int beam, int H, int S, int p0, int hist, int hist_dev, const int32_t* src, int ld_src,
+                                                  const float* q, const float* kv_new, float* ext, float* out, int32_t* stray, char* kernel, const int32_t* key_start) {
+  return asr_guard([&] {
+    ASR_REQUIRE(kernel, "probe_decode_attention_beam_ks: null kernel buffer");
+    asr_require_device(0);
+    gemm_reload_env();
+    if (bf16) probe_decode_attention_beam<bf16_t>(rows, beam, H, S, p0, hist, hist_dev, src, ld_src, q, kv_new, ext, out, stray, kernel, key_start);
+    else probe_decode_attention_beam<float>(rows, beam, H, S, p0, hist, hist_dev, src, ld_src, q, kv_new, ext, out, stray, kernel, key_start);
   });
 }
 
@@ -1075,6 +1115,25 @@ extern "C" int asr_probe_decode_attention(asr_probe_decode_attn_desc* d) {
     gemm_reload_env();
     if (d->bf16) probe_decode_attention<bf16_t>(d);
     else probe_decode_attention<float>(d);
+  });
+}
+
+extern "C" int asr_probe_decode_attention_ks(asr_probe_decode_attn_desc* d, const int32_t* key_start) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d, "probe_decode_attention_ks: null descriptor");
+    asr_require_device(0);
+    gemm_reload_env();
+    if (d->bf16) probe_decode_attention<bf16_t>(d, key_start);
+    else probe_decode_attention<float>(d, key_start);
+  });
+}
+
+extern "C" int asr_probe_prompt_attention(asr_probe_decode_attn_desc* d, const int32_t* key_start) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d, "probe_prompt_attention: null descriptor");
+    asr_require_device(0);
+    if (d->bf16) probe_decode_attention<bf16_t>(d, key_start, true);
+    else probe_decode_attention<float>(d, key_start, true);
   });
 }
 

@@ -21,7 +21,7 @@ namespace {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-// Beam search: the prompt's self-K/V rows (positions < p0 of every layer, at most 8) from the session's cache -- the paged pool or the contiguous extents --
+// Beam search: the prompt's self-K/V rows (slots < p0 of every layer: the prefill's, pad slots of a left-padded prompt included -- key_start keeps those out of the attention) from the session's cache -- the paged pool or the contiguous extents --
 // into every hypothesis row's extent, once per search. Grid (rows, layers x 2 x heads); extents [layer][row][K | V][head][S][64].
 template <typename T>
 __global__ __launch_bounds__(256) void wh_beam_prompt_kernel(const T* __restrict__ pool, const int32_t* __restrict__ ptable, int pages_per_seq,
@@ -67,6 +67,13 @@ struct WhSession : asr_session {
   DeviceBuffer d_plan, d_audio, d_mel, d_blkmax, d_x0, d_h1, d_xa, d_xb, d_xc, d_h, d_qk, d_vt, d_ctx, d_ffn, d_cross;
   // decoder state
   DeviceBuffer d_kc, d_vc, d_ids, d_next, d_logits, d_dx, d_dqkv, d_dtok, d_hist;
+  // Text prompts (asr_whisper_prefill_prompts): a batch of ragged prompt lengths is prefilled as n = max(len) slots per sequence, sequence b LEFT-padded by
+  // pad[b] = n - len[b] slots, so the session keeps ONE history counter and every later single-token step stays uniform (one position per sequence, one
+  // captured graph). Slot s of sequence b is position s - pad[b]; the keys in slots below pad[b] do not exist for it. d_kstart [B] holds pad[b] while
+  // kstart_on (from such a prefill until the next prefill / encode): the embedding subtracts it, the single-token self-attention forms skip the keys below it.
+  DeviceBuffer d_kstart;
+  bool kstart_on = false;
+  const int32_t* kstart() const { return kstart_on ? d_kstart.as<int32_t>() : nullptr; }
   // Paged self-KV cache (the default; ASR_KV_PAGED=0 keeps one contiguous max_target_positions extent per sequence and head in d_kc / d_vc).
   // Pool d_kvpool: pages of KV_PAGE positions, page-major [page][layer][K | V][head][KV_PAGE][64], so a page carries one 16-position slice of a
   // sequence for every layer and the pool grows by appending pages (the old pool is a prefix of the new one: one copy). Block table d_ptable
@@ -131,8 +138,9 @@ struct WhSession : asr_session {
   SplitKGemm sk;
   void gemm(const GemmArgs& g) { sk.run(g, precision, stream); }
   template <typename T> void encode(const void* audio, int audio_mem, const int64_t* offs, int B, int32_t* n_pos_out);
-  template <typename T> void enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev, const BeamStep* bs = nullptr);
-  template <typename T> void step(const int32_t* ids_host, int n, bool is_prefill, int32_t* next_out, float* logits_out);
+  template <typename T> void enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev, const BeamStep* bs = nullptr, bool prompt = false);
+  template <typename T> void step(const int32_t* ids_host, int n, bool is_prefill, int32_t* next_out, float* logits_out, const int32_t* pad_host = nullptr);
+  void prefill_prompts(const int32_t* ids, const int32_t* offsets, int32_t* next_out, float* logits_out);
   template <typename T> void beam_search(int beam, int max_new, int eos_id, int32_t* tokens_out, int32_t* n_out, float* scores_out);
 };
 
@@ -428,8 +436,9 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, in
 // Beam search (bs set, n = beam): the R = B * beam rows are hypotheses, one new position each (bs->hist); the self-attention follows every row's
 // ancestry through the row extents, the cross-attention reads each utterance's slab once for its n = beam rows (the prefill's form), and the head
 // ranks the rows' extensions instead of taking an arg-max.
+// prompt: a prefill of left-padded prompts (pad_host of step()): n may exceed 8 and both attentions run on the prompt-attention kernel (csrc/prompt_attn.hip).
 template <typename T>
-void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev, const BeamStep* bs) {
+void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, bool use_hist_dev, const BeamStep* bs, bool prompt) {
   const auto& c = cfg;
   const int B = batch, d = c.d_model, dff = c.d_ffn, Ld = c.n_dec_layers, H = c.n_heads;
   const int R = B * n, Rp = round_up(R, 128);
@@ -485,7 +494,7 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
   auto run_chain = [&](hipStream_t st, int ci, int b0, int nb) {
     const int r0 = b0 * n, Rc = nb * n;
     { ProfScope ps(prof, "dec_embed", st);
-      launch_embed_pos<T>(ids_dev + r0, Rc, bs ? 1 : n, hist, hd, (const T*)embed, dec_pos, d, xa + (size_t)r0 * d, st);
+      launch_embed_pos<T>(ids_dev + r0, Rc, bs ? 1 : n, hist, hd, (const T*)embed, dec_pos, d, xa + (size_t)r0 * d, st, kstart(), bs ? bs->beam : n);
       if (dgm) launch_rows_to_bf16(xa + (size_t)r0 * d, xa_lo + (size_t)r0 * d, (size_t)(NC == 1 ? Rp : Rc) * d, st); }
     for (int l = 0; l < Ld; ++l) {
       const DecLayer& L = dec[l];
@@ -503,7 +512,7 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
           T* ext = d_bext.as<T>() + (size_t)l * R * 2 * H * bs->S * 64;
           a.k_base = ext; a.v_base = ext + (size_t)H * bs->S * 64;
           a.stride_b = (int64_t)2 * H * bs->S * 64; a.stride_h = (int64_t)bs->S * 64;
-          a.beam_src = bs->src; a.ld_src = bs->ld_src; a.beam_p0 = bs->p0; a.beam = bs->beam;
+          a.beam_src = bs->src; a.ld_src = bs->ld_src; a.beam_p0 = bs->p0; a.beam = bs->beam; a.key_start = kstart();
           a.plan = nullptr; a.hist = 0; a.hist_dev = hd; a.n = 1; a.n_heads = H; a.causal = 1; a.out = ctx; a.ld_out = d;
           a.max_keys = c.max_target_positions;
           launch_decode_attention<T>(a, R, st);
@@ -519,7 +528,17 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
         a.plan = nullptr; a.hist = hist; a.hist_dev = hd; a.n = n; a.n_heads = H; a.causal = 1; a.out = ctx; a.ld_out = d;
         a.max_keys = c.max_target_positions;
         a.b0 = b0;
-        launch_decode_attention<T>(a, nb, st);
+        if (prompt) {                                      // left-padded prompt rows (history 0): all n K / V rows go to the cache, row i sees slots pad[b] .. i
+          PromptAttnArgs pa;
+          pa.q = qkv; pa.ld_q = 3 * d; pa.kv_new = qkv; pa.ld_new = 3 * d; pa.k_col0 = d; pa.v_col0 = 2 * d;
+          pa.k_base = a.k_base; pa.v_base = a.v_base; pa.stride_b = a.stride_b; pa.stride_h = a.stride_h;
+          pa.page_table = a.page_table; pa.pages_per_seq = a.pages_per_seq; pa.page_stride = a.page_stride;
+          pa.key_start = kstart(); pa.n = n; pa.n_heads = H; pa.out = ctx; pa.ld_out = d;
+          launch_prompt_attention<T>(pa, nb, st);
+        } else {
+          a.key_start = kstart();
+          launch_decode_attention<T>(a, nb, st);
+        }
         }
       }
       if (dgm) {
@@ -559,7 +578,14 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
           a.k_scale = d_cscale.as<float>() + (size_t)(0 * Ld + l) * H * B; a.v_scale = d_cscale.as<float>() + (size_t)(1 * Ld + l) * H * B;
         }
         a.b0 = b0; a.scale_ld = B;
-        launch_decode_attention<T>(a, nb, st);
+        if (prompt) {
+          PromptAttnArgs pa;
+          pa.q = cq; pa.ld_q = d; pa.k_base = a.k_base; pa.v_base = a.v_base; pa.stride_h = a.stride_h; pa.plan = dp;
+          pa.key_start = kstart(); pa.n = n; pa.n_heads = H; pa.out = ctx; pa.ld_out = d;
+          launch_prompt_attention<T>(pa, nb, st);
+        } else {
+          launch_decode_attention<T>(a, nb, st);
+        }
       }
       if (dgm) {
         dg(st, ci, r0, Rc, l, ctx, d, L.wco, 3, d, d, L.bco, nullptr, xb, ACT_NONE, xc, xc_lo, d);
@@ -650,11 +676,13 @@ void WhSession::ensure_kv_pages(int B, int positions, size_t elem_bytes) {
 }
 
 template <typename T>
-void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* next_out, float* logits_out) {
+void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* next_out, float* logits_out, const int32_t* pad_host) {
   const auto& c = cfg;
   ASR_REQUIRE(batch > 0, "whisper: encode a batch before prefill / decode");
-  ASR_REQUIRE(n >= 1 && n <= 8, "whisper: %d tokens per step (1..8)", n);
-  if (is_prefill) hist = 0;                      // the reference always prefills with an empty self-KV (:476-480)
+  const bool prompt = pad_host != nullptr;       // left-padded prompts: [B][n] ids with pad_host[b] pad slots in front (prefill_prompts)
+  ASR_REQUIRE(!prompt || (is_prefill && ids_host), "whisper: left-padded prompts belong to a prefill");
+  ASR_REQUIRE(n >= 1 && n <= (prompt ? c.max_target_positions : 8), "whisper: %d tokens per step (1..%d)", n, prompt ? c.max_target_positions : 8);
+  if (is_prefill) { hist = 0; kstart_on = false; }   // the reference always prefills with an empty self-KV (:476-480)
   ASR_REQUIRE(hist + n <= c.max_target_positions, "whisper: %d positions exceed max_target_positions %d", hist + n, c.max_target_positions);
   HIP_CHECK(hipSetDevice(device));
   const int B = batch, d = c.d_model, dff = c.d_ffn, Ld = c.n_dec_layers, H = c.n_heads;
@@ -664,7 +692,7 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { void* before = buf.ptr; buf.reserve(bytes, stream); if (buf.ptr != before) ++ws_epoch; };
   if (kv_paged) ensure_kv_pages(B, hist + n, eT);
   else { grow(d_kc, cache_elems * eT); grow(d_vc, cache_elems * eT); }
-  grow(d_ids, (size_t)B * 8 * 4);
+  grow(d_ids, (size_t)B * std::max(n, 8) * 4);
   grow(d_next, (size_t)B * 4);
   grow(d_hist, 256);
   head.reserve(B, stream);
@@ -680,7 +708,7 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
   }
   const int32_t* ids_dev;
   if (ids_host) {
-    h_io.reserve((size_t)R * 4 + 64);
+    h_io.reserve((size_t)(R + B) * 4 + 64);
     int32_t* stage = h_io.as<int32_t>();
     for (int i = 0; i < R; ++i) {
       ASR_REQUIRE(ids_host[i] >= 0 && ids_host[i] < c.vocab, "whisper: token id %d out of range", ids_host[i]);
@@ -696,13 +724,21 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
     HIP_CHECK(hipMemsetAsync(d_hist.ptr, 0, 4, stream));
     head.restart(stream);
   }
+  if (prompt) {                                    // pad[b] behind the ids in the staging buffer (the copies above and here are ordered on the stream)
+    grow(d_kstart, (size_t)std::max(B, 64) * 4);
+    int32_t* stage = h_io.as<int32_t>() + R;
+    for (int b = 0; b < B; ++b) stage[b] = pad_host[b];
+    HIP_CHECK(hipMemcpyAsync(d_kstart.ptr, stage, (size_t)B * 4, hipMemcpyHostToDevice, stream));
+    kstart_on = true;
+  }
   // single-token steps fed from the device are position independent => one graph for all of them
   const bool graphable = use_graph && !ids_host && n == 1 && !taps_enabled && !prof.enabled && !head.noise_armed;
   GraphKey gk;
   gk.mix((uint64_t)B).mix((uint64_t)Mpad).mix(ws_epoch).mix(head.epoch).mix(stream);
+  if (kstart_on) gk.mix((uint64_t)2).mix(d_kstart.ptr);                              // the single-token forms with key_start, and the pointer they read
   if (wts_on) gk.mix((uint64_t)1).mix(wts_epoch).mix((uint64_t)wts_p0).mix((uint64_t)wts_max_rows).mix((uint64_t)wts_ld).mix(d_wscores.ptr);      // what the capture bakes in
   const uint64_t key = gk.h;
-  dec_graph.run(stream, graphable, key, [&] { enqueue_step<T>(ids_dev, n, is_prefill, true); });
+  dec_graph.run(stream, graphable, key, [&] { enqueue_step<T>(ids_dev, n, is_prefill, true, nullptr, prompt); });
   if (wts_on) wts_rows = std::min(wts_rows + 1, wts_max_rows);
   hist += n;
   head.consumed();
@@ -711,6 +747,39 @@ void WhSession::step(const int32_t* ids_host, int n, bool is_prefill, int32_t* n
     download_step(h_io, d_next.ptr, d_logits.ptr, vpad, B, c.vocab, next_out, logits_out, stream);
     if (prof.enabled) prof.collect();
   }
+}
+
+// Prefill with one prompt per sequence (asr_whisper_prefill_prompts): equal lengths of at most 8 ids are the plain prefill; anything else is prefilled as
+// max(len) left-padded slots per sequence. A pad slot is staged with id 0 at position 0: it only has to read inside the tables, no real row attends it.
+void WhSession::prefill_prompts(const int32_t* ids, const int32_t* offsets, int32_t* next_out, float* logits_out) {
+  const auto& c = cfg;
+  ASR_REQUIRE(batch > 0, "whisper: encode a batch before prefill / decode");
+  const int B = batch;
+  ASR_REQUIRE(offsets[0] >= 0, "whisper_prefill_prompts: offsets[0] = %d is negative", offsets[0]);
+  int n = 0, n_min = c.max_target_positions + 1;
+  for (int b = 0; b < B; ++b) {
+    ASR_REQUIRE(offsets[b + 1] > offsets[b], "whisper_prefill_prompts: offsets must ascend and every prompt needs at least one id (offsets[%d] = %d, offsets[%d] = %d)",
+                b, offsets[b], b + 1, offsets[b + 1]);
+    const int len = offsets[b + 1] - offsets[b];
+    ASR_REQUIRE(len <= c.max_target_positions, "whisper_prefill_prompts: prompt %d has %d ids, max_target_positions is %d", b, len, c.max_target_positions);
+    n = std::max(n, len); n_min = std::min(n_min, len);
+  }
+  const bool bf = precision == ASR_PRECISION_BF16;
+  if (n == n_min && n <= 8) {                                      // uniform and short: the existing prefill, bit for bit
+    if (bf) step<bf16_t>(ids + offsets[0], n, true, next_out, logits_out);
+    else step<float>(ids + offsets[0], n, true, next_out, logits_out);
+    return;
+  }
+  ASR_REQUIRE(!fp8, "whisper_prefill_prompts: FP8W / FP8MM / MXFP4W sessions take equal prompt lengths of at most 8 ids (their cross-K/V slabs are e4m3; "
+                    "prompts of %d..%d ids need an F32 or BF16 session)", n_min, n);
+  std::vector<int32_t> padded((size_t)B * n, 0), pad(B);
+  for (int b = 0; b < B; ++b) {
+    const int len = offsets[b + 1] - offsets[b];
+    pad[b] = n - len;
+    memcpy(padded.data() + (size_t)b * n + pad[b], ids + offsets[b], (size_t)len * 4);
+  }
+  if (bf) step<bf16_t>(padded.data(), n, true, next_out, logits_out, pad.data());
+  else step<float>(padded.data(), n, true, next_out, logits_out, pad.data());
 }
 
 // Beam search after a prefill (semantics of oracle/qwen_asr_oracle.py:beam_search_core, stop set {eos_id}): the first ranking reads the prefill's logits + BEGIN_SUPPRESS,
@@ -760,7 +829,7 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   const bool graphable = use_graph && !taps_enabled && !prof.enabled;
   GraphKey key;                                             // everything the captured step bakes in
   for (uint64_t v : {(uint64_t)B, (uint64_t)beam, (uint64_t)S, (uint64_t)p0, (uint64_t)ld, (uint64_t)n_stop, (uint64_t)Mpad, ws_epoch, ranker.epoch,
-                     (uint64_t)(uintptr_t)stream, head.epoch})
+                     (uint64_t)(uintptr_t)stream, head.epoch, (uint64_t)(kstart_on ? (uintptr_t)d_kstart.ptr : 0)})
     key.mix(v);
   for (int t = 0; t + 1 < max_new && !ranker.all_done(stream); ++t) {
     bs.src = ranker.ancestry();
@@ -918,6 +987,7 @@ extern "C" int asr_whisper_encode(asr_session* s, const void* audio, int audio_m
     WhSession* w = static_cast<WhSession*>(s);
     w->after_prefill = false;
     w->wts_p0 = -1; w->wts_rows = 0;                      // captured rows belong to the slabs they were scored against
+    w->kstart_on = false;
     if (w->precision == ASR_PRECISION_BF16) w->encode<bf16_t>(audio, audio_mem, audio_offsets, batch, n_positions_out);
     else w->encode<float>(audio, audio_mem, audio_offsets, batch, n_positions_out);
   });
@@ -931,6 +1001,17 @@ extern "C" int asr_whisper_prefill(asr_session* s, const int32_t* ids, int n, in
     w->after_prefill = false;
     if (w->precision == ASR_PRECISION_BF16) w->step<bf16_t>(ids, n, true, next_ids_out, logits_out);
     else w->step<float>(ids, n, true, next_ids_out, logits_out);
+    w->after_prefill = true;
+  });
+}
+
+extern "C" int asr_whisper_prefill_prompts(asr_session* s, const int32_t* ids, const int32_t* offsets, int32_t* next_ids_out, float* logits_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 2 && ids && offsets, "whisper_prefill_prompts: bad argument");
+    TenantScope tenant(s);
+    WhSession* w = static_cast<WhSession*>(s);
+    w->after_prefill = false;
+    w->prefill_prompts(ids, offsets, next_ids_out, logits_out);
     w->after_prefill = true;
   });
 }

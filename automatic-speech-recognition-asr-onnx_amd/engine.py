@@ -598,6 +598,21 @@ class WhisperSession(_token_head("whisper", 20, "Decode head: 1.0 = plain arg-ma
         _lib.check(_lib.load().asr_whisper_prefill(self._h, _ip(ids), ids.shape[1], _ip(nxt), _fp(logits)))
         return nxt, logits
 
+    def prefill_prompts(self, prompts, want_logits: bool = True):
+        """Prefill with one prompt (an array of ids, 1 .. max_target_positions of them) per sequence -- asr_whisper_prefill_prompts. Ragged or long prompts
+        are left-padded to the longest one on the device; decode / generate / beam_search / token scores / align then work as after prefill(), with the
+        longest prompt as the prompt length (it bounds the whole batch: longest + new positions <= max_target_positions)."""
+        prompts = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in prompts]
+        if not self.batch or len(prompts) != self.batch:
+            raise ValueError(f"{len(prompts)} prompts != encoded batch {self.batch}")
+        offs = np.zeros(len(prompts) + 1, dtype=np.int32)
+        offs[1:] = np.cumsum([p.size for p in prompts])
+        ids = np.ascontiguousarray(np.concatenate(prompts + [np.zeros(1, dtype=np.int32)]))      # (never empty: a prompt of 0 ids is the library's error)
+        nxt = np.zeros(self.batch, dtype=np.int32)
+        logits = np.empty((self.batch, self.cfg.vocab), dtype=np.float32) if want_logits else None
+        _lib.check(_lib.load().asr_whisper_prefill_prompts(self._h, _ip(ids), _ip(offs), _ip(nxt), _fp(logits)))
+        return nxt, logits
+
     def decode(self, ids=None, want_logits: bool = False, sync: bool = True):
         nxt = np.zeros(self.batch, dtype=np.int32) if sync else None
         logits = np.empty((self.batch, self.cfg.vocab), dtype=np.float32) if want_logits else None

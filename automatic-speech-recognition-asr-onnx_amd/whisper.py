@@ -243,6 +243,16 @@ def compression_ratio(text: str) -> float:
     return len(raw) / len(zlib.compress(raw))
 
 
+def build_prompt(cfg: WhisperConfig, head_ids: Sequence[int], prev_ids: Sequence[int] | None) -> list[int]:
+    """OpenAI Whisper's _get_initial_tokens: [<|startofprev|>] + the last max_target_positions // 2 - 1 ids of the previous text + the decoding head
+    ([SOT, language, task(, <|notimestamps|>)]); the head alone when there is no previous text."""
+    prev = [int(t) for t in prev_ids] if prev_ids is not None else []
+    if not prev:
+        return [int(t) for t in head_ids]
+    keep = cfg.max_target_positions // 2 - 1
+    return [cfg.sot_prev_id] + prev[-keep:] + [int(t) for t in head_ids]
+
+
 class WhisperTranscriber:
     def __init__(self, cfg: WhisperConfig, session: WhisperSession, suppress_tokens=None, task: str = "transcribe",
                  detect_language: bool = True, no_speech_detection: bool = True, no_speech_threshold: float = 0.6,
@@ -252,7 +262,19 @@ class WhisperTranscriber:
                  timestamps: bool = False, max_initial_timestamp: float | None = 1.0, word_timestamps: bool = False, alignment_heads=None,
                  medfilt_width: int = 7, piece_decoder=None, token_scores: bool = False, temperature_fallback=None,
                  compression_ratio_threshold: float | None = 2.4, logprob_threshold: float | None = -1.0,
-                 hotwords=None, hotword_boost: float = 2.0, hotword_encoder=None):
+                 hotwords=None, hotword_boost: float = 2.0, hotword_encoder=None,
+                 initial_prompt=None, condition_on_previous_text: bool = False, prompt_encoder=None, prompt_reset_temperature: float = 0.5):
+        # text prompts (the build's own mode, OpenAI Whisper's options; WhisperSession.prefill_prompts): initial_prompt = token ids of a glossary / style hint,
+        # or text when prompt_encoder(text) -> ids is given (a tokenizer's encode without special tokens); condition_on_previous_text: transcribe_file runs
+        # its windows in order, each prompted with the ids kept so far, and forgets them after a window whose fallback ended above prompt_reset_temperature.
+        if isinstance(initial_prompt, str):
+            if prompt_encoder is None:
+                raise ValueError("initial_prompt given as text needs prompt_encoder(text) -> ids")
+            initial_prompt = prompt_encoder((" " + initial_prompt.strip()))
+        self.initial_prompt = [int(t) for t in initial_prompt] if initial_prompt is not None else []
+        if any(t < 0 or t >= cfg.eot_id for t in self.initial_prompt):
+            raise ValueError("initial_prompt holds text ids only (0 .. eot_id - 1)")
+        self.condition_on_previous_text, self.prompt_reset_temperature = bool(condition_on_previous_text), float(prompt_reset_temperature)
         # hotword boosting (the build's own: asr_whisper_set_hotwords): token-id lists, or text when hotword_encoder(text) -> ids is given (a tokenizer's
         # encode without special tokens; a text phrase is boosted in both of its spellings, at the start of the text and inside it). The list is in force from
         # the full-prompt prefill to the last id of every decode, fallback attempts and the beam search included; the [SOT] probe and the forced alignment
@@ -299,6 +321,23 @@ class WhisperTranscriber:
         head = [self.cfg.sot_id, int(lang), self.task_token]
         return head if self.timestamps else head + [self.cfg.no_timestamps_id]
 
+    def _prompts(self, langs, prev=None):
+        """One prompt per utterance: build_prompt over its decoding head and initial_prompt + its previous-text ids (prev: per utterance, or None)."""
+        return [np.asarray(build_prompt(self.cfg, self._prompt(l), self.initial_prompt + ([int(t) for t in prev[b]] if prev is not None else [])), np.int32)
+                for b, l in enumerate(langs)]
+
+    def _limit(self, prompts, max_new=None) -> int:
+        """New ids a batch may take: the longest prompt bounds all of it (its slots are the batch's), then max_new."""
+        limit = max(0, self.cfg.max_target_positions - max(len(p) for p in prompts))
+        return limit if max_new is None else min(limit, int(max_new))
+
+    def _prefill(self, prompts):
+        """The full-prompt prefill: equal lengths of at most 8 ids are the plain prefill, anything else goes through prefill_prompts (left-padded on the device)."""
+        n = len(prompts[0])
+        if n <= 8 and all(len(p) == n for p in prompts):
+            return self.sess.prefill(np.stack([np.asarray(p, np.int32) for p in prompts]), want_logits=False)
+        return self.sess.prefill_prompts(prompts, want_logits=False)
+
     def _probe_prefill(self, B: int):
         """The [SOT] probe: raw logits from the plain arg-max head (no penalty, no sampling, no timestamp rules)."""
         self.sess.set_sampling(False)
@@ -315,7 +354,7 @@ class WhisperTranscriber:
         -> (ids, frames, scores). frames: per utterance (the aligned frames of its text tokens -- None: nothing aligned --, whether the ids ended with eot); with
         word_timestamps they are captured live while the ids are generated, or by a forced pass when the ids carry timestamps or come from the beam search
         (align=False: neither, the caller aligns the ids it keeps). scores: sess.token_scores() of this decode, None with token_scores off."""
-        B = prompt.shape[0]
+        B = len(prompt)
         live = self.word_timestamps and not self.timestamps and self.beam_size == 1 and limit > 0 and align
         frames = [(None, True)] * B
         scores = None
@@ -330,7 +369,7 @@ class WhisperTranscriber:
         if self.hotwords:
             self.sess.set_hotwords(self.hotwords, self.hotword_boost)
         try:
-            self.sess.prefill(prompt, want_logits=False)
+            self._prefill(prompt)
             toks = self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * B
             if self.token_scores:
                 scores = self.sess.token_scores()
@@ -373,7 +412,7 @@ class WhisperTranscriber:
         if not self.token_scores:
             toks, frames, _ = self._prefill_and_continue(prompt, limit, audio_samples, skip)
             return toks, frames, None
-        B = prompt.shape[0]
+        B = len(prompt)
         fallback = bool(self.temperature_fallback)
         use, temperature, top_k, top_p, rep_penalty, seed = self.sampling
         toks, quality, frames = [None] * B, [None] * B, [(None, True)] * B
@@ -419,15 +458,17 @@ class WhisperTranscriber:
         """What OpenAI does after decoding: the capture over the final text ids only, behind a <|notimestamps|> prompt -- a prefill and host-fed decode steps
         under the plain head, timestamp rules off; an utterance that has run out of ids is fed eot. The row of the last text id predicts eot."""
         cfg, sess = self.cfg, self.sess
-        B, longest = prompt.shape[0], max((len(t) for t in text_ids), default=0)
+        B, longest = len(prompt), max((len(t) for t in text_ids), default=0)
         if longest == 0:
             return [(None, True)] * B
-        forced = np.concatenate([prompt[:, :3], np.full((B, 1), cfg.no_timestamps_id, np.int32)], axis=1).astype(np.int32)
+        hl = 3 if self.timestamps else 4                     # the decoding head ends every prompt; what stands in front of it (previous text) stays
+        forced = [np.concatenate([np.asarray(p[:len(p) - hl], np.int32), np.asarray(p[len(p) - hl:][:3], np.int32), [cfg.no_timestamps_id]]).astype(np.int32)
+                  for p in prompt]
         sess.set_penalty(1.0, self.penalty_range)
         sess.set_sampling(False)
         sess.set_word_timestamps(True, self.alignment_heads, longest + 1)
         try:
-            sess.prefill(forced, want_logits=False)
+            self._prefill(forced)
             for t in range(longest):
                 sess.decode(np.asarray([ids[t] if t < len(ids) else cfg.eot_id for ids in text_ids], np.int32))
             return self._align([len(ids) + 1 if ids else 0 for ids in text_ids], [True] * B, audio_samples, skip)
@@ -468,9 +509,11 @@ class WhisperTranscriber:
             return [hyps[0][0] for hyps in self.sess.beam_search(self.beam_size, limit, eos_id=self.cfg.eot_id)]
         return self.sess.generate(limit, eos_id=self.cfg.eot_id)
 
-    def transcribe(self, clips_int16: Sequence[np.ndarray], language_ids: Sequence[int] | None = None, max_new: int | None = None):
-        """List of int16 mono 16 kHz clips (each <= 30 s) -> per clip dict(tokens, language_id, no_speech_prob, skipped). Timestamp mode adds
-        segments = [{"start", "end", "tokens"}] (seconds from the clip's start) and keeps text ids only in tokens; the repeat guard is not applied."""
+    def transcribe(self, clips_int16: Sequence[np.ndarray], language_ids: Sequence[int] | None = None, max_new: int | None = None, prompts=None):
+        """List of int16 mono 16 kHz clips (each <= 30 s) -> per clip dict(tokens, language_id, no_speech_prob, skipped, prompt_len). Timestamp mode adds
+        segments = [{"start", "end", "tokens"}] (seconds from the clip's start) and keeps text ids only in tokens; the repeat guard is not applied.
+        prompts: per clip the ids of its previous text (any lengths, None / empty: none) -- how a caller batches window k of many files; initial_prompt goes
+        in front of each. The longest prompt bounds the whole batch: new ids <= max_target_positions - longest prompt."""
         cfg = self.cfg
         audios = [prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(-1), self.sess.audio_dtype) for c in clips_int16]
         B = len(audios)
@@ -485,16 +528,16 @@ class WhisperTranscriber:
             if self.no_speech_detection:
                 probs = self.sess.no_speech_prob(cfg.no_speech_id)          # device head over the probe's logits
         skipped = probs >= self.no_speech_threshold if self.no_speech_detection else np.zeros(B, dtype=bool)
-        prompt = np.stack([self._prompt(l) for l in lang]).astype(np.int32)
-        limit = max(0, cfg.max_target_positions - prompt.shape[1])
-        if max_new is not None:
-            limit = min(limit, max_new)
+        if prompts is not None and len(prompts) != B:
+            raise ValueError(f"{len(prompts)} prompts for {B} clips")
+        prompt = self._prompts(lang, None if prompts is None else [p if p is not None else [] for p in prompts])
+        limit = self._limit(prompt, max_new)
         toks, aligned, quality = self._decode(prompt, limit, [a.size for a in audios], skipped)
         wall = time.time() - t0
         out = []
         for b in range(B):
             ids = [] if skipped[b] else toks[b].tolist()
-            res = {"language_id": int(lang[b]), "no_speech_prob": float(probs[b]), "skipped": bool(skipped[b])}
+            res = {"language_id": int(lang[b]), "no_speech_prob": float(probs[b]), "skipped": bool(skipped[b]), "prompt_len": len(prompt[b])}
             lps = None
             if quality is not None:
                 q = quality[b]
@@ -528,7 +571,12 @@ class WhisperTranscriber:
         included) and the repeat guard is not applied.
         With token_scores the result gains token_logprobs (the windows' scores concatenated as their ids are), avg_logprob (pooled over every pick of every
         window), compression_ratio (of the whole text), temperature (the highest any window needed) and window_scores = per window
-        {"avg_logprob", "compression_ratio", "temperature"}: the fallback decides window by window, so these are the figures it acted on."""
+        {"avg_logprob", "compression_ratio", "temperature"}: the fallback decides window by window, so these are the figures it acted on.
+        Text prompts: initial_prompt stands in front of every window's prompt (OpenAI's carry_initial_prompt) and the windows stay one batch. With
+        condition_on_previous_text the windows run IN ORDER, one encode each: window w is prompted with initial_prompt + the text ids kept since the last
+        reset (build_prompt keeps the last max_target_positions // 2 - 1 of them); a window whose decode ended at a temperature above prompt_reset_temperature
+        forgets them (that needs temperature_fallback: without it the temperature never rises and nothing is reset), a later window whose own [SOT] probe says
+        no speech is skipped and adds nothing. max_new is clamped to max_target_positions - prompt length. The result gains prompt_len, per window."""
         cfg = self.cfg
         raw = np.asarray(pcm_int16, dtype=np.int16).reshape(-1)
         audio_len = int(raw.size)
@@ -543,10 +591,12 @@ class WhisperTranscriber:
         clips = [np.ascontiguousarray(audio[w * stride:w * stride + window]) for w in range(n_win)]
         lang = cfg.first_language_id if language_id is None else int(language_id)
         t0 = time.time()
-        self.sess.encode(clips)
+        chained = self.condition_on_previous_text and n_win > 1
+        self.sess.encode(clips[:1] if chained else clips)                # (chained: one encode per window, as each one's turn comes)
+        n_probe = 1 if chained else n_win
         prob, no_speech = 0.0, False
         if self.detect_language or self.no_speech_detection:            # needs_probe: window 0 only (:768)
-            logits = self._probe_prefill(n_win)
+            logits = self._probe_prefill(n_probe)
             if self.detect_language:
                 lang = int(self.language_token_ids[np.argmax(logits[0, self.language_token_ids])])
             if self.no_speech_detection:
@@ -554,17 +604,46 @@ class WhisperTranscriber:
                 no_speech = prob >= self.no_speech_threshold             # aborts the file (:801-805)
         windows: list[list[int]] = []
         quality = None
-        if not no_speech:
-            prompt = np.tile(np.asarray([self._prompt(lang)], dtype=np.int32), (n_win, 1))
-            limit = max(0, cfg.max_target_positions - prompt.shape[1])
-            if max_new is not None:
-                limit = min(limit, max_new)
-            toks, frames_w, quality = self._decode(prompt, limit, [min(window, max(1, audio_len - w * stride)) for w in range(n_win)])
+        prompt_lens: list[int] = []
+        samples = [min(window, max(1, audio_len - w * stride)) for w in range(n_win)]
+        limit = 0
+        if not no_speech and not chained:
+            prompt = self._prompts([lang] * n_win)
+            limit = self._limit(prompt, max_new)
+            toks, frames_w, quality = self._decode(prompt, limit, samples)
             windows = [t.astype(int).tolist() for t in toks]
+            prompt_lens = [len(p) for p in prompt]
+        elif not no_speech:
+            # the windows in order: each sees what the ones before it kept. limits[w] is window w's own (its prompt's) limit
+            prev: list[int] = []
+            frames_w, limits = [], []
+            quality = [] if self.token_scores else None
+            for w in range(n_win):
+                if w > 0:
+                    self.sess.encode(clips[w:w + 1])
+                    if self.no_speech_detection:
+                        self._probe_prefill(1)
+                        if float(self.sess.no_speech_prob(cfg.no_speech_id)[0]) >= self.no_speech_threshold:      # nothing said here: nothing decoded, nothing added
+                            windows.append([]); frames_w.append((None, True)); limits.append(0); prompt_lens.append(0)
+                            if quality is not None:
+                                quality.append({"logprobs": np.zeros(0, np.float32), "avg_logprob": 0.0, "compression_ratio": None, "temperature": 0.0})
+                            continue
+                prompt = self._prompts([lang], [prev])
+                lim = self._limit(prompt, max_new)
+                toks, fr, q = self._decode(prompt, lim, samples[w:w + 1])
+                ids_w = toks[0].astype(int).tolist()
+                windows.append(ids_w); frames_w.append(fr[0]); limits.append(lim); prompt_lens.append(len(prompt[0]))
+                if quality is not None:
+                    quality.append(q[0])
+                if q is not None and q[0]["temperature"] > self.prompt_reset_temperature:
+                    prev = []                                        # OpenAI's prompt_reset_since: a window decoded that hot is not trusted as context
+                else:
+                    prev = prev + self._text_ids(ids_w)
+            limit = None
         wall = time.time() - t0
         ids = [t for w in windows for t in w]
         res = {"windows": windows, "language_id": lang, "no_speech_prob": prob,
-               "no_speech": bool(no_speech), "n_windows": n_win, "stride": stride, "window": window}
+               "no_speech": bool(no_speech), "n_windows": n_win, "stride": stride, "window": window, "prompt_len": prompt_lens}
         if self.timestamps:
             res["segments"] = [seg for w, win in enumerate(windows)
                                for seg in split_segments(win, self.ts_begin, w * stride / cfg.sample_rate, window / cfg.sample_rate)]
@@ -578,7 +657,7 @@ class WhisperTranscriber:
             quality = quality or []
             win_lps = [self._text_logprobs(win, q["logprobs"]) for win, q in zip(windows, quality)]
             res["token_logprobs"] = np.concatenate(win_lps).astype(np.float32) if win_lps else np.zeros(0, np.float32)
-            picks = [len(win) + int(len(win) < limit) for win in windows]
+            picks = [len(win) + int(len(win) < (limit if limit is not None else limits[w])) for w, win in enumerate(windows)]
             res["avg_logprob"] = float(sum(q["avg_logprob"] * n for q, n in zip(quality, picks) if n) / max(1, sum(picks)))
             res["compression_ratio"] = compression_ratio(self.piece_decoder(ids)) if self.piece_decoder is not None and windows else None
             res["temperature"] = max((q["temperature"] for q in quality), default=0.0)

@@ -253,6 +253,19 @@ int asr_whisper_encode(asr_session* s, const void* audio, int audio_mem, const i
  * nullable): arg-max(logits + begin_suppress); logits_out (host [B][vocab], nullable): raw logits incl. the -128
  * suppress penalty -- what language detection and NO_SPEECH_DETECTION read (Inference_Whisper_ONNX.py:780-805). */
 int asr_whisper_prefill(asr_session* s, const int32_t* ids, int n, int32_t* next_ids_out, float* logits_out);
+/* prefill with one text prompt per sequence -- OpenAI Whisper's initial_prompt / condition_on_previous_text ([<|startofprev|>, previous text ...,
+ * <|startoftranscript|>, language, task, ...]; decoding.py:_get_initial_tokens). The reference always decodes [SOT, language, task, <|notimestamps|>], so this
+ * is the build's own mode; the truth for parity is oracle/whisper_oracle.py (WhisperOracle.decoder / .greedy take a prompt of any length per utterance).
+ * ids: host, sequence b's prompt = ids[offsets[b] .. offsets[b+1]) (1 .. max_target_positions ids each), offsets: host [B + 1], ascending. Outputs and head
+ * behaviour are those of asr_whisper_prefill (BEGIN_SUPPRESS, penalty, sampler, timestamp rules, token scores, hotwords: the hotword node starts at the
+ * root, prompt ids do not move it). Equal lengths of at most 8 ids forward to asr_whisper_prefill and give identical results. Otherwise the batch is
+ * prefilled as n = max(len) slots per sequence, sequence b left-padded by n - len[b] slots (slot s is position s - pad; the keys of the pad slots do not
+ * exist for it), so the session keeps one history counter and asr_whisper_decode / _generate / _beam_search / _token_scores / _align and word-timestamp
+ * capture work as after a prefill, with n as the prompt length: the LONGEST prompt bounds the whole batch -- n + new positions <= max_target_positions
+ * (asr_whisper_beam_search refuses more, asr_whisper_generate stops there). F32 and BF16 sessions; FP8W / FP8MM / MXFP4W sessions refuse ragged lengths
+ * and prompts of more than 8 ids (their cross-K/V slabs are e4m3, the prompt-attention kernel reads bf16 / f32 slabs). Errors: a prompt of 0 ids or of more
+ * than max_target_positions, offsets that do not ascend, an id outside the vocabulary. */
+int asr_whisper_prefill_prompts(asr_session* s, const int32_t* ids, const int32_t* offsets, int32_t* next_ids_out, float* logits_out);
 /* one position per sequence. ids: host [B], or NULL to feed the device-resident arg-max of the previous step (no
  * host round trip); next_ids_out / logits_out nullable (NULL, NULL => fully asynchronous step). */
 int asr_whisper_decode(asr_session* s, const int32_t* ids, int32_t* next_ids_out, float* logits_out);

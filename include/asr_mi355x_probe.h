@@ -109,6 +109,19 @@ int asr_probe_decode_attention(asr_probe_decode_attn_desc* d);
 int asr_probe_decode_attention_beam(int bf16, int rows, int beam, int H, int S, int p0, int hist, int hist_dev, const int32_t* src, int ld_src,
                                     const float* q, const float* kv_new, float* ext, float* out, int32_t* stray, char* kernel);
 
+/* Left-padded prompts (asr_whisper_prefill_prompts). The descriptor is the one of asr_probe_decode_attention.
+ *   asr_probe_decode_attention_ks: the same call with DecAttnArgs::key_start = key_start (host [B], 0 .. hist each; null: the plain entry): single-token
+ *         self-attention only; sequence b sees cached keys key_start[b] .. hist - 1 and its new row. `kernel`: "self_wave_ks", "general_n1_ks".
+ *   asr_probe_decode_attention_beam_ks: the beam form with key_start [rows / beam] ("self_beam_ks").
+ *   asr_probe_prompt_attention: the call goes to launch_prompt_attention (csrc/prompt_attn.hip) instead -- any n up to 1536, the whole batch (b0 = nb = 0),
+ *         self: hist = 0 (the cache image starts as NaN everywhere; k_after / v_after [B][H][n][64] and stray as above), query slot i of sequence b sees key
+ *         slots key_start[b] .. i and the slots below key_start[b] write zeros; cross: unmasked over the plan, pad slots write zeros.
+ *         `kernel`: "prompt_self" / "prompt_cross". */
+int asr_probe_decode_attention_ks(asr_probe_decode_attn_desc* d, const int32_t* key_start);
+int asr_probe_decode_attention_beam_ks(int bf16, int rows, int beam, int H, int S, int p0, int hist, int hist_dev, const int32_t* src, int ld_src,
+                                       const float* q, const float* kv_new, float* ext, float* out, int32_t* stray, char* kernel, const int32_t* key_start);
+int asr_probe_prompt_attention(asr_probe_decode_attn_desc* d, const int32_t* key_start);
+
 /* The attention stage of one Qwen3 decoder layer through the session's launcher (launch_qwen_attention, csrc/qwen_attn.h; head_dim 128) on host arrays:
  * per-head RMSNorm of q and k, RoPE, cache write, causal GQA attention. Which kernels run follows from bf16 / step / no_fuse / H / KV exactly as in a session:
  * "fused_g1|2|4" (a step), "beam_g1|2|4" (a step with beam > 0), "rope_mfma" (bf16 prefill), "rope_scalar" (f32, no_fuse). Cache operands are rounded to

@@ -74,6 +74,8 @@ def run(a) -> dict:
         raise SystemExit("--word-timestamps exists for --family whisper only")
     if timestamps and a.family not in ("sensevoice", "paraformer", "whisper"):
         raise SystemExit("--timestamps exists for --family sensevoice / paraformer (per token) and --family whisper (per segment), not for --family qwen_asr")
+    if (getattr(a, "initial_prompt_ids", None) or getattr(a, "condition_on_previous_text", False)) and a.family != "whisper":
+        raise SystemExit("--initial-prompt-ids / --condition-on-previous-text exist for --family whisper only")
     nbest, hot_file = getattr(a, "nbest", 1), getattr(a, "hotwords", None)
     if (nbest > 1 or hot_file) and a.family != "sensevoice":
         raise SystemExit("--nbest / --hotwords exist for --family sensevoice only")
@@ -142,7 +144,9 @@ def run(a) -> dict:
                                               repeat_penalty=a.repeat_penalty, beam_size=a.beam, timestamps=timestamps, word_timestamps=word_ts,
                                               alignment_heads=heads, piece_decoder=tok.decode if tok is not None and (word_ts or scores) else None,
                                               token_scores=scores, temperature_fallback=fallback, hotwords=dec_hot, hotword_boost=dec_hot_boost,
-                                              hotword_encoder=(lambda t: tok.encode(t, add_special_tokens=False)) if tok is not None else None)
+                                              hotword_encoder=(lambda t: tok.encode(t, add_special_tokens=False)) if tok is not None else None,
+                                              initial_prompt=parse_prompt_ids_file(a.initial_prompt_ids) if getattr(a, "initial_prompt_ids", None) else None,
+                                              condition_on_previous_text=bool(getattr(a, "condition_on_previous_text", False)))
         lang_id = None
         if a.language != "auto":
             if tok is None:
@@ -160,6 +164,8 @@ def run(a) -> dict:
                 text = "[no speech detected]" if r["no_speech"] else (whisper_text(tok, flat, remove_repeats=not (timestamps or word_ts or scores)) if flat else "")
             files.append({"path": p, "n_samples": int(pcm.size), "language": a.language, "windows": ids, "text": text, "rtf": stat["rtf"],
                           "language_ids": [r["language_id"]] * len(ids), "no_speech_prob": [r["no_speech_prob"]], "no_speech": r["no_speech"]})
+            if tr.initial_prompt or tr.condition_on_previous_text:        # the build's own mode: the prompt length each window was decoded behind
+                files[-1]["prompt_len"] = r["prompt_len"]
             if scores:                      # the build's own mode: one log-probability per entry of r["tokens"], OpenAI's avg_logprob / compression ratio per file and per window
                 files[-1].update(tokens=r["tokens"].astype(int).tolist(), token_logprobs=[float(v) for v in r["token_logprobs"]], avg_logprob=r["avg_logprob"],
                                  compression_ratio=r["compression_ratio"], temperature=r["temperature"], window_scores=r["window_scores"])
@@ -238,7 +244,16 @@ json.dump({"family": "<family>", "precision": "f32", "engine": "onnxruntime CPUE
 '''
 
 
-def main():
+def parse_prompt_ids_file(path):
+    """--initial-prompt-ids FILE: text token ids separated by blanks, commas or line ends."""
+    with open(path, encoding="utf-8") as f:
+        ids = [int(t) for t in f.read().replace(",", " ").split()]
+    if not ids:
+        raise SystemExit(f"--initial-prompt-ids: {path} holds no ids")
+    return ids
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
     r = sub.add_parser("run")
@@ -267,6 +282,10 @@ def main():
                         "dump; Whisper with --tokenizer also the compression ratio, and with --word-timestamps a probability per word")
     r.add_argument("--temperature-fallback", type=float, nargs="+", metavar="T", help="Whisper: decode an utterance again by sampling at these temperatures, in "
                         "order, while its average log-probability is below -1.0 or its compression ratio above 2.4 (e.g. 0.2 0.4 0.6 0.8 1.0); implies --token-scores")
+    r.add_argument("--initial-prompt-ids", metavar="FILE", help="Whisper: text token ids (blank- or comma-separated) put in front of every window's prompt behind "
+                        "<|startofprev|>: a glossary or style hint (OpenAI's initial_prompt)")
+    r.add_argument("--condition-on-previous-text", action="store_true", help="Whisper: run a file's windows in order, each prompted with the text ids of the windows "
+                        "before it; with --temperature-fallback the context is dropped after a window decoded above temperature 0.5")
     r.add_argument("--out", required=True)
     r.add_argument("--any-wav-width", dest="strict_wav", action="store_false",
                    help="accept 8 / 24 / 32-bit wav (rescaled to int16); by default only 16-bit wav is taken: the only width whose samples equal the reference's, "
@@ -275,7 +294,11 @@ def main():
     c.add_argument("ours")
     c.add_argument("reference")
     sub.add_parser("reference-stub")
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = build_parser().parse_args()
     if a.cmd == "run":
         dump = run(a)
         with open(a.out, "w", encoding="utf-8") as f:
