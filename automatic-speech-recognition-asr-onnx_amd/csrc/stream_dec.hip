@@ -16,7 +16,10 @@
 //   5  out-projection columns 128 h .. + bo + x2 = dec slab of the next layer                          -- exchange 4: dec -->
 //
 // A stream that fired no token in this chunk step leaves the launch at once (all four of its workgroups: its decoder state stays untouched, as on the
-// per-launch path). Rounding points are those of the per-launch path (bf16 GEMM operands, bf16 q / k / v / ctx, f32 everything else).
+// per-launch path). Rounding points are those of the per-launch path (bf16 GEMM operands, bf16 q / k / v / ctx, f32 everything else) with ONE addition, as in
+// the encoder launch: the soft-max weights enter P V as bf16 MFMA operands. Accuracy statement: tests/test_paraformer_stream_ref_gpu.py holds the logits of
+// every (stream, step) that fired -- one token to nine, carry and cache behind chunks that fired nothing -- to the float64 reference of the chunk step
+// (tests/paraformer_stream_ref.py) within three times the noise of exactly these rounding points.
 #include <type_traits>
 #include "stream_cluster.h"
 

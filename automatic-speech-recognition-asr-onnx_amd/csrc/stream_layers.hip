@@ -15,8 +15,10 @@
 //     per wave instruction, in consumption order), 12-16 KB per wave in flight, and the first batch of the NEXT phase is requested before the
 //     workgroup waits for its cluster -- the exchange latency hides the weight latency and the other way round;
 //   * rounding points are those of the per-launch path (bf16 operand of every GEMM, bf16 q|k|v and ctx, f32 residual stream, f32 soft-max
-//     and FSMN in LDS) with ONE addition: the soft-max weights enter P V as bf16 MFMA operands here, where stream_attn_kernel multiplies them in f32. The
-//     fixtures of the per-launch path hold for this one within the bars of tests/test_paraformer_streaming_gpu.py::test_fused_launches_vs_per_launch_path.
+//     and FSMN in LDS) with ONE addition: the soft-max weights enter P V as bf16 MFMA operands here, where stream_attn_kernel multiplies them in f32.
+//     Accuracy statement: tests/test_paraformer_stream_ref_gpu.py holds every (stream, step) of this launch -- both workgroup-to-cluster maps, mixed history
+//     lengths, a reset stream beside full histories -- to the float64 reference of the chunk step (tests/paraformer_stream_ref.py) within three times the noise
+//     of exactly these rounding points; tests/test_paraformer_streaming_gpu.py::test_fused_launches_vs_per_launch_path owns launch counts and token agreement.
 //
 // Give-up: a cluster that waits 0.2 s on a counter raises `err` and the launch runs out (results void, histories half-rolled). Round 5: when other sessions exist on the
 // GPU the host snapshots the active streams' state in front of the step, restores it and redoes the step on the per-launch path (SvSession::stream_step); without a
