@@ -301,7 +301,10 @@ def build_whisper_arena(cfg, ck: dict, precision: int = PRECISION_BF16, suppress
     # conv stem as GEMMs over time-major strided views: weight column index = tap * C_in + c_in
     c1 = ck["model.encoder.conv1.weight"]                       # (d, n_mels, 3)
     c2 = ck["model.encoder.conv2.weight"]                       # (d, d, 3)
-    w.weight("enc.conv1_w", np.ascontiguousarray(c1.transpose(0, 2, 1)).reshape(d, 3 * cfg.n_mels), precision)
+    k1 = (3 * cfg.n_mels + 63) // 64 * 64                       # conv1's K in whole GEMM K steps: zero columns behind the three taps (80 mels: 240 -> 256)
+    c1w = np.zeros((d, k1), dtype=np.float32)
+    c1w[:, :3 * cfg.n_mels] = np.ascontiguousarray(c1.transpose(0, 2, 1)).reshape(d, 3 * cfg.n_mels)
+    w.weight("enc.conv1_w", c1w, precision)
     w.add("enc.conv1_b", ck["model.encoder.conv1.bias"], DT_F32)
     w.weight("enc.conv2_w", np.ascontiguousarray(c2.transpose(0, 2, 1)).reshape(d, 3 * d), precision)
     w.add("enc.conv2_b", ck["model.encoder.conv2.bias"], DT_F32)
@@ -524,9 +527,11 @@ def _build_qwen_arena(cfg, ck: dict, precision: int, classify_num: int) -> np.nd
     co[:, :, :C] = f32(ck[a + "conv_out.weight"]).reshape(de, C, n_f).transpose(0, 2, 1)
     w.weight("enc.conv_out_w", co.reshape(de, n_f * cpad), precision)
     half = de // 2
-    inv = np.exp(-(np.log(10000.0) / (half - 1)) * np.arange(half, dtype=np.float32)).astype(np.float32)
-    st = np.arange(13, dtype=np.float32)[:, None] * inv[None, :]               # SinusoidsPositionEmbedding rows 0..12 (:869-872)
-    w.add("enc.pos", np.concatenate([np.sin(st), np.cos(st)], 1).astype(np.float32), DT_F32)
+    # SinusoidsPositionEmbedding rows 0..12 (:869-872), with torch's f32 exp / sin / cos as the reference computes them: numpy's f32 exp differs in the
+    # last bit of 47 of the 64 inverse timescales, which the position index multiplies to 4.6e-7 on the rows
+    inv = torch.exp(-float(np.log(10000.0) / (half - 1)) * torch.arange(half).float())
+    st = torch.arange(13)[:, None] * inv[None, :]
+    w.add("enc.pos", torch.cat([torch.sin(st), torch.cos(st)], 1).numpy().astype(np.float32), DT_F32)
 
     s = np.float64((de // cfg.enc_heads) ** -0.25)
     for i in range(cfg.n_enc_layers):

@@ -281,6 +281,7 @@ FbankArgs FrontEnd::args(const void* audio, int audio_dtype, const UttPlan* plan
   fa.audio = audio; fa.audio_dtype = audio_dtype; fa.plan = plan; fa.blk_utt = blk_utt; fa.blk_f0 = blk_f0; fa.dft_packed = dft; fa.mel_packed = melp;
   fa.mel_out = mel_out; fa.n_bin_tiles = n_bin_tiles; fa.n_kchunks = n_kchunks; fa.n_mel_tiles = n_mels / 16; fa.n_mels = n_mels;
   fa.win = win; fa.hop = hop; fa.log_floor = log_floor; fa.whisper = whisper; fa.blk_max = blk_max; fa.dft_split = dft_split;
+  fa.log_at_floor = (float)(whisper ? std::log10((double)log_floor) : std::log((double)log_floor));
   return fa;
 }
 

@@ -42,6 +42,9 @@ struct FbankArgs {
   float* blk_max;
   // bf16 sessions: the DFT on the bf16 matrix pipe with split operands (launch_fbank_split_table): null = exact-f32 MFMA
   const void* dft_split = nullptr;
+  // log10 / ln of log_floor, rounded once from double on the host: a bin at the floor (digital silence) gets exactly the value the reference's CPU
+  // graph gives (-10 for Whisper), not the device logarithm's last-bit approximation of it
+  float log_at_floor = 0.0f;
   // sample type of `audio`: the kernels are instantiated per type and launch_fbank dispatches (kept last: the kernels never read it, and the
   // offsets of the fields they do read stay what they were)
   int audio_dtype = AUDIO_F32;

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(const FbankArgs a) {
       const int f = f0 + wave * 16 + fgrp * 4 + r;
       if (f < up.n_frames) {
         const float c = fmaxf(acc[r], a.log_floor);
-        const float v = a.whisper ? log10f(c) : logf(c);
+        const float v = c <= a.log_floor ? a.log_at_floor : a.whisper ? log10f(c) : logf(c);   // digital silence: the floor's exact logarithm
         a.mel_out[(size_t)(up.frame_off + f) * a.n_mels + nt * 16 + frow] = v;
         wmax = fmaxf(wmax, v);
       }
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(64 * FB_WAVES) void fbank_split_kernel(const FbankA
         const int f = f0 + fw * 16 + fgrp * 4 + r;
         if (f < up.n_frames) {
           const float c = fmaxf(acc[q][r], a.log_floor);
-          const float v = a.whisper ? log10f(c) : logf(c);
+          const float v = c <= a.log_floor ? a.log_at_floor : a.whisper ? log10f(c) : logf(c);
           a.mel_out[(size_t)(up.frame_off + f) * a.n_mels + (nt0 + 2 * q) * 16 + frow] = v;
           wmax = fmaxf(wmax, v);
         }

@@ -1161,6 +1161,7 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
     if (taps_enabled) save_tap("mel", d_mel.ptr, frames, c.n_mels, c.n_mels, 4);       // log10 mel before the per-utterance clamp: what the front end made of the samples
     hipLaunchKernelGGL(qw_mel_finish_kernel<T>, dim3(slots * chunk), dim3(128), 0, stream, d_mel.as<float>(), d_blkmax.as<float>(), dup, d_slot_utt,
                        d_slot_local, c.n_mels, chunk, d_feat.as<T>());
+    if (taps_enabled) save_tap("feat", d_feat.ptr, (int64_t)slots * chunk, c.n_mels, c.n_mels, (int)eT);   // what the conv stem reads: [slot][frame][mel]
   }
   {
     ProfScope ps(prof, "conv_stem", stream);

@@ -60,6 +60,7 @@ struct WhSession : asr_session {
               *enc_ln_b = nullptr, *ckv_b = nullptr, *dec_pos = nullptr, *suppress = nullptr, *begin = nullptr, *dec_ln_g = nullptr,
               *dec_ln_b = nullptr;
   const void *conv1_w = nullptr, *conv2_w = nullptr, *ckv_w = nullptr, *embed = nullptr;
+  int k_conv1 = 0;
 
   // encoder state of the current batch
   int batch = 0, rows = 0, Mpad = 0, hist = 0, max_T_enc = 0;
@@ -149,7 +150,7 @@ void WhSession::init() {
   ASR_REQUIRE(c.d_model == c.n_heads * c.d_head && c.d_head == 64, "whisper: head_dim must be 64 and d_model = heads * 64");
   ASR_REQUIRE(c.d_model % 128 == 0 && c.d_ffn % 128 == 0, "whisper: d_model and d_ffn must be multiples of 128");
   ASR_REQUIRE(c.nfft == 400 && c.hop_length == 160, "whisper: front-end is built for n_fft 400 / hop 160");
-  ASR_REQUIRE(c.n_mels % 16 == 0 && (3 * c.n_mels) % 64 == 0, "whisper: n_mels must make 3*n_mels a multiple of 64");
+  ASR_REQUIRE(c.n_mels % 16 == 0, "whisper: n_mels must be a multiple of 16");
   ASR_REQUIRE(c.max_target_positions <= 1536, "whisper: decoder context too long for the attention kernel");
   vpad = round_up(c.vocab, 128);
   head.init(c.max_target_positions, 0, 20, 512);
@@ -162,7 +163,8 @@ void WhSession::init() {
   auto W = [&](const std::string& n, std::initializer_list<int64_t> sh) { return arena.get(n, wt, sh).ptr; };
   fe.dft = F("fe.dft", {(int64_t)fe.n_bin_tiles * 2 * fe.n_kchunks * 64 * 4});
   fe.melp = F("fe.mel", {(int64_t)(c.n_mels / 16) * fe.n_bin_tiles * 64 * 4});
-  conv1_w = W("enc.conv1_w", {d, 3 * c.n_mels});
+  k_conv1 = round_up(3 * c.n_mels, 64);                 // whole GEMM K steps: the arena pads the three taps with zero columns (80 mels: 240 -> 256)
+  conv1_w = W("enc.conv1_w", {d, k_conv1});
   conv1_b = F("enc.conv1_b", {d});
   conv2_w = W("enc.conv2_w", {d, 3 * d});
   conv2_b = F("enc.conv2_b", {d});
@@ -310,6 +312,8 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, in
     // per-utterance max clamp + (x+4)/4, written behind one leading zero row (the conv view of row j starts at j-1)
     T* x0 = d_x0.as<T>();
     HIP_CHECK(hipMemsetAsync(x0, 0, (size_t)c.n_mels * eT, stream));
+    // a padded K reads up to 63 elements behind a view's three rows; behind the last written row (R) they meet zero weights but must be finite
+    if (k_conv1 > 3 * c.n_mels) HIP_CHECK(hipMemsetAsync(x0 + (size_t)(R + 1) * c.n_mels, 0, (size_t)4 * c.n_mels * eT, stream));
     launch_whisper_mel_finish<T>(d_mel.as<float>(), d_blkmax.as<float>(), dps, d_grow_utt, R, c.n_mels, x0 + c.n_mels, stream);
   }
   if (taps_enabled) save_tap("mel_gapped", d_x0.as<T>() + c.n_mels, R, c.n_mels, c.n_mels, (int)eT);
@@ -317,7 +321,7 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, in
   {
     ProfScope ps(prof, "conv_stem", stream);
     GemmArgs g1;
-    g1.A = d_x0.ptr; g1.lda = c.n_mels; g1.W = conv1_w; g1.ldw = 3 * c.n_mels; g1.M = R; g1.N = d; g1.K = 3 * c.n_mels;
+    g1.A = d_x0.ptr; g1.lda = c.n_mels; g1.W = conv1_w; g1.ldw = k_conv1; g1.M = R; g1.N = d; g1.K = k_conv1;
     g1.bias = conv1_b; g1.act = act; g1.out_lo = d_h1.ptr; g1.ld_out_lo = d;
     gemm(g1);
     launch_zero_gap_rows<T>(d_h1.as<T>(), d, d, dps, d_grow_utt, R, stream);     // conv2's zero padding
