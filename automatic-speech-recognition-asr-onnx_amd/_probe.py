@@ -96,6 +96,7 @@ SIGNATURES = {
     "asr_probe_gemm": (C.c_int, [C.POINTER(GemmDesc)]),
     "asr_probe_ctc_head": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, _ip, _fp, _ip, C.c_char_p]),
     "asr_probe_ctc_topk": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _fp, C.c_char_p]),
+    "asr_probe_ctc_target_logprob": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, _ip, C.c_int, C.c_int, _fp, _ip, C.c_char_p]),
     "asr_probe_gemm_chain": (C.c_int, [C.c_int] * 6 + [_fp]),
     "asr_probe_last_kernel": (C.c_char_p, []),
     "asr_probe_quantize_fp8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, _fp, C.c_void_p]),
@@ -193,6 +194,28 @@ def ctc_topk(a, w, bias, topk, n_valid=0, variant=-1, precision=0):
     _lib.check(load().asr_probe_ctc_topk(M, N, K, a.ctypes.data_as(_fp), w.ctypes.data_as(_fp), bias.ctypes.data_as(_fp), n_valid, variant, precision, topk,
                                          ids.ctypes.data_as(_ip), lp.ctypes.data_as(_fp), name))
     return ids, lp, name.value.decode()
+
+
+def ctc_target_logprob(a, w, bias, row_utt, targets, blank_id=0, n_valid=0, variant=-1, precision=0, ld_em=None):
+    """The emission kernel of the CTC forced alignment behind the head of ctc_head (asr_probe_ctc_target_logprob); `targets` is one id list per transcript,
+    row_utt[m] the transcript of row m (-1: none). Returns (em[M, ld_em], words written past row M, kernel family name of the head GEMM)."""
+    a, w, bias = _f32(a), _f32(w), _f32(bias)
+    M, K = a.shape
+    N = w.shape[0]
+    row_utt = np.ascontiguousarray(row_utt, dtype=np.int32)
+    assert row_utt.shape == (M,)
+    targets = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
+    offs = np.zeros(len(targets) + 1, dtype=np.int32)
+    offs[1:] = np.cumsum([t.size for t in targets])
+    ids = np.ascontiguousarray(np.concatenate(targets + [np.zeros(1, np.int32)]), dtype=np.int32)
+    if ld_em is None:
+        ld_em = (max(t.size for t in targets) + 1 + 3) // 4 * 4
+    em = np.zeros((M, ld_em), dtype=np.float32)
+    stray, name = C.c_int32(-1), C.create_string_buffer(32)
+    _lib.check(load().asr_probe_ctc_target_logprob(M, N, K, a.ctypes.data_as(_fp), w.ctypes.data_as(_fp), bias.ctypes.data_as(_fp), n_valid, variant, precision,
+                                                   row_utt.ctypes.data_as(_ip), len(targets), ids.ctypes.data_as(_ip), offs.ctypes.data_as(_ip), blank_id, ld_em,
+                                                   em.ctypes.data_as(_fp), C.byref(stray), name))
+    return em, stray.value, name.value.decode()
 
 
 def gemm_bench(M, N, K, variant=-1, epilogue=0, iters=50) -> float:

@@ -511,6 +511,57 @@ extern "C" int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_
   });
 }
 
+extern "C" int asr_op_ctc_align(const float* em, int ld_em, const int32_t* seq_lens, int batch, int row0, const int32_t* target_ids, const int32_t* target_offsets,
+                                int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, float* path_score, float* loglik, int32_t* status) {
+  return asr_guard([&] {
+    ASR_REQUIRE(em && seq_lens && target_ids && target_offsets && first_frame && last_frame && token_logprob && path_score && loglik && status && batch > 0 && max_tokens > 0,
+                "op_ctc_align: bad argument");
+    ASR_REQUIRE(target_offsets[0] == 0 && row0 >= 0, "op_ctc_align: target_offsets[0] = %d, row0 = %d", target_offsets[0], row0);
+    int max_L = 0, max_T = 1;
+    for (int b = 0; b < batch; ++b) {
+      const int L = target_offsets[b + 1] - target_offsets[b];
+      ASR_REQUIRE(L >= 0, "op_ctc_align: target_offsets decrease at sequence %d", b);
+      ASR_REQUIRE(seq_lens[b] > row0, "op_ctc_align: sequence %d has %d rows, row0 = %d", b, seq_lens[b], row0);
+      max_L = std::max(max_L, L); max_T = std::max(max_T, seq_lens[b]);
+    }
+    ASR_REQUIRE(ld_em >= max_L + 1 && max_tokens >= max_L, "op_ctc_align: ld_em = %d, max_tokens = %d for a transcript of %d tokens", ld_em, max_tokens, max_L);
+    asr_require_device(0);
+    Tmp t;
+    PackedPlan pp(seq_lens, batch);
+    std::vector<float> ea;
+    to_aligned(pp, seq_lens, batch, ld_em, em, ea);
+    const size_t out_bytes = (size_t)batch * max_tokens * 4, n_tgt = (size_t)target_offsets[batch];
+    float* dem = (float*)t.alloc(ea.size() * 4);
+    UttPlan* dplan = (UttPlan*)t.alloc(sizeof(UttPlan) * batch);
+    int32_t* dtgt = (int32_t*)t.alloc(n_tgt * 4);
+    int32_t* doff = (int32_t*)t.alloc((size_t)(batch + 1) * 4);
+    int32_t* dfirst = (int32_t*)t.alloc(out_bytes);
+    int32_t* dlast = (int32_t*)t.alloc(out_bytes);
+    float* dtlp = (float*)t.alloc(out_bytes);
+    float* dpath = (float*)t.alloc((size_t)batch * 4);
+    float* dlik = (float*)t.alloc((size_t)batch * 4);
+    int32_t* dstat = (int32_t*)t.alloc((size_t)batch * 4);
+    const size_t ws = ctc_align_ws_bytes(batch, max_T, row0, max_L);
+    uint32_t* dbp = ws ? (uint32_t*)t.alloc(ws) : nullptr;
+    HIP_CHECK(hipMemcpy(dem, ea.data(), ea.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dplan, pp.plan.data(), sizeof(UttPlan) * batch, hipMemcpyHostToDevice));
+    if (n_tgt) HIP_CHECK(hipMemcpy(dtgt, target_ids, n_tgt * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(doff, target_offsets, (size_t)(batch + 1) * 4, hipMemcpyHostToDevice));
+    // the caller's arrays go up first, so that slots the kernel leaves alone come back as they were
+    HIP_CHECK(hipMemcpy(dfirst, first_frame, out_bytes, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dlast, last_frame, out_bytes, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dtlp, token_logprob, out_bytes, hipMemcpyHostToDevice));
+    launch_ctc_align(dem, ld_em, dplan, batch, row0, max_T, dtgt, doff, max_L, dbp, dfirst, dlast, dtlp, max_tokens, dpath, dlik, dstat, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(first_frame, dfirst, out_bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(last_frame, dlast, out_bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(token_logprob, dtlp, out_bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(path_score, dpath, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(loglik, dlik, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(status, dstat, (size_t)batch * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 extern "C" int asr_op_cif_scan_timed(const float* alpha, const float* enc, int d, const int32_t* seq_lens, int batch, float tail_threshold,
                                      float* acoustic_out, int32_t* fire_frame_out, int max_tokens, int32_t* num_id_out) {
   return asr_guard([&] {

@@ -3,6 +3,7 @@
 // ctc_prefix_beam_kernel runs the search, one workgroup per utterance. The float64 statement of the search is tests/ctc_beam_ref.py.
 #include <map>
 
+#include "ctc_dev.h"
 #include "engine.h"
 #include "hot_trie.h"
 #include "kernels.h"
@@ -23,27 +24,6 @@ __device__ __forceinline__ void wave_best(float& v, int& i) {        // (higher 
     if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
   }
 }
-
-__device__ __forceinline__ float dot8(const float* hs, const bf16_t* w) {
-  const uint4 q = *reinterpret_cast<const uint4*>(w);
-  const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-  float a = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    a = fmaf(hs[2 * i], __uint_as_float(u[i] << 16), a);
-    a = fmaf(hs[2 * i + 1], __uint_as_float(u[i] & 0xffff0000u), a);
-  }
-  return a;
-}
-__device__ __forceinline__ float dot8(const float* hs, const float* w) {
-  const float4 p = *reinterpret_cast<const float4*>(w), q = *reinterpret_cast<const float4*>(w + 4);
-  float a = 0.0f;
-  a = fmaf(hs[0], p.x, a); a = fmaf(hs[1], p.y, a); a = fmaf(hs[2], p.z, a); a = fmaf(hs[3], p.w, a);
-  a = fmaf(hs[4], q.x, a); a = fmaf(hs[5], q.y, a); a = fmaf(hs[6], q.z, a); a = fmaf(hs[7], q.w, a);
-  return a;
-}
-__device__ __forceinline__ float elem_f32(float v) { return v; }
-__device__ __forceinline__ float elem_f32(bf16_t v) { return bf16_to_f32(v); }
 
 template <typename T>
 __global__ __launch_bounds__(64 * TOPK_ROWS) void ctc_topk_kernel(const T* __restrict__ h, int ldh, const T* __restrict__ W, int ldw, const float* __restrict__ bias,
@@ -75,23 +55,14 @@ __global__ __launch_bounds__(64 * TOPK_ROWS) void ctc_topk_kernel(const T* __res
     pv = bv; ps = bs;
     if (bs < 0) { for (int q = j + 1; q < topk; ++q) if (lane == 0) sel[wv][q] = -1; break; }
   }
-  float tot = 0.0f;                                   // the row's sum of exponentials, as argmax_lse_reduce_kernel forms it
-  for (int s = lane; s < n_slabs; s += 64) tot += rs[s] * expf(rv[s] - best_row);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
-  const float lse = best_row + logf(tot);
+  const float lse = ctc_row_lse(rv, rs, n_slabs, best_row, lane);      // the row's log-sum-exp, as argmax_lse_reduce_kernel forms it
   __syncthreads();
   for (int j = 0; j < topk; ++j) {
     const int s = sel[wv][j];
     const int col = s * 64 + lane;
     float v = -INFINITY;
     if (s >= 0 && col < n_valid) {
-      const T* wr = W + (size_t)col * ldw;
-      float a0 = 0.0f, a1 = 0.0f;
-      int k = 0;
-      for (; k + 16 <= K; k += 16) { a0 += dot8(hs + k, wr + k); a1 += dot8(hs + k + 8, wr + k + 8); }
-      for (; k < K; k += 8) a0 += dot8(hs + k, wr + k);
-      v = a0 + a1 + bias[col];
+      v = ctc_logit(hs, W + (size_t)col * ldw, K, bias[col]);
     }
     vals[j * 64 + lane] = v;
   }
@@ -120,12 +91,6 @@ __global__ __launch_bounds__(64 * TOPK_ROWS) void ctc_topk_kernel(const T* __res
 // ---- search --------------------------------------------------------------------------------------------------------------------------------------
 constexpr int CTC_BEAM_MAX = 16;
 constexpr int CTC_BEAM_THREADS = CTC_BEAM_MAX + CTC_BEAM_MAX * CTC_BEAM_MAX + 48;     // one thread per entry of a frame (16 stays + 256 extensions), rounded up to whole waves
-
-__device__ __forceinline__ float lae(float a, float b) {
-  if (a == -INFINITY) return b;
-  if (b == -INFINITY) return a;
-  return fmaxf(a, b) + log1pf(expf(-fabsf(a - b)));
-}
 
 // identity of a prefix is its content: a 64-bit rolling hash (splitmix64 finaliser over hash * golden + token + 1) beside its length and last token
 __device__ __forceinline__ uint64_t hash_step(uint64_t h, int c) {

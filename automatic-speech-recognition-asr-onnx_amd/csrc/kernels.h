@@ -441,6 +441,23 @@ void launch_ctc_prefix_beam(const int32_t* cand_id, const float* cand_lp, int to
                             const HotTrie& trie, int2* pool, int pool_stride, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score,
                             hipStream_t s);
 
+// ---- CTC forced alignment of a given transcript (ctc_align.hip)
+// Emissions: for every row m < M with u = row_utt[m] >= 0, em[m][j] = log soft-max of h W^T + bias at slot j's column -- slot 0 the blank, slot j = 1 .. L_u
+// target_ids[target_offsets[u] + j - 1] -- and -inf for L_u < j < ld_em. The logit is recomputed as launch_ctc_topk recomputes it and the row's log-sum-exp comes
+// from the same per-slab partials, so a target that is also a candidate has that candidate's bits. Rows with row_utt < 0 are left alone.
+template <typename T>
+void launch_ctc_target_logprob(const T* h, int ldh, const T* W, int ldw, const float* bias, int K, const float* amax_val, const float* amax_sum, int n_slabs, int M,
+                               const int32_t* row_utt, const int32_t* target_ids, const int32_t* target_offsets, int blank_id, float* em, int ld_em, hipStream_t s);
+// Viterbi + forward trellis and the walk back, one workgroup per utterance over rows plan[u].row_off + row0 .. plan[u].row_off + plan[u].T - 1 of em
+// [rows][ld_em] (slots as above). max_rows >= every plan[u].T, max_L >= every L_u (at most 1023). Per target j of utterance u, at [u][max_tokens]:
+// first_frame / last_frame (rows of the utterance's sequence, row0 included) and token_logprob (mean emission over the span); per utterance path_score, loglik
+// and status (0 aligned; 1 no alignment exists: the spans keep what they held and both scores are -inf). bp_ws: ctc_align_ws_bytes(...) bytes of workspace
+// for the backpointers, may be null when that is 0 (they then live in LDS).
+size_t ctc_align_ws_bytes(int n_utts, int max_rows, int row0, int max_L);
+void launch_ctc_align(const float* em, int ld_em, const UttPlan* plan, int n_utts, int row0, int max_rows, const int32_t* target_ids, const int32_t* target_offsets,
+                      int max_L, uint32_t* bp_ws, int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, float* path_score, float* loglik,
+                      int32_t* status, hipStream_t s);
+
 // ---- Paraformer CIF predictor + decoder helpers (Paraformer/Non-Streaming/Export_Paraformer.py:499-563)
 // [x[t-1] | x[t] | x[t+1]] rows with zero padding at utterance edges: the k=3 conv as one GEMM (K = 3 d)
 template <typename T>

@@ -560,6 +560,82 @@ extern "C" int asr_probe_ctc_topk(int M, int N, int K, const float* a, const flo
   });
 }
 
+// The emission kernel of the forced alignment behind the same head (launch_ctc_target_logprob): operands, `variant` and `precision` as asr_probe_ctc_topk.
+// row_utt [M] maps every row to one of n_utts transcripts (or -1: the row is left alone), target_ids / target_offsets are ragged over the transcripts.
+// out_em [M][ld_em]. The device buffer is padded to the tile edge and NaN-filled first; *stray counts the words of rows >= M that no longer hold the pattern.
+extern "C" int asr_probe_ctc_target_logprob(int M, int N, int K, const float* a, const float* w, const float* bias, int n_valid, int variant, int precision,
+                                            const int32_t* row_utt, int n_utts, const int32_t* target_ids, const int32_t* target_offsets, int blank_id, int ld_em,
+                                            float* out_em, int32_t* stray, char* kernel32) {
+  return asr_guard([&] {
+    ASR_REQUIRE(a && w && bias && out_em && row_utt && target_ids && target_offsets && M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 64 == 0 && n_valid >= 0 && n_valid <= N && n_utts > 0,
+                "probe_ctc_target_logprob: bad argument");
+    ASR_REQUIRE(precision == ASR_PRECISION_BF16 || precision == ASR_PRECISION_F32, "probe_ctc_target_logprob: precision %d (bf16 or f32)", precision);
+    const int nv = n_valid > 0 ? n_valid : N;
+    ASR_REQUIRE(target_offsets[0] == 0 && blank_id >= 0 && blank_id < nv, "probe_ctc_target_logprob: target_offsets[0] = %d, blank %d", target_offsets[0], blank_id);
+    for (int u = 0; u < n_utts; ++u) {
+      ASR_REQUIRE(target_offsets[u + 1] >= target_offsets[u] && target_offsets[u + 1] - target_offsets[u] < ld_em, "probe_ctc_target_logprob: transcript %d does not fit ld_em = %d", u, ld_em);
+      for (int32_t i = target_offsets[u]; i < target_offsets[u + 1]; ++i) ASR_REQUIRE(target_ids[i] >= 0 && target_ids[i] < nv, "probe_ctc_target_logprob: target %d outside the valid columns", target_ids[i]);
+    }
+    for (int m = 0; m < M; ++m) ASR_REQUIRE(row_utt[m] >= -1 && row_utt[m] < n_utts, "probe_ctc_target_logprob: row_utt[%d] = %d", m, row_utt[m]);
+    asr_require_device(0);
+    gemm_reload_env();
+    Tmp t;
+    const bool lo = precision == ASR_PRECISION_BF16;
+    const int Mp = round_up(M, 128) + 128, n_slabs = N / 64;
+    void *da = nullptr, *dw = nullptr;
+    if (lo) {
+      std::vector<bf16_t> ha((size_t)Mp * K, 0), hw((size_t)N * K);
+      for (size_t i = 0; i < (size_t)M * K; ++i) ha[i] = f32_to_bf16(a[i]);
+      for (size_t i = 0; i < (size_t)N * K; ++i) hw[i] = f32_to_bf16(w[i]);
+      da = t.alloc(ha.size() * 2); dw = t.alloc(hw.size() * 2);
+      HIP_CHECK(hipMemcpy(da, ha.data(), ha.size() * 2, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+    } else {
+      da = t.alloc((size_t)Mp * K * 4); dw = t.alloc((size_t)N * K * 4);
+      HIP_CHECK(hipMemcpy(da, a, (size_t)M * K * 4, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dw, w, (size_t)N * K * 4, hipMemcpyHostToDevice));
+    }
+    float* db = (float*)t.alloc((size_t)N * 4);
+    HIP_CHECK(hipMemcpy(db, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+    const size_t part = (size_t)Mp * n_slabs, n_tgt = (size_t)target_offsets[n_utts];
+    float* dav = (float*)t.alloc(part * 4); int32_t* dai = (int32_t*)t.alloc(part * 4); float* das = (float*)t.alloc(part * 4);
+    std::vector<int32_t> hru(Mp, -1);
+    memcpy(hru.data(), row_utt, (size_t)M * 4);
+    int32_t* dru = (int32_t*)t.alloc((size_t)Mp * 4);
+    int32_t* dtgt = (int32_t*)t.alloc(n_tgt * 4);
+    int32_t* doff = (int32_t*)t.alloc((size_t)(n_utts + 1) * 4);
+    uint32_t* dem = (uint32_t*)t.alloc((size_t)Mp * ld_em * 4);
+    HIP_CHECK(hipMemcpy(dru, hru.data(), (size_t)Mp * 4, hipMemcpyHostToDevice));
+    if (n_tgt) HIP_CHECK(hipMemcpy(dtgt, target_ids, n_tgt * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(doff, target_offsets, (size_t)(n_utts + 1) * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(dem, 0xff, (size_t)Mp * ld_em * 4));
+    GemmArgs g;
+    g.A = da; g.lda = K; g.W = dw; g.ldw = K; g.M = M; g.N = N; g.K = K; g.bias = db;
+    g.amax_val = dav; g.amax_idx = dai; g.amax_sum = das; g.n_valid = nv;
+    if (lo) {
+      g.sk_ws = (float*)t.alloc((size_t)16 << 20); g.sk_ws_bytes = (size_t)16 << 20; g.sk_cnt = (int32_t*)t.alloc(4096 * 4);
+      gemm_set_variant(variant);
+      try { launch_gemm_bf16(g, nullptr); } catch (...) { gemm_set_variant(-1); throw; }
+      gemm_set_variant(-1);
+      if (kernel32) snprintf(kernel32, 32, "%s", gemm_last_kernel());
+      launch_ctc_target_logprob<bf16_t>((const bf16_t*)da, K, (const bf16_t*)dw, K, db, K, dav, das, n_slabs, M, dru, dtgt, doff, blank_id, (float*)dem, ld_em, nullptr);
+    } else {
+      launch_gemm_f32(g, nullptr);
+      if (kernel32) snprintf(kernel32, 32, "f32");
+      launch_ctc_target_logprob<float>((const float*)da, K, (const float*)dw, K, db, K, dav, das, n_slabs, M, dru, dtgt, doff, blank_id, (float*)dem, ld_em, nullptr);
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out_em, dem, (size_t)M * ld_em * 4, hipMemcpyDeviceToHost));
+    if (stray) {
+      std::vector<uint32_t> h((size_t)(Mp - M) * ld_em);
+      HIP_CHECK(hipMemcpy(h.data(), dem + (size_t)M * ld_em, h.size() * 4, hipMemcpyDeviceToHost));
+      int bad = 0;
+      for (uint32_t v : h) bad += v != 0xffffffffu;
+      *stray = bad;
+    }
+  });
+}
+
 // ---- decoder attention (launch_decode_attention) on host arrays: self-attention over a contiguous or paged cache, cross-attention over
 // packed slabs (optionally FP8 through the product's quantiser). Reports which form the dispatcher chose (asr_mi355x_probe.h).
 namespace {

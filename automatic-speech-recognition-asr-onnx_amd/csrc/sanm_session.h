@@ -24,9 +24,10 @@ struct PfDecLayer {
   bool full;     // false: FFN-only block (decoders3)
 };
 
-// What a call asks for. PLAIN: ids and counts; TIMED: also per-token times and log-probabilities; BEAM (SenseVoice): n-best hypotheses with scores.
-enum class SvForm { PLAIN, TIMED, BEAM };
-struct SvRunReq {               // offline: asr_sensevoice_run / _run_timed / _run_beam, asr_paraformer_run / _run_timed
+// What a call asks for. PLAIN: ids and counts; TIMED: also per-token times and log-probabilities; BEAM (SenseVoice): n-best hypotheses with scores;
+// ALIGN (SenseVoice): the spans and scores of a transcript the caller supplies.
+enum class SvForm { PLAIN, TIMED, BEAM, ALIGN };
+struct SvRunReq {               // offline: asr_sensevoice_run / _run_timed / _run_beam / _align, asr_paraformer_run / _run_timed
   SvForm form = SvForm::PLAIN;
   const void* audio = nullptr; int audio_mem = 0; const int64_t* offs = nullptr; int batch = 0;
   const int32_t* lang = nullptr;                        // SenseVoice only
@@ -36,6 +37,9 @@ struct SvRunReq {               // offline: asr_sensevoice_run / _run_timed / _r
   float* logprob_out = nullptr;                         // TIMED
   int beam = 0, topk = 0, nbest = 0;                    // BEAM
   float *score_out = nullptr, *ctc_out = nullptr;       // BEAM
+  // ALIGN: the transcripts (ragged: ids [sum L], offsets [batch + 1]); first_out / last_out / logprob_out are ragged in the same layout, no tok_out / num_out
+  const int32_t *tgt_ids = nullptr, *tgt_off = nullptr;
+  float *path_out = nullptr, *loglik_out = nullptr; int32_t* astatus_out = nullptr;      // [batch]
 };
 struct SvStepReq {              // streaming: asr_paraformer_stream_step / _step_timed
   SvForm form = SvForm::PLAIN;
@@ -55,6 +59,9 @@ struct SvRunCtx {
   bool tiles = false;
   bool timed = false;         // CTC head with frame log-probabilities, collapse with spans
   int beam = 0, topk = 0, nbest = 0, pool_stride = 0;     // beam > 0: CTC head with the sum-of-exponentials partial, candidates, prefix beam search
+  bool align = false;         // CTC head with the sum-of-exponentials partial, gathered emissions, forced alignment (max_tokens = the longest transcript)
+  int max_L = 0, ld_em = 0;
+  const int32_t *d_tgt_ids = nullptr, *d_tgt_off = nullptr;
   const ResultBlob* out = nullptr;                        // where the step's D2H copies land
 };
 
@@ -144,6 +151,10 @@ struct ASR_LOCAL SvSession : asr_session {
   uint64_t beam_epoch = 1;      // bumped when a beam-only buffer moves or the hotword list changes: part of the beam graph's key, not of the others'
   StepGraph graph_beam;         // hipGraph replay of the beam form
   void set_hotwords(const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+  // align runs only (asr_sensevoice_align, ctc_align.hip): emissions [rows][ld_em], the backpointer workspace of transcripts too long for LDS, per-utterance
+  // scores and status; the spans land in d_first / d_last / d_tlp
+  DeviceBuffer d_em, d_abp, d_apath, d_alik, d_astat;
+  StepGraph graph_align;        // hipGraph replay of the align form
 
   // ---- offline Paraformer: CIF predictor + decoder ------------------------------------------------------------------------------------
   bool paraformer = false;

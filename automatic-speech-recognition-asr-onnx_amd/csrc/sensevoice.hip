@@ -399,7 +399,7 @@ void SvSession::enqueue(const SvRunCtx& r) {
     GemmArgs g;
     g.A = h; g.lda = d; g.W = ctc_w; g.ldw = d; g.M = rows; g.N = vpad; g.K = d; g.bias = ctc_b;
     g.amax_val = d_amax_v.as<float>(); g.amax_idx = d_amax_i.as<int32_t>(); g.n_valid = c.vocab;
-    if (r.timed || r.beam) g.amax_sum = d_amax_s.as<float>();
+    if (r.timed || r.beam || r.align) g.amax_sum = d_amax_s.as<float>();
     if (taps_enabled) { g.out_f32 = d_logits.as<float>(); g.ld_out_f32 = vpad; }
     gemm(g);
   }
@@ -423,6 +423,27 @@ void SvSession::enqueue(const SvRunCtx& r) {
     }
     copy_block_status(r);                                 // the plain outputs' sections stay unused; the beam block comes home in one copy
     o.enqueue_copy(o.lay.beam, d_bout.ptr, stream);
+    return;
+  }
+  if (r.align) {                                          // ---- 5c. forced alignment of the caller's transcripts
+    const ResultBlob& o = *r.out;
+    {
+      ProfScope ps(prof, "ctc_align_em", stream);
+      launch_ctc_target_logprob<T>(h, d, (const T*)ctc_w, d, ctc_b, d, d_amax_v.as<float>(), d_amax_s.as<float>(), n_slabs, rows, r.d_row_utt, r.d_tgt_ids, r.d_tgt_off,
+                                   c.blank_id, d_em.as<float>(), r.ld_em, stream);
+    }
+    {
+      ProfScope ps(prof, "ctc_align", stream);
+      launch_ctc_align(d_em.as<float>(), r.ld_em, r.dp, r.batch, c.n_prompt, r.max_T, r.d_tgt_ids, r.d_tgt_off, r.max_L, d_abp.as<uint32_t>(), d_first.as<int32_t>(),
+                       d_last.as<int32_t>(), d_tlp.as<float>(), r.max_tokens, d_apath.as<float>(), d_alik.as<float>(), d_astat.as<int32_t>(), stream);
+    }
+    if (taps_enabled) {
+      save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
+      save_tap("align_logprob", d_em.ptr, rows, r.ld_em, r.ld_em, 4);
+    }
+    copy_block_status(r);                                 // the token sections stay unused
+    o.enqueue_copy(o.lay.first, d_first.ptr, stream); o.enqueue_copy(o.lay.last, d_last.ptr, stream); o.enqueue_copy(o.lay.logprob, d_tlp.ptr, stream);
+    o.enqueue_copy(o.lay.path_score, d_apath.ptr, stream); o.enqueue_copy(o.lay.loglik, d_alik.ptr, stream); o.enqueue_copy(o.lay.align_status, d_astat.ptr, stream);
     return;
   }
   {
@@ -608,20 +629,38 @@ void SvSession::validate(const SvRunReq& q) const {
     ASR_REQUIRE(q.tok_out && q.num_out && q.score_out && q.ctc_out, "sensevoice_run_beam: null output");
     ASR_REQUIRE(cfg.d_model <= 2048, "sensevoice_run_beam: d_model %d (the candidate kernel holds a row of 2048 at most)", cfg.d_model);
   }
+  if (q.form == SvForm::ALIGN) {
+    ASR_REQUIRE(!paraformer, "sensevoice_align: not a SenseVoice session");
+    ASR_REQUIRE(q.batch > 0 && q.tgt_ids && q.tgt_off && q.first_out && q.last_out && q.logprob_out && q.path_out && q.loglik_out && q.astatus_out, "sensevoice_align: null argument");
+    ASR_REQUIRE(cfg.d_model <= 2048, "sensevoice_align: d_model %d (the emission kernel holds a row of 2048 at most)", cfg.d_model);
+    ASR_REQUIRE(q.tgt_off[0] == 0, "sensevoice_align: target_offsets[0] = %d", q.tgt_off[0]);
+    for (int b = 0; b < q.batch; ++b) {
+      ASR_REQUIRE(q.tgt_off[b + 1] >= q.tgt_off[b], "sensevoice_align: target_offsets decrease at utterance %d", b);
+      ASR_REQUIRE(q.tgt_off[b + 1] - q.tgt_off[b] <= 1023, "sensevoice_align: utterance %d has %d targets (at most 1023)", b, q.tgt_off[b + 1] - q.tgt_off[b]);
+      for (int32_t i = q.tgt_off[b]; i < q.tgt_off[b + 1]; ++i) {
+        ASR_REQUIRE(q.tgt_ids[i] >= 0 && q.tgt_ids[i] < cfg.vocab, "sensevoice_align: utterance %d holds token %d (vocabulary %d)", b, q.tgt_ids[i], cfg.vocab);
+        ASR_REQUIRE(q.tgt_ids[i] != cfg.blank_id, "sensevoice_align: utterance %d holds the blank id", b);
+      }
+    }
+  }
   ASR_REQUIRE(q.form != SvForm::TIMED || (q.first_out && q.logprob_out && (paraformer ? !q.last_out : q.last_out != nullptr)),
               "sensevoice: the timed form needs all of its outputs");
   ASR_REQUIRE(q.batch > 0, "sensevoice: empty batch");
-  ASR_REQUIRE(q.audio && q.offs && (q.lang || paraformer) && q.tok_out && q.num_out, "sensevoice: null argument");
+  ASR_REQUIRE(q.audio && q.offs && (q.lang || paraformer) && (q.form == SvForm::ALIGN || (q.tok_out && q.num_out)), "sensevoice: null argument");
 }
 
 template <typename T>
 void SvSession::run(const SvRunReq& q) {
   const auto& c = cfg;
   validate(q);
-  const bool timed = q.form == SvForm::TIMED, bq = q.form == SvForm::BEAM;
+  const bool timed = q.form == SvForm::TIMED, bq = q.form == SvForm::BEAM, al = q.form == SvForm::ALIGN;
   const int64_t* const offs = q.offs;
   const int32_t* const lang = q.lang;
-  const int batch = q.batch, max_tokens = q.max_tokens;
+  const int batch = q.batch;
+  int max_L = 0;
+  if (al) for (int b = 0; b < batch; ++b) max_L = std::max(max_L, q.tgt_off[b + 1] - q.tgt_off[b]);
+  const int max_tokens = al ? std::max(max_L, 1) : q.max_tokens;          // the align form's token sections are as wide as its longest transcript
+  const int n_tgt = al ? q.tgt_off[batch] : 0, ld_em = round_up(max_L + 1, 4);
   HIP_CHECK(hipSetDevice(device));
   // no cluster kernel beside a foreign (RCCL) section: this whole call -- it returns with the stream drained -- is one cluster pass, or takes the four-launch path
   ClusterScope cluster(device);
@@ -659,10 +698,17 @@ void SvSession::run(const SvRunReq& q) {
   const auto s_plan = pb.add<UttPlan>(batch);
   const auto s_blk_utt = pb.add<int32_t>(n_fb), s_blk_f0 = pb.add<int32_t>(n_fb), s_qb_utt = pb.add<int32_t>(n_qb), s_qb_q0 = pb.add<int32_t>(n_qb);
   const auto s_row_utt = pb.add<int32_t>(Mpad), s_tile_win = pb.add<int32_t>(n_tiles), s_tile_idx = pb.add<int32_t>(n_tiles);
+  PlanSection<int32_t> s_tgt_ids{}, s_tgt_off{};         // the align form's transcripts ride behind the sections every form has
+  if (al) { s_tgt_ids = pb.add<int32_t>(std::max(n_tgt, 1)); s_tgt_off = pb.add<int32_t>(batch + 1); }
   pb.commit(stream);
   if (pb.host_moved) ++ws_epoch;                        // (any re-allocation invalidates the captured graph)
   if (pb.dev_moved) ++ws_epoch;
   memcpy(pb.host(s_plan), plan.data(), sizeof(UttPlan) * batch);
+  if (al) {
+    pb.host(s_tgt_ids)[0] = 0;
+    memcpy(pb.host(s_tgt_ids), q.tgt_ids, (size_t)n_tgt * 4);
+    memcpy(pb.host(s_tgt_off), q.tgt_off, (size_t)(batch + 1) * 4);
+  }
   fill_fbank_blocks(plan.data(), batch, pb.host(s_blk_utt), pb.host(s_blk_f0));
   fill_query_blocks(plan.data(), batch, q_rows, pb.host(s_qb_utt), pb.host(s_qb_q0));
   {
@@ -683,7 +729,7 @@ void SvSession::run(const SvRunReq& q) {
   // ---- workspace (grow-only; any re-allocation invalidates the captured graph) -----------------
   const size_t eT = sizeof(T);
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { if (reserve_moved(buf, bytes, stream)) ++ws_epoch; };
-  ResultBlob out(h_out, ResultLayout(batch, max_tokens, bq ? ResultForm::SV_BEAM : !timed ? ResultForm::PLAIN : paraformer ? ResultForm::PF_TIMED : ResultForm::SV_TIMED, bq ? q.nbest : 1));
+  ResultBlob out(h_out, ResultLayout(batch, max_tokens, bq ? ResultForm::SV_BEAM : al ? ResultForm::SV_ALIGN : !timed ? ResultForm::PLAIN : paraformer ? ResultForm::PF_TIMED : ResultForm::SV_TIMED, bq ? q.nbest : 1));
   if (out.commit()) ++ws_epoch;
   r.out = &out;
   bool audio_moved = false;
@@ -714,6 +760,13 @@ void SvSession::run(const SvRunReq& q) {
     grow(d_flp, (size_t)Mpad * 4);
     for (DeviceBuffer* b : {&d_first, &d_last, &d_tlp}) grow(*b, (size_t)batch * max_tokens * 4);
   }
+  if (al) {
+    grow(d_amax_s, (size_t)Mpad * n_slabs * 4);
+    grow(d_em, (size_t)Mpad * ld_em * 4);
+    for (DeviceBuffer* b : {&d_first, &d_last, &d_tlp}) grow(*b, (size_t)batch * max_tokens * 4);
+    for (DeviceBuffer* b : {&d_apath, &d_alik, &d_astat}) grow(*b, (size_t)batch * 4);
+    grow(d_abp, ctc_align_ws_bytes(batch, max_T, c.n_prompt, max_L));     // 0 when the backpointers fit in LDS
+  }
   if (bq) {
     auto grow_beam = [&](DeviceBuffer& buf, size_t bytes) { if (reserve_moved(buf, bytes, stream)) ++beam_epoch; };
     grow(d_amax_s, (size_t)Mpad * n_slabs * 4);
@@ -740,12 +793,17 @@ void SvSession::run(const SvRunReq& q) {
   r.dp = pb.dev(s_plan);
   r.n_tiles = n_tiles; r.tiles = tiles; r.timed = timed;
   if (bq) { r.beam = q.beam; r.topk = q.topk; r.nbest = q.nbest; r.pool_stride = max_T * q.beam; }
+  if (al) { r.align = true; r.max_L = max_L; r.ld_em = ld_em; r.d_tgt_ids = pb.dev(s_tgt_ids); r.d_tgt_off = pb.dev(s_tgt_off); }
   r.d_blk_utt = pb.dev(s_blk_utt); r.d_blk_f0 = pb.dev(s_blk_f0); r.d_qb_utt = pb.dev(s_qb_utt); r.d_qb_q0 = pb.dev(s_qb_q0);
   r.d_row_utt = pb.dev(s_row_utt); r.d_tile_win = pb.dev(s_tile_win); r.d_tile_idx = pb.dev(s_tile_idx);
   // (the result blob adds nothing to the key: its offsets are functions of batch, max_tokens, timed and nbest, all mixed in here; a moved h_out bumps ws_epoch)
   key.mix((uint64_t)batch); key.mix((uint64_t)max_tokens); key.mix((uint64_t)(uintptr_t)r.d_aud); key.mix((uint64_t)audio_dtype); key.mix(ws_epoch); key.mix((uint64_t)(uintptr_t)stream);
   key.mix((uint64_t)(block_cooldown > 0 || foreign_now));        // a session cooling down after a cluster give-up replays the four-launch capture, not the block one
   key.mix((uint64_t)timed);                                      // the timed CTC tail is another launch sequence
+  if (al) {                                                      // the align tail, per transcript length: ld_em, the trellis launch, where the plan blob's sections lie
+    key.mix((uint64_t)q.form);
+    for (int b = 0; b < batch; ++b) key.mix((uint64_t)(q.tgt_off[b + 1] - q.tgt_off[b]));
+  }
   if (bq) {                                                      // ... and so is the beam tail, per (beam, topk, nbest), hotword list and boost
     uint32_t boost_bits; memcpy(&boost_bits, &hot_boost, 4);
     key.mix((uint64_t)q.beam); key.mix((uint64_t)q.topk); key.mix((uint64_t)q.nbest); key.mix(beam_epoch); key.mix((uint64_t)hot_nodes); key.mix((uint64_t)boost_bits);
@@ -757,7 +815,7 @@ void SvSession::run(const SvRunReq& q) {
   if (tiles) ensure_tiles_pack();
   // ---- launch: eager the first time a geometry is seen (allocations settle), then capture once and replay ----
   // 570 launches per forward are host-launch-bound when issued eagerly (~13 us each); replay costs ~1 us per node.
-  (bq ? graph_beam : timed ? graph_timed : graph).run(stream, use_graph && !taps_enabled && !prof.enabled, key.h, [&] { enqueue<T>(r); });
+  (bq ? graph_beam : al ? graph_align : timed ? graph_timed : graph).run(stream, use_graph && !taps_enabled && !prof.enabled, key.h, [&] { enqueue<T>(r); });
   HIP_CHECK(hipStreamSynchronize(stream));
   if (prof.enabled) prof.collect();
   char title[48];
@@ -793,6 +851,19 @@ void SvSession::run(const SvRunReq& q) {
     memcpy(q.score_out, out.host(L.hyp_scores), L.bytes(L.hyp_scores));
     memcpy(q.ctc_out, out.host(L.hyp_ctc), L.bytes(L.hyp_ctc));
     out.scatter_rows(L.hyp_tokens, q.tok_out, q.num_out, max_tokens);
+    return;
+  }
+  if (al) {                                              // ragged, in the layout of the targets; an utterance without an alignment keeps the caller's fill
+    memcpy(q.path_out, out.host(L.path_score), L.bytes(L.path_score));
+    memcpy(q.loglik_out, out.host(L.loglik), L.bytes(L.loglik));
+    memcpy(q.astatus_out, out.host(L.align_status), L.bytes(L.align_status));
+    for (int b = 0; b < batch; ++b) {
+      if (q.astatus_out[b] != 0) continue;
+      const size_t n = (size_t)(q.tgt_off[b + 1] - q.tgt_off[b]) * 4, src = (size_t)b * max_tokens, dst = q.tgt_off[b];
+      memcpy(q.first_out + dst, out.host(L.first) + src, n);
+      memcpy(q.last_out + dst, out.host(L.last) + src, n);
+      memcpy(q.logprob_out + dst, out.host(L.logprob) + src, n);
+    }
     return;
   }
   memcpy(q.num_out, out.host(L.counts), L.bytes(L.counts));
@@ -929,6 +1000,18 @@ extern "C" int asr_sensevoice_run_beam(asr_session* s, const void* audio, int au
     ASR_REQUIRE(s && s->kind == 1, "sensevoice_run_beam: not a SenseVoice session");
     SvRunReq q = run_req(SvForm::BEAM, audio, audio_mem, audio_offsets, batch, language_idx, token_ids_out, max_tokens, num_id_out);
     q.beam = beam; q.topk = topk; q.nbest = nbest; q.score_out = score_out; q.ctc_out = ctc_score_out;
+    run_entry(s, q);
+  });
+}
+
+extern "C" int asr_sensevoice_align(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* language_idx,
+                                    const int32_t* target_ids, const int32_t* target_offsets, int32_t* first_frame_out, int32_t* last_frame_out,
+                                    float* token_logprob_out, float* path_score_out, float* loglik_out, int32_t* status_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && (s->kind == 1 || s->kind == 3), "sensevoice_align: not a SenseVoice session");
+    SvRunReq q = run_req(SvForm::ALIGN, audio, audio_mem, audio_offsets, batch, language_idx, nullptr, 0, nullptr);
+    q.tgt_ids = target_ids; q.tgt_off = target_offsets; q.first_out = first_frame_out; q.last_out = last_frame_out; q.logprob_out = token_logprob_out;
+    q.path_out = path_score_out; q.loglik_out = loglik_out; q.astatus_out = status_out;
     run_entry(s, q);
   });
 }

@@ -269,6 +269,53 @@ class SenseVoiceSession(_Session):
         return [[{"tokens": tok[b, n, :num[b, n]].copy(), "score": float(score[b, n]), "ctc_score": float(ctc[b, n])}
                  for n in range(nbest) if np.isfinite(score[b, n])] for b in range(len(flat))]
 
+    def align_packed(self, audio, offsets: np.ndarray, language_idx: np.ndarray, target_ids: np.ndarray, target_offsets: np.ndarray,
+                     audio_device_ptr: int | None = None, fill=None):
+        """CTC forced alignment of given transcripts (asr_sensevoice_align): utterance b's targets are target_ids[target_offsets[b]:target_offsets[b + 1]].
+        Returns (first_frame, last_frame, logprob, path_score, loglik, status): the first three ragged in the layout of target_ids (int32, int32, float32; rows
+        of the utterance's sequence as run_packed_timed reports them, logprob the mean over the span of log soft-max at the target), the last three [B].
+        status 1: no alignment exists; that utterance's spans keep `fill` = (int, float) (default zeros) and both scores are -inf."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        lang = np.ascontiguousarray(language_idx, dtype=np.int32)
+        B = lang.shape[0]
+        toff = np.ascontiguousarray(target_offsets, dtype=np.int32)
+        tids = np.ascontiguousarray(target_ids, dtype=np.int32).reshape(-1)
+        assert offsets.shape[0] == B + 1 and toff.shape[0] == B + 1 and tids.size == int(toff[-1])
+        n = max(tids.size, 1)
+        fi, ff = (0, 0.0) if fill is None else fill
+        tids_c = tids if tids.size else np.zeros(1, np.int32)
+        first, last = np.full(n, fi, dtype=np.int32), np.full(n, fi, dtype=np.int32)
+        logprob = np.full(n, ff, dtype=np.float32)
+        path, lik = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+        status = np.zeros(B, dtype=np.int32)
+        if audio_device_ptr is not None:
+            ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
+        else:
+            audio = self._audio(audio).reshape(-1)
+            ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
+        _lib.check(_lib.load().asr_sensevoice_align(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, _ip(lang), _ip(tids_c), _ip(toff),
+                                                    _ip(first), _ip(last), _fp(logprob), _fp(path), _fp(lik), _ip(status)))
+        return first[:tids.size], last[:tids.size], logprob[:tids.size], path, lik, status
+
+    def align(self, audios: Sequence[np.ndarray], language_idx: Sequence[int], targets: Sequence[Sequence[int]]):
+        """List of 1-D utterances and one token-id list each -> one record per utterance: {"first_frame", "last_frame", "logprob", "path_score", "loglik",
+        "aligned"}; the three arrays have the transcript's length and are empty when `aligned` is False (no alignment exists: the scores are -inf)."""
+        flat, packed, offs = self._pack(audios)
+        targets = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
+        if len(targets) != len(flat):
+            raise ValueError(f"align: {len(flat)} utterances, {len(targets)} transcripts")
+        toff = np.zeros(len(targets) + 1, dtype=np.int32)
+        toff[1:] = np.cumsum([t.size for t in targets])
+        tids = np.concatenate(targets) if targets else np.zeros(0, np.int32)
+        first, last, logprob, path, lik, status = self.align_packed(packed, offs, np.asarray(language_idx, dtype=np.int32), tids, toff)
+        out = []
+        for b in range(len(flat)):
+            ok = status[b] == 0
+            sl = slice(int(toff[b]), int(toff[b + 1]) if ok else int(toff[b]))
+            out.append({"first_frame": first[sl].copy(), "last_frame": last[sl].copy(), "logprob": logprob[sl].copy(), "path_score": float(path[b]),
+                        "loglik": float(lik[b]), "aligned": bool(ok)})
+        return out
+
     def utterance_rows(self, lengths: Sequence[int]):
         """(row_off, T) of each utterance inside the packed tap tensors (16-row aligned)."""
         out, r = [], 0
@@ -404,6 +451,29 @@ def op_ctc_prefix_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, blank_id=
     _lib.check(_lib.load().asr_op_ctc_prefix_beam(_ip(ids), _fp(lp), ids.shape[1], _ip(sl), sl.size, blank_id, *targs, n_nodes, float(boost), int(beam),
                                                   int(nbest), _ip(tok), max_t, _ip(num), _fp(score), _fp(ctc)))
     return tok, num, score, ctc
+
+
+def op_ctc_align(em, seq_lens, targets, row0=0, max_tokens=None, fill=None):
+    """The forced-alignment trellis on host arrays (asr_op_ctc_align): em [sum T, ld] log-probabilities (slot 0 the blank, slot j target j - 1 of the row's
+    sequence), `targets` one id list per sequence; each sequence is aligned against its rows row0 .. T - 1. Returns (first_frame, last_frame, token_logprob
+    [B, max_tokens], path_score, loglik, status [B]); the three arrays start out holding `fill` = (int, float) (default zeros), which slots the kernel does
+    not write keep."""
+    em = _f32(em)
+    sl = np.ascontiguousarray(seq_lens, dtype=np.int32)
+    assert em.ndim == 2 and em.shape[0] == int(sl.sum()) and len(targets) == sl.size
+    targets = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
+    toff = np.zeros(sl.size + 1, dtype=np.int32)
+    toff[1:] = np.cumsum([t.size for t in targets])
+    tids = np.ascontiguousarray(np.concatenate(targets + [np.zeros(1, np.int32)]), dtype=np.int32)
+    max_t = max(1, max(t.size for t in targets)) if max_tokens is None else int(max_tokens)
+    fi, ff = (0, 0.0) if fill is None else fill
+    first, last = np.full((sl.size, max_t), fi, dtype=np.int32), np.full((sl.size, max_t), fi, dtype=np.int32)
+    tlp = np.full((sl.size, max_t), ff, dtype=np.float32)
+    path, lik = np.zeros(sl.size, dtype=np.float32), np.zeros(sl.size, dtype=np.float32)
+    status = np.zeros(sl.size, dtype=np.int32)
+    _lib.check(_lib.load().asr_op_ctc_align(_fp(em), em.shape[1], _ip(sl), sl.size, int(row0), _ip(tids), _ip(toff), _ip(first), _ip(last), _fp(tlp), max_t,
+                                            _fp(path), _fp(lik), _ip(status)))
+    return first, last, tlp, path, lik, status
 
 
 def op_cif_scan_timed(alpha, enc, seq_lens, tail_threshold, max_tokens=None, fill=0):

@@ -59,6 +59,37 @@ def plan_windows(audio: np.ndarray, audio_len: int, window: int, stride: int) ->
     return audio
 
 
+def _is_cjk(piece: str) -> bool:
+    """Every character of the piece is a CJK ideograph, kana or hangul (such scripts write no spaces: a piece is a word)."""
+    def cjk(ch):
+        c = ord(ch)
+        return (0x3040 <= c <= 0x30FF or 0x3400 <= c <= 0x4DBF or 0x4E00 <= c <= 0x9FFF or 0xAC00 <= c <= 0xD7AF or 0xF900 <= c <= 0xFAFF or
+                0x20000 <= c <= 0x2FA1F)
+    return len(piece) > 0 and all(cjk(ch) for ch in piece)
+
+
+def group_words(pieces, spans, logprobs):
+    """SentencePiece pieces with their (start, end) spans in seconds and log-probabilities -> words: [{"text", "start", "end", "probability"}]. A piece that
+    begins with "\u2581" opens a word (the marker is dropped); a CJK piece is a word of its own, and the piece behind it opens a new one; every other piece
+    continues the word in front of it (the first piece always opens one). A word spans from its first piece's start to its last piece's end;
+    probability = exp(mean logprob of its pieces)."""
+    words, lps, closed = [], [], True
+    for piece, (start, end), lp in zip(pieces, spans, logprobs):
+        text = piece[1:] if piece.startswith("\u2581") else piece
+        cjk = _is_cjk(text)
+        if closed or cjk or piece.startswith("\u2581"):
+            words.append({"text": text, "start": float(start), "end": float(end)})
+            lps.append([float(lp)])
+        else:
+            words[-1]["text"] += text
+            words[-1]["end"] = float(end)
+            lps[-1].append(float(lp))
+        closed = cjk
+    for w, l in zip(words, lps):
+        w["probability"] = float(np.exp(np.mean(l)))
+    return words
+
+
 class SenseVoiceTranscriber:
     def __init__(self, model_folder: str, target_language: str = "en", tokenizer_path: str | None = None, device_id: int = 0,
                  device_type: str = "cpu"):
@@ -102,6 +133,44 @@ class SenseVoiceTranscriber:
             tokens.append({"id": int(tok[0, k]), "start": min(offset_s + t0, duration_s), "end": min(offset_s + t1, duration_s),
                            "logprob": float(logprob[0, k])})
         return tok[0, :n].copy(), tokens
+
+    def align(self, audio_int16: np.ndarray, text_or_ids, normalise: bool = False):
+        """CTC forced alignment of a transcript the caller supplies against one window of int16 mono PCM (SenseVoiceSession.align_packed). The transcript is
+        text (tokenised with the transcriber's tokenizer) or a list of token ids, taken as they are. Returns dict(tokens, words, path_score, loglik, aligned):
+        tokens = [{"id", "start", "end", "logprob"}] in seconds (SenseVoiceConfig.row_span_seconds, clipped to the audio's duration; logprob = mean over
+        the span of log soft-max at the token), words = group_words over the tokenizer's pieces (None without a tokenizer), path_score / loglik = the best
+        path's and the whole transcript's log-probability, aligned = False when the transcript does not fit the audio (tokens and words are then empty
+        and the scores -inf). Audio longer than one window raises ValueError: splitting a transcript across windows is not done here."""
+        native = self.session._native
+        audio_len = int(np.asarray(audio_int16).size)
+        shape_in = self.audio_meta.shape[-1]
+        limit = int(native.cfg.max_audio_len) if is_dynamic_dim(shape_in) else min(int(shape_in), int(native.cfg.max_audio_len))
+        if audio_len > limit:
+            raise ValueError(f"align handles one window: {audio_len} samples given, at most {limit} (max_audio_len) fit")
+        if isinstance(text_or_ids, str):
+            if self.tokenizer is None:
+                raise ValueError("a transcript given as text needs a tokenizer (tokenizer_path); pass token ids instead")
+            ids = [int(t) for t in self.tokenizer.encode(text_or_ids)]
+        else:
+            ids = [int(t) for t in text_or_ids]
+        audio = prepare_audio_input(np.asarray(audio_int16, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype,
+                                    audio_pcm_scale=self.audio_pcm_scale, normalise=normalise)
+        window = audio_len if is_dynamic_dim(shape_in) else int(shape_in)
+        audio = plan_windows(audio, audio_len, window, window)
+        win = array_for(self.audio_meta, audio[:, :, :window], axes={0: 1, 1: 1, 2: window})
+        offsets = np.array([0, win.size], dtype=np.int64)
+        first, last, logprob, path, lik, status = native.align_packed(win.reshape(-1), offsets, np.asarray([self.selector_index], dtype=np.int32),
+                                                                      np.asarray(ids, dtype=np.int32), np.asarray([0, len(ids)], dtype=np.int32))
+        ok = int(status[0]) == 0
+        duration = audio_len / self.sample_rate
+        tokens = []
+        for k in range(len(ids) if ok else 0):
+            t0, t1 = native.cfg.row_span_seconds(first[k], last[k])
+            tokens.append({"id": ids[k], "start": min(t0, duration), "end": min(t1, duration), "logprob": float(logprob[k])})
+        words = None
+        if self.tokenizer is not None:
+            words = group_words([self.tokenizer.id_to_piece(t["id"]) for t in tokens], [(t["start"], t["end"]) for t in tokens], [t["logprob"] for t in tokens])
+        return {"tokens": tokens, "words": words, "path_score": float(path[0]), "loglik": float(lik[0]), "aligned": ok}
 
     def _hotword_ids(self, hotwords):
         """Hotwords as token-id lists: id lists pass through, text needs the tokenizer (tokenizer.encode)."""

@@ -155,6 +155,18 @@ int asr_sensevoice_run_beam(asr_session* s, const void* audio, int audio_mem, co
  * while it spells a phrase; a partial match that breaks off, or is still open at the end of the utterance, gives its part back. n_phrases == 0 clears the
  * list. Ids outside the vocabulary, empty phrases and phrases containing the blank id are rejected (the list in force stays). */
 int asr_sensevoice_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+/* CTC forced alignment of transcripts the caller supplies (no reference counterpart: the reference graph returns its own greedy ids and no times; DESIGN
+ * 4.3c). The forward pass is asr_sensevoice_run's up to the head; per row the log soft-max at the blank and at the utterance's target columns is taken without
+ * storing the logits, and a Viterbi and a forward trellis run over every utterance's speech rows (rows >= n_prompt). Targets are ragged: utterance b's are
+ * target_ids[target_offsets[b] .. target_offsets[b + 1]) (host; target_offsets[0] = 0, at most 1023 per utterance, none is legal: the path is all blank).
+ * Ids outside [0, vocab), the blank id and decreasing offsets are rejected. first_frame_out / last_frame_out / token_logprob_out are host arrays in the layout
+ * of target_ids: the rows of the target's span on the best path, in the row convention of asr_sensevoice_run_timed, and the mean over the span of log soft-max
+ * at the target. Ties go to the smaller move (stay, then one state, then two) and, at the end, to the last target over the final blank. path_score_out [B] =
+ * the best path's log-probability, loglik_out [B] = the transcript's log-likelihood (all paths), status_out [B] = 0 aligned, 1 no alignment exists (fewer
+ * speech rows than targets plus adjacent equal targets): the utterance's spans then keep the caller's fill, both scores are -inf, and the call succeeds. */
+int asr_sensevoice_align(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch, const int32_t* language_idx,
+                         const int32_t* target_ids, const int32_t* target_offsets, int32_t* first_frame_out, int32_t* last_frame_out,
+                         float* token_logprob_out, float* path_score_out, float* loglik_out, int32_t* status_out);
 
 /* sequence length (prompt + LFR rows) the graph produces for an utterance of n_samples */
 int asr_sensevoice_seq_len(const asr_sensevoice_config* cfg, int n_samples, int* seq_len);
@@ -521,6 +533,12 @@ int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, in
                            const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
                            const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
                            int32_t* num_id, float* score, float* ctc_score);
+/* the trellis of asr_sensevoice_align on host arrays: em [sum T][ld_em] log-probabilities, slot 0 the blank and slot j the sequence's target j - 1 (ld_em >
+ * the longest transcript); each sequence is aligned against its rows row0 .. seq_lens[b] - 1 (seq_lens[b] > row0; earlier rows are never read). Targets ragged as
+ * above (any ids: only the equality of neighbours matters). first_frame / last_frame / token_logprob host [batch][max_tokens], max_tokens >= the longest
+ * transcript: slots past a sequence's length, and every slot of a sequence with status 1, are not written. path_score / loglik / status host [batch]. */
+int asr_op_ctc_align(const float* em, int ld_em, const int32_t* seq_lens, int batch, int row0, const int32_t* target_ids, const int32_t* target_offsets,
+                     int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, float* path_score, float* loglik, int32_t* status);
 /* the CIF scan of asr_paraformer_run_timed on host arrays: alpha [sum T], enc [sum T][d], seq_lens [batch] (each >= 1); acoustic_out [sum T][d] receives, per
  * utterance, its token embeddings in its first rows and zeros behind them (tokens past row T - 1 of a 16-row-padded range are not returned);
  * fire_frame_out host [batch][max_tokens] (slots at or past the token count, or past max_tokens, are not written); num_id_out [batch] holds the full count */

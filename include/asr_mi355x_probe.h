@@ -45,6 +45,14 @@ int asr_probe_ctc_head(int M, int N, int K, const float* a, const float* w, cons
 int asr_probe_ctc_topk(int M, int N, int K, const float* a, const float* w, const float* bias, int n_valid, int variant, int precision, int topk,
                        int32_t* out_ids, float* out_logprob, char* kernel32);
 
+/* The emission kernel of asr_sensevoice_align behind the same head: operands, `variant` and `precision` as asr_probe_ctc_topk. row_utt [M] names every row's
+ * transcript (0 .. n_utts - 1, or -1: the row is left alone); transcript u = target_ids[target_offsets[u] .. target_offsets[u + 1]), ids < n_valid.
+ * out_em [M][ld_em]: slot 0 the log soft-max at blank_id, slot j at the transcript's target j - 1, slots past its length -inf (ld_em > the longest transcript).
+ * *stray: words written to rows at or past M. */
+int asr_probe_ctc_target_logprob(int M, int N, int K, const float* a, const float* w, const float* bias, int n_valid, int variant, int precision,
+                                 const int32_t* row_utt, int n_utts, const int32_t* target_ids, const int32_t* target_offsets, int blank_id, int ld_em,
+                                 float* out_em, int32_t* stray, char* kernel32);
+
 /* Decode-shaped GEMM (M <= 64 rows) as a captured chain of dependent launches over `cold_mb` megabytes of weight copies (larger than
  * the Infinity Cache => every launch streams its weights from HBM, like a decoder stack does once per token): microseconds per launch.
  * epilogue: 0 bias -> bf16, 1 bias + GELU -> bf16, 2 bias + residual -> f32, 3 LayerNorm prologue (f32 rows in) -> bf16. */
