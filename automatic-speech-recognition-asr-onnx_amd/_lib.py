@@ -65,6 +65,7 @@ SIGNATURES = {
     "asr_sensevoice_run_timed": (_i, [_vp, _vp, _i, _lp, _i, _ip, _ip, _i, _ip, _ip, _ip, _fp]),
     "asr_sensevoice_run_beam": (_i, [_vp, _vp, _i, _lp, _i, _ip, _i, _i, _i, _ip, _i, _ip, _fp, _fp]),
     "asr_sensevoice_set_hotwords": (_i, [_vp, _ip, _ip, _i, C.c_float]),
+    "asr_sensevoice_set_lm": (_i, [_vp, _ip, C.c_int64, C.c_float, C.c_float, C.c_float]),
     "asr_sensevoice_align": (_i, [_vp, _vp, _i, _lp, _i, _ip, _ip, _ip, _ip, _ip, _fp, _fp, _fp, _ip]),
     "asr_sanm_stats": (_i, [_vp, _ip]),
     "asr_sensevoice_seq_len": (_i, [C.POINTER(SenseVoiceConfigC), _i, C.POINTER(C.c_int)]),
@@ -133,6 +134,8 @@ SIGNATURES = {
     "asr_op_ctc_collapse": (_i, [_ip, _ip, _i, _i, _ip, _i, _ip]),
     "asr_op_ctc_collapse_timed": (_i, [_ip, _fp, _ip, _i, _i, _ip, _ip, _ip, _fp, _i, _ip]),
     "asr_op_ctc_prefix_beam": (_i, [_ip, _fp, _i, _ip, _i, _i, _ip, _ip, _ip, _ip, _ip, _i, C.c_float, _i, _i, _ip, _i, _ip, _fp, _fp]),
+    "asr_op_ctc_prefix_beam_lm": (_i, [_ip, _fp, _i, _ip, _i, _i, _ip, _ip, _ip, _ip, _ip, _i, C.c_float, _i, _i, _ip, _i, _ip, _fp, _fp, _ip, C.c_int64, C.c_float,
+                                       C.c_float, C.c_float]),
     "asr_op_ctc_align": (_i, [_fp, _i, _ip, _i, _i, _ip, _ip, _ip, _ip, _fp, _i, _fp, _fp, _ip]),
     "asr_op_cif_scan_timed": (_i, [_fp, _fp, _i, _ip, _i, C.c_float, _fp, _ip, _i, _ip]),
 }

@@ -5,6 +5,7 @@
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "ngram_lm.h"
 
 const std::string& asr_get_error();
 
@@ -441,10 +442,12 @@ extern "C" int asr_op_ctc_collapse_timed(const int32_t* frame_ids, const float* 
   });
 }
 
-extern "C" int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id,
-                                      const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
-                                      const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
-                                      int32_t* num_id, float* score, float* ctc_score) {
+namespace {
+// both host-array entries of the search; lm_image null: without a language model
+int op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id, const int32_t* trie_depth,
+                       const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node, int n_nodes, float boost,
+                       int beam, int nbest, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score, const int32_t* lm_image, int64_t lm_words,
+                       float alpha, float beta, float oov_logprob) {
   return asr_guard([&] {
     ASR_REQUIRE(cand_id && cand_logprob && seq_lens && token_ids && num_id && score && ctc_score && batch > 0 && max_tokens > 0, "op_ctc_prefix_beam: bad argument");
     ASR_REQUIRE(topk >= 1 && topk <= 16 && beam >= 1 && beam <= 16 && nbest >= 1 && nbest <= beam, "op_ctc_prefix_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)",
@@ -460,6 +463,14 @@ extern "C" int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_
                       "op_ctc_prefix_beam: malformed trie (node %d, child entry %d)", n, e);
         }
       }
+    }
+    if (lm_image) {                                      // the image, then every id the walk will look up
+      ngram_lm_validate(lm_image, lm_words, lm_words >= NGRAM_LM_HEADER ? lm_image[3] : 0, blank_id, alpha, beta, oov_logprob, "op_ctc_prefix_beam_lm");
+      int64_t rows = 0;
+      for (int b = 0; b < batch; ++b) rows += seq_lens[b];
+      for (int64_t i = 0; i < rows * topk; ++i)
+        ASR_REQUIRE(cand_logprob[i] == -INFINITY || (cand_id[i] >= 0 && cand_id[i] < lm_image[3]), "op_ctc_prefix_beam_lm: candidate %d outside the model's vocabulary of %d",
+                    cand_id[i], lm_image[3]);
     }
     asr_require_device(0);
     Tmp t;
@@ -502,13 +513,38 @@ extern "C" int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_
     int32_t* dnum = (int32_t*)t.alloc(hyps * 4);
     float* dsc = (float*)t.alloc(hyps * 4);
     float* dctc = (float*)t.alloc(hyps * 4);
-    launch_ctc_prefix_beam(dids, dlp, topk, dplan, batch, blank_id, beam, nbest, trie, dpool, pool_stride, dtok, max_tokens, dnum, dsc, dctc, nullptr);
+    NgramLm lm;
+    if (lm_image) {
+      int32_t* dlm = (int32_t*)t.alloc((size_t)lm_words * 4);
+      HIP_CHECK(hipMemcpy(dlm, lm_image, (size_t)lm_words * 4, hipMemcpyHostToDevice));
+      lm = ngram_lm_view(dlm, lm_image, alpha, beta, oov_logprob);
+    }
+    launch_ctc_prefix_beam(dids, dlp, topk, dplan, batch, blank_id, beam, nbest, trie, dpool, pool_stride, dtok, max_tokens, dnum, dsc, dctc, nullptr, &lm);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(token_ids, dtok, hyps * max_tokens * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(num_id, dnum, hyps * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(score, dsc, hyps * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(ctc_score, dctc, hyps * 4, hipMemcpyDeviceToHost));
   });
+}
+}  // namespace
+
+extern "C" int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id,
+                                      const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
+                                      const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
+                                      int32_t* num_id, float* score, float* ctc_score) {
+  return op_ctc_prefix_beam(cand_id, cand_logprob, topk, seq_lens, batch, blank_id, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost,
+                            beam, nbest, token_ids, max_tokens, num_id, score, ctc_score, nullptr, 0, 0.0f, 0.0f, 0.0f);
+}
+
+extern "C" int asr_op_ctc_prefix_beam_lm(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id,
+                                         const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
+                                         const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
+                                         int32_t* num_id, float* score, float* ctc_score, const int32_t* lm_image, int64_t lm_words, float alpha, float beta,
+                                         float oov_logprob) {
+  if (!lm_image) return asr_guard([&] { ASR_REQUIRE(false, "op_ctc_prefix_beam_lm: no language model image"); });
+  return op_ctc_prefix_beam(cand_id, cand_logprob, topk, seq_lens, batch, blank_id, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost,
+                            beam, nbest, token_ids, max_tokens, num_id, score, ctc_score, lm_image, lm_words, alpha, beta, oov_logprob);
 }
 
 extern "C" int asr_op_ctc_align(const float* em, int ld_em, const int32_t* seq_lens, int batch, int row0, const int32_t* target_ids, const int32_t* target_offsets,

@@ -1,12 +1,15 @@
 // CTC prefix beam search over the top-k tokens of every frame, with a hotword context graph. Two kernels behind the timed CTC head
 // (GemmArgs::amax_sum): ctc_topk_kernel picks each row's candidates from the head's per-slab partials without the logits ever being stored,
-// ctc_prefix_beam_kernel runs the search, one workgroup per utterance. The float64 statement of the search is tests/ctc_beam_ref.py.
+// ctc_prefix_beam_kernel runs the search, one workgroup per utterance. The float64 statement of the search is tests/ctc_beam_ref.py; with a back-off n-gram
+// language model fused in (the kLm instantiation) it is tests/ctc_lm_ref.py.
 #include <map>
+#include <type_traits>
 
 #include "ctc_dev.h"
 #include "engine.h"
 #include "hot_trie.h"
 #include "kernels.h"
+#include "ngram_lm.h"
 
 namespace {
 
@@ -100,11 +103,18 @@ __device__ __forceinline__ uint64_t hash_step(uint64_t h, int c) {
   return z ^ (z >> 31);
 }
 
-struct BeamLive {                     // the live prefixes of one frame, in rank order
+template <bool kLm> struct BeamLmState {};
+template <> struct BeamLmState<true> {               // a prefix's language-model total (alpha * logp + beta over its tokens) and state: functions of its content
+  float lm[CTC_BEAM_MAX];
+  int lmstate[CTC_BEAM_MAX];
+};
+template <bool kLm>
+struct BeamLive : BeamLmState<kLm> {  // the live prefixes of one frame, in rank order
   float pb[CTC_BEAM_MAX], pnb[CTC_BEAM_MAX], bonus[CTC_BEAM_MAX];
   uint64_t hash[CTC_BEAM_MAX];
   int len[CTC_BEAM_MAX], last[CTC_BEAM_MAX], pool[CTC_BEAM_MAX], node[CTC_BEAM_MAX];
 };
+struct NoLm {};
 
 // One workgroup per utterance, sequential over its rows plan[u].row_off .. + T. Entry e of a frame: e < 16 the "stay" of live prefix e (blank, and a repeat of
 // its last token), e = 16 + p * topk + j the extension of live prefix p by candidate column j. An extension that spells a live prefix (same hash, length and
@@ -112,11 +122,18 @@ struct BeamLive {                     // the live prefixes of one frame, in rank
 // pnb' has at most two terms and logaddexp of two terms does not depend on their order. The best `beam` entries by logaddexp(pb', pnb') + bonus survive,
 // ties to the lower entry index; their rank is their index in the next frame. Kept extensions append a (parent, token) node to the utterance's pool at
 // [t * beam + rank], which the final backtrace walks. Candidates of a row must have distinct ids; a candidate with lp = -inf is ignored.
+// kLm: every prefix also carries lm, the sum of alpha * log P(token | state) + beta over its tokens, and the model's state. Both are functions of the prefix's
+// content, as the bonus is, so merging by content is unchanged: a stay keeps them, an extension walks the image (lm_step) beside the trie, one dependent chain
+// per frame on all extension threads at once. The ranking score gains + lm; at the end a prefix adds alpha * log P(</s> | state) when the model lists </s>.
+// Candidate ids must lie in [0, vocab) of the image. The kLm = false instantiation is the search without a model: the instructions it had, the
+// arguments behind the (empty) model argument 8 bytes further on.
+template <bool kLm>
 __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const int32_t* __restrict__ cand_id, const float* __restrict__ cand_lp, int topk,
                                                                        const UttPlan* __restrict__ plan, int blank, int beam, int nbest, HotTrie tr,
+                                                                       typename std::conditional<kLm, NgramLm, NoLm>::type lmod,
                                                                        int2* __restrict__ pool_all, int pool_stride, int32_t* __restrict__ tok_out, int max_tokens,
                                                                        int32_t* __restrict__ num_out, float* __restrict__ score_out, float* __restrict__ ctc_out) {
-  __shared__ BeamLive live[2];
+  __shared__ BeamLive<kLm> live[2];
   __shared__ float s_pb[CTC_BEAM_MAX], s_pnb[CTC_BEAM_MAX], e_score[CTC_BEAM_MAX + CTC_BEAM_MAX * CTC_BEAM_MAX];
   __shared__ int c_id[CTC_BEAM_MAX], n_valid_entries, f_order[CTC_BEAM_MAX];
   __shared__ float c_lp[CTC_BEAM_MAX], f_score[CTC_BEAM_MAX], f_ctc[CTC_BEAM_MAX];
@@ -127,13 +144,14 @@ __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const
   if (e == 0) {
     live[0].pb[0] = 0.0f; live[0].pnb[0] = -INFINITY; live[0].bonus[0] = 0.0f; live[0].hash[0] = 0; live[0].len[0] = 0; live[0].last[0] = -1;
     live[0].pool[0] = -1; live[0].node[0] = 0;
+    if constexpr (kLm) { live[0].lm[0] = 0.0f; live[0].lmstate[0] = lmod.start_node; }
   }
   int n_live = 1;
   int nx_id = 0; float nx_lp = 0.0f;                    // the next row's candidate of this thread (threads < topk), fetched a frame ahead
   if (e < topk && T > 0) { nx_id = cand_id[(size_t)row0 * topk + e]; nx_lp = cand_lp[(size_t)row0 * topk + e]; }
   for (int t = 0; t < T; ++t) {
-    const BeamLive& cur = live[t & 1];
-    BeamLive& nxt = live[(t + 1) & 1];
+    const BeamLive<kLm>& cur = live[t & 1];
+    BeamLive<kLm>& nxt = live[(t + 1) & 1];
     if (e < topk) {
       c_id[e] = nx_id; c_lp[e] = nx_lp;
       if (t + 1 < T) { nx_id = cand_id[(size_t)(row0 + t + 1) * topk + e]; nx_lp = cand_lp[(size_t)(row0 + t + 1) * topk + e]; }
@@ -148,6 +166,8 @@ __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const
     float val = -INFINITY, nb_bonus = 0.0f;
     uint64_t nh = 0;
     int c = -1, merge_to = -1, nnode = 0;
+    float nlm = 0.0f;                                  // (kLm) the language-model total and state of this thread's extension
+    int nstate = 0;
     if (active && is_stay) {
       const float pb = cur.pb[p], pnb = cur.pnb[p], tot = lae(pb, pnb);
       const int last = cur.last[p];
@@ -179,11 +199,19 @@ __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const
     __syncthreads();
     // 3. scores
     float sc = -INFINITY;
-    if (active && is_stay) sc = lae(s_pb[p], s_pnb[p]) + cur.bonus[p];
-    else if (active) {
+    if (active && is_stay) {
+      sc = lae(s_pb[p], s_pnb[p]) + cur.bonus[p];
+      if constexpr (kLm) sc += cur.lm[p];
+    } else if (active) {
       nnode = cur.node[p]; nb_bonus = cur.bonus[p];
       trie_step(tr, nnode, nb_bonus, c);
       sc = val + nb_bonus;
+      if constexpr (kLm) {
+        nstate = cur.lmstate[p];
+        const float lp = lm_step(lmod, nstate, c);
+        nlm = cur.lm[p] + (lmod.alpha * lp + lmod.beta);
+        sc += nlm;
+      }
     }
     if (sc == -INFINITY) active = false;
     if (e < N_ENT) e_score[e] = sc;
@@ -201,11 +229,13 @@ __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const
         if (is_stay) {
           nxt.pb[rank] = s_pb[p]; nxt.pnb[rank] = s_pnb[p]; nxt.bonus[rank] = cur.bonus[p]; nxt.hash[rank] = cur.hash[p]; nxt.len[rank] = cur.len[p];
           nxt.last[rank] = cur.last[p]; nxt.pool[rank] = cur.pool[p]; nxt.node[rank] = cur.node[p];
+          if constexpr (kLm) { nxt.lm[rank] = cur.lm[p]; nxt.lmstate[rank] = cur.lmstate[p]; }
         } else {
           const int idx = t * beam + rank;
           pool[idx] = make_int2(cur.pool[p], c);
           nxt.pb[rank] = -INFINITY; nxt.pnb[rank] = val; nxt.bonus[rank] = nb_bonus; nxt.hash[rank] = nh; nxt.len[rank] = cur.len[p] + 1;
           nxt.last[rank] = c; nxt.pool[rank] = idx; nxt.node[rank] = nnode;
+          if constexpr (kLm) { nxt.lm[rank] = nlm; nxt.lmstate[rank] = nstate; }
         }
       }
     }
@@ -213,13 +243,20 @@ __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const
     n_live = min(beam, n_valid_entries);
     __syncthreads();                                   // (n_valid_entries is cleared at the top of the next frame)
   }
-  // ---- the end of the utterance: a prefix still inside a phrase gives its partial bonus back; sort by ctc + bonus (stable over the rank order)
-  const BeamLive& fin = live[T & 1];
+  // ---- the end of the utterance: a prefix still inside a phrase gives its partial bonus back; sort by ctc + bonus (stable over the rank order);
+  // (kLm) + lm, which gains alpha * log P(</s> | state) when the model lists </s>
+  const BeamLive<kLm>& fin = live[T & 1];
   if (e < n_live) {
     float bonus = fin.bonus[e];
     if (tr.n_nodes > 1 && fin.node[e] != 0) bonus -= (float)tr.depth[fin.node[e]] * tr.boost;
     const float ctc = lae(fin.pb[e], fin.pnb[e]);
-    f_ctc[e] = ctc; f_score[e] = ctc + bonus;
+    float sc = ctc + bonus;
+    if constexpr (kLm) {
+      float lm = fin.lm[e];
+      if (lmod.eos >= 0) { int st = fin.lmstate[e]; lm += lmod.alpha * lm_step(lmod, st, lmod.eos); }
+      sc += lm;
+    }
+    f_ctc[e] = ctc; f_score[e] = sc;
   }
   __syncthreads();
   if (e < n_live) {
@@ -262,12 +299,16 @@ template void launch_ctc_topk<bf16_t>(const bf16_t*, int, const bf16_t*, int, co
 
 void launch_ctc_prefix_beam(const int32_t* cand_id, const float* cand_lp, int topk, const UttPlan* plan, int n_utts, int blank_id, int beam, int nbest,
                             const HotTrie& trie, int2* pool, int pool_stride, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score,
-                            hipStream_t s) {
+                            hipStream_t s, const NgramLm* lm) {
   ASR_REQUIRE(beam >= 1 && beam <= CTC_BEAM_MAX && topk >= 1 && topk <= CTC_BEAM_MAX && nbest >= 1 && nbest <= beam, "ctc_prefix_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)",
               beam, topk, nbest);
   ASR_REQUIRE(n_utts > 0 && max_tokens >= 1 && pool && pool_stride >= beam, "ctc_prefix_beam: bad argument");
-  hipLaunchKernelGGL(ctc_prefix_beam_kernel, dim3(n_utts), dim3(CTC_BEAM_THREADS), 0, s, cand_id, cand_lp, topk, plan, blank_id, beam, nbest, trie, pool, pool_stride,
-                     token_ids, max_tokens, num_id, score, ctc_score);
+  if (lm && lm->n_nodes > 0)
+    hipLaunchKernelGGL(ctc_prefix_beam_kernel<true>, dim3(n_utts), dim3(CTC_BEAM_THREADS), 0, s, cand_id, cand_lp, topk, plan, blank_id, beam, nbest, trie, *lm, pool,
+                       pool_stride, token_ids, max_tokens, num_id, score, ctc_score);
+  else
+    hipLaunchKernelGGL(ctc_prefix_beam_kernel<false>, dim3(n_utts), dim3(CTC_BEAM_THREADS), 0, s, cand_id, cand_lp, topk, plan, blank_id, beam, nbest, trie, NoLm{}, pool,
+                       pool_stride, token_ids, max_tokens, num_id, score, ctc_score);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -436,10 +436,12 @@ void launch_ctc_topk(const T* h, int ldh, const T* W, int ldw, const float* bias
                      int n_valid, int topk, int32_t* cand_id, float* cand_lp, hipStream_t s);
 // The search, one workgroup per utterance over rows plan[u].row_off .. + T of the candidate arrays. pool: [n_utts][pool_stride] (parent, token) nodes,
 // pool_stride >= max T * beam. Outputs [n_utts][nbest] (token_ids [n_utts][nbest][max_tokens], best first; num_id keeps the full length); hypotheses beyond the
-// number found have num_id 0 and score -inf.
+// number found have num_id 0 and score -inf. lm (ngram_lm.h; null or without nodes: none): a back-off n-gram model fused into the ranking; score
+// then holds ctc + bonus + lm, ctc_score stays the CTC figure, and candidate ids must lie in the image's vocabulary.
+struct NgramLm;
 void launch_ctc_prefix_beam(const int32_t* cand_id, const float* cand_lp, int topk, const UttPlan* plan, int n_utts, int blank_id, int beam, int nbest,
                             const HotTrie& trie, int2* pool, int pool_stride, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score,
-                            hipStream_t s);
+                            hipStream_t s, const NgramLm* lm = nullptr);
 
 // ---- CTC forced alignment of a given transcript (ctc_align.hip)
 // Emissions: for every row m < M with u = row_utt[m] >= 0, em[m][j] = log soft-max of h W^T + bias at slot j's column -- slot 0 the blank, slot j = 1 .. L_u

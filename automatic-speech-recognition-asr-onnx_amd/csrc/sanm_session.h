@@ -7,6 +7,7 @@
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "ngram_lm.h"
 
 struct SvBlock {
   const float *ln1_g, *ln1_b, *bqkv, *wfsmn, *bfsmn, *ln2_g, *ln2_b, *b1, *b2;
@@ -148,9 +149,14 @@ struct ASR_LOCAL SvSession : asr_session {
   // beam runs only: candidates [rows][topk], the (parent, token) node pool, the outputs as one block (result_layout.h: the beam block), the hotword trie image
   DeviceBuffer d_cand_i, d_cand_l, d_pool, d_bout, d_hot;
   int hot_nodes = 0; float hot_boost = 0.0f;
-  uint64_t beam_epoch = 1;      // bumped when a beam-only buffer moves or the hotword list changes: part of the beam graph's key, not of the others'
+  uint64_t beam_epoch = 1;      // bumped when a beam-only buffer moves or the hotword list or language model changes: part of the beam graph's key, not of the others'
   StepGraph graph_beam;         // hipGraph replay of the beam form
   void set_hotwords(const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+  // the n-gram language model of the beam form (asr_sensevoice_set_lm, ngram_lm.h): the image in HBM, its checked header, the weights
+  DeviceBuffer d_lm;
+  int32_t lm_header[6] = {0, 0, 0, 0, 0, -1};            // n_nodes (word 1) == 0: no model
+  float lm_alpha = 0.0f, lm_beta = 0.0f, lm_oov = 0.0f;
+  void set_lm(const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob);
   // align runs only (asr_sensevoice_align, ctc_align.hip): emissions [rows][ld_em], the backpointer workspace of transcripts too long for LDS, per-utterance
   // scores and status; the spans land in d_first / d_last / d_tlp
   DeviceBuffer d_em, d_abp, d_apath, d_alik, d_astat;

@@ -412,9 +412,11 @@ void SvSession::enqueue(const SvRunCtx& r) {
     }
     {
       ProfScope ps(prof, "ctc_beam", stream);
+      NgramLm lm;                                         // (no nodes: the search without a model is launched)
+      if (lm_header[1] > 0) lm = ngram_lm_view(d_lm.as<int32_t>(), lm_header, lm_alpha, lm_beta, lm_oov);
       launch_ctc_prefix_beam(d_cand_i.as<int32_t>(), d_cand_l.as<float>(), r.topk, r.dp, r.batch, c.blank_id, r.beam, r.nbest,
                              hot_trie_view(d_hot.as<int32_t>(), hot_nodes, hot_boost), (int2*)d_pool.ptr, r.pool_stride, o.dev(o.lay.hyp_tokens, d_bout), r.max_tokens,
-                             o.dev(o.lay.hyp_counts, d_bout), o.dev(o.lay.hyp_scores, d_bout), o.dev(o.lay.hyp_ctc, d_bout), stream);
+                             o.dev(o.lay.hyp_counts, d_bout), o.dev(o.lay.hyp_scores, d_bout), o.dev(o.lay.hyp_ctc, d_bout), stream, &lm);
     }
     if (taps_enabled) {
       save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
@@ -804,9 +806,11 @@ void SvSession::run(const SvRunReq& q) {
     key.mix((uint64_t)q.form);
     for (int b = 0; b < batch; ++b) key.mix((uint64_t)(q.tgt_off[b + 1] - q.tgt_off[b]));
   }
-  if (bq) {                                                      // ... and so is the beam tail, per (beam, topk, nbest), hotword list and boost
+  if (bq) {                                                      // ... and so is the beam tail, per (beam, topk, nbest), hotword list and boost, language model and weights
     uint32_t boost_bits; memcpy(&boost_bits, &hot_boost, 4);
     key.mix((uint64_t)q.beam); key.mix((uint64_t)q.topk); key.mix((uint64_t)q.nbest); key.mix(beam_epoch); key.mix((uint64_t)hot_nodes); key.mix((uint64_t)boost_bits);
+    uint32_t lm_bits[3]; memcpy(lm_bits, &lm_alpha, 4); memcpy(lm_bits + 1, &lm_beta, 4); memcpy(lm_bits + 2, &lm_oov, 4);
+    key.mix((uint64_t)lm_header[1]); key.mix((uint64_t)lm_header[2]); key.mix((uint64_t)lm_bits[0]); key.mix((uint64_t)lm_bits[1]); key.mix((uint64_t)lm_bits[2]);
   }
 
   if (sizeof(T) == 2 && use_block && cfg.n_blocks > 1 && blocks[cfg.n_blocks - 1].cqkv && blocks[cfg.n_blocks - 1].c1 && batch >= block_min_utts &&
@@ -896,6 +900,22 @@ void SvSession::set_hotwords(const int32_t* ids, const int32_t* offsets, int n_p
   HIP_CHECK(hipStreamSynchronize(stream));
   hot_nodes = n_nodes; hot_boost = boost;
   ++beam_epoch;                                          // the trie's words are graph-kernel operands: a captured beam step is stale
+}
+
+// The image is checked in full before it replaces the one in force (a rejected image changes nothing); its words are graph-kernel operands like the trie's.
+void SvSession::set_lm(const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob) {
+  ASR_REQUIRE(!paraformer, "sensevoice_set_lm: not a SenseVoice session");
+  ASR_REQUIRE(n_words >= 0 && (n_words == 0 || image_words), "sensevoice_set_lm: bad argument");
+  HIP_CHECK(hipSetDevice(device));
+  if (n_words == 0) { lm_header[1] = 0; lm_alpha = lm_beta = lm_oov = 0.0f; ++beam_epoch; return; }
+  ngram_lm_validate(image_words, n_words, cfg.vocab, cfg.blank_id, alpha, beta, oov_logprob, "sensevoice_set_lm");
+  HIP_CHECK(hipStreamSynchronize(stream));
+  d_lm.reserve((size_t)n_words * 4, stream);
+  HIP_CHECK(hipMemcpyAsync(d_lm.ptr, image_words, (size_t)n_words * 4, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  memcpy(lm_header, image_words, sizeof lm_header);
+  lm_alpha = alpha; lm_beta = beta; lm_oov = oov_logprob;
+  ++beam_epoch;                                          // a captured beam step is stale
 }
 
 namespace {
@@ -1013,6 +1033,13 @@ extern "C" int asr_sensevoice_align(asr_session* s, const void* audio, int audio
     q.tgt_ids = target_ids; q.tgt_off = target_offsets; q.first_out = first_frame_out; q.last_out = last_frame_out; q.logprob_out = token_logprob_out;
     q.path_out = path_score_out; q.loglik_out = loglik_out; q.astatus_out = status_out;
     run_entry(s, q);
+  });
+}
+
+extern "C" int asr_sensevoice_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 1, "sensevoice_set_lm: not a SenseVoice session");
+    static_cast<SvSession*>(s)->set_lm(image_words, n_words, alpha, beta, oov_logprob);
   });
 }
 

@@ -239,6 +239,17 @@ class SenseVoiceSession(_Session):
         ids = ids if ids.size else np.zeros(1, np.int32)
         _lib.check(_lib.load().asr_sensevoice_set_hotwords(self._h, _ip(ids), _ip(offs), len(phrases), float(boost)))
 
+    def set_lm(self, lm, alpha: float = 0.5, beta: float = 0.0, oov_logprob: float | None = None):
+        """The n-gram language model of run_beam (asr_sensevoice_set_lm; shallow fusion): `lm` an lm.NgramLM, or an int32 image as NgramLM.image returns it;
+        None clears it. Every token a hypothesis appends adds alpha * log P(token | history) + beta to its ranking score (alpha the LM weight, beta a
+        length bonus); a token the model has no unigram for costs oov_logprob (default: the model's <unk>, else 0) and leaves the history alone. A
+        malformed image or a bad weight raises AsrError and the model in force stays."""
+        if lm is None:
+            _lib.check(_lib.load().asr_sensevoice_set_lm(self._h, None, 0, 0.0, 0.0, 0.0))
+            return
+        img, oov = _lm_image(lm, self.cfg.vocab, oov_logprob)
+        _lib.check(_lib.load().asr_sensevoice_set_lm(self._h, _ip(img), img.size, float(alpha), float(beta), oov))
+
     def run_packed_beam(self, audio, offsets: np.ndarray, language_idx: np.ndarray, beam: int, topk: int | None = None, nbest: int = 1,
                         audio_device_ptr: int | None = None):
         """run_packed with a CTC prefix beam search instead of the arg-max collapse (asr_sensevoice_run_beam): the `topk` (default: beam) best tokens
@@ -432,9 +443,25 @@ def hotword_trie(phrases):
             "child_node": i32(node)}
 
 
-def op_ctc_prefix_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, blank_id=0, trie=None, boost=0.0, max_tokens=None):
+def _lm_image(lm, vocab, oov_logprob):
+    """(int32 image, oov_logprob) of an lm.NgramLM or a ready image"""
+    if hasattr(lm, "image"):
+        if vocab is None:
+            raise ValueError("an lm.NgramLM needs the vocabulary size (vocab=) to become an image")
+        img, default = lm.image(vocab), lm.default_oov_logprob
+    else:
+        img, default = lm, 0.0
+    img = np.ascontiguousarray(img, dtype=np.int32).reshape(-1)
+    img = img if img.size else np.zeros(1, np.int32)
+    return img, float(default if oov_logprob is None else oov_logprob)
+
+
+def op_ctc_prefix_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, blank_id=0, trie=None, boost=0.0, max_tokens=None, lm=None, alpha=0.5, beta=0.0,
+                       oov_logprob=None, vocab=None):
     """The CTC prefix beam search on host arrays (asr_op_ctc_prefix_beam): cand_id / cand_logprob [sum T, topk], `trie` as hotword_trie returns it (None:
-    no hotwords). Returns (token_ids [B, nbest, max_tokens], num_id [B, nbest], score [B, nbest], ctc_score [B, nbest]), best first."""
+    no hotwords). Returns (token_ids [B, nbest, max_tokens], num_id [B, nbest], score [B, nbest], ctc_score [B, nbest]), best first. With `lm` (an
+    lm.NgramLM, built for `vocab` ids, or an int32 image) the search runs with that language model (asr_op_ctc_prefix_beam_lm; alpha, beta and oov_logprob
+    as SenseVoiceSession.set_lm takes them) and score includes its term."""
     ids = np.ascontiguousarray(cand_id, dtype=np.int32)
     lp = _f32(cand_logprob)
     sl = np.ascontiguousarray(seq_lens, dtype=np.int32)
@@ -448,6 +475,12 @@ def op_ctc_prefix_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, blank_id=
         targs, n_nodes = [_ip(t[k]) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")], int(t["depth"].size)
     else:
         targs, n_nodes = [None] * 5, 0
+    if lm is not None:
+        img, oov = _lm_image(lm, vocab, oov_logprob)
+        _lib.check(_lib.load().asr_op_ctc_prefix_beam_lm(_ip(ids), _fp(lp), ids.shape[1], _ip(sl), sl.size, blank_id, *targs, n_nodes, float(boost), int(beam),
+                                                         int(nbest), _ip(tok), max_t, _ip(num), _fp(score), _fp(ctc), _ip(img), img.size, float(alpha),
+                                                         float(beta), oov))
+        return tok, num, score, ctc
     _lib.check(_lib.load().asr_op_ctc_prefix_beam(_ip(ids), _fp(lp), ids.shape[1], _ip(sl), sl.size, blank_id, *targs, n_nodes, float(boost), int(beam),
                                                   int(nbest), _ip(tok), max_t, _ip(num), _fp(score), _fp(ctc)))
     return tok, num, score, ctc

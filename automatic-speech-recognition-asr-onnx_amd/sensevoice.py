@@ -183,6 +183,18 @@ class SenseVoiceTranscriber:
             out.append([int(t) for t in h])
         return out
 
+    def load_lm(self, arpa_path):
+        """An ARPA file as lm.NgramLM: words are token ids, or pieces of this transcriber's tokenizer."""
+        from .lm import NgramLM
+        tok = self.tokenizer
+        if tok is None:
+            return NgramLM.from_arpa(arpa_path)
+
+        def piece_id(piece):                               # (SentencePiece answers an unknown piece with the id of <unk>)
+            i = int(tok.piece_to_id(piece))
+            return i if tok.id_to_piece(i) == piece else None
+        return NgramLM.from_arpa(arpa_path, token_to_id=piece_id)
+
     def _run_window_beam(self, win: np.ndarray, language_idx: np.ndarray, beam_size: int, nbest: int):
         """One window through the native session's CTC prefix beam search: (token ids of the best hypothesis, the hypotheses found, best first)."""
         native = self.session._native
@@ -198,19 +210,23 @@ class SenseVoiceTranscriber:
         return hyps[0]["token_ids"], hyps
 
     def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False, timestamps: bool = False, beam_size: int = 1,
-                   nbest: int = 1, hotwords=None, hotword_boost: float = 2.0):
+                   nbest: int = 1, hotwords=None, hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0):
         """int16 mono PCM at `sample_rate` -> dict(token_ids, text, rtf, windows). timestamps=True adds "tokens": one {"id", "start", "end", "logprob"}
         per token over all windows, in seconds of the whole audio (SenseVoiceConfig.row_span_seconds; logprob = mean frame log-probability).
         beam_size > 1, nbest > 1 or hotwords: every window is decoded by the CTC prefix beam search (SenseVoiceSession.run_packed_beam) instead of the
         arg-max collapse; token_ids / text hold the best hypothesis and "nbest" holds, per window, the hypotheses found, best first:
-        {"token_ids", "score", "ctc_score", "text"}. hotwords: token-id lists, or text when a tokenizer is loaded; hotword_boost per matched token."""
-        use_beam = beam_size > 1 or nbest > 1 or bool(hotwords)
+        {"token_ids", "score", "ctc_score", "text"}. hotwords: token-id lists, or text when a tokenizer is loaded; hotword_boost per matched token.
+        lm: an lm.NgramLM (NgramLM.from_arpa; load_lm reads a file with this transcriber's tokenizer) fused into the search, which it implies as hotwords
+        do: every token adds lm_weight * log P(token | history) + length_bonus to a hypothesis' score (SenseVoiceSession.set_lm). The call sets exactly
+        its own model: None clears one an earlier call set."""
+        use_beam = beam_size > 1 or nbest > 1 or bool(hotwords) or lm is not None
         if use_beam:
             if timestamps:
                 raise ValueError("timestamps are not available for beam hypotheses")
             if not 1 <= nbest <= beam_size <= 16:
                 raise ValueError(f"beam_size {beam_size}, nbest {nbest}: expected 1 <= nbest <= beam_size <= 16")
             self.session._native.set_hotwords(self._hotword_ids(hotwords), hotword_boost)        # exactly this call's list (an empty one clears)
+            self.session._native.set_lm(lm, lm_weight, length_bonus)                             # ... and exactly this call's model
         audio_len = int(np.asarray(audio_int16).size)
         audio = prepare_audio_input(np.asarray(audio_int16, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype,
                                     audio_pcm_scale=self.audio_pcm_scale, normalise=normalise)

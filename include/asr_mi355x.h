@@ -147,7 +147,9 @@ int asr_sensevoice_run_timed(asr_session* s, const void* audio, int audio_mem, c
  * `beam` (1..16) runs over every utterance's rows, prompt rows included. The `nbest` (1..beam) best hypotheses come back best first: token_ids_out host
  * [B][nbest][max_tokens] (each row holds min(num, max_tokens) ids, rest untouched), num_id_out [B][nbest] (the full length), score_out [B][nbest] = the
  * hypothesis' CTC log-probability over the candidates plus its hotword bonus, ctc_score_out [B][nbest] = without the bonus. Hypotheses beyond the number
- * found have num 0 and score -inf. Scores tie-break to the earlier entry of the documented enumeration; two calls on the same input return the same bytes. */
+ * found have num 0 and score -inf. Scores tie-break to the earlier entry of the documented enumeration; two calls on the same input return the same bytes.
+ * With a language model set (asr_sensevoice_set_lm) the search ranks by CTC + bonus + LM and score_out includes the LM term (alpha * log P + beta per token,
+ * alpha * log P(</s>) at the end when the model lists it); ctc_score_out stays the CTC figure. */
 int asr_sensevoice_run_beam(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                             const int32_t* language_idx, int beam, int topk, int nbest, int32_t* token_ids_out, int max_tokens,
                             int32_t* num_id_out, float* score_out, float* ctc_score_out);
@@ -155,6 +157,20 @@ int asr_sensevoice_run_beam(asr_session* s, const void* audio, int audio_mem, co
  * while it spells a phrase; a partial match that breaks off, or is still open at the end of the utterance, gives its part back. n_phrases == 0 clears the
  * list. Ids outside the vocabulary, empty phrases and phrases containing the blank id are rejected (the list in force stays). */
 int asr_sensevoice_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+/* Back-off n-gram language model of asr_sensevoice_run_beam, fused into the search (shallow fusion). image_words (host): one blob of n_words 32-bit
+ * words over token ids, order N in 1..5 --
+ *   [order, n_nodes, n_edges, vocab, start_node, eos_edge_token]
+ *   depth i32 [n_nodes], backoff f32 [n_nodes], suffix i32 [n_nodes], child_off i32 [n_nodes + 1], tok i32 [n_edges], logp f32 [n_edges], next i32 [n_edges],
+ *   uni i32 [vocab + 2]
+ * Nodes are the contexts (node 0 the empty one, every listed n-gram of order 1..N-1 a node of that depth; suffix = its longest proper suffix that is a node);
+ * edges [child_off[n], child_off[n + 1]) are node n's listed continuations sorted by token, logp / backoff natural logs, next = the node of the longest suffix
+ * of the full n-gram that is a node. uni[c] is the root's edge for token c or -1; </s> and <s> take the ids vocab and vocab + 1. start_node is next of the <s>
+ * unigram (0 without one), eos_edge_token is vocab when </s> is listed, else -1. A token without a unigram is out of vocabulary: it costs oov_logprob and
+ * leaves the state alone. Every appended token adds alpha * log P(token | state) + beta to the hypothesis' ranking score.
+ * n_words == 0 clears the model. The image is checked on the host before it replaces the one in force: sizes against n_words, vocab against the session's,
+ * monotone offsets, children strictly sorted and none on the blank id, suffix links to smaller depths, next in range, logp finite and <= 0, backoff finite,
+ * oov_logprob finite and <= 0, alpha finite and >= 0, beta finite. A rejected image leaves the previous one in force. */
+int asr_sensevoice_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob);
 /* CTC forced alignment of transcripts the caller supplies (no reference counterpart: the reference graph returns its own greedy ids and no times; DESIGN
  * 4.3c). The forward pass is asr_sensevoice_run's up to the head; per row the log soft-max at the blank and at the utterance's target columns is taken without
  * storing the logits, and a Viterbi and a forward trellis run over every utterance's speech rows (rows >= n_prompt). Targets are ragged: utterance b's are
@@ -533,6 +549,13 @@ int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, in
                            const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
                            const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
                            int32_t* num_id, float* score, float* ctc_score);
+/* the same with a language model image as asr_sensevoice_set_lm takes it (lm_words 32-bit words, checked the same way against blank_id; its header's vocab
+ * bounds the candidate ids with a finite log-probability) */
+int asr_op_ctc_prefix_beam_lm(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id,
+                              const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
+                              const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
+                              int32_t* num_id, float* score, float* ctc_score, const int32_t* lm_image, int64_t lm_words, float alpha, float beta,
+                              float oov_logprob);
 /* the trellis of asr_sensevoice_align on host arrays: em [sum T][ld_em] log-probabilities, slot 0 the blank and slot j the sequence's target j - 1 (ld_em >
  * the longest transcript); each sequence is aligned against its rows row0 .. seq_lens[b] - 1 (seq_lens[b] > row0; earlier rows are never read). Targets ragged as
  * above (any ids: only the equality of neighbours matters). first_frame / last_frame / token_logprob host [batch][max_tokens], max_tokens >= the longest

@@ -79,9 +79,16 @@ def run(a) -> dict:
     nbest, hot_file = getattr(a, "nbest", 1), getattr(a, "hotwords", None)
     if (nbest > 1 or hot_file) and a.family != "sensevoice":
         raise SystemExit("--nbest / --hotwords exist for --family sensevoice only")
-    sv_beam = a.family == "sensevoice" and (a.beam > 1 or nbest > 1 or bool(hot_file))
+    lm_file, lm_weight, length_bonus = getattr(a, "lm", None), getattr(a, "lm_weight", None), getattr(a, "length_bonus", None)
+    if (lm_file or lm_weight is not None or length_bonus is not None) and a.family != "sensevoice":
+        raise SystemExit("--lm / --lm-weight / --length-bonus exist for --family sensevoice only")
+    if (lm_weight is not None or length_bonus is not None) and not lm_file:
+        raise SystemExit("--lm-weight / --length-bonus need --lm FILE.arpa")
+    if lm_file and not os.path.isfile(lm_file):
+        raise SystemExit("--lm %s: no such file" % lm_file)
+    sv_beam = a.family == "sensevoice" and (a.beam > 1 or nbest > 1 or bool(hot_file) or bool(lm_file))
     if sv_beam and timestamps:
-        raise SystemExit("--timestamps is not available with --beam / --nbest / --hotwords (beam hypotheses carry no time spans)")
+        raise SystemExit("--timestamps is not available with --beam / --nbest / --hotwords / --lm (beam hypotheses carry no time spans)")
     if sv_beam and not 1 <= nbest <= a.beam <= 16:
         raise SystemExit("--family sensevoice: --beam 1..16 and --nbest 1..beam (got --beam %d --nbest %d)" % (a.beam, nbest))
     dec_hot_file, dec_hot_boost = getattr(a, "decoder_hotwords", None), getattr(a, "decoder_hotword_boost", 2.0)
@@ -108,13 +115,15 @@ def run(a) -> dict:
             tr = mod.SenseVoiceTranscriber(a.model, target_language=a.language, tokenizer_path=a.tokenizer, device_type="cuda")
         else:
             tr = mod.ParaformerTranscriber(a.model, vocab_path=a.tokenizer, device_type="cuda")
+        lm = tr.load_lm(lm_file) if lm_file else None
         for p in a.wav:
             pcm = audio_io.read_wav_int16(p, tr.sample_rate, exact_width=a.strict_wav)
             if timestamps:
                 r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=True)
             elif sv_beam:
                 r = tr.transcribe(pcm, sliding_window=a.sliding_window, beam_size=a.beam, nbest=nbest, hotwords=parse_hotword_file(hot_file) if hot_file else None,
-                                  hotword_boost=getattr(a, "hotword_boost", 2.0))
+                                  hotword_boost=getattr(a, "hotword_boost", 2.0), lm=lm, lm_weight=0.5 if lm_weight is None else lm_weight,
+                                  length_bonus=0.0 if length_bonus is None else length_bonus)
             else:
                 r = tr.transcribe(pcm, sliding_window=a.sliding_window)
             files.append({"path": p, "n_samples": int(pcm.size), "language": r.get("language", a.language),
@@ -271,6 +280,10 @@ def build_parser():
     r.add_argument("--nbest", type=int, default=1, help="SenseVoice: keep the N best hypotheses of every window in the dump (1..beam), with their scores")
     r.add_argument("--hotwords", metavar="FILE", help="SenseVoice: phrases the beam search favours, one per line: token ids, or text with --tokenizer")
     r.add_argument("--hotword-boost", type=float, default=2.0, help="SenseVoice: log-probability bonus per matched hotword token")
+    r.add_argument("--lm", metavar="FILE.arpa", help="SenseVoice: back-off n-gram language model (ARPA; words are token ids, or pieces with --tokenizer) fused "
+                        "into the beam search, which it implies")
+    r.add_argument("--lm-weight", type=float, default=None, help="SenseVoice: weight of the language model's log-probability (default 0.5)")
+    r.add_argument("--length-bonus", type=float, default=None, help="SenseVoice: bonus per token with --lm (default 0)")
     r.add_argument("--decoder-hotwords", metavar="FILE", help="Whisper, Qwen3-ASR: phrases the decoder favours (greedy, sampling and --beam alike), one per line: "
                         "token ids, or text with --tokenizer (boosted in both spellings, at the start of the text and inside it)")
     r.add_argument("--decoder-hotword-boost", type=float, default=2.0, help="Whisper, Qwen3-ASR: logit / log-probability bonus per matched hotword token")
