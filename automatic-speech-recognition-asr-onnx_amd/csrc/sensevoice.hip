@@ -521,6 +521,9 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
     launch_compact_rows(x2_own, own_plan, tplan, r.batch, d, dec, stream);
   }
   save_tap("alphas", d_alpha.ptr, rows, 1, 1, 4);
+  if (taps_enabled) save_tap("acoustic", dec, rows, d, d, 4);          // the packed token rows; like `logits`, rows at or past *m_dev hold nothing defined
+  int tap_i = 0;
+  auto tap_layer = [&] { if (taps_enabled) save_tap(("dec" + std::to_string(tap_i++)).c_str(), dec, rows, d, d, 4); };
   auto ffn_block = [&](const PfDecLayer& L, float* out, const float* res) {
     { ProfScope ps(prof, "layernorm", stream); launch_layernorm<T>(dec, d, rows, d, nullptr, nullptr, 1e-5f, h, d, d, stream, m_dev); }
     ProfScope ps(prof, "gemm_dec", stream);
@@ -547,7 +550,7 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
   }
   int full_i = 0;
   for (const PfDecLayer& L : pdec) {
-    if (!L.full) { ffn_block(L, dec, nullptr); continue; }           // decoders3: dec = FFN(dec), no residual (:553-555)
+    if (!L.full) { ffn_block(L, dec, nullptr); tap_layer(); continue; }           // decoders3: dec = FFN(dec), no residual (:553-555)
     T* ck_l = kv_all ? ck + (size_t)full_i * d : ck;
     T* cvt_l = kv_all ? cvt + (size_t)full_i * d * Mpad : cvt;
     ++full_i;
@@ -589,6 +592,7 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
       g.A = ctx; g.lda = d; g.W = L.wo; g.ldw = d; g.M = rows; g.N = d; g.K = d; g.bias = L.bo; g.add = x2; g.ld_add = d; g.out_f32 = dec; g.ld_out_f32 = d; g.m_dev = m_dev;
       gemm(g);
     }
+    tap_layer();
   }
   { ProfScope ps(prof, "layernorm", stream); launch_layernorm<T>(dec, d, rows, d, nullptr, nullptr, 1e-5f, h, d, d, stream, m_dev); }
   {

@@ -516,7 +516,9 @@ int asr_session_profile_read(asr_session* s, int cap, char* names, double* total
 
 /* Debug taps (the reference's decode graphs expose no logits; the 1e-3 logit check needs one).
  * enable before a run; read copies the named f32 tensor of the LAST run to host.
- * names: "mel" "enc_in" "block0" "enc_out" "logits" "frame_ids"(i32); timed Paraformer runs add "fire_frames"(i32) "token_logprob" ([utterances][max_tokens]) */
+ * names: "mel" "enc_in" "block0" "enc_out" "logits" "frame_ids"(i32); timed Paraformer runs add "fire_frames"(i32) "token_logprob" ([utterances][max_tokens]);
+ * offline Paraformer runs add "alphas" and, on the packed token rows like "logits" (rows at or past the device-side count hold nothing defined),
+ * "acoustic" (the CIF output) and "dec0" .. (the rows behind each decoder layer, full layers first, then the decoders3 ones) */
 int asr_session_taps_enable(asr_session* s, int enable);
 int asr_session_tap_shape(asr_session* s, const char* name, int64_t* rows, int64_t* cols);
 int asr_session_tap_read(asr_session* s, const char* name, void* host_out, size_t bytes);
