@@ -72,6 +72,9 @@ SIGNATURES = {
     "asr_paraformer_create": (_i, [C.POINTER(ParaformerConfigC), _vp, _sz, _i, _i, _i, C.POINTER(_vp)]),
     "asr_paraformer_run": (_i, [_vp, _vp, _i, _lp, _i, _ip, _i, _ip]),
     "asr_paraformer_run_timed": (_i, [_vp, _vp, _i, _lp, _i, _ip, _i, _ip, _ip, _fp]),
+    "asr_paraformer_run_beam": (_i, [_vp, _vp, _i, _lp, _i, _i, _i, _i, _ip, _i, _ip, _fp, _fp, _ip, _fp]),
+    "asr_paraformer_set_hotwords": (_i, [_vp, _ip, _ip, _i, C.c_float]),
+    "asr_paraformer_set_lm": (_i, [_vp, _ip, C.c_int64, C.c_float, C.c_float, C.c_float]),
     "asr_paraformer_stream_create": (_i, [C.POINTER(ParaformerConfigC), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "asr_paraformer_stream_reset": (_i, [_vp, _i]),
     "asr_paraformer_stream_step": (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _ip]),
@@ -136,6 +139,8 @@ SIGNATURES = {
     "asr_op_ctc_prefix_beam": (_i, [_ip, _fp, _i, _ip, _i, _i, _ip, _ip, _ip, _ip, _ip, _i, C.c_float, _i, _i, _ip, _i, _ip, _fp, _fp]),
     "asr_op_ctc_prefix_beam_lm": (_i, [_ip, _fp, _i, _ip, _i, _i, _ip, _ip, _ip, _ip, _ip, _i, C.c_float, _i, _i, _ip, _i, _ip, _fp, _fp, _ip, C.c_int64, C.c_float,
                                        C.c_float, C.c_float]),
+    "asr_op_nar_beam": (_i, [_ip, _fp, _i, _ip, _i, _ip, _ip, _ip, _ip, _ip, _i, C.c_float, _ip, C.c_int64, C.c_float, C.c_float, C.c_float, _i, _i, _ip, _i, _ip,
+                             _fp, _fp, _fp]),
     "asr_op_ctc_align": (_i, [_fp, _i, _ip, _i, _i, _ip, _ip, _ip, _ip, _fp, _i, _fp, _fp, _ip]),
     "asr_op_cif_scan_timed": (_i, [_fp, _fp, _i, _ip, _i, C.c_float, _fp, _ip, _i, _ip]),
 }

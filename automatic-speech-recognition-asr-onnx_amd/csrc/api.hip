@@ -443,6 +443,34 @@ extern "C" int asr_op_ctc_collapse_timed(const int32_t* frame_ids, const float* 
 }
 
 namespace {
+// the hotword trie arrays of the host-array searches: a tree in the documented layout -- every node but the root is the child of exactly one node, one level below it
+void require_trie(const char* who, const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
+                  const int32_t* trie_child_node, int n_nodes, int blank_id) {
+  ASR_REQUIRE(n_nodes >= 0 && (n_nodes <= 1 || (trie_depth && trie_is_end && trie_child_off && trie_child_tok && trie_child_node)), "%s: trie arrays missing", who);
+  if (n_nodes <= 1) return;
+  ASR_REQUIRE(trie_child_off[0] == 0 && trie_child_off[n_nodes] == n_nodes - 1 && trie_depth[0] == 0, "%s: malformed trie", who);
+  for (int n = 0; n < n_nodes; ++n) {
+    ASR_REQUIRE(trie_child_off[n] <= trie_child_off[n + 1], "%s: malformed trie (child_off)", who);
+    for (int e = trie_child_off[n]; e < trie_child_off[n + 1]; ++e) {
+      const int ch = trie_child_node[e];
+      ASR_REQUIRE(ch > 0 && ch < n_nodes && trie_depth[ch] == trie_depth[n] + 1 && trie_child_tok[e] != blank_id && (e == trie_child_off[n] || trie_child_tok[e - 1] < trie_child_tok[e]),
+                  "%s: malformed trie (node %d, child entry %d)", who, n, e);
+    }
+  }
+}
+// ... and their device copy (t keeps it alive)
+HotTrie upload_trie(Tmp& t, const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node,
+                    int n_nodes, float boost) {
+  if (n_nodes <= 1) return HotTrie{};
+  std::vector<int32_t> img;
+  img.insert(img.end(), trie_depth, trie_depth + n_nodes); img.insert(img.end(), trie_is_end, trie_is_end + n_nodes);
+  img.insert(img.end(), trie_child_off, trie_child_off + n_nodes + 1); img.insert(img.end(), trie_child_tok, trie_child_tok + n_nodes - 1);
+  img.insert(img.end(), trie_child_node, trie_child_node + n_nodes - 1);
+  int32_t* dtrie = (int32_t*)t.alloc(img.size() * 4);
+  HIP_CHECK(hipMemcpy(dtrie, img.data(), img.size() * 4, hipMemcpyHostToDevice));
+  return hot_trie_view(dtrie, n_nodes, boost);
+}
+
 // both host-array entries of the search; lm_image null: without a language model
 int op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id, const int32_t* trie_depth,
                        const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node, int n_nodes, float boost,
@@ -452,18 +480,7 @@ int op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int to
     ASR_REQUIRE(cand_id && cand_logprob && seq_lens && token_ids && num_id && score && ctc_score && batch > 0 && max_tokens > 0, "op_ctc_prefix_beam: bad argument");
     ASR_REQUIRE(topk >= 1 && topk <= 16 && beam >= 1 && beam <= 16 && nbest >= 1 && nbest <= beam, "op_ctc_prefix_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)",
                 beam, topk, nbest);
-    ASR_REQUIRE(n_nodes >= 0 && (n_nodes <= 1 || (trie_depth && trie_is_end && trie_child_off && trie_child_tok && trie_child_node)), "op_ctc_prefix_beam: trie arrays missing");
-    if (n_nodes > 1) {                                   // a tree in the documented layout: every node but the root is the child of exactly one node, one level below it
-      ASR_REQUIRE(trie_child_off[0] == 0 && trie_child_off[n_nodes] == n_nodes - 1 && trie_depth[0] == 0, "op_ctc_prefix_beam: malformed trie");
-      for (int n = 0; n < n_nodes; ++n) {
-        ASR_REQUIRE(trie_child_off[n] <= trie_child_off[n + 1], "op_ctc_prefix_beam: malformed trie (child_off)");
-        for (int e = trie_child_off[n]; e < trie_child_off[n + 1]; ++e) {
-          const int ch = trie_child_node[e];
-          ASR_REQUIRE(ch > 0 && ch < n_nodes && trie_depth[ch] == trie_depth[n] + 1 && trie_child_tok[e] != blank_id && (e == trie_child_off[n] || trie_child_tok[e - 1] < trie_child_tok[e]),
-                      "op_ctc_prefix_beam: malformed trie (node %d, child entry %d)", n, e);
-        }
-      }
-    }
+    require_trie("op_ctc_prefix_beam", trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, blank_id);
     if (lm_image) {                                      // the image, then every id the walk will look up
       ngram_lm_validate(lm_image, lm_words, lm_words >= NGRAM_LM_HEADER ? lm_image[3] : 0, blank_id, alpha, beta, oov_logprob, "op_ctc_prefix_beam_lm");
       int64_t rows = 0;
@@ -496,16 +513,7 @@ int op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int to
     HIP_CHECK(hipMemcpy(dids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dlp, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dplan, pp.plan.data(), sizeof(UttPlan) * batch, hipMemcpyHostToDevice));
-    HotTrie trie;
-    if (n_nodes > 1) {
-      std::vector<int32_t> img;
-      img.insert(img.end(), trie_depth, trie_depth + n_nodes); img.insert(img.end(), trie_is_end, trie_is_end + n_nodes);
-      img.insert(img.end(), trie_child_off, trie_child_off + n_nodes + 1); img.insert(img.end(), trie_child_tok, trie_child_tok + n_nodes - 1);
-      img.insert(img.end(), trie_child_node, trie_child_node + n_nodes - 1);
-      int32_t* dtrie = (int32_t*)t.alloc(img.size() * 4);
-      HIP_CHECK(hipMemcpy(dtrie, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-      trie = hot_trie_view(dtrie, n_nodes, boost);
-    }
+    const HotTrie trie = upload_trie(t, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost);
     const int pool_stride = max_T * beam;
     int2* dpool = (int2*)t.alloc((size_t)batch * pool_stride * sizeof(int2));
     const size_t hyps = (size_t)batch * nbest;
@@ -545,6 +553,84 @@ extern "C" int asr_op_ctc_prefix_beam_lm(const int32_t* cand_id, const float* ca
   if (!lm_image) return asr_guard([&] { ASR_REQUIRE(false, "op_ctc_prefix_beam_lm: no language model image"); });
   return op_ctc_prefix_beam(cand_id, cand_logprob, topk, seq_lens, batch, blank_id, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost,
                             beam, nbest, token_ids, max_tokens, num_id, score, ctc_score, lm_image, lm_words, alpha, beta, oov_logprob);
+}
+
+// The beam search over token rows on host arrays. The rows go up in the layout of the compact token plan (16-row aligned per sequence, an empty sequence keeps
+// one dummy row), with the total row count on the device, as the Paraformer session hands them to the kernel.
+extern "C" int asr_op_nar_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, const int32_t* trie_depth,
+                               const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node, int n_nodes,
+                               float boost, const int32_t* lm_image, int64_t lm_words, float alpha, float beta, float oov_logprob, int beam, int nbest,
+                               int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* am_score, float* token_logprob) {
+  return asr_guard([&] {
+    ASR_REQUIRE(cand_id && cand_logprob && seq_lens && token_ids && num_id && score && am_score && batch > 0 && max_tokens > 0, "op_nar_beam: bad argument");
+    ASR_REQUIRE(topk >= 1 && topk <= 16 && beam >= 1 && beam <= 16 && nbest >= 1 && nbest <= beam, "op_nar_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)", beam, topk,
+                nbest);
+    require_trie("op_nar_beam", trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, -1);
+    int64_t n_rows = 0;
+    for (int b = 0; b < batch; ++b) {
+      ASR_REQUIRE(seq_lens[b] >= 0, "op_nar_beam: sequence %d has %d rows", b, seq_lens[b]);
+      n_rows += seq_lens[b];
+    }
+    if (lm_image) {                                      // the image ("no blank"), then every id the walk will look up
+      ngram_lm_validate(lm_image, lm_words, lm_words >= NGRAM_LM_HEADER ? lm_image[3] : 0, -1, alpha, beta, oov_logprob, "op_nar_beam");
+      for (int64_t i = 0; i < n_rows * topk; ++i)
+        ASR_REQUIRE(cand_logprob[i] == -INFINITY || (cand_id[i] >= 0 && cand_id[i] < lm_image[3]), "op_nar_beam: candidate %d outside the model's vocabulary of %d", cand_id[i],
+                    lm_image[3]);
+    }
+    asr_require_device(0);
+    Tmp t;
+    std::vector<UttPlan> plan(batch);
+    int rows = 0, max_N = 1;
+    for (int b = 0; b < batch; ++b) {
+      memset(&plan[b], 0, sizeof(UttPlan));
+      plan[b].n_lfr = seq_lens[b]; plan[b].T = std::max(seq_lens[b], 1); plan[b].row_off = rows;
+      rows += round_up(plan[b].T, 16);
+      max_N = std::max(max_N, seq_lens[b]);
+    }
+    std::vector<int32_t> ids((size_t)rows * topk, 0);
+    std::vector<float> lp((size_t)rows * topk, 0.0f);
+    size_t r = 0;
+    for (int b = 0; b < batch; ++b) {
+      const size_t n = (size_t)seq_lens[b] * topk;
+      for (int q = 0; q < seq_lens[b]; ++q)
+        for (int i = 0; i < topk; ++i)
+          for (int j = 0; j < i; ++j)
+            ASR_REQUIRE(cand_id[(r + q) * topk + i] != cand_id[(r + q) * topk + j], "op_nar_beam: sequence %d row %d lists token %d twice", b, q, cand_id[(r + q) * topk + i]);
+      memcpy(&ids[(size_t)plan[b].row_off * topk], cand_id + r * topk, n * 4);
+      memcpy(&lp[(size_t)plan[b].row_off * topk], cand_logprob + r * topk, n * 4);
+      r += seq_lens[b];
+    }
+    int32_t* dids = (int32_t*)t.alloc(ids.size() * 4);
+    float* dlp = (float*)t.alloc(lp.size() * 4);
+    UttPlan* dplan = (UttPlan*)t.alloc(sizeof(UttPlan) * batch);
+    int32_t* dm = (int32_t*)t.alloc(4);
+    HIP_CHECK(hipMemcpy(dids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dlp, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dplan, plan.data(), sizeof(UttPlan) * batch, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dm, &rows, 4, hipMemcpyHostToDevice));
+    const HotTrie trie = upload_trie(t, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost);
+    const int pool_stride = max_N * beam;
+    int2* dpool = (int2*)t.alloc((size_t)batch * pool_stride * sizeof(int2));
+    const size_t hyps = (size_t)batch * nbest;
+    int32_t* dtok = (int32_t*)t.alloc(hyps * max_tokens * 4);
+    float* dtlp = (float*)t.alloc(hyps * max_tokens * 4);
+    int32_t* dnum = (int32_t*)t.alloc(hyps * 4);
+    float* dsc = (float*)t.alloc(hyps * 4);
+    float* dam = (float*)t.alloc(hyps * 4);
+    NgramLm lm;
+    if (lm_image) {
+      int32_t* dlm = (int32_t*)t.alloc((size_t)lm_words * 4);
+      HIP_CHECK(hipMemcpy(dlm, lm_image, (size_t)lm_words * 4, hipMemcpyHostToDevice));
+      lm = ngram_lm_view(dlm, lm_image, alpha, beta, oov_logprob);
+    }
+    launch_nar_beam(dids, dlp, topk, dplan, dm, batch, beam, nbest, trie, dpool, pool_stride, dtok, max_tokens, dnum, dsc, dam, dtlp, nullptr, &lm);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(token_ids, dtok, hyps * max_tokens * 4, hipMemcpyDeviceToHost));
+    if (token_logprob) HIP_CHECK(hipMemcpy(token_logprob, dtlp, hyps * max_tokens * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(num_id, dnum, hyps * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(score, dsc, hyps * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(am_score, dam, hyps * 4, hipMemcpyDeviceToHost));
+  });
 }
 
 extern "C" int asr_op_ctc_align(const float* em, int ld_em, const int32_t* seq_lens, int batch, int row0, const int32_t* target_ids, const int32_t* target_offsets,

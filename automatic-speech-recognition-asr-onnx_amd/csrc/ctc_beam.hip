@@ -28,14 +28,22 @@ __device__ __forceinline__ void wave_best(float& v, int& i) {        // (higher 
   }
 }
 
-template <typename T>
+// kDev (the token rows of the Paraformer decoder, nar_beam.hip): the row count is known on the device only. Rows at or past *m_dev were never computed and
+// their partials hold nothing defined: a wave there repeats the last computed row, like a wave past M, and stores nothing. The kDev = false instantiation is
+// the kernel as it was; its (empty) last argument is never read.
+struct TopkHostRows {};
+struct TopkDevRows { const int32_t* m_dev; };
+template <typename T, bool kDev>
 __global__ __launch_bounds__(64 * TOPK_ROWS) void ctc_topk_kernel(const T* __restrict__ h, int ldh, const T* __restrict__ W, int ldw, const float* __restrict__ bias,
-                                                                  int K, const float* __restrict__ amax_val, const float* __restrict__ amax_sum, int n_slabs, int M,
-                                                                  int n_valid, int topk, int32_t* __restrict__ cand_id, float* __restrict__ cand_lp) {
+                                                                  int K, const float* __restrict__ amax_val, const float* __restrict__ amax_sum, int n_slabs, int M_host,
+                                                                  int n_valid, int topk, int32_t* __restrict__ cand_id, float* __restrict__ cand_lp,
+                                                                  typename std::conditional<kDev, TopkDevRows, TopkHostRows>::type dev_rows) {
   extern __shared__ float topk_lds[];                 // [TOPK_ROWS][K] activation rows, then [TOPK_ROWS][16][64] slab logits
   __shared__ int sel[TOPK_ROWS][16];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m_raw = blockIdx.x * TOPK_ROWS + wv;
+  int M = M_host;
+  if constexpr (kDev) M = max(min(M_host, *dev_rows.m_dev), 1);      // (the compact token plan has at least 16 rows)
   const int m = min(m_raw, M - 1);                    // (a wave past the last row repeats it and stores nothing: every wave reaches the barriers)
   float* hs = topk_lds + (size_t)wv * K;
   float* vals = topk_lds + (size_t)TOPK_ROWS * K + (size_t)wv * 16 * 64;
@@ -286,16 +294,20 @@ __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const
 
 template <typename T>
 void launch_ctc_topk(const T* h, int ldh, const T* W, int ldw, const float* bias, int K, const float* amax_val, const float* amax_sum, int n_slabs, int M,
-                     int n_valid, int topk, int32_t* cand_id, float* cand_lp, hipStream_t s) {
+                     int n_valid, int topk, int32_t* cand_id, float* cand_lp, hipStream_t s, const int32_t* m_dev) {
   ASR_REQUIRE(topk >= 1 && topk <= 16 && topk <= n_valid && n_valid <= n_slabs * 64, "ctc_topk: topk %d of %d valid columns (1..16)", topk, n_valid);
   ASR_REQUIRE(K % 8 == 0 && K <= 2048 && (ldw * sizeof(T)) % 16 == 0 && M > 0, "ctc_topk: K = %d, ldw = %d", K, ldw);
   const size_t lds = ((size_t)TOPK_ROWS * K + (size_t)TOPK_ROWS * 16 * 64) * 4;
-  hipLaunchKernelGGL(ctc_topk_kernel<T>, dim3((M + TOPK_ROWS - 1) / TOPK_ROWS), dim3(64 * TOPK_ROWS), lds, s, h, ldh, W, ldw, bias, K, amax_val, amax_sum, n_slabs, M,
-                     n_valid, topk, cand_id, cand_lp);
+  if (m_dev)
+    hipLaunchKernelGGL((ctc_topk_kernel<T, true>), dim3((M + TOPK_ROWS - 1) / TOPK_ROWS), dim3(64 * TOPK_ROWS), lds, s, h, ldh, W, ldw, bias, K, amax_val, amax_sum, n_slabs,
+                       M, n_valid, topk, cand_id, cand_lp, TopkDevRows{m_dev});
+  else
+    hipLaunchKernelGGL((ctc_topk_kernel<T, false>), dim3((M + TOPK_ROWS - 1) / TOPK_ROWS), dim3(64 * TOPK_ROWS), lds, s, h, ldh, W, ldw, bias, K, amax_val, amax_sum, n_slabs,
+                       M, n_valid, topk, cand_id, cand_lp, TopkHostRows{});
   HIP_CHECK(hipGetLastError());
 }
-template void launch_ctc_topk<float>(const float*, int, const float*, int, const float*, int, const float*, const float*, int, int, int, int, int32_t*, float*, hipStream_t);
-template void launch_ctc_topk<bf16_t>(const bf16_t*, int, const bf16_t*, int, const float*, int, const float*, const float*, int, int, int, int, int32_t*, float*, hipStream_t);
+template void launch_ctc_topk<float>(const float*, int, const float*, int, const float*, int, const float*, const float*, int, int, int, int, int32_t*, float*, hipStream_t, const int32_t*);
+template void launch_ctc_topk<bf16_t>(const bf16_t*, int, const bf16_t*, int, const float*, int, const float*, const float*, int, int, int, int, int32_t*, float*, hipStream_t, const int32_t*);
 
 void launch_ctc_prefix_beam(const int32_t* cand_id, const float* cand_lp, int topk, const UttPlan* plan, int n_utts, int blank_id, int beam, int nbest,
                             const HotTrie& trie, int2* pool, int pool_stride, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score,

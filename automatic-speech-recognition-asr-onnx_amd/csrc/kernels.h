@@ -430,10 +430,11 @@ std::vector<int32_t> build_hot_trie(const int32_t* ids, const int32_t* offsets, 
 HotTrie hot_trie_view(const int32_t* dev_words, int n_nodes, float boost);
 // Per row the `topk` (1..16) best columns n < n_valid of h W^T + bias and their log soft-max, from the per-slab partials of the timed CTC head (amax_val /
 // amax_sum [M][n_slabs], 64-column slabs): only the topk slabs with the largest maxima are recomputed (f32 accumulation from the operand type T).
-// cand_id / cand_lp [M][topk], higher value first, lower id on ties.
+// cand_id / cand_lp [M][topk], higher value first, lower id on ties. m_dev (Paraformer's token rows; null: every row < M): a device-side row count -- rows at
+// or past *m_dev are neither read nor written (their partials hold nothing defined).
 template <typename T>
 void launch_ctc_topk(const T* h, int ldh, const T* W, int ldw, const float* bias, int K, const float* amax_val, const float* amax_sum, int n_slabs, int M,
-                     int n_valid, int topk, int32_t* cand_id, float* cand_lp, hipStream_t s);
+                     int n_valid, int topk, int32_t* cand_id, float* cand_lp, hipStream_t s, const int32_t* m_dev = nullptr);
 // The search, one workgroup per utterance over rows plan[u].row_off .. + T of the candidate arrays. pool: [n_utts][pool_stride] (parent, token) nodes,
 // pool_stride >= max T * beam. Outputs [n_utts][nbest] (token_ids [n_utts][nbest][max_tokens], best first; num_id keeps the full length); hypotheses beyond the
 // number found have num_id 0 and score -inf. lm (ngram_lm.h; null or without nodes: none): a back-off n-gram model fused into the ranking; score
@@ -442,6 +443,16 @@ struct NgramLm;
 void launch_ctc_prefix_beam(const int32_t* cand_id, const float* cand_lp, int topk, const UttPlan* plan, int n_utts, int blank_id, int beam, int nbest,
                             const HotTrie& trie, int2* pool, int pool_stride, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score,
                             hipStream_t s, const NgramLm* lm = nullptr);
+
+// ---- beam search over the token rows of a non-autoregressive decoder (nar_beam.hip)
+// One workgroup per utterance over rows token_plan[u].row_off .. + token_plan[u].n_lfr of the candidate arrays (the compact token plan of the CIF scan; the
+// count is read on the device and cut at *m_dev when m_dev is given). Every hypothesis picks one candidate per row. pool: [n_utts][pool_stride] (parent rank,
+// candidate column) nodes, pool_stride >= max n_lfr * beam. Outputs [n_utts][nbest], best first: token_ids / token_logprob (nullable) [n_utts][nbest][max_tokens],
+// num_id the token count, score = acoustic + hotword bonus + lm, am_score = the sum of the picked candidates' log-probabilities; hypotheses beyond the number
+// found have num_id 0 and both scores -inf. trie / lm as launch_ctc_prefix_beam takes them.
+void launch_nar_beam(const int32_t* cand_id, const float* cand_lp, int topk, const UttPlan* token_plan, const int32_t* m_dev, int n_utts, int beam, int nbest,
+                     const HotTrie& trie, int2* pool, int pool_stride, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* am_score,
+                     float* token_logprob, hipStream_t s, const NgramLm* lm = nullptr);
 
 // ---- CTC forced alignment of a given transcript (ctc_align.hip)
 // Emissions: for every row m < M with u = row_utt[m] >= 0, em[m][j] = log soft-max of h W^T + bias at slot j's column -- slot 0 the blank, slot j = 1 .. L_u

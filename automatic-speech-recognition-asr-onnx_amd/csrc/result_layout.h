@@ -5,6 +5,7 @@
 //   SenseVoice timed   ... [first][last][logprob]      (n x max_tokens each)
 //   Paraformer timed   ... [first][logprob]            (offline: fire rows, streaming: fire steps; one layout for both)
 //   SenseVoice beam    ... [beam block: hyp_tokens n nbest x max_tokens][hyp_counts n nbest][hyp_scores n nbest][hyp_ctc n nbest]
+//   Paraformer beam    ... [first: the fire rows][beam block: the four sections above, hyp_ctc holding the acoustic score, then hyp_logprob n nbest x max_tokens]
 //   SenseVoice align   ... [first][last][logprob][path_score n][loglik n][align_status n]      (max_tokens = the longest transcript, at least 1)
 // The beam block is a layout of its own: the device-side block the beam kernel writes has the same four sections from offset 0 and comes home in one copy.
 #pragma once
@@ -12,7 +13,7 @@
 
 #include "plan_layout.h"
 
-enum class ResultForm { PLAIN, SV_TIMED, PF_TIMED, SV_BEAM, SV_ALIGN };
+enum class ResultForm { PLAIN, SV_TIMED, PF_TIMED, SV_BEAM, SV_ALIGN, PF_BEAM };
 
 template <typename T> struct ResultSection { int i = -1; bool in_beam = false; };      // i < 0: the form has no such section
 
@@ -21,8 +22,8 @@ struct ResultLayout {
   size_t n_rows, max_tokens;
   ResultSection<int32_t> tokens, counts, first, last, hyp_tokens, hyp_counts, align_status;
   ResultSection<uint32_t> status;
-  ResultSection<float> logprob, hyp_scores, hyp_ctc, path_score, loglik;
-  ResultSection<unsigned char> beam;                     // the four hyp_* sections as one
+  ResultSection<float> logprob, hyp_scores, hyp_ctc, hyp_logprob, path_score, loglik;
+  ResultSection<unsigned char> beam;                     // the hyp_* sections as one
   ResultLayout(size_t n, size_t max_tok, ResultForm form, size_t nbest = 1) : n_rows(n), max_tokens(max_tok) {
     const size_t toks = n * max_tok, hyps = n * nbest;
     tokens.i = lay.add(4, 4, toks);
@@ -34,11 +35,13 @@ struct ResultLayout {
     if (spans) last.i = lay.add(4, 4, toks);
     if (spans || form == ResultForm::PF_TIMED) logprob.i = lay.add(4, 4, toks);
     if (form == ResultForm::SV_ALIGN) { path_score.i = lay.add(4, 4, n); loglik.i = lay.add(4, 4, n); align_status.i = lay.add(4, 4, n); }
-    if (form != ResultForm::SV_BEAM) return;
+    if (form == ResultForm::PF_BEAM) first.i = lay.add(4, 4, toks);
+    if (form != ResultForm::SV_BEAM && form != ResultForm::PF_BEAM) return;
     hyp_tokens = {beam_lay.add(4, 4, hyps * max_tok), true};
     hyp_counts = {beam_lay.add(4, 4, hyps), true};
     hyp_scores = {beam_lay.add(4, 4, hyps), true};
     hyp_ctc = {beam_lay.add(4, 4, hyps), true};
+    if (form == ResultForm::PF_BEAM) hyp_logprob = {beam_lay.add(4, 4, hyps * max_tok), true};
     beam.i = lay.add(1, 4, beam_lay.total);
   }
   size_t total() const { return lay.total; }             // what the pinned buffer is reserved for

@@ -25,10 +25,11 @@ struct PfDecLayer {
   bool full;     // false: FFN-only block (decoders3)
 };
 
-// What a call asks for. PLAIN: ids and counts; TIMED: also per-token times and log-probabilities; BEAM (SenseVoice): n-best hypotheses with scores;
-// ALIGN (SenseVoice): the spans and scores of a transcript the caller supplies.
+// What a call asks for. PLAIN: ids and counts; TIMED: also per-token times and log-probabilities; BEAM: n-best hypotheses with scores (SenseVoice: CTC prefix
+// beam search; Paraformer: beam search over the decoder's token rows, with the fire rows and per-token log-probabilities); ALIGN (SenseVoice): the spans and
+// scores of a transcript the caller supplies.
 enum class SvForm { PLAIN, TIMED, BEAM, ALIGN };
-struct SvRunReq {               // offline: asr_sensevoice_run / _run_timed / _run_beam / _align, asr_paraformer_run / _run_timed
+struct SvRunReq {               // offline: asr_sensevoice_run / _run_timed / _run_beam / _align, asr_paraformer_run / _run_timed / _run_beam
   SvForm form = SvForm::PLAIN;
   const void* audio = nullptr; int audio_mem = 0; const int64_t* offs = nullptr; int batch = 0;
   const int32_t* lang = nullptr;                        // SenseVoice only
@@ -37,7 +38,8 @@ struct SvRunReq {               // offline: asr_sensevoice_run / _run_timed / _r
   int32_t *first_out = nullptr, *last_out = nullptr;    // TIMED: SenseVoice frame spans; Paraformer: first_out = the CIF fire rows, no last_out
   float* logprob_out = nullptr;                         // TIMED
   int beam = 0, topk = 0, nbest = 0;                    // BEAM
-  float *score_out = nullptr, *ctc_out = nullptr;       // BEAM
+  float *score_out = nullptr, *ctc_out = nullptr;       // BEAM (Paraformer: ctc_out = the acoustic score)
+  float* hyp_logprob_out = nullptr;                     // Paraformer BEAM, nullable: [batch][nbest][max_tokens]; first_out (nullable) = the CIF fire rows [batch][max_tokens]
   // ALIGN: the transcripts (ragged: ids [sum L], offsets [batch + 1]); first_out / last_out / logprob_out are ragged in the same layout, no tok_out / num_out
   const int32_t *tgt_ids = nullptr, *tgt_off = nullptr;
   float *path_out = nullptr, *loglik_out = nullptr; int32_t* astatus_out = nullptr;      // [batch]
@@ -143,7 +145,8 @@ struct ASR_LOCAL SvSession : asr_session {
     else launch_gemm_bf16(g, stream);
   }
 
-  // ---- SenseVoice: CTC head, prefix beam search (asr_sensevoice_run_beam, ctc_beam.hip) -----------------------------------------------
+  // ---- SenseVoice: CTC head, prefix beam search (asr_sensevoice_run_beam, ctc_beam.hip); the beam buffers, hotwords and language model also serve
+  // Paraformer's beam search over token rows (asr_paraformer_run_beam, nar_beam.hip) ----------------------------------------------------
   const float *tp_g = nullptr, *tp_b = nullptr, *ctc_b = nullptr;
   const void* ctc_w = nullptr;
   // beam runs only: candidates [rows][topk], the (parent, token) node pool, the outputs as one block (result_layout.h: the beam block), the hotword trie image

@@ -512,7 +512,7 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
     launch_alpha<T>(ctx, d, cif_out_w, cif_out_b, rows, d_alpha.as<float>(), stream);
     // fired frames land in the utterance's own rows first; then they are packed (16-row aligned per utterance) so that the decoder
     // touches ~ the token count of the batch instead of every encoder row -- the count stays on the device (GemmArgs::m_dev)
-    if (r.timed)
+    if (r.timed || r.beam)                                   // (the beam form reports the fire rows too: every hypothesis of an utterance shares them)
       launch_cif_scan_timed(d_alpha.as<float>(), enc32, d, r.dp, r.batch, pcfg.tail_threshold, x2_own, own_plan, d_num.as<int32_t>(), d_first.as<int32_t>(),
                             r.max_tokens, stream);
     else
@@ -600,7 +600,7 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
     GemmArgs g;
     g.A = h; g.lda = d; g.W = pf_out_w; g.ldw = d; g.M = rows; g.N = vpad; g.K = d; g.bias = pf_out_b;
     g.amax_val = d_amax_v.as<float>(); g.amax_idx = d_amax_i.as<int32_t>(); g.n_valid = c.vocab; g.m_dev = m_dev;
-    if (r.timed) g.amax_sum = d_amax_s.as<float>();         // (rows at or past *m_dev are neither computed nor stored: the epilogue's row guard uses the device-side count)
+    if (r.timed || r.beam) g.amax_sum = d_amax_s.as<float>();         // (rows at or past *m_dev are neither computed nor stored: the epilogue's row guard uses the device-side count)
     if (taps_enabled) { g.out_f32 = d_logits.as<float>(); g.ld_out_f32 = vpad; }
     gemm(g);
     if (r.timed) {
@@ -609,10 +609,36 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
       launch_argmax_lse_reduce(d_amax_v.as<float>(), d_amax_i.as<int32_t>(), d_amax_s.as<float>(), rows, n_slabs, d_ids.as<int32_t>(), d_flp.as<float>(), stream);
       launch_gather_tokens(d_ids.as<int32_t>(), tplan, r.batch, d_tok.as<int32_t>(), r.max_tokens, stream);
       launch_gather_token_logprob(d_flp.as<float>(), tplan, r.batch, d_tlp.as<float>(), r.max_tokens, stream);
-    } else {
+    } else if (!r.beam) {                                    // (the beam form has no row arg-max: its candidates come from the partials, below)
       launch_argmax_reduce(d_amax_v.as<float>(), d_amax_i.as<int32_t>(), rows, n_slabs, d_ids.as<int32_t>(), stream);
       launch_gather_tokens(d_ids.as<int32_t>(), tplan, r.batch, d_tok.as<int32_t>(), r.max_tokens, stream);
     }
+  }
+  if (r.beam) {                                          // ---- beam search over the token rows
+    const ResultBlob& o = *r.out;
+    {
+      ProfScope ps(prof, "ctc_topk", stream);
+      launch_ctc_topk<T>(h, d, (const T*)pf_out_w, d, pf_out_b, d, d_amax_v.as<float>(), d_amax_s.as<float>(), n_slabs, rows, c.vocab, r.topk, d_cand_i.as<int32_t>(),
+                         d_cand_l.as<float>(), stream, m_dev);
+    }
+    {
+      ProfScope ps(prof, "nar_beam", stream);
+      NgramLm lm;                                         // (no nodes: the search without a model is launched)
+      if (lm_header[1] > 0) lm = ngram_lm_view(d_lm.as<int32_t>(), lm_header, lm_alpha, lm_beta, lm_oov);
+      launch_nar_beam(d_cand_i.as<int32_t>(), d_cand_l.as<float>(), r.topk, tplan, m_dev, r.batch, r.beam, r.nbest, hot_trie_view(d_hot.as<int32_t>(), hot_nodes, hot_boost),
+                      (int2*)d_pool.ptr, r.pool_stride, o.dev(o.lay.hyp_tokens, d_bout), r.max_tokens, o.dev(o.lay.hyp_counts, d_bout), o.dev(o.lay.hyp_scores, d_bout),
+                      o.dev(o.lay.hyp_ctc, d_bout), o.dev(o.lay.hyp_logprob, d_bout), stream, &lm);
+    }
+    if (taps_enabled) {                                   // (rows at or past *m_dev hold nothing defined, in all three)
+      save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
+      save_tap("cand_ids", d_cand_i.ptr, rows, r.topk, r.topk, 4);
+      save_tap("cand_logprob", d_cand_l.ptr, rows, r.topk, r.topk, 4);
+      save_tap("fire_frames", d_first.ptr, r.batch, r.max_tokens, r.max_tokens, 4);
+    }
+    o.enqueue_copy(o.lay.counts, d_num.ptr, stream);      // the fire counts: how much of each fire row is valid; the token section stays unused
+    o.enqueue_copy(o.lay.first, d_first.ptr, stream);
+    o.enqueue_copy(o.lay.beam, d_bout.ptr, stream);
+    return;
   }
   if (taps_enabled) {
     save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
@@ -629,11 +655,11 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
 
 void SvSession::validate(const SvRunReq& q) const {
   if (q.form == SvForm::BEAM) {
-    ASR_REQUIRE(!paraformer, "sensevoice_run_beam: not a SenseVoice session");
+    const char* who = paraformer ? "paraformer_run_beam" : "sensevoice_run_beam";
     ASR_REQUIRE(q.beam >= 1 && q.beam <= 16 && q.topk >= 1 && q.topk <= 16 && q.nbest >= 1 && q.nbest <= q.beam && q.topk <= cfg.vocab,
-                "sensevoice_run_beam: beam %d, topk %d, nbest %d (beam and topk 1..16, nbest 1..beam)", q.beam, q.topk, q.nbest);
-    ASR_REQUIRE(q.tok_out && q.num_out && q.score_out && q.ctc_out, "sensevoice_run_beam: null output");
-    ASR_REQUIRE(cfg.d_model <= 2048, "sensevoice_run_beam: d_model %d (the candidate kernel holds a row of 2048 at most)", cfg.d_model);
+                "%s: beam %d, topk %d, nbest %d (beam and topk 1..16, nbest 1..beam)", who, q.beam, q.topk, q.nbest);
+    ASR_REQUIRE(q.tok_out && q.num_out && q.score_out && q.ctc_out, "%s: null output", who);
+    ASR_REQUIRE(cfg.d_model <= 2048, "%s: d_model %d (the candidate kernel holds a row of 2048 at most)", who, cfg.d_model);
   }
   if (q.form == SvForm::ALIGN) {
     ASR_REQUIRE(!paraformer, "sensevoice_align: not a SenseVoice session");
@@ -735,7 +761,7 @@ void SvSession::run(const SvRunReq& q) {
   // ---- workspace (grow-only; any re-allocation invalidates the captured graph) -----------------
   const size_t eT = sizeof(T);
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { if (reserve_moved(buf, bytes, stream)) ++ws_epoch; };
-  ResultBlob out(h_out, ResultLayout(batch, max_tokens, bq ? ResultForm::SV_BEAM : al ? ResultForm::SV_ALIGN : !timed ? ResultForm::PLAIN : paraformer ? ResultForm::PF_TIMED : ResultForm::SV_TIMED, bq ? q.nbest : 1));
+  ResultBlob out(h_out, ResultLayout(batch, max_tokens, bq ? (paraformer ? ResultForm::PF_BEAM : ResultForm::SV_BEAM) : al ? ResultForm::SV_ALIGN : !timed ? ResultForm::PLAIN : paraformer ? ResultForm::PF_TIMED : ResultForm::SV_TIMED, bq ? q.nbest : 1));
   if (out.commit()) ++ws_epoch;
   r.out = &out;
   bool audio_moved = false;
@@ -777,8 +803,9 @@ void SvSession::run(const SvRunReq& q) {
     auto grow_beam = [&](DeviceBuffer& buf, size_t bytes) { if (reserve_moved(buf, bytes, stream)) ++beam_epoch; };
     grow(d_amax_s, (size_t)Mpad * n_slabs * 4);
     for (DeviceBuffer* b : {&d_cand_i, &d_cand_l}) grow_beam(*b, (size_t)Mpad * q.topk * 4);
-    grow_beam(d_pool, (size_t)batch * max_T * q.beam * sizeof(int2));
+    grow_beam(d_pool, (size_t)batch * (max_T + (paraformer ? 1 : 0)) * q.beam * sizeof(int2));      // (the CIF scan fires at most T + 1 tokens: the tail threshold is row T)
     grow_beam(d_bout, out.lay.bytes(out.lay.beam));
+    if (paraformer) grow(d_first, (size_t)batch * max_tokens * 4);
   }
   if (paraformer) {
     const int dd = pcfg.d_dec_ffn;
@@ -798,7 +825,7 @@ void SvSession::run(const SvRunReq& q) {
   r.max_tokens = max_tokens; r.att_qt = att_qt; r.att_nw = att_nw;
   r.dp = pb.dev(s_plan);
   r.n_tiles = n_tiles; r.tiles = tiles; r.timed = timed;
-  if (bq) { r.beam = q.beam; r.topk = q.topk; r.nbest = q.nbest; r.pool_stride = max_T * q.beam; }
+  if (bq) { r.beam = q.beam; r.topk = q.topk; r.nbest = q.nbest; r.pool_stride = (max_T + (paraformer ? 1 : 0)) * q.beam; }
   if (al) { r.align = true; r.max_L = max_L; r.ld_em = ld_em; r.d_tgt_ids = pb.dev(s_tgt_ids); r.d_tgt_off = pb.dev(s_tgt_off); }
   r.d_blk_utt = pb.dev(s_blk_utt); r.d_blk_f0 = pb.dev(s_blk_f0); r.d_qb_utt = pb.dev(s_qb_utt); r.d_qb_q0 = pb.dev(s_qb_q0);
   r.d_row_utt = pb.dev(s_row_utt); r.d_tile_win = pb.dev(s_tile_win); r.d_tile_idx = pb.dev(s_tile_idx);
@@ -859,6 +886,10 @@ void SvSession::run(const SvRunReq& q) {
     memcpy(q.score_out, out.host(L.hyp_scores), L.bytes(L.hyp_scores));
     memcpy(q.ctc_out, out.host(L.hyp_ctc), L.bytes(L.hyp_ctc));
     out.scatter_rows(L.hyp_tokens, q.tok_out, q.num_out, max_tokens);
+    if (paraformer) {                                    // the hypotheses' token log-probabilities, and the fire rows every hypothesis of an utterance shares
+      if (q.hyp_logprob_out) out.scatter_rows(L.hyp_logprob, q.hyp_logprob_out, q.num_out, max_tokens);
+      if (q.first_out) out.scatter_rows(L.first, q.first_out, out.host(L.counts), max_tokens);
+    }
     return;
   }
   if (al) {                                              // ragged, in the layout of the targets; an utterance without an alignment keeps the caller's fill
@@ -884,16 +915,16 @@ void SvSession::run(const SvRunReq& q) {
 }
 
 void SvSession::set_hotwords(const int32_t* ids, const int32_t* offsets, int n_phrases, float boost) {
-  ASR_REQUIRE(!paraformer, "sensevoice_set_hotwords: not a SenseVoice session");
-  ASR_REQUIRE(n_phrases >= 0 && (n_phrases == 0 || (ids && offsets)) && std::isfinite(boost), "sensevoice_set_hotwords: bad argument");
+  const char* who = paraformer ? "paraformer_set_hotwords" : "sensevoice_set_hotwords";      // (Paraformer has no blank: cfg.blank_id is -1 and no id is refused for it)
+  ASR_REQUIRE(n_phrases >= 0 && (n_phrases == 0 || (ids && offsets)) && std::isfinite(boost), "%s: bad argument", who);
   HIP_CHECK(hipSetDevice(device));
   if (n_phrases == 0) { hot_nodes = 0; hot_boost = 0.0f; ++beam_epoch; return; }
-  ASR_REQUIRE(offsets[0] >= 0, "sensevoice_set_hotwords: offsets[0] = %d", offsets[0]);
+  ASR_REQUIRE(offsets[0] >= 0, "%s: offsets[0] = %d", who, offsets[0]);
   for (int p = 0; p < n_phrases; ++p) {
-    ASR_REQUIRE(offsets[p + 1] > offsets[p], "sensevoice_set_hotwords: phrase %d is empty", p);
+    ASR_REQUIRE(offsets[p + 1] > offsets[p], "%s: phrase %d is empty", who, p);
     for (int32_t i = offsets[p]; i < offsets[p + 1]; ++i) {
-      ASR_REQUIRE(ids[i] >= 0 && ids[i] < cfg.vocab, "sensevoice_set_hotwords: phrase %d holds token %d (vocabulary %d)", p, ids[i], cfg.vocab);
-      ASR_REQUIRE(ids[i] != cfg.blank_id, "sensevoice_set_hotwords: phrase %d holds the blank id", p);
+      ASR_REQUIRE(ids[i] >= 0 && ids[i] < cfg.vocab, "%s: phrase %d holds token %d (vocabulary %d)", who, p, ids[i], cfg.vocab);
+      ASR_REQUIRE(ids[i] != cfg.blank_id, "%s: phrase %d holds the blank id", who, p);
     }
   }
   int n_nodes = 0;
@@ -908,11 +939,11 @@ void SvSession::set_hotwords(const int32_t* ids, const int32_t* offsets, int n_p
 
 // The image is checked in full before it replaces the one in force (a rejected image changes nothing); its words are graph-kernel operands like the trie's.
 void SvSession::set_lm(const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob) {
-  ASR_REQUIRE(!paraformer, "sensevoice_set_lm: not a SenseVoice session");
-  ASR_REQUIRE(n_words >= 0 && (n_words == 0 || image_words), "sensevoice_set_lm: bad argument");
+  const char* who = paraformer ? "paraformer_set_lm" : "sensevoice_set_lm";                  // (Paraformer: the image check is told "no blank", cfg.blank_id = -1)
+  ASR_REQUIRE(n_words >= 0 && (n_words == 0 || image_words), "%s: bad argument", who);
   HIP_CHECK(hipSetDevice(device));
   if (n_words == 0) { lm_header[1] = 0; lm_alpha = lm_beta = lm_oov = 0.0f; ++beam_epoch; return; }
-  ngram_lm_validate(image_words, n_words, cfg.vocab, cfg.blank_id, alpha, beta, oov_logprob, "sensevoice_set_lm");
+  ngram_lm_validate(image_words, n_words, cfg.vocab, cfg.blank_id, alpha, beta, oov_logprob, who);
   HIP_CHECK(hipStreamSynchronize(stream));
   d_lm.reserve((size_t)n_words * 4, stream);
   HIP_CHECK(hipMemcpyAsync(d_lm.ptr, image_words, (size_t)n_words * 4, hipMemcpyHostToDevice, stream));
@@ -1079,5 +1110,30 @@ extern "C" int asr_paraformer_run_timed(asr_session* s, const void* audio, int a
     SvRunReq q = run_req(SvForm::TIMED, audio, audio_mem, audio_offsets, batch, nullptr, token_ids_out, max_tokens, num_id_out);
     q.first_out = fire_frame_out; q.logprob_out = logprob_out;
     run_entry(s, q);
+  });
+}
+
+extern "C" int asr_paraformer_run_beam(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch, int beam, int topk, int nbest,
+                                       int32_t* token_ids_out, int max_tokens, int32_t* num_id_out, float* score_out, float* am_score_out, int32_t* fire_frame_out,
+                                       float* token_logprob_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 3, "paraformer_run_beam: not a Paraformer session");
+    SvRunReq q = run_req(SvForm::BEAM, audio, audio_mem, audio_offsets, batch, nullptr, token_ids_out, max_tokens, num_id_out);
+    q.beam = beam; q.topk = topk; q.nbest = nbest; q.score_out = score_out; q.ctc_out = am_score_out; q.first_out = fire_frame_out; q.hyp_logprob_out = token_logprob_out;
+    run_entry(s, q);
+  });
+}
+
+extern "C" int asr_paraformer_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 3, "paraformer_set_hotwords: not an offline Paraformer session");
+    static_cast<SvSession*>(s)->set_hotwords(ids, offsets, n_phrases, boost);
+  });
+}
+
+extern "C" int asr_paraformer_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 3, "paraformer_set_lm: not an offline Paraformer session");
+    static_cast<SvSession*>(s)->set_lm(image_words, n_words, alpha, beta, oov_logprob);
   });
 }

@@ -486,6 +486,37 @@ def op_ctc_prefix_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, blank_id=
     return tok, num, score, ctc
 
 
+def op_nar_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, trie=None, boost=0.0, max_tokens=None, lm=None, alpha=0.5, beta=0.0, oov_logprob=None,
+                vocab=None):
+    """The beam search over the token rows of a non-autoregressive decoder on host arrays (asr_op_nar_beam): cand_id / cand_logprob [sum N, topk], seq_lens the
+    token counts (0 is legal), `trie` as hotword_trie returns it, `lm` an lm.NgramLM (built for `vocab` ids) or an int32 image, or None. Returns (token_ids
+    [B, nbest, max_tokens], num_id [B, nbest], score [B, nbest], am_score [B, nbest], token_logprob [B, nbest, max_tokens]), best first; every hypothesis of a
+    sequence has its N tokens, hypotheses beyond the number found have num 0 and both scores -inf."""
+    ids = np.ascontiguousarray(cand_id, dtype=np.int32)
+    lp = _f32(cand_logprob)
+    sl = np.ascontiguousarray(seq_lens, dtype=np.int32)
+    assert ids.ndim == 2 and ids.shape == lp.shape and ids.shape[0] == int(sl.sum())
+    max_t = max(int(sl.max()), 1) if max_tokens is None else int(max_tokens)
+    tok = np.zeros((sl.size, nbest, max_t), dtype=np.int32)
+    tlp = np.zeros((sl.size, nbest, max_t), dtype=np.float32)
+    num = np.zeros((sl.size, nbest), dtype=np.int32)
+    score, am = np.zeros((sl.size, nbest), dtype=np.float32), np.zeros((sl.size, nbest), dtype=np.float32)
+    if trie is not None and trie["depth"].size > 1:
+        t = {k: np.ascontiguousarray(trie[k], dtype=np.int32) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")}
+        targs, n_nodes = [_ip(t[k]) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")], int(t["depth"].size)
+    else:
+        targs, n_nodes = [None] * 5, 0
+    if lm is not None:
+        img, oov = _lm_image(lm, vocab, oov_logprob)
+        largs = [_ip(img), img.size, float(alpha), float(beta), oov]
+    else:
+        largs = [None, 0, 0.0, 0.0, 0.0]
+    ids_c, lp_c = (ids, lp) if ids.size else (np.zeros((1, ids.shape[1]), np.int32), np.zeros((1, ids.shape[1]), np.float32))
+    _lib.check(_lib.load().asr_op_nar_beam(_ip(ids_c), _fp(lp_c), ids.shape[1], _ip(sl), sl.size, *targs, n_nodes, float(boost), *largs, int(beam), int(nbest),
+                                           _ip(tok), max_t, _ip(num), _fp(score), _fp(am), _fp(tlp)))
+    return tok, num, score, am, tlp
+
+
 def op_ctc_align(em, seq_lens, targets, row0=0, max_tokens=None, fill=None):
     """The forced-alignment trellis on host arrays (asr_op_ctc_align): em [sum T, ld] log-probabilities (slot 0 the blank, slot j target j - 1 of the row's
     sequence), `targets` one id list per sequence; each sequence is aligned against its rows row0 .. T - 1. Returns (first_frame, last_frame, token_logprob
@@ -891,6 +922,57 @@ class ParaformerSession(_Session):
         tok, num, fire, logprob = self.run_packed_timed(packed, offs)
         return [{"ids": tok[b, :num[b]].copy(), "fire_frame": fire[b, :num[b]].copy(), "logprob": logprob[b, :num[b]].copy()}
                 for b in range(len(flat))]
+
+    def set_hotwords(self, phrases: Sequence[Sequence[int]], boost: float = 2.0):
+        """Hotwords of run_beam (asr_paraformer_set_hotwords): token-id lists; a hypothesis gains `boost` per token while it spells one of them, and a partial
+        match gives its part back. An empty list clears them. Empty phrases and ids outside the vocabulary raise AsrError (this family has no blank id)."""
+        ids, offs = _flatten_phrases(phrases)
+        _lib.check(_lib.load().asr_paraformer_set_hotwords(self._h, _ip(ids), _ip(offs), len(phrases), float(boost)))
+
+    def set_lm(self, lm, alpha: float = 0.5, beta: float = 0.0, oov_logprob: float | None = None):
+        """The n-gram language model of run_beam (asr_paraformer_set_lm; shallow fusion), arguments as SenseVoiceSession.set_lm takes them: every token of a
+        hypothesis adds alpha * log P(token | history) + beta to its ranking score. None clears it; a malformed image or a bad weight raises AsrError and the
+        model in force stays."""
+        if lm is None:
+            _lib.check(_lib.load().asr_paraformer_set_lm(self._h, None, 0, 0.0, 0.0, 0.0))
+            return
+        img, oov = _lm_image(lm, self.cfg.vocab, oov_logprob)
+        _lib.check(_lib.load().asr_paraformer_set_lm(self._h, _ip(img), img.size, float(alpha), float(beta), oov))
+
+    def run_packed_beam(self, audio, offsets, beam: int, topk: int | None = None, nbest: int = 1, audio_device_ptr: int | None = None):
+        """run_packed with a beam search over the decoder's token rows instead of the per-row arg-max (asr_paraformer_run_beam): the `topk` (default: beam)
+        best tokens of every row, `beam` live hypotheses, the `nbest` best of them. Returns (token_ids [B, nbest, max_T] int32, num_id [B, nbest] int32, score
+        [B, nbest], am_score [B, nbest] float32, fire_frame [B, max_T] int32, logprob [B, nbest, max_T] float32), best first. Every hypothesis of utterance b
+        has its CIF fire count as length and shares row b of fire_frame; hypotheses beyond the number found have num 0 and score -inf."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        B = offsets.size - 1
+        topk = int(beam if topk is None else topk)
+        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        tok = np.zeros((B, nbest, max_t), dtype=np.int32)
+        logprob = np.zeros((B, nbest, max_t), dtype=np.float32)
+        fire = np.zeros((B, max_t), dtype=np.int32)
+        num = np.zeros((B, nbest), dtype=np.int32)
+        score, am = np.zeros((B, nbest), dtype=np.float32), np.zeros((B, nbest), dtype=np.float32)
+        if audio_device_ptr is not None:
+            ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
+        else:
+            audio = self._audio(audio).reshape(-1)
+            ap, mem = audio.ctypes.data_as(C.c_void_p), MEM_HOST
+        _lib.check(_lib.load().asr_paraformer_run_beam(self._h, ap, mem, offsets.ctypes.data_as(C.POINTER(C.c_int64)), B, int(beam), topk, int(nbest), _ip(tok), max_t,
+                                                       _ip(num), _fp(score), _fp(am), _ip(fire), _fp(logprob)))
+        return tok, num, score, am, fire, logprob
+
+    def run_beam(self, audios: Sequence[np.ndarray], beam: int, topk: int | None = None, nbest: int = 1):
+        """List of 1-D utterances -> per utterance (hyps, fire_frame): hyps the hypotheses found (at most nbest), best first, each {"tokens", "score",
+        "am_score", "logprob"}; fire_frame the utterance's CIF fire rows, one per token, shared by all of its hypotheses."""
+        flat, packed, offs = self._pack(audios)
+        tok, num, score, am, fire, logprob = self.run_packed_beam(packed, offs, beam, topk, nbest)
+        out = []
+        for b in range(len(flat)):
+            hyps = [{"tokens": tok[b, n, :num[b, n]].copy(), "score": float(score[b, n]), "am_score": float(am[b, n]), "logprob": logprob[b, n, :num[b, n]].copy()}
+                    for n in range(nbest) if np.isfinite(score[b, n])]
+            out.append((hyps, fire[b, :num[b, 0]].copy()))
+        return out
 
     def utterance_rows(self, lengths: Sequence[int]):
         out, r = [], 0

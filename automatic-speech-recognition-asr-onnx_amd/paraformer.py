@@ -6,6 +6,7 @@
   decode_tokens()       = Inference_Paraformer_ONNX.py:86-89 ("en": BPE "@@ " joins; otherwise plain concatenation)
   transcribe()          = :236-297 (window/pad, one pre-bound audio buffer updated in place, per-window run, stop ids stripped)
   token_times()         the build's own rule (no reference counterpart): CIF fire rows -> a (start, end) per token
+  transcribe(beam_size=, nbest=, hotwords=, lm=)   the build's own mode: n-best beam search over the decoder's token rows (ParaformerSession.run_beam)
 prepare_audio_input / plan_windows are the SenseVoice ones (identical code in the reference, :62-84, :243-259).
 """
 from __future__ import annotations
@@ -123,10 +124,76 @@ class ParaformerTranscriber:
                    "end": min(offset_s + float(spans[k, 1]), duration_s), "logprob": float(logprob[0, k])} for k in range(n)]
         return tok[0, :n].copy(), tokens
 
-    def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False, timestamps: bool = False, max_token_rows: int = 4):
+    def _hotword_ids(self, hotwords):
+        """Hotwords as token-id lists: id lists pass through; text is looked up in the vocabulary -- as one entry, else piece by piece ("en": the words
+        between blanks, otherwise the characters). A piece the vocabulary does not list is an error."""
+        index = None
+        out = []
+        for h in hotwords or []:
+            if isinstance(h, str):
+                if index is None:
+                    index = {str(t): i for i, t in reversed(list(enumerate(self.tokenizer.tolist())))}
+                text = h.strip()
+                pieces = [text] if text in index else text.split() if self.decode_mode == "en" else [c for c in text if not c.isspace()]
+                missing = [p for p in pieces if p not in index]
+                if missing or not pieces:
+                    raise ValueError(f"hotword {h!r}: not in the vocabulary: {missing}")
+                h = [index[p] for p in pieces]
+            out.append([int(t) for t in h])
+        return out
+
+    def load_lm(self, arpa_path):
+        """An ARPA file as lm.NgramLM: words are token ids, or entries of this transcriber's vocabulary."""
+        from .lm import NgramLM
+        index = {str(t): i for i, t in reversed(list(enumerate(self.tokenizer.tolist())))}
+        return NgramLM.from_arpa(arpa_path, token_to_id=index.get)
+
+    def _run_window_beam(self, win: np.ndarray, beam_size: int, nbest: int, offset_s: float, duration_s: float, timestamps: bool, max_token_rows: int):
+        """One window through the native session's beam search: (token ids of the best hypothesis, the hypotheses found, best first). Every hypothesis has
+        one token per CIF fire, so with timestamps each carries "tokens" with the times of the window's shared fire rows (as _run_window_timed forms them)
+        and its own log-probabilities; stop ids are dropped from a hypothesis' ids, text and records alike."""
+        native = self.session._native
+        cfg = native.cfg
+        tok, num, score, am, fire, logprob = native.run_packed_beam(win.reshape(-1), np.array([0, win.size], dtype=np.int64), beam_size, None, nbest)
+        return self._assemble_hypotheses(tok[0], num[0], score[0], am[0], fire[0], logprob[0], cfg.seq_len(win.size),
+                                         cfg.lfr_n * cfg.hop_length / cfg.sample_rate, offset_s, duration_s, timestamps, max_token_rows)
+
+    def _assemble_hypotheses(self, tok, num, score, am, fire, logprob, n_rows, row_seconds, offset_s, duration_s, timestamps, max_token_rows):
+        """The arrays of one utterance as ParaformerSession.run_packed_beam returns them ([nbest, max_T] / [nbest] / fire [max_T]) -> (best ids, hypotheses)."""
+        hyps, spans = [], None
+        for n in range(len(num)):
+            if not np.isfinite(score[n]):
+                break
+            count = int(num[n])
+            ids = np.asarray(tok[n, :count])
+            keep = ~np.isin(ids, self.stop_token_ids)
+            h = {"token_ids": ids[keep].copy(), "score": float(score[n]), "am_score": float(am[n]),
+                 "text": decode_tokens(self.tokenizer[ids[keep]].tolist(), self.decode_mode)}
+            if timestamps:
+                if spans is None:                                                   # the fire rows are the utterance's, not the hypothesis'
+                    spans = token_times(fire[:count], n_rows, row_seconds, max_token_rows)
+                h["tokens"] = [{"id": int(ids[k]), "text": str(self.tokenizer[ids[k]]), "start": min(offset_s + float(spans[k, 0]), duration_s),
+                                "end": min(offset_s + float(spans[k, 1]), duration_s), "logprob": float(logprob[n, k])} for k in range(count) if keep[k]]
+            hyps.append(h)
+        return hyps[0]["token_ids"], hyps
+
+    def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False, timestamps: bool = False, max_token_rows: int = 4,
+                   beam_size: int = 1, nbest: int = 1, hotwords=None, hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0):
         """int16 mono PCM at `sample_rate` -> dict(token_ids per window, text, rtf, windows). timestamps=True adds "tokens": one {"id", "text", "start",
         "end", "logprob"} per kept token over all windows, in seconds of the whole audio (token_times over the CIF fire rows; logprob = log soft-max of the
-        decoder head at the pick); records of stop ids are dropped with their ids."""
+        decoder head at the pick); records of stop ids are dropped with their ids.
+        beam_size > 1, nbest > 1, hotwords or lm: every window is decoded by the beam search over the decoder's token rows (ParaformerSession.run_packed_beam)
+        instead of the per-row arg-max; token_ids / text (and "tokens") hold the best hypothesis and "nbest" holds, per window, the hypotheses found, best
+        first: {"token_ids", "score", "am_score", "text"} and, with timestamps, "tokens" -- all hypotheses of a window share its CIF fire rows, so each has
+        times. hotwords: token-id lists, or text spelled in the vocabulary; hotword_boost per matched token. lm: an lm.NgramLM (load_lm reads an ARPA file
+        over this vocabulary): every token adds lm_weight * log P(token | history) + length_bonus to a hypothesis' score. The call sets exactly its own list
+        and model. With all of them at their defaults nothing changes."""
+        use_beam = beam_size > 1 or nbest > 1 or bool(hotwords) or lm is not None
+        if use_beam:
+            if not 1 <= nbest <= beam_size <= 16:
+                raise ValueError(f"beam_size {beam_size}, nbest {nbest}: expected 1 <= nbest <= beam_size <= 16")
+            self.session._native.set_hotwords(self._hotword_ids(hotwords), hotword_boost)        # exactly this call's list (an empty one clears)
+            self.session._native.set_lm(lm, lm_weight, length_bonus)                             # ... and exactly this call's model
         audio_len = int(np.asarray(audio_int16).size)
         audio = prepare_audio_input(np.asarray(audio_int16, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype,
                                     audio_pcm_scale=self.audio_pcm_scale, normalise=normalise)
@@ -139,12 +206,17 @@ class ParaformerTranscriber:
         audio_buffer = onnxruntime.OrtValue.ortvalue_from_numpy(
             filled_for(self.audio_meta, axes={0: 1, 1: 1, 2: window}), self.device_type, self.device_id)
         binding.bind_ortvalue_input(self.audio_meta.name, audio_buffer)
-        ids_all, pieces, tokens_all = [], [], []
+        ids_all, pieces, tokens_all, nbest_all = [], [], [], []
         start, end = 0, window
         t0 = time.time()
         while end <= aligned:
             win = array_for(self.audio_meta, audio[:, :, start:end], axes={0: 1, 1: 1, 2: window})
-            if timestamps:
+            if use_beam:
+                token_ids, hyps = self._run_window_beam(win, beam_size, nbest, start / self.sample_rate, audio_len / self.sample_rate, timestamps, max_token_rows)
+                nbest_all.append(hyps)
+                if timestamps:
+                    tokens_all.extend(hyps[0]["tokens"])
+            elif timestamps:
                 token_ids, toks = self._run_window_timed(win, start / self.sample_rate, audio_len / self.sample_rate, max_token_rows)
                 tokens_all.extend(t for t in toks if t["id"] not in self.stop_token_ids)
             else:
@@ -163,4 +235,6 @@ class ParaformerTranscriber:
                "windows": len(ids_all), "language": self.language}
         if timestamps:
             out["tokens"] = tokens_all
+        if use_beam:
+            out["nbest"] = nbest_all
         return out

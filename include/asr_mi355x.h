@@ -218,6 +218,27 @@ int asr_paraformer_run(asr_session* s, const void* audio, int audio_mem, const i
 int asr_paraformer_run_timed(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch,
                              int32_t* token_ids_out, int max_tokens, int32_t* num_id_out, int32_t* fire_frame_out, float* logprob_out);
 
+/* The same forward pass with a beam search over the decoder's token rows in place of the per-row arg-max (no reference counterpart). Per token
+ * row the `topk` (1..16) best tokens and their log soft-max are taken from the head without storing the logits. Every hypothesis picks one candidate per row,
+ * so all hypotheses of utterance b have its CIF fire count N_b as their length: there is no blank, no collapse and no merging. A hypothesis ranks by the sum
+ * of its candidates' log-probabilities + its hotword bonus (asr_paraformer_set_hotwords) + its language-model term (asr_paraformer_set_lm: alpha * log P(token |
+ * history) + beta per token, alpha * log P(</s> | history) at the end when the model lists </s>); `beam` (1..16) hypotheses stay live from row to row, ties go
+ * to the earlier entry of the enumeration (live hypothesis in rank order, then candidate column), and the `nbest` (1..beam) best come back, best first.
+ * token_ids_out host [B][nbest][max_tokens] and num_id_out host [B][nbest] follow the row contract of asr_sensevoice_run_beam; score_out [B][nbest] is
+ * acoustic + bonus + LM, am_score_out [B][nbest] the acoustic sum alone. Hypotheses beyond the number found (early rows offer fewer than `beam`) have num 0 and
+ * both scores -inf; an utterance without tokens yields one empty hypothesis of score 0 (+ the </s> term) and am_score 0. fire_frame_out (nullable, host
+ * [B][max_tokens]) holds the CIF fire rows of asr_paraformer_run_timed, N_b entries in row b: every hypothesis of the utterance shares them. token_logprob_out
+ * (nullable, host [B][nbest][max_tokens]) holds each hypothesis' per-token log soft-max, rows as token_ids_out. Without hotwords and without a model,
+ * hypothesis 0 holds asr_paraformer_run's ids. Two calls on the same input return the same bytes. */
+int asr_paraformer_run_beam(asr_session* s, const void* audio, int audio_mem, const int64_t* audio_offsets, int batch, int beam, int topk, int nbest,
+                            int32_t* token_ids_out, int max_tokens, int32_t* num_id_out, float* score_out, float* am_score_out, int32_t* fire_frame_out,
+                            float* token_logprob_out);
+/* Hotwords and language model of asr_paraformer_run_beam: arguments, rules and rejections as asr_sensevoice_set_hotwords / asr_sensevoice_set_lm, except that
+ * this family has no blank id -- every id in [0, vocab) is legal in a phrase or an image. A rejected list or image leaves the one in force. Offline sessions
+ * only: a streaming chunk step commits its tokens when it returns. */
+int asr_paraformer_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+int asr_paraformer_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob);
+
 /* Streaming Paraformer: replaces Paraformer_Streaming_Encoder.onnx + Paraformer_Streaming_Decoder.onnx (PARAFORMER_ENCODER /
  * PARAFORMER_DECODER, Paraformer/Streaming/Export_Paraformer_Streaming.py:330-553) and the state shuttling of
  * Inference_Paraformer_Streaming_ONNX.py:309-449. The 100 in_en_key/value tensors, in_previous_mel_features, in_cif_hidden,
@@ -558,6 +579,15 @@ int asr_op_ctc_prefix_beam_lm(const int32_t* cand_id, const float* cand_logprob,
                               const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
                               int32_t* num_id, float* score, float* ctc_score, const int32_t* lm_image, int64_t lm_words, float alpha, float beta,
                               float oov_logprob);
+/* the search of asr_paraformer_run_beam on host arrays: cand_id / cand_logprob [sum N][topk] (ids distinct inside a row, a -inf log-probability makes no
+ * entry), seq_lens [batch] = the token counts N (0 is legal: one empty hypothesis). The hotword trie as above; the language model image as
+ * asr_paraformer_set_lm takes it, or null for none (its header's vocab then bounds the candidate ids with a finite log-probability). Outputs [batch][nbest],
+ * best first: token_ids / token_logprob (nullable) [batch][nbest][max_tokens] (slots the search does not write come back 0), num_id, score (acoustic + bonus +
+ * lm) and am_score (the sum of the picked candidates' log-probabilities); hypotheses beyond the number found have num_id 0 and both scores -inf. */
+int asr_op_nar_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, const int32_t* trie_depth,
+                    const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node, int n_nodes,
+                    float boost, const int32_t* lm_image, int64_t lm_words, float alpha, float beta, float oov_logprob, int beam, int nbest,
+                    int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* am_score, float* token_logprob);
 /* the trellis of asr_sensevoice_align on host arrays: em [sum T][ld_em] log-probabilities, slot 0 the blank and slot j the sequence's target j - 1 (ld_em >
  * the longest transcript); each sequence is aligned against its rows row0 .. seq_lens[b] - 1 (seq_lens[b] > row0; earlier rows are never read). Targets ragged as
  * above (any ids: only the equality of neighbours matters). first_frame / last_frame / token_logprob host [batch][max_tokens], max_tokens >= the longest

@@ -63,6 +63,34 @@ def parse_hotword_file(path):
     return phrases
 
 
+def nar_options(a):
+    """The --nar-* flags (Paraformer's beam search over the decoder's token rows), checked before a model is opened: None when none is given, else
+    dict(beam_size, nbest, hotwords, hotword_boost, lm_file, lm_weight, length_bonus) as ParaformerTranscriber.transcribe takes them (lm_file still a path)."""
+    beam, nbest = getattr(a, "nar_beam", None), getattr(a, "nar_nbest", None)
+    hot_file, boost = getattr(a, "nar_hotwords", None), getattr(a, "nar_hotword_boost", None)
+    lm_file, weight, bonus = getattr(a, "nar_lm", None), getattr(a, "nar_lm_weight", None), getattr(a, "nar_length_bonus", None)
+    if all(v is None for v in (beam, nbest, hot_file, boost, lm_file, weight, bonus)):
+        return None
+    if a.family != "paraformer":
+        raise SystemExit("--nar-beam / --nar-nbest / --nar-hotwords / --nar-hotword-boost / --nar-lm / --nar-lm-weight / --nar-length-bonus exist for "
+                         "--family paraformer only")
+    if boost is not None and not hot_file:
+        raise SystemExit("--nar-hotword-boost needs --nar-hotwords FILE")
+    if (weight is not None or bonus is not None) and not lm_file:
+        raise SystemExit("--nar-lm-weight / --nar-length-bonus need --nar-lm FILE.arpa")
+    if weight is not None and not weight >= 0:
+        raise SystemExit("--nar-lm-weight %r: expected a weight >= 0" % weight)
+    for flag, path in (("--nar-hotwords", hot_file), ("--nar-lm", lm_file)):
+        if path and not os.path.isfile(path):
+            raise SystemExit("%s %s: no such file" % (flag, path))
+    nbest = 1 if nbest is None else nbest
+    beam = max(nbest, 1) if beam is None else beam                      # (--nar-nbest alone: the narrowest beam that can return them)
+    if not 1 <= nbest <= beam <= 16:
+        raise SystemExit("--family paraformer: --nar-beam 1..16 and --nar-nbest 1..beam (got --nar-beam %d --nar-nbest %d)" % (beam, nbest))
+    return {"beam_size": beam, "nbest": nbest, "hotwords": parse_hotword_file(hot_file) if hot_file else None, "hotword_boost": 2.0 if boost is None else boost,
+            "lm_file": lm_file, "lm_weight": 0.5 if weight is None else weight, "length_bonus": 0.0 if bonus is None else bonus}
+
+
 def run(a) -> dict:
     shim, eng, audio_io, cfgm = _m("ort_shim"), _m("engine"), _m("audio_io"), _m("config")
     prec = 1 if a.precision == "f32" else 0
@@ -91,6 +119,7 @@ def run(a) -> dict:
         raise SystemExit("--timestamps is not available with --beam / --nbest / --hotwords / --lm (beam hypotheses carry no time spans)")
     if sv_beam and not 1 <= nbest <= a.beam <= 16:
         raise SystemExit("--family sensevoice: --beam 1..16 and --nbest 1..beam (got --beam %d --nbest %d)" % (a.beam, nbest))
+    nar = nar_options(a)
     dec_hot_file, dec_hot_boost = getattr(a, "decoder_hotwords", None), getattr(a, "decoder_hotword_boost", 2.0)
     if dec_hot_file and a.family not in ("whisper", "qwen_asr"):
         raise SystemExit("--decoder-hotwords exists for --family whisper and --family qwen_asr only (SenseVoice: --hotwords)")
@@ -116,9 +145,15 @@ def run(a) -> dict:
         else:
             tr = mod.ParaformerTranscriber(a.model, vocab_path=a.tokenizer, device_type="cuda")
         lm = tr.load_lm(lm_file) if lm_file else None
+        nar_kw = None
+        if nar:                             # Paraformer: beam search over the decoder's token rows; its hypotheses keep the CIF times, so --timestamps combines
+            nar_kw = {k: v for k, v in nar.items() if k != "lm_file"}
+            nar_kw["lm"] = tr.load_lm(nar["lm_file"]) if nar["lm_file"] else None
         for p in a.wav:
             pcm = audio_io.read_wav_int16(p, tr.sample_rate, exact_width=a.strict_wav)
-            if timestamps:
+            if nar_kw:
+                r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=timestamps, **nar_kw)
+            elif timestamps:
                 r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=True)
             elif sv_beam:
                 r = tr.transcribe(pcm, sliding_window=a.sliding_window, beam_size=a.beam, nbest=nbest, hotwords=parse_hotword_file(hot_file) if hot_file else None,
@@ -133,6 +168,9 @@ def run(a) -> dict:
             if sv_beam:                     # per window the hypotheses found, best first (windows[k] is nbest[k][0])
                 files[-1]["nbest"] = [[{"ids": np.asarray(h["token_ids"]).astype(int).tolist(), "score": h["score"], "ctc_score": h["ctc_score"], "text": h["text"]}
                                        for h in win] for win in r["nbest"]]
+            if nar_kw and "nbest" in r:     # the same for Paraformer: am_score in place of ctc_score, and every hypothesis' token times with --timestamps
+                files[-1]["nbest"] = [[dict({"ids": np.asarray(h["token_ids"]).astype(int).tolist(), "score": h["score"], "am_score": h["am_score"], "text": h["text"]},
+                                            **({"tokens": h["tokens"]} if timestamps else {})) for h in win] for win in r["nbest"]]
     elif a.family == "whisper":
         info, blob = shim.load_model(os.path.join(a.model, "Whisper.asrmodel"))
         cfg = cfgm.WhisperConfig(**info["config"])
@@ -284,6 +322,15 @@ def build_parser():
                         "into the beam search, which it implies")
     r.add_argument("--lm-weight", type=float, default=None, help="SenseVoice: weight of the language model's log-probability (default 0.5)")
     r.add_argument("--length-bonus", type=float, default=None, help="SenseVoice: bonus per token with --lm (default 0)")
+    r.add_argument("--nar-beam", type=int, default=None, metavar="N", help="Paraformer: beam search over the decoder's token rows, N live hypotheses (1..16; default: "
+                        "--nar-nbest, else 1); every hypothesis has one token per CIF fire, so --timestamps combines with it")
+    r.add_argument("--nar-nbest", type=int, default=None, metavar="M", help="Paraformer: keep the M best hypotheses of every window in the dump (1..beam), with their scores")
+    r.add_argument("--nar-hotwords", metavar="FILE", help="Paraformer: phrases the beam search favours, one per line: token ids, or text spelled in the vocabulary")
+    r.add_argument("--nar-hotword-boost", type=float, default=None, metavar="X", help="Paraformer: log-probability bonus per matched hotword token (default 2.0)")
+    r.add_argument("--nar-lm", metavar="FILE.arpa", help="Paraformer: back-off n-gram language model (ARPA; words are token ids or vocabulary entries) fused into the "
+                        "beam search, which it implies")
+    r.add_argument("--nar-lm-weight", type=float, default=None, metavar="X", help="Paraformer: weight of the language model's log-probability (default 0.5)")
+    r.add_argument("--nar-length-bonus", type=float, default=None, metavar="Y", help="Paraformer: bonus per token with --nar-lm (default 0)")
     r.add_argument("--decoder-hotwords", metavar="FILE", help="Whisper, Qwen3-ASR: phrases the decoder favours (greedy, sampling and --beam alike), one per line: "
                         "token ids, or text with --tokenizer (boosted in both spellings, at the start of the text and inside it)")
     r.add_argument("--decoder-hotword-boost", type=float, default=2.0, help="Whisper, Qwen3-ASR: logit / log-probability bonus per matched hotword token")
