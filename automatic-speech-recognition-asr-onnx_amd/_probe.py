@@ -18,7 +18,10 @@ class GemmDesc(C.Structure):
     _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("a", _fp), ("w", _fp), ("bias", _fp), ("add", _fp),
                 ("act", C.c_int32), ("ln", C.c_int32), ("ln_eps", C.c_float), ("argmax", C.c_int32), ("n_valid", C.c_int32),
                 ("variant", C.c_int32), ("out_lo", _fp), ("out_f32", _fp), ("out_stats", _fp), ("out_ids", _ip),
-                ("kernel", C.c_char * 32)]
+                ("kernel", C.c_char * 32),
+                ("precision", C.c_int32), ("add2", _fp), ("add2_table_rows", C.c_int32), ("add2_rows", _ip), ("a_rms_eps", C.c_float),
+                ("m_dev", C.c_int32), ("lo_group", C.c_int32), ("out_t", _fp), ("ld_out_t", C.c_int32), ("out_rms", _fp), ("rms_eps", C.c_float),
+                ("pad_a", C.c_int32), ("pad_w", C.c_int32), ("pad_out", C.c_int32), ("with_ws", C.c_int32), ("stray", C.c_int32)]
 
 
 class DecodeAttnDesc(C.Structure):
@@ -143,30 +146,56 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-def gemm(a, w, bias=None, add=None, act=0, ln=False, ln_eps=1e-5, argmax=False, n_valid=0, variant=-1, want=("lo",)):
-    """One bf16 GEMM through the product dispatcher; returns (dict of outputs, kernel family name)."""
+def gemm(a, w, bias=None, add=None, act=0, ln=False, ln_eps=1e-5, argmax=False, n_valid=0, variant=-1, want=("lo",), precision=0, add2=None,
+         add2_rows=None, a_rms_eps=0.0, m_dev=None, lo_group=0, ld_out_t=0, rms_eps=1e-6, pad_a=0, pad_w=0, pad_out=0, with_ws=True):
+    """One GEMM through the product dispatcher (precision 0: operands rounded to bf16, launch_gemm_bf16; 1: launch_gemm_f32); returns
+    (dict of outputs, kernel family name). want: "lo" ([M][N]; [M][N / 2] with act 4; with lo_group the slabs as laid out, [N / lo_group][round_up(M, 128)]
+    [lo_group], unwritten rows NaN), "f32", "stats" ([M][N / 32][2]), "t" (the transposed store, [N][M]), "rms" ([M][N], the split-K reduce's second
+    output). With m_dev (the device-side row count beside the launch bound M) the outputs hold min(M, m_dev) rows. add2 is a table [R][N] read at row
+    add2_rows[m] (row m without add2_rows). pad_*: extra elements per row of A, W and of every output / add / add2 buffer; with_ws=False launches without
+    the split-K workspace. out["stray"]: words outside the valid rows x valid columns of the NaN-filled output buffers that the launch changed."""
     a, w = _f32(a), _f32(w)
     M, K = a.shape
     N = w.shape[0]
+    Mv = M if m_dev is None else min(M, int(m_dev))
     d = GemmDesc()
     d.M, d.N, d.K, d.act, d.ln, d.ln_eps, d.argmax, d.n_valid, d.variant = M, N, K, act, int(ln), ln_eps, int(argmax), n_valid, variant
+    d.precision, d.a_rms_eps, d.m_dev, d.lo_group, d.ld_out_t, d.rms_eps = int(precision), a_rms_eps, -1 if m_dev is None else int(m_dev), lo_group, ld_out_t, rms_eps
+    d.pad_a, d.pad_w, d.pad_out, d.with_ws, d.stray = pad_a, pad_w, pad_out, int(with_ws), -1
     keep = [a, w]
     d.a, d.w = a.ctypes.data_as(_fp), w.ctypes.data_as(_fp)
     if bias is not None:
         bias = _f32(bias); keep.append(bias); d.bias = bias.ctypes.data_as(_fp)
     if add is not None:
         add = _f32(add); keep.append(add); d.add = add.ctypes.data_as(_fp)
+        assert add.shape == (M, N), add.shape
+    if add2 is not None:
+        add2 = _f32(add2); keep.append(add2); d.add2 = add2.ctypes.data_as(_fp); d.add2_table_rows = add2.shape[0]
+        assert add2.shape[1] == N, add2.shape
+        if add2_rows is not None:
+            add2_rows = np.ascontiguousarray(add2_rows, dtype=np.int32); keep.append(add2_rows); d.add2_rows = add2_rows.ctypes.data_as(_ip)
+            assert add2_rows.shape == (M,), add2_rows.shape
     out = {}
+
+    def buf(key, shape, field):
+        out[key] = np.zeros(shape, dtype=np.float32)
+        setattr(d, field, out[key].ctypes.data_as(_fp))
+
     if argmax:
-        out["ids"] = np.zeros((M,), dtype=np.int32); d.out_ids = out["ids"].ctypes.data_as(_ip)
+        out["ids"] = np.zeros((Mv,), dtype=np.int32); d.out_ids = out["ids"].ctypes.data_as(_ip)
     else:
         if "lo" in want:
-            out["lo"] = np.zeros((M, N), dtype=np.float32); d.out_lo = out["lo"].ctypes.data_as(_fp)
+            buf("lo", (N // lo_group, (M + 127) // 128 * 128, lo_group) if lo_group else (Mv, N // 2 if act == 4 else N), "out_lo")
         if "f32" in want:
-            out["f32"] = np.zeros((M, N), dtype=np.float32); d.out_f32 = out["f32"].ctypes.data_as(_fp)
+            buf("f32", (Mv, N), "out_f32")
         if "stats" in want:
-            out["stats"] = np.zeros((M, N // 32, 2), dtype=np.float32); d.out_stats = out["stats"].ctypes.data_as(_fp)
+            buf("stats", (Mv, N // 32, 2), "out_stats")
+        if "t" in want:
+            buf("t", (N, Mv), "out_t")
+        if "rms" in want:
+            buf("rms", (Mv, N), "out_rms")
     _lib.check(load().asr_probe_gemm(C.byref(d)))
+    out["stray"] = int(d.stray)
     return out, d.kernel.decode()
 
 

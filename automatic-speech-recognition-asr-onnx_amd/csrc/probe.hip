@@ -32,6 +32,44 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 char g_chain_kernel[32] = "";
 inline float bf16_bits_to_f32(bf16_t b) { union { uint32_t u; float f; } c; c.u = ((uint32_t)b) << 16; return c.f; }
 
+// Guarded output buffer of asr_probe_gemm: rows x pitch elements of 2 (bf16) or 4 (f32 / int32) bytes, every byte 0xff before the launch -- a NaN in both
+// formats, -1 as an index.
+struct Guarded { void* dev = nullptr; size_t rows = 0, pitch = 0; int elt = 4; };
+inline Guarded guarded(Tmp& t, size_t rows, size_t pitch, int elt) {
+  Guarded b;
+  b.rows = rows; b.pitch = pitch; b.elt = elt;
+  b.dev = t.alloc(rows * pitch * elt);
+  HIP_CHECK(hipMemset(b.dev, 0xff, rows * pitch * elt));
+  return b;
+}
+inline uint32_t guard_word(int elt) { return elt == 2 ? 0xffff0000u : 0xffffffffu; }
+// the whole buffer -> h (one 32-bit word per element, bf16 widened to its f32 bits); returns the elements outside the top-left rows_v x cols_v block
+// that no longer hold the pattern
+inline int collect(const Guarded& b, size_t rows_v, size_t cols_v, std::vector<uint32_t>& h) {
+  const size_t n = b.rows * b.pitch;
+  h.resize(n);
+  if (b.elt == 2) {
+    std::vector<uint16_t> raw(n);
+    HIP_CHECK(hipMemcpy(raw.data(), b.dev, n * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) h[i] = (uint32_t)raw[i] << 16;
+  } else {
+    HIP_CHECK(hipMemcpy(h.data(), b.dev, n * 4, hipMemcpyDeviceToHost));
+  }
+  const uint32_t pat = guard_word(b.elt);
+  int bad = 0;
+  for (size_t r = 0; r < b.rows; ++r)
+    for (size_t c = 0; c < b.pitch; ++c)
+      if ((r >= rows_v || c >= cols_v) && h[r * b.pitch + c] != pat) ++bad;
+  return bad;
+}
+// lo_group slabs [slab][Mp][G]: elements of the rows Mv .. Mp of every slab that no longer hold the pattern
+inline int stale_rows(const std::vector<uint32_t>& h, size_t pitch, int slabs, int Mv, int Mp, int G, int elt) {
+  int bad = 0;
+  for (int s = 0; s < slabs; ++s)
+    for (size_t i = (size_t)Mv * G; i < (size_t)Mp * G; ++i) bad += h[s * pitch + i] != guard_word(elt);
+  return bad;
+}
+
 }  // namespace
 
 extern "C" int asr_probe_gemm_bench(int variant, int M, int N, int K, int epilogue, int iters, float* avg_ms) {
@@ -382,37 +420,64 @@ extern "C" int asr_probe_gemm_counts(int reset, char* buf, int cap) {
 
 // Parity hook for the epilogue families the product's batch-64 path uses and asr_op_gemm cannot express: the LayerNorm folded into
 // the product (row statistics handed over in 32-column groups, column sums of the bf16 weights), the fused row arg-max, and the
-// producer epilogue (f32 + bf16 stores + row statistics). Reports which kernel family the dispatcher chose.
+// producer epilogue (f32 + bf16 stores + row statistics) -- and every other GemmArgs term at op level (the transposed store, per-head slabs, the
+// post-activation term with its row table, SwiGLU, the RMSNorm fold, rms_out, the device-side row count, pitches wider than the matrix, a launch without
+// the split-K workspace, the f32 kernel). Every output buffer reaches the documented edge plus its pitch gap and is filled with a NaN pattern first;
+// d->stray counts what changed outside valid rows x valid columns. Reports which kernel family the dispatcher chose.
 extern "C" int asr_probe_gemm(asr_probe_gemm_desc* d) {
   return asr_guard([&] {
-    ASR_REQUIRE(d && d->a && d->w && d->M > 0 && d->N > 0 && d->K > 0 && d->N % 128 == 0 && d->K % 64 == 0, "probe_gemm: bad argument");
+    ASR_REQUIRE(d && d->a && d->w && d->M > 0 && d->N > 0 && d->K > 0 && d->N % 16 == 0 && d->K % 16 == 0, "probe_gemm: bad argument");
+    ASR_REQUIRE(d->pad_a >= 0 && d->pad_w >= 0 && d->pad_out >= 0 && d->pad_out % 8 == 0, "probe_gemm: pad_out must be a multiple of 8");
     asr_require_device(0);
     gemm_reload_env();
+    d->stray = 0;
     Tmp t;
-    const int M = d->M, N = d->N, K = d->K, Mp = round_up(M, 128);
-    std::vector<bf16_t> ha((size_t)Mp * K, 0), hw((size_t)N * K);
-    for (size_t i = 0; i < (size_t)M * K; ++i) ha[i] = f32_to_bf16(d->a[i]);
-    for (size_t i = 0; i < (size_t)N * K; ++i) hw[i] = f32_to_bf16(d->w[i]);
-    bf16_t* da = (bf16_t*)t.alloc(ha.size() * 2);
-    bf16_t* dw = (bf16_t*)t.alloc(hw.size() * 2);
-    HIP_CHECK(hipMemcpy(da, ha.data(), ha.size() * 2, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
+    const bool f32 = d->precision != 0;
+    const int elt = f32 ? 4 : 2;
+    ASR_REQUIRE((d->pad_a * elt) % 16 == 0 && (d->pad_w * elt) % 16 == 0, "probe_gemm: pad_a / pad_w must keep the rows 16-byte aligned");
+    ASR_REQUIRE(!(f32 && (d->ln || d->a_rms_eps > 0.0f || d->m_dev >= 0 || d->out_stats || d->out_rms)),
+                "probe_gemm: the f32 kernel has no LayerNorm / RMSNorm fold, device-side row count or row statistics, and gemm_reduce_can_norm describes the bf16 dispatcher");
+    const int M = d->M, N = d->N, K = d->K, Mp = round_up(M, 128), Mv = d->m_dev >= 0 ? std::min(M, d->m_dev) : M, pad = d->pad_out;
+    const int lda = K + d->pad_a, ldw = K + d->pad_w;
+    // operands: A [round_up(M, 128)][lda], W [N][ldw]; the pitch gaps and A's rows from M to the tile edge hold NaN (every byte 0xff)
+    std::vector<float> ra((size_t)M * K), rw((size_t)N * K);      // the operand values the kernels see
+    std::vector<unsigned char> ha((size_t)Mp * lda * elt, 0xff), hw((size_t)N * ldw * elt, 0xff);
+    auto put = [&](std::vector<unsigned char>& h, std::vector<float>& r, const float* src, int rows, int ld) {
+      for (int m = 0; m < rows; ++m)
+        for (int k = 0; k < K; ++k) {
+          const float v = src[(size_t)m * K + k];
+          if (f32) { memcpy(&h[((size_t)m * ld + k) * 4], &v, 4); r[(size_t)m * K + k] = v; }
+          else { const bf16_t b = f32_to_bf16(v); memcpy(&h[((size_t)m * ld + k) * 2], &b, 2); r[(size_t)m * K + k] = bf16_bits_to_f32(b); }
+        }
+    };
+    put(ha, ra, d->a, M, lda);
+    put(hw, rw, d->w, N, ldw);
+    void* da = t.alloc(ha.size());
+    void* dw = t.alloc(hw.size());
+    HIP_CHECK(hipMemcpy(da, ha.data(), ha.size(), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dw, hw.data(), hw.size(), hipMemcpyHostToDevice));
     GemmArgs g;
-    g.A = da; g.lda = K; g.W = dw; g.ldw = K; g.M = M; g.N = N; g.K = K; g.act = d->act;
+    g.A = da; g.lda = lda; g.W = dw; g.ldw = ldw; g.M = M; g.N = N; g.K = K; g.act = d->act; g.a_rms_eps = d->a_rms_eps;
     if (d->bias) {
       float* db = (float*)t.alloc((size_t)N * 4);
       HIP_CHECK(hipMemcpy(db, d->bias, (size_t)N * 4, hipMemcpyHostToDevice));
       g.bias = db;
     }
-    g.sk_ws = (float*)t.alloc((size_t)16 << 20); g.sk_ws_bytes = (size_t)16 << 20; g.sk_cnt = (int32_t*)t.alloc(4096 * 4);
+    if (d->with_ws) { g.sk_ws = (float*)t.alloc((size_t)16 << 20); g.sk_ws_bytes = (size_t)16 << 20; g.sk_cnt = (int32_t*)t.alloc(4096 * 4); }
+    if (d->m_dev >= 0) {
+      int32_t* dm = (int32_t*)t.alloc(4);
+      HIP_CHECK(hipMemcpy(dm, &d->m_dev, 4, hipMemcpyHostToDevice));
+      g.m_dev = dm;
+    }
     if (d->ln) {            // LayerNorm(no affine, eps) of the bf16-rounded A rows folded into the product
+      ASR_REQUIRE(K % 64 == 0 && N % 128 == 0, "probe_gemm: the LayerNorm fold needs K %% 64 == 0 and N %% 128 == 0");
       std::vector<float> cs(N);
-      for (int n = 0; n < N; ++n) { double s = 0.0; for (int k = 0; k < K; ++k) s += bf16_bits_to_f32(hw[(size_t)n * K + k]); cs[n] = (float)s; }
+      for (int n = 0; n < N; ++n) { double s = 0.0; for (int k = 0; k < K; ++k) s += rw[(size_t)n * K + k]; cs[n] = (float)s; }
       std::vector<float> st((size_t)Mp * (K / 32) * 2, 0.0f);
       for (int m = 0; m < M; ++m)
         for (int q = 0; q < K / 32; ++q) {
           float s1 = 0.0f, s2 = 0.0f;
-          for (int k = 0; k < 32; ++k) { const float v = bf16_bits_to_f32(ha[(size_t)m * K + q * 32 + k]); s1 += v; s2 += v * v; }
+          for (int k = 0; k < 32; ++k) { const float v = ra[(size_t)m * K + q * 32 + k]; s1 += v; s2 += v * v; }
           st[((size_t)m * (K / 32) + q) * 2] = s1; st[((size_t)m * (K / 32) + q) * 2 + 1] = s2;
         }
       float* dcs = (float*)t.alloc((size_t)N * 4);
@@ -422,39 +487,80 @@ extern "C" int asr_probe_gemm(asr_probe_gemm_desc* d) {
       g.ln_colsum = dcs; g.ln_dim = K; g.ln_stats_in = dst; g.ln_slots = K / 32; g.ln_eps = d->ln_eps;
       ASR_REQUIRE(gemm_ln_fusable(g), "probe_gemm: shape cannot take the LayerNorm-folded kernels");
     }
-    float* d_add = nullptr;
-    if (d->add) {
-      d_add = (float*)t.alloc((size_t)Mp * N * 4);
-      HIP_CHECK(hipMemcpy(d_add, d->add, (size_t)M * N * 4, hipMemcpyHostToDevice));
-      g.add = d_add; g.ld_add = N;
+    // f32 terms [rows][N + pad]: the pitch gap and the rows the kernels may touch without using them hold NaN
+    auto upload_rows = [&](const float* src, int rows, int rows_alloc) {
+      const int ld = N + pad;
+      std::vector<uint32_t> h((size_t)rows_alloc * ld, 0xffffffffu);
+      for (int m = 0; m < rows; ++m) memcpy(&h[(size_t)m * ld], src + (size_t)m * N, (size_t)N * 4);
+      float* p = (float*)t.alloc(h.size() * 4);
+      HIP_CHECK(hipMemcpy(p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+      return p;
+    };
+    if (d->add) { g.add = upload_rows(d->add, M, Mp); g.ld_add = N + pad; }      // readable to the tile edge
+    if (d->add2) {
+      const int R = d->add2_table_rows > 0 ? d->add2_table_rows : M;
+      ASR_REQUIRE(d->add2_rows || R >= M, "probe_gemm: the add2 table has fewer rows than the product");
+      g.add2 = upload_rows(d->add2, R, R); g.ld_add2 = N + pad;
+      if (d->add2_rows) {
+        for (int m = 0; m < M; ++m) ASR_REQUIRE(d->add2_rows[m] >= 0 && d->add2_rows[m] < R, "probe_gemm: add2_rows[%d] = %d outside the table", m, d->add2_rows[m]);
+        int32_t* dr = (int32_t*)t.alloc((size_t)M * 4);
+        HIP_CHECK(hipMemcpy(dr, d->add2_rows, (size_t)M * 4, hipMemcpyHostToDevice));
+        g.add2_rows = dr;
+      }
     }
-    bf16_t* dlo = nullptr; float* df32 = nullptr; float2* dso = nullptr; float* dav = nullptr; int32_t* dai = nullptr; int32_t* dids = nullptr;
-    const int n_slabs = N / 64;
+    // outputs: every buffer reaches the documented edge (round_up(M, 128) rows) plus its pitch gap and holds the NaN pattern before the launch
+    Guarded lo, o32, ot, rms, st, av, ai, ids;
+    const int n_slabs = N / 64, G = d->lo_group, n_lo = d->act == ACT_SWIGLU ? N / 2 : N;
     if (d->argmax) {
-      dav = (float*)t.alloc((size_t)Mp * n_slabs * 4); dai = (int32_t*)t.alloc((size_t)Mp * n_slabs * 4); dids = (int32_t*)t.alloc((size_t)Mp * 4);
-      g.amax_val = dav; g.amax_idx = dai; g.n_valid = d->n_valid > 0 ? d->n_valid : N;
+      ASR_REQUIRE(N % 128 == 0 && d->out_ids, "probe_gemm: the arg-max head needs N %% 128 == 0 and out_ids");
+      av = guarded(t, Mp, n_slabs, 4); ai = guarded(t, Mp, n_slabs, 4); ids = guarded(t, Mp, 1, 4);
+      g.amax_val = (float*)av.dev; g.amax_idx = (int32_t*)ai.dev; g.n_valid = d->n_valid > 0 ? d->n_valid : N;
+    }
+    if (d->out_lo) {
+      if (G > 0) {                                             // [N / G] slabs of [Mp][G] (+ gap)
+        ASR_REQUIRE(N % G == 0 && d->act != ACT_SWIGLU, "probe_gemm: lo_group must divide N");
+        lo = guarded(t, N / G, (size_t)Mp * G + pad, elt); g.lo_group = G;
+      } else lo = guarded(t, Mp, n_lo + pad, elt);
+      g.out_lo = lo.dev; g.ld_out_lo = (int)lo.pitch;
+    }
+    if (d->out_f32) { o32 = guarded(t, Mp, N + pad, 4); g.out_f32 = (float*)o32.dev; g.ld_out_f32 = N + pad; }
+    if (d->out_t) {
+      const int ld = d->ld_out_t > 0 ? d->ld_out_t : round_up(M, 4) + pad;
+      ASR_REQUIRE(ld >= M, "probe_gemm: ld_out_t = %d below M", ld);
+      ot = guarded(t, N, ld, elt); g.out_t = ot.dev; g.ld_out_t = ld;
+    }
+    if (d->out_rms) { rms = guarded(t, Mp, N + pad, elt); g.rms_out = rms.dev; g.ld_rms_out = N + pad; g.rms_eps = d->rms_eps; }
+    if (d->out_stats) {
+      ASR_REQUIRE(d->out_lo && N % 32 == 0, "probe_gemm: row statistics describe the bf16 output");
+      st = guarded(t, Mp, (size_t)(N / 32) * 2, 4); g.st_out = (float2*)st.dev;
+    }
+    if (f32) {
+      launch_gemm_f32(g, nullptr);
     } else {
-      if (d->out_lo) { dlo = (bf16_t*)t.alloc((size_t)Mp * N * 2); g.out_lo = dlo; g.ld_out_lo = N; }
-      if (d->out_f32) { df32 = (float*)t.alloc((size_t)Mp * N * 4); g.out_f32 = df32; g.ld_out_f32 = N; }
-      if (d->out_stats) { ASR_REQUIRE(d->out_lo, "probe_gemm: row statistics describe the bf16 output"); dso = (float2*)t.alloc((size_t)Mp * (N / 32) * 8); g.st_out = dso; }
+      if (g.rms_out) ASR_REQUIRE(gemm_reduce_can_norm(g), "probe_gemm: this shape does not take the split-K reduce that writes rms_out (gemm_reduce_can_norm)");
+      gemm_set_variant(d->variant);
+      try { launch_gemm_bf16(g, nullptr); } catch (...) { gemm_set_variant(-1); throw; }
+      gemm_set_variant(-1);
     }
-    gemm_set_variant(d->variant);
-    try { launch_gemm_bf16(g, nullptr); } catch (...) { gemm_set_variant(-1); throw; }
-    gemm_set_variant(-1);
     snprintf(d->kernel, sizeof(d->kernel), "%s", gemm_last_kernel());
-    if (d->argmax) launch_argmax_reduce(dav, dai, M, n_slabs, dids, nullptr);
+    if (d->argmax && Mv > 0) launch_argmax_reduce((const float*)av.dev, (const int32_t*)ai.dev, Mv, n_slabs, (int32_t*)ids.dev, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
-    if (d->argmax) {
-      ASR_REQUIRE(d->out_ids, "probe_gemm: out_ids missing");
-      HIP_CHECK(hipMemcpy(d->out_ids, dids, (size_t)M * 4, hipMemcpyDeviceToHost));
-    }
-    if (dlo) {
-      std::vector<bf16_t> tmp((size_t)M * N);
-      HIP_CHECK(hipMemcpy(tmp.data(), dlo, tmp.size() * 2, hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < tmp.size(); ++i) d->out_lo[i] = bf16_bits_to_f32(tmp[i]);
-    }
-    if (df32) HIP_CHECK(hipMemcpy(d->out_f32, df32, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    if (dso) HIP_CHECK(hipMemcpy(d->out_stats, dso, (size_t)M * (N / 32) * 8, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> h;
+    int stray = 0;
+    auto fetch = [&](const Guarded& b, size_t rows_v, size_t cols_v) { if (b.dev) stray += collect(b, rows_v, cols_v, h); return b.dev != nullptr; };
+    auto block = [&](const Guarded& b, void* dst, size_t rows, size_t cols) {       // the top-left rows x cols words of h -> dst
+      for (size_t r = 0; r < rows; ++r) memcpy((uint32_t*)dst + r * cols, &h[r * b.pitch], cols * 4);
+    };
+    if (fetch(ids, Mv, 1)) block(ids, d->out_ids, Mv, 1);
+    fetch(av, Mv, n_slabs);
+    fetch(ai, Mv, n_slabs);
+    if (G > 0) { if (fetch(lo, N / G, (size_t)Mp * G)) { stray += stale_rows(h, lo.pitch, N / G, Mv, Mp, G, elt); block(lo, d->out_lo, N / G, (size_t)Mp * G); } }
+    else if (fetch(lo, Mv, n_lo)) block(lo, d->out_lo, Mv, n_lo);
+    if (fetch(o32, Mv, N)) block(o32, d->out_f32, Mv, N);
+    if (fetch(ot, N, Mv)) block(ot, d->out_t, N, Mv);
+    if (fetch(rms, Mv, N)) block(rms, d->out_rms, Mv, N);
+    if (fetch(st, Mv, (size_t)(N / 32) * 2)) block(st, d->out_stats, Mv, (size_t)(N / 32) * 2);
+    d->stray = stray;
   });
 }
 

@@ -24,12 +24,31 @@ typedef struct asr_probe_gemm_desc {
   float ln_eps;
   int32_t argmax;          /* 1: fused row arg-max over n < n_valid -> out_ids[M] (no matrix output) */
   int32_t n_valid;
-  int32_t variant;         /* -1 heuristic; 0..7 pins a kernel variant (csrc/gemm.hip) */
+  int32_t variant;         /* -1 heuristic; pins a kernel (csrc/gemm.hip): 1..4 pipe, 5 / 6 t144, 7 big, 8 pp, 136 pp with one workgroup per tile */
   float* out_lo;           /* [M][N] bf16 results widened to f32, or NULL */
   float* out_f32;          /* [M][N] f32 results, or NULL */
   float* out_stats;        /* [M][N/32][2] (sum, sum of squares) of the bf16 outputs per 32-column group, or NULL */
   int32_t* out_ids;        /* [M] when argmax */
-  char kernel[32];         /* out: "t288w", "t288w_amax", "t144w", "t144", "big", "pipe", "pipe_splitk", "skinny" */
+  char kernel[32];         /* out: "t288w", "t288w_amax", "t144w", "t144", "big", "pp", "pp_amax", "pipe", "pipe_splitk", "skinny", "skinny_ln",
+                            * "skinny_w8", "skinny_w4"; precision 1: "f32", "f32_splitk" */
+  /* ---- every GemmArgs term at op level. The behaviour above: all zero except m_dev = -1 and with_ws = 1. */
+  int32_t precision;       /* 0: operands rounded to bf16, launch_gemm_bf16; 1: operands kept, launch_gemm_f32 (out_lo / out_t / rms_out elements are then f32) */
+  const float* add2;       /* [add2_table_rows][N] f32 term added AFTER the activation, or NULL */
+  int32_t add2_table_rows; /* rows of the add2 table (>= M without add2_rows) */
+  const int32_t* add2_rows;/* [M] row of the table per output row (any order, repeats allowed), or NULL: row m */
+  float a_rms_eps;         /* > 0: RMSNorm of the A rows folded into the product (weight-streaming kernel) */
+  int32_t m_dev;           /* >= 0: uploaded as the device-side row count beside the launch bound M (0 is a row count); < 0: none */
+  int32_t lo_group;        /* > 0: out_lo is [N / lo_group][round_up(M, 128)][lo_group], returned as laid out (unwritten rows hold NaN) */
+  float* out_t;            /* [N][M] transposed result in the operand dtype, or NULL; stored with pitch ld_out_t */
+  int32_t ld_out_t;        /* 0: round_up(M, 4) + pad_out; else >= M, a multiple of 4 */
+  float* out_rms;          /* [M][N] second output of the split-K reduce (RMS-normalised rows), or NULL; needs gemm_reduce_can_norm */
+  float rms_eps;
+  int32_t pad_a, pad_w;    /* extra elements per row of A / W (16-byte multiples); the gap holds NaN */
+  int32_t pad_out;         /* extra elements per row of every output, of add and of add2 (a multiple of 8) */
+  int32_t with_ws;         /* 0: launch without sk_ws / sk_cnt (the paths the dispatcher takes for callers without a workspace) */
+  /* out: 32-bit (f32 / index) or 16-bit (bf16) words of the output buffers outside valid rows x valid columns that no longer hold the NaN pattern they
+   * were filled with. Buffers reach round_up(M, 128) rows plus the pitch gap; valid rows are m < min(M, m_dev). */
+  int32_t stray;
 } asr_probe_gemm_desc;
 int asr_probe_gemm(asr_probe_gemm_desc* d);
 /* The CTC head with frame log-probabilities through the same dispatcher: operands as asr_probe_gemm with `argmax` (bias required), the arg-max epilogue also

@@ -3,11 +3,13 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_ref as R
 from conftest import sub
 
 pytestmark = pytest.mark.gpu
 
 BF16, F32 = 0, 1
+WIDE_ORDERS = ("lib", (32, 1), (32, 2))       # the float32 orders of gemm_ref.py that a K = 512 product of ten thousand rows affords in a few seconds
 
 
 def _bf16_round(a):
@@ -277,6 +279,10 @@ def test_gemm_layernorm_folded_wide_tiles(M, want):
     ref = _ln_ref(a, w, bias)
     err = np.abs(out["lo"] - ref)
     assert (err <= 2.0 ** -7 * np.abs(ref) + 6e-3).all(), float(err.max())          # bf16 store (2^-8 relative) + f32 summation order
+    # ... and against the float64 statement: worst row's RMS and max abs within 3 x E_round of the float32 evaluations (gemm_ref.py)
+    exact, rounded = R.forms(a, w, orders=WIDE_ORDERS, bias=bias, act=1, ln_dim=K, only=("lo",))
+    ok, ratio = R.judge(out["lo"], exact, rounded, "lo")
+    assert ok and out["stray"] == 0, (ratio, out["stray"])
     # the same product through the 144 x 128 tiles (variant 6): other tiling, other summation order, same function
     base, kern6 = probe.gemm(a[:2304], w, bias, act=1, ln=True, variant=6)
     assert kern6 == "t144"
@@ -327,6 +333,11 @@ def test_gemm_producer_epilogue_at_batch64():
     lo = out["lo"].reshape(M, N // 32, 32).astype(np.float64)
     assert np.abs(out["stats"][..., 0] - lo.sum(-1)).max() < 1e-3
     assert np.abs(out["stats"][..., 1] - (lo * lo).sum(-1)).max() < 1e-2
+    exact, rounded = R.forms(a, w, orders=WIDE_ORDERS, add=add, only=("f32", "lo"))
+    for key in ("f32", "lo"):
+        ok, ratio = R.judge(out[key], exact, rounded, key)
+        assert ok, (key, ratio)
+    assert out["stray"] == 0
 
 
 def test_skinny_gemm_four_row_tiles(monkeypatch):
