@@ -43,6 +43,19 @@ class QwenAttnDesc(C.Structure):
                 ("stray", C.c_int32), ("qt", C.c_int32), ("nw", C.c_int32), ("kernel", C.c_char * 32)]
 
 
+class EncAttnDesc(C.Structure):
+    _fields_ = [("bf16", C.c_int32), ("head_dim", C.c_int32), ("n_heads", C.c_int32), ("kv_group", C.c_int32), ("causal", C.c_int32), ("batch", C.c_int32),
+                ("key_lens", _ip), ("q_lens", _ip), ("packed_qk", C.c_int32), ("slack_rows", C.c_int32), ("pad_fill_k", C.c_float), ("pad_fill_v", C.c_float),
+                ("q", _fp), ("k", _fp), ("v", _fp), ("ctx", _fp),
+                ("hd", C.c_int32), ("chunk", C.c_int32), ("qt", C.c_int32), ("waves", C.c_int32), ("grid_z", C.c_int32), ("n_qblocks", C.c_int32),
+                ("stray", C.c_int32)]
+
+
+class FsmnDesc(C.Structure):
+    _fields_ = [("bf16", C.c_int32), ("batch", C.c_int32), ("channels", C.c_int32), ("lens", _ip), ("pad_fill", C.c_float),
+                ("v", _fp), ("w", _fp), ("b", _fp), ("out", _fp), ("stray", C.c_int32)]
+
+
 class BeamSelectDesc(C.Structure):
     _fields_ = [("n_utt", C.c_int32), ("beam", C.c_int32), ("K", C.c_int32), ("ld", C.c_int32), ("first", C.c_int32), ("n_slots", C.c_int32),
                 ("n_stop", C.c_int32), ("topv", _fp), ("topi", _ip), ("cum", _fp), ("fin", _ip), ("len", _ip), ("next", _ip), ("done", _ip),
@@ -108,6 +121,8 @@ SIGNATURES = {
     "asr_probe_decode_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _fp, _fp, C.c_int, _fp]),
     "asr_probe_decode_attention": (C.c_int, [C.POINTER(DecodeAttnDesc)]),
     "asr_probe_qwen_attention": (C.c_int, [C.POINTER(QwenAttnDesc)]),
+    "asr_probe_encoder_attention": (C.c_int, [C.POINTER(EncAttnDesc)]),
+    "asr_probe_fsmn": (C.c_int, [C.POINTER(FsmnDesc)]),
     "asr_probe_beam_select": (C.c_int, [C.POINTER(BeamSelectDesc)]),
     "asr_probe_token_head": (C.c_int, [C.POINTER(TokenHeadDesc)]),
     "asr_probe_whisper_align": (C.c_int, [C.POINTER(WhisperAlignDesc)]),
@@ -424,6 +439,46 @@ def qwen_attention(qkv, H, KV, qn, kn, rope, eps, hist, T, S_max, bf16=True, ste
     _lib.check(load().asr_probe_qwen_attention(C.byref(d)))
     out.update(stray=d.stray, kernel=d.kernel.decode(), qt=d.qt, nw=d.nw)
     return out
+
+
+def encoder_attention(q, k, v, key_lens, n_heads, head_dim, bf16=True, q_lens=None, kv_group=1, causal=False, packed_qk=False, slack_rows=128,
+                      pad_fill_k=64.0, pad_fill_v=1e4):
+    """The ragged encoder attention through the sessions' launchers (asr_probe_encoder_attention, asr_mi355x_probe.h): q [sum Tq][H hd],
+    k / v [sum T][(H / kv_group) hd], dense. Returns dict(ctx [sum Tq][H hd], instance = (hd, chunk, qt, waves) of the bf16 kernel that ran,
+    grid_z (f32: the gridDim.z chosen; bf16: 0), n_qblocks, stray)."""
+    q, k, v = _f32(q), _f32(k), _f32(v)
+    key_lens = np.ascontiguousarray(key_lens, np.int32)
+    d = EncAttnDesc()
+    d.bf16, d.head_dim, d.n_heads, d.kv_group, d.causal, d.batch = int(bf16), head_dim, n_heads, kv_group, int(causal), key_lens.size
+    d.packed_qk, d.slack_rows, d.pad_fill_k, d.pad_fill_v = int(packed_qk), slack_rows, pad_fill_k, pad_fill_v
+    d.key_lens = key_lens.ctypes.data_as(_ip)
+    n_q = int(key_lens.sum())
+    if q_lens is not None:
+        q_lens = np.ascontiguousarray(q_lens, np.int32)
+        assert q_lens.shape == key_lens.shape
+        d.q_lens = q_lens.ctypes.data_as(_ip)
+        n_q = int(q_lens.sum())
+    dk = n_heads // kv_group * head_dim
+    assert q.shape == (n_q, n_heads * head_dim) and k.shape == v.shape == (int(key_lens.sum()), dk), (q.shape, k.shape, v.shape)
+    ctx = np.zeros((n_q, n_heads * head_dim), np.float32)
+    d.q, d.k, d.v, d.ctx = (x.ctypes.data_as(_fp) for x in (q, k, v, ctx))
+    d.stray = -1
+    _lib.check(load().asr_probe_encoder_attention(C.byref(d)))
+    return dict(ctx=ctx, instance=(d.hd, d.chunk, d.qt, d.waves), grid_z=d.grid_z, n_qblocks=d.n_qblocks, stray=int(d.stray))
+
+
+def fsmn(v, w, b, lens, bf16=False, pad_fill=1e4):
+    """launch_fsmn on v [sum T][C] with poisoned pad columns (asr_probe_fsmn) -> (out [sum T][C] f32, stray)."""
+    v, w, b = _f32(v), _f32(w), _f32(b)
+    lens = np.ascontiguousarray(lens, np.int32)
+    C_ = v.shape[1]
+    assert v.shape[0] == int(lens.sum()) and w.shape == (C_, 11) and b.shape == (C_,), (v.shape, w.shape, b.shape)
+    out = np.zeros_like(v)
+    d = FsmnDesc()
+    d.bf16, d.batch, d.channels, d.pad_fill, d.stray = int(bf16), lens.size, C_, pad_fill, -1
+    d.lens, d.v, d.w, d.b, d.out = lens.ctypes.data_as(_ip), v.ctypes.data_as(_fp), w.ctypes.data_as(_fp), b.ctypes.data_as(_fp), out.ctypes.data_as(_fp)
+    _lib.check(load().asr_probe_fsmn(C.byref(d)))
+    return out, int(d.stray)
 
 
 def beam_select(beam, K, n_slots, topv, topi, cum, fin, length, nxt, done, src_in, tok_in, src_out, tok_out, stop=(), first=False):

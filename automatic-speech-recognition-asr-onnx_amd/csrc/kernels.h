@@ -322,6 +322,11 @@ void launch_layernorm_with_bf16_copy(const float* x, int ld_x, int rows, int D, 
 // ---- multi-head self-attention over packed ragged utterances (no mask inside an utterance).
 // q, k: [rows][ld] row-major; vt: [H*HD][ld_vt] (time-contiguous); ctx out: [rows][ld_ctx].
 // Scale is pre-folded into q and k (d^-1/4 each, Export_SenseVoice.py:210-216).
+// Pad rows: the bf16 kernel stages keys in 32-key sub-tiles, so it READS the K rows and V^T columns from an utterance's T up to the next multiple of 32 (the
+// rows up to its 16-row boundary, then whatever follows: the next utterance, or slack; reads past the allocation are clamped to its last row / last 8
+// columns -- n_rows_alloc = ld_vt). Their scores are masked to -inf and their probabilities are exactly 0, but the zeros still enter the P.V product:
+// every such row and column must hold FINITE values (0 x NaN and 0 x Inf are NaN). Any finite value gives the same bits. NaN / Inf there is outside the
+// contract. The f32 kernel reads keys [0, T) only; it keeps a row's scores in LDS and takes max_T <= 2048 (launch_attention_f32 refuses more).
 struct AttnArgs {
   const void* q; const void* k; int ld_qk;   // ld_qk: row stride of k (and of q unless ld_q is set)
   int ld_q = 0;
@@ -345,6 +350,10 @@ void attention_geometry(int max_T, int head_dim, int* qt, int* n_waves);
 void launch_attention_bf16_hd128(const AttnArgs& a, hipStream_t s);
 void launch_attention_bf16_hd64(const AttnArgs& a, hipStream_t s);
 void launch_attention_f32(const AttnArgs& a, int head_dim, hipStream_t s);
+// what this thread's last launch_attention_* ran: the bf16 instance <hd, chunk, qt> and its waves per workgroup (grid_z = 0), or the f32 kernel
+// (chunk = qt = 0, waves = 4) and its gridDim.z: test hook
+struct AttnLaunchInfo { int hd = 0, chunk = 0, qt = 0, waves = 0, grid_z = 0; };
+const AttnLaunchInfo& attention_last_launch();
 
 // ---- fused SANM attention half for windows of <= 144 rows (sanm_fused.hip): per (utterance, head) workgroup
 // q|k|v projection -> attention -> FSMN, intermediates in LDS. h: [rows][ld_h] operand-dtype LayerNorm output;

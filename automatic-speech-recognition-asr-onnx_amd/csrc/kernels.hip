@@ -1832,9 +1832,13 @@ void launch_layernorm_fp8(const float* x, int ld_x, int rows, int D, float eps, 
   HIP_CHECK(hipGetLastError());
 }
 
+static thread_local AttnLaunchInfo g_attn_launch;
+const AttnLaunchInfo& attention_last_launch() { return g_attn_launch; }
+
 template <int HD, int CHUNK, int QT>
 static void launch_attn_inst(const AttnArgs& a, hipStream_t s) {
   constexpr int lds = CHUNK * HD * 2 * 2;
+  g_attn_launch = AttnLaunchInfo{HD, CHUNK, QT, a.n_waves, 0};
   static PerDeviceOnce attr_once;
   if (attr_once.first()) {
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bf16_kernel<HD, CHUNK, QT>),
@@ -1875,10 +1879,13 @@ void launch_attention_bf16_hd64(const AttnArgs& a, hipStream_t s) {
 
 void launch_attention_f32(const AttnArgs& a, int head_dim, hipStream_t s) {
   ASR_REQUIRE(head_dim <= 128 && head_dim % 4 == 0, "attention_f32: head_dim %d unsupported", head_dim);
+  // the kernel keeps one query row's scores in LDS, ATT32_MAXT floats per wave: a longer utterance would write past its row
+  ASR_REQUIRE(a.max_T >= 1 && a.max_T <= ATT32_MAXT, "attention_f32: longest utterance %d outside 1 .. %d keys (the f32 kernel's LDS score row)", a.max_T, ATT32_MAXT);
   AttnArgs b = a;
   if (b.ld_q == 0) b.ld_q = b.ld_qk;
   const int wgs = a.n_qblocks * a.n_heads;
   const int z = wgs >= 1024 ? 1 : wgs >= 256 ? 4 : 16;           // few query blocks (single utterances): one row per wave
+  g_attn_launch = AttnLaunchInfo{head_dim, 0, 0, 4, z};
   hipLaunchKernelGGL(attn_f32_kernel, dim3(a.n_qblocks, a.n_heads, z), dim3(256), 0, s, b, head_dim);
   HIP_CHECK(hipGetLastError());
 }

@@ -1857,3 +1857,196 @@ extern "C" int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d) {
     }
   });
 }
+
+// =========================================================================================== encoder attention / FSMN on poisoned buffers
+namespace {
+
+// A logical buffer of n elements inside a larger allocation: `guard` elements in front of it and behind it, every element of the allocation `fill` before
+// the rows are placed. A read that strays off the logical buffer then finds a finite number, not an unmapped page.
+template <typename T>
+struct Poisoned {
+  std::vector<T> host;
+  size_t guard = 0, n = 0;
+  T* dev = nullptr;
+  Poisoned(size_t n_, size_t guard_, float fill) : host(n_ + 2 * guard_, elem_from_f32<T>(fill)), guard(guard_), n(n_) {}
+  T& at(size_t i) { return host[guard + i]; }
+  T* upload(Tmp& t) {
+    T* base = (T*)t.alloc(host.size() * sizeof(T));
+    HIP_CHECK(hipMemcpy(base, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+    dev = base + guard;
+    return dev;
+  }
+  // after the launch: the logical buffer -> out; returns the guard elements whose bits changed
+  int64_t download(std::vector<T>& out) {
+    std::vector<T> all(host.size());
+    HIP_CHECK(hipMemcpy(all.data(), dev - guard, all.size() * sizeof(T), hipMemcpyDeviceToHost));
+    int64_t bad = 0;
+    for (size_t i = 0; i < guard; ++i) bad += (same_bits(all[i], host[i]) ? 0 : 1) + (same_bits(all[guard + n + i], host[guard + n + i]) ? 0 : 1);
+    out.assign(all.begin() + guard, all.begin() + guard + n);
+    return bad;
+  }
+};
+
+template <typename T>
+void probe_encoder_attention(asr_probe_enc_attn_desc* d) {
+  const int B = d->batch, H = d->n_heads, G = d->kv_group, HD = d->head_dim;
+  const bool bf = sizeof(T) == 2, cross = d->q_lens != nullptr;
+  ASR_REQUIRE(B > 0 && H > 0 && G >= 1 && H % G == 0 && d->key_lens && d->q && d->k && d->v && d->ctx, "probe_encoder_attention: bad argument");
+  ASR_REQUIRE(HD == 64 || HD == 128, "probe_encoder_attention: head_dim %d (64 or 128)", HD);
+  ASR_REQUIRE(bf || (G == 1 && !d->causal), "probe_encoder_attention: the f32 kernel has no causal / grouped-query form");
+  ASR_REQUIRE(!d->packed_qk || (!cross && G == 1), "probe_encoder_attention: the packed q|k layout is the self form with one k head per q head");
+  ASR_REQUIRE(d->slack_rows >= 0 && d->slack_rows % 8 == 0, "probe_encoder_attention: slack_rows %d (0 or a multiple of 8)", d->slack_rows);
+  ASR_REQUIRE(std::isfinite(d->pad_fill_k) && std::isfinite(d->pad_fill_v), "probe_encoder_attention: the poison must be finite");
+  const int KV = H / G, dq = H * HD, dk = KV * HD;
+  std::vector<UttPlan> kp(B), qp(B);
+  std::memset(kp.data(), 0, kp.size() * sizeof(UttPlan));
+  std::memset(qp.data(), 0, qp.size() * sizeof(UttPlan));
+  int max_T = 0, rows_k = 0, rows_q = 0;
+  for (int b = 0; b < B; ++b) {
+    const int Tk = d->key_lens[b], Tq = cross ? d->q_lens[b] : Tk;
+    // (a session lays the query blocks of the cross form over the KEY rows -- csrc/sensevoice.hip, the Paraformer decoder -- so it has Tq <= T)
+    ASR_REQUIRE(Tk >= 1 && Tq >= 1 && Tq <= Tk, "probe_encoder_attention: utterance %d has %d keys, %d queries", b, Tk, Tq);
+    kp[b].T = kp[b].n_lfr = Tk; kp[b].row_off = rows_k;
+    qp[b].T = qp[b].n_lfr = Tq; qp[b].row_off = rows_q;
+    rows_k += round_up(Tk, 16); rows_q += round_up(Tq, 16);
+    max_T = std::max(max_T, Tk);
+  }
+  int qt = 0, nw = 4, q_rows = 64;
+  if (bf) { attention_geometry(max_T, HD, &qt, &nw); q_rows = 16 * qt * nw; }
+  std::vector<int32_t> qb_utt, qb_q0;
+  for (int b = 0; b < B; ++b)
+    for (int q0 = 0; q0 < d->key_lens[b]; q0 += q_rows) { qb_utt.push_back(b); qb_q0.push_back(q0); }
+  const int alloc_k = rows_k + d->slack_rows, alloc_q = rows_q + d->slack_rows;
+  const int ld_k = d->packed_qk ? 2 * dq : dk, ld_q = d->packed_qk ? 2 * dq : dq;
+  const size_t guard = (size_t)64 * 2 * dq;
+  // ---- operands: poison everywhere, then the rows of the utterances
+  Poisoned<T> hk((size_t)alloc_k * ld_k, guard, d->pad_fill_k), hv((size_t)dk * alloc_k, guard, d->pad_fill_v);
+  Poisoned<T> hq(d->packed_qk ? 0 : (size_t)alloc_q * ld_q, guard, d->pad_fill_k), hc((size_t)alloc_q * dq, guard, d->pad_fill_v);
+  Poisoned<T>& hq_in = d->packed_qk ? hk : hq;
+  size_t rk = 0, rq = 0;
+  for (int b = 0; b < B; ++b) {
+    for (int t = 0; t < kp[b].T; ++t, ++rk) {
+      const size_t row = (size_t)kp[b].row_off + t;
+      for (int c = 0; c < dk; ++c) {
+        hk.at(row * ld_k + (d->packed_qk ? dq : 0) + c) = elem_from_f32<T>(d->k[rk * dk + c]);
+        hv.at((size_t)c * alloc_k + row) = elem_from_f32<T>(d->v[rk * dk + c]);
+      }
+    }
+    for (int t = 0; t < qp[b].T; ++t, ++rq) {
+      const size_t row = (size_t)qp[b].row_off + t;
+      for (int c = 0; c < dq; ++c) hq_in.at(row * ld_q + c) = elem_from_f32<T>(d->q[rq * dq + c]);
+    }
+  }
+  Tmp t;
+  auto up_raw = [&](const void* h, size_t bytes) -> void* {
+    void* p = t.alloc(bytes);
+    HIP_CHECK(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+    return p;
+  };
+  T* dkb = hk.upload(t);
+  T* dqb = d->packed_qk ? dkb : hq.upload(t);
+  AttnArgs aa;
+  aa.q = dqb; aa.k = dkb + (d->packed_qk ? dq : 0); aa.ld_qk = ld_k;
+  aa.ld_q = (cross || G > 1) ? ld_q : 0;                  // (the self form leaves ld_q to the launcher, as the sessions do)
+  aa.vt = hv.upload(t); aa.ld_vt = alloc_k;
+  aa.ctx = hc.upload(t); aa.ld_ctx = dq;
+  aa.plan = (const UttPlan*)up_raw(kp.data(), kp.size() * sizeof(UttPlan));
+  if (cross) aa.q_plan = (const UttPlan*)up_raw(qp.data(), qp.size() * sizeof(UttPlan));
+  aa.qb_utt = (const int32_t*)up_raw(qb_utt.data(), qb_utt.size() * 4);
+  aa.qb_q0 = (const int32_t*)up_raw(qb_q0.data(), qb_q0.size() * 4);
+  aa.n_qblocks = (int)qb_utt.size(); aa.n_heads = H; aa.qt = qt; aa.n_waves = nw; aa.max_T = max_T;
+  aa.causal = d->causal ? 1 : 0; aa.kv_group = G;
+  d->n_qblocks = aa.n_qblocks;
+  d->hd = d->chunk = d->qt = d->waves = d->grid_z = 0;
+  if (!bf) launch_attention_f32(aa, HD, nullptr);
+  else if (HD == 128) launch_attention_bf16_hd128(aa, nullptr);
+  else launch_attention_bf16_hd64(aa, nullptr);
+  const AttnLaunchInfo ran = attention_last_launch();
+  d->hd = ran.hd; d->chunk = ran.chunk; d->qt = ran.qt; d->waves = ran.waves; d->grid_z = ran.grid_z;
+  HIP_CHECK(hipDeviceSynchronize());
+  // ---- results: the query rows; stray = context elements outside them (pad rows, slack, guards) whose bits changed
+  std::vector<T> ctx;
+  int64_t stray = hc.download(ctx);
+  std::vector<unsigned char> valid((size_t)alloc_q, 0);
+  rq = 0;
+  for (int b = 0; b < B; ++b)
+    for (int tq = 0; tq < qp[b].T; ++tq, ++rq) {
+      const size_t row = (size_t)qp[b].row_off + tq;
+      valid[row] = 1;
+      for (int c = 0; c < dq; ++c) d->ctx[rq * dq + c] = elem_to_f32(ctx[row * dq + c]);
+    }
+  for (int r = 0; r < alloc_q; ++r)
+    if (!valid[r])
+      for (int c = 0; c < dq; ++c) stray += same_bits(ctx[(size_t)r * dq + c], hc.at((size_t)r * dq + c)) ? 0 : 1;
+  d->stray = (int32_t)std::min<int64_t>(stray, 0x7fffffff);
+}
+
+template <typename T>
+void probe_fsmn(asr_probe_fsmn_desc* d) {
+  const int B = d->batch, C = d->channels;
+  ASR_REQUIRE(B > 0 && C > 0 && d->lens && d->v && d->w && d->b && d->out, "probe_fsmn: bad argument");
+  ASR_REQUIRE(std::isfinite(d->pad_fill), "probe_fsmn: the poison must be finite");
+  std::vector<UttPlan> plan(B);
+  std::memset(plan.data(), 0, plan.size() * sizeof(UttPlan));
+  int rows = 0;
+  for (int b = 0; b < B; ++b) {
+    ASR_REQUIRE(d->lens[b] >= 1, "probe_fsmn: empty utterance %d", b);
+    plan[b].T = plan[b].n_lfr = d->lens[b]; plan[b].row_off = rows;
+    rows += round_up(d->lens[b], 16);
+  }
+  const int Mpad = round_up(rows, 128);                   // the sessions' packed row count: V^T's leading dimension and the launch's row bound
+  std::vector<int32_t> row_utt(Mpad, -1);
+  for (int b = 0; b < B; ++b)
+    for (int r = 0; r < round_up(d->lens[b], 16); ++r) row_utt[plan[b].row_off + r] = b;
+  Poisoned<T> hv((size_t)C * Mpad, 4096, d->pad_fill);
+  Poisoned<float> ho((size_t)Mpad * C, 4096, d->pad_fill);
+  size_t r = 0;
+  for (int b = 0; b < B; ++b)
+    for (int tt = 0; tt < plan[b].T; ++tt, ++r)
+      for (int c = 0; c < C; ++c) hv.at((size_t)c * Mpad + plan[b].row_off + tt) = elem_from_f32<T>(d->v[r * C + c]);
+  Tmp t;
+  auto up_raw = [&](const void* h, size_t bytes) -> void* {
+    void* p = t.alloc(bytes);
+    HIP_CHECK(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+    return p;
+  };
+  const T* dvt = hv.upload(t);
+  float* dout = ho.upload(t);
+  launch_fsmn<T>(dvt, Mpad, (const float*)up_raw(d->w, (size_t)C * 11 * 4), (const float*)up_raw(d->b, (size_t)C * 4), C, 11,
+                 (const UttPlan*)up_raw(plan.data(), plan.size() * sizeof(UttPlan)), (const int32_t*)up_raw(row_utt.data(), row_utt.size() * 4), Mpad, dout, C,
+                 nullptr);
+  HIP_CHECK(hipDeviceSynchronize());
+  // ---- results: the utterances' rows; stray = guard elements whose bits changed + pad rows (an utterance's T .. its 16-row boundary, rows of no
+  // utterance) that are not the zeros the out-projection adds
+  std::vector<float> out;
+  int64_t stray = ho.download(out);
+  std::vector<unsigned char> valid((size_t)Mpad, 0);
+  r = 0;
+  for (int b = 0; b < B; ++b)
+    for (int tt = 0; tt < plan[b].T; ++tt, ++r) {
+      valid[plan[b].row_off + tt] = 1;
+      std::memcpy(d->out + r * C, &out[(size_t)(plan[b].row_off + tt) * C], (size_t)C * 4);
+    }
+  for (int m = 0; m < Mpad; ++m)
+    if (!valid[m])
+      for (int c = 0; c < C; ++c) stray += out[(size_t)m * C + c] == 0.0f ? 0 : 1;
+  d->stray = (int32_t)std::min<int64_t>(stray, 0x7fffffff);
+}
+
+}  // namespace
+
+extern "C" int asr_probe_encoder_attention(asr_probe_enc_attn_desc* d) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d, "probe_encoder_attention: null descriptor");
+    asr_require_device(0);
+    if (d->bf16) probe_encoder_attention<bf16_t>(d); else probe_encoder_attention<float>(d);
+  });
+}
+
+extern "C" int asr_probe_fsmn(asr_probe_fsmn_desc* d) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d, "probe_fsmn: null descriptor");
+    asr_require_device(0);
+    if (d->bf16) probe_fsmn<bf16_t>(d); else probe_fsmn<float>(d);
+  });
+}

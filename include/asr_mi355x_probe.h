@@ -184,6 +184,42 @@ typedef struct asr_probe_qwen_attn_desc {
 } asr_probe_qwen_attn_desc;
 int asr_probe_qwen_attention(asr_probe_qwen_attn_desc* d);
 
+/* The ragged encoder attention (launch_attention_bf16_hd128 / _hd64 / launch_attention_f32, csrc/kernels.hip) in every form a session launches, on host
+ * arrays laid out as a session lays them out: utterance b's rows start at the sum of the earlier lengths rounded up to 16, V is stored transposed with
+ * the packed row count as its leading dimension, and the query blocks hold 16 qt waves rows from attention_geometry(longest utterance) (f32: 64).
+ *   q [sum Tq][n_heads hd], k / v [sum T][(n_heads / kv_group) hd], ctx [sum Tq][n_heads hd] (dense, utterance after utterance; rounded to bf16 on upload).
+ *   key_lens [batch]; q_lens null: the self form; else the cross form (q_plan, ld_q != ld_qk) with q_lens[b] <= key_lens[b]: the query blocks are laid over
+ *   the key rows, as the Paraformer decoder's are.   causal, kv_group: bf16 only.   packed_qk: q and k share one buffer of 2 n_heads hd columns, k at column
+ *   n_heads hd, as the Qwen3 audio encoder launches it (self form, kv_group 1).
+ *   slack_rows: rows allocated behind the last utterance's 16-row boundary (0 or a multiple of 8): n_rows_alloc == ld_vt == sum of the rounded lengths + slack.
+ *   pad_fill_k / pad_fill_v: FINITE values in every K (and Q) row / every V^T column that belongs to no key -- rows T .. roundup16(T) of every utterance and
+ *   the slack -- and in the guard bytes in front of and behind every buffer (ctx: pad_fill_v), so that a stray read is a wrong number and not a fault.
+ * Out: hd, chunk, qt, waves: the bf16 instance that ran (grid_z 0); f32: hd, waves 4, grid_z = the gridDim.z chosen (chunk, qt 0). n_qblocks. stray: context
+ * elements outside the query rows, guards included, whose bits changed. */
+typedef struct asr_probe_enc_attn_desc {
+  int32_t bf16, head_dim, n_heads, kv_group, causal, batch;
+  const int32_t* key_lens; const int32_t* q_lens;
+  int32_t packed_qk, slack_rows;
+  float pad_fill_k, pad_fill_v;
+  const float* q; const float* k; const float* v;
+  float* ctx;
+  int32_t hd, chunk, qt, waves, grid_z, n_qblocks, stray;
+} asr_probe_enc_attn_desc;
+int asr_probe_encoder_attention(asr_probe_enc_attn_desc* d);
+
+/* launch_fsmn (11 taps) on v [sum T][channels] as a session lays it out (V^T [channels][round_up(rows, 128)], rows rounded up to 16 per utterance), every
+ * element of V^T that belongs to no utterance row and the guards around both buffers = pad_fill (finite). w [channels][11], b [channels],
+ * out [sum T][channels] (f32). stray: guard elements whose bits changed + output elements of pad rows that are not zero. */
+typedef struct asr_probe_fsmn_desc {
+  int32_t bf16, batch, channels;
+  const int32_t* lens;
+  float pad_fill;
+  const float* v; const float* w; const float* b;
+  float* out;
+  int32_t stray;
+} asr_probe_fsmn_desc;
+int asr_probe_fsmn(asr_probe_fsmn_desc* d);
+
 /* One pass of the beam-search ranking (launch_beam_select, shared by the Qwen3-ASR and Whisper searches) on host arrays. Hypotheses of utterance b
  * are rows b * beam + r. topv / topi: the rows' K best (log-prob, id) pairs, [rows][K] ([n_utt][K] when first = 1); cum / fin / len / next [rows] and
  * done [n_utt] are the search state, updated in place; stop [n_stop]; src_in / tok_in [rows][ld] the tables the pass reads, src_out / tok_out [rows][ld]
