@@ -108,7 +108,23 @@ class HotwordRankDesc(C.Structure):
                 ("iters", C.c_int32), ("ms_topk", C.c_float), ("ms_rerank", C.c_float)]
 
 
+class DecGemmDesc(C.Structure):
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("plan_M", C.c_int32), ("lda", C.c_int32), ("ldw", C.c_int32), ("ld_add", C.c_int32),
+                ("ld_out_f32", C.c_int32), ("ld_out_lo", C.c_int32), ("wkind", C.c_int32), ("a", C.c_void_p), ("w_bf16", C.c_void_p), ("wq", C.c_void_p),
+                ("w_scale", _fp), ("w_scale8", C.c_void_p), ("bias", _fp), ("fold", C.c_int32), ("ln_eps", C.c_float), ("add", _fp), ("act", C.c_int32),
+                ("out_f32", _fp), ("out_lo", _fp), ("with_ws", C.c_int32), ("repeats", C.c_int32), ("force_nt", C.c_int32), ("force_splits", C.c_int32),
+                ("force_row_blocks", C.c_int32), ("pre_M", C.c_int32), ("pre_splits", C.c_int32), ("mt", C.c_int32), ("nt", C.c_int32), ("splits", C.c_int32),
+                ("row_blocks", C.c_int32), ("stray", C.c_int32), ("tickets_zero", C.c_int32)]
+
+
 SIGNATURES = {
+    "asr_probe_decode_gemm_desc": (C.c_int, [C.POINTER(DecGemmDesc)]),
+    "asr_probe_quantize_fp8_ld": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, _fp, C.c_void_p]),
+    "asr_probe_quantize_mxfp4_ld": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "asr_probe_quantize_crosskv_fp8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, C.c_int, C.c_int, C.c_void_p, _fp]),
+    "asr_probe_layernorm_fp8": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "asr_probe_gemm_fp8_v2": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, _fp, C.c_float, _fp, _fp, C.c_int, C.c_int, C.c_float,
+                                        C.c_void_p, C.c_int, _fp, C.c_int, C.POINTER(C.c_uint64)]),
     "asr_probe_gemm": (C.c_int, [C.POINTER(GemmDesc)]),
     "asr_probe_ctc_head": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, _ip, _fp, _ip, C.c_char_p]),
     "asr_probe_ctc_topk": (C.c_int, [C.c_int] * 3 + [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _fp, C.c_char_p]),
@@ -753,21 +769,38 @@ def _bf16_to_f32(bits):
     return (np.ascontiguousarray(bits, np.uint16).astype(np.uint32) << 16).view(np.float32)
 
 
-def quantize_fp8(w):
-    """Row quantiser of the FP8 mode on an f32 array (rounded to bf16 first): (bytes [N][K] uint8, scale [N] f32, dequantised f32 [N][K])."""
+def _pitched(wb, ld):
+    """[N][K] bf16 bits -> [N][ld] with 0x7f00 (1.7e38) in the gap: a quantiser that read it would take its scale from it."""
+    out = np.full((wb.shape[0], ld), 0x7F00, np.uint16)
+    out[:, :wb.shape[1]] = wb
+    return out
+
+
+def quantize_fp8(w, ld=0):
+    """Row quantiser of the FP8 mode on an f32 array (rounded to bf16 first): (bytes [N][K] uint8, scale [N] f32, dequantised f32 [N][K]). ld > K: the rows are
+    uploaded with that pitch, the gap holding 1.7e38."""
     wb = _bf16_bits(w)
     N, K = wb.shape
     q = np.zeros((N, K), np.uint8); sc = np.zeros((N,), np.float32); dq = np.zeros((N, K), np.uint16)
-    _lib.check(load().asr_probe_quantize_fp8(wb.ctypes.data, N, K, q.ctypes.data, sc.ctypes.data_as(_fp), dq.ctypes.data))
+    if ld:
+        wp = _pitched(wb, ld)
+        _lib.check(load().asr_probe_quantize_fp8_ld(wp.ctypes.data, ld, N, K, q.ctypes.data, sc.ctypes.data_as(_fp), dq.ctypes.data))
+    else:
+        _lib.check(load().asr_probe_quantize_fp8(wb.ctypes.data, N, K, q.ctypes.data, sc.ctypes.data_as(_fp), dq.ctypes.data))
     return q, sc, _bf16_to_f32(dq)
 
 
-def quantize_mxfp4(w):
-    """Block quantiser of the MXFP4 mode on an f32 array (rounded to bf16 first): (nibbles [N][K / 2] uint8, e8m0 scales [N][K / 32] uint8, dequantised f32 [N][K])."""
+def quantize_mxfp4(w, ld=0):
+    """Block quantiser of the MXFP4 mode on an f32 array (rounded to bf16 first): (nibbles [N][K / 2] uint8, e8m0 scales [N][K / 32] uint8, dequantised f32 [N][K]).
+    ld > K: as quantize_fp8."""
     wb = _bf16_bits(w)
     N, K = wb.shape
     q = np.zeros((N, K // 2), np.uint8); sc = np.zeros((N, K // 32), np.uint8); dq = np.zeros((N, K), np.uint16)
-    _lib.check(load().asr_probe_quantize_mxfp4(wb.ctypes.data, N, K, q.ctypes.data, sc.ctypes.data, dq.ctypes.data))
+    if ld:
+        wp = _pitched(wb, ld)
+        _lib.check(load().asr_probe_quantize_mxfp4_ld(wp.ctypes.data, ld, N, K, q.ctypes.data, sc.ctypes.data, dq.ctypes.data))
+    else:
+        _lib.check(load().asr_probe_quantize_mxfp4(wb.ctypes.data, N, K, q.ctypes.data, sc.ctypes.data, dq.ctypes.data))
     return q, sc, _bf16_to_f32(dq)
 
 
@@ -799,6 +832,81 @@ def decode_gemm(a, w=None, w8=None, scale=None, bias=None, fold=False):
                                             None if s is None else s.ctypes.data_as(_fp), None if b is None else b.ctypes.data_as(_fp), int(fold),
                                             out.ctypes.data_as(_fp)))
     return out
+
+
+def decode_gemm_desc(a, w, wq=None, w_scale=None, w_scale8=None, bias=None, fold=False, ln_eps=1e-5, add=None, act=0, want=("f32",), plan_M=0, lda=0, ldw=0,
+                     ld_add=0, ld_out_f32=0, ld_out_lo=0, with_ws=True, repeats=1, nt=0, splits=0, row_blocks=0, pre_M=0, pre_splits=0):
+    """The decode GEMM with every DecGemmArgs term (asr_probe_decode_gemm_desc). a [M][K], w [N][K] f32, both exact in bf16 after rounding here; w is the weight
+    matrix, or with wq its dequantised copy: (wq [N][K] uint8, w_scale [N]) = e4m3 bytes, (wq [N][K / 2], w_scale8 [N][K / 32]) = e2m1 nibbles + e8m0.
+    nt / splits / row_blocks force the plan (0: decode_gemm_plan). -> dict: "f32" / "lo" [M][N], "plan" = (mt, nt, splits, row_blocks) as launched, "stray",
+    "tickets_zero"."""
+    ab, wb = _bf16_bits(a), _bf16_bits(w)
+    (M, K), N = ab.shape, wb.shape[0]
+    d = DecGemmDesc(M=M, N=N, K=K, plan_M=plan_M, lda=lda, ldw=ldw, ld_add=ld_add, ld_out_f32=ld_out_f32, ld_out_lo=ld_out_lo, fold=int(fold), ln_eps=ln_eps,
+                    act=act, with_ws=int(with_ws), repeats=repeats, force_nt=nt, force_splits=splits, force_row_blocks=row_blocks, pre_M=pre_M, pre_splits=pre_splits)
+    keep = [ab, wb]
+    d.a, d.w_bf16 = ab.ctypes.data, wb.ctypes.data
+    if wq is not None:
+        q = np.ascontiguousarray(wq, np.uint8); keep.append(q); d.wq = q.ctypes.data
+        if w_scale8 is not None:
+            s8 = np.ascontiguousarray(w_scale8, np.uint8); keep.append(s8); d.w_scale8 = s8.ctypes.data; d.wkind = 2
+            assert q.shape == (N, K // 2) and s8.shape == (N, K // 32)
+        else:
+            sc = _f32(w_scale); keep.append(sc); d.w_scale = sc.ctypes.data_as(_fp); d.wkind = 1
+            assert q.shape == (N, K) and sc.shape == (N,)
+    if bias is not None:
+        bias = _f32(bias); keep.append(bias); d.bias = bias.ctypes.data_as(_fp)
+    if add is not None:
+        add = _f32(add); keep.append(add); d.add = add.ctypes.data_as(_fp)
+        assert add.shape == (M, N)
+    out = {}
+    for key in want:
+        out[key] = np.zeros((M, N), np.float32)
+        setattr(d, {"f32": "out_f32", "lo": "out_lo"}[key], out[key].ctypes.data_as(_fp))
+    _lib.check(load().asr_probe_decode_gemm_desc(C.byref(d)))
+    out["plan"], out["stray"], out["tickets_zero"] = (d.mt, d.nt, d.splits, d.row_blocks), d.stray, bool(d.tickets_zero)
+    return out
+
+
+def quantize_crosskv_fp8(slabs, row_off, n_lfr, dq_in_place=False):
+    """launch_quantize_crosskv_fp8 on an f32 array [n_slabs][rows][64] (rounded to bf16 first): (bytes [n_slabs][rows][64], 0xa5 where nothing was written;
+    scale [n_slabs][batch]; the slabs after the launch as f32)."""
+    sb = _bf16_bits(slabs)
+    S, R, hd = sb.shape
+    assert hd == 64
+    ro, nl = _i32(row_off), _i32(n_lfr)
+    q = np.zeros((S, R, 64), np.uint8); sc = np.zeros((S, ro.size), np.float32)
+    _lib.check(load().asr_probe_quantize_crosskv_fp8(sb.ctypes.data, S, R, _ptr(ro, _ip), _ptr(nl, _ip), ro.size, int(dq_in_place), q.ctypes.data, _ptr(sc, _fp)))
+    return q, sc, _bf16_to_f32(sb)
+
+
+def layernorm_fp8(x, D, eps, inv_scale, ld_out):
+    """launch_layernorm_fp8 on x [rows][ld_x] f32 (the first D columns are the row): bytes [rows + 4][ld_out], 0xa5 where nothing was written."""
+    x = _f32(x)
+    rows, ld_x = x.shape
+    out = np.zeros((rows + 4, ld_out), np.uint8)
+    _lib.check(load().asr_probe_layernorm_fp8(_ptr(x, _fp), ld_x, rows, D, eps, inv_scale, ld_out, out.ctypes.data))
+    return out
+
+
+def gemm_fp8_v2(a8, w8, w_scale, bias, a_scale=1.0, add=None, act=0, out_inv_scale=1.0, lda=0, ldw=0, ld_add=0, ld_out=0):
+    """FP8 matrix-pipe GEMM with pitches (0: the extent), out_inv_scale and the saturation count: -> (out as laid out, [M + 8][ld_out], uint8 with 0xa5 where nothing
+    was written / float32 with NaN there when `add` is given; sat_count)."""
+    a8, w8 = np.ascontiguousarray(a8, np.uint8), np.ascontiguousarray(w8, np.uint8)
+    (M, K), N = a8.shape, w8.shape[0]
+    sc, b = _f32(w_scale), _f32(bias)
+    ld_out = ld_out or N
+    sat = C.c_uint64(0)
+    if add is None:
+        out = np.zeros((M + 8, ld_out), np.uint8)
+        _lib.check(load().asr_probe_gemm_fp8_v2(M, N, K, a8.ctypes.data, lda or K, w8.ctypes.data, ldw or K, _ptr(sc, _fp), a_scale, _ptr(b, _fp), None, 0, act,
+                                                out_inv_scale, out.ctypes.data, ld_out, None, 0, C.byref(sat)))
+    else:
+        r = _f32(add)
+        out = np.zeros((M + 8, ld_out), np.float32)
+        _lib.check(load().asr_probe_gemm_fp8_v2(M, N, K, a8.ctypes.data, lda or K, w8.ctypes.data, ldw or K, _ptr(sc, _fp), a_scale, _ptr(b, _fp), _ptr(r, _fp),
+                                                ld_add or N, act, out_inv_scale, None, 0, _ptr(out, _fp), ld_out, C.byref(sat)))
+    return out, int(sat.value)
 
 
 def e4m3_table():

@@ -16,6 +16,9 @@
 // producing GEMM) and  LN(x) W^T = rstd (x W^T - mean c),  c[n] = sum_k W[n][k];  sum(x) and sum(x^2) of every row come from two extra
 // MFMAs per activation fragment (ones x A^T, A A^T) on the otherwise idle matrix pipe. This removes the per-workgroup LayerNorm prologue
 // of the weight-streaming kernel (every workgroup re-normalising all rows: +4.7 us per launch) and the stand-alone LayerNorm launch.
+// The variance is the one-pass form sum(x^2) / K - mean^2 (clamped at 0) in f32. Summed the way this kernel sums (32-element steps, eight wave shares, splits in
+// order) it stays within the float32 rounding budget of the two-pass form up to |mean| / std = 100 at K <= 1024 on the CPU reference (tests/lowbit_ref.py;
+// tests/test_decode_gemm_ref_gpu.py runs 0, 0.3 and 3); what a trained residual stream carries there has not been measured.
 //
 // FP8 weights (W8, precision mode ASR_PRECISION_FP8W): W holds OCP e4m3 bytes [N][K] with one power-of-two f32 scale per output
 // column; a lane loads 8 bytes per fragment, widens them to bf16 in registers (exact: 4 significant bits) and the epilogue multiplies the
@@ -398,18 +401,36 @@ void decode_gemm_plan(const DecGemmArgs& g, int* nt, int* splits, int* row_block
   if (row_blocks) *row_blocks = best_rb;
 }
 
-void launch_decode_gemm(const DecGemmArgs& g, hipStream_t s) {
+// the admissibility rules of decode_gemm_plan for a plan given from outside (test hook): column granule, one finishing wave per tile, two K-steps per split at
+// least, the hand-over workspace, row blocks only without a K split
+bool decode_gemm_plan_admissible(const DecGemmArgs& g, int nt, int splits, int row_blocks) {
+  const int pm = g.plan_M > g.M ? g.plan_M : g.M;
+  const int ws_rows = pm <= 16 ? 16 : pm <= 32 ? 32 : 64;
+  const int mt = ws_rows / 16;
+  if (nt < 1 || nt > 2 || g.N % (16 * nt) != 0 || mt * nt > DW) return false;
+  if (splits < 1 || splits > 16 || row_blocks < 1 || row_blocks > 2) return false;
+  if (splits > 1) {
+    const int granules = g.N / (16 * nt);
+    if (!(g.ws && g.cnt) || (g.K >> 5) < splits * 2) return false;
+    if ((size_t)splits * ws_rows * g.N * 4 + (size_t)granules * splits * ws_rows * 8 > g.ws_bytes) return false;
+  }
+  if (row_blocks == 2 && (splits != 1 || mt < 2)) return false;
+  return true;
+}
+
+void launch_decode_gemm_planned(const DecGemmArgs& g, int nt, int splits, int rb, hipStream_t s, int* launched) {
   ASR_REQUIRE(decode_gemm_supported(g), "decode_gemm: unsupported shape (M = %d, N = %d, K = %d)", g.M, g.N, g.K);
   ASR_REQUIRE(g.A && (g.W || g.W8 || g.W4) && (g.out_f32 || g.out_lo), "decode_gemm: null operand");
-  int nt = 1, splits = 1, rb = 1;
-  decode_gemm_plan(g, &nt, &splits, &rb);
   ASR_REQUIRE(g.N % (16 * nt) == 0, "decode_gemm: N = %d", g.N);
+  auto report = [&](int mt, int sp, int blocks) { if (launched) { launched[0] = mt; launched[1] = nt; launched[2] = sp; launched[3] = blocks; } };
   if (rb == 2 && g.M > 32) {                                        // two 32-row blocks side by side (splits == 1)
     if (nt == 2) launch_inst<2, 2>(g, 1, s, 2); else launch_inst<2, 1>(g, 1, s, 2);
+    report(2, 1, 2);
     return;
   }
   if (rb == 2 && g.M > 16) {                                        // two 16-row blocks
     if (nt == 2) launch_inst<1, 2>(g, 1, s, 2); else launch_inst<1, 1>(g, 1, s, 2);
+    report(1, 1, 2);
     return;
   }
   const int mt = g.M <= 16 ? 1 : g.M <= 32 ? 2 : 4;
@@ -417,6 +438,15 @@ void launch_decode_gemm(const DecGemmArgs& g, hipStream_t s) {
   else if (mt == 1) launch_inst<1, 1>(g, splits, s);
   else if (mt == 2) launch_inst<2, 1>(g, splits, s);
   else launch_inst<4, 1>(g, splits, s);
+  report(mt, splits, 1);
+}
+
+void launch_decode_gemm(const DecGemmArgs& g, hipStream_t s) {
+  ASR_REQUIRE(decode_gemm_supported(g), "decode_gemm: unsupported shape (M = %d, N = %d, K = %d)", g.M, g.N, g.K);
+  ASR_REQUIRE(g.A && (g.W || g.W8 || g.W4) && (g.out_f32 || g.out_lo), "decode_gemm: null operand");
+  int nt = 1, splits = 1, rb = 1;
+  decode_gemm_plan(g, &nt, &splits, &rb);
+  launch_decode_gemm_planned(g, nt, splits, rb, s);
 }
 
 void launch_colsum_bf16(const bf16_t* W, int ldw, int N, int K, float* c, hipStream_t s) {

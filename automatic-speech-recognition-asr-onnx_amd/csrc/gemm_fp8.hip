@@ -9,6 +9,11 @@
 // conflict-free ds_read_b128 as before; (3) one 16x16x128 MFMA per (row fragment, column fragment) and phase: 8 per matrix segment (32 cycles each)
 // for twice the flops of the 16 bf16 MFMAs. Epilogues: scale + bias + erf-GELU -> e4m3 bytes (saturating at 448; the next GEMM's operand), or
 // scale + bias + f32 residual rows -> f32.
+//
+// Precision of the product (tests/test_lowbit_ref_gpu.py, measured): the instruction does NOT add its 128 products in float32. The products are aligned to the
+// largest of the instruction and the bits below are dropped, so on general e4m3 operands the accumulator differs from the exact sum by up to ~1.5e-5 of
+// sum |a||w| (hundreds of float32 ulps of the sum, biased downwards), far more than any float32 summation order gives; operands of one binade and whole-number
+// operands are summed exactly. The f32 output is therefore NOT "the float64 product to float32 accumulation order": its contract is 2e-5 of sum |a||w| + 1.
 #include <algorithm>
 #include "gemm_dev.h"
 

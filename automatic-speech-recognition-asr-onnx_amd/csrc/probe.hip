@@ -275,19 +275,23 @@ extern "C" int asr_probe_gemm_chain(int M, int N, int K, int epilogue, int cold_
 }
 
 // ---- FP8 mode (ASR_PRECISION_FP8W): the row quantiser and the decode GEMM over byte weights, on host arrays
-extern "C" int asr_probe_quantize_fp8(const uint16_t* w_bf16, int N, int K, uint8_t* out8, float* scale, uint16_t* dq_bf16) {
+// w_bf16 is [N][ld] with ld >= K: the quantiser must read K columns of every row and nothing of the gap
+extern "C" int asr_probe_quantize_fp8_ld(const uint16_t* w_bf16, int ld, int N, int K, uint8_t* out8, float* scale, uint16_t* dq_bf16) {
   return asr_guard([&] {
-    ASR_REQUIRE(w_bf16 && out8 && scale && N > 0 && K > 0 && K % 8 == 0, "probe_quantize_fp8: bad argument");
+    ASR_REQUIRE(w_bf16 && out8 && scale && N > 0 && K > 0 && K % 8 == 0 && ld >= K, "probe_quantize_fp8: bad argument");
     asr_require_device(0);
     DeviceBuffer w, q, sc, dq;
-    w.reserve((size_t)N * K * 2, nullptr); q.reserve((size_t)N * K, nullptr); sc.reserve((size_t)N * 4, nullptr); dq.reserve((size_t)N * K * 2, nullptr);
-    HIP_CHECK(hipMemcpy(w.ptr, w_bf16, (size_t)N * K * 2, hipMemcpyHostToDevice));
-    launch_quantize_rows_fp8(w.as<bf16_t>(), K, N, K, q.as<unsigned char>(), sc.as<float>(), dq.as<bf16_t>(), nullptr);
+    w.reserve((size_t)N * ld * 2, nullptr); q.reserve((size_t)N * K, nullptr); sc.reserve((size_t)N * 4, nullptr); dq.reserve((size_t)N * K * 2, nullptr);
+    HIP_CHECK(hipMemcpy(w.ptr, w_bf16, (size_t)N * ld * 2, hipMemcpyHostToDevice));
+    launch_quantize_rows_fp8(w.as<bf16_t>(), ld, N, K, q.as<unsigned char>(), sc.as<float>(), dq.as<bf16_t>(), nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out8, q.ptr, (size_t)N * K, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(scale, sc.ptr, (size_t)N * 4, hipMemcpyDeviceToHost));
     if (dq_bf16) HIP_CHECK(hipMemcpy(dq_bf16, dq.ptr, (size_t)N * K * 2, hipMemcpyDeviceToHost));
   });
+}
+extern "C" int asr_probe_quantize_fp8(const uint16_t* w_bf16, int N, int K, uint8_t* out8, float* scale, uint16_t* dq_bf16) {
+  return asr_probe_quantize_fp8_ld(w_bf16, K, N, K, out8, scale, dq_bf16);
 }
 
 // out[M][N] (f32) = decode GEMM of a[M][K] (bf16) with EITHER w_bf16[N][K] OR (w8[N][K], scale[N]); fold != 0: LayerNorm folded in
@@ -319,19 +323,22 @@ extern "C" int asr_probe_decode_gemm(int M, int N, int K, const uint16_t* a, con
 }
 
 // ---- MXFP4 mode (ASR_PRECISION_MXFP4W): the block quantiser and the decode GEMM over nibble weights, on host arrays
-extern "C" int asr_probe_quantize_mxfp4(const uint16_t* w_bf16, int N, int K, uint8_t* out4, uint8_t* scale8, uint16_t* dq_bf16) {
+extern "C" int asr_probe_quantize_mxfp4_ld(const uint16_t* w_bf16, int ld, int N, int K, uint8_t* out4, uint8_t* scale8, uint16_t* dq_bf16) {
   return asr_guard([&] {
-    ASR_REQUIRE(w_bf16 && out4 && scale8 && N > 0 && K > 0 && K % 32 == 0, "probe_quantize_mxfp4: bad argument");
+    ASR_REQUIRE(w_bf16 && out4 && scale8 && N > 0 && K > 0 && K % 32 == 0 && ld >= K, "probe_quantize_mxfp4: bad argument");
     asr_require_device(0);
     DeviceBuffer w, q, sc, dq;
-    w.reserve((size_t)N * K * 2, nullptr); q.reserve((size_t)N * K / 2, nullptr); sc.reserve((size_t)N * K / 32, nullptr); dq.reserve((size_t)N * K * 2, nullptr);
-    HIP_CHECK(hipMemcpy(w.ptr, w_bf16, (size_t)N * K * 2, hipMemcpyHostToDevice));
-    launch_quantize_rows_mxfp4(w.as<bf16_t>(), K, N, K, q.as<unsigned char>(), sc.as<unsigned char>(), dq.as<bf16_t>(), nullptr);
+    w.reserve((size_t)N * ld * 2, nullptr); q.reserve((size_t)N * K / 2, nullptr); sc.reserve((size_t)N * K / 32, nullptr); dq.reserve((size_t)N * K * 2, nullptr);
+    HIP_CHECK(hipMemcpy(w.ptr, w_bf16, (size_t)N * ld * 2, hipMemcpyHostToDevice));
+    launch_quantize_rows_mxfp4(w.as<bf16_t>(), ld, N, K, q.as<unsigned char>(), sc.as<unsigned char>(), dq.as<bf16_t>(), nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out4, q.ptr, (size_t)N * K / 2, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(scale8, sc.ptr, (size_t)N * K / 32, hipMemcpyDeviceToHost));
     if (dq_bf16) HIP_CHECK(hipMemcpy(dq_bf16, dq.ptr, (size_t)N * K * 2, hipMemcpyDeviceToHost));
   });
+}
+extern "C" int asr_probe_quantize_mxfp4(const uint16_t* w_bf16, int N, int K, uint8_t* out4, uint8_t* scale8, uint16_t* dq_bf16) {
+  return asr_probe_quantize_mxfp4_ld(w_bf16, K, N, K, out4, scale8, dq_bf16);
 }
 
 // out[M][N] (f32) = decode GEMM of a[M][K] (bf16) with the MXFP4 weights (w4 [N][K / 2], scale8 [N][K / 32]); fold != 0: LayerNorm folded in, column sums
@@ -399,6 +406,201 @@ extern "C" int asr_probe_gemm_fp8(int M, int N, int K, const uint8_t* a8, const 
       *us = ms * 1e3f / iters;
       (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
+  });
+}
+
+// ---- the decode GEMM with every DecGemmArgs term, a forced plan and guarded buffers (tests/test_decode_gemm_ref_gpu.py)
+namespace {
+// rows x `pitch` elements of `elt` bytes, every byte 0xff (a NaN in bf16, f32 and e4m3), the top-left rows_v x cols_v block copied in from the host
+void* nan_padded(Tmp& t, const void* host, size_t rows_v, size_t cols_v, size_t rows, size_t pitch, int elt) {
+  void* p = t.alloc(rows * pitch * elt);
+  HIP_CHECK(hipMemset(p, 0xff, rows * pitch * elt));
+  if (rows_v && cols_v) HIP_CHECK(hipMemcpy2D(p, pitch * elt, host, cols_v * elt, cols_v * elt, rows_v, hipMemcpyHostToDevice));
+  return p;
+}
+}  // namespace
+
+extern "C" int asr_probe_decode_gemm_desc(asr_probe_dec_gemm_args* d) {
+  return asr_guard([&] {
+    ASR_REQUIRE(d && d->a && d->w_bf16 && (d->out_f32 || d->out_lo) && d->M >= 1 && d->M <= 64 && d->N >= 16 && d->N <= 65536 && d->K >= 32 && d->repeats >= 1,
+                "probe_decode_gemm_desc: bad argument");
+    ASR_REQUIRE(d->wkind == 0 || (d->wkind == 1 && d->wq && d->w_scale) || (d->wkind == 2 && d->wq && d->w_scale8), "probe_decode_gemm_desc: weight kind %d", d->wkind);
+    asr_require_device(0);
+    const int M = d->M, N = d->N, K = d->K;
+    const int lda = d->lda ? d->lda : K, ldw = d->ldw ? d->ldw : K, ld_add = d->ld_add ? d->ld_add : N;
+    const int ld_f32 = d->ld_out_f32 ? d->ld_out_f32 : N, ld_lo = d->ld_out_lo ? d->ld_out_lo : N;
+    ASR_REQUIRE(lda >= K && ldw >= K && ld_add >= N && ld_f32 >= N && ld_lo >= N && ld_add % 4 == 0 && ld_f32 % 4 == 0 && ld_lo % 4 == 0 && N % 16 == 0,
+                "probe_decode_gemm_desc: a pitch below the extent or off the vector alignment");
+    ASR_REQUIRE(d->pre_M >= 0 && d->pre_M <= 64, "probe_decode_gemm_desc: pre_M");
+    Tmp t;
+    const int SLACK = 16;                                 // NaN rows behind the M rows of A and add: the kernel must not need zeros past M
+    DecGemmArgs g;
+    g.M = M; g.N = N; g.K = K; g.plan_M = d->plan_M; g.lda = lda; g.ldw = ldw; g.act = d->act; g.ln_eps = d->ln_eps;
+    g.A = (const bf16_t*)nan_padded(t, d->a, M, K, M + SLACK, lda, 2);
+    const bf16_t* w_dense = nullptr;                      // the bf16 weights (or the dequantised copy) the column sums come from
+    if (d->wkind == 0) { g.W = (const bf16_t*)nan_padded(t, d->w_bf16, N, K, N, ldw, 2); }
+    else if (d->wkind == 1) {
+      g.W8 = (const unsigned char*)nan_padded(t, d->wq, N, K, N, ldw, 1);
+      float* sc = (float*)t.alloc((size_t)N * 4); HIP_CHECK(hipMemcpy(sc, d->w_scale, (size_t)N * 4, hipMemcpyHostToDevice)); g.w_scale = sc;
+    } else {
+      ASR_REQUIRE(ldw % 2 == 0, "probe_decode_gemm_desc: ldw");
+      g.W4 = (const unsigned char*)nan_padded(t, d->wq, N, K / 2, N, ldw / 2, 1);
+      unsigned char* sc = (unsigned char*)t.alloc((size_t)N * (K / 32)); HIP_CHECK(hipMemcpy(sc, d->w_scale8, (size_t)N * (K / 32), hipMemcpyHostToDevice)); g.w_scale4 = sc;
+    }
+    if (d->fold) {
+      int ld_dense = ldw;
+      if (d->wkind == 0) w_dense = g.W;
+      else { w_dense = (const bf16_t*)nan_padded(t, d->w_bf16, N, K, N, K, 2); ld_dense = K; }
+      float* cs = (float*)t.alloc((size_t)N * 4);
+      launch_colsum_bf16(w_dense, ld_dense, N, K, cs, nullptr);
+      g.colsum = cs;
+    }
+    if (d->bias) { float* b = (float*)t.alloc((size_t)N * 4); HIP_CHECK(hipMemcpy(b, d->bias, (size_t)N * 4, hipMemcpyHostToDevice)); g.bias = b; }
+    if (d->add) { g.add = (const float*)nan_padded(t, d->add, M, N, M + SLACK, ld_add, 4); g.ld_add = ld_add; }
+    const size_t out_rows = 64 + 16;
+    Guarded of32, olo;
+    if (d->out_f32) { of32 = guarded(t, out_rows, ld_f32, 4); g.out_f32 = (float*)of32.dev; g.ld_out_f32 = ld_f32; }
+    if (d->out_lo) { olo = guarded(t, out_rows, ld_lo, 2); g.out_lo = (bf16_t*)olo.dev; g.ld_out_lo = ld_lo; }
+    const int n_tickets = 4096;
+    ASR_REQUIRE(N / 16 <= n_tickets, "probe_decode_gemm_desc: N");
+    int32_t* cnt = nullptr;
+    if (d->with_ws) {                                     // partials hold NaN before the first launch, the tickets 0
+      const size_t ws_bytes = std::max<size_t>((size_t)1 << 20, (size_t)16 * 64 * N * 4 + (size_t)(N / 16) * 16 * 64 * 8);
+      g.ws = (float*)t.alloc(ws_bytes); g.ws_bytes = ws_bytes;
+      HIP_CHECK(hipMemset(g.ws, 0xff, ws_bytes));
+      cnt = (int32_t*)t.alloc((size_t)n_tickets * 4); g.cnt = cnt;
+    }
+    ASR_REQUIRE(decode_gemm_supported(g), "probe_decode_gemm_desc: unsupported shape (M = %d, N = %d, K = %d)", M, N, K);
+    int nt = 1, splits = 1, rb = 1;
+    decode_gemm_plan(g, &nt, &splits, &rb);
+    if (d->force_nt || d->force_splits || d->force_row_blocks) {
+      if (d->force_nt) nt = d->force_nt;
+      if (d->force_splits) splits = d->force_splits; else if (d->force_row_blocks == 2) splits = 1;
+      if (d->force_row_blocks) rb = d->force_row_blocks; else if (d->force_splits) rb = 1;
+      ASR_REQUIRE(decode_gemm_plan_admissible(g, nt, splits, rb), "probe_decode_gemm_desc: the forced plan (nt %d, splits %d, row blocks %d) is not admissible", nt, splits, rb);
+    }
+    if (d->pre_M > 0) {                                   // a launch of pre_M rows (row i = row i % M of A and add) and pre_splits splits on the same workspace first
+      ASR_REQUIRE(d->with_ws && d->pre_splits >= 1, "probe_decode_gemm_desc: the launch before needs the workspace");
+      const int P = d->pre_M;
+      std::vector<uint16_t> ha((size_t)P * K);
+      for (int r = 0; r < P; ++r) memcpy(&ha[(size_t)r * K], d->a + (size_t)(r % M) * K, (size_t)K * 2);
+      DecGemmArgs p = g;
+      p.M = P; p.plan_M = 0;
+      p.A = (const bf16_t*)nan_padded(t, ha.data(), P, K, P + SLACK, lda, 2);
+      if (d->add) {
+        std::vector<float> hadd((size_t)P * N);
+        for (int r = 0; r < P; ++r) memcpy(&hadd[(size_t)r * N], d->add + (size_t)(r % M) * N, (size_t)N * 4);
+        p.add = (const float*)nan_padded(t, hadd.data(), P, N, P + SLACK, ld_add, 4);
+      }
+      if (g.out_f32) p.out_f32 = (float*)t.alloc(out_rows * ld_f32 * 4);
+      if (g.out_lo) p.out_lo = (bf16_t*)t.alloc(out_rows * ld_lo * 2);
+      ASR_REQUIRE(decode_gemm_plan_admissible(p, nt, d->pre_splits, 1), "probe_decode_gemm_desc: the launch before (%d rows, %d splits) is not admissible", P, d->pre_splits);
+      launch_decode_gemm_planned(p, nt, d->pre_splits, 1, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+    }
+    int launched[4] = {0, 0, 0, 0};
+    for (int r = 0; r < d->repeats; ++r) launch_decode_gemm_planned(g, nt, splits, rb, nullptr, launched);
+    HIP_CHECK(hipDeviceSynchronize());
+    d->mt = launched[0]; d->nt = launched[1]; d->splits = launched[2]; d->row_blocks = launched[3];
+    std::vector<uint32_t> h;
+    d->stray = 0;
+    if (d->out_f32) {
+      d->stray += collect(of32, M, N, h);
+      for (int m = 0; m < M; ++m) memcpy(d->out_f32 + (size_t)m * N, &h[(size_t)m * ld_f32], (size_t)N * 4);
+    }
+    if (d->out_lo) {
+      d->stray += collect(olo, M, N, h);
+      for (int m = 0; m < M; ++m) memcpy(d->out_lo + (size_t)m * N, &h[(size_t)m * ld_lo], (size_t)N * 4);
+    }
+    d->tickets_zero = 1;
+    if (cnt) {
+      std::vector<int32_t> hc(n_tickets);
+      HIP_CHECK(hipMemcpy(hc.data(), cnt, (size_t)n_tickets * 4, hipMemcpyDeviceToHost));
+      for (int32_t v : hc) if (v != 0) d->tickets_zero = 0;
+    }
+  });
+}
+
+// launch_quantize_crosskv_fp8 on host arrays: slabs [n_slabs][rows][64] bf16 bits (returned as the launch leaves them), sequence b at rows
+// [row_off[b], row_off[b] + n_lfr[b]); out8 [n_slabs][rows][64] (0xa5 where the kernel wrote nothing), scale [n_slabs][batch]
+extern "C" int asr_probe_quantize_crosskv_fp8(uint16_t* slabs, int n_slabs, int rows, const int32_t* row_off, const int32_t* n_lfr, int batch, int dq_in_place,
+                                              uint8_t* out8, float* scale) {
+  return asr_guard([&] {
+    ASR_REQUIRE(slabs && row_off && n_lfr && out8 && scale && n_slabs >= 1 && rows >= 1 && batch >= 1, "probe_quantize_crosskv_fp8: bad argument");
+    for (int b = 0; b < batch; ++b)
+      ASR_REQUIRE(row_off[b] >= 0 && n_lfr[b] >= 0 && row_off[b] % 16 == 0 && row_off[b] + n_lfr[b] <= rows, "probe_quantize_crosskv_fp8: sequence %d leaves the slab", b);
+    asr_require_device(0);
+    Tmp t;
+    const size_t elems = (size_t)n_slabs * rows * 64;
+    bf16_t* ds = (bf16_t*)t.alloc(elems * 2);
+    unsigned char* d8 = (unsigned char*)t.alloc(elems);
+    float* dsc = (float*)t.alloc((size_t)n_slabs * batch * 4);
+    UttPlan* dp = (UttPlan*)t.alloc((size_t)batch * sizeof(UttPlan));
+    std::vector<UttPlan> hp(batch);
+    for (int b = 0; b < batch; ++b) { memset(&hp[b], 0, sizeof(UttPlan)); hp[b].row_off = row_off[b]; hp[b].n_lfr = n_lfr[b]; hp[b].T = n_lfr[b]; }
+    HIP_CHECK(hipMemcpy(dp, hp.data(), (size_t)batch * sizeof(UttPlan), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(ds, slabs, elems * 2, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(d8, 0xa5, elems));
+    HIP_CHECK(hipMemset(dsc, 0xff, (size_t)n_slabs * batch * 4));
+    launch_quantize_crosskv_fp8(ds, (size_t)rows * 64, n_slabs, dp, batch, d8, dsc, dq_in_place, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(slabs, ds, elems * 2, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(out8, d8, elems, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(scale, dsc, (size_t)n_slabs * batch * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+// launch_layernorm_fp8 on host arrays: x [rows][ld_x] f32 -> out [rows + 4][ld_out] bytes, every byte 0xa5 before the launch (the sentinel)
+extern "C" int asr_probe_layernorm_fp8(const float* x, int ld_x, int rows, int D, float eps, float inv_scale, int ld_out, uint8_t* out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(x && out && rows >= 1 && D >= 1 && ld_x >= D && ld_out >= D, "probe_layernorm_fp8: bad argument");
+    asr_require_device(0);
+    Tmp t;
+    float* dx = (float*)t.alloc((size_t)rows * ld_x * 4);
+    unsigned char* dout = (unsigned char*)t.alloc((size_t)(rows + 4) * ld_out);
+    HIP_CHECK(hipMemcpy(dx, x, (size_t)rows * ld_x * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(dout, 0xa5, (size_t)(rows + 4) * ld_out));
+    launch_layernorm_fp8(dx, ld_x, rows, D, eps, inv_scale, dout, ld_out, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out, dout, (size_t)(rows + 4) * ld_out, hipMemcpyDeviceToHost));
+  });
+}
+
+// asr_probe_gemm_fp8 with pitches on every operand, out_inv_scale and the saturation count. Outputs are returned as laid out, 8 rows past M included:
+// out8 [M + 8][ld_out8] (0xa5 before the launch) or out_f32 [M + 8][ld_out_f32] (every byte 0xff before the launch); the gaps of a8 / w8 / add hold 0xff
+extern "C" int asr_probe_gemm_fp8_v2(int M, int N, int K, const uint8_t* a8, int lda, const uint8_t* w8, int ldw, const float* w_scale, float a_scale, const float* bias,
+                                     const float* add, int ld_add, int act, float out_inv_scale, uint8_t* out8, int ld_out8, float* out_f32, int ld_out_f32,
+                                     uint64_t* sat_count) {
+  return asr_guard([&] {
+    ASR_REQUIRE(a8 && w8 && w_scale && bias && (out8 || out_f32) && !(out8 && out_f32) && M >= 1 && lda >= K && ldw >= K, "probe_gemm_fp8_v2: bad argument");
+    asr_require_device(0);
+    Tmp t;
+    Fp8GemmArgs g;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.a_scale = a_scale; g.act = act; g.out_inv_scale = out_inv_scale;
+    g.A = (const unsigned char*)nan_padded(t, a8, M, K, M, lda, 1);
+    g.W = (const unsigned char*)nan_padded(t, w8, N, K, N, ldw, 1);
+    float* sc = (float*)t.alloc((size_t)N * 4); HIP_CHECK(hipMemcpy(sc, w_scale, (size_t)N * 4, hipMemcpyHostToDevice)); g.w_scale = sc;
+    float* b = (float*)t.alloc((size_t)N * 4); HIP_CHECK(hipMemcpy(b, bias, (size_t)N * 4, hipMemcpyHostToDevice)); g.bias = b;
+    unsigned long long* sat = (unsigned long long*)t.alloc(8);
+    void* dout = nullptr;
+    const size_t R = (size_t)M + 8;
+    if (out8) {
+      ASR_REQUIRE(ld_out8 >= N && !add, "probe_gemm_fp8_v2: byte output");
+      dout = t.alloc(R * ld_out8); HIP_CHECK(hipMemset(dout, 0xa5, R * ld_out8));
+      g.out8 = (unsigned char*)dout; g.ld_out8 = ld_out8; g.sat_count = sat;
+    } else {
+      ASR_REQUIRE(add && ld_add >= N && ld_out_f32 >= N, "probe_gemm_fp8_v2: the f32 output needs the residual rows");
+      g.add = (const float*)nan_padded(t, add, M, N, M, ld_add, 4); g.ld_add = ld_add;
+      dout = t.alloc(R * ld_out_f32 * 4); HIP_CHECK(hipMemset(dout, 0xff, R * ld_out_f32 * 4));
+      g.out_f32 = (float*)dout; g.ld_out_f32 = ld_out_f32;
+    }
+    launch_gemm_fp8(g, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (out8) HIP_CHECK(hipMemcpy(out8, dout, R * ld_out8, hipMemcpyDeviceToHost));
+    else HIP_CHECK(hipMemcpy(out_f32, dout, R * ld_out_f32 * 4, hipMemcpyDeviceToHost));
+    unsigned long long hs = 0;
+    HIP_CHECK(hipMemcpy(&hs, sat, 8, hipMemcpyDeviceToHost));
+    if (sat_count) *sat_count = hs;
   });
 }
 

@@ -84,6 +84,9 @@ const char* asr_probe_last_kernel(void);      /* kernel family of the last asr_p
 int asr_probe_quantize_fp8(const uint16_t* w_bf16, int N, int K, uint8_t* out8, float* scale, uint16_t* dq_bf16);
 /* MXFP4 mode: block quantiser (out4 [N][K / 2] nibbles, scale8 [N][K / 32] e8m0 bytes, dq the exact bf16 dequantisation) and the decode GEMM over them */
 int asr_probe_quantize_mxfp4(const uint16_t* w_bf16, int N, int K, uint8_t* out4, uint8_t* scale8, uint16_t* dq_bf16);
+/* the two row quantisers over w_bf16 [N][ld], ld >= K a multiple of 8: K columns of every row are read, the gap is the caller's */
+int asr_probe_quantize_fp8_ld(const uint16_t* w_bf16, int ld, int N, int K, uint8_t* out8, float* scale, uint16_t* dq_bf16);
+int asr_probe_quantize_mxfp4_ld(const uint16_t* w_bf16, int ld, int N, int K, uint8_t* out4, uint8_t* scale8, uint16_t* dq_bf16);
 int asr_probe_decode_gemm_mxfp4(int M, int N, int K, const uint16_t* a, const uint8_t* w4, const uint8_t* scale8, const uint16_t* w_dq, const float* bias,
                                 int fold, float* out);
 int asr_probe_decode_gemm(int M, int N, int K, const uint16_t* a, const uint16_t* w_bf16, const uint8_t* w8, const float* scale,
@@ -93,6 +96,50 @@ int asr_probe_decode_gemm(int M, int N, int K, const uint16_t* a, const uint16_t
  * (a8 w8^T) a_scale w_scale[n] + bias + add as f32 (out_f32). iters > 0 also times the launch (microseconds in *us). */
 int asr_probe_gemm_fp8(int M, int N, int K, const uint8_t* a8, const uint8_t* w8, const float* w_scale, float a_scale, const float* bias,
                        const float* add, int act, uint8_t* out8, float* out_f32, int iters, float* us);
+
+/* The decode GEMM (csrc/decode_gemm.hip) with every DecGemmArgs term on host arrays. A holds exactly M rows followed by NaN rows, the pitch gaps of A, W and
+ * add hold NaN, both outputs are NaN-filled buffers of 64 + 16 rows, the split-K partials hold NaN and the tickets 0 before the first launch.
+ * force_*: 0 = what decode_gemm_plan says; a forced plan that breaks the plan's admissibility rules (N % (16 nt), one finishing wave per tile, K / 32 >= 2 splits,
+ * the workspace size, row blocks only without a split and above 16 planned rows) is refused. */
+typedef struct asr_probe_dec_gemm_args {
+  int32_t M, N, K, plan_M;
+  int32_t lda, ldw, ld_add, ld_out_f32, ld_out_lo;   /* elements; 0 = the extent (K / K / N / N / N) */
+  int32_t wkind;           /* 0 bf16 weights, 1 e4m3 bytes + one f32 scale per output column, 2 e2m1 nibbles + one e8m0 byte per (column, 32 k) */
+  const uint16_t* a;       /* [M][K] bf16 bits */
+  const uint16_t* w_bf16;  /* [N][K] bf16 bits: the weights (wkind 0) or their dequantised copy (the column sums of the fold come from it) */
+  const uint8_t* wq;       /* wkind 1: [N][K] bytes; wkind 2: [N][K / 2], element 2 i in the low nibble of byte i */
+  const float* w_scale;    /* wkind 1: [N] */
+  const uint8_t* w_scale8; /* wkind 2: [N][K / 32] */
+  const float* bias;       /* [N] or NULL */
+  int32_t fold;            /* 1: the affine-free LayerNorm of the rows of A folded in (colsum) */
+  float ln_eps;
+  const float* add;        /* [M][N] or NULL */
+  int32_t act;             /* 0 none, 1 relu, 2 gelu(erf), 3 gelu(tanh) */
+  float* out_f32;          /* [M][N] or NULL */
+  float* out_lo;           /* [M][N] bf16 results widened to f32, or NULL */
+  int32_t with_ws;         /* 0: ws == cnt == NULL */
+  int32_t repeats;         /* >= 1 launches into the same buffers, workspace and tickets */
+  int32_t force_nt, force_splits, force_row_blocks;
+  int32_t pre_M, pre_splits; /* pre_M > 0: first a launch of pre_M rows (row i = row i % M) with pre_splits splits on the same workspace, into scratch outputs */
+  /* out */
+  int32_t mt, nt, splits, row_blocks;  /* the instance <mt, nt> and the grid (K splits, row blocks) of the last launch */
+  int32_t stray;           /* words of the two output buffers outside M rows x N columns that no longer hold the NaN pattern */
+  int32_t tickets_zero;    /* 1: every ticket word reads 0 after the launches */
+} asr_probe_dec_gemm_args;
+int asr_probe_decode_gemm_desc(asr_probe_dec_gemm_args* d);
+
+/* launch_quantize_crosskv_fp8 (the FP8 cross-K/V cache) on host arrays: slabs [n_slabs][rows][64] bf16 bits, updated in place by dq_in_place; sequence b holds
+ * rows [row_off[b], row_off[b] + n_lfr[b]) of every slab (row_off on 16-row boundaries). out8 [n_slabs][rows][64] holds 0xa5 where nothing was written;
+ * scale [n_slabs][batch]. */
+int asr_probe_quantize_crosskv_fp8(uint16_t* slabs, int n_slabs, int rows, const int32_t* row_off, const int32_t* n_lfr, int batch, int dq_in_place,
+                                   uint8_t* out8, float* scale);
+/* launch_layernorm_fp8 on host arrays: x [rows][ld_x] -> out [rows + 4][ld_out] e4m3 bytes; every byte of out is 0xa5 before the launch. */
+int asr_probe_layernorm_fp8(const float* x, int ld_x, int rows, int D, float eps, float inv_scale, int ld_out, uint8_t* out);
+/* asr_probe_gemm_fp8 with a pitch on every operand, out_inv_scale and the saturation count. Either out8 [M + 8][ld_out8] (0xa5 before the launch; *sat_count
+ * receives Fp8GemmArgs::sat_count) or out_f32 [M + 8][ld_out_f32] (every byte 0xff before the launch; needs add [M][N], uploaded with pitch ld_add). */
+int asr_probe_gemm_fp8_v2(int M, int N, int K, const uint8_t* a8, int lda, const uint8_t* w8, int ldw, const float* w_scale, float a_scale, const float* bias,
+                          const float* add, int ld_add, int act, float out_inv_scale, uint8_t* out8, int ld_out8, float* out_f32, int ld_out_f32,
+                          uint64_t* sat_count);
 
 /* One Whisper decoder attention call through the product dispatcher (launch_decode_attention<bf16 | f32>, head_dim 64) on host arrays.
  * Operands are rounded to the element type on upload. Sequences [b0, b0 + nb) of a batch of B are launched (nb = 0: B - b0).

@@ -33,8 +33,11 @@ Not compared here, and why:
     far above a few-second case. test_ops_gpu.py dispatches to them at their real sizes; its LayerNorm-fold and producer-epilogue value checks now also
     go through within(). Here variants 7, 8 and 136 run the same big / pp kernels, arg-max instance included, at small shapes.
   * The E_LSE arg-max instances (third partial, sum of exponentials): asr_probe_ctc_head and test_ctc_head_lse_gpu.py own them.
+  * The decode GEMM (csrc/decode_gemm.hip, launch_decode_gemm: every Whisper decode step, Qwen3-ASR o_proj / down_proj) is not a launch_gemm_bf16 family:
+    test_decode_gemm_ref_gpu.py owns it -- all 36 instances under a forced plan, bf16 / e4m3 / MXFP4 weights, against the float64 statement of lowbit_ref.py.
   * skinny_ln (ln_x prologue), skinny_w8 / skinny_w4 and the two-granule (N / 16 > 256) instance: operands the hook does not carry; test_ops_gpu.py,
-    test_qwen_fp8_gpu.py, test_whisper_mxfp4_gpu.py and test_qwen_asr_gpu.py hold them.
+    test_qwen_fp8_gpu.py, test_whisper_mxfp4_gpu.py and test_qwen_asr_gpu.py hold them (the byte / nibble files assert that the low-bit path equals the bf16
+    path of the same kernel, under a whole-matrix budget: no float64 statement of skinny_w8 / skinny_w4 exists yet).
   * The ping-pong tuning instances (variants 9 .. 135) and the timing switches (GemmArgs::dbg): bench hooks, not product paths.
   * rms_out / st_out / m_dev in f32 mode: launch_gemm_f32 has no such term (the hook refuses them instead of returning unwritten buffers).
 """

@@ -21,6 +21,7 @@ import torch
 
 from conftest import sub
 from helpers import golden_cases, load_golden
+from lowbit_ref import pow2_scale as _pow2_scale
 from oracle.whisper_oracle import WhisperOracle
 from test_oracle_whisper import unit_audio, whisper_setup
 
@@ -39,14 +40,6 @@ def _session(cfg_name, prec, env=None):
         for k, v in old.items():
             os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
     return cfg, ck, sup, beg, sess
-
-
-def _pow2_scale(amax):
-    s = np.ones_like(amax, dtype=np.float32)
-    nz = amax > 0
-    m, e = np.frexp(amax[nz].astype(np.float32) / np.float32(448.0))
-    s[nz] = np.ldexp(np.float32(1.0), np.where(m == 0.5, e - 1, e)).astype(np.float32)
-    return s
 
 
 def test_row_quantiser_is_ocp_e4m3_with_power_of_two_scales():

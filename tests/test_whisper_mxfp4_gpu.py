@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import sub
+from lowbit_ref import mxfp4_reference as _mxfp4_reference
 from oracle.whisper_oracle import WhisperOracle
 from test_oracle_whisper import unit_audio, whisper_setup
 from test_whisper_fp8_gpu import _run, _session
@@ -21,29 +22,6 @@ from test_whisper_fp8_gpu import _run, _session
 pytestmark = pytest.mark.gpu
 
 BF16, FP8W, MXFP4W = 0, 2, 4
-LEVELS = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
-
-
-def _mxfp4_reference(wb):
-    """OCP MX v1.0, e2m1 + e8m0 over blocks of 32 along the last axis: (codes [N][K] uint8 incl. the sign bit, scale bytes [N][K / 32], dequantised f64)."""
-    N, K = wb.shape
-    blk = wb.reshape(N, K // 32, 32).astype(np.float64)
-    amax = np.abs(blk).max(axis=2)
-    e = np.where(amax > 0, np.floor(np.log2(np.where(amax > 0, amax, 1.0))) - 2, 0.0)
-    sb = np.clip(e + 127, 1, 254).astype(np.int64)
-    scale = 2.0 ** (sb - 127.0)
-    v = np.abs(blk) / scale[..., None]
-    # round to nearest level, ties to the even code; above 6 saturates
-    code = np.zeros(v.shape, np.int64)
-    for lo, hi, c_lo in ((0.0, 0.5, 0), (0.5, 1.0, 1), (1.0, 1.5, 2), (1.5, 2.0, 3), (2.0, 3.0, 4), (3.0, 4.0, 5), (4.0, 6.0, 6)):
-        mid = 0.5 * (lo + hi)
-        up = (v > mid) | ((v == mid) & (c_lo % 2 == 1))                       # a tie goes to the even code
-        code = np.where((v >= lo) & up, c_lo + 1, code)
-        code = np.where((v >= lo) & (v < hi) & ~up, c_lo, code)
-    code = np.where(v >= 6.0, 7, code)
-    sign = (np.signbit(blk)).astype(np.int64)
-    dq = np.where(sign == 1, -1.0, 1.0) * LEVELS[code] * scale[..., None]
-    return (code | (sign << 3)).reshape(N, K).astype(np.uint8), sb.astype(np.uint8), dq.reshape(N, K)
 
 
 def test_block_quantiser_is_ocp_mxfp4():
