@@ -79,6 +79,11 @@ SIGNATURES = {
     "asr_paraformer_stream_reset": (_i, [_vp, _i]),
     "asr_paraformer_stream_step": (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _ip]),
     "asr_paraformer_stream_step_timed": (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _ip, _ip, _fp]),
+    "asr_paraformer_stream_set_beam": (_i, [_vp, _i, _i, _i, _i]),
+    "asr_paraformer_stream_set_hotwords": (_i, [_vp, _ip, _ip, _i, C.c_float]),
+    "asr_paraformer_stream_set_lm": (_i, [_vp, _ip, C.c_int64, C.c_float, C.c_float, C.c_float]),
+    "asr_paraformer_stream_step_beam": (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _ip, _ip, _fp, _ip, _fp, _ip, _ip, _fp, _ip, _fp, _fp, _ip]),
+    "asr_paraformer_stream_finish_beam": (_i, [_vp, _ip, _i, _ip, _fp, _ip, _ip, _fp, _ip, _fp, _fp, _ip]),
     "asr_paraformer_stream_stats": (_i, [_vp, _ip]),
     "asr_whisper_create": (_i, [C.POINTER(WhisperConfigC), _vp, _sz, _i, _i, _i, C.POINTER(_vp)]),
     "asr_whisper_encode": (_i, [_vp, _vp, _i, _lp, _i, _ip]),
@@ -141,6 +146,9 @@ SIGNATURES = {
                                        C.c_float, C.c_float]),
     "asr_op_nar_beam": (_i, [_ip, _fp, _i, _ip, _i, _ip, _ip, _ip, _ip, _ip, _i, C.c_float, _ip, C.c_int64, C.c_float, C.c_float, C.c_float, _i, _i, _ip, _i, _ip,
                              _fp, _fp, _fp]),
+    "asr_nar_stream_beam_state_words": (_i, [_i, _i]),
+    "asr_op_nar_stream_beam": (_i, [_ip, _fp, _i, _i, _i, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _i, C.c_float, _ip, C.c_int64, C.c_float, C.c_float, C.c_float,
+                                    _i, _i, _i, _ip, _i, _ip, _fp, _i, _ip, _ip, _fp, _ip, _fp, _fp, _ip]),
     "asr_op_ctc_align": (_i, [_fp, _i, _ip, _i, _i, _ip, _ip, _ip, _ip, _fp, _i, _fp, _fp, _ip]),
     "asr_op_cif_scan_timed": (_i, [_fp, _fp, _i, _ip, _i, C.c_float, _fp, _ip, _i, _ip]),
 }

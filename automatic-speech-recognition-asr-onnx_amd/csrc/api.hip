@@ -633,6 +633,142 @@ extern "C" int asr_op_nar_beam(const int32_t* cand_id, const float* cand_logprob
   });
 }
 
+// The streaming search on host arrays: `n_steps` launches over state the call keeps between them. Step s has the slots step_off[s] .. step_off[s + 1]; slot i
+// is stream slot_stream[i] with slot_rows[i] rows (in slot order in cand_id / cand_logprob) and the flag slot_final[i]. The rows go up in the compact token
+// plan's layout, as asr_op_nar_beam sends them. state_io (nullable: every stream starts cleared) holds every stream's state before the call and after it.
+extern "C" int asr_nar_stream_beam_state_words(int beam, int pend_cap) {
+  if (beam < 1 || beam > 16 || pend_cap < 1 || pend_cap > NAR_STREAM_PEND_MAX) return -1;
+  return nar_stream_beam_state_words(beam, pend_cap);
+}
+
+extern "C" int asr_op_nar_stream_beam(const int32_t* cand_id, const float* cand_logprob, int topk, int n_streams, int n_steps, const int32_t* step_off,
+                                      const int32_t* slot_stream, const int32_t* slot_rows, const int32_t* slot_final, const int32_t* trie_depth,
+                                      const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node,
+                                      int n_nodes, float boost, const int32_t* lm_image, int64_t lm_words, float alpha, float beta, float oov_logprob, int beam,
+                                      int nbest, int pend_cap, int32_t* state_io, int state_words, int32_t* commit_ids, float* commit_logprob, int commit_cap,
+                                      int32_t* commit_num, int32_t* pend_ids, float* pend_logprob, int32_t* pend_num, float* pend_score, float* pend_am,
+                                      int32_t* total) {
+  return asr_guard([&] {
+    ASR_REQUIRE(cand_id && cand_logprob && step_off && slot_stream && slot_rows && slot_final && commit_ids && commit_logprob && commit_num && pend_ids && pend_logprob &&
+                    pend_num && pend_score && pend_am && total && n_streams > 0 && n_steps > 0,
+                "op_nar_stream_beam: bad argument");
+    ASR_REQUIRE(topk >= 1 && topk <= 16 && beam >= 1 && beam <= 16 && nbest >= 1 && nbest <= beam && pend_cap >= 1 && pend_cap <= NAR_STREAM_PEND_MAX,
+                "op_nar_stream_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam), pend_cap %d (1..%d)", beam, topk, nbest, pend_cap, NAR_STREAM_PEND_MAX);
+    require_trie("op_nar_stream_beam", trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, -1);
+    const int sw = nar_stream_beam_state_words(beam, pend_cap);
+    ASR_REQUIRE(!state_io || state_words == sw, "op_nar_stream_beam: a state of %d words per stream, beam %d and pend_cap %d take %d", state_words, beam, pend_cap, sw);
+    ASR_REQUIRE(step_off[0] == 0, "op_nar_stream_beam: step_off[0] = %d", step_off[0]);
+    const int lm_nodes = lm_image && lm_words >= NGRAM_LM_HEADER ? lm_image[1] : 0;
+    std::vector<int> seen(n_streams);
+    int max_rows = 0;
+    for (int s = 0; s < n_steps; ++s) {
+      ASR_REQUIRE(step_off[s + 1] > step_off[s], "op_nar_stream_beam: step %d has no stream", s);
+      std::fill(seen.begin(), seen.end(), 0);
+      for (int i = step_off[s]; i < step_off[s + 1]; ++i) {
+        const int sid = slot_stream[i];
+        ASR_REQUIRE(sid >= 0 && sid < n_streams && !seen[sid], "op_nar_stream_beam: step %d names stream %d (of %d, once per step)", s, sid, n_streams);
+        ASR_REQUIRE(slot_rows[i] >= 0, "op_nar_stream_beam: step %d, stream %d has %d rows", s, sid, slot_rows[i]);
+        seen[sid] = 1;
+        max_rows = std::max(max_rows, slot_rows[i]);
+        if (state_io && state_io[(size_t)sid * sw] > 0) {                // a stream that comes with history: everything the kernel will index with
+          const int32_t* st = state_io + (size_t)sid * sw;
+          ASR_REQUIRE(st[1] >= 0 && st[1] <= st[0] && st[0] - st[1] <= pend_cap && st[2] >= 1 && st[2] <= beam, "op_nar_stream_beam: stream %d: L %d, C %d, %d live", sid, st[0],
+                      st[1], st[2]);
+          for (int r = 0; r < st[2]; ++r)
+            ASR_REQUIRE(st[4 + 32 + r] >= 0 && st[4 + 32 + r] < std::max(n_nodes, 1) && (!lm_nodes || (st[4 + 64 + r] >= 0 && st[4 + 64 + r] < lm_nodes)),
+                        "op_nar_stream_beam: stream %d, hypothesis %d: a trie node or model state out of range", sid, r);
+          for (int i2 = 0; i2 < pend_cap * beam; ++i2)
+            ASR_REQUIRE(st[4 + 80 + i2] >= 0 && st[4 + 80 + i2] < beam, "op_nar_stream_beam: stream %d: ring parent %d", sid, st[4 + 80 + i2]);
+        }
+      }
+    }
+    const int n_slots = step_off[n_steps];
+    ASR_REQUIRE(commit_cap >= pend_cap + max_rows, "op_nar_stream_beam: commit_cap %d, pend_cap + the longest step is %d", commit_cap, pend_cap + max_rows);
+    int64_t n_rows = 0;
+    for (int i = 0; i < n_slots; ++i) n_rows += slot_rows[i];
+    if (lm_image) {                                      // the image ("no blank"), then every id the walk will look up
+      ngram_lm_validate(lm_image, lm_words, lm_words >= NGRAM_LM_HEADER ? lm_image[3] : 0, -1, alpha, beta, oov_logprob, "op_nar_stream_beam");
+      for (int64_t i = 0; i < n_rows * topk; ++i)
+        ASR_REQUIRE(cand_logprob[i] == -INFINITY || (cand_id[i] >= 0 && cand_id[i] < lm_image[3]), "op_nar_stream_beam: candidate %d outside the model's vocabulary of %d",
+                    cand_id[i], lm_image[3]);
+    }
+    asr_require_device(0);
+    Tmp t;
+    std::vector<UttPlan> plan(n_slots);
+    int rows = 0;
+    for (int i = 0; i < n_slots; ++i) {
+      memset(&plan[i], 0, sizeof(UttPlan));
+      plan[i].n_lfr = slot_rows[i]; plan[i].T = std::max(slot_rows[i], 1); plan[i].row_off = rows; plan[i].lang = slot_stream[i];
+      rows += round_up(plan[i].T, 16);
+    }
+    std::vector<int32_t> ids((size_t)rows * topk, 0);
+    std::vector<float> lp((size_t)rows * topk, 0.0f);
+    size_t r = 0;
+    for (int i = 0; i < n_slots; ++i) {
+      const size_t n = (size_t)slot_rows[i] * topk;
+      for (int q = 0; q < slot_rows[i]; ++q)
+        for (int a = 0; a < topk; ++a)
+          for (int c = 0; c < a; ++c)
+            ASR_REQUIRE(cand_id[(r + q) * topk + a] != cand_id[(r + q) * topk + c], "op_nar_stream_beam: slot %d row %d lists token %d twice", i, q, cand_id[(r + q) * topk + a]);
+      memcpy(&ids[(size_t)plan[i].row_off * topk], cand_id + r * topk, n * 4);
+      memcpy(&lp[(size_t)plan[i].row_off * topk], cand_logprob + r * topk, n * 4);
+      r += slot_rows[i];
+    }
+    int32_t* dids = (int32_t*)t.alloc(ids.size() * 4);
+    float* dlp = (float*)t.alloc(lp.size() * 4);
+    UttPlan* dplan = (UttPlan*)t.alloc(sizeof(UttPlan) * n_slots);
+    int32_t* dm = (int32_t*)t.alloc(4);
+    int32_t* dfinal = (int32_t*)t.alloc((size_t)n_slots * 4);
+    const size_t state_bytes = (size_t)n_streams * sw * 4;
+    int32_t* dstate = (int32_t*)t.alloc(state_bytes);
+    HIP_CHECK(hipMemcpy(dids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dlp, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dplan, plan.data(), sizeof(UttPlan) * n_slots, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dm, &rows, 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dfinal, slot_final, (size_t)n_slots * 4, hipMemcpyHostToDevice));
+    if (state_io) HIP_CHECK(hipMemcpy(dstate, state_io, state_bytes, hipMemcpyHostToDevice));
+    else HIP_CHECK(hipMemset(dstate, 0, state_bytes));
+    const HotTrie trie = upload_trie(t, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost);
+    const size_t hyps = (size_t)n_slots * nbest, n_commit = (size_t)n_slots * commit_cap;
+    NarStreamOut o;
+    o.commit_ids = (int32_t*)t.alloc(n_commit * 4); o.commit_lp = (float*)t.alloc(n_commit * 4); o.commit_cap = commit_cap;
+    o.commit_num = (int32_t*)t.alloc((size_t)n_slots * 4);
+    o.pend_ids = (int32_t*)t.alloc(hyps * pend_cap * 4); o.pend_lp = (float*)t.alloc(hyps * pend_cap * 4);
+    o.pend_num = (int32_t*)t.alloc(hyps * 4); o.pend_score = (float*)t.alloc(hyps * 4); o.pend_am = (float*)t.alloc(hyps * 4);
+    o.total = (int32_t*)t.alloc((size_t)n_slots * 4);
+    // the caller's arrays go up first, so that slots the kernel leaves alone come back as they were
+    HIP_CHECK(hipMemcpy(o.commit_ids, commit_ids, n_commit * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(o.commit_lp, commit_logprob, n_commit * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(o.pend_ids, pend_ids, hyps * pend_cap * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(o.pend_lp, pend_logprob, hyps * pend_cap * 4, hipMemcpyHostToDevice));
+    NgramLm lm;
+    if (lm_image) {
+      int32_t* dlm = (int32_t*)t.alloc((size_t)lm_words * 4);
+      HIP_CHECK(hipMemcpy(dlm, lm_image, (size_t)lm_words * 4, hipMemcpyHostToDevice));
+      lm = ngram_lm_view(dlm, lm_image, alpha, beta, oov_logprob);
+    }
+    for (int s = 0; s < n_steps; ++s) {
+      const size_t at = step_off[s];
+      NarStreamOut so = o;
+      so.commit_ids += at * commit_cap; so.commit_lp += at * commit_cap; so.commit_num += at;
+      so.pend_ids += at * nbest * pend_cap; so.pend_lp += at * nbest * pend_cap; so.pend_num += at * nbest; so.pend_score += at * nbest; so.pend_am += at * nbest;
+      so.total += at;
+      launch_nar_stream_beam(dids, dlp, topk, dplan + at, dm, dfinal + at, step_off[s + 1] - step_off[s], beam, nbest, pend_cap, trie, dstate, sw, so, nullptr, &lm);
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    if (state_io) HIP_CHECK(hipMemcpy(state_io, dstate, state_bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(commit_ids, o.commit_ids, n_commit * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(commit_logprob, o.commit_lp, n_commit * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(commit_num, o.commit_num, (size_t)n_slots * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(pend_ids, o.pend_ids, hyps * pend_cap * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(pend_logprob, o.pend_lp, hyps * pend_cap * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(pend_num, o.pend_num, hyps * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(pend_score, o.pend_score, hyps * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(pend_am, o.pend_am, hyps * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(total, o.total, (size_t)n_slots * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 extern "C" int asr_op_ctc_align(const float* em, int ld_em, const int32_t* seq_lens, int batch, int row0, const int32_t* target_ids, const int32_t* target_offsets,
                                 int32_t* first_frame, int32_t* last_frame, float* token_logprob, int max_tokens, float* path_score, float* loglik, int32_t* status) {
   return asr_guard([&] {

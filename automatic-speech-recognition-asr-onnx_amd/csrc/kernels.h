@@ -463,6 +463,25 @@ void launch_nar_beam(const int32_t* cand_id, const float* cand_lp, int topk, con
                      const HotTrie& trie, int2* pool, int pool_stride, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* am_score,
                      float* token_logprob, hipStream_t s, const NgramLm* lm = nullptr);
 
+// ---- the same search for a stream that arrives in chunks (nar_stream_beam.hip): carried state, fixed-lag commits
+// One workgroup per stream of the call; token_plan[u].lang is the stream id (its state is state + id * state_stride, nar_stream_beam_state_words words; zeroed
+// memory is a cleared stream), token_plan[u].row_off .. + n_lfr its rows of this call (0 is legal; cut at *m_dev when given). Streams not in the call are not
+// touched, and a stream id may appear once per call. Before the row at position L is extended, L - C == pend_cap commits position C with the token of the best
+// live hypothesis. Outputs per slot u of the call: the tokens committed by it (commit_* [n][commit_cap], commit_cap >= pend_cap + the call's longest row
+// count), the pending tails of the best nbest live hypotheses (pend_ids / pend_lp [n][nbest][pend_cap], pend_num / pend_score / pend_am [n][nbest]; score and
+// am without the end terms; num 0 and -inf beyond the live ones) and total = L. final_flags (nullable) [n]: a set flag ends the stream behind its rows -- the
+// end terms of launch_nar_beam, the tails ranked again with their final scores, the best one's tail committed, the state cleared.
+constexpr int NAR_STREAM_PEND_MAX = 64;
+struct NarStreamOut {
+  int32_t* commit_ids = nullptr; float* commit_lp = nullptr; int commit_cap = 0; int32_t* commit_num = nullptr;
+  int32_t* pend_ids = nullptr; float* pend_lp = nullptr; int32_t* pend_num = nullptr; float* pend_score = nullptr; float* pend_am = nullptr;
+  int32_t* total = nullptr;
+};
+int nar_stream_beam_state_words(int beam, int pend_cap);
+void launch_nar_stream_beam(const int32_t* cand_id, const float* cand_lp, int topk, const UttPlan* token_plan, const int32_t* m_dev, const int32_t* final_flags,
+                            int n_streams, int beam, int nbest, int pend_cap, const HotTrie& trie, int32_t* state, int state_stride, const NarStreamOut& out,
+                            hipStream_t s, const NgramLm* lm = nullptr);
+
 // ---- CTC forced alignment of a given transcript (ctc_align.hip)
 // Emissions: for every row m < M with u = row_utt[m] >= 0, em[m][j] = log soft-max of h W^T + bias at slot j's column -- slot 0 the blank, slot j = 1 .. L_u
 // target_ids[target_offsets[u] + j - 1] -- and -inf for L_u < j < ld_em. The logit is recomputed as launch_ctc_topk recomputes it and the row's log-sum-exp comes

@@ -139,7 +139,106 @@ void SvSession::stream_reset(int sid) {
   const size_t hist = (size_t)(c.fsmn_kernel - 1) * c.d_model;
   for (int l = 0; l < pcfg.n_dec; ++l)
     HIP_CHECK(hipMemsetAsync(st_defsmn.as<float>() + ((size_t)l * st_max + lo) * hist, 0, (size_t)cnt * hist * 4, stream));
+  if (sb_beam > 0) {                                     // the stream's search too: zeroed words are a cleared stream (nar_stream_beam.hip)
+    HIP_CHECK(hipMemsetAsync(st_bstate.as<int32_t>() + (size_t)lo * sb_words, 0, (size_t)cnt * sb_words * 4, stream));
+    std::fill(sb_len.begin() + lo, sb_len.begin() + lo + cnt, 0);
+  }
   HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// ---- the streaming beam search (the build's own mode) -----------------------------------------------------------------------------
+void SvSession::stream_set_beam(int beam, int topk, int nbest, int pend_cap) {
+  ASR_REQUIRE(st_max > 0, "paraformer_stream_set_beam: session was not created with asr_paraformer_stream_create");
+  ASR_REQUIRE(!stream_search_history(), "paraformer_stream_set_beam: a stream holds search history; finish or reset it first");
+  HIP_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (beam == 0) {                                       // off: the state is freed
+    sb_beam = sb_topk = sb_nbest = sb_cap = sb_words = 0;
+    st_bstate.release(); st_bfinal.release();
+    sb_len.clear();
+    return;
+  }
+  ASR_REQUIRE(beam >= 1 && beam <= 16 && topk >= 1 && topk <= BEAM_MAX && topk <= cfg.vocab && nbest >= 1 && nbest <= beam && pend_cap >= 1 && pend_cap <= NAR_STREAM_PEND_MAX,
+              "paraformer_stream_set_beam: beam %d (1..16), topk %d (1..%d), nbest %d (1..beam), pend_cap %d (1..%d)", beam, topk, BEAM_MAX, nbest, pend_cap, NAR_STREAM_PEND_MAX);
+  const int words = nar_stream_beam_state_words(beam, pend_cap);
+  st_bstate.reserve((size_t)st_max * words * 4, stream);
+  HIP_CHECK(hipMemsetAsync(st_bstate.ptr, 0, (size_t)st_max * words * 4, stream));
+  st_bfinal.reserve((size_t)st_max * 4, stream);
+  const std::vector<int32_t> ones(st_max, 1);
+  HIP_CHECK(hipMemcpyAsync(st_bfinal.ptr, ones.data(), (size_t)st_max * 4, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  sb_beam = beam; sb_topk = topk; sb_nbest = nbest; sb_cap = pend_cap; sb_words = words;
+  sb_len.assign(st_max, 0);
+}
+
+// The candidates of the step's token rows and the search, or (rows == 0) the finish: enqueued once, behind a validated step and outside every captured graph,
+// so a step that was redone on the per-launch path advances the search state exactly once. The second synchronisation of a beam step is here.
+void SvSession::stream_search(const ResultBlob& out, const UttPlan* token_plan, const int32_t* stream_ids, int n, int rows, bool final, const SvStreamBeamOut& o) {
+  const ResultLayout& lay = out.lay;
+  d_bout.reserve(lay.bytes(lay.beam), stream);
+  if (rows > 0) {                                        // the log soft-max pairs of every row of the step's slots, lower id on ties as the greedy pick
+    d_cand_i.reserve((size_t)rows * sb_topk * 4, stream);
+    d_cand_l.reserve((size_t)rows * sb_topk * 4, stream);
+    ProfScope ps(prof, "beam_topk", stream);
+    launch_beam_topk(d_logits.as<float>(), vpad, rows, cfg.vocab, nullptr, sb_topk, d_cand_l.as<float>(), d_cand_i.as<int32_t>(), stream);
+  }
+  {
+    ProfScope ps(prof, "nar_stream_beam", stream);
+    NgramLm lm;                                           // (no nodes: the search without a model is launched)
+    if (lm_header[1] > 0) lm = ngram_lm_view(d_lm.as<int32_t>(), lm_header, lm_alpha, lm_beta, lm_oov);
+    NarStreamOut so;
+    so.commit_ids = out.dev(lay.commit_ids, d_bout); so.commit_lp = out.dev(lay.commit_logprob, d_bout); so.commit_cap = (int)lay.commit_cap;
+    so.commit_num = out.dev(lay.commit_num, d_bout); so.pend_ids = out.dev(lay.pend_ids, d_bout); so.pend_lp = out.dev(lay.pend_logprob, d_bout);
+    so.pend_num = out.dev(lay.pend_num, d_bout); so.pend_score = out.dev(lay.pend_score, d_bout); so.pend_am = out.dev(lay.pend_am, d_bout);
+    so.total = out.dev(lay.total_rows, d_bout);
+    launch_nar_stream_beam(d_cand_i.as<int32_t>(), d_cand_l.as<float>(), sb_topk, token_plan, nullptr, final ? st_bfinal.as<int32_t>() : nullptr, n, sb_beam, sb_nbest, sb_cap,
+                           hot_trie_view(d_hot.as<int32_t>(), hot_nodes, hot_boost), st_bstate.as<int32_t>(), sb_words, so, stream, &lm);
+  }
+  if (taps_enabled && rows > 0) {                         // (only the token rows of a slot hold candidates of a decoder row)
+    save_tap("cand_ids", d_cand_i.ptr, rows, sb_topk, sb_topk, 4);
+    save_tap("cand_logprob", d_cand_l.ptr, rows, sb_topk, sb_topk, 4);
+  }
+  out.enqueue_copy(lay.beam, d_bout.ptr, stream);
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (prof.enabled) prof.collect();
+  const size_t cc = lay.commit_cap, nb = sb_nbest, pc = sb_cap;
+  memcpy(o.commit_num, out.host(lay.commit_num), lay.bytes(lay.commit_num));
+  memcpy(o.total, out.host(lay.total_rows), lay.bytes(lay.total_rows));
+  memcpy(o.pend_num, out.host(lay.pend_num), lay.bytes(lay.pend_num));
+  memcpy(o.pend_score, out.host(lay.pend_score), lay.bytes(lay.pend_score));
+  memcpy(o.pend_am, out.host(lay.pend_am), lay.bytes(lay.pend_am));
+  for (int i = 0; i < n; ++i) {                          // rows hold their counts' worth of entries, the rest of the caller's arrays stays untouched
+    const size_t nc = (size_t)std::min<int64_t>(std::max(o.commit_num[i], 0), (int64_t)cc);
+    memcpy(o.commit_ids + i * cc, out.host(lay.commit_ids) + i * cc, nc * 4);
+    memcpy(o.commit_logprob + i * cc, out.host(lay.commit_logprob) + i * cc, nc * 4);
+    for (size_t m = 0; m < nb; ++m) {
+      const size_t at = (i * nb + m) * pc, np = (size_t)std::min<int64_t>(std::max(o.pend_num[i * nb + m], 0), (int64_t)pc);
+      memcpy(o.pend_ids + at, out.host(lay.pend_ids) + at, np * 4);
+      memcpy(o.pend_logprob + at, out.host(lay.pend_logprob) + at, np * 4);
+    }
+    sb_len[stream_ids[i]] = final ? 0 : o.total[i];
+  }
+}
+
+void SvSession::stream_finish_beam(const int32_t* stream_ids, int n, const SvStreamBeamOut& o) {
+  ASR_REQUIRE(st_max > 0 && sb_beam > 0, "paraformer_stream_finish_beam: the beam mode is off (asr_paraformer_stream_set_beam)");
+  ASR_REQUIRE(stream_ids && n >= 1 && n <= st_max && o.complete(), "paraformer_stream_finish_beam: bad argument (n = %d)", n);
+  HIP_CHECK(hipSetDevice(device));
+  std::vector<char> seen(st_max, 0);
+  PlanBlob pb(h_plan, d_plan);
+  const auto s_plan = pb.add<UttPlan>(n);
+  pb.commit(stream);
+  UttPlan* hp = pb.host(s_plan);
+  for (int i = 0; i < n; ++i) {
+    ASR_REQUIRE(stream_ids[i] >= 0 && stream_ids[i] < st_max && !seen[stream_ids[i]], "paraformer_stream_finish_beam: stream id %d invalid or repeated", stream_ids[i]);
+    seen[stream_ids[i]] = 1;
+    memset(&hp[i], 0, sizeof(UttPlan));
+    hp[i].row_off = i * 16; hp[i].lang = stream_ids[i];  // no rows: n_lfr = 0
+  }
+  ResultBlob out(h_out, ResultLayout(n, 0, ResultForm::PF_STREAM_BEAM, sb_nbest, sb_cap));
+  out.commit();
+  pb.upload(stream);
+  stream_search(out, pb.dev(s_plan), stream_ids, n, 0, true, o);
 }
 
 template <typename T>
@@ -147,8 +246,10 @@ void SvSession::stream_step(const SvStepReq& q) {
   const auto& c = cfg;
   const int32_t* const stream_ids = q.stream_ids;
   const int n = q.n, max_tokens = q.max_tokens;
-  const bool timed = q.form == SvForm::TIMED;
+  const bool beam = q.form == SvForm::STREAM_BEAM;      // the timed step, then (behind its validation, below) the candidates and the search
+  const bool timed = q.form == SvForm::TIMED || beam;
   ASR_REQUIRE(st_max > 0, "streaming: session was not created with asr_paraformer_stream_create");
+  ASR_REQUIRE(!beam || (sb_beam > 0 && q.beam_out.complete()), "streaming: the beam step needs the mode on (asr_paraformer_stream_set_beam) and all of its outputs");
   ASR_REQUIRE(q.audio && stream_ids && q.tok_out && q.num_out && n >= 1 && n <= st_max && max_tokens >= st_B + 1, "streaming: bad argument (n = %d)", n);
   ASR_REQUIRE(!timed || (q.fire_out && q.logprob_out), "streaming: the timed step needs both of its outputs");
   HIP_CHECK(hipSetDevice(device));
@@ -217,7 +318,7 @@ void SvSession::stream_step(const SvStepReq& q) {
     grow(d_xblo, (size_t)Mpad * d * 2);
     grow(d_stb, (size_t)Mpad * (d / 32) * 8);
   }
-  ResultBlob out(h_out, ResultLayout(n, max_tokens, timed ? ResultForm::PF_TIMED : ResultForm::PLAIN));
+  ResultBlob out(h_out, beam ? ResultLayout(n, max_tokens, ResultForm::PF_STREAM_BEAM, sb_nbest, sb_cap) : ResultLayout(n, max_tokens, timed ? ResultForm::PF_TIMED : ResultForm::PLAIN));
   const ResultLayout& lay = out.lay;
   out.commit();                                          // (the copies into it are issued behind the captured step, not inside it)
   pb.upload(stream);
@@ -547,6 +648,7 @@ void SvSession::stream_step(const SvStepReq& q) {
     out.scatter_rows(lay.first, q.fire_out, q.num_out, max_tokens);
     out.scatter_rows(lay.logprob, q.logprob_out, q.num_out, max_tokens);
   }
+  if (beam) stream_search(out, d_tplan.as<UttPlan>(), stream_ids, n, rows, false, q.beam_out);
 }
 
 extern "C" int asr_paraformer_stream_create(const asr_paraformer_config* cfg, const void* arena, size_t arena_bytes, int arena_mem,
@@ -574,12 +676,13 @@ extern "C" int asr_paraformer_stream_reset(asr_session* s, int stream_id) {
 
 namespace {
 void step_entry(asr_session* s, SvForm form, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams, int32_t* tok_out, int max_tokens, int32_t* num_out,
-                int32_t* fire_out, float* logprob_out) {
+                int32_t* fire_out, float* logprob_out, const SvStreamBeamOut* beam_out = nullptr) {
   TenantScope tenant(s);
   SvSession* sv = static_cast<SvSession*>(s);
   SvStepReq q;
   q.form = form; q.audio = audio; q.audio_mem = audio_mem; q.stream_ids = stream_ids; q.n = n_streams; q.max_tokens = max_tokens;
   q.tok_out = tok_out; q.num_out = num_out; q.fire_out = fire_out; q.logprob_out = logprob_out;
+  if (beam_out) q.beam_out = *beam_out;
   by_precision(sv, [&](auto t) { sv->stream_step<decltype(t)>(q); });
 }
 }  // namespace
@@ -598,6 +701,64 @@ extern "C" int asr_paraformer_stream_step_timed(asr_session* s, const void* audi
     ASR_REQUIRE(s && s->kind == 4, "paraformer_stream_step_timed: not a streaming Paraformer session");
     ASR_REQUIRE(fire_step_out && logprob_out, "paraformer_stream_step_timed: null timed output");
     step_entry(s, SvForm::TIMED, audio, audio_mem, stream_ids, n_streams, token_ids_out, max_tokens, num_id_out, fire_step_out, logprob_out);
+  });
+}
+
+namespace {
+SvStreamBeamOut beam_out_of(int32_t* commit_ids, float* commit_logprob, int32_t* commit_num, int32_t* pend_ids, float* pend_logprob, int32_t* pend_num, float* pend_score,
+                            float* pend_am, int32_t* total) {
+  SvStreamBeamOut o;
+  o.commit_ids = commit_ids; o.commit_logprob = commit_logprob; o.commit_num = commit_num; o.pend_ids = pend_ids; o.pend_logprob = pend_logprob; o.pend_num = pend_num;
+  o.pend_score = pend_score; o.pend_am = pend_am; o.total = total;
+  return o;
+}
+}  // namespace
+
+extern "C" int asr_paraformer_stream_set_beam(asr_session* s, int beam, int topk, int nbest, int pend_cap) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 4, "paraformer_stream_set_beam: not a streaming Paraformer session");
+    static_cast<SvSession*>(s)->stream_set_beam(beam, topk, nbest, pend_cap);
+  });
+}
+
+extern "C" int asr_paraformer_stream_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 4, "paraformer_stream_set_hotwords: not a streaming Paraformer session");
+    SvSession* sv = static_cast<SvSession*>(s);
+    ASR_REQUIRE(!sv->stream_search_history(), "paraformer_stream_set_hotwords: a stream holds search history (its trie nodes belong to the list in force); finish or reset it first");
+    sv->set_hotwords(ids, offsets, n_phrases, boost);
+  });
+}
+
+extern "C" int asr_paraformer_stream_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 4, "paraformer_stream_set_lm: not a streaming Paraformer session");
+    SvSession* sv = static_cast<SvSession*>(s);
+    ASR_REQUIRE(!sv->stream_search_history(), "paraformer_stream_set_lm: a stream holds search history (its model states belong to the image in force); finish or reset it first");
+    sv->set_lm(image_words, n_words, alpha, beta, oov_logprob);
+  });
+}
+
+extern "C" int asr_paraformer_stream_step_beam(asr_session* s, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams, int32_t* token_ids_out,
+                                               int max_tokens, int32_t* num_id_out, int32_t* fire_step_out, float* logprob_out, int32_t* commit_ids_out,
+                                               float* commit_logprob_out, int32_t* commit_num_out, int32_t* pend_ids_out, float* pend_logprob_out, int32_t* pend_num_out,
+                                               float* pend_score_out, float* pend_am_out, int32_t* total_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 4, "paraformer_stream_step_beam: not a streaming Paraformer session");
+    ASR_REQUIRE(fire_step_out && logprob_out, "paraformer_stream_step_beam: null timed output");
+    const SvStreamBeamOut o = beam_out_of(commit_ids_out, commit_logprob_out, commit_num_out, pend_ids_out, pend_logprob_out, pend_num_out, pend_score_out, pend_am_out, total_out);
+    step_entry(s, SvForm::STREAM_BEAM, audio, audio_mem, stream_ids, n_streams, token_ids_out, max_tokens, num_id_out, fire_step_out, logprob_out, &o);
+  });
+}
+
+extern "C" int asr_paraformer_stream_finish_beam(asr_session* s, const int32_t* stream_ids, int n_streams, int32_t* commit_ids_out, float* commit_logprob_out,
+                                                 int32_t* commit_num_out, int32_t* pend_ids_out, float* pend_logprob_out, int32_t* pend_num_out, float* pend_score_out,
+                                                 float* pend_am_out, int32_t* total_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 4, "paraformer_stream_finish_beam: not a streaming Paraformer session");
+    TenantScope tenant(s);
+    static_cast<SvSession*>(s)->stream_finish_beam(stream_ids, n_streams, beam_out_of(commit_ids_out, commit_logprob_out, commit_num_out, pend_ids_out, pend_logprob_out,
+                                                                                       pend_num_out, pend_score_out, pend_am_out, total_out));
   });
 }
 

@@ -27,8 +27,9 @@ struct PfDecLayer {
 
 // What a call asks for. PLAIN: ids and counts; TIMED: also per-token times and log-probabilities; BEAM: n-best hypotheses with scores (SenseVoice: CTC prefix
 // beam search; Paraformer: beam search over the decoder's token rows, with the fire rows and per-token log-probabilities); ALIGN (SenseVoice): the spans and
-// scores of a transcript the caller supplies.
-enum class SvForm { PLAIN, TIMED, BEAM, ALIGN };
+// scores of a transcript the caller supplies. STREAM_BEAM (streaming Paraformer): the timed step followed by the candidates of its token rows and the streaming
+// search (nar_stream_beam.hip) -- the caller keeps the timed step's outputs and gets the committed tokens and the pending tails on top.
+enum class SvForm { PLAIN, TIMED, BEAM, ALIGN, STREAM_BEAM };
 struct SvRunReq {               // offline: asr_sensevoice_run / _run_timed / _run_beam / _align, asr_paraformer_run / _run_timed / _run_beam
   SvForm form = SvForm::PLAIN;
   const void* audio = nullptr; int audio_mem = 0; const int64_t* offs = nullptr; int batch = 0;
@@ -44,11 +45,19 @@ struct SvRunReq {               // offline: asr_sensevoice_run / _run_timed / _r
   const int32_t *tgt_ids = nullptr, *tgt_off = nullptr;
   float *path_out = nullptr, *loglik_out = nullptr; int32_t* astatus_out = nullptr;      // [batch]
 };
-struct SvStepReq {              // streaming: asr_paraformer_stream_step / _step_timed
+struct SvStreamBeamOut {        // host arrays of the streaming search (asr_paraformer_stream_step_beam / _finish_beam), per stream of the call
+  int32_t* commit_ids = nullptr; float* commit_logprob = nullptr; int32_t* commit_num = nullptr;      // [n][pend_cap + max_tokens], [n]
+  int32_t* pend_ids = nullptr; float* pend_logprob = nullptr;                                         // [n][nbest][pend_cap]
+  int32_t* pend_num = nullptr; float *pend_score = nullptr, *pend_am = nullptr;                       // [n][nbest]
+  int32_t* total = nullptr;                                                                            // [n]
+  bool complete() const { return commit_ids && commit_logprob && commit_num && pend_ids && pend_logprob && pend_num && pend_score && pend_am && total; }
+};
+struct SvStepReq {              // streaming: asr_paraformer_stream_step / _step_timed / _step_beam
   SvForm form = SvForm::PLAIN;
   const void* audio = nullptr; int audio_mem = 0; const int32_t* stream_ids = nullptr; int n = 0, max_tokens = 0;
-  int32_t *tok_out = nullptr, *num_out = nullptr, *fire_out = nullptr;      // fire_out / logprob_out: TIMED
+  int32_t *tok_out = nullptr, *num_out = nullptr, *fire_out = nullptr;      // fire_out / logprob_out: TIMED, STREAM_BEAM
   float* logprob_out = nullptr;
+  SvStreamBeamOut beam_out;                                                 // STREAM_BEAM
 };
 
 // Everything a forward pass needs once the host plan is uploaded; captured into a hipGraph for replay.
@@ -203,6 +212,16 @@ struct ASR_LOCAL SvSession : asr_session {
   int st_n_segs = 0, st_n_items = 0;
   StepGraph st_graph[3];                // streaming chunk step: per-launch / fused / fused + snapshot
   StepGraph st_graph_timed[3];          // ... of the timed step
+  // the streaming beam search (asr_paraformer_stream_set_beam, nar_stream_beam.hip; the build's own mode): per-stream search state for st_max streams, made by
+  // the setter; the hotword trie and the language model are the offline search's members above (d_hot, d_lm). sb_len is what the host knows of every stream's
+  // L from the totals that came back: the setters refuse to change anything the carried trie nodes and model states refer to while a stream holds history.
+  int sb_beam = 0, sb_topk = 0, sb_nbest = 0, sb_cap = 0, sb_words = 0;
+  DeviceBuffer st_bstate, st_bfinal;    // [st_max][sb_words] search state; [st_max] ones: the finish's flags
+  std::vector<int32_t> sb_len;
+  bool stream_search_history() const { for (int32_t v : sb_len) if (v > 0) return true; return false; }
+  void stream_set_beam(int beam, int topk, int nbest, int pend_cap);
+  void stream_search(const ResultBlob& out, const UttPlan* token_plan, const int32_t* stream_ids, int n, int rows, bool final, const SvStreamBeamOut& o);
+  void stream_finish_beam(const int32_t* stream_ids, int n, const SvStreamBeamOut& o);
   void ensure_stream_shadow();
   void stream_init(int chunk, int look_back_encoder, int look_back_decoder, int max_streams);
   void stream_reset(int sid);

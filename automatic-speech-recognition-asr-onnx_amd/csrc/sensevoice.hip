@@ -915,7 +915,7 @@ void SvSession::run(const SvRunReq& q) {
 }
 
 void SvSession::set_hotwords(const int32_t* ids, const int32_t* offsets, int n_phrases, float boost) {
-  const char* who = paraformer ? "paraformer_set_hotwords" : "sensevoice_set_hotwords";      // (Paraformer has no blank: cfg.blank_id is -1 and no id is refused for it)
+  const char* who = kind == 4 ? "paraformer_stream_set_hotwords" : paraformer ? "paraformer_set_hotwords" : "sensevoice_set_hotwords";      // (Paraformer has no blank: cfg.blank_id is -1 and no id is refused for it)
   ASR_REQUIRE(n_phrases >= 0 && (n_phrases == 0 || (ids && offsets)) && std::isfinite(boost), "%s: bad argument", who);
   HIP_CHECK(hipSetDevice(device));
   if (n_phrases == 0) { hot_nodes = 0; hot_boost = 0.0f; ++beam_epoch; return; }
@@ -939,7 +939,7 @@ void SvSession::set_hotwords(const int32_t* ids, const int32_t* offsets, int n_p
 
 // The image is checked in full before it replaces the one in force (a rejected image changes nothing); its words are graph-kernel operands like the trie's.
 void SvSession::set_lm(const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob) {
-  const char* who = paraformer ? "paraformer_set_lm" : "sensevoice_set_lm";                  // (Paraformer: the image check is told "no blank", cfg.blank_id = -1)
+  const char* who = kind == 4 ? "paraformer_stream_set_lm" : paraformer ? "paraformer_set_lm" : "sensevoice_set_lm";                  // (Paraformer: the image check is told "no blank", cfg.blank_id = -1)
   ASR_REQUIRE(n_words >= 0 && (n_words == 0 || image_words), "%s: bad argument", who);
   HIP_CHECK(hipSetDevice(device));
   if (n_words == 0) { lm_header[1] = 0; lm_alpha = lm_beta = lm_oov = 0.0f; ++beam_epoch; return; }

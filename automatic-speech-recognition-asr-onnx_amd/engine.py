@@ -517,6 +517,68 @@ def op_nar_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, trie=None, boost
     return tok, num, score, am, tlp
 
 
+def nar_stream_beam_state_words(beam, pend_cap):
+    """int32 words of one stream's search state (asr_nar_stream_beam_state_words)"""
+    n = _lib.load().asr_nar_stream_beam_state_words(int(beam), int(pend_cap))
+    if n < 0:
+        raise ValueError(f"beam {beam} (1..16), pend_cap {pend_cap} (1..64)")
+    return n
+
+
+def op_nar_stream_beam(steps, n_streams, beam, nbest=1, pend_cap=16, trie=None, boost=0.0, lm=None, alpha=0.5, beta=0.0, oov_logprob=None, vocab=None,
+                       state=None, fill=None):
+    """The streaming beam search with carried state and fixed-lag commits on host arrays (asr_op_nar_stream_beam; the build's own mode). `steps`: one list per
+    step of (stream id, cand_id [n, topk], cand_logprob [n, topk], final) -- any subset of the streams in any order, n = 0 is legal, `final` ends the stream
+    behind its rows. One launch per step over state kept between them; `state` (int32 [n_streams, nar_stream_beam_state_words], None: all cleared) is the
+    streams' state before the call and is updated in place; a stream whose first word is 0 is cleared. Returns one dict per step with, per slot of the step:
+    commit_ids / commit_logprob [n, cap], commit_num [n], pend_ids / pend_logprob [n, nbest, pend_cap], pend_num / pend_score / pend_am [n, nbest], total [n];
+    array slots the search does not write hold `fill` = (int, float) (default zeros)."""
+    slots = [sl for st in steps for sl in st]
+    assert steps and all(len(st) > 0 for st in steps)
+    ids_l = [np.ascontiguousarray(sl[1], dtype=np.int32) for sl in slots]
+    lp_l = [_f32(sl[2]) for sl in slots]
+    topk = ids_l[0].shape[1]
+    assert all(i.ndim == 2 and i.shape[1] == topk and i.shape == l.shape for i, l in zip(ids_l, lp_l))
+    ids = np.ascontiguousarray(np.concatenate(ids_l + [np.zeros((1, topk), np.int32)]))
+    lp = np.ascontiguousarray(np.concatenate(lp_l + [np.zeros((1, topk), np.float32)]))
+    off = np.zeros(len(steps) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(st) for st in steps])
+    sid = np.ascontiguousarray([sl[0] for sl in slots], dtype=np.int32)
+    rows = np.ascontiguousarray([i.shape[0] for i in ids_l], dtype=np.int32)
+    fin = np.ascontiguousarray([1 if sl[3] else 0 for sl in slots], dtype=np.int32)
+    n, cap = len(slots), int(pend_cap) + max(int(rows.max()), 0)
+    fi, ff = (0, 0.0) if fill is None else fill
+    commit_ids, commit_lp = np.full((n, cap), fi, dtype=np.int32), np.full((n, cap), ff, dtype=np.float32)
+    pend_ids, pend_lp = np.full((n, nbest, pend_cap), fi, dtype=np.int32), np.full((n, nbest, pend_cap), ff, dtype=np.float32)
+    commit_num, total = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    pend_num = np.zeros((n, nbest), dtype=np.int32)
+    pend_score, pend_am = np.zeros((n, nbest), dtype=np.float32), np.zeros((n, nbest), dtype=np.float32)
+    if trie is not None and trie["depth"].size > 1:
+        t = {k: np.ascontiguousarray(trie[k], dtype=np.int32) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")}
+        targs, n_nodes = [_ip(t[k]) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")], int(t["depth"].size)
+    else:
+        targs, n_nodes = [None] * 5, 0
+    if lm is not None:
+        img, oov = _lm_image(lm, vocab, oov_logprob)
+        largs = [_ip(img), img.size, float(alpha), float(beta), oov]
+    else:
+        largs = [None, 0, 0.0, 0.0, 0.0]
+    if state is not None:
+        assert state.dtype == np.int32 and state.flags["C_CONTIGUOUS"] and state.ndim == 2 and state.shape[0] == n_streams
+        sargs = [_ip(state), state.shape[1]]
+    else:
+        sargs = [None, 0]
+    _lib.check(_lib.load().asr_op_nar_stream_beam(_ip(ids), _fp(lp), topk, int(n_streams), len(steps), _ip(off), _ip(sid), _ip(rows), _ip(fin), *targs, n_nodes,
+                                                  float(boost), *largs, int(beam), int(nbest), int(pend_cap), *sargs, _ip(commit_ids), _fp(commit_lp), cap,
+                                                  _ip(commit_num), _ip(pend_ids), _fp(pend_lp), _ip(pend_num), _fp(pend_score), _fp(pend_am), _ip(total)))
+    out = []
+    for s in range(len(steps)):
+        a, b = int(off[s]), int(off[s + 1])
+        out.append({"commit_ids": commit_ids[a:b], "commit_logprob": commit_lp[a:b], "commit_num": commit_num[a:b], "pend_ids": pend_ids[a:b],
+                    "pend_logprob": pend_lp[a:b], "pend_num": pend_num[a:b], "pend_score": pend_score[a:b], "pend_am": pend_am[a:b], "total": total[a:b]})
+    return out
+
+
 def op_ctc_align(em, seq_lens, targets, row0=0, max_tokens=None, fill=None):
     """The forced-alignment trellis on host arrays (asr_op_ctc_align): em [sum T, ld] log-probabilities (slot 0 the blank, slot j target j - 1 of the row's
     sequence), `targets` one id list per sequence; each sequence is aligned against its rows row0 .. T - 1. Returns (first_frame, last_frame, token_logprob
@@ -1036,6 +1098,9 @@ class ParaformerStreamSession(_Session):
             self.chunks_done[:] = 0
         else:
             self.chunks_done[int(stream_id)] = 0
+        for s in (range(self.max_streams) if stream_id < 0 else [int(stream_id)]):      # (the stream's beam search, if the mode is on, was cleared with it)
+            if getattr(self, "_beam", None):
+                self._fire_rows[s] = []
 
     def step(self, chunks, stream_ids, audio_device_ptr: int | None = None):
         """chunks: (n, chunk) int16-range samples of the session's audio_dtype (or None with `audio_device_ptr`: HBM-resident [n][chunk]); stream_ids: n
@@ -1076,6 +1141,91 @@ class ParaformerStreamSession(_Session):
         self.chunks_done[sid] += 1
         return [{"ids": tok[i, :n].copy(), "fire_step": fire[i, :n].copy(), "row": rows[i, :n].copy(), "logprob": logprob[i, :n].copy()}
                 for i, n in enumerate(num)]
+
+    # ---- beam search with hotwords and a language model, fixed-lag commits (the build's own mode)
+    def set_beam(self, beam: int, topk: int | None = None, nbest: int = 1, pend_cap: int = 16):
+        """Switches the streaming beam search on (asr_paraformer_stream_set_beam): `beam` live hypotheses (1..16) over the `topk` (default min(beam, 8); 1..8)
+        best tokens of every token row, the `nbest` best reported, at most `pend_cap` (1..64) uncommitted tokens per stream. beam = 0 switches it off. Fails
+        while a stream holds search history (tokens since its last finish_beam or reset), as set_hotwords and set_lm do."""
+        beam = int(beam)
+        topk = min(beam, 8) if topk is None else int(topk)
+        _lib.check(_lib.load().asr_paraformer_stream_set_beam(self._h, beam, topk if beam else 0, int(nbest) if beam else 0, int(pend_cap) if beam else 0))
+        self._beam = (beam, topk, int(nbest), int(pend_cap)) if beam else None
+        self._fire_rows = [[] for _ in range(self.max_streams)]           # absolute fire rows of each stream's tokens that are searched but not yet committed
+
+    def set_hotwords(self, phrases: Sequence[Sequence[int]], boost: float = 2.0):
+        """Hotwords of step_beam (asr_paraformer_stream_set_hotwords), as ParaformerSession.set_hotwords takes them. An empty list clears them."""
+        ids, offs = _flatten_phrases(phrases)
+        _lib.check(_lib.load().asr_paraformer_stream_set_hotwords(self._h, _ip(ids), _ip(offs), len(phrases), float(boost)))
+
+    def set_lm(self, lm, alpha: float = 0.5, beta: float = 0.0, oov_logprob: float | None = None):
+        """The n-gram language model of step_beam (asr_paraformer_stream_set_lm), as ParaformerSession.set_lm takes it. None clears it."""
+        if lm is None:
+            _lib.check(_lib.load().asr_paraformer_stream_set_lm(self._h, None, 0, 0.0, 0.0, 0.0))
+            return
+        img, oov = _lm_image(lm, self.cfg.vocab, oov_logprob)
+        _lib.check(_lib.load().asr_paraformer_stream_set_lm(self._h, _ip(img), img.size, float(alpha), float(beta), oov))
+
+    def _beam_arrays(self, n, max_tokens):
+        _, _, nbest, cap = self._beam
+        return (np.zeros((n, cap + max_tokens), np.int32), np.zeros((n, cap + max_tokens), np.float32), np.zeros(n, np.int32), np.zeros((n, nbest, cap), np.int32),
+                np.zeros((n, nbest, cap), np.float32), np.zeros((n, nbest), np.int32), np.zeros((n, nbest), np.float32), np.zeros((n, nbest), np.float32),
+                np.zeros(n, np.int32))
+
+    def _beam_records(self, sid, arrays):
+        cid, clp, cnum, pid, plp, pnum, pscore, pam, total = arrays
+        out = []
+        for i, s in enumerate(sid):
+            k = int(cnum[i])
+            rows, self._fire_rows[s] = self._fire_rows[s][:k], self._fire_rows[s][k:]
+            pending = [{"ids": pid[i, m, :pnum[i, m]].copy(), "logprob": plp[i, m, :pnum[i, m]].copy(), "score": float(pscore[i, m]), "am_score": float(pam[i, m])}
+                       for m in range(pid.shape[1]) if np.isfinite(pscore[i, m])]
+            out.append({"committed": {"ids": cid[i, :k].copy(), "logprob": clp[i, :k].copy(), "row": np.asarray(rows, dtype=np.int64)}, "pending": pending,
+                        "total": int(total[i])})
+        return out
+
+    def step_beam(self, chunks, stream_ids, audio_device_ptr: int | None = None):
+        """`step_timed` followed by the streaming beam search over the step's token rows (asr_paraformer_stream_step_beam) -> one record per stream: "ids",
+        "fire_step", "row", "logprob" as step_timed gives them (the greedy picks), plus "committed" = {"ids", "logprob", "row"}: the tokens this step
+        committed, final from now on, with the absolute LFR rows their token rows fired at; "pending" = the uncommitted tails of the best nbest live
+        hypotheses, best first, each {"ids", "logprob", "score", "am_score"} (scores since the stream's search was cleared, without the end terms); "total" =
+        token rows searched since the clear. What a caller shows: everything committed so far, then pending[0]."""
+        assert getattr(self, "_beam", None), "set_beam first"
+        sid = np.ascontiguousarray(stream_ids, dtype=np.int32)
+        if audio_device_ptr is not None:
+            ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
+        else:
+            a = self._audio(chunks).reshape(sid.size, self.chunk)
+            ap, mem = a.ctypes.data_as(C.c_void_p), MEM_HOST
+        cap = self.rows_per_chunk + 1
+        tok = np.zeros((sid.size, cap), dtype=np.int32)
+        fire = np.zeros((sid.size, cap), dtype=np.int32)
+        logprob = np.zeros((sid.size, cap), dtype=np.float32)
+        num = np.zeros(sid.size, dtype=np.int32)
+        arrays = self._beam_arrays(sid.size, cap)
+        cid, clp, cnum, pid, plp, pnum, pscore, pam, total = arrays
+        _lib.check(_lib.load().asr_paraformer_stream_step_beam(self._h, ap, mem, _ip(sid), sid.size, _ip(tok), cap, _ip(num), _ip(fire), _fp(logprob), _ip(cid), _fp(clp),
+                                                               _ip(cnum), _ip(pid), _fp(plp), _ip(pnum), _fp(pscore), _fp(pam), _ip(total)))
+        rows = np.maximum(self.chunks_done[sid][:, None] * self.rows_per_chunk + fire - self.rows_carried, 0)
+        self.chunks_done[sid] += 1
+        for i, s in enumerate(sid):
+            self._fire_rows[s] += [int(r) for r in rows[i, :num[i]]]
+        out = self._beam_records(sid, arrays)
+        for i, n in enumerate(num):
+            out[i].update({"ids": tok[i, :n].copy(), "fire_step": fire[i, :n].copy(), "row": rows[i, :n].copy(), "logprob": logprob[i, :n].copy()})
+        return out
+
+    def finish_beam(self, stream_ids):
+        """The end of the named streams' searches (asr_paraformer_stream_finish_beam; no audio): the end terms, the final ranking, the best hypothesis' tail
+        committed, the search state cleared -> one record per stream: "committed" (the tail of the best hypothesis), "pending" (the nbest tails with their final
+        scores; pending[0] is what was committed), "total". The acoustic state is left alone: `reset` the stream before it takes another utterance."""
+        assert getattr(self, "_beam", None), "set_beam first"
+        sid = np.ascontiguousarray(stream_ids, dtype=np.int32)
+        arrays = self._beam_arrays(sid.size, 0)
+        cid, clp, cnum, pid, plp, pnum, pscore, pam, total = arrays
+        _lib.check(_lib.load().asr_paraformer_stream_finish_beam(self._h, _ip(sid), sid.size, _ip(cid), _fp(clp), _ip(cnum), _ip(pid), _fp(plp), _ip(pnum), _fp(pscore),
+                                                                 _fp(pam), _ip(total)))
+        return self._beam_records(sid, arrays)
 
     def stream_stats(self) -> dict:
         """Which path the chunk steps took (asr_paraformer_stream_stats): give-ups recovered, steps moved to the per-launch path because the GPU was shared,

@@ -6,6 +6,9 @@
 The 200+ cache tensors the reference re-binds between the two ONNX sessions every chunk (encoder_feedback / decoder_feedback /
 encoder_decoder_bridge, :309-338) are device-resident state of `ParaformerStreamSession`, addressed by a stream id, so several
 clips can advance in lock-step (`transcribe_many`).
+
+  transcribe_many(beam_size=, nbest=, hotwords=, lm=, revise_tokens=)   the build's own mode: the streaming beam search with fixed-lag commits
+                                 (ParaformerStreamSession.step_beam / finish_beam); the reference host loop has no counterpart
 """
 from __future__ import annotations
 
@@ -49,15 +52,89 @@ class ParaformerStreamTranscriber:
         """"INT16" | "F32" | "F16": the type of the session's `audio` input (the reference reads it off the graph, Inference_Paraformer_Streaming_ONNX.py prepare_audio_input)."""
         return audio_dtype_name(self.sess.audio_dtype)
 
+    def _hotword_ids(self, hotwords):
+        """Hotwords as token-id lists: id lists pass through; text is looked up in the vocabulary as ParaformerTranscriber does -- as one entry, else piece by
+        piece ("en": the words between blanks, otherwise the characters). A piece the vocabulary does not list is an error."""
+        index, out = None, []
+        for h in hotwords or []:
+            if isinstance(h, str):
+                if index is None:
+                    index = {str(t): i for i, t in reversed(list(enumerate(self.tokens.tolist())))}
+                text = h.strip()
+                pieces = [text] if text in index else text.split() if self.decode_mode == "en" else [c for c in text if not c.isspace()]
+                missing = [p for p in pieces if p not in index]
+                if missing or not pieces:
+                    raise ValueError(f"hotword {h!r}: not in the vocabulary: {missing}")
+                h = [index[p] for p in pieces]
+            out.append([int(t) for t in h])
+        return out
+
+    def _transcribe_many_beam(self, prepared, clips_int16, n_chunks, timestamps, max_token_rows, beam_size, nbest, hotwords, hotword_boost, lm, lm_weight,
+                              length_bonus, revise_tokens):
+        sess, chunk = self.sess, self.sess.chunk
+        if not 1 <= nbest <= beam_size <= 16:
+            raise ValueError(f"beam_size {beam_size}, nbest {nbest}: expected 1 <= nbest <= beam_size <= 16")
+        ids = list(range(len(prepared)))
+        for i in ids:
+            sess.reset(i)
+        sess.set_beam(beam_size, None, nbest, revise_tokens)
+        sess.set_hotwords(self._hotword_ids(hotwords), hotword_boost)          # exactly this call's list (an empty one clears)
+        sess.set_lm(lm, lm_weight, length_bonus)                               # ... and exactly this call's model
+        done = [dict(ids=[], rows=[], logprob=[]) for _ in prepared]             # committed tokens: final when they are appended
+        last, rtfs = {}, []
+        for k in range(max(n_chunks)):
+            live = [i for i in ids if k < n_chunks[i]]
+            t0 = time.time()
+            recs = sess.step_beam(np.stack([prepared[i][k * chunk:(k + 1) * chunk] for i in live]), live)
+            ending = [i for i in live if k == n_chunks[i] - 1]
+            fins = dict(zip(ending, sess.finish_beam(ending))) if ending else {}
+            rtfs.append((time.time() - t0) / (chunk / self.sample_rate))
+            for i, r in zip(live, recs):
+                for c in [r["committed"]] + ([fins[i]["committed"]] if i in fins else []):
+                    done[i]["ids"] += c["ids"].tolist(); done[i]["rows"] += c["row"].tolist(); done[i]["logprob"] += c["logprob"].tolist()
+                if i in fins:
+                    last[i] = (len(done[i]["ids"]) - len(fins[i]["committed"]["ids"]), fins[i]["pending"])
+        cfg = sess.cfg
+        row_s = cfg.lfr_n * cfg.hop_length / cfg.sample_rate
+        out = []
+        for i, (d, clip, n) in enumerate(zip(done, clips_int16, n_chunks)):
+            tok, lps = np.asarray(d["ids"], dtype=np.int32), np.asarray(d["logprob"], dtype=np.float32)
+            keep = ~np.isin(tok, self.stop)
+            o = dict(token_ids=tok[keep], text=decode_tokens(self.tokens[tok[keep]].tolist(), self.decode_mode), pieces=[])
+            n_prefix, tails = last[i]
+            o["nbest"] = []
+            for t in tails:                                                      # full hypotheses: the committed prefix + the tail, with the final scores
+                full = np.concatenate([tok[:n_prefix], t["ids"]]).astype(np.int32)
+                full = full[~np.isin(full, self.stop)]
+                o["nbest"].append({"token_ids": full, "text": decode_tokens(self.tokens[full].tolist(), self.decode_mode), "score": t["score"], "am_score": t["am_score"]})
+            o["pieces"] = [o["text"]] if o["text"] else []
+            if timestamps:
+                dur = np.asarray(clip).size / self.sample_rate
+                spans = token_times(np.asarray(d["rows"], dtype=np.int64), n * sess.rows_per_chunk - sess.rows_carried, row_s, max_token_rows)
+                o["tokens"] = [{"id": int(t), "text": str(self.tokens[int(t)]), "start": min(float(s), dur), "end": min(float(e), dur), "logprob": float(lp)}
+                               for t, (s, e), lp in zip(tok, spans, lps) if int(t) not in self.stop]
+            out.append(o)
+        return out, {"rtf_per_chunk": rtfs, "chunks": max(n_chunks)}
+
     def transcribe_many(self, clips_int16: Sequence[np.ndarray], rng: np.random.Generator | None = None, timestamps: bool = False,
-                        max_token_rows: int = 4):
+                        max_token_rows: int = 4, beam_size: int = 1, nbest: int = 1, hotwords=None, hotword_boost: float = 2.0, lm=None,
+                        lm_weight: float = 0.5, length_bonus: float = 0.0, revise_tokens: int = 16):
         """Concurrent streams, one per clip (<= session.max_streams). Returns per clip dict(text, pieces, token_ids), and stats. timestamps=True takes the
         timed step and adds "tokens" per clip: one {"id", "text", "start", "end", "logprob"} per kept token, in seconds of the clip (paraformer.token_times
-        over the stream's absolute fire rows, ends clipped to the clip's duration); records of stop ids are dropped with their ids."""
+        over the stream's absolute fire rows, ends clipped to the clip's duration); records of stop ids are dropped with their ids.
+
+        beam_size > 1, nbest > 1, hotwords or lm (the build's own mode): every chunk takes step_beam, and a clip is finished (finish_beam) behind its last
+        chunk. A stream's last `revise_tokens` tokens stay open to revision; older ones are committed and final. text / token_ids (and "tokens") are the
+        committed tokens, "nbest" the best hypotheses found, best first, each {"token_ids", "text", "score", "am_score"}. hotwords: token-id lists, or text
+        spelled in the vocabulary; hotword_boost per matched token. lm: an lm.NgramLM: every token adds lm_weight * log P(token | history) + length_bonus.
+        The call sets exactly its own list and model. Without any of these the call does exactly what it did before the mode existed."""
         chunk = self.sess.chunk
         prepared = [pad_to_chunks(prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype, audio_pcm_scale=self.audio_pcm_scale),
                                   chunk, rng)[0, 0] for c in clips_int16]
         n_chunks = [a.size // chunk for a in prepared]
+        if beam_size > 1 or nbest > 1 or bool(hotwords) or lm is not None:
+            return self._transcribe_many_beam(prepared, clips_int16, n_chunks, timestamps, max_token_rows, beam_size, nbest, hotwords, hotword_boost, lm, lm_weight,
+                                              length_bonus, revise_tokens)
         ids = list(range(len(prepared)))
         for i in ids:
             self.sess.reset(i)

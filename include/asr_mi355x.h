@@ -265,6 +265,37 @@ int asr_paraformer_stream_step(asr_session* s, const void* audio, int audio_mem,
  * freely on one session. */
 int asr_paraformer_stream_step_timed(asr_session* s, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams,
                                      int32_t* token_ids_out, int max_tokens, int32_t* num_id_out, int32_t* fire_step_out, float* logprob_out);
+/* Beam search for the streaming session, with hotwords and an n-gram language model: the build's own mode (the reference graph returns the per-row arg-max;
+ * Export_Paraformer_Streaming.py). The search of asr_paraformer_run_beam cannot keep hypotheses open across chunk steps whose tokens are final when they
+ * return, so this one carries its state per stream and per hypothesis in HBM and commits with a fixed lag: a stream holds at most pend_cap uncommitted
+ * tokens; before a further token row is searched the oldest of them is committed with the token of the best live hypothesis, and the hypotheses that
+ * disagree there are dropped. A committed token is final and never revised; the pending tokens are reported as pending. The result depends on the sequence
+ * of a stream's token rows, not on how the chunks cut it; a stream of at most pend_cap tokens followed by a finish is the offline search bit for bit.
+ * set_beam switches the mode on (beam 1..16, topk 1..8, nbest 1..beam, pend_cap 1..64; the search state of every stream is allocated and cleared) or, with
+ * beam = 0, off (the state is freed). This entry, the hotword list and the language model -- the build's own too, taken and checked as
+ * asr_paraformer_set_hotwords / asr_paraformer_set_lm take theirs, which keep refusing a streaming session -- fail while any stream holds search history
+ * (tokens searched since its last finish or reset): the carried trie nodes and model states belong to the list and the image in force. */
+int asr_paraformer_stream_set_beam(asr_session* s, int beam, int topk, int nbest, int pend_cap);
+int asr_paraformer_stream_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+int asr_paraformer_stream_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob);
+/* asr_paraformer_stream_step_timed (same arguments, same outputs, bit for bit), then the topk candidates of the step's token rows and the search (the build's
+ * own mode). Per stream i of the call, host arrays: commit_ids_out / commit_logprob_out [n_streams][pend_cap + max_tokens] and commit_num_out [n_streams]: the
+ * tokens this step committed, with their log-probabilities; pend_ids_out / pend_logprob_out [n_streams][nbest][pend_cap] and pend_num_out / pend_score_out /
+ * pend_am_out [n_streams][nbest]: the uncommitted tails of the best nbest live hypotheses, best first (score = acoustic + hotword bonus + lm and am = the sum
+ * of the picked log-probabilities since the stream's search was cleared, both without the end terms; hypotheses beyond the live ones: num 0, both scores
+ * -inf); total_out [n_streams]: the token rows searched since the clear. Rows hold their counts' worth of entries, the rest is untouched. The greedy ids of
+ * the step are not the search's tokens: a caller shows the committed tokens followed by the best pending tail. The step costs a second synchronisation. */
+int asr_paraformer_stream_step_beam(asr_session* s, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams, int32_t* token_ids_out,
+                                    int max_tokens, int32_t* num_id_out, int32_t* fire_step_out, float* logprob_out, int32_t* commit_ids_out,
+                                    float* commit_logprob_out, int32_t* commit_num_out, int32_t* pend_ids_out, float* pend_logprob_out, int32_t* pend_num_out,
+                                    float* pend_score_out, float* pend_am_out, int32_t* total_out);
+/* The end of the named streams' searches (the build's own mode); takes no audio. The end terms of asr_paraformer_run_beam -- an open phrase gives its bonus
+ * back, a model that lists </s> adds alpha log P(</s> | state) -- the hypotheses ranked again, the best nbest tails with their final scores in the pend_*
+ * arrays, the best one's tail committed (commit_* arrays [n_streams][pend_cap]) and the search state cleared. The acoustic state stays the caller's to
+ * asr_paraformer_stream_reset (which clears the stream's search state too). A stream that was never stepped gives the one empty hypothesis. */
+int asr_paraformer_stream_finish_beam(asr_session* s, const int32_t* stream_ids, int n_streams, int32_t* commit_ids_out, float* commit_logprob_out,
+                                      int32_t* commit_num_out, int32_t* pend_ids_out, float* pend_logprob_out, int32_t* pend_num_out, float* pend_score_out,
+                                      float* pend_am_out, int32_t* total_out);
 /* Which path the chunk steps of a streaming session took (no reference counterpart: the reference runs one stream per InferenceSession and has no
  * co-tenancy to manage). A bf16 step runs the encoder / decoder layer loops as two cluster launches when (i) no more than fused_max streams are active,
  * (ii) no other session of this process is computing on the same GPU (otherwise the per-launch path, which leaves CUs to the other tenant and waits on nobody);
@@ -588,6 +619,29 @@ int asr_op_nar_beam(const int32_t* cand_id, const float* cand_logprob, int topk,
                     const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node, int n_nodes,
                     float boost, const int32_t* lm_image, int64_t lm_words, float alpha, float beta, float oov_logprob, int beam, int nbest,
                     int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* am_score, float* token_logprob);
+/* The search of asr_op_nar_beam for streams that arrive in chunks, on host arrays: the build's own mode (the reference graph returns the per-row arg-max).
+ * Search state is carried per stream and per hypothesis, and tokens are committed with a fixed lag: before the row at position L of a stream is searched, a
+ * stream with pend_cap (1..64) uncommitted positions commits the oldest one with the token of its best live hypothesis and drops the hypotheses that disagree
+ * there. A committed token is final. The row rule is asr_op_nar_beam's, bit for bit, so a stream of at most pend_cap rows followed by a finish is that search
+ * however it was cut. One call runs n_steps launches over state it keeps between them: step s has the slots step_off[s] .. step_off[s + 1] - 1 (step_off
+ * [n_steps + 1], step_off[0] = 0, no empty step); slot i is stream slot_stream[i] (0 .. n_streams - 1, once per step, any order, any subset) with slot_rows[i]
+ * candidate rows (0 is legal) and, where slot_final[i] != 0, the end of the stream behind them. cand_id / cand_logprob [sum of slot_rows][topk] in slot order.
+ * Trie and language model as asr_op_nar_beam takes them. state_io: null (every stream starts cleared) or host [n_streams][state_words], state_words =
+ * asr_nar_stream_beam_state_words of (beam, pend_cap): the streams' states before the call and after it; a stream whose first word is 0 is cleared, and the
+ * words of a stream that no step names come back as they went in. Outputs per slot: commit_ids / commit_logprob [slots][commit_cap] (commit_cap >= pend_cap +
+ * the longest slot_rows) and commit_num: the tokens the step committed; pend_ids / pend_logprob [slots][nbest][pend_cap], pend_num / pend_score / pend_am
+ * [slots][nbest]: the uncommitted tails of the best nbest live hypotheses, best first, score (acoustic + bonus + lm) and am without the end terms --
+ * hypotheses beyond the live ones have num 0 and both scores -inf; total [slots] = L, the rows searched since the stream was cleared. A finished slot applies
+ * the end terms of asr_op_nar_beam, ranks again, reports the tails with their final scores, commits the best one's tail and clears the stream. Array slots the
+ * search does not write come back as they went in. */
+int asr_nar_stream_beam_state_words(int beam, int pend_cap); /* words of one stream's state; -1 for a beam outside 1..16 or a pend_cap outside 1..64 */
+int asr_op_nar_stream_beam(const int32_t* cand_id, const float* cand_logprob, int topk, int n_streams, int n_steps, const int32_t* step_off,
+                           const int32_t* slot_stream, const int32_t* slot_rows, const int32_t* slot_final, const int32_t* trie_depth,
+                           const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node,
+                           int n_nodes, float boost, const int32_t* lm_image, int64_t lm_words, float alpha, float beta, float oov_logprob, int beam,
+                           int nbest, int pend_cap, int32_t* state_io, int state_words, int32_t* commit_ids, float* commit_logprob, int commit_cap,
+                           int32_t* commit_num, int32_t* pend_ids, float* pend_logprob, int32_t* pend_num, float* pend_score, float* pend_am,
+                           int32_t* total);
 /* the trellis of asr_sensevoice_align on host arrays: em [sum T][ld_em] log-probabilities, slot 0 the blank and slot j the sequence's target j - 1 (ld_em >
  * the longest transcript); each sequence is aligned against its rows row0 .. seq_lens[b] - 1 (seq_lens[b] > row0; earlier rows are never read). Targets ragged as
  * above (any ids: only the equality of neighbours matters). first_frame / last_frame / token_logprob host [batch][max_tokens], max_tokens >= the longest
