@@ -102,6 +102,7 @@ SIGNATURES = {
     "asr_whisper_set_timestamps": (_i, [_vp, _i, _i, _i, _i, _i]),
     "asr_whisper_set_token_scores": (_i, [_vp, _i]),
     "asr_whisper_set_hotwords": (_i, [_vp, _ip, _ip, _i, C.c_float]),
+    "asr_whisper_set_lm": (_i, [_vp, _ip, C.c_int64, C.c_float, C.c_float, C.c_float, _i, _ip, _i]),
     "asr_whisper_token_scores": (_i, [_vp, _fp, _i, _ip]),
     "asr_whisper_set_word_timestamps": (_i, [_vp, _i, _ip, _i, _i]),
     "asr_whisper_align": (_i, [_vp, _ip, _ip, _i, _ip, _i]),
@@ -118,6 +119,7 @@ SIGNATURES = {
     "asr_qwen_set_sampling_noise": (_i, [_vp, _fp, _i]),
     "asr_qwen_set_token_scores": (_i, [_vp, _i]),
     "asr_qwen_set_hotwords": (_i, [_vp, _ip, _ip, _i, C.c_float]),
+    "asr_qwen_set_lm": (_i, [_vp, _ip, C.c_int64, C.c_float, C.c_float, C.c_float, _i, _ip, _i]),
     "asr_qwen_token_scores": (_i, [_vp, _fp, _i, _ip]),
     "asr_qwen_align": (_i, [_vp, _vp, _i, _lp, _i, _ip, _ip, _ip, _ip, C.c_int32, _ip, _ip, C.c_int64, _fp, _ip]),
     "asr_mem_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),

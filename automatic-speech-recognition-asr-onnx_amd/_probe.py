@@ -108,6 +108,22 @@ class HotwordRankDesc(C.Structure):
                 ("iters", C.c_int32), ("ms_topk", C.c_float), ("ms_rerank", C.c_float)]
 
 
+class LmModel(C.Structure):
+    _fields_ = [("image", _ip), ("n_words", C.c_int64), ("alpha", C.c_float), ("beta", C.c_float), ("oov_logprob", C.c_float), ("topk", C.c_int32),
+                ("end_ids", _ip), ("n_end", C.c_int32)]
+
+
+class LmTopkDesc(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("n_valid", C.c_int32), ("ld", C.c_int32), ("M", C.c_int32), ("logits", _fp), ("vec", _fp),
+                ("cand_v", _fp), ("cand_i", _ip), ("lse", _fp), ("slow_rows", C.c_int32), ("iters", C.c_int32), ("ms_lm_topk", C.c_float),
+                ("ms_beam_topk", C.c_float)]
+
+
+class LmPickDesc(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("n_saved", C.c_int32), ("ld_save", C.c_int32), ("cand_v", _fp), ("cand_i", _ip), ("lse", _fp),
+                ("state", _ip), ("next", _ip), ("logprob", _fp)]
+
+
 class DecGemmDesc(C.Structure):
     _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("plan_M", C.c_int32), ("lda", C.c_int32), ("ldw", C.c_int32), ("ld_add", C.c_int32),
                 ("ld_out_f32", C.c_int32), ("ld_out_lo", C.c_int32), ("wkind", C.c_int32), ("a", C.c_void_p), ("w_bf16", C.c_void_p), ("wq", C.c_void_p),
@@ -145,6 +161,10 @@ SIGNATURES = {
     "asr_probe_hotword": (C.c_int, [C.POINTER(HotwordDesc)]),
     "asr_probe_hotword_head_steps": (C.c_int, [C.POINTER(HotwordHeadDesc)]),
     "asr_probe_hotword_rank": (C.c_int, [C.POINTER(HotwordRankDesc)]),
+    "asr_probe_lm_topk": (C.c_int, [C.POINTER(LmTopkDesc)]),
+    "asr_probe_lm_pick": (C.c_int, [C.POINTER(LmModel), C.POINTER(LmPickDesc)]),
+    "asr_probe_lm_head_steps": (C.c_int, [C.POINTER(LmModel), C.POINTER(HotwordHeadDesc), _ip]),
+    "asr_probe_lm_rank": (C.c_int, [C.POINTER(LmModel), C.POINTER(HotwordRankDesc), _ip, _ip]),
     "asr_probe_decode_attention_beam": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p]),
     "asr_probe_decode_attention_ks": (C.c_int, [C.POINTER(DecodeAttnDesc), _ip]),
     "asr_probe_decode_attention_beam_ks": (C.c_int, [C.c_int] * 8 + [_ip, C.c_int, _fp, _fp, _fp, _fp, _ip, C.c_char_p, _ip]),
@@ -684,14 +704,65 @@ def hotword_op(op, phrases, boost, node, logits=None, n_saved=1, next_ids=None, 
     return out
 
 
+def _lm_model(lm, keep):
+    """lm = dict(image, alpha, beta, oov, topk, end_ids) -> the model descriptor of the LM hooks."""
+    m = LmModel()
+    img = np.ascontiguousarray(lm["image"], np.int32)
+    ends = np.ascontiguousarray(list(lm.get("end_ids", ())) or [0], np.int32)
+    keep += [img, ends]
+    m.image, m.n_words, m.alpha, m.beta, m.oov_logprob = img.ctypes.data_as(_ip), img.size, float(lm["alpha"]), float(lm["beta"]), float(lm.get("oov", 0.0))
+    m.topk, m.end_ids, m.n_end = int(lm["topk"]), ends.ctypes.data_as(_ip), len(lm.get("end_ids", ()))
+    return m
+
+
+def lm_topk(logits, M, bias=None, iters=0):
+    """launch_lm_topk on logits [rows][n_valid], padded as token_head pads them (asr_probe_lm_topk) -> {"cand_v", "cand_i" [rows][M], "lse" [rows],
+    "slow_rows": rows that took the strict-order passes}; iters > 0 adds "ms_lm_topk" / "ms_beam_topk" (beam_topk at K = min(M, 8)) per `iters` launches."""
+    d, keep = LmTopkDesc(), []
+    padded, n_valid, ld = _pad_rows(logits)
+    rows = len(padded)
+    d.rows, d.n_valid, d.ld, d.M, d.logits, d.iters = rows, n_valid, ld, int(M), padded.ctypes.data_as(_fp), int(iters)
+    if bias is not None:
+        v = np.zeros(ld, np.float32)
+        v[:n_valid] = _f32(bias)
+        keep.append(v); d.vec = v.ctypes.data_as(_fp)
+    out = {"cand_v": np.full((rows, M), np.nan, np.float32), "cand_i": np.full((rows, M), -1, np.int32), "lse": np.full(rows, np.nan, np.float32)}
+    d.cand_v, d.cand_i, d.lse = out["cand_v"].ctypes.data_as(_fp), out["cand_i"].ctypes.data_as(_ip), out["lse"].ctypes.data_as(_fp)
+    _lib.check(load().asr_probe_lm_topk(C.byref(d)))
+    out["slow_rows"] = int(d.slow_rows)
+    if iters:
+        out["ms_lm_topk"], out["ms_beam_topk"] = float(d.ms_lm_topk), float(d.ms_beam_topk)
+    return out
+
+
+def lm_pick(lm, cand_v, cand_i, lse, state, n_saved=1, ld_save=0):
+    """launch_lm_pick on host candidates [rows][topk] (asr_probe_lm_pick) -> {"next", "state" [rows]} and "logprob" [rows][ld_save] (NaN where nothing was
+    written) when ld_save > 0."""
+    d, keep = LmPickDesc(), []
+    m = _lm_model(lm, keep)
+    cv, ci, ls = _f32(cand_v), np.ascontiguousarray(cand_i, np.int32), _f32(lse)
+    rows = len(cv)
+    assert cv.shape == ci.shape == (rows, m.topk) and ls.shape == (rows,)
+    out = {"state": np.array(state, np.int32, order="C", copy=True), "next": np.full(rows, -1, np.int32)}
+    d.rows, d.n_saved, d.ld_save = rows, int(n_saved), int(ld_save)
+    d.cand_v, d.cand_i, d.lse = cv.ctypes.data_as(_fp), ci.ctypes.data_as(_ip), ls.ctypes.data_as(_fp)
+    d.state, d.next = out["state"].ctypes.data_as(_ip), out["next"].ctypes.data_as(_ip)
+    if ld_save:
+        out["logprob"] = np.full((rows, ld_save), np.nan, np.float32)
+        d.logprob = out["logprob"].ctypes.data_as(_fp)
+    _lib.check(load().asr_probe_lm_pick(C.byref(m), C.byref(d)))
+    return out
+
+
 def hotword_head_steps(logits, phrases, boost, ld_save, range_=4, value=1.0, partial=0, bias=None, sampler=None, noise=None, timestamps=None, scores=False,
-                       want_logits=False, timed=0):
+                       want_logits=False, timed=0, lm=None):
     """A TokenHead with hotwords driven through logits [steps][rows][n_valid], a different row per step (asr_probe_hotword_head_steps): step 0 is a prefill
     (`bias` added, no penalty). sampler: (temperature, top_k, top_p, repetition_penalty, seed); noise [steps][rows][top_k]: caller uniforms for every step;
     timestamps: (ts_begin, no_timestamps_id, eot_id, max_initial). An empty phrase list leaves the mode off.
     Returns {"picks" [steps][rows], "save_ids" [rows][ld_save], "n_saved", "nodes" [steps][rows] (-1 with the mode off)} and "logprob" [rows][ld_save] with
     scores, "logits" [steps][rows][ld] with want_logits. timed = N > 0 (arg-max head): logits holds one step's rows [1][rows][n_valid], reused by N steps
-    whose launches run back to back between two device events -> "head_ms" (tools/probes/hotword_timing.py); picks and histories are not results then."""
+    whose launches run back to back between two device events -> "head_ms" (tools/probes/hotword_timing.py); picks and histories are not results then.
+    lm: dict(image, alpha, beta, oov, topk, end_ids) -- the model is set after the hotwords (asr_probe_lm_head_steps) and "states" [steps][rows] comes back."""
     d, keep = HotwordHeadDesc(), []
     padded, n_valid, ld = _pad_rows(logits)
     steps, rows = padded.shape[:2]
@@ -722,16 +793,23 @@ def hotword_head_steps(logits, phrases, boost, ld_save, range_=4, value=1.0, par
         out["logits"] = np.zeros_like(padded)
         d.logits_out = out["logits"].ctypes.data_as(_fp)
     d.timed = int(bool(timed))
-    _lib.check(load().asr_probe_hotword_head_steps(C.byref(d)))
+    if lm is not None:
+        out["states"] = np.full((steps, rows), -1, np.int32)
+        _lib.check(load().asr_probe_lm_head_steps(C.byref(_lm_model(lm, keep)), C.byref(d), out["states"].ctypes.data_as(_ip)))
+    else:
+        _lib.check(load().asr_probe_hotword_head_steps(C.byref(d)))
     out["n_saved"] = d.n_saved_after
     if timed:
         out["head_ms"] = float(d.head_ms)
     return out
 
 
-def hotword_rank(logits, phrases, boost, beam, n_slots, cum, fin, length, nxt, done, src_in, tok_in, node_in, stop=(), first=False, bias=None, iters=0):
+def hotword_rank(logits, phrases, boost, beam, n_slots, cum, fin, length, nxt, done, src_in, tok_in, node_in, stop=(), first=False, bias=None, iters=0, lm=None,
+                 state_in=None):
     """One ranking pass of the beam search with hotwords (asr_probe_hotword_rank): beam_topk + re-rank + select with the node hand-over, on logits
-    [rows][n_valid] ([n_utt][n_valid] when first). Returns the state, the tables written (from a -1 fill), "node_out" and the re-ranked "topv" / "topi"."""
+    [rows][n_valid] ([n_utt][n_valid] when first). Returns the state, the tables written (from a -1 fill), "node_out" and the re-ranked "topv" / "topi".
+    lm: dict(image, alpha, beta, oov, topk, end_ids) -- the pass with the model on (asr_probe_lm_rank: lm_topk + lm_rerank + select; the phrase list may be
+    empty), state_in [rows] the rows' LM states; "state_out" comes back."""
     d, keep = HotwordRankDesc(), []
     f32 = lambda x: np.array(x, np.float32, order="C", copy=True)
     i32 = lambda x: np.array(x, np.int32, order="C", copy=True)
@@ -753,7 +831,12 @@ def hotword_rank(logits, phrases, boost, beam, n_slots, cum, fin, length, nxt, d
     for k in ("fin", "len", "next", "done", "stop", "src_in", "tok_in", "src_out", "tok_out", "node_in", "node_out", "topi"):
         setattr(d, k, st[k].ctypes.data_as(_ip))
     d.iters = int(iters)
-    _lib.check(load().asr_probe_hotword_rank(C.byref(d)))
+    if lm is not None:
+        sin = i32(state_in if state_in is not None else np.zeros(st["node_in"].size, np.int32))
+        st["state_out"] = np.full_like(sin, -1)
+        _lib.check(load().asr_probe_lm_rank(C.byref(_lm_model(lm, keep)), C.byref(d), sin.ctypes.data_as(_ip), st["state_out"].ctypes.data_as(_ip)))
+    else:
+        _lib.check(load().asr_probe_hotword_rank(C.byref(d)))
     if iters:
         st["ms_topk"], st["ms_rerank"] = float(d.ms_topk), float(d.ms_rerank)
     return st

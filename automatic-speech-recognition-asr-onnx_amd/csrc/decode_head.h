@@ -38,6 +38,19 @@ struct ASR_LOCAL HotScope {            // the hotword launches of the head and t
   ~HotScope() { if (p) p->end(s); }
 };
 
+// ---- n-gram LM fusion (kernels.h: launch_lm_*) as the beam ranker takes it from the head: the image's view, the candidate width and the end ids
+struct ASR_LOCAL LmView {
+  NgramLm lm;
+  int topk = 0;
+  LmEnds ends;
+  bool on() const { return lm.n_nodes > 0; }
+};
+struct ASR_LOCAL LmScope {             // the LM launches of the head and the ranker are a profile class of their own, beside "hotwords"
+  Profiler* p; hipStream_t s;
+  LmScope(Profiler* p_, hipStream_t s_) : p(p_ && p_->enabled ? p_ : nullptr), s(s_) { if (p) p->begin(p->cls("lm"), s); }
+  ~LmScope() { if (p) p->end(s); }
+};
+
 // ---- token-selection head (Export_Whisper.py:228-325, Inference_Qwen_ASR_ONNX.py:369-376): arg-max, penalty-greedy (APPLY_PENALTY + GREEDY_SEARCH) or
 // TOPK_TOPP_SAMPLING, and the history of picked ids [rows][ld_save] the last two read. What differs between the families is data, set by init().
 struct ASR_LOCAL TokenHead {
@@ -68,6 +81,11 @@ struct ASR_LOCAL TokenHead {
   float hot_boost = 0.0f;
   uint64_t hot_gen = 0, biased_gen = 0;   // the list's generation, and the one the last prefill row was biased with
   bool row_biased = false;             // the logits row of the last prefill carries the bias (restart clears)
+  // language model: the image on the device (once per session), every row's state, and the candidate list of a step (launch_lm_topk's outputs). Off
+  // (lm.on() false) nothing is allocated and no step launches anything new.
+  DeviceBuffer d_lm, d_lmstate, d_lmv, d_lmi, d_lmlse;
+  LmView lm;
+  int lm_rows = 0;
 
   void init(int ld_save_, int partial_, int default_range, int sampling_ld_limit_) {
     ld_save = ld_save_; partial = partial_; penalty_range = default_range; sampling_ld_limit = sampling_ld_limit_;
@@ -141,6 +159,32 @@ struct ASR_LOCAL TokenHead {
     ++hot_gen;
     ++epoch;
   }
+  // The back-off n-gram model fused into the greedy heads and the beam ranker: image_words as asr_sensevoice_set_lm takes them, checked by
+  // ngram_lm_validate against `vocab` (these families have no blank id); null or n_words == 0 clears the model. Everything is checked before anything
+  // changes: a refused call leaves the model in force. Every row's state goes back to start_node.
+  void set_lm(const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov, int topk, const int32_t* end_ids, int n_end, int vocab, hipStream_t s,
+              const char* who) {
+    const bool clear = !image_words || n_words == 0;
+    LmView v;
+    if (!clear) {
+      ASR_REQUIRE(topk >= 1 && topk <= LM_TOPK_MAX, "%s: topk %d outside 1..%d", who, topk, LM_TOPK_MAX);
+      ASR_REQUIRE(n_end >= 0 && n_end <= LM_ENDS_MAX && (n_end == 0 || end_ids), "%s: %d end ids (at most %d)", who, n_end, LM_ENDS_MAX);
+      for (int i = 0; i < n_end; ++i) ASR_REQUIRE(end_ids[i] >= 0 && end_ids[i] < vocab, "%s: end id %d outside the vocabulary of %d", who, end_ids[i], vocab);
+      ngram_lm_validate(image_words, n_words, vocab, -1, alpha, beta, oov, who);
+      v.topk = topk; v.ends.n = n_end;
+      for (int i = 0; i < n_end; ++i) v.ends.id[i] = end_ids[i];
+    }
+    HIP_CHECK(hipStreamSynchronize(s));                  // (nothing in flight reads the image that is about to change)
+    if (!clear) {
+      d_lm.reserve((size_t)n_words * 4, s);
+      HIP_CHECK(hipMemcpyAsync(d_lm.ptr, image_words, (size_t)n_words * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      v.lm = ngram_lm_view(d_lm.as<int32_t>(), image_words, alpha, beta, oov);
+    }
+    lm = v;
+    if (lm.on() && d_lmstate.ptr && lm_rows > 0) fill_states(0, std::max(lm_rows, 64), s);
+    ++epoch;
+  }
   void arm_noise(const float* uniforms, int count, hipStream_t s) {
     d_noise.reserve((size_t)count * 4, s);
     HIP_CHECK(hipMemcpyAsync(d_noise.ptr, uniforms, (size_t)count * 4, hipMemcpyHostToDevice, s));
@@ -159,6 +203,16 @@ struct ASR_LOCAL TokenHead {
       }
       node_rows = std::max(node_rows, rows);
       moved |= reserve_moved(d_rootsave, (size_t)rows * std::max(hot_root, 1) * 4, s);
+    }
+    if (lm.on()) {
+      const int cap = std::max(rows, 64);
+      if (reserve_moved(d_lmstate, (size_t)cap * 4, s) || rows > lm_rows) {                     // fresh rows start at start_node
+        moved = true;
+        fill_states(0, cap, s);
+      }
+      lm_rows = std::max(lm_rows, rows);
+      for (DeviceBuffer* q : {&d_lmv, &d_lmi}) moved |= reserve_moved(*q, (size_t)rows * LM_TOPK_MAX * 4, s);
+      moved |= reserve_moved(d_lmlse, (size_t)cap * 4, s);
     }
     if (moved) ++epoch;
   }
@@ -198,13 +252,19 @@ struct ASR_LOCAL TokenHead {
         ScoreScope sc(prof, s);
         launch_logprob_at_rows(logits, ld, rows, n_valid, bias, next, d_scores.as<float>(), ld_save, n_saved, s);
       }
+    } else if (lm.on()) {                  // the fused greedy pick: the topk best columns of the row as it stands, value + LM term, the state follows the pick
+      ASR_REQUIRE(d_lmstate.ptr && rows <= lm_rows, "language model: the state table holds %d rows, this step has %d", d_lmstate.ptr ? lm_rows : 0, rows);
+      LmScope ls(prof, s);
+      launch_lm_topk(logits, ld, rows, n_valid, bias, lm.topk, d_lmv.as<float>(), d_lmi.as<int32_t>(), d_lmlse.as<float>(), s);
+      launch_lm_pick(d_lmv.as<float>(), d_lmi.as<int32_t>(), d_lmlse.as<float>(), rows, lm.topk, lm.lm, lm.ends, d_lmstate.as<int32_t>(), n_saved, next,
+                     scores ? d_scores.as<float>() : nullptr, ld_save, s);
     } else if (scores) {
       ScoreScope sc(prof, s);
       launch_argmax_logprob_rows(logits, ld, rows, n_valid, bias, next, d_scores.as<float>(), ld_save, n_saved, s);
     } else {
       launch_argmax_rows(logits, ld, rows, n_valid, bias, next, s);
     }
-    if (penalised || sampling || track_history || ts.on || scores || hot()) {   // GREEDY_SEARCH / the sampling head append their pick to the history
+    if (penalised || sampling || track_history || ts.on || scores || hot() || lm.on()) {   // GREEDY_SEARCH / the sampling head append their pick to the history
       if (hot()) {                         // the append and the node's step are one launch: the mode adds the bias kernel to a head that keeps a history
         HotScope hs(prof, s);
         launch_hotword_advance(next, rows, trie, d_node.as<int32_t>(), n_saved, s, save, ld_save);
@@ -235,6 +295,11 @@ struct ASR_LOCAL TokenHead {
   }
 
  private:
+  void fill_states(int first, int count, hipStream_t s) {      // rows [first, first + count) of d_lmstate = start_node (returns with the copy done)
+    const std::vector<int32_t> h((size_t)count, lm.lm.start_node);
+    HIP_CHECK(hipMemcpyAsync(d_lmstate.as<int32_t>() + first, h.data(), (size_t)count * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
   struct ScoreScope {                  // the score launches are a profile class of their own, as the timestamp rules are
     Profiler* p; hipStream_t s;
     ScoreScope(Profiler* p_, hipStream_t s_) : p(p_ && p_->enabled ? p_ : nullptr), s(s_) { if (p) p->begin(p->cls("token_scores"), s); }
@@ -248,6 +313,8 @@ struct ASR_LOCAL BeamRanker {
   DeviceBuffer topv, topi, cum, fin, len, done, next, stop, src[2], tok[2];
   DeviceBuffer node[2], lse;           // hotwords: the rows' trie nodes, double-buffered with `cur` like src / tok, and beam_topk's log-sum-exp per row
   HotView hot;                         // set by begin (the head's); off, no pass launches anything new
+  DeviceBuffer state[2], lmv, lmi;     // language model: the rows' states, double-buffered like node, and launch_lm_topk's candidate list per row (lse is shared)
+  LmView lmod;                         // set by begin (the head's); off, no pass launches anything new
   PinnedBuffer stage;                  // its own: a prefill called with null outputs may still be copying from the session's. [0, done_off) stop ids, then done flags
   uint64_t epoch = 0;                  // moves when a buffer moved: a captured step that ranks is stale
   int B = 0, beam = 0, ld = 0, n_stop = 0, done_off = 0, cur = 0;
@@ -260,8 +327,10 @@ struct ASR_LOCAL BeamRanker {
   const int32_t* ancestry() const { return src[cur].as<int32_t>(); }     // the table the next pass's self-attention follows
   int32_t* next_ids() const { return next.as<int32_t>(); }
 
-  void begin(int B_, int beam_, int ld_, const int32_t* stop_ids, int n_stop_, const TimestampRule& ts_, const HotView& hot_, hipStream_t s) {
-    B = B_; beam = beam_; ld = ld_; n_stop = n_stop_; cur = 0; slots_dev = nullptr; slots_off = 0; ts = ts_; hot = hot_;
+  void begin(int B_, int beam_, int ld_, const int32_t* stop_ids, int n_stop_, const TimestampRule& ts_, const HotView& hot_, hipStream_t s,
+             const LmView& lm_ = LmView{}, const char* who = "beam_search") {
+    ASR_REQUIRE(!lm_.on() || lm_.topk >= beam_, "%s: the language model's topk %d is below the beam width %d", who, lm_.topk, beam_);
+    B = B_; beam = beam_; ld = ld_; n_stop = n_stop_; cur = 0; slots_dev = nullptr; slots_off = 0; ts = ts_; hot = hot_; lmod = lm_;
     const size_t N = (size_t)rows(), Nn = std::max<size_t>(N, 64);
     bool moved = false;
     for (DeviceBuffer* q : {&topv, &topi}) moved |= reserve_moved(*q, Nn * BEAM_MAX * 4, s);
@@ -269,6 +338,10 @@ struct ASR_LOCAL BeamRanker {
     moved |= reserve_moved(stop, (size_t)std::max(n_stop, 16) * 4, s);
     for (DeviceBuffer* q : {&src[0], &src[1], &tok[0], &tok[1]}) moved |= reserve_moved(*q, N * ld * 4, s);
     if (hot.on()) for (DeviceBuffer* q : {&node[0], &node[1], &lse}) moved |= reserve_moved(*q, Nn * 4, s);
+    if (lmod.on()) {
+      for (DeviceBuffer* q : {&state[0], &state[1], &lse}) moved |= reserve_moved(*q, Nn * 4, s);
+      for (DeviceBuffer* q : {&lmv, &lmi}) moved |= reserve_moved(*q, Nn * LM_TOPK_MAX * 4, s);
+    }
     if (moved) ++epoch;
     HIP_CHECK(hipStreamSynchronize(s));
     done_off = std::max(n_stop, 16);
@@ -287,8 +360,11 @@ struct ASR_LOCAL BeamRanker {
   void rank_first(float* logits, int ld_logits, int n_valid, const float* bias, hipStream_t s) {
     if (hot.on() && hot.root_save) { HotScope hs(prof, s); launch_hotword_restore(logits, ld_logits, B, n_valid, hot.trie, hot.root_save, s); }
     if (ts.on) ts.enqueue(prof, logits, ld_logits, B, n_valid, tok[cur].as<int32_t>(), ld, len.as<int32_t>(), 0, s);
-    launch_beam_topk(logits, ld_logits, B, n_valid, bias, beam, topv.as<float>(), topi.as<int32_t>(), s, hot.on() ? lse.as<float>() : nullptr);
-    if (hot.on()) rerank(logits, ld_logits, B, n_valid, bias, beam, s);        // utterance b's one row is at the root, as node[cur][b * beam] says
+    if (lmod.on()) rerank_lm(logits, ld_logits, B, n_valid, bias, beam, true, s);     // every utterance starts at the model's start_node
+    else {
+      launch_beam_topk(logits, ld_logits, B, n_valid, bias, beam, topv.as<float>(), topi.as<int32_t>(), s, hot.on() ? lse.as<float>() : nullptr);
+      if (hot.on()) rerank(logits, ld_logits, B, n_valid, bias, beam, s);      // utterance b's one row is at the root, as node[cur][b * beam] says
+    }
     select(1, 0, s);
     flip();
   }
@@ -297,8 +373,11 @@ struct ASR_LOCAL BeamRanker {
   // Timestamp mode: the rules first, row r's history being its len[r] ids of the current token table.
   void enqueue_rank(float* logits, int ld_logits, int n_valid, int n_slots, hipStream_t s) {
     if (ts.on) ts.enqueue(prof, logits, ld_logits, rows(), n_valid, tok[cur].as<int32_t>(), ld, len.as<int32_t>(), 1, s);
-    launch_beam_topk(logits, ld_logits, rows(), n_valid, nullptr, beam, topv.as<float>(), topi.as<int32_t>(), s, hot.on() ? lse.as<float>() : nullptr);
-    if (hot.on()) rerank(logits, ld_logits, rows(), n_valid, nullptr, 1, s);
+    if (lmod.on()) rerank_lm(logits, ld_logits, rows(), n_valid, nullptr, 1, false, s);
+    else {
+      launch_beam_topk(logits, ld_logits, rows(), n_valid, nullptr, beam, topv.as<float>(), topi.as<int32_t>(), s, hot.on() ? lse.as<float>() : nullptr);
+      if (hot.on()) rerank(logits, ld_logits, rows(), n_valid, nullptr, 1, s);
+    }
     select(0, n_slots, s);
   }
   void flip() { cur ^= 1; }
@@ -334,6 +413,15 @@ struct ASR_LOCAL BeamRanker {
     launch_hotword_rerank(logits, ld_logits, n_rows, n_valid, bias, lse.as<float>(), hot.trie, node[cur].as<int32_t>(), node_stride, beam, topv.as<float>(),
                           topi.as<int32_t>(), s);
   }
+  // language model: the topk best columns of every row, then the K best of topM u S by log-prob + delta + LM term (launch_lm_topk / launch_lm_rerank: they
+  // replace beam_topk + the hotword re-rank; the trie is optional)
+  void rerank_lm(const float* logits, int ld_logits, int n_rows, int n_valid, const float* bias, int stride, bool first, hipStream_t s) {
+    LmScope ls(prof, s);
+    launch_lm_topk(logits, ld_logits, n_rows, n_valid, bias, lmod.topk, lmv.as<float>(), lmi.as<int32_t>(), lse.as<float>(), s);
+    launch_lm_rerank(logits, ld_logits, n_rows, n_valid, bias, lmv.as<float>(), lmi.as<int32_t>(), lse.as<float>(), lmod.topk, hot.trie,
+                     hot.on() ? node[cur].as<int32_t>() : nullptr, lmod.lm, lmod.ends, first ? nullptr : state[cur].as<int32_t>(), stride, beam, topv.as<float>(),
+                     topi.as<int32_t>(), s);
+  }
   void select(int first, int n_slots, hipStream_t s) {
     BeamArgs a{};
     a.beam = beam; a.K = beam; a.ld = ld; a.first = first; a.n_slots = n_slots;
@@ -344,6 +432,7 @@ struct ASR_LOCAL BeamRanker {
     a.src_out = src[cur ^ 1].as<int32_t>(); a.tok_out = tok[cur ^ 1].as<int32_t>();
     if (!first) { a.slots_dev = slots_dev; a.slots_off = slots_off; }
     if (hot.on()) { a.node_in = node[cur].as<int32_t>(); a.node_out = node[cur ^ 1].as<int32_t>(); a.trie = hot.trie; }
+    if (lmod.on()) { a.lm = lmod.lm; a.ends = lmod.ends; a.state_in = state[cur].as<int32_t>(); a.state_out = state[cur ^ 1].as<int32_t>(); }
     launch_beam_select(a, B, s);
   }
 };

@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ngram_lm.h"
 
 // Per-utterance geometry, built on the host for every run and uploaded with one copy.
 struct UttPlan {
@@ -151,6 +152,30 @@ struct HotTrie {
   float boost = 0.0f;
 };
 
+// ---- n-gram LM fusion of the autoregressive decoders (decoder_lm.hip; the float64 statement is tests/decoder_lm_ref.py). Every row carries a
+// state of the NgramLm image. The LM term of token c from state s: c one of `ends` and the image lists </s> -> alpha * lm_step(s, </s>), the state stays;
+// else (lp, s') = lm_step(s, c) and the term is __fadd_rn(__fmul_rn(alpha, lp), beta).
+// (ngram_lm.h: lm_token_term, LmEnds)
+constexpr int LM_TOPK_MAX = 32;
+//   launch_lm_topk: per row the M <= LM_TOPK_MAX best (value, id) pairs of v[n] = logits[r][n] + (bias ? bias[n] : 0) over n < n_valid, value descending
+//     then id ascending, and the row's log-sum-exp as launch_beam_topk forms it. cand_v / cand_i [rows][M]: raw values (not log-probabilities); a -inf
+//     column is no candidate, ranks past the last candidate are (-inf, 0); lse [rows] (-inf for a row without a finite column). Exact for every layout
+//     of the row: one pass in launch_beam_topk's geometry with per-thread best-8 lists, and a row where some thread dropped a value that is not
+//     strictly below the M-th winner is redone by M strict-order passes. slow_rows (nullable, device): incremented once per row that took those.
+//   launch_lm_pick: the greedy pick among a row's candidates by (value + LM term, then id ascending): next[r], and the pick's state into state[r]. The
+//     row's state reads as lm.start_node while *n_saved == 0. logprob (nullable) [rows][ld_save]: value - lse of the pick at column *n_saved (dropped at
+//     or past ld_save); a row without a candidate picks id 0, keeps its state and scores -inf. One wave per row, one candidate per lane.
+//   launch_lm_rerank: the beam ranker's merge with the LM on. The K best of topM u S by ((value - lse) + delta) + LM term, then id ascending, go to
+//     topv / topi [rows][K]; S and delta are launch_hotword_rerank's (a trie with n_nodes <= 1: S is empty, delta 0, node is not read). Row r's state is
+//     state[r * stride], or lm.start_node when state is null (the first ranking). Ranks past the last candidate are (-inf, 0).
+void launch_lm_topk(const float* logits, int ld, int rows, int n_valid, const float* bias, int M, float* cand_v, int32_t* cand_i, float* lse, hipStream_t s,
+                    int32_t* slow_rows = nullptr);
+void launch_lm_pick(const float* cand_v, const int32_t* cand_i, const float* lse, int rows, int M, const NgramLm& lm, const LmEnds& ends, int32_t* state,
+                    const int32_t* n_saved, int32_t* next, float* logprob, int ld_save, hipStream_t s);
+void launch_lm_rerank(const float* logits, int ld, int rows, int n_valid, const float* bias, const float* cand_v, const int32_t* cand_i, const float* lse, int M,
+                      const HotTrie& trie, const int32_t* node, const NgramLm& lm, const LmEnds& ends, const int32_t* state, int stride, int K, float* topv,
+                      int32_t* topi, hipStream_t s);
+
 // ---- beam search ranking (Qwen3-ASR and Whisper; semantics of oracle/qwen_asr_oracle.py:beam_search_core). Hypotheses of utterance b are rows b * beam + r.
 constexpr int BEAM_MAX = 8;
 // per row: log-soft-max over the first n_valid columns of logits (+ bias[col] when bias is set: Whisper's BEGIN_SUPPRESS on the first ranking) and the
@@ -170,6 +195,12 @@ struct BeamArgs {
   // token (trie_step); a finished hypothesis and the rows of a finished utterance keep theirs. first: every parent is at the root, node_in is not read.
   const int32_t* node_in = nullptr; int32_t* node_out = nullptr;
   HotTrie trie;
+  // language model (state_out null: none): state_in / state_out [rows] the rows' LM states before / after the pass, handed over as the nodes are -- a kept
+  // row inherits its parent's state advanced by its token (lm_token_term), a finished hypothesis and the rows of a finished utterance keep theirs.
+  // first: every parent is at lm.start_node, state_in is not read.
+  NgramLm lm;
+  const int32_t* state_in = nullptr; int32_t* state_out = nullptr;
+  LmEnds ends;
 };
 // one wave per utterance: rank the <= beam * K extensions (finished hypotheses stand as themselves), keep the best `beam` in order (score
 // descending, then hypothesis, then rank inside the hypothesis), rebuild the rows' ancestry / token tables from their parents'; done[b] = best has ended

@@ -3032,7 +3032,7 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict
 __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
   const int b = blockIdx.x, lane = threadIdx.x, beam = a.beam, K = a.K, base = b * beam;
   const int n_slots = a.slots_dev ? *a.slots_dev + a.slots_off : a.n_slots;
-  __shared__ int par[BEAM_MAX], ntok[BEAM_MAX], nfin[BEAM_MAX], nlen[BEAM_MAX], nnext[BEAM_MAX], nnode[BEAM_MAX];
+  __shared__ int par[BEAM_MAX], ntok[BEAM_MAX], nfin[BEAM_MAX], nlen[BEAM_MAX], nnext[BEAM_MAX], nnode[BEAM_MAX], nstate[BEAM_MAX];
   __shared__ float ncum[BEAM_MAX];
   const bool frozen_utt = !a.first && a.done[b] != 0;
   const int r = lane / K, k = lane - r * K;
@@ -3070,6 +3070,12 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
       if (!frozen) trie_step(a.trie, nd, unused, tokv);
       nnode[rank] = nd;
     }
+    if (a.state_out) {                                     // language model: the parent's state, advanced the same way (an end id scored as </s> leaves it)
+      int st = a.first ? a.lm.start_node : a.state_in[base + r];
+      if (st < 0 || st >= a.lm.n_nodes) st = a.lm.start_node;
+      if (!frozen) (void)lm_token_term(a.lm, a.ends, st, tokv);
+      nstate[rank] = st;
+    }
   }
   __syncthreads();
   // tables: row r' = parent's generated-slot ancestry + the parent itself for the slot written by this pass; parent's tokens + the new id.
@@ -3089,6 +3095,7 @@ __global__ __launch_bounds__(64) void beam_select_kernel(BeamArgs a) {
   }
   if (lane == 0) a.done[b] = nfin[0];
   if (a.node_in && lane < beam) a.node_out[base + lane] = nnode[lane];
+  if (a.state_out && lane < beam) a.state_out[base + lane] = nstate[lane];
 }
 
 }  // namespace
@@ -3102,6 +3109,8 @@ void launch_beam_topk(const float* logits, int ld, int rows, int n_valid, const 
 void launch_beam_select(const BeamArgs& a, int n_utt, hipStream_t s) {
   ASR_REQUIRE(a.beam >= 1 && a.beam <= BEAM_MAX && a.K >= 1 && a.beam * a.K <= 64, "beam_select: beam %d K %d", a.beam, a.K);
   ASR_REQUIRE(!a.node_in || (a.node_out && a.node_out != a.node_in), "beam_select: the hotword node tables are double-buffered");
+  ASR_REQUIRE(!a.state_out || (a.lm.n_nodes > 0 && a.ends.n >= 0 && a.ends.n <= LM_ENDS_MAX && (a.first || (a.state_in && a.state_in != a.state_out))),
+              "beam_select: the language model's state tables are double-buffered");
   hipLaunchKernelGGL(beam_select_kernel, dim3(n_utt), dim3(64), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }

@@ -107,3 +107,17 @@ __device__ __forceinline__ float lm_step(const NgramLm& lm, int& state, int c) {
   }
   return acc;                         // (not reached with a checked image)
 }
+
+// ---- the autoregressive decoders' use of the walk (decoder_lm.hip, beam_select_kernel). `ends`: the family's end-of-text ids, scored as </s>.
+constexpr int LM_ENDS_MAX = 8;
+struct LmEnds { int n = 0; int32_t id[LM_ENDS_MAX] = {}; };
+
+// The LM term of token c from `state`, and the state after it: an end id, when the image lists </s>, costs alpha * log P(</s> | state) without the length
+// bonus and leaves the state; every other token alpha * log P(c | state) + beta, each operation rounded on its own.
+__device__ __forceinline__ float lm_token_term(const NgramLm& lm, const LmEnds& ends, int& state, int c) {
+  bool is_end = false;
+#pragma unroll
+  for (int i = 0; i < LM_ENDS_MAX; ++i) is_end = is_end || (i < ends.n && ends.id[i] == c);     // (constant indices: the list stays in scalar registers)
+  if (is_end && lm.eos >= 0) { int keep = state; return __fmul_rn(lm.alpha, lm_step(lm, keep, lm.eos)); }
+  return __fadd_rn(__fmul_rn(lm.alpha, lm_step(lm, state, c)), lm.beta);
+}

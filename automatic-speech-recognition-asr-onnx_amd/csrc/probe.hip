@@ -1871,7 +1871,8 @@ struct ProbeTrie {
   HotTrie view;
   int n_nodes = 0, n_root = 0;
   // phrases -> the product's trie image on the device (build_hot_trie + hot_trie_view, as TokenHead::set_hotwords does); ids are checked against n_valid first
-  ProbeTrie(Tmp& t, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost, int n_valid, const char* who) {
+  ProbeTrie(Tmp& t, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost, int n_valid, const char* who, bool optional = false) {
+    if (optional && n_phrases == 0) return;                // (the LM hooks: no phrases, no trie -- the view stays empty)
     ASR_REQUIRE(n_phrases >= 1 && ids && offsets && offsets[0] >= 0 && std::isfinite(boost), "%s: hotword phrases missing", who);
     for (int p = 0; p < n_phrases; ++p) {
       ASR_REQUIRE(offsets[p + 1] > offsets[p], "%s: phrase %d is empty", who, p);
@@ -1882,6 +1883,22 @@ struct ProbeTrie {
     HIP_CHECK(hipMemcpy(dw, words.data(), words.size() * 4, hipMemcpyHostToDevice));
     view = hot_trie_view(dw, n_nodes, boost);
     n_root = words[(size_t)2 * n_nodes + 1];
+  }
+};
+
+// the model of the LM hooks on the device: checked as TokenHead::set_lm checks it, uploaded, viewed
+struct ProbeLm {
+  LmView view;
+  ProbeLm(Tmp& t, const asr_probe_lm_model* m, int vocab, const char* who) {
+    ASR_REQUIRE(m && m->image && m->n_words > 0 && m->topk >= 1 && m->topk <= LM_TOPK_MAX && m->n_end >= 0 && m->n_end <= LM_ENDS_MAX && (m->n_end == 0 || m->end_ids),
+                "%s: bad model descriptor", who);
+    for (int i = 0; i < m->n_end; ++i) ASR_REQUIRE(m->end_ids[i] >= 0 && m->end_ids[i] < vocab, "%s: end id %d outside the vocabulary of %d", who, m->end_ids[i], vocab);
+    ngram_lm_validate(m->image, m->n_words, vocab, -1, m->alpha, m->beta, m->oov_logprob, who);
+    int32_t* dw = (int32_t*)t.alloc((size_t)m->n_words * 4);
+    HIP_CHECK(hipMemcpy(dw, m->image, (size_t)m->n_words * 4, hipMemcpyHostToDevice));
+    view.lm = ngram_lm_view(dw, m->image, m->alpha, m->beta, m->oov_logprob);
+    view.topk = m->topk; view.ends.n = m->n_end;
+    for (int i = 0; i < m->n_end; ++i) view.ends.id[i] = m->end_ids[i];
   }
 };
 }  // namespace
@@ -1932,9 +1949,10 @@ extern "C" int asr_probe_hotword(asr_probe_hotword_desc* d) {
   });
 }
 
-extern "C" int asr_probe_hotword_head_steps(asr_probe_hotword_head_desc* d) {
+// the body of asr_probe_hotword_head_steps; with a model (asr_probe_lm_head_steps) it is set after the hotwords and `states` gets the state table per step
+static int probe_head_steps(asr_probe_hotword_head_desc* d, const asr_probe_lm_model* m, int32_t* states, const char* who) {
   return asr_guard([&] {
-    const char* who = "probe_hotword_head_steps";
+    ASR_REQUIRE(!m || states, "%s: the state table is missing", who);
     ASR_REQUIRE(d && d->rows > 0 && d->steps >= 1 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0 && d->logits && d->picks && d->save_ids && d->nodes,
                 "%s: bad descriptor", who);
     ASR_REQUIRE(d->ld_save >= d->steps && d->ld_save <= 1024 && d->range >= 1 && d->range <= d->ld_save, "%s: %d steps / range %d and a history table of %d", who, d->steps,
@@ -1962,6 +1980,11 @@ extern "C" int asr_probe_hotword_head_steps(asr_probe_hotword_head_desc* d) {
     if (d->timestamps) h.set_timestamps(true, d->ts_begin, d->no_timestamps_id, d->eot_id, d->max_initial, d->n_valid, who);
     h.set_scores(d->scores != 0);
     h.set_hotwords(d->ids, d->offsets, d->n_phrases, d->boost, d->n_valid, nullptr, who);
+    if (m) {
+      ASR_REQUIRE(m->image && m->n_words > 0, "%s: the model's image is missing", who);
+      h.set_lm(m->image, m->n_words, m->alpha, m->beta, m->oov_logprob, m->topk, m->end_ids, m->n_end, d->n_valid, nullptr, who);
+    }
+    int32_t* dstates = m ? (int32_t*)t.alloc((size_t)steps * rows * 4) : nullptr;
     h.reserve(rows, nullptr);
     h.restart(nullptr);
     if (d->scores) HIP_CHECK(hipMemset(h.d_scores.ptr, 0xFF, (size_t)rows * d->ld_save * 4));
@@ -1975,6 +1998,7 @@ extern "C" int asr_probe_hotword_head_steps(asr_probe_hotword_head_desc* d) {
       h.enqueue(row, ld, rows, d->n_valid, i == 0 ? dvec : nullptr, i > 0, dpick + (size_t)i * rows, nullptr);
       h.consumed();
       if (h.hot() && !d->timed) HIP_CHECK(hipMemcpyAsync(dnodes + (size_t)i * rows, h.d_node.ptr, (size_t)rows * 4, hipMemcpyDeviceToDevice, nullptr));
+      if (m && !d->timed) HIP_CHECK(hipMemcpyAsync(dstates + (size_t)i * rows, h.d_lmstate.ptr, (size_t)rows * 4, hipMemcpyDeviceToDevice, nullptr));
       if (d->logits_out && !d->timed) {
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(d->logits_out + (size_t)i * rows * ld, row, lbytes, hipMemcpyDeviceToHost));
@@ -1988,25 +2012,34 @@ extern "C" int asr_probe_hotword_head_steps(asr_probe_hotword_head_desc* d) {
     }
     HIP_CHECK(hipMemcpy(d->picks, dpick, (size_t)steps * rows * 4, hipMemcpyDeviceToHost));
     if (h.hot() && !d->timed) HIP_CHECK(hipMemcpy(d->nodes, dnodes, (size_t)steps * rows * 4, hipMemcpyDeviceToHost));
+    if (m && !d->timed) HIP_CHECK(hipMemcpy(states, dstates, (size_t)steps * rows * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(d->save_ids, h.d_save.ptr, (size_t)rows * d->ld_save * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(&d->n_saved_after, h.d_nsaved.ptr, 4, hipMemcpyDeviceToHost));
     if (d->scores) HIP_CHECK(hipMemcpy(d->logprob, h.d_scores.ptr, (size_t)rows * d->ld_save * 4, hipMemcpyDeviceToHost));
   });
 }
 
-extern "C" int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d) {
+extern "C" int asr_probe_hotword_head_steps(asr_probe_hotword_head_desc* d) { return probe_head_steps(d, nullptr, nullptr, "probe_hotword_head_steps"); }
+extern "C" int asr_probe_lm_head_steps(const asr_probe_lm_model* m, asr_probe_hotword_head_desc* d, int32_t* states) {
+  if (!m) return asr_guard([&] { ASR_REQUIRE(false, "probe_lm_head_steps: the model is missing"); });
+  return probe_head_steps(d, m, states, "probe_lm_head_steps");
+}
+
+// the body of asr_probe_hotword_rank; with a model (asr_probe_lm_rank) the pass is BeamRanker's with the LM on and the trie is optional
+static int probe_rank(asr_probe_hotword_rank_desc* d, const asr_probe_lm_model* m, const int32_t* state_in, int32_t* state_out, const char* who) {
   return asr_guard([&] {
-    const char* who = "probe_hotword_rank";
     ASR_REQUIRE(d && d->n_utt > 0 && d->beam >= 1 && d->beam <= BEAM_MAX && d->beam * d->beam <= 64 && d->tab_ld > 0 && d->n_slots >= 0 && d->n_slots <= d->tab_ld &&
                 d->n_stop >= 0 && (d->n_stop == 0 || d->stop) && d->logits && d->n_valid >= d->beam && d->ld >= d->n_valid && d->ld % 128 == 0 && d->cum && d->fin && d->len &&
                 d->next && d->done && d->src_in && d->tok_in && d->src_out && d->tok_out && d->node_in && d->node_out && d->topv && d->topi, "%s: bad descriptor", who);
+    ASR_REQUIRE(!m || (state_out && (d->first || state_in)), "%s: the state tables are missing", who);
     asr_require_device(0);
     Tmp t;
     const int N = d->n_utt * d->beam, R = d->first ? d->n_utt : N, K = d->beam;
-    ProbeTrie tr(t, d->ids, d->offsets, d->n_phrases, d->boost, d->n_valid, who);
+    ProbeTrie tr(t, d->ids, d->offsets, d->n_phrases, d->boost, d->n_valid, who, m != nullptr);
+    const bool hot = tr.view.n_nodes > 1;
     for (int r = 0; r < N; ++r) {
       ASR_REQUIRE(d->len[r] >= 0 && d->len[r] <= d->tab_ld, "%s: row %d length %d outside the table", who, r, d->len[r]);
-      ASR_REQUIRE(d->node_in[r] >= 0 && d->node_in[r] < tr.n_nodes, "%s: node %d of row %d outside the trie", who, d->node_in[r], r);
+      ASR_REQUIRE(!hot || (d->node_in[r] >= 0 && d->node_in[r] < tr.n_nodes), "%s: node %d of row %d outside the trie", who, d->node_in[r], r);
     }
     auto up = [&](const void* h, size_t bytes) -> void* {
       void* p = t.alloc(std::max(bytes, (size_t)4));
@@ -2025,10 +2058,32 @@ extern "C" int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d) {
     a.stop = d->n_stop ? (const int32_t*)up(d->stop, (size_t)d->n_stop * 4) : nullptr; a.n_stop = d->n_stop;
     a.src_in = (const int32_t*)up(d->src_in, tab); a.tok_in = (const int32_t*)up(d->tok_in, tab);
     a.src_out = (int32_t*)up(d->src_out, tab); a.tok_out = (int32_t*)up(d->tok_out, tab);
-    a.node_in = (const int32_t*)up(d->node_in, rows4); a.node_out = (int32_t*)up(d->node_out, rows4); a.trie = tr.view;
-    // the ranker's sequence (decode_head.h: BeamRanker::rank_first / enqueue_rank with hotwords on)
-    launch_beam_topk(dlog, d->ld, R, d->n_valid, dvec, K, dv, di, nullptr, dl);
-    launch_hotword_rerank(dlog, d->ld, R, d->n_valid, dvec, dl, tr.view, a.node_in, d->first ? d->beam : 1, K, dv, di, nullptr);
+    const int32_t* dnode_in = (const int32_t*)up(d->node_in, rows4);
+    int32_t* dnode_out = (int32_t*)up(d->node_out, rows4);
+    if (hot) { a.node_in = dnode_in; a.node_out = dnode_out; a.trie = tr.view; }
+    const int stride = d->first ? d->beam : 1;
+    float* cv = nullptr; int32_t* ci = nullptr;
+    LmView lmv;
+    if (m) {
+      ProbeLm pl(t, m, d->n_valid, who);
+      lmv = pl.view;
+      ASR_REQUIRE(lmv.topk >= K, "%s: the language model's topk %d is below the beam width %d", who, lmv.topk, K);
+      for (int r = 0; r < N && !d->first; ++r) ASR_REQUIRE(state_in[r] >= 0 && state_in[r] < lmv.lm.n_nodes, "%s: state %d of row %d outside the image", who, state_in[r], r);
+      cv = (float*)t.alloc((size_t)R * lmv.topk * 4); ci = (int32_t*)t.alloc((size_t)R * lmv.topk * 4);
+      a.lm = lmv.lm; a.ends = lmv.ends;
+      a.state_in = d->first ? nullptr : (const int32_t*)up(state_in, rows4);
+      a.state_out = (int32_t*)up(state_out, rows4);
+    }
+    // the ranker's sequence (decode_head.h: BeamRanker::rank_first / enqueue_rank with hotwords on, or with a model)
+    auto rank_lm = [&] {
+      launch_lm_topk(dlog, d->ld, R, d->n_valid, dvec, lmv.topk, cv, ci, dl, nullptr);
+      launch_lm_rerank(dlog, d->ld, R, d->n_valid, dvec, cv, ci, dl, lmv.topk, tr.view, hot ? a.node_in : nullptr, lmv.lm, lmv.ends, a.state_in, stride, K, dv, di, nullptr);
+    };
+    auto rank_plain = [&](bool with_lse) {
+      launch_beam_topk(dlog, d->ld, R, d->n_valid, dvec, K, dv, di, nullptr, with_lse ? dl : nullptr);
+      if (with_lse && hot) launch_hotword_rerank(dlog, d->ld, R, d->n_valid, dvec, dl, tr.view, a.node_in, stride, K, dv, di, nullptr);
+    };
+    if (m) rank_lm(); else rank_plain(true);
     launch_beam_select(a, d->n_utt, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(d->topv, dv, kb, hipMemcpyDeviceToHost));
@@ -2040,7 +2095,8 @@ extern "C" int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d) {
     HIP_CHECK(hipMemcpy(d->done, a.done, (size_t)d->n_utt * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(d->src_out, a.src_out, tab, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(d->tok_out, a.tok_out, tab, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(d->node_out, a.node_out, rows4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->node_out, dnode_out, rows4, hipMemcpyDeviceToHost));
+    if (m) HIP_CHECK(hipMemcpy(state_out, a.state_out, rows4, hipMemcpyDeviceToHost));
     d->ms_topk = d->ms_rerank = 0.0f;
     if (d->iters > 0) {                  // timing: beam_topk alone against beam_topk (lse_out) + re-rank, `iters` launches back to back (the pairs go to scratch)
       hipEvent_t ev[2];
@@ -2048,8 +2104,9 @@ extern "C" int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d) {
       for (int mode = 0; mode < 2; ++mode) {
         HIP_CHECK(hipEventRecord(ev[0], nullptr));
         for (int i = 0; i < d->iters; ++i) {
-          launch_beam_topk(dlog, d->ld, R, d->n_valid, dvec, K, dv, di, nullptr, mode ? dl : nullptr);
-          if (mode) launch_hotword_rerank(dlog, d->ld, R, d->n_valid, dvec, dl, tr.view, a.node_in, d->first ? d->beam : 1, K, dv, di, nullptr);
+          if (!m) rank_plain(mode != 0);                   // beam_topk alone against beam_topk (lse_out) + re-rank
+          else if (mode) rank_lm();                        // with a model: the pass without it (the re-rank only with a trie) against lm_topk + lm_rerank
+          else rank_plain(hot);
         }
         HIP_CHECK(hipEventRecord(ev[1], nullptr));
         HIP_CHECK(hipDeviceSynchronize());
@@ -2057,6 +2114,85 @@ extern "C" int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d) {
       }
       HIP_CHECK(hipEventDestroy(ev[0])); HIP_CHECK(hipEventDestroy(ev[1]));
     }
+  });
+}
+
+extern "C" int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d) { return probe_rank(d, nullptr, nullptr, nullptr, "probe_hotword_rank"); }
+extern "C" int asr_probe_lm_rank(const asr_probe_lm_model* m, asr_probe_hotword_rank_desc* d, const int32_t* state_in, int32_t* state_out) {
+  if (!m) return asr_guard([&] { ASR_REQUIRE(false, "probe_lm_rank: the model is missing"); });
+  return probe_rank(d, m, state_in, state_out, "probe_lm_rank");
+}
+
+extern "C" int asr_probe_lm_topk(asr_probe_lm_topk_desc* d) {
+  return asr_guard([&] {
+    const char* who = "probe_lm_topk";
+    ASR_REQUIRE(d && d->rows > 0 && d->n_valid >= 1 && d->ld >= d->n_valid && d->ld % 128 == 0 && d->M >= 1 && d->M <= LM_TOPK_MAX && d->logits && d->cand_v && d->cand_i &&
+                d->lse && d->iters >= 0, "%s: bad descriptor", who);
+    asr_require_device(0);
+    Tmp t;
+    const int rows = d->rows, M = d->M;
+    const size_t lbytes = (size_t)rows * d->ld * 4, cb = (size_t)rows * M * 4;
+    float* dlog = (float*)t.alloc(lbytes);
+    HIP_CHECK(hipMemcpy(dlog, d->logits, lbytes, hipMemcpyHostToDevice));
+    float* dvec = nullptr;
+    if (d->vec) { dvec = (float*)t.alloc((size_t)d->ld * 4); HIP_CHECK(hipMemcpy(dvec, d->vec, (size_t)d->ld * 4, hipMemcpyHostToDevice)); }
+    float* cv = (float*)t.alloc(cb); int32_t* ci = (int32_t*)t.alloc(cb); float* dl = (float*)t.alloc((size_t)rows * 4);
+    int32_t* slow = (int32_t*)t.alloc(256);
+    HIP_CHECK(hipMemset(slow, 0, 4));
+    launch_lm_topk(dlog, d->ld, rows, d->n_valid, dvec, M, cv, ci, dl, nullptr, slow);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(d->cand_v, cv, cb, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->cand_i, ci, cb, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->lse, dl, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&d->slow_rows, slow, 4, hipMemcpyDeviceToHost));
+    d->ms_lm_topk = d->ms_beam_topk = 0.0f;
+    if (d->iters > 0) {
+      const int K = std::min(M, (int)BEAM_MAX);
+      float* dv = (float*)t.alloc((size_t)rows * K * 4); int32_t* di = (int32_t*)t.alloc((size_t)rows * K * 4);
+      hipEvent_t ev[2];
+      HIP_CHECK(hipEventCreate(&ev[0])); HIP_CHECK(hipEventCreate(&ev[1]));
+      for (int mode = 0; mode < 2; ++mode) {
+        HIP_CHECK(hipEventRecord(ev[0], nullptr));
+        for (int i = 0; i < d->iters; ++i) {
+          if (mode) launch_lm_topk(dlog, d->ld, rows, d->n_valid, dvec, M, cv, ci, dl, nullptr, nullptr);
+          else launch_beam_topk(dlog, d->ld, rows, d->n_valid, dvec, K, dv, di, nullptr, dl);
+        }
+        HIP_CHECK(hipEventRecord(ev[1], nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipEventElapsedTime(mode ? &d->ms_lm_topk : &d->ms_beam_topk, ev[0], ev[1]));
+      }
+      HIP_CHECK(hipEventDestroy(ev[0])); HIP_CHECK(hipEventDestroy(ev[1]));
+    }
+  });
+}
+
+extern "C" int asr_probe_lm_pick(const asr_probe_lm_model* m, asr_probe_lm_pick_desc* d) {
+  return asr_guard([&] {
+    const char* who = "probe_lm_pick";
+    ASR_REQUIRE(m && d && d->rows > 0 && d->cand_v && d->cand_i && d->lse && d->state && d->next && (!d->logprob || d->ld_save >= 1) && d->n_saved >= 0, "%s: bad descriptor", who);
+    ASR_REQUIRE(m->image && m->n_words >= NGRAM_LM_HEADER, "%s: the model's image is missing", who);
+    asr_require_device(0);
+    Tmp t;
+    const int rows = d->rows, vocab = m->image[3];
+    ProbeLm pl(t, m, vocab, who);
+    const int M = pl.view.topk;
+    for (int i = 0; i < rows * M; ++i) ASR_REQUIRE(d->cand_i[i] >= 0 && d->cand_i[i] < vocab, "%s: candidate id %d outside the image's vocabulary of %d", who, d->cand_i[i], vocab);
+    for (int r = 0; r < rows; ++r) ASR_REQUIRE(d->state[r] >= 0 && d->state[r] < pl.view.lm.n_nodes, "%s: state %d of row %d outside the image", who, d->state[r], r);
+    auto up = [&](const void* h, size_t bytes) -> void* {
+      void* p = t.alloc(std::max(bytes, (size_t)4));
+      HIP_CHECK(hipMemcpy(p, h, bytes, hipMemcpyHostToDevice));
+      return p;
+    };
+    const size_t cb = (size_t)rows * M * 4, sb = (size_t)rows * std::max(d->ld_save, 1) * 4;
+    int32_t* dstate = (int32_t*)up(d->state, (size_t)rows * 4);
+    int32_t* dnext = (int32_t*)t.alloc((size_t)rows * 4);
+    float* dlp = d->logprob ? (float*)up(d->logprob, sb) : nullptr;
+    launch_lm_pick((const float*)up(d->cand_v, cb), (const int32_t*)up(d->cand_i, cb), (const float*)up(d->lse, (size_t)rows * 4), rows, M, pl.view.lm, pl.view.ends, dstate,
+                   (const int32_t*)up(&d->n_saved, 4), dnext, dlp, d->ld_save, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(d->state, dstate, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(d->next, dnext, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (dlp) HIP_CHECK(hipMemcpy(d->logprob, dlp, sb, hipMemcpyDeviceToHost));
   });
 }
 

@@ -1388,7 +1388,7 @@ void QwSession::beam_search(int beam, int max_new, const int32_t* stop_ids, int 
   max_new = std::min(max_new, c.max_seq_len - max_len);  // positions (RoPE rows) end at max_seq_len
   const int Sb = round_up(max_new, 16), ld = Sb;         // generated slots per hypothesis row; the prompts stay in the prefill cache
   // ---- the first ranking reads the prefill logits; do it before any buffer grows
-  ranker.begin(B, beam, ld, stop_ids, n_stop, TimestampRule{}, head.hot_view("qwen_beam_search"), stream);
+  ranker.begin(B, beam, ld, stop_ids, n_stop, TimestampRule{}, head.hot_view("qwen_beam_search"), stream, head.lm, "qwen_beam_search");
   ranker.rank_first(d_logits.as<float>(), vpad, c.vocab, nullptr, stream);
   // ---- hypothesis rows: caches, counters, row buffers, the one-row-per-hypothesis plan
   for (DeviceBuffer* q : {&d_bhist, &d_bp0}) q->reserve((size_t)std::max(N, 64) * 4, stream);
@@ -1504,6 +1504,16 @@ extern "C" int asr_qwen_set_hotwords(asr_session* s, const int32_t* ids, const i
     QwSession* q = qwen_session(s, "qwen_set_hotwords");
     HIP_CHECK(hipSetDevice(q->device));
     q->head.set_hotwords(ids, offsets, n_phrases, boost, q->cfg.vocab, q->stream, "qwen_set_hotwords");
+  });
+}
+
+extern "C" int asr_qwen_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob, int topk,
+                               const int32_t* end_ids, int n_end_ids) {
+  return asr_guard([&] {
+    QwSession* q = qwen_session(s, "qwen_set_lm");
+    ASR_REQUIRE(!q->aligner(), "qwen_set_lm: a forced-aligner session (classify_num %d) has no LM head to fuse a language model into", q->cfg.classify_num);
+    HIP_CHECK(hipSetDevice(q->device));
+    q->head.set_lm(image_words, n_words, alpha, beta, oov_logprob, topk, end_ids, n_end_ids, q->cfg.vocab, q->stream, "qwen_set_lm");
   });
 }
 

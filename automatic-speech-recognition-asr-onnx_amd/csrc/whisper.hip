@@ -814,7 +814,7 @@ void WhSession::beam_search(int beam, int max_new, int eos_id, int32_t* tokens_o
   if (precision == ASR_PRECISION_BF16) grow(d_dlo, (size_t)3 * Rp * d * 2);
   grow(d_dqkv, (size_t)Rp * (3 * d + d + d + dff + d) * eT + (size_t)Rp * d * eT);
   const int n_stop = eos_id >= 0 ? 1 : 0;
-  ranker.begin(B, beam, ld, &eos_id, n_stop, head.ts, head.hot_view("whisper_beam_search"), stream);
+  ranker.begin(B, beam, ld, &eos_id, n_stop, head.ts, head.hot_view("whisper_beam_search"), stream, head.lm, "whisper_beam_search");
   HIP_CHECK(hipMemcpyAsync(d_bhist.ptr, d_hist.ptr, 4, hipMemcpyDeviceToDevice, stream));      // the rows' position: the prompt length p0 the prefill left
   // ---- first ranking: the prefill's logits (B rows, left in place) + BEGIN_SUPPRESS, as the arg-max head after a prefill. In timestamp mode the head has
   // already masked them by the initial rule; the ranker applies it again, which changes nothing.
@@ -1101,6 +1101,15 @@ extern "C" int asr_whisper_set_hotwords(asr_session* s, const int32_t* ids, cons
     WhSession* w = whisper_session(s, "whisper_set_hotwords");
     HIP_CHECK(hipSetDevice(w->device));
     w->head.set_hotwords(ids, offsets, n_phrases, boost, w->cfg.vocab, w->stream, "whisper_set_hotwords");
+  });
+}
+
+extern "C" int asr_whisper_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob, int topk,
+                                  const int32_t* end_ids, int n_end_ids) {
+  return asr_guard([&] {
+    WhSession* w = whisper_session(s, "whisper_set_lm");
+    HIP_CHECK(hipSetDevice(w->device));
+    w->head.set_lm(image_words, n_words, alpha, beta, oov_logprob, topk, end_ids, n_end_ids, w->cfg.vocab, w->stream, "whisper_set_lm");
   });
 }
 

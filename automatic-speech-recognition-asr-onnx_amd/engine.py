@@ -688,6 +688,22 @@ def _token_head(prefix: str, default_range: int, penalty_doc: str):
             ids, offs = _flatten_phrases(phrases)
             _lib.check(entry("set_hotwords")(self._h, _ip(ids), _ip(offs), len(offs) - 1, C.c_float(boost)))
 
+        def set_lm(self, lm, alpha: float = 0.5, beta: float = 0.0, oov_logprob: float | None = None, topk: int = 16, end_ids: Sequence[int] = ()):
+            """n-gram LM shallow fusion in the decoder's selection (asr_<family>_set_lm): `lm` an lm.NgramLM, or an int32 image as NgramLM.image returns
+            it; None clears it. Every sequence -- every hypothesis of beam_search -- carries a state of the model that follows its own picks from the start
+            state after a prefill. Of the `topk` (1..32) best columns of the row the selection sees, the greedy heads pick the one with the largest logit +
+            alpha * log P(token | history) + beta; beam_search ranks by log-probability + hotword bonus change + that term (its scores include it; topk
+            must reach the beam width). A token without a unigram costs oov_logprob (default: the model's <unk>, else 0) and leaves the history alone; one
+            of `end_ids` (at most 8: the family's end-of-text ids) costs alpha * log P(</s> | history). Tokens outside the topk columns are not considered.
+            The sampling head ignores the model. A malformed image or a bad argument raises AsrError and leaves the model in force."""
+            if lm is None:
+                _lib.check(entry("set_lm")(self._h, None, 0, 0.0, 0.0, 0.0, 0, None, 0))
+                return
+            img, oov = _lm_image(lm, self.cfg.vocab, oov_logprob)
+            end_ids = [int(e) for e in end_ids]
+            ends = np.ascontiguousarray(end_ids or [0], dtype=np.int32)
+            _lib.check(entry("set_lm")(self._h, _ip(img), img.size, float(alpha), float(beta), oov, int(topk), _ip(ends), len(end_ids)))
+
     TokenHeadMixin.set_penalty.__doc__ = penalty_doc
     return TokenHeadMixin
 

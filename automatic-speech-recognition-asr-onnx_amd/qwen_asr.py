@@ -124,8 +124,12 @@ class QwenAsrTranscriber:
     def __init__(self, cfg: QwenAsrConfig, session: QwenAsrSession, metadata: dict, tokenizer=None, normalise_audio: bool = False,
                  repeat_penalty: float = 1.0, penalty_range: int = 10, use_sampling: bool = False, temperature: float = 0.8, top_k: int = 10,
                  top_p: float = 0.95, sampling_repetition_penalty: float = 1.0, seed: int = 0, beam_size: int = 1, token_scores: bool = False,
-                 hotwords=None, hotword_boost: float = 2.0):
+                 hotwords=None, hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0, lm_topk: int = 16):
         self.cfg, self.sess, self.tokenizer = cfg, session, tokenizer
+        # n-gram LM shallow fusion (the build's own: asr_qwen_set_lm): an lm.NgramLM or an image, in force where the hotwords are; the stop ids are scored as </s>
+        self.lm, self.lm_weight, self.length_bonus, self.lm_topk = lm, float(lm_weight), float(length_bonus), int(lm_topk)
+        if lm is not None and int(beam_size) > self.lm_topk:
+            raise ValueError(f"lm_topk {self.lm_topk} is below beam_size {beam_size}")
         # hotword boosting (the build's own: asr_qwen_set_hotwords): token-id lists, or text when a tokenizer is loaded (both spellings of a phrase, at the
         # start of the text and inside it); in force for the prefill and every id after it, the beam search included
         from .engine import hotword_id_variants
@@ -188,6 +192,8 @@ class QwenAsrTranscriber:
             self.sess.set_token_scores(True)
         if self.hotwords:
             self.sess.set_hotwords(self.hotwords, self.hotword_boost)
+        if self.lm is not None:
+            self.sess.set_lm(self.lm, self.lm_weight, self.length_bonus, topk=self.lm_topk, end_ids=self.stop[:8])
         try:
             toks, limits, ids_len, scores = self._prefill_and_generate(audios, pre, post, max_new)
         finally:
@@ -195,6 +201,8 @@ class QwenAsrTranscriber:
                 self.sess.set_token_scores(False)
             if self.hotwords:
                 self.sess.set_hotwords([])
+            if self.lm is not None:
+                self.sess.set_lm(None)
         wall = time.time() - t0
         out = []
         for b in range(B):

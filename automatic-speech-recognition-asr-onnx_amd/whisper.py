@@ -37,6 +37,9 @@
                             decoder favours (asr_whisper_set_hotwords): a pick that continues a phrase gains hotword_boost, a broken partial match gives its
                             part back. In force from the full-prompt prefill to the last id of every decode (fallback attempts and beam_size > 1 included);
                             the [SOT] probe and the forced alignment pass run without it.
+  lm=NgramLM              = this build's own mode: a back-off n-gram model fused into the selection (asr_whisper_set_lm; lm_weight * log P(token | history)
+                            + length_bonus per token over the lm_topk best columns, eot scored as </s>), in force where the hotwords are; the sampler
+                            of a temperature fallback ignores it.
 Batch extension: `transcribe` takes a list of independent clips as one batch (language detection / no-speech per clip);
 `transcribe_file` is the reference's per-file behaviour (the windows of one file form the batch).
 """
@@ -263,6 +266,7 @@ class WhisperTranscriber:
                  medfilt_width: int = 7, piece_decoder=None, token_scores: bool = False, temperature_fallback=None,
                  compression_ratio_threshold: float | None = 2.4, logprob_threshold: float | None = -1.0,
                  hotwords=None, hotword_boost: float = 2.0, hotword_encoder=None,
+                 lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0, lm_topk: int = 16,
                  initial_prompt=None, condition_on_previous_text: bool = False, prompt_encoder=None, prompt_reset_temperature: float = 0.5):
         # text prompts (the build's own mode, OpenAI Whisper's options; WhisperSession.prefill_prompts): initial_prompt = token ids of a glossary / style hint,
         # or text when prompt_encoder(text) -> ids is given (a tokenizer's encode without special tokens); condition_on_previous_text: transcribe_file runs
@@ -281,6 +285,10 @@ class WhisperTranscriber:
         # pass run without it.
         from .engine import hotword_id_variants
         self.hotwords, self.hotword_boost = hotword_id_variants(hotwords, hotword_encoder), float(hotword_boost)
+        # n-gram LM shallow fusion (the build's own: asr_whisper_set_lm): an lm.NgramLM or an image, in force where the hotwords are; eot is scored as </s>
+        self.lm, self.lm_weight, self.length_bonus, self.lm_topk = lm, float(lm_weight), float(length_bonus), int(lm_topk)
+        if lm is not None and beam_size > self.lm_topk:
+            raise ValueError(f"lm_topk {self.lm_topk} is below beam_size {beam_size}")
         if beam_size > 1 and (float(repeat_penalty) != 1.0 or use_sampling):
             raise ValueError("beam_size > 1 does not combine with a repeat penalty or sampling")
         # token scores / the temperature fallback (the build's own; thresholds are OpenAI's defaults, arguments and not measurements)
@@ -346,6 +354,8 @@ class WhisperTranscriber:
             self.sess.set_timestamps(False)
         if self.hotwords:
             self.sess.set_hotwords([])                                      # language detection and the no-speech probability read raw logits
+        if self.lm is not None:
+            self.sess.set_lm(None)                                          # ... and the probe's pick is the model's own
         return self.sess.prefill(np.full((B, 1), self.cfg.sot_id, dtype=np.int32))[1]
 
     def _prefill_and_continue(self, prompt: np.ndarray, limit: int, audio_samples=None, skip=None, sampling=None, align: bool = True):
@@ -368,6 +378,8 @@ class WhisperTranscriber:
             self.sess.set_word_timestamps(True, self.alignment_heads, limit + 1)
         if self.hotwords:
             self.sess.set_hotwords(self.hotwords, self.hotword_boost)
+        if self.lm is not None:
+            self.sess.set_lm(self.lm, self.lm_weight, self.length_bonus, topk=self.lm_topk, end_ids=(self.cfg.eot_id,))
         try:
             self._prefill(prompt)
             toks = self._continue(limit) if limit > 0 else [np.zeros(0, np.int32)] * B
@@ -385,6 +397,8 @@ class WhisperTranscriber:
                 self.sess.set_word_timestamps(False)
             if self.hotwords:
                 self.sess.set_hotwords([])
+            if self.lm is not None:
+                self.sess.set_lm(None)
         if self.word_timestamps and not live and limit > 0 and align:
             frames = self._forced_alignment(prompt, [self._text_ids(tk) for tk in toks], audio_samples, skip)
         return toks, frames, scores

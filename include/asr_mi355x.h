@@ -420,6 +420,19 @@ int asr_whisper_set_token_scores(asr_session* s, int enable);
  * Every call returns all nodes to the root. Ids outside the vocabulary, empty phrases and a boost that is not finite are rejected (the list in force stays).
  * Set the list before the prefill; asr_whisper_beam_search refuses a list that changed between the prefill and the search. */
 int asr_whisper_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+/* Back-off n-gram language model fused into the decoder's selection (shallow fusion; the build's own mode). image_words / n_words / alpha / beta /
+ * oov_logprob as asr_sensevoice_set_lm takes them, the image checked the same way against the session's vocabulary (this family has no blank id); a null image
+ * or n_words == 0 clears the model. Every sequence (in asr_whisper_beam_search every hypothesis) carries a state of the model that follows its own picks from
+ * start_node after a prefill; prompt tokens and ids the host feeds to asr_whisper_decode do not move it. The LM term of a token is alpha * log P(token | state)
+ * + beta; a token without a unigram (timestamps, specials) costs oov_logprob and keeps the state; one of the n_end_ids (at most 8, inside the vocabulary)
+ * end_ids costs alpha * log P(</s> | state) when the image lists </s>, no beta, and keeps the state. Only the `topk` (1..32) best columns of the row the
+ * selection sees -- after the penalty, the hotword bias, the timestamp rules and BEGIN_SUPPRESS, by value then id -- are candidates (a -inf column never is):
+ * the arg-max, penalty-greedy, timestamp and token-score heads pick the candidate with the largest logit + LM term (ties to the lower id); a token score stays
+ * the model's log-soft-max of the row at the pick. The sampling head ignores the model. asr_whisper_beam_search ranks a row's extensions by log-soft-max +
+ * hotword bonus change + LM term over the topk columns and the hotword columns, scores_out includes the LM terms, and topk below the beam width is refused
+ * there. Setting or clearing returns every state to start_node. A refused call leaves the model in force. */
+int asr_whisper_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob, int topk,
+                       const int32_t* end_ids, int n_end_ids);
 int asr_whisper_token_scores(asr_session* s, float* logprob_out, int out_stride, int32_t* n_out);
 /* Segment timestamps: OpenAI Whisper's ApplyTimestampRules inside the decode head. The reference has no timestamp mode (it defines NO_TIMESTAMPS_TOKEN and
  * always puts it in the prompt), so -- like the beam search -- this mode is the build's own. With enable != 0 the prompt carries no <|notimestamps|> and,
@@ -510,6 +523,9 @@ int asr_qwen_set_sampling_noise(asr_session* s, const float* uniforms, int count
 int asr_qwen_set_token_scores(asr_session* s, int enable);
 /* hotword boosting, as asr_whisper_set_hotwords (no timestamp rules here; in asr_qwen_beam_search every hypothesis carries its node) */
 int asr_qwen_set_hotwords(asr_session* s, const int32_t* ids, const int32_t* offsets, int n_phrases, float boost);
+/* n-gram language model fusion, as asr_whisper_set_lm (no timestamp rules or BEGIN_SUPPRESS here; a forced-aligner session refuses the call) */
+int asr_qwen_set_lm(asr_session* s, const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob, int topk, const int32_t* end_ids,
+                    int n_end_ids);
 int asr_qwen_token_scores(asr_session* s, float* logprob_out, int out_stride, int32_t* n_out);
 /* continuation after a prefill with the selected head (:687-745): tokens_out host [B][max_new], n_out host [B]; a sequence ends at
  * the first id in stop_ids (not emitted) or when the cache is full. */

@@ -383,6 +383,42 @@ typedef struct asr_probe_hotword_rank_desc {
 } asr_probe_hotword_rank_desc;
 int asr_probe_hotword_rank(asr_probe_hotword_rank_desc* d);
 
+/* n-gram LM fusion of the autoregressive decoders (csrc/decoder_lm.hip, launchers in csrc/kernels.h). The model of every hook: an image as
+ * asr_whisper_set_lm takes it (checked against n_valid as the vocabulary), the weights, the candidate width topk (1..32) and the end ids. */
+typedef struct asr_probe_lm_model {
+  const int32_t* image; int64_t n_words;
+  float alpha, beta, oov_logprob;
+  int32_t topk;
+  const int32_t* end_ids; int32_t n_end;
+} asr_probe_lm_model;
+/* launch_lm_topk on host arrays: logits [rows][ld], vec (bias, nullable) -> cand_v / cand_i [rows][M], lse [rows], slow_rows = the rows that took the
+ * strict-order passes. iters > 0: afterwards launch_lm_topk (ms_lm_topk) and launch_beam_topk at K = min(M, 8) with lse_out (ms_beam_topk) are timed, `iters`
+ * launches each back to back between two device events. */
+typedef struct asr_probe_lm_topk_desc {
+  int32_t rows, n_valid, ld, M;
+  const float* logits; const float* vec;
+  float* cand_v; int32_t* cand_i; float* lse;
+  int32_t slow_rows;
+  int32_t iters; float ms_lm_topk, ms_beam_topk;
+} asr_probe_lm_topk_desc;
+int asr_probe_lm_topk(asr_probe_lm_topk_desc* d);
+/* launch_lm_pick on host arrays: candidates cand_v / cand_i [rows][topk] and lse [rows] as launch_lm_topk leaves them (ids inside the image's vocabulary),
+ * state [rows] in / out, n_saved the device counter's value (0: every row counts as at start_node) -> next [rows], logprob (nullable) [rows][ld_save]. */
+typedef struct asr_probe_lm_pick_desc {
+  int32_t rows, n_saved, ld_save;
+  const float* cand_v; const int32_t* cand_i; const float* lse;
+  int32_t* state; int32_t* next; float* logprob;
+} asr_probe_lm_pick_desc;
+int asr_probe_lm_pick(const asr_probe_lm_model* m, asr_probe_lm_pick_desc* d);
+/* asr_probe_hotword_head_steps with the model set on the head after the hotwords (TokenHead::set_lm); states [steps][rows]: the state table after every
+ * step. n_phrases == 0 leaves the hotwords off. */
+int asr_probe_lm_head_steps(const asr_probe_lm_model* m, asr_probe_hotword_head_desc* d, int32_t* states);
+/* asr_probe_hotword_rank with the model on, as BeamRanker runs it: launch_lm_topk (M = topk), launch_lm_rerank, launch_beam_select with the node and the
+ * state hand-over. n_phrases == 0: no trie (node_in / node_out are not used). state_in [rows] the rows' states before the pass (not read when first != 0),
+ * state_out [rows] uploaded as given and read back. iters > 0: ms_topk times the pass without a model (launch_beam_topk at K = beam, + lse_out and
+ * launch_hotword_rerank with a trie), ms_rerank launch_lm_topk + launch_lm_rerank. */
+int asr_probe_lm_rank(const asr_probe_lm_model* m, asr_probe_hotword_rank_desc* d, const int32_t* state_in, int32_t* state_out);
+
 /* One kernel of the Whisper token-timestamp path (csrc/whisper_align.hip, launchers in csrc/kernels.h) on host arrays. Every extent a kernel follows is checked
  * here first. op:
  *   0 launch_align_scores: q [B n][H 64] and the K slabs k_slab [H][slab_rows][64] (rounded to bf16 on upload when bf16 != 0), sequence b at slab rows

@@ -91,6 +91,39 @@ def nar_options(a):
             "lm_file": lm_file, "lm_weight": 0.5 if weight is None else weight, "length_bonus": 0.0 if bonus is None else bonus}
 
 
+def decoder_lm_options(a):
+    """The --decoder-lm* flags of the autoregressive families: None when none is given, else dict(lm_file, lm_weight, length_bonus, lm_topk) as
+    WhisperTranscriber / QwenAsrTranscriber take them (lm_file still a path)."""
+    lm_file, weight = getattr(a, "decoder_lm", None), getattr(a, "decoder_lm_weight", None)
+    bonus, topk = getattr(a, "decoder_length_bonus", None), getattr(a, "decoder_lm_topk", None)
+    if not lm_file and weight is None and bonus is None and topk is None:
+        return None
+    if a.family not in ("whisper", "qwen_asr"):
+        raise SystemExit("--decoder-lm / --decoder-lm-weight / --decoder-length-bonus / --decoder-lm-topk exist for --family whisper and --family qwen_asr only "
+                         "(SenseVoice: --lm, Paraformer: --nar-lm)")
+    if not lm_file:
+        raise SystemExit("--decoder-lm-weight / --decoder-length-bonus / --decoder-lm-topk need --decoder-lm FILE.arpa")
+    if not os.path.isfile(lm_file):
+        raise SystemExit("--decoder-lm %s: no such file" % lm_file)
+    topk = 16 if topk is None else topk
+    if not 1 <= topk <= 32 or topk < a.beam:
+        raise SystemExit("--decoder-lm-topk 1..32 and at least --beam (got --decoder-lm-topk %d --beam %d)" % (topk, a.beam))
+    return {"lm_file": lm_file, "lm_weight": 0.5 if weight is None else weight, "length_bonus": 0.0 if bonus is None else bonus, "lm_topk": topk}
+
+
+def load_decoder_lm(opts, tok):
+    """The transcribers' lm keywords from decoder_lm_options: ARPA words are token ids, or tokens of the tokenizer's vocabulary when one is loaded."""
+    if not opts:
+        return {}
+    NgramLM = _m("lm").NgramLM
+    if tok is None:
+        lm = NgramLM.from_arpa(opts["lm_file"])
+    else:
+        vocab = tok.get_vocab()
+        lm = NgramLM.from_arpa(opts["lm_file"], token_to_id=lambda piece: vocab.get(piece))
+    return {"lm": lm, "lm_weight": opts["lm_weight"], "length_bonus": opts["length_bonus"], "lm_topk": opts["lm_topk"]}
+
+
 def run(a) -> dict:
     shim, eng, audio_io, cfgm = _m("ort_shim"), _m("engine"), _m("audio_io"), _m("config")
     prec = 1 if a.precision == "f32" else 0
@@ -126,6 +159,7 @@ def run(a) -> dict:
     dec_hot = parse_hotword_file(dec_hot_file) if dec_hot_file else None
     if dec_hot and any(isinstance(p, str) for p in dec_hot) and not a.tokenizer:
         raise SystemExit("--decoder-hotwords: text phrases need --tokenizer (or give token ids)")
+    dec_lm = decoder_lm_options(a)
     bundle = {"sensevoice": "SenseVoiceSmall", "paraformer": "Paraformer", "whisper": "Whisper", "qwen_asr": "Qwen_ASR"}[a.family]
     if not any(os.path.isfile(os.path.join(a.model, bundle + ext)) for ext in (".asrmodel", ".onnx")):
         raise SystemExit("--model %s holds no %s.asrmodel: it is not a --family %s folder" % (a.model, bundle, a.family))
@@ -193,7 +227,7 @@ def run(a) -> dict:
                                               token_scores=scores, temperature_fallback=fallback, hotwords=dec_hot, hotword_boost=dec_hot_boost,
                                               hotword_encoder=(lambda t: tok.encode(t, add_special_tokens=False)) if tok is not None else None,
                                               initial_prompt=parse_prompt_ids_file(a.initial_prompt_ids) if getattr(a, "initial_prompt_ids", None) else None,
-                                              condition_on_previous_text=bool(getattr(a, "condition_on_previous_text", False)))
+                                              condition_on_previous_text=bool(getattr(a, "condition_on_previous_text", False)), **load_decoder_lm(dec_lm, tok))
         lang_id = None
         if a.language != "auto":
             if tok is None:
@@ -239,7 +273,7 @@ def run(a) -> dict:
             from transformers import AutoTokenizer
             tok = AutoTokenizer.from_pretrained(a.tokenizer)
         tr = _m("qwen_asr").QwenAsrTranscriber(cfg, sess, info["metadata"], tokenizer=tok, repeat_penalty=a.repeat_penalty, beam_size=a.beam,
-                                               token_scores=scores, hotwords=dec_hot, hotword_boost=dec_hot_boost)
+                                               token_scores=scores, hotwords=dec_hot, hotword_boost=dec_hot_boost, **load_decoder_lm(dec_lm, tok))
         for p in a.wav:
             pcm = audio_io.read_wav_int16(p, cfg.sample_rate, exact_width=a.strict_wav)
             out, stat = tr.transcribe([pcm], language_prompts=("" if a.language == "auto" else a.language,))
@@ -334,6 +368,11 @@ def build_parser():
     r.add_argument("--decoder-hotwords", metavar="FILE", help="Whisper, Qwen3-ASR: phrases the decoder favours (greedy, sampling and --beam alike), one per line: "
                         "token ids, or text with --tokenizer (boosted in both spellings, at the start of the text and inside it)")
     r.add_argument("--decoder-hotword-boost", type=float, default=2.0, help="Whisper, Qwen3-ASR: logit / log-probability bonus per matched hotword token")
+    r.add_argument("--decoder-lm", metavar="FILE.arpa", help="Whisper, Qwen3-ASR: back-off n-gram language model (ARPA; words are token ids, or tokens of the "
+                   "vocabulary with --tokenizer) fused into the selection head and --beam (shallow fusion over the best --decoder-lm-topk columns)")
+    r.add_argument("--decoder-lm-weight", type=float, default=None, metavar="X", help="Whisper, Qwen3-ASR: weight of the model's log-probability (default 0.5)")
+    r.add_argument("--decoder-length-bonus", type=float, default=None, metavar="Y", help="Whisper, Qwen3-ASR: bonus per token with --decoder-lm (default 0)")
+    r.add_argument("--decoder-lm-topk", type=int, default=None, metavar="M", help="Whisper, Qwen3-ASR: candidate columns per step, 1..32 and at least --beam (default 16)")
     r.add_argument("--timestamps", action="store_true", help="SenseVoice: add each token's start / end (seconds) and mean frame log-probability to the dump; Paraformer: each token's start / end from its CIF fire row and its log-probability; Whisper: decode with timestamp tokens and add "
                         "segments (start / end in seconds, token ids, text with --tokenizer)")
     r.add_argument("--word-timestamps", action="store_true", help="Whisper: add each text token's start / end in seconds (cross-attention DTW on the bundle's "
