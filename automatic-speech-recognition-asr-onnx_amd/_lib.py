@@ -130,6 +130,8 @@ SIGNATURES = {
     "asr_session_device": (_i, [_vp, C.POINTER(C.c_int)]),
     "asr_session_set_audio_dtype": (_i, [_vp, _i]),
     "asr_session_audio_dtype": (_i, [_vp, C.POINTER(C.c_int)]),
+    "asr_session_set_input_format": (_i, [_vp, _i, _i]),
+    "asr_session_input_format": (_i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "asr_session_profile_enable": (_i, [_vp, _i]),
     "asr_session_profile_reset": (_i, [_vp]),
     "asr_session_profile_read": (_i, [_vp, _i, C.c_char_p, _dp, _lp, C.POINTER(C.c_int)]),
@@ -153,6 +155,8 @@ SIGNATURES = {
                                     _i, _i, _i, _ip, _i, _ip, _fp, _i, _ip, _ip, _fp, _ip, _fp, _fp, _ip]),
     "asr_op_ctc_align": (_i, [_fp, _i, _ip, _i, _i, _ip, _ip, _ip, _ip, _fp, _i, _fp, _fp, _ip]),
     "asr_op_cif_scan_timed": (_i, [_fp, _fp, _i, _ip, _i, C.c_float, _fp, _ip, _i, _ip]),
+    "asr_op_resample": (_i, [_vp, _lp, _i, _i, _i, _i, _i, _i, _fp, C.c_int64, _lp]),
+    "asr_resample_table": (_i, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _fp]),
 }
 
 

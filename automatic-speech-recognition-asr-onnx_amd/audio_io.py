@@ -9,23 +9,46 @@ its graphs -- without pydub / ffmpeg (neither ships here). Other sample widths a
 reference: it casts pydub's sample array straight to int16 (no rescale of 24- / 32-bit data), whereas this module rescales with
 `audioop.lin2lin`; the parity harness (tools/transcribe.py compare) therefore takes 16-bit wav only (`exact_width=True`).
 Compressed inputs (.mp3 ...) are out of scope: convert them to .wav first.
+
+`read_wav_native` is the other way in, the build's own: the file's frames as they are -- interleaved int16 at the file's rate and channel count --
+for a session that resamples on the device (`set_input_format`). It converts nothing and, for 16-bit PCM, needs no `audioop`.
 """
 from __future__ import annotations
 
 import wave
 
-try:
-    import audioop                                   # standard library up to Python 3.12
-except ImportError as e:                             # removed in 3.13 (PEP 594)
-    raise ImportError("audio_io needs the standard-library `audioop` module (Python <= 3.12); on newer interpreters install the "
-                      "`audioop-lts` backport or convert audio to 16 kHz mono int16 yourself and pass arrays") from e
-
 import numpy as np
+
+
+def _audioop():
+    try:
+        import audioop                               # standard library up to Python 3.12
+    except ImportError as e:                         # removed in 3.13 (PEP 594)
+        raise ImportError("this conversion needs the standard-library `audioop` module (Python <= 3.12); on newer interpreters install the "
+                          "`audioop-lts` backport, or read 16-bit wav with read_wav_native and let the session resample (set_input_format)") from e
+    return audioop
+
+
+def read_wav_native(path: str) -> tuple[np.ndarray, int, int]:
+    """(int16 frames [n, channels], sample rate, channels) of a PCM wav as the file holds them: no down-mix, no rate conversion. 16-bit files are
+    read as they are; other widths are rescaled to 16 bits with `audioop.lin2lin` (8-bit: biased to signed first), as read_wav_int16 does."""
+    with wave.open(path, "rb") as w:
+        n_ch, width, rate, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+        if w.getcomptype() != "NONE":
+            raise ValueError(f"{path}: compressed wav ({w.getcomptype()}) is not supported")
+        data = w.readframes(n)
+    if width != 2:
+        audioop = _audioop()
+        if width == 1:
+            data = audioop.bias(data, 1, -128)
+        data = audioop.lin2lin(data, width, 2)
+    return np.frombuffer(data, dtype="<i2").astype(np.int16).reshape(-1, n_ch), int(rate), int(n_ch)
 
 
 def read_wav_int16(path: str, sample_rate: int = 16000, exact_width: bool = False) -> np.ndarray:
     """Mono int16 samples at `sample_rate`. PCM wav of any width / channel count / rate; `exact_width` rejects everything but 16-bit
     input (the only width for which the samples equal the reference's)."""
+    audioop = _audioop()
     with wave.open(path, "rb") as w:
         n_ch, width, rate, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
         if w.getcomptype() != "NONE":

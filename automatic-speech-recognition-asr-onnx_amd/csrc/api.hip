@@ -91,6 +91,27 @@ extern "C" int asr_session_audio_dtype(asr_session* s, int* audio_dtype_out) {
   });
 }
 
+// The input format is read where an audio entry stages its audio (stage_input), in front of everything a step graph captures, so it may change between any
+// two compute calls. A refused format leaves the one in force.
+extern "C" int asr_session_set_input_format(asr_session* s, int sample_rate, int channels) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s, "set_input_format: null session");
+    ASR_REQUIRE(channels >= 1 && channels <= 8, "input format: %d channels (1..8)", channels);
+    (void)resample_design(sample_rate, s->model_rate);   // the rate checks; the table itself is built by the first call that uses it
+    const bool off = sample_rate == s->model_rate && channels == 1;
+    s->in_rate = off ? 0 : sample_rate;
+    s->in_channels = channels;
+  });
+}
+
+extern "C" int asr_session_input_format(asr_session* s, int* sample_rate_out, int* channels_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && sample_rate_out && channels_out, "input_format: null argument");
+    *sample_rate_out = s->in_rate ? s->in_rate : s->model_rate;
+    *channels_out = s->in_channels;
+  });
+}
+
 extern "C" int asr_session_profile_enable(asr_session* s, int enable) {
   return asr_guard([&] {
     ASR_REQUIRE(s, "profile_enable: null session");
@@ -875,6 +896,37 @@ extern "C" int asr_op_gemm_ln(const float* x, const float* w, const float* bias,
     launch_gemm_bf16(g, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out, dout, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+extern "C" int asr_resample_table(int rate_in, int rate_model, int* L, int* M, int* W, float* coeffs) {
+  return asr_guard([&] {
+    ASR_REQUIRE(L && M && W, "resample_table: null argument");
+    const ResampleDesign d = resample_design(rate_in, rate_model);
+    *L = d.L; *M = d.M; *W = d.W;
+    if (coeffs) resample_table(d, coeffs);
+  });
+}
+
+extern "C" int asr_op_resample(const void* audio, const int64_t* offsets, int batch, int audio_dtype, int rate_in, int rate_model, int channels, int int16_scale,
+                               float* out, int64_t out_cap, int64_t* offsets_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(audio && offsets && out && offsets_out && batch > 0, "op_resample: bad argument");
+    ASR_REQUIRE(audio_dtype == ASR_AUDIO_F32 || audio_dtype == ASR_AUDIO_I16 || audio_dtype == ASR_AUDIO_F16, "op_resample: unknown audio dtype %d", audio_dtype);
+    const ResampleDesign d = resample_design(rate_in, rate_model);
+    int64_t total = 0;
+    for (int b = 0; b < batch; ++b) {
+      ASR_REQUIRE(offsets[b + 1] >= offsets[b], "op_resample: offsets decrease at utterance %d", b);
+      total += resample_n_out(offsets[b + 1] - offsets[b], d);
+    }
+    ASR_REQUIRE(out_cap >= total, "op_resample: out holds %lld samples, the batch has %lld at the model rate", (long long)out_cap, (long long)total);
+    asr_require_device(0);
+    Resampler rs;                                        // (the session path's launcher on its own buffers, on the null stream)
+    const float scale = audio_dtype == ASR_AUDIO_I16 && int16_scale ? 0x1p-15f : 1.0f;
+    const float* dout = rs.run(audio, ASR_MEM_HOST, audio_dtype, rate_in, rate_model, channels, scale, offsets, batch, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (total) HIP_CHECK(hipMemcpy(out, dout, (size_t)total * 4, hipMemcpyDeviceToHost));
+    memcpy(offsets_out, rs.offs.data(), (size_t)(batch + 1) * 8);
   });
 }
 

@@ -193,6 +193,20 @@ struct Tap {
   int elt = 4;
 };
 
+// The device resampler of a session (or of asr_op_resample): the coefficient tables it has built, one per (rate_in, rate_model), and the buffers of a call.
+// run() leaves model-rate mono f32 in d_out and the utterances' new offsets (from 0) in `offs`.
+struct Resampler {
+  struct Table { ResampleDesign d; DeviceBuffer tab_t; };
+  std::map<std::pair<int, int>, Table> tables;
+  DeviceBuffer d_in, d_out, d_plan;
+  PinnedBuffer h_plan;
+  std::vector<int64_t> offs;
+  const Table& table(int rate_in, int rate_model, hipStream_t s);
+  // audio / offsets_in in input frames of `channels` interleaved samples of audio_dtype; host audio is copied into d_in, device audio is read in place
+  const float* run(const void* audio, int audio_mem, int audio_dtype, int rate_in, int rate_model, int channels, float scale, const int64_t* offsets_in, int batch,
+                   hipStream_t s);
+};
+
 struct asr_session {
   int kind = 0;               // 1 = sensevoice, 2 = whisper
   int device = 0;
@@ -200,6 +214,11 @@ struct asr_session {
   int precision = 0;
   int audio_dtype = 0;        // asr_audio_dtype: the sample type every audio entry of this session reads its `audio` pointer as (asr_session_set_audio_dtype)
   size_t audio_elt() const { return audio_dtype == 0 ? 4 : 2; }
+  // asr_session_set_input_format: in_rate == 0 is the default format (model-rate mono: nothing is launched in front of the front end); otherwise every audio
+  // entry's audio and offsets count frames of in_channels interleaved samples at in_rate Hz, and stage_input resamples them on the device
+  int model_rate = 16000;     // the family's sample_rate, set by its constructor
+  int in_rate = 0, in_channels = 1;
+  Resampler resampler;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   Arena arena;
@@ -225,9 +244,18 @@ struct FrontEnd {
 };
 void fill_fbank_blocks(const UttPlan* plan, int B, int32_t* blk_utt, int32_t* blk_f0);                    // one entry per 64 frames
 void fill_query_blocks(const UttPlan* plan, int n, int q_rows, int32_t* qb_utt, int32_t* qb_q0);         // one entry per q_rows of every plan's T
-// samples [first_sample, first_sample + n_samples) of `audio` where the kernels can read them: host audio is copied into d_audio (grow-only; *moved
+// What a call plans its front end from: packed model-rate mono samples of `dtype`, and the utterances' offsets into them.
+struct AudioIn {
+  const void* audio; int mem; const int64_t* offs; int dtype;
+  bool resampled;             // the samples are the session's resampler output (device f32), not the caller's
+};
+// The first thing an audio entry does with its arguments. Default input format: they come back as they are (the session's audio_dtype) and nothing is launched.
+// Otherwise the frames are resampled on the session's stream (profiler class "resample") and the result is the f32 buffer with offsets from 0, which the session
+// owns until its next call; int16_unit_scale: the front end behind is the Whisper / Qwen one, so int16 PCM takes its 2^-15 here (Pcm<int16_t>::widen).
+AudioIn stage_input(asr_session& s, bool int16_unit_scale, const void* audio, int audio_mem, const int64_t* offs, int batch);
+// samples [first_sample, first_sample + n_samples) of `in` where the kernels can read them: host audio is copied into d_audio (grow-only; *moved
 // reports a re-allocation), device audio is used in place
-const void* stage_audio(asr_session& s, DeviceBuffer& d_audio, const void* audio, int audio_mem, int64_t first_sample, int64_t n_samples, bool* moved = nullptr);
+const void* stage_audio(asr_session& s, DeviceBuffer& d_audio, const AudioIn& in, int64_t first_sample, int64_t n_samples, bool* moved = nullptr);
 
 // The split-K workspace (16 MiB) and tickets of the skinny / decode GEMMs. Per session (sessions may run concurrently), allocated at the first use.
 struct SplitKGemm {

@@ -294,8 +294,82 @@ void fill_query_blocks(const UttPlan* plan, int n, int q_rows, int32_t* qb_utt, 
     for (int q0 = 0; q0 < plan[u].T; q0 += q_rows) { qb_utt[i] = u; qb_q0[i++] = q0; }
 }
 
-const void* stage_audio(asr_session& s, DeviceBuffer& d_audio, const void* audio, int audio_mem, int64_t first_sample, int64_t n_samples, bool* moved) {
-  const size_t eA = s.audio_elt();                       // the session's sample type: offsets are samples, bytes step in eA
+const Resampler::Table& Resampler::table(int rate_in, int rate_model, hipStream_t s) {
+  auto it = tables.find({rate_in, rate_model});
+  if (it != tables.end()) return it->second;
+  const ResampleDesign d = resample_design(rate_in, rate_model);
+  std::vector<float> c((size_t)d.L * d.T), ct(c.size());
+  resample_table(d, c.data());
+  for (int p = 0; p < d.L; ++p)
+    for (int k = 0; k < d.T; ++k) ct[(size_t)k * d.L + p] = c[(size_t)p * d.T + k];
+  Table& t = tables[{rate_in, rate_model}];
+  t.d = d;
+  t.tab_t.reserve(ct.size() * 4, s);
+  HIP_CHECK(hipMemcpyAsync(t.tab_t.ptr, ct.data(), ct.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));                    // (ct is a local; once per format)
+  return t;
+}
+
+const float* Resampler::run(const void* audio, int audio_mem, int audio_dtype, int rate_in, int rate_model, int channels, float scale, const int64_t* offsets_in,
+                            int batch, hipStream_t s) {
+  ASR_REQUIRE(audio && offsets_in && batch >= 1, "resample: null argument");
+  ASR_REQUIRE(channels >= 1 && channels <= 8, "input format: %d channels (1..8)", channels);
+  const Table& tb = table(rate_in, rate_model, s);
+  const ResampleDesign& d = tb.d;
+  // ---- host plan: per utterance its frames and its n_out = ceil(n_in L / M) outputs; one (utterance, first output) entry per tile
+  offs.assign((size_t)batch + 1, 0);
+  int64_t n_tiles = 0;
+  for (int b = 0; b < batch; ++b) {
+    const int64_t n_in = offsets_in[b + 1] - offsets_in[b];
+    ASR_REQUIRE(n_in >= 0 && n_in <= INT32_MAX, "resample: utterance %d has %lld frames", b, (long long)n_in);
+    const int64_t n_out = resample_n_out(n_in, d);
+    ASR_REQUIRE(n_out <= INT32_MAX, "resample: utterance %d has %lld samples at the model rate", b, (long long)n_out);
+    offs[b + 1] = offs[b] + n_out;
+    n_tiles += (n_out + d.tile - 1) / d.tile;
+  }
+  ASR_REQUIRE(n_tiles <= INT32_MAX, "resample: %lld tiles", (long long)n_tiles);
+  PlanBlob pb(h_plan, d_plan);
+  const auto s_utt = pb.add<RsUtt>(batch);
+  const auto s_tile_utt = pb.add<int32_t>(std::max<int64_t>(n_tiles, 1)), s_tile_n0 = pb.add<int32_t>(std::max<int64_t>(n_tiles, 1));
+  pb.commit(s);
+  RsUtt* hu = pb.host(s_utt);
+  int32_t *tile_utt = pb.host(s_tile_utt), *tile_n0 = pb.host(s_tile_n0);
+  const int64_t base0 = offsets_in[0];
+  for (int b = 0, i = 0; b < batch; ++b) {
+    hu[b].in_off = offsets_in[b] - base0; hu[b].out_off = offs[b];
+    hu[b].n_in = (int32_t)(offsets_in[b + 1] - offsets_in[b]); hu[b].n_out = (int32_t)(offs[b + 1] - offs[b]);
+    for (int n0 = 0; n0 < hu[b].n_out; n0 += d.tile) { tile_utt[i] = b; tile_n0[i++] = n0; }
+  }
+  pb.upload(s);
+  // ---- the frames where the kernel can read them, the output buffer, the launch
+  const size_t frame_bytes = (size_t)channels * audio_elt_bytes(audio_dtype), in_bytes = (size_t)(offsets_in[batch] - base0) * frame_bytes;
+  const void* src = static_cast<const unsigned char*>(audio) + (size_t)base0 * frame_bytes;
+  if (audio_mem == ASR_MEM_HOST) {
+    d_in.reserve(std::max<size_t>(in_bytes, 16), s);
+    if (in_bytes) HIP_CHECK(hipMemcpyAsync(d_in.ptr, src, in_bytes, hipMemcpyHostToDevice, s));
+    src = d_in.ptr;
+  }
+  d_out.reserve(std::max<size_t>((size_t)offs[batch] * 4, 16), s);
+  ResampleArgs a;
+  a.audio = src; a.utt = pb.dev(s_utt); a.tile_utt = pb.dev(s_tile_utt); a.tile_n0 = pb.dev(s_tile_n0); a.tab_t = tb.tab_t.as<float>(); a.out = d_out.as<float>();
+  a.d = d; a.channels = channels; a.scale = scale; a.audio_dtype = audio_dtype;
+  launch_resample(a, (int)n_tiles, s);
+  return d_out.as<float>();
+}
+
+AudioIn stage_input(asr_session& s, bool int16_unit_scale, const void* audio, int audio_mem, const int64_t* offs, int batch) {
+  if (!s.in_rate) return AudioIn{audio, audio_mem, offs, s.audio_dtype, false};
+  ProfScope ps(s.prof, "resample", s.stream);
+  const float scale = s.audio_dtype == AUDIO_I16 && int16_unit_scale ? 0x1p-15f : 1.0f;
+  const float* out = s.resampler.run(audio, audio_mem, s.audio_dtype, s.in_rate, s.model_rate, s.in_channels, scale, offs, batch, s.stream);
+  if (s.resampler.offs[batch] > 0) s.save_tap("resampled", out, 1, s.resampler.offs[batch], s.resampler.offs[batch], 4);
+  return AudioIn{out, ASR_MEM_DEVICE, s.resampler.offs.data(), AUDIO_F32, true};
+}
+
+const void* stage_audio(asr_session& s, DeviceBuffer& d_audio, const AudioIn& in, int64_t first_sample, int64_t n_samples, bool* moved) {
+  const size_t eA = audio_elt_bytes(in.dtype);           // the sample type of the call: offsets are samples, bytes step in eA
+  const void* audio = in.audio;
+  const int audio_mem = in.mem;
   const void* src = static_cast<const unsigned char*>(audio) + (size_t)first_sample * eA;
   void* before = d_audio.ptr;
   if (audio_mem == ASR_MEM_HOST) {

@@ -56,6 +56,40 @@ void launch_fbank(const FbankArgs& a, int n_blocks, hipStream_t s);
 size_t fbank_split_table_bytes(int n_bin_tiles, int win);
 void launch_fbank_split_table(const float* dft_packed, int n_bin_tiles, int n_kchunks16, void* out, hipStream_t s);
 
+// ---- resampler (resample.hip): packed frames of any rate and channel count -> model-rate mono f32, in front of the fbank launch.
+// A polyphase Kaiser-windowed sinc (beta 9, 32 zero crossings a side, cutoff 0.945 of the narrower Nyquist). With g = gcd(rate_in, rate_model), L = rate_model / g,
+// M = rate_in / g, fc = 0.945 min(1, L / M), W = ceil(32 / fc), T = 2 W + 1:   c[p][k] = fc sinc(t) I0(9 sqrt(1 - (t / 32)^2)) / I0(9),  t = ((k - W) - p / L) fc
+// (0 at |t| >= 32), and output n of an utterance of n_in frames (n_out = ceil(n_in L / M)) is   sum_k c[(n M) mod L][k] x[floor(n M / L) - W + k]   with x zero
+// outside the utterance and, for C interleaved channels, x[i] = (x[i][0] + ... + x[i][C - 1]) (1 / C) in f32 after Pcm<S>::widen. rate_in == rate_model is the pure
+// down-mix L = M = T = 1, W = 0.
+struct ResampleDesign {
+  int L, M, W, T;
+  int tile;                    // outputs per workgroup (1024, 512 or 256: the largest whose input span fits the LDS budget)
+  int span_max;                // LDS floats of a tile: ((L - 1) + (tile - 1) M) / L + T
+};
+// INVALID (with a message) for a rate < 1, L > 1024, or a ratio whose smallest tile does not fit in LDS (rate_in beyond ~40 x rate_model)
+ResampleDesign resample_design(int rate_in, int rate_model);
+void resample_table(const ResampleDesign& d, float* coeffs);                        // [L][T], computed in double and rounded once
+inline int64_t resample_n_out(int64_t n_in, const ResampleDesign& d) { return (n_in * d.L + d.M - 1) / d.M; }
+struct RsUtt {
+  int64_t in_off;              // first input frame in the packed buffer (a frame = `channels` interleaved samples)
+  int64_t out_off;             // first output sample in the packed f32 buffer
+  int32_t n_in, n_out;
+};
+struct ResampleArgs {
+  const void* audio;           // packed interleaved samples of type audio_dtype
+  const RsUtt* utt;
+  const int32_t* tile_utt;     // per workgroup: utterance
+  const int32_t* tile_n0;      // per workgroup: first output sample (multiple of d.tile)
+  const float* tab_t;          // the coefficients TRANSPOSED, [T][L]: at tap k the lanes of a wave read one row of L floats, whatever their phases
+  float* out;
+  ResampleDesign d;
+  int channels;
+  float scale;                 // int16 only: 2^-15 where the front end behind is the Whisper / Qwen one (Pcm<int16_t>::widen), else 1
+  int audio_dtype = AUDIO_F32;
+};
+void launch_resample(const ResampleArgs& a, int n_tiles, hipStream_t s);
+
 // ---- Whisper log-mel finish (Export_Whisper.py:425-427): max(x, utterance_max - 8), (x + 4) / 4, written in the
 // GAPPED time-major layout the conv stem reads: utterance b owns rows [2*row_off_b, 2*row_off_b + 2*rows_b); row
 // 2*row_off_b is the conv's left zero pad, frame f sits at row 2*row_off_b + 1 + f, everything else is zero.

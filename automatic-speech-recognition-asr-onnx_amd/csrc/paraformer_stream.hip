@@ -249,6 +249,7 @@ void SvSession::stream_step(const SvStepReq& q) {
   const bool beam = q.form == SvForm::STREAM_BEAM;      // the timed step, then (behind its validation, below) the candidates and the search
   const bool timed = q.form == SvForm::TIMED || beam;
   ASR_REQUIRE(st_max > 0, "streaming: session was not created with asr_paraformer_stream_create");
+  ASR_REQUIRE(!in_rate, "input format: streaming sessions take model-rate mono");      // (a streaming filter needs per-stream history and a fixed delay: another contract)
   ASR_REQUIRE(!beam || (sb_beam > 0 && q.beam_out.complete()), "streaming: the beam step needs the mode on (asr_paraformer_stream_set_beam) and all of its outputs");
   ASR_REQUIRE(q.audio && stream_ids && q.tok_out && q.num_out && n >= 1 && n <= st_max && max_tokens >= st_B + 1, "streaming: bad argument (n = %d)", n);
   ASR_REQUIRE(!timed || (q.fire_out && q.logprob_out), "streaming: the timed step needs both of its outputs");
@@ -279,7 +280,7 @@ void SvSession::stream_step(const SvStepReq& q) {
   for (int t = rows; t < Mpad; ++t) row_utt[t] = -1;
   const size_t eT = sizeof(T);
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { buf.reserve(bytes, stream); };
-  const void* d_aud = stage_audio(*this, d_audio, q.audio, q.audio_mem, 0, (int64_t)n * st_chunk);
+  const void* d_aud = stage_audio(*this, d_audio, AudioIn{q.audio, q.audio_mem, nullptr, audio_dtype, false}, 0, (int64_t)n * st_chunk);
   grow(d_mel, (size_t)frames * c.n_mels * 4);
   grow(d_x0, (size_t)Mpad * kpad0 * 4);
   grow(d_xa, (size_t)Mpad * d * 4);

@@ -730,6 +730,7 @@ void QwSession::init() {
   hpad = aligner() ? round_up(c.classify_num, 128) : vpad;   // rows of dec.lm_head: the vocabulary, or the aligner's timestamp buckets
   cpad = round_up(c.conv_channels, 128);
   fe.init(c.nfft, c.nfft, c.hop_length, c.n_mels, 1, 1e-10f);
+  model_rate = c.sample_rate;
   const int wt = precision == ASR_PRECISION_BF16 ? ARENA_BF16 : ARENA_F32;
   const int de = c.enc_d, d = c.d_model, qkvn = (c.n_heads + 2 * c.n_kv_heads) * c.d_head;
   auto F = [&](const std::string& n, std::initializer_list<int64_t> sh) { return (const float*)arena.get(n, ARENA_F32, sh).ptr; };
@@ -1022,12 +1023,14 @@ DecPass QwSession::step_plan(DeviceBuffer& dev, int rows) {
 }
 
 template <typename T>
-void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
+void QwSession::prefill(const void* audio, int audio_mem, const int64_t* audio_offs, int B, const int32_t* pre_ids, const int32_t* pre_off,
                         const int32_t* post_ids, const int32_t* post_off, int32_t* next_out, float* logits_out, int32_t* ids_len_out,
                         const AlignReq* al) {
   const auto& c = cfg;
-  ASR_REQUIRE(audio && offs && B >= 1 && pre_off && post_off, "qwen_prefill: bad argument");
+  ASR_REQUIRE(audio && audio_offs && B >= 1 && pre_off && post_off, "qwen_prefill: bad argument");
   HIP_CHECK(hipSetDevice(device));
+  const AudioIn in = stage_input(*this, true, audio, audio_mem, audio_offs, B);     // default input format: the caller's own; else model-rate f32 and its offsets
+  const int64_t* const offs = in.offs;
   const int de = c.enc_d, d = c.d_model, H = c.enc_heads, dff = c.enc_ffn;
   const size_t eT = sizeof(T);
   // ---- host plan: per utterance frames / chunk slots / windows; per window an attention unit
@@ -1136,7 +1139,7 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
   const int32_t *d_slot_utt = pb.dev(s_slot_utt), *d_slot_local = pb.dev(s_slot_local), *d_pos_rows = pb.dev(s_pos_rows), *d_src = pb.dev(s_src);
   const int32_t *d_row_seq = pb.dev(s_row_seq), *d_row_t = pb.dev(s_row_t), *d_last_rows = pb.dev(s_last), *d_dqb_utt = pb.dev(s_dqb_utt), *d_dqb_q0 = pb.dev(s_dqb_q0);
 
-  const void* d_aud = stage_audio(*this, d_audio, audio, audio_mem, base0, offs[B] - base0);
+  const void* d_aud = stage_audio(*this, d_audio, in, base0, offs[B] - base0);
   // ---- front-end + conv stem
   const size_t r1 = (size_t)slots * 50 * 64, r2 = (size_t)slots * 25 * 32, r3 = (size_t)wins * rpw * 16;
   d_mel.reserve((size_t)frames * c.n_mels * 4, stream);
@@ -1156,7 +1159,7 @@ void QwSession::prefill(const void* audio, int audio_mem, const int64_t* offs, i
   d_aud_out.reserve((size_t)Me * d * 4, stream);
   {
     ProfScope ps(prof, "logmel", stream);
-    const FbankArgs fa = fe.args(d_aud, audio_dtype, dup, d_blk_utt, d_blk_f0, d_mel.as<float>(), d_blkmax.as<float>());
+    const FbankArgs fa = fe.args(d_aud, in.dtype, dup, d_blk_utt, d_blk_f0, d_mel.as<float>(), d_blkmax.as<float>());
     launch_fbank(fa, n_fb, stream);
     if (taps_enabled) save_tap("mel", d_mel.ptr, frames, c.n_mels, c.n_mels, 4);       // log10 mel before the per-utterance clamp: what the front end made of the samples
     hipLaunchKernelGGL(qw_mel_finish_kernel<T>, dim3(slots * chunk), dim3(128), 0, stream, d_mel.as<float>(), d_blkmax.as<float>(), dup, d_slot_utt,

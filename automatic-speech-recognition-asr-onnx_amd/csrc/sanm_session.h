@@ -63,7 +63,8 @@ struct SvStepReq {              // streaming: asr_paraformer_stream_step / _step
 // Everything a forward pass needs once the host plan is uploaded; captured into a hipGraph for replay.
 struct SvRunCtx {
   int batch, rows, Mpad, frames, n_fb, n_qb, max_T, max_tokens, att_qt, att_nw;
-  const void* d_aud;          // packed samples of the session's audio_dtype
+  const void* d_aud;          // packed samples of audio_dtype: the session's, or f32 behind the resampler
+  int audio_dtype;
   const UttPlan* dp;
   const int32_t *d_blk_utt, *d_blk_f0, *d_qb_utt, *d_qb_q0, *d_row_utt;
   const int32_t *d_tile_win = nullptr, *d_tile_idx = nullptr;    // small batches (sanm_tiles.hip): per 16-row tile its window / its index inside the window

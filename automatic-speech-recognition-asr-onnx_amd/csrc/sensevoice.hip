@@ -21,6 +21,7 @@ void SvSession::init() {
   kpad0 = round_up(feat, 64);
   vpad = round_up(c.vocab, 128);
   fe.init(c.nfft, c.win_length, c.hop_length, c.n_mels, 0, 1.1920928955078125e-07f);
+  model_rate = c.sample_rate;
   const int n_frames_max = (c.max_audio_len - c.win_length) / c.hop_length + 1;
   max_lfr = (n_frames_max + c.lfr_n - 1) / c.lfr_n;
   const int wt = precision == ASR_PRECISION_BF16 ? ARENA_BF16 : ARENA_F32;
@@ -172,7 +173,7 @@ void SvSession::enqueue(const SvRunCtx& r) {
   // ---- 1. Kaldi fbank (Export_SenseVoice.py:275-278) ---------------------------------------
   {
     ProfScope ps(prof, "fbank", stream);
-    const FbankArgs fa = fe.args(r.d_aud, audio_dtype, r.dp, r.d_blk_utt, r.d_blk_f0, d_mel.as<float>(), nullptr);
+    const FbankArgs fa = fe.args(r.d_aud, r.audio_dtype, r.dp, r.d_blk_utt, r.d_blk_f0, d_mel.as<float>(), nullptr);
     launch_fbank(fa, r.n_fb, stream);
   }
   save_tap("mel", d_mel.ptr, r.frames, c.n_mels, c.n_mels, 4);
@@ -686,14 +687,17 @@ void SvSession::run(const SvRunReq& q) {
   const auto& c = cfg;
   validate(q);
   const bool timed = q.form == SvForm::TIMED, bq = q.form == SvForm::BEAM, al = q.form == SvForm::ALIGN;
-  const int64_t* const offs = q.offs;
   const int32_t* const lang = q.lang;
   const int batch = q.batch;
+  HIP_CHECK(hipSetDevice(device));
+  // a non-default input format is resampled here, in front of everything the step graphs capture: the plan below sees model-rate lengths, and a captured step
+  // reads the resampler's buffer (its address and the f32 type are in the key), so it is the same step whatever format filled that buffer
+  const AudioIn in = stage_input(*this, false, q.audio, q.audio_mem, q.offs, batch);
+  const int64_t* const offs = in.offs;
   int max_L = 0;
   if (al) for (int b = 0; b < batch; ++b) max_L = std::max(max_L, q.tgt_off[b + 1] - q.tgt_off[b]);
   const int max_tokens = al ? std::max(max_L, 1) : q.max_tokens;          // the align form's token sections are as wide as its longest transcript
   const int n_tgt = al ? q.tgt_off[batch] : 0, ld_em = round_up(max_L + 1, 4);
-  HIP_CHECK(hipSetDevice(device));
   // no cluster kernel beside a foreign (RCCL) section: this whole call -- it returns with the stream drained -- is one cluster pass, or takes the four-launch path
   ClusterScope cluster(device);
   foreign_now = !cluster.ok;
@@ -765,7 +769,8 @@ void SvSession::run(const SvRunReq& q) {
   if (out.commit()) ++ws_epoch;
   r.out = &out;
   bool audio_moved = false;
-  r.d_aud = stage_audio(*this, d_audio, q.audio, q.audio_mem, base0, offs[batch] - base0, &audio_moved);
+  r.d_aud = stage_audio(*this, d_audio, in, base0, offs[batch] - base0, &audio_moved);
+  r.audio_dtype = in.dtype;
   if (audio_moved) ++ws_epoch;
   grow(d_mel, (size_t)frames * c.n_mels * 4);
   grow(d_x0, (size_t)Mpad * kpad0 * 4);
@@ -830,7 +835,7 @@ void SvSession::run(const SvRunReq& q) {
   r.d_blk_utt = pb.dev(s_blk_utt); r.d_blk_f0 = pb.dev(s_blk_f0); r.d_qb_utt = pb.dev(s_qb_utt); r.d_qb_q0 = pb.dev(s_qb_q0);
   r.d_row_utt = pb.dev(s_row_utt); r.d_tile_win = pb.dev(s_tile_win); r.d_tile_idx = pb.dev(s_tile_idx);
   // (the result blob adds nothing to the key: its offsets are functions of batch, max_tokens, timed and nbest, all mixed in here; a moved h_out bumps ws_epoch)
-  key.mix((uint64_t)batch); key.mix((uint64_t)max_tokens); key.mix((uint64_t)(uintptr_t)r.d_aud); key.mix((uint64_t)audio_dtype); key.mix(ws_epoch); key.mix((uint64_t)(uintptr_t)stream);
+  key.mix((uint64_t)batch); key.mix((uint64_t)max_tokens); key.mix((uint64_t)(uintptr_t)r.d_aud); key.mix((uint64_t)in.dtype); key.mix((uint64_t)in.resampled); key.mix(ws_epoch); key.mix((uint64_t)(uintptr_t)stream);
   key.mix((uint64_t)(block_cooldown > 0 || foreign_now));        // a session cooling down after a cluster give-up replays the four-launch capture, not the block one
   key.mix((uint64_t)timed);                                      // the timed CTC tail is another launch sequence
   if (al) {                                                      // the align tail, per transcript length: ld_em, the trellis launch, where the plan blob's sections lie

@@ -156,6 +156,7 @@ void WhSession::init() {
   head.init(c.max_target_positions, 0, 20, 512);
   head.prof = &prof; ranker.prof = &prof;
   fe.init(c.nfft, c.nfft, c.hop_length, c.n_mels, 1, 1e-10f);
+  model_rate = c.sample_rate;
   act = c.gelu_tanh ? ACT_GELU_TANH : ACT_GELU_ERF;
   const int wt = precision == ASR_PRECISION_BF16 ? ARENA_BF16 : ARENA_F32;
   const int d = c.d_model, dff = c.d_ffn, Ld = c.n_dec_layers;
@@ -228,10 +229,12 @@ void WhSession::init() {
 
 // ======================================================================================== encoder
 template <typename T>
-void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, int B, int32_t* n_pos_out) {
+void WhSession::encode(const void* audio, int audio_mem, const int64_t* audio_offs, int B, int32_t* n_pos_out) {
   const auto& c = cfg;
-  ASR_REQUIRE(B > 0 && audio && offs, "whisper_encode: bad argument");
+  ASR_REQUIRE(B > 0 && audio && audio_offs, "whisper_encode: bad argument");
   HIP_CHECK(hipSetDevice(device));
+  const AudioIn in = stage_input(*this, true, audio, audio_mem, audio_offs, B);     // default input format: the caller's own; else model-rate f32 and its offsets
+  const int64_t* const offs = in.offs;
   const int d = c.d_model, dff = c.d_ffn, Ld = c.n_dec_layers, H = c.n_heads;
   plan.assign(B, UttPlan{});
   std::vector<UttPlan> splan(B);                          // the conv stem's view: same utterances, row_off in the gapped layout's row space
@@ -288,7 +291,7 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, in
   const int32_t *d_row_utt = pb.dev(s_row_utt), *d_pos_rows = pb.dev(s_pos_rows), *d_grow_utt = pb.dev(s_grow_utt);
 
   const size_t eT = sizeof(T);
-  const void* d_aud = stage_audio(*this, d_audio, audio, audio_mem, base0, offs[B] - base0);
+  const void* d_aud = stage_audio(*this, d_audio, in, base0, offs[B] - base0);
   const int Rpad = R + 256;                                        // tile-edge + halo rows of the strided conv views
   d_mel.reserve((size_t)frames * c.n_mels * 4, stream);
   d_blkmax.reserve((size_t)n_fb * 4, stream);
@@ -307,7 +310,7 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* offs, in
   // ---- STFT power -> mel -> log10 (STFT_Process.py:224-246, Export_Whisper.py:424-425)
   {
     ProfScope ps(prof, "logmel", stream);
-    const FbankArgs fa = fe.args(d_aud, audio_dtype, dp, d_blk_utt, d_blk_f0, d_mel.as<float>(), d_blkmax.as<float>());
+    const FbankArgs fa = fe.args(d_aud, in.dtype, dp, d_blk_utt, d_blk_f0, d_mel.as<float>(), d_blkmax.as<float>());
     launch_fbank(fa, n_fb, stream);
     // per-utterance max clamp + (x+4)/4, written behind one leading zero row (the conv view of row j starts at j-1)
     T* x0 = d_x0.as<T>();

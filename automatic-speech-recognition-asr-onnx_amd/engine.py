@@ -65,6 +65,7 @@ class _Session:
         self._h = C.c_void_p(None)
         self._keep = None
         self._audio_np = np.dtype(np.float32)
+        self._format = None                       # (sample rate, channels) once set_input_format has been called
 
     @property
     def audio_dtype(self) -> np.dtype:
@@ -89,10 +90,38 @@ class _Session:
                             f"(convert it explicitly, or set audio_dtype)")
         return np.ascontiguousarray(a)
 
+    @property
+    def input_format(self) -> tuple[int, int]:
+        """(sample rate in Hz, interleaved channels) of the audio entries (asr_session_input_format); the default is (the model's rate, 1)."""
+        rate, ch = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.load().asr_session_input_format(self._h, C.byref(rate), C.byref(ch)))
+        return rate.value, ch.value
+
+    def set_input_format(self, sample_rate: int, channels: int = 1):
+        """Sample rate and interleaved channel count of the audio entries (asr_session_set_input_format). With anything but (the model's rate, 1) every
+        `audio` / `offsets` of this session counts frames of `channels` interleaved samples at `sample_rate`, a clip is [frames, channels] (or flat
+        interleaved), and the library resamples to model-rate mono on the device; frame counts and result frames refer to the resampled clip
+        (`model_lengths`). May be set between any two calls; a refused format raises AsrError and leaves the one in force."""
+        _lib.check(_lib.load().asr_session_set_input_format(self._h, int(sample_rate), int(channels)))
+        self._format = self.input_format
+
+    def model_lengths(self, frames) -> np.ndarray:
+        """Input frames per utterance -> samples at the model's rate: ceil(n * rate_model / rate_in), the resampler's own count."""
+        n = np.asarray(frames, dtype=np.int64)
+        rate, _ = self._format or (0, 1)
+        model = int(self.cfg.sample_rate)
+        if not rate or rate == model:
+            return n
+        g = int(np.gcd(rate, model))
+        return -((-n * (model // g)) // (rate // g))
+
     def _pack(self, audios):
+        ch = (self._format or (0, 1))[1]
         flat = [self._audio(a).reshape(-1) for a in audios]
+        if any(a.size % ch for a in flat):
+            raise ValueError(f"{type(self).__name__}: a clip's sample count is not a multiple of the {ch} interleaved channels of the input format")
         offs = np.zeros(len(flat) + 1, dtype=np.int64)
-        offs[1:] = np.cumsum([a.size for a in flat])
+        offs[1:] = np.cumsum([a.size // ch for a in flat])
         return flat, np.concatenate(flat), offs
 
     def close(self):
@@ -179,7 +208,7 @@ class SenseVoiceSession(_Session):
         lang = np.ascontiguousarray(language_idx, dtype=np.int32)
         B = lang.shape[0]
         assert offsets.shape[0] == B + 1
-        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        max_t = max(self.cfg.seq_len(int(n)) for n in self.model_lengths(np.diff(offsets))) if B else 1
         tok = np.zeros((B, max_t), dtype=np.int32)
         num = np.zeros((B,), dtype=np.int32)
         lib = _lib.load()
@@ -207,7 +236,7 @@ class SenseVoiceSession(_Session):
         lang = np.ascontiguousarray(language_idx, dtype=np.int32)
         B = lang.shape[0]
         assert offsets.shape[0] == B + 1
-        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        max_t = max(self.cfg.seq_len(int(n)) for n in self.model_lengths(np.diff(offsets))) if B else 1
         tok = np.zeros((B, max_t), dtype=np.int32)
         first, last = np.zeros((B, max_t), dtype=np.int32), np.zeros((B, max_t), dtype=np.int32)
         logprob = np.zeros((B, max_t), dtype=np.float32)
@@ -260,7 +289,7 @@ class SenseVoiceSession(_Session):
         B = lang.shape[0]
         assert offsets.shape[0] == B + 1
         topk = int(beam if topk is None else topk)
-        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        max_t = max(self.cfg.seq_len(int(n)) for n in self.model_lengths(np.diff(offsets))) if B else 1
         tok = np.zeros((B, nbest, max_t), dtype=np.int32)
         num = np.zeros((B, nbest), dtype=np.int32)
         score, ctc = np.zeros((B, nbest), dtype=np.float32), np.zeros((B, nbest), dtype=np.float32)
@@ -380,6 +409,36 @@ def op_fsmn(v, w, b, seq_lens, precision=PRECISION_F32):
     out = np.empty_like(v)
     _lib.check(_lib.load().asr_op_fsmn(precision, _fp(v), _fp(w), _fp(b), _ip(sl), sl.size, v.shape[1], w.shape[1], _fp(out)))
     return out
+
+
+def resample_table(sample_rate: int, model_rate: int = 16000):
+    """The resampler's filter (asr_resample_table) -> (L, M, W, coeffs [L, 2 W + 1] float32): output n reads input frames floor(n M / L) - W .. + W against
+    row (n M) mod L."""
+    L, M, W = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib = _lib.load()
+    _lib.check(lib.asr_resample_table(int(sample_rate), int(model_rate), C.byref(L), C.byref(M), C.byref(W), None))
+    coeffs = np.empty((L.value, 2 * W.value + 1), dtype=np.float32)
+    _lib.check(lib.asr_resample_table(int(sample_rate), int(model_rate), C.byref(L), C.byref(M), C.byref(W), _fp(coeffs)))
+    return L.value, M.value, W.value, coeffs
+
+
+def op_resample(audio, offsets, sample_rate: int, model_rate: int = 16000, channels: int = 1, int16_scale: bool = False):
+    """The device resampler on host arrays (asr_op_resample, the launch of set_input_format): audio = packed frames of `channels` interleaved float32 / int16 /
+    float16 samples at sample_rate, offsets [B + 1] in frames (any first offset) -> (packed model-rate mono float32, offsets [B + 1] from 0)."""
+    audio = np.ascontiguousarray(audio).reshape(-1)
+    code = _AUDIO_CODES[audio_np_dtype(audio.dtype)]
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offs.size < 2 or np.any(np.diff(offs) < 0) or offs[0] < 0 or int(offs[-1]) * int(channels) > audio.size:
+        raise ValueError("op_resample: offsets must be non-decreasing frame offsets inside the audio given")
+    L, M, W = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.check(_lib.load().asr_resample_table(int(sample_rate), int(model_rate), C.byref(L), C.byref(M), C.byref(W), None))      # (refuses bad rates)
+    n_out = -((-np.diff(offs) * L.value) // M.value)
+    out = np.empty(max(int(n_out.sum()), 1), dtype=np.float32)
+    offs_out = np.zeros(offs.size, dtype=np.int64)
+    lp = C.POINTER(C.c_int64)
+    _lib.check(_lib.load().asr_op_resample(audio.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(lp), offs.size - 1, code, int(sample_rate), int(model_rate),
+                                           int(channels), int(bool(int16_scale)), _fp(out), out.size, offs_out.ctypes.data_as(lp)))
+    return out[:int(offs_out[-1])], offs_out
 
 
 def op_ctc_collapse(frame_ids, seq_lens, blank_id=0):
@@ -958,7 +1017,7 @@ class ParaformerSession(_Session):
     def run_packed(self, audio, offsets, audio_device_ptr: int | None = None):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         B = offsets.size - 1
-        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        max_t = max(self.cfg.seq_len(int(n)) for n in self.model_lengths(np.diff(offsets))) if B else 1
         tok = np.zeros((B, max_t), dtype=np.int32)
         num = np.zeros((B,), dtype=np.int32)
         if audio_device_ptr is not None:
@@ -980,7 +1039,7 @@ class ParaformerSession(_Session):
         at which the token fired, in [0, T]; T means the tail threshold fired it behind the last row (paraformer.token_times maps rows to seconds)."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         B = offsets.size - 1
-        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        max_t = max(self.cfg.seq_len(int(n)) for n in self.model_lengths(np.diff(offsets))) if B else 1
         tok = np.zeros((B, max_t), dtype=np.int32)
         fire = np.zeros((B, max_t), dtype=np.int32)
         logprob = np.zeros((B, max_t), dtype=np.float32)
@@ -1025,7 +1084,7 @@ class ParaformerSession(_Session):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         B = offsets.size - 1
         topk = int(beam if topk is None else topk)
-        max_t = max(self.cfg.seq_len(int(n)) for n in np.diff(offsets)) if B else 1
+        max_t = max(self.cfg.seq_len(int(n)) for n in self.model_lengths(np.diff(offsets))) if B else 1
         tok = np.zeros((B, nbest, max_t), dtype=np.int32)
         logprob = np.zeros((B, nbest, max_t), dtype=np.float32)
         fire = np.zeros((B, max_t), dtype=np.int32)

@@ -23,6 +23,7 @@ from .arena import build_paraformer_arena
 from .config import ParaformerConfig
 from .ort_io import (array_for, filled_for, is_dynamic_dim, load_special_token_ids, load_supported_languages, numpy_dtype,
                      resolve_supported_language)
+from .input_format import as_frames, cut_windows, session_input_format
 from .sensevoice import plan_windows, prepare_audio_input
 
 C = onnxruntime
@@ -112,14 +113,16 @@ class ParaformerTranscriber:
         with open(vocab_path or os.path.join(model_folder, "Vocab_Paraformer.txt"), "r", encoding="UTF-8") as f:
             self.tokenizer = np.array([line.rstrip("\n") for line in f], dtype=np.str_)
 
-    def _run_window_timed(self, win: np.ndarray, offset_s: float, duration_s: float, max_token_rows: int):
+    def _run_window_timed(self, win: np.ndarray, offset_s: float, duration_s: float, max_token_rows: int, n_frames: int | None = None, n_model: int | None = None):
         """One window through the native session under the shim session (the graph's two outputs carry no times): (token ids as the graph returns them,
-        one record per token with the window's offset added and both ends clipped to the audio's duration)."""
+        one record per token with the window's offset added and both ends clipped to the audio's duration). n_frames / n_model: the window's length in
+        frames of the session's input format and in model-rate samples, where they are not win.size."""
         native = self.session._native
         cfg = native.cfg
-        tok, num, fire, logprob = native.run_packed_timed(win.reshape(-1), np.array([0, win.size], dtype=np.int64))
+        n_frames, n_model = win.size if n_frames is None else n_frames, win.size if n_model is None else n_model
+        tok, num, fire, logprob = native.run_packed_timed(win.reshape(-1), np.array([0, n_frames], dtype=np.int64))
         n = int(num[0])
-        spans = token_times(fire[0, :n], cfg.seq_len(win.size), cfg.lfr_n * cfg.hop_length / cfg.sample_rate, max_token_rows)
+        spans = token_times(fire[0, :n], cfg.seq_len(n_model), cfg.lfr_n * cfg.hop_length / cfg.sample_rate, max_token_rows)
         tokens = [{"id": int(tok[0, k]), "text": str(self.tokenizer[tok[0, k]]), "start": min(offset_s + float(spans[k, 0]), duration_s),
                    "end": min(offset_s + float(spans[k, 1]), duration_s), "logprob": float(logprob[0, k])} for k in range(n)]
         return tok[0, :n].copy(), tokens
@@ -148,14 +151,16 @@ class ParaformerTranscriber:
         index = {str(t): i for i, t in reversed(list(enumerate(self.tokenizer.tolist())))}
         return NgramLM.from_arpa(arpa_path, token_to_id=index.get)
 
-    def _run_window_beam(self, win: np.ndarray, beam_size: int, nbest: int, offset_s: float, duration_s: float, timestamps: bool, max_token_rows: int):
+    def _run_window_beam(self, win: np.ndarray, beam_size: int, nbest: int, offset_s: float, duration_s: float, timestamps: bool, max_token_rows: int,
+                         n_frames: int | None = None, n_model: int | None = None):
         """One window through the native session's beam search: (token ids of the best hypothesis, the hypotheses found, best first). Every hypothesis has
         one token per CIF fire, so with timestamps each carries "tokens" with the times of the window's shared fire rows (as _run_window_timed forms them)
         and its own log-probabilities; stop ids are dropped from a hypothesis' ids, text and records alike."""
         native = self.session._native
         cfg = native.cfg
-        tok, num, score, am, fire, logprob = native.run_packed_beam(win.reshape(-1), np.array([0, win.size], dtype=np.int64), beam_size, None, nbest)
-        return self._assemble_hypotheses(tok[0], num[0], score[0], am[0], fire[0], logprob[0], cfg.seq_len(win.size),
+        n_frames, n_model = win.size if n_frames is None else n_frames, win.size if n_model is None else n_model
+        tok, num, score, am, fire, logprob = native.run_packed_beam(win.reshape(-1), np.array([0, n_frames], dtype=np.int64), beam_size, None, nbest)
+        return self._assemble_hypotheses(tok[0], num[0], score[0], am[0], fire[0], logprob[0], cfg.seq_len(n_model),
                                          cfg.lfr_n * cfg.hop_length / cfg.sample_rate, offset_s, duration_s, timestamps, max_token_rows)
 
     def _assemble_hypotheses(self, tok, num, score, am, fire, logprob, n_rows, row_seconds, offset_s, duration_s, timestamps, max_token_rows):
@@ -178,7 +183,8 @@ class ParaformerTranscriber:
         return hyps[0]["token_ids"], hyps
 
     def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False, timestamps: bool = False, max_token_rows: int = 4,
-                   beam_size: int = 1, nbest: int = 1, hotwords=None, hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0):
+                   beam_size: int = 1, nbest: int = 1, hotwords=None, hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0,
+                   sample_rate: int | None = None, channels: int = 1):
         """int16 mono PCM at `sample_rate` -> dict(token_ids per window, text, rtf, windows). timestamps=True adds "tokens": one {"id", "text", "start",
         "end", "logprob"} per kept token over all windows, in seconds of the whole audio (token_times over the CIF fire rows; logprob = log soft-max of the
         decoder head at the pick); records of stop ids are dropped with their ids.
@@ -187,13 +193,18 @@ class ParaformerTranscriber:
         first: {"token_ids", "score", "am_score", "text"} and, with timestamps, "tokens" -- all hypotheses of a window share its CIF fire rows, so each has
         times. hotwords: token-id lists, or text spelled in the vocabulary; hotword_boost per matched token. lm: an lm.NgramLM (load_lm reads an ARPA file
         over this vocabulary): every token adds lm_weight * log P(token | history) + length_bonus to a hypothesis' score. The call sets exactly its own list
-        and model. With all of them at their defaults nothing changes."""
+        and model. With all of them at their defaults nothing changes.
+        sample_rate / channels: the audio is frames [n, channels] (or flat interleaved) of int16 at that rate, resampled on the device (the session's
+        input format, set for this call); windows are cut in input frames (input_format.cut_windows) and every result is what it is for the resampled
+        audio, in the same seconds. None: the model's own rate, mono -- the reference's loop, untouched."""
         use_beam = beam_size > 1 or nbest > 1 or bool(hotwords) or lm is not None
         if use_beam:
             if not 1 <= nbest <= beam_size <= 16:
                 raise ValueError(f"beam_size {beam_size}, nbest {nbest}: expected 1 <= nbest <= beam_size <= 16")
             self.session._native.set_hotwords(self._hotword_ids(hotwords), hotword_boost)        # exactly this call's list (an empty one clears)
             self.session._native.set_lm(lm, lm_weight, length_bonus)                             # ... and exactly this call's model
+        if sample_rate is not None:
+            return self._transcribe_frames(audio_int16, sample_rate, channels, sliding_window, normalise, timestamps, max_token_rows, use_beam, beam_size, nbest)
         audio_len = int(np.asarray(audio_int16).size)
         audio = prepare_audio_input(np.asarray(audio_int16, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype,
                                     audio_pcm_scale=self.audio_pcm_scale, normalise=normalise)
@@ -233,6 +244,44 @@ class ParaformerTranscriber:
         wall = time.time() - t0
         out = {"token_ids": ids_all, "text": decode_tokens(pieces, self.decode_mode), "rtf": wall / (audio_len / self.sample_rate),
                "windows": len(ids_all), "language": self.language}
+        if timestamps:
+            out["tokens"] = tokens_all
+        if use_beam:
+            out["nbest"] = nbest_all
+        return out
+
+    def _transcribe_frames(self, audio_int16, sample_rate, channels, sliding_window, normalise, timestamps, max_token_rows, use_beam, beam_size, nbest):
+        """`transcribe` for audio in another input format: the same windows, cut in input frames, each through the native session (the shim's graph is
+        the reference's: model-rate mono), which resamples on the device."""
+        native = self.session._native
+        frames = as_frames(audio_int16, channels)
+        audio = prepare_audio_input(frames.reshape(1, 1, -1), self.input_audio_dtype, audio_pcm_scale=self.audio_pcm_scale, normalise=normalise,
+                                    channels=channels).reshape(-1, channels)
+        shape_in = self.audio_meta.shape[-1]
+        fixed = None if is_dynamic_dim(shape_in) else int(shape_in)
+        window, cuts = cut_windows(audio, fixed, fixed if fixed is None or sliding_window <= 0 else sliding_window, sample_rate, self.sample_rate)
+        duration = frames.shape[0] / sample_rate
+        ids_all, pieces, tokens_all, nbest_all = [], [], [], []
+        t0 = time.time()
+        with session_input_format(native, sample_rate, channels):
+            for start, win in cuts:
+                where = dict(n_frames=win.shape[0], n_model=window)
+                if use_beam:
+                    token_ids, hyps = self._run_window_beam(win, beam_size, nbest, start / self.sample_rate, duration, timestamps, max_token_rows, **where)
+                    nbest_all.append(hyps)
+                    if timestamps:
+                        tokens_all.extend(hyps[0]["tokens"])
+                elif timestamps:
+                    token_ids, toks = self._run_window_timed(win, start / self.sample_rate, duration, max_token_rows, **where)
+                    tokens_all.extend(t for t in toks if t["id"] not in self.stop_token_ids)
+                else:
+                    tok, num = native.run_packed(win.reshape(-1), np.array([0, win.shape[0]], dtype=np.int64))
+                    token_ids = tok[0, :num[0]]
+                token_ids = token_ids[~np.isin(token_ids, self.stop_token_ids)]
+                ids_all.append(token_ids.copy())
+                pieces.extend(self.tokenizer[token_ids].tolist())
+        wall = time.time() - t0
+        out = {"token_ids": ids_all, "text": decode_tokens(pieces, self.decode_mode), "rtf": wall / duration, "windows": len(ids_all), "language": self.language}
         if timestamps:
             out["tokens"] = tokens_all
         if use_beam:

@@ -26,6 +26,7 @@ import numpy as np
 
 from .config import QwenAsrConfig
 from .engine import QwenAsrSession, audio_dtype_name
+from .input_format import as_frames, model_samples, ratio, session_input_format
 from .whisper import avg_logprob, prepare_audio_input
 
 ASR_TEXT_TAG = "<asr_text>"
@@ -173,16 +174,29 @@ class QwenAsrTranscriber:
         return [int(t) for t in system_prompt]
 
     def transcribe(self, clips_int16: Sequence[np.ndarray], task_prompts: Sequence = ("",), language_prompts: Sequence[str] = ("",),
-                   max_new: int | None = None):
+                   max_new: int | None = None, sample_rate: int | None = None, channels: int = 1):
         """int16 mono 16 kHz clips -> per clip dict(tokens, language, text, prompt_tokens); one prompt / language may serve all clips
-        (the reference's TASK_PROMPTS / LANGUAGE_PROMPTS broadcasting, :494-509). `text` is None without a tokenizer."""
+        (the reference's TASK_PROMPTS / LANGUAGE_PROMPTS broadcasting, :494-509). `text` is None without a tokenizer.
+        sample_rate / channels: the clips are frames [n, channels] (or flat interleaved) at that rate, resampled on the device (the session's input
+        format, set for this call); a clip is cut at max_audio_len samples of the resampled audio. None: 16 kHz mono, nothing changes."""
+        with session_input_format(self.sess, sample_rate, channels) as formatted:
+            return self._transcribe(clips_int16, task_prompts, language_prompts, max_new, (int(sample_rate), int(channels)) if formatted else None)
+
+    def _transcribe(self, clips_int16, task_prompts, language_prompts, max_new, fmt):
         B = len(clips_int16)
         tasks = list(task_prompts) * B if len(task_prompts) == 1 else list(task_prompts)
         langs = list(language_prompts) * B if len(language_prompts) == 1 else list(language_prompts)
         if len(tasks) != B or len(langs) != B:
             raise ValueError("task_prompts / language_prompts must have one entry or one per clip")
-        audios = [prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(-1), self.sess.audio_dtype, audio_pcm_scale=self.audio_pcm_scale,
-                                      normalise=self.normalise_audio)[:self.cfg.max_audio_len] for c in clips_int16]
+        if fmt is None:
+            audios = [prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(-1), self.sess.audio_dtype, audio_pcm_scale=self.audio_pcm_scale,
+                                          normalise=self.normalise_audio)[:self.cfg.max_audio_len] for c in clips_int16]
+            n_model = [a.size for a in audios]
+        else:                                                            # frames: the cut at max_audio_len model-rate samples falls on floor(max M / L) frames
+            L, M = ratio(fmt[0], self.cfg.sample_rate)
+            audios = [prepare_audio_input(as_frames(c, fmt[1]).reshape(-1), self.sess.audio_dtype, audio_pcm_scale=self.audio_pcm_scale,
+                                          normalise=self.normalise_audio, channels=fmt[1]).reshape(-1, fmt[1])[:self.cfg.max_audio_len * M // L] for c in clips_int16]
+            n_model = [model_samples(a.shape[0], fmt[0], self.cfg.sample_rate) for a in audios]
         pre = [self.head_ids + self._query_ids(t) + self.suffix_ids for t in tasks]
         post = [self.tail_ids + (list(resolve_language(self.languages, l)[1]["prompt_token_ids"]) if l else []) for l in langs]
         t0 = time.time()
@@ -221,7 +235,7 @@ class QwenAsrTranscriber:
                 res["token_logprobs"] = np.asarray(scores[b][:len(ids)], dtype=np.float32)
                 res["avg_logprob"] = avg_logprob(scores[b], len(ids), ended)
             out.append(res)
-        total_s = sum(a.size for a in audios) / self.cfg.sample_rate
+        total_s = sum(n_model) / self.cfg.sample_rate
         return out, {"rtf": wall / total_s, "wall_s": wall}
 
     def _prefill_and_generate(self, audios, pre, post, max_new):

@@ -17,6 +17,7 @@ import numpy as np
 from . import ort_shim as onnxruntime
 from .arena import build_sensevoice_arena
 from .config import SenseVoiceConfig
+from .input_format import as_frames, cut_windows, session_input_format
 from .ort_io import array_for, filled_for, is_dynamic_dim, load_supported_languages, numpy_dtype, resolve_supported_language
 
 C = onnxruntime  # `C.OrtDevice` in the reference scripts
@@ -33,7 +34,9 @@ def export_sensevoice(folder: str, cfg: SenseVoiceConfig, ck: dict, precision: i
 
 
 def prepare_audio_input(audio_int16: np.ndarray, input_audio_dtype: str, *, audio_pcm_scale: int, normalise: bool = False,
-                        target_rms: float = 4096.0) -> np.ndarray:
+                        target_rms: float = 4096.0, channels: int = 1) -> np.ndarray:
+    if normalise and channels > 1:
+        raise ValueError("RMS normalisation is defined on mono PCM: interleaved channels are mixed on the device, behind it (normalise=False, or mix first)")
     if not normalise and input_audio_dtype == "INT16":
         return np.ascontiguousarray(audio_int16, dtype=np.int16)
     audio = audio_int16.astype(np.float32)
@@ -120,11 +123,11 @@ class SenseVoiceTranscriber:
             self.tokenizer = SentencePieceProcessor()
             self.tokenizer.Load(tokenizer_path)
 
-    def _run_window_timed(self, win: np.ndarray, language_idx: np.ndarray, offset_s: float, duration_s: float):
+    def _run_window_timed(self, win: np.ndarray, language_idx: np.ndarray, offset_s: float, duration_s: float, n_frames: int | None = None):
         """One window through the native session under the shim session (the graph's two outputs carry no spans): (token ids, token records with the
-        window's offset added and both ends clipped to the audio's duration)."""
+        window's offset added and both ends clipped to the audio's duration). n_frames: the window's length in frames of the session's input format."""
         native = self.session._native
-        offsets = np.array([0, win.size], dtype=np.int64)
+        offsets = np.array([0, win.size if n_frames is None else n_frames], dtype=np.int64)
         tok, num, first, last, logprob = native.run_packed_timed(win.reshape(-1), offsets, np.asarray(language_idx, dtype=np.int32).reshape(-1))
         n = int(num[0])
         tokens = []
@@ -195,10 +198,10 @@ class SenseVoiceTranscriber:
             return i if tok.id_to_piece(i) == piece else None
         return NgramLM.from_arpa(arpa_path, token_to_id=piece_id)
 
-    def _run_window_beam(self, win: np.ndarray, language_idx: np.ndarray, beam_size: int, nbest: int):
+    def _run_window_beam(self, win: np.ndarray, language_idx: np.ndarray, beam_size: int, nbest: int, n_frames: int | None = None):
         """One window through the native session's CTC prefix beam search: (token ids of the best hypothesis, the hypotheses found, best first)."""
         native = self.session._native
-        offsets = np.array([0, win.size], dtype=np.int64)
+        offsets = np.array([0, win.size if n_frames is None else n_frames], dtype=np.int64)
         tok, num, score, ctc = native.run_packed_beam(win.reshape(-1), offsets, np.asarray(language_idx, dtype=np.int32).reshape(-1), beam_size, None, nbest)
         hyps = []
         for n in range(nbest):
@@ -210,7 +213,8 @@ class SenseVoiceTranscriber:
         return hyps[0]["token_ids"], hyps
 
     def transcribe(self, audio_int16: np.ndarray, sliding_window: int = 0, normalise: bool = False, timestamps: bool = False, beam_size: int = 1,
-                   nbest: int = 1, hotwords=None, hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0):
+                   nbest: int = 1, hotwords=None, hotword_boost: float = 2.0, lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0,
+                   sample_rate: int | None = None, channels: int = 1):
         """int16 mono PCM at `sample_rate` -> dict(token_ids, text, rtf, windows). timestamps=True adds "tokens": one {"id", "start", "end", "logprob"}
         per token over all windows, in seconds of the whole audio (SenseVoiceConfig.row_span_seconds; logprob = mean frame log-probability).
         beam_size > 1, nbest > 1 or hotwords: every window is decoded by the CTC prefix beam search (SenseVoiceSession.run_packed_beam) instead of the
@@ -218,7 +222,10 @@ class SenseVoiceTranscriber:
         {"token_ids", "score", "ctc_score", "text"}. hotwords: token-id lists, or text when a tokenizer is loaded; hotword_boost per matched token.
         lm: an lm.NgramLM (NgramLM.from_arpa; load_lm reads a file with this transcriber's tokenizer) fused into the search, which it implies as hotwords
         do: every token adds lm_weight * log P(token | history) + length_bonus to a hypothesis' score (SenseVoiceSession.set_lm). The call sets exactly
-        its own model: None clears one an earlier call set."""
+        its own model: None clears one an earlier call set.
+        sample_rate / channels: the audio is frames [n, channels] (or flat interleaved) of int16 at that rate, resampled on the device (the session's
+        input format, set for this call); windows are cut in input frames (input_format.cut_windows) and every result is what it is for the resampled
+        audio, in the same seconds. None: the model's own rate, mono -- the reference's loop, untouched."""
         use_beam = beam_size > 1 or nbest > 1 or bool(hotwords) or lm is not None
         if use_beam:
             if timestamps:
@@ -227,6 +234,8 @@ class SenseVoiceTranscriber:
                 raise ValueError(f"beam_size {beam_size}, nbest {nbest}: expected 1 <= nbest <= beam_size <= 16")
             self.session._native.set_hotwords(self._hotword_ids(hotwords), hotword_boost)        # exactly this call's list (an empty one clears)
             self.session._native.set_lm(lm, lm_weight, length_bonus)                             # ... and exactly this call's model
+        if sample_rate is not None:
+            return self._transcribe_frames(audio_int16, sample_rate, channels, sliding_window, normalise, timestamps, use_beam, beam_size, nbest)
         audio_len = int(np.asarray(audio_int16).size)
         audio = prepare_audio_input(np.asarray(audio_int16, dtype=np.int16).reshape(1, 1, -1), self.input_audio_dtype,
                                     audio_pcm_scale=self.audio_pcm_scale, normalise=normalise)
@@ -273,6 +282,43 @@ class SenseVoiceTranscriber:
         wall = time.time() - t0
         out = {"token_ids": ids_all, "text": text if self.tokenizer is not None else None,
                "rtf": wall / (audio_len / self.sample_rate), "windows": len(ids_all), "language": self.language}
+        if timestamps:
+            out["tokens"] = tokens_all
+        if use_beam:
+            out["nbest"] = nbest_all
+        return out
+
+    def _transcribe_frames(self, audio_int16, sample_rate, channels, sliding_window, normalise, timestamps, use_beam, beam_size, nbest):
+        """`transcribe` for audio in another input format: the same windows, cut in input frames, each through the native session (the shim's graph is
+        the reference's: model-rate mono), which resamples on the device."""
+        native = self.session._native
+        frames = as_frames(audio_int16, channels)
+        audio = prepare_audio_input(frames.reshape(1, 1, -1), self.input_audio_dtype, audio_pcm_scale=self.audio_pcm_scale, normalise=normalise,
+                                    channels=channels).reshape(-1, channels)
+        shape_in = self.audio_meta.shape[-1]
+        fixed = None if is_dynamic_dim(shape_in) else int(shape_in)
+        window, cuts = cut_windows(audio, fixed, fixed if fixed is None or sliding_window <= 0 else sliding_window, sample_rate, self.sample_rate)
+        duration = frames.shape[0] / sample_rate
+        lang = np.asarray([self.selector_index], dtype=np.int32)
+        ids_all, text, tokens_all, nbest_all = [], "", [], []
+        t0 = time.time()
+        with session_input_format(native, sample_rate, channels):
+            for start, win in cuts:
+                if timestamps:
+                    token_ids, toks = self._run_window_timed(win, lang, start / self.sample_rate, duration, n_frames=win.shape[0])
+                    tokens_all.extend(toks)
+                elif use_beam:
+                    token_ids, hyps = self._run_window_beam(win, lang, beam_size, nbest, n_frames=win.shape[0])
+                    nbest_all.append(hyps)
+                else:
+                    tok, num = native.run_packed(win.reshape(-1), np.array([0, win.shape[0]], dtype=np.int64), lang)
+                    token_ids = tok[0, :num[0]]
+                ids_all.append(token_ids.copy())
+                if self.tokenizer is not None:
+                    text += self.tokenizer.decode([token_ids.tolist()])[0]
+        wall = time.time() - t0
+        out = {"token_ids": ids_all, "text": text if self.tokenizer is not None else None, "rtf": wall / duration, "windows": len(ids_all),
+               "language": self.language}
         if timestamps:
             out["tokens"] = tokens_all
         if use_beam:

@@ -54,10 +54,13 @@ import numpy as np
 
 from .config import WhisperConfig
 from .engine import WhisperSession, audio_dtype_name
+from .input_format import as_frames, cut_windows, model_samples, session_input_format
 
 
 def prepare_audio_input(audio_int16: np.ndarray, target_dtype=np.float32, *, audio_pcm_scale: int = 32768,
-                        normalise: bool = False, target_rms: float = 4096.0) -> np.ndarray:
+                        normalise: bool = False, target_rms: float = 4096.0, channels: int = 1) -> np.ndarray:
+    if normalise and channels > 1:
+        raise ValueError("RMS normalisation is defined on mono PCM: interleaved channels are mixed on the device, behind it (normalise=False, or mix first)")
     target_dtype = np.dtype(target_dtype)
     if not normalise and target_dtype == np.int16:
         return np.ascontiguousarray(audio_int16, dtype=np.int16)
@@ -523,13 +526,22 @@ class WhisperTranscriber:
             return [hyps[0][0] for hyps in self.sess.beam_search(self.beam_size, limit, eos_id=self.cfg.eot_id)]
         return self.sess.generate(limit, eos_id=self.cfg.eot_id)
 
-    def transcribe(self, clips_int16: Sequence[np.ndarray], language_ids: Sequence[int] | None = None, max_new: int | None = None, prompts=None):
+    def transcribe(self, clips_int16: Sequence[np.ndarray], language_ids: Sequence[int] | None = None, max_new: int | None = None, prompts=None,
+                   sample_rate: int | None = None, channels: int = 1):
         """List of int16 mono 16 kHz clips (each <= 30 s) -> per clip dict(tokens, language_id, no_speech_prob, skipped, prompt_len). Timestamp mode adds
         segments = [{"start", "end", "tokens"}] (seconds from the clip's start) and keeps text ids only in tokens; the repeat guard is not applied.
         prompts: per clip the ids of its previous text (any lengths, None / empty: none) -- how a caller batches window k of many files; initial_prompt goes
-        in front of each. The longest prompt bounds the whole batch: new ids <= max_target_positions - longest prompt."""
+        in front of each. The longest prompt bounds the whole batch: new ids <= max_target_positions - longest prompt.
+        sample_rate / channels: the clips are frames [n, channels] (or flat interleaved) at that rate, resampled on the device (the session's input
+        format, set for this call); lengths and seconds are the resampled clips'. None: 16 kHz mono, nothing changes."""
+        with session_input_format(self.sess, sample_rate, channels) as formatted:
+            return self._transcribe(clips_int16, language_ids, max_new, prompts, channels if formatted else None)
+
+    def _transcribe(self, clips_int16, language_ids, max_new, prompts, channels):
         cfg = self.cfg
         audios = [prepare_audio_input(np.asarray(c, dtype=np.int16).reshape(-1), self.sess.audio_dtype) for c in clips_int16]
+        # samples per clip at the model's rate: the clip's own size, or what the resampler makes of its frames
+        n_model = [a.size for a in audios] if channels is None else [int(n) for n in self.sess.model_lengths([a.size // channels for a in audios])]
         B = len(audios)
         lang = np.asarray(language_ids if language_ids is not None else [cfg.first_language_id] * B, dtype=np.int64)
         t0 = time.time()
@@ -546,7 +558,7 @@ class WhisperTranscriber:
             raise ValueError(f"{len(prompts)} prompts for {B} clips")
         prompt = self._prompts(lang, None if prompts is None else [p if p is not None else [] for p in prompts])
         limit = self._limit(prompt, max_new)
-        toks, aligned, quality = self._decode(prompt, limit, [a.size for a in audios], skipped)
+        toks, aligned, quality = self._decode(prompt, limit, n_model, skipped)
         wall = time.time() - t0
         out = []
         for b in range(B):
@@ -559,21 +571,21 @@ class WhisperTranscriber:
                 res.update(token_logprobs=lps, avg_logprob=0.0 if skipped[b] else q["avg_logprob"],
                            compression_ratio=None if skipped[b] else q["compression_ratio"], temperature=q["temperature"])
             if self.timestamps:
-                res["segments"] = split_segments(ids, self.ts_begin, 0.0, audios[b].size / cfg.sample_rate)
+                res["segments"] = split_segments(ids, self.ts_begin, 0.0, n_model[b] / cfg.sample_rate)
                 ids = [t for t in ids if t < self.ts_begin]
             elif self.remove_repeats and not self.word_timestamps and not self.token_scores:
                 ids = list(remove_repeated_parts(ids, 3, len(ids)))
             res["tokens"] = np.asarray(ids, dtype=np.int32)
             if self.word_timestamps:
-                res.update(self._token_times(aligned[b], ids, 0.0, audios[b].size / cfg.sample_rate, lps))
+                res.update(self._token_times(aligned[b], ids, 0.0, n_model[b] / cfg.sample_rate, lps))
                 if self.timestamps:
                     self._add_segment_times(res["segments"], res["token_times"], logprobs=lps)
             out.append(res)
-        total_s = sum(a.size for a in audios) / cfg.sample_rate
+        total_s = sum(n_model) / cfg.sample_rate
         return out, {"rtf": wall / total_s, "wall_s": wall}
 
     def transcribe_file(self, pcm_int16: np.ndarray, language_id: int | None = None, sliding_window: int = 0,
-                        input_audio_length: int | None = -1, max_new: int | None = None):
+                        input_audio_length: int | None = -1, max_new: int | None = None, sample_rate: int | None = None, channels: int = 1):
         """One file the way the reference's loop walks it (Inference_Whisper_ONNX.py:741-829). input_audio_length: the encoder's static audio
         dimension, None = dynamic axis (one unpadded window), -1 = dynamic when the file fits the encoder, else windows of cfg.max_audio_len.
         -> dict(tokens = the windows' ids concatenated (repeat guard applied when enabled), windows = per-window ids,
@@ -590,19 +602,35 @@ class WhisperTranscriber:
         condition_on_previous_text the windows run IN ORDER, one encode each: window w is prompted with initial_prompt + the text ids kept since the last
         reset (build_prompt keeps the last max_target_positions // 2 - 1 of them); a window whose decode ended at a temperature above prompt_reset_temperature
         forgets them (that needs temperature_fallback: without it the temperature never rises and nothing is reset), a later window whose own [SOT] probe says
-        no speech is skipped and adds nothing. max_new is clamped to max_target_positions - prompt length. The result gains prompt_len, per window."""
+        no speech is skipped and adds nothing. max_new is clamped to max_target_positions - prompt length. The result gains prompt_len, per window.
+        sample_rate / channels: the file is frames [n, channels] (or flat interleaved) at that rate, resampled on the device (the session's input format,
+        set for this call). Windows and strides stay model-rate figures and are cut in input frames (input_format.cut_windows: both have to be whole
+        numbers of frames); lengths, offsets and seconds are the resampled file's. None: 16 kHz mono, nothing changes."""
+        with session_input_format(self.sess, sample_rate, channels) as formatted:
+            return self._transcribe_file(pcm_int16, language_id, sliding_window, input_audio_length, max_new, (int(sample_rate), int(channels)) if formatted else None)
+
+    def _transcribe_file(self, pcm_int16, language_id, sliding_window, input_audio_length, max_new, fmt):
         cfg = self.cfg
-        raw = np.asarray(pcm_int16, dtype=np.int16).reshape(-1)
-        audio_len = int(raw.size)
+        if fmt is None:
+            raw = np.asarray(pcm_int16, dtype=np.int16).reshape(-1)
+            audio_len = int(raw.size)
+        else:
+            frames = as_frames(pcm_int16, fmt[1])
+            audio_len = model_samples(frames.shape[0], fmt[0], cfg.sample_rate)
         if input_audio_length == -1:
             # the reference's default export keeps the audio axis dynamic (Export_Whisper.py:743): the window is the file, unpadded. A file longer than
             # the encoder's position table can only run through the static-axis export: windows of max_audio_len, the tail zero-padded.
             input_audio_length = None if audio_len <= cfg.max_audio_len else cfg.max_audio_len
-        audio = prepare_audio_input(raw, self.sess.audio_dtype)
         n_win, stride, window, aligned = plan_windows(audio_len, input_audio_length, sliding_window)
-        if audio.size < aligned:                                         # zero-padded tail (:751-757)
-            audio = np.concatenate([audio, np.zeros(aligned - audio.size, dtype=audio.dtype)])
-        clips = [np.ascontiguousarray(audio[w * stride:w * stride + window]) for w in range(n_win)]
+        if fmt is None:
+            audio = prepare_audio_input(raw, self.sess.audio_dtype)
+            if audio.size < aligned:                                     # zero-padded tail (:751-757)
+                audio = np.concatenate([audio, np.zeros(aligned - audio.size, dtype=audio.dtype)])
+            clips = [np.ascontiguousarray(audio[w * stride:w * stride + window]) for w in range(n_win)]
+        else:                                                            # the same windows, cut in input frames
+            audio = prepare_audio_input(frames.reshape(-1), self.sess.audio_dtype).reshape(-1, fmt[1])
+            clips = [np.ascontiguousarray(w) for _, w in cut_windows(audio, None if input_audio_length is None else window, stride, fmt[0], cfg.sample_rate)[1]]
+            assert len(clips) == n_win
         lang = cfg.first_language_id if language_id is None else int(language_id)
         t0 = time.time()
         chained = self.condition_on_previous_text and n_win > 1

@@ -78,7 +78,8 @@ enum asr_mem { ASR_MEM_HOST = 0, ASR_MEM_DEVICE = 1 };
  *   Whisper / Qwen3-ASR / ForcedAligner (Whisper/Export_Whisper.py:43,367,423,735,741; Qwen_ASR/Export_Qwen_ASR.py:80,710-731,854,1596): I16 = raw PCM, the
  *     1/32768 that the export folds into the STFT window (STFT_Process.py:143) is applied at the load; F32 / F16 = values already in [-1, 1].
  * Widening int16 / f16 to f32 is exact and 2^-15 commutes with every f32 rounding, so an I16 call equals the F32 call on the widened (and, for the second
- * group, scaled) samples bit for bit. audio_offsets always count samples; a 2-byte utterance needs 2-byte alignment only. */
+ * group, scaled) samples bit for bit. audio_offsets always count samples (frames of interleaved samples once asr_session_set_input_format has set another
+ * format); a 2-byte utterance needs 2-byte alignment only. */
 enum asr_audio_dtype { ASR_AUDIO_F32 = 0, ASR_AUDIO_I16 = 1, ASR_AUDIO_F16 = 2 };
 
 typedef struct asr_session asr_session;
@@ -575,6 +576,16 @@ int asr_session_device(asr_session* s, int* device_id);
  * end are keyed by it. INVALID for a null session or an unknown value. */
 int asr_session_set_audio_dtype(asr_session* s, int audio_dtype);
 int asr_session_audio_dtype(asr_session* s, int* audio_dtype_out);
+/* Sample rate (Hz) and interleaved channel count of the session's audio entries; the default is the model's own rate (the config's sample_rate) and one channel,
+ * and with it nothing changes and nothing is launched. With any other format every audio entry's `audio` and `audio_offsets` count FRAMES -- one frame is
+ * `channels` interleaved samples of the session's audio dtype, host or device memory alike -- and the library turns them into model-rate mono f32 on the device in
+ * front of the front end: channel mean, then a polyphase Kaiser-windowed sinc (cutoff 0.945 of the narrower Nyquist; the table is asr_resample_table's). An
+ * utterance of n frames becomes ceil(n * rate_model / sample_rate) samples, and frame counts, length limits (max_audio_len) and result frames all refer to those.
+ * This is the build's own mode (the reference resamples on the host with audioop, no low-pass): sample parity with the reference holds for the default format only.
+ * May be set between any two compute calls. INVALID (the format in force stays) for a null session, a rate < 1, channels outside 1..8, rates whose reduced ratio
+ * needs more than 1024 filter phases (16001 Hz), or a rate beyond ~40 x the model's. The streaming step refuses a non-default format: it takes model-rate mono. */
+int asr_session_set_input_format(asr_session* s, int sample_rate, int channels);
+int asr_session_input_format(asr_session* s, int* sample_rate_out, int* channels_out);
 
 /* Per-kernel-class timing with HIP events on the session stream (bench.py roofline leg).
  * read: up to `cap` classes; names are NUL-terminated, 32 bytes apart in `names`. */
@@ -586,7 +597,8 @@ int asr_session_profile_read(asr_session* s, int cap, char* names, double* total
  * enable before a run; read copies the named f32 tensor of the LAST run to host.
  * names: "mel" "enc_in" "block0" "enc_out" "logits" "frame_ids"(i32); timed Paraformer runs add "fire_frames"(i32) "token_logprob" ([utterances][max_tokens]);
  * offline Paraformer runs add "alphas" and, on the packed token rows like "logits" (rows at or past the device-side count hold nothing defined),
- * "acoustic" (the CIF output) and "dec0" .. (the rows behind each decoder layer, full layers first, then the decoders3 ones) */
+ * "acoustic" (the CIF output) and "dec0" .. (the rows behind each decoder layer, full layers first, then the decoders3 ones); every family with a
+ * non-default input format adds "resampled" ([1][samples]: the packed model-rate mono samples the front end read) */
 int asr_session_taps_enable(asr_session* s, int enable);
 int asr_session_tap_shape(asr_session* s, const char* name, int64_t* rows, int64_t* cols);
 int asr_session_tap_read(asr_session* s, const char* name, void* host_out, size_t bytes);
@@ -669,6 +681,15 @@ int asr_op_ctc_align(const float* em, int ld_em, const int32_t* seq_lens, int ba
  * fire_frame_out host [batch][max_tokens] (slots at or past the token count, or past max_tokens, are not written); num_id_out [batch] holds the full count */
 int asr_op_cif_scan_timed(const float* alpha, const float* enc, int d, const int32_t* seq_lens, int batch, float tail_threshold, float* acoustic_out,
                           int32_t* fire_frame_out, int max_tokens, int32_t* num_id_out);
+/* The resampler of asr_session_set_input_format on host arrays (the same launch): audio = packed frames of `channels` interleaved samples of audio_dtype at rate_in,
+ * offsets [batch + 1] in frames (any first offset). out [out_cap] receives the packed model-rate mono f32 samples, offsets_out [batch + 1] their offsets from 0:
+ * utterance b has ceil(n_b * rate_model / rate_in) samples. int16_scale != 0: int16 samples are scaled by 2^-15, as in front of the Whisper / Qwen front end. */
+int asr_op_resample(const void* audio, const int64_t* offsets, int batch, int audio_dtype, int rate_in, int rate_model, int channels, int int16_scale,
+                    float* out, int64_t out_cap, int64_t* offsets_out);
+/* The filter the library uses for rate_in -> rate_model: with g their greatest common divisor L = rate_model / g phases, M = rate_in / g, half width W input
+ * frames, T = 2 W + 1 taps per phase; output n reads input frames floor(n M / L) - W .. + W against row (n M) mod L. coeffs: null, or [L][T] f32 (computed in
+ * double, rounded once). Equal rates give L = M = 1, W = 0 and the single coefficient 1. INVALID as asr_session_set_input_format refuses rates. */
+int asr_resample_table(int rate_in, int rate_model, int* L, int* M, int* W, float* coeffs);
 
 #ifdef __cplusplus
 }

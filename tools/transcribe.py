@@ -13,7 +13,8 @@ machine that has the checkpoints (none exist offline; tests/test_transcribe_cpu.
     python tools/transcribe.py compare ours.json reference.json
 
 Dump schema: {"family", "precision", "files": [{"path", "n_samples", "language", "windows": [[token ids], ...], "text"}]}.
-Audio ingest = audio_io.read_wav_int16 (the reference's pydub calls restated on stdlib wave / audioop); detokenisation: SentencePiece
+Audio ingest = audio_io.read_wav_int16 (the reference's pydub calls restated on stdlib wave / audioop), or with --device-resample the wav's own frames at
+its own rate and channel count, resampled by the session on the device (the build's own mode: not sample-exact against the reference); detokenisation: SentencePiece
 (SenseVoice, :305), vocabulary join (Paraformer), `tokenizer._decode_asr` (Whisper, Inference_Whisper_ONNX.py:702-715),
 `tokenizer.decode(..., skip_special_tokens=True)` + parse_asr_output (Qwen3-ASR, Inference_Qwen_ASR_ONNX.py:746-752) -- each only
 when a tokenizer is given; the token ids are what is compared.
@@ -124,6 +125,17 @@ def load_decoder_lm(opts, tok):
     return {"lm": lm, "lm_weight": opts["lm_weight"], "length_bonus": opts["length_bonus"], "lm_topk": opts["lm_topk"]}
 
 
+def read_audio(a, path, reference_ingest):
+    """One wav -> (int16 audio, the transcriber's format arguments, what the dump records about it). Default: reference_ingest(), mono PCM at the model's rate,
+    converted on the host as the reference's pydub ingest does. --device-resample: the file's own frames [n, channels] at its own rate; the session resamples
+    on the device."""
+    if getattr(a, "device_resample", False):
+        frames, rate, channels = _m("audio_io").read_wav_native(path)
+        return frames, {"sample_rate": rate, "channels": channels}, {"n_samples": int(frames.shape[0]), "sample_rate": rate, "channels": channels}
+    pcm = reference_ingest()
+    return pcm, {}, {"n_samples": int(pcm.size)}
+
+
 def run(a) -> dict:
     shim, eng, audio_io, cfgm = _m("ort_shim"), _m("engine"), _m("audio_io"), _m("config")
     prec = 1 if a.precision == "f32" else 0
@@ -184,18 +196,18 @@ def run(a) -> dict:
             nar_kw = {k: v for k, v in nar.items() if k != "lm_file"}
             nar_kw["lm"] = tr.load_lm(nar["lm_file"]) if nar["lm_file"] else None
         for p in a.wav:
-            pcm = audio_io.read_wav_int16(p, tr.sample_rate, exact_width=a.strict_wav)
+            pcm, fmt, about = read_audio(a, p, lambda: audio_io.read_wav_int16(p, tr.sample_rate, exact_width=a.strict_wav))
             if nar_kw:
-                r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=timestamps, **nar_kw)
+                r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=timestamps, **nar_kw, **fmt)
             elif timestamps:
-                r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=True)
+                r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=True, **fmt)
             elif sv_beam:
                 r = tr.transcribe(pcm, sliding_window=a.sliding_window, beam_size=a.beam, nbest=nbest, hotwords=parse_hotword_file(hot_file) if hot_file else None,
                                   hotword_boost=getattr(a, "hotword_boost", 2.0), lm=lm, lm_weight=0.5 if lm_weight is None else lm_weight,
-                                  length_bonus=0.0 if length_bonus is None else length_bonus)
+                                  length_bonus=0.0 if length_bonus is None else length_bonus, **fmt)
             else:
-                r = tr.transcribe(pcm, sliding_window=a.sliding_window)
-            files.append({"path": p, "n_samples": int(pcm.size), "language": r.get("language", a.language),
+                r = tr.transcribe(pcm, sliding_window=a.sliding_window, **fmt)
+            files.append({"path": p, **about, "language": r.get("language", a.language),
                           "windows": [np.asarray(w).reshape(-1).astype(int).tolist() for w in r["token_ids"]], "text": r.get("text"), "rtf": r["rtf"]})
             if timestamps:
                 files[-1]["tokens"] = r["tokens"]
@@ -234,16 +246,16 @@ def run(a) -> dict:
                 raise SystemExit("--language other than 'auto' needs --tokenizer (language token ids come from its vocabulary)")
             lang_id = tok.convert_tokens_to_ids(f"<|{a.language}|>")
         for p in a.wav:
-            pcm = audio_io.read_wav_int16(p, cfg.sample_rate, exact_width=a.strict_wav)
+            pcm, fmt, about = read_audio(a, p, lambda: audio_io.read_wav_int16(p, cfg.sample_rate, exact_width=a.strict_wav))
             # the reference's per-file loop (Inference_Whisper_ONNX.py:741-829): SLIDING_WINDOW stride, zero-padded tail, probe on window 0 only,
             # a no-speech verdict aborts the file, later windows reuse window 0's language
-            r, stat = tr.transcribe_file(pcm, language_id=lang_id, sliding_window=a.sliding_window)
+            r, stat = tr.transcribe_file(pcm, language_id=lang_id, sliding_window=a.sliding_window, **fmt)
             ids = r["windows"]
             flat = r["tokens"].tolist() if timestamps else [t for w in ids for t in w]      # timestamp mode: the text ids, repeat guard not applied
             text = None
             if tok is not None:
                 text = "[no speech detected]" if r["no_speech"] else (whisper_text(tok, flat, remove_repeats=not (timestamps or word_ts or scores)) if flat else "")
-            files.append({"path": p, "n_samples": int(pcm.size), "language": a.language, "windows": ids, "text": text, "rtf": stat["rtf"],
+            files.append({"path": p, **about, "language": a.language, "windows": ids, "text": text, "rtf": stat["rtf"],
                           "language_ids": [r["language_id"]] * len(ids), "no_speech_prob": [r["no_speech_prob"]], "no_speech": r["no_speech"]})
             if tr.initial_prompt or tr.condition_on_previous_text:        # the build's own mode: the prompt length each window was decoded behind
                 files[-1]["prompt_len"] = r["prompt_len"]
@@ -275,10 +287,10 @@ def run(a) -> dict:
         tr = _m("qwen_asr").QwenAsrTranscriber(cfg, sess, info["metadata"], tokenizer=tok, repeat_penalty=a.repeat_penalty, beam_size=a.beam,
                                                token_scores=scores, hotwords=dec_hot, hotword_boost=dec_hot_boost, **load_decoder_lm(dec_lm, tok))
         for p in a.wav:
-            pcm = audio_io.read_wav_int16(p, cfg.sample_rate, exact_width=a.strict_wav)
-            out, stat = tr.transcribe([pcm], language_prompts=("" if a.language == "auto" else a.language,))
+            pcm, fmt, about = read_audio(a, p, lambda: audio_io.read_wav_int16(p, cfg.sample_rate, exact_width=a.strict_wav))
+            out, stat = tr.transcribe([pcm], language_prompts=("" if a.language == "auto" else a.language,), **fmt)
             r = out[0]
-            files.append({"path": p, "n_samples": int(pcm.size), "language": r.get("language") or a.language,
+            files.append({"path": p, **about, "language": r.get("language") or a.language,
                           "windows": [np.asarray(r["tokens"]).astype(int).tolist()], "text": r.get("text"), "rtf": stat["rtf"]})
             if scores:
                 files[-1].update(token_logprobs=[float(v) for v in r["token_logprobs"]], avg_logprob=r["avg_logprob"])
@@ -385,6 +397,9 @@ def build_parser():
                         "<|startofprev|>: a glossary or style hint (OpenAI's initial_prompt)")
     r.add_argument("--condition-on-previous-text", action="store_true", help="Whisper: run a file's windows in order, each prompted with the text ids of the windows "
                         "before it; with --temperature-fallback the context is dropped after a window decoded above temperature 0.5")
+    r.add_argument("--device-resample", action="store_true", help="feed each wav at its own sample rate and channel count and let the session resample on the "
+                   "device (set_input_format: low-pass polyphase filter, channel mean). The build's own mode: without it the ingest is the reference's host-side "
+                   "conversion, sample for sample")
     r.add_argument("--out", required=True)
     r.add_argument("--any-wav-width", dest="strict_wav", action="store_false",
                    help="accept 8 / 24 / 32-bit wav (rescaled to int16); by default only 16-bit wav is taken: the only width whose samples equal the reference's, "
