@@ -2,9 +2,11 @@
 #include <cstring>
 
 #include "../../include/asr_mi355x.h"
+#include "beam_dev.h"
 #include "engine.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "nar_stream_state.h"
 #include "ngram_lm.h"
 
 const std::string& asr_get_error();
@@ -464,91 +466,124 @@ extern "C" int asr_op_ctc_collapse_timed(const int32_t* frame_ids, const float* 
 }
 
 namespace {
-// the hotword trie arrays of the host-array searches: a tree in the documented layout -- every node but the root is the child of exactly one node, one level below it
-void require_trie(const char* who, const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
-                  const int32_t* trie_child_node, int n_nodes, int blank_id) {
-  ASR_REQUIRE(n_nodes >= 0 && (n_nodes <= 1 || (trie_depth && trie_is_end && trie_child_off && trie_child_tok && trie_child_node)), "%s: trie arrays missing", who);
+// the hotword trie arrays and the language model image of the host-array searches, as their entry points take them (lm words null: no model)
+struct TrieArrays { const int32_t *depth, *is_end, *child_off, *child_tok, *child_node; int n_nodes; float boost; };
+struct LmImage { const int32_t* words; int64_t n_words; float alpha, beta, oov; };
+
+// a tree in the documented layout -- every node but the root is the child of exactly one node, one level below it
+void require_trie(const char* who, const TrieArrays& tr, int blank_id) {
+  const int n_nodes = tr.n_nodes;
+  ASR_REQUIRE(n_nodes >= 0 && (n_nodes <= 1 || (tr.depth && tr.is_end && tr.child_off && tr.child_tok && tr.child_node)), "%s: trie arrays missing", who);
   if (n_nodes <= 1) return;
-  ASR_REQUIRE(trie_child_off[0] == 0 && trie_child_off[n_nodes] == n_nodes - 1 && trie_depth[0] == 0, "%s: malformed trie", who);
+  ASR_REQUIRE(tr.child_off[0] == 0 && tr.child_off[n_nodes] == n_nodes - 1 && tr.depth[0] == 0, "%s: malformed trie", who);
   for (int n = 0; n < n_nodes; ++n) {
-    ASR_REQUIRE(trie_child_off[n] <= trie_child_off[n + 1], "%s: malformed trie (child_off)", who);
-    for (int e = trie_child_off[n]; e < trie_child_off[n + 1]; ++e) {
-      const int ch = trie_child_node[e];
-      ASR_REQUIRE(ch > 0 && ch < n_nodes && trie_depth[ch] == trie_depth[n] + 1 && trie_child_tok[e] != blank_id && (e == trie_child_off[n] || trie_child_tok[e - 1] < trie_child_tok[e]),
+    ASR_REQUIRE(tr.child_off[n] <= tr.child_off[n + 1], "%s: malformed trie (child_off)", who);
+    for (int e = tr.child_off[n]; e < tr.child_off[n + 1]; ++e) {
+      const int ch = tr.child_node[e];
+      ASR_REQUIRE(ch > 0 && ch < n_nodes && tr.depth[ch] == tr.depth[n] + 1 && tr.child_tok[e] != blank_id && (e == tr.child_off[n] || tr.child_tok[e - 1] < tr.child_tok[e]),
                   "%s: malformed trie (node %d, child entry %d)", who, n, e);
     }
   }
 }
 // ... and their device copy (t keeps it alive)
-HotTrie upload_trie(Tmp& t, const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node,
-                    int n_nodes, float boost) {
+HotTrie upload_trie(Tmp& t, const TrieArrays& tr) {
+  const int n_nodes = tr.n_nodes;
   if (n_nodes <= 1) return HotTrie{};
   std::vector<int32_t> img;
-  img.insert(img.end(), trie_depth, trie_depth + n_nodes); img.insert(img.end(), trie_is_end, trie_is_end + n_nodes);
-  img.insert(img.end(), trie_child_off, trie_child_off + n_nodes + 1); img.insert(img.end(), trie_child_tok, trie_child_tok + n_nodes - 1);
-  img.insert(img.end(), trie_child_node, trie_child_node + n_nodes - 1);
+  img.insert(img.end(), tr.depth, tr.depth + n_nodes); img.insert(img.end(), tr.is_end, tr.is_end + n_nodes);
+  img.insert(img.end(), tr.child_off, tr.child_off + n_nodes + 1); img.insert(img.end(), tr.child_tok, tr.child_tok + n_nodes - 1);
+  img.insert(img.end(), tr.child_node, tr.child_node + n_nodes - 1);
   int32_t* dtrie = (int32_t*)t.alloc(img.size() * 4);
   HIP_CHECK(hipMemcpy(dtrie, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  return hot_trie_view(dtrie, n_nodes, boost);
+  return hot_trie_view(dtrie, n_nodes, tr.boost);
 }
 
-// both host-array entries of the search; lm_image null: without a language model
-int op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id, const int32_t* trie_depth,
-                       const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node, int n_nodes, float boost,
-                       int beam, int nbest, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score, const int32_t* lm_image, int64_t lm_words,
-                       float alpha, float beta, float oov_logprob) {
-  return asr_guard([&] {
-    ASR_REQUIRE(cand_id && cand_logprob && seq_lens && token_ids && num_id && score && ctc_score && batch > 0 && max_tokens > 0, "op_ctc_prefix_beam: bad argument");
-    ASR_REQUIRE(topk >= 1 && topk <= 16 && beam >= 1 && beam <= 16 && nbest >= 1 && nbest <= beam, "op_ctc_prefix_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)",
-                beam, topk, nbest);
-    require_trie("op_ctc_prefix_beam", trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, blank_id);
-    if (lm_image) {                                      // the image, then every id the walk will look up
-      ngram_lm_validate(lm_image, lm_words, lm_words >= NGRAM_LM_HEADER ? lm_image[3] : 0, blank_id, alpha, beta, oov_logprob, "op_ctc_prefix_beam_lm");
-      int64_t rows = 0;
-      for (int b = 0; b < batch; ++b) rows += seq_lens[b];
-      for (int64_t i = 0; i < rows * topk; ++i)
-        ASR_REQUIRE(cand_logprob[i] == -INFINITY || (cand_id[i] >= 0 && cand_id[i] < lm_image[3]), "op_ctc_prefix_beam_lm: candidate %d outside the model's vocabulary of %d",
-                    cand_id[i], lm_image[3]);
+// What the three host-array searches share on their way to the device. cand_id / cand_lp hold lens[i] rows of topk candidates per sequence i < n, densely; the
+// rows go up by plan: PACKED is PackedPlan's layout (the CTC search), COMPACT the compact token plan's (16-row aligned per sequence, an empty sequence keeps one
+// dummy row, the total row count on the device in m_dev, plan[i].lang = streams[i] when given), as the Paraformer sessions hand them to the kernels. Checked
+// on the way, in this order: with a model the image (blank_id -1: "no blank") and every id the walk will look up, then the device, then distinct ids per row.
+// who / lm_who / unit are the names the messages carry. t keeps everything alive; the entry point allocates its outputs from it.
+struct BeamOpInput {
+  enum Layout { PACKED, COMPACT };
+  Tmp t;
+  int32_t* ids = nullptr; float* lp = nullptr; UttPlan* plan = nullptr; int32_t* m_dev = nullptr;
+  HotTrie trie;
+  NgramLm lm;
+  int max_len = 1;                    // the longest sequence's rows, at least 1
+  BeamOpInput(const char* who, const char* lm_who, const char* unit, const int32_t* cand_id, const float* cand_lp, int topk, const int32_t* lens, int n, Layout layout,
+              const int32_t* streams, int blank_id, const TrieArrays& tr, const LmImage& model) {
+    if (model.words) {
+      const int vocab = model.n_words >= NGRAM_LM_HEADER ? model.words[3] : 0;
+      ngram_lm_validate(model.words, model.n_words, vocab, blank_id, model.alpha, model.beta, model.oov, lm_who);
+      int64_t n_rows = 0;
+      for (int i = 0; i < n; ++i) n_rows += lens[i];
+      for (int64_t i = 0; i < n_rows * topk; ++i)
+        ASR_REQUIRE(cand_lp[i] == -INFINITY || (cand_id[i] >= 0 && cand_id[i] < vocab), "%s: candidate %d outside the model's vocabulary of %d", lm_who, cand_id[i], vocab);
     }
     asr_require_device(0);
-    Tmp t;
-    PackedPlan pp(seq_lens, batch);
-    int max_T = 1;
-    std::vector<int32_t> ids((size_t)pp.Mpad * topk, 0);
-    std::vector<float> lp((size_t)pp.Mpad * topk, 0.0f);
-    size_t r = 0;
-    for (int b = 0; b < batch; ++b) {
-      const size_t n = (size_t)seq_lens[b] * topk;
-      for (int q = 0; q < seq_lens[b]; ++q)
-        for (int i = 0; i < topk; ++i)
-          for (int j = 0; j < i; ++j)
-            ASR_REQUIRE(cand_id[(r + q) * topk + i] != cand_id[(r + q) * topk + j], "op_ctc_prefix_beam: utterance %d row %d lists token %d twice", b, q, cand_id[(r + q) * topk + i]);
-      memcpy(&ids[(size_t)pp.plan[b].row_off * topk], cand_id + r * topk, n * 4);
-      memcpy(&lp[(size_t)pp.plan[b].row_off * topk], cand_logprob + r * topk, n * 4);
-      r += seq_lens[b];
-      max_T = std::max(max_T, seq_lens[b]);
+    std::vector<UttPlan> hplan;
+    int rows = 0;
+    if (layout == PACKED) {
+      PackedPlan pp(lens, n);
+      hplan = pp.plan; rows = pp.Mpad;
+    } else {
+      hplan.resize(n);
+      for (int i = 0; i < n; ++i) {
+        memset(&hplan[i], 0, sizeof(UttPlan));
+        hplan[i].n_lfr = lens[i]; hplan[i].T = std::max(lens[i], 1); hplan[i].row_off = rows; hplan[i].lang = streams ? streams[i] : 0;
+        rows += round_up(hplan[i].T, 16);
+      }
     }
-    int32_t* dids = (int32_t*)t.alloc(ids.size() * 4);
-    float* dlp = (float*)t.alloc(lp.size() * 4);
-    UttPlan* dplan = (UttPlan*)t.alloc(sizeof(UttPlan) * batch);
-    HIP_CHECK(hipMemcpy(dids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dlp, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dplan, pp.plan.data(), sizeof(UttPlan) * batch, hipMemcpyHostToDevice));
-    const HotTrie trie = upload_trie(t, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost);
-    const int pool_stride = max_T * beam;
+    std::vector<int32_t> hids((size_t)rows * topk, 0);
+    std::vector<float> hlp((size_t)rows * topk, 0.0f);
+    size_t r = 0;
+    for (int i = 0; i < n; ++i) {
+      for (int q = 0; q < lens[i]; ++q)
+        for (int a = 0; a < topk; ++a)
+          for (int c = 0; c < a; ++c)
+            ASR_REQUIRE(cand_id[(r + q) * topk + a] != cand_id[(r + q) * topk + c], "%s: %s %d row %d lists token %d twice", who, unit, i, q, cand_id[(r + q) * topk + a]);
+      memcpy(&hids[(size_t)hplan[i].row_off * topk], cand_id + r * topk, (size_t)lens[i] * topk * 4);
+      memcpy(&hlp[(size_t)hplan[i].row_off * topk], cand_lp + r * topk, (size_t)lens[i] * topk * 4);
+      r += lens[i];
+      max_len = std::max(max_len, lens[i]);
+    }
+    ids = (int32_t*)t.alloc(hids.size() * 4);
+    lp = (float*)t.alloc(hlp.size() * 4);
+    plan = (UttPlan*)t.alloc(sizeof(UttPlan) * n);
+    HIP_CHECK(hipMemcpy(ids, hids.data(), hids.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(lp, hlp.data(), hlp.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(plan, hplan.data(), sizeof(UttPlan) * n, hipMemcpyHostToDevice));
+    if (layout == COMPACT) {
+      m_dev = (int32_t*)t.alloc(4);
+      HIP_CHECK(hipMemcpy(m_dev, &rows, 4, hipMemcpyHostToDevice));
+    }
+    trie = upload_trie(t, tr);
+    if (model.words) {
+      int32_t* dlm = (int32_t*)t.alloc((size_t)model.n_words * 4);
+      HIP_CHECK(hipMemcpy(dlm, model.words, (size_t)model.n_words * 4, hipMemcpyHostToDevice));
+      lm = ngram_lm_view(dlm, model.words, model.alpha, model.beta, model.oov);
+    }
+  }
+};
+
+// both host-array entries of the search; lm.words null: without a language model
+int op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id, const TrieArrays& tr, int beam, int nbest,
+                       int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score, const LmImage& lm) {
+  return asr_guard([&] {
+    ASR_REQUIRE(cand_id && cand_logprob && seq_lens && token_ids && num_id && score && ctc_score && batch > 0 && max_tokens > 0, "op_ctc_prefix_beam: bad argument");
+    ASR_REQUIRE(topk >= 1 && topk <= TOKEN_BEAM_MAX && beam >= 1 && beam <= TOKEN_BEAM_MAX && nbest >= 1 && nbest <= beam,
+                "op_ctc_prefix_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)", beam, topk, nbest);
+    require_trie("op_ctc_prefix_beam", tr, blank_id);
+    BeamOpInput in("op_ctc_prefix_beam", "op_ctc_prefix_beam_lm", "utterance", cand_id, cand_logprob, topk, seq_lens, batch, BeamOpInput::PACKED, nullptr, blank_id, tr, lm);
+    Tmp& t = in.t;
+    const int pool_stride = in.max_len * beam;
     int2* dpool = (int2*)t.alloc((size_t)batch * pool_stride * sizeof(int2));
     const size_t hyps = (size_t)batch * nbest;
     int32_t* dtok = (int32_t*)t.alloc(hyps * max_tokens * 4);
     int32_t* dnum = (int32_t*)t.alloc(hyps * 4);
     float* dsc = (float*)t.alloc(hyps * 4);
     float* dctc = (float*)t.alloc(hyps * 4);
-    NgramLm lm;
-    if (lm_image) {
-      int32_t* dlm = (int32_t*)t.alloc((size_t)lm_words * 4);
-      HIP_CHECK(hipMemcpy(dlm, lm_image, (size_t)lm_words * 4, hipMemcpyHostToDevice));
-      lm = ngram_lm_view(dlm, lm_image, alpha, beta, oov_logprob);
-    }
-    launch_ctc_prefix_beam(dids, dlp, topk, dplan, batch, blank_id, beam, nbest, trie, dpool, pool_stride, dtok, max_tokens, dnum, dsc, dctc, nullptr, &lm);
+    launch_ctc_prefix_beam(in.ids, in.lp, topk, in.plan, batch, blank_id, beam, nbest, in.trie, dpool, pool_stride, dtok, max_tokens, dnum, dsc, dctc, nullptr, &in.lm);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(token_ids, dtok, hyps * max_tokens * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(num_id, dnum, hyps * 4, hipMemcpyDeviceToHost));
@@ -562,8 +597,8 @@ extern "C" int asr_op_ctc_prefix_beam(const int32_t* cand_id, const float* cand_
                                       const int32_t* trie_depth, const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok,
                                       const int32_t* trie_child_node, int n_nodes, float boost, int beam, int nbest, int32_t* token_ids, int max_tokens,
                                       int32_t* num_id, float* score, float* ctc_score) {
-  return op_ctc_prefix_beam(cand_id, cand_logprob, topk, seq_lens, batch, blank_id, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost,
-                            beam, nbest, token_ids, max_tokens, num_id, score, ctc_score, nullptr, 0, 0.0f, 0.0f, 0.0f);
+  return op_ctc_prefix_beam(cand_id, cand_logprob, topk, seq_lens, batch, blank_id, TrieArrays{trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost},
+                            beam, nbest, token_ids, max_tokens, num_id, score, ctc_score, LmImage{nullptr, 0, 0.0f, 0.0f, 0.0f});
 }
 
 extern "C" int asr_op_ctc_prefix_beam_lm(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, int blank_id,
@@ -572,65 +607,26 @@ extern "C" int asr_op_ctc_prefix_beam_lm(const int32_t* cand_id, const float* ca
                                          int32_t* num_id, float* score, float* ctc_score, const int32_t* lm_image, int64_t lm_words, float alpha, float beta,
                                          float oov_logprob) {
   if (!lm_image) return asr_guard([&] { ASR_REQUIRE(false, "op_ctc_prefix_beam_lm: no language model image"); });
-  return op_ctc_prefix_beam(cand_id, cand_logprob, topk, seq_lens, batch, blank_id, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost,
-                            beam, nbest, token_ids, max_tokens, num_id, score, ctc_score, lm_image, lm_words, alpha, beta, oov_logprob);
+  return op_ctc_prefix_beam(cand_id, cand_logprob, topk, seq_lens, batch, blank_id, TrieArrays{trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost},
+                            beam, nbest, token_ids, max_tokens, num_id, score, ctc_score, LmImage{lm_image, lm_words, alpha, beta, oov_logprob});
 }
 
-// The beam search over token rows on host arrays. The rows go up in the layout of the compact token plan (16-row aligned per sequence, an empty sequence keeps
-// one dummy row), with the total row count on the device, as the Paraformer session hands them to the kernel.
+// The beam search over token rows on host arrays (the rows in the compact token plan's layout: BeamOpInput).
 extern "C" int asr_op_nar_beam(const int32_t* cand_id, const float* cand_logprob, int topk, const int32_t* seq_lens, int batch, const int32_t* trie_depth,
                                const int32_t* trie_is_end, const int32_t* trie_child_off, const int32_t* trie_child_tok, const int32_t* trie_child_node, int n_nodes,
                                float boost, const int32_t* lm_image, int64_t lm_words, float alpha, float beta, float oov_logprob, int beam, int nbest,
                                int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* am_score, float* token_logprob) {
   return asr_guard([&] {
     ASR_REQUIRE(cand_id && cand_logprob && seq_lens && token_ids && num_id && score && am_score && batch > 0 && max_tokens > 0, "op_nar_beam: bad argument");
-    ASR_REQUIRE(topk >= 1 && topk <= 16 && beam >= 1 && beam <= 16 && nbest >= 1 && nbest <= beam, "op_nar_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)", beam, topk,
-                nbest);
-    require_trie("op_nar_beam", trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, -1);
-    int64_t n_rows = 0;
-    for (int b = 0; b < batch; ++b) {
-      ASR_REQUIRE(seq_lens[b] >= 0, "op_nar_beam: sequence %d has %d rows", b, seq_lens[b]);
-      n_rows += seq_lens[b];
-    }
-    if (lm_image) {                                      // the image ("no blank"), then every id the walk will look up
-      ngram_lm_validate(lm_image, lm_words, lm_words >= NGRAM_LM_HEADER ? lm_image[3] : 0, -1, alpha, beta, oov_logprob, "op_nar_beam");
-      for (int64_t i = 0; i < n_rows * topk; ++i)
-        ASR_REQUIRE(cand_logprob[i] == -INFINITY || (cand_id[i] >= 0 && cand_id[i] < lm_image[3]), "op_nar_beam: candidate %d outside the model's vocabulary of %d", cand_id[i],
-                    lm_image[3]);
-    }
-    asr_require_device(0);
-    Tmp t;
-    std::vector<UttPlan> plan(batch);
-    int rows = 0, max_N = 1;
-    for (int b = 0; b < batch; ++b) {
-      memset(&plan[b], 0, sizeof(UttPlan));
-      plan[b].n_lfr = seq_lens[b]; plan[b].T = std::max(seq_lens[b], 1); plan[b].row_off = rows;
-      rows += round_up(plan[b].T, 16);
-      max_N = std::max(max_N, seq_lens[b]);
-    }
-    std::vector<int32_t> ids((size_t)rows * topk, 0);
-    std::vector<float> lp((size_t)rows * topk, 0.0f);
-    size_t r = 0;
-    for (int b = 0; b < batch; ++b) {
-      const size_t n = (size_t)seq_lens[b] * topk;
-      for (int q = 0; q < seq_lens[b]; ++q)
-        for (int i = 0; i < topk; ++i)
-          for (int j = 0; j < i; ++j)
-            ASR_REQUIRE(cand_id[(r + q) * topk + i] != cand_id[(r + q) * topk + j], "op_nar_beam: sequence %d row %d lists token %d twice", b, q, cand_id[(r + q) * topk + i]);
-      memcpy(&ids[(size_t)plan[b].row_off * topk], cand_id + r * topk, n * 4);
-      memcpy(&lp[(size_t)plan[b].row_off * topk], cand_logprob + r * topk, n * 4);
-      r += seq_lens[b];
-    }
-    int32_t* dids = (int32_t*)t.alloc(ids.size() * 4);
-    float* dlp = (float*)t.alloc(lp.size() * 4);
-    UttPlan* dplan = (UttPlan*)t.alloc(sizeof(UttPlan) * batch);
-    int32_t* dm = (int32_t*)t.alloc(4);
-    HIP_CHECK(hipMemcpy(dids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dlp, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dplan, plan.data(), sizeof(UttPlan) * batch, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dm, &rows, 4, hipMemcpyHostToDevice));
-    const HotTrie trie = upload_trie(t, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost);
-    const int pool_stride = max_N * beam;
+    ASR_REQUIRE(topk >= 1 && topk <= TOKEN_BEAM_MAX && beam >= 1 && beam <= TOKEN_BEAM_MAX && nbest >= 1 && nbest <= beam,
+                "op_nar_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)", beam, topk, nbest);
+    const TrieArrays tr{trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost};
+    require_trie("op_nar_beam", tr, -1);
+    for (int b = 0; b < batch; ++b) ASR_REQUIRE(seq_lens[b] >= 0, "op_nar_beam: sequence %d has %d rows", b, seq_lens[b]);
+    BeamOpInput in("op_nar_beam", "op_nar_beam", "sequence", cand_id, cand_logprob, topk, seq_lens, batch, BeamOpInput::COMPACT, nullptr, -1, tr,
+                   LmImage{lm_image, lm_words, alpha, beta, oov_logprob});
+    Tmp& t = in.t;
+    const int pool_stride = in.max_len * beam;
     int2* dpool = (int2*)t.alloc((size_t)batch * pool_stride * sizeof(int2));
     const size_t hyps = (size_t)batch * nbest;
     int32_t* dtok = (int32_t*)t.alloc(hyps * max_tokens * 4);
@@ -638,13 +634,7 @@ extern "C" int asr_op_nar_beam(const int32_t* cand_id, const float* cand_logprob
     int32_t* dnum = (int32_t*)t.alloc(hyps * 4);
     float* dsc = (float*)t.alloc(hyps * 4);
     float* dam = (float*)t.alloc(hyps * 4);
-    NgramLm lm;
-    if (lm_image) {
-      int32_t* dlm = (int32_t*)t.alloc((size_t)lm_words * 4);
-      HIP_CHECK(hipMemcpy(dlm, lm_image, (size_t)lm_words * 4, hipMemcpyHostToDevice));
-      lm = ngram_lm_view(dlm, lm_image, alpha, beta, oov_logprob);
-    }
-    launch_nar_beam(dids, dlp, topk, dplan, dm, batch, beam, nbest, trie, dpool, pool_stride, dtok, max_tokens, dnum, dsc, dam, dtlp, nullptr, &lm);
+    launch_nar_beam(in.ids, in.lp, topk, in.plan, in.m_dev, batch, beam, nbest, in.trie, dpool, pool_stride, dtok, max_tokens, dnum, dsc, dam, dtlp, nullptr, &in.lm);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(token_ids, dtok, hyps * max_tokens * 4, hipMemcpyDeviceToHost));
     if (token_logprob) HIP_CHECK(hipMemcpy(token_logprob, dtlp, hyps * max_tokens * 4, hipMemcpyDeviceToHost));
@@ -658,7 +648,7 @@ extern "C" int asr_op_nar_beam(const int32_t* cand_id, const float* cand_logprob
 // is stream slot_stream[i] with slot_rows[i] rows (in slot order in cand_id / cand_logprob) and the flag slot_final[i]. The rows go up in the compact token
 // plan's layout, as asr_op_nar_beam sends them. state_io (nullable: every stream starts cleared) holds every stream's state before the call and after it.
 extern "C" int asr_nar_stream_beam_state_words(int beam, int pend_cap) {
-  if (beam < 1 || beam > 16 || pend_cap < 1 || pend_cap > NAR_STREAM_PEND_MAX) return -1;
+  if (beam < 1 || beam > TOKEN_BEAM_MAX || pend_cap < 1 || pend_cap > NAR_STREAM_PEND_MAX) return -1;
   return nar_stream_beam_state_words(beam, pend_cap);
 }
 
@@ -670,12 +660,14 @@ extern "C" int asr_op_nar_stream_beam(const int32_t* cand_id, const float* cand_
                                       int32_t* commit_num, int32_t* pend_ids, float* pend_logprob, int32_t* pend_num, float* pend_score, float* pend_am,
                                       int32_t* total) {
   return asr_guard([&] {
+    namespace S = nar_stream_state;
     ASR_REQUIRE(cand_id && cand_logprob && step_off && slot_stream && slot_rows && slot_final && commit_ids && commit_logprob && commit_num && pend_ids && pend_logprob &&
                     pend_num && pend_score && pend_am && total && n_streams > 0 && n_steps > 0,
                 "op_nar_stream_beam: bad argument");
-    ASR_REQUIRE(topk >= 1 && topk <= 16 && beam >= 1 && beam <= 16 && nbest >= 1 && nbest <= beam && pend_cap >= 1 && pend_cap <= NAR_STREAM_PEND_MAX,
+    ASR_REQUIRE(topk >= 1 && topk <= TOKEN_BEAM_MAX && beam >= 1 && beam <= TOKEN_BEAM_MAX && nbest >= 1 && nbest <= beam && pend_cap >= 1 && pend_cap <= NAR_STREAM_PEND_MAX,
                 "op_nar_stream_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam), pend_cap %d (1..%d)", beam, topk, nbest, pend_cap, NAR_STREAM_PEND_MAX);
-    require_trie("op_nar_stream_beam", trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, -1);
+    const TrieArrays tr{trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost};
+    require_trie("op_nar_stream_beam", tr, -1);
     const int sw = nar_stream_beam_state_words(beam, pend_cap);
     ASR_REQUIRE(!state_io || state_words == sw, "op_nar_stream_beam: a state of %d words per stream, beam %d and pend_cap %d take %d", state_words, beam, pend_cap, sw);
     ASR_REQUIRE(step_off[0] == 0, "op_nar_stream_beam: step_off[0] = %d", step_off[0]);
@@ -691,65 +683,30 @@ extern "C" int asr_op_nar_stream_beam(const int32_t* cand_id, const float* cand_
         ASR_REQUIRE(slot_rows[i] >= 0, "op_nar_stream_beam: step %d, stream %d has %d rows", s, sid, slot_rows[i]);
         seen[sid] = 1;
         max_rows = std::max(max_rows, slot_rows[i]);
-        if (state_io && state_io[(size_t)sid * sw] > 0) {                // a stream that comes with history: everything the kernel will index with
+        if (state_io && state_io[(size_t)sid * sw + S::L] > 0) {         // a stream that comes with history: everything the kernel will index with
           const int32_t* st = state_io + (size_t)sid * sw;
-          ASR_REQUIRE(st[1] >= 0 && st[1] <= st[0] && st[0] - st[1] <= pend_cap && st[2] >= 1 && st[2] <= beam, "op_nar_stream_beam: stream %d: L %d, C %d, %d live", sid, st[0],
-                      st[1], st[2]);
-          for (int r = 0; r < st[2]; ++r)
-            ASR_REQUIRE(st[4 + 32 + r] >= 0 && st[4 + 32 + r] < std::max(n_nodes, 1) && (!lm_nodes || (st[4 + 64 + r] >= 0 && st[4 + 64 + r] < lm_nodes)),
+          const int L = st[S::L], C = st[S::C], n_live = st[S::N_LIVE];
+          ASR_REQUIRE(C >= 0 && C <= L && L - C <= pend_cap && n_live >= 1 && n_live <= beam, "op_nar_stream_beam: stream %d: L %d, C %d, %d live", sid, L, C, n_live);
+          for (int r = 0; r < n_live; ++r)
+            ASR_REQUIRE(st[S::NODE + r] >= 0 && st[S::NODE + r] < std::max(n_nodes, 1) && (!lm_nodes || (st[S::LMSTATE + r] >= 0 && st[S::LMSTATE + r] < lm_nodes)),
                         "op_nar_stream_beam: stream %d, hypothesis %d: a trie node or model state out of range", sid, r);
+          const int32_t* parent = st + S::ring_parent(beam, pend_cap);
           for (int i2 = 0; i2 < pend_cap * beam; ++i2)
-            ASR_REQUIRE(st[4 + 80 + i2] >= 0 && st[4 + 80 + i2] < beam, "op_nar_stream_beam: stream %d: ring parent %d", sid, st[4 + 80 + i2]);
+            ASR_REQUIRE(parent[i2] >= 0 && parent[i2] < beam, "op_nar_stream_beam: stream %d: ring parent %d", sid, parent[i2]);
         }
       }
     }
     const int n_slots = step_off[n_steps];
     ASR_REQUIRE(commit_cap >= pend_cap + max_rows, "op_nar_stream_beam: commit_cap %d, pend_cap + the longest step is %d", commit_cap, pend_cap + max_rows);
-    int64_t n_rows = 0;
-    for (int i = 0; i < n_slots; ++i) n_rows += slot_rows[i];
-    if (lm_image) {                                      // the image ("no blank"), then every id the walk will look up
-      ngram_lm_validate(lm_image, lm_words, lm_words >= NGRAM_LM_HEADER ? lm_image[3] : 0, -1, alpha, beta, oov_logprob, "op_nar_stream_beam");
-      for (int64_t i = 0; i < n_rows * topk; ++i)
-        ASR_REQUIRE(cand_logprob[i] == -INFINITY || (cand_id[i] >= 0 && cand_id[i] < lm_image[3]), "op_nar_stream_beam: candidate %d outside the model's vocabulary of %d",
-                    cand_id[i], lm_image[3]);
-    }
-    asr_require_device(0);
-    Tmp t;
-    std::vector<UttPlan> plan(n_slots);
-    int rows = 0;
-    for (int i = 0; i < n_slots; ++i) {
-      memset(&plan[i], 0, sizeof(UttPlan));
-      plan[i].n_lfr = slot_rows[i]; plan[i].T = std::max(slot_rows[i], 1); plan[i].row_off = rows; plan[i].lang = slot_stream[i];
-      rows += round_up(plan[i].T, 16);
-    }
-    std::vector<int32_t> ids((size_t)rows * topk, 0);
-    std::vector<float> lp((size_t)rows * topk, 0.0f);
-    size_t r = 0;
-    for (int i = 0; i < n_slots; ++i) {
-      const size_t n = (size_t)slot_rows[i] * topk;
-      for (int q = 0; q < slot_rows[i]; ++q)
-        for (int a = 0; a < topk; ++a)
-          for (int c = 0; c < a; ++c)
-            ASR_REQUIRE(cand_id[(r + q) * topk + a] != cand_id[(r + q) * topk + c], "op_nar_stream_beam: slot %d row %d lists token %d twice", i, q, cand_id[(r + q) * topk + a]);
-      memcpy(&ids[(size_t)plan[i].row_off * topk], cand_id + r * topk, n * 4);
-      memcpy(&lp[(size_t)plan[i].row_off * topk], cand_logprob + r * topk, n * 4);
-      r += slot_rows[i];
-    }
-    int32_t* dids = (int32_t*)t.alloc(ids.size() * 4);
-    float* dlp = (float*)t.alloc(lp.size() * 4);
-    UttPlan* dplan = (UttPlan*)t.alloc(sizeof(UttPlan) * n_slots);
-    int32_t* dm = (int32_t*)t.alloc(4);
+    BeamOpInput in("op_nar_stream_beam", "op_nar_stream_beam", "slot", cand_id, cand_logprob, topk, slot_rows, n_slots, BeamOpInput::COMPACT, slot_stream, -1, tr,
+                   LmImage{lm_image, lm_words, alpha, beta, oov_logprob});
+    Tmp& t = in.t;
     int32_t* dfinal = (int32_t*)t.alloc((size_t)n_slots * 4);
     const size_t state_bytes = (size_t)n_streams * sw * 4;
     int32_t* dstate = (int32_t*)t.alloc(state_bytes);
-    HIP_CHECK(hipMemcpy(dids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dlp, lp.data(), lp.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dplan, plan.data(), sizeof(UttPlan) * n_slots, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dm, &rows, 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dfinal, slot_final, (size_t)n_slots * 4, hipMemcpyHostToDevice));
     if (state_io) HIP_CHECK(hipMemcpy(dstate, state_io, state_bytes, hipMemcpyHostToDevice));
     else HIP_CHECK(hipMemset(dstate, 0, state_bytes));
-    const HotTrie trie = upload_trie(t, trie_depth, trie_is_end, trie_child_off, trie_child_tok, trie_child_node, n_nodes, boost);
     const size_t hyps = (size_t)n_slots * nbest, n_commit = (size_t)n_slots * commit_cap;
     NarStreamOut o;
     o.commit_ids = (int32_t*)t.alloc(n_commit * 4); o.commit_lp = (float*)t.alloc(n_commit * 4); o.commit_cap = commit_cap;
@@ -762,19 +719,14 @@ extern "C" int asr_op_nar_stream_beam(const int32_t* cand_id, const float* cand_
     HIP_CHECK(hipMemcpy(o.commit_lp, commit_logprob, n_commit * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(o.pend_ids, pend_ids, hyps * pend_cap * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(o.pend_lp, pend_logprob, hyps * pend_cap * 4, hipMemcpyHostToDevice));
-    NgramLm lm;
-    if (lm_image) {
-      int32_t* dlm = (int32_t*)t.alloc((size_t)lm_words * 4);
-      HIP_CHECK(hipMemcpy(dlm, lm_image, (size_t)lm_words * 4, hipMemcpyHostToDevice));
-      lm = ngram_lm_view(dlm, lm_image, alpha, beta, oov_logprob);
-    }
     for (int s = 0; s < n_steps; ++s) {
       const size_t at = step_off[s];
       NarStreamOut so = o;
       so.commit_ids += at * commit_cap; so.commit_lp += at * commit_cap; so.commit_num += at;
       so.pend_ids += at * nbest * pend_cap; so.pend_lp += at * nbest * pend_cap; so.pend_num += at * nbest; so.pend_score += at * nbest; so.pend_am += at * nbest;
       so.total += at;
-      launch_nar_stream_beam(dids, dlp, topk, dplan + at, dm, dfinal + at, step_off[s + 1] - step_off[s], beam, nbest, pend_cap, trie, dstate, sw, so, nullptr, &lm);
+      launch_nar_stream_beam(in.ids, in.lp, topk, in.plan + at, in.m_dev, dfinal + at, step_off[s + 1] - step_off[s], beam, nbest, pend_cap, in.trie, dstate, sw, so, nullptr,
+                             &in.lm);
     }
     HIP_CHECK(hipDeviceSynchronize());
     if (state_io) HIP_CHECK(hipMemcpy(state_io, dstate, state_bytes, hipMemcpyDeviceToHost));

@@ -3,13 +3,10 @@
 // ctc_prefix_beam_kernel runs the search, one workgroup per utterance. The float64 statement of the search is tests/ctc_beam_ref.py; with a back-off n-gram
 // language model fused in (the kLm instantiation) it is tests/ctc_lm_ref.py.
 #include <map>
-#include <type_traits>
 
+#include "beam_dev.h"
 #include "ctc_dev.h"
 #include "engine.h"
-#include "hot_trie.h"
-#include "kernels.h"
-#include "ngram_lm.h"
 
 namespace {
 
@@ -100,8 +97,7 @@ __global__ __launch_bounds__(64 * TOPK_ROWS) void ctc_topk_kernel(const T* __res
 }
 
 // ---- search --------------------------------------------------------------------------------------------------------------------------------------
-constexpr int CTC_BEAM_MAX = 16;
-constexpr int CTC_BEAM_THREADS = CTC_BEAM_MAX + CTC_BEAM_MAX * CTC_BEAM_MAX + 48;     // one thread per entry of a frame (16 stays + 256 extensions), rounded up to whole waves
+constexpr int CTC_BEAM_THREADS = TOKEN_BEAM_MAX + TOKEN_BEAM_MAX * TOKEN_BEAM_MAX + 48;     // one thread per entry of a frame (16 stays + 256 extensions), rounded up to whole waves
 
 // identity of a prefix is its content: a 64-bit rolling hash (splitmix64 finaliser over hash * golden + token + 1) beside its length and last token
 __device__ __forceinline__ uint64_t hash_step(uint64_t h, int c) {
@@ -111,18 +107,12 @@ __device__ __forceinline__ uint64_t hash_step(uint64_t h, int c) {
   return z ^ (z >> 31);
 }
 
-template <bool kLm> struct BeamLmState {};
-template <> struct BeamLmState<true> {               // a prefix's language-model total (alpha * logp + beta over its tokens) and state: functions of its content
-  float lm[CTC_BEAM_MAX];
-  int lmstate[CTC_BEAM_MAX];
-};
 template <bool kLm>
-struct BeamLive : BeamLmState<kLm> {  // the live prefixes of one frame, in rank order
-  float pb[CTC_BEAM_MAX], pnb[CTC_BEAM_MAX], bonus[CTC_BEAM_MAX];
-  uint64_t hash[CTC_BEAM_MAX];
-  int len[CTC_BEAM_MAX], last[CTC_BEAM_MAX], pool[CTC_BEAM_MAX], node[CTC_BEAM_MAX];
+struct BeamLive : LmLive<kLm> {       // the live prefixes of one frame, in rank order
+  float pb[TOKEN_BEAM_MAX], pnb[TOKEN_BEAM_MAX], bonus[TOKEN_BEAM_MAX];
+  uint64_t hash[TOKEN_BEAM_MAX];
+  int len[TOKEN_BEAM_MAX], last[TOKEN_BEAM_MAX], pool[TOKEN_BEAM_MAX], node[TOKEN_BEAM_MAX];
 };
-struct NoLm {};
 
 // One workgroup per utterance, sequential over its rows plan[u].row_off .. + T. Entry e of a frame: e < 16 the "stay" of live prefix e (blank, and a repeat of
 // its last token), e = 16 + p * topk + j the extension of live prefix p by candidate column j. An extension that spells a live prefix (same hash, length and
@@ -133,42 +123,40 @@ struct NoLm {};
 // kLm: every prefix also carries lm, the sum of alpha * log P(token | state) + beta over its tokens, and the model's state. Both are functions of the prefix's
 // content, as the bonus is, so merging by content is unchanged: a stay keeps them, an extension walks the image (lm_step) beside the trie, one dependent chain
 // per frame on all extension threads at once. The ranking score gains + lm; at the end a prefix adds alpha * log P(</s> | state) when the model lists </s>.
+// This search fuses its LM terms, fmaf(alpha, logp, beta) and fmaf(alpha, logp(</s>), lm): the NAR searches (beam_dev.h: lm_extend) round the product first.
 // Candidate ids must lie in [0, vocab) of the image. The kLm = false instantiation is the search without a model: the instructions it had, the
 // arguments behind the (empty) model argument 8 bytes further on.
 template <bool kLm>
 __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const int32_t* __restrict__ cand_id, const float* __restrict__ cand_lp, int topk,
                                                                        const UttPlan* __restrict__ plan, int blank, int beam, int nbest, HotTrie tr,
-                                                                       typename std::conditional<kLm, NgramLm, NoLm>::type lmod,
-                                                                       int2* __restrict__ pool_all, int pool_stride, int32_t* __restrict__ tok_out, int max_tokens,
+                                                                       LmArg<kLm> lmod, int2* __restrict__ pool_all, int pool_stride,
+                                                                       int32_t* __restrict__ tok_out, int max_tokens,
                                                                        int32_t* __restrict__ num_out, float* __restrict__ score_out, float* __restrict__ ctc_out) {
   __shared__ BeamLive<kLm> live[2];
-  __shared__ float s_pb[CTC_BEAM_MAX], s_pnb[CTC_BEAM_MAX], e_score[CTC_BEAM_MAX + CTC_BEAM_MAX * CTC_BEAM_MAX];
-  __shared__ int c_id[CTC_BEAM_MAX], n_valid_entries, f_order[CTC_BEAM_MAX];
-  __shared__ float c_lp[CTC_BEAM_MAX], f_score[CTC_BEAM_MAX], f_ctc[CTC_BEAM_MAX];
+  __shared__ float s_pb[TOKEN_BEAM_MAX], s_pnb[TOKEN_BEAM_MAX], e_score[TOKEN_BEAM_MAX + TOKEN_BEAM_MAX * TOKEN_BEAM_MAX];
+  __shared__ int c_id[TOKEN_BEAM_MAX], n_valid_entries, f_order[TOKEN_BEAM_MAX];
+  __shared__ float c_lp[TOKEN_BEAM_MAX], f_score[TOKEN_BEAM_MAX], f_ctc[TOKEN_BEAM_MAX];
   const int u = blockIdx.x, e = threadIdx.x;
   const int T = plan[u].T, row0 = plan[u].row_off;
   int2* pool = pool_all + (size_t)u * pool_stride;
-  constexpr int N_ENT = CTC_BEAM_MAX + CTC_BEAM_MAX * CTC_BEAM_MAX;
+  constexpr int N_ENT = TOKEN_BEAM_MAX + TOKEN_BEAM_MAX * TOKEN_BEAM_MAX;
   if (e == 0) {
     live[0].pb[0] = 0.0f; live[0].pnb[0] = -INFINITY; live[0].bonus[0] = 0.0f; live[0].hash[0] = 0; live[0].len[0] = 0; live[0].last[0] = -1;
     live[0].pool[0] = -1; live[0].node[0] = 0;
     if constexpr (kLm) { live[0].lm[0] = 0.0f; live[0].lmstate[0] = lmod.start_node; }
   }
   int n_live = 1;
-  int nx_id = 0; float nx_lp = 0.0f;                    // the next row's candidate of this thread (threads < topk), fetched a frame ahead
-  if (e < topk && T > 0) { nx_id = cand_id[(size_t)row0 * topk + e]; nx_lp = cand_lp[(size_t)row0 * topk + e]; }
+  int nx_id = 0; float nx_lp = 0.0f;
+  cand_fetch(cand_id, cand_lp, topk, row0, T > 0, nx_id, nx_lp);
   for (int t = 0; t < T; ++t) {
     const BeamLive<kLm>& cur = live[t & 1];
     BeamLive<kLm>& nxt = live[(t + 1) & 1];
-    if (e < topk) {
-      c_id[e] = nx_id; c_lp[e] = nx_lp;
-      if (t + 1 < T) { nx_id = cand_id[(size_t)(row0 + t + 1) * topk + e]; nx_lp = cand_lp[(size_t)(row0 + t + 1) * topk + e]; }
-    }
+    cand_advance(cand_id, cand_lp, topk, row0 + t + 1, t + 1 < T, nx_id, nx_lp, c_id, c_lp);
     if (e == 0) n_valid_entries = 0;
     __syncthreads();
     // 1. every entry's own contribution
-    const bool is_stay = e < CTC_BEAM_MAX;
-    const int x = e - CTC_BEAM_MAX;
+    const bool is_stay = e < TOKEN_BEAM_MAX;
+    const int x = e - TOKEN_BEAM_MAX;
     const int p = is_stay ? e : x / topk, j = is_stay ? 0 : x % topk;
     bool active = e < N_ENT && p < n_live;
     float val = -INFINITY, nb_bonus = 0.0f;
@@ -217,7 +205,7 @@ __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const
       if constexpr (kLm) {
         nstate = cur.lmstate[p];
         const float lp = lm_step(lmod, nstate, c);
-        nlm = cur.lm[p] + (lmod.alpha * lp + lmod.beta);
+        nlm = cur.lm[p] + fmaf(lmod.alpha, lp, lmod.beta);
         sc += nlm;
       }
     }
@@ -227,7 +215,9 @@ __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const
     __syncthreads();
     // 4. rank by (score descending, entry ascending); the best `beam` are the next frame's live prefixes
     if (active) {
-      const int n_ent = CTC_BEAM_MAX + n_live * topk;
+      // beam_rank's rule, written in place: through the helper this one loop leaves the compiler short of scalar registers for the constants of lae in
+      // the steps above, which it then reloads per use (measured 2 % on the kernel with a model)
+      const int n_ent = TOKEN_BEAM_MAX + n_live * topk;
       int rank = 0;
       for (int q = 0; q < n_ent; ++q) {
         const float o = e_score[q];
@@ -255,24 +245,18 @@ __global__ __launch_bounds__(CTC_BEAM_THREADS) void ctc_prefix_beam_kernel(const
   // (kLm) + lm, which gains alpha * log P(</s> | state) when the model lists </s>
   const BeamLive<kLm>& fin = live[T & 1];
   if (e < n_live) {
-    float bonus = fin.bonus[e];
-    if (tr.n_nodes > 1 && fin.node[e] != 0) bonus -= (float)tr.depth[fin.node[e]] * tr.boost;
+    const float bonus = beam_end_bonus(tr, fin.bonus[e], fin.node[e]);
     const float ctc = lae(fin.pb[e], fin.pnb[e]);
     float sc = ctc + bonus;
     if constexpr (kLm) {
       float lm = fin.lm[e];
-      if (lmod.eos >= 0) { int st = fin.lmstate[e]; lm += lmod.alpha * lm_step(lmod, st, lmod.eos); }
+      if (lmod.eos >= 0) { int st = fin.lmstate[e]; lm = fmaf(lmod.alpha, lm_step(lmod, st, lmod.eos), lm); }
       sc += lm;
     }
     f_ctc[e] = ctc; f_score[e] = sc;
   }
   __syncthreads();
-  if (e < n_live) {
-    const float sc = f_score[e];
-    int rank = 0;
-    for (int q = 0; q < n_live; ++q) rank += (f_score[q] > sc || (f_score[q] == sc && q < e)) ? 1 : 0;
-    f_order[rank] = e;
-  }
+  beam_final_order(f_score, n_live, f_order);
   __syncthreads();
   if (e < nbest) {
     const size_t o = (size_t)u * nbest + e;
@@ -312,15 +296,13 @@ template void launch_ctc_topk<bf16_t>(const bf16_t*, int, const bf16_t*, int, co
 void launch_ctc_prefix_beam(const int32_t* cand_id, const float* cand_lp, int topk, const UttPlan* plan, int n_utts, int blank_id, int beam, int nbest,
                             const HotTrie& trie, int2* pool, int pool_stride, int32_t* token_ids, int max_tokens, int32_t* num_id, float* score, float* ctc_score,
                             hipStream_t s, const NgramLm* lm) {
-  ASR_REQUIRE(beam >= 1 && beam <= CTC_BEAM_MAX && topk >= 1 && topk <= CTC_BEAM_MAX && nbest >= 1 && nbest <= beam, "ctc_prefix_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)",
+  ASR_REQUIRE(beam >= 1 && beam <= TOKEN_BEAM_MAX && topk >= 1 && topk <= TOKEN_BEAM_MAX && nbest >= 1 && nbest <= beam, "ctc_prefix_beam: beam %d, topk %d, nbest %d (1..16, nbest <= beam)",
               beam, topk, nbest);
   ASR_REQUIRE(n_utts > 0 && max_tokens >= 1 && pool && pool_stride >= beam, "ctc_prefix_beam: bad argument");
-  if (lm && lm->n_nodes > 0)
-    hipLaunchKernelGGL(ctc_prefix_beam_kernel<true>, dim3(n_utts), dim3(CTC_BEAM_THREADS), 0, s, cand_id, cand_lp, topk, plan, blank_id, beam, nbest, trie, *lm, pool,
-                       pool_stride, token_ids, max_tokens, num_id, score, ctc_score);
-  else
-    hipLaunchKernelGGL(ctc_prefix_beam_kernel<false>, dim3(n_utts), dim3(CTC_BEAM_THREADS), 0, s, cand_id, cand_lp, topk, plan, blank_id, beam, nbest, trie, NoLm{}, pool,
-                       pool_stride, token_ids, max_tokens, num_id, score, ctc_score);
+  launch_with_lm(lm, [&](auto k_lm, const auto& lmod) {
+    hipLaunchKernelGGL(ctc_prefix_beam_kernel<decltype(k_lm)::value>, dim3(n_utts), dim3(CTC_BEAM_THREADS), 0, s, cand_id, cand_lp, topk, plan, blank_id, beam, nbest, trie, lmod,
+                       pool, pool_stride, token_ids, max_tokens, num_id, score, ctc_score);
+  });
   HIP_CHECK(hipGetLastError());
 }
 

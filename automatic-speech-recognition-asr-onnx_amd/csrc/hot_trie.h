@@ -1,5 +1,6 @@
-// Device-side walk of the hotword context graph (kernels.h: HotTrie), shared by the CTC prefix beam search (ctc_beam.hip), the hotword kernels of the
-// autoregressive decoders (hotword.hip) and the beam ranker's node hand-over (kernels.hip). The float64 statement is tests/ctc_beam_ref.py: trie_step.
+// Device-side walk of the hotword context graph (kernels.h: HotTrie), shared by the three token-synchronous beam searches through beam_dev.h (ctc_beam.hip,
+// nar_beam.hip, nar_stream_beam.hip), the hotword kernels of the autoregressive decoders (hotword.hip), their LM re-rank (decoder_lm.hip) and the beam ranker's
+// node hand-over (kernels.hip). The float64 statement is tests/ctc_beam_ref.py: trie_step.
 #pragma once
 #include "kernels.h"
 

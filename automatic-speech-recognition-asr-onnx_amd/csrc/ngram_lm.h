@@ -1,5 +1,7 @@
-// Back-off n-gram language model of the CTC prefix beam search (ctc_beam.hip): the image's layout, its host-side check and the device-side
-// walk. The float64 statement is tests/ctc_lm_ref.py: build_image / lm_step.
+// Back-off n-gram language model: the image's layout, its host-side check and the device-side walk. Its users: the three token-synchronous
+// beam searches through beam_dev.h (ctc_beam.hip, nar_beam.hip, nar_stream_beam.hip), the autoregressive decoders' selection head and beam ranker
+// (decoder_lm.hip, kernels.hip; the end of this file), the sessions that hold an image (sanm_session.h, decode_head.h) and the host-array entry points
+// (api.hip). The float64 statement is tests/ctc_lm_ref.py: build_image / lm_step.
 //
 // One blob of 32-bit words over token ids, order N in 1..5:
 //   header  [order, n_nodes, n_edges, vocab, start_node, eos_edge_token]

@@ -184,8 +184,7 @@ void SvSession::stream_search(const ResultBlob& out, const UttPlan* token_plan, 
   }
   {
     ProfScope ps(prof, "nar_stream_beam", stream);
-    NgramLm lm;                                           // (no nodes: the search without a model is launched)
-    if (lm_header[1] > 0) lm = ngram_lm_view(d_lm.as<int32_t>(), lm_header, lm_alpha, lm_beta, lm_oov);
+    const NgramLm lm = lm_view();
     NarStreamOut so;
     so.commit_ids = out.dev(lay.commit_ids, d_bout); so.commit_lp = out.dev(lay.commit_logprob, d_bout); so.commit_cap = (int)lay.commit_cap;
     so.commit_num = out.dev(lay.commit_num, d_bout); so.pend_ids = out.dev(lay.pend_ids, d_bout); so.pend_lp = out.dev(lay.pend_logprob, d_bout);

@@ -170,6 +170,9 @@ struct ASR_LOCAL SvSession : asr_session {
   int32_t lm_header[6] = {0, 0, 0, 0, 0, -1};            // n_nodes (word 1) == 0: no model
   float lm_alpha = 0.0f, lm_beta = 0.0f, lm_oov = 0.0f;
   void set_lm(const int32_t* image_words, int64_t n_words, float alpha, float beta, float oov_logprob);
+  NgramLm lm_view() const {     // what the three searches take; without a model it has no nodes, and the search without one is launched
+    return lm_header[1] > 0 ? ngram_lm_view(d_lm.as<int32_t>(), lm_header, lm_alpha, lm_beta, lm_oov) : NgramLm{};
+  }
   // align runs only (asr_sensevoice_align, ctc_align.hip): emissions [rows][ld_em], the backpointer workspace of transcripts too long for LDS, per-utterance
   // scores and status; the spans land in d_first / d_last / d_tlp
   DeviceBuffer d_em, d_abp, d_apath, d_alik, d_astat;

@@ -413,8 +413,7 @@ void SvSession::enqueue(const SvRunCtx& r) {
     }
     {
       ProfScope ps(prof, "ctc_beam", stream);
-      NgramLm lm;                                         // (no nodes: the search without a model is launched)
-      if (lm_header[1] > 0) lm = ngram_lm_view(d_lm.as<int32_t>(), lm_header, lm_alpha, lm_beta, lm_oov);
+      const NgramLm lm = lm_view();
       launch_ctc_prefix_beam(d_cand_i.as<int32_t>(), d_cand_l.as<float>(), r.topk, r.dp, r.batch, c.blank_id, r.beam, r.nbest,
                              hot_trie_view(d_hot.as<int32_t>(), hot_nodes, hot_boost), (int2*)d_pool.ptr, r.pool_stride, o.dev(o.lay.hyp_tokens, d_bout), r.max_tokens,
                              o.dev(o.lay.hyp_counts, d_bout), o.dev(o.lay.hyp_scores, d_bout), o.dev(o.lay.hyp_ctc, d_bout), stream, &lm);
@@ -624,8 +623,7 @@ void SvSession::enqueue_paraformer_tail(const SvRunCtx& r) {
     }
     {
       ProfScope ps(prof, "nar_beam", stream);
-      NgramLm lm;                                         // (no nodes: the search without a model is launched)
-      if (lm_header[1] > 0) lm = ngram_lm_view(d_lm.as<int32_t>(), lm_header, lm_alpha, lm_beta, lm_oov);
+      const NgramLm lm = lm_view();
       launch_nar_beam(d_cand_i.as<int32_t>(), d_cand_l.as<float>(), r.topk, tplan, m_dev, r.batch, r.beam, r.nbest, hot_trie_view(d_hot.as<int32_t>(), hot_nodes, hot_boost),
                       (int2*)d_pool.ptr, r.pool_stride, o.dev(o.lay.hyp_tokens, d_bout), r.max_tokens, o.dev(o.lay.hyp_counts, d_bout), o.dev(o.lay.hyp_scores, d_bout),
                       o.dev(o.lay.hyp_ctc, d_bout), o.dev(o.lay.hyp_logprob, d_bout), stream, &lm);

@@ -273,11 +273,7 @@ class SenseVoiceSession(_Session):
         None clears it. Every token a hypothesis appends adds alpha * log P(token | history) + beta to its ranking score (alpha the LM weight, beta a
         length bonus); a token the model has no unigram for costs oov_logprob (default: the model's <unk>, else 0) and leaves the history alone. A
         malformed image or a bad weight raises AsrError and the model in force stays."""
-        if lm is None:
-            _lib.check(_lib.load().asr_sensevoice_set_lm(self._h, None, 0, 0.0, 0.0, 0.0))
-            return
-        img, oov = _lm_image(lm, self.cfg.vocab, oov_logprob)
-        _lib.check(_lib.load().asr_sensevoice_set_lm(self._h, _ip(img), img.size, float(alpha), float(beta), oov))
+        _lib.check(_lib.load().asr_sensevoice_set_lm(self._h, *_lm_args(lm, self.cfg.vocab, oov_logprob, alpha, beta)))
 
     def run_packed_beam(self, audio, offsets: np.ndarray, language_idx: np.ndarray, beam: int, topk: int | None = None, nbest: int = 1,
                         audio_device_ptr: int | None = None):
@@ -515,6 +511,22 @@ def _lm_image(lm, vocab, oov_logprob):
     return img, float(default if oov_logprob is None else oov_logprob)
 
 
+def _trie_args(trie):
+    """the five trie arrays and the node count as the host-array searches take them (`trie` as hotword_trie returns it; None or a lone root: no hotwords)"""
+    if trie is None or trie["depth"].size <= 1:
+        return [None] * 5 + [0]
+    t = [np.ascontiguousarray(trie[k], dtype=np.int32) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")]
+    return [_ip(a) for a in t] + [int(t[0].size)]
+
+
+def _lm_args(lm, vocab, oov_logprob, alpha, beta):
+    """(image, words, alpha, beta, oov_logprob) as the entry points take a language model (`lm` as _lm_image takes it; None: no model)"""
+    if lm is None:
+        return [None, 0, 0.0, 0.0, 0.0]
+    img, oov = _lm_image(lm, vocab, oov_logprob)
+    return [_ip(img), img.size, float(alpha), float(beta), oov]
+
+
 def op_ctc_prefix_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, blank_id=0, trie=None, boost=0.0, max_tokens=None, lm=None, alpha=0.5, beta=0.0,
                        oov_logprob=None, vocab=None):
     """The CTC prefix beam search on host arrays (asr_op_ctc_prefix_beam): cand_id / cand_logprob [sum T, topk], `trie` as hotword_trie returns it (None:
@@ -529,18 +541,13 @@ def op_ctc_prefix_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, blank_id=
     tok = np.zeros((sl.size, nbest, max_t), dtype=np.int32)
     num = np.zeros((sl.size, nbest), dtype=np.int32)
     score, ctc = np.zeros((sl.size, nbest), dtype=np.float32), np.zeros((sl.size, nbest), dtype=np.float32)
-    if trie is not None and trie["depth"].size > 1:
-        t = {k: np.ascontiguousarray(trie[k], dtype=np.int32) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")}
-        targs, n_nodes = [_ip(t[k]) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")], int(t["depth"].size)
-    else:
-        targs, n_nodes = [None] * 5, 0
+    targs = _trie_args(trie)
     if lm is not None:
-        img, oov = _lm_image(lm, vocab, oov_logprob)
-        _lib.check(_lib.load().asr_op_ctc_prefix_beam_lm(_ip(ids), _fp(lp), ids.shape[1], _ip(sl), sl.size, blank_id, *targs, n_nodes, float(boost), int(beam),
-                                                         int(nbest), _ip(tok), max_t, _ip(num), _fp(score), _fp(ctc), _ip(img), img.size, float(alpha),
-                                                         float(beta), oov))
+        _lib.check(_lib.load().asr_op_ctc_prefix_beam_lm(_ip(ids), _fp(lp), ids.shape[1], _ip(sl), sl.size, blank_id, *targs, float(boost), int(beam),
+                                                         int(nbest), _ip(tok), max_t, _ip(num), _fp(score), _fp(ctc),
+                                                         *_lm_args(lm, vocab, oov_logprob, alpha, beta)))
         return tok, num, score, ctc
-    _lib.check(_lib.load().asr_op_ctc_prefix_beam(_ip(ids), _fp(lp), ids.shape[1], _ip(sl), sl.size, blank_id, *targs, n_nodes, float(boost), int(beam),
+    _lib.check(_lib.load().asr_op_ctc_prefix_beam(_ip(ids), _fp(lp), ids.shape[1], _ip(sl), sl.size, blank_id, *targs, float(boost), int(beam),
                                                   int(nbest), _ip(tok), max_t, _ip(num), _fp(score), _fp(ctc)))
     return tok, num, score, ctc
 
@@ -560,18 +567,10 @@ def op_nar_beam(cand_id, cand_logprob, seq_lens, beam, nbest=1, trie=None, boost
     tlp = np.zeros((sl.size, nbest, max_t), dtype=np.float32)
     num = np.zeros((sl.size, nbest), dtype=np.int32)
     score, am = np.zeros((sl.size, nbest), dtype=np.float32), np.zeros((sl.size, nbest), dtype=np.float32)
-    if trie is not None and trie["depth"].size > 1:
-        t = {k: np.ascontiguousarray(trie[k], dtype=np.int32) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")}
-        targs, n_nodes = [_ip(t[k]) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")], int(t["depth"].size)
-    else:
-        targs, n_nodes = [None] * 5, 0
-    if lm is not None:
-        img, oov = _lm_image(lm, vocab, oov_logprob)
-        largs = [_ip(img), img.size, float(alpha), float(beta), oov]
-    else:
-        largs = [None, 0, 0.0, 0.0, 0.0]
+    targs = _trie_args(trie)
+    largs = _lm_args(lm, vocab, oov_logprob, alpha, beta)
     ids_c, lp_c = (ids, lp) if ids.size else (np.zeros((1, ids.shape[1]), np.int32), np.zeros((1, ids.shape[1]), np.float32))
-    _lib.check(_lib.load().asr_op_nar_beam(_ip(ids_c), _fp(lp_c), ids.shape[1], _ip(sl), sl.size, *targs, n_nodes, float(boost), *largs, int(beam), int(nbest),
+    _lib.check(_lib.load().asr_op_nar_beam(_ip(ids_c), _fp(lp_c), ids.shape[1], _ip(sl), sl.size, *targs, float(boost), *largs, int(beam), int(nbest),
                                            _ip(tok), max_t, _ip(num), _fp(score), _fp(am), _fp(tlp)))
     return tok, num, score, am, tlp
 
@@ -612,22 +611,14 @@ def op_nar_stream_beam(steps, n_streams, beam, nbest=1, pend_cap=16, trie=None, 
     commit_num, total = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
     pend_num = np.zeros((n, nbest), dtype=np.int32)
     pend_score, pend_am = np.zeros((n, nbest), dtype=np.float32), np.zeros((n, nbest), dtype=np.float32)
-    if trie is not None and trie["depth"].size > 1:
-        t = {k: np.ascontiguousarray(trie[k], dtype=np.int32) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")}
-        targs, n_nodes = [_ip(t[k]) for k in ("depth", "is_end", "child_off", "child_tok", "child_node")], int(t["depth"].size)
-    else:
-        targs, n_nodes = [None] * 5, 0
-    if lm is not None:
-        img, oov = _lm_image(lm, vocab, oov_logprob)
-        largs = [_ip(img), img.size, float(alpha), float(beta), oov]
-    else:
-        largs = [None, 0, 0.0, 0.0, 0.0]
+    targs = _trie_args(trie)
+    largs = _lm_args(lm, vocab, oov_logprob, alpha, beta)
     if state is not None:
         assert state.dtype == np.int32 and state.flags["C_CONTIGUOUS"] and state.ndim == 2 and state.shape[0] == n_streams
         sargs = [_ip(state), state.shape[1]]
     else:
         sargs = [None, 0]
-    _lib.check(_lib.load().asr_op_nar_stream_beam(_ip(ids), _fp(lp), topk, int(n_streams), len(steps), _ip(off), _ip(sid), _ip(rows), _ip(fin), *targs, n_nodes,
+    _lib.check(_lib.load().asr_op_nar_stream_beam(_ip(ids), _fp(lp), topk, int(n_streams), len(steps), _ip(off), _ip(sid), _ip(rows), _ip(fin), *targs,
                                                   float(boost), *largs, int(beam), int(nbest), int(pend_cap), *sargs, _ip(commit_ids), _fp(commit_lp), cap,
                                                   _ip(commit_num), _ip(pend_ids), _fp(pend_lp), _ip(pend_num), _fp(pend_score), _fp(pend_am), _ip(total)))
     out = []
@@ -1070,11 +1061,7 @@ class ParaformerSession(_Session):
         """The n-gram language model of run_beam (asr_paraformer_set_lm; shallow fusion), arguments as SenseVoiceSession.set_lm takes them: every token of a
         hypothesis adds alpha * log P(token | history) + beta to its ranking score. None clears it; a malformed image or a bad weight raises AsrError and the
         model in force stays."""
-        if lm is None:
-            _lib.check(_lib.load().asr_paraformer_set_lm(self._h, None, 0, 0.0, 0.0, 0.0))
-            return
-        img, oov = _lm_image(lm, self.cfg.vocab, oov_logprob)
-        _lib.check(_lib.load().asr_paraformer_set_lm(self._h, _ip(img), img.size, float(alpha), float(beta), oov))
+        _lib.check(_lib.load().asr_paraformer_set_lm(self._h, *_lm_args(lm, self.cfg.vocab, oov_logprob, alpha, beta)))
 
     def run_packed_beam(self, audio, offsets, beam: int, topk: int | None = None, nbest: int = 1, audio_device_ptr: int | None = None):
         """run_packed with a beam search over the decoder's token rows instead of the per-row arg-max (asr_paraformer_run_beam): the `topk` (default: beam)
@@ -1235,11 +1222,7 @@ class ParaformerStreamSession(_Session):
 
     def set_lm(self, lm, alpha: float = 0.5, beta: float = 0.0, oov_logprob: float | None = None):
         """The n-gram language model of step_beam (asr_paraformer_stream_set_lm), as ParaformerSession.set_lm takes it. None clears it."""
-        if lm is None:
-            _lib.check(_lib.load().asr_paraformer_stream_set_lm(self._h, None, 0, 0.0, 0.0, 0.0))
-            return
-        img, oov = _lm_image(lm, self.cfg.vocab, oov_logprob)
-        _lib.check(_lib.load().asr_paraformer_stream_set_lm(self._h, _ip(img), img.size, float(alpha), float(beta), oov))
+        _lib.check(_lib.load().asr_paraformer_stream_set_lm(self._h, *_lm_args(lm, self.cfg.vocab, oov_logprob, alpha, beta)))
 
     def _beam_arrays(self, n, max_tokens):
         _, _, nbest, cap = self._beam

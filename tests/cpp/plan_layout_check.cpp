@@ -2,11 +2,13 @@
 // For the section lists of the four call sites that build a plan blob -- WhSession::encode, QwSession::prefill (+ its step plan), SvSession::run and
 // SvSession::stream_step -- it checks every section's alignment, bounds and order, the total, and that the offsets are those of the hand-written layout
 // these sites used before PlanLayout: the expected numbers below are written out from those formulas, none comes from PlanLayout.
-// The same for csrc/result_layout.h, the result blob of the SenseVoice / Paraformer session, in every form (result_blob below).
+// The same for csrc/result_layout.h, the result blob of the SenseVoice / Paraformer session, in every form (result_blob below), and for
+// csrc/nar_stream_state.h, the carried state of the streaming beam search (stream_state below).
 #include <cstdint>
 #include <cstdio>
 #include <vector>
 
+#include "nar_stream_state.h"
 #include "plan_layout.h"
 #include "result_layout.h"
 
@@ -139,7 +141,29 @@ static void result_blob(size_t n, size_t mt, size_t nbest) {
   }
 }
 
+// ---- the carried state of one stream of the streaming beam search (csrc/nar_stream_state.h) against the documented layout, written out in words: the
+// header [L, C, live, unused], five live planes of 16 (am, bonus, node, lm, lmstate), three ring planes [pend_cap][beam] (parent, token, log-probability)
+static void stream_state_planes() {                       // what does not depend on (beam, pend_cap)
+  namespace S = nar_stream_state;
+  const char* name = "stream state header and live planes";
+  CHECK(S::L == 0 && S::C == 1 && S::N_LIVE == 2 && S::UNUSED == 3 && S::HEADER == 4, "header words %d %d %d %d, %d in all", S::L, S::C, S::N_LIVE, S::UNUSED, S::HEADER);
+  CHECK(S::AM == 4 && S::BONUS == 4 + 16 && S::NODE == 4 + 32 && S::LM == 4 + 48 && S::LMSTATE == 4 + 64, "live planes at %d %d %d %d %d", S::AM, S::BONUS, S::NODE,
+        S::LM, S::LMSTATE);
+}
+static void stream_state(int beam, int pend_cap) {
+  namespace S = nar_stream_state;
+  char name[64];
+  snprintf(name, sizeof name, "stream state beam=%d pend_cap=%d", beam, pend_cap);
+  const int ring = pend_cap * beam;
+  CHECK(S::ring_parent(beam, pend_cap) == 4 + 5 * 16 && S::ring_token(beam, pend_cap) == 4 + 5 * 16 + ring && S::ring_logprob(beam, pend_cap) == 4 + 5 * 16 + 2 * ring,
+        "ring planes at %d %d %d", S::ring_parent(beam, pend_cap), S::ring_token(beam, pend_cap), S::ring_logprob(beam, pend_cap));
+  CHECK(S::words(beam, pend_cap) == 4 + 5 * 16 + 3 * pend_cap * beam, "%d words", S::words(beam, pend_cap));
+}
+
 int main() {
+  stream_state_planes();
+  stream_state(4, 16);
+  stream_state(16, 64);                                         // the widest beam at the longest lag
   result_blob(1, 1, 1);
   result_blob(1, 5, 1);
   result_blob(3, 7, 2);
