@@ -50,6 +50,12 @@ class QwenConfigC(C.Structure):
         "max_audio_len")] + [("rms_eps", C.c_float), ("rope_theta", C.c_float), ("classify_num", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
+class VadParamsC(C.Structure):
+    """asr_vad_params: analysis frames and level steps."""
+    _fields_ = [("p_floor", C.c_float)] + [(n, C.c_int32) for n in (
+        "margin", "peak_drop", "abs_level", "min_speech", "min_pause", "pad", "max_frames")] + [("reserved", C.c_int32 * 8)]
+
+
 # name -> (restype, argtypes); every symbol include/asr_mi355x.h declares
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 _fp, _ip, _lp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
@@ -157,6 +163,8 @@ SIGNATURES = {
     "asr_op_cif_scan_timed": (_i, [_fp, _fp, _i, _ip, _i, C.c_float, _fp, _ip, _i, _ip]),
     "asr_op_resample": (_i, [_vp, _lp, _i, _i, _i, _i, _i, _i, _fp, C.c_int64, _lp]),
     "asr_resample_table": (_i, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _fp]),
+    "asr_vad_default_params": (_i, [_i, C.c_float, C.POINTER(VadParamsC)]),
+    "asr_op_vad": (_i, [_vp, _i, _lp, _i, _i, _i, _i, C.POINTER(VadParamsC), _lp, C.c_int64, _ip, _ip, _fp, _ip, _ip]),
 }
 
 

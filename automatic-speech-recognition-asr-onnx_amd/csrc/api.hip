@@ -882,3 +882,90 @@ extern "C" int asr_op_resample(const void* audio, const int64_t* offsets, int ba
   });
 }
 
+
+static int vad_level_of(double a) { return vad_level((float)a); }
+
+extern "C" int asr_vad_default_params(int rate, float full_scale, asr_vad_params* p) {
+  return asr_guard([&] {
+    ASR_REQUIRE(p, "vad_default_params: null argument");
+    ASR_REQUIRE(rate >= 100, "vad: sample rate %d (at least 100 Hz)", rate);
+    ASR_REQUIRE(full_scale > 0.f, "vad: full scale %g (positive)", (double)full_scale);
+    memset(p, 0, sizeof(*p));
+    p->p_floor = 0.10f; p->margin = 24; p->peak_drop = 16;
+    const double amp = (double)full_scale * 1e-3;          // -60 dBFS
+    p->abs_level = vad_level_of((double)vad_hop(rate) * amp * amp);
+    p->min_speech = 10; p->min_pause = 50; p->pad = 10; p->max_frames = 3000;
+  });
+}
+
+extern "C" int asr_op_vad(const void* audio, int mem, const int64_t* offsets, int batch, int audio_dtype, int rate, int channels, const asr_vad_params* params,
+                          int64_t* seg_out, int64_t seg_cap, int32_t* seg_utt, int32_t* seg_count, float* energy_out, int32_t* level_out, int32_t* stats_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(audio && offsets && params && seg_count && batch > 0 && seg_cap >= 0 && (seg_out || seg_cap == 0), "op_vad: bad argument");
+    ASR_REQUIRE(mem == ASR_MEM_HOST || mem == ASR_MEM_DEVICE, "op_vad: unknown memory kind %d", mem);
+    ASR_REQUIRE(audio_dtype == ASR_AUDIO_F32 || audio_dtype == ASR_AUDIO_I16 || audio_dtype == ASR_AUDIO_F16, "op_vad: unknown audio dtype %d", audio_dtype);
+    ASR_REQUIRE(rate >= 100, "vad: sample rate %d (at least 100 Hz)", rate);
+    ASR_REQUIRE(channels >= 1 && channels <= 8, "vad: %d channels (1..8)", channels);
+    ASR_REQUIRE(params->max_frames >= 2, "vad: max_frames %d (at least 2)", params->max_frames);
+    ASR_REQUIRE(params->p_floor > 0.f && params->p_floor <= 1.f, "vad: p_floor %g (in (0, 1])", (double)params->p_floor);
+    const int H = vad_hop(rate);
+    // ---- host plan: per utterance its frames, F = ceil(n / H) and the floor's count; one (utterance, first frame) entry per stage-1 tile
+    std::vector<VadUtt> hu((size_t)batch);
+    std::vector<int32_t> tile_utt, tile_f0;
+    int64_t total_F = 0;
+    int max_F = 0;
+    for (int b = 0; b < batch; ++b) {
+      const int64_t n = offsets[b + 1] - offsets[b];
+      ASR_REQUIRE(n >= 0 && n <= INT32_MAX, "op_vad: utterance %d has %lld frames", b, (long long)n);
+      const int64_t F = (n + H - 1) / H;
+      ASR_REQUIRE(F <= VAD_MAX_F, "vad: utterance %d has %lld analysis frames (at most %d, about 2.9 h)", b, (long long)F, VAD_MAX_F);
+      VadUtt& u = hu[b];
+      u.in_off = offsets[b] - offsets[0]; u.abs_off = offsets[b]; u.f_off = total_F; u.n = (int32_t)n; u.F = (int32_t)F; u.pad_ = 0;
+      u.need = (int32_t)std::min<int64_t>(F, std::max<int64_t>(1, (int64_t)std::ceil((double)params->p_floor * (double)F)));
+      for (int f0 = 0; f0 < F; f0 += VAD_TILE_F) { tile_utt.push_back(b); tile_f0.push_back(f0); }
+      total_F += F;
+      max_F = std::max(max_F, (int)F);
+    }
+    asr_require_device(0);
+    Tmp t;
+    const size_t frame_bytes = (size_t)channels * audio_elt_bytes(audio_dtype), in_bytes = (size_t)(offsets[batch] - offsets[0]) * frame_bytes;
+    const void* src = static_cast<const unsigned char*>(audio) + (size_t)offsets[0] * frame_bytes;
+    if (mem == ASR_MEM_HOST) {
+      void* d_in = nullptr;                                // (no memset of a buffer the copy fills)
+      HIP_CHECK(hipMalloc(&d_in, std::max<size_t>(in_bytes, 256)));
+      t.ptrs.push_back(d_in);
+      if (in_bytes) HIP_CHECK(hipMemcpy(d_in, src, in_bytes, hipMemcpyHostToDevice));
+      src = d_in;
+    }
+    const size_t n_tiles = tile_utt.size(), nF = (size_t)std::max<int64_t>(total_F, 1);
+    VadUtt* d_utt = (VadUtt*)t.alloc(sizeof(VadUtt) * batch);
+    int32_t* d_tile_utt = (int32_t*)t.alloc(4 * std::max<size_t>(n_tiles, 1));
+    int32_t* d_tile_f0 = (int32_t*)t.alloc(4 * std::max<size_t>(n_tiles, 1));
+    HIP_CHECK(hipMemcpy(d_utt, hu.data(), sizeof(VadUtt) * batch, hipMemcpyHostToDevice));
+    if (n_tiles) {
+      HIP_CHECK(hipMemcpy(d_tile_utt, tile_utt.data(), 4 * n_tiles, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(d_tile_f0, tile_f0.data(), 4 * n_tiles, hipMemcpyHostToDevice));
+    }
+    const size_t cap = (size_t)std::min<int64_t>(seg_cap, total_F);      // (an utterance has at most F segments)
+    VadArgs a{};
+    a.audio = src; a.utt = d_utt; a.tile_utt = d_tile_utt; a.tile_f0 = d_tile_f0;
+    a.energy = (float*)t.alloc(4 * nF); a.level = (int32_t*)t.alloc(4 * nF); a.hist = (int32_t*)t.alloc((size_t)batch * VAD_LEVELS * 4);
+    a.seg_tmp = (int32_t*)t.alloc(8 * nF); a.seg_count = (int32_t*)t.alloc((size_t)batch * 4); a.stats = (int32_t*)t.alloc((size_t)batch * 12);
+    a.seg_out = (int64_t*)t.alloc(16 * std::max<size_t>(cap, 1)); a.seg_utt = (int32_t*)t.alloc(4 * std::max<size_t>(cap, 1)); a.seg_cap = (int64_t)cap;
+    a.r = VadRules{params->margin, params->peak_drop, params->abs_level, params->min_speech, params->min_pause, params->pad, params->max_frames};
+    a.H = H; a.channels = channels; a.batch = batch; a.max_F = max_F; a.audio_dtype = audio_dtype;
+    launch_vad(a, (int)n_tiles, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(seg_count, a.seg_count, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    int64_t total = 0;
+    for (int b = 0; b < batch; ++b) total += seg_count[b];
+    const size_t n_out = (size_t)std::min<int64_t>(total, (int64_t)cap);
+    if (n_out) {
+      HIP_CHECK(hipMemcpy(seg_out, a.seg_out, n_out * 16, hipMemcpyDeviceToHost));
+      if (seg_utt) HIP_CHECK(hipMemcpy(seg_utt, a.seg_utt, n_out * 4, hipMemcpyDeviceToHost));
+    }
+    if (energy_out && total_F) HIP_CHECK(hipMemcpy(energy_out, a.energy, (size_t)total_F * 4, hipMemcpyDeviceToHost));
+    if (level_out && total_F) HIP_CHECK(hipMemcpy(level_out, a.level, (size_t)total_F * 4, hipMemcpyDeviceToHost));
+    if (stats_out) HIP_CHECK(hipMemcpy(stats_out, a.stats, (size_t)batch * 12, hipMemcpyDeviceToHost));
+  });
+}

@@ -90,6 +90,49 @@ struct ResampleArgs {
 };
 void launch_resample(const ResampleArgs& a, int n_tiles, hipStream_t s);
 
+// ---- energy VAD (vad.hip): packed frames of any rate and channel count -> speech segments, per utterance of a ragged batch (the statement: asr_mi355x.h).
+// Stage 1 (one launch, a tile list over (utterance, first analysis frame)): e[f] = sum of x^2 over the H input frames of analysis frame f, its level q[f], and the
+// utterance's 1024-bin level histogram. Stage 2 (one launch, one workgroup per utterance, the mask as bits in LDS): floor / peak / thr, the mask, the three run rules,
+// the cuts of long runs; its segments land in the utterance's own range of seg_tmp and vad_pack_kernel (one launch) packs the batch's in order.
+constexpr int VAD_TILE_F = 256;              // analysis frames per stage-1 workgroup
+constexpr int VAD_MAX_F = 1 << 20;           // analysis frames per utterance: the mask is 128 KiB of LDS
+constexpr int VAD_LEVELS = 1024;
+struct VadUtt {
+  int64_t in_off;              // first input frame in the packed buffer, from the buffer's start
+  int64_t abs_off;             // the caller's offset of that frame (what segments are reported in)
+  int64_t f_off;               // first analysis frame in the packed e[] / q[] (and first slot in seg_tmp)
+  int32_t n, F;                // input frames, analysis frames = ceil(n / H)
+  int32_t need;                // ceil(p_floor F): the cumulative count the floor level reaches
+  int32_t pad_;
+};
+struct VadRules { int32_t margin, peak_drop, abs_level, min_speech, min_pause, pad, max_frames; };
+struct VadArgs {
+  const void* audio;           // packed interleaved samples of type audio_dtype
+  const VadUtt* utt;
+  const int32_t* tile_utt;     // per stage-1 workgroup: utterance
+  const int32_t* tile_f0;      // per stage-1 workgroup: first analysis frame (multiple of VAD_TILE_F)
+  float* energy;               // [sum F]
+  int32_t* level;              // [sum F]
+  int32_t* hist;               // [batch][VAD_LEVELS], zero before stage 1
+  int32_t* seg_tmp;            // [sum F][2]: utterance u's segments in analysis frames, from slot f_off
+  int32_t* seg_count;          // [batch]
+  int32_t* stats;              // [batch][3] floor, peak, thr
+  int64_t* seg_out;            // [seg_cap][2]
+  int32_t* seg_utt;            // [seg_cap]
+  int64_t seg_cap;
+  VadRules r;
+  int H, channels, batch, max_F;
+  int audio_dtype = AUDIO_F32;
+};
+inline int vad_hop(int rate) { const int h = (rate + 50) / 100; return h < 1 ? 1 : h; }
+// (bits(max(e, 2^-40)) >> 20) - (bits(2^-40) >> 20), at most 1023: host and device use this one definition
+__host__ __device__ inline int vad_level(float e) {
+  const float m = e > 0x1p-40f ? e : 0x1p-40f;         // (a NaN takes the floor)
+  const int q = (int)(__builtin_bit_cast(uint32_t, m) >> 20) - (int)((87u << 23) >> 20);
+  return q > 1023 ? 1023 : q;
+}
+void launch_vad(const VadArgs& a, int n_tiles, hipStream_t s);      // the memset of hist, stage 1, stage 2, the pack: four nodes on s, no host work between
+
 // ---- Whisper log-mel finish (Export_Whisper.py:425-427): max(x, utterance_max - 8), (x + 4) / 4, written in the
 // GAPPED time-major layout the conv stem reads: utterance b owns rows [2*row_off_b, 2*row_off_b + 2*rows_b); row
 // 2*row_off_b is the conv's left zero pad, frame f sits at row 2*row_off_b + 1 + f, everything else is zero.

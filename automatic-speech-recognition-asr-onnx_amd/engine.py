@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import warnings
 from typing import Sequence
 
@@ -435,6 +436,99 @@ def op_resample(audio, offsets, sample_rate: int, model_rate: int = 16000, chann
     _lib.check(_lib.load().asr_op_resample(audio.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(lp), offs.size - 1, code, int(sample_rate), int(model_rate),
                                            int(channels), int(bool(int16_scale)), _fp(out), out.size, offs_out.ctypes.data_as(lp)))
     return out[:int(offs_out[-1])], offs_out
+
+
+VAD_LEVEL_DB = 10.0 * np.log10(2.0) / 8.0         # one level step in dB of power: 8 steps per octave
+VAD_MAX_F = 1 << 20
+
+
+def vad_hop(rate: int) -> int:
+    """Input frames per analysis frame: max(1, (rate + 50) // 100), about 10 ms."""
+    return max(1, (int(rate) + 50) // 100)
+
+
+def vad_level(energy) -> np.ndarray:
+    """The detector's level of float32 frame energies: min(1023, (bits(max(e, 2^-40)) >> 20) - (bits(2^-40) >> 20))."""
+    e = np.asarray(energy, dtype=np.float32)
+    m = np.where(e > np.float32(2.0 ** -40), e, np.float32(2.0 ** -40)).astype(np.float32)
+    return np.minimum(1023, (m.view(np.uint32) >> 20).astype(np.int64) - ((87 << 23) >> 20))
+
+
+@dataclasses.dataclass
+class VadParams:
+    """The energy detector's parameters in seconds and dB (asr_vad_params holds them in analysis frames and level steps; `to_c` converts). The defaults are
+    design choices, not measurements. max_seconds None: the caller's limit (a transcriber's window), or 30 s."""
+    p_floor: float = 0.10
+    margin_db: float = 9.0
+    peak_drop_db: float = 6.0
+    abs_dbfs: float = -60.0
+    min_speech: float = 0.1
+    min_pause: float = 0.5
+    pad: float = 0.1
+    max_seconds: float | None = None
+
+    def to_c(self, rate: int, full_scale: float, max_frames: int | None = None) -> _lib.VadParamsC:
+        H = vad_hop(rate)
+        frames = lambda sec: max(0, int(round(float(sec) * rate / H)))
+        c = _lib.VadParamsC()
+        c.p_floor = float(self.p_floor)
+        c.margin, c.peak_drop = int(round(self.margin_db / VAD_LEVEL_DB)), int(round(self.peak_drop_db / VAD_LEVEL_DB))
+        amp = float(np.float32(full_scale)) * 10.0 ** (self.abs_dbfs / 20.0)
+        c.abs_level = int(vad_level(np.float32(H * amp * amp)))
+        c.min_speech, c.min_pause, c.pad = frames(self.min_speech), frames(self.min_pause), frames(self.pad)
+        limit = int(self.max_seconds * rate) // H if self.max_seconds is not None else None
+        if max_frames is not None:
+            limit = max_frames if limit is None else min(limit, max_frames)
+        c.max_frames = limit if limit is not None else (30 * int(rate)) // H
+        return c
+
+
+def vad_default_params(rate: int, full_scale: float) -> _lib.VadParamsC:
+    """asr_vad_default_params: the library's own defaults for this rate and sample scale."""
+    c = _lib.VadParamsC()
+    _lib.check(_lib.load().asr_vad_default_params(int(rate), float(full_scale), C.byref(c)))
+    return c
+
+
+def op_vad(audio, offsets, rate: int = 16000, channels: int = 1, params=None, full_scale: float | None = None, audio_device_ptr: int | None = None,
+           details: bool = False, seg_cap: int | None = None):
+    """The energy speech / pause detector on a ragged batch (asr_op_vad): audio = packed frames of `channels` interleaved float32 / int16 / float16 samples at
+    `rate` Hz, offsets [B + 1] in frames (any first offset). params: a VadParams (seconds, dB), an asr_vad_params struct, or None = the library's defaults.
+    full_scale: 32768 for int16-range samples, 1 for unit-range ones (default: 32768 for int16 audio, else 1). audio_device_ptr: the same packed frames in
+    device memory, read there instead of `audio` (which then only gives the sample type and size).
+    -> (segments [S, 2] int64 input-frame offsets in the coordinates of `offsets`, seg_utt [S] int32, counts [B] int32); with details also
+    (energy [sum F] float32, level [sum F] int32, stats [B, 3] int32 = floor, peak, thr). seg_cap: write at most that many segments (counts stay full)."""
+    audio = np.ascontiguousarray(audio).reshape(-1)
+    code = _AUDIO_CODES[audio_np_dtype(audio.dtype)]
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offs.size < 2 or np.any(np.diff(offs) < 0) or offs[0] < 0 or int(offs[-1]) * max(int(channels), 1) > audio.size:
+        raise ValueError("op_vad: offsets must be non-decreasing frame offsets inside the audio given")
+    if full_scale is None:
+        full_scale = 32768.0 if audio.dtype == np.int16 else 1.0
+    if params is None:
+        pc = vad_default_params(rate, full_scale)
+    elif isinstance(params, VadParams):
+        pc = params.to_c(rate, full_scale)
+    else:
+        pc = params
+    H = vad_hop(rate) if rate >= 1 else 1
+    F = -((-np.diff(offs)) // H)
+    total_f = int(F.sum())
+    cap = total_f if seg_cap is None else int(seg_cap)
+    seg = np.zeros((max(cap, 1), 2), dtype=np.int64)
+    utt = np.zeros(max(cap, 1), dtype=np.int32)
+    counts = np.zeros(offs.size - 1, dtype=np.int32)
+    energy = np.zeros(max(total_f, 1), dtype=np.float32) if details else None
+    level = np.zeros(max(total_f, 1), dtype=np.int32) if details else None
+    stats = np.zeros((offs.size - 1, 3), dtype=np.int32) if details else None
+    lp = C.POINTER(C.c_int64)
+    ptr = C.c_void_p(int(audio_device_ptr)) if audio_device_ptr is not None else audio.ctypes.data_as(C.c_void_p)
+    _lib.check(_lib.load().asr_op_vad(ptr, MEM_DEVICE if audio_device_ptr is not None else MEM_HOST, offs.ctypes.data_as(lp), offs.size - 1, code, int(rate),
+                                      int(channels), C.byref(pc), seg.ctypes.data_as(lp), cap, _ip(utt), _ip(counts), _fp(energy),
+                                      _ip(level) if details else None, _ip(stats) if details else None))
+    n = min(int(counts.sum()), cap)
+    res = (seg[:n].copy(), utt[:n].copy(), counts)
+    return res + (energy[:total_f], level[:total_f], stats) if details else res
 
 
 def op_ctc_collapse(frame_ids, seq_lens, blank_id=0):

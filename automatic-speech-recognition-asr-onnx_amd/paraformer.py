@@ -24,6 +24,7 @@ from .config import ParaformerConfig
 from .ort_io import (array_for, filled_for, is_dynamic_dim, load_special_token_ids, load_supported_languages, numpy_dtype,
                      resolve_supported_language)
 from .input_format import as_frames, cut_windows, session_input_format
+from .segmenter import pack, run_long
 from .sensevoice import plan_windows, prepare_audio_input
 
 C = onnxruntime
@@ -287,3 +288,66 @@ class ParaformerTranscriber:
         if use_beam:
             out["nbest"] = nbest_all
         return out
+
+    def transcribe_long(self, audio_int16: np.ndarray, vad=None, sample_rate: int | None = None, channels: int = 1, normalise: bool = False,
+                        timestamps: bool = False, max_token_rows: int = 4, beam_size: int = 1, nbest: int = 1, hotwords=None, hotword_boost: float = 2.0,
+                        lm=None, lm_weight: float = 0.5, length_bonus: float = 0.0, max_batch: int = 32):
+        """A long file cut at its pauses instead of at fixed windows: the device VAD (engine.op_vad; vad = an engine.VadParams, None: the defaults) finds
+        the speech, no segment longer than max_audio_len, and the segments run as ragged batches of at most max_batch through the native session
+        (run_packed / run_packed_timed / run_packed_beam). The other options are `transcribe`'s. With sample_rate the detector works on the frames at
+        that rate and the session's input format is set for the calls, so only kept segments are resampled.
+        -> dict(segments = [{"start", "end", "token_ids", "text"} + "tokens" (timestamps) / "nbest" (beam)] in seconds of the file, token_ids = the
+        segments' ids in file order (stop ids dropped), text, speech_seconds, audio_seconds, rtf, language). A file with no speech makes no session call."""
+        use_beam = beam_size > 1 or nbest > 1 or bool(hotwords) or lm is not None
+        if use_beam and not 1 <= nbest <= beam_size <= 16:
+            raise ValueError(f"beam_size {beam_size}, nbest {nbest}: expected 1 <= nbest <= beam_size <= 16")
+        native = self.session._native
+        cfg = native.cfg
+        rate = self.sample_rate if sample_rate is None else int(sample_rate)
+        row_seconds = cfg.lfr_n * cfg.hop_length / cfg.sample_rate
+
+        def prepare(frames):
+            return prepare_audio_input(frames.reshape(1, 1, -1), self.input_audio_dtype, audio_pcm_scale=self.audio_pcm_scale, normalise=normalise,
+                                       channels=channels).reshape(-1, channels)
+
+        def run_batch(prepared, segs):
+            packed, offs = pack(prepared, segs, channels)
+            n_rows = [cfg.seq_len(int(n)) for n in native.model_lengths(np.diff(offs))]
+            durs = [int(e - s) / rate for s, e in segs]
+            out = []
+            if use_beam:
+                tok, num, score, am, fire, logprob = native.run_packed_beam(packed, offs, beam_size, None, nbest)
+                for b in range(segs.shape[0]):
+                    best, hyps = self._assemble_hypotheses(tok[b], num[b], score[b], am[b], fire[b], logprob[b], n_rows[b], row_seconds, 0.0, durs[b],
+                                                           timestamps, max_token_rows)
+                    r = {"token_ids": best, "nbest": hyps}
+                    if timestamps:
+                        r["tokens"] = [dict(t) for t in hyps[0]["tokens"]]
+                    out.append(r)
+            elif timestamps:
+                tok, num, fire, logprob = native.run_packed_timed(packed, offs)
+                for b in range(segs.shape[0]):
+                    n = int(num[b])
+                    spans = token_times(fire[b, :n], n_rows[b], row_seconds, max_token_rows)
+                    toks = [{"id": int(tok[b, k]), "text": str(self.tokenizer[tok[b, k]]), "start": min(float(spans[k, 0]), durs[b]),
+                             "end": min(float(spans[k, 1]), durs[b]), "logprob": float(logprob[b, k])} for k in range(n)]
+                    out.append({"token_ids": tok[b, :n].copy(), "tokens": [t for t in toks if t["id"] not in self.stop_token_ids]})
+            else:
+                tok, num = native.run_packed(packed, offs)
+                out = [{"token_ids": tok[b, :num[b]].copy()} for b in range(segs.shape[0])]
+            for r in out:
+                r["token_ids"] = r["token_ids"][~np.isin(r["token_ids"], self.stop_token_ids)]
+                r["text"] = decode_tokens(self.tokenizer[r["token_ids"]].tolist(), self.decode_mode)
+            return out
+
+        t0 = time.time()
+        if use_beam:
+            native.set_hotwords(self._hotword_ids(hotwords), hotword_boost)
+            native.set_lm(lm, lm_weight, length_bonus)
+        with session_input_format(native, sample_rate, channels):
+            records, info = run_long(audio_int16, vad, sample_rate, channels, self.sample_rate, int(cfg.max_audio_len), prepare, run_batch, max_batch)
+        ids = [r["token_ids"] for r in records]
+        all_ids = np.concatenate(ids) if ids else np.zeros(0, np.int32)
+        return {"segments": records, "token_ids": all_ids, "text": decode_tokens(self.tokenizer[all_ids].tolist(), self.decode_mode),
+                "speech_seconds": info["speech_seconds"], "audio_seconds": info["audio_seconds"],
+                "rtf": (time.time() - t0) / max(info["audio_seconds"], 1e-9), "language": self.language}

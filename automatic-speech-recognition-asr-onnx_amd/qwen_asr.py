@@ -27,6 +27,7 @@ import numpy as np
 from .config import QwenAsrConfig
 from .engine import QwenAsrSession, audio_dtype_name
 from .input_format import as_frames, model_samples, ratio, session_input_format
+from .segmenter import run_long
 from .whisper import avg_logprob, prepare_audio_input
 
 ASR_TEXT_TAG = "<asr_text>"
@@ -181,6 +182,29 @@ class QwenAsrTranscriber:
         format, set for this call); a clip is cut at max_audio_len samples of the resampled audio. None: 16 kHz mono, nothing changes."""
         with session_input_format(self.sess, sample_rate, channels) as formatted:
             return self._transcribe(clips_int16, task_prompts, language_prompts, max_new, (int(sample_rate), int(channels)) if formatted else None)
+
+    def transcribe_long(self, pcm_int16: np.ndarray, vad=None, sample_rate: int | None = None, channels: int = 1, task_prompt="", language_prompt: str = "",
+                        max_new: int | None = None, max_batch: int = 16):
+        """A long file cut at its pauses: the device VAD (engine.op_vad; vad = an engine.VadParams, None: the defaults) finds the speech, no segment longer
+        than cfg.max_audio_len, and the segments go through `transcribe` as clip lists of at most max_batch, with this transcriber's settings as they
+        are; task_prompt / language_prompt serve every segment. With sample_rate the detector works on the frames at that rate and only kept segments
+        are resampled. -> dict(segments = [{"start", "end", ...the clip's result...}] in seconds of the file, token_ids = the segments' ids in file
+        order, text (None without a tokenizer), speech_seconds, audio_seconds), stats. No speech: no session call."""
+        wall = [0.0]
+
+        def run_batch(frames, segs):
+            out, stats = self.transcribe([frames[s:e] for s, e in segs], (task_prompt,), (language_prompt,), max_new, sample_rate, channels)
+            wall[0] += stats["wall_s"]
+            for r in out:
+                r["token_ids"] = r["tokens"]
+            return out
+
+        records, info = run_long(pcm_int16, vad, sample_rate, channels, self.cfg.sample_rate, int(self.cfg.max_audio_len), lambda f: f, run_batch, max_batch)
+        ids = [r["token_ids"] for r in records]
+        text = " ".join(r["text"] for r in records if r["text"]) if self.tokenizer is not None else None
+        res = {"segments": records, "token_ids": np.concatenate(ids) if ids else np.zeros(0, np.int32), "text": text,
+               "speech_seconds": info["speech_seconds"], "audio_seconds": info["audio_seconds"]}
+        return res, {"rtf": wall[0] / max(info["audio_seconds"], 1e-9), "wall_s": wall[0]}
 
     def _transcribe(self, clips_int16, task_prompts, language_prompts, max_new, fmt):
         B = len(clips_int16)

@@ -18,6 +18,7 @@ from . import ort_shim as onnxruntime
 from .arena import build_sensevoice_arena
 from .config import SenseVoiceConfig
 from .input_format import as_frames, cut_windows, session_input_format
+from .segmenter import pack, run_long
 from .ort_io import array_for, filled_for, is_dynamic_dim, load_supported_languages, numpy_dtype, resolve_supported_language
 
 C = onnxruntime  # `C.OrtDevice` in the reference scripts
@@ -324,3 +325,61 @@ class SenseVoiceTranscriber:
         if use_beam:
             out["nbest"] = nbest_all
         return out
+
+    def transcribe_long(self, audio_int16: np.ndarray, vad=None, sample_rate: int | None = None, channels: int = 1, normalise: bool = False,
+                        timestamps: bool = False, beam_size: int = 1, nbest: int = 1, hotwords=None, hotword_boost: float = 2.0, lm=None,
+                        lm_weight: float = 0.5, length_bonus: float = 0.0, max_batch: int = 32):
+        """A long file cut at its pauses instead of at fixed windows: the device VAD (engine.op_vad; vad = an engine.VadParams, None: the defaults) finds
+        the speech, no segment longer than max_audio_len, and the segments run as ragged batches of at most max_batch through the native session
+        (run_packed / run_packed_timed / run_packed_beam). The other options are `transcribe`'s. With sample_rate the detector works on the frames at
+        that rate and the session's input format is set for the calls, so only kept segments are resampled.
+        -> dict(segments = [{"start", "end", "token_ids", "text"} + "tokens" (timestamps) / "nbest" (beam)] in seconds of the file, token_ids = the
+        segments' ids in file order, text, speech_seconds, audio_seconds, rtf, language). A file with no speech makes no session call."""
+        use_beam = beam_size > 1 or nbest > 1 or bool(hotwords) or lm is not None
+        if use_beam and timestamps:
+            raise ValueError("timestamps are not available for beam hypotheses")
+        if use_beam and not 1 <= nbest <= beam_size <= 16:
+            raise ValueError(f"beam_size {beam_size}, nbest {nbest}: expected 1 <= nbest <= beam_size <= 16")
+        native = self.session._native
+        rate = self.sample_rate if sample_rate is None else int(sample_rate)
+        decode = (lambda ids: self.tokenizer.decode([ids.tolist()])[0]) if self.tokenizer is not None else (lambda ids: None)
+
+        def prepare(frames):
+            return prepare_audio_input(frames.reshape(1, 1, -1), self.input_audio_dtype, audio_pcm_scale=self.audio_pcm_scale, normalise=normalise,
+                                       channels=channels).reshape(-1, channels)
+
+        def run_batch(prepared, segs):
+            packed, offs = pack(prepared, segs, channels)
+            lang = np.full(segs.shape[0], self.selector_index, dtype=np.int32)
+            out = []
+            if timestamps:
+                tok, num, first, last, logprob = native.run_packed_timed(packed, offs, lang)
+                for b, (s, e) in enumerate(segs):
+                    dur = int(e - s) / rate
+                    spans = [native.cfg.row_span_seconds(first[b, k], last[b, k]) for k in range(num[b])]
+                    out.append({"token_ids": tok[b, :num[b]].copy(),
+                                "tokens": [{"id": int(tok[b, k]), "start": min(t0, dur), "end": min(t1, dur), "logprob": float(logprob[b, k])}
+                                           for k, (t0, t1) in enumerate(spans)]})
+            elif use_beam:
+                tok, num, score, ctc = native.run_packed_beam(packed, offs, lang, beam_size, None, nbest)
+                for b in range(segs.shape[0]):
+                    hyps = [{"token_ids": tok[b, n, :num[b, n]].copy(), "score": float(score[b, n]), "ctc_score": float(ctc[b, n]),
+                             "text": decode(tok[b, n, :num[b, n]])} for n in range(nbest) if np.isfinite(score[b, n])]
+                    out.append({"token_ids": hyps[0]["token_ids"], "nbest": hyps})
+            else:
+                tok, num = native.run_packed(packed, offs, lang)
+                out = [{"token_ids": tok[b, :num[b]].copy()} for b in range(segs.shape[0])]
+            for r in out:
+                r["text"] = decode(r["token_ids"])
+            return out
+
+        t0 = time.time()
+        if use_beam:
+            native.set_hotwords(self._hotword_ids(hotwords), hotword_boost)
+            native.set_lm(lm, lm_weight, length_bonus)
+        with session_input_format(native, sample_rate, channels):
+            records, info = run_long(audio_int16, vad, sample_rate, channels, self.sample_rate, int(native.cfg.max_audio_len), prepare, run_batch, max_batch)
+        ids = [r["token_ids"] for r in records]
+        return {"segments": records, "token_ids": np.concatenate(ids) if ids else np.zeros(0, np.int32),
+                "text": "".join(r["text"] for r in records) if self.tokenizer is not None else None, "speech_seconds": info["speech_seconds"],
+                "audio_seconds": info["audio_seconds"], "rtf": (time.time() - t0) / max(info["audio_seconds"], 1e-9), "language": self.language}

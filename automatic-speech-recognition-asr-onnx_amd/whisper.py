@@ -55,6 +55,7 @@ import numpy as np
 from .config import WhisperConfig
 from .engine import WhisperSession, audio_dtype_name
 from .input_format import as_frames, cut_windows, model_samples, session_input_format
+from .segmenter import run_long
 
 
 def prepare_audio_input(audio_int16: np.ndarray, target_dtype=np.float32, *, audio_pcm_scale: int = 32768,
@@ -536,6 +537,34 @@ class WhisperTranscriber:
         format, set for this call); lengths and seconds are the resampled clips'. None: 16 kHz mono, nothing changes."""
         with session_input_format(self.sess, sample_rate, channels) as formatted:
             return self._transcribe(clips_int16, language_ids, max_new, prompts, channels if formatted else None)
+
+    def transcribe_long(self, pcm_int16: np.ndarray, vad=None, sample_rate: int | None = None, channels: int = 1, language_id: int | None = None,
+                        max_new: int | None = None, prompt=None, max_batch: int = 16):
+        """A long file cut at its pauses instead of at fixed 30 s windows: the device VAD (engine.op_vad; vad = an engine.VadParams, None: the defaults)
+        finds the speech, no segment longer than cfg.max_audio_len, and the segments go through `transcribe` as clip lists of at most max_batch, with
+        this transcriber's settings (timestamps, word timestamps, beam, hotwords, lm, ...) as they are. language_id / prompt (ids of previous text): given
+        to every segment. With sample_rate the detector works on the frames at that rate and only kept segments are resampled.
+        -> dict(segments = [{"start", "end", ...the clip's result...}] with segments / token_times / words in seconds of the file, token_ids = the
+        segments' text ids in file order, text (None without a piece decoder), speech_seconds, audio_seconds), stats. No speech: no session call."""
+        wall = [0.0]
+
+        def run_batch(frames, segs):
+            clips = [frames[s:e] for s, e in segs]
+            out, stats = self.transcribe(clips, None if language_id is None else [language_id] * len(clips), max_new,
+                                         None if prompt is None else [prompt] * len(clips), sample_rate, channels)
+            wall[0] += stats["wall_s"]
+            for r in out:
+                r["token_ids"] = r["tokens"]
+            return out
+
+        records, info = run_long(pcm_int16, vad, sample_rate, channels, self.cfg.sample_rate, int(self.cfg.max_audio_len), lambda f: f, run_batch, max_batch)
+        ids = [r["token_ids"] for r in records]
+        all_ids = np.concatenate(ids) if ids else np.zeros(0, np.int32)
+        text = None
+        if self.piece_decoder is not None:
+            text = "".join(p for p in decode_pieces(all_ids.tolist(), self.piece_decoder) if p)
+        res = {"segments": records, "token_ids": all_ids, "text": text, "speech_seconds": info["speech_seconds"], "audio_seconds": info["audio_seconds"]}
+        return res, {"rtf": wall[0] / max(info["audio_seconds"], 1e-9), "wall_s": wall[0]}
 
     def _transcribe(self, clips_int16, language_ids, max_new, prompts, channels):
         cfg = self.cfg

@@ -691,6 +691,33 @@ int asr_op_resample(const void* audio, const int64_t* offsets, int batch, int au
  * double, rounded once). Equal rates give L = M = 1, W = 0 and the single coefficient 1. INVALID as asr_session_set_input_format refuses rates. */
 int asr_resample_table(int rate_in, int rate_model, int* L, int* M, int* W, float* coeffs);
 
+/* ------------------------------------------------------------------ voice activity: pause-aware segmentation of long audio (csrc/vad.hip)
+ * An energy detector over analysis frames of H = max(1, (rate + 50) / 100) input frames (about 10 ms). An utterance of n frames has F = ceil(n / H) analysis
+ * frames; e[f] is the f32 sum of x^2 over frame f with x the widened channel mean (int16 as is, never scaled: full_scale says what the values mean), and its level
+ * q[f] = min(1023, (bits(max(e[f], 2^-40)) >> 20) - (bits(2^-40) >> 20)): the f32 exponent and three mantissa bits, 8 steps per octave. Everything after e[] is
+ * integer work on q[]: floor = the lowest level whose cumulative count reaches ceil(p_floor F), peak = max q, thr = max(abs_level, min(floor + margin,
+ * peak - peak_drop)), mask q >= thr; then speech runs shorter than min_speech are cleared, pauses shorter than min_pause between two speech runs are set, every run
+ * grows by pad on both sides (touching runs are one), and a run longer than max_frames is cut -- while end - start > max_frames -- at the frame of lowest level in
+ * [start + max_frames / 2, start + max_frames], the latest on a tie. All fields but p_floor count analysis frames or level steps. */
+typedef struct {
+  float p_floor;          /* (0, 1] */
+  int32_t margin, peak_drop, abs_level;
+  int32_t min_speech, min_pause, pad;
+  int32_t max_frames;     /* >= 2 */
+  int32_t reserved[8];
+} asr_vad_params;
+/* The defaults: p_floor 0.10, margin 24 (9 dB), peak_drop 16 (6 dB), abs_level = the level of H (full_scale 10^(-60/20))^2 (-60 dBFS), min_speech 10, min_pause 50,
+ * pad 10, max_frames 3000. full_scale: 32768 for int16-range samples, 1 for unit-range ones. INVALID for rate < 100 or full_scale <= 0. */
+int asr_vad_default_params(int rate, float full_scale, asr_vad_params* params);
+/* The detector on a ragged batch: audio = packed frames of `channels` interleaved samples of audio_dtype at `rate` Hz, in host (ASR_MEM_HOST) or device memory;
+ * offsets host [batch + 1] in frames (any first offset). The detector works at the input's own rate and never resamples. seg_out host [seg_cap][2] receives the
+ * segments of all utterances in order as (start, end) input-frame offsets in the coordinates of `offsets`; seg_utt (nullable) host [seg_cap] the utterance of
+ * each; seg_count host [batch] the FULL count of every utterance, even where the segments past seg_cap were not written. energy_out / level_out (nullable): host,
+ * packed [sum F]; stats_out (nullable): host [batch][3] = floor, peak, thr. The op owns its device buffers for the call and touches no session.
+ * INVALID (nothing written): an utterance of more than 2^20 analysis frames, rate < 100, channels outside 1..8, max_frames < 2, p_floor outside (0, 1]. */
+int asr_op_vad(const void* audio, int mem, const int64_t* offsets, int batch, int audio_dtype, int rate, int channels, const asr_vad_params* params,
+               int64_t* seg_out, int64_t seg_cap, int32_t* seg_utt, int32_t* seg_count, float* energy_out, int32_t* level_out, int32_t* stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,41 @@ def load_decoder_lm(opts, tok):
     return {"lm": lm, "lm_weight": opts["lm_weight"], "length_bonus": opts["length_bonus"], "lm_topk": opts["lm_topk"]}
 
 
+def vad_params(a):
+    """--vad and its options -> engine.VadParams, or None without --vad."""
+    if not getattr(a, "vad", False):
+        if any(getattr(a, k, None) is not None for k in ("vad_margin_db", "vad_min_pause", "vad_pad", "vad_max_seconds", "vad_dump")):
+            raise SystemExit("--vad-margin-db / --vad-min-pause / --vad-pad / --vad-max-seconds / --vad-dump need --vad")
+        return None
+    if a.sliding_window:
+        raise SystemExit("--vad cuts the file at its pauses: it does not combine with --sliding-window")
+    if getattr(a, "condition_on_previous_text", False):
+        raise SystemExit("--vad runs a file's segments as batches: it does not combine with --condition-on-previous-text")
+    kw = {k: v for k, v in (("margin_db", a.vad_margin_db), ("min_pause", a.vad_min_pause), ("pad", a.vad_pad), ("max_seconds", a.vad_max_seconds)) if v is not None}
+    return _m("engine").VadParams(**kw)
+
+
+def _plain(v):
+    """A transcribe_long record as JSON takes it."""
+    if isinstance(v, np.ndarray):
+        return v.tolist()
+    if isinstance(v, (np.integer,)):
+        return int(v)
+    if isinstance(v, (np.floating,)):
+        return float(v)
+    if isinstance(v, dict):
+        return {k: _plain(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    return v
+
+
+def vad_file_record(p, about, r, language, rtf):
+    """The dump's entry for a file transcribed with --vad: `windows` holds the segments' ids, `segments` every segment's record in seconds of the file."""
+    return {"path": p, **about, "language": language, "windows": [np.asarray(g["token_ids"]).astype(int).tolist() for g in r["segments"]], "text": r.get("text"),
+            "rtf": rtf, "vad": True, "speech_seconds": r["speech_seconds"], "audio_seconds": r["audio_seconds"], "segments": _plain(r["segments"])}
+
+
 def read_audio(a, path, reference_ingest):
     """One wav -> (int16 audio, the transcriber's format arguments, what the dump records about it). Default: reference_ingest(), mono PCM at the model's rate,
     converted on the host as the reference's pydub ingest does. --device-resample: the file's own frames [n, channels] at its own rate; the session resamples
@@ -184,6 +219,7 @@ def run(a) -> dict:
     if scores and a.beam > 1:
         raise SystemExit("--token-scores / --temperature-fallback need --beam 1 (the beam search reports a score per hypothesis)")
     files = []
+    vad = vad_params(a)
     if a.family in ("sensevoice", "paraformer"):
         mod = _m(a.family)
         if a.family == "sensevoice":
@@ -197,6 +233,17 @@ def run(a) -> dict:
             nar_kw["lm"] = tr.load_lm(nar["lm_file"]) if nar["lm_file"] else None
         for p in a.wav:
             pcm, fmt, about = read_audio(a, p, lambda: audio_io.read_wav_int16(p, tr.sample_rate, exact_width=a.strict_wav))
+            if vad is not None:             # cut at the pauses: the same options, the segments as ragged batches
+                if nar_kw:
+                    kw = dict(timestamps=timestamps, **nar_kw)
+                elif sv_beam:
+                    kw = dict(beam_size=a.beam, nbest=nbest, hotwords=parse_hotword_file(hot_file) if hot_file else None, hotword_boost=getattr(a, "hotword_boost", 2.0),
+                              lm=lm, lm_weight=0.5 if lm_weight is None else lm_weight, length_bonus=0.0 if length_bonus is None else length_bonus)
+                else:
+                    kw = dict(timestamps=timestamps)
+                r = tr.transcribe_long(pcm, vad=vad, **kw, **fmt)
+                files.append(vad_file_record(p, about, r, r.get("language", a.language), r["rtf"]))
+                continue
             if nar_kw:
                 r = tr.transcribe(pcm, sliding_window=a.sliding_window, timestamps=timestamps, **nar_kw, **fmt)
             elif timestamps:
@@ -247,6 +294,14 @@ def run(a) -> dict:
             lang_id = tok.convert_tokens_to_ids(f"<|{a.language}|>")
         for p in a.wav:
             pcm, fmt, about = read_audio(a, p, lambda: audio_io.read_wav_int16(p, cfg.sample_rate, exact_width=a.strict_wav))
+            if vad is not None:             # cut at the pauses: the transcriber's settings as they are, the segments as clip batches
+                r, stat = tr.transcribe_long(pcm, vad=vad, language_id=lang_id, **fmt)
+                if tok is not None:
+                    for g in r["segments"]:
+                        g["text"] = whisper_text(tok, np.asarray(g["token_ids"]).tolist(), remove_repeats=False)
+                    r["text"] = "".join(g["text"] for g in r["segments"])
+                files.append(vad_file_record(p, about, r, a.language, stat["rtf"]))
+                continue
             # the reference's per-file loop (Inference_Whisper_ONNX.py:741-829): SLIDING_WINDOW stride, zero-padded tail, probe on window 0 only,
             # a no-speech verdict aborts the file, later windows reuse window 0's language
             r, stat = tr.transcribe_file(pcm, language_id=lang_id, sliding_window=a.sliding_window, **fmt)
@@ -288,6 +343,10 @@ def run(a) -> dict:
                                                token_scores=scores, hotwords=dec_hot, hotword_boost=dec_hot_boost, **load_decoder_lm(dec_lm, tok))
         for p in a.wav:
             pcm, fmt, about = read_audio(a, p, lambda: audio_io.read_wav_int16(p, cfg.sample_rate, exact_width=a.strict_wav))
+            if vad is not None:
+                r, stat = tr.transcribe_long(pcm, vad=vad, language_prompt="" if a.language == "auto" else a.language, **fmt)
+                files.append(vad_file_record(p, about, r, a.language, stat["rtf"]))
+                continue
             out, stat = tr.transcribe([pcm], language_prompts=("" if a.language == "auto" else a.language,), **fmt)
             r = out[0]
             files.append({"path": p, **about, "language": r.get("language") or a.language,
@@ -296,6 +355,10 @@ def run(a) -> dict:
                 files[-1].update(token_logprobs=[float(v) for v in r["token_logprobs"]], avg_logprob=r["avg_logprob"])
     else:
         raise SystemExit(a.family)
+    if vad is not None and getattr(a, "vad_dump", None):
+        with open(a.vad_dump, "w", encoding="utf-8") as f:
+            json.dump({"files": [{"path": r["path"], "audio_seconds": r["audio_seconds"], "speech_seconds": r["speech_seconds"],
+                                  "segments": [[g["start"], g["end"]] for g in r["segments"]]} for r in files]}, f, indent=1)
     return {"family": a.family, "precision": a.precision, "engine": "automatic-speech-recognition-asr-onnx_amd (MI355X)", "files": files}
 
 
@@ -400,6 +463,13 @@ def build_parser():
     r.add_argument("--device-resample", action="store_true", help="feed each wav at its own sample rate and channel count and let the session resample on the "
                    "device (set_input_format: low-pass polyphase filter, channel mean). The build's own mode: without it the ingest is the reference's host-side "
                    "conversion, sample for sample")
+    r.add_argument("--vad", action="store_true", help="cut each file at its pauses with the device energy detector (transcribe_long) instead of at fixed windows; "
+                   "the dump gains `segments` in seconds of the file. Without it nothing changes")
+    r.add_argument("--vad-margin-db", type=float, default=None, metavar="DB", help="--vad: threshold above the noise floor (default 9)")
+    r.add_argument("--vad-min-pause", type=float, default=None, metavar="S", help="--vad: shorter pauses between speech are bridged (default 0.5)")
+    r.add_argument("--vad-pad", type=float, default=None, metavar="S", help="--vad: every segment grows by this much on both sides (default 0.1)")
+    r.add_argument("--vad-max-seconds", type=float, default=None, metavar="S", help="--vad: longest segment (default: the family's window)")
+    r.add_argument("--vad-dump", metavar="FILE", default=None, help="--vad: also write the segments' [start, end] per file as JSON")
     r.add_argument("--out", required=True)
     r.add_argument("--any-wav-width", dest="strict_wav", action="store_false",
                    help="accept 8 / 24 / 32-bit wav (rescaled to int16); by default only 16-bit wav is taken: the only width whose samples equal the reference's, "
