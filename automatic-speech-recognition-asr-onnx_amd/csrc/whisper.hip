@@ -392,6 +392,7 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* audio_of
         g.add = xb; g.ld_add = d; g.out_f32 = xa; g.ld_out_f32 = d;
         launch_gemm_fp8(g, stream);
       }
+      if (taps_enabled) save_tap(("enc" + std::to_string(i)).c_str(), xa, rows, d, d, 4);
       continue;
     }
     { ProfScope ps(prof, "layernorm", stream); launch_layernorm<T>(xb, d, rows, d, nullptr, nullptr, 1e-5f, h, d, d, stream); }
@@ -408,6 +409,7 @@ void WhSession::encode(const void* audio, int audio_mem, const int64_t* audio_of
       g.out_f32 = xa; g.ld_out_f32 = d;
       gemm(g);
     }
+    if (taps_enabled) save_tap(("enc" + std::to_string(i)).c_str(), xa, rows, d, d, 4);    // the f32 residual stream behind layer i (tests/whisper_layers_ref.py)
   }
   // ---- final LayerNorm + fused cross-KV projection into [kv][layer][head] slabs of [row][64] (:438-447)
   if (taps_enabled) {
@@ -503,6 +505,7 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
     { ProfScope ps(prof, "dec_embed", st);
       launch_embed_pos<T>(ids_dev + r0, Rc, bs ? 1 : n, hist, hd, (const T*)embed, dec_pos, d, xa + (size_t)r0 * d, st, kstart(), bs ? bs->beam : n);
       if (dgm) launch_rows_to_bf16(xa + (size_t)r0 * d, xa_lo + (size_t)r0 * d, (size_t)(NC == 1 ? Rp : Rc) * d, st); }
+    if (taps_enabled) save_tap("dec_in", xa, R, d, d, 4);     // (a tapped step is never captured: `graphable` in step())
     for (int l = 0; l < Ld; ++l) {
       const DecLayer& L = dec[l];
       if (dgm) dg(st, ci, r0, Rc, l, xa_lo, d, L.wqkv, 0, 3 * d, d, L.bqkv, csum + l * cs_l, nullptr, ACT_NONE, nullptr, qkv, 3 * d);
@@ -513,7 +516,7 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
       }
       {
         ProfScope ps(prof, "dec_self_attn", st);
-        DecAttnArgs a;
+        DecAttnArgs a{};                                   // (zeroed: the paged form sets no strides, and the prompt-attention launcher checks their alignment)
         a.q = qkv; a.ld_q = 3 * d; a.q_col0 = 0; a.kv_new = qkv; a.ld_new = 3 * d; a.k_col0 = d; a.v_col0 = 2 * d;
         if (bs) {
           T* ext = d_bext.as<T>() + (size_t)l * R * 2 * H * bs->S * 64;
@@ -621,6 +624,7 @@ void WhSession::enqueue_step(const int32_t* ids_dev, int n, bool is_prefill, boo
         g2.out_f32 = xa; g2.ld_out_f32 = d;
         gemm(g2);
       }
+      if (taps_enabled) save_tap(("dec" + std::to_string(l)).c_str(), xa, R, d, d, 4);     // the f32 residual stream behind layer l, all R rows
     }
   };
   run_chain(stream, 0, 0, B);
