@@ -83,6 +83,7 @@ SIGNATURES = {
     "asr_paraformer_set_lm": (_i, [_vp, _ip, C.c_int64, C.c_float, C.c_float, C.c_float]),
     "asr_paraformer_stream_create": (_i, [C.POINTER(ParaformerConfigC), _vp, _sz, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "asr_paraformer_stream_reset": (_i, [_vp, _i]),
+    "asr_paraformer_stream_input_frames": (_i, [_vp, _ip, _i, _ip, _ip]),
     "asr_paraformer_stream_step": (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _ip]),
     "asr_paraformer_stream_step_timed": (_i, [_vp, _vp, _i, _ip, _i, _ip, _i, _ip, _ip, _fp]),
     "asr_paraformer_stream_set_beam": (_i, [_vp, _i, _i, _i, _i]),
@@ -162,6 +163,7 @@ SIGNATURES = {
     "asr_op_ctc_align": (_i, [_fp, _i, _ip, _i, _i, _ip, _ip, _ip, _ip, _fp, _i, _fp, _fp, _ip]),
     "asr_op_cif_scan_timed": (_i, [_fp, _fp, _i, _ip, _i, C.c_float, _fp, _ip, _i, _ip]),
     "asr_op_resample": (_i, [_vp, _lp, _i, _i, _i, _i, _i, _i, _fp, C.c_int64, _lp]),
+    "asr_op_resample_stream": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _ip, _fp, _ip, _ip]),
     "asr_resample_table": (_i, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _fp]),
     "asr_vad_default_params": (_i, [_i, C.c_float, C.POINTER(VadParamsC)]),
     "asr_op_vad": (_i, [_vp, _i, _lp, _i, _i, _i, _i, C.POINTER(VadParamsC), _lp, C.c_int64, _ip, _ip, _fp, _ip, _ip]),

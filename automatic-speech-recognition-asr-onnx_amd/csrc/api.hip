@@ -100,6 +100,7 @@ extern "C" int asr_session_set_input_format(asr_session* s, int sample_rate, int
     ASR_REQUIRE(s, "set_input_format: null session");
     ASR_REQUIRE(channels >= 1 && channels <= 8, "input format: %d channels (1..8)", channels);
     (void)resample_design(sample_rate, s->model_rate);   // the rate checks; the table itself is built by the first call that uses it
+    s->check_input_format_change(sample_rate, channels);  // (a streaming session whose streams carry frames of the filter in force)
     const bool off = sample_rate == s->model_rate && channels == 1;
     s->in_rate = off ? 0 : sample_rate;
     s->in_channels = channels;
@@ -879,6 +880,60 @@ extern "C" int asr_op_resample(const void* audio, const int64_t* offsets, int ba
     HIP_CHECK(hipDeviceSynchronize());
     if (total) HIP_CHECK(hipMemcpy(out, dout, (size_t)total * 4, hipMemcpyDeviceToHost));
     memcpy(offsets_out, rs.offs.data(), (size_t)(batch + 1) * 8);
+  });
+}
+
+extern "C" int asr_op_resample_stream(const void* audio, int audio_dtype, int rate_in, int rate_model, int channels, int int16_scale, int chunk, int n_streams, int n_steps,
+                                      const int32_t* mode, float* out, int32_t* frames_out, int32_t* pitch_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(audio && mode && out && frames_out && pitch_out && chunk >= 1 && n_streams >= 1 && n_steps >= 1, "op_resample_stream: bad argument");
+    ASR_REQUIRE(audio_dtype == ASR_AUDIO_F32 || audio_dtype == ASR_AUDIO_I16 || audio_dtype == ASR_AUDIO_F16, "op_resample_stream: unknown audio dtype %d", audio_dtype);
+    ASR_REQUIRE(channels >= 1 && channels <= 8, "input format: %d channels (1..8)", channels);
+    for (int i = 0; i < n_steps * n_streams; ++i) ASR_REQUIRE(mode[i] >= 0 && mode[i] <= 2, "op_resample_stream: mode %d (0, 1 or 2)", mode[i]);
+    asr_require_device(0);
+    Resampler rs;                                        // (the session path's table and launcher, on the null stream)
+    const Resampler::Table& tb = rs.table(rate_in, rate_model, nullptr);
+    const int pitch = resample_stream_pitch(tb.d, chunk), keep = resample_stream_keep(tb.d);
+    *pitch_out = pitch;
+    Tmp t;                                               // (zeroed: every stream starts reset)
+    const size_t row_bytes = (size_t)pitch * channels * audio_elt_bytes(audio_dtype);
+    int32_t* d_count = (int32_t*)t.alloc((size_t)n_streams * 4);
+    float* d_hist = (float*)t.alloc((size_t)2 * n_streams * keep * 4);
+    unsigned char* d_rows = (unsigned char*)t.alloc(row_bytes * n_streams);
+    float* d_out = (float*)t.alloc((size_t)n_streams * chunk * 4);
+    int32_t* d_sid = (int32_t*)t.alloc((size_t)n_streams * 4);
+    int32_t* d_need = (int32_t*)t.alloc((size_t)n_streams * 4);
+    std::vector<int32_t> sid, need;
+    for (int k = 0; k < n_steps; ++k) {
+      const int32_t* mk = mode + (size_t)k * n_streams;
+      sid.clear();
+      for (int u = 0; u < n_streams; ++u) {
+        frames_out[(size_t)k * n_streams + u] = 0;
+        if (mk[u] == 0) continue;
+        if (mk[u] == 2) {                                // what asr_paraformer_stream_reset does to the stream's count and carried frames
+          HIP_CHECK(hipMemset(d_count + u, 0, 4));
+          for (int half = 0; half < 2 && keep > 0; ++half) HIP_CHECK(hipMemset(d_hist + ((size_t)half * n_streams + u) * keep, 0, (size_t)keep * 4));
+        }
+        HIP_CHECK(hipMemcpy(d_rows + row_bytes * sid.size(), static_cast<const unsigned char*>(audio) + row_bytes * ((size_t)k * n_streams + u), row_bytes,
+                            hipMemcpyHostToDevice));
+        sid.push_back(u);
+      }
+      const int n = (int)sid.size();
+      if (n == 0) continue;
+      HIP_CHECK(hipMemcpy(d_sid, sid.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+      ResampleStreamArgs a;
+      a.audio = d_rows; a.sid = d_sid; a.sid_stride = 1; a.count = d_count; a.hist = d_hist; a.streams = n_streams; a.tab_t = tb.tab_t.as<float>(); a.out = d_out;
+      a.need_out = d_need; a.d = tb.d; a.chunk = chunk; a.pitch = pitch; a.channels = channels;
+      a.scale = audio_dtype == ASR_AUDIO_I16 && int16_scale ? 0x1p-15f : 1.0f; a.audio_dtype = audio_dtype;
+      launch_resample_stream(a, n, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      need.resize(n);
+      HIP_CHECK(hipMemcpy(need.data(), d_need, (size_t)n * 4, hipMemcpyDeviceToHost));
+      for (int i = 0; i < n; ++i) {
+        HIP_CHECK(hipMemcpy(out + ((size_t)k * n_streams + sid[i]) * chunk, d_out + (size_t)i * chunk, (size_t)chunk * 4, hipMemcpyDeviceToHost));
+        frames_out[(size_t)k * n_streams + sid[i]] = need[i];
+      }
+    }
   });
 }
 

@@ -226,6 +226,8 @@ struct asr_session {
   bool taps_enabled = false;
   std::map<std::string, Tap> taps;
   virtual ~asr_session();     // destroys an owned stream; a derived session's members are gone by then
+  // asr_session_set_input_format, behind the rate checks and in front of the change: a session whose state belongs to the format in force throws here
+  virtual void check_input_format_change(int /*sample_rate*/, int /*channels*/) {}
   void save_tap(const char* name, const void* src, int64_t rows, int64_t cols, int64_t ld_src, int elt);
 };
 

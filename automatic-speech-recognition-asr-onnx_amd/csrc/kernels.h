@@ -90,6 +90,41 @@ struct ResampleArgs {
 };
 void launch_resample(const ResampleArgs& a, int n_tiles, hipStream_t s);
 
+// ---- the streaming form (asr_mi355x.h "streaming input format"): step c of a stream (c = 0, 1, .. since its reset) produces outputs
+// [c S, (c + 1) S) of the signal above, S = chunk. hi(c) = floor(((c + 1) S - 1) M / L) + W is the last input frame they read; the step consumes the stream's
+// frames [A(c), A(c + 1)), A(0) = 0, A(c) = hi(c - 1) + 1, and reaches back at most 2 W frames before A(c). Host and device use these definitions.
+__host__ __device__ inline int64_t resample_stream_hi(const ResampleDesign& d, int chunk, int64_t c) { return ((c + 1) * chunk - 1) * d.M / d.L + d.W; }
+__host__ __device__ inline int64_t resample_stream_start(const ResampleDesign& d, int chunk, int64_t c) { return c <= 0 ? 0 : resample_stream_hi(d, chunk, c - 1) + 1; }
+__host__ __device__ inline int resample_stream_need(const ResampleDesign& d, int chunk, int64_t c) {
+  return (int)(resample_stream_hi(d, chunk, c) + 1 - resample_stream_start(d, chunk, c));
+}
+// Frames a stream carries from step to step. A(c) - (floor(c S M / L) - W), the reach of step c's first output, is 2 W when outputs c S - 1 and c S have different
+// centre frames -- always when M >= L -- and 2 W + 1 when they share one, which up-sampling allows (8 kHz with an odd chunk). The pure down-mix carries nothing.
+__host__ __device__ inline int resample_stream_keep(const ResampleDesign& d) { return d.M < d.L ? 2 * d.W + 1 : 2 * d.W; }
+inline int resample_stream_pitch(const ResampleDesign& d, int chunk) {        // frames per row of a step's audio: need(0), or a later step's largest count
+  const int64_t later = (int64_t)chunk * d.M / d.L + 1, first = resample_stream_need(d, chunk, 0);
+  return (int)(first > later ? first : later);
+}
+// Slot i of a launch is stream sid[i * sid_stride]; its geometry comes from count[stream] on the device, so the launch arguments depend on n only. Two launches:
+// the tiles (offline geometry: at most d.tile outputs and d.span_max frames of span per workgroup, the span staged from the stream's carried frames and the
+// slot's row), then one workgroup per slot that writes the last 2 W frames of (carried | row[0, need)) into the OTHER half of hist and advances the count.
+struct ResampleStreamArgs {
+  const void* audio;           // [n][pitch][channels] samples of audio_dtype; slot i reads the first need(c_i) frames of row i
+  const int32_t* sid;          // slot -> stream, at a stride of sid_stride words (the lang field of the step's UttPlan array, or a plain list)
+  int sid_stride;
+  int32_t* count;              // [streams] steps since the stream's reset
+  float* hist;                 // [2][streams][2 W] mono f32 (widened and averaged as the kernel stages them): step c reads half c & 1
+  int streams;
+  const float* tab_t;          // [T][L]
+  float* out;                  // [n][chunk]
+  int32_t* need_out;           // nullable [n]: the frames each slot's step read
+  ResampleDesign d;
+  int chunk, pitch, channels;
+  float scale;
+  int audio_dtype = AUDIO_F32;
+};
+void launch_resample_stream(const ResampleStreamArgs& a, int n, hipStream_t s);
+
 // ---- energy VAD (vad.hip): packed frames of any rate and channel count -> speech segments, per utterance of a ragged batch (the statement: asr_mi355x.h).
 // Stage 1 (one launch, a tile list over (utterance, first analysis frame)): e[f] = sum of x^2 over the H input frames of analysis frame f, its level q[f], and the
 // utterance's 1024-bin level histogram. Stage 2 (one launch, one workgroup per utterance, the mask as bits in LDS): floor / peak / thr, the mask, the three run rules,

@@ -90,6 +90,9 @@ void SvSession::stream_init(int chunk, int look_back_encoder, int look_back_deco
     HIP_CHECK(hipMemcpyAsync(st_dlayer_tab.ptr, tab.data(), sizeof(StreamDecLayer) * ndl, hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
   }
+  st_rs_count.reserve((size_t)max_streams * 4, stream);
+  st_rs_steps.assign(max_streams, 0);
+  st_rs_state.assign(max_streams, 0);
   stream_reset(-1);
 }
 
@@ -143,7 +146,40 @@ void SvSession::stream_reset(int sid) {
     HIP_CHECK(hipMemsetAsync(st_bstate.as<int32_t>() + (size_t)lo * sb_words, 0, (size_t)cnt * sb_words * 4, stream));
     std::fill(sb_len.begin() + lo, sb_len.begin() + lo + cnt, 0);
   }
+  // the streaming input format: step count 0, no carried frames (frames in front of a stream's first are zeros: both halves)
+  HIP_CHECK(hipMemsetAsync(st_rs_count.as<int32_t>() + lo, 0, (size_t)cnt * 4, stream));
+  if (st_rs_hist.ptr && st_rs_rate) {
+    const int keep = resample_stream_keep(resampler.table(st_rs_rate, model_rate, stream).d);
+    for (int half = 0; half < 2 && keep > 0; ++half)
+      HIP_CHECK(hipMemsetAsync(st_rs_hist.as<float>() + ((size_t)half * st_max + lo) * keep, 0, (size_t)cnt * keep * 4, stream));
+  }
+  std::fill(st_rs_steps.begin() + lo, st_rs_steps.begin() + lo + cnt, 0);
+  std::fill(st_rs_state.begin() + lo, st_rs_state.begin() + lo + cnt, 0);
   HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// ---- the streaming input format (asr_mi355x.h) ---------------------------------------------------------------------------------------
+void SvSession::check_input_format_change(int, int) {
+  if (st_max <= 0) return;
+  for (int i = 0; i < st_max; ++i)
+    ASR_REQUIRE(st_rs_state[i] != 2, "input format: stream %d holds audio history (it was stepped with the format in force and not reset since: its carried frames belong to "
+                "that filter); reset it first", i);
+}
+
+void SvSession::stream_input_frames(const int32_t* stream_ids, int n, int32_t* frames_out, int32_t* pitch_out) {
+  ASR_REQUIRE(st_max > 0, "paraformer_stream_input_frames: session was not created with asr_paraformer_stream_create");
+  ASR_REQUIRE((stream_ids && frames_out) || n == 0, "paraformer_stream_input_frames: null argument");
+  ASR_REQUIRE(n >= 0 && pitch_out, "paraformer_stream_input_frames: bad argument (n = %d)", n);
+  ResampleDesign d{};
+  if (in_rate) { HIP_CHECK(hipSetDevice(device)); d = resampler.table(in_rate, model_rate, stream).d; }
+  *pitch_out = in_rate ? resample_stream_pitch(d, st_chunk) : st_chunk;
+  for (int i = 0; i < n; ++i) {
+    const int id = stream_ids[i];
+    ASR_REQUIRE(id >= 0 && id < st_max, "paraformer_stream_input_frames: stream id %d out of range", id);
+    ASR_REQUIRE(!in_rate || st_rs_state[id] != 1, "input format: stream %d was stepped at the default format and not reset since; until the reset of such a stream "
+                "streaming sessions take model-rate mono for it", id);
+    frames_out[i] = in_rate ? resample_stream_need(d, st_chunk, st_rs_steps[id]) : st_chunk;
+  }
 }
 
 // ---- the streaming beam search (the build's own mode) -----------------------------------------------------------------------------
@@ -248,7 +284,6 @@ void SvSession::stream_step(const SvStepReq& q) {
   const bool beam = q.form == SvForm::STREAM_BEAM;      // the timed step, then (behind its validation, below) the candidates and the search
   const bool timed = q.form == SvForm::TIMED || beam;
   ASR_REQUIRE(st_max > 0, "streaming: session was not created with asr_paraformer_stream_create");
-  ASR_REQUIRE(!in_rate, "input format: streaming sessions take model-rate mono");      // (a streaming filter needs per-stream history and a fixed delay: another contract)
   ASR_REQUIRE(!beam || (sb_beam > 0 && q.beam_out.complete()), "streaming: the beam step needs the mode on (asr_paraformer_stream_set_beam) and all of its outputs");
   ASR_REQUIRE(q.audio && stream_ids && q.tok_out && q.num_out && n >= 1 && n <= st_max && max_tokens >= st_B + 1, "streaming: bad argument (n = %d)", n);
   ASR_REQUIRE(!timed || (q.fire_out && q.logprob_out), "streaming: the timed step needs both of its outputs");
@@ -259,6 +294,20 @@ void SvSession::stream_step(const SvStepReq& q) {
   const int d = c.d_model, dff = c.d_ffn, dd = pcfg.d_dec_ffn, H = c.n_heads, n_cur = st_B + st_C;
   const int rows = n * 16, Mpad = round_up(rows, 128), frames = n * st_frames, n_slabs = vpad / 64;
   std::vector<char> seen(st_max, 0);
+  // ---- a non-default input format: the step's rows are frames at in_rate, resampled per stream in front of the fbank launch (inside the captured step: its geometry
+  // is the streams' own step counts on the device). The first formatted step at a rate lays the carried frames out for its filter; no stream holds any then.
+  const bool fmt = in_rate != 0;
+  const Resampler::Table* rs = fmt ? &resampler.table(in_rate, model_rate, stream) : nullptr;
+  const int rs_pitch = fmt ? resample_stream_pitch(rs->d, st_chunk) : 0, rs_keep = fmt ? resample_stream_keep(rs->d) : 0;
+  if (fmt) {
+    ASR_REQUIRE(in_channels >= 1 && in_channels <= 8, "input format: %d channels (1..8)", in_channels);
+    if (st_rs_rate != in_rate) {
+      st_rs_hist.reserve(std::max<size_t>((size_t)2 * st_max * rs_keep * 4, 16), stream);
+      HIP_CHECK(hipMemsetAsync(st_rs_hist.ptr, 0, std::max<size_t>((size_t)2 * st_max * rs_keep * 4, 16), stream));
+      st_rs_rate = in_rate;
+    }
+    st_rs_out.reserve((size_t)n * st_chunk * 4, stream);
+  }
   // ---- plan: one 16-row slot / one fbank workgroup per active stream
   // plan blob: [UttPlan n][blk_utt n][blk_f0 n][row_utt Mpad]
   PlanBlob pb(h_plan, d_plan);
@@ -270,6 +319,8 @@ void SvSession::stream_step(const SvStepReq& q) {
   for (int i = 0; i < n; ++i) {
     ASR_REQUIRE(stream_ids[i] >= 0 && stream_ids[i] < st_max && !seen[stream_ids[i]], "streaming: stream id %d invalid or repeated", stream_ids[i]);
     seen[stream_ids[i]] = 1;
+    ASR_REQUIRE(!fmt || st_rs_state[stream_ids[i]] != 1, "input format: stream %d was stepped at the default format and not reset since; until the reset of such a stream "
+                "streaming sessions take model-rate mono for it", stream_ids[i]);
     UttPlan& p = hp[i];
     p.audio_off = (int64_t)i * st_chunk; p.n_samples = st_chunk; p.n_frames = st_frames; p.frame_off = i * st_frames;
     p.n_lfr = st_B; p.T = n_cur; p.row_off = i * 16; p.lang = stream_ids[i]; p.blk0 = i;
@@ -279,7 +330,11 @@ void SvSession::stream_step(const SvStepReq& q) {
   for (int t = rows; t < Mpad; ++t) row_utt[t] = -1;
   const size_t eT = sizeof(T);
   auto grow = [&](DeviceBuffer& buf, size_t bytes) { buf.reserve(bytes, stream); };
-  const void* d_aud = stage_audio(*this, d_audio, AudioIn{q.audio, q.audio_mem, nullptr, audio_dtype, false}, 0, (int64_t)n * st_chunk);
+  // (one fixed-size copy either way: n chunks, or n rows of rs_pitch frames)
+  const void* d_raw = stage_audio(*this, d_audio, AudioIn{q.audio, q.audio_mem, nullptr, audio_dtype, false}, 0, fmt ? (int64_t)n * rs_pitch * in_channels : (int64_t)n * st_chunk);
+  const void* d_aud = fmt ? st_rs_out.ptr : d_raw;       // what the front end reads
+  const int fe_dtype = fmt ? AUDIO_F32 : audio_dtype;
+  bool resample_now = fmt;                               // (a step that is redone behind a give-up keeps the samples and the advanced counts of its first pass)
   grow(d_mel, (size_t)frames * c.n_mels * 4);
   grow(d_x0, (size_t)Mpad * kpad0 * 4);
   grow(d_xa, (size_t)Mpad * d * 4);
@@ -337,12 +392,21 @@ void SvSession::stream_step(const SvStepReq& q) {
   // Everything below reads its geometry from the uploaded plan and the device-side state (history lengths, fired-token counts), so
   // the launch sequence depends on n only: one captured hipGraph replays every chunk step of a given set size.
   auto enqueue = [&]() {
+  if (resample_now) {
+    ProfScope ps(prof, "resample", stream);
+    ResampleStreamArgs ra;
+    ra.audio = d_raw; ra.sid = &dp[0].lang; ra.sid_stride = (int)(sizeof(UttPlan) / 4); ra.count = st_rs_count.as<int32_t>(); ra.hist = st_rs_hist.as<float>();
+    ra.streams = st_max; ra.tab_t = rs->tab_t.as<float>(); ra.out = st_rs_out.as<float>(); ra.need_out = nullptr; ra.d = rs->d; ra.chunk = st_chunk;
+    ra.pitch = rs_pitch; ra.channels = in_channels; ra.scale = 1.0f; ra.audio_dtype = audio_dtype;      // (int16 as the offline Paraformer session widens it)
+    launch_resample_stream(ra, n, stream);
+    save_tap("resampled", st_rs_out.ptr, n, st_chunk, st_chunk, 4);
+  }
   if (snapshot && step_fused)
     launch_stream_state_copy(st_segs.as<StreamStateSeg>(), st_n_segs, st_n_items, dp, n, false, stream);
   // ---- front-end: fbank of the chunk, LFR rows, carried rows in front (:386-399)
   {
     ProfScope ps(prof, "fbank", stream);
-    const FbankArgs fa = fe.args(d_aud, audio_dtype, dp, d_blk_utt, d_blk_f0, d_mel.as<float>(), nullptr);
+    const FbankArgs fa = fe.args(d_aud, fe_dtype, dp, d_blk_utt, d_blk_f0, d_mel.as<float>(), nullptr);
     launch_fbank(fa, n, stream);
   }
   if (taps_enabled) save_tap("mel", d_mel.ptr, frames, c.n_mels, c.n_mels, 4);
@@ -594,11 +658,18 @@ void SvSession::stream_step(const SvStepReq& q) {
                           (const void*)(uintptr_t)max_tokens, (const void*)st_shadow.ptr, (const void*)d_xblo.ptr, (const void*)d_stb.ptr})
       key.mix(q);
     key.mix((uint64_t)audio_dtype);                                 // the front end is inside the captured step
+    key.mix((uint64_t)in_rate); key.mix((uint64_t)in_channels);     // ... and so is the resampler of a non-default format, with its buffers
+    if (fmt) for (const void* q : {d_raw, (const void*)st_rs_hist.ptr, (const void*)st_rs_count.ptr, (const void*)rs->tab_t.ptr}) key.mix(q);
     key.mix((uint64_t)timed);                                       // the timed step is another launch sequence ...
     if (timed) for (const void* q : {(const void*)d_flp.ptr, (const void*)d_first.ptr, (const void*)d_tlp.ptr}) key.mix(q);     // ... over three more buffers
     const int gi = step_fused ? (snapshot ? 2 : 1) : 0;            // one cached graph per path: a session that alternates (a co-tenant comes and goes) does not re-capture
     (timed ? st_graph_timed : st_graph)[gi].run(stream, use_graph && !taps_enabled && !prof.enabled && !inject_fault, key.h, enqueue);
   }
+  for (int i = 0; i < n; ++i) {                          // what the streams hold from here on, and the counts the device moved
+    st_rs_state[stream_ids[i]] = fmt ? 2 : 1;
+    if (fmt) ++st_rs_steps[stream_ids[i]];
+  }
+  resample_now = false;
   if (taps_enabled) {
     save_tap("logits", d_logits.ptr, rows, c.vocab, vpad, 4);
     if (timed) {
@@ -665,6 +736,13 @@ extern "C" int asr_paraformer_stream_create(const asr_paraformer_config* cfg, co
   });
   if (rc2 != ASR_OK) delete base;
   return rc2;
+}
+
+extern "C" int asr_paraformer_stream_input_frames(asr_session* s, const int32_t* stream_ids, int n_streams, int32_t* frames_out, int32_t* pitch_out) {
+  return asr_guard([&] {
+    ASR_REQUIRE(s && s->kind == 4, "paraformer_stream_input_frames: not a streaming Paraformer session");
+    static_cast<SvSession*>(s)->stream_input_frames(stream_ids, n_streams, frames_out, pitch_out);
+  });
 }
 
 extern "C" int asr_paraformer_stream_reset(asr_session* s, int stream_id) {

@@ -230,6 +230,15 @@ struct ASR_LOCAL SvSession : asr_session {
   void stream_init(int chunk, int look_back_encoder, int look_back_decoder, int max_streams);
   void stream_reset(int sid);
   template <typename T> void stream_step(const SvStepReq& q);
+  // the streaming input format (launch_resample_stream in front of the chunk step). Per stream in HBM: its step count since the reset and the last
+  // 2 W input frames as mono f32, in two halves by step parity. On the host: the same counts (what asr_paraformer_stream_input_frames answers from) and what
+  // each stream holds -- 0 nothing (reset), 1 stepped at the default format (no frames), 2 stepped with a format (frames that belong to its filter).
+  DeviceBuffer st_rs_count, st_rs_hist, st_rs_out;        // [st_max] int32; [2][st_max][2 W] f32; [n][chunk] f32: what the front end of a formatted step reads
+  int st_rs_rate = 0;                                     // the rate st_rs_hist is laid out for (0: not yet)
+  std::vector<int64_t> st_rs_steps;
+  std::vector<char> st_rs_state;
+  void check_input_format_change(int sample_rate, int channels) override;
+  void stream_input_frames(const int32_t* stream_ids, int n, int32_t* frames_out, int32_t* pitch_out);
 };
 
 // f(T{}) with T the operand type of the session's precision: `by_precision(sv, [&](auto t) { sv->run<decltype(t)>(q); })`

@@ -438,6 +438,31 @@ def op_resample(audio, offsets, sample_rate: int, model_rate: int = 16000, chann
     return out[:int(offs_out[-1])], offs_out
 
 
+def op_resample_stream(audio, mode, sample_rate: int, model_rate: int = 16000, channels: int = 1, int16_scale: bool = False, chunk: int = 960):
+    """The streaming input format's launches on host arrays (asr_op_resample_stream): audio [n_steps, n_streams, pitch, channels] (or [.., pitch] at one channel)
+    float32 / int16 / float16 frames at sample_rate, pitch = input_format.stream_pitch(chunk, sample_rate, model_rate); mode [n_steps, n_streams]: 0 = the stream
+    is not in the step, 1 = stepped, 2 = reset, then stepped; every stream starts reset. -> (out [n_steps, n_streams, chunk] float32, rows of streams not in a step
+    zero; frames [n_steps, n_streams] the frames each step read, 0 where not in it; pitch)."""
+    from .input_format import stream_pitch
+    audio = np.ascontiguousarray(audio)
+    code = _AUDIO_CODES[audio_np_dtype(audio.dtype)]
+    mode = np.ascontiguousarray(mode, dtype=np.int32)
+    if mode.ndim != 2 or mode.size == 0:
+        raise ValueError("op_resample_stream: mode is [n_steps, n_streams]")
+    L, M, W = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.check(_lib.load().asr_resample_table(int(sample_rate), int(model_rate), C.byref(L), C.byref(M), C.byref(W), None))      # (refuses bad rates)
+    pitch = stream_pitch(chunk, sample_rate, model_rate)
+    if audio.size != mode.size * pitch * int(channels):
+        raise ValueError(f"op_resample_stream: audio holds {audio.size} samples, {mode.shape[0]} steps x {mode.shape[1]} streams x pitch {pitch} x {channels} channels "
+                         f"is {mode.size * pitch * int(channels)}")
+    out = np.zeros(mode.shape + (int(chunk),), dtype=np.float32)
+    frames, pitch_c = np.zeros(mode.shape, dtype=np.int32), C.c_int32(0)
+    _lib.check(_lib.load().asr_op_resample_stream(audio.ctypes.data_as(C.c_void_p), code, int(sample_rate), int(model_rate), int(channels), int(bool(int16_scale)),
+                                                  int(chunk), mode.shape[1], mode.shape[0], _ip(mode), _fp(out), _ip(frames), C.byref(pitch_c)))
+    assert pitch_c.value == pitch, (pitch_c.value, pitch)
+    return out, frames, pitch
+
+
 VAD_LEVEL_DB = 10.0 * np.log10(2.0) / 8.0         # one level step in dB of power: 8 steps per octave
 VAD_MAX_F = 1 << 20
 
@@ -1258,14 +1283,33 @@ class ParaformerStreamSession(_Session):
             if getattr(self, "_beam", None):
                 self._fire_rows[s] = []
 
+    def input_frames(self, stream_ids):
+        """(frames, pitch) of the listed streams' next step (asr_paraformer_stream_input_frames): frames[i] = the input frames the step reads from row i of its
+        audio, pitch = the row pitch in frames. The default format gives (chunk, chunk). With a format set, step c of a stream reads
+        input_format.stream_frames(chunk, rate, model_rate, c) frames: W more at its first step than later (the filter's look-ahead)."""
+        sid = np.ascontiguousarray(stream_ids, dtype=np.int32)
+        frames, pitch = np.zeros(sid.size, dtype=np.int32), C.c_int32(0)
+        _lib.check(_lib.load().asr_paraformer_stream_input_frames(self._h, _ip(sid), sid.size, _ip(frames), C.byref(pitch)))
+        return frames, int(pitch.value)
+
+    def _step_rows(self, chunks, sid):
+        """The host rows of a step: (n, chunk) at the default format, else (n, pitch * channels) from (n, pitch, channels) or (n, pitch) arrays."""
+        rate, ch = self._format or (int(self.cfg.sample_rate), 1)
+        if (rate, ch) == (int(self.cfg.sample_rate), 1):
+            return self._audio(chunks).reshape(sid.size, self.chunk)
+        _, pitch = self.input_frames(sid)
+        return self._audio(chunks).reshape(sid.size, pitch * ch)
+
     def step(self, chunks, stream_ids, audio_device_ptr: int | None = None):
         """chunks: (n, chunk) int16-range samples of the session's audio_dtype (or None with `audio_device_ptr`: HBM-resident [n][chunk]); stream_ids: n
-        distinct ids -> list of n int32 arrays (tokens fired by this chunk)."""
+        distinct ids -> list of n int32 arrays (tokens fired by this chunk). With an input format set (set_input_format) chunks is (n, pitch, channels) -- or
+        (n, pitch) -- frames at the format's rate, row i filled with the input_frames(stream_ids)[0][i] frames stream i's step reads (the rest of a row is
+        ignored), and the library resamples each stream on the device with its own carried frames; step_timed and step_beam take the same rows."""
         sid = np.ascontiguousarray(stream_ids, dtype=np.int32)
         if audio_device_ptr is not None:
             ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
         else:
-            a = self._audio(chunks).reshape(sid.size, self.chunk)
+            a = self._step_rows(chunks, sid)
             ap, mem = a.ctypes.data_as(C.c_void_p), MEM_HOST
         cap = self.rows_per_chunk + 1
         tok = np.zeros((sid.size, cap), dtype=np.int32)
@@ -1285,7 +1329,7 @@ class ParaformerStreamSession(_Session):
         if audio_device_ptr is not None:
             ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
         else:
-            a = self._audio(chunks).reshape(sid.size, self.chunk)
+            a = self._step_rows(chunks, sid)
             ap, mem = a.ctypes.data_as(C.c_void_p), MEM_HOST
         cap = self.rows_per_chunk + 1
         tok = np.zeros((sid.size, cap), dtype=np.int32)
@@ -1347,7 +1391,7 @@ class ParaformerStreamSession(_Session):
         if audio_device_ptr is not None:
             ap, mem = C.c_void_p(audio_device_ptr), MEM_DEVICE
         else:
-            a = self._audio(chunks).reshape(sid.size, self.chunk)
+            a = self._step_rows(chunks, sid)
             ap, mem = a.ctypes.data_as(C.c_void_p), MEM_HOST
         cap = self.rows_per_chunk + 1
         tok = np.zeros((sid.size, cap), dtype=np.int32)

@@ -34,6 +34,38 @@ def input_frames(samples: int, sample_rate: int, model_rate: int, what: str = "w
     return int(samples) * M // L
 
 
+def half_width(sample_rate: int, model_rate: int) -> int:
+    """W of the resampler's filter (asr_resample_table): ceil(32 / fc) input frames, fc = 0.945 min(1, L / M); 0 at equal rates (the pure down-mix)."""
+    L, M = ratio(sample_rate, model_rate)
+    if L == M:
+        return 0
+    return math.ceil(32.0 / (0.945 * min(1.0, L / M)))
+
+
+def _stream_hi(chunk: int, L: int, M: int, W: int, step: int) -> int:
+    return ((int(step) + 1) * int(chunk) - 1) * M // L + W
+
+
+def stream_start(chunk: int, sample_rate: int, model_rate: int, step: int) -> int:
+    """A(step): the first input frame the stream's step `step` (0, 1, .. since its reset) consumes. A(0) = 0, A(c) = hi(c - 1) + 1 with
+    hi(c) = floor(((c + 1) chunk - 1) M / L) + W, the last frame the step's outputs [c chunk, (c + 1) chunk) read."""
+    L, M = ratio(sample_rate, model_rate)
+    return 0 if step <= 0 else _stream_hi(chunk, L, M, half_width(sample_rate, model_rate), step - 1) + 1
+
+
+def stream_frames(chunk: int, sample_rate: int, model_rate: int, step: int) -> int:
+    """need(step) = hi(step) + 1 - A(step): the frames a streaming session with this format reads from a stream's row at that step. The first step takes W
+    frames more than the later ones (the look-ahead)."""
+    L, M = ratio(sample_rate, model_rate)
+    return _stream_hi(chunk, L, M, half_width(sample_rate, model_rate), step) + 1 - stream_start(chunk, sample_rate, model_rate, step)
+
+
+def stream_pitch(chunk: int, sample_rate: int, model_rate: int) -> int:
+    """Frames per row of a formatted step's audio: max(need(0), floor(chunk M / L) + 1), at least every step's need."""
+    L, M = ratio(sample_rate, model_rate)
+    return max(stream_frames(chunk, sample_rate, model_rate, 0), int(chunk) * M // L + 1)
+
+
 def as_frames(audio_int16, channels: int) -> np.ndarray:
     """int16 frames [n, channels] of a clip given as [n, channels] or flat interleaved."""
     a = np.asarray(audio_int16, dtype=np.int16)

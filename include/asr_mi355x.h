@@ -252,7 +252,9 @@ int asr_paraformer_set_lm(asr_session* s, const int32_t* image_words, int64_t n_
 int asr_paraformer_stream_create(const asr_paraformer_config* cfg, const void* arena, size_t arena_bytes, int arena_mem, int device_id,
                                  int precision, int chunk_samples, int look_back_encoder, int look_back_decoder, int max_streams,
                                  asr_session** out);
-int asr_paraformer_stream_reset(asr_session* s, int stream_id);      /* -1 = every stream: empty histories, zero CIF state */
+int asr_paraformer_stream_reset(asr_session* s, int stream_id);      /* -1 = every stream: empty histories, zero CIF state, no carried input frames, step count 0 */
+/* Per listed stream the frames its next step reads; *pitch_out: the row pitch in frames. Default format: chunk_samples and chunk_samples. */
+int asr_paraformer_stream_input_frames(asr_session* s, const int32_t* stream_ids, int n_streams, int32_t* frames_out, int32_t* pitch_out);
 int asr_paraformer_stream_step(asr_session* s, const void* audio, int audio_mem, const int32_t* stream_ids, int n_streams,
                                int32_t* token_ids_out, int max_tokens, int32_t* num_id_out);
 /* The same step with the integration step at which each token fired and the token's log-probability (the build's own mode, as asr_paraformer_run_timed).
@@ -583,7 +585,22 @@ int asr_session_audio_dtype(asr_session* s, int* audio_dtype_out);
  * utterance of n frames becomes ceil(n * rate_model / sample_rate) samples, and frame counts, length limits (max_audio_len) and result frames all refer to those.
  * This is the build's own mode (the reference resamples on the host with audioop, no low-pass): sample parity with the reference holds for the default format only.
  * May be set between any two compute calls. INVALID (the format in force stays) for a null session, a rate < 1, channels outside 1..8, rates whose reduced ratio
- * needs more than 1024 filter phases (16001 Hz), or a rate beyond ~40 x the model's. The streaming step refuses a non-default format: it takes model-rate mono. */
+ * needs more than 1024 filter phases (16001 Hz), or a rate beyond ~40 x the model's.
+ *
+ * The streaming input format (asr_paraformer_stream_create sessions, chunk_samples = S; filter (L, M, W, T = 2 W + 1) of asr_resample_table). The model-rate
+ * signal of a stream is the one the offline resampler defines: output n reads the stream's input frames floor(n M / L) - W .. + W against phase (n M) mod L,
+ * frames before the stream's first are zeros, widening and the channel mean are the offline kernel's. The stream's c-th step since its reset (c = 0, 1, ..)
+ * produces outputs [c S, (c + 1) S) and feeds them to the unchanged chunk step. With hi(c) = floor(((c + 1) S - 1) M / L) + W, A(0) = 0 and A(c) = hi(c - 1) + 1,
+ * step c consumes the stream's frames [A(c), A(c + 1)): need(c) = hi(c) + 1 - A(c) of them. The first step takes W frames more than the later ones (the
+ * look-ahead: 2.1 ms at 48 kHz, 4.25 ms at 8 kHz; S = 8000: 24100 then 24000 at 48 kHz, 22142 then 22050 at 44.1 kHz, 5546 then 5512 or 5513 at 11.025 kHz, 4034
+ * then 4000 at 8 kHz). A step reaches back at most 2 W frames before A(c); the session keeps them per stream in HBM as mono f32. The `audio` of the three step
+ * entries is then [n_streams][pitch][channels] samples of the session's audio dtype, host or device memory, pitch = max(need(0), floor(S M / L) + 1); the library
+ * reads the first need(c_i) frames of row i, c_i that stream's own step count, and ignores the rest of the row (asr_paraformer_stream_input_frames reports both).
+ * The end of a stream is the caller's to pad: to A(C) frames for a whole number C of chunks. For any input x of A(C) frames the C S samples the steps produce
+ * equal asr_op_resample(x)[: C S] bit for bit, however the streams' steps interleave. int16 audio is widened with the offline Paraformer session's scale (1).
+ * A stream's state belongs to one format from reset to reset: a streaming session refuses asr_session_set_input_format (INVALID, the format in force stays)
+ * while a stream holds audio history -- it was stepped with a non-default format in force and not reset since (the carried frames belong to that filter) -- and a
+ * formatted step refuses (INVALID) a stream that was stepped at the default format and not reset since: until its reset such a stream takes model-rate mono. */
 int asr_session_set_input_format(asr_session* s, int sample_rate, int channels);
 int asr_session_input_format(asr_session* s, int* sample_rate_out, int* channels_out);
 
@@ -598,7 +615,7 @@ int asr_session_profile_read(asr_session* s, int cap, char* names, double* total
  * names: "mel" "enc_in" "block0" "enc_out" "logits" "frame_ids"(i32); timed Paraformer runs add "fire_frames"(i32) "token_logprob" ([utterances][max_tokens]);
  * offline Paraformer runs add "alphas" and, on the packed token rows like "logits" (rows at or past the device-side count hold nothing defined),
  * "acoustic" (the CIF output) and "dec0" .. (the rows behind each decoder layer, full layers first, then the decoders3 ones); every family with a
- * non-default input format adds "resampled" ([1][samples]: the packed model-rate mono samples the front end read) */
+ * non-default input format adds "resampled" ([1][samples]: the packed model-rate mono samples the front end read; a streaming step: [n_streams][chunk_samples]) */
 int asr_session_taps_enable(asr_session* s, int enable);
 int asr_session_tap_shape(asr_session* s, const char* name, int64_t* rows, int64_t* cols);
 int asr_session_tap_read(asr_session* s, const char* name, void* host_out, size_t bytes);
@@ -686,6 +703,11 @@ int asr_op_cif_scan_timed(const float* alpha, const float* enc, int d, const int
  * utterance b has ceil(n_b * rate_model / rate_in) samples. int16_scale != 0: int16 samples are scaled by 2^-15, as in front of the Whisper / Qwen front end. */
 int asr_op_resample(const void* audio, const int64_t* offsets, int batch, int audio_dtype, int rate_in, int rate_model, int channels, int int16_scale,
                     float* out, int64_t out_cap, int64_t* offsets_out);
+/* The streaming input format's launches on host arrays (every stream starts reset): n_steps steps over n_streams streams. audio [n_steps][n_streams][pitch][channels];
+ * mode [n_steps][n_streams]: 0 = not in this step, 1 = stepped, 2 = reset, then stepped.
+ * out [n_steps][n_streams][chunk] f32 (rows of streams not in a step untouched); frames_out [n_steps][n_streams]: frames the step read (0 if not in it). */
+int asr_op_resample_stream(const void* audio, int audio_dtype, int rate_in, int rate_model, int channels, int int16_scale, int chunk, int n_streams, int n_steps,
+                           const int32_t* mode, float* out, int32_t* frames_out, int32_t* pitch_out);
 /* The filter the library uses for rate_in -> rate_model: with g their greatest common divisor L = rate_model / g phases, M = rate_in / g, half width W input
  * frames, T = 2 W + 1 taps per phase; output n reads input frames floor(n M / L) - W .. + W against row (n M) mod L. coeffs: null, or [L][T] f32 (computed in
  * double, rounded once). Equal rates give L = M = 1, W = 0 and the single coefficient 1. INVALID as asr_session_set_input_format refuses rates. */
